@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- fp64 tiled Cholesky TFlop/s on N MI355X (BASELINE.json metric).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 A step is ONE factorization of the synthetic SPD matrix (set_random_hermitian_positive_definite,
@@ -55,7 +55,13 @@ def parse():
     p.add_argument("--transport", default="rccl", choices=["rccl", "host", "peer"],
                    help="host = gloo-staged broadcasts: lets several ranks rehearse the N > 1 path on ONE GPU; "
                         "peer = device-to-device copies out of hipIpc-mapped staging buffers, control messages over gloo")
-    return p.parse_args()
+    p.add_argument("--dump-outputs", metavar="DIR",
+                   help="after the timed steps, write what the last one computed (a fixed sample of the factor, info) "
+                        "as DIR/<name>.npy")
+    args = p.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        p.error("--steps must be >= 1 and --warmup >= 0")
+    return args
 
 
 def cpu_baseline(args):
@@ -148,6 +154,68 @@ def eigensolver_line(dlaf, grid, n, nb, runs=2):
             "wall_s_host_arrays_incl_pcie": round(wall, 3), "runs": runs,
             "sampled_check": {"columns": int(len(cols)), "max|A z - w z|": res, "bar_2_n_err_wmax": 2 * n * err * float(np.abs(w).max()),
                               "max|Z^T Z - I|": orth, "bar_10_n_err": 10 * n * err, "sorted": bool(np.all(np.diff(w) >= 0))}}
+
+
+DUMP_LIMIT_BYTES = 64 * 10**6
+DUMP_SEED = 20480
+DUMP_MAX_TILES = 4096   # bounds the device-to-host copies at small block sizes
+DUMP_PER_TILE = 1024
+
+
+def dump_outputs(dirname, w, info, rank, world, dist):
+    """--dump-outputs: what the timed path hands its caller, the factored matrix and info, as .npy files in float32 /
+    float64 (a complex array gets a trailing axis of 2: real, imaginary).  The factor of the metric's workload is
+    32 GiB, so it is sampled, the same way on every run with the same arguments:
+      factor_tile_<i>_<j>.npy  the first and the last diagonal tile, whole, while they take at most half of
+                               DUMP_LIMIT_BYTES;
+      factor_sample.npy        the same DUMP_PER_TILE seeded positions of every tile of the stored triangle (a seeded
+                               subset of DUMP_MAX_TILES tiles when there are more), tiles in column-major order --
+                               fewer positions per tile when the files would pass DUMP_LIMIT_BYTES;
+      info.npy                 the info of the last timed step.
+    Every rank fetches the tiles it owns; rank 0 writes."""
+    n, nb, uplo, item = w.n, w.nb, w.uplo, w.dtype.itemsize
+    nt = -(-n // nb)
+    rng = np.random.default_rng(DUMP_SEED)
+    tiles = [(i, j) for j in range(nt) for i in range(nt) if (i >= j if uplo == "L" else i <= j)]
+    if len(tiles) > DUMP_MAX_TILES:
+        tiles = [tiles[k] for k in np.sort(rng.choice(len(tiles), DUMP_MAX_TILES, replace=False))]
+    whole, whole_bytes = [], 0
+    for i, j in sorted({(0, 0), (nt - 1, nt - 1)}):
+        size = min(nb, n - i * nb) * min(nb, n - j * nb) * item
+        if whole_bytes + size <= DUMP_LIMIT_BYTES // 2:
+            whole.append((i, j))
+            whole_bytes += size
+    budget = DUMP_LIMIT_BYTES - 4096 - whole_bytes  # 4096: room for the .npy headers
+    per_tile = max(1, min(nb * nb, DUMP_PER_TILE, budget // (len(tiles) * item)))
+    pos = rng.choice(nb * nb, per_tile, replace=False)  # column-major offsets within a full tile
+    sample, full = {}, {}
+    for i, j in sorted(set(tiles) | set(whole)):
+        t = w.fetch_tile(i, j)
+        if t is None:  # another rank's tile
+            continue
+        if (i, j) in whole:
+            full[(i, j)] = t
+        if (i, j) in tiles:
+            p = pos[(pos % nb < t.shape[0]) & (pos // nb < t.shape[1])]  # an edge tile keeps the positions it has
+            sample[(i, j)] = t[p % nb, p // nb]
+    if world > 1:
+        parts = [None] * world
+        dist.all_gather_object(parts, (sample, full))
+        for part_sample, part_full in parts:
+            sample.update(part_sample)
+            full.update(part_full)
+    if rank != 0:
+        return
+
+    def real(a):
+        a = np.ascontiguousarray(a)
+        return a.view(a.real.dtype).reshape(a.shape + (2,)) if np.iscomplexobj(a) else a
+
+    os.makedirs(dirname, exist_ok=True)
+    for i, j in whole:
+        np.save(os.path.join(dirname, f"factor_tile_{i}_{j}.npy"), real(full[(i, j)]))
+    np.save(os.path.join(dirname, "factor_sample.npy"), real(np.concatenate([sample[t] for t in tiles])))
+    np.save(os.path.join(dirname, "info.npy"), np.array([info], dtype=np.float64))
 
 
 def host_grid(dlaf, dist, torch, nprow, npcol):
@@ -271,6 +339,9 @@ def main():
         tt = torch.tensor([elapsed], dtype=torch.float64, device="cuda" if args.transport == "rccl" else "cpu")
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         elapsed = float(tt.item())
+    if args.dump_outputs:
+        # the last timed step's factor, read before the untimed extras below run on the device
+        dump_outputs(args.dump_outputs, pool[(args.steps - 1) % npool], info, rank, world, dist)
 
     flops = (4.0 if args.type in "cz" else 1.0) * n ** 3 / 3.0
     sec_per_step = elapsed / args.steps

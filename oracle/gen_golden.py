@@ -1,8 +1,9 @@
 #!/usr/bin/env python3
 """gen_golden.py -- TEST INFRASTRUCTURE ONLY: regenerates tests/golden/*.json.
 
-Run in the build container (needs g++ for the <random> probe and scipy for LAPACK):
-    python oracle/gen_golden.py
+Run where the reference is present (needs g++ for the <random> probe and the `ref` shim, scipy for LAPACK):
+    python oracle/gen_golden.py                        # every fixture
+    python oracle/gen_golden.py distribution_sweep     # only the named ones
 
 Fixtures written (all DATA: inputs + expected outputs, no reference source text):
   rng_stream.json        libstdc++ mt19937_64 + uniform_real_distribution(-1,1) streams for a few
@@ -14,7 +15,11 @@ Fixtures written (all DATA: inputs + expected outputs, no reference source text)
                          n=34 nb=13, s/d/c/z, L and U: an independent numeric answer for the same
                          input the HIP path and the oracle are fed.
   hpd_34_13.json         the first column and the diagonal of that input (pins the generator itself).
+  distribution_sweep.json the answers of the reference's own util_distribution.h (compiled by
+                         `make -C oracle ref`, oracle/ref_distribution_shim.cpp) over the exhaustive sweep
+                         of tests/test_oracle.py::test_distribution_against_reference_header (numbers only).
 """
+import ctypes as C
 import json
 import os
 import subprocess
@@ -90,20 +95,69 @@ def potrf_lapack():
     return out, hpd
 
 
-def main():
+# The sweep of tests/test_oracle.py::test_distribution_against_reference_header; every list below is flattened
+# in the loop order of distribution_sweep().
+SWEEP_GRID_SIZES = (1, 2, 3, 5)
+SWEEP_TILES_PER_BLOCK = (1, 2, 4)
+SWEEP_GLOBAL_TILES = 41
+SWEEP_TILE_SIZES = (1, 7, 10)
+SWEEP_ELEMENTS = 50
+
+
+def distribution_sweep():
+    subprocess.check_call(["make", "-C", HERE, "ref"], stdout=subprocess.DEVNULL)
+    R = C.CDLL(os.path.join(HERE, "_ref", "libref_distribution.so"))
+    for f in ("ref_local_tile_from_global_tile", "ref_next_local_tile_from_global_tile",
+              "ref_global_tile_from_local_tile", "ref_tile_from_element", "ref_tile_element_from_element"):
+        getattr(R, f).restype = C.c_long
+    lg = C.c_long
+    rank_tile, local_tile, local_tile_next, global_tile = [], [], [], []
+    for gs in SWEEP_GRID_SIZES:
+        for tpb in SWEEP_TILES_PER_BLOCK:
+            for src in range(gs):
+                for toff in range(tpb):
+                    for rank in range(gs):
+                        for gt in range(SWEEP_GLOBAL_TILES):
+                            rank_tile.append(R.ref_rank_global_tile(lg(gt), lg(tpb), gs, src, lg(toff)))
+                            b = (lg(gt), lg(tpb), gs, rank, src, lg(toff))
+                            lt = R.ref_local_tile_from_global_tile(*b)
+                            local_tile.append(lt)
+                            local_tile_next.append(R.ref_next_local_tile_from_global_tile(*b))
+                            # null where the tile is not local (the reference's precondition excludes lt < 0)
+                            global_tile.append(R.ref_global_tile_from_local_tile(lg(lt), lg(tpb), gs, rank, src, lg(toff))
+                                               if lt >= 0 else None)
+    tile, tile_element = [], []
+    for ts in SWEEP_TILE_SIZES:
+        for off in range(ts):
+            for e in range(SWEEP_ELEMENTS):
+                tile.append(R.ref_tile_from_element(lg(e), lg(ts), lg(off)))
+                tile_element.append(R.ref_tile_element_from_element(lg(e), lg(ts), lg(off)))
+    return {"source": "include/dlaf/matrix/util_distribution.h via oracle/ref_distribution_shim.cpp",
+            "grid_sizes": SWEEP_GRID_SIZES, "tiles_per_block": SWEEP_TILES_PER_BLOCK,
+            "global_tiles": SWEEP_GLOBAL_TILES, "tile_sizes": SWEEP_TILE_SIZES, "elements": SWEEP_ELEMENTS,
+            "rank_global_tile": rank_tile, "local_tile_from_global_tile": local_tile,
+            "next_local_tile_from_global_tile": local_tile_next, "global_tile_from_local_tile": global_tile,
+            "tile_from_element": tile, "tile_element_from_element": tile_element}
+
+
+def main(only=()):
     os.makedirs(GOLD, exist_ok=True)
-    with open(os.path.join(GOLD, "rng_stream.json"), "w") as f:
-        json.dump(rng_stream(), f, indent=0)
-    with open(os.path.join(GOLD, "distribution_rows.json"), "w") as f:
-        json.dump({"columns": DIST_COLS, "rows": DIST_ROWS,
-                   "source": "test/unit/matrix/test_util_distribution.cpp:45-62"}, f)
-    lap, hpd = potrf_lapack()
-    with open(os.path.join(GOLD, "potrf_lapack.json"), "w") as f:
-        json.dump({"n": 34, "nb": 13, "factors": lap}, f)
-    with open(os.path.join(GOLD, "hpd_34_13.json"), "w") as f:
-        json.dump({"n": 34, "nb": 13, "samples": hpd}, f)
+
+    def write(name, obj, **kw):
+        if not only or name in only:
+            with open(os.path.join(GOLD, name + ".json"), "w") as f:
+                json.dump(obj() if callable(obj) else obj, f, **kw)
+
+    write("rng_stream", rng_stream, indent=0)
+    write("distribution_rows", {"columns": DIST_COLS, "rows": DIST_ROWS,
+                                "source": "test/unit/matrix/test_util_distribution.cpp:45-62"})
+    if not only or "potrf_lapack" in only or "hpd_34_13" in only:
+        lap, hpd = potrf_lapack()
+        write("potrf_lapack", {"n": 34, "nb": 13, "factors": lap})
+        write("hpd_34_13", {"n": 34, "nb": 13, "samples": hpd})
+    write("distribution_sweep", distribution_sweep)
     print("golden fixtures written to", GOLD)
 
 
 if __name__ == "__main__":
-    main()
+    main(tuple(sys.argv[1:]))

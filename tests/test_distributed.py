@@ -11,6 +11,7 @@ import socket
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -146,17 +147,19 @@ def test_rccl_communicators_on_a_one_process_grid():
 
 @pytest.mark.gpu
 @pytest.mark.parametrize("transport", ["host", "peer"])
-def test_bench_line_on_a_four_rank_grid_with_the_host_transport(transport):
+def test_bench_line_on_a_four_rank_grid_with_the_host_transport(transport, tmp_path, oracle):
     """bench.py --gpus 4 as the driver launches it (torch.distributed.run, one rank per process), with the
     host-staged (or the peer-copy) transport so that the four ranks can share this box's one GPU: exercises the
-    N > 1 JSON line (grid, transport, MAX-reduced time, device-side residual over the grid)."""
+    N > 1 JSON line (grid, transport, MAX-reduced time, device-side residual over the grid) and the outputs
+    gathered from the four ranks by --dump-outputs."""
     import json
     from conftest import gpu_process_budget
     gpu_process_budget(4)
     env = dict(os.environ, OMP_NUM_THREADS="1", DLAF_MI355X_DEVICE="0")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "4", "--master-addr", "127.0.0.1",
            "--master-port", str(free_port()), os.path.join(ROOT, "bench.py"), "--gpus", "4", "--steps", "2", "--warmup", "1",
-           "--matrix-size", "4096", "--block-size", "256", "--transport", transport, "--check", "--no-cpu-baseline"]
+           "--matrix-size", "4096", "--block-size", "256", "--transport", transport, "--check", "--no-cpu-baseline",
+           "--dump-outputs", str(tmp_path)]
     r = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, (r.stdout[-1500:], r.stderr[-3000:])
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{") and '"metric"' in ln]
@@ -166,3 +169,9 @@ def test_bench_line_on_a_four_rank_grid_with_the_host_transport(transport):
     assert line["steps"] == 2 and line["value"] > 0 and line["unit"] == "TFlop/s"
     assert line["residual"]["ok"], line["residual"]
     assert "roofline" in line and "cpu_baseline" not in line   # the CPU baseline is an N = 1 item
+    out = {f: np.load(tmp_path / f) for f in os.listdir(tmp_path)}
+    assert sorted(out) == ["factor_sample.npy", "factor_tile_0_0.npy", "factor_tile_15_15.npy", "info.npy"]
+    assert out["info.npy"].tolist() == [0.0] and out["factor_sample.npy"].shape == (136 * 1024,)
+    l00 = np.tril(out["factor_tile_0_0.npy"])
+    a00 = oracle.random_hpd_tile(4096, 256, 0, 0, np.float64)
+    assert np.abs(l00 @ l00.T - a00).max() <= 256 * np.finfo(np.float64).eps * np.abs(a00).max()

@@ -241,3 +241,62 @@ def test_bench_refuses_to_run_without_a_gpu():
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "1"], cwd=ROOT, capture_output=True,
                        text=True, timeout=300)
     assert r.returncode != 0 and "needs a GPU" in (r.stderr + r.stdout) and '"metric"' not in r.stdout
+
+
+class _FactorTiles:
+    """Stands in for bench.py's DeviceMatrix in dump_outputs: tile (i, j) holds i * 1000 + j (+ 1j), and with
+    `world` > 1 this rank owns the tiles with (i + j) % world == rank."""
+
+    def __init__(self, n, nb, dtype, uplo, rank=0, world=1):
+        self.n, self.nb, self.dtype, self.uplo, self.rank, self.world = n, nb, np.dtype(dtype), uplo, rank, world
+
+    def fetch_tile(self, i, j):
+        if (i + j) % self.world != self.rank:
+            return None
+        t = np.full((min(self.nb, self.n - i * self.nb), min(self.nb, self.n - j * self.nb)), i * 1000 + j,
+                    dtype=self.dtype, order="F")
+        return t + 1j if np.iscomplexobj(t) else t
+
+
+class _Gather:
+    """torch.distributed stand-in for all_gather_object on rank 0 of `others` + 1 ranks: the other ranks' objects were
+    recorded beforehand (by a _Gather without others, which records what it is given)."""
+
+    def __init__(self, others=()):
+        self.others, self.seen = list(others), []
+
+    def all_gather_object(self, parts, obj):
+        self.seen.append(obj)
+        parts[:] = [obj] + (self.others or [obj] * (len(parts) - 1))
+
+
+@pytest.mark.parametrize("n,nb,t,uplo", [(65536, 1024, "d", "L"), (1000, 300, "z", "U"), (4096, 32, "s", "L"),
+                                         (8192, 4096, "d", "L"), (100, 128, "c", "L")])
+def test_bench_dump_outputs_sample(tmp_path, n, nb, t, uplo):
+    """bench.py --dump-outputs: float32 / float64 files only, at most 64 MB, the same files run after run, and on
+    two ranks the same files as on one."""
+    import bench
+    dtype = {"s": np.float32, "d": np.float64, "c": np.complex64, "z": np.complex128}[t]
+
+    def dump(d, rank=0, world=1, dist=None):
+        bench.dump_outputs(str(d), _FactorTiles(n, nb, dtype, uplo, rank, world), 0, rank, world, dist)
+        return {f: np.load(os.path.join(d, f)) for f in sorted(os.listdir(d))} if rank == 0 else None
+
+    one = dump(tmp_path / "one")
+    nt = -(-n // nb)
+    assert "factor_sample.npy" in one and one["info.npy"].tolist() == [0.0]
+    assert sum(os.path.getsize(tmp_path / "one" / f) for f in one) <= 64 * 10**6
+    real = np.float32 if t in "sc" else np.float64
+    assert {f: a.dtype for f, a in one.items() if f != "info.npy"} == dict.fromkeys(set(one) - {"info.npy"}, np.dtype(real))
+    if nb <= 1024:  # whole diagonal tiles fit the budget
+        assert "factor_tile_0_0.npy" in one and f"factor_tile_{nt - 1}_{nt - 1}.npy" in one
+        last = one[f"factor_tile_{nt - 1}_{nt - 1}.npy"]
+        assert last.shape[:2] == (n - (nt - 1) * nb,) * 2 and (last[..., 0] if t in "cz" else last).max() == (nt - 1) * 1001
+    again = dump(tmp_path / "again")
+    assert again.keys() == one.keys() and all(np.array_equal(one[f], again[f]) for f in one)
+    # two ranks: rank 1 runs first and hands its part to rank 0's gather
+    rank1 = _Gather()
+    dump(tmp_path / "rank1", 1, 2, rank1)
+    assert not (tmp_path / "rank1").exists()   # rank 0 writes
+    two = dump(tmp_path / "two", 0, 2, _Gather(rank1.seen))
+    assert two.keys() == one.keys() and all(np.array_equal(one[f], two[f]) for f in one)

@@ -7,7 +7,6 @@ Mirrors, with the reference's tolerances:
   test/unit/test_blas_tile/test_{trsm,herk,gemm}.h       tile BLAS closed forms
   test/unit/factorization/test_cholesky.cpp:54-120       local + distributed factorization
 """
-import ctypes as C
 import itertools
 import json
 import os
@@ -50,45 +49,45 @@ def test_distribution_golden_rows(oracle, golden_dir):
                                                      p["src_rank"], p["tile_offset"]) == p["global_tile"]
 
 
-def test_distribution_against_reference_header(oracle):
-    """oracle/_ref/libref_distribution.so = the reference's own util_distribution.h compiled
-    where it lies (oracle/Makefile `ref`); exhaustive sweep of the restatement against it."""
-    path = os.path.join(os.path.dirname(oracle.__file__), "_ref", "libref_distribution.so")
-    if not os.path.exists(path):
-        pytest.skip("oracle/_ref not built (reference not present at build time)")
-    R = C.CDLL(path)
+def test_distribution_against_reference_header(oracle, golden_dir):
+    """The answers of the reference's own util_distribution.h over an exhaustive sweep, stored by
+    oracle/gen_golden.py (tests/golden/distribution_sweep.json, produced through oracle/_ref = that header
+    compiled where it lies, oracle/Makefile `ref`); the restatement must give every one of them."""
+    g = json.load(open(os.path.join(golden_dir, "distribution_sweep.json")))
     L = oracle.lib()
-    for f in ("ref_local_tile_from_global_tile", "ref_next_local_tile_from_global_tile",
-              "ref_global_tile_from_local_tile", "ref_tile_from_element", "ref_tile_element_from_element",
-              "ref_element_from_tile_and_tile_element"):
-        getattr(R, f).restype = C.c_long
-        getattr(R, f).argtypes = None
-    lg = C.c_long
+    rank_tile = iter(g["rank_global_tile"])
+    local_tile = iter(g["local_tile_from_global_tile"])
+    local_tile_next = iter(g["next_local_tile_from_global_tile"])
+    global_tile = iter(g["global_tile_from_local_tile"])
     n = 0
-    for gs in (1, 2, 3, 5):
-        for tpb in (1, 2, 4):
+    for gs in g["grid_sizes"]:
+        for tpb in g["tiles_per_block"]:
             for src in range(gs):
                 for toff in range(tpb):
                     for rank in range(gs):
-                        for gt in range(0, 41, 1):
-                            a = (lg(gt), lg(tpb), gs, src, lg(toff))
-                            assert R.ref_rank_global_tile(*a) == L.orc_rank_global_tile(gt, tpb, gs, src, toff)
-                            b = (lg(gt), lg(tpb), gs, rank, src, lg(toff))
+                        for gt in range(g["global_tiles"]):
+                            assert next(rank_tile) == L.orc_rank_global_tile(gt, tpb, gs, src, toff)
                             lt = L.orc_local_tile_from_global_tile(gt, tpb, gs, rank, src, toff)
-                            assert R.ref_local_tile_from_global_tile(*b) == lt
-                            assert R.ref_next_local_tile_from_global_tile(*b) == \
+                            assert next(local_tile) == lt
+                            assert next(local_tile_next) == \
                                 L.orc_next_local_tile_from_global_tile(gt, tpb, gs, rank, src, toff)
+                            ref_gt = next(global_tile)
                             if lt >= 0:
-                                assert R.ref_global_tile_from_local_tile(lg(lt), lg(tpb), gs, rank, src, lg(toff)) == gt
+                                assert ref_gt == gt
                                 assert L.orc_global_tile_from_local_tile(lt, tpb, gs, rank, src, toff) == gt
+                            else:
+                                assert ref_gt is None
                             n += 1
-    for ts in (1, 7, 10):
+    tile = iter(g["tile_from_element"])
+    tile_element = iter(g["tile_element_from_element"])
+    for ts in g["tile_sizes"]:
         for off in range(ts):
-            for e in range(0, 50):
-                assert R.ref_tile_from_element(lg(e), lg(ts), lg(off)) == L.orc_tile_from_element(e, ts, off)
-                assert R.ref_tile_element_from_element(lg(e), lg(ts), lg(off)) == \
-                    L.orc_tile_element_from_element(e, ts, off)
-    assert n > 1000
+            for e in range(g["elements"]):
+                assert next(tile) == L.orc_tile_from_element(e, ts, off)
+                assert next(tile_element) == L.orc_tile_element_from_element(e, ts, off)
+    for it in (rank_tile, local_tile, local_tile_next, global_tile, tile, tile_element):
+        assert next(it, None) is None, "fixture longer than the sweep"
+    assert n == len(g["rank_global_tile"]) > 1000
 
 
 def test_local_sizes_sum_to_global(oracle):

@@ -117,13 +117,15 @@ bool panel_qr_blocked_supported(int b, long m, int nr, size_t elem_size, bool is
 template <class T>
 void launch_hr_transpose(T* qt, int b, long m, T* cm, long ld, bool to_cm, const int* flag, hipStream_t stream);
 // raises *flag when max / min of the diagonal of the lower factor l (b x b, ld) exceeds `limit` (<= 0: no gate) or is
-// not finite; zeroes the strict upper triangle of l
+// not finite, or when the factorization's own `status` (may be null) is non-zero; zeroes the strict upper triangle of l.
+// Does nothing when *flag or *skip (may be null) is already raised.
 template <class T>
-void launch_hr_gate(T* l, int ld, int b, double limit, int* flag, hipStream_t stream);
-// g2 = Q1^T Q1 after the first pass: within `tol` of the identity -> g2 := I, *skip = 1 (the second pass returns at
-// once: it takes `skip` as its status word); farther than 0.1 -> *flag
+void launch_hr_gate(T* l, int ld, int b, double limit, int* flag, const int* skip, const int* status, hipStream_t stream);
+// g2 = Q1^T Q1 after the first pass: within `tol` of the identity -> g2 := I, *skip = 1 and *status2 = 1 (the second
+// factorization, whose status word is status2, returns at once, and so do the launches that take `skip`); farther
+// than `fail` -> *flag
 template <class T>
-void launch_hr_orth(T* g2, int ld, int b, double tol, int* skip, int* flag, hipStream_t stream);
+void launch_hr_orth(T* g2, int ld, int b, double tol, double fail, int* skip, int* status2, int* flag, hipStream_t stream);
 // Householder reconstruction of the top b x b block from it and R = L2^T L1^T (see kernels_hr.hip: hr_lu_kernel)
 template <class T>
 void launch_hr_lu(T* q, long ldq, int b, const T* rmat, T* lu, T* y1, T* tb, T* taus, const int* flag, hipStream_t stream);

@@ -128,16 +128,26 @@ __global__ __launch_bounds__(256) void hr_transpose_kernel(T* qt, int b, long m,
   }
 }
 
-// The gate between the first Cholesky factorization and everything built on it: the diagonal of the factor L of
-// G = P^T P bounds the condition number of P from below (max / min of |l_jj|); CholeskyQR2 delivers a Q that is
-// orthonormal to rounding while cond(P)^2 eps << 1.  Beyond `limit` (<= 0: no gate), or for a factor that is not
-// finite, the flag is raised.  The strict upper triangle of l -- which the factorization leaves as it found it -- is
-// zeroed, so that R = L2^T L1^T can be formed by the general product.  One workgroup.
+// The gate behind each Cholesky factorization.  First pass: max / min of |l_jj| of the factor L of G = P^T P is a LOWER
+// bound of cond(P) only -- Kahan-like panels keep it near 1 up to cond 1e11 -- so the ratio gate (`limit`) is a cheap
+// first exit for panels that are plainly ill conditioned, not a guarantee; the bound that keeps the path inside
+// CholeskyQR2's proven range is hr_orth's failure threshold.  It stays because it sends those panels back before the
+// solve and the second Gram product.  Second pass (no ratio: limit <= 0): the factorization has its own status word
+// `status`, and a non-zero one (a non-positive pivot, or strips that were not co-resident) is folded into `flag` here,
+// unless the pass was skipped (`skip`).  Either pass: a factor that is not finite raises the flag.  The strict upper
+// triangle of l -- which the factorization leaves as it found it -- is zeroed, so that R = L2^T L1^T can be formed by
+// the general product.  One workgroup.
 template <class T>
-__global__ __launch_bounds__(256) void hr_gate_kernel(T* l, int ld, int b, real_t<T> limit, int* flag) {
+__global__ __launch_bounds__(256) void hr_gate_kernel(T* l, int ld, int b, real_t<T> limit, int* flag, const int* skip,
+                                                      const int* status) {
   using R = real_t<T>;
-  if (*flag != 0)
+  if (*flag != 0 || (skip != nullptr && *skip != 0))
     return;
+  if (status != nullptr && *status != 0) {
+    if (threadIdx.x == 0)
+      atomicCAS(flag, 0, 3);
+    return;
+  }
   for (int idx = threadIdx.x; idx < b * b; idx += 256) {
     const int r = idx % b, c = idx / b;
     if (r < c)
@@ -172,10 +182,14 @@ __global__ __launch_bounds__(256) void hr_gate_kernel(T* l, int ld, int b, real_
 // After the first CholeskyQR pass: g2 = Q1^T Q1 (b x b, ld).  When it equals the identity to `tol` (max norm) the
 // second pass would change nothing above rounding -- the panels of a random matrix have condition numbers close to 1
 // and come out of ONE pass orthonormal to a few 1e-15 -- so g2 is replaced by the identity (its "Cholesky factor":
-// R = L2^T L1^T = L1^T) and *skip is raised: the second factorization and solve, which take `skip` as their status
-// word, return at once.  A g2 that is far from the identity (> 0.1) means the first pass failed outright: *flag.
+// R = L2^T L1^T = L1^T) and *skip and *status2 are raised: the second factorization (status word status2), its gate
+// and its solve return at once.  A g2 farther from the identity than `fail` raises *flag.  That measure grows like
+// cond(P)^2 eps, so `fail` (the host's hr_orth_fail_tol(m, b), of order 1e-11 at m = 384) is what keeps the blocked path
+// inside the condition numbers for which CholeskyQR2 is proven backward stable with an orthonormal Q; the ratio gate
+// in front of it admits Kahan-like panels of any condition.
 template <class T>
-__global__ __launch_bounds__(256) void hr_orth_kernel(T* g2, int ld, int b, real_t<T> tol, int* skip, int* flag) {
+__global__ __launch_bounds__(256) void hr_orth_kernel(T* g2, int ld, int b, real_t<T> tol, real_t<T> fail, int* skip,
+                                                      int* status2, int* flag) {
   using R = real_t<T>;
   __shared__ R red[256];
   if (*flag != 0)
@@ -204,7 +218,7 @@ __global__ __launch_bounds__(256) void hr_orth_kernel(T* g2, int ld, int b, real
     __syncthreads();
   }
   const R m = red[0];
-  if (!(m <= R(0.1))) {
+  if (!(m <= fail)) {
     if (threadIdx.x == 0)
       atomicCAS(flag, 0, 2);
     return;
@@ -214,8 +228,10 @@ __global__ __launch_bounds__(256) void hr_orth_kernel(T* g2, int ld, int b, real
       const int r = idx % b, c = idx / b;
       g2[r + (long) c * ld] = make_el<T>((r == c) ? R(1) : R(0), R(0));
     }
-    if (threadIdx.x == 0)
+    if (threadIdx.x == 0) {
       *skip = 1;
+      *status2 = 1;
+    }
   }
 }
 
@@ -360,13 +376,14 @@ void launch_hr_transpose(T* qt, int b, long m, T* cm, long ld, bool to_cm, const
 }
 
 template <class T>
-void launch_hr_gate(T* l, int ld, int b, double limit, int* flag, hipStream_t stream) {
-  hipLaunchKernelGGL((hr_gate_kernel<T>), dim3(1), dim3(256), 0, stream, l, ld, b, (real_t<T>) limit, flag);
+void launch_hr_gate(T* l, int ld, int b, double limit, int* flag, const int* skip, const int* status, hipStream_t stream) {
+  hipLaunchKernelGGL((hr_gate_kernel<T>), dim3(1), dim3(256), 0, stream, l, ld, b, (real_t<T>) limit, flag, skip, status);
 }
 
 template <class T>
-void launch_hr_orth(T* g2, int ld, int b, double tol, int* skip, int* flag, hipStream_t stream) {
-  hipLaunchKernelGGL((hr_orth_kernel<T>), dim3(1), dim3(256), 0, stream, g2, ld, b, (real_t<T>) tol, skip, flag);
+void launch_hr_orth(T* g2, int ld, int b, double tol, double fail, int* skip, int* status2, int* flag, hipStream_t stream) {
+  hipLaunchKernelGGL((hr_orth_kernel<T>), dim3(1), dim3(256), 0, stream, g2, ld, b, (real_t<T>) tol, (real_t<T>) fail,
+                     skip, status2, flag);
 }
 
 template <class T>
@@ -392,8 +409,8 @@ void hr_kernels_init() {}
 
 #define INST(T)                                                                                            \
   template void launch_hr_transpose<T>(T*, int, long, T*, long, bool, const int*, hipStream_t);            \
-  template void launch_hr_gate<T>(T*, int, int, double, int*, hipStream_t);                                \
-  template void launch_hr_orth<T>(T*, int, int, double, int*, int*, hipStream_t);                          \
+  template void launch_hr_gate<T>(T*, int, int, double, int*, const int*, const int*, hipStream_t);         \
+  template void launch_hr_orth<T>(T*, int, int, double, double, int*, int*, int*, hipStream_t);            \
   template void launch_hr_lu<T>(T*, long, int, const T*, T*, T*, T*, T*, const int*, hipStream_t);
 INST(float)
 INST(double)

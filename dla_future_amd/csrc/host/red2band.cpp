@@ -49,6 +49,23 @@ T scalar(double re) {
   return make_host_el<T>(re);
 }
 
+// The thresholds of the blocked panel factorization (kernels_hr.hip).  oracle/red2band.py restates them
+// (HR_GATE_RATIO, HR_SKIP_TOL, HR_ORTH_FAIL_SCALE, blocked_panel_path) and tests/test_oracle_red2band.py reads them
+// from this file.
+constexpr double kHrGateRatio = 1.0e4;       // max / min of diag(L1) beyond which the panel is sent back at once
+constexpr double kHrSkipTol = 2.0e-13;       // |Q1^H Q1 - I| up to which the second CholeskyQR pass is skipped
+constexpr double kHrOrthFailScale = 2.0e-5;  // see hr_orth_fail_tol
+
+// The failure threshold of hr_orth for an m x b panel.  CholeskyQR2 is proven backward stable with an orthonormal Q for
+// cond(P) <= (11 (m b + b (b + 1)) u)^(-1/2), u = 2^-53 (Yamamoto et al., ETNA 44, 2015); the first pass's
+// |Q1^H Q1 - I| grows like cond(P)^2 u, which is 1 / (11 (m b + b (b + 1))) at that bound.  The scale below it is
+// chosen with the CPU model (oracle/red2band.py: blocked_panel_path over Kahan-like panels, which measure >= 2.5e-4 of
+// that value once they are past the bound) so that an accepted panel is inside the bound with margin for the device's
+// other rounding.  Never below kHrSkipTol: a panel that one pass leaves orthonormal is accepted whatever m is.
+double hr_orth_fail_tol(long m, int b) {
+  return std::max(kHrSkipTol, kHrOrthFailScale / (11.0 * ((double) m * b + (double) b * (b + 1))));
+}
+
 double g_last_ms = 0, g_last_flops = 0;
 long g_last_panels[2] = {0, 0};  // panels of the last reduction factored blocked / sent back to the reflector kernel
 }  // namespace
@@ -170,7 +187,8 @@ int reduction_to_band_device(DeviceMatrix<T>& A, int band, T* taus_host) {
     hr_lu = dalloc<T>((size_t) b * b);
     hr_y1 = dalloc<T>((size_t) b * b);
     hr_winv = dalloc<T>(4 * hr_wblk);
-    DLAF_HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&hr_flag), 2 * sizeof(int)));  // [0] failure, [1] second pass skipped
+    // [0] failure, [1] second pass skipped, [2] status of the second Cholesky factorization
+    DLAF_HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&hr_flag), 3 * sizeof(int)));
     DLAF_HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&hr_sync), sizeof(unsigned) * potrf_coop_sync_words(b)));
   }
   int* hr_flag_host = nullptr;
@@ -252,7 +270,7 @@ int reduction_to_band_device(DeviceMatrix<T>& A, int band, T* taus_host) {
           T* P = Pcm;
           T* qtp = qt + (size_t) o * b;
           const int nrt = (int) ((m + b - 1) / b);
-          DLAF_HIP_CHECK(hipMemsetAsync(hr_flag, 0, 2 * sizeof(int), s));
+          DLAF_HIP_CHECK(hipMemsetAsync(hr_flag, 0, 3 * sizeof(int), s));
           launch_hr_transpose(qtp, b, m, P, ldp, true, nullptr, s);
           auto gram = [&](T* out) {
             GemmArgs<T> g;
@@ -296,16 +314,19 @@ int reduction_to_band_device(DeviceMatrix<T>& A, int band, T* taus_host) {
           (void) nrt;
           gram(hr_g);
           launch_potrf_coop(hr_g, b, b, hr_winv, hr_flag, 0, hr_sync, s, false, false);
-          // cond(P) >= max / min of the factor's diagonal; CholeskyQR2 is safe far beyond this gate (cond^2 eps << 1)
-          launch_hr_gate(hr_g, b, b, 1.0e4, hr_flag, s);
+          // max / min of the factor's diagonal is only a LOWER bound of cond(P): a cheap first exit for panels that are
+          // plainly ill conditioned; the bound that keeps the path inside CholeskyQR2's proven range is hr_orth's below
+          launch_hr_gate(hr_g, b, b, kHrGateRatio, hr_flag, nullptr, nullptr, s);
           solve(0, hr_g, hr_winv);
           gram(hr_l2);
-          // second pass -- unless the first one left Q orthonormal already (|Q1^T Q1 - I| <= 2e-13: hr_skip is raised,
-          // hr_l2 becomes the identity, and the three launches below, which take hr_skip as their status word, return
-          // at once: 19 ms of the 380 at N = 20480)
-          launch_hr_orth(hr_l2, b, b, 2.0e-13, hr_flag + 1, hr_flag, s);
-          launch_potrf_coop(hr_l2, b, b, hr_winv + hr_wblk, hr_flag + 1, 0, hr_sync, s, false, false);
-          launch_hr_gate(hr_l2, b, b, 0.0, hr_flag + 1, s);  // (no gate: zeroes the strict upper triangle)
+          // second pass -- unless the first one left Q orthonormal already (|Q1^T Q1 - I| <= kHrSkipTol: hr_flag[1] is
+          // raised, hr_l2 becomes the identity, and the three launches below return at once: 19 ms of the 380 at
+          // N = 20480).  A measure above hr_orth_fail_tol(m, b) sends the panel to the reflector-by-reflector kernel.
+          // The second factorization has a status word of its own, hr_flag[2] (hr_orth sets it as well when it skips):
+          // the second gate folds a failure of it into hr_flag[0], which everything downstream looks at.
+          launch_hr_orth(hr_l2, b, b, kHrSkipTol, hr_orth_fail_tol(m, b), hr_flag + 1, hr_flag + 2, hr_flag, s);
+          launch_potrf_coop(hr_l2, b, b, hr_winv + hr_wblk, hr_flag + 2, 0, hr_sync, s, false, false);
+          launch_hr_gate(hr_l2, b, b, 0.0, hr_flag, hr_flag + 1, hr_flag + 2, s);  // (no ratio gate)
           solve(0, hr_l2, hr_winv + hr_wblk, hr_flag + 1);
           {
             GemmArgs<T> g;  // R = L2^T L1^T

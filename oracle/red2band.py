@@ -90,18 +90,19 @@ def compute_panel_reflectors(p: np.ndarray, nrefls: int) -> np.ndarray:
     return taus
 
 
-def panel_reflectors_blocked(p: np.ndarray):
+def panel_reflectors_blocked(p: np.ndarray, second_pass: bool = True):
     """The BLOCKED panel factorization of the MI355X build (csrc/device/kernels_hr.hip, red2band.cpp), restated in numpy
     so that it can be pinned on the CPU against compute_panel_reflectors / LAPACK ?geqrf: CholeskyQR2, then the
     Householder representation of Q reconstructed by an LU factorization without pivoting of Q - [S; 0] with
     S = diag(-sign(Re q_jj)) chosen during the elimination (Ballard et al., "Reconstructing Householder vectors from
     TSQR", IPDPS 2014).  p: m x b, m >= b, full column rank.  Returns (out, taus, t): `out` in xGEQR2's layout (S R on and
-    above the diagonal of the top block, the reflectors below), taus = -u_jj s_j, t = -U S V1^-H (the T factor)."""
+    above the diagonal of the top block, the reflectors below), taus = -u_jj s_j, t = -U S V1^-H (the T factor).
+    second_pass=False: the device's skip (blocked_panel_path's "one pass"), L2 = I."""
     m, b = p.shape
     g = p.conj().T @ p
     l1 = np.linalg.cholesky(g)
     q = np.linalg.solve(l1, p.conj().T).conj().T          # P L1^-H
-    l2 = np.linalg.cholesky(q.conj().T @ q)
+    l2 = np.linalg.cholesky(q.conj().T @ q) if second_pass else np.eye(b, dtype=p.dtype)
     q = np.linalg.solve(l2, q.conj().T).conj().T
     r = l2.conj().T @ l1.conj().T
     w = q[:b, :].copy()
@@ -118,6 +119,80 @@ def panel_reflectors_blocked(p: np.ndarray):
     t = np.linalg.solve(y1.conj(), (-u * sgn[None, :]).T).T   # (-U S) V1^-H
     out = np.vstack([np.tril(y1, -1) + np.triu(sgn[:, None] * r), y2]).astype(p.dtype)
     return out, taus, t.astype(p.dtype)
+
+
+# The thresholds of the device's decision between the blocked panel factorization and the reflector-by-reflector
+# kernel.  Each names its counterpart in dla_future_amd/csrc/host/red2band.cpp; tests/test_oracle_red2band.py reads
+# those from the source and fails when the two drift apart.
+HR_GATE_RATIO = 1.0e4           # kHrGateRatio: hr_gate_kernel's limit on max / min of diag(L1)
+HR_SKIP_TOL = 2.0e-13           # kHrSkipTol: hr_orth_kernel's "Q1 is orthonormal already, skip the second pass"
+HR_ORTH_FAIL_SCALE = 2.0e-5     # kHrOrthFailScale: hr_orth_fail_tol(m, b), hr_orth_kernel's failure threshold
+
+
+def cholqr2_cond_bound(m: int, b: int) -> float:
+    """The condition number up to which CholeskyQR2 is proven backward stable with an orthonormal Q (Yamamoto,
+    Nakatsukasa, Yanagisawa, Fukaya, "Roundoff error analysis of the CholeskyQR2 algorithm", ETNA 44, 2015):
+    cond(P) <= (11 (m b + b (b + 1)) u)^(-1/2), u = 2^-53 the unit roundoff (about 1.1e5 at m = 384, b = 128)."""
+    return (11.0 * (m * b + b * (b + 1)) * 2.0 ** -53) ** -0.5
+
+
+def hr_orth_fail_tol(m: int, b: int) -> float:
+    """hr_orth_fail_tol (red2band.cpp): the largest max|Q1^H Q1 - I| after the first CholeskyQR pass that keeps an m x b
+    panel on the blocked path.  That measure grows like cond(P)^2 eps; the threshold is HR_ORTH_FAIL_SCALE times its
+    value at the proven bound, cond_bound^2 u = 1 / (11 (m b + b (b + 1))), and never below HR_SKIP_TOL."""
+    return max(HR_SKIP_TOL, HR_ORTH_FAIL_SCALE / (11.0 * (m * b + b * (b + 1))))
+
+
+def hr_orth_measure(g2: np.ndarray) -> float:
+    """What hr_orth_kernel measures on g2 = Q1^H Q1: the largest of |Re - delta| and |Im| over the lower triangle with
+    the diagonal (NaN wins)."""
+    low = np.tril(g2) - np.eye(g2.shape[0])
+    v = np.maximum(np.abs(low.real), np.abs(low.imag))
+    return float("nan") if np.isnan(v).any() else float(v.max())
+
+
+def blocked_panel_path(p: np.ndarray, fail_tol: float | None = None):
+    """The device's choice for one m x b panel (red2band.cpp, the blocked branch of the panel loop), restated: Cholesky
+    of G1 = P^H P (failure: fallback), the ratio gate on diag(L1), hr_orth's measure of Q1 = P L1^-H against the skip
+    and failure thresholds, and the Cholesky of G2 = Q1^H Q1 (failure: fallback).  fail_tol: hr_orth's failure
+    threshold (default hr_orth_fail_tol(m, b)).  Returns (path, reason, orth): path "blocked" or "fallback"; reason
+    "cholesky1", "gate", "orth", "cholesky2" (fallback) or "one pass", "two passes" (blocked); orth the measure (NaN
+    when the first factorization did not get that far)."""
+    m, b = p.shape
+    if fail_tol is None:
+        fail_tol = hr_orth_fail_tol(m, b)
+    try:
+        l1 = np.linalg.cholesky(p.conj().T @ p)
+    except np.linalg.LinAlgError:
+        return "fallback", "cholesky1", float("nan")
+    d = np.real(np.diag(l1))
+    if not (np.isfinite(d).all() and (d > 0).all()) or not d.max() <= HR_GATE_RATIO * d.min():
+        return "fallback", "gate", float("nan")
+    q = np.linalg.solve(l1, p.conj().T).conj().T
+    g2 = q.conj().T @ q
+    orth = hr_orth_measure(g2)
+    if not orth <= fail_tol:
+        return "fallback", "orth", orth
+    if orth <= HR_SKIP_TOL:
+        return "blocked", "one pass", orth
+    try:
+        np.linalg.cholesky(g2)
+    except np.linalg.LinAlgError:
+        return "fallback", "cholesky2", orth
+    return "blocked", "two passes", orth
+
+
+def kahan_panel(m: int, b: int, c: float, dtype, seed: int = 0) -> np.ndarray:
+    """P = Q0 R(c): Q0 a random m x b matrix with orthonormal columns, R = I + triu(full(-c), 1) (flat unit diagonal,
+    Kahan-like).  cond(P) = cond(R) grows like (1 + c)^b while max / min of diag(chol(P^H P)) stays close to 1."""
+    rng = np.random.default_rng(seed)
+    dt = np.dtype(dtype)
+    x = rng.standard_normal((m, b))
+    if dt.kind == "c":
+        x = x + 1j * rng.standard_normal((m, b))
+    q0, _ = np.linalg.qr(x)
+    r = np.eye(b) + np.triu(np.full((b, b), -c), 1)
+    return np.asfortranarray((q0 @ r).astype(dt))
 
 
 def well_formed_v(p: np.ndarray, nrefls: int) -> np.ndarray:
@@ -143,9 +218,10 @@ def compute_t_factor(v: np.ndarray, taus: np.ndarray) -> np.ndarray:
     return t
 
 
-def reduction_to_band(a: np.ndarray, nb: int, band: int):
+def reduction_to_band(a: np.ndarray, nb: int, band: int, panel_hook=None):
     """ReductionToBand::call (impl.h:968-1110) on a dense column-major matrix whose LOWER triangle holds the
-    Hermitian input; in place; the strict upper triangle is neither read nor written.  Returns taus."""
+    Hermitian input; in place; the strict upper triangle is neither read nor written.  Returns taus.
+    panel_hook(panel, nrefls): called with a copy of each panel before it is factored (tests model per-panel decisions)."""
     n = a.shape[0]
     assert a.shape == (n, n) and band >= 2 and nb % band == 0
     dt = a.dtype
@@ -158,6 +234,8 @@ def reduction_to_band(a: np.ndarray, nb: int, band: int):
         r0, c0 = (j_sub + 1) * band, j_sub * band
         nrefls_tile = min(band, nrefls - j_sub * band)
         panel = a[r0:, c0:c0 + band]                       # SubPanelView (views.h:128-171): a view, in place
+        if panel_hook is not None:
+            panel_hook(panel.copy(order="F"), nrefls_tile)
         taus[c0:c0 + nrefls_tile] = compute_panel_reflectors(panel, nrefls_tile)
         v = well_formed_v(panel, nrefls_tile)
         t = compute_t_factor(v, taus[c0:c0 + nrefls_tile])

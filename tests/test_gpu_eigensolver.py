@@ -214,6 +214,49 @@ def test_bt_band_to_tridiag_vs_definition(dlaf, grid, td, t, n, band, k):
     assert np.abs(emat - ref).max() <= tol, (t, n, band, np.abs(emat - ref).max(), tol)
 
 
+
+# (n, k) covering the fused kernel's edges at band 128: a last block of a wavefront with fewer than 2b rows (n = 129, 130,
+# 257, 258, 385), strips of fewer than 64 columns and waves of fewer than 16 (k = 1, 15, 17, 63, 65, 130), whole strips
+# (k = 16, 64), several blocks per wavefront (n = 640)
+BT_FUSED_EDGES = [(129, 1), (130, 17), (256, 16), (257, 63), (258, 64), (385, 65), (385, 15), (640, 130), (640, 1)]
+
+
+@pytest.mark.parametrize("n,k", BT_FUSED_EDGES)
+def test_bt_band_to_tridiag_fused_edges(dlaf, grid, td, n, k):
+    """bt_band_to_tridiagonal on the fused kernel (d, band 128) at its edges, with E inside a store whose ld is padded
+    and whose rows above and below E and the column next to it are sentinels that must stay bit-identical; v must come
+    back unchanged.  Reference: the one-reflector-at-a-time definition in extended precision from the same inputs."""
+    dt, band = np.float64, 128
+    a0 = random_band(n, band, dt, 11 + n)
+    d, e, v = dlaf.band_to_tridiagonal(grid, a0.copy(order="F"), 2 * band, band)
+    rng = np.random.default_rng(n + k)
+    e0 = rng.uniform(-1, 1, (n, k))
+    store = np.full((n + 7, k + 1), -3.25, order="F")
+    emat = store[3:n + 3, :k]
+    emat[...] = e0
+    sentinel = store.copy(order="F")
+    v_in = v.copy(order="F")
+    dlaf.bt_band_to_tridiagonal(band, emat, v_in)
+    assert np.array_equal(v_in, v)
+    assert np.array_equal(store[:3], sentinel[:3]) and np.array_equal(store[n + 3:], sentinel[n + 3:])
+    assert np.array_equal(store[:, k:], sentinel[:, k:])
+    ref = td.apply_q(v.astype(np.longdouble), band, e0.astype(np.longdouble))
+    err = float(np.abs(emat - ref).max())
+    tol = 20 * n * td.error_of(dt)
+    assert err <= tol, (n, k, err, tol)
+
+
+def test_bt_band_to_tridiag_fused_zero_reflectors(dlaf, grid, td):
+    """A diagonal band matrix: every tau is 0, so E must come back bit-identical (through a padded ld as well)."""
+    n, k, band = 385, 65, 128
+    a0 = np.asfortranarray(np.diag(np.random.default_rng(3).uniform(-1, 1, n)))
+    d, e, v = dlaf.band_to_tridiagonal(grid, a0.copy(order="F"), 2 * band, band)
+    assert not np.abs(e).any()
+    store = np.asfortranarray(np.random.default_rng(4).uniform(-1, 1, (n + 5, k)))
+    before = store.copy(order="F")
+    dlaf.bt_band_to_tridiagonal(band, store[2:n + 2, :], v)
+    assert np.array_equal(store, before)
+
 def random_hermitian(n, dt, seed):
     rng = np.random.default_rng(seed)
     a = rng.uniform(-1, 1, (n, n)).astype(dt)

@@ -169,3 +169,104 @@ def test_red2band_then_bt_recovers_the_eigenvectors(dlaf, grid, rb, oracle, t):
     assert np.abs(zc.conj().T @ zc - np.eye(n)).max() <= n * n * rb.error_of(dt)
     ms, flops = dlaf.red2band_profile()
     assert ms > 0 and flops > 0
+
+
+def expected_panel_counts(t, n, b):
+    """(blocked, fallback) for a matrix whose every eligible panel keeps the blocked path: the panel loop of red2band.cpp
+    with panel_qr_blocked_supported (d / z, band 64 / 128, a full set of b reflectors, m >= 2 b)."""
+    nrefls = max(0, n - b - 1)
+    blocked = 0
+    for p in range((nrefls - 1) // b + 1 if nrefls else 0):
+        r0 = (p + 1) * b
+        nr = min(b, nrefls - p * b)
+        m = n - r0
+        blocked += t in ("d", "z") and b in (64, 128) and nr == b and m >= 2 * b
+    return blocked, 0
+
+
+@pytest.mark.parametrize("t", ["d", "z"])
+@pytest.mark.parametrize("b", [64, 128])
+def test_reduction_to_band_blocked_dispatch_is_exact(dlaf, grid, rb, oracle, t, b):
+    """The blocked path is taken by exactly the panels panel_qr_blocked_supported admits, no more and no fewer, at its
+    boundaries: n = 3b (the first panel has m = 2b exactly), 3b - 1 (no blocked panel), 3b + 1, a ragged last tile, and
+    nb = b next to nb = 2b -- with the usual parity checks."""
+    for n, nb in [(3 * b, 2 * b), (3 * b - 1, 2 * b), (3 * b + 1, b), (3 * b + 1, 2 * b), (5 * b + 17, 2 * b)]:
+        run_and_check(dlaf, grid, rb, oracle, t, n, nb, b, False)
+        assert dlaf.red2band_panel_stats() == expected_panel_counts(t, n, b), (t, n, nb, b, dlaf.red2band_panel_stats())
+    assert expected_panel_counts(t, 3 * b, b) == (1, 0) and expected_panel_counts(t, 3 * b - 1, b) == (0, 0)
+
+
+def kahan_hermitian(rb, n, b, c, dt, seed):
+    """A random Hermitian matrix whose first panel A[b:n, 0:b] is rb.kahan_panel(n - b, b, c) (mirrored above)."""
+    a = rb.random_hermitian(n, dt, seed=seed)
+    p = rb.kahan_panel(n - b, b, c, dt, seed=seed)
+    a[b:, :b] = p
+    a[:b, b:] = p.conj().T
+    return np.asfortranarray(a)
+
+
+def decisive_path(rb, p):
+    """The model's path for panel p ("blocked" / "fallback") when that decision is two orders of magnitude from every
+    threshold that decides it (the ratio gate and hr_orth's failure threshold; the skip tolerance only chooses between one
+    and two passes of the blocked path), else None."""
+    path, why, orth = rb.blocked_panel_path(p)
+    m, b = p.shape
+    if why in ("one pass", "two passes"):
+        d = np.real(np.diag(np.linalg.cholesky(p.conj().T @ p)))
+        return path if d.max() <= d.min() * rb.HR_GATE_RATIO / 100 and orth <= rb.hr_orth_fail_tol(m, b) / 100 else None
+    if why == "orth" and orth >= 100 * rb.hr_orth_fail_tol(m, b):
+        return path
+    return None
+
+
+# (c well inside the blocked region, c between CholeskyQR2's proven bound and the former 0.1 exit, c near breakdown)
+KAHAN_CASES = [(t, n, nb, b, c) for t in ("d", "z") for n, nb, b in [(512, 256, 128), (512, 128, 64)]
+               for c in (0.02, 0.1 if b == 128 else 0.2, 0.4)]
+
+
+@pytest.mark.parametrize("t,n,nb,b,c", KAHAN_CASES)
+def test_reduction_to_band_ill_conditioned_first_panel(dlaf, grid, rb, oracle, t, n, nb, b, c):
+    """A first panel P = Q0 R(c) with a flat unit diagonal: the ratio gate sees ~1 at every condition number, so what keeps
+    the blocked path inside CholeskyQR2's proven range is hr_orth's failure threshold.  Whatever path each panel takes:
+    the reference's backward check, an orthogonal Q (bt_reduction_to_band of the identity), the untouched upper triangle
+    and padding; elementwise parity with the oracle only where the QR of the panel is well conditioned enough for two
+    Householder codes to agree (model spread below a tenth of the tolerance); the panel counts only where the model's
+    decision is two orders of magnitude from every threshold."""
+    dt = oracle.DTYPES[t]
+    a0 = kahan_hermitian(rb, n, b, c, dt, seed=2000 + n + b)
+    store = np.full((n + 2, n), 5.5, dtype=dt, order="F")
+    a = store[:n, :n]
+    a[...] = a0
+    up = np.triu_indices(n, 1)
+    a[up] = -9.9
+    taus = dlaf.reduction_to_band(grid, a, nb, b)
+    blocked, fallback = dlaf.red2band_panel_stats()
+    assert (a[up] == dt(-9.9)).all() and (store[n:, :] == 5.5).all()
+    ok, diff, tol = rb.check_result(a0, a, taus, b)
+    assert ok, (t, n, nb, b, c, diff, tol, blocked, fallback)
+    q = np.asfortranarray(np.eye(n, dtype=dt))
+    dlaf.bt_reduction_to_band(grid, b, q, a.copy(order="F"), taus, nb)
+    orth = np.abs(q.conj().T @ q - np.eye(n)).max()
+    assert orth <= 10 * n * rb.error_of(dt), (t, n, nb, b, c, orth, blocked, fallback)
+    print(f"KAHAN t={t} n={n} nb={nb} b={b} c={c} cond={np.linalg.cond(a0[b:, :b]):.3g} backward={diff:.3g} "
+          f"orth={orth:.3g} blocked={blocked} fallback={fallback}")
+    # the model: each panel's path (counts), and the spread of two Householder codes on inputs that differ by rounding
+    paths = []
+
+    def hook(p, nr):
+        m = p.shape[0]
+        if nr == b and m >= 2 * b:
+            paths.append(decisive_path(rb, p))
+    ref = a0.copy(order="F")
+    rtaus = rb.reduction_to_band(ref, nb, b, panel_hook=hook)
+    if None not in paths:
+        assert (blocked, fallback) == (paths.count("blocked"), paths.count("fallback")), (paths, blocked, fallback)
+    rng = np.random.default_rng(1)
+    pert = a0 * (1 + rb.error_of(dt) * rng.uniform(-1, 1, a0.shape))
+    pert = np.asfortranarray(np.tril(pert) + np.tril(pert, -1).conj().T)
+    np.fill_diagonal(pert, np.real(np.diag(pert)))
+    rb.reduction_to_band(pert, nb, b)
+    spread = np.abs(np.tril(ref) - np.tril(pert)).max()
+    if spread <= tol / 10:
+        assert np.abs(np.tril(ref) - np.tril(a)).max() <= tol, (t, n, nb, b, c, np.abs(np.tril(ref) - np.tril(a)).max(), tol)
+        assert np.abs(rtaus - taus).max() <= tol

@@ -113,3 +113,70 @@ def test_blocked_panel_factorization_reproduces_geqr2(dt):
         assert np.abs(out - qr).max() <= tol and np.abs(taus - tl).max() <= tol
         v = rb.well_formed_v(out, b)
         assert np.abs(t - rb.compute_t_factor(v, taus)).max() <= tol
+
+
+def test_blocked_panel_thresholds_match_the_device_source():
+    """The model's thresholds (oracle.red2band.blocked_panel_path) are the ones red2band.cpp passes to the kernels."""
+    import os
+    import re
+    src = open(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "dla_future_amd", "csrc", "host",
+                            "red2band.cpp")).read()
+
+    def const(name):
+        found = re.findall(r"constexpr double %s = ([0-9.eE+-]+);" % name, src)
+        assert len(found) == 1, name
+        return float(found[0])
+    assert const("kHrGateRatio") == rb.HR_GATE_RATIO
+    assert const("kHrSkipTol") == rb.HR_SKIP_TOL
+    assert const("kHrOrthFailScale") == rb.HR_ORTH_FAIL_SCALE
+    # the formula of hr_orth_fail_tol and the launches that use the three
+    assert "std::max(kHrSkipTol, kHrOrthFailScale / (11.0 * ((double) m * b + (double) b * (b + 1))))" in src
+    assert "launch_hr_gate(hr_g, b, b, kHrGateRatio," in src
+    assert "launch_hr_orth(hr_l2, b, b, kHrSkipTol, hr_orth_fail_tol(m, b)," in src
+
+
+KAHAN_C = [0.0, 0.02, 0.04, 0.06, 0.08, 0.1, 0.15, 0.2, 0.3, 0.6]
+
+
+@pytest.mark.parametrize("dt", [np.float64, np.complex128])
+@pytest.mark.parametrize("b", [64, 128])
+def test_blocked_panel_path_stays_in_cholqr2s_proven_range(dt, b):
+    """Kahan-like panels P = Q0 R(c) (flat unit diagonal: the ratio gate sees ~1 at any condition number) from well
+    conditioned to Cholesky breakdown.  Wherever the model of the device's decision says "blocked", the blocked
+    restatement must be backward stable and its reflectors orthogonal to 10 m eps (a panel that skips the second pass may
+    keep |Q^H Q - I| up to the skip tolerance 2e-13, 7 m eps at m = 128), and cond(P) must lie inside CholeskyQR2's
+    proven bound.  With the former failure threshold 0.1 the last assertion failed: cond 7e5 to 1e11 were accepted."""
+    eps = np.finfo(np.float64).eps
+    seen = set()
+    for m in (2 * b, 3 * b, 448):
+        bound = rb.cholqr2_cond_bound(m, b)
+        for seed in range(3):
+            for c in KAHAN_C:
+                p = rb.kahan_panel(m, b, c, dt, seed=seed)
+                path, why, orth = rb.blocked_panel_path(p)
+                seen.add(why)
+                cond = np.linalg.cond(p)
+                if path == "fallback":
+                    continue
+                assert cond <= bound, (m, b, seed, c, cond, bound, why, orth)
+                out, taus, t = rb.panel_reflectors_blocked(p.copy(), second_pass=(why == "two passes"))
+                v = rb.well_formed_v(out, b)
+                q = np.eye(m, dtype=dt) - v @ t @ v.conj().T
+                back = np.abs(q[:, :b] @ np.triu(out[:b, :]) - p).max() / np.abs(p).max()
+                orth_q = np.abs(q.conj().T @ q - np.eye(m)).max()
+                assert back <= 10 * m * eps and orth_q <= 10 * m * eps, (m, b, seed, c, cond, why, back, orth_q)
+    # the family reaches every exit the device has, apart from a failed second factorization
+    assert {"one pass", "two passes", "orth", "cholesky1"} <= seen or {"one pass", "two passes", "orth", "gate"} <= seen, seen
+
+
+def test_blocked_panel_path_keeps_random_panels():
+    """Panels of random matrices (condition numbers near 1) keep the blocked path, with one CholeskyQR pass, at the
+    shapes of the suite and of the benchmark's largest panel."""
+    rng = np.random.default_rng(11)
+    for dt in (np.float64, np.complex128):
+        for m, b in [(128, 64), (448, 64), (256, 128), (1920, 128), (20352, 128)]:
+            p = rng.uniform(-1, 1, (m, b))
+            if np.dtype(dt).kind == "c":
+                p = p + 1j * rng.uniform(-1, 1, (m, b))
+            path, why, orth = rb.blocked_panel_path(np.asfortranarray(p.astype(dt)))
+            assert path == "blocked" and orth < rb.hr_orth_fail_tol(m, b) / 10, (dt, m, b, why, orth)

@@ -89,7 +89,7 @@ int gen_to_std_device(DeviceMatrix<T>& A, DeviceMatrix<T>& L) {
 
   // One process: lookahead.  The chain diagonal tile -> panel of step k+1 runs on a side stream beside the trailing
   // update of step k, which takes column k+1 first and leaves `side_slots` workgroup slots free afterwards (the
-  // Cholesky's "sidecar" order, runtime.cpp).  On a grid everything stays on one stream (the single panel workspaces
+  // Cholesky's "sidecar" order, cholesky.cpp).  On a grid everything stays on one stream (the single panel workspaces
   // are reused step by step).  Measured on MI355X (tools/run_hegst.sh, profiles/r03_gen_to_std_lookahead_ab.txt): NO
   // gain -- fp64 N=16384 nb=512 44.8 (lookahead) vs 46.9 TFlop/s (one stream), N=32768 nb=1024 60.5 vs 61.3, z
   // N=16384 nb=512 53.4 vs 52.7: on 32 slots the chain (two single-tile solves, panel solve, hemm) takes about as

@@ -1,4 +1,5 @@
-// runtime.cpp -- device matrix, stream/event executor of the right-looking tile DAG, tile ops.
+// runtime.cpp -- device matrix, pool, transports, wait() and the blocking entry points, tile ops; the issue
+// order of a factorization is in cholesky.cpp.
 // See runtime.hpp for what each piece replaces in the reference.
 #include "runtime.hpp"
 
@@ -666,837 +667,6 @@ void DeviceMatrix<T>::prof_end(int kind, hipStream_t s, double flops, double byt
   p.bytes += bytes;
 }
 
-// ------------------------------------------------------------------------------- tile POTRF
-// Blocked lower Cholesky of one kb x kb tile (ld) with inner block 64: diagonal block kernel,
-// sub-panel solve (TRSM kernel, one column block), in-tile trailing update (update kernel).
-// winv receives the ceil(kb/64) inverted diagonal blocks.  Replaces rocsolver potrf
-// (lapack/tile.h:577-606).
-static bool potrf_use_chain() {
-  static const bool chain = [] {
-    const char* e = std::getenv("DLAF_MI355X_POTRF");
-    return e && std::strcmp(e, "chain") == 0;
-  }();
-  return chain;
-}
-
-template <class T>
-static void potrf_tile(T* t, int ld, int kb, T* winv, int* info, int info_base, unsigned* sync, hipStream_t s,
-                       bool sync_is_zero = false, bool count_strips = true) {
-  constexpr int JB = kDiagBlock;
-  if (!potrf_use_chain()) {
-    // one resident cooperative launch (kernels_potrf_coop.hip); DLAF_MI355X_POTRF=chain selects the
-    // multi-launch form below (diagonal block kernel + TRSM kernel + update kernel per 64 columns)
-    launch_potrf_coop(t, ld, kb, winv, info, info_base, sync, s, sync_is_zero, count_strips);
-    return;
-  }
-  for (int j0 = 0; j0 < kb; j0 += JB) {
-    const int jb = std::min(JB, kb - j0);
-    T* djj = t + j0 + (size_t) j0 * ld;
-    T* wj = winv + (size_t) (j0 / JB) * JB * JB;
-    launch_potrf_diag(djj, ld, jb, wj, info, info_base + j0, s);
-    const int rem = kb - j0 - jb;
-    if (rem <= 0)
-      break;
-    T* sub = t + (j0 + jb) + (size_t) j0 * ld;  // rem x jb panel below the diagonal block
-    TrsmArgs<T> ta;
-    ta.b = sub;
-    ta.b_ts = 0;
-    ta.ldb = ld;
-    ta.il0 = 0;
-    ta.il1 = 1;
-    ta.pr = 1;
-    ta.ri = 0;
-    ta.nb = rem;
-    ta.nt = 1;
-    ta.last_rows = rem;
-    ta.l = djj;
-    ta.ldl = ld;
-    ta.winv = wj;
-    ta.n = jb;
-    ta.info = info;
-    launch_trsm(ta, s);
-    UpdateArgs<T> ua;
-    ua.c = t + (j0 + jb) + (size_t) (j0 + jb) * ld;
-    ua.c_tsr = ua.c_tsc = 0;
-    ua.ldc = ld;
-    ua.a = sub;
-    ua.a_ts = 0;
-    ua.lda = ld;
-    ua.b = sub;
-    ua.b_ts = 0;
-    ua.ldb = ld;
-    ua.il0 = ua.jl0 = 0;
-    ua.il1 = ua.jl1 = 1;
-    ua.nb = rem;
-    ua.K = jb;
-    ua.pr = ua.pc = 1;
-    ua.ri = ua.ci = 0;
-    ua.nt = 1;
-    ua.last_rows = rem;
-    ua.info = info;
-    launch_update(ua, s, 2);
-  }
-}
-
-// ------------------------------------------------------------------------------- transposed panel
-static long gcd_l(long a, long b) {
-  while (b) {
-    const long t = a % b;
-    a = b;
-    b = t;
-  }
-  return a;
-}
-
-template <class T>
-int DeviceMatrix<T>::bcast_transposed_panel(Transport* tr, CommAxis ax_col, const T* a_base, long il_n, long jl_n,
-                                            T* dst, hipStream_t s, int& period, long& ts2) {
-  const size_t tile_bytes = tile_elems * sizeof(T);
-  const long ncols = ltc - jl_n;
-  // owner(global_of(jl)) repeats in jl with period lcm(Pr, Pc) / Pc = Pr / gcd(Pr, Pc)
-  const long g = gcd_l(rows.P, cols.P);
-  period = (int) (rows.P / g);
-  const long lstep = cols.P / g;  // local-row distance on the root between consecutive tiles of a class
-  const long cap = ncols > 0 ? (ncols + period - 1) / period : 0;
-  ts2 = cap * (long) tile_elems;
-  int issued = 0;
-  tr->group_begin();
-  for (long c = 0; c < period && c < ncols; ++c) {
-    const long jl_first = jl_n + c;
-    const long gj_first = cols.global_of(jl_first);
-    const int root_r = rows.owner(gj_first);
-    long cnt = (ncols - c + period - 1) / period;
-    if (cols.global_of(jl_first + (cnt - 1) * period) == nt - 1)
-      --cnt;
-    if (cnt <= 0)
-      continue;
-    T* d = dst + c * ts2;
-    if (rows.rank == root_r) {
-      const T* src = a_base + (size_t) (rows.local_of(gj_first) - il_n) * tile_elems;
-      DLAF_HIP_CHECK(hipMemcpy2DAsync(d, tile_bytes, src, (size_t) lstep * tile_bytes, tile_bytes, (size_t) cnt,
-                                      hipMemcpyDeviceToDevice, s));
-    }
-    tr->bcast(ax_col, root_r, rows.rank, d, d, (size_t) cnt * tile_bytes, s);
-    ++issued;
-  }
-  tr->group_end();
-  return issued;
-}
-
-// ------------------------------------------------------------------------------- the tile DAG
-// Right-looking Cholesky (cholesky/impl.h:150-189 local, :192-313 distributed) of the lower
-// triangle of the view.  Three in-order streams; events carry the RAW/WAR edges the reference gets
-// from per-tile async_rw_mutex.  U(k, J) = trailing update of tile columns J with panel k.
-//
-// "classic" schedule (one process):
-//
-//   s_main : U(k-1, col k) . U(k-1, rest_A) . TRSM(k) . U(k-1, rest_B) . U(k, col k+1) . U(k, rest_A) ...
-//   s_panel:                  POTRF(k)                                     POTRF(k+1)
-//
-// the narrow, latency-bound POTRF of the NEXT diagonal tile runs beside the first slice (rest_A) of the
-// current bulk update in workgroup slots that slice leaves free.  This is the reference's lookahead rule
-// (high priority for potrf/trsm and for trailing column k+1, impl.h:172-173 / :280-281) expressed as an
-// explicit order, because on this GPU a high-priority stream's kernels do not pre-empt the queued
-// workgroups of a running bulk kernel.
-//
-// "sidecar" schedule (one process, real types, nb <= 768, where a step's bulk is short and the serial TRSM
-// and the split of the bulk into two launches cost most): POTRF(k) AND TRSM(k) ride on s_panel beside the
-// WHOLE bulk update of step k-1, one persistent launch that leaves 32 workgroup slots free; the lookahead
-// column follows both:
-//
-//   s_main : U(k-1, rest) ................. U(k, col k+1) . U(k, rest) ...
-//   s_panel: POTRF(k) . TRSM(k)                              POTRF(k+1) . TRSM(k+1)
-//
-// "early diagonal" schedule (process grids; DLAF_MI355X_SCHEDULE=early|classic|sidecar overrides): with
-// broadcasts in the loop the per-step chain POTRF -> bcast -> TRSM -> bcast -> U(col k+1) -> POTRF is
-// what bounds a multi-GPU run, so the diagonal tile leaves that chain.  The lookahead is two columns
-// deep, the panel's first tile ("head": A(k+1,k), the only operand D(k+1) needs) is solved and
-// broadcast ahead of the rest, and D(k+1) is updated and factored on s_panel while the panel of step k
-// is still on the wire:
-//
-//   s_main : TRSMhead(k) . TRSMtail(k) . U(k-1, cols >= k+2) . U(k, cols {k+1,k+2} below D(k+1)) . TRSMhead(k+1) ...
-//   s_comm : [diag(k)]  head(k) . tail(k) . panelT(k)                                  [diag(k+1)] head(k+1) ...
-//   s_panel:             herk D(k+1) -= head head^H . POTRF(k+1)
-template <class T>
-void DeviceMatrix<T>::factorize_async() {
-  Transport* tr = grid_transport(*grid);
-  const bool dist = grid->nranks > 1;
-  if (dist && !tr)
-    fatal("[dlaf_mi355x] grid with %d ranks has no transport\n", grid->nranks);
-  const size_t tile_bytes = tile_elems * sizeof(T);
-  const int last_rows = rows.last_extent();
-  // uplo == 'U' runs on the transposed view: its process rows are the caller's process columns
-  const CommAxis ax_row = transposed ? CommAxis::Col : CommAxis::Row;
-  const CommAxis ax_col = transposed ? CommAxis::Row : CommAxis::Col;
-  hipStream_t s_main = s_low, s_panel = s_high;
-  const bool early = [&] {
-    if (const char* e = std::getenv("DLAF_MI355X_SCHEDULE"))
-      return std::strcmp(e, "early") == 0;
-    return dist;
-  }();
-  // one process only: POTRF(k) and TRSM(k) both ride on the panel stream beside the WHOLE bulk update of
-  // step k-1 (one persistent launch that leaves `sidecar_slots` workgroup slots free)
-  // Measured (one MI355X, fp64): nb=512 N=32768 48.6 -> 52.5 TFlop/s, nb=256 N=16384 27.6 -> 30.1, nb=768
-  // 47.6 -> 51.0; at nb=1024 the classic order with its tuned lookahead slice is 2 % faster, and for complex
-  // types (one TRSM workgroup per compute unit) it is 3 % faster at every size tried.
-  const bool sidecar = [&] {
-    if (const char* e = std::getenv("DLAF_MI355X_SCHEDULE"))
-      return std::strcmp(e, "sidecar") == 0 && !dist;
-    return !dist && !TypeInfo<T>::is_complex && nb <= 768;
-  }();
-  // one process: the bulk update takes the panels of TWO steps per pass (K = 2 nb): half the read-modify-write
-  // traffic of the trailing matrix, half the launches, half the per-block epilogues -- what a small block
-  // size loses against nb = 1024, and 1.5 % at nb = 1024 itself (DLAF_MI355X_SCHEDULE=pairs; default for one
-  // process; measured fp64: N=32768 nb=512 55.0 -> 57.2 TFlop/s, N=65536 nb=1024 64.9 -> 65.9; z N=32768 nb=512
-  // 57.3 -> 59.7)
-  const bool pairs = [&] {
-    if (const char* e = std::getenv("DLAF_MI355X_SCHEDULE"))
-      return std::strcmp(e, "pairs") == 0 && !dist;
-    return !dist && nb % 16 == 0;
-  }();
-  const long sidecar_slots = [&]() -> long {
-    if (const char* e = std::getenv("DLAF_MI355X_SIDECAR_SLOTS"))
-      return std::atol(e);
-    if (const char* e = std::getenv("DLAF_MI355X_SIDECAR_DEFAULT"))  // another starting value, the late boost stays on
-      return std::atol(e);
-    return 32;
-  }();
-
-  for (auto& ps : prof) {
-    ps.used = 0;
-    ps.flops = ps.bytes = ps.ms = 0;
-    ps.launches = 0;
-  }
-  DLAF_HIP_CHECK(hipMemsetAsync(info, 0, sizeof(int), s_panel));
-  DLAF_HIP_CHECK(hipMemsetAsync(coop_sync, 0, sizeof(unsigned) * coop_sync_words, s_panel));
-  if (unsigned long long* tb = potrf_coop_trace_buffer())
-    DLAF_HIP_CHECK(hipMemsetAsync(tb, 0, 32 * sizeof(unsigned long long), s_panel));
-  size_t next_update_slice = 0;
-  // DLAF_MI355X_SYNC_POOL=0: a fill kernel per launch instead (A/B)
-  const bool sync_pool = [] {
-    const char* e = std::getenv("DLAF_MI355X_SYNC_POOL");
-    return e == nullptr || std::atoi(e) != 0;
-  }();
-  DLAF_HIP_CHECK(hipEventRecord(ev_start[0], s_panel));
-  DLAF_HIP_CHECK(hipStreamWaitEvent(s_main, ev_start[0], 0));
-  DLAF_HIP_CHECK(hipStreamWaitEvent(s_comm, ev_start[0], 0));
-
-  // algorithmic work of one grouped update launch (BASELINE.md roofline table):
-  // gemm tile 2 m n k flop / (m k + n k + 2 m n) elements, herk tile n (n+1) k flop / (n k + n^2) elements
-  auto update_work = [&](long il0, long il1, long j0, long j1, int kb, double& flops, double& bytes) {
-    flops = bytes = 0;
-    const double cx = TypeInfo<T>::is_complex ? 4.0 : 1.0;
-    for (long jl = j0; jl < j1; ++jl) {
-      const long gj = cols.global_of(jl);
-      const double nj = rows.tile_extent(gj);
-      for (long il = std::max(il0, rows.next_local(gj)); il < il1; ++il) {
-        const long gi = rows.global_of(il);
-        const double mi = rows.tile_extent(gi);
-        if (gi == gj) {
-          flops += cx * mi * (mi + 1) * kb;
-          bytes += (mi * kb + mi * mi) * sizeof(T);
-        }
-        else {
-          flops += cx * 2.0 * mi * nj * kb;
-          bytes += (mi * kb + nj * kb + 2.0 * mi * nj) * sizeof(T);
-        }
-      }
-    }
-  };
-
-  // operands of step k's trailing update, kept until the update has been issued in full
-  struct Step {
-    const T* a_base = nullptr;  // column panel: tile of local row il at a_base + (il - il_n)*tile_elems
-    const T* b_base = nullptr;  // transposed panel: tile of local col jl at b_base + (jl - jl_n)*b_ts
-    long b_ts = 0, il_n = 0, jl_n = 0;
-    int b_period = 1;  // transposed panel grouped by root process row: see bcast_transposed_panel
-    long b_ts2 = 0;
-    // two panels applied in one pass (one process, "pairs" order): columns k1 .. kb-1 of the operands are
-    // the panel of the following step
-    const T* a2_base = nullptr;
-    const T* b2_base = nullptr;
-    int k1 = 0;
-    int kb = 0;
-    long rest0 = 0, split = 0;  // classic: rest_A = [rest0, split), rest_B = [split, ltc); early: rest = [rest0, ltc)
-    bool valid = false;
-  };
-
-  // Update of local tile columns [j0, j1), local tile rows [max(il_from, diagonal), il_to) with the
-  // panels of step `st`.  reserve: workgroup slots the launch must leave free (resident POTRF / RCCL
-  // kernels run beside it).  kind: profile class.
-  auto update = [&](const Step& st, long j0, long j1, hipStream_t s, int role, long reserve, long il_from = -1,
-                    long il_to = -1, int kind = -1) {
-    if (!st.valid || j0 >= j1)
-      return;
-    // rows that can hold tiles on/below the diagonal of column block j0
-    const long il0 = std::max(std::max(st.il_n, il_from), rows.next_local(cols.global_of(j0)));
-    const long il1 = il_to < 0 ? ltr : std::min(il_to, ltr);
-    if (il0 >= il1)
-      return;
-    UpdateArgs<T> ua;
-    ua.c = tiles;
-    ua.c_tsr = (long) tile_elems;
-    ua.c_tsc = (long) (tile_elems * ltr);
-    ua.ldc = nb;
-    ua.a = st.a_base + (size_t) (il0 - st.il_n) * tile_elems;
-    ua.a_ts = (long) tile_elems;
-    ua.lda = nb;
-    ua.b = st.b_base;
-    ua.b_ts = st.b_ts;
-    ua.b_period = st.b_period;
-    ua.b_ts2 = st.b_ts2;
-    ua.b_jl0 = (int) st.jl_n;
-    if (st.k1 > 0) {
-      ua.K1 = st.k1;
-      ua.a2 = st.a2_base + (size_t) (il0 - st.il_n) * tile_elems;
-      ua.b2 = st.b2_base;
-    }
-    ua.ldb = nb;
-    ua.il0 = (int) il0;
-    ua.il1 = (int) il1;
-    ua.jl0 = (int) j0;
-    ua.jl1 = (int) j1;
-    ua.nb = nb;
-    ua.K = st.kb;
-    ua.pr = rows.P;
-    ua.ri = rows.shift();
-    ua.pc = cols.P;
-    ua.ci = cols.shift();
-    ua.nt = (int) nt;
-    ua.last_rows = last_rows;
-    ua.info = info;
-    double fl, by;
-    update_work(il0, il1, j0, j1, st.kb, fl, by);
-    const int pk = kind < 0 ? role : kind;
-    prof_begin(pk, s);
-    // (persistent launches only: each takes the next pre-zeroed slice; past the end of the pool -- never with the
-    // schedules below -- the last slice is re-zeroed per launch)
-    unsigned* cnt = coop_sync;
-    bool zero = false;
-    if (reserve > 0) {
-      const size_t sl = std::min(next_update_slice, coop_sync_update_slices - 1);
-      cnt = coop_sync + 16 * sl;
-      zero = sync_pool && next_update_slice < coop_sync_update_slices - 1;
-      ++next_update_slice;
-    }
-    // Reservations that are whole rounds over the shader engines (multiples of 64 slots on MI355X: the grid orders
-    // with a device-side transport at nb = 1024, the widened reservations near the end of the pairs order) are made
-    // as EXCLUSIVE compute units: the launch covers every slot and the workgroups that land on a reserved compute
-    // unit leave (kernels_update.hip), so the tile POTRF beside it runs at its stand-alone speed (0.87 instead of
-    // 2.3 ms per 1024-tile).  The others -- the 32 slots of the one-process orders, where 64 would cost the bulk
-    // launch 7 % -- stay free slots.  DLAF_MI355X_EXCLUSIVE_CUS=0: free slots always.
-    static const bool exclusive = [] {
-      const char* e = std::getenv("DLAF_MI355X_EXCLUSIVE_CUS");
-      return e ? std::atoi(e) != 0 : true;
-    }();
-    if (reserve > 0 && exclusive)
-      launch_update(ua, s, role, bulk_slots, cnt, zero, reserve);
-    else
-      launch_update(ua, s, role, reserve > 0 ? std::max<long>(8, bulk_slots - reserve) : 0, cnt, zero);
-    DLAF_HIP_CHECK(hipGetLastError());
-    prof_end(pk, s, fl, by);
-  };
-
-  // panel TRSM of local tile rows [il0, il1) of local tile column klc with the factored diagonal tile
-  auto trsm = [&](long il0, long il1, long klc, const T* Lkk, const T* Wkk, int kb, hipStream_t ts = nullptr) {
-    if (ts == nullptr)
-      ts = s_main;
-    if (il0 >= il1)
-      return;
-    TrsmArgs<T> ta;
-    ta.b = tile(il0, klc);
-    ta.b_ts = (long) tile_elems;
-    ta.ldb = nb;
-    ta.il0 = (int) il0;
-    ta.il1 = (int) il1;
-    ta.pr = rows.P;
-    ta.ri = rows.shift();
-    ta.nb = nb;
-    ta.nt = (int) nt;
-    ta.last_rows = last_rows;
-    ta.l = Lkk;
-    ta.ldl = nb;
-    ta.winv = Wkk;
-    ta.n = kb;
-    ta.info = info;
-    // on the side stream the solve runs beside the bulk update and every later step waits for it
-    static const int trsm_prio = [] {
-      const char* e = std::getenv("DLAF_MI355X_TRSM_PRIO");
-      return e ? std::atoi(e) : 1;
-    }();
-    ta.prio = (ts != s_main) ? trsm_prio : 0;
-    // algorithmic work: n^2 m flop and (n^2/2 + 2 m n) elements per tile
-    double fl = 0, by = 0;
-    for (long il = il0; il < il1; ++il) {
-      const double mi = rows.tile_extent(rows.global_of(il));
-      fl += (TypeInfo<T>::is_complex ? 4.0 : 1.0) * (double) kb * kb * mi;
-      by += (0.5 * kb * kb + 2.0 * mi * kb) * sizeof(T);
-    }
-    prof_begin(2, ts);
-    launch_trsm(ta, ts);
-    DLAF_HIP_CHECK(hipGetLastError());
-    prof_end(2, ts, fl, by);
-  };
-
-  // diagonal tile k on its owner (s_panel); the inverted diagonal blocks alternate between two buffers
-  // because POTRF(k+1) may run while TRSM(k) still reads those of step k
-  auto winv_of = [&](long k) { return winv + (size_t) (k & 1) * winv_elems(); };
-  auto diag_ws_of = [&](long k) { return diag_ws + (size_t) (k & 1) * (tile_elems + winv_elems()); };
-  auto potrf = [&](long k) {
-    if (rows.rank != rows.owner(k) || cols.rank != cols.owner(k))
-      return;
-    const int kb = rows.tile_extent(k);
-    const double cxf = TypeInfo<T>::is_complex ? 4.0 : 1.0;
-    prof_begin(3, s_panel);
-    potrf_tile(tile(rows.local_of(k), cols.local_of(k)), nb, kb, winv_of(k), info, (int) (k * nb),
-               coop_sync + 16 * coop_sync_update_slices + coop_sync_potrf_words * (size_t) k, s_panel, sync_pool,
-               /* the strips register for the POTRF yield, on one process and on grids */ true);
-    DLAF_HIP_CHECK(hipGetLastError());  // (a launch that did not happen leaves winv unwritten and info 0)
-    prof_end(3, s_panel, cxf * (double) kb * kb * kb / 3.0, (double) kb * kb * sizeof(T));
-  };
-
-  // after POTRF(k) on s_panel: the factored tile and its inverse blocks travel down the owning process
-  // column; returns through Lkk / Wkk what TRSM(k) reads and records ev_diag[k] when that is ready
-  auto diag_bcast = [&](long k, bool in_row, bool in_col, const T*& Lkk, const T*& Wkk) {
-    Lkk = Wkk = nullptr;
-    if (in_row && in_col) {
-      Lkk = tile(rows.local_of(k), cols.local_of(k));
-      Wkk = winv_of(k);
-    }
-    if (in_col && rows.P > 1) {
-      T* ws = diag_ws_of(k);
-      if (in_row) {
-        DLAF_HIP_CHECK(hipMemcpyAsync(ws, Lkk, tile_bytes, hipMemcpyDeviceToDevice, s_panel));
-        DLAF_HIP_CHECK(hipMemcpyAsync(ws + tile_elems, Wkk, winv_elems() * sizeof(T), hipMemcpyDeviceToDevice, s_panel));
-      }
-      DLAF_HIP_CHECK(hipEventRecord(ev_diag[k], s_panel));
-      DLAF_HIP_CHECK(hipStreamWaitEvent(s_comm, ev_diag[k], 0));
-      tr->bcast(ax_col, rows.owner(k), rows.rank, ws, ws, tile_bytes + winv_elems() * sizeof(T), s_comm);
-      DLAF_HIP_CHECK(hipEventRecord(ev_diag[k], s_comm));
-      Lkk = ws;
-      Wkk = ws + tile_elems;
-    }
-    else {
-      DLAF_HIP_CHECK(hipEventRecord(ev_diag[k], s_panel));
-    }
-  };
-
-  // transposed panel of step k down the process columns (after the row broadcast), or the view of the
-  // column panel that plays its role when this process holds every row
-  auto transposed_panel = [&](long k, Step& cur, int buf) {
-    if (rows.P > 1) {
-      bcast_transposed_panel(tr, ax_col, cur.a_base, cur.il_n, cur.jl_n, panelT[buf], s_comm, cur.b_period, cur.b_ts2);
-      cur.b_base = panelT[buf];
-      cur.b_ts = (long) tile_elems;
-    }
-    else {
-      // I hold every row of the panel: tile gj sits at local row gj
-      cur.b_base = cur.a_base + (cols.global_of(cur.jl_n) - cur.il_n) * (long) tile_elems;
-      cur.b_ts = (long) tile_elems * cols.P;
-    }
-    (void) k;
-  };
-
-  // Workgroup slots kept free by the bulk launches for the cooperative POTRF of the next diagonal tile
-  // (one workgroup per 64 rows) and for the RCCL broadcast kernels of the step.
-  const long potrf_slots = [&]() -> long {
-    if (const char* e = std::getenv("DLAF_MI355X_POTRF_SLOTS"))
-      return std::atol(e);
-    return potrf_use_chain() ? 0 : 2 * ((nb + kDiagBlock - 1) / kDiagBlock);
-  }();
-  const long comm_slots = [&]() -> long {
-    if (const char* e = std::getenv("DLAF_MI355X_COMM_SLOTS"))
-      return std::atol(e);
-    return (dist && tr->device_side()) ? 32 : 0;
-  }();
-
-  // early-diagonal order: what the bulk leaves to the tile POTRF and the transport's kernels (a whole round over the
-  // shader engines -- 64 slots: nb = 1024 with a device-side transport -- is made as exclusive compute units, see
-  // `update` above; otherwise the strips share compute units and the bulk workgroups beside them sit out)
-  const long grid_reserve = potrf_slots + comm_slots;
-
-  Step prev;  // step k-1, whose bulk update is still to be issued (in part or in full)
-
-  if (pairs) {
-    // s_main : LA(p-1) . restA(p-1) ........ U1(k -> col k+1) . restB(p-1) ................. LA(p) . restA(p) ...
-    // s_panel:           POTRF(k) . TRSM(k) ^                    POTRF(k+1) . TRSM(k+1) ^
-    // pair p = steps (k, k+1); LA(p) = the two-panel update of tile columns k+2, k+3 (what the next pair's panels
-    // need), rest(p) = columns >= k+4 in two persistent launches that leave `sidecar_slots` free for the panel
-    // kernels beside them, U1 = column k+1 under panel k alone on s_main between the two.
-    auto single = [&](long k) {  // the one-panel step of step k (operands of U1)
-      Step st;
-      st.valid = true;
-      st.kb = rows.tile_extent(k);
-      st.il_n = st.jl_n = k + 1;
-      st.a_base = tile(k + 1 < ltr ? k + 1 : 0, k);
-      st.b_base = st.a_base;
-      st.b_ts = (long) tile_elems;
-      return st;
-    };
-    // Workgroup slots rest(p-1) leaves free for the panel work of pair p running beside it.  32 (the POTRF's
-    // strips plus a few TRSM workgroups) is the measured optimum while the bulk outlasts the panel chain (16 ->
-    // 65.5, 32 -> 67.4, 48 -> 66.8 TFlop/s at N=65536 nb=1024).  Towards the end of the factorization the bulk
-    // of a pair is shorter than the chain 2 POTRF + 2 TRSM beside it; there the reservation grows until the two
-    // balance (the TRSM's throughput is proportional to the slots it finds).  Rates: in-situ measurements on
-    // MI355X.  DLAF_MI355X_SIDECAR_SLOTS fixes the reservation, DLAF_MI355X_LATE_BOOST=0 keeps it at its default.
-    const bool slots_fixed = std::getenv("DLAF_MI355X_SIDECAR_SLOTS") != nullptr ||
-                             (std::getenv("DLAF_MI355X_LATE_BOOST") && std::atoi(std::getenv("DLAF_MI355X_LATE_BOOST")) == 0);
-    // one rate table for both placement decisions below (in-situ measurements on MI355X): the bulk
-    // update, the panel TRSM per free slot beside it, the tile POTRF per (64-column block)^2 beside it
-    const bool cxt = TypeInfo<T>::is_complex, dbl = sizeof(real_t<T>) == 8;
-    const double r_bulk = dbl ? 66e12 : 118e12;
-    const double r_trsm_slot = (dbl ? 5e12 : 8e12) / 32.0;
-    const double t_potrf_blk2 = 11.3e-6 * (cxt ? 2.0 : 1.0);  // 2.9 ms per real 1024-tile
-    auto pair_slots = [&](long k, const Step& bulk) -> long {
-      if (slots_fixed || !bulk.valid || bulk.rest0 >= ltc)
-        return sidecar_slots;
-      double fl_b = 0, by;
-      for (long jl = bulk.rest0; jl < ltc; ++jl) {
-        double f;
-        update_work(std::max(bulk.il_n, rows.next_local(cols.global_of(jl))), ltr, jl, jl + 1, bulk.kb, f, by);
-        fl_b += f;
-      }
-      const double cxf = cxt ? 4.0 : 1.0;
-      const double below = (double) std::max<long>(0, n - (k + 1) * (long) nb) + (double) std::max<long>(0, n - (k + 2) * (long) nb);
-      const double fl_t = cxf * (double) nb * nb * below;
-      const double nblk = (double) nb / kDiagBlock;
-      const double t_potrf = 2.0 * nblk * nblk * t_potrf_blk2;
-      auto t_of = [&](long sl) {
-        const double share = (double) sl / (double) bulk_slots;
-        return std::max(fl_b / (r_bulk * (1.0 - share)), t_potrf + fl_t / (r_trsm_slot * (double) sl));
-      };
-      long best = sidecar_slots;
-      double best_t = t_of(best);
-      if (fl_b / (r_bulk * (1.0 - (double) best / (double) bulk_slots)) >= best_t)
-        return best;  // the bulk is the longer of the two: nothing to gain
-      for (long cand : {48L, 64L, 96L, 128L, 192L, 256L}) {
-        if (cand <= sidecar_slots || cand * 2 > bulk_slots)
-          continue;
-        const double t = t_of(cand);
-        if (t < best_t) {
-          best_t = t;
-          best = cand;
-        }
-      }
-      return best;
-    };
-    // share of rest(p-1) issued BEFORE U1 on s_main (it runs beside POTRF(k) + TRSM(k))
-    const double split_frac = [&] {
-      if (const char* e = std::getenv("DLAF_MI355X_PAIR_SPLIT"))
-        return std::atof(e);
-      return 0.3;
-    }();
-    for (long k = 0; k < nt; k += 2) {
-      if (tr)
-        tr->mark(k);
-      if (k >= 2)
-        DLAF_HIP_CHECK(hipStreamWaitEvent(s_panel, ev_high[k - 2], 0));  // LA(p-1): columns k, k+1 are final
-      potrf(k);
-      const bool second = k + 1 < nt;       // the pair has a second step
-      const bool more = k + 2 < nt;         // something trails the pair
-      if (second) {
-        trsm(k + 1, ltr, k, tile(k, k), winv_of(k), rows.tile_extent(k), s_panel);
-        DLAF_HIP_CHECK(hipEventRecord(ev_panel[k], s_panel));
-        panels_issued.store(k, std::memory_order_release);
-      }
-      // U1 (column k+1 under panel k) is on the chain POTRF(k) . TRSM(k) . U1 . POTRF(k+1) . TRSM(k+1).  Two places
-      // for it: (a) on s_panel beside the bulk, on the few slots the bulk leaves free -- ~16 ms instead of 1 ms at
-      // N=65536 nb=1024, harmless while the bulk of the pair outlasts the chain anyway; (b) alone on s_main between
-      // two halves of the bulk -- the chain shrinks to what the GPU can do, at the price of a second ramp-down of
-      // the persistent bulk launch.  (a) while the bulk is the longer of the two, (b) towards the end.
-      long splitA = prev.rest0;
-      const long slots = pair_slots(k, prev);
-      bool u1_on_main = false;
-      if (prev.valid && prev.rest0 < ltc && second) {
-        double total = 0, by;
-        std::vector<double> colfl((size_t) (ltc - prev.rest0));
-        for (long jl = prev.rest0; jl < ltc; ++jl) {
-          double f;
-          update_work(std::max(prev.il_n, rows.next_local(cols.global_of(jl))), ltr, jl, jl + 1, prev.kb, f, by);
-          colfl[(size_t) (jl - prev.rest0)] = f;
-          total += f;
-        }
-        const double cxf = TypeInfo<T>::is_complex ? 4.0 : 1.0;
-        const double below1 = (double) std::max<long>(0, n - (k + 1) * (long) nb), below2 = (double) std::max<long>(0, n - (k + 2) * (long) nb);
-        const double fl_chain = cxf * (double) nb * nb * (below1 + below2) + cxf * 2.0 * (double) nb * nb * below1;  // 2 TRSM + U1
-        const double nblk = (double) nb / kDiagBlock;
-        const double t_chain = 2.0 * nblk * nblk * t_potrf_blk2 + fl_chain / (r_trsm_slot * (double) slots);
-        const double t_bulk = total / (r_bulk * (1.0 - (double) slots / (double) bulk_slots));
-        const char* force = std::getenv("DLAF_MI355X_U1");  // "main" / "panel": fix the placement
-        u1_on_main = force ? std::strcmp(force, "main") == 0 : t_bulk < t_chain;
-        if (u1_on_main) {
-          double acc = 0;
-          while (splitA < ltc && acc < split_frac * total)
-            acc += colfl[(size_t) (splitA++ - prev.rest0)];
-        }
-      }
-      else if (second && !(prev.valid && prev.rest0 < ltc)) {
-        u1_on_main = true;  // nothing to run beside: plain sequence
-      }
-      if (!u1_on_main)
-        splitA = prev.rest0;  // the whole bulk in one launch, below
-      update(prev, prev.rest0, splitA, s_main, 0, slots);
-      if (second) {
-        if (u1_on_main) {
-          DLAF_HIP_CHECK(hipStreamWaitEvent(s_main, ev_panel[k], 0));
-          update(single(k), k + 1, k + 2, s_main, 1, 0);
-          DLAF_HIP_CHECK(hipEventRecord(ev_head[k], s_main));
-          DLAF_HIP_CHECK(hipStreamWaitEvent(s_panel, ev_head[k], 0));
-        }
-        else {
-          update(single(k), k + 1, k + 2, s_panel, 1, 0);
-        }
-        potrf(k + 1);
-        if (more) {
-          trsm(k + 2, ltr, k + 1, tile(k + 1, k + 1), winv_of(k + 1), rows.tile_extent(k + 1), s_panel);
-          DLAF_HIP_CHECK(hipEventRecord(ev_panel[k + 1], s_panel));
-          panels_issued.store(k + 1, std::memory_order_release);
-        }
-      }
-      update(prev, splitA, ltc, s_main, 0, slots);
-      prev.valid = false;
-      if (!more) {
-        DLAF_HIP_CHECK(hipEventRecord(ev_diag[k], s_panel));
-        DLAF_HIP_CHECK(hipStreamWaitEvent(s_main, ev_diag[k], 0));
-        break;
-      }
-      DLAF_HIP_CHECK(hipStreamWaitEvent(s_main, ev_panel[k + 1], 0));
-      Step cur;
-      cur.valid = true;
-      cur.il_n = cur.jl_n = k + 2;
-      cur.k1 = rows.tile_extent(k);
-      cur.kb = cur.k1 + rows.tile_extent(k + 1);
-      cur.a_base = tile(k + 2, k);
-      cur.a2_base = tile(k + 2, k + 1);
-      cur.b_base = cur.a_base;
-      cur.b2_base = cur.a2_base;
-      cur.b_ts = (long) tile_elems;
-      update(cur, k + 2, std::min<long>(k + 4, ltc), s_main, 1, 0);
-      DLAF_HIP_CHECK(hipEventRecord(ev_high[k], s_main));
-      cur.rest0 = std::min<long>(k + 4, ltc);
-      prev = cur;
-    }
-  }
-  else if (sidecar) {
-    for (long k = 0; k < nt; ++k) {
-      const int kb = rows.tile_extent(k);
-      if (tr)
-        tr->mark(k);
-      const long il_n = rows.next_local(k + 1), jl_n = cols.next_local(k + 1);
-      const long klc = cols.local_of(k);
-      if (k >= 1)
-        DLAF_HIP_CHECK(hipStreamWaitEvent(s_panel, ev_high[k - 1], 0));
-      potrf(k);
-      if (k == nt - 1) {
-        update(prev, prev.rest0, ltc, s_main, 0, sidecar_slots);
-        DLAF_HIP_CHECK(hipEventRecord(ev_diag[k], s_panel));
-        DLAF_HIP_CHECK(hipStreamWaitEvent(s_main, ev_diag[k], 0));
-        break;
-      }
-      trsm(il_n, ltr, klc, tile(rows.local_of(k), klc), winv_of(k), kb, s_panel);
-      DLAF_HIP_CHECK(hipEventRecord(ev_panel[k], s_panel));
-      panels_issued.store(k, std::memory_order_release);
-      // the whole bulk of step k-1 beside them
-      update(prev, prev.rest0, ltc, s_main, 0, sidecar_slots);
-      DLAF_HIP_CHECK(hipStreamWaitEvent(s_main, ev_panel[k], 0));
-      Step cur;
-      cur.valid = true;
-      cur.kb = kb;
-      cur.il_n = il_n;
-      cur.jl_n = jl_n;
-      cur.a_base = tile(il_n < ltr ? il_n : 0, klc);
-      cur.b_base = cur.a_base + (cols.global_of(jl_n) - il_n) * (long) tile_elems;
-      cur.b_ts = (long) tile_elems * cols.P;
-      cur.rest0 = jl_n;
-      if (jl_n < ltc) {
-        update(cur, jl_n, jl_n + 1, s_main, 1, 0);
-        cur.rest0 = jl_n + 1;
-      }
-      DLAF_HIP_CHECK(hipEventRecord(ev_high[k], s_main));
-      prev = cur;
-    }
-  }
-  else if (early) {
-    potrf(0);
-    for (long k = 0; k < nt; ++k) {
-      const int kb = rows.tile_extent(k);
-      if (tr)
-        tr->mark(k);
-      const int own_c = cols.owner(k);
-      const bool in_row = rows.rank == rows.owner(k), in_col = cols.rank == own_c;
-      const long il_n = rows.next_local(k + 1), jl_n = cols.next_local(k + 1);
-      const int buf = (int) (k & 1);
-      const long klc = in_col ? cols.local_of(k) : -1;
-      if (k == nt - 1) {
-        update(prev, prev.rest0, ltc, s_main, 0, 0);  // (empty: nothing lies right of column nt-1)
-        DLAF_HIP_CHECK(hipEventRecord(ev_diag[k], s_panel));
-        DLAF_HIP_CHECK(hipStreamWaitEvent(s_main, ev_diag[k], 0));
-        break;
-      }
-      const T *Lkk, *Wkk;
-      diag_bcast(k, in_row, in_col, Lkk, Wkk);
-
-      // ---- s_main: the head tile A(k+1,k) first, then the rest of the panel -------------------------
-      // the head lives in process row owner(k+1), where it is the first local row below the diagonal
-      const bool head_row = rows.rank == rows.owner(k + 1);
-      const long il_t = il_n + (head_row ? 1 : 0);  // first local row of the tail
-      DLAF_HIP_CHECK(hipStreamWaitEvent(s_main, ev_diag[k], 0));
-      if (in_col && head_row)
-        trsm(il_n, il_n + 1, klc, Lkk, Wkk, kb);
-      DLAF_HIP_CHECK(hipEventRecord(ev_head[k], s_main));
-      if (in_col)
-        trsm(il_t, ltr, klc, Lkk, Wkk, kb);
-      DLAF_HIP_CHECK(hipEventRecord(ev_panel[k], s_main));
-      panels_issued.store(k, std::memory_order_release);
-
-      // ---- s_comm: head, tail along process rows; transposed panel along process columns -----------
-      Step cur;
-      cur.valid = true;
-      cur.kb = kb;
-      cur.il_n = il_n;
-      cur.jl_n = jl_n;
-      cur.b_ts = (long) tile_elems;
-      // the workspace of step k-2 is free: its readers are behind TRSM(k) on s_main (ev_head[k])
-      T* dst = in_col ? tile(il_n < ltr ? il_n : 0, klc) : panel[buf];
-      cur.a_base = dst;
-      if (dist)
-        DLAF_HIP_CHECK(hipStreamWaitEvent(s_comm, ev_head[k], 0));
-      if (cols.P > 1 && head_row)
-        tr->bcast(ax_row, own_c, cols.rank, dst, dst, tile_bytes, s_comm);
-      if (dist)
-        DLAF_HIP_CHECK(hipEventRecord(ev_headb[k], s_comm));
-
-      // ---- s_panel: D(k+1) -= head head^H, POTRF(k+1) -------------------------------------------------
-      // (every earlier update of D(k+1) is in the two-column lookahead of step k-1: ev_high[k-1])
-      if (head_row && cols.rank == cols.owner(k + 1)) {
-        if (k >= 1)
-          DLAF_HIP_CHECK(hipStreamWaitEvent(s_panel, ev_high[k - 1], 0));
-        DLAF_HIP_CHECK(hipStreamWaitEvent(s_panel, (dist && cols.P > 1) ? ev_headb[k] : ev_head[k], 0));
-        Step head = cur;
-        head.b_base = cur.a_base;  // the herk tile takes both operands from the column panel
-        update(head, jl_n, jl_n + 1, s_panel, 2, 0, il_n, il_n + 1, 3);
-        potrf(k + 1);
-      }
-
-      if (dist)
-        DLAF_HIP_CHECK(hipStreamWaitEvent(s_comm, ev_panel[k], 0));
-      if (cols.P > 1 && il_t < ltr)
-        tr->bcast(ax_row, own_c, cols.rank, dst + (size_t) (il_t - il_n) * tile_elems,
-                  dst + (size_t) (il_t - il_n) * tile_elems, (size_t) (ltr - il_t) * tile_bytes, s_comm);
-      transposed_panel(k, cur, buf);
-      if (dist)
-        DLAF_HIP_CHECK(hipEventRecord(ev_bcast[k], s_comm));
-
-      // ---- s_main: bulk of step k-1 beside the broadcasts of step k and POTRF(k+1) -----------------
-      update(prev, prev.rest0, ltc, s_main, 0, grid_reserve);
-      if (dist)
-        DLAF_HIP_CHECK(hipStreamWaitEvent(s_main, ev_bcast[k], 0));
-
-      // ---- s_main: two-column lookahead of step k (D(k+1) itself is on s_panel) ----------------------
-      cur.rest0 = cols.next_local(k + 3);
-      update(cur, jl_n, cur.rest0, s_main, 1, 0, rows.next_local(k + 2));
-      DLAF_HIP_CHECK(hipEventRecord(ev_high[k], s_main));
-      prev = cur;
-    }
-  }
-  else {
-    // rest_A must last as long as the POTRF of the next diagonal tile takes BESIDE it: nb/64 dependent
-    // sub-steps of ~90 us alone, 2-3x that under the bulk kernel's memory traffic (measured at nb = 1024:
-    // 1.1 ms alone, 2.2-3.4 ms beside rest_A; the whole factorization is fastest with rest_A ~ 4 ms)
-    const double lookahead_flops = [&] {
-      if (const char* e = std::getenv("DLAF_MI355X_LOOKAHEAD_FLOPS"))
-        return std::atof(e);
-      return 270e-6 * ((double) nb / kDiagBlock) * 55e12;
-    }();
-    for (long k = 0; k < nt; ++k) {
-      const int kb = rows.tile_extent(k);
-      if (tr)
-        tr->mark(k);
-      const int own_c = cols.owner(k);
-      const bool in_row = rows.rank == rows.owner(k), in_col = cols.rank == own_c;
-      const long il_n = rows.next_local(k + 1), jl_n = cols.next_local(k + 1);
-      const int buf = (int) (k & 1);
-      const long klc = in_col ? cols.local_of(k) : -1;
-
-      // ---- s_panel: diagonal tile (column k is final once U(k-1, col k) has run: ev_high[k-1]) -------
-      if (k >= 1)
-        DLAF_HIP_CHECK(hipStreamWaitEvent(s_panel, ev_high[k - 1], 0));
-      potrf(k);
-      if (k == nt - 1) {
-        // nothing trails the last diagonal tile; flush what is left of step k-1
-        update(prev, prev.rest0, prev.split, s_main, 0, potrf_slots);
-        update(prev, prev.split, ltc, s_main, 0, comm_slots);
-        prev.valid = false;
-        DLAF_HIP_CHECK(hipEventRecord(ev_diag[k], s_panel));
-        DLAF_HIP_CHECK(hipStreamWaitEvent(s_main, ev_diag[k], 0));
-        break;
-      }
-      const T *Lkk, *Wkk;
-      diag_bcast(k, in_row, in_col, Lkk, Wkk);
-
-      // ---- s_main: first slice of the previous step's bulk update runs beside the POTRF -------------
-      update(prev, prev.rest0, prev.split, s_main, 0, potrf_slots);
-
-      // ---- s_main: panel TRSM --------------------------------------------------------------------------
-      DLAF_HIP_CHECK(hipStreamWaitEvent(s_main, ev_diag[k], 0));
-      if (in_col)
-        trsm(il_n, ltr, klc, Lkk, Wkk, kb);
-      DLAF_HIP_CHECK(hipEventRecord(ev_panel[k], s_main));
-      panels_issued.store(k, std::memory_order_release);
-
-      // ---- s_comm: panel along process rows, transposed panel along process columns ----------------
-      Step cur;
-      cur.valid = true;
-      cur.kb = kb;
-      cur.il_n = il_n;
-      cur.jl_n = jl_n;
-      cur.b_ts = (long) tile_elems;
-      if (dist)
-        DLAF_HIP_CHECK(hipStreamWaitEvent(s_comm, ev_panel[k], 0));
-      if (cols.P > 1) {
-        // the workspace of step k-2 is free: its readers are behind TRSM(k) on s_main (ev_panel[k])
-        T* dst = in_col ? tile(il_n < ltr ? il_n : 0, klc) : panel[buf];
-        if (il_n < ltr)
-          tr->bcast(ax_row, own_c, cols.rank, dst, dst, (size_t) (ltr - il_n) * tile_bytes, s_comm);
-        cur.a_base = dst;
-      }
-      else {
-        cur.a_base = tile(il_n < ltr ? il_n : 0, klc);
-      }
-      transposed_panel(k, cur, buf);
-      if (dist)
-        DLAF_HIP_CHECK(hipEventRecord(ev_bcast[k], s_comm));
-
-      // ---- s_main: rest of step k-1 (the broadcasts of step k fly underneath) -------------------------
-      update(prev, prev.split, ltc, s_main, 0, comm_slots);
-      if (dist)
-        DLAF_HIP_CHECK(hipStreamWaitEvent(s_main, ev_bcast[k], 0));
-
-      // ---- s_main: lookahead column of step k, then split the rest ----------------------------------
-      cur.rest0 = jl_n;
-      if (cols.mine(k + 1) && jl_n < ltc) {
-        update(cur, jl_n, jl_n + 1, s_main, 1, 0);
-        cur.rest0 = jl_n + 1;
-      }
-      DLAF_HIP_CHECK(hipEventRecord(ev_high[k], s_main));
-      cur.split = cur.rest0;
-      {
-        double acc = 0;
-        while (cur.split < ltc && acc < lookahead_flops) {
-          double fl, by;
-          update_work(std::max(il_n, rows.next_local(cols.global_of(cur.split))), ltr, cur.split, cur.split + 1, kb, fl, by);
-          acc += fl;
-          ++cur.split;
-        }
-      }
-      prev = cur;
-    }
-  }
-  DLAF_HIP_CHECK(hipEventRecord(ev_done[0], s_main));
-  DLAF_HIP_CHECK(hipStreamWaitEvent(s_panel, ev_done[0], 0));
-  DLAF_HIP_CHECK(hipMemcpyAsync(info_host, info, sizeof(int), hipMemcpyDeviceToHost, s_panel));
-}
-
 // ------------------------------------------------------------------------------- grid self-test
 int grid_selftest(Grid& g, size_t bytes) {
   runtime_init();
@@ -1907,6 +1077,7 @@ int tile_potrf(char uplo, int n, T* a, int lda) {
   DevBuf<int> info(1);
   DevBuf<unsigned> sync(potrf_coop_sync_words(n));
   DLAF_HIP_CHECK(hipMemsetAsync(info.p, 0, sizeof(int), s));
+  DLAF_HIP_CHECK(hipMemsetAsync(sync.p, 0, sizeof(unsigned) * potrf_coop_sync_words(n), s));
   // tmp keeps the caller's image (host orientation); da the device orientation
   DLAF_HIP_CHECK(hipMemcpy2DAsync(tmp.p, (size_t) n * sizeof(T), a, (size_t) lda * sizeof(T), (size_t) n * sizeof(T),
                                   (size_t) n, hipMemcpyHostToDevice, s));

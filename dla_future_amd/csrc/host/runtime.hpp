@@ -222,6 +222,11 @@ struct DeviceMatrix : MatrixBase {
   double trsm_profile(int reps, double* flops, double* bytes);
 };
 
+// Lower Cholesky of one kb x kb diagonal tile (ld) on stream s, with its ceil(kb/64) inverted 64 x 64 diagonal blocks in
+// winv (cholesky.cpp).  sync: potrf_coop_sync_words(kb) words the caller has zeroed on the stream.
+template <class T>
+void potrf_tile(T* t, int ld, int kb, T* winv, int* info, int info_base, unsigned* sync, hipStream_t s);
+
 // single-tile operations with host operands (tests of the tile kernels through the C ABI)
 template <class T>
 int tile_potrf(char uplo, int n, T* a, int lda);

@@ -221,7 +221,7 @@ def main():
         # DLAF_MI355X_COMM_SLOTS) forced onto this host-side one -- the path the first real 2 x 4 RCCL run takes
         # (replaces cholesky/impl.h:223-304) -- at a size whose bulk launches have more work items than the GPU has
         # workgroup slots, so that they really run in persistent form: POTRF strips (2 x 128 / 64 = 4 slots) + 60 = one
-        # whole round over the shader engines -> EXCLUSIVE compute units (runtime.cpp `update`), + 28 = 32 -> free slots.
+        # whole round over the shader engines -> EXCLUSIVE compute units (cholesky.cpp `update`), + 28 = 32 -> free slots.
         # Checked like the miniapp (residual on the device, MAX over the grid) and by the identical-sequence property
         # of the communicators.
         # (the grids with four and six ranks the host-staged transport runs on: 2 x 2 and 2 x 3)

@@ -43,7 +43,7 @@ def test_cholesky_local_analytic(dlaf, grid, oracle, t, uplo):
 
 @pytest.fixture(params=["classic", "early", "sidecar", "pairs"])
 def schedule(request, monkeypatch):
-    """The issue orders of the tile DAG (runtime.cpp: classic / pairs = one-process defaults for large /
+    """The issue orders of the tile DAG (cholesky.cpp: classic / pairs = one-process defaults for large /
     small blocks, sidecar = the round-1 small-block order, early diagonal = process-grid default);
     DLAF_MI355X_SCHEDULE is read at every factorization."""
     monkeypatch.setenv("DLAF_MI355X_SCHEDULE", request.param)

@@ -22,7 +22,5 @@ for cfg in "c2|--steps 3 --warmup 1" "c1|--n 32768 --nb 512 --steps 5 --warmup 1
   tag=${cfg%%|*}; BARGS=${cfg#*|}
   run ${tag}_excl0 DLAF_MI355X_EXCLUSIVE_CUS=0
   run ${tag}_excl1 DLAF_MI355X_EXCLUSIVE_CUS=1
-  run ${tag}_excl1_s64 DLAF_MI355X_EXCLUSIVE_CUS=1 DLAF_MI355X_SIDECAR_SLOTS=64
-  run ${tag}_excl0_s64 DLAF_MI355X_EXCLUSIVE_CUS=0 DLAF_MI355X_SIDECAR_SLOTS=64
 done
 cat $out/ab_excl.txt

@@ -20,7 +20,7 @@ rows and r / Pc tile columns of the trailing matrix.  Kernel times:
 Schedules (both take the update + solve flops of a step at R_eff, the whole-factorization in-situ rate of ONE GPU --
 68.0 TFlop/s at C2 (BENCH_r02), 63.1 for z N=32768 nb=512 (profiles/r02_final_*) -- so that the 1 x 1 row reproduces the
 measured run by construction; what the model adds is the dependency chain of a step at stand-alone kernel speeds):
-  early  (what the grid executor issues today, runtime.cpp "early diagonal"): the panel TRSM runs on the main stream
+  early  (what the grid executor issues today, cholesky.cpp "early diagonal"): the panel TRSM runs on the main stream
          in front of the bulk at full width (serial with it), POTRF(k+1) beside the bulk on shared compute units:
              T_k = max( work_k / R_eff + t_trsm_alone ,  potrf_in_situ + bc(diag) + trsm(1) + bc(head) + upd(1) ,
                         bc(panel) + bc(panel^T) )

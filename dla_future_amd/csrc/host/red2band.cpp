@@ -24,7 +24,7 @@
 //     T, W, W2 and the X update are recomputed by every rank from the replicated panels (b x b work).  The panel
 //     itself is factored redundantly by the ranks of the owning process column from the gathered copy: ONE
 //     cooperative kernel (panel_qr_kernel) instead of a per-reflector reduction over the column communicator.
-// One stream, no lookahead yet (DESIGN.md says what that costs).
+// On one process the trailing update of a panel runs beside the next panel's chain (use_lookahead below).
 #include <algorithm>
 #include <cstdlib>
 #include <cstring>
@@ -105,330 +105,333 @@ int get_band_size(int nb) {
   return nb;
 }
 
+namespace {
+Transport* checked_transport(Grid& grid) {
+  Transport* tr = grid_transport(grid);
+  if (grid.nranks > 1 && !tr)
+    fatal("[dlaf_mi355x] grid with %d ranks has no transport\n", grid.nranks);
+  return tr;
+}
+
 template <class T>
-int reduction_to_band_device(DeviceMatrix<T>& A, int band, T* taus_host) {
-  if (A.transposed)
-    fatal("[dlaf_mi355x] reduction_to_band: the matrix must be held as uplo = L (the reference references the lower "
-          "triangle only, reduction_to_band.h:66-68)\n");
-  if (band < 2 || A.nb % band != 0)
-    fatal("[dlaf_mi355x] reduction_to_band: band_size %d must be >= 2 and divide the block size %d\n", band, A.nb);
-  Grid* grid = A.grid;
-  Transport* tr = grid_transport(*grid);
-  const bool dist = grid->nranks > 1;
-  if (dist && !tr)
-    fatal("[dlaf_mi355x] grid with %d ranks has no transport\n", grid->nranks);
-  const Axis& rows = A.rows;
-  const Axis& cols = A.cols;
-  const long n = A.n, nt = A.nt, ltr = A.ltr, ltc = A.ltc;
-  const int nb = A.nb, b = band;
-  const size_t te = A.tile_elems;
-  hipStream_t s = A.s_high;
-  int* info = A.info;
-  DLAF_HIP_CHECK(hipMemsetAsync(info, 0, sizeof(int), s));
-  const long nrefls = std::max<long>(0, n - b - 1);
-  if (nrefls == 0) {
-    DLAF_HIP_CHECK(hipStreamSynchronize(s));
-    return 0;
-  }
-  const long npanels = (nrefls - 1) / b + 1;
-  const long ldp = ((n + 15) / 16) * 16;
+void gemm(int M, int N, int K, const T* a, long lda, char opa, const T* b, long ldb, char opb, T* c, long ldc,
+          double alpha, double beta, hipStream_t s, int ksplit = 1, T* partial = nullptr) {
+  GemmArgs<T> g;
+  g.M = M;
+  g.N = N;
+  g.K = K;
+  g.a = a;
+  g.lda = lda;
+  g.opa = opa;
+  g.b = b;
+  g.ldb = ldb;
+  g.opb = opb;
+  g.c = c;
+  g.ldc = ldc;
+  g.alpha = scalar<T>(alpha);
+  g.beta = scalar<T>(beta);
+  g.ksplit = ksplit;
+  g.partial = partial;
+  launch_gemm(g, s);
+}
 
-  // ---- workspaces --------------------------------------------------------------------------------------------
-  T* qt = dalloc<T>((size_t) b * (size_t) n);
-  // V and X alternate between two buffers: the bulk of the trailing update of panel p reads them on the second
-  // stream while the panel chain of p + 1 is already writing the next ones
-  T* Vb[2] = {dalloc<T>((size_t) ldp * b), dalloc<T>((size_t) ldp * b)};
-  T* W = dalloc<T>((size_t) ldp * b);
-  T* Xb[2] = {dalloc<T>((size_t) ldp * b), dalloc<T>((size_t) ldp * b)};
-  T* S = dalloc<T>((size_t) b * b);
-  T* Tm = dalloc<T>((size_t) b * b);
-  T* W2 = dalloc<T>((size_t) b * b);
-  T* taus = dalloc<T>((size_t) nrefls + 1);
-  for (int q = 0; q < 2; ++q) {
-    DLAF_HIP_CHECK(hipMemsetAsync(Vb[q], 0, (size_t) ldp * b * sizeof(T), s));
-    DLAF_HIP_CHECK(hipMemsetAsync(Xb[q], 0, (size_t) ldp * b * sizeof(T), s));
-  }
-  DLAF_HIP_CHECK(hipMemsetAsync(W, 0, (size_t) ldp * b * sizeof(T), s));
-  DLAF_HIP_CHECK(hipMemsetAsync(taus, 0, ((size_t) nrefls + 1) * sizeof(T), s));
-  const int ksplit_max = std::max(1, gemm_pick_ksplit<T>(b, b, n));
-  T* gpart = dalloc<T>(gemm_partial_elems<T>(b, b, ksplit_max));
-  // partial layers of the xHEMM: (layers + 1) * out tiles at its maximum over the panels (trailing matrices of
-  // ot x ot local tiles: the local tile counts shrink together)
-  long cap_s = 2, cap_t = 2;
-  for (long k = 0; k <= std::max(ltr, ltc); ++k) {
-    const long otr = std::max<long>(ltr - k, 0), otc = std::max<long>(ltc - k, 0);
-    if (otr == 0 || otc == 0)
-      break;
-    const int cs = tile_panel_pick_chunk(otr, nb, b, otc, true, sizeof(T));
-    const int ct = tile_panel_pick_chunk(otc, nb, b, otr, true, sizeof(T));
-    cap_s = std::max<long>(cap_s, (long) (tile_panel_layers(otc, cs) + 1) * otr);
-    cap_t = std::max<long>(cap_t, (long) (tile_panel_layers(otr, ct) + 1) * otc);
-    // (rows and columns of a process grid need not shrink in step: one more tile either way)
-    cap_s = std::max<long>(cap_s, (long) (tile_panel_layers(otc + 1, cs) + 1) * (otr + 1));
-    cap_t = std::max<long>(cap_t, (long) (tile_panel_layers(otr + 1, ct) + 1) * (otc + 1));
-  }
-  T* part_s = dalloc<T>((size_t) cap_s * nb * (size_t) b);
-  T* part_t = dalloc<T>((size_t) cap_t * nb * (size_t) b);
-  void* qr_scratch = nullptr;
-  DLAF_HIP_CHECK(hipMalloc(&qr_scratch, panel_qr_scratch_bytes(b, sizeof(T))));
-  // blocked panel factorization (kernels_hr.hip): the panel column-major, two Gram / Cholesky factors, U^T, V1, the
-  // inverted diagonal blocks of the three triangular solves, the flag that sends a panel to the reflector-by-reflector
-  // kernel, the cooperative POTRF's flags
-  const bool blocked_any = panel_qr_blocked_supported(b, std::max<long>(n - b, 0), b, sizeof(T), TypeInfo<T>::is_complex);
-  T *Pcm = nullptr, *hr_g = nullptr, *hr_l2 = nullptr, *hr_r = nullptr, *hr_lu = nullptr, *hr_y1 = nullptr, *hr_winv = nullptr;
-  int* hr_flag = nullptr;
-  unsigned* hr_sync = nullptr;
-  const size_t hr_wblk = (size_t) ((b + kDiagBlock - 1) / kDiagBlock) * kDiagBlock * kDiagBlock;
-  if (blocked_any) {
-    Pcm = dalloc<T>((size_t) ldp * b);
-    hr_g = dalloc<T>((size_t) b * b);
-    hr_l2 = dalloc<T>((size_t) b * b);
-    hr_r = dalloc<T>((size_t) b * b);
-    hr_lu = dalloc<T>((size_t) b * b);
-    hr_y1 = dalloc<T>((size_t) b * b);
-    hr_winv = dalloc<T>(4 * hr_wblk);
-    // [0] failure, [1] second pass skipped, [2] status of the second Cholesky factorization
-    DLAF_HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&hr_flag), 3 * sizeof(int)));
-    DLAF_HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&hr_sync), sizeof(unsigned) * potrf_coop_sync_words(b)));
-  }
-  int* hr_flag_host = nullptr;
-  DLAF_HIP_CHECK(hipHostMalloc(reinterpret_cast<void**>(&hr_flag_host), sizeof(int), hipHostMallocDefault));
-  long panels_blocked = 0, panels_fallback = 0;
+// B L^-H in place for the rows x b matrix B (ld ldb), in tiles of b rows; L: b x b lower (ld b), winv: its inverted
+// diagonal blocks
+template <class T>
+void trsm_rows(T* B, long ldb, long rows, int b, const T* L, const T* winv, const int* status, hipStream_t s) {
+  TrsmArgs<T> ta;
+  ta.b = B;
+  ta.b_ts = b;
+  ta.ldb = (int) ldb;
+  ta.il0 = 0;
+  ta.il1 = (int) ((rows + b - 1) / b);
+  ta.pr = 1;
+  ta.ri = 0;
+  ta.nb = b;
+  ta.nt = ta.il1;
+  ta.last_rows = (int) (rows - (long) (ta.il1 - 1) * b);
+  ta.l = L;
+  ta.ldl = b;
+  ta.winv = winv;
+  ta.n = b;
+  ta.info = status;
+  launch_trsm(ta, s);
+}
 
-  hipEvent_t ev0, ev1;
-  DLAF_HIP_CHECK(hipEventCreate(&ev0));
-  DLAF_HIP_CHECK(hipEventCreate(&ev1));
-  DLAF_HIP_CHECK(hipEventRecord(ev0, s));
-  // Lookahead (one process): the trailing update of panel p is issued in two launches -- the tile column that
-  // holds panel p + 1 on the panel stream, everything else on a second stream -- so that the latency-bound panel
-  // kernel of p + 1 runs beside the bulk of the update of p; X = A W of p + 1 waits for both.
-  // DLAF_MI355X_R2B_LOOKAHEAD=1 turns it on (off by default, see below).
-  // DLAF_MI355X_R2B_LOOKAHEAD=0/1 forces it; default: on where the panel is factored blocked (a chain of small kernels
-  // that finds room beside the update: 27.9 -> 30.0 TFlop/s at N = 20480, nb = 512, profiles/r04_red2band_lookahead_ab.txt),
-  // off with the reflector-by-reflector kernel (measured in round 3: no gain, its 1024-thread workgroups need whole CUs)
-  static const int want_lookahead = [] {
+// Lookahead (one process): the trailing update of panel p is issued in two launches -- the tile column that holds panel
+// p + 1 on the panel stream, everything else on a second stream -- so that the latency-bound panel chain of p + 1 runs
+// beside the bulk of the update of p; X = A W of p + 1 waits for both.  DLAF_MI355X_R2B_LOOKAHEAD=0/1 forces it; default:
+// on where the panel is factored blocked (a chain of small kernels that finds room beside the update: 27.9 -> 30.0
+// TFlop/s at N = 20480, nb = 512, profiles/r04_red2band_lookahead_ab.txt), off with the reflector-by-reflector kernel
+// (measured in round 3: no gain, its 1024-thread workgroups need whole CUs).  The bulk is a plain launch: leaving
+// workgroup slots free for the panel chain measured slower at every count tried (same profile).
+bool use_lookahead(bool blocked, bool dist, bool two_streams) {
+  static const int want = [] {
     const char* e = std::getenv("DLAF_MI355X_R2B_LOOKAHEAD");
     return e ? (std::atoi(e) != 0 ? 1 : 0) : -1;
   }();
-  const bool blocked_panels = panel_qr_blocked_supported(b, std::max<long>(n - b, 0), b, sizeof(T), TypeInfo<T>::is_complex);
-  const bool lookahead = (want_lookahead < 0 ? blocked_panels : want_lookahead != 0) && !dist && A.s_low != A.s_high;
-  // workgroup slots the bulk of the trailing update leaves to the panel chain beside it (DLAF_MI355X_R2B_SLOTS; a plain
-  // launch's queued workgroups are not overtaken by the side stream's kernels)
-  static const long la_slots = [] {
-    const char* e = std::getenv("DLAF_MI355X_R2B_SLOTS");
-    return e ? std::max(0L, std::atol(e)) : 0L;  // measured: 0 (plain launch) 30.0, 64 28.5, 96 28.7, 160 29.7, 256 29.6 TFlop/s
-  }();
-  unsigned* la_counters = nullptr;
-  if (lookahead && la_slots > 0)
-    DLAF_HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&la_counters), 32 * sizeof(unsigned)));
-  hipStream_t s2 = lookahead ? A.s_low : s;
-  hipEvent_t ev_x[2], ev_rest[2];
-  for (int q = 0; q < 2; ++q) {
-    DLAF_HIP_CHECK(hipEventCreateWithFlags(&ev_x[q], hipEventDisableTiming));
-    DLAF_HIP_CHECK(hipEventCreateWithFlags(&ev_rest[q], hipEventDisableTiming));
-  }
-  if (lookahead) {
-    DLAF_HIP_CHECK(hipEventRecord(ev_x[0], s));
-    DLAF_HIP_CHECK(hipStreamWaitEvent(s2, ev_x[0], 0));  // the workspaces are ready
+  return (want < 0 ? blocked : want != 0) && !dist && two_streams;
+}
+
+// One panel of reflectors: columns [c0, c0 + nr) of A (tile column J0, tile-local columns from cc), stored below row r0;
+// held transposed in qt as w x me, and in V, W, X zero-extended over the me = n - e0 rows from e0, the origin of r0's
+// tile row.  il0: the first local tile row at or below I0; pcol: the process column that owns the panel.
+struct Panel {
+  long k, r0, c0, I0, e0, J0, me, il0;
+  int cc, w, nr, pcol;
+  bool in_pcol;
+};
+
+// The panel steps that the reduction and the back-transformation share, on the matrix A that holds the reflectors; every
+// step is enqueued on the panel stream s.  The workspaces are allocated by the caller.
+template <class T>
+struct PanelSteps {
+  DeviceMatrix<T>& A;
+  Transport* const tr;
+  const bool dist;
+  const hipStream_t s;
+  const long ldp;  // leading dimension of V, W, X: n rounded up to 16
+  T *qt = nullptr, *S = nullptr, *Tm = nullptr, *W = nullptr, *taus = nullptr, *gpart = nullptr;
+  int ksplit_max = 1;  // most K slices of the panel-width Gram products (K <= n); gpart holds their partial sums
+
+  PanelSteps(DeviceMatrix<T>& a, Transport* t)
+      : A(a), tr(t), dist(a.grid->nranks > 1), s(a.s_high), ldp(((a.n + 15) / 16) * 16) {}
+
+  Panel make_panel(long k, long r0, long c0, int w, int nr) const {
+    const long I0 = r0 / A.nb, e0 = I0 * A.nb, J0 = c0 / A.nb;
+    const int pcol = A.cols.owner(J0);
+    return {k, r0, c0, I0, e0, J0, A.n - e0, A.rows.next_local(I0), (int) (c0 % A.nb), w, nr, pcol, A.cols.rank == pcol};
   }
 
-  const CommAxis ax_row = CommAxis::Row, ax_col = CommAxis::Col;
-  for (long p = 0; p < npanels; ++p) {
-    if (tr)
-      tr->mark(p);
-    T* V = Vb[p & 1];
-    T* X = Xb[p & 1];
-    const long r0 = (p + 1) * b, c0 = p * b;
-    const int nr = (int) std::min<long>(b, nrefls - c0);
-    if (nr <= 0)
-      break;
-    const long I0 = r0 / nb, e0 = I0 * nb, J0 = c0 / nb;
-    const long me = n - e0, m = n - r0, o = r0 - e0;
-    const int cc = (int) (c0 % nb);
-    const long il0 = rows.next_local(I0), jl0 = cols.next_local(I0);
-    const int pcol = cols.owner(J0);
-    const bool in_pcol = cols.rank == pcol;
-    // ---- 1. the panel, transposed, gathered inside the owning process column ------------------------------------
-    bool panel_t_ready = false;  // the blocked factorization left the T factor in Tm
-    if (in_pcol) {
-      const long jlp = cols.local_of(J0);
-      launch_panel_move(A.tiles, ltr, nb, (int) il0, (int) ltr, (int) jlp, rows.P, rows.shift(), (int) nt,
-                        rows.last_extent(), cc, b, qt, e0, r0, true, s);
-      if (rows.P > 1) {
-        tr->group_begin();
-        for (long I = I0; I < nt; ++I)
-          tr->bcast(ax_col, rows.owner(I), rows.rank, qt + (size_t) (I * nb - e0) * b, qt + (size_t) (I * nb - e0) * b,
-                    (size_t) rows.tile_extent(I) * b * sizeof(T), s);
-        tr->group_end();
+  // the panel's columns of A (rows >= r0 of this rank's tiles) into qt, or back
+  void move_panel(const Panel& P, bool to_qt) const {
+    launch_panel_move(A.tiles, A.ltr, A.nb, (int) P.il0, (int) A.ltr, (int) A.cols.local_of(P.J0), A.rows.P,
+                      A.rows.shift(), (int) A.nt, A.rows.last_extent(), P.cc, P.w, qt, P.e0, P.r0, to_qt, s);
+  }
+
+  // ranks of the owning process column: the panel, transposed, gathered from all process rows
+  void gather_panel(const Panel& P) const {
+    move_panel(P, true);
+    if (A.rows.P > 1) {
+      tr->group_begin();
+      for (long I = P.I0; I < A.nt; ++I) {
+        T* q = qt + (size_t) (I * A.nb - P.e0) * P.w;
+        tr->bcast(CommAxis::Col, A.rows.owner(I), A.rows.rank, q, q, (size_t) A.rows.tile_extent(I) * P.w * sizeof(T), s);
       }
-      // ---- 2. reflectors (xGEQR2 without the size-1 reflector) ---------------------------------------------------
-      bool t_ready = false;
-      if constexpr (!std::is_same_v<T, cfloat>) {  // (the small kernels are instantiated for float, double, cdouble)
-        if (blocked_any && panel_qr_blocked_supported(b, m, nr, sizeof(T), TypeInfo<T>::is_complex)) {
-          // CholeskyQR2 on the column-major copy, then the Householder reconstruction (kernels_hr.hip).  Every kernel
-          // behind the first factorization looks at hr_flag and does nothing once it is raised.
-          T* P = Pcm;
-          T* qtp = qt + (size_t) o * b;
-          const int nrt = (int) ((m + b - 1) / b);
-          DLAF_HIP_CHECK(hipMemsetAsync(hr_flag, 0, 3 * sizeof(int), s));
-          launch_hr_transpose(qtp, b, m, P, ldp, true, nullptr, s);
-          auto gram = [&](T* out) {
-            GemmArgs<T> g;
-            g.M = b;
-            g.N = b;
-            g.K = (int) m;
-            g.a = P;
-            g.lda = ldp;
-            g.opa = 'C';
-            g.b = P;
-            g.ldb = ldp;
-            g.opb = 'N';
-            g.c = out;
-            g.ldc = b;
-            g.alpha = scalar<T>(1.0);
-            g.beta = scalar<T>(0.0);
-            g.ksplit = std::min(ksplit_max, gemm_pick_ksplit<T>(b, b, m));
-            g.partial = gpart;
-            launch_gemm(g, s);
-          };
-          // X L^-T in place on the rows [row0, m) of P (tiles of b rows)
-          auto solve = [&](long row0, const T* L, const T* winv_blocks, const int* status = nullptr) {
-            TrsmArgs<T> ta;
-            ta.b = P + row0;
-            ta.b_ts = b;
-            ta.ldb = (int) ldp;
-            ta.il0 = 0;
-            ta.il1 = (int) ((m - row0 + b - 1) / b);
-            ta.pr = 1;
-            ta.ri = 0;
-            ta.nb = b;
-            ta.nt = ta.il1;
-            ta.last_rows = (int) ((m - row0) - (long) (ta.il1 - 1) * b);
-            ta.l = L;
-            ta.ldl = b;
-            ta.winv = winv_blocks;
-            ta.n = b;
-            ta.info = status ? status : hr_flag;
-            launch_trsm(ta, s);
-          };
-          (void) nrt;
-          gram(hr_g);
-          launch_potrf_coop(hr_g, b, b, hr_winv, hr_flag, 0, hr_sync, s, false, false);
-          // max / min of the factor's diagonal is only a LOWER bound of cond(P): a cheap first exit for panels that are
-          // plainly ill conditioned; the bound that keeps the path inside CholeskyQR2's proven range is hr_orth's below
-          launch_hr_gate(hr_g, b, b, kHrGateRatio, hr_flag, nullptr, nullptr, s);
-          solve(0, hr_g, hr_winv);
-          gram(hr_l2);
-          // second pass -- unless the first one left Q orthonormal already (|Q1^T Q1 - I| <= kHrSkipTol: hr_flag[1] is
-          // raised, hr_l2 becomes the identity, and the three launches below return at once: 19 ms of the 380 at
-          // N = 20480).  A measure above hr_orth_fail_tol(m, b) sends the panel to the reflector-by-reflector kernel.
-          // The second factorization has a status word of its own, hr_flag[2] (hr_orth sets it as well when it skips):
-          // the second gate folds a failure of it into hr_flag[0], which everything downstream looks at.
-          launch_hr_orth(hr_l2, b, b, kHrSkipTol, hr_orth_fail_tol(m, b), hr_flag + 1, hr_flag + 2, hr_flag, s);
-          launch_potrf_coop(hr_l2, b, b, hr_winv + hr_wblk, hr_flag + 2, 0, hr_sync, s, false, false);
-          launch_hr_gate(hr_l2, b, b, 0.0, hr_flag, hr_flag + 1, hr_flag + 2, s);  // (no ratio gate)
-          solve(0, hr_l2, hr_winv + hr_wblk, hr_flag + 1);
-          {
-            GemmArgs<T> g;  // R = L2^T L1^T
-            g.M = b;
-            g.N = b;
-            g.K = b;
-            g.a = hr_l2;
-            g.lda = b;
-            g.opa = 'C';
-            g.b = hr_g;
-            g.ldb = b;
-            g.opb = 'C';
-            g.c = hr_r;
-            g.ldc = b;
-            g.alpha = scalar<T>(1.0);
-            g.beta = scalar<T>(0.0);
-            launch_gemm(g, s);
-          }
-          // reconstruction: top block, V2 = Q2 U^-1, T = -U S V1^-T
-          launch_hr_lu(P, ldp, b, hr_r, hr_lu, hr_y1, Tm, taus + c0, hr_flag, s);
-          launch_invert_diag_blocks(hr_lu, b, b, hr_winv + 2 * hr_wblk, hr_flag, s, false, false);
-          solve(b, hr_lu, hr_winv + 2 * hr_wblk);
-          launch_invert_diag_blocks(hr_y1, b, b, hr_winv + 3 * hr_wblk, hr_flag, s, false, true);
-          {
-            TrsmArgs<T> ta;
-            ta.b = Tm;
-            ta.b_ts = b;
-            ta.ldb = b;
-            ta.il0 = 0;
-            ta.il1 = 1;
-            ta.pr = 1;
-            ta.ri = 0;
-            ta.nb = b;
-            ta.nt = 1;
-            ta.last_rows = b;
-            ta.l = hr_y1;
-            ta.ldl = b;
-            ta.winv = hr_winv + 3 * hr_wblk;
-            ta.n = b;
-            ta.info = hr_flag;
-            launch_trsm(ta, s);
-          }
-          launch_hr_transpose(qtp, b, m, P, ldp, false, hr_flag, s);
-          DLAF_HIP_CHECK(hipMemcpyAsync(hr_flag_host, hr_flag, sizeof(int), hipMemcpyDeviceToHost, s));
-          DLAF_HIP_CHECK(hipStreamSynchronize(s));
-          t_ready = (*hr_flag_host == 0);
-          ++(t_ready ? panels_blocked : panels_fallback);
-        }
+      tr->group_end();
+    }
+  }
+
+  // the factored panel from the owning process column to the others; with_taus: its taus too (the reduction's, which
+  // only that column has computed)
+  void bcast_panel(const Panel& P, bool with_taus) const {
+    if (A.cols.P == 1)
+      return;
+    tr->bcast(CommAxis::Row, P.pcol, A.cols.rank, qt, qt, (size_t) P.me * P.w * sizeof(T), s);
+    if (with_taus)
+      tr->bcast(CommAxis::Row, P.pcol, A.cols.rank, taus + P.c0, taus + P.c0, (size_t) P.nr * sizeof(T), s);
+  }
+
+  // well-formed V from qt; unless t_given, S = V^H V and the T factor in Tm (S and Tm: ld lds; zero_t: Tm is zeroed
+  // first, for a product that reads T past the panel's nr reflectors); then W = V op_t(T).  Every rank, from the
+  // replicated panel.
+  void form_vtw(const Panel& P, T* V, int lds, bool t_given, bool zero_t, char op_t) const {
+    launch_make_v(qt, P.w, P.nr, P.e0, P.r0, A.n, V, ldp, s);
+    if (!t_given) {
+      gemm(P.w, P.w, (int) P.me, V, ldp, 'C', V, ldp, 'N', S, lds, 1.0, 0.0, s,
+           std::min(ksplit_max, gemm_pick_ksplit<T>(P.w, P.w, P.me)), gpart);
+      if (zero_t)
+        DLAF_HIP_CHECK(hipMemsetAsync(Tm, 0, (size_t) lds * lds * sizeof(T), s));
+      launch_tfactor(S, (long) lds, taus + P.c0, P.nr, Tm, (long) lds, s);
+    }
+    gemm((int) P.me, P.w, P.w, V, ldp, 'N', Tm, lds, op_t, W, ldp, 1.0, 0.0, s);
+  }
+};
+
+// The issue side of one reduction_to_band: the workspaces, events and streams, and one member per step of a panel.
+template <class T>
+struct Red2BandIssue : PanelSteps<T> {
+  using Base = PanelSteps<T>;
+  using Base::A, Base::tr, Base::dist, Base::s, Base::ldp, Base::qt, Base::S, Base::Tm, Base::W, Base::taus,
+      Base::gpart, Base::ksplit_max;
+  const int b;
+  const long nrefls;
+  // the blocked panel factorization may take panels of this matrix: its workspaces exist
+  const bool blocked;
+  const bool lookahead;
+  const hipStream_t s2;  // the bulk of the trailing update (the panel stream s without lookahead)
+  // V and X alternate between two buffers: the bulk of the trailing update of panel p reads them on the second
+  // stream while the panel chain of p + 1 is already writing the next ones
+  T *Vb[2] = {}, *Xb[2] = {}, *W2 = nullptr;
+  long cap_s = 2, cap_t = 2;
+  T *part_s = nullptr, *part_t = nullptr;
+  void* qr_scratch = nullptr;
+  // blocked panel factorization (kernels_hr.hip): the panel column-major, two Gram / Cholesky factors, U^T, V1, the
+  // inverted diagonal blocks of the three triangular solves, the flag that sends a panel to the reflector-by-reflector
+  // kernel, the cooperative POTRF's flags
+  T *Pcm = nullptr, *hr_g = nullptr, *hr_l2 = nullptr, *hr_r = nullptr, *hr_lu = nullptr, *hr_y1 = nullptr,
+    *hr_winv = nullptr;
+  const size_t hr_wblk;
+  int* hr_flag = nullptr;
+  unsigned* hr_sync = nullptr;
+  int* hr_flag_host = nullptr;
+  long panels_blocked = 0, panels_fallback = 0;
+  hipEvent_t ev0, ev1, ev_x[2], ev_rest[2];
+
+  Red2BandIssue(DeviceMatrix<T>& a, Transport* t, int band, long nr)
+      : Base(a, t), b(band), nrefls(nr),
+        blocked(panel_qr_blocked_supported(b, std::max<long>(a.n - b, 0), b, sizeof(T), TypeInfo<T>::is_complex)),
+        lookahead(use_lookahead(blocked, this->dist, a.s_low != a.s_high)), s2(lookahead ? a.s_low : a.s_high),
+        hr_wblk((size_t) ((b + kDiagBlock - 1) / kDiagBlock) * kDiagBlock * kDiagBlock) {
+    // (the pool hands out blocks of equal size in the order they were released: this order is kept on purpose)
+    const long n = A.n, ltr = A.ltr, ltc = A.ltc;
+    const int nb = A.nb;
+    qt = dalloc<T>((size_t) b * (size_t) n);
+    Vb[0] = dalloc<T>((size_t) ldp * b);
+    Vb[1] = dalloc<T>((size_t) ldp * b);
+    W = dalloc<T>((size_t) ldp * b);
+    Xb[0] = dalloc<T>((size_t) ldp * b);
+    Xb[1] = dalloc<T>((size_t) ldp * b);
+    S = dalloc<T>((size_t) b * b);
+    Tm = dalloc<T>((size_t) b * b);
+    W2 = dalloc<T>((size_t) b * b);
+    taus = dalloc<T>((size_t) nrefls + 1);
+    for (int q = 0; q < 2; ++q) {
+      DLAF_HIP_CHECK(hipMemsetAsync(Vb[q], 0, (size_t) ldp * b * sizeof(T), s));
+      DLAF_HIP_CHECK(hipMemsetAsync(Xb[q], 0, (size_t) ldp * b * sizeof(T), s));
+    }
+    DLAF_HIP_CHECK(hipMemsetAsync(W, 0, (size_t) ldp * b * sizeof(T), s));
+    DLAF_HIP_CHECK(hipMemsetAsync(taus, 0, ((size_t) nrefls + 1) * sizeof(T), s));
+    ksplit_max = std::max(1, gemm_pick_ksplit<T>(b, b, n));
+    gpart = dalloc<T>(gemm_partial_elems<T>(b, b, ksplit_max));
+    // partial layers of the xHEMM: (layers + 1) * out tiles at its maximum over the panels (trailing matrices of
+    // ot x ot local tiles: the local tile counts shrink together)
+    for (long k = 0; k <= std::max(ltr, ltc); ++k) {
+      const long otr = std::max<long>(ltr - k, 0), otc = std::max<long>(ltc - k, 0);
+      if (otr == 0 || otc == 0)
+        break;
+      const int cs = tile_panel_pick_chunk(otr, nb, b, otc, true, sizeof(T));
+      const int ct = tile_panel_pick_chunk(otc, nb, b, otr, true, sizeof(T));
+      cap_s = std::max<long>(cap_s, (long) (tile_panel_layers(otc, cs) + 1) * otr);
+      cap_t = std::max<long>(cap_t, (long) (tile_panel_layers(otr, ct) + 1) * otc);
+      // (rows and columns of a process grid need not shrink in step: one more tile either way)
+      cap_s = std::max<long>(cap_s, (long) (tile_panel_layers(otc + 1, cs) + 1) * (otr + 1));
+      cap_t = std::max<long>(cap_t, (long) (tile_panel_layers(otr + 1, ct) + 1) * (otc + 1));
+    }
+    part_s = dalloc<T>((size_t) cap_s * nb * (size_t) b);
+    part_t = dalloc<T>((size_t) cap_t * nb * (size_t) b);
+    DLAF_HIP_CHECK(hipMalloc(&qr_scratch, panel_qr_scratch_bytes(b, sizeof(T))));
+    if (blocked) {
+      Pcm = dalloc<T>((size_t) ldp * b);
+      hr_g = dalloc<T>((size_t) b * b);
+      hr_l2 = dalloc<T>((size_t) b * b);
+      hr_r = dalloc<T>((size_t) b * b);
+      hr_lu = dalloc<T>((size_t) b * b);
+      hr_y1 = dalloc<T>((size_t) b * b);
+      hr_winv = dalloc<T>(4 * hr_wblk);
+      // [0] failure, [1] second pass skipped, [2] status of the second Cholesky factorization
+      DLAF_HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&hr_flag), 3 * sizeof(int)));
+      DLAF_HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&hr_sync), sizeof(unsigned) * potrf_coop_sync_words(b)));
+    }
+    DLAF_HIP_CHECK(hipHostMalloc(reinterpret_cast<void**>(&hr_flag_host), sizeof(int), hipHostMallocDefault));
+    DLAF_HIP_CHECK(hipEventCreate(&ev0));
+    DLAF_HIP_CHECK(hipEventCreate(&ev1));
+    DLAF_HIP_CHECK(hipEventRecord(ev0, s));
+    for (int q = 0; q < 2; ++q) {
+      DLAF_HIP_CHECK(hipEventCreateWithFlags(&ev_x[q], hipEventDisableTiming));
+      DLAF_HIP_CHECK(hipEventCreateWithFlags(&ev_rest[q], hipEventDisableTiming));
+    }
+    if (lookahead) {
+      DLAF_HIP_CHECK(hipEventRecord(ev_x[0], s));
+      DLAF_HIP_CHECK(hipStreamWaitEvent(s2, ev_x[0], 0));  // the workspaces are ready
+    }
+  }
+
+  // the events and the workspaces, in the order of their creation
+  void release() {
+    DLAF_HIP_CHECK(hipEventDestroy(ev0));
+    DLAF_HIP_CHECK(hipEventDestroy(ev1));
+    for (int q = 0; q < 2; ++q) {
+      DLAF_HIP_CHECK(hipEventDestroy(ev_x[q]));
+      DLAF_HIP_CHECK(hipEventDestroy(ev_rest[q]));
+    }
+    for (T* q : {qt, Vb[0], Vb[1], W, Xb[0], Xb[1], S, Tm, W2, taus, gpart, part_s, part_t})
+      DLAF_HIP_CHECK(pool_free(q));
+    DLAF_HIP_CHECK(hipFree(qr_scratch));
+    if (blocked) {
+      for (T* q : {Pcm, hr_g, hr_l2, hr_r, hr_lu, hr_y1, hr_winv})
+        DLAF_HIP_CHECK(pool_free(q));
+      DLAF_HIP_CHECK(hipFree(hr_flag));
+      DLAF_HIP_CHECK(hipFree(hr_sync));
+    }
+    DLAF_HIP_CHECK(hipHostFree(hr_flag_host));
+  }
+
+  Panel panel(long p) const {
+    return this->make_panel(p, (p + 1) * b, p * b, b, (int) std::min<long>(b, nrefls - p * b));
+  }
+  T* V(const Panel& P) const { return Vb[P.k & 1]; }
+  T* X(const Panel& P) const { return Xb[P.k & 1]; }
+
+  // CholeskyQR2 on the column-major copy of the panel, then the Householder reconstruction (kernels_hr.hip): the
+  // reflectors in qt, their taus, and T in Tm.  Every kernel behind the first factorization looks at hr_flag and does
+  // nothing once it is raised; returns whether the panel was accepted (hr_flag still zero).
+  bool factor_panel_blocked(const Panel& P) {
+    const long m = A.n - P.r0;
+    T* qtp = qt + (size_t) (P.r0 - P.e0) * b;
+    const int ks = std::min(ksplit_max, gemm_pick_ksplit<T>(b, b, m));
+    DLAF_HIP_CHECK(hipMemsetAsync(hr_flag, 0, 3 * sizeof(int), s));
+    launch_hr_transpose(qtp, b, m, Pcm, ldp, true, nullptr, s);
+    gemm(b, b, (int) m, Pcm, ldp, 'C', Pcm, ldp, 'N', hr_g, b, 1.0, 0.0, s, ks, gpart);
+    launch_potrf_coop(hr_g, b, b, hr_winv, hr_flag, 0, hr_sync, s, false, false);
+    // max / min of the factor's diagonal is only a LOWER bound of cond(P): a cheap first exit for panels that are
+    // plainly ill conditioned; the bound that keeps the path inside CholeskyQR2's proven range is hr_orth's below
+    launch_hr_gate(hr_g, b, b, kHrGateRatio, hr_flag, nullptr, nullptr, s);
+    trsm_rows(Pcm, ldp, m, b, hr_g, hr_winv, hr_flag, s);
+    gemm(b, b, (int) m, Pcm, ldp, 'C', Pcm, ldp, 'N', hr_l2, b, 1.0, 0.0, s, ks, gpart);
+    // second pass -- unless the first one left Q orthonormal already (|Q1^T Q1 - I| <= kHrSkipTol: hr_flag[1] is
+    // raised, hr_l2 becomes the identity, and the three launches below return at once: 19 ms of the 380 at
+    // N = 20480).  A measure above hr_orth_fail_tol(m, b) sends the panel to the reflector-by-reflector kernel.
+    // The second factorization has a status word of its own, hr_flag[2] (hr_orth sets it as well when it skips):
+    // the second gate folds a failure of it into hr_flag[0], which everything downstream looks at.
+    launch_hr_orth(hr_l2, b, b, kHrSkipTol, hr_orth_fail_tol(m, b), hr_flag + 1, hr_flag + 2, hr_flag, s);
+    launch_potrf_coop(hr_l2, b, b, hr_winv + hr_wblk, hr_flag + 2, 0, hr_sync, s, false, false);
+    launch_hr_gate(hr_l2, b, b, 0.0, hr_flag, hr_flag + 1, hr_flag + 2, s);  // (no ratio gate)
+    trsm_rows(Pcm, ldp, m, b, hr_l2, hr_winv + hr_wblk, hr_flag + 1, s);
+    gemm(b, b, b, hr_l2, b, 'C', hr_g, b, 'C', hr_r, b, 1.0, 0.0, s);  // R = L2^T L1^T
+    // reconstruction: top block, V2 = Q2 U^-1, T = -U S V1^-T
+    launch_hr_lu(Pcm, ldp, b, hr_r, hr_lu, hr_y1, Tm, taus + P.c0, hr_flag, s);
+    launch_invert_diag_blocks(hr_lu, b, b, hr_winv + 2 * hr_wblk, hr_flag, s, false, false);
+    trsm_rows(Pcm + b, ldp, m - b, b, hr_lu, hr_winv + 2 * hr_wblk, hr_flag, s);
+    launch_invert_diag_blocks(hr_y1, b, b, hr_winv + 3 * hr_wblk, hr_flag, s, false, true);
+    trsm_rows(Tm, b, b, b, hr_y1, hr_winv + 3 * hr_wblk, hr_flag, s);
+    launch_hr_transpose(qtp, b, m, Pcm, ldp, false, hr_flag, s);
+    DLAF_HIP_CHECK(hipMemcpyAsync(hr_flag_host, hr_flag, sizeof(int), hipMemcpyDeviceToHost, s));
+    DLAF_HIP_CHECK(hipStreamSynchronize(s));
+    return *hr_flag_host == 0;
+  }
+
+  // 2. the reflectors of the gathered panel (xGEQR2 without the size-1 reflector), on the ranks of the owning process
+  // column: blocked where the panel qualifies and passes its checks, else the reflector-by-reflector kernel.  The one
+  // place where a panel's path is chosen; returns whether T is in Tm already.
+  bool factor_panel(const Panel& P) {
+    bool t_ready = false;
+    if constexpr (!std::is_same_v<T, cfloat>) {  // (the small kernels are instantiated for float, double, cdouble)
+      if (blocked && panel_qr_blocked_supported(b, A.n - P.r0, P.nr, sizeof(T), TypeInfo<T>::is_complex)) {
+        t_ready = factor_panel_blocked(P);
+        ++(t_ready ? panels_blocked : panels_fallback);
       }
-      if (!t_ready)
-        launch_panel_qr(qt + (size_t) o * b, m, b, nr, taus + c0, qr_scratch, info, s);
-      panel_t_ready = t_ready;
-      launch_panel_move(A.tiles, ltr, nb, (int) il0, (int) ltr, (int) jlp, rows.P, rows.shift(), (int) nt,
-                        rows.last_extent(), cc, b, qt, e0, r0, false, s);
     }
-    if (cols.P > 1) {
-      tr->bcast(ax_row, pcol, cols.rank, qt, qt, (size_t) me * b * sizeof(T), s);
-      tr->bcast(ax_row, pcol, cols.rank, taus + c0, taus + c0, (size_t) nr * sizeof(T), s);
-    }
-    // ---- 3. well-formed V, T factor, W = V T  (every rank, from the replicated panel) ------------------------
-    launch_make_v(qt, b, nr, e0, r0, n, V, ldp, s);
-    // (the blocked factorization delivers T = -U S V1^-T with the reflectors; on a grid with several process columns
-    // the ranks outside the panel's column have only the reflectors, and every rank forms T the same way)
-    if (!(panel_t_ready && cols.P == 1)) {
-      GemmArgs<T> g;
-      g.M = b;
-      g.N = b;
-      g.K = (int) me;
-      g.a = V;
-      g.lda = ldp;
-      g.opa = 'C';
-      g.b = V;
-      g.ldb = ldp;
-      g.opb = 'N';
-      g.c = S;
-      g.ldc = b;
-      g.alpha = scalar<T>(1.0);
-      g.beta = scalar<T>(0.0);
-      g.ksplit = std::min(ksplit_max, gemm_pick_ksplit<T>(b, b, me));
-      g.partial = gpart;
-      launch_gemm(g, s);
-      DLAF_HIP_CHECK(hipMemsetAsync(Tm, 0, (size_t) b * b * sizeof(T), s));
-      launch_tfactor(S, (long) b, taus + c0, nr, Tm, (long) b, s);
-    }
-    {
-      GemmArgs<T> g;
-      g.M = (int) me;
-      g.N = b;
-      g.K = b;
-      g.a = V;
-      g.lda = ldp;
-      g.opa = 'N';
-      g.b = Tm;
-      g.ldb = b;
-      g.opb = 'N';
-      g.c = W;
-      g.ldc = ldp;
-      g.alpha = scalar<T>(1.0);
-      g.beta = scalar<T>(0.0);
-      launch_gemm(g, s);
-    }
-    // ---- 4. X = A_t W (xHEMM on the lower tiles), summed over the grid -------------------------------------------
+    if (!t_ready)
+      launch_panel_qr(qt + (size_t) (P.r0 - P.e0) * b, A.n - P.r0, b, P.nr, taus + P.c0, qr_scratch, A.info, s);
+    return t_ready;
+  }
+
+  // 4. X = A_t W (xHEMM on the lower tiles), summed over the grid
+  void hemm_x(const Panel& P) {
+    const Axis &rows = A.rows, &cols = A.cols;
+    const long ltr = A.ltr, ltc = A.ltc, il0 = P.il0, jl0 = cols.next_local(P.I0);
+    const int nb = A.nb;
     TilePanelArgs<T> h;
     h.tiles = A.tiles;
     h.ltr = ltr;
@@ -441,14 +444,14 @@ int reduction_to_band_device(DeviceMatrix<T>& A, int band, T* taus_host) {
     h.ri = rows.shift();
     h.pc = cols.P;
     h.ci = cols.shift();
-    h.nt_r = (int) nt;
+    h.nt_r = (int) A.nt;
     h.last_rows = rows.last_extent();
-    h.nt_c = (int) nt;
+    h.nt_c = (int) A.nt;
     h.last_cols = cols.last_extent();
     h.herm = 1;
     h.w = W;
     h.ldw = ldp;
-    h.e0 = e0;
+    h.e0 = P.e0;
     h.ncols = b;
     // (a rank without local trailing rows or columns has no work items at all: nothing to sum either)
     h.kinds = (il0 < ltr && jl0 < ltc) ? 3 : 0;
@@ -461,138 +464,133 @@ int reduction_to_band_device(DeviceMatrix<T>& A, int band, T* taus_host) {
             h.layers_s + 1, ltr - il0, h.layers_t + 1, ltc - jl0, cap_s, cap_t);
     h.part_s = part_s;
     h.part_t = part_t;
-    if (lookahead && p > 0)
-      DLAF_HIP_CHECK(hipStreamWaitEvent(s, ev_rest[(p - 1) & 1], 0));  // the bulk of the previous trailing update
+    if (lookahead && P.k > 0)
+      DLAF_HIP_CHECK(hipStreamWaitEvent(s, ev_rest[(P.k - 1) & 1], 0));  // the bulk of the previous trailing update
     launch_tile_panel(h, s);
-    launch_hemm_reduce(h, r0, X, ldp, s);
+    launch_hemm_reduce(h, P.r0, X(P), ldp, s);
     if (dist)
-      tr->allreduce_sum(X, (size_t) ldp * b, TypeInfo<T>::tag, 'A', s);
-    // ---- 5. W2 = W^H X,  X -= 1/2 V W2 -----------------------------------------------------------------------------
-    {
-      GemmArgs<T> g;
-      g.M = b;
-      g.N = b;
-      g.K = (int) me;
-      g.a = W;
-      g.lda = ldp;
-      g.opa = 'C';
-      g.b = X;
-      g.ldb = ldp;
-      g.opb = 'N';
-      g.c = W2;
-      g.ldc = b;
-      g.alpha = scalar<T>(1.0);
-      g.beta = scalar<T>(0.0);
-      g.ksplit = std::min(ksplit_max, gemm_pick_ksplit<T>(b, b, me));
-      g.partial = gpart;
-      launch_gemm(g, s);
+      tr->allreduce_sum(X(P), (size_t) ldp * b, TypeInfo<T>::tag, 'A', s);
+  }
+
+  // 5. W2 = W^H X,  X -= 1/2 V W2
+  void correct_x(const Panel& P) {
+    gemm(b, b, (int) P.me, W, ldp, 'C', X(P), ldp, 'N', W2, b, 1.0, 0.0, s,
+         std::min(ksplit_max, gemm_pick_ksplit<T>(b, b, P.me)), gpart);
+    gemm((int) P.me, b, b, V(P), ldp, 'N', W2, b, 'N', X(P), ldp, -0.5, 1.0, s);
+  }
+
+  // A_t -= X V^H + V X^H on the local tile columns [ja, jb) (tile::her2k / 2 x tile::gemm, impl.h:545-585)
+  void her2k(const Panel& P, long ja, long jb, hipStream_t st) {
+    const Axis &rows = A.rows, &cols = A.cols;
+    if (P.il0 >= A.ltr || ja >= jb)
+      return;
+    const int nb = A.nb;
+    UpdateArgs<T> ua;
+    ua.c = A.tiles;
+    ua.c_tsr = (long) A.tile_elems;
+    ua.c_tsc = (long) (A.tile_elems * A.ltr);
+    ua.ldc = nb;
+    ua.a = X(P) + (rows.global_of(P.il0) * nb - P.e0);
+    ua.a2 = V(P) + (rows.global_of(P.il0) * nb - P.e0);
+    ua.a_ts = (long) rows.P * nb;
+    ua.lda = (int) ldp;
+    ua.b = V(P) + (cols.global_of(ja) * nb - P.e0);
+    ua.b2 = X(P) + (cols.global_of(ja) * nb - P.e0);
+    ua.b_ts = (long) cols.P * nb;
+    ua.ldb = (int) ldp;
+    ua.il0 = (int) P.il0;
+    ua.il1 = (int) A.ltr;
+    ua.jl0 = (int) ja;
+    ua.jl1 = (int) jb;
+    ua.nb = nb;
+    ua.K1 = b;
+    ua.K = 2 * b;
+    ua.her2k = 1;
+    ua.pr = rows.P;
+    ua.ri = rows.shift();
+    ua.pc = cols.P;
+    ua.ci = cols.shift();
+    ua.nt = (int) A.nt;
+    ua.last_rows = rows.last_extent();
+    ua.info = A.info;
+    launch_update(ua, st, 3);
+  }
+
+  // 6. the trailing update; with lookahead the tile column of the next panel first, on the panel stream, and the rest
+  // beside the next panel chain
+  void trailing_update(const Panel& P) {
+    const long jl0 = A.cols.next_local(P.I0);
+    if (!lookahead) {
+      her2k(P, jl0, A.ltc, s);
+      return;
     }
-    {
-      GemmArgs<T> g;
-      g.M = (int) me;
-      g.N = b;
-      g.K = b;
-      g.a = V;
-      g.lda = ldp;
-      g.opa = 'N';
-      g.b = W2;
-      g.ldb = b;
-      g.opb = 'N';
-      g.c = X;
-      g.ldc = ldp;
-      g.alpha = scalar<T>(-0.5);
-      g.beta = scalar<T>(1.0);
-      launch_gemm(g, s);
+    const long jsplit = std::min<long>(A.ltc, jl0 + 1);
+    DLAF_HIP_CHECK(hipEventRecord(ev_x[P.k & 1], s));
+    her2k(P, jl0, jsplit, s);
+    DLAF_HIP_CHECK(hipStreamWaitEvent(s2, ev_x[P.k & 1], 0));
+    her2k(P, jsplit, A.ltc, s2);
+    DLAF_HIP_CHECK(hipEventRecord(ev_rest[P.k & 1], s2));
+  }
+};
+}  // namespace
+
+template <class T>
+int reduction_to_band_device(DeviceMatrix<T>& A, int band, T* taus_host) {
+  if (A.transposed)
+    fatal("[dlaf_mi355x] reduction_to_band: the matrix must be held as uplo = L (the reference references the lower "
+          "triangle only, reduction_to_band.h:66-68)\n");
+  if (band < 2 || A.nb % band != 0)
+    fatal("[dlaf_mi355x] reduction_to_band: band_size %d must be >= 2 and divide the block size %d\n", band, A.nb);
+  Transport* tr = checked_transport(*A.grid);
+  const long n = A.n;
+  hipStream_t s = A.s_high;
+  DLAF_HIP_CHECK(hipMemsetAsync(A.info, 0, sizeof(int), s));
+  const long nrefls = std::max<long>(0, n - band - 1);
+  if (nrefls == 0) {
+    DLAF_HIP_CHECK(hipStreamSynchronize(s));
+    return 0;
+  }
+
+  Red2BandIssue<T> r(A, tr, band, nrefls);
+  const long npanels = (nrefls - 1) / band + 1;
+  for (long p = 0; p < npanels; ++p) {
+    if (tr)
+      tr->mark(p);
+    const Panel P = r.panel(p);
+    bool t_ready = false;  // the blocked factorization left the T factor in Tm
+    if (P.in_pcol) {
+      r.gather_panel(P);
+      t_ready = r.factor_panel(P);
+      r.move_panel(P, false);
     }
-    // ---- 6. A_t -= X V^H + V X^H on the lower tiles (tile::her2k / 2 x tile::gemm, impl.h:545-585) ----------------
-    // reserve > 0: persistent form that leaves that many workgroup slots to the panel chain running beside it
-    auto her2k = [&](long ja, long jb, hipStream_t st, long reserve = 0) {
-      if (il0 >= ltr || ja >= jb)
-        return;
-      UpdateArgs<T> ua;
-      ua.c = A.tiles;
-      ua.c_tsr = (long) te;
-      ua.c_tsc = (long) (te * ltr);
-      ua.ldc = nb;
-      ua.a = X + (rows.global_of(il0) * nb - e0);
-      ua.a2 = V + (rows.global_of(il0) * nb - e0);
-      ua.a_ts = (long) rows.P * nb;
-      ua.lda = (int) ldp;
-      ua.b = V + (cols.global_of(ja) * nb - e0);
-      ua.b2 = X + (cols.global_of(ja) * nb - e0);
-      ua.b_ts = (long) cols.P * nb;
-      ua.ldb = (int) ldp;
-      ua.il0 = (int) il0;
-      ua.il1 = (int) ltr;
-      ua.jl0 = (int) ja;
-      ua.jl1 = (int) jb;
-      ua.nb = nb;
-      ua.K1 = b;
-      ua.K = 2 * b;
-      ua.her2k = 1;
-      ua.pr = rows.P;
-      ua.ri = rows.shift();
-      ua.pc = cols.P;
-      ua.ci = cols.shift();
-      ua.nt = (int) nt;
-      ua.last_rows = rows.last_extent();
-      ua.info = info;
-      if (reserve > 0 && la_counters != nullptr) {
-        unsigned* cnt = la_counters + 16 * (size_t) (p & 1);
-        launch_update(ua, st, 3, std::max<long>(64, A.bulk_slots - reserve), cnt, false);
-      }
-      else
-        launch_update(ua, st, 3);
-    };
-    if (lookahead) {
-      // the tile column of the next panel first, on the panel stream; the rest beside the next panel chain
-      const long jsplit = std::min<long>(ltc, jl0 + 1);
-      DLAF_HIP_CHECK(hipEventRecord(ev_x[p & 1], s));
-      her2k(jl0, jsplit, s);
-      DLAF_HIP_CHECK(hipStreamWaitEvent(s2, ev_x[p & 1], 0));
-      her2k(jsplit, ltc, s2, la_slots);
-      DLAF_HIP_CHECK(hipEventRecord(ev_rest[p & 1], s2));
-    }
-    else
-      her2k(jl0, ltc, s);
-    if (dist)
+    r.bcast_panel(P, true);
+    // 3. (the blocked factorization delivers T = -U S V1^-T with the reflectors; on a grid with several process columns
+    // the ranks outside the panel's column have only the reflectors, and every rank forms T the same way)
+    r.form_vtw(P, r.V(P), band, t_ready && A.cols.P == 1, true, 'N');
+    r.hemm_x(P);
+    r.correct_x(P);
+    r.trailing_update(P);
+    if (r.dist)
       DLAF_HIP_CHECK(hipStreamSynchronize(s));
   }
-  if (lookahead) {
-    DLAF_HIP_CHECK(hipEventRecord(ev_rest[0], s2));
-    DLAF_HIP_CHECK(hipStreamWaitEvent(s, ev_rest[0], 0));
+  if (r.lookahead) {
+    DLAF_HIP_CHECK(hipEventRecord(r.ev_rest[0], r.s2));
+    DLAF_HIP_CHECK(hipStreamWaitEvent(s, r.ev_rest[0], 0));
   }
-  DLAF_HIP_CHECK(hipEventRecord(ev1, s));
+  DLAF_HIP_CHECK(hipEventRecord(r.ev1, s));
   int h_info = 0;
-  DLAF_HIP_CHECK(hipMemcpyAsync(&h_info, info, sizeof(int), hipMemcpyDeviceToHost, s));
+  DLAF_HIP_CHECK(hipMemcpyAsync(&h_info, A.info, sizeof(int), hipMemcpyDeviceToHost, s));
   if (taus_host)
-    DLAF_HIP_CHECK(hipMemcpyAsync(taus_host, taus, (size_t) nrefls * sizeof(T), hipMemcpyDeviceToHost, s));
+    DLAF_HIP_CHECK(hipMemcpyAsync(taus_host, r.taus, (size_t) nrefls * sizeof(T), hipMemcpyDeviceToHost, s));
   DLAF_HIP_CHECK(hipStreamSynchronize(s));
   float ms = 0;
-  DLAF_HIP_CHECK(hipEventElapsedTime(&ms, ev0, ev1));
+  DLAF_HIP_CHECK(hipEventElapsedTime(&ms, r.ev0, r.ev1));
   g_last_ms = ms;
   // miniapp_reduction_to_band.cpp:163-168: add_mul = 2/3 n^3 - n^2 nb, one add + one mul each (x4 complex)
-  g_last_flops = (TypeInfo<T>::is_complex ? 4.0 : 1.0) * 2.0 * (2.0 / 3.0 * (double) n * n * n - (double) n * n * nb);
-  DLAF_HIP_CHECK(hipEventDestroy(ev0));
-  DLAF_HIP_CHECK(hipEventDestroy(ev1));
-  for (int q = 0; q < 2; ++q) {
-    DLAF_HIP_CHECK(hipEventDestroy(ev_x[q]));
-    DLAF_HIP_CHECK(hipEventDestroy(ev_rest[q]));
-  }
-  for (T* q : {qt, Vb[0], Vb[1], W, Xb[0], Xb[1], S, Tm, W2, taus, gpart, part_s, part_t})
-    DLAF_HIP_CHECK(pool_free(q));
-  DLAF_HIP_CHECK(pool_free(qr_scratch));
-  if (blocked_any) {
-    for (T* q : {Pcm, hr_g, hr_l2, hr_r, hr_lu, hr_y1, hr_winv})
-      DLAF_HIP_CHECK(pool_free(q));
-    DLAF_HIP_CHECK(pool_free(hr_flag));
-    DLAF_HIP_CHECK(pool_free(hr_sync));
-  }
-  DLAF_HIP_CHECK(hipHostFree(hr_flag_host));
-  if (la_counters)
-    DLAF_HIP_CHECK(hipFree(la_counters));
-  g_last_panels[0] = panels_blocked;
-  g_last_panels[1] = panels_fallback;
+  g_last_flops = (TypeInfo<T>::is_complex ? 4.0 : 1.0) * 2.0 * (2.0 / 3.0 * (double) n * n * n - (double) n * n * A.nb);
+  r.release();
+  g_last_panels[0] = r.panels_blocked;
+  g_last_panels[1] = r.panels_fallback;
   if (h_info == kInfoSchedulingFailure)
     fatal("[dlaf_mi355x] reduction_to_band: the cooperative panel kernel could not make progress (its workgroups were "
           "not co-resident)\n");
@@ -625,15 +623,10 @@ int bt_reduction_to_band_device(int band, TileMatrix<T>& C, DeviceMatrix<T>& A, 
     fatal("[dlaf_mi355x] bt_reduction_to_band: the reflectors must be held as uplo = L\n");
   if (C.grid != A.grid || C.nb != A.nb || C.rows.n != A.n || C.rows.src != A.rows.src || C.transposed)
     fatal("[dlaf_mi355x] bt_reduction_to_band: C must have A's block size, row count and row source rank\n");
-  Grid* grid = A.grid;
-  Transport* tr = grid_transport(*grid);
-  const bool dist = grid->nranks > 1;
-  if (dist && !tr)
-    fatal("[dlaf_mi355x] grid with %d ranks has no transport\n", grid->nranks);
+  Transport* tr = checked_transport(*A.grid);
   const Axis& rows = A.rows;
-  const Axis& cols = A.cols;
   const Axis& ccols = C.cols;
-  const long n = A.n, nt = A.nt, ltr = A.ltr;
+  const long n = A.n, nt = A.nt;
   const int nb = A.nb, b = band;
   const size_t te = A.tile_elems;
   hipStream_t s = A.s_high;
@@ -646,21 +639,22 @@ int bt_reduction_to_band_device(int band, TileMatrix<T>& C, DeviceMatrix<T>& A, 
     return 0;
   }
   const long nblocks = (total - 1) / nb + 1;
-  const long ldp = ((n + 15) / 16) * 16;
+  PanelSteps<T> ps(A, tr);
+  const long ldp = ps.ldp;
   const long ldw2 = std::max<long>(cltc * nb, 1);
 
-  T* qt = dalloc<T>((size_t) nb * (size_t) n);
+  ps.qt = dalloc<T>((size_t) nb * (size_t) n);
   T* V = dalloc<T>((size_t) ldp * nb);
-  T* W = dalloc<T>((size_t) ldp * nb);
-  T* S = dalloc<T>((size_t) nb * nb);
-  T* Tm = dalloc<T>((size_t) nb * nb);
+  ps.W = dalloc<T>((size_t) ldp * nb);
+  ps.S = dalloc<T>((size_t) nb * nb);
+  ps.Tm = dalloc<T>((size_t) nb * nb);
   T* W2H = dalloc<T>((size_t) ldw2 * nb);
-  T* taus = dalloc<T>((size_t) total + 1);
-  DLAF_HIP_CHECK(hipMemcpyAsync(taus, taus_host, (size_t) total * sizeof(T), hipMemcpyHostToDevice, s));
+  ps.taus = dalloc<T>((size_t) total + 1);
+  DLAF_HIP_CHECK(hipMemcpyAsync(ps.taus, taus_host, (size_t) total * sizeof(T), hipMemcpyHostToDevice, s));
   DLAF_HIP_CHECK(hipMemsetAsync(V, 0, (size_t) ldp * nb * sizeof(T), s));
-  DLAF_HIP_CHECK(hipMemsetAsync(W, 0, (size_t) ldp * nb * sizeof(T), s));
-  const int ksplit_max = std::max(1, gemm_pick_ksplit<T>(nb, nb, n));
-  T* gpart = dalloc<T>(gemm_partial_elems<T>(nb, nb, ksplit_max));
+  DLAF_HIP_CHECK(hipMemsetAsync(ps.W, 0, (size_t) ldp * nb * sizeof(T), s));
+  ps.ksplit_max = std::max(1, gemm_pick_ksplit<T>(nb, nb, n));
+  ps.gpart = dalloc<T>(gemm_partial_elems<T>(nb, nb, ps.ksplit_max));
   long lay_cap = 2;
   for (long src = 1; src <= std::max<long>(cltr, 1); ++src) {
     const int ch = tile_panel_pick_chunk(std::max<long>(cltc, 1), nb, nb, src, false, sizeof(T));
@@ -673,69 +667,16 @@ int bt_reduction_to_band_device(int band, TileMatrix<T>& C, DeviceMatrix<T>& A, 
   DLAF_HIP_CHECK(hipEventCreate(&ev1));
   DLAF_HIP_CHECK(hipEventRecord(ev0, s));
 
-  const CommAxis ax_row = CommAxis::Row, ax_col = CommAxis::Col;
   for (long k = nblocks - 1; k >= 0; --k) {
     if (tr)
       tr->mark(k);
     const int nrefl = (int) std::min<long>(nb, total - k * nb);
-    const long r0 = k * nb + b, c0 = k * nb;
-    const long I0 = r0 / nb, e0 = I0 * nb, J0 = k;
-    const long me = n - e0;
-    const long il0 = rows.next_local(I0);
-    const int pcol = cols.owner(J0);
-    const bool in_pcol = cols.rank == pcol;
-    if (in_pcol) {
-      const long jlp = cols.local_of(J0);
-      launch_panel_move(A.tiles, ltr, nb, (int) il0, (int) ltr, (int) jlp, rows.P, rows.shift(), (int) nt,
-                        rows.last_extent(), 0, nrefl, qt, e0, r0, true, s);
-      if (rows.P > 1) {
-        tr->group_begin();
-        for (long I = I0; I < nt; ++I)
-          tr->bcast(ax_col, rows.owner(I), rows.rank, qt + (size_t) (I * nb - e0) * nrefl,
-                    qt + (size_t) (I * nb - e0) * nrefl, (size_t) rows.tile_extent(I) * nrefl * sizeof(T), s);
-        tr->group_end();
-      }
-    }
-    if (cols.P > 1)
-      tr->bcast(ax_row, pcol, cols.rank, qt, qt, (size_t) me * nrefl * sizeof(T), s);
-    launch_make_v(qt, nrefl, nrefl, e0, r0, n, V, ldp, s);
-    {
-      GemmArgs<T> g;
-      g.M = nrefl;
-      g.N = nrefl;
-      g.K = (int) me;
-      g.a = V;
-      g.lda = ldp;
-      g.opa = 'C';
-      g.b = V;
-      g.ldb = ldp;
-      g.opb = 'N';
-      g.c = S;
-      g.ldc = nb;
-      g.alpha = scalar<T>(1.0);
-      g.beta = scalar<T>(0.0);
-      g.ksplit = std::min(ksplit_max, gemm_pick_ksplit<T>(nrefl, nrefl, me));
-      g.partial = gpart;
-      launch_gemm(g, s);
-    }
-    launch_tfactor(S, (long) nb, taus + c0, nrefl, Tm, (long) nb, s);
-    {
-      GemmArgs<T> g;  // W = V T^H
-      g.M = (int) me;
-      g.N = nrefl;
-      g.K = nrefl;
-      g.a = V;
-      g.lda = ldp;
-      g.opa = 'N';
-      g.b = Tm;
-      g.ldb = nb;
-      g.opb = 'C';
-      g.c = W;
-      g.ldc = ldp;
-      g.alpha = scalar<T>(1.0);
-      g.beta = scalar<T>(0.0);
-      launch_gemm(g, s);
-    }
+    const Panel P = ps.make_panel(k, k * nb + b, k * nb, nrefl, nrefl);
+    const long il0 = P.il0, e0 = P.e0;
+    if (P.in_pcol)
+      ps.gather_panel(P);
+    ps.bcast_panel(P, false);
+    ps.form_vtw(P, V, nb, false, false, 'C');  // W = V T^H
     if (cltc > 0) {
       // W2^H = C^H W over the local tiles of C with global tile row >= I0
       TilePanelArgs<T> h;
@@ -755,7 +696,7 @@ int bt_reduction_to_band_device(int band, TileMatrix<T>& C, DeviceMatrix<T>& A, 
       h.nt_c = (int) ccols.nt();
       h.last_cols = ccols.last_extent();
       h.herm = 0;
-      h.w = W;
+      h.w = ps.W;
       h.ldw = ldp;
       h.e0 = e0;
       h.ncols = nrefl;
@@ -805,7 +746,7 @@ int bt_reduction_to_band_device(int band, TileMatrix<T>& C, DeviceMatrix<T>& A, 
         launch_update(ua, s, 3);
       }
     }
-    if (dist)
+    if (ps.dist)
       DLAF_HIP_CHECK(hipStreamSynchronize(s));
   }
   DLAF_HIP_CHECK(hipEventRecord(ev1, s));
@@ -817,7 +758,7 @@ int bt_reduction_to_band_device(int band, TileMatrix<T>& C, DeviceMatrix<T>& A, 
   g_last_flops = (TypeInfo<T>::is_complex ? 4.0 : 1.0) * 2.0 * (double) (n - b) * (double) (n - b) * (double) ccols.n;
   DLAF_HIP_CHECK(hipEventDestroy(ev0));
   DLAF_HIP_CHECK(hipEventDestroy(ev1));
-  for (T* q : {qt, V, W, S, Tm, W2H, taus, gpart, part_t})
+  for (T* q : {ps.qt, V, ps.W, ps.S, ps.Tm, W2H, ps.taus, ps.gpart, part_t})
     DLAF_HIP_CHECK(pool_free(q));
   return 0;
 }

@@ -92,20 +92,30 @@ SIGNATURES = {
     "dlaf_mi355x_triangular_solver_d": (_i, [_i, _ch, _ch, _ch, _ch, _vp, _vp, DLAFDescriptor, _vp, DLAFDescriptor]),
     "dlaf_mi355x_triangular_solver_c": (_i, [_i, _ch, _ch, _ch, _ch, _vp, _vp, DLAFDescriptor, _vp, DLAFDescriptor]),
     "dlaf_mi355x_triangular_solver_z": (_i, [_i, _ch, _ch, _ch, _ch, _vp, _vp, DLAFDescriptor, _vp, DLAFDescriptor]),
+    "dlaf_mi355x_triangular_multiplication_s": (_i, [_i, _ch, _ch, _ch, _ch, _vp, _vp, DLAFDescriptor, _vp, DLAFDescriptor]),
+    "dlaf_mi355x_triangular_multiplication_d": (_i, [_i, _ch, _ch, _ch, _ch, _vp, _vp, DLAFDescriptor, _vp, DLAFDescriptor]),
+    "dlaf_mi355x_triangular_multiplication_c": (_i, [_i, _ch, _ch, _ch, _ch, _vp, _vp, DLAFDescriptor, _vp, DLAFDescriptor]),
+    "dlaf_mi355x_triangular_multiplication_z": (_i, [_i, _ch, _ch, _ch, _ch, _vp, _vp, DLAFDescriptor, _vp, DLAFDescriptor]),
     "dlaf_mi355x_pstrsm": (None, [_ch, _ch, _ch, _ch, _i, _i, _vp, _vp, _i, _i, _IP, _vp, _i, _i, _IP]),
     "dlaf_mi355x_pdtrsm": (None, [_ch, _ch, _ch, _ch, _i, _i, _vp, _vp, _i, _i, _IP, _vp, _i, _i, _IP]),
     "dlaf_mi355x_pctrsm": (None, [_ch, _ch, _ch, _ch, _i, _i, _vp, _vp, _i, _i, _IP, _vp, _i, _i, _IP]),
     "dlaf_mi355x_pztrsm": (None, [_ch, _ch, _ch, _ch, _i, _i, _vp, _vp, _i, _i, _IP, _vp, _i, _i, _IP]),
+    "dlaf_mi355x_pstrmm": (None, [_ch, _ch, _ch, _ch, _i, _i, _vp, _vp, _i, _i, _IP, _vp, _i, _i, _IP]),
+    "dlaf_mi355x_pdtrmm": (None, [_ch, _ch, _ch, _ch, _i, _i, _vp, _vp, _i, _i, _IP, _vp, _i, _i, _IP]),
+    "dlaf_mi355x_pctrmm": (None, [_ch, _ch, _ch, _ch, _i, _i, _vp, _vp, _i, _i, _IP, _vp, _i, _i, _IP]),
+    "dlaf_mi355x_pztrmm": (None, [_ch, _ch, _ch, _ch, _i, _i, _vp, _vp, _i, _i, _IP, _vp, _i, _i, _IP]),
     "dlaf_mi355x_pspotrs": (None, [_ch, _i, _i, _vp, _i, _i, _IP, _vp, _i, _i, _IP, _IP]),
     "dlaf_mi355x_pdpotrs": (None, [_ch, _i, _i, _vp, _i, _i, _IP, _vp, _i, _i, _IP, _IP]),
     "dlaf_mi355x_pcpotrs": (None, [_ch, _i, _i, _vp, _i, _i, _IP, _vp, _i, _i, _IP, _IP]),
     "dlaf_mi355x_pzpotrs": (None, [_ch, _i, _i, _vp, _i, _i, _IP, _vp, _i, _i, _IP, _IP]),
     "dlaf_mi355x_solver_profile": (_i, [C.POINTER(C.c_double), C.POINTER(C.c_double)]),
+    "dlaf_mi355x_multiplication_profile": (_i, [C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     "dlaf_mi355x_gmatrix_create": (_i, [_i, _ch, DLAFDescriptor, C.POINTER(_vp)]),
     "dlaf_mi355x_gmatrix_destroy": (None, [_vp]),
     "dlaf_mi355x_gmatrix_upload": (_i, [_vp, _vp, _i]),
     "dlaf_mi355x_gmatrix_download": (_i, [_vp, _vp, _i]),
     "dlaf_mi355x_triangular_solver_device": (_i, [_ch, _ch, _ch, _ch, _vp, _vp, _vp]),
+    "dlaf_mi355x_triangular_multiplication_device": (_i, [_ch, _ch, _ch, _ch, _vp, _vp, _vp]),
     "dlaf_mi355x_potrs_device": (_i, [_ch, _vp, _vp]),
     "dlaf_mi355x_generalized_to_standard_s": (_i, [_i, _ch, _vp, DLAFDescriptor, _vp, DLAFDescriptor]),
     "dlaf_mi355x_generalized_to_standard_d": (_i, [_i, _ch, _vp, DLAFDescriptor, _vp, DLAFDescriptor]),

@@ -196,6 +196,49 @@ def triangular_solver(grid: Grid, side: str, uplo: str, op: str, diag: str, alph
         raise ValueError(f"dlaf_mi355x_triangular_solver_{t} failed with {r}")
 
 
+def triangular_multiplication(grid: Grid, side: str, uplo: str, op: str, diag: str, alpha, a: np.ndarray, b: np.ndarray,
+                              nb: int, m: int | None = None, n: int | None = None, a_src=(0, 0), b_src=(0, 0),
+                              b_block: tuple[int, int] | None = None) -> None:
+    """dlaf::triangular_multiplication(grid, side, uplo, op, diag, alpha, A, B)
+    (include/dlaf/multiplication/triangular.h) == dlaf_mi355x_triangular_multiplication_{s,d,c,z}:
+    side 'L': B = alpha op(A) B, side 'R': B = alpha B op(A); `b` (this process's local column-major part of the
+    m x n matrix B) is overwritten.  The other arguments are triangular_solver's."""
+    t = type_char(b.dtype)
+    if a.dtype != b.dtype:
+        raise ValueError("A and B must have the same element type")
+    if m is None or n is None:
+        if grid.nranks != 1:
+            raise ValueError("the global size m x n of B is required on a distributed grid")
+        m, n = b.shape
+    na = m if side.upper() == "L" else n
+    da = DLAFDescriptor(na, na, nb, nb, a_src[0], a_src[1], 0, 0, _ld_of(a))
+    mb_b, nb_b = b_block if b_block is not None else (nb, nb)
+    db = DLAFDescriptor(m, n, mb_b, nb_b, b_src[0], b_src[1], 0, 0, _ld_of(b))
+    al = np.array([alpha], dtype=b.dtype)
+    fn = getattr(lib(), f"dlaf_mi355x_triangular_multiplication_{t}")
+    r = fn(grid.context, side.encode(), uplo.encode(), op.encode(), diag.encode(), _ptr(al), _ptr(a), da, _ptr(b), db)
+    if r != 0:
+        raise ValueError(f"dlaf_mi355x_triangular_multiplication_{t} failed with {r}")
+
+
+def pxtrmm(side: str, uplo: str, op: str, diag: str, m: int, n: int, alpha, a: np.ndarray, ia: int, ja: int, desca,
+           b: np.ndarray, ib: int, jb: int, descb) -> None:
+    """dlaf_mi355x_p{s,d,c,z}trmm: ScaLAPACK's p?trmm argument list (9-int descriptors)."""
+    t = type_char(b.dtype)
+    da = (C.c_int * 9)(*[int(x) for x in desca])
+    db = (C.c_int * 9)(*[int(x) for x in descb])
+    al = np.array([alpha], dtype=b.dtype)
+    getattr(lib(), f"dlaf_mi355x_p{t}trmm")(side.encode(), uplo.encode(), op.encode(), diag.encode(), m, n, _ptr(al),
+                                            _ptr(a), ia, ja, da, _ptr(b), ib, jb, db)
+
+
+def multiplication_profile():
+    """(ms, flops) of the sweep of the last triangular multiplication on this process (device time, no staging)."""
+    ms, fl = C.c_double(0), C.c_double(0)
+    lib().dlaf_mi355x_multiplication_profile(C.byref(ms), C.byref(fl))
+    return ms.value, fl.value
+
+
 def pxpotrs(uplo: str, n: int, nrhs: int, a: np.ndarray, ia: int, ja: int, desca, b: np.ndarray, ib: int, jb: int,
             descb) -> int:
     """dlaf_mi355x_p{s,d,c,z}potrs: A X = B with the factor p?potrf left in `a`; returns info."""
@@ -421,6 +464,17 @@ def triangular_solver_device(side: str, uplo: str, op: str, diag: str, alpha, a:
                                                    a._h, b._h)
     if r != 0:
         raise ValueError(f"dlaf_mi355x_triangular_solver_device failed with {r}")
+
+
+def triangular_multiplication_device(side: str, uplo: str, op: str, diag: str, alpha, a: DeviceMatrix,
+                                     b: GeneralDeviceMatrix) -> None:
+    """dlaf::triangular_multiplication on resident operands: `a` holds the triangular matrix in its uplo triangle
+    (e.g. the factor a.factorize() left there), `b` is overwritten by the product; no PCIe traffic."""
+    al = np.array([alpha], dtype=b.dtype)
+    r = lib().dlaf_mi355x_triangular_multiplication_device(side.encode(), uplo.encode(), op.encode(), diag.encode(),
+                                                           _ptr(al), a._h, b._h)
+    if r != 0:
+        raise ValueError(f"dlaf_mi355x_triangular_multiplication_device failed with {r}")
 
 
 def potrs_device(uplo: str, factor: DeviceMatrix, b: GeneralDeviceMatrix) -> None:

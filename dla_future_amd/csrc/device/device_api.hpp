@@ -74,7 +74,8 @@ struct UpdateArgs {
   int her2k = 0;
 };
 // role: 0 trailing bulk, 1 lookahead column, 2 in-tile POTRF update / single-tile entries, 3 residual checker
-// and triangular solver (same code, separate kernel names, so that profiles of the factorization stay clean)
+// and triangular solver (same code, separate kernel names, so that profiles of the factorization stay clean),
+// 4 triangular multiplication: the ADDITIVE form C += A * B^H (its own instantiation; every other role subtracts)
 // max_blocks > 0 (with counters = 16 device words of scratch): launch at most that many workgroups and
 // let them pull work items (persistent form): what is left of the GPU stays free for kernels that
 // must run beside the update.  excl_slots > 0 (persistent form only): the workgroups that land on the first
@@ -112,6 +113,27 @@ struct TrsmArgs {
 };
 template <class T>
 void launch_trsm(const TrsmArgs<T>& args, hipStream_t stream);
+
+// ------------------------------------------------------------------------------------------
+// Panel TRMM (the diagonal-tile step of triangular_multiplication):  X(il) = B(il) * L^H for local tiles il in
+// [il0, il1), in place.  L: n x n (n <= nb, ldl), lower or upper; only its triangle is read, and with unit != 0
+// not its diagonal either (taken as 1).  No inverse, no chain: the tiles' row strips are independent.
+template <class T>
+struct TrmmArgs {
+  T* b;
+  long b_ts;
+  int ldb;
+  int il0, il1;
+  int pr, ri;
+  int nb, nt, last_rows;
+  const T* l;
+  int ldl;
+  int n;
+  int upper = 0;
+  int unit = 0;
+};
+template <class T>
+void launch_trmm(const TrmmArgs<T>& args, hipStream_t stream);
 
 // ------------------------------------------------------------------------------------------
 // Diagonal block factorization + inversion (one workgroup):  a (jb x jb, lda, jb <= 64) is

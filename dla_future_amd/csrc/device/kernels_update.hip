@@ -112,7 +112,17 @@ __global__ void cu_probe_kernel(unsigned* seen) {
 // One work item = one BM x BN block of one tile.  Returns early for blocks outside the domain.
 // PART: 0 every block; 1 only the interior blocks (whole BM x BN, whole slabs, no triangle mask: the K loop on the
 // direct-to-LDS path + the wide epilogue, nothing else compiled in); 2 only the others (edge / masked blocks)
-template <class T, bool VEC, bool UTAIL = false, int PART = 0>
+// ADD: C += A B^H instead of C -= A B^H (the triangular multiplication's update)
+template <class X, class Y>
+__device__ __forceinline__ X upd_apply(X cv, Y a, std::false_type) {
+  return cv - a;
+}
+template <class X, class Y>
+__device__ __forceinline__ X upd_apply(X cv, Y a, std::true_type) {
+  return cv + a;
+}
+
+template <class T, bool VEC, bool UTAIL = false, int PART = 0, bool ADD = false>
 __device__ __forceinline__ void update_block(const UpdateArgs<T>& p, const UpdateMap& mp, long w,
                                              real_t<T>* __restrict__ lds, int s0 = 0) {
   using Cfg = typename UpdateCfg<T>::type;
@@ -269,7 +279,7 @@ __device__ __forceinline__ void update_block(const UpdateArgs<T>& p, const Updat
             acc.re[2 * q + 1][j][v] = cv[1];
           }
         }
-      gemm_nt_block<Cfg, T, VEC, false, UTAIL, true>(A, DLAF_LDA_X, mrows, B, DLAF_LDB_X, ncols, p.K, lds, acc, K1, A2,
+      gemm_nt_block<Cfg, T, VEC, false, UTAIL, !ADD>(A, DLAF_LDA_X, mrows, B, DLAF_LDB_X, ncols, p.K, lds, acc, K1, A2,
                                                      B2);
 #pragma unroll
       for (int j = 0; j < Cfg::TN; ++j)
@@ -308,7 +318,8 @@ __device__ __forceinline__ void update_block(const UpdateArgs<T>& p, const Updat
     return;
   }
 #endif
-  // ---- epilogue: C -= acc -------------------------------------------------------------------
+  // ---- epilogue: C -= acc (ADD: C += acc) --------------------------------------------------
+  constexpr std::integral_constant<bool, ADD> add{};
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int wm = wave % Cfg::WAVES_M, wn = wave / Cfg::WAVES_M;
   const int g = lane >> 4, c = lane & 15;
@@ -343,8 +354,8 @@ __device__ __forceinline__ void update_block(const UpdateArgs<T>& p, const Updat
           T* col = C + (long) (wn * Cfg::WN + acc_n<Cfg>(j, g, v)) * p.ldc;
 #pragma unroll
           for (int q = 0; q < Cfg::TM / 2; ++q) {
-            cv[ii][q][0] -= acc.re[2 * q][j][v];
-            cv[ii][q][1] -= acc.re[2 * q + 1][j][v];
+            cv[ii][q][0] = upd_apply(cv[ii][q][0], acc.re[2 * q][j][v], add);
+            cv[ii][q][1] = upd_apply(cv[ii][q][1], acc.re[2 * q + 1][j][v], add);
             *reinterpret_cast<r2*>(col + wm * Cfg::WM + q * 32 + 2 * c) = cv[ii][q];
           }
         }
@@ -361,7 +372,7 @@ __device__ __forceinline__ void update_block(const UpdateArgs<T>& p, const Updat
           for (int i = 0; i < Cfg::TM; ++i) {
             const int ml = wm * Cfg::WM + acc_m<Cfg>(i, c);
             if (!masked || (ml < mrows && nl < ncols && (!diag || (m0 + ml) >= (n0 + nl))))
-              col[ml] = col[ml] - acc.re[i][j][v];
+              col[ml] = upd_apply(col[ml], acc.re[i][j][v], add);
           }
         }
       }
@@ -385,9 +396,10 @@ __device__ __forceinline__ void update_block(const UpdateArgs<T>& p, const Updat
 #pragma unroll
         for (int i = 0; i < Cfg::TM; ++i) {
           if constexpr (Cfg::CX)
-            col[wm * Cfg::WM + acc_m<Cfg>(i, c)] = T{cv[v][i].re - acc.re[i][j][v], cv[v][i].im - acc.im[i][j][v]};
+            col[wm * Cfg::WM + acc_m<Cfg>(i, c)] = T{upd_apply(cv[v][i].re, acc.re[i][j][v], add),
+                                                     upd_apply(cv[v][i].im, acc.im[i][j][v], add)};
           else
-            col[wm * Cfg::WM + acc_m<Cfg>(i, c)] = cv[v][i] - acc.re[i][j][v];
+            col[wm * Cfg::WM + acc_m<Cfg>(i, c)] = upd_apply(cv[v][i], acc.re[i][j][v], add);
         }
       }
     }
@@ -405,13 +417,13 @@ __device__ __forceinline__ void update_block(const UpdateArgs<T>& p, const Updat
           if (ml < mrows && nl < ncols && (!diag || (m0 + ml) >= (n0 + nl))) {
             const T cv = col[ml];
             if constexpr (Cfg::CX) {
-              T r{cv.re - acc.re[i][j][v], cv.im - acc.im[i][j][v]};
+              T r{upd_apply(cv.re, acc.re[i][j][v], add), upd_apply(cv.im, acc.im[i][j][v], add)};
               if (diag && (m0 + ml) == (n0 + nl))
                 r.im = R(0);
               col[ml] = r;
             }
             else {
-              col[ml] = cv - acc.re[i][j][v];
+              col[ml] = upd_apply(cv, acc.re[i][j][v], add);
             }
           }
         }
@@ -420,9 +432,10 @@ __device__ __forceinline__ void update_block(const UpdateArgs<T>& p, const Updat
   }
 }
 
-// ROLE only names the instantiation (0 trailing bulk, 1 lookahead column, 2 in-tile POTRF / single-tile
+// ROLE names the instantiation (0 trailing bulk, 1 lookahead column, 2 in-tile POTRF / single-tile
 // entries, 3 callers outside the factorization: residual checker, triangular solver) so
-// that rocprof statistics and the library's own HIP-event timing refer to the same set of launches.
+// that rocprof statistics and the library's own HIP-event timing refer to the same set of launches; ROLE 4 (the
+// triangular multiplication) is the one that changes the code: it adds the product instead of subtracting it.
 // Work item v -> block w: the 8 XCDs (workgroup id mod 8 under round-robin dispatch) get contiguous runs
 // of 8x8-block patches.  Persistent form: gridDim.x workgroups stride over the work items, which (a)
 // leaves the compute units the launcher did not ask for free for the resident POTRF / RCCL kernels
@@ -439,9 +452,9 @@ __global__ __launch_bounds__(UpdateCfg<T>::type::THREADS, UpdateCfg<T>::min_wave
     const long v = blockIdx.x;
     const long w = mp.xcd ? (v & 7) * (mp.total >> 3) + (v >> 3) : v;
 #ifdef DLAF_UPD_LEAN
-    update_block<T, VEC, false, (ROLE == 0 ? 1 : 0)>(p, mp, w, lds);
+    update_block<T, VEC, false, (ROLE == 0 ? 1 : 0), ROLE == 4>(p, mp, w, lds);
 #else
-    update_block<T, VEC>(p, mp, w, lds);
+    update_block<T, VEC, false, 0, ROLE == 4>(p, mp, w, lds);
 #endif
     return;
   }
@@ -541,9 +554,9 @@ __global__ __launch_bounds__(UpdateCfg<T>::type::THREADS, UpdateCfg<T>::min_wave
       __syncthreads();
     }
 #ifdef DLAF_UPD_LEAN
-    update_block<T, VEC, ROLE == 0, (ROLE == 0 ? 1 : 0)>(p, mp, (long) q * per_q + i, lds, s0);
+    update_block<T, VEC, ROLE == 0, (ROLE == 0 ? 1 : 0), ROLE == 4>(p, mp, (long) q * per_q + i, lds, s0);
 #else
-    update_block<T, VEC, ROLE == 0>(p, mp, (long) q * per_q + i, lds, s0);
+    update_block<T, VEC, ROLE == 0, 0, ROLE == 4>(p, mp, (long) q * per_q + i, lds, s0);
 #endif
     if (mp.lockstep && threadIdx.x == 0)
       __hip_atomic_fetch_add(&mp.counters[8 + q], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -735,6 +748,7 @@ void launch_update(const UpdateArgs<T>& a, hipStream_t stream, int role, long ma
       case 0: go(vtag, std::integral_constant<int, 0>{}); break;
       case 1: go(vtag, std::integral_constant<int, 1>{}); break;
       case 3: go(vtag, std::integral_constant<int, 3>{}); break;
+      case 4: go(vtag, std::integral_constant<int, 4>{}); break;
       default: go(vtag, std::integral_constant<int, 2>{}); break;
     }
   };
@@ -765,10 +779,12 @@ static void update_init_one() {
   SET_ONE(true, 1);
   SET_ONE(true, 2);
   SET_ONE(true, 3);
+  SET_ONE(true, 4);
   SET_ONE(false, 0);
   SET_ONE(false, 1);
   SET_ONE(false, 2);
   SET_ONE(false, 3);
+  SET_ONE(false, 4);
 #undef SET_ONE
 }
 

@@ -145,36 +145,77 @@ void pxpotrf(char uplo, int n, HT* a, int ia, int ja, const int desca[9], int* i
     *info = r;
 }
 
+// Preconditions of the triangular solver and multiplication through descriptors (who names the routine in the
+// messages); they terminate before the GPU is touched.  Returns the grid.
+static Grid& triangular_checks(const char* who, int ctx, char side, char uplo, char op, char diag,
+                               const DLAF_descriptor& da, const DLAF_descriptor& db) {
+  auto is = [](char c, const char* set) { return c != 0 && std::strchr(set, c) != nullptr; };
+  if (!is(side, "LlRr") || !is(uplo, "LlUu") || !is(op, "NnTtCc") || !is(diag, "NnUu"))
+    fatal("[dlaf_mi355x] %s: bad side/uplo/op/diag '%c' '%c' '%c' '%c'\n", who, side, uplo, op, diag);
+  if (da.i != 0 || da.j != 0 || db.i != 0 || db.j != 0)
+    fatal("[dlaf_mi355x] sub-matrices are not supported: offsets must be 0\n");
+  // preconditions of triangular.h:43-48, :57 / :93-98: A square with square blocks, op(A) and B multipliable
+  if (da.m != da.n || da.mb != da.nb || da.nb < 1)
+    fatal("[dlaf_mi355x] %s: A must be square with square blocks (%d x %d, %d x %d)\n", who, da.m, da.n, da.mb, da.nb);
+  const bool left = (side == 'L' || side == 'l');
+  if (db.m < 0 || db.n < 0 || da.m != (left ? db.m : db.n))
+    fatal("[dlaf_mi355x] %s: A is %d x %d, B is %d x %d (side %c)\n", who, da.m, da.n, db.m, db.n, side);
+  // multipliable (util_matrix.h:123-143): B's block along the triangular dimension is A's; the other one is free
+  // (the device tiles stay square: the free dimension is re-cut locally, tile_matrix.hpp create_rhs)
+  if ((left ? db.mb : db.nb) != da.nb || db.mb < 1 || db.nb < 1)
+    fatal("[dlaf_mi355x] %s: B's blocks (%d x %d) do not match A's (%d x %d) for side %c\n", who, db.mb, db.nb, da.mb,
+          da.nb, side);
+  Grid& g = grid_from_context(ctx);
+  for (const DLAF_descriptor* d : {&da, &db})
+    if (d->isrc < 0 || d->isrc >= g.nprow || d->jsrc < 0 || d->jsrc >= g.npcol)
+      fatal("[dlaf_mi355x] source rank (%d,%d) outside the %d x %d grid\n", d->isrc, d->jsrc, g.nprow, g.npcol);
+  if (db.m > 0 && db.n > 0 && (left ? (da.isrc != db.isrc) : (da.jsrc != db.jsrc)))
+    fatal("[dlaf_mi355x] %s: A and B must share the source process along the triangular dimension\n", who);
+  return g;
+}
+
 // dlaf::triangular_solver (include/dlaf/solver/triangular.h:41-177) through descriptors
 template <class HT>
 int triangular_solver_c(int ctx, char side, char uplo, char op, char diag, const HT* alpha, const HT* a,
                         const DLAF_descriptor& da, HT* b, const DLAF_descriptor& db) {
   using DT = typename DevType<HT>::type;
-  auto is = [](char c, const char* set) { return c != 0 && std::strchr(set, c) != nullptr; };
-  if (!is(side, "LlRr") || !is(uplo, "LlUu") || !is(op, "NnTtCc") || !is(diag, "NnUu"))
-    fatal("[dlaf_mi355x] triangular solver: bad side/uplo/op/diag '%c' '%c' '%c' '%c'\n", side, uplo, op, diag);
-  if (da.i != 0 || da.j != 0 || db.i != 0 || db.j != 0)
-    fatal("[dlaf_mi355x] sub-matrices are not supported: offsets must be 0\n");
-  // preconditions of triangular.h:43-48, :57 / :93-98: A square with square blocks, op(A) and B multipliable
-  if (da.m != da.n || da.mb != da.nb || da.nb < 1)
-    fatal("[dlaf_mi355x] triangular solver: A must be square with square blocks (%d x %d, %d x %d)\n", da.m, da.n,
-          da.mb, da.nb);
+  Grid& g = triangular_checks("triangular solver", ctx, side, uplo, op, diag, da, db);
   const bool left = (side == 'L' || side == 'l');
-  if (db.m < 0 || db.n < 0 || da.m != (left ? db.m : db.n))
-    fatal("[dlaf_mi355x] triangular solver: A is %d x %d, B is %d x %d (side %c)\n", da.m, da.n, db.m, db.n, side);
-  // multipliable (util_matrix.h:123-143): B's block along the triangular dimension is A's; the other one is free
-  // (the device tiles stay square: the free dimension is re-cut locally, tile_matrix.hpp create_rhs)
-  if ((left ? db.mb : db.nb) != da.nb || db.mb < 1 || db.nb < 1)
-    fatal("[dlaf_mi355x] triangular solver: B's blocks (%d x %d) do not match A's (%d x %d) for side %c\n", db.mb, db.nb,
-          da.mb, da.nb, side);
-  Grid& g = grid_from_context(ctx);
-  for (const DLAF_descriptor* d : {&da, &db})
-    if (d->isrc < 0 || d->isrc >= g.nprow || d->jsrc < 0 || d->jsrc >= g.npcol)
-      fatal("[dlaf_mi355x] source rank (%d,%d) outside the %d x %d grid\n", d->isrc, d->jsrc, g.nprow, g.npcol);
   DT al;
   std::memcpy(&al, alpha, sizeof(DT));
   return triangular_solver_host<DT>(&g, side, uplo, op, diag, al, reinterpret_cast<const DT*>(a), da.ld, da.isrc,
                                     da.jsrc, reinterpret_cast<DT*>(b), db.ld, db.m, db.n, da.nb, db.isrc, db.jsrc, left ? db.nb : db.mb);
+}
+
+// dlaf::triangular_multiplication (include/dlaf/multiplication/triangular.h) through descriptors: B = alpha op(A) B
+// (side L) / alpha B op(A) (side R), the solver's arguments and preconditions
+template <class HT>
+int triangular_multiplication_c(int ctx, char side, char uplo, char op, char diag, const HT* alpha, const HT* a,
+                                const DLAF_descriptor& da, HT* b, const DLAF_descriptor& db) {
+  using DT = typename DevType<HT>::type;
+  Grid& g = triangular_checks("triangular multiplication", ctx, side, uplo, op, diag, da, db);
+  const bool left = (side == 'L' || side == 'l');
+  DT al;
+  std::memcpy(&al, alpha, sizeof(DT));
+  return triangular_multiplication_host<DT>(&g, side, uplo, op, diag, al, reinterpret_cast<const DT*>(a), da.ld, da.isrc,
+                                            da.jsrc, reinterpret_cast<DT*>(b), db.ld, db.m, db.n, da.nb, db.isrc, db.jsrc,
+                                            left ? db.nb : db.mb);
+}
+
+// ScaLAPACK p?trmm argument list
+template <class HT>
+void pxtrmm(char side, char uplo, char op, char diag, int m, int n, const HT* alpha, const HT* a, int ia, int ja,
+            const int desca[9], HT* b, int ib, int jb, const int descb[9]) {
+  if (desca[0] != 1 || descb[0] != 1)
+    fatal("[dlaf_mi355x] desc[0] (dtype) must be 1\n");
+  if (ia != 1 || ja != 1 || ib != 1 || jb != 1)
+    fatal("[dlaf_mi355x] ia, ja, ib, jb must be 1\n");
+  if (desca[1] != descb[1])
+    fatal("[dlaf_mi355x] A and B live on different contexts (%d, %d)\n", desca[1], descb[1]);
+  const int na = (side == 'L' || side == 'l') ? m : n;
+  const DLAF_descriptor da = make_dlaf_descriptor(na, na, ia, ja, desca);
+  const DLAF_descriptor db = make_dlaf_descriptor(m, n, ib, jb, descb);
+  (void) triangular_multiplication_c<HT>(desca[1], side, uplo, op, diag, alpha, a, da, b, db);
 }
 
 // ScaLAPACK p?trsm argument list
@@ -652,6 +693,23 @@ int dlaf_mi355x_grid_host_bcast(int ctx, int axis, int root, void* host_buf, siz
     pxtrsm<HT>(side, uplo, op, diag, m, n, reinterpret_cast<const HT*>(alpha), reinterpret_cast<const HT*>(a), ia, \
                ja, desca, reinterpret_cast<HT*>(b), ib, jb, descb);                                              \
   }
+#define DLAF_MI355X_TRMM_ENTRY(S, HT, CT)                                                                        \
+  int dlaf_mi355x_triangular_multiplication_##S(int ctx, char side, char uplo, char op, char diag, const CT* alpha, \
+                                                const CT* a, DLAF_descriptor desca, CT* b,                       \
+                                                DLAF_descriptor descb) noexcept {                                \
+    return triangular_multiplication_c<HT>(ctx, side, uplo, op, diag, reinterpret_cast<const HT*>(alpha),       \
+                                           reinterpret_cast<const HT*>(a), desca, reinterpret_cast<HT*>(b), descb); \
+  }                                                                                                             \
+  void dlaf_mi355x_p##S##trmm(char side, char uplo, char op, char diag, int m, int n, const CT* alpha, const CT* a, \
+                              int ia, int ja, const int desca[9], CT* b, int ib, int jb, const int descb[9]) noexcept { \
+    pxtrmm<HT>(side, uplo, op, diag, m, n, reinterpret_cast<const HT*>(alpha), reinterpret_cast<const HT*>(a), ia, \
+               ja, desca, reinterpret_cast<HT*>(b), ib, jb, descb);                                              \
+  }
+DLAF_MI355X_TRMM_ENTRY(s, float, float)
+DLAF_MI355X_TRMM_ENTRY(d, double, double)
+DLAF_MI355X_TRMM_ENTRY(c, std::complex<float>, dlaf_complex_c)
+DLAF_MI355X_TRMM_ENTRY(z, std::complex<double>, dlaf_complex_z)
+#undef DLAF_MI355X_TRMM_ENTRY
 #define DLAF_MI355X_POTRS_ENTRY(S, HT, CT)                                                                       \
   void dlaf_mi355x_p##S##potrs(char uplo, int n, int nrhs, const CT* a, int ia, int ja, const int desca[9], CT* b,  \
                                int ib, int jb, const int descb[9], int* info) noexcept {                        \
@@ -857,6 +915,21 @@ int dlaf_mi355x_potrs_device(char uplo, dlaf_mi355x_matrix_t factor, dlaf_mi355x
 
 int dlaf_mi355x_solver_profile(double* ms, double* flops) noexcept {
   solver_last_profile(ms, flops);
+  return 0;
+}
+
+int dlaf_mi355x_triangular_multiplication_device(char side, char uplo, char op, char diag, const void* alpha,
+                                                 dlaf_mi355x_matrix_t a, dlaf_mi355x_gmatrix_t b) noexcept {
+  if (!a || !a->m || !b || !b->m || a->ctx != b->ctx)
+    return -1;
+  auto is = [](char c, const char* set) { return c != 0 && std::strchr(set, c) != nullptr; };
+  if (!is(side, "LlRr") || !is(uplo, "LlUu") || !is(op, "NnTtCc") || !is(diag, "NnUu"))
+    fatal("[dlaf_mi355x] triangular multiplication: bad side/uplo/op/diag '%c' '%c' '%c' '%c'\n", side, uplo, op, diag);
+  return triangular_multiplication_device(side, uplo, op, diag, alpha, a->m.get(), b->m.get());
+}
+
+int dlaf_mi355x_multiplication_profile(double* ms, double* flops) noexcept {
+  multiplication_last_profile(ms, flops);
   return 0;
 }
 

@@ -258,6 +258,16 @@ MatrixBase* general_matrix_create(Grid* g, char type, long m, long n, int nb, in
 void general_matrix_transfer(MatrixBase* h, void* host, long ld, bool upload);
 int triangular_solver_device(char side, char uplo, char op, char diag, const void* alpha, MatrixBase* a, MatrixBase* b);
 
+// B = alpha op(A) B (side L) / B = alpha B op(A) (side R) on the grid (multiplication.cpp): the arguments and the
+// operand mapping of triangular_solver_host, host and resident forms; device time of the last sweep
+template <class T>
+int triangular_multiplication_host(Grid* g, char side, char uplo, char op, char diag, T alpha, const T* a, long lda,
+                                   int a_isrc, int a_jsrc, T* b, long ldb, long m, long n, int nb, int b_isrc, int b_jsrc,
+                                   int nb_free = 0);
+int triangular_multiplication_device(char side, char uplo, char op, char diag, const void* alpha, MatrixBase* a,
+                                     MatrixBase* b);
+void multiplication_last_profile(double* ms, double* flops);
+
 // A <- L^-1 A L^-H (uplo L) / U^-H A U^-1 (uplo U) with the Cholesky factor held in the same uplo triangle of
 // `l` (gen_to_std.cpp; dlaf::eigensolver::internal::generalized_to_standard); device-resident and host forms
 template <class T>

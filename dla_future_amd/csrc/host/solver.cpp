@@ -35,6 +35,7 @@
 #include <vector>
 
 #include "runtime.hpp"
+#include "t_operand.hpp"
 #include "tile_matrix.hpp"
 
 namespace dlaf_mi355x {
@@ -75,19 +76,6 @@ double im_of_host(const T& v) {
 static double g_last_sweep_ms = 0;
 static double g_last_sweep_flops = 0;
 
-struct Events {
-  std::vector<hipEvent_t> v;
-  explicit Events(size_t n) : v(n) {
-    for (auto& e : v)
-      DLAF_HIP_CHECK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-  }
-  ~Events() {
-    for (auto e : v)
-      (void) hipEventDestroy(e);
-  }
-  hipEvent_t operator[](size_t i) const { return v[i]; }
-};
-
 // X T^H = B in place on Bd; Td lower (swept forward) or upper (swept backward) triangular, unit: its
 // diagonal is taken as 1.  Both operands on the same grid; Td's index distribution along the grid dimension
 // it shares with Bd's columns must be the one of Bd's columns (checked by the caller).
@@ -104,17 +92,11 @@ void solve_canonical(TileMatrix<T>& Td, TileMatrix<T>& Bd, bool upper, bool unit
   const size_t winv_elems = (size_t) ((nb + kDiagBlock - 1) / kDiagBlock) * kDiagBlock * kDiagBlock;
   const size_t diag_elems = tile_elems + winv_elems;
 
-  // communicators seen from Bd's view: along its rows (members differ in view-column coordinate) and
-  // along its columns
+  // the communicator along Bd's rows (members differ in view-column coordinate); aligned: Td's rows live on the
+  // grid dimension of Bd's columns; crossed: on the one of Bd's rows
   const CommAxis along_row = Bd.transposed ? CommAxis::Col : CommAxis::Row;
-  const CommAxis along_col = Bd.transposed ? CommAxis::Row : CommAxis::Col;
-  // aligned: Td's rows live on the grid dimension of Bd's columns; crossed: on the one of Bd's rows
   const bool aligned = Td.row_dim() == Bd.col_dim();
-  const Axis& t_match = aligned ? Td.rows : Td.cols;  // Td axis that shares Bd.cols' dimension
-  const Axis& t_other = aligned ? Td.cols : Td.rows;  // ... and the one that shares Bd.rows' dimension
-  if (t_match.P != Bd.cols.P || t_match.src != Bd.cols.src || t_match.n != Bd.cols.n)
-    fatal("[dlaf_mi355x] triangular solver: A and B are not aligned along the triangular dimension "
-          "(source process %d vs %d)\n", t_match.src, Bd.cols.src);
+  check_t_aligned(Td, Bd, "triangular solver");
 
   hipStream_t s_main = nullptr, s_comm = nullptr;
   int lo = 0, hi = 0;
@@ -147,7 +129,7 @@ void solve_canonical(TileMatrix<T>& Td, TileMatrix<T>& Bd, bool upper, bool unit
   // workspaces, kBuf of each (step s uses s % kBuf; the T operands of step s+1 are fetched while step s-1 is
   // still being applied): [T_kk | W_k], the T column panel as the update's second operand (one tile per
   // local column of Bd), its staging for the crossed shape, the X panel on non-owners
-  constexpr int kBuf = 3;
+  constexpr int kBuf = TOperandFetch<T>::kBuf;
   T* diag_ws[kBuf] = {nullptr, nullptr, nullptr};
   T* tpanel[kBuf] = {nullptr, nullptr, nullptr};
   T* tstage[kBuf] = {nullptr, nullptr, nullptr};
@@ -162,115 +144,15 @@ void solve_canonical(TileMatrix<T>& Td, TileMatrix<T>& Bd, bool upper, bool unit
     }
   }
 
-  // global step order and the set of columns "beyond" step k
+  // global step order and the T operands of every step (t_operand.hpp)
   auto step_k = [&](long s) { return upper ? nt - 1 - s : s; };
-
-  struct TOperand {
-    const T* diag = nullptr;  // T_kk
-    const T* winv = nullptr;  // its inverted diagonal blocks
-    const T* base = nullptr;  // T(j,k) for local column jl of Bd at base + (jl - jl0) * ts
-    long ts = 0;
-    long jl0 = 0, jl1 = 0;    // local columns of Bd beyond step k
-  };
-  std::vector<TOperand> top((size_t) nt);
-
-  // ---- s_comm: everything the step needs of T (depends on A only: issued ahead of the sweep) ----------
-  auto fetch_t = [&](long s) {
-    const long k = step_k(s);
-    const int buf = (int) (s % kBuf);
-    TOperand& o = top[(size_t) s];
-    // local columns of Bd beyond k
-    o.jl0 = upper ? 0 : Bd.cols.next_local(k + 1);
-    o.jl1 = upper ? Bd.cols.next_local(k) : Bd.ltc;
-    // these buffers were last read by the kernels of step s - kBuf (event recorded before this call is made)
-    if (s >= kBuf)
-      DLAF_HIP_CHECK(hipStreamWaitEvent(s_comm, ev_free[(size_t) (s - kBuf)], 0));
-
-    // (1) T_kk and its inverted diagonal blocks to every process holding column k of Bd
-    const bool own_diag = Td.rows.mine(k) && Td.cols.mine(k);
-    const bool need_diag = Bd.cols.mine(k);
-    const T* tkk = nullptr;
-    const T* wk = nullptr;
-    if (own_diag) {
-      const size_t q = (size_t) (std::find(my_diag.begin(), my_diag.end(), k) - my_diag.begin());
-      tkk = Td.tile(Td.rows.local_of(k), Td.cols.local_of(k));
-      wk = winv_all + q * winv_elems;
-    }
-    if (need_diag && Bd.row_P > 1) {
-      // (own_diag implies need_diag: the owner sits in Bd's column k by the alignment requirement)
-      if (own_diag) {
-        DLAF_HIP_CHECK(hipMemcpyAsync(diag_ws[buf], tkk, tile_bytes, hipMemcpyDeviceToDevice, s_comm));
-        DLAF_HIP_CHECK(hipMemcpyAsync(diag_ws[buf] + tile_elems, wk, winv_elems * sizeof(T), hipMemcpyDeviceToDevice, s_comm));
-      }
-      tr->bcast(along_col, t_other.owner(k), Bd.row_rank, diag_ws[buf], diag_ws[buf], diag_elems * sizeof(T), s_comm);
-      tkk = diag_ws[buf];
-      wk = diag_ws[buf] + tile_elems;
-    }
-    o.diag = tkk;
-    o.winv = wk;
-
-    // (2) T(j,k) for the local columns j of Bd beyond k
-    const long ncols = o.jl1 - o.jl0;
-    if (!dist) {
-      // one process: Td's local row index of global j is Bd's local column index
-      o.base = Td.tile(o.jl0 < Td.ltr ? o.jl0 : 0, k);
-      o.ts = (long) tile_elems;
-    }
-    else if (aligned) {
-      // Td's rows are spread like Bd's columns: the tiles sit on the process of the same Bd-column
-      // coordinate whose Bd-row coordinate owns Td's column k -> one broadcast along Bd's columns
-      const bool have = t_other.mine(k);
-      T* dst = tpanel[buf];
-      if (ncols > 0) {
-        const T* src = have ? Td.tile(o.jl0, Td.cols.local_of(k)) : nullptr;
-        if (Bd.row_P > 1)
-          tr->bcast(along_col, t_other.owner(k), Bd.row_rank, src, dst, (size_t) ncols * tile_bytes, s_comm);
-        else
-          dst = const_cast<T*>(src);
-      }
-      o.base = dst;
-      o.ts = (long) tile_elems;
-    }
-    else {
-      // crossed: Td's rows are spread like Bd's ROWS.  Column panel k of Td along Bd's rows first, then
-      // tile j down Bd's columns from the Bd-row coordinate that owns Td's row j (broadcast_panel.h:125-210)
-      const long il0 = upper ? 0 : Td.rows.next_local(k + 1);
-      const long il1 = upper ? Td.rows.next_local(k) : Td.ltr;
-      const bool have = Td.cols.mine(k);
-      const T* colp = nullptr;  // my rows [il0, il1) of Td's column k
-      if (il1 > il0) {
-        if (Bd.cols.P > 1) {
-          const T* src = have ? Td.tile(il0, Td.cols.local_of(k)) : nullptr;
-          tr->bcast(along_row, Td.cols.owner(k), Bd.cols.rank, src, tstage[buf], (size_t) (il1 - il0) * tile_bytes, s_comm);
-          colp = tstage[buf];
-        }
-        else {
-          colp = Td.tile(il0, Td.cols.local_of(k));
-        }
-      }
-      if (Bd.row_P > 1) {
-        tr->group_begin();
-        for (long jl = o.jl0; jl < o.jl1; ++jl) {
-          const long gj = Bd.cols.global_of(jl);
-          const int root = Td.rows.owner(gj);
-          const T* src = (Td.rows.rank == root) ? colp + (size_t) (Td.rows.local_of(gj) - il0) * tile_elems : nullptr;
-          tr->bcast(along_col, root, Bd.row_rank, src, tpanel[buf] + (size_t) (jl - o.jl0) * tile_elems, tile_bytes, s_comm);
-        }
-        tr->group_end();
-        o.base = tpanel[buf];
-        o.ts = (long) tile_elems;
-      }
-      else {
-        // I hold every row of Td's column k: tile gj sits at local row gj
-        o.base = colp ? colp + (size_t) (Bd.cols.global_of(o.jl0 < Bd.ltc ? o.jl0 : 0) - il0) * tile_elems : nullptr;
-        o.ts = (long) tile_elems * Bd.cols.P;
-      }
-    }
-    DLAF_HIP_CHECK(hipEventRecord(ev_t[(size_t) s], s_comm));
-  };
+  std::vector<TOperand<T>> top((size_t) nt);
+  TOperandFetch<T> tf{Td, Bd, tr, upper, upper, s_comm, my_diag, winv_all, winv_elems, diag_ws, tpanel, tstage,
+                      ev_free.v.data(), ev_t.v.data(), top};
+  auto fetch_t = [&](long s) { tf.fetch(s); };
 
   auto update = [&](long s, const T* xp, long j0, long j1) {
-    const TOperand& o = top[(size_t) s];
+    const TOperand<T>& o = top[(size_t) s];
     j0 = std::max(j0, o.jl0);
     j1 = std::min(j1, o.jl1);
     if (j0 >= j1 || Bd.ltr == 0)
@@ -425,11 +307,13 @@ void solver_last_profile(double* ms, double* flops) {
     *flops = g_last_sweep_flops;
 }
 
-// Host entry: a (local part of the triangular matrix, column-major lda), b (local part of the m x n right-hand
-// sides, ldb) on the grid; b is overwritten by the solution.
+// Host entry of a canonical sweep (the solve, or the multiplication of multiplication.cpp): a (local part of the
+// triangular matrix, column-major lda), b (local part of the m x n matrix B, ldb) on the grid; b is overwritten by
+// the result.  may_reverse: the one-process reversal of an upper T below is allowed (the solve).
 template <class T>
-int triangular_solver_host(Grid* g, char side, char uplo, char op, char diag, T alpha, const T* a, long lda, int a_isrc,
-                           int a_jsrc, T* b, long ldb, long m, long n, int nb, int b_isrc, int b_jsrc, int nb_free) {
+int triangular_canonical_host(const char* who, CanonicalSweep<T> sweep, bool may_reverse, Grid* g, char side, char uplo,
+                              char op, char diag, T alpha, const T* a, long lda, int a_isrc, int a_jsrc, T* b, long ldb,
+                              long m, long n, int nb, int b_isrc, int b_jsrc, int nb_free) {
   runtime_init();
   (void) grid_transport(*g);
   if (g->nranks > 1 && !g->transport)
@@ -442,8 +326,7 @@ int triangular_solver_host(Grid* g, char side, char uplo, char op, char diag, T 
   const bool unit = (diag == 'U' || diag == 'u');
   const long na = left ? m : n;
   if (left ? (a_isrc != b_isrc) : (a_jsrc != b_jsrc))
-    fatal("[dlaf_mi355x] triangular solver: A and B must share the source process along the triangular "
-          "dimension\n");
+    fatal("[dlaf_mi355x] %s: A and B must share the source process along the triangular dimension\n", who);
 
   // T = A (Right C / Left N), A^H (Right N / Left C), conj(A) (Right T), A^T (Left T)
   bool t_transposed, t_conj;
@@ -474,7 +357,7 @@ int triangular_solver_host(Grid* g, char side, char uplo, char op, char diag, T 
       const char* e = std::getenv("DLAF_MI355X_SOLVER_REVERSE");
       return e ? std::atoi(e) != 0 : true;
     }();
-    const bool reversed = reverse_on && t_upper && g->nranks == 1 && na % nb == 0;
+    const bool reversed = may_reverse && reverse_on && t_upper && g->nranks == 1 && na % nb == 0;
     if (reversed) {
       Td.rev_rows = Td.rev_cols = true;
       Bd.rev_cols = true;  // the view's columns are the triangular dimension
@@ -483,12 +366,19 @@ int triangular_solver_host(Grid* g, char side, char uplo, char op, char diag, T 
     // Left: B_dev = (alpha B)^H = conj(alpha) B^H (the relayout conjugates first, then scales)
     Bd.upload(b, ldb, left, true, left ? conj_el(alpha) : alpha, s);
     DLAF_HIP_CHECK(hipStreamSynchronize(s));
-    solve_canonical(Td, Bd, reversed ? false : t_upper, unit);
+    sweep(Td, Bd, reversed ? false : t_upper, unit);
     Bd.download(b, ldb, left, s);
     DLAF_HIP_CHECK(hipStreamSynchronize(s));
   }
   DLAF_HIP_CHECK(hipStreamDestroy(s));
   return 0;
+}
+
+template <class T>
+int triangular_solver_host(Grid* g, char side, char uplo, char op, char diag, T alpha, const T* a, long lda, int a_isrc,
+                           int a_jsrc, T* b, long ldb, long m, long n, int nb, int b_isrc, int b_jsrc, int nb_free) {
+  return triangular_canonical_host<T>("triangular solver", solve_canonical<T>, true, g, side, uplo, op, diag, alpha, a,
+                                      lda, a_isrc, a_jsrc, b, ldb, m, n, nb, b_isrc, b_jsrc, nb_free);
 }
 
 // ================================================================================ device-resident operands
@@ -554,32 +444,34 @@ static void xform_tiles(T* dst, long dltr, long dltc, const T* src, long sltr, s
   }
 }
 
-// dlaf::triangular_solver on RESIDENT operands: A = a DeviceMatrix (its uplo triangle: a Cholesky factor, or any
-// triangular matrix uploaded as such), B = a general resident matrix, overwritten by the solution.  Nothing crosses
-// PCIe: the operand views of the one device algorithm (X T^H = B) are made by tile transforms on the device.
+// A canonical sweep on RESIDENT operands (dlaf::triangular_solver, or the multiplication): A = a DeviceMatrix (its
+// uplo triangle: a Cholesky factor, or any triangular matrix uploaded as such), B = a general resident matrix,
+// overwritten by the result.  Nothing crosses PCIe: the operand views of the one device algorithm (X T^H = B, or
+// X = B T^H) are made by tile transforms on the device.
 template <class T>
-static int solver_device(char side, char uplo, char op, char diag, T alpha, DeviceMatrix<T>& A, GeneralMatrix<T>& B) {
+int triangular_canonical_device(const char* who, CanonicalSweep<T> sweep, char side, char uplo, char op, char diag,
+                                T alpha, DeviceMatrix<T>& A, GeneralMatrix<T>& B) {
   Grid* g = A.grid;
   if (B.m.grid != g)
-    fatal("[dlaf_mi355x] triangular solver: A and B live on different grids\n");
+    fatal("[dlaf_mi355x] %s: A and B live on different grids\n", who);
   const bool left = (side == 'L' || side == 'l');
   const bool a_upper = (uplo == 'U' || uplo == 'u');
   if (a_upper != A.transposed)
-    fatal("[dlaf_mi355x] triangular solver: uplo '%c' but the resident matrix holds its '%c' triangle\n", uplo, A.uplo);
+    fatal("[dlaf_mi355x] %s: uplo '%c' but the resident matrix holds its '%c' triangle\n", who, uplo, A.uplo);
   const char o = (op == 'n') ? 'N' : (op == 't') ? 'T' : (op == 'c') ? 'C' : op;
   const bool unit = (diag == 'U' || diag == 'u');
   const long m = B.rows_g, n = B.cols_g, na = left ? m : n;
   const int nb = A.nb;
   if (A.n != na || B.m.nb != nb)
-    fatal("[dlaf_mi355x] triangular solver: A is %ld x %ld (block %d), B is %ld x %ld (block %d), side %c\n", A.n, A.n,
-          nb, m, n, B.m.nb, side);
+    fatal("[dlaf_mi355x] %s: A is %ld x %ld (block %d), B is %ld x %ld (block %d), side %c\n", who, A.n, A.n, nb, m, n,
+          B.m.nb, side);
   if (m == 0 || n == 0)
     return 0;
   // the caller's A and its source process (the DeviceMatrix holds the transposed view for uplo U)
   const Axis& a_rows = A.transposed ? A.cols : A.rows;
   const Axis& a_cols = A.transposed ? A.rows : A.cols;
   if (left ? (a_rows.src != B.isrc) : (a_cols.src != B.jsrc))
-    fatal("[dlaf_mi355x] triangular solver: A and B must share the source process along the triangular dimension\n");
+    fatal("[dlaf_mi355x] %s: A and B must share the source process along the triangular dimension\n", who);
   // T = A (Right C / Left N), A^H (Right N / Left C), conj(A) (Right T), A^T (Left T) -- as in triangular_solver_host
   bool t_transposed, t_conj;
   if (left) {
@@ -619,7 +511,7 @@ static int solver_device(char side, char uplo, char op, char diag, T alpha, Devi
         xform_tiles(Bd.tiles, Bd.ltr, Bd.ltc, B.m.tiles, B.m.ltr, te, nb, 5, alpha, true, s);
     }
     DLAF_HIP_CHECK(hipStreamSynchronize(s));
-    solve_canonical(Td, Bd, t_upper, unit);
+    sweep(Td, Bd, t_upper, unit);
     if (left) {
       xform_tiles(B.m.tiles, B.m.ltr, B.m.ltc, Bd.tiles, Bd.ltr, te, nb, 0, T{}, false, s);
       DLAF_HIP_CHECK(hipStreamSynchronize(s));
@@ -632,18 +524,31 @@ static int solver_device(char side, char uplo, char op, char diag, T alpha, Devi
 int triangular_solver_device(char side, char uplo, char op, char diag, const void* alpha, MatrixBase* a, MatrixBase* b) {
   if (!a || !b || a->type != b->type)
     fatal("[dlaf_mi355x] triangular solver: operands of different element types\n");
+  auto run = [&](auto* tag) {
+    using T = std::remove_pointer_t<decltype(tag)>;
+    return triangular_canonical_device<T>("triangular solver", solve_canonical<T>, side, uplo, op, diag,
+                                          *static_cast<const T*>(alpha), static_cast<DeviceMatrix<T>&>(*a),
+                                          static_cast<GeneralMatrix<T>&>(*b));
+  };
   switch (a->type) {
-    case 's': return solver_device<float>(side, uplo, op, diag, *static_cast<const float*>(alpha),
-                                          static_cast<DeviceMatrix<float>&>(*a), static_cast<GeneralMatrix<float>&>(*b));
-    case 'd': return solver_device<double>(side, uplo, op, diag, *static_cast<const double*>(alpha),
-                                           static_cast<DeviceMatrix<double>&>(*a), static_cast<GeneralMatrix<double>&>(*b));
-    case 'c': return solver_device<cfloat>(side, uplo, op, diag, *static_cast<const cfloat*>(alpha),
-                                           static_cast<DeviceMatrix<cfloat>&>(*a), static_cast<GeneralMatrix<cfloat>&>(*b));
-    case 'z': return solver_device<cdouble>(side, uplo, op, diag, *static_cast<const cdouble*>(alpha),
-                                            static_cast<DeviceMatrix<cdouble>&>(*a), static_cast<GeneralMatrix<cdouble>&>(*b));
+    case 's': return run((float*) nullptr);
+    case 'd': return run((double*) nullptr);
+    case 'c': return run((cfloat*) nullptr);
+    case 'z': return run((cdouble*) nullptr);
     default: fatal("[dlaf_mi355x] bad matrix type\n");
   }
 }
+
+#define DLAF_CANONICAL_INST(T)                                                                                   \
+  template int triangular_canonical_host<T>(const char*, CanonicalSweep<T>, bool, Grid*, char, char, char, char, T,  \
+                                            const T*, long, int, int, T*, long, long, long, int, int, int, int);    \
+  template int triangular_canonical_device<T>(const char*, CanonicalSweep<T>, char, char, char, char, T,             \
+                                              DeviceMatrix<T>&, GeneralMatrix<T>&);
+DLAF_CANONICAL_INST(float)
+DLAF_CANONICAL_INST(double)
+DLAF_CANONICAL_INST(cfloat)
+DLAF_CANONICAL_INST(cdouble)
+#undef DLAF_CANONICAL_INST
 
 template int triangular_solver_host<float>(Grid*, char, char, char, char, float, const float*, long, int, int, float*,
                                            long, long, long, int, int, int, int);

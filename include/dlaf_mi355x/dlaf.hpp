@@ -8,6 +8,8 @@
  *     }                                                                       // include/dlaf/factorization/cholesky.h:39-79
  *     dlaf::triangular_solver<Backend::GPU, Device::GPU, T>(grid, side, uplo, op, diag, alpha, a, b);
  *                                                                             // include/dlaf/solver/triangular.h:41-177
+ *     dlaf::triangular_multiplication<Backend::GPU, Device::GPU, T>(grid, side, uplo, op, diag, alpha, a, b);
+ *                                                                     // include/dlaf/multiplication/triangular.h
  *
  * What differs from the reference, by design: there is no pika runtime (the calls are blocking, no pika::wait),
  * Backend::MC does not exist (the library has no CPU path: static_assert), Matrix<T, Device::CPU> stores its
@@ -388,6 +390,43 @@ void triangular_solver(blas::Side side, blas::Uplo uplo, blas::Op op, blas::Diag
                        Matrix<T, Device::CPU>& mat_a, Matrix<T, Device::CPU>& mat_b) {
   comm::CommunicatorGrid grid = comm::CommunicatorGrid::single();
   triangular_solver<B, D, T>(grid, side, uplo, op, diag, alpha, mat_a, mat_b);
+}
+
+// include/dlaf/multiplication/triangular.h: B = alpha op(A) B (Left) / alpha B op(A) (Right), host-resident operands;
+// every op on grids too (the reference's distributed version implements NoTrans only)
+template <Backend B, Device D, class T>
+void triangular_multiplication(comm::CommunicatorGrid& grid, blas::Side side, blas::Uplo uplo, blas::Op op,
+                               blas::Diag diag, T alpha, Matrix<T, Device::CPU>& mat_a, Matrix<T, Device::CPU>& mat_b) {
+  static_assert(B == Backend::GPU, "this library has no CPU backend");
+  auto desc_of = [](const Matrix<T, Device::CPU>& m) {
+    const auto& d = m.distribution();
+    return DLAF_descriptor{(int) d.size().rows(), (int) d.size().cols(), (int) d.block_size().rows(),
+                           (int) d.block_size().cols(), (int) d.source_rank_index().row(),
+                           (int) d.source_rank_index().col(), 0, 0, (int) m.ld()};
+  };
+  int r;
+  if constexpr (std::is_same_v<T, float>)
+    r = dlaf_mi355x_triangular_multiplication_s(grid.context(), (char) side, (char) uplo, (char) op, (char) diag, &alpha,
+                                                mat_a.ptr(), desc_of(mat_a), mat_b.ptr(), desc_of(mat_b));
+  else if constexpr (std::is_same_v<T, double>)
+    r = dlaf_mi355x_triangular_multiplication_d(grid.context(), (char) side, (char) uplo, (char) op, (char) diag, &alpha,
+                                                mat_a.ptr(), desc_of(mat_a), mat_b.ptr(), desc_of(mat_b));
+  else if constexpr (std::is_same_v<T, std::complex<float>>)
+    r = dlaf_mi355x_triangular_multiplication_c(grid.context(), (char) side, (char) uplo, (char) op, (char) diag, &alpha,
+                                                mat_a.ptr(), desc_of(mat_a), mat_b.ptr(), desc_of(mat_b));
+  else
+    r = dlaf_mi355x_triangular_multiplication_z(grid.context(), (char) side, (char) uplo, (char) op, (char) diag, &alpha,
+                                                mat_a.ptr(), desc_of(mat_a), mat_b.ptr(), desc_of(mat_b));
+  if (r != 0)
+    internal::fail("triangular_multiplication");
+}
+
+// the local overload
+template <Backend B, Device D, class T>
+void triangular_multiplication(blas::Side side, blas::Uplo uplo, blas::Op op, blas::Diag diag, T alpha,
+                               Matrix<T, Device::CPU>& mat_a, Matrix<T, Device::CPU>& mat_b) {
+  comm::CommunicatorGrid grid = comm::CommunicatorGrid::single();
+  triangular_multiplication<B, D, T>(grid, side, uplo, op, diag, alpha, mat_a, mat_b);
 }
 
 // include/dlaf/eigensolver/gen_to_std.h:50, :101: A <- inv(L) A inv(L^H) (Lower) / inv(U^H) A inv(U) (Upper) with

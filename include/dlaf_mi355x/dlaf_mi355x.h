@@ -163,6 +163,46 @@ DLAF_EXTERN_C void dlaf_mi355x_pztrsm(char side, char uplo, char op, char diag, 
                                       const int desca[9], dlaf_complex_z* b, int ib, int jb,
                                       const int descb[9]) DLAF_NOEXCEPT;
 
+/* ---- triangular multiplication ------------------------------------------------------------- */
+/* dlaf::triangular_multiplication(grid, side, uplo, op, diag, alpha, A, B), include/dlaf/multiplication/triangular.h
+ * (the reference has no C entry for it; the p?trmm names take ScaLAPACK's argument list):
+ *   side 'L': B = alpha op(A) B,  side 'R': B = alpha B op(A);  B (m x n) is overwritten.
+ * A: na x na triangular (na = m for 'L', n for 'R'), only the uplo triangle is read (diag 'U': its diagonal
+ * is taken as 1), op in N/T/C (every op on every grid), alpha passed by address.  a, b: local column-major parts on
+ * the grid of `context`.  Requirements of this build, as for the solver: square blocks of A, B's block along the
+ * triangular dimension = A's, no sub-matrix offsets, A and B share the source process along the triangular
+ * dimension.  Returns 0; bad arguments terminate like the reference's DLAF_ASSERTs, before the GPU is touched. */
+DLAF_EXTERN_C int dlaf_mi355x_triangular_multiplication_s(int context, char side, char uplo, char op, char diag,
+                                                          const float* alpha, const float* a,
+                                                          struct DLAF_descriptor desca, float* b,
+                                                          struct DLAF_descriptor descb) DLAF_NOEXCEPT;
+DLAF_EXTERN_C int dlaf_mi355x_triangular_multiplication_d(int context, char side, char uplo, char op, char diag,
+                                                          const double* alpha, const double* a,
+                                                          struct DLAF_descriptor desca, double* b,
+                                                          struct DLAF_descriptor descb) DLAF_NOEXCEPT;
+DLAF_EXTERN_C int dlaf_mi355x_triangular_multiplication_c(int context, char side, char uplo, char op, char diag,
+                                                          const dlaf_complex_c* alpha, const dlaf_complex_c* a,
+                                                          struct DLAF_descriptor desca, dlaf_complex_c* b,
+                                                          struct DLAF_descriptor descb) DLAF_NOEXCEPT;
+DLAF_EXTERN_C int dlaf_mi355x_triangular_multiplication_z(int context, char side, char uplo, char op, char diag,
+                                                          const dlaf_complex_z* alpha, const dlaf_complex_z* a,
+                                                          struct DLAF_descriptor desca, dlaf_complex_z* b,
+                                                          struct DLAF_descriptor descb) DLAF_NOEXCEPT;
+DLAF_EXTERN_C void dlaf_mi355x_pstrmm(char side, char uplo, char op, char diag, int m, int n, const float* alpha,
+                                      const float* a, int ia, int ja, const int desca[9], float* b, int ib, int jb,
+                                      const int descb[9]) DLAF_NOEXCEPT;
+DLAF_EXTERN_C void dlaf_mi355x_pdtrmm(char side, char uplo, char op, char diag, int m, int n, const double* alpha,
+                                      const double* a, int ia, int ja, const int desca[9], double* b, int ib, int jb,
+                                      const int descb[9]) DLAF_NOEXCEPT;
+DLAF_EXTERN_C void dlaf_mi355x_pctrmm(char side, char uplo, char op, char diag, int m, int n,
+                                      const dlaf_complex_c* alpha, const dlaf_complex_c* a, int ia, int ja,
+                                      const int desca[9], dlaf_complex_c* b, int ib, int jb,
+                                      const int descb[9]) DLAF_NOEXCEPT;
+DLAF_EXTERN_C void dlaf_mi355x_pztrmm(char side, char uplo, char op, char diag, int m, int n,
+                                      const dlaf_complex_z* alpha, const dlaf_complex_z* a, int ia, int ja,
+                                      const int desca[9], dlaf_complex_z* b, int ib, int jb,
+                                      const int descb[9]) DLAF_NOEXCEPT;
+
 /* ScaLAPACK p?potrs: A X = B with the factor dlaf_p?potrf left in a (two triangular solves; b is overwritten) */
 DLAF_EXTERN_C void dlaf_mi355x_pspotrs(char uplo, int n, int nrhs, const float* a, int ia, int ja, const int desca[9],
                                        float* b, int ib, int jb, const int descb[9], int* info) DLAF_NOEXCEPT;
@@ -320,6 +360,16 @@ DLAF_EXTERN_C int dlaf_mi355x_bt_reduction_to_band_device(int band_size, dlaf_mi
  * -- relayout and PCIe staging excluded -- and the whole-grid algorithmic flops it stands for (m n^2 for side
  * R, m^2 n for side L; x4 complex). */
 DLAF_EXTERN_C int dlaf_mi355x_solver_profile(double* ms, double* flops) DLAF_NOEXCEPT;
+
+/* triangular_multiplication on resident operands (a: the uplo triangle of a dlaf_mi355x_matrix_t, b: a general
+ * resident matrix, overwritten by the product); nothing crosses PCIe.  Same requirements as the host entry. */
+DLAF_EXTERN_C int dlaf_mi355x_triangular_multiplication_device(char side, char uplo, char op, char diag,
+                                                               const void* alpha, dlaf_mi355x_matrix_t a,
+                                                               dlaf_mi355x_gmatrix_t b) DLAF_NOEXCEPT;
+/* Device time (ms, HIP events on the compute stream) of the sweep of the last triangular multiplication on this
+ * process -- relayout and PCIe staging excluded -- and the whole-grid algorithmic flops it stands for (m n^2 for
+ * side R, m^2 n for side L; x4 complex), as dlaf_mi355x_solver_profile. */
+DLAF_EXTERN_C int dlaf_mi355x_multiplication_profile(double* ms, double* flops) DLAF_NOEXCEPT;
 
 /* ---- synthetic input ------------------------------------------------------------------------ */
 /* Fills this process's local array (column-major, ld) of the n x n matrix with the reference's

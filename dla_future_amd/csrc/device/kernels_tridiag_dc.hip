@@ -60,6 +60,14 @@ __device__ __forceinline__ R r_tiny() {
     return R(FLT_MIN);
 }
 
+template <class R>
+__device__ __forceinline__ R r_sqrt_tiny() {
+  if constexpr (sizeof(R) == 8)
+    return R(0x1p-511);  // sqrt(DBL_MIN)
+  else
+    return R(0x1p-63f);  // sqrt(FLT_MIN)
+}
+
 // ======================================================================================= leaves
 // One wave per leaf (size <= 64): implicit QL with Wilkinson shifts (the algorithm of EISPACK tql2 / LAPACK xSTEQR's
 // QL branch); lane r owns row r of the eigenvector matrix, kept in LDS column-major with an odd column stride.
@@ -84,8 +92,11 @@ __global__ __launch_bounds__(64) void dc_leaf_kernel(DcLeafArgs<R> p) {
     for (;;) {
       int m = l;
       for (; m < n - 1; ++m) {
+        // relative test, and an absolute floor sqrt(tiny) for the underflow range (the safmin term of xSTEQR's test): a
+        // strongly graded leaf (entries spanning the exponent range) otherwise stalls on couplings that cannot shrink any
+        // further; T is normalised to max |T| in [1, 2), so the floor is far below eps |T|
         const R dd = fabs(ds[m]) + fabs(ds[m + 1]);
-        if (fabs(es[m]) <= r_eps<R>() * dd)
+        if (fabs(es[m]) <= r_eps<R>() * dd || fabs(es[m]) <= r_sqrt_tiny<R>())
           break;
       }
       if (m == l)
@@ -619,16 +630,58 @@ __global__ __launch_bounds__(256) void dc_finish_kernel(DcMergeArgs<R> p) {
   }
 }
 
-// final: w[i] = d[ord[i]], z[:, i] = q[:, ord[i]]
+// final: w[i] = 2^wexp d[ord[i]] (undoes the normalisation exactly), z[:, i] = q[:, ord[i]]
 template <class R>
-__global__ __launch_bounds__(256) void dc_output_kernel(const R* q, long ldq, const R* d, const int* ord, long n, R* w,
-                                                        R* z, long ldz) {
+__global__ __launch_bounds__(256) void dc_output_kernel(const R* q, long ldq, const R* d, const int* ord, long n, int wexp,
+                                                        R* w, R* z, long ldz) {
   for (long c = blockIdx.y; c < n; c += gridDim.y) {
     const long src = ord[c];
     if (blockIdx.x == 0 && threadIdx.x == 0)
-      w[c] = d[src];
+      w[c] = ldexp(d[src], wexp);
     for (long r = (long) blockIdx.x * 256 + threadIdx.x; r < n; r += (long) gridDim.x * 256)
       z[r + c * ldz] = q[r + src * ldq];
+  }
+}
+
+// max of |x| that lets a NaN through (fmax would drop it)
+template <class R>
+__device__ __forceinline__ R nan_max(R a, R b) {
+  if (a != a)
+    return a;
+  return (b > a || b != b) ? b : a;
+}
+
+// one workgroup: mx[0] = max(|d[0, n)|, |e[0, n - 1)|)
+template <class R>
+__global__ __launch_bounds__(kDcThreads) void dc_maxabs_kernel(const R* d, const R* e, long n, R* mx) {
+  __shared__ R red[kDcThreads / 64];
+  const int tid = threadIdx.x;
+  R m = R(0);
+  for (long i = tid; i < n; i += kDcThreads) {
+    m = nan_max(m, fabs(d[i]));
+    if (i + 1 < n)
+      m = nan_max(m, fabs(e[i]));
+  }
+#pragma unroll
+  for (int off = 32; off >= 1; off >>= 1)
+    m = nan_max(m, __shfl_xor(m, off));
+  if ((tid & 63) == 0)
+    red[tid >> 6] = m;
+  __syncthreads();
+  if (tid == 0) {
+    R t = R(0);
+    for (int w = 0; w < kDcThreads / 64; ++w)
+      t = nan_max(t, red[w]);
+    mx[0] = t;
+  }
+}
+
+template <class R>
+__global__ __launch_bounds__(256) void dc_scale_kernel(R* d, R* e, long n, int k) {
+  for (long i = (long) blockIdx.x * 256 + threadIdx.x; i < n; i += (long) gridDim.x * 256) {
+    d[i] = ldexp(d[i], k);
+    if (i + 1 < n)
+      e[i] = ldexp(e[i], k);
   }
 }
 
@@ -648,6 +701,16 @@ __global__ __launch_bounds__(256) void dc_cuppen_kernel(R* d, const R* e, const 
 
 }  // namespace
 
+template <class R>
+void launch_dc_maxabs(const R* d, const R* e, long n, R* mx, hipStream_t s) {
+  hipLaunchKernelGGL((dc_maxabs_kernel<R>), dim3(1), dim3(kDcThreads), 0, s, d, e, n, mx);
+}
+template <class R>
+void launch_dc_scale(R* d, R* e, long n, int k, hipStream_t s) {
+  if (n <= 0)
+    return;
+  hipLaunchKernelGGL((dc_scale_kernel<R>), dim3((unsigned) std::min<long>(1024, (n + 255) / 256)), dim3(256), 0, s, d, e, n, k);
+}
 template <class R>
 void launch_dc_cuppen(R* d, const R* e, const long* bounds, R* rho, int nsplit, hipStream_t s) {
   if (nsplit <= 0)
@@ -687,21 +750,23 @@ void launch_dc_finish(const DcMergeArgs<R>& a, int nmerges, int nmax, hipStream_
                      0, s, a);
 }
 template <class R>
-void launch_dc_output(const R* q, long ldq, const R* d, const int* ord, long n, R* w, R* z, long ldz, hipStream_t s) {
+void launch_dc_output(const R* q, long ldq, const R* d, const int* ord, long n, int wexp, R* w, R* z, long ldz, hipStream_t s) {
   if (n <= 0)
     return;
   hipLaunchKernelGGL((dc_output_kernel<R>), dim3((unsigned) std::min<long>(8, (n + 255) / 256), (unsigned) std::min<long>(n, 8192)),
-                     dim3(256), 0, s, q, ldq, d, ord, n, w, z, ldz);
+                     dim3(256), 0, s, q, ldq, d, ord, n, wexp, w, z, ldz);
 }
 
 #define INST(R)                                                                                        \
+  template void launch_dc_maxabs<R>(const R*, const R*, long, R*, hipStream_t);                        \
+  template void launch_dc_scale<R>(R*, R*, long, int, hipStream_t);                                    \
   template void launch_dc_cuppen<R>(R*, const R*, const long*, R*, int, hipStream_t);                  \
   template void launch_dc_leaves<R>(const DcLeafArgs<R>&, int, hipStream_t);                           \
   template void launch_dc_prepare<R>(const DcMergeArgs<R>&, int, hipStream_t);                         \
   template void launch_dc_rotate_gather<R>(const DcMergeArgs<R>&, int, int, hipStream_t);              \
   template void launch_dc_secular<R>(const DcMergeArgs<R>&, int, int, hipStream_t);                    \
   template void launch_dc_finish<R>(const DcMergeArgs<R>&, int, int, hipStream_t);                     \
-  template void launch_dc_output<R>(const R*, long, const R*, const int*, long, R*, R*, long, hipStream_t);
+  template void launch_dc_output<R>(const R*, long, const R*, const int*, long, int, R*, R*, long, hipStream_t);
 INST(float)
 INST(double)
 #undef INST

@@ -65,6 +65,12 @@ struct DcMergeArgs {
   DcRot<R>* rots;
 };
 
+// normalisation of T by a power of two (xSTEDC scales T to unit max-norm before DLAED0; a power of two keeps it exact):
+// mx[0] = max(|d[0, n)|, |e[0, n - 1)|) (NaN if any entry is NaN); d, e <- 2^k d, 2^k e
+template <class R>
+void launch_dc_maxabs(const R* d, const R* e, long n, R* mx, hipStream_t s);
+template <class R>
+void launch_dc_scale(R* d, R* e, long n, int k, hipStream_t s);
 template <class R>
 void launch_dc_cuppen(R* d, const R* e, const long* bounds, R* rho, int nsplit, hipStream_t s);
 template <class R>
@@ -77,7 +83,8 @@ template <class R>
 void launch_dc_secular(const DcMergeArgs<R>& a, int nmerges, int kmax, hipStream_t s);
 template <class R>
 void launch_dc_finish(const DcMergeArgs<R>& a, int nmerges, int nmax, hipStream_t s);
+// w[i] = 2^wexp d[ord[i]], z[:, i] = q[:, ord[i]]
 template <class R>
-void launch_dc_output(const R* q, long ldq, const R* d, const int* ord, long n, R* w, R* z, long ldz, hipStream_t s);
+void launch_dc_output(const R* q, long ldq, const R* d, const int* ord, long n, int wexp, R* w, R* z, long ldz, hipStream_t s);
 
 }  // namespace dlaf_mi355x

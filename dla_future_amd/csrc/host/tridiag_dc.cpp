@@ -6,6 +6,7 @@
 // per merge; here the merges of one HEIGHT of the tree run together (batched launches), the host learns the
 // non-deflated counts of a whole level with one small copy and then issues that level's products.
 #include <algorithm>
+#include <cmath>
 #include <cstdlib>
 #include <vector>
 
@@ -130,6 +131,25 @@ int tridiag_solver_device(long n, int /*nb*/, R* d, R* e, R* w, R* z, long ldz, 
   if (!hm.empty())
     DLAF_HIP_CHECK(hipMemcpyAsync(d_merges, hm.data(), hm.size() * sizeof(DcMerge), hipMemcpyHostToDevice, s));
 
+  // T <- 2^-k T with 2^k <= max(|d|, |e|) < 2^(k+1): the deflation tolerance 8 eps max(|d|, |z|) mixes the scale of T with
+  // that of the unit vector z, so without it a T of small norm deflates couplings that are not negligible (xSTEDC scales
+  // to unit max-norm before DLAED0 for the same reason).  A power of two is exact in both directions, so the solver's
+  // result for 2^j T is 2^j times its result for T, bit for bit.  Every rank of a grid sees the same d, e and takes the
+  // same k.  d and e are work arrays: no caller reads them afterwards.
+  int wexp = 0;
+  {
+    R* d_mx = dcalloc<R>(1);
+    R mx = R(0);
+    launch_dc_maxabs(d, e, n, d_mx, s);
+    DLAF_HIP_CHECK(hipMemcpyAsync(&mx, d_mx, sizeof(R), hipMemcpyDeviceToHost, s));
+    DLAF_HIP_CHECK(hipStreamSynchronize(s));
+    DLAF_HIP_CHECK(pool_free(d_mx));
+    if (mx > R(0) && std::isfinite(mx)) {
+      wexp = std::ilogb(mx);
+      if (wexp != 0)
+        launch_dc_scale(d, e, n, -wexp, s);
+    }
+  }
   launch_dc_cuppen(d, e, d_bounds, d_rho, (int) bounds.size(), s);
   DcLeafArgs<R> la;
   la.d = d;
@@ -264,7 +284,7 @@ int tridiag_solver_device(long n, int /*nb*/, R* d, R* e, R* w, R* z, long ldz, 
     launch_dc_finish(a, cnt, nmax, s);
     first = last;
   }
-  launch_dc_output(q, ldq, d, iv, n, w, z, ldz, s);
+  launch_dc_output(q, ldq, d, iv, n, wexp, w, z, ldz, s);
   int h_info = 0;
   DLAF_HIP_CHECK(hipMemcpyAsync(&h_info, info, sizeof(int), hipMemcpyDeviceToHost, s));
   DLAF_HIP_CHECK(hipStreamSynchronize(s));

@@ -204,3 +204,198 @@ def check_eigensolver(a_full: np.ndarray, evals: np.ndarray, evecs: np.ndarray):
     res_ok = bool(np.all((diff <= tol) | (diff <= tol * np.abs(el))))
     return {"sorted": srt, "orth": orth, "orth_bar": 10 * m * err, "residual": float(diff.max(initial=0)),
             "residual_bar": tol, "residual_ok": res_ok}
+
+
+# ------------------------------------------------------------------ extended-precision reference of the tridiagonal solver
+def sturm_eigvals(d: np.ndarray, e: np.ndarray, iters: int = 80) -> np.ndarray:
+    """All eigenvalues (ascending, np.longdouble) of the symmetric tridiagonal matrix with diagonal d and off-diagonal
+    e[:n - 1], by Sturm-count bisection in 80-bit long double from the Gershgorin bounds: `iters` halvings of every
+    bracket at once (one numpy operation per row on all n brackets), a bracket of width (hi - lo) 2^-iters at the end.
+    A zero pivot of the LDL^T recurrence is replaced by `tiny`."""
+    ld = np.longdouble
+    assert np.finfo(ld).eps < 1e-18, "sturm_eigvals needs an 80-bit long double (x87): this platform has none"
+    d = np.asarray(d).astype(ld)
+    n = d.shape[0]
+    if n == 0:
+        return np.zeros(0, dtype=ld)
+    e = np.asarray(e).astype(ld)[:n - 1]
+    ae = np.abs(e)
+    r = np.zeros(n, dtype=ld)
+    r[:-1] += ae
+    r[1:] += ae
+    lo0, hi0 = np.min(d - r), np.max(d + r)
+    pad = (hi0 - lo0 + max(abs(lo0), abs(hi0))) * np.finfo(ld).eps * 4 * n
+    lo = np.full(n, lo0 - pad, dtype=ld)
+    hi = np.full(n, hi0 + pad, dtype=ld)
+    if hi0 == lo0 == 0:
+        return np.zeros(n, dtype=ld)
+    k = np.arange(n)
+    e2 = e * e
+    tiny = np.finfo(ld).tiny
+    q, t = np.empty(n, dtype=ld), np.empty(n, dtype=ld)
+    neg = np.empty(n, dtype=bool)
+    cnt = np.empty(n, dtype=np.int64)
+    with np.errstate(over="ignore", divide="ignore", invalid="ignore"):
+        for _ in range(iters):
+            x = lo + (hi - lo) / 2
+            np.subtract(d[0], x, out=q)
+            if not q.all():
+                q[q == 0] = tiny
+            np.less(q, 0, out=neg)
+            cnt[:] = neg
+            for i in range(1, n):
+                np.divide(e2[i - 1], q, out=t)
+                np.subtract(d[i], x, out=q)
+                q -= t
+                if not q.all():
+                    q[q == 0] = tiny
+                np.less(q, 0, out=neg)
+                cnt += neg
+            # cnt = number of eigenvalues below x
+            above = cnt > k
+            hi = np.where(above, x, hi)
+            lo = np.where(above, lo, x)
+    return lo + (hi - lo) / 2
+
+
+def check_tridiag_solution(d, e, w, z, dtype, w_ref=None) -> dict:
+    """Findings of a tridiagonal eigensolver's (w, z) for the tridiagonal matrix T = (d, e), all relative to
+    |T|_2 = max |w_ref| (w_ref: sturm_eigvals(d, e) unless given) and in units of eps of `dtype`: sorted,
+    eig = max |w - w_ref| / (eps |T|), residual = max_j |T z_j - w_j z_j|_inf / (eps |T|) (long double), orth =
+    max |Z^T Z - I| / eps (float64 products)."""
+    ld = np.longdouble
+    eps = float(np.finfo(dtype).eps)
+    n = len(d)
+    if w_ref is None:
+        w_ref = sturm_eigvals(d, e)
+    tn = float(np.abs(w_ref).max(initial=0))
+    unit = eps * tn if tn > 0 else np.finfo(np.float64).tiny
+    wl = np.asarray(w).astype(ld)
+    out = {"n": n, "norm": tn, "sorted": bool(np.all(np.diff(wl) >= 0)),
+           "eig": float(np.abs(wl - np.asarray(w_ref, dtype=ld)).max(initial=0)) / unit}
+    dl = np.asarray(d).astype(ld)
+    el = np.asarray(e).astype(ld)[:max(n - 1, 0)]
+    res = []  # per chunk of columns; np.max of them lets a NaN through (the built-in max would drop it)
+    for c0 in range(0, n, 256):
+        zl = np.asarray(z[:, c0:c0 + 256]).astype(ld)
+        tz = dl[:, None] * zl
+        tz[:-1] += el[:, None] * zl[1:]
+        tz[1:] += el[:, None] * zl[:-1]
+        tz -= zl * wl[None, c0:c0 + 256]
+        res.append(np.abs(tz).max(initial=0))
+    out["residual"] = float(np.max(res, initial=0)) / unit
+    z64 = np.asarray(z, dtype=np.float64)
+    out["orth"] = float(np.abs(z64.T @ z64 - np.eye(n)).max(initial=0)) / eps
+    return out
+
+
+LEAF = 64  # the solver's default leaf size: its merge boundaries are at rows 64 j - 1 / 64 j
+
+FAMILIES = ["zero", "const", "diag", "rand_neg", "rand_alt", "rand_mixed", "clement", "wilkinson", "glued_wilk_1e-14",
+            "glued_wilk_sqrteps", "graded", "dlatms_a", "dlatms_b", "dlatms_c", "dlatms_d", "dlatms_e", "rho0",
+            "zero_e_inside", "repeated"]
+
+
+def _wilkinson(m: int):
+    """W+ of order m: d_i = |(m - 1)/2 - i|, e = 1 (W+_{2k+1} for odd m)."""
+    return np.abs((m - 1) / 2 - np.arange(m)), np.ones(max(m - 1, 0))
+
+
+def _glued(block: int, n: int, glue_rel: float):
+    bd, be = _wilkinson(block)
+    bn = float(np.abs(np.linalg.eigvalsh(np.diag(bd) + np.diag(be, 1) + np.diag(be, -1))).max())
+    reps = -(-n // block)
+    d = np.tile(bd, reps)[:n]
+    e = np.tile(np.append(be, bn * glue_rel), reps)[:max(n - 1, 0)]
+    return d, e
+
+
+def _dlatms(mode: str, n: int, dtype, rng):
+    """Q Lambda Q^T (Q Haar-distributed) reduced to tridiagonal form in float64 (LAPACK dsytrd), Lambda of the
+    xLATMS modes with kappa = 1/eps of `dtype` and random signs."""
+    import scipy.linalg as sl
+    kappa = 1 / float(np.finfo(dtype).eps)
+    i = np.arange(n)
+    if mode == "a":
+        lam = np.full(n, 1 / kappa)
+        lam[0] = 1
+    elif mode == "b":
+        lam = np.ones(n)
+        lam[-1] = 1 / kappa
+    elif mode == "c":
+        lam = kappa ** (-i / max(n - 1, 1))
+    elif mode == "d":
+        lam = 1 - i / max(n - 1, 1) * (1 - 1 / kappa)
+    else:
+        lam = np.exp(-rng.uniform(0, np.log(kappa), n))
+    lam = lam * rng.choice([-1.0, 1.0], n)
+    if n == 1:
+        return lam.copy(), np.zeros(0)
+    q, rr = np.linalg.qr(rng.standard_normal((n, n)))
+    q *= np.sign(np.diag(rr))[None, :]
+    a = (q * lam[None, :]) @ q.T
+    a = (a + a.T) / 2
+    _, dd, ee, _, info = sl.lapack.dsytrd(a, lower=1)
+    assert info == 0
+    return dd, ee
+
+
+def tridiag_family(name: str, n: int, dtype, seed: int = 0):
+    """(d, e) of the named test-matrix family (FAMILIES), in `dtype`, e of length max(n - 1, 0).  Deterministic in
+    (name, n, dtype, seed).  The classes of the LAPACK xSTEDC tester (xCHKST: zero, constant / random diagonal,
+    Clement, Wilkinson, glued Wilkinson, xLATMS spectra) and of the tridiagonal test-set literature (graded), plus
+    the structures of this solver's divide & conquer tree (leaves of LEAF rows): rho = 0 at merge boundaries, zero
+    couplings inside leaves, repeated blocks whose merges tie."""
+    dtype = np.dtype(dtype)
+    rng = np.random.default_rng([seed, n, sum(map(ord, name)), dtype.itemsize])
+    m = max(n - 1, 0)
+    eps = float(np.finfo(dtype).eps)
+    if name == "zero":
+        d, e = np.zeros(n), np.zeros(m)
+    elif name == "const":
+        d, e = np.full(n, -0.3), np.zeros(m)
+    elif name == "diag":
+        d, e = rng.permutation(np.linspace(-1, 1, n) + rng.uniform(0, 0.5 / max(n, 1), n)), np.zeros(m)
+    elif name.startswith("rand_"):
+        d = rng.uniform(-1, 1, n)
+        e = rng.uniform(0.05, 1, m)
+        if name == "rand_neg":
+            e = -e
+        elif name == "rand_alt":
+            e = e * (-1.0) ** np.arange(m)
+        else:
+            e = e * rng.choice([-1.0, 1.0], m)
+    elif name == "clement":
+        i = np.arange(1, n)
+        d, e = np.zeros(n), np.sqrt(i * (n - i))
+    elif name == "wilkinson":
+        d, e = _wilkinson(n)
+    elif name == "glued_wilk_1e-14":
+        d, e = _glued(21, n, 1e-14)
+    elif name == "glued_wilk_sqrteps":
+        d, e = _glued(21, n, np.sqrt(eps))
+    elif name == "graded":
+        # d_i = 2^(-i s), e_i = 2^(-(i + 1/2) s): the smallest entry stays two binades above the smallest normal number
+        span = -np.log2(float(np.finfo(dtype).tiny)) - 2
+        s = span / max(n - 1, 1)
+        i = np.arange(n, dtype=np.float64)
+        d, e = 2.0 ** (-i * s), 2.0 ** (-(i[:m] + 0.5) * s)
+    elif name.startswith("dlatms_"):
+        d, e = _dlatms(name[-1], n, dtype, rng)
+    elif name == "rho0":
+        d, e = rng.uniform(-1, 1, n), rng.uniform(-1, 1, m)
+        e[LEAF - 1::LEAF] = 0
+    elif name == "zero_e_inside":
+        d, e = rng.uniform(-1, 1, n), rng.uniform(-1, 1, m)
+        for r in (10, 31, 32, 62):
+            e[r::LEAF] = 0
+    elif name == "repeated":
+        bd, be = rng.uniform(-1, 1, LEAF), rng.uniform(-1, 1, LEAF - 1)
+        bn = float(np.abs(np.linalg.eigvalsh(np.diag(bd) + np.diag(be, 1) + np.diag(be, -1))).max())
+        glue = eps * 2.0 ** np.ceil(np.log2(bn))
+        reps = -(-n // LEAF)
+        d = np.tile(bd, reps)[:n]
+        e = np.tile(np.append(be, glue), reps)[:m]
+    else:
+        raise ValueError(f"unknown family {name}")
+    return np.asarray(d, dtype=dtype), np.asarray(e, dtype=dtype)

@@ -19,6 +19,8 @@
 // accumulate per wave in LDS and are summed once.
 #include <cstdio>
 #include <cstdlib>
+#include <limits>
+#include <type_traits>
 
 #include "device_api.hpp"
 #include "lane_ops.hpp"
@@ -152,13 +154,63 @@ __global__ __launch_bounds__(kThreads) void band_extract_kernel(const T* tiles, 
   }
 }
 
+// ---- normalisation of the band copy by a power of two.  The max of |Re|, |Im| is kept as the bits of a non-negative
+// real: their unsigned order is the order of the values, and a NaN (sign cleared) lies above +inf, so it survives.
+template <class R>
+using MaxBits = std::conditional_t<sizeof(R) == 8, unsigned long long, unsigned>;
+
+template <class R>
+__device__ __forceinline__ MaxBits<R> abs_bits(R x) {
+  return __builtin_bit_cast(MaxBits<R>, fabs(x));
+}
+
+// k with 2^k <= max < 2^(k + 1); 0 for an all-zero band and for a band that holds an inf or a NaN (left as it is)
+template <class R>
+__device__ __forceinline__ int band_scale_exp(const MaxBits<R>* mx) {
+  const R m = __builtin_bit_cast(R, *mx);
+  return (m > R(0) && m <= std::numeric_limits<R>::max()) ? ilogb(m) : 0;
+}
+
 template <class T>
-__global__ __launch_bounds__(kThreads) void tridiag_extract_kernel(const T* band, long n, int b, real_t<T>* d,
+__global__ __launch_bounds__(kThreads) void band_maxabs_kernel(const T* band, long total, MaxBits<real_t<T>>* mx) {
+  using R = real_t<T>;
+  using B = MaxBits<R>;
+  B m = 0;
+  for (long i = (long) blockIdx.x * kThreads + threadIdx.x; i < total; i += (long) gridDim.x * kThreads) {
+    const T v = band[i];
+    const B br = abs_bits(re_of(v)), bi = abs_bits(im_of(v));
+    m = br > m ? br : m;
+    m = bi > m ? bi : m;
+  }
+#pragma unroll
+  for (int off = 32; off >= 1; off >>= 1) {
+    const B o = __shfl_xor(m, off);
+    m = o > m ? o : m;
+  }
+  if ((threadIdx.x & 63) == 0 && m != 0)
+    atomicMax(mx, m);
+}
+
+template <class T>
+__global__ __launch_bounds__(kThreads) void band_scale_kernel(T* band, long total, const MaxBits<real_t<T>>* mx) {
+  const int k = band_scale_exp<real_t<T>>(mx);
+  if (k == 0)
+    return;
+  for (long i = (long) blockIdx.x * kThreads + threadIdx.x; i < total; i += (long) gridDim.x * kThreads) {
+    const T v = band[i];
+    band[i] = make_el<T>(ldexp(re_of(v), -k), ldexp(im_of(v), -k));
+  }
+}
+
+template <class T>
+__global__ __launch_bounds__(kThreads) void tridiag_extract_kernel(const T* band, long n, int b,
+                                                                   const MaxBits<real_t<T>>* mx, real_t<T>* d,
                                                                    real_t<T>* e) {
   const long i = (long) blockIdx.x * kThreads + threadIdx.x;
+  const int k = band_scale_exp<real_t<T>>(mx);
   if (i < n) {
-    d[i] = re_of(band[i * 2 * b]);
-    e[i] = (i + 1 < n) ? re_of(band[i * 2 * b + 1]) : real_t<T>(0);
+    d[i] = ldexp(re_of(band[i * 2 * b]), k);
+    e[i] = (i + 1 < n) ? ldexp(re_of(band[i * 2 * b + 1]), k) : real_t<T>(0);
   }
 }
 
@@ -1159,11 +1211,24 @@ void launch_band_extract(const T* tiles, long ltr, int nb, int pr, int ri, int p
 }
 
 template <class T>
-void launch_tridiag_extract(const T* band, long n, int b, real_t<T>* d, real_t<T>* e, hipStream_t stream) {
+void launch_band_normalise(T* band, long n, int b, unsigned long long* mx, hipStream_t stream) {
+  using B = MaxBits<real_t<T>>;
+  (void) hipMemsetAsync(mx, 0, sizeof(unsigned long long), stream);
+  const long total = n * 2 * b;
+  if (total <= 0)
+    return;
+  const unsigned g = (unsigned) std::min<long>((total + kThreads - 1) / kThreads, 2048);
+  hipLaunchKernelGGL((band_maxabs_kernel<T>), dim3(g), dim3(kThreads), 0, stream, band, total, reinterpret_cast<B*>(mx));
+  hipLaunchKernelGGL((band_scale_kernel<T>), dim3(g), dim3(kThreads), 0, stream, band, total, reinterpret_cast<const B*>(mx));
+}
+
+template <class T>
+void launch_tridiag_extract(const T* band, long n, int b, const unsigned long long* mx, real_t<T>* d, real_t<T>* e,
+                            hipStream_t stream) {
   if (n <= 0)
     return;
   hipLaunchKernelGGL((tridiag_extract_kernel<T>), dim3((unsigned) ((n + kThreads - 1) / kThreads)), dim3(kThreads), 0,
-                     stream, band, n, b, d, e);
+                     stream, band, n, b, reinterpret_cast<const MaxBits<real_t<T>>*>(mx), d, e);
 }
 
 template <class T>
@@ -1237,7 +1302,9 @@ void launch_b2t_expand(const T* vout, long ldv, long n, int b, T* vx, T* taus, h
 
 #define INST(T)                                                                                                      \
   template void launch_band_extract<T>(const T*, long, int, int, int, int, int, long, int, T*, hipStream_t);        \
-  template void launch_tridiag_extract<T>(const T*, long, int, real_t<T>*, real_t<T>*, hipStream_t);                \
+  template void launch_band_normalise<T>(T*, long, int, unsigned long long*, hipStream_t);                        \
+  template void launch_tridiag_extract<T>(const T*, long, int, const unsigned long long*, real_t<T>*, real_t<T>*,   \
+                                          hipStream_t);                                                             \
   template void launch_band_to_tridiag<T>(T*, long, int, T*, long, unsigned*, int*, hipStream_t);                   \
   template void launch_b2t_expand<T>(const T*, long, long, int, T*, T*, hipStream_t, bool);                                \
   template void launch_rows_to_tiles<T>(const T*, long, long, long, int, int, int, long, long, T*, hipStream_t);

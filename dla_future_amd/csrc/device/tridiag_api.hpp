@@ -29,7 +29,8 @@ void launch_band_extract(const T* tiles, long ltr, int nb, int pr, int ri, int p
 // mc.h:683-709; the register kernel waits for step t and the first column of step t + 1, kernels_tridiag.hip).  Hand-offs between workgroups: write-through stores, sc1 loads, one progress word per sweep.
 //   vout (n x n, ldv): the compact reflectors, tau in the place of the leading 1 (band_to_tridiag.h:56-63)
 //   sync: b2t_sync_words(n) unsigned words, zeroed by the launcher
-// Afterwards d[i] = Re band[i * ldb], e[i] = Re band[i * ldb + 1] (launch_tridiag_extract).
+// Afterwards d[i] = 2^k Re band[i * ldb], e[i] = 2^k Re band[i * ldb + 1] (launch_tridiag_extract, k of
+// launch_band_normalise).
 template <class T>
 void launch_band_to_tridiag(T* band, long n, int b, T* vout, long ldv, unsigned* sync, int* info, hipStream_t stream);
 // (a sweep's progress word has a 128-byte line to itself: pollers and publishers of neighbouring sweeps would
@@ -38,8 +39,15 @@ constexpr int kB2tProgressStride = 32;
 inline size_t b2t_sync_words(long n) {
   return (size_t) n * kB2tProgressStride + 64;
 }
+// The band copy (n columns) <- 2^-k band copy, 2^k <= max(|Re|, |Im|) < 2^(k + 1), k = 0 for a band that is zero or
+// not finite; mx (one 8-byte device word) keeps that max for launch_tridiag_extract.  The reflectors' xLARFG sums
+// squares unscaled: in [1, 2) they neither overflow nor underflow for any scale of A, and a power of two is exact, so
+// v(2^j A) = v(A) and (d, e)(2^j A) = 2^j (d, e)(A) bit for bit (LAPACK's xLARFG rescales for the same reason).
 template <class T>
-void launch_tridiag_extract(const T* band, long n, int b, real_t<T>* d, real_t<T>* e, hipStream_t stream);
+void launch_band_normalise(T* band, long n, int b, unsigned long long* mx, hipStream_t stream);
+template <class T>
+void launch_tridiag_extract(const T* band, long n, int b, const unsigned long long* mx, real_t<T>* d, real_t<T>* e,
+                            hipStream_t stream);
 int b2t_max_band();
 
 // ------------------------------------------------------------------------------------------ band <- tridiagonal

@@ -112,13 +112,18 @@ int band_to_tridiag_device(DeviceMatrix<T>& A, int band, real_t<T>* d, real_t<T>
   if (dist)
     tr->allreduce_sum(bandm, (size_t) n * 2 * band, TypeInfo<T>::tag, 'A', s);
   DLAF_HIP_CHECK(hipMemset2DAsync(v, (size_t) ldv * sizeof(T), 0, (size_t) n * sizeof(T), (size_t) n, s));
+  // the bulge chase works on 2^-k A, max(|Re|, |Im|) in [1, 2): its unscaled sums of squares neither overflow nor
+  // underflow whatever the scale of A (every rank holds the same band after the all-reduce and takes the same k)
+  unsigned long long* mx = ealloc<unsigned long long>(1);
+  launch_band_normalise(bandm, n, band, mx, s);
   launch_band_to_tridiag(bandm, n, band, v, ldv, sync, A.info, s);
-  launch_tridiag_extract(bandm, n, band, d, e, s);
+  launch_tridiag_extract(bandm, n, band, mx, d, e, s);
   int h_info = 0;
   DLAF_HIP_CHECK(hipMemcpyAsync(&h_info, A.info, sizeof(int), hipMemcpyDeviceToHost, s));
   g_stage_ms[1] = timer.stop();
   DLAF_HIP_CHECK(pool_free(bandm));
   DLAF_HIP_CHECK(pool_free(sync));
+  DLAF_HIP_CHECK(pool_free(mx));
   if (h_info == kInfoSchedulingFailure)
     fatal("[dlaf_mi355x] band_to_tridiagonal: a sweep gave up waiting for its predecessor (the workgroup that owns it "
           "made no progress)\n");

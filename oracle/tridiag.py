@@ -399,3 +399,151 @@ def tridiag_family(name: str, n: int, dtype, seed: int = 0):
     else:
         raise ValueError(f"unknown family {name}")
     return np.asarray(d, dtype=dtype), np.asarray(e, dtype=dtype)
+
+
+# ------------------------------------------------------------------ long-double checkers of band -> tridiagonal
+# Each returns (ratio to its bar, where): a stage passes when ratio <= 1.  A NaN anywhere makes the ratio NaN (which
+# fails `ratio <= 1`); there is no absolute floor, so a matrix of any scale is held to its own norm.
+def _ld_type(dtype):
+    return np.clongdouble if is_complex(dtype) else np.longdouble
+
+
+def _eps(dtype) -> float:
+    return float(np.finfo(np.zeros(0, dtype=dtype).real.dtype).eps)
+
+
+def _ratio(err, bar) -> float:
+    err = float(err)
+    if err != err:
+        return float("nan")
+    if bar > 0:
+        return err / bar
+    return 0.0 if err == 0 else float("inf")
+
+
+def hermitian_band_matmul(a: np.ndarray, band: int, x: np.ndarray):
+    """(A x, |A|_F) in long double, A the Hermitian band matrix of the lower band of `a` (the diagonal's imaginary part
+    dropped), one diagonal at a time."""
+    n = a.shape[0]
+    ldt = _ld_type(a.dtype)
+    diag = np.diagonal(a).real.astype(np.longdouble)
+    y = diag[:, None] * x
+    fro = np.sum(diag ** 2)
+    for o in range(1, min(band, n - 1) + 1):
+        sub = np.diagonal(a, -o).astype(ldt)  # A(i + o, i)
+        y[o:] += sub[:, None] * x[:n - o]
+        y[:n - o] += sub.conj()[:, None] * x[o:]
+        fro += 2 * np.sum(np.abs(sub) ** 2)
+    return y, np.sqrt(fro)
+
+
+def b2t_backward_error(a: np.ndarray, band: int, d, e, v, nprobe: int = 8, seed: int = 0):
+    """|A X - Q T Q^H X|_F / (n eps |A|_F |X|_F) on `nprobe` random probe columns X, in long double (A: the Hermitian
+    band matrix of the lower band of `a`, Q from v by apply_q)."""
+    n = a.shape[0]
+    if n == 0:
+        return 0.0, "n = 0"
+    ldt = _ld_type(a.dtype)
+    rng = np.random.default_rng(seed)
+    x = rng.standard_normal((n, nprobe))
+    if is_complex(a.dtype):
+        x = x + 1j * rng.standard_normal((n, nprobe))
+    x = x.astype(ldt)
+    vl = np.asarray(v).astype(ldt)
+    dl = np.asarray(d).astype(np.longdouble)
+    el = np.asarray(e).astype(np.longdouble)[:n - 1]
+    y = apply_q(vl, band, x, adjoint=True)
+    ty = dl[:, None] * y
+    ty[:-1] += el[:, None] * y[1:]
+    ty[1:] += el[:, None] * y[:-1]
+    ax, an = hermitian_band_matmul(a, band, x)
+    r = ax - apply_q(vl, band, ty)
+    xn = np.sqrt(np.sum(np.abs(x) ** 2))
+    err = np.sqrt(np.sum(np.abs(r) ** 2))
+    if not (np.all(np.isfinite(dl)) and np.all(np.isfinite(el)) and np.all(np.isfinite(vl))):
+        err = float("nan")
+    return _ratio(err, n * _eps(a.dtype) * float(an) * float(xn)), f"|A X - Q T Q^H X| = {float(err):.3e}"
+
+
+def b2t_reflector_unitarity(v, band: int, c: float = 2.0):
+    """max over the reflector slots of |2 Re tau - |tau|^2 v^H v| / (c (b + 8) eps): H = I - tau v v^H is unitary exactly
+    when that is zero (b eps for the sum v^H v, 8 eps for rounding the stored tau, |tau| <= 2, itself).  `where` names the
+    worst (sweep, step)."""
+    v = np.asarray(v)
+    n = v.shape[0]
+    bar = c * (band + 8) * _eps(v.dtype)
+    worst, where = 0.0, "no reflector"
+    for sweep, step, first, size, pos in reflector_list(n, band, v.dtype):
+        col = v[pos:pos + size, sweep].astype(_ld_type(v.dtype))
+        tau = col[0]
+        vhv = 1 + np.sum(np.abs(col[1:]) ** 2)
+        dev = float(abs(2 * tau.real - abs(tau) ** 2 * vhv))
+        if dev != dev:
+            return float("nan"), f"NaN in the reflector of (sweep {sweep}, step {step})"
+        if dev > worst or where == "no reflector":
+            worst, where = dev, f"(sweep {sweep}, step {step})"
+    return _ratio(worst, bar), where
+
+
+def b2t_layout(v, band: int, d, e):
+    """v is exactly zero outside the reflector slots of reflector_list, and d, e are finite: ratio 0 when so, inf (or NaN)
+    when not."""
+    v = np.asarray(v)
+    n = v.shape[0]
+    slot = np.zeros((n, n), dtype=bool)
+    for sweep, step, first, size, pos in reflector_list(n, band, v.dtype):
+        slot[pos:pos + size, sweep] = True
+    stray = np.argwhere(~slot & (v != 0))
+    if not (np.all(np.isfinite(d)) and np.all(np.isfinite(e))):
+        return float("nan"), "d or e not finite"
+    if stray.size:
+        r, c = stray[0]
+        return float("inf"), f"{len(stray)} entries of v outside the slots, first ({r}, {c}) = {v[r, c]}"
+    if not np.all(np.isfinite(v)):
+        return float("nan"), "v not finite"
+    return 0.0, "layout ok"
+
+
+def b2t_spectrum(a: np.ndarray, band: int, d, e, iters: int = 64, sturm_max: int = 400):
+    """max |eig(T) - eig(A)| / (n eps |A|_2): eig(A) by LAPACK in fp64 on A / 2^k (eigvals_banded), so that no scale of A
+    over- or underflows it; |A|_2 = max |eig(A)|.  eig(T) by sturm_eigvals (long double) up to n = sturm_max, beyond it
+    (where the bisection takes seconds per matrix) by LAPACK in fp64 on T / 2^k."""
+    import scipy.linalg as sl
+    n = a.shape[0]
+    if n == 0:
+        return 0.0, "n = 0"
+    if not (np.all(np.isfinite(d)) and np.all(np.isfinite(e))):
+        return float("nan"), "d or e not finite"
+    cx = is_complex(a.dtype)
+    wide = np.complex128 if cx else np.float64
+    mx = 0.0
+    ab = np.zeros((band + 1, n), dtype=wide)
+    for o in range(min(band, n - 1) + 1):
+        diag = np.diagonal(a, -o).astype(wide)
+        ab[o, :n - o] = diag
+        mx = max(mx, float(np.abs(diag.real).max(initial=0)), float(np.abs(diag.imag).max(initial=0)) if cx else 0.0)
+    ab[0] = ab[0].real
+    k = int(np.frexp(mx)[1]) if mx > 0 else 0
+    ab = np.ldexp(ab.real, -k) + 1j * np.ldexp(ab.imag, -k) if cx else np.ldexp(ab, -k)
+    ref = np.sort(sl.eigvals_banded(ab, lower=True).astype(np.longdouble)) * np.longdouble(2) ** k
+    if n <= sturm_max:
+        got = sturm_eigvals(d, e, iters=iters)
+    else:
+        kt = int(np.frexp(max(float(np.abs(d).max(initial=0)), float(np.abs(e).max(initial=0))))[1])
+        got = sl.eigvalsh_tridiagonal(np.ldexp(np.asarray(d, dtype=np.float64), -kt),
+                                      np.ldexp(np.asarray(e, dtype=np.float64)[:n - 1], -kt),
+                                      ).astype(np.longdouble) * np.longdouble(2) ** kt
+    anorm = float(np.abs(ref).max(initial=0))
+    err = float(np.abs(got - ref).max(initial=0))
+    return _ratio(err, n * _eps(a.dtype) * anorm), f"max |eig(T) - eig(A)| = {err:.3e}, |A|_2 = {anorm:.3e}"
+
+
+def b2t_checks(a: np.ndarray, band: int, d, e, v) -> dict:
+    """The four checkers at once: {name: (ratio, where)}."""
+    return {"backward": b2t_backward_error(a, band, d, e, v), "unitarity": b2t_reflector_unitarity(v, band),
+            "layout": b2t_layout(v, band, d, e), "spectrum": b2t_spectrum(a, band, d, e)}
+
+
+def b2t_failures(checks: dict) -> dict:
+    """The findings of b2t_checks that do not pass (ratio > 1 or NaN)."""
+    return {k: r for k, r in checks.items() if not r[0] <= 1}

@@ -11,6 +11,7 @@ Python doorway onto that ABI, mirroring the reference's operator surface for the
     dlaf::cholesky_factorization(uplo, Matrix&)        include/dlaf/factorization/cholesky.h:39-79
     dlaf::triangular_solver(side, uplo, op, diag, ...)  include/dlaf/solver/triangular.h:41-177 (next row, SURVEY 8(f)2)
     dlaf::triangular_multiplication(side, uplo, ...)   include/dlaf/multiplication/triangular.h
+    dlaf::hermitian_multiplication(side, uplo, ...)    include/dlaf/multiplication/hermitian.h
     generalized_to_standard(grid, uplo, A, B)          include/dlaf/eigensolver/gen_to_std.h:50,:101
     reduction_to_band / bt_reduction_to_band           include/dlaf/eigensolver/reduction_to_band.h:40-122, bt_reduction_to_band.h
 
@@ -22,7 +23,8 @@ from .cholesky import (DeviceMatrix, GeneralDeviceMatrix, Grid, cholesky_factori
                        initialize, make_descriptor, potrf_trace, pxhegst, pxpotrf, pxpotrs, pxtrsm, set_random_hermitian_positive_definite, tile_gemm, tile_herk, tile_potrf,
                        tile_trsm, triangular_solver, triangular_solver_device, potrs_device, release_workspace_pool, solver_profile,
                        update_launch_stats, multiplication_profile, pxtrmm, triangular_multiplication,
-                       triangular_multiplication_device)
+                       triangular_multiplication_device, hermitian_multiplication, hermitian_multiplication_device,
+                       pxhemm)
 from . import distribution  # noqa: F401
 from .eigensolver import (band_to_tridiagonal, bt_band_to_tridiagonal, bt_reduction_to_band,  # noqa: F401
                           bt_reduction_to_band_device, eigensolver_min_band, eigensolver_profile, get_band_size, hermitian_eigensolver,
@@ -35,4 +37,5 @@ __all__ = ["band_to_tridiagonal", "bt_band_to_tridiagonal", "eigensolver_profile
            "finalize", "generalized_to_standard", "initialize", "lib", "lib_path", "make_descriptor", "pxhegst", "pxpotrf", "pxpotrs", "pxtrsm",
            "set_random_hermitian_positive_definite", "solver_profile", "tile_gemm", "tile_herk", "tile_potrf", "tile_trsm",
            "triangular_solver", "triangular_solver_device", "potrs_device", "type_char", "version",
-           "triangular_multiplication", "triangular_multiplication_device", "pxtrmm", "multiplication_profile"]
+           "triangular_multiplication", "triangular_multiplication_device", "pxtrmm", "multiplication_profile",
+           "hermitian_multiplication", "hermitian_multiplication_device", "pxhemm"]

@@ -232,8 +232,51 @@ def pxtrmm(side: str, uplo: str, op: str, diag: str, m: int, n: int, alpha, a: n
                                             _ptr(a), ia, ja, da, _ptr(b), ib, jb, db)
 
 
+def hermitian_multiplication(grid: Grid, side: str, uplo: str, alpha, a: np.ndarray, b: np.ndarray, beta, c: np.ndarray,
+                             nb: int, m: int | None = None, n: int | None = None, a_src=(0, 0), c_src=(0, 0),
+                             c_block: tuple[int, int] | None = None) -> None:
+    """dlaf::hermitian_multiplication(grid, side, uplo, alpha, A, B, beta, C) (include/dlaf/multiplication/hermitian.h)
+    == dlaf_mi355x_hermitian_multiplication_{s,d,c,z}: side 'L': C = beta C + alpha A B, side 'R': C = beta C + alpha B A
+    with A Hermitian (only its uplo triangle is read).  `a`, `b`, `c`: this process's local column-major parts; `c` is
+    overwritten.  nb: A's square block; c_block: the MB x NB blocks of B and C (their block along A's dimension must be
+    nb); c_src: the source process of B and C."""
+    t = type_char(c.dtype)
+    if a.dtype != c.dtype or b.dtype != c.dtype:
+        raise ValueError("A, B and C must have the same element type")
+    if m is None or n is None:
+        if grid.nranks != 1:
+            raise ValueError("the global size m x n of C is required on a distributed grid")
+        m, n = c.shape
+    na = m if side.upper() == "L" else n
+    da = DLAFDescriptor(na, na, nb, nb, a_src[0], a_src[1], 0, 0, _ld_of(a))
+    mb_c, nb_c = c_block if c_block is not None else (nb, nb)
+    db = DLAFDescriptor(m, n, mb_c, nb_c, c_src[0], c_src[1], 0, 0, _ld_of(b))
+    dc = DLAFDescriptor(m, n, mb_c, nb_c, c_src[0], c_src[1], 0, 0, _ld_of(c))
+    al = np.array([alpha], dtype=c.dtype)
+    be = np.array([beta], dtype=c.dtype)
+    fn = getattr(lib(), f"dlaf_mi355x_hermitian_multiplication_{t}")
+    r = fn(grid.context, side.encode(), uplo.encode(), _ptr(al), _ptr(a), da, _ptr(b), db, _ptr(be), _ptr(c), dc)
+    if r != 0:
+        raise ValueError(f"dlaf_mi355x_hermitian_multiplication_{t} failed with {r}")
+
+
+def pxhemm(side: str, uplo: str, m: int, n: int, alpha, a: np.ndarray, ia: int, ja: int, desca, b: np.ndarray, ib: int,
+           jb: int, descb, beta, c: np.ndarray, ic: int, jc: int, descc) -> None:
+    """dlaf_mi355x_p{s,d}symm / p{c,z}hemm: ScaLAPACK's argument list (9-int descriptors)."""
+    t = type_char(c.dtype)
+    da = (C.c_int * 9)(*[int(x) for x in desca])
+    db = (C.c_int * 9)(*[int(x) for x in descb])
+    dc = (C.c_int * 9)(*[int(x) for x in descc])
+    al = np.array([alpha], dtype=c.dtype)
+    be = np.array([beta], dtype=c.dtype)
+    name = f"dlaf_mi355x_p{t}{'hemm' if t in 'cz' else 'symm'}"
+    getattr(lib(), name)(side.encode(), uplo.encode(), m, n, _ptr(al), _ptr(a), ia, ja, da, _ptr(b), ib, jb, db,
+                         _ptr(be), _ptr(c), ic, jc, dc)
+
+
 def multiplication_profile():
-    """(ms, flops) of the sweep of the last triangular multiplication on this process (device time, no staging)."""
+    """(ms, flops) of the sweep of the last multiplication (triangular or Hermitian) on this process (device time, no
+    staging)."""
     ms, fl = C.c_double(0), C.c_double(0)
     lib().dlaf_mi355x_multiplication_profile(C.byref(ms), C.byref(fl))
     return ms.value, fl.value
@@ -475,6 +518,18 @@ def triangular_multiplication_device(side: str, uplo: str, op: str, diag: str, a
                                                            _ptr(al), a._h, b._h)
     if r != 0:
         raise ValueError(f"dlaf_mi355x_triangular_multiplication_device failed with {r}")
+
+
+def hermitian_multiplication_device(side: str, uplo: str, alpha, a: DeviceMatrix, b: GeneralDeviceMatrix, beta,
+                                    c: GeneralDeviceMatrix) -> None:
+    """dlaf::hermitian_multiplication on resident operands: `a` holds the Hermitian matrix in its uplo triangle, `b` and
+    `c` are general resident matrices of the same shape; only `c` is written; no PCIe traffic."""
+    al = np.array([alpha], dtype=c.dtype)
+    be = np.array([beta], dtype=c.dtype)
+    r = lib().dlaf_mi355x_hermitian_multiplication_device(side.encode(), uplo.encode(), _ptr(al), a._h, b._h, _ptr(be),
+                                                          c._h)
+    if r != 0:
+        raise ValueError(f"dlaf_mi355x_hermitian_multiplication_device failed with {r}")
 
 
 def potrs_device(uplo: str, factor: DeviceMatrix, b: GeneralDeviceMatrix) -> None:

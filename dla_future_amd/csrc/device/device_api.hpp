@@ -136,6 +136,38 @@ template <class T>
 void launch_trmm(const TrmmArgs<T>& args, hipStream_t stream);
 
 // ------------------------------------------------------------------------------------------
+// One step of the Hermitian multiplication (kernels_hemm.hip):  Y(il, jl) (+)= alpha X(il, l) H(l, j) for every
+// local tile of Y in ONE launch, H Hermitian with its LOWER triangle stored.  H(l, j) of local column jl (global
+// j = jl pc + ci) is taken from the stored triangle:
+//   j > l : the adjoint of the stored tile H(j, l) at hc + (jl - jc0) hc_ts
+//   j = l : the Hermitian image of the lower triangle of hd (its diagonal taken as real)
+//   j < l : the stored tile H(l, j) as it is, at hr + jl hr_ts
+// first != 0: Y = beta Y + ... (beta == 0: Y is not read); else Y += ...  conj_h: the stored tiles hold conj(H).
+template <class T>
+struct HemmArgs {
+  T* y;
+  long y_tsr, y_tsc;
+  const T* x;
+  long x_ts;
+  const T* hc;
+  long hc_ts;
+  const T* hd;
+  const T* hr;
+  long hr_ts;
+  int jc0;
+  int l, K;       // the step's global tile column of X = tile row of H, and its extent
+  int ltr, ltc;   // local tiles of Y
+  int nb;         // tile size = leading dimension of every tile
+  int pr, ri, nt_r, last_rows;
+  int pc, ci, nt_c, last_cols;
+  T alpha, beta;
+  int first = 0;
+  int conj_h = 0;
+};
+template <class T>
+void launch_hemm(const HemmArgs<T>& args, hipStream_t stream);
+
+// ------------------------------------------------------------------------------------------
 // Diagonal block factorization + inversion (one workgroup):  a (jb x jb, lda, jb <= 64) is
 // overwritten by its lower Cholesky factor (strict upper part untouched); winv_block (64 x 64,
 // ld 64) receives inv(L) (lower, zero elsewhere).  On a non-positive pivot at column c the

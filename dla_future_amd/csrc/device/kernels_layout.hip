@@ -345,6 +345,7 @@ void launch_zero_upper_diag(T* tiles, int ltr, int ltc, int nb, int pr, int ri, 
 void update_kernels_init();
 void trsm_kernels_init();
 void trmm_kernels_init();
+void hemm_kernels_init();
 void potrf_kernels_init();
 void potrf_coop_kernels_init();
 void band_kernels_init();
@@ -355,6 +356,7 @@ void device_kernels_init() {
   update_kernels_init();
   trsm_kernels_init();
   trmm_kernels_init();
+  hemm_kernels_init();
   potrf_kernels_init();
   potrf_coop_kernels_init();
   band_kernels_init();

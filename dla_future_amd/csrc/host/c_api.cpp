@@ -218,6 +218,72 @@ void pxtrmm(char side, char uplo, char op, char diag, int m, int n, const HT* al
   (void) triangular_multiplication_c<HT>(desca[1], side, uplo, op, diag, alpha, a, da, b, db);
 }
 
+// Preconditions of dlaf::hermitian_multiplication (include/dlaf/multiplication/hermitian.h) through descriptors, and
+// this build's own (the solver's); they terminate before the GPU is touched.  Returns the grid.
+static Grid& hermitian_checks(int ctx, char side, char uplo, const DLAF_descriptor& da, const DLAF_descriptor& db,
+                              const DLAF_descriptor& dc) {
+  const char* who = "hermitian multiplication";
+  auto is = [](char c, const char* set) { return c != 0 && std::strchr(set, c) != nullptr; };
+  if (!is(side, "LlRr") || !is(uplo, "LlUu"))
+    fatal("[dlaf_mi355x] %s: bad side/uplo '%c' '%c'\n", who, side, uplo);
+  if (da.i != 0 || da.j != 0 || db.i != 0 || db.j != 0 || dc.i != 0 || dc.j != 0)
+    fatal("[dlaf_mi355x] %s: sub-matrices are not supported: offsets must be 0\n", who);
+  if (da.m != da.n || da.mb != da.nb || da.nb < 1)
+    fatal("[dlaf_mi355x] %s: A must be square with square blocks (%d x %d, %d x %d)\n", who, da.m, da.n, da.mb, da.nb);
+  const bool left = (side == 'L' || side == 'l');
+  if (dc.m < 0 || dc.n < 0 || db.m != dc.m || db.n != dc.n || db.mb != dc.mb || db.nb != dc.nb)
+    fatal("[dlaf_mi355x] %s: B (%d x %d, blocks %d x %d) and C (%d x %d, blocks %d x %d) differ\n", who, db.m, db.n, db.mb,
+          db.nb, dc.m, dc.n, dc.mb, dc.nb);
+  if (da.m != (left ? dc.m : dc.n))
+    fatal("[dlaf_mi355x] %s: A is %d x %d, B and C are %d x %d (side %c)\n", who, da.m, da.n, dc.m, dc.n, side);
+  if ((left ? dc.mb : dc.nb) != da.nb || dc.mb < 1 || dc.nb < 1)
+    fatal("[dlaf_mi355x] %s: the blocks of B and C (%d x %d) do not match A's (%d x %d) for side %c\n", who, dc.mb, dc.nb,
+          da.mb, da.nb, side);
+  Grid& g = grid_from_context(ctx);
+  for (const DLAF_descriptor* d : {&da, &db, &dc})
+    if (d->isrc < 0 || d->isrc >= g.nprow || d->jsrc < 0 || d->jsrc >= g.npcol)
+      fatal("[dlaf_mi355x] %s: source rank (%d,%d) outside the %d x %d grid\n", who, d->isrc, d->jsrc, g.nprow, g.npcol);
+  if (db.isrc != dc.isrc || db.jsrc != dc.jsrc)
+    fatal("[dlaf_mi355x] %s: B and C must share the source process ((%d,%d) vs (%d,%d))\n", who, db.isrc, db.jsrc,
+          dc.isrc, dc.jsrc);
+  if (dc.m > 0 && dc.n > 0 && (left ? (da.isrc != dc.isrc) : (da.jsrc != dc.jsrc)))
+    fatal("[dlaf_mi355x] %s: A must share the source process of B and C along A's dimension\n", who);
+  return g;
+}
+
+// dlaf::hermitian_multiplication through descriptors: C = beta C + alpha A B (side L) / beta C + alpha B A (side R)
+template <class HT>
+int hermitian_multiplication_c(int ctx, char side, char uplo, const HT* alpha, const HT* a, const DLAF_descriptor& da,
+                               const HT* b, const DLAF_descriptor& db, const HT* beta, HT* c, const DLAF_descriptor& dc) {
+  using DT = typename DevType<HT>::type;
+  Grid& g = hermitian_checks(ctx, side, uplo, da, db, dc);
+  const bool left = (side == 'L' || side == 'l');
+  DT al, be;
+  std::memcpy(&al, alpha, sizeof(DT));
+  std::memcpy(&be, beta, sizeof(DT));
+  return hermitian_multiplication_host<DT>(&g, side, uplo, al, reinterpret_cast<const DT*>(a), da.ld, da.isrc, da.jsrc,
+                                           reinterpret_cast<const DT*>(b), db.ld, be, reinterpret_cast<DT*>(c), dc.ld, dc.m,
+                                           dc.n, da.nb, dc.isrc, dc.jsrc, left ? dc.nb : dc.mb);
+}
+
+// ScaLAPACK p?symm / p?hemm argument list
+template <class HT>
+void pxhemm(char side, char uplo, int m, int n, const HT* alpha, const HT* a, int ia, int ja, const int desca[9],
+            const HT* b, int ib, int jb, const int descb[9], const HT* beta, HT* c, int ic, int jc, const int descc[9]) {
+  if (desca[0] != 1 || descb[0] != 1 || descc[0] != 1)
+    fatal("[dlaf_mi355x] hermitian multiplication: desc[0] (dtype) must be 1\n");
+  if (ia != 1 || ja != 1 || ib != 1 || jb != 1 || ic != 1 || jc != 1)
+    fatal("[dlaf_mi355x] hermitian multiplication: ia, ja, ib, jb, ic, jc must be 1\n");
+  if (desca[1] != descb[1] || desca[1] != descc[1])
+    fatal("[dlaf_mi355x] hermitian multiplication: A, B and C live on different contexts (%d, %d, %d)\n", desca[1],
+          descb[1], descc[1]);
+  const int na = (side == 'L' || side == 'l') ? m : n;
+  const DLAF_descriptor da = make_dlaf_descriptor(na, na, ia, ja, desca);
+  const DLAF_descriptor db = make_dlaf_descriptor(m, n, ib, jb, descb);
+  const DLAF_descriptor dc = make_dlaf_descriptor(m, n, ic, jc, descc);
+  (void) hermitian_multiplication_c<HT>(desca[1], side, uplo, alpha, a, da, b, db, beta, c, dc);
+}
+
 // ScaLAPACK p?trsm argument list
 template <class HT>
 void pxtrsm(char side, char uplo, char op, char diag, int m, int n, const HT* alpha, const HT* a, int ia, int ja,
@@ -710,6 +776,26 @@ DLAF_MI355X_TRMM_ENTRY(d, double, double)
 DLAF_MI355X_TRMM_ENTRY(c, std::complex<float>, dlaf_complex_c)
 DLAF_MI355X_TRMM_ENTRY(z, std::complex<double>, dlaf_complex_z)
 #undef DLAF_MI355X_TRMM_ENTRY
+#define DLAF_MI355X_HEMM_ENTRY(S, HT, CT, NAME)                                                                  \
+  int dlaf_mi355x_hermitian_multiplication_##S(int ctx, char side, char uplo, const CT* alpha, const CT* a,         \
+                                               DLAF_descriptor desca, const CT* b, DLAF_descriptor descb,          \
+                                               const CT* beta, CT* c, DLAF_descriptor descc) noexcept {            \
+    return hermitian_multiplication_c<HT>(ctx, side, uplo, reinterpret_cast<const HT*>(alpha),                     \
+                                          reinterpret_cast<const HT*>(a), desca, reinterpret_cast<const HT*>(b),   \
+                                          descb, reinterpret_cast<const HT*>(beta), reinterpret_cast<HT*>(c), descc); \
+  }                                                                                                             \
+  void dlaf_mi355x_p##S##NAME(char side, char uplo, int m, int n, const CT* alpha, const CT* a, int ia, int ja,     \
+                              const int desca[9], const CT* b, int ib, int jb, const int descb[9], const CT* beta,  \
+                              CT* c, int ic, int jc, const int descc[9]) noexcept {                               \
+    pxhemm<HT>(side, uplo, m, n, reinterpret_cast<const HT*>(alpha), reinterpret_cast<const HT*>(a), ia, ja, desca, \
+               reinterpret_cast<const HT*>(b), ib, jb, descb, reinterpret_cast<const HT*>(beta),                   \
+               reinterpret_cast<HT*>(c), ic, jc, descc);                                                          \
+  }
+DLAF_MI355X_HEMM_ENTRY(s, float, float, symm)
+DLAF_MI355X_HEMM_ENTRY(d, double, double, symm)
+DLAF_MI355X_HEMM_ENTRY(c, std::complex<float>, dlaf_complex_c, hemm)
+DLAF_MI355X_HEMM_ENTRY(z, std::complex<double>, dlaf_complex_z, hemm)
+#undef DLAF_MI355X_HEMM_ENTRY
 #define DLAF_MI355X_POTRS_ENTRY(S, HT, CT)                                                                       \
   void dlaf_mi355x_p##S##potrs(char uplo, int n, int nrhs, const CT* a, int ia, int ja, const int desca[9], CT* b,  \
                                int ib, int jb, const int descb[9], int* info) noexcept {                        \
@@ -926,6 +1012,17 @@ int dlaf_mi355x_triangular_multiplication_device(char side, char uplo, char op, 
   if (!is(side, "LlRr") || !is(uplo, "LlUu") || !is(op, "NnTtCc") || !is(diag, "NnUu"))
     fatal("[dlaf_mi355x] triangular multiplication: bad side/uplo/op/diag '%c' '%c' '%c' '%c'\n", side, uplo, op, diag);
   return triangular_multiplication_device(side, uplo, op, diag, alpha, a->m.get(), b->m.get());
+}
+
+int dlaf_mi355x_hermitian_multiplication_device(char side, char uplo, const void* alpha, dlaf_mi355x_matrix_t a,
+                                               dlaf_mi355x_gmatrix_t b, const void* beta,
+                                               dlaf_mi355x_gmatrix_t c) noexcept {
+  if (!a || !a->m || !b || !b->m || !c || !c->m || a->ctx != b->ctx || a->ctx != c->ctx)
+    return -1;
+  auto is = [](char ch, const char* set) { return ch != 0 && std::strchr(set, ch) != nullptr; };
+  if (!is(side, "LlRr") || !is(uplo, "LlUu"))
+    fatal("[dlaf_mi355x] hermitian multiplication: bad side/uplo '%c' '%c'\n", side, uplo);
+  return hermitian_multiplication_device(side, uplo, alpha, a->m.get(), b->m.get(), beta, c->m.get());
 }
 
 int dlaf_mi355x_multiplication_profile(double* ms, double* flops) noexcept {

@@ -1,8 +1,10 @@
 // multiplication.cpp -- distributed triangular multiplication  B = alpha op(A) B  /  B = alpha B op(A)  on the tile
-// kernels of the triangular solver.
+// kernels of the triangular solver, and (second half) the Hermitian multiplication  C = beta C + alpha A B  /
+// beta C + alpha B A  on its own step kernel.
 //
 // Reference: dlaf::triangular_multiplication (include/dlaf/multiplication/triangular.h) and its hand-written
-// variants (multiplication/triangular/impl.h).
+// variants (multiplication/triangular/impl.h); dlaf::hermitian_multiplication (include/dlaf/multiplication/hermitian.h),
+// which implements side L / uplo L only and reduces a panel of C along process columns at every step.
 //
 // MI355X design: the solver's operand mapping (solver.cpp header: side / op decide T and B_dev, the relayout
 // transposes, conjugates and scales) turns every combination into ONE device algorithm,
@@ -28,7 +30,8 @@ namespace dlaf_mi355x {
 
 namespace {
 
-// device time of the last sweep on this process (HIP events on the compute stream; relayout and PCIe excluded)
+// device time of the last sweep of either multiplication on this process (HIP events on the compute stream; relayout
+// and PCIe excluded)
 double g_last_mult_ms = 0;
 double g_last_mult_flops = 0;
 
@@ -219,6 +222,230 @@ void multiply_canonical(TileMatrix<T>& Td, TileMatrix<T>& Bd, bool upper, bool u
   }
 }
 
+// ================================================================================ Hermitian multiplication
+// Y = beta Y + alpha X H, H Hermitian with its LOWER triangle stored in Hd (conj_h: the stored tiles hold conj(H), what
+// a resident uplo = U matrix keeps).  Xd and Yd are two views of the same shape and distribution; Hd is aligned with
+// their columns like the T of the triangular sweeps.  Step l (forward, no step reads a computed value):
+//        Y(:, j) += alpha X(:, l) H(l, j)    for every local tile column j         one launch (kernels_hemm.hip)
+// H(l, j) comes from the stored column l (j > l, adjoint), the diagonal tile (j = l) and the stored row l (j < l).
+// Broadcasts per step on a grid (all on s_comm, one step ahead, a ring of kBuf buffers per operand; no reduce):
+//   X(:, l)            along the process rows of the view from the owner column             Yd.ltr tiles
+//   column l of H      TOperandFetch (t_operand.hpp): one broadcast when H's rows are spread like Y's columns,
+//                      else the Cholesky's panel + transposed-panel pair                    <= Yd.ltc (+ Hd.ltr) tiles
+//   row l of H         the mirror image: one broadcast when H's COLUMNS are spread like Y's columns, else the row
+//                      along Y's columns' dimension and then tile by tile down the other    <= Yd.ltc (+ Hd.ltc) tiles
+//   H(l, l)            to the processes that hold column l of Y (TOperandFetch)             1 tile
+template <class T>
+void hermitian_canonical(TileMatrix<T>& Hd, TileMatrix<T>& Xd, TileMatrix<T>& Yd, T alpha, T beta, bool conj_h) {
+  Grid* g = Yd.grid;
+  Transport* tr = grid_transport(*g);
+  const bool dist = g->nranks > 1;
+  const int nb = Yd.nb;
+  const long nt = Yd.cols.nt();
+  if (nt == 0 || Yd.rows_global == 0)
+    return;
+  const size_t tile_elems = Yd.tile_elems, tile_bytes = tile_elems * sizeof(T);
+  const CommAxis along_row = Yd.transposed ? CommAxis::Col : CommAxis::Row;
+  const CommAxis along_col = Yd.transposed ? CommAxis::Row : CommAxis::Col;
+  const bool aligned = Hd.row_dim() == Yd.col_dim();
+  check_t_aligned(Hd, Yd, "hermitian multiplication");
+
+  hipStream_t s_main = nullptr, s_comm = nullptr;
+  int lo = 0, hi = 0;
+  DLAF_HIP_CHECK(hipDeviceGetStreamPriorityRange(&lo, &hi));
+  DLAF_HIP_CHECK(hipStreamCreateWithPriority(&s_main, hipStreamNonBlocking, lo));
+  DLAF_HIP_CHECK(hipStreamCreateWithPriority(&s_comm, hipStreamNonBlocking, hi));
+  // ev_t: column l and the diagonal tile are in place (TOperandFetch); ev_in: so are row l and X(:, l);
+  // ev_done: the launch of step s is done, its buffers are free
+  Events ev_t((size_t) nt), ev_in((size_t) nt), ev_done((size_t) nt);
+
+  constexpr int kBuf = TOperandFetch<T>::kBuf;
+  T* diag_ws[kBuf] = {nullptr, nullptr, nullptr};
+  T* tpanel[kBuf] = {nullptr, nullptr, nullptr};
+  T* tstage[kBuf] = {nullptr, nullptr, nullptr};
+  T* rpanel[kBuf] = {nullptr, nullptr, nullptr};
+  T* rstage[kBuf] = {nullptr, nullptr, nullptr};
+  T* xpanel[kBuf] = {nullptr, nullptr, nullptr};
+  for (int b = 0; b < kBuf; ++b) {
+    diag_ws[b] = tm_dev_alloc<T>(tile_elems);
+    if (dist) {
+      tpanel[b] = tm_dev_alloc<T>((size_t) Yd.ltc * tile_elems);
+      rpanel[b] = tm_dev_alloc<T>((size_t) Yd.ltc * tile_elems);
+      if (aligned)
+        rstage[b] = tm_dev_alloc<T>((size_t) Hd.ltc * tile_elems);
+      else
+        tstage[b] = tm_dev_alloc<T>((size_t) Hd.ltr * tile_elems);
+      xpanel[b] = tm_dev_alloc<T>((size_t) Yd.ltr * tile_elems);
+    }
+  }
+
+  const std::vector<long> my_diag;  // (no inverted blocks)
+  std::vector<TOperand<T>> top((size_t) nt);
+  TOperandFetch<T> tf{Hd, Yd, tr, false, false, s_comm, my_diag, nullptr, 0, diag_ws, tpanel, tstage,
+                      ev_done.v.data(), ev_t.v.data(), top};
+  struct RowOperand {
+    const T* base = nullptr;  // stored H(l, j) of local column jl < jr1 of Yd at base + jl * ts
+    long ts = 0;
+    const T* x = nullptr;     // X(:, l)
+  };
+  std::vector<RowOperand> rop((size_t) nt);
+
+  // local tiles (lrow, 0 .. count) of Hd, one tile row, packed next to each other
+  auto pack_row = [&](T* dst, long lrow, long count) {
+    if (count > 0)
+      DLAF_HIP_CHECK(hipMemcpy2DAsync(dst, tile_bytes, Hd.tile(lrow, 0), (size_t) Hd.ltr * tile_bytes, tile_bytes,
+                                      (size_t) count, hipMemcpyDeviceToDevice, s_comm));
+  };
+
+  auto fetch = [&](long l) {
+    tf.fetch(l);  // waits for the buffers of step l - kBuf first
+    const int buf = (int) (l % kBuf);
+    RowOperand& o = rop[(size_t) l];
+    const long jr1 = Yd.cols.next_local(l);  // local columns of Yd left of l
+    if (!dist) {
+      o.base = Hd.tile(l, 0);
+      o.ts = (long) (tile_elems * Hd.ltr);
+    }
+    else if (!aligned) {
+      // Hd's columns are spread like Yd's: row l sits on the process of my Yd-column coordinate whose other
+      // coordinate owns Hd's row l -> one broadcast
+      const bool have = Hd.rows.mine(l);
+      if (Yd.row_P > 1) {
+        if (have)
+          pack_row(rpanel[buf], Hd.rows.local_of(l), jr1);
+        if (jr1 > 0)
+          tr->bcast(along_col, Hd.rows.owner(l), Yd.row_rank, rpanel[buf], rpanel[buf], (size_t) jr1 * tile_bytes, s_comm);
+        o.base = rpanel[buf];
+        o.ts = (long) tile_elems;
+      }
+      else {
+        o.base = Hd.tile(Hd.rows.local_of(l), 0);
+        o.ts = (long) (tile_elems * Hd.ltr);
+      }
+    }
+    else {
+      // Hd's rows are spread like Yd's columns: row l along that dimension first (every process gets the
+      // columns its other coordinate owns), then tile j down the other dimension from the owner of Hd's column j
+      const long hj1 = Hd.cols.next_local(l);
+      if (Hd.rows.mine(l))
+        pack_row(rstage[buf], Hd.rows.local_of(l), hj1);
+      if (Yd.cols.P > 1 && hj1 > 0)
+        tr->bcast(along_row, Hd.rows.owner(l), Yd.cols.rank, rstage[buf], rstage[buf], (size_t) hj1 * tile_bytes, s_comm);
+      if (Yd.row_P > 1) {
+        tr->group_begin();
+        for (long jl = 0; jl < jr1; ++jl) {
+          const long gj = Yd.cols.global_of(jl);
+          const int root = Hd.cols.owner(gj);
+          const T* src = (Hd.cols.rank == root) ? rstage[buf] + (size_t) Hd.cols.local_of(gj) * tile_elems : nullptr;
+          tr->bcast(along_col, root, Yd.row_rank, src, rpanel[buf] + (size_t) jl * tile_elems, tile_bytes, s_comm);
+        }
+        tr->group_end();
+        o.base = rpanel[buf];
+        o.ts = (long) tile_elems;
+      }
+      else {
+        // I hold every column of Hd's row l: tile gj sits at local column gj
+        o.base = rstage[buf] + (size_t) Yd.cols.global_of(0) * tile_elems;
+        o.ts = (long) tile_elems * Yd.cols.P;
+      }
+    }
+    // X(:, l) to the other members of my row of the view (X is not written: the owner sends its own tiles)
+    const bool in_col = Xd.cols.mine(l);
+    const T* xp = in_col ? Xd.tile(0, Xd.cols.local_of(l)) : nullptr;
+    if (Xd.cols.P > 1) {
+      T* dst = in_col ? Xd.tile(0, Xd.cols.local_of(l)) : xpanel[buf];
+      if (Xd.ltr > 0)
+        tr->bcast(along_row, Xd.cols.owner(l), Xd.cols.rank, dst, dst, (size_t) Xd.ltr * tile_bytes, s_comm);
+      xp = dst;
+    }
+    o.x = xp;
+    DLAF_HIP_CHECK(hipEventRecord(ev_in[(size_t) l], s_comm));
+  };
+
+  hipEvent_t ev_t0, ev_t1;
+  DLAF_HIP_CHECK(hipEventCreate(&ev_t0));
+  DLAF_HIP_CHECK(hipEventCreate(&ev_t1));
+  DLAF_HIP_CHECK(hipEventRecord(ev_t0, s_main));
+  DLAF_HIP_CHECK(hipStreamWaitEvent(s_comm, ev_t0, 0));
+
+  fetch(0);
+  for (long l = 0; l < nt; ++l) {
+    if (l + 1 < nt)
+      fetch(l + 1);
+    DLAF_HIP_CHECK(hipStreamWaitEvent(s_main, ev_in[(size_t) l], 0));
+    if (Yd.ltr > 0 && Yd.ltc > 0) {
+      const TOperand<T>& o = top[(size_t) l];
+      const RowOperand& r = rop[(size_t) l];
+      HemmArgs<T> ha;
+      ha.y = Yd.tiles;
+      ha.y_tsr = (long) tile_elems;
+      ha.y_tsc = (long) (tile_elems * Yd.ltr);
+      ha.x = r.x;
+      ha.x_ts = (long) tile_elems;
+      ha.hc = o.base;
+      ha.hc_ts = o.ts;
+      ha.jc0 = (int) o.jl0;
+      ha.hd = o.diag;
+      ha.hr = r.base;
+      ha.hr_ts = r.ts;
+      ha.l = (int) l;
+      ha.K = Yd.cols.tile_extent(l);
+      ha.ltr = (int) Yd.ltr;
+      ha.ltc = (int) Yd.ltc;
+      ha.nb = nb;
+      ha.pr = Yd.rows.P;
+      ha.ri = Yd.rows.shift();
+      ha.nt_r = (int) Yd.rows.nt();
+      ha.last_rows = Yd.rows.last_extent();
+      ha.pc = Yd.cols.P;
+      ha.ci = Yd.cols.shift();
+      ha.nt_c = (int) nt;
+      ha.last_cols = Yd.cols.last_extent();
+      ha.alpha = alpha;
+      ha.beta = beta;
+      ha.first = l == 0 ? 1 : 0;
+      ha.conj_h = conj_h ? 1 : 0;
+      launch_hemm(ha, s_main);
+    }
+    DLAF_HIP_CHECK(hipEventRecord(ev_done[(size_t) l], s_main));
+  }
+
+  DLAF_HIP_CHECK(hipEventRecord(ev_t1, s_main));
+  DLAF_HIP_CHECK(hipStreamSynchronize(s_comm));
+  DLAF_HIP_CHECK(hipStreamSynchronize(s_main));
+  {
+    float ms = 0;
+    DLAF_HIP_CHECK(hipEventElapsedTime(&ms, ev_t0, ev_t1));
+    g_last_mult_ms = ms;
+    // whole-grid algorithmic flops: 2 x rows x na^2 (x4 complex)
+    g_last_mult_flops = (TypeInfo<T>::is_complex ? 8.0 : 2.0) * (double) Yd.rows_global * (double) Yd.cols.n * (double) Yd.cols.n;
+  }
+  (void) hipEventDestroy(ev_t0);
+  (void) hipEventDestroy(ev_t1);
+  (void) hipStreamDestroy(s_main);
+  (void) hipStreamDestroy(s_comm);
+  for (int b = 0; b < kBuf; ++b) {
+    (void) hipFree(diag_ws[b]);
+    for (T* p : {tpanel[b], tstage[b], rpanel[b], rstage[b], xpanel[b]})
+      if (p)
+        (void) hipFree(p);
+  }
+}
+
+template <class T>
+T conj_of(T v) {
+  if constexpr (TypeInfo<T>::is_complex)
+    v.im = -v.im;
+  return v;
+}
+template <class T>
+bool is_zero(const T& v) {
+  if constexpr (TypeInfo<T>::is_complex)
+    return v.re == 0 && v.im == 0;
+  else
+    return v == 0;
+}
+
 }  // namespace
 
 void multiplication_last_profile(double* ms, double* flops) {
@@ -254,6 +481,130 @@ int triangular_multiplication_device(char side, char uplo, char op, char diag, c
     default: fatal("[dlaf_mi355x] bad matrix type\n");
   }
 }
+
+// C = beta C + alpha A B (side L) / beta C + alpha B A (side R), A Hermitian in its uplo triangle.  Side R is the
+// canonical form; side L runs it on the adjoints, C^H = conj(beta) C^H + conj(alpha) B^H A (the relayout transposes and
+// conjugates).  uplo U: the transposed, conjugated view of A holds A itself with its LOWER triangle valid.
+template <class T>
+int hermitian_multiplication_host(Grid* g, char side, char uplo, T alpha, const T* a, long lda, int a_isrc, int a_jsrc,
+                                  const T* b, long ldb, T beta, T* c, long ldc, long m, long n, int nb, int isrc, int jsrc,
+                                  int nb_free) {
+  const bool left = (side == 'L' || side == 'l');
+  const bool a_upper = (uplo == 'U' || uplo == 'u');
+  if (left ? (a_isrc != isrc) : (a_jsrc != jsrc))
+    fatal("[dlaf_mi355x] hermitian multiplication: A must share the source process of B and C along A's dimension\n");
+  if (m == 0 || n == 0)
+    return 0;
+  runtime_init();
+  (void) grid_transport(*g);
+  if (g->nranks > 1 && !g->transport)
+    fatal("[dlaf_mi355x] grid with %d ranks has no transport\n", g->nranks);
+  const long na = left ? m : n;
+  hipStream_t s = nullptr;
+  DLAF_HIP_CHECK(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
+  {
+    TileMatrix<T> Hd, Xd, Yd;
+    Hd.create(g, a_upper, na, na, nb, a_isrc, a_jsrc);
+    if (nb_free <= 0)
+      nb_free = nb;
+    Xd.create_rhs(g, left, m, n, left ? nb : nb_free, left ? nb_free : nb, isrc, jsrc);
+    Yd.create_rhs(g, left, m, n, left ? nb : nb_free, left ? nb_free : nb, isrc, jsrc);
+    Hd.upload(a, lda, a_upper, false, T{}, s);
+    Xd.upload(b, ldb, left, false, T{}, s);
+    if (!is_zero(beta))  // beta = 0: C is not read
+      Yd.upload(c, ldc, left, false, T{}, s);
+    DLAF_HIP_CHECK(hipStreamSynchronize(s));
+    hermitian_canonical(Hd, Xd, Yd, left ? conj_of(alpha) : alpha, left ? conj_of(beta) : beta, false);
+    Yd.download(c, ldc, left, s);
+    DLAF_HIP_CHECK(hipStreamSynchronize(s));
+  }
+  DLAF_HIP_CHECK(hipStreamDestroy(s));
+  return 0;
+}
+
+// The same on RESIDENT operands: A a DeviceMatrix (its uplo triangle; for uplo U it holds the transposed view, whose
+// lower triangle is conj(A)'s: conj_h), B and C general resident matrices of the same shape.  Side R works on B's and
+// C's tiles in place; side L on adjoint copies made by tile transforms on the device.  Only C is written.
+template <class T>
+int hermitian_device_t(char side, char uplo, T alpha, DeviceMatrix<T>& A, GeneralMatrix<T>& B, T beta,
+                       GeneralMatrix<T>& C) {
+  const char* who = "hermitian multiplication";
+  Grid* g = A.grid;
+  if (B.m.grid != g || C.m.grid != g)
+    fatal("[dlaf_mi355x] %s: A, B and C live on different grids\n", who);
+  const bool left = (side == 'L' || side == 'l');
+  const bool a_upper = (uplo == 'U' || uplo == 'u');
+  if (a_upper != A.transposed)
+    fatal("[dlaf_mi355x] %s: uplo '%c' but the resident matrix holds its '%c' triangle\n", who, uplo, A.uplo);
+  const long m = C.rows_g, n = C.cols_g, na = left ? m : n;
+  const int nb = A.nb;
+  if (B.rows_g != m || B.cols_g != n || B.m.nb != C.m.nb || B.isrc != C.isrc || B.jsrc != C.jsrc)
+    fatal("[dlaf_mi355x] %s: B (%ld x %ld, block %d, source %d,%d) and C (%ld x %ld, block %d, source %d,%d) differ\n", who,
+          B.rows_g, B.cols_g, B.m.nb, B.isrc, B.jsrc, m, n, C.m.nb, C.isrc, C.jsrc);
+  if (A.n != na || C.m.nb != nb)
+    fatal("[dlaf_mi355x] %s: A is %ld x %ld (block %d), C is %ld x %ld (block %d), side %c\n", who, A.n, A.n, nb, m, n,
+          C.m.nb, side);
+  const Axis& a_rows = A.transposed ? A.cols : A.rows;
+  const Axis& a_cols = A.transposed ? A.rows : A.cols;
+  if (left ? (a_rows.src != C.isrc) : (a_cols.src != C.jsrc))
+    fatal("[dlaf_mi355x] %s: A must share the source process of B and C along A's dimension\n", who);
+  if (m == 0 || n == 0)
+    return 0;
+  hipStream_t s = nullptr;
+  DLAF_HIP_CHECK(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
+  {
+    TileMatrix<T> Hd, Xd, Yd;
+    const size_t te = A.tile_elems;
+    Hd.create(g, A.transposed, na, na, nb, a_rows.src, a_cols.src, A.tiles);
+    if (left) {
+      Xd.create(g, true, m, n, nb, C.isrc, C.jsrc);
+      Yd.create(g, true, m, n, nb, C.isrc, C.jsrc);
+      xform_tiles(Xd.tiles, Xd.ltr, Xd.ltc, B.m.tiles, B.m.ltr, te, nb, 0, T{}, false, s);
+      if (!is_zero(beta))
+        xform_tiles(Yd.tiles, Yd.ltr, Yd.ltc, C.m.tiles, C.m.ltr, te, nb, 0, T{}, false, s);
+      DLAF_HIP_CHECK(hipStreamSynchronize(s));
+    }
+    else {
+      Xd.create(g, false, m, n, nb, C.isrc, C.jsrc, B.m.tiles);
+      Yd.create(g, false, m, n, nb, C.isrc, C.jsrc, C.m.tiles);
+    }
+    hermitian_canonical(Hd, Xd, Yd, left ? conj_of(alpha) : alpha, left ? conj_of(beta) : beta, A.transposed);
+    if (left) {
+      xform_tiles(C.m.tiles, C.m.ltr, C.m.ltc, Yd.tiles, Yd.ltr, te, nb, 0, T{}, false, s);
+      DLAF_HIP_CHECK(hipStreamSynchronize(s));
+    }
+  }
+  DLAF_HIP_CHECK(hipStreamDestroy(s));
+  return 0;
+}
+
+int hermitian_multiplication_device(char side, char uplo, const void* alpha, MatrixBase* a, MatrixBase* b,
+                                    const void* beta, MatrixBase* c) {
+  if (!a || !b || !c || a->type != b->type || a->type != c->type)
+    fatal("[dlaf_mi355x] hermitian multiplication: operands of different element types\n");
+  auto run = [&](auto* tag) {
+    using T = std::remove_pointer_t<decltype(tag)>;
+    return hermitian_device_t<T>(side, uplo, *static_cast<const T*>(alpha), static_cast<DeviceMatrix<T>&>(*a),
+                                 static_cast<GeneralMatrix<T>&>(*b), *static_cast<const T*>(beta),
+                                 static_cast<GeneralMatrix<T>&>(*c));
+  };
+  switch (a->type) {
+    case 's': return run((float*) nullptr);
+    case 'd': return run((double*) nullptr);
+    case 'c': return run((cfloat*) nullptr);
+    case 'z': return run((cdouble*) nullptr);
+    default: fatal("[dlaf_mi355x] bad matrix type\n");
+  }
+}
+
+#define DLAF_HEMM_INST(T)                                                                                          \
+  template int hermitian_multiplication_host<T>(Grid*, char, char, T, const T*, long, int, int, const T*, long, T, T*, \
+                                                long, long, long, int, int, int, int);
+DLAF_HEMM_INST(float)
+DLAF_HEMM_INST(double)
+DLAF_HEMM_INST(cfloat)
+DLAF_HEMM_INST(cdouble)
+#undef DLAF_HEMM_INST
 
 template int triangular_multiplication_host<float>(Grid*, char, char, char, char, float, const float*, long, int, int,
                                                    float*, long, long, long, int, int, int, int);

@@ -266,7 +266,19 @@ int triangular_multiplication_host(Grid* g, char side, char uplo, char op, char 
                                    int nb_free = 0);
 int triangular_multiplication_device(char side, char uplo, char op, char diag, const void* alpha, MatrixBase* a,
                                      MatrixBase* b);
+// device time and whole-grid flops of the last sweep of EITHER multiplication (triangular or Hermitian) on this process
 void multiplication_last_profile(double* ms, double* flops);
+
+// C = beta C + alpha A B (side L) / beta C + alpha B A (side R), A Hermitian with only its uplo triangle read
+// (multiplication.cpp; dlaf::hermitian_multiplication, every side x uplo).  m x n: size of B and C, nb: A's square block =
+// their block along A's dimension, nb_free: their block along the other one (<= 0: nb); (isrc, jsrc): source process of
+// B and C.  Host and resident forms.
+template <class T>
+int hermitian_multiplication_host(Grid* g, char side, char uplo, T alpha, const T* a, long lda, int a_isrc, int a_jsrc,
+                                  const T* b, long ldb, T beta, T* c, long ldc, long m, long n, int nb, int isrc, int jsrc,
+                                  int nb_free = 0);
+int hermitian_multiplication_device(char side, char uplo, const void* alpha, MatrixBase* a, MatrixBase* b,
+                                    const void* beta, MatrixBase* c);
 
 // A <- L^-1 A L^-H (uplo L) / U^-H A U^-1 (uplo U) with the Cholesky factor held in the same uplo triangle of
 // `l` (gen_to_std.cpp; dlaf::eigensolver::internal::generalized_to_standard); device-resident and host forms

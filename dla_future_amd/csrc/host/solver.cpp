@@ -433,7 +433,7 @@ void general_matrix_transfer(MatrixBase* h, void* host, long ld, bool upload) {
 // for the transposing ones (0 adjoint, 3 transpose).  A transposed view of a block-cyclic matrix stays on the
 // same process (tile (i,j) of the view is tile (j,i) of the source), so this is local work on every rank.
 template <class T>
-static void xform_tiles(T* dst, long dltr, long dltc, const T* src, long sltr, size_t te, int nb, int mode, T alpha,
+void xform_tiles(T* dst, long dltr, long dltc, const T* src, long sltr, size_t te, int nb, int mode, T alpha,
                         bool use_alpha, hipStream_t s) {
   const bool tr = (mode == 0 || mode == 3);
   for (long jl = 0; jl < dltc; ++jl) {
@@ -543,7 +543,8 @@ int triangular_solver_device(char side, char uplo, char op, char diag, const voi
   template int triangular_canonical_host<T>(const char*, CanonicalSweep<T>, bool, Grid*, char, char, char, char, T,  \
                                             const T*, long, int, int, T*, long, long, long, int, int, int, int);    \
   template int triangular_canonical_device<T>(const char*, CanonicalSweep<T>, char, char, char, char, T,             \
-                                              DeviceMatrix<T>&, GeneralMatrix<T>&);
+                                              DeviceMatrix<T>&, GeneralMatrix<T>&);                                \
+  template void xform_tiles<T>(T*, long, long, const T*, long, size_t, int, int, T, bool, hipStream_t);
 DLAF_CANONICAL_INST(float)
 DLAF_CANONICAL_INST(double)
 DLAF_CANONICAL_INST(cfloat)

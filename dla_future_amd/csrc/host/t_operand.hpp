@@ -186,4 +186,10 @@ template <class T>
 int triangular_canonical_device(const char* who, CanonicalSweep<T> sweep, char side, char uplo, char op, char diag,
                                 T alpha, DeviceMatrix<T>& A, GeneralMatrix<T>& B);
 
+// dst view tile (il, jl) = alpha * op(src tile) for the dltr x dltc tiles of a view (solver.cpp): mode 0 adjoint and
+// 3 transpose take src tile (jl, il), 4 conjugate and 5 copy take src tile (il, jl); sltr: local tile rows of src
+template <class T>
+void xform_tiles(T* dst, long dltr, long dltc, const T* src, long sltr, size_t te, int nb, int mode, T alpha,
+                 bool use_alpha, hipStream_t s);
+
 }  // namespace dlaf_mi355x

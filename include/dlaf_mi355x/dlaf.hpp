@@ -10,6 +10,8 @@
  *                                                                             // include/dlaf/solver/triangular.h:41-177
  *     dlaf::triangular_multiplication<Backend::GPU, Device::GPU, T>(grid, side, uplo, op, diag, alpha, a, b);
  *                                                                     // include/dlaf/multiplication/triangular.h
+ *     dlaf::hermitian_multiplication<Backend::GPU, Device::GPU, T>(grid, side, uplo, alpha, a, b, beta, c);
+ *                                                                     // include/dlaf/multiplication/hermitian.h
  *
  * What differs from the reference, by design: there is no pika runtime (the calls are blocking, no pika::wait),
  * Backend::MC does not exist (the library has no CPU path: static_assert), Matrix<T, Device::CPU> stores its
@@ -427,6 +429,49 @@ void triangular_multiplication(blas::Side side, blas::Uplo uplo, blas::Op op, bl
                                Matrix<T, Device::CPU>& mat_a, Matrix<T, Device::CPU>& mat_b) {
   comm::CommunicatorGrid grid = comm::CommunicatorGrid::single();
   triangular_multiplication<B, D, T>(grid, side, uplo, op, diag, alpha, mat_a, mat_b);
+}
+
+// include/dlaf/multiplication/hermitian.h:52, :114: C = beta C + alpha A B (Left) / beta C + alpha B A (Right), A
+// Hermitian with only its uplo triangle read; host-resident operands, every side x uplo (the reference implements
+// Left / Lower only).  The reference's read-only Matrix<const T, D>& operands are const Matrix<T, D>& here.
+template <Backend B, Device D, class T>
+void hermitian_multiplication(comm::CommunicatorGrid& grid, blas::Side side, blas::Uplo uplo, const T alpha,
+                              const Matrix<T, Device::CPU>& mat_a, const Matrix<T, Device::CPU>& mat_b, const T beta,
+                              Matrix<T, Device::CPU>& mat_c) {
+  static_assert(B == Backend::GPU, "this library has no CPU backend");
+  auto desc_of = [](const auto& m) {
+    const auto& d = m.distribution();
+    return DLAF_descriptor{(int) d.size().rows(), (int) d.size().cols(), (int) d.block_size().rows(),
+                           (int) d.block_size().cols(), (int) d.source_rank_index().row(),
+                           (int) d.source_rank_index().col(), 0, 0, (int) m.ld()};
+  };
+  int r;
+  if constexpr (std::is_same_v<T, float>)
+    r = dlaf_mi355x_hermitian_multiplication_s(grid.context(), (char) side, (char) uplo, &alpha, mat_a.ptr(),
+                                               desc_of(mat_a), mat_b.ptr(), desc_of(mat_b), &beta, mat_c.ptr(),
+                                               desc_of(mat_c));
+  else if constexpr (std::is_same_v<T, double>)
+    r = dlaf_mi355x_hermitian_multiplication_d(grid.context(), (char) side, (char) uplo, &alpha, mat_a.ptr(),
+                                               desc_of(mat_a), mat_b.ptr(), desc_of(mat_b), &beta, mat_c.ptr(),
+                                               desc_of(mat_c));
+  else if constexpr (std::is_same_v<T, std::complex<float>>)
+    r = dlaf_mi355x_hermitian_multiplication_c(grid.context(), (char) side, (char) uplo, &alpha, mat_a.ptr(),
+                                               desc_of(mat_a), mat_b.ptr(), desc_of(mat_b), &beta, mat_c.ptr(),
+                                               desc_of(mat_c));
+  else
+    r = dlaf_mi355x_hermitian_multiplication_z(grid.context(), (char) side, (char) uplo, &alpha, mat_a.ptr(),
+                                               desc_of(mat_a), mat_b.ptr(), desc_of(mat_b), &beta, mat_c.ptr(),
+                                               desc_of(mat_c));
+  if (r != 0)
+    internal::fail("hermitian_multiplication");
+}
+
+// the local overload
+template <Backend B, Device D, class T>
+void hermitian_multiplication(blas::Side side, blas::Uplo uplo, const T alpha, const Matrix<T, Device::CPU>& mat_a,
+                              const Matrix<T, Device::CPU>& mat_b, const T beta, Matrix<T, Device::CPU>& mat_c) {
+  comm::CommunicatorGrid grid = comm::CommunicatorGrid::single();
+  hermitian_multiplication<B, D, T>(grid, side, uplo, alpha, mat_a, mat_b, beta, mat_c);
 }
 
 // include/dlaf/eigensolver/gen_to_std.h:50, :101: A <- inv(L) A inv(L^H) (Lower) / inv(U^H) A inv(U) (Upper) with

@@ -203,6 +203,52 @@ DLAF_EXTERN_C void dlaf_mi355x_pztrmm(char side, char uplo, char op, char diag, 
                                       const int desca[9], dlaf_complex_z* b, int ib, int jb,
                                       const int descb[9]) DLAF_NOEXCEPT;
 
+/* ---- Hermitian multiplication -------------------------------------------------------------- */
+/* dlaf::hermitian_multiplication(grid, side, uplo, alpha, A, B, beta, C), include/dlaf/multiplication/hermitian.h
+ * (the reference has no C entry for it; the p?symm / p?hemm names take ScaLAPACK's argument list):
+ *   side 'L': C = beta C + alpha A B,  side 'R': C = beta C + alpha B A;  C (m x n) is overwritten, A and B are not.
+ * A: na x na Hermitian (na = m for 'L', n for 'R'); only its uplo triangle is read and, for complex types, the
+ * imaginary part of its diagonal is ignored (xHEMM).  Every side x uplo, on every grid (the reference implements
+ * side L / uplo L only).  beta = 0: C is not read.  alpha, beta passed by address; a, b, c: local column-major parts
+ * on the grid of `context`; only the m x n elements of c are written.  Requirements of this build, as for the solver:
+ * square blocks of A; B and C with the same blocks and source process, their block along A's dimension = A's (the
+ * other one is free); no sub-matrix offsets; A shares the source process of B and C along A's dimension.  Returns 0;
+ * a violated requirement terminates with a message "hermitian multiplication: ..." before the GPU is touched. */
+DLAF_EXTERN_C int dlaf_mi355x_hermitian_multiplication_s(int context, char side, char uplo, const float* alpha,
+                                                         const float* a, struct DLAF_descriptor desca, const float* b,
+                                                         struct DLAF_descriptor descb, const float* beta, float* c,
+                                                         struct DLAF_descriptor descc) DLAF_NOEXCEPT;
+DLAF_EXTERN_C int dlaf_mi355x_hermitian_multiplication_d(int context, char side, char uplo, const double* alpha,
+                                                         const double* a, struct DLAF_descriptor desca, const double* b,
+                                                         struct DLAF_descriptor descb, const double* beta, double* c,
+                                                         struct DLAF_descriptor descc) DLAF_NOEXCEPT;
+DLAF_EXTERN_C int dlaf_mi355x_hermitian_multiplication_c(int context, char side, char uplo, const dlaf_complex_c* alpha,
+                                                         const dlaf_complex_c* a, struct DLAF_descriptor desca,
+                                                         const dlaf_complex_c* b, struct DLAF_descriptor descb,
+                                                         const dlaf_complex_c* beta, dlaf_complex_c* c,
+                                                         struct DLAF_descriptor descc) DLAF_NOEXCEPT;
+DLAF_EXTERN_C int dlaf_mi355x_hermitian_multiplication_z(int context, char side, char uplo, const dlaf_complex_z* alpha,
+                                                         const dlaf_complex_z* a, struct DLAF_descriptor desca,
+                                                         const dlaf_complex_z* b, struct DLAF_descriptor descb,
+                                                         const dlaf_complex_z* beta, dlaf_complex_z* c,
+                                                         struct DLAF_descriptor descc) DLAF_NOEXCEPT;
+DLAF_EXTERN_C void dlaf_mi355x_pssymm(char side, char uplo, int m, int n, const float* alpha, const float* a, int ia,
+                                      int ja, const int desca[9], const float* b, int ib, int jb, const int descb[9],
+                                      const float* beta, float* c, int ic, int jc, const int descc[9]) DLAF_NOEXCEPT;
+DLAF_EXTERN_C void dlaf_mi355x_pdsymm(char side, char uplo, int m, int n, const double* alpha, const double* a, int ia,
+                                      int ja, const int desca[9], const double* b, int ib, int jb, const int descb[9],
+                                      const double* beta, double* c, int ic, int jc, const int descc[9]) DLAF_NOEXCEPT;
+DLAF_EXTERN_C void dlaf_mi355x_pchemm(char side, char uplo, int m, int n, const dlaf_complex_c* alpha,
+                                      const dlaf_complex_c* a, int ia, int ja, const int desca[9],
+                                      const dlaf_complex_c* b, int ib, int jb, const int descb[9],
+                                      const dlaf_complex_c* beta, dlaf_complex_c* c, int ic, int jc,
+                                      const int descc[9]) DLAF_NOEXCEPT;
+DLAF_EXTERN_C void dlaf_mi355x_pzhemm(char side, char uplo, int m, int n, const dlaf_complex_z* alpha,
+                                      const dlaf_complex_z* a, int ia, int ja, const int desca[9],
+                                      const dlaf_complex_z* b, int ib, int jb, const int descb[9],
+                                      const dlaf_complex_z* beta, dlaf_complex_z* c, int ic, int jc,
+                                      const int descc[9]) DLAF_NOEXCEPT;
+
 /* ScaLAPACK p?potrs: A X = B with the factor dlaf_p?potrf left in a (two triangular solves; b is overwritten) */
 DLAF_EXTERN_C void dlaf_mi355x_pspotrs(char uplo, int n, int nrhs, const float* a, int ia, int ja, const int desca[9],
                                        float* b, int ib, int jb, const int descb[9], int* info) DLAF_NOEXCEPT;
@@ -366,9 +412,16 @@ DLAF_EXTERN_C int dlaf_mi355x_solver_profile(double* ms, double* flops) DLAF_NOE
 DLAF_EXTERN_C int dlaf_mi355x_triangular_multiplication_device(char side, char uplo, char op, char diag,
                                                                const void* alpha, dlaf_mi355x_matrix_t a,
                                                                dlaf_mi355x_gmatrix_t b) DLAF_NOEXCEPT;
+/* hermitian_multiplication on resident operands (a: the uplo triangle of a dlaf_mi355x_matrix_t, b and c: general
+ * resident matrices of the same size, blocks and source process; only c is written); nothing crosses PCIe.  Same
+ * requirements as the host entry, with square blocks for b and c. */
+DLAF_EXTERN_C int dlaf_mi355x_hermitian_multiplication_device(char side, char uplo, const void* alpha,
+                                                              dlaf_mi355x_matrix_t a, dlaf_mi355x_gmatrix_t b,
+                                                              const void* beta, dlaf_mi355x_gmatrix_t c) DLAF_NOEXCEPT;
 /* Device time (ms, HIP events on the compute stream) of the sweep of the last triangular multiplication on this
  * process -- relayout and PCIe staging excluded -- and the whole-grid algorithmic flops it stands for (m n^2 for
- * side R, m^2 n for side L; x4 complex), as dlaf_mi355x_solver_profile. */
+ * side R, m^2 n for side L; x4 complex), as dlaf_mi355x_solver_profile.  The last multiplication of EITHER kind is
+ * reported: after a Hermitian multiplication, its sweep and twice those flops (2 m n^2 / 2 m^2 n; x4 complex). */
 DLAF_EXTERN_C int dlaf_mi355x_multiplication_profile(double* ms, double* flops) DLAF_NOEXCEPT;
 
 /* ---- synthetic input ------------------------------------------------------------------------ */

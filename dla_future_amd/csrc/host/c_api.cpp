@@ -174,38 +174,39 @@ static Grid& triangular_checks(const char* who, int ctx, char side, char uplo, c
   return g;
 }
 
-// dlaf::triangular_solver (include/dlaf/solver/triangular.h:41-177) through descriptors
+// The two routines over a triangular A, B = the m x n matrix they overwrite: dlaf::triangular_solver
+// (include/dlaf/solver/triangular.h:41-177) and dlaf::triangular_multiplication
+// (include/dlaf/multiplication/triangular.h), B = alpha op(A) B (side L) / alpha B op(A) (side R).  Same arguments,
+// same preconditions; who names the routine in the messages.
 template <class HT>
-int triangular_solver_c(int ctx, char side, char uplo, char op, char diag, const HT* alpha, const HT* a,
-                        const DLAF_descriptor& da, HT* b, const DLAF_descriptor& db) {
+struct TriangularOp {
   using DT = typename DevType<HT>::type;
-  Grid& g = triangular_checks("triangular solver", ctx, side, uplo, op, diag, da, db);
+  const char* who;
+  int (*host)(Grid*, char, char, char, char, DT, const DT*, long, int, int, DT*, long, long, long, int, int, int, int);
+};
+template <class HT>
+constexpr TriangularOp<HT> kTrsm{"triangular solver", &triangular_solver_host<typename DevType<HT>::type>};
+template <class HT>
+constexpr TriangularOp<HT> kTrmm{"triangular multiplication",
+                                 &triangular_multiplication_host<typename DevType<HT>::type>};
+
+// through descriptors
+template <class HT>
+int triangular_c(const TriangularOp<HT>& op_, int ctx, char side, char uplo, char op, char diag, const HT* alpha,
+                 const HT* a, const DLAF_descriptor& da, HT* b, const DLAF_descriptor& db) {
+  using DT = typename DevType<HT>::type;
+  Grid& g = triangular_checks(op_.who, ctx, side, uplo, op, diag, da, db);
   const bool left = (side == 'L' || side == 'l');
   DT al;
   std::memcpy(&al, alpha, sizeof(DT));
-  return triangular_solver_host<DT>(&g, side, uplo, op, diag, al, reinterpret_cast<const DT*>(a), da.ld, da.isrc,
-                                    da.jsrc, reinterpret_cast<DT*>(b), db.ld, db.m, db.n, da.nb, db.isrc, db.jsrc, left ? db.nb : db.mb);
+  return op_.host(&g, side, uplo, op, diag, al, reinterpret_cast<const DT*>(a), da.ld, da.isrc, da.jsrc,
+                  reinterpret_cast<DT*>(b), db.ld, db.m, db.n, da.nb, db.isrc, db.jsrc, left ? db.nb : db.mb);
 }
 
-// dlaf::triangular_multiplication (include/dlaf/multiplication/triangular.h) through descriptors: B = alpha op(A) B
-// (side L) / alpha B op(A) (side R), the solver's arguments and preconditions
+// ScaLAPACK p?trsm / p?trmm argument list
 template <class HT>
-int triangular_multiplication_c(int ctx, char side, char uplo, char op, char diag, const HT* alpha, const HT* a,
-                                const DLAF_descriptor& da, HT* b, const DLAF_descriptor& db) {
-  using DT = typename DevType<HT>::type;
-  Grid& g = triangular_checks("triangular multiplication", ctx, side, uplo, op, diag, da, db);
-  const bool left = (side == 'L' || side == 'l');
-  DT al;
-  std::memcpy(&al, alpha, sizeof(DT));
-  return triangular_multiplication_host<DT>(&g, side, uplo, op, diag, al, reinterpret_cast<const DT*>(a), da.ld, da.isrc,
-                                            da.jsrc, reinterpret_cast<DT*>(b), db.ld, db.m, db.n, da.nb, db.isrc, db.jsrc,
-                                            left ? db.nb : db.mb);
-}
-
-// ScaLAPACK p?trmm argument list
-template <class HT>
-void pxtrmm(char side, char uplo, char op, char diag, int m, int n, const HT* alpha, const HT* a, int ia, int ja,
-            const int desca[9], HT* b, int ib, int jb, const int descb[9]) {
+void pxtriangular(const TriangularOp<HT>& op_, char side, char uplo, char op, char diag, int m, int n, const HT* alpha,
+                  const HT* a, int ia, int ja, const int desca[9], HT* b, int ib, int jb, const int descb[9]) {
   if (desca[0] != 1 || descb[0] != 1)
     fatal("[dlaf_mi355x] desc[0] (dtype) must be 1\n");
   if (ia != 1 || ja != 1 || ib != 1 || jb != 1)
@@ -215,7 +216,7 @@ void pxtrmm(char side, char uplo, char op, char diag, int m, int n, const HT* al
   const int na = (side == 'L' || side == 'l') ? m : n;
   const DLAF_descriptor da = make_dlaf_descriptor(na, na, ia, ja, desca);
   const DLAF_descriptor db = make_dlaf_descriptor(m, n, ib, jb, descb);
-  (void) triangular_multiplication_c<HT>(desca[1], side, uplo, op, diag, alpha, a, da, b, db);
+  (void) triangular_c<HT>(op_, desca[1], side, uplo, op, diag, alpha, a, da, b, db);
 }
 
 // Preconditions of dlaf::hermitian_multiplication (include/dlaf/multiplication/hermitian.h) through descriptors, and
@@ -284,30 +285,14 @@ void pxhemm(char side, char uplo, int m, int n, const HT* alpha, const HT* a, in
   (void) hermitian_multiplication_c<HT>(desca[1], side, uplo, alpha, a, da, b, db, beta, c, dc);
 }
 
-// ScaLAPACK p?trsm argument list
-template <class HT>
-void pxtrsm(char side, char uplo, char op, char diag, int m, int n, const HT* alpha, const HT* a, int ia, int ja,
-            const int desca[9], HT* b, int ib, int jb, const int descb[9]) {
-  if (desca[0] != 1 || descb[0] != 1)
-    fatal("[dlaf_mi355x] desc[0] (dtype) must be 1\n");
-  if (ia != 1 || ja != 1 || ib != 1 || jb != 1)
-    fatal("[dlaf_mi355x] ia, ja, ib, jb must be 1\n");
-  if (desca[1] != descb[1])
-    fatal("[dlaf_mi355x] A and B live on different contexts (%d, %d)\n", desca[1], descb[1]);
-  const int na = (side == 'L' || side == 'l') ? m : n;
-  const DLAF_descriptor da = make_dlaf_descriptor(na, na, ia, ja, desca);
-  const DLAF_descriptor db = make_dlaf_descriptor(m, n, ib, jb, descb);
-  (void) triangular_solver_c<HT>(desca[1], side, uplo, op, diag, alpha, a, da, b, db);
-}
-
 // ScaLAPACK p?potrs: solve A X = B with the factor p?potrf left in a (uplo L: L L^H, uplo U: U^H U)
 template <class HT>
 void pxpotrs(char uplo, int n, int nrhs, const HT* a, int ia, int ja, const int desca[9], HT* b, int ib, int jb,
              const int descb[9], int* info) {
   const HT one(1);
   const bool lower = (uplo == 'L' || uplo == 'l');
-  pxtrsm<HT>('L', uplo, lower ? 'N' : 'C', 'N', n, nrhs, &one, a, ia, ja, desca, b, ib, jb, descb);
-  pxtrsm<HT>('L', uplo, lower ? 'C' : 'N', 'N', n, nrhs, &one, a, ia, ja, desca, b, ib, jb, descb);
+  pxtriangular<HT>(kTrsm<HT>, 'L', uplo, lower ? 'N' : 'C', 'N', n, nrhs, &one, a, ia, ja, desca, b, ib, jb, descb);
+  pxtriangular<HT>(kTrsm<HT>, 'L', uplo, lower ? 'C' : 'N', 'N', n, nrhs, &one, a, ia, ja, desca, b, ib, jb, descb);
   if (info)
     *info = 0;
 }
@@ -493,15 +478,10 @@ struct MatrixHandle {
   int ctx;
 };
 
+// dispatch_type (runtime.hpp) on a type letter that comes from the caller: -2 for one that names no type
 template <class F>
-int dispatch_type(char type, F&& f) {
-  switch (type) {
-    case 's': return f((float*) nullptr);
-    case 'd': return f((double*) nullptr);
-    case 'c': return f((cfloat*) nullptr);
-    case 'z': return f((cdouble*) nullptr);
-    default: return -2;
-  }
+int dispatch_api_type(char type, F&& f) {
+  return dispatch_type(type, f, [] { return -2; });
 }
 }  // namespace
 
@@ -748,34 +728,28 @@ int dlaf_mi355x_grid_host_bcast(int ctx, int axis, int root, void* host_buf, siz
   return g.host_bcast(g.host_user, axis, root, host_buf, bytes);
 }
 
-#define DLAF_MI355X_TRSM_ENTRY(S, HT, CT)                                                                        \
-  int dlaf_mi355x_triangular_solver_##S(int ctx, char side, char uplo, char op, char diag, const CT* alpha,      \
-                                        const CT* a, DLAF_descriptor desca, CT* b, DLAF_descriptor descb) noexcept { \
-    return triangular_solver_c<HT>(ctx, side, uplo, op, diag, reinterpret_cast<const HT*>(alpha),               \
-                                   reinterpret_cast<const HT*>(a), desca, reinterpret_cast<HT*>(b), descb);     \
+// NAME / PNAME / OP: triangular_solver / trsm / kTrsm, triangular_multiplication / trmm / kTrmm
+#define DLAF_MI355X_TRIANGULAR_ENTRY(S, HT, CT, NAME, PNAME, OP)                                                 \
+  int dlaf_mi355x_##NAME##_##S(int ctx, char side, char uplo, char op, char diag, const CT* alpha, const CT* a,   \
+                               DLAF_descriptor desca, CT* b, DLAF_descriptor descb) noexcept {                   \
+    return triangular_c<HT>(OP<HT>, ctx, side, uplo, op, diag, reinterpret_cast<const HT*>(alpha),               \
+                            reinterpret_cast<const HT*>(a), desca, reinterpret_cast<HT*>(b), descb);             \
   }                                                                                                             \
-  void dlaf_mi355x_p##S##trsm(char side, char uplo, char op, char diag, int m, int n, const CT* alpha, const CT* a, \
-                              int ia, int ja, const int desca[9], CT* b, int ib, int jb, const int descb[9]) noexcept { \
-    pxtrsm<HT>(side, uplo, op, diag, m, n, reinterpret_cast<const HT*>(alpha), reinterpret_cast<const HT*>(a), ia, \
-               ja, desca, reinterpret_cast<HT*>(b), ib, jb, descb);                                              \
+  void dlaf_mi355x_p##S##PNAME(char side, char uplo, char op, char diag, int m, int n, const CT* alpha, const CT* a, \
+                               int ia, int ja, const int desca[9], CT* b, int ib, int jb,                        \
+                               const int descb[9]) noexcept {                                                   \
+    pxtriangular<HT>(OP<HT>, side, uplo, op, diag, m, n, reinterpret_cast<const HT*>(alpha),                     \
+                     reinterpret_cast<const HT*>(a), ia, ja, desca, reinterpret_cast<HT*>(b), ib, jb, descb);    \
   }
-#define DLAF_MI355X_TRMM_ENTRY(S, HT, CT)                                                                        \
-  int dlaf_mi355x_triangular_multiplication_##S(int ctx, char side, char uplo, char op, char diag, const CT* alpha, \
-                                                const CT* a, DLAF_descriptor desca, CT* b,                       \
-                                                DLAF_descriptor descb) noexcept {                                \
-    return triangular_multiplication_c<HT>(ctx, side, uplo, op, diag, reinterpret_cast<const HT*>(alpha),       \
-                                           reinterpret_cast<const HT*>(a), desca, reinterpret_cast<HT*>(b), descb); \
-  }                                                                                                             \
-  void dlaf_mi355x_p##S##trmm(char side, char uplo, char op, char diag, int m, int n, const CT* alpha, const CT* a, \
-                              int ia, int ja, const int desca[9], CT* b, int ib, int jb, const int descb[9]) noexcept { \
-    pxtrmm<HT>(side, uplo, op, diag, m, n, reinterpret_cast<const HT*>(alpha), reinterpret_cast<const HT*>(a), ia, \
-               ja, desca, reinterpret_cast<HT*>(b), ib, jb, descb);                                              \
-  }
-DLAF_MI355X_TRMM_ENTRY(s, float, float)
-DLAF_MI355X_TRMM_ENTRY(d, double, double)
-DLAF_MI355X_TRMM_ENTRY(c, std::complex<float>, dlaf_complex_c)
-DLAF_MI355X_TRMM_ENTRY(z, std::complex<double>, dlaf_complex_z)
-#undef DLAF_MI355X_TRMM_ENTRY
+#define DLAF_MI355X_TRIANGULAR_ENTRIES(NAME, PNAME, OP)                                  \
+  DLAF_MI355X_TRIANGULAR_ENTRY(s, float, float, NAME, PNAME, OP)                         \
+  DLAF_MI355X_TRIANGULAR_ENTRY(d, double, double, NAME, PNAME, OP)                       \
+  DLAF_MI355X_TRIANGULAR_ENTRY(c, std::complex<float>, dlaf_complex_c, NAME, PNAME, OP)  \
+  DLAF_MI355X_TRIANGULAR_ENTRY(z, std::complex<double>, dlaf_complex_z, NAME, PNAME, OP)
+DLAF_MI355X_TRIANGULAR_ENTRIES(triangular_multiplication, trmm, kTrmm)
+DLAF_MI355X_TRIANGULAR_ENTRIES(triangular_solver, trsm, kTrsm)
+#undef DLAF_MI355X_TRIANGULAR_ENTRIES
+#undef DLAF_MI355X_TRIANGULAR_ENTRY
 #define DLAF_MI355X_HEMM_ENTRY(S, HT, CT, NAME)                                                                  \
   int dlaf_mi355x_hermitian_multiplication_##S(int ctx, char side, char uplo, const CT* alpha, const CT* a,         \
                                                DLAF_descriptor desca, const CT* b, DLAF_descriptor descb,          \
@@ -807,11 +781,6 @@ DLAF_MI355X_POTRS_ENTRY(d, double, double)
 DLAF_MI355X_POTRS_ENTRY(c, std::complex<float>, dlaf_complex_c)
 DLAF_MI355X_POTRS_ENTRY(z, std::complex<double>, dlaf_complex_z)
 #undef DLAF_MI355X_POTRS_ENTRY
-DLAF_MI355X_TRSM_ENTRY(s, float, float)
-DLAF_MI355X_TRSM_ENTRY(d, double, double)
-DLAF_MI355X_TRSM_ENTRY(c, std::complex<float>, dlaf_complex_c)
-DLAF_MI355X_TRSM_ENTRY(z, std::complex<double>, dlaf_complex_z)
-#undef DLAF_MI355X_TRSM_ENTRY
 
 #define DLAF_MI355X_HEGST_ENTRY(S, HT, CT, RT)                                                                    \
   int dlaf_mi355x_generalized_to_standard_##S(int ctx, char uplo, CT* a, DLAF_descriptor desca, const CT* b,       \
@@ -1046,7 +1015,7 @@ int dlaf_mi355x_matrix_create(int ctx, char type, char uplo, DLAF_descriptor d, 
   auto* h = new dlaf_mi355x_matrix_s;
   h->type = type;
   h->ctx = ctx;
-  const int r = dispatch_type(type, [&](auto* tag) {
+  const int r = dispatch_api_type(type, [&](auto* tag) {
     using DT = std::remove_pointer_t<decltype(tag)>;
     auto m = std::make_unique<DeviceMatrix<DT>>();
     m->create(g, uplo, d.m, d.nb, d.isrc, d.jsrc);
@@ -1068,7 +1037,7 @@ void dlaf_mi355x_matrix_destroy(dlaf_mi355x_matrix_t m) noexcept {
 #define WITH_MATRIX(handle, body)                                       \
   if (!(handle) || !(handle)->m)                                        \
     return -1;                                                          \
-  return dispatch_type((handle)->type, [&](auto* tag) -> int {         \
+  return dispatch_api_type((handle)->type, [&](auto* tag) -> int {         \
     using DT = std::remove_pointer_t<decltype(tag)>;                    \
     auto& M = static_cast<DeviceMatrix<DT>&>(*(handle)->m);             \
     body                                                                \
@@ -1161,31 +1130,29 @@ int dlaf_mi355x_set_random_hpd(int ctx, char type, void* host, DLAF_descriptor d
   if (d.m != d.n || d.mb != d.nb || d.nb < 1)
     return -3;
   Axis rows{d.m, d.nb, g.nprow, g.myrow, d.isrc}, cols{d.n, d.nb, g.npcol, g.mycol, d.jsrc};
-  switch (type) {
-    case 's': set_random_hpd_local(static_cast<float*>(host), d.ld, d.m, d.nb, rows, cols, nthreads); break;
-    case 'd': set_random_hpd_local(static_cast<double*>(host), d.ld, d.m, d.nb, rows, cols, nthreads); break;
-    case 'c': set_random_hpd_local(static_cast<std::complex<float>*>(host), d.ld, d.m, d.nb, rows, cols, nthreads); break;
-    case 'z': set_random_hpd_local(static_cast<std::complex<double>*>(host), d.ld, d.m, d.nb, rows, cols, nthreads); break;
-    default: return -2;
-  }
-  return 0;
+  return dispatch_api_type(type, [&](auto* tag) {
+    using DT = std::remove_pointer_t<decltype(tag)>;
+    using HT = std::conditional_t<TypeInfo<DT>::is_complex, std::complex<real_t<DT>>, DT>;
+    set_random_hpd_local(static_cast<HT*>(host), d.ld, d.m, d.nb, rows, cols, nthreads);
+    return 0;
+  });
 }
 
 int dlaf_mi355x_tile_potrf(char type, char uplo, int n, void* a, int lda) noexcept {
-  return dispatch_type(type, [&](auto* tag) {
+  return dispatch_api_type(type, [&](auto* tag) {
     using DT = std::remove_pointer_t<decltype(tag)>;
     return tile_potrf<DT>(uplo, n, static_cast<DT*>(a), lda);
   });
 }
 int dlaf_mi355x_tile_trsm(char type, char uplo, int m, int n, const void* a, int lda, void* b, int ldb) noexcept {
-  return dispatch_type(type, [&](auto* tag) {
+  return dispatch_api_type(type, [&](auto* tag) {
     using DT = std::remove_pointer_t<decltype(tag)>;
     tile_trsm<DT>(uplo, m, n, static_cast<const DT*>(a), lda, static_cast<DT*>(b), ldb);
     return 0;
   });
 }
 int dlaf_mi355x_tile_herk(char type, char uplo, int n, int k, const void* a, int lda, void* c, int ldc) noexcept {
-  return dispatch_type(type, [&](auto* tag) {
+  return dispatch_api_type(type, [&](auto* tag) {
     using DT = std::remove_pointer_t<decltype(tag)>;
     tile_herk<DT>(uplo, n, k, static_cast<const DT*>(a), lda, static_cast<DT*>(c), ldc);
     return 0;
@@ -1193,7 +1160,7 @@ int dlaf_mi355x_tile_herk(char type, char uplo, int n, int k, const void* a, int
 }
 int dlaf_mi355x_tile_gemm(char type, char uplo, int m, int n, int k, const void* a, int lda, const void* b, int ldb,
                           void* c, int ldc) noexcept {
-  return dispatch_type(type, [&](auto* tag) {
+  return dispatch_api_type(type, [&](auto* tag) {
     using DT = std::remove_pointer_t<decltype(tag)>;
     tile_gemm<DT>(uplo, m, n, k, static_cast<const DT*>(a), lda, static_cast<const DT*>(b), ldb, static_cast<DT*>(c), ldc);
     return 0;

@@ -23,7 +23,7 @@
 #include <vector>
 
 #include "runtime.hpp"
-#include "t_operand.hpp"
+#include "sweep.hpp"
 #include "tile_matrix.hpp"
 
 namespace dlaf_mi355x {
@@ -42,108 +42,43 @@ void multiply_canonical(TileMatrix<T>& Td, TileMatrix<T>& Bd, bool upper, bool u
   Grid* g = Bd.grid;
   Transport* tr = grid_transport(*g);
   const bool dist = g->nranks > 1;
-  const int nb = Bd.nb;
   const long nt = Bd.cols.nt();  // tiles along n
   if (nt == 0 || Bd.rows_global == 0)
     return;
-  const size_t tile_elems = Bd.tile_elems, tile_bytes = tile_elems * sizeof(T);
-  const CommAxis along_row = Bd.transposed ? CommAxis::Col : CommAxis::Row;
-  const bool aligned = Td.row_dim() == Bd.col_dim();
+  const size_t tile_elems = Bd.tile_elems;
   check_t_aligned(Td, Bd, "triangular multiplication");
 
-  // s_main: the updates; s_side: the panel TRMMs; s_comm: T operands and the P_k broadcasts
-  hipStream_t s_main = nullptr, s_side = nullptr, s_comm = nullptr;
-  int lo = 0, hi = 0;
-  DLAF_HIP_CHECK(hipDeviceGetStreamPriorityRange(&lo, &hi));
-  DLAF_HIP_CHECK(hipStreamCreateWithPriority(&s_main, hipStreamNonBlocking, lo));
-  DLAF_HIP_CHECK(hipStreamCreateWithPriority(&s_side, hipStreamNonBlocking, hi));
-  DLAF_HIP_CHECK(hipStreamCreateWithPriority(&s_comm, hipStreamNonBlocking, hi));
+  // s_main: the updates; s_side: the panel TRMMs; s_comm: T operands and the P_k broadcasts; the update kernel's
+  // status word (nothing here fails: it stays 0)
+  Sweep sw(true, true);
+  const hipStream_t s_main = sw.s_main, s_side = sw.s_side, s_comm = sw.s_comm;
   // ev_u: the update of step s has read P_k; ev_m: the TRMM of step s is done (and every buffer of the step free)
-  Events ev_t((size_t) nt), ev_xb((size_t) nt), ev_u((size_t) nt), ev_m((size_t) nt);
-  // the update kernel's status word (nothing here fails: it stays 0)
-  int* info = nullptr;
-  DLAF_HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&info), sizeof(int)));
-  DLAF_HIP_CHECK(hipMemsetAsync(info, 0, sizeof(int), s_main));
+  Events ev_xb((size_t) nt), ev_u((size_t) nt), ev_m((size_t) nt);
 
-  constexpr int kBuf = TOperandFetch<T>::kBuf;
-  T* diag_ws[kBuf] = {nullptr, nullptr, nullptr};
-  T* tpanel[kBuf] = {nullptr, nullptr, nullptr};
-  T* tstage[kBuf] = {nullptr, nullptr, nullptr};
-  T* xpanel[kBuf] = {nullptr, nullptr, nullptr};
-  for (int b = 0; b < kBuf; ++b) {
-    diag_ws[b] = tm_dev_alloc<T>(tile_elems);
-    if (dist) {
-      tpanel[b] = tm_dev_alloc<T>((size_t) Bd.ltc * tile_elems);
-      if (!aligned)
-        tstage[b] = tm_dev_alloc<T>((size_t) Td.ltr * tile_elems);
-      xpanel[b] = tm_dev_alloc<T>((size_t) Bd.ltr * tile_elems);
-    }
-  }
-
-  const std::vector<long> my_diag;  // (no inverted blocks)
-  std::vector<TOperand<T>> top((size_t) nt);
-  TOperandFetch<T> tf{Td, Bd, tr, upper, !upper, s_comm, my_diag, nullptr, 0, diag_ws, tpanel, tstage,
-                      ev_m.v.data(), ev_t.v.data(), top};
+  TOperandFetch<T> tf(Td, Bd, tr, upper, !upper, s_comm, ev_m);
+  Ring<T> xpanel((size_t) Bd.ltr * tile_elems, dist);
   std::vector<const T*> xp((size_t) nt, nullptr);  // P_k of step s as the update's first operand
 
   // s_comm: the T operands of step s and the original column k to the other members of my Bd row
   auto fetch = [&](long s) {
     tf.fetch(s);
-    const long k = tf.step_k(s);
-    const bool in_col = Bd.cols.mine(k);
-    const T* p = in_col ? Bd.tile(0, Bd.cols.local_of(k)) : nullptr;
-    if (Bd.cols.P > 1) {
-      T* dst = in_col ? Bd.tile(0, Bd.cols.local_of(k)) : xpanel[s % kBuf];
-      if (Bd.ltr > 0)
-        tr->bcast(along_row, Bd.cols.owner(k), Bd.cols.rank, dst, dst, (size_t) Bd.ltr * tile_bytes, s_comm);
-      p = dst;
+    xp[(size_t) s] = bcast_view_column(tr, Bd, tf.step_k(s), xpanel[(int) (s % kBuf)], s_comm);
+    if (Bd.cols.P > 1)
       DLAF_HIP_CHECK(hipEventRecord(ev_xb[(size_t) s], s_comm));
-    }
-    xp[(size_t) s] = p;
   };
 
   auto update = [&](long s, long j0, long j1) {
-    const TOperand<T>& o = top[(size_t) s];
+    const TOperand<T>& o = tf.top[(size_t) s];
     j0 = std::max(j0, o.jl0);
     j1 = std::min(j1, o.jl1);
     if (j0 >= j1 || Bd.ltr == 0)
       return;
-    const long k = tf.step_k(s);
-    UpdateArgs<T> ua;
-    ua.c = Bd.tiles;
-    ua.c_tsr = (long) tile_elems;
-    ua.c_tsc = (long) (tile_elems * Bd.ltr);
-    ua.ldc = nb;
-    ua.a = xp[(size_t) s];
-    ua.a_ts = (long) tile_elems;
-    ua.lda = nb;
-    ua.b = o.base + (j0 - o.jl0) * o.ts;
-    ua.b_ts = o.ts;
-    ua.ldb = nb;
-    ua.il0 = 0;
-    ua.il1 = (int) Bd.ltr;
-    ua.jl0 = (int) j0;
-    ua.jl1 = (int) j1;
-    ua.nb = nb;
-    ua.K = Bd.cols.tile_extent(k);
-    ua.pr = Bd.rows.P;
-    ua.ri = Bd.rows.shift();
-    ua.pc = Bd.cols.P;
-    ua.ci = Bd.cols.shift();
-    ua.nt = (int) Bd.rows.nt();
-    ua.last_rows = Bd.rows.last_extent();
-    ua.rect = 1;
-    ua.nt_c = (int) nt;
-    ua.last_cols = Bd.cols.last_extent();
-    ua.info = info;
-    launch_update(ua, s_main, 4);
+    launch_update(rect_update_args(Bd, tf.step_k(s), xp[(size_t) s], o.base + (j0 - o.jl0) * o.ts, o.ts, j0, j1,
+                                   sw.info.p),
+                  s_main, 4);
   };
 
-  hipEvent_t ev_t0, ev_t1;
-  DLAF_HIP_CHECK(hipEventCreate(&ev_t0));
-  DLAF_HIP_CHECK(hipEventCreate(&ev_t1));
-  DLAF_HIP_CHECK(hipEventRecord(ev_t0, s_main));
-  DLAF_HIP_CHECK(hipStreamWaitEvent(s_comm, ev_t0, 0));
+  sw.begin(true);
 
   // ---- the sweep --------------------------------------------------------------------------------------
   // s_main: U(s, all but the previous step's column) . [TRMM(s-1) done] . U(s, that column) -- the TRMM of step s-1
@@ -153,7 +88,7 @@ void multiply_canonical(TileMatrix<T>& Td, TileMatrix<T>& Bd, bool upper, bool u
     const long k = tf.step_k(s);
     if (s + 1 < nt)
       fetch(s + 1);
-    DLAF_HIP_CHECK(hipStreamWaitEvent(s_main, ev_t[(size_t) s], 0));
+    DLAF_HIP_CHECK(hipStreamWaitEvent(s_main, tf.ev_t[(size_t) s], 0));
     if (Bd.cols.P > 1)
       DLAF_HIP_CHECK(hipStreamWaitEvent(s_main, ev_xb[(size_t) s], 0));
     const long kp = s >= 1 ? tf.step_k(s - 1) : -1;  // the column the previous step's TRMM writes (beyond k)
@@ -172,20 +107,7 @@ void multiply_canonical(TileMatrix<T>& Td, TileMatrix<T>& Bd, bool upper, bool u
     // column k: B(:,k) = P_k T_kk^H once every read of P_k (the update above, the broadcast) is done
     DLAF_HIP_CHECK(hipStreamWaitEvent(s_side, ev_u[(size_t) s], 0));
     if (Bd.cols.mine(k) && Bd.ltr > 0) {
-      TrmmArgs<T> ta;
-      ta.b = Bd.tile(0, Bd.cols.local_of(k));
-      ta.b_ts = (long) tile_elems;
-      ta.ldb = nb;
-      ta.il0 = 0;
-      ta.il1 = (int) Bd.ltr;
-      ta.pr = Bd.rows.P;
-      ta.ri = Bd.rows.shift();
-      ta.nb = nb;
-      ta.nt = (int) Bd.rows.nt();
-      ta.last_rows = Bd.rows.last_extent();
-      ta.l = top[(size_t) s].diag;
-      ta.ldl = nb;
-      ta.n = Bd.cols.tile_extent(k);
+      auto ta = column_panel_args<TrmmArgs<T>>(Bd, k, tf.top[(size_t) s].diag);
       ta.upper = upper ? 1 : 0;
       ta.unit = unit ? 1 : 0;
       launch_trmm(ta, s_side);
@@ -194,32 +116,9 @@ void multiply_canonical(TileMatrix<T>& Td, TileMatrix<T>& Bd, bool upper, bool u
   }
   DLAF_HIP_CHECK(hipStreamWaitEvent(s_main, ev_m[(size_t) (nt - 1)], 0));
 
-  DLAF_HIP_CHECK(hipEventRecord(ev_t1, s_main));
-  DLAF_HIP_CHECK(hipStreamSynchronize(s_comm));
-  DLAF_HIP_CHECK(hipStreamSynchronize(s_side));
-  DLAF_HIP_CHECK(hipStreamSynchronize(s_main));
-  {
-    float ms = 0;
-    DLAF_HIP_CHECK(hipEventElapsedTime(&ms, ev_t0, ev_t1));
-    g_last_mult_ms = ms;
-    // whole-grid algorithmic flops: rows x n^2 (x4 complex), as for the solve
-    g_last_mult_flops = (TypeInfo<T>::is_complex ? 4.0 : 1.0) * (double) Bd.rows_global * (double) Bd.cols.n * (double) Bd.cols.n;
-  }
-  (void) hipEventDestroy(ev_t0);
-  (void) hipEventDestroy(ev_t1);
-  (void) hipStreamDestroy(s_main);
-  (void) hipStreamDestroy(s_side);
-  (void) hipStreamDestroy(s_comm);
-  (void) hipFree(info);
-  for (int b = 0; b < kBuf; ++b) {
-    (void) hipFree(diag_ws[b]);
-    if (tpanel[b])
-      (void) hipFree(tpanel[b]);
-    if (tstage[b])
-      (void) hipFree(tstage[b]);
-    if (xpanel[b])
-      (void) hipFree(xpanel[b]);
-  }
+  g_last_mult_ms = sw.finish();
+  // whole-grid algorithmic flops: rows x n^2 (x4 complex), as for the solve
+  g_last_mult_flops = (TypeInfo<T>::is_complex ? 4.0 : 1.0) * (double) Bd.rows_global * (double) Bd.cols.n * (double) Bd.cols.n;
 }
 
 // ================================================================================ Hermitian multiplication
@@ -230,7 +129,7 @@ void multiply_canonical(TileMatrix<T>& Td, TileMatrix<T>& Bd, bool upper, bool u
 // H(l, j) comes from the stored column l (j > l, adjoint), the diagonal tile (j = l) and the stored row l (j < l).
 // Broadcasts per step on a grid (all on s_comm, one step ahead, a ring of kBuf buffers per operand; no reduce):
 //   X(:, l)            along the process rows of the view from the owner column             Yd.ltr tiles
-//   column l of H      TOperandFetch (t_operand.hpp): one broadcast when H's rows are spread like Y's columns,
+//   column l of H      TOperandFetch (sweep.hpp)    : one broadcast when H's rows are spread like Y's columns,
 //                      else the Cholesky's panel + transposed-panel pair                    <= Yd.ltc (+ Hd.ltr) tiles
 //   row l of H         the mirror image: one broadcast when H's COLUMNS are spread like Y's columns, else the row
 //                      along Y's columns' dimension and then tile by tile down the other    <= Yd.ltc (+ Hd.ltc) tiles
@@ -250,39 +149,15 @@ void hermitian_canonical(TileMatrix<T>& Hd, TileMatrix<T>& Xd, TileMatrix<T>& Yd
   const bool aligned = Hd.row_dim() == Yd.col_dim();
   check_t_aligned(Hd, Yd, "hermitian multiplication");
 
-  hipStream_t s_main = nullptr, s_comm = nullptr;
-  int lo = 0, hi = 0;
-  DLAF_HIP_CHECK(hipDeviceGetStreamPriorityRange(&lo, &hi));
-  DLAF_HIP_CHECK(hipStreamCreateWithPriority(&s_main, hipStreamNonBlocking, lo));
-  DLAF_HIP_CHECK(hipStreamCreateWithPriority(&s_comm, hipStreamNonBlocking, hi));
-  // ev_t: column l and the diagonal tile are in place (TOperandFetch); ev_in: so are row l and X(:, l);
+  Sweep sw(false, false);
+  const hipStream_t s_main = sw.s_main, s_comm = sw.s_comm;
+  // tf.ev_t: column l and the diagonal tile are in place (TOperandFetch); ev_in: so are row l and X(:, l);
   // ev_done: the launch of step s is done, its buffers are free
-  Events ev_t((size_t) nt), ev_in((size_t) nt), ev_done((size_t) nt);
+  Events ev_in((size_t) nt), ev_done((size_t) nt);
 
-  constexpr int kBuf = TOperandFetch<T>::kBuf;
-  T* diag_ws[kBuf] = {nullptr, nullptr, nullptr};
-  T* tpanel[kBuf] = {nullptr, nullptr, nullptr};
-  T* tstage[kBuf] = {nullptr, nullptr, nullptr};
-  T* rpanel[kBuf] = {nullptr, nullptr, nullptr};
-  T* rstage[kBuf] = {nullptr, nullptr, nullptr};
-  T* xpanel[kBuf] = {nullptr, nullptr, nullptr};
-  for (int b = 0; b < kBuf; ++b) {
-    diag_ws[b] = tm_dev_alloc<T>(tile_elems);
-    if (dist) {
-      tpanel[b] = tm_dev_alloc<T>((size_t) Yd.ltc * tile_elems);
-      rpanel[b] = tm_dev_alloc<T>((size_t) Yd.ltc * tile_elems);
-      if (aligned)
-        rstage[b] = tm_dev_alloc<T>((size_t) Hd.ltc * tile_elems);
-      else
-        tstage[b] = tm_dev_alloc<T>((size_t) Hd.ltr * tile_elems);
-      xpanel[b] = tm_dev_alloc<T>((size_t) Yd.ltr * tile_elems);
-    }
-  }
-
-  const std::vector<long> my_diag;  // (no inverted blocks)
-  std::vector<TOperand<T>> top((size_t) nt);
-  TOperandFetch<T> tf{Hd, Yd, tr, false, false, s_comm, my_diag, nullptr, 0, diag_ws, tpanel, tstage,
-                      ev_done.v.data(), ev_t.v.data(), top};
+  TOperandFetch<T> tf(Hd, Yd, tr, false, false, s_comm, ev_done);
+  Ring<T> rpanel((size_t) Yd.ltc * tile_elems, dist), rstage((size_t) Hd.ltc * tile_elems, dist && aligned);
+  Ring<T> xpanel((size_t) Yd.ltr * tile_elems, dist);
   struct RowOperand {
     const T* base = nullptr;  // stored H(l, j) of local column jl < jr1 of Yd at base + jl * ts
     long ts = 0;
@@ -350,23 +225,11 @@ void hermitian_canonical(TileMatrix<T>& Hd, TileMatrix<T>& Xd, TileMatrix<T>& Yd
       }
     }
     // X(:, l) to the other members of my row of the view (X is not written: the owner sends its own tiles)
-    const bool in_col = Xd.cols.mine(l);
-    const T* xp = in_col ? Xd.tile(0, Xd.cols.local_of(l)) : nullptr;
-    if (Xd.cols.P > 1) {
-      T* dst = in_col ? Xd.tile(0, Xd.cols.local_of(l)) : xpanel[buf];
-      if (Xd.ltr > 0)
-        tr->bcast(along_row, Xd.cols.owner(l), Xd.cols.rank, dst, dst, (size_t) Xd.ltr * tile_bytes, s_comm);
-      xp = dst;
-    }
-    o.x = xp;
+    o.x = bcast_view_column(tr, Xd, l, xpanel[buf], s_comm);
     DLAF_HIP_CHECK(hipEventRecord(ev_in[(size_t) l], s_comm));
   };
 
-  hipEvent_t ev_t0, ev_t1;
-  DLAF_HIP_CHECK(hipEventCreate(&ev_t0));
-  DLAF_HIP_CHECK(hipEventCreate(&ev_t1));
-  DLAF_HIP_CHECK(hipEventRecord(ev_t0, s_main));
-  DLAF_HIP_CHECK(hipStreamWaitEvent(s_comm, ev_t0, 0));
+  sw.begin(true);
 
   fetch(0);
   for (long l = 0; l < nt; ++l) {
@@ -374,7 +237,7 @@ void hermitian_canonical(TileMatrix<T>& Hd, TileMatrix<T>& Xd, TileMatrix<T>& Yd
       fetch(l + 1);
     DLAF_HIP_CHECK(hipStreamWaitEvent(s_main, ev_in[(size_t) l], 0));
     if (Yd.ltr > 0 && Yd.ltc > 0) {
-      const TOperand<T>& o = top[(size_t) l];
+      const TOperand<T>& o = tf.top[(size_t) l];
       const RowOperand& r = rop[(size_t) l];
       HemmArgs<T> ha;
       ha.y = Yd.tiles;
@@ -410,40 +273,9 @@ void hermitian_canonical(TileMatrix<T>& Hd, TileMatrix<T>& Xd, TileMatrix<T>& Yd
     DLAF_HIP_CHECK(hipEventRecord(ev_done[(size_t) l], s_main));
   }
 
-  DLAF_HIP_CHECK(hipEventRecord(ev_t1, s_main));
-  DLAF_HIP_CHECK(hipStreamSynchronize(s_comm));
-  DLAF_HIP_CHECK(hipStreamSynchronize(s_main));
-  {
-    float ms = 0;
-    DLAF_HIP_CHECK(hipEventElapsedTime(&ms, ev_t0, ev_t1));
-    g_last_mult_ms = ms;
-    // whole-grid algorithmic flops: 2 x rows x na^2 (x4 complex)
-    g_last_mult_flops = (TypeInfo<T>::is_complex ? 8.0 : 2.0) * (double) Yd.rows_global * (double) Yd.cols.n * (double) Yd.cols.n;
-  }
-  (void) hipEventDestroy(ev_t0);
-  (void) hipEventDestroy(ev_t1);
-  (void) hipStreamDestroy(s_main);
-  (void) hipStreamDestroy(s_comm);
-  for (int b = 0; b < kBuf; ++b) {
-    (void) hipFree(diag_ws[b]);
-    for (T* p : {tpanel[b], tstage[b], rpanel[b], rstage[b], xpanel[b]})
-      if (p)
-        (void) hipFree(p);
-  }
-}
-
-template <class T>
-T conj_of(T v) {
-  if constexpr (TypeInfo<T>::is_complex)
-    v.im = -v.im;
-  return v;
-}
-template <class T>
-bool is_zero(const T& v) {
-  if constexpr (TypeInfo<T>::is_complex)
-    return v.re == 0 && v.im == 0;
-  else
-    return v == 0;
+  g_last_mult_ms = sw.finish();
+  // whole-grid algorithmic flops: 2 x rows x na^2 (x4 complex)
+  g_last_mult_flops = (TypeInfo<T>::is_complex ? 8.0 : 2.0) * (double) Yd.rows_global * (double) Yd.cols.n * (double) Yd.cols.n;
 }
 
 }  // namespace
@@ -467,19 +299,12 @@ int triangular_multiplication_device(char side, char uplo, char op, char diag, c
                                      MatrixBase* b) {
   if (!a || !b || a->type != b->type)
     fatal("[dlaf_mi355x] triangular multiplication: operands of different element types\n");
-  auto run = [&](auto* tag) {
+  return dispatch_type(a->type, [&](auto* tag) {
     using T = std::remove_pointer_t<decltype(tag)>;
     return triangular_canonical_device<T>("triangular multiplication", multiply_canonical<T>, side, uplo, op, diag,
                                           *static_cast<const T*>(alpha), static_cast<DeviceMatrix<T>&>(*a),
                                           static_cast<GeneralMatrix<T>&>(*b));
-  };
-  switch (a->type) {
-    case 's': return run((float*) nullptr);
-    case 'd': return run((double*) nullptr);
-    case 'c': return run((cfloat*) nullptr);
-    case 'z': return run((cdouble*) nullptr);
-    default: fatal("[dlaf_mi355x] bad matrix type\n");
-  }
+  });
 }
 
 // C = beta C + alpha A B (side L) / beta C + alpha B A (side R), A Hermitian in its uplo triangle.  Side R is the
@@ -489,8 +314,7 @@ template <class T>
 int hermitian_multiplication_host(Grid* g, char side, char uplo, T alpha, const T* a, long lda, int a_isrc, int a_jsrc,
                                   const T* b, long ldb, T beta, T* c, long ldc, long m, long n, int nb, int isrc, int jsrc,
                                   int nb_free) {
-  const bool left = (side == 'L' || side == 'l');
-  const bool a_upper = (uplo == 'U' || uplo == 'u');
+  const bool left = side_is_left(side), a_upper = uplo_is_upper(uplo);
   if (left ? (a_isrc != isrc) : (a_jsrc != jsrc))
     fatal("[dlaf_mi355x] hermitian multiplication: A must share the source process of B and C along A's dimension\n");
   if (m == 0 || n == 0)
@@ -532,8 +356,7 @@ int hermitian_device_t(char side, char uplo, T alpha, DeviceMatrix<T>& A, Genera
   Grid* g = A.grid;
   if (B.m.grid != g || C.m.grid != g)
     fatal("[dlaf_mi355x] %s: A, B and C live on different grids\n", who);
-  const bool left = (side == 'L' || side == 'l');
-  const bool a_upper = (uplo == 'U' || uplo == 'u');
+  const bool left = side_is_left(side), a_upper = uplo_is_upper(uplo);
   if (a_upper != A.transposed)
     fatal("[dlaf_mi355x] %s: uplo '%c' but the resident matrix holds its '%c' triangle\n", who, uplo, A.uplo);
   const long m = C.rows_g, n = C.cols_g, na = left ? m : n;
@@ -582,37 +405,23 @@ int hermitian_multiplication_device(char side, char uplo, const void* alpha, Mat
                                     const void* beta, MatrixBase* c) {
   if (!a || !b || !c || a->type != b->type || a->type != c->type)
     fatal("[dlaf_mi355x] hermitian multiplication: operands of different element types\n");
-  auto run = [&](auto* tag) {
+  return dispatch_type(a->type, [&](auto* tag) {
     using T = std::remove_pointer_t<decltype(tag)>;
     return hermitian_device_t<T>(side, uplo, *static_cast<const T*>(alpha), static_cast<DeviceMatrix<T>&>(*a),
                                  static_cast<GeneralMatrix<T>&>(*b), *static_cast<const T*>(beta),
                                  static_cast<GeneralMatrix<T>&>(*c));
-  };
-  switch (a->type) {
-    case 's': return run((float*) nullptr);
-    case 'd': return run((double*) nullptr);
-    case 'c': return run((cfloat*) nullptr);
-    case 'z': return run((cdouble*) nullptr);
-    default: fatal("[dlaf_mi355x] bad matrix type\n");
-  }
+  });
 }
 
-#define DLAF_HEMM_INST(T)                                                                                          \
+#define DLAF_MULT_INST(T)                                                                                          \
   template int hermitian_multiplication_host<T>(Grid*, char, char, T, const T*, long, int, int, const T*, long, T, T*, \
-                                                long, long, long, int, int, int, int);
-DLAF_HEMM_INST(float)
-DLAF_HEMM_INST(double)
-DLAF_HEMM_INST(cfloat)
-DLAF_HEMM_INST(cdouble)
-#undef DLAF_HEMM_INST
-
-template int triangular_multiplication_host<float>(Grid*, char, char, char, char, float, const float*, long, int, int,
-                                                   float*, long, long, long, int, int, int, int);
-template int triangular_multiplication_host<double>(Grid*, char, char, char, char, double, const double*, long, int, int,
-                                                    double*, long, long, long, int, int, int, int);
-template int triangular_multiplication_host<cfloat>(Grid*, char, char, char, char, cfloat, const cfloat*, long, int, int,
-                                                    cfloat*, long, long, long, int, int, int, int);
-template int triangular_multiplication_host<cdouble>(Grid*, char, char, char, char, cdouble, const cdouble*, long, int,
-                                                     int, cdouble*, long, long, long, int, int, int, int);
+                                                long, long, long, int, int, int, int);                                \
+  template int triangular_multiplication_host<T>(Grid*, char, char, char, char, T, const T*, long, int, int, T*, long, \
+                                                 long, long, int, int, int, int);
+DLAF_MULT_INST(float)
+DLAF_MULT_INST(double)
+DLAF_MULT_INST(cfloat)
+DLAF_MULT_INST(cdouble)
+#undef DLAF_MULT_INST
 
 }  // namespace dlaf_mi355x

@@ -2,6 +2,7 @@
 // order of a factorization is in cholesky.cpp.
 // See runtime.hpp for what each piece replaces in the reference.
 #include "runtime.hpp"
+#include "tile_matrix.hpp"
 
 #include <cstdarg>
 #include <cstdio>
@@ -1046,13 +1047,6 @@ int DeviceMatrix<T>::factorize_and_download(T* host, long ld) {
 
 // =============================================================================== single-tile ops
 namespace {
-template <class T>
-struct DevBuf {
-  T* p = nullptr;
-  explicit DevBuf(size_t elems) { p = dev_alloc<T>(elems); }
-  ~DevBuf() { (void) hipFree(p); }
-};
-
 // host (rows x cols, ld) -> dense device buffer in "device orientation" (transposed when tr)
 template <class T>
 void to_device(T* dst, const T* host, int ld, int rows, int cols, bool tr, T* tmp, hipStream_t s) {

@@ -131,6 +131,23 @@ struct MatrixBase {
   char type = 'd';
 };
 
+// f((T*) nullptr) with T the element type the letter names (s, d, c, z); bad() for any other letter
+template <class F, class Bad>
+auto dispatch_type(char type, F&& f, Bad&& bad) -> decltype(f((float*) nullptr)) {
+  switch (type) {
+    case 's': return f((float*) nullptr);
+    case 'd': return f((double*) nullptr);
+    case 'c': return f((cfloat*) nullptr);
+    case 'z': return f((cdouble*) nullptr);
+    default: return bad();
+  }
+}
+// the same for the type letter of a handle, where any other letter is a broken handle
+template <class F>
+auto dispatch_type(char type, F&& f) -> decltype(f((float*) nullptr)) {
+  return dispatch_type(type, f, []() -> decltype(f((float*) nullptr)) { fatal("[dlaf_mi355x] bad matrix type\n"); });
+}
+
 template <class T>
 struct DeviceMatrix : MatrixBase {
   Grid* grid = nullptr;

@@ -35,42 +35,12 @@
 #include <vector>
 
 #include "runtime.hpp"
-#include "t_operand.hpp"
+#include "sweep.hpp"
 #include "tile_matrix.hpp"
 
 namespace dlaf_mi355x {
 
 namespace {
-
-template <class T>
-T* dev_alloc(size_t elems) {
-  T* p = nullptr;
-  if (elems == 0)
-    elems = 1;
-  DLAF_HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&p), elems * sizeof(T)));
-  return p;
-}
-
-template <class T>
-T conj_el(T v) {
-  if constexpr (TypeInfo<T>::is_complex)
-    v.im = -v.im;
-  return v;
-}
-template <class T>
-double re_of_host(const T& v) {
-  if constexpr (TypeInfo<T>::is_complex)
-    return (double) v.re;
-  else
-    return (double) v;
-}
-template <class T>
-double im_of_host(const T& v) {
-  if constexpr (TypeInfo<T>::is_complex)
-    return (double) v.im;
-  else
-    return 0.0;
-}
 
 // device time of the last sweep on this process (HIP events on the compute stream; relayout and PCIe excluded)
 static double g_last_sweep_ms = 0;
@@ -88,142 +58,62 @@ void solve_canonical(TileMatrix<T>& Td, TileMatrix<T>& Bd, bool upper, bool unit
   const long nt = Bd.cols.nt();  // tiles along n
   if (nt == 0 || Bd.rows_global == 0)
     return;
-  const size_t tile_elems = Bd.tile_elems, tile_bytes = tile_elems * sizeof(T);
+  const size_t tile_elems = Bd.tile_elems;
   const size_t winv_elems = (size_t) ((nb + kDiagBlock - 1) / kDiagBlock) * kDiagBlock * kDiagBlock;
-  const size_t diag_elems = tile_elems + winv_elems;
-
-  // the communicator along Bd's rows (members differ in view-column coordinate); aligned: Td's rows live on the
-  // grid dimension of Bd's columns; crossed: on the one of Bd's rows
-  const CommAxis along_row = Bd.transposed ? CommAxis::Col : CommAxis::Row;
-  const bool aligned = Td.row_dim() == Bd.col_dim();
   check_t_aligned(Td, Bd, "triangular solver");
 
-  hipStream_t s_main = nullptr, s_comm = nullptr;
-  int lo = 0, hi = 0;
-  DLAF_HIP_CHECK(hipDeviceGetStreamPriorityRange(&lo, &hi));
-  DLAF_HIP_CHECK(hipStreamCreateWithPriority(&s_main, hipStreamNonBlocking, lo));
-  DLAF_HIP_CHECK(hipStreamCreateWithPriority(&s_comm, hipStreamNonBlocking, hi));
-  Events ev_t((size_t) nt), ev_x((size_t) nt), ev_xb((size_t) nt), ev_free((size_t) nt);
-
-  int* info = nullptr;
-  DLAF_HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&info), sizeof(int)));
-  DLAF_HIP_CHECK(hipMemsetAsync(info, 0, sizeof(int), s_main));
+  Sweep sw(false, true);
+  const hipStream_t s_main = sw.s_main, s_comm = sw.s_comm;
+  int* const info = sw.info.p;
+  Events ev_x((size_t) nt), ev_xb((size_t) nt), ev_free((size_t) nt), ev_prep(1);
 
   // ---- preparation: inverted 64 x 64 diagonal blocks of every local diagonal tile of Td ---------------
   std::vector<long> my_diag;  // global indices of the diagonal tiles I own
   for (long k = 0; k < nt; ++k)
     if (Td.rows.mine(k) && Td.cols.mine(k))
       my_diag.push_back(k);
-  T* winv_all = dev_alloc<T>(my_diag.size() * winv_elems);
-  DLAF_HIP_CHECK(hipMemsetAsync(winv_all, 0, std::max<size_t>(1, my_diag.size() * winv_elems) * sizeof(T), s_main));
+  DevBuf<T> winv_all(my_diag.size() * winv_elems);
+  std::vector<const T*> winv_of((size_t) nt, nullptr);
+  DLAF_HIP_CHECK(hipMemsetAsync(winv_all.p, 0, std::max<size_t>(1, my_diag.size() * winv_elems) * sizeof(T), s_main));
   for (size_t q = 0; q < my_diag.size(); ++q) {
     const long k = my_diag[q];
+    winv_of[(size_t) k] = winv_all.p + q * winv_elems;
     launch_invert_diag_blocks(Td.tile(Td.rows.local_of(k), Td.cols.local_of(k)), nb, Td.rows.tile_extent(k),
-                              winv_all + q * winv_elems, info, s_main, upper, unit);
+                              winv_all.p + q * winv_elems, info, s_main, upper, unit);
   }
-  hipEvent_t ev_prep;
-  DLAF_HIP_CHECK(hipEventCreateWithFlags(&ev_prep, hipEventDisableTiming));
-  DLAF_HIP_CHECK(hipEventRecord(ev_prep, s_main));
-  DLAF_HIP_CHECK(hipStreamWaitEvent(s_comm, ev_prep, 0));
+  DLAF_HIP_CHECK(hipEventRecord(ev_prep[0], s_main));
+  DLAF_HIP_CHECK(hipStreamWaitEvent(s_comm, ev_prep[0], 0));
 
-  // workspaces, kBuf of each (step s uses s % kBuf; the T operands of step s+1 are fetched while step s-1 is
-  // still being applied): [T_kk | W_k], the T column panel as the update's second operand (one tile per
-  // local column of Bd), its staging for the crossed shape, the X panel on non-owners
-  constexpr int kBuf = TOperandFetch<T>::kBuf;
-  T* diag_ws[kBuf] = {nullptr, nullptr, nullptr};
-  T* tpanel[kBuf] = {nullptr, nullptr, nullptr};
-  T* tstage[kBuf] = {nullptr, nullptr, nullptr};
-  T* xpanel[kBuf] = {nullptr, nullptr, nullptr};
-  for (int b = 0; b < kBuf; ++b) {
-    diag_ws[b] = dev_alloc<T>(diag_elems);
-    if (dist) {
-      tpanel[b] = dev_alloc<T>((size_t) Bd.ltc * tile_elems);
-      if (!aligned)
-        tstage[b] = dev_alloc<T>((size_t) Td.ltr * tile_elems);
-      xpanel[b] = dev_alloc<T>((size_t) Bd.ltr * tile_elems);
-    }
-  }
-
-  // global step order and the T operands of every step (t_operand.hpp)
-  auto step_k = [&](long s) { return upper ? nt - 1 - s : s; };
-  std::vector<TOperand<T>> top((size_t) nt);
-  TOperandFetch<T> tf{Td, Bd, tr, upper, upper, s_comm, my_diag, winv_all, winv_elems, diag_ws, tpanel, tstage,
-                      ev_free.v.data(), ev_t.v.data(), top};
-  auto fetch_t = [&](long s) { tf.fetch(s); };
+  // the T operands of every step (and the global step order), the X panel on the processes that do not own it
+  TOperandFetch<T> tf(Td, Bd, tr, upper, upper, s_comm, ev_free, winv_of.data(), winv_elems);
+  Ring<T> xpanel((size_t) Bd.ltr * tile_elems, dist);
 
   auto update = [&](long s, const T* xp, long j0, long j1) {
-    const TOperand<T>& o = top[(size_t) s];
+    const TOperand<T>& o = tf.top[(size_t) s];
     j0 = std::max(j0, o.jl0);
     j1 = std::min(j1, o.jl1);
     if (j0 >= j1 || Bd.ltr == 0)
       return;
-    const long k = step_k(s);
-    UpdateArgs<T> ua;
-    ua.c = Bd.tiles;
-    ua.c_tsr = (long) tile_elems;
-    ua.c_tsc = (long) (tile_elems * Bd.ltr);
-    ua.ldc = nb;
-    ua.a = xp;
-    ua.a_ts = (long) tile_elems;
-    ua.lda = nb;
-    ua.b = o.base + (j0 - o.jl0) * o.ts;
-    ua.b_ts = o.ts;
-    ua.ldb = nb;
-    ua.il0 = 0;
-    ua.il1 = (int) Bd.ltr;
-    ua.jl0 = (int) j0;
-    ua.jl1 = (int) j1;
-    ua.nb = nb;
-    ua.K = Bd.cols.tile_extent(k);
-    ua.pr = Bd.rows.P;
-    ua.ri = Bd.rows.shift();
-    ua.pc = Bd.cols.P;
-    ua.ci = Bd.cols.shift();
-    ua.nt = (int) Bd.rows.nt();
-    ua.last_rows = Bd.rows.last_extent();
-    ua.rect = 1;
-    ua.nt_c = (int) nt;
-    ua.last_cols = Bd.cols.last_extent();
-    ua.info = info;
-    launch_update(ua, s_main, 3);
+    launch_update(rect_update_args(Bd, tf.step_k(s), xp, o.base + (j0 - o.jl0) * o.ts, o.ts, j0, j1, info), s_main, 3);
   };
 
-  hipEvent_t ev_t0, ev_t1;
-  DLAF_HIP_CHECK(hipEventCreate(&ev_t0));
-  DLAF_HIP_CHECK(hipEventCreate(&ev_t1));
-  DLAF_HIP_CHECK(hipEventRecord(ev_t0, s_main));
+  sw.begin(false);  // (the preparation stays outside the window; s_comm waits for ev_prep)
 
   // ---- the sweep --------------------------------------------------------------------------------------
   // s_main: TRSM(s) . U(s, next column) . TRSM(s+1) . U(s, the rest) . U(s+1, next column) ...  so that the
   // X panel of step s+1 is on the wire under the bulk of step s; T operands arrive one step ahead on s_comm
-  fetch_t(0);
+  tf.fetch(0);
   const T* xp_prev = nullptr;
   for (long s = 0; s < nt; ++s) {
-    const long k = step_k(s);
-    const int buf = (int) (s % kBuf);
+    const long k = tf.step_k(s);
     if (s + 1 < nt)
-      fetch_t(s + 1);
-    DLAF_HIP_CHECK(hipStreamWaitEvent(s_main, ev_t[(size_t) s], 0));
+      tf.fetch(s + 1);
+    DLAF_HIP_CHECK(hipStreamWaitEvent(s_main, tf.ev_t[(size_t) s], 0));
 
     // column k of Bd: X(:,k) = B(:,k) T_kk^-H
-    const bool in_col = Bd.cols.mine(k);
-    const long klc = in_col ? Bd.cols.local_of(k) : -1;
-    if (in_col && Bd.ltr > 0) {
-      TrsmArgs<T> ta;
-      ta.b = Bd.tile(0, klc);
-      ta.b_ts = (long) tile_elems;
-      ta.ldb = nb;
-      ta.il0 = 0;
-      ta.il1 = (int) Bd.ltr;
-      ta.pr = Bd.rows.P;
-      ta.ri = Bd.rows.shift();
-      ta.nb = nb;
-      ta.nt = (int) Bd.rows.nt();
-      ta.last_rows = Bd.rows.last_extent();
-      ta.l = top[(size_t) s].diag;
-      ta.ldl = nb;
-      ta.winv = top[(size_t) s].winv;
-      ta.n = Bd.cols.tile_extent(k);
+    if (Bd.cols.mine(k) && Bd.ltr > 0) {
+      auto ta = column_panel_args<TrsmArgs<T>>(Bd, k, tf.top[(size_t) s].diag);
+      ta.winv = tf.top[(size_t) s].winv;
       ta.info = info;
       ta.upper = upper ? 1 : 0;
       launch_trsm(ta, s_main);
@@ -231,15 +121,11 @@ void solve_canonical(TileMatrix<T>& Td, TileMatrix<T>& Bd, bool upper, bool unit
     DLAF_HIP_CHECK(hipEventRecord(ev_x[(size_t) s], s_main));
 
     // the solved panel to the other members of my Bd row
-    const T* xp = in_col ? Bd.tile(0, klc) : nullptr;
-    if (Bd.cols.P > 1) {
+    if (Bd.cols.P > 1)
       DLAF_HIP_CHECK(hipStreamWaitEvent(s_comm, ev_x[(size_t) s], 0));
-      T* dst = in_col ? Bd.tile(0, klc) : xpanel[buf];
-      if (Bd.ltr > 0)
-        tr->bcast(along_row, Bd.cols.owner(k), Bd.cols.rank, dst, dst, (size_t) Bd.ltr * tile_bytes, s_comm);
-      xp = dst;
+    const T* xp = bcast_view_column(tr, Bd, k, xpanel[(int) (s % kBuf)], s_comm);
+    if (Bd.cols.P > 1)
       DLAF_HIP_CHECK(hipEventRecord(ev_xb[(size_t) s], s_comm));
-    }
 
     // what is left of the previous step's update runs under that broadcast
     if (s >= 1) {
@@ -259,7 +145,7 @@ void solve_canonical(TileMatrix<T>& Td, TileMatrix<T>& Bd, bool upper, bool unit
 
     // lookahead: the column the next step solves
     if (s + 1 < nt) {
-      const long kn = step_k(s + 1);
+      const long kn = tf.step_k(s + 1);
       if (Bd.cols.mine(kn)) {
         const long jn = Bd.cols.local_of(kn);
         update(s, xp, jn, jn + 1);
@@ -270,32 +156,9 @@ void solve_canonical(TileMatrix<T>& Td, TileMatrix<T>& Bd, bool upper, bool unit
   // the last step has nothing beyond it; its event only releases the buffers
   DLAF_HIP_CHECK(hipEventRecord(ev_free[(size_t) (nt - 1)], s_main));
 
-  DLAF_HIP_CHECK(hipEventRecord(ev_t1, s_main));
-  DLAF_HIP_CHECK(hipStreamSynchronize(s_comm));
-  DLAF_HIP_CHECK(hipStreamSynchronize(s_main));
-  {
-    float ms = 0;
-    DLAF_HIP_CHECK(hipEventElapsedTime(&ms, ev_t0, ev_t1));
-    g_last_sweep_ms = ms;
-    // whole-grid algorithmic flops: rows x n^2 (x4 complex)
-    g_last_sweep_flops = (TypeInfo<T>::is_complex ? 4.0 : 1.0) * (double) Bd.rows_global * (double) Bd.cols.n * (double) Bd.cols.n;
-  }
-  (void) hipEventDestroy(ev_t0);
-  (void) hipEventDestroy(ev_t1);
-  (void) hipEventDestroy(ev_prep);
-  (void) hipStreamDestroy(s_main);
-  (void) hipStreamDestroy(s_comm);
-  (void) hipFree(info);
-  (void) hipFree(winv_all);
-  for (int b = 0; b < kBuf; ++b) {
-    (void) hipFree(diag_ws[b]);
-    if (tpanel[b])
-      (void) hipFree(tpanel[b]);
-    if (tstage[b])
-      (void) hipFree(tstage[b]);
-    if (xpanel[b])
-      (void) hipFree(xpanel[b]);
-  }
+  g_last_sweep_ms = sw.finish();
+  // whole-grid algorithmic flops: rows x n^2 (x4 complex)
+  g_last_sweep_flops = (TypeInfo<T>::is_complex ? 4.0 : 1.0) * (double) Bd.rows_global * (double) Bd.cols.n * (double) Bd.cols.n;
 }
 
 }  // namespace
@@ -320,25 +183,10 @@ int triangular_canonical_host(const char* who, CanonicalSweep<T> sweep, bool may
     fatal("[dlaf_mi355x] grid with %d ranks has no transport\n", g->nranks);
   if (m == 0 || n == 0)
     return 0;
-  const bool left = (side == 'L' || side == 'l');
-  const bool a_upper = (uplo == 'U' || uplo == 'u');
-  const char o = (op == 'n') ? 'N' : (op == 't') ? 'T' : (op == 'c') ? 'C' : op;
-  const bool unit = (diag == 'U' || diag == 'u');
+  const auto [left, a_upper, unit, t_transposed, t_conj, t_upper] = operand_map(side, uplo, op, diag);
   const long na = left ? m : n;
   if (left ? (a_isrc != b_isrc) : (a_jsrc != b_jsrc))
     fatal("[dlaf_mi355x] %s: A and B must share the source process along the triangular dimension\n", who);
-
-  // T = A (Right C / Left N), A^H (Right N / Left C), conj(A) (Right T), A^T (Left T)
-  bool t_transposed, t_conj;
-  if (left) {
-    t_transposed = (o != 'N');
-    t_conj = (o == 'C');
-  }
-  else {
-    t_transposed = (o == 'N');
-    t_conj = (o == 'N' || o == 'T');
-  }
-  const bool t_upper = a_upper != t_transposed;
 
   hipStream_t s = nullptr;
   DLAF_HIP_CHECK(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
@@ -364,7 +212,7 @@ int triangular_canonical_host(const char* who, CanonicalSweep<T> sweep, bool may
     }
     Td.upload(a, lda, t_conj, false, T{}, s);
     // Left: B_dev = (alpha B)^H = conj(alpha) B^H (the relayout conjugates first, then scales)
-    Bd.upload(b, ldb, left, true, left ? conj_el(alpha) : alpha, s);
+    Bd.upload(b, ldb, left, true, left ? conj_of(alpha) : alpha, s);
     DLAF_HIP_CHECK(hipStreamSynchronize(s));
     sweep(Td, Bd, reversed ? false : t_upper, unit);
     Bd.download(b, ldb, left, s);
@@ -398,13 +246,7 @@ MatrixBase* general_matrix_create(Grid* g, char type, long m, long n, int nb, in
     gm->m.create(g, false, m, n, nb, isrc, jsrc);
     return gm;
   };
-  switch (type) {
-    case 's': return make((float*) nullptr);
-    case 'd': return make((double*) nullptr);
-    case 'c': return make((cfloat*) nullptr);
-    case 'z': return make((cdouble*) nullptr);
-    default: return nullptr;
-  }
+  return dispatch_type(type, make, []() -> MatrixBase* { return nullptr; });
 }
 
 template <class T>
@@ -420,13 +262,9 @@ static void gm_transfer(GeneralMatrix<T>& gm, void* host, long ld, bool up) {
 }
 
 void general_matrix_transfer(MatrixBase* h, void* host, long ld, bool upload) {
-  switch (h->type) {
-    case 's': gm_transfer(static_cast<GeneralMatrix<float>&>(*h), host, ld, upload); break;
-    case 'd': gm_transfer(static_cast<GeneralMatrix<double>&>(*h), host, ld, upload); break;
-    case 'c': gm_transfer(static_cast<GeneralMatrix<cfloat>&>(*h), host, ld, upload); break;
-    case 'z': gm_transfer(static_cast<GeneralMatrix<cdouble>&>(*h), host, ld, upload); break;
-    default: fatal("[dlaf_mi355x] bad matrix type\n");
-  }
+  dispatch_type(h->type, [&](auto* tag) {
+    gm_transfer(static_cast<GeneralMatrix<std::remove_pointer_t<decltype(tag)>>&>(*h), host, ld, upload);
+  });
 }
 
 // dst view tile (il, jl) = alpha * op(src tile): src (il, jl) for the copying ops (4 conjugate, 5 copy), src (jl, il)
@@ -454,12 +292,9 @@ int triangular_canonical_device(const char* who, CanonicalSweep<T> sweep, char s
   Grid* g = A.grid;
   if (B.m.grid != g)
     fatal("[dlaf_mi355x] %s: A and B live on different grids\n", who);
-  const bool left = (side == 'L' || side == 'l');
-  const bool a_upper = (uplo == 'U' || uplo == 'u');
+  const auto [left, a_upper, unit, t_transposed, t_conj, t_upper] = operand_map(side, uplo, op, diag);
   if (a_upper != A.transposed)
     fatal("[dlaf_mi355x] %s: uplo '%c' but the resident matrix holds its '%c' triangle\n", who, uplo, A.uplo);
-  const char o = (op == 'n') ? 'N' : (op == 't') ? 'T' : (op == 'c') ? 'C' : op;
-  const bool unit = (diag == 'U' || diag == 'u');
   const long m = B.rows_g, n = B.cols_g, na = left ? m : n;
   const int nb = A.nb;
   if (A.n != na || B.m.nb != nb)
@@ -472,17 +307,6 @@ int triangular_canonical_device(const char* who, CanonicalSweep<T> sweep, char s
   const Axis& a_cols = A.transposed ? A.rows : A.cols;
   if (left ? (a_rows.src != B.isrc) : (a_cols.src != B.jsrc))
     fatal("[dlaf_mi355x] %s: A and B must share the source process along the triangular dimension\n", who);
-  // T = A (Right C / Left N), A^H (Right N / Left C), conj(A) (Right T), A^T (Left T) -- as in triangular_solver_host
-  bool t_transposed, t_conj;
-  if (left) {
-    t_transposed = (o != 'N');
-    t_conj = (o == 'C');
-  }
-  else {
-    t_transposed = (o == 'N');
-    t_conj = (o == 'N' || o == 'T');
-  }
-  const bool t_upper = a_upper != t_transposed;
   // in terms of the STORED tiles S (S = A for uplo L, S = A^T for uplo U): T = op(S)
   const bool s_transpose = t_transposed != A.transposed;
   const int t_mode = s_transpose ? (t_conj ? 0 : 3) : (t_conj ? 4 : 5);
@@ -499,11 +323,11 @@ int triangular_canonical_device(const char* who, CanonicalSweep<T> sweep, char s
       Td.create(g, t_transposed, na, na, nb, a_rows.src, a_cols.src);
       xform_tiles(Td.tiles, Td.ltr, Td.ltc, A.tiles, A.ltr, te, nb, t_mode, T{}, false, s);
     }
-    const bool scale = !(re_of_host(alpha) == 1 && im_of_host(alpha) == 0);
+    const bool scale = !is_one(alpha);
     if (left) {
       // B_dev = (alpha B)^H = conj(alpha) B^H
       Bd.create(g, true, m, n, nb, B.isrc, B.jsrc);
-      xform_tiles(Bd.tiles, Bd.ltr, Bd.ltc, B.m.tiles, B.m.ltr, te, nb, 0, conj_el(alpha), scale, s);
+      xform_tiles(Bd.tiles, Bd.ltr, Bd.ltc, B.m.tiles, B.m.ltr, te, nb, 0, conj_of(alpha), scale, s);
     }
     else {
       Bd.create(g, false, m, n, nb, B.isrc, B.jsrc, B.m.tiles);  // in place
@@ -524,19 +348,12 @@ int triangular_canonical_device(const char* who, CanonicalSweep<T> sweep, char s
 int triangular_solver_device(char side, char uplo, char op, char diag, const void* alpha, MatrixBase* a, MatrixBase* b) {
   if (!a || !b || a->type != b->type)
     fatal("[dlaf_mi355x] triangular solver: operands of different element types\n");
-  auto run = [&](auto* tag) {
+  return dispatch_type(a->type, [&](auto* tag) {
     using T = std::remove_pointer_t<decltype(tag)>;
     return triangular_canonical_device<T>("triangular solver", solve_canonical<T>, side, uplo, op, diag,
                                           *static_cast<const T*>(alpha), static_cast<DeviceMatrix<T>&>(*a),
                                           static_cast<GeneralMatrix<T>&>(*b));
-  };
-  switch (a->type) {
-    case 's': return run((float*) nullptr);
-    case 'd': return run((double*) nullptr);
-    case 'c': return run((cfloat*) nullptr);
-    case 'z': return run((cdouble*) nullptr);
-    default: fatal("[dlaf_mi355x] bad matrix type\n");
-  }
+  });
 }
 
 #define DLAF_CANONICAL_INST(T)                                                                                   \
@@ -544,20 +361,13 @@ int triangular_solver_device(char side, char uplo, char op, char diag, const voi
                                             const T*, long, int, int, T*, long, long, long, int, int, int, int);    \
   template int triangular_canonical_device<T>(const char*, CanonicalSweep<T>, char, char, char, char, T,             \
                                               DeviceMatrix<T>&, GeneralMatrix<T>&);                                \
-  template void xform_tiles<T>(T*, long, long, const T*, long, size_t, int, int, T, bool, hipStream_t);
+  template void xform_tiles<T>(T*, long, long, const T*, long, size_t, int, int, T, bool, hipStream_t);            \
+  template int triangular_solver_host<T>(Grid*, char, char, char, char, T, const T*, long, int, int, T*, long, long, \
+                                         long, int, int, int, int);
 DLAF_CANONICAL_INST(float)
 DLAF_CANONICAL_INST(double)
 DLAF_CANONICAL_INST(cfloat)
 DLAF_CANONICAL_INST(cdouble)
 #undef DLAF_CANONICAL_INST
-
-template int triangular_solver_host<float>(Grid*, char, char, char, char, float, const float*, long, int, int, float*,
-                                           long, long, long, int, int, int, int);
-template int triangular_solver_host<double>(Grid*, char, char, char, char, double, const double*, long, int, int,
-                                            double*, long, long, long, int, int, int, int);
-template int triangular_solver_host<cfloat>(Grid*, char, char, char, char, cfloat, const cfloat*, long, int, int,
-                                            cfloat*, long, long, long, int, int, int, int);
-template int triangular_solver_host<cdouble>(Grid*, char, char, char, char, cdouble, const cdouble*, long, int, int,
-                                             cdouble*, long, long, long, int, int, int, int);
 
 }  // namespace dlaf_mi355x

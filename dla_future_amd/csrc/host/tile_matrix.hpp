@@ -19,6 +19,18 @@ inline T* tm_dev_alloc(size_t elems) {
   return p;
 }
 
+// a device allocation that lives as long as its scope (empty until alloc())
+template <class T>
+struct DevBuf {
+  T* p = nullptr;
+  DevBuf() = default;
+  explicit DevBuf(size_t elems) { alloc(elems); }
+  DevBuf(const DevBuf&) = delete;
+  DevBuf& operator=(const DevBuf&) = delete;
+  ~DevBuf() { (void) hipFree(p); }
+  void alloc(size_t elems) { p = tm_dev_alloc<T>(elems); }
+};
+
 // General block-cyclic matrix in device tile layout (nb x nb tiles, tile (il,jl) at (il + jl*ltr) nb^2).
 template <class T>
 struct TileMatrix {

@@ -34,25 +34,11 @@ template <>
 struct UpdateCfg<double> {
   // 2 stages x BK 16 and 4 stages x BK 8 measure the same (67.5 TFlop/s standalone): the in-loop
   // global traffic costs clock (DVFS), not latency -- see DESIGN.md
-#if defined(DLAF_UPD_BIG)
-  // 256 x 128 block, 8 waves (4 x 2 wave tiles of 64 x 64), one workgroup per compute unit: 25 % fewer
-  // L2 -> LDS bytes per flop than two independent 128 x 128 blocks
-  using type = BlockCfg<double, 256, 128, 64, 64, 16, true, DLAF_UPD_BIG, 512>;
-  static constexpr int min_waves = 2;
-#elif defined(DLAF_UPD_WIDE4)
-  // tuning aid (round 3): 256 x 128 block on FOUR waves (2 x 2 wave tiles of 128 x 64 = 8 x 4 MFMA tiles, 256
-  // accumulator registers: one wave per SIMD, one workgroup per compute unit) -- the "fewer LDS bytes per flop"
-  // variant of DESIGN section 8.2: 0.375 fragment reads per MFMA instead of 0.5, 25 % fewer L2 -> LDS bytes
-  using type = BlockCfg<double, 256, 128, 128, 64, 16, true, DLAF_UPD_WIDE4, 256>;
-  static constexpr int min_waves = 1;
-#elif defined(DLAF_UPD_BK) && defined(DLAF_UPD_ST)
-  // tuning aid (tools/run_ab_ring.sh): slab depth / ring depth of the direct-to-LDS pipeline
-  using type = BlockCfg<double, 128, 128, 64, 64, DLAF_UPD_BK, true, DLAF_UPD_ST>;
-  static constexpr int min_waves = 2;
-#else
+  // The 256 x 128 blocks (8 waves, and 4 waves with 128 x 64 wave tiles) and deeper rings measured slower or equal:
+  // profiles/r02_update_kernel_block_shapes_timing.txt, r03_update_kernel_wide4_lean_ab_timing.txt,
+  // r02_update_kernel_ring_depth_timing.txt
   using type = BlockCfg<double, 128, 128, 64, 64, 16, true, 2>;
   static constexpr int min_waves = 2;
-#endif
 };
 template <>
 struct UpdateCfg<cfloat> {
@@ -110,8 +96,6 @@ __global__ void cu_probe_kernel(unsigned* seen) {
 }
 
 // One work item = one BM x BN block of one tile.  Returns early for blocks outside the domain.
-// PART: 0 every block; 1 only the interior blocks (whole BM x BN, whole slabs, no triangle mask: the K loop on the
-// direct-to-LDS path + the wide epilogue, nothing else compiled in); 2 only the others (edge / masked blocks)
 // ADD: C += A B^H instead of C -= A B^H (the triangular multiplication's update)
 template <class X, class Y>
 __device__ __forceinline__ X upd_apply(X cv, Y a, std::false_type) {
@@ -122,7 +106,7 @@ __device__ __forceinline__ X upd_apply(X cv, Y a, std::true_type) {
   return cv + a;
 }
 
-template <class T, bool VEC, bool UTAIL = false, int PART = 0, bool ADD = false>
+template <class T, bool VEC, bool UTAIL = false, bool ADD = false>
 __device__ __forceinline__ void update_block(const UpdateArgs<T>& p, const UpdateMap& mp, long w,
                                              real_t<T>* __restrict__ lds, int s0 = 0) {
   using Cfg = typename UpdateCfg<T>::type;
@@ -202,23 +186,6 @@ __device__ __forceinline__ void update_block(const UpdateArgs<T>& p, const Updat
     A2 = p.a2 + aoff + m0 - (long) K1 * p.lda;
     B2 -= (long) K1 * ldb;
   }
-#ifdef DLAF_DBG_STRIP_PACKED
-  // tuning aid (tools/update_bench.hip): operands read as if every BM-row strip of a tile were stored
-  // contiguously (k-major, leading dimension BM): one sequential 1 MiB stream per strip instead of 1 KiB pieces
-  // 8 KiB apart.  Timing only -- the values are whatever lies there.
-  const long lda_x = Cfg::BM, ldb_x = Cfg::BN;
-  A = p.a + aoff + (long) (m0 / Cfg::BM) * Cfg::BM * p.nb;
-  B = (diag ? p.a + aoff : p.b + boff) + (long) (n0 / Cfg::BN) * Cfg::BN * p.nb;
-#define DLAF_LDA_X lda_x
-#define DLAF_LDB_X ldb_x
-#else
-#define DLAF_LDA_X p.lda
-#define DLAF_LDB_X ldb
-#endif
-#ifdef DLAF_DBG_SAME_STRIPS
-  A = p.a;  // tuning aid (tools/update_bench.hip): every block streams the same two strips = perfect L2 locality
-  B = p.b;
-#endif
   T* C = p.c + (long) il * p.c_tsr + (long) jl * p.c_tsc + m0 + (long) n0 * p.ldc;
 
   // The operand bases are the same for every lane of the workgroup; say so (they come out of the work-item
@@ -229,30 +196,20 @@ __device__ __forceinline__ void update_block(const UpdateArgs<T>& p, const Updat
     const unsigned hi = (unsigned) __builtin_amdgcn_readfirstlane((int) (unsigned) (v >> 32));
     return reinterpret_cast<const T*>(((unsigned long long) hi << 32) | lo);
   };
-#if DLAF_GLDS_SCALAR_ADDR
   A = uniform(A);
   B = uniform(B);
   A2 = uniform(A2);
   B2 = uniform(B2);
-#endif
   const bool full = (mrows == Cfg::BM) && (ncols == Cfg::BN) && (p.K % Cfg::BK == 0) && (p.K1 % Cfg::BK == 0);
-  if constexpr (PART != 0) {
-    const bool interior = full && !(diag && m0 < n0 + ncols - 1) && VEC && ((p.ldc * (long) sizeof(T)) % 16 == 0) &&
-                          (reinterpret_cast<uintptr_t>(C) % 16 == 0);
-    if ((PART == 1) != interior)
-      return;
-  }
   Acc<Cfg> acc;
-#ifndef DLAF_UPD_PRELOAD
-#define DLAF_UPD_PRELOAD 1
-#endif
-  if constexpr (DLAF_UPD_PRELOAD && Cfg::PAIRED && !Cfg::CX && sizeof(R) == 8 && VEC && !UTAIL) {
+  if constexpr (Cfg::PAIRED && !Cfg::CX && sizeof(R) == 8 && VEC && !UTAIL) {
     // Interior blocks (fp64 fast path): C is loaded INTO the accumulators before the K loop -- the loads travel
     // with the first slabs, whose arrival the loop waits for anyway -- and the MFMAs subtract (neg:[1,0,0]), so
     // the block ends with plain stores instead of 16 load -> wait -> subtract -> store round trips.  A/B on one
-    // MI355X (tools/run_ab_preload.sh): one-block-per-workgroup launches 66.3 -> 67.8 TFlop/s (N = 49152, K =
-    // 1024); the persistent bulk launches LOSE 3 % (66.9 -> 65.0; nb = 512: 61.2 -> 57.4 -- the stores of block i
-    // and the C loads of block i+1 queue ahead of its first slabs), so the bulk instantiation keeps the old form.
+    // MI355X (profiles/r02_update_kernel_preload_ab_timing.txt): one-block-per-workgroup launches 66.3 -> 67.8
+    // TFlop/s (N = 49152, K = 1024); the persistent bulk launches LOSE 3 % (66.9 -> 65.0; nb = 512: 61.2 -> 57.4 --
+    // the stores of block i and the C loads of block i+1 queue ahead of its first slabs), so the bulk instantiation
+    // keeps the old form.
     const bool unmasked = full && !(diag && m0 < n0 + ncols - 1);
     if (unmasked && ((p.ldc * (long) sizeof(T)) % 16 == 0) && (reinterpret_cast<uintptr_t>(C) % 16 == 0)) {
       typedef R r2 __attribute__((ext_vector_type(2)));
@@ -279,8 +236,7 @@ __device__ __forceinline__ void update_block(const UpdateArgs<T>& p, const Updat
             acc.re[2 * q + 1][j][v] = cv[1];
           }
         }
-      gemm_nt_block<Cfg, T, VEC, false, UTAIL, !ADD>(A, DLAF_LDA_X, mrows, B, DLAF_LDB_X, ncols, p.K, lds, acc, K1, A2,
-                                                     B2);
+      gemm_nt_block<Cfg, T, VEC, false, UTAIL, !ADD>(A, p.lda, mrows, B, ldb, ncols, p.K, lds, acc, K1, A2, B2);
 #pragma unroll
       for (int j = 0; j < Cfg::TN; ++j)
 #pragma unroll
@@ -294,49 +250,27 @@ __device__ __forceinline__ void update_block(const UpdateArgs<T>& p, const Updat
     }
   }
   acc.clear();
-  if constexpr (PART == 1) {
-    gemm_nt_block<Cfg, T, VEC, false, UTAIL>(A, DLAF_LDA_X, mrows, B, DLAF_LDB_X, ncols, p.K, lds, acc, K1, A2, B2,
-                                             s0);
-  }
-  else {
-    if (full)
-      gemm_nt_block<Cfg, T, VEC, false, UTAIL>(A, DLAF_LDA_X, mrows, B, DLAF_LDB_X, ncols, p.K, lds, acc, K1, A2, B2,
-                                               s0);
-    else
-      gemm_nt_block<Cfg, T, false, true>(A, p.lda, mrows, B, ldb, ncols, p.K, lds, acc, K1, A2, B2);
-  }
+  if (full)
+    gemm_nt_block<Cfg, T, VEC, false, UTAIL>(A, p.lda, mrows, B, ldb, ncols, p.K, lds, acc, K1, A2, B2, s0);
+  else
+    gemm_nt_block<Cfg, T, false, true>(A, p.lda, mrows, B, ldb, ncols, p.K, lds, acc, K1, A2, B2);
 
-#ifdef DLAF_DBG_SKIP_EPILOGUE
-  {
-    R sum = 0;  // keep every accumulator live; the comparison is never true on real data
-    for (int i = 0; i < Cfg::TM; ++i)
-      for (int j = 0; j < Cfg::TN; ++j)
-        for (int v = 0; v < 4; ++v)
-          sum += acc.re[i][j][v];
-    if (sum == R(12345.678))
-      C[0] = make_el<T>(sum, 0);
-    return;
-  }
-#endif
   // ---- epilogue: C -= acc (ADD: C += acc) --------------------------------------------------
   constexpr std::integral_constant<bool, ADD> add{};
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int wm = wave % Cfg::WAVES_M, wn = wave / Cfg::WAVES_M;
   const int g = lane >> 4, c = lane & 15;
-  const bool masked = PART == 1 ? false : (!full || (diag && m0 < n0 + ncols - 1));
+  const bool masked = !full || (diag && m0 < n0 + ncols - 1);
   if constexpr (Cfg::PAIRED) {
     // lane holds rows (m, m+1) of tiles (2q, 2q+1): 16-byte accesses when the tile column is aligned
     typedef R r2 __attribute__((ext_vector_type(2)));
-    const bool wide = PART == 1 ? true
-                                : (!masked && VEC && ((p.ldc * (long) sizeof(T)) % 16 == 0) &&
-                                   (reinterpret_cast<uintptr_t>(C) % 16 == 0));
-#ifndef DLAF_EPI_COLS
-#define DLAF_EPI_COLS 4  // A/B on one MI355X (tools/run_ab_epi.sh): 1 -> 4 columns per round trip +0.7 ... 1.2 % on the bulk launches
-#endif
+    const bool wide =
+        !masked && VEC && ((p.ldc * (long) sizeof(T)) % 16 == 0) && (reinterpret_cast<uintptr_t>(C) % 16 == 0);
     if (wide) {
-      // DLAF_EPI_COLS accumulator columns (a column = one (j, v) pair, TM/2 16-byte accesses per lane) are
-      // loaded together before any is subtracted and stored
-      constexpr int NB = DLAF_EPI_COLS;
+      // NB accumulator columns (a column = one (j, v) pair, TM/2 16-byte accesses per lane) are loaded together
+      // before any is subtracted and stored: 1 -> 4 columns per round trip is +0.7 ... 1.2 % on the bulk launches
+      // (profiles/r02_update_kernel_epilogue_batching_ab_timing.txt)
+      constexpr int NB = 4;
 #pragma unroll
       for (int i0 = 0; i0 < Cfg::TN * 4; i0 += NB) {
         r2 cv[NB][Cfg::TM / 2];
@@ -451,11 +385,7 @@ __global__ __launch_bounds__(UpdateCfg<T>::type::THREADS, UpdateCfg<T>::min_wave
   if (!mp.persist) {
     const long v = blockIdx.x;
     const long w = mp.xcd ? (v & 7) * (mp.total >> 3) + (v >> 3) : v;
-#ifdef DLAF_UPD_LEAN
-    update_block<T, VEC, false, (ROLE == 0 ? 1 : 0), ROLE == 4>(p, mp, w, lds);
-#else
-    update_block<T, VEC, false, 0, ROLE == 4>(p, mp, w, lds);
-#endif
+    update_block<T, VEC, false, ROLE == 4>(p, mp, w, lds);
     return;
   }
   // persistent: workgroups with the same id mod 8 (same XCD under round-robin dispatch) drain the
@@ -527,13 +457,8 @@ __global__ __launch_bounds__(UpdateCfg<T>::type::THREADS, UpdateCfg<T>::min_wave
     // (wave-uniform: everything derived from the work item -- operand and C addresses, segment selection, the
     // LDS ring -- then lives in scalar registers; left as a per-lane LDS value, the address of every in-loop load
     // costs a 64-bit multiply-add and a select per lane in the middle of the MFMA stream)
-#if DLAF_GLDS_SCALAR_ADDR
     const long i = (long) (unsigned) __builtin_amdgcn_readfirstlane((int) next_item);
     const int s0 = __builtin_amdgcn_readfirstlane(next_s0);
-#else
-    const long i = next_item;
-    const int s0 = next_s0;
-#endif
     __syncthreads();
     if (i >= per_q) {
       // own queue drained: help with the others (keeps the end of a launch balanced when the queues lost
@@ -553,11 +478,7 @@ __global__ __launch_bounds__(UpdateCfg<T>::type::THREADS, UpdateCfg<T>::min_wave
       }
       __syncthreads();
     }
-#ifdef DLAF_UPD_LEAN
-    update_block<T, VEC, ROLE == 0, (ROLE == 0 ? 1 : 0), ROLE == 4>(p, mp, (long) q * per_q + i, lds, s0);
-#else
-    update_block<T, VEC, ROLE == 0, 0, ROLE == 4>(p, mp, (long) q * per_q + i, lds, s0);
-#endif
+    update_block<T, VEC, ROLE == 0, ROLE == 4>(p, mp, (long) q * per_q + i, lds, s0);
     if (mp.lockstep && threadIdx.x == 0)
       __hip_atomic_fetch_add(&mp.counters[8 + q], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   }

@@ -7,10 +7,6 @@
 
 namespace dlaf_mi355x {
 
-#ifdef DLAF_DBG_STAMPS
-__device__ unsigned long long g_dbg_stamps[8];
-#endif
-
 // PAIRED_ (real types): MFMA tiles 2q and 2q+1 of a wave hold the even / odd rows of a 32-row group,
 // so one 16-byte LDS read feeds two fragments and the epilogue moves two consecutive rows per lane
 // (16-byte global accesses).  With it the LDS image is unpadded ([k][ROWS], column stride = 0 mod
@@ -82,7 +78,7 @@ struct NoHook {
 // hook(p) is called before each group of TM MFMAs (p = k4 * TN + j counts the groups of a slab): the
 // direct-to-LDS pipeline issues its loads of a later slab there, one at a time in the shadow of the MFMAs,
 // instead of as one block at the head of the iteration (8 x global_load_lds back to back keep the wave from
-// issuing MFMAs for ~1k cycles per slab; measured with in-kernel stamps, tools/update_bench.hip)
+// issuing MFMAs for ~1k cycles per slab; measured with in-kernel cycle stamps)
 // NEG: acc -= A B^H instead of += (the accumulators were preloaded with the block the product is subtracted from)
 template <class Cfg, bool NEG = false, class Hook = NoHook>
 __device__ __forceinline__ void mma_slab(const typename Cfg::R* __restrict__ As,
@@ -236,9 +232,6 @@ __device__ __forceinline__ void stage_glds(const T* __restrict__ A, long lda, co
 
 // The IDX-th of the LPS instructions stage_glds issues for this wave (real types), alone: lets the pipelined
 // loop spread them over the MFMA stream.
-#ifndef DLAF_GLDS_SCALAR_ADDR
-#define DLAF_GLDS_SCALAR_ADDR 1  // 0: the per-lane address arithmetic of rounds 1-2 (A/B, tools/run_ab_saddr.sh)
-#endif
 template <class Cfg, class T, int IDX>
 __device__ __forceinline__ void stage_glds_one(const T* __restrict__ A, long lda, const T* __restrict__ B, long ldb,
                                                int k0, typename Cfg::R* __restrict__ buf, int wave, int lane) {
@@ -250,27 +243,10 @@ __device__ __forceinline__ void stage_glds_one(const T* __restrict__ A, long lda
   // PER elements at e0 + l PER, i.e. row (e0 + l PER) % ROWS of column (e0 + l PER) / ROWS.  With ROWS | EPP or
   // EPP | ROWS the lane part is (l PER) % ROWS + ((l PER) / ROWS) ld and the uniform part (e0 % ROWS) + (k0 + e0 /
   // ROWS) ld.  Written per lane -- "(e % ROWS) + (k0 + e / ROWS) * ld" -- every load costs a 64-bit multiply-add
-  // per lane in the middle of the MFMA stream.
+  // per lane in the middle of the MFMA stream (A/B: profiles/r02_update_kernel_scalar_addressing_ab_timing.txt).
   auto at = [](const T* base, unsigned byte_off) {
     return reinterpret_cast<const T*>(reinterpret_cast<const char*>(base) + byte_off);
   };
-#if !DLAF_GLDS_SCALAR_ADDR
-  if constexpr (IDX < NA) {
-    const int e0 = (wave * NA + IDX) * EPP;
-    const int e = e0 + lane * PER;
-    const T* ga = A + (e % Cfg::BM) + (long) (k0 + e / Cfg::BM) * lda;
-    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*) ga,
-                                     (__attribute__((address_space(3))) void*) (buf + e0), 16, 0, 0);
-  }
-  else if constexpr (IDX < NA + NB) {
-    const int e0 = (wave * NB + (IDX - NA)) * EPP;
-    const int e = e0 + lane * PER;
-    const T* gb = B + (e % Cfg::BN) + (long) (k0 + e / Cfg::BN) * ldb;
-    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*) gb,
-                                     (__attribute__((address_space(3))) void*) (buf + Cfg::A_ELEMS + e0), 16, 0, 0);
-  }
-  return;
-#endif
   if constexpr (IDX < NA) {
     static_assert(EPP % Cfg::BM == 0 || Cfg::BM % EPP == 0, "pieces and columns nest");
     const int e0 = (wave * NA + IDX) * EPP;
@@ -308,11 +284,7 @@ __device__ __forceinline__ void gemm_nt_block(const T* __restrict__ A, long lda,
                                               const T* __restrict__ B2 = nullptr, int s0 = 0) {
   using R = typename Cfg::R;
   const int lane = threadIdx.x & 63;
-#if DLAF_GLDS_SCALAR_ADDR
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);  // wave-uniform: scalar address math
-#else
-  const int wave = threadIdx.x >> 6;
-#endif
   const int wm = wave % Cfg::WAVES_M, wn = wave / Cfg::WAVES_M;
   const int nk = (K + Cfg::BK - 1) / Cfg::BK;
   if (nk == 0)
@@ -341,31 +313,15 @@ __device__ __forceinline__ void gemm_nt_block(const T* __restrict__ A, long lda,
     else
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __builtin_amdgcn_s_barrier();
-#ifndef DLAF_GLDS_INTERLEAVE
-#define DLAF_GLDS_INTERLEAVE 1
-#endif
-#if DLAF_GLDS_INTERLEAVE
     int cur_i = 0, nxt_i = ST - 1;
-#ifdef DLAF_DBG_STAMPS
-    // tuning aid (tools/update_bench.hip): where a K-loop iteration spends its cycles, per wave
-    unsigned long long st_issue = 0, st_mma = 0, st_vm = 0, st_bar = 0;
-#endif
     // The loads of slab kt+ST-1 are issued INSIDE the MFMA stream of slab kt, one instruction per group of TM
     // MFMAs over the first groups of the slab, instead of as a block of LPS instructions at the head of the
-    // iteration.  Measured (tools/run_ab_interleave.sh, fp64): persistent launches 65.7 -> 67.0 TFlop/s at
-    // K = 1024, 66.2 -> 67.4 at K = 2048, 60.4 -> 61.5 at nb = 512.  The last ST-1 iterations load nothing.
+    // iteration.  Measured (profiles/r02_update_kernel_kloop_ab_timing.txt, fp64): persistent launches 65.7 -> 67.0
+    // TFlop/s at K = 1024, 66.2 -> 67.4 at K = 2048, 60.4 -> 61.5 at nb = 512.  The last ST-1 iterations load nothing.
     constexpr bool SPLIT = !Cfg::CXI && LPS <= (Cfg::BK / 4) * Cfg::TN && LPS <= 16;
     for (int kt = 0; kt < nk; ++kt) {
-#ifdef DLAF_DBG_STAMPS
-      const unsigned long long t0 = __builtin_amdgcn_s_memtime();
-#endif
       R* cur = lds + cur_i * Cfg::BUF_ELEMS;
-#ifdef DLAF_DBG_SKIP_GLOBAL
-      cur = lds;
-      const bool load = false;
-#else
       const bool load = UTAIL || (kt + ST - 1 < nk);
-#endif
       // (one copy of the MFMA stream: `load` only guards the single instructions, a scalar branch each)
       int sn = s0 + min(kt + ST - 1, nk - 1);
       sn = sn >= nk ? sn - nk : sn;
@@ -398,22 +354,8 @@ __device__ __forceinline__ void gemm_nt_block(const T* __restrict__ A, long lda,
         __builtin_amdgcn_s_waitcnt(0x0070 | ((LPS * (ST - 2)) & 0xF) | ((((LPS * (ST - 2)) >> 4) & 0x3) << 14));
       else
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-#ifdef DLAF_DBG_STAMPS
-      const unsigned long long t2 = __builtin_amdgcn_s_memtime();
-#endif
       asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-#ifdef DLAF_DBG_STAMPS
-      const unsigned long long t3 = __builtin_amdgcn_s_memtime();
-#endif
-#ifndef DLAF_DBG_NO_SLAB_BARRIER  // tuning aid (timing only, the results are garbage): what the slab barrier costs
       __builtin_amdgcn_s_barrier();
-#endif
-#ifdef DLAF_DBG_STAMPS
-      const unsigned long long t4 = __builtin_amdgcn_s_memtime();
-      st_mma += t2 - t0;
-      st_vm += t3 - t2;
-      st_bar += t4 - t3;
-#endif
       cur_i = (cur_i + 1 == ST) ? 0 : cur_i + 1;
       nxt_i = (nxt_i + 1 == ST) ? 0 : nxt_i + 1;
     }
@@ -423,40 +365,6 @@ __device__ __forceinline__ void gemm_nt_block(const T* __restrict__ A, long lda,
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
       __builtin_amdgcn_s_barrier();
     }
-#ifdef DLAF_DBG_STAMPS
-    if (lane == 0) {
-      atomicAdd(&g_dbg_stamps[0], st_issue);
-      atomicAdd(&g_dbg_stamps[1], st_mma);
-      atomicAdd(&g_dbg_stamps[2], st_vm);
-      atomicAdd(&g_dbg_stamps[3], st_bar);
-      atomicAdd(&g_dbg_stamps[4], 1ull);
-    }
-#endif
-#else
-    int cur_i = 0, nxt_i = ST - 1;
-    for (int kt = 0; kt < nk; ++kt) {
-      R* cur = lds + cur_i * Cfg::BUF_ELEMS;
-#ifdef DLAF_DBG_SKIP_GLOBAL
-      cur = lds;
-#else
-      if (kt + ST - 1 < nk) {
-        const int kn = (kt + ST - 1) * Cfg::BK;
-        stage_glds<Cfg, T>(kn < K1 ? A : A2, lda, kn < K1 ? B : B2, ldb, kn, lds + nxt_i * Cfg::BUF_ELEMS, wave, lane);
-      }
-#endif
-      mma_slab<Cfg, NEG>(cur, cur + Cfg::A_ELEMS, acc, wm, wn, lane);
-      // next slab (kt+1) landed?  loads still allowed in flight: those of slabs kt+2 .. kt+ST-1
-      const int younger = min(ST - 2, max(0, nk - 2 - kt));
-      if (younger == ST - 2)
-        __builtin_amdgcn_s_waitcnt(0x0070 | ((LPS * (ST - 2)) & 0xF) | ((((LPS * (ST - 2)) >> 4) & 0x3) << 14));
-      else
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-      __builtin_amdgcn_s_barrier();
-      cur_i = (cur_i + 1 == ST) ? 0 : cur_i + 1;
-      nxt_i = (nxt_i + 1 == ST) ? 0 : nxt_i + 1;
-    }
-#endif
     return;
   }
   Slab<T, Cfg::BM, Cfg::BK, VEC, Cfg::LDA, Cfg::CXI, Cfg::THREADS> sa;
@@ -470,12 +378,7 @@ __device__ __forceinline__ void gemm_nt_block(const T* __restrict__ A, long lda,
   for (int kt = 0; kt < nk; ++kt) {
     R* cur = lds + (kt & 1) * Cfg::BUF_ELEMS;
     R* nxt = lds + ((kt + 1) & 1) * Cfg::BUF_ELEMS;
-#ifdef DLAF_DBG_SKIP_GLOBAL
-    const bool more = false;  // tuning aid: reuse the first slab, no global traffic in the loop
-    cur = lds;
-#else
     const bool more = (kt + 1) < nk;
-#endif
     if (more) {
       const int kn = (kt + 1) * Cfg::BK;
       sa.template load<EDGE>(kn < K1 ? A : A2, lda, kn, mrows, K, A2, K1);

@@ -1,8 +1,7 @@
 // update_bench.hip -- standalone timing of the grouped trailing-update kernel on a synthetic
 // local matrix (one launch over all tiles below the first tile column), for kernel tuning.
 //   hipcc --offload-arch=gfx950 -O3 -std=c++17 -I include tools/update_bench.hip -o /tmp/update_bench
-//   /tmp/update_bench [nt=24] [nb=1024] [reps=3]
-// Debug variants (compile-time): -DDLAF_DBG_SKIP_EPILOGUE  -DDLAF_DBG_SKIP_GLOBAL
+//   /tmp/update_bench [nt=24] [nb=1024] [reps=3] [max_blocks=0]
 #include "../dla_future_amd/csrc/device/kernels_update.hip"
 
 #include <cstdio>
@@ -76,25 +75,5 @@ int main(int argc, char** argv) {
     (void) hipEventElapsedTime(&ms, e0, e1);
     printf("nt=%d nb=%d max_blocks=%ld: %.3f ms  %.2f TFlop/s\n", nt, nb, max_blocks, ms, flops / ms / 1e9);
   }
-#ifdef DLAF_DBG_STAMPS
-  {
-    unsigned long long z[8] = {0}, h[8];
-    (void) hipMemcpyToSymbol(HIP_SYMBOL(g_dbg_stamps), z, sizeof(z));
-    hipEvent_t a0, a1;
-    (void) hipEventCreate(&a0);
-    (void) hipEventCreate(&a1);
-    (void) hipEventRecord(a0);
-    launch_update(ua, nullptr, 0, max_blocks, ctr);
-    (void) hipEventRecord(a1);
-    (void) hipDeviceSynchronize();
-    float ms;
-    (void) hipEventElapsedTime(&ms, a0, a1);
-    (void) hipMemcpyFromSymbol(h, HIP_SYMBOL(g_dbg_stamps), sizeof(h));
-    const double tot = (double) (h[0] + h[1] + h[2] + h[3]);
-    printf("stamps (instrumented run %.3f ms): wave-blocks %llu; per K-loop share: issue glds %.1f %%, ds_read+mfma %.1f %%, "
-           "vmcnt/lgkm wait %.1f %%, barrier %.1f %%; mean cycles per wave-block %.0f\n",
-           ms, h[4], 100.0 * h[0] / tot, 100.0 * h[1] / tot, 100.0 * h[2] / tot, 100.0 * h[3] / tot, tot / (double) h[4]);
-  }
-#endif
   return 0;
 }

@@ -1,6 +1,7 @@
 // cholesky.cpp -- the issue side of the tile Cholesky: which kernels, broadcasts and events one factorization
 // enqueues on the three streams of a DeviceMatrix, in one of four orders.  See runtime.hpp for the matrix and the
 // transports, runtime.cpp for wait() and the blocking entry points.
+#include "launch_args.hpp"
 #include "runtime.hpp"
 
 #include <algorithm>
@@ -255,7 +256,6 @@ struct CholeskyIssue {
   Transport* tr;
   const bool dist;
   const size_t tile_bytes;
-  const int last_rows;
   // uplo == 'U' runs on the transposed view: its process rows are the caller's process columns
   const CommAxis ax_row, ax_col;
   const hipStream_t s_main, s_panel, s_comm;
@@ -270,7 +270,7 @@ struct CholeskyIssue {
 
   explicit CholeskyIssue(DeviceMatrix<T>& mat)
       : m(mat), tr(grid_transport(*mat.grid)), dist(mat.grid->nranks > 1), tile_bytes(mat.tile_elems * sizeof(T)),
-        last_rows(mat.rows.last_extent()), ax_row(mat.transposed ? CommAxis::Col : CommAxis::Row),
+        ax_row(mat.transposed ? CommAxis::Col : CommAxis::Row),
         ax_col(mat.transposed ? CommAxis::Row : CommAxis::Col), s_main(mat.s_low), s_panel(mat.s_high),
         s_comm(mat.s_comm) {
     if (dist && !tr)
@@ -332,16 +332,8 @@ struct CholeskyIssue {
     const long il1 = il_to < 0 ? m.ltr : std::min(il_to, m.ltr);
     if (il0 >= il1)
       return;
-    UpdateArgs<T> ua;
-    ua.c = m.tiles;
-    ua.c_tsr = (long) m.tile_elems;
-    ua.c_tsc = (long) (m.tile_elems * m.ltr);
-    ua.ldc = m.nb;
-    ua.a = st.a_base + (size_t) (il0 - st.il_n) * m.tile_elems;
-    ua.a_ts = (long) m.tile_elems;
-    ua.lda = m.nb;
-    ua.b = st.b_base;
-    ua.b_ts = st.b_ts;
+    UpdateArgs<T> ua = update_args(m, il0, il1, j0, j1, st.a_base + (size_t) (il0 - st.il_n) * m.tile_elems, st.b_base,
+                                   st.b_ts, st.kb, m.info);
     ua.b_period = st.b_period;
     ua.b_ts2 = st.b_ts2;
     ua.b_jl0 = (int) st.jl_n;
@@ -350,20 +342,6 @@ struct CholeskyIssue {
       ua.a2 = st.a2_base + (size_t) (il0 - st.il_n) * m.tile_elems;
       ua.b2 = st.b2_base;
     }
-    ua.ldb = m.nb;
-    ua.il0 = (int) il0;
-    ua.il1 = (int) il1;
-    ua.jl0 = (int) j0;
-    ua.jl1 = (int) j1;
-    ua.nb = m.nb;
-    ua.K = st.kb;
-    ua.pr = m.rows.P;
-    ua.ri = m.rows.shift();
-    ua.pc = m.cols.P;
-    ua.ci = m.cols.shift();
-    ua.nt = (int) m.nt;
-    ua.last_rows = last_rows;
-    ua.info = m.info;
     double fl, by;
     update_work(il0, il1, j0, j1, st.kb, fl, by);
     const int pk = kind < 0 ? role : kind;
@@ -402,21 +380,8 @@ struct CholeskyIssue {
       ts = s_main;
     if (il0 >= il1)
       return;
-    TrsmArgs<T> ta;
-    ta.b = m.tile(il0, klc);
-    ta.b_ts = (long) m.tile_elems;
-    ta.ldb = m.nb;
-    ta.il0 = (int) il0;
-    ta.il1 = (int) il1;
-    ta.pr = m.rows.P;
-    ta.ri = m.rows.shift();
-    ta.nb = m.nb;
-    ta.nt = (int) m.nt;
-    ta.last_rows = last_rows;
-    ta.l = Lkk;
-    ta.ldl = m.nb;
+    TrsmArgs<T> ta = panel_args<TrsmArgs<T>>(m, il0, il1, klc, Lkk, kb);
     ta.winv = Wkk;
-    ta.n = kb;
     ta.info = m.info;
     // on the side stream the solve runs beside the bulk update and every later step waits for it
     ta.prio = (ts != s_main) ? 1 : 0;

@@ -73,8 +73,8 @@ void multiply_canonical(TileMatrix<T>& Td, TileMatrix<T>& Bd, bool upper, bool u
     j1 = std::min(j1, o.jl1);
     if (j0 >= j1 || Bd.ltr == 0)
       return;
-    launch_update(rect_update_args(Bd, tf.step_k(s), xp[(size_t) s], o.base + (j0 - o.jl0) * o.ts, o.ts, j0, j1,
-                                   sw.info.p),
+    launch_update(rect_update_args(Bd, 0, Bd.ltr, j0, j1, xp[(size_t) s], o.base + (j0 - o.jl0) * o.ts, o.ts,
+                                   Bd.cols.tile_extent(tf.step_k(s)), sw.info.p),
                   s_main, 4);
   };
 
@@ -107,7 +107,7 @@ void multiply_canonical(TileMatrix<T>& Td, TileMatrix<T>& Bd, bool upper, bool u
     // column k: B(:,k) = P_k T_kk^H once every read of P_k (the update above, the broadcast) is done
     DLAF_HIP_CHECK(hipStreamWaitEvent(s_side, ev_u[(size_t) s], 0));
     if (Bd.cols.mine(k) && Bd.ltr > 0) {
-      auto ta = column_panel_args<TrmmArgs<T>>(Bd, k, tf.top[(size_t) s].diag);
+      auto ta = panel_args<TrmmArgs<T>>(Bd, 0, Bd.ltr, Bd.cols.local_of(k), tf.top[(size_t) s].diag, Bd.cols.tile_extent(k));
       ta.upper = upper ? 1 : 0;
       ta.unit = unit ? 1 : 0;
       launch_trmm(ta, s_side);

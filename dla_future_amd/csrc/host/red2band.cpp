@@ -31,6 +31,7 @@
 #include <vector>
 
 #include "../device/band_api.hpp"
+#include "launch_args.hpp"
 #include "red2band.hpp"
 #include "runtime.hpp"
 #include "tile_matrix.hpp"
@@ -485,34 +486,15 @@ struct Red2BandIssue : PanelSteps<T> {
     if (P.il0 >= A.ltr || ja >= jb)
       return;
     const int nb = A.nb;
-    UpdateArgs<T> ua;
-    ua.c = A.tiles;
-    ua.c_tsr = (long) A.tile_elems;
-    ua.c_tsc = (long) (A.tile_elems * A.ltr);
-    ua.ldc = nb;
-    ua.a = X(P) + (rows.global_of(P.il0) * nb - P.e0);
+    // the operands are row ranges of the column-major panels X and V (ld ldp), not tiles
+    UpdateArgs<T> ua = update_args(A, P.il0, A.ltr, ja, jb, X(P) + (rows.global_of(P.il0) * nb - P.e0),
+                                   V(P) + (cols.global_of(ja) * nb - P.e0), (long) cols.P * nb, 2 * b, A.info);
     ua.a2 = V(P) + (rows.global_of(P.il0) * nb - P.e0);
-    ua.a_ts = (long) rows.P * nb;
-    ua.lda = (int) ldp;
-    ua.b = V(P) + (cols.global_of(ja) * nb - P.e0);
     ua.b2 = X(P) + (cols.global_of(ja) * nb - P.e0);
-    ua.b_ts = (long) cols.P * nb;
-    ua.ldb = (int) ldp;
-    ua.il0 = (int) P.il0;
-    ua.il1 = (int) A.ltr;
-    ua.jl0 = (int) ja;
-    ua.jl1 = (int) jb;
-    ua.nb = nb;
+    ua.a_ts = (long) rows.P * nb;
+    ua.lda = ua.ldb = (int) ldp;
     ua.K1 = b;
-    ua.K = 2 * b;
     ua.her2k = 1;
-    ua.pr = rows.P;
-    ua.ri = rows.shift();
-    ua.pc = cols.P;
-    ua.ci = cols.shift();
-    ua.nt = (int) A.nt;
-    ua.last_rows = rows.last_extent();
-    ua.info = A.info;
     launch_update(ua, st, 3);
   }
 
@@ -628,7 +610,6 @@ int bt_reduction_to_band_device(int band, TileMatrix<T>& C, DeviceMatrix<T>& A, 
   const Axis& ccols = C.cols;
   const long n = A.n, nt = A.nt;
   const int nb = A.nb, b = band;
-  const size_t te = A.tile_elems;
   hipStream_t s = A.s_high;
   int* info = A.info;
   DLAF_HIP_CHECK(hipMemsetAsync(info, 0, sizeof(int), s));
@@ -716,33 +697,12 @@ int bt_reduction_to_band_device(int band, TileMatrix<T>& C, DeviceMatrix<T>& A, 
         tr->allreduce_sum(W2H, (size_t) ldw2 * nrefl, TypeInfo<T>::tag, 'C', s);
       // C -= V W2 = V (W2^H)^H
       if (il0 < cltr) {
-        UpdateArgs<T> ua;
-        ua.c = C.tiles;
-        ua.c_tsr = (long) te;
-        ua.c_tsc = (long) (te * cltr);
-        ua.ldc = nb;
-        ua.a = V + (rows.global_of(il0) * nb - e0);
+        // (C's rows are spread like A's; V is a row range of the column-major panel, W2^H one nb-row block per column)
+        UpdateArgs<T> ua = rect_update_args(C, il0, cltr, 0, cltc, V + (rows.global_of(il0) * nb - e0), W2H, (long) nb,
+                                            nrefl, info);
         ua.a_ts = (long) rows.P * nb;
         ua.lda = (int) ldp;
-        ua.b = W2H;
-        ua.b_ts = (long) nb;
         ua.ldb = (int) ldw2;
-        ua.il0 = (int) il0;
-        ua.il1 = (int) cltr;
-        ua.jl0 = 0;
-        ua.jl1 = (int) cltc;
-        ua.nb = nb;
-        ua.K = nrefl;
-        ua.pr = rows.P;
-        ua.ri = rows.shift();
-        ua.pc = ccols.P;
-        ua.ci = ccols.shift();
-        ua.nt = (int) nt;
-        ua.last_rows = rows.last_extent();
-        ua.info = info;
-        ua.rect = 1;
-        ua.nt_c = (int) ccols.nt();
-        ua.last_cols = ccols.last_extent();
         launch_update(ua, s, 3);
       }
     }

@@ -2,6 +2,7 @@
 // order of a factorization is in cholesky.cpp.
 // See runtime.hpp for what each piece replaces in the reference.
 #include "runtime.hpp"
+#include "launch_args.hpp"
 #include "tile_matrix.hpp"
 
 #include <cstdarg>
@@ -351,21 +352,18 @@ Transport* grid_transport(Grid& g) {
   return g.transport.get();
 }
 
-// =============================================================================== DeviceMatrix
-template <class T>
-static T* dev_alloc(size_t elems) {
-  T* p = nullptr;
-  if (elems == 0)
-    elems = 1;
-  if (hipMalloc(reinterpret_cast<void**>(&p), elems * sizeof(T)) != hipSuccess) {
-    // the workspace pool of the eigensolver stages may be holding what this allocation needs
-    (void) hipGetLastError();
-    pool_release();
-    DLAF_HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&p), elems * sizeof(T)));
+int agree_on_info(Grid& g, int info) {
+  if (g.nranks > 1 && g.transport) {
+    // v[0] carries the LAPACK index (MAX of 2^31 - info = MIN of info), v[1] the scheduling failure
+    constexpr double kTop = 2147483648.0;
+    double v[2] = {info > 0 ? kTop - (double) info : 0.0, info == kInfoSchedulingFailure ? 1.0 : 0.0};
+    g.transport->allreduce_max(v, 2, g.nprow, g.npcol, g.myrow, g.mycol);
+    info = v[1] > 0 ? kInfoSchedulingFailure : (v[0] > 0 ? (int) (kTop - v[0]) : 0);
   }
-  return p;
+  return info;
 }
 
+// =============================================================================== DeviceMatrix
 static std::vector<hipEvent_t> make_events(size_t n) {
   std::vector<hipEvent_t> v(n);
   for (auto& e : v)
@@ -787,33 +785,11 @@ void DeviceMatrix<T>::residual_of(DeviceMatrix<T>& L, double* max_diff, double* 
     const long il0 = std::max(il_f, rows.next_local(cols.global_of(jl_f)));
     if (il0 >= ltr)
       continue;
-    UpdateArgs<T> ua;
-    ua.c = tiles;
-    ua.c_tsr = (long) tile_elems;
-    ua.c_tsc = (long) (tile_elems * ltr);
-    ua.ldc = nb;
-    ua.a = a_base + (size_t) (il0 - il_f) * tile_elems;
-    ua.a_ts = (long) tile_elems;
-    ua.lda = nb;
-    ua.b = b_base;
-    ua.b_ts = b_ts;
+    UpdateArgs<T> ua = update_args(*this, il0, ltr, jl_f, ltc, a_base + (size_t) (il0 - il_f) * tile_elems, b_base, b_ts,
+                                   kb, info);
     ua.b_period = b_period;
     ua.b_ts2 = b_ts2;
     ua.b_jl0 = (int) jl_f;
-    ua.ldb = nb;
-    ua.il0 = (int) il0;
-    ua.il1 = (int) ltr;
-    ua.jl0 = (int) jl_f;
-    ua.jl1 = (int) ltc;
-    ua.nb = nb;
-    ua.K = kb;
-    ua.pr = rows.P;
-    ua.ri = rows.shift();
-    ua.pc = cols.P;
-    ua.ci = cols.shift();
-    ua.nt = (int) nt;
-    ua.last_rows = rows.last_extent();
-    ua.info = info;
     launch_update(ua, s, 3);
     if (dist)
       DLAF_HIP_CHECK(hipStreamSynchronize(s));  // the single panel workspace is reused by the next step
@@ -848,16 +824,9 @@ int DeviceMatrix<T>::wait() {
   if (info_verbose)
     std::fprintf(stderr, "[dlaf_mi355x] rank (%d,%d) of %dx%d: local info %d (n %ld nb %d)\n", grid->myrow, grid->mycol,
                  grid->nprow, grid->npcol, *info_host, n, nb);
-  if (grid->nranks > 1 && grid->transport) {
-      // one value for the whole grid (ScaLAPACK's p?potrf contract; the reference aborts every rank,
-    // src/cusolver/assert_info.cu:35-45): v[0] carries the LAPACK index, v[1] the scheduling failure
-    // (the SMALLEST positive index wins: ranks that did not see the failing tile keep computing on the
-    // garbage it broadcast and may flag a later pivot of their own; MAX of 2^31 - info = MIN of info)
-    constexpr double kTop = 2147483648.0;
-    double v[2] = {*info_host > 0 ? kTop - (double) *info_host : 0.0, *info_host == kInfoSchedulingFailure ? 1.0 : 0.0};
-    grid->transport->allreduce_max(v, 2, grid->nprow, grid->npcol, grid->myrow, grid->mycol);
-    *info_host = v[1] > 0 ? kInfoSchedulingFailure : (v[0] > 0 ? (int) (kTop - v[0]) : 0);
-  }
+  // one value for the whole grid (ScaLAPACK's p?potrf contract; the reference aborts every rank,
+  // src/cusolver/assert_info.cu:35-45)
+  *info_host = agree_on_info(*grid, *info_host);
   if (*info_host == kInfoSchedulingFailure)
     fatal("[dlaf_mi355x] cooperative POTRF: a bounded inter-workgroup wait expired (workgroups not co-resident); "
           "the result is invalid. DLAF_MI355X_POTRF=chain selects the non-cooperative path.\n");
@@ -912,21 +881,10 @@ double DeviceMatrix<T>::trsm_profile(int reps, double* flops, double* bytes) {
   hipStream_t s = s_low;
   DLAF_HIP_CHECK(hipMemsetAsync(info, 0, sizeof(int), s));
   launch_invert_diag_blocks(tile(0, 0), nb, nb, w, info, s, false, false);
-  TrsmArgs<T> ta;
+  // the panel of step 0 (one process: local row il is global tile il), solved on the copy
+  TrsmArgs<T> ta = panel_args<TrsmArgs<T>>(*this, 1, ltr, 0, tile(0, 0), nb);
   ta.b = scratch;
-  ta.b_ts = (long) tile_elems;
-  ta.ldb = nb;
-  ta.il0 = 1;
-  ta.il1 = (int) ltr;
-  ta.pr = 1;
-  ta.ri = 0;
-  ta.nb = nb;
-  ta.nt = (int) nt;
-  ta.last_rows = rows.last_extent();
-  ta.l = tile(0, 0);
-  ta.ldl = nb;
   ta.winv = w;
-  ta.n = nb;
   ta.info = info;
   hipEvent_t e0, e1;
   DLAF_HIP_CHECK(hipEventCreate(&e0));

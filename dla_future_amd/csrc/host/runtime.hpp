@@ -40,6 +40,21 @@ hipError_t pool_free(void* p);
 void pool_release();
 size_t pool_idle_bytes();
 
+// hipMalloc of `elems` elements (at least one); an allocation that fails releases the workspace pool -- it may be
+// holding what this allocation needs -- and is tried once more before it is fatal
+template <class T>
+T* dev_alloc(size_t elems) {
+  T* p = nullptr;
+  if (elems == 0)
+    elems = 1;
+  if (hipMalloc(reinterpret_cast<void**>(&p), elems * sizeof(T)) != hipSuccess) {
+    (void) hipGetLastError();
+    pool_release();
+    DLAF_HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&p), elems * sizeof(T)));
+  }
+  return p;
+}
+
 // ------------------------------------------------------------------------------------------------
 // Transport: the broadcast primitive along a process row / column (communication/kernels/
 // internal/broadcast.h:36-119 in the reference: MPI_Ibcast).  Two implementations:
@@ -116,6 +131,10 @@ void rccl_get_unique_id(void* out128);
 // creates the lazily-built host transport of a grid and, when the grid's communication log is on, wraps the
 // transport with the recorder; idempotent.  Returns the transport (null for a 1x1 grid without communicators).
 Transport* grid_transport(Grid& g);
+// One status word for the whole grid from every rank's own (collective; a one-process grid returns `info`): the
+// SMALLEST positive LAPACK index wins -- ranks that did not see the failing tile keep computing on the garbage it
+// broadcast and may flag a later pivot of their own --, and the scheduling-failure code wins over everything.
+int agree_on_info(Grid& g, int info);
 std::unique_ptr<Transport> make_host_transport(dlaf_host_bcast_fn bcast, dlaf_host_barrier_fn barrier,
                                                void* user);
 // host-driven peer copies (hipIpc mappings + interprocess events), control messages over the host callbacks

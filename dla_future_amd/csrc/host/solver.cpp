@@ -94,7 +94,9 @@ void solve_canonical(TileMatrix<T>& Td, TileMatrix<T>& Bd, bool upper, bool unit
     j1 = std::min(j1, o.jl1);
     if (j0 >= j1 || Bd.ltr == 0)
       return;
-    launch_update(rect_update_args(Bd, tf.step_k(s), xp, o.base + (j0 - o.jl0) * o.ts, o.ts, j0, j1, info), s_main, 3);
+    launch_update(rect_update_args(Bd, 0, Bd.ltr, j0, j1, xp, o.base + (j0 - o.jl0) * o.ts, o.ts,
+                                   Bd.cols.tile_extent(tf.step_k(s)), info),
+                  s_main, 3);
   };
 
   sw.begin(false);  // (the preparation stays outside the window; s_comm waits for ev_prep)
@@ -112,7 +114,7 @@ void solve_canonical(TileMatrix<T>& Td, TileMatrix<T>& Bd, bool upper, bool unit
 
     // column k of Bd: X(:,k) = B(:,k) T_kk^-H
     if (Bd.cols.mine(k) && Bd.ltr > 0) {
-      auto ta = column_panel_args<TrsmArgs<T>>(Bd, k, tf.top[(size_t) s].diag);
+      auto ta = panel_args<TrsmArgs<T>>(Bd, 0, Bd.ltr, Bd.cols.local_of(k), tf.top[(size_t) s].diag, Bd.cols.tile_extent(k));
       ta.winv = tf.top[(size_t) s].winv;
       ta.info = info;
       ta.upper = upper ? 1 : 0;

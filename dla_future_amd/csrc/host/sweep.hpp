@@ -5,12 +5,13 @@
 //   Events, Ring       one event per step; kBuf device buffers, step s uses s % kBuf
 //   TOperandFetch      the operands taken from the triangular / Hermitian matrix, one step ahead (below)
 //   bcast_view_column  tile column k of a view to the other members of the view's row communicator
-//   rect_update_args, column_panel_args   the launch arguments over every local row of Bd
+//   launch_args.hpp    rect_update_args / panel_args over every local row of Bd: the launch arguments of a step
 //   operand_map        side / uplo / op / diag -> T and B_dev (the table in solver.cpp's header)
 #pragma once
 #include <algorithm>
 #include <vector>
 
+#include "launch_args.hpp"
 #include "runtime.hpp"
 #include "tile_matrix.hpp"
 
@@ -285,62 +286,6 @@ const T* bcast_view_column(Transport* tr, const TileMatrix<T>& V, long k, T* els
     tr->bcast(V.transposed ? CommAxis::Col : CommAxis::Row, V.cols.owner(k), V.cols.rank, p, p,
               (size_t) V.ltr * V.tile_elems * sizeof(T), s_comm);
   return p;
-}
-
-// B(:, j) -= / += A T(j,k)^H over every local row of Bd, local columns [j0, j1): the rectangular form of the grouped
-// NT update, `a` one tile per local row, T(j,k) of local column j at b + (j - j0) * b_ts
-template <class T>
-UpdateArgs<T> rect_update_args(const TileMatrix<T>& Bd, long k, const T* a, const T* b, long b_ts, long j0, long j1,
-                               const int* info) {
-  UpdateArgs<T> ua;
-  ua.c = Bd.tiles;
-  ua.c_tsr = (long) Bd.tile_elems;
-  ua.c_tsc = (long) (Bd.tile_elems * Bd.ltr);
-  ua.ldc = Bd.nb;
-  ua.a = a;
-  ua.a_ts = (long) Bd.tile_elems;
-  ua.lda = Bd.nb;
-  ua.b = b;
-  ua.b_ts = b_ts;
-  ua.ldb = Bd.nb;
-  ua.il0 = 0;
-  ua.il1 = (int) Bd.ltr;
-  ua.jl0 = (int) j0;
-  ua.jl1 = (int) j1;
-  ua.nb = Bd.nb;
-  ua.K = Bd.cols.tile_extent(k);
-  ua.pr = Bd.rows.P;
-  ua.ri = Bd.rows.shift();
-  ua.pc = Bd.cols.P;
-  ua.ci = Bd.cols.shift();
-  ua.nt = (int) Bd.rows.nt();
-  ua.last_rows = Bd.rows.last_extent();
-  ua.rect = 1;
-  ua.nt_c = (int) Bd.cols.nt();
-  ua.last_cols = Bd.cols.last_extent();
-  ua.info = info;
-  return ua;
-}
-
-// The row geometry TrsmArgs and TrmmArgs share: every local row of column k of Bd (which this process holds) against
-// the diagonal tile l
-template <class Args, class T>
-Args column_panel_args(const TileMatrix<T>& Bd, long k, const T* l) {
-  Args ta;
-  ta.b = Bd.tile(0, Bd.cols.local_of(k));
-  ta.b_ts = (long) Bd.tile_elems;
-  ta.ldb = Bd.nb;
-  ta.il0 = 0;
-  ta.il1 = (int) Bd.ltr;
-  ta.pr = Bd.rows.P;
-  ta.ri = Bd.rows.shift();
-  ta.nb = Bd.nb;
-  ta.nt = (int) Bd.rows.nt();
-  ta.last_rows = Bd.rows.last_extent();
-  ta.l = l;
-  ta.ldl = Bd.nb;
-  ta.n = Bd.cols.tile_extent(k);
-  return ta;
 }
 
 // ---- drivers ----------------------------------------------------------------------------------------------

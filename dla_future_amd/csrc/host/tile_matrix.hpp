@@ -6,19 +6,6 @@
 
 namespace dlaf_mi355x {
 
-template <class T>
-inline T* tm_dev_alloc(size_t elems) {
-  T* p = nullptr;
-  if (elems == 0)
-    elems = 1;
-  if (hipMalloc(reinterpret_cast<void**>(&p), elems * sizeof(T)) != hipSuccess) {
-    (void) hipGetLastError();
-    pool_release();  // (the workspace pool of the eigensolver stages may be holding what this allocation needs)
-    DLAF_HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&p), elems * sizeof(T)));
-  }
-  return p;
-}
-
 // a device allocation that lives as long as its scope (empty until alloc())
 template <class T>
 struct DevBuf {
@@ -28,7 +15,7 @@ struct DevBuf {
   DevBuf(const DevBuf&) = delete;
   DevBuf& operator=(const DevBuf&) = delete;
   ~DevBuf() { (void) hipFree(p); }
-  void alloc(size_t elems) { p = tm_dev_alloc<T>(elems); }
+  void alloc(size_t elems) { p = dev_alloc<T>(elems); }
 };
 
 // General block-cyclic matrix in device tile layout (nb x nb tiles, tile (il,jl) at (il + jl*ltr) nb^2).
@@ -64,7 +51,7 @@ struct TileMatrix {
     ltc = cols.local_tiles();
     tile_elems = (size_t) nb * nb;
     owns = borrow == nullptr;
-    tiles = owns ? tm_dev_alloc<T>((size_t) ltr * ltc * tile_elems) : borrow;
+    tiles = owns ? dev_alloc<T>((size_t) ltr * ltc * tile_elems) : borrow;
     row_P = rows.P;
     row_rank = rows.rank;
     rows_global = rows.n;
@@ -91,7 +78,7 @@ struct TileMatrix {
     ltc = cols.local_tiles();
     tile_elems = (size_t) nb * nb;
     owns = true;
-    tiles = tm_dev_alloc<T>((size_t) ltr * ltc * tile_elems);
+    tiles = dev_alloc<T>((size_t) ltr * ltc * tile_elems);
   }
   ~TileMatrix() {
     if (tiles && owns)
@@ -134,7 +121,7 @@ struct TileMatrix {
     if (srows == 0 || scols == 0)
       return;
     if (!staging)
-      staging = tm_dev_alloc<T>((size_t) srows * scols);
+      staging = dev_alloc<T>((size_t) srows * scols);
     DLAF_HIP_CHECK(hipMemcpy2DAsync(staging, (size_t) srows * sizeof(T), host, (size_t) ld * sizeof(T),
                                     (size_t) srows * sizeof(T), (size_t) scols, hipMemcpyHostToDevice, s));
     LayoutArgs<T> a = layout(staging, srows);
@@ -149,7 +136,7 @@ struct TileMatrix {
     if (srows == 0 || scols == 0)
       return;
     if (!staging)
-      staging = tm_dev_alloc<T>((size_t) srows * scols);
+      staging = dev_alloc<T>((size_t) srows * scols);
     LayoutArgs<T> a = layout(staging, srows);
     a.conj = conj ? 1 : 0;
     launch_from_tiles(a, s);

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- fp64 tiled Cholesky TFlop/s on N MI355X (BASELINE.json metric).
 
-    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 A step is ONE factorization of the synthetic SPD matrix (set_random_hermitian_positive_definite,
@@ -10,6 +10,10 @@ timed region starts -- the window of the reference's miniapp (miniapp/miniapp_ch
 Default workload: the configuration the metric is quoted on, d N=65536 nb=1024 uplo=L, which fits one
 GPU (32 GiB); grids 1x1, 1x2, 2x2, 2x4 (column-major rank order like the miniapp, :113).
 Flop model: N^3/3 (miniapp_cholesky.cpp:157-162).  Prints ONE JSON line on rank 0.
+
+A plain run does what the metric needs and no more: set-up, warm-up, the timed steps, --dump-outputs, the line (with the
+per-kernel figures that the timed steps' own HIP events give).  --full adds everything that takes device or host runs
+of its own (EXTRAS below) as further objects of the same line; the --no-* options take single ones out of a --full run.
 """
 import argparse
 import json
@@ -40,16 +44,19 @@ def parse():
     p.add_argument("--block-size", "--nb", dest="nb", type=int, default=1024)
     p.add_argument("--type", default="d", choices=["s", "d", "c", "z"])
     p.add_argument("--uplo", default="L", choices=["L", "U"])
-    p.add_argument("--no-cpu-baseline", action="store_true")
+    p.add_argument("--full", action="store_true",
+                   help="after the timed steps, also run what the metric does not need (one GPU: the device-side residual "
+                        "check, the panel TRSM alone, the eigensolver and reduction_to_band lines, the CPU baseline)")
+    p.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
     p.add_argument("--cpu-n", type=int, default=16384)
     p.add_argument("--cpu-nb", type=int, default=512)
-    p.add_argument("--check", action="store_true", help="check_cholesky of the miniapp on the device after the timed runs (any size, any grid)")
-    p.add_argument("--no-check", action="store_true", help="skip the (untimed) device-side residual check at N = 1")
-    p.add_argument("--no-trsm-profile", action="store_true", help="skip the stand-alone panel-TRSM timing (PMC passes: only the factorization's own launches are counted)")
+    p.add_argument("--check", action="store_true", help="check_cholesky of the miniapp on the device after the timed runs (any size, any grid; part of --full on one GPU)")
+    p.add_argument("--no-check", action="store_true", help="--full without the (untimed) device-side residual check at N = 1")
+    p.add_argument("--no-trsm-profile", action="store_true", help="--full without the stand-alone panel-TRSM timing")
     p.add_argument("--no-red2band", action="store_true",
-                   help="skip the extra (untimed-for-the-metric) reduction_to_band line at N = 1")
+                   help="--full without the extra (untimed-for-the-metric) reduction_to_band line at N = 1")
     p.add_argument("--no-eigensolver", action="store_true",
-                   help="skip the extra (untimed-for-the-metric) whole-eigensolver line at N = 1")
+                   help="--full without the extra (untimed-for-the-metric) whole-eigensolver line at N = 1")
     p.add_argument("--r2b-n", type=int, default=20480)
     p.add_argument("--r2b-nb", type=int, default=512)
     p.add_argument("--transport", default="rccl", choices=["rccl", "host", "peer"],
@@ -62,6 +69,31 @@ def parse():
     if args.steps < 1 or args.warmup < 0:
         p.error("--steps must be >= 1 and --warmup >= 0")
     return args
+
+
+EXTRAS = ("residual", "trsm_alone", "eigensolver", "reduction_to_band", "cpu_baseline")
+
+
+def extras(args, world, full=None):
+    """What this run does beside the metric, as a subset of EXTRAS.  All of it sits behind --full, on one GPU (the
+    --no-* options take single items out); --check alone asks for the residual on any grid.  `full` overrides
+    args.full: what the run would do with / without --full."""
+    on = set()
+    if (args.full if full is None else full) and world == 1:
+        on = set(EXTRAS)
+        if args.no_check:
+            on.discard("residual")
+        if args.no_trsm_profile or args.nb * 2 > args.n:
+            on.discard("trsm_alone")
+        if args.no_red2band or args.type != "d":   # the eigensolver line runs beside the reduction_to_band line only
+            on -= {"eigensolver", "reduction_to_band"}
+        if args.no_eigensolver:
+            on.discard("eigensolver")
+        if args.no_cpu_baseline:
+            on.discard("cpu_baseline")
+    if args.check:
+        on.add("residual")
+    return on
 
 
 def cpu_baseline(args):
@@ -277,11 +309,12 @@ def main():
     a = np.zeros((max(1, lrows), max(1, lcols)), dtype=dt, order="F")[:lrows, :lcols]
     dlaf.set_random_hermitian_positive_definite(grid, a, n, nb)
     t_gen = time.perf_counter() - t_gen
+    todo = extras(args, world)
     # The two matrices of the reduction_to_band line are allocated FIRST: device memory handed out after the release of
     # the factorization's 137 GB is slower on this stack -- the same stage 407 ms on matrices allocated behind that release,
     # 344 ms on matrices allocated before it or in a fresh process (tools/diag_r2b_after_alloc.py)
     r2b_mats = None
-    if world == 1 and not args.no_red2band and args.type == "d":
+    if "reduction_to_band" in todo:
         r2b_mats = (dlaf.DeviceMatrix(grid, np.float64, "L", args.r2b_n, args.r2b_nb),
                     dlaf.DeviceMatrix(grid, np.float64, "L", args.r2b_n, args.r2b_nb))
     ref = dlaf.DeviceMatrix(grid, dt, args.uplo, n, nb)
@@ -294,6 +327,10 @@ def main():
     # pristine copy outside the timer (the miniapp takes a fresh copy of the input outside its timer, :133-141)
     local_bytes = lrows * lcols * np.dtype(dt).itemsize
     free_b, _total = torch.cuda.mem_get_info()
+    if r2b_mats is None and "reduction_to_band" in extras(args, world, full=True):
+        # a plain run times on as many work copies as the same run with --full: the memory which that one gives to
+        # the two matrices of the reduction_to_band line is left out of the count here too
+        free_b -= 2 * (-(-args.r2b_n // args.r2b_nb) * args.r2b_nb) ** 2 * np.dtype(np.float64).itemsize
     npool = max(1, min(args.steps, int((free_b * 0.8) // max(local_bytes * 1.05, 1))))
     pool = [dlaf.DeviceMatrix(grid, dt, args.uplo, n, nb) for _ in range(npool)]
 
@@ -350,14 +387,14 @@ def main():
     # --check: the miniapp's check_cholesky on the device (ref is overwritten with A - L L^H): works at
     # the full size and on every grid; OK bar of the miniapp = n * eps (miniapp_cholesky.cpp:432-442)
     check = None
-    if args.check or (world == 1 and not args.no_check):
+    if "residual" in todo:
         diff, norm_a = ref.residual_against(pool[(args.steps - 1) % npool])
         check = diff / norm_a
 
     # the panel TRSM alone on the device (in the factorization it runs beside the bulk update on a few free
     # workgroup slots, so its in-situ duration does not describe the kernel)
     trsm_alone = None
-    if world == 1 and nb * 2 <= n and not args.no_trsm_profile:
+    if "trsm_alone" in todo:
         trsm_alone = pool[(args.steps - 1) % npool].trsm_profile(5)
 
     if rank == 0:
@@ -423,14 +460,14 @@ def main():
         if check is not None:
             eps = float(np.finfo(np.float32 if args.type in "sc" else np.float64).eps)
             line["residual"] = {"max|A-LL^H|/max|A|": check, "bar_n_eps": n * eps, "ok": bool(check <= n * eps)}
-        if world == 1 and not args.no_red2band and args.type == "d":
+        if "reduction_to_band" in todo:
             try:
                 for w in pool:
                     w.close()
                 ref.close()
             except Exception:
                 pass
-            if not args.no_eigensolver:
+            if "eigensolver" in todo:
                 try:
                     line["eigensolver"] = eigensolver_line(dlaf, grid, args.r2b_n, args.r2b_nb)
                 except Exception as e:
@@ -439,7 +476,7 @@ def main():
                 line["reduction_to_band"] = red2band_line(dlaf, grid, args.r2b_n, args.r2b_nb, runs=3, mats=r2b_mats)
             except Exception as e:  # an extra line: it must never take the metric down with it
                 line["reduction_to_band"] = {"value": None, "error": repr(e)}
-        if not args.no_cpu_baseline and world == 1:
+        if "cpu_baseline" in todo:
             try:
                 line["cpu_baseline"] = cpu_baseline(args)
             except Exception as e:  # the baseline must never take the GPU number down with it

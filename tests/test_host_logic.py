@@ -243,6 +243,33 @@ def test_bench_refuses_to_run_without_a_gpu():
     assert r.returncode != 0 and "needs a GPU" in (r.stderr + r.stdout) and '"metric"' not in r.stdout
 
 
+def test_bench_extras_sit_behind_full(monkeypatch):
+    """A plain bench.py run does nothing beside the metric; --full turns every extra on, on one GPU only; the --no-*
+    options take single ones out of a --full run and turn nothing on by themselves; --check asks for the residual on
+    any grid."""
+    import bench
+
+    def on(*argv, world=1):
+        monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", str(world), "--steps", "3", "--warmup", "1", *argv])
+        return bench.extras(bench.parse(), world)
+
+    every = {"residual", "trsm_alone", "eigensolver", "reduction_to_band", "cpu_baseline"}
+    assert set(bench.EXTRAS) == every
+    assert on() == set() and on("--dump-outputs", "d") == set()
+    assert on("--full") == every
+    assert on("--full", world=4) == set() and on(world=4) == set()
+    assert on("--check") == {"residual"} and on("--check", world=4) == {"residual"} == on("--full", "--check", world=4)
+    for flag, gone in [("--no-check", {"residual"}), ("--no-trsm-profile", {"trsm_alone"}), ("--no-eigensolver", {"eigensolver"}),
+                       ("--no-red2band", {"eigensolver", "reduction_to_band"}), ("--no-cpu-baseline", {"cpu_baseline"})]:
+        assert on(flag) == set(), flag
+        assert on("--full", flag) == every - gone, flag
+    assert on("--full", "--type", "z") == every - {"eigensolver", "reduction_to_band"}
+    assert on("--full", "--matrix-size", "1024", "--block-size", "1024") == every - {"trsm_alone"}
+    # what a plain run would do with --full (it sizes its pool of work copies like that run)
+    monkeypatch.setattr(sys, "argv", ["bench.py"])
+    assert bench.extras(bench.parse(), 1, full=True) == every and bench.extras(bench.parse(), 1, full=False) == set()
+
+
 class _FactorTiles:
     """Stands in for bench.py's DeviceMatrix in dump_outputs: tile (i, j) holds i * 1000 + j (+ 1j), and with
     `world` > 1 this rank owns the tiles with (i + j) % world == rank."""

@@ -24,7 +24,7 @@ from .cholesky import (DeviceMatrix, GeneralDeviceMatrix, Grid, cholesky_factori
                        tile_trsm, triangular_solver, triangular_solver_device, potrs_device, release_workspace_pool, solver_profile,
                        update_launch_stats, multiplication_profile, pxtrmm, triangular_multiplication,
                        triangular_multiplication_device, hermitian_multiplication, hermitian_multiplication_device,
-                       pxhemm)
+                       pxhemm, update_direct, update_bulk_slots)
 from . import distribution  # noqa: F401
 from .eigensolver import (band_to_tridiagonal, bt_band_to_tridiagonal, bt_reduction_to_band,  # noqa: F401
                           bt_reduction_to_band_device, eigensolver_min_band, eigensolver_profile, get_band_size, hermitian_eigensolver,
@@ -38,4 +38,4 @@ __all__ = ["band_to_tridiagonal", "bt_band_to_tridiagonal", "eigensolver_profile
            "set_random_hermitian_positive_definite", "solver_profile", "tile_gemm", "tile_herk", "tile_potrf", "tile_trsm",
            "triangular_solver", "triangular_solver_device", "potrs_device", "type_char", "version",
            "triangular_multiplication", "triangular_multiplication_device", "pxtrmm", "multiplication_profile",
-           "hermitian_multiplication", "hermitian_multiplication_device", "pxhemm"]
+           "hermitian_multiplication", "hermitian_multiplication_device", "pxhemm", "update_direct", "update_bulk_slots"]

@@ -24,6 +24,20 @@ class DLAFDescriptor(C.Structure):
                 ("jsrc", C.c_int), ("i", C.c_int), ("j", C.c_int), ("ld", C.c_int)]
 
 
+class UpdateDesc(C.Structure):
+    """struct dlaf_mi355x_update_desc (include/dlaf_mi355x/dlaf_mi355x.h): one launch of the grouped update kernel."""
+    _fields_ = ([(n, C.c_long) for n in ("c_elems", "a_elems", "b_elems", "a2_elems", "b2_elems",
+                                         "c_off", "a_off", "b_off", "a2_off", "b2_off")] +
+                [("tile_layout", C.c_int), ("ltr", C.c_int), ("ltc", C.c_int),
+                 ("c_tsr", C.c_long), ("c_tsc", C.c_long), ("ldc", C.c_int),
+                 ("a_ts", C.c_long), ("lda", C.c_int),
+                 ("b_ts", C.c_long), ("ldb", C.c_int), ("b_period", C.c_int), ("b_ts2", C.c_long), ("b_jl0", C.c_int)] +
+                [(n, C.c_int) for n in ("il0", "il1", "jl0", "jl1", "nb", "K", "pr", "ri", "pc", "ci", "nt", "last_rows",
+                                        "rect", "nt_c", "last_cols", "K1", "her2k", "info", "role")] +
+                [("max_blocks", C.c_long), ("excl_rounds", C.c_int),
+                 ("persistent", C.c_long), ("exclusive", C.c_long), ("bulk_slots", C.c_long)])
+
+
 BCAST_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_size_t)
 BARRIER_FN = C.CFUNCTYPE(C.c_int, C.c_void_p)
 
@@ -191,6 +205,11 @@ SIGNATURES = {
     "dlaf_mi355x_tile_trsm": (_i, [_ch, _ch, _i, _i, _vp, _i, _vp, _i]),
     "dlaf_mi355x_tile_herk": (_i, [_ch, _ch, _i, _i, _vp, _i, _vp, _i]),
     "dlaf_mi355x_tile_gemm": (_i, [_ch, _ch, _i, _i, _i, _vp, _i, _vp, _i, _vp, _i]),
+    "dlaf_mi355x_update_direct_s": (_i, [C.POINTER(UpdateDesc), _vp, _vp, _vp, _vp, _vp, _vp]),
+    "dlaf_mi355x_update_direct_d": (_i, [C.POINTER(UpdateDesc), _vp, _vp, _vp, _vp, _vp, _vp]),
+    "dlaf_mi355x_update_direct_c": (_i, [C.POINTER(UpdateDesc), _vp, _vp, _vp, _vp, _vp, _vp]),
+    "dlaf_mi355x_update_direct_z": (_i, [C.POINTER(UpdateDesc), _vp, _vp, _vp, _vp, _vp, _vp]),
+    "dlaf_mi355x_update_bulk_slots": (_l, [_ch]),
     "dlaf_mi355x_dist_owner": (_i, [_l, _i, _i]),
     "dlaf_mi355x_dist_local_tile": (_l, [_l, _i, _i, _i]),
     "dlaf_mi355x_dist_next_local_tile": (_l, [_l, _i, _i, _i]),

@@ -566,3 +566,42 @@ def tile_gemm(uplo: str, a: np.ndarray, b: np.ndarray, c: np.ndarray) -> None:
     k = a.shape[1] if uplo in "Ll" else a.shape[0]
     lib().dlaf_mi355x_tile_gemm(type_char(c.dtype).encode(), uplo.encode(), m, n, k, _ptr(a), _ld_of(a), _ptr(b),
                                 _ld_of(b), _ptr(c), _ld_of(c))
+
+
+def update_bulk_slots(dtype) -> int:
+    """Workgroup slots of the bulk update kernel on this GPU for `dtype` (what the drivers size persistent launches by)."""
+    return int(lib().dlaf_mi355x_update_bulk_slots(type_char(dtype).encode()))
+
+
+def update_direct(c: np.ndarray, a: np.ndarray, b: np.ndarray, *, a2: np.ndarray = None, b2: np.ndarray = None,
+                  offsets=(0, 0, 0, 0, 0), repeat: bool = False, **fields):
+    """ONE launch of the grouped update kernel (UpdateArgs of csrc/device/device_api.hpp) on flat host arrays.
+
+    `c`, `a`, `b` (and `a2`, `b2` with K1 > 0) are one-dimensional arrays of the same dtype holding the operands as
+    the kernel addresses them; `fields` are the fields of struct dlaf_mi355x_update_desc (strides and leading
+    dimensions in elements); `offsets` are the element offsets of (c, a, b, a2, b2) into their device allocations.
+    `c` is updated in place.  Returns (persistent, exclusive, c_again): how many launches took the persistent / the
+    exclusive form, and with `repeat` the result of the same launch repeated on the original `c` with the counter
+    words the first launch left behind (else None)."""
+    from .capi import UpdateDesc
+    ops = [c, a, b] + ([a2, b2] if fields.get("K1", 0) > 0 else [])
+    for x in ops:
+        if x is None or x.ndim != 1 or x.dtype != c.dtype or not x.flags.c_contiguous:
+            raise ValueError("update_direct takes flat contiguous arrays of one dtype")
+    d = UpdateDesc()
+    d.b_period, d.b_jl0 = 1, -1
+    for k, v in fields.items():
+        if k not in {n for n, _ in UpdateDesc._fields_}:
+            raise TypeError(f"update_direct: unknown field {k}")
+        setattr(d, k, v)
+    d.c_elems, d.a_elems, d.b_elems = c.size, a.size, b.size
+    d.a2_elems = a2.size if a2 is not None else 0
+    d.b2_elems = b2.size if b2 is not None else 0
+    d.c_off, d.a_off, d.b_off, d.a2_off, d.b2_off = offsets
+    again = np.empty_like(c) if repeat else None
+    fn = getattr(lib(), "dlaf_mi355x_update_direct_" + type_char(c.dtype))
+    r = fn(C.byref(d), _ptr(c), _ptr(a), _ptr(b), _ptr(a2) if a2 is not None else None,
+           _ptr(b2) if b2 is not None else None, _ptr(again) if repeat else None)
+    if r != 0:
+        raise ValueError(f"dlaf_mi355x_update_direct_{type_char(c.dtype)} refused the launch ({r})")
+    return int(d.persistent), int(d.exclusive), again

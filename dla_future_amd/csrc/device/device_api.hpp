@@ -86,6 +86,10 @@ void launch_update(const UpdateArgs<T>& args, hipStream_t stream, int role = 0, 
                    unsigned* counters = nullptr, bool counters_are_zero = false, long excl_slots = 0);
 template <class T>
 int update_blocks_per_cu();
+// workgroup slots of one whole round of exclusive compute units -- excl_slots is honoured in multiples of it (0: the
+// compute-unit probe found nothing and no launch takes the exclusive form)
+template <class T>
+long update_exclusive_round();
 
 // ------------------------------------------------------------------------------------------
 // Panel TRSM (tile::trsm Right/Lower/ConjTrans/NonUnit of a whole panel in ONE launch,

@@ -20,6 +20,7 @@
 
 #include "device_api.hpp"
 #include "mma_core.hpp"
+#include "update_map.hpp"
 
 namespace dlaf_mi355x {
 
@@ -49,33 +50,6 @@ template <>
 struct UpdateCfg<cdouble> {
   using type = BlockCfg<cdouble, 128, 64, 64, 32, 8, true, 3>;  // interleaved LDS image, direct-to-LDS, 3 stages
   static constexpr int min_waves = 2;
-};
-
-constexpr int kMaxPatchCols = 256;
-
-struct UpdateMap {
-  int ps;        // patch = (1<<ps) block rows x (1<<psc) block columns, square in ELEMENTS
-  int psc;
-  int PR;        // patch rows
-  int tri;       // != 0: only the patches at/below the block-cyclic diagonal are enumerated, patch column by
-                 // patch column, through colstart[] (prefix sums of the valid patches per patch column)
-  int PC;        // patch columns
-  int colstart[kMaxPatchCols + 1];
-  int xcd;       // remap blockIdx so each XCD works on consecutive patches
-  int RB, CB;    // block rows / cols of the domain
-  int bpt_m, bpt_n;
-  long total;    // work items (blocks of the patch enumeration)
-  int persist;   // != 0: the grid is smaller than `total`; workgroups pull work items from `counters`
-  unsigned* counters;  // persist: 8 (per workgroup-id-mod-8, i.e. per XCD) or 1 dequeue heads, zeroed per launch;
-                       // counters[8 + q]: work items of queue q that are finished (lockstep pacing)
-  int lockstep;        // persist: the workgroups of a queue start their items in rounds (see update_kernel)
-  unsigned kphase_ticks;  // persist: wall-clock ticks per K slab of a block (0: every block starts at slab 0)
-  int excl_rank;       // persist: workgroups that find themselves on one of the first `excl_rank` compute units of their
-                       // XCD (g_cu_rank) leave at once -- whole compute units stay free for the kernels beside the update
-  unsigned excl_budget;  // ... but no more than this many per launch (counters[15] counts them)
-  int steal;           // persist: a workgroup whose queue is empty drains the other queues
-  int* cu_busy;        // persist: per (XCD, compute unit) count of tile-POTRF strips resident there (null: off) -- a bulk
-                       // workgroup that shares its compute unit with a strip pauses between two work items
 };
 
 // rank of a compute unit among the compute units of its XCD that the probe launch of update_kernels_init() saw
@@ -384,7 +358,7 @@ __global__ __launch_bounds__(UpdateCfg<T>::type::THREADS, UpdateCfg<T>::min_wave
     return;
   if (!mp.persist) {
     const long v = blockIdx.x;
-    const long w = mp.xcd ? (v & 7) * (mp.total >> 3) + (v >> 3) : v;
+    const long w = update_xcd_remap(mp, v);
     update_block<T, VEC, false, ROLE == 4>(p, mp, w, lds);
     return;
   }
@@ -573,47 +547,8 @@ void launch_update(const UpdateArgs<T>& a, hipStream_t stream, int role, long ma
   if (a.il1 <= a.il0 || a.jl1 <= a.jl0 || a.K <= 0 || a.nb <= 0)
     return;
   UpdateMap mp;
-  mp.bpt_m = (a.nb + Cfg::BM - 1) / Cfg::BM;
-  mp.bpt_n = (a.nb + Cfg::BN - 1) / Cfg::BN;
-  mp.RB = (a.il1 - a.il0) * mp.bpt_m;
-  mp.CB = (a.jl1 - a.jl0) * mp.bpt_n;
-  // patches are square in elements (8 block rows x 8*BM/BN block columns), so the triangular patch
-  // enumeration also serves rectangular blocks: without it half of a launch is empty workgroups whose
-  // long runs starve the compute units (measured on the complex kernel: SQ busy 54 %)
-  static_assert(Cfg::BM % Cfg::BN == 0 && ((Cfg::BM / Cfg::BN) & (Cfg::BM / Cfg::BN - 1)) == 0, "BM = 2^s * BN");
-  constexpr int kAspectShift = (Cfg::BM / Cfg::BN == 1) ? 0 : (Cfg::BM / Cfg::BN == 2) ? 1 : 2;
-  const bool big = (mp.RB >= 16 && mp.CB >= 16);
-  mp.ps = big ? 3 : 0;
-  mp.psc = big ? 3 + kAspectShift : 0;
-  mp.PR = (mp.RB + (1 << mp.ps) - 1) >> mp.ps;
-  mp.PC = (mp.CB + (1 << mp.psc) - 1) >> mp.psc;
-  long npatch = (long) mp.PR * mp.PC;
-  mp.tri = 0;
-  if (mp.PC <= kMaxPatchCols) {
-    // first patch row of every patch column that can hold a tile with global row >= global column
-    mp.tri = 1;
-    mp.colstart[0] = 0;
-    for (int pj = 0; pj < mp.PC; ++pj) {
-      const int jl_min = a.jl0 + (pj << mp.psc) / mp.bpt_n;
-      const long gj_min = (long) jl_min * a.pc + a.ci;
-      long il_first = (gj_min - a.ri + a.pr - 1) / a.pr;  // ceil((gj - ri) / pr) for gj >= ri
-      if (gj_min <= a.ri || a.rect)
-        il_first = 0;
-      if (il_first < a.il0)
-        il_first = a.il0;
-      int cnt = 0;
-      if (il_first < a.il1) {
-        const int pi0 = (int) (((il_first - a.il0) * mp.bpt_m) >> mp.ps);
-        cnt = mp.PR - pi0;
-      }
-      mp.colstart[pj + 1] = mp.colstart[pj] + cnt;
-    }
-    npatch = mp.colstart[mp.PC];
-    if (npatch == 0)
-      return;
-  }
-  mp.total = npatch << (mp.ps + mp.psc);
-  mp.xcd = (mp.ps > 0) ? 1 : 0;
+  if (!build_update_map<Cfg::BM, Cfg::BN>(a, mp))
+    return;
   long grid = mp.total;
   mp.persist = 0;
   mp.lockstep = 0;
@@ -688,6 +623,13 @@ int update_blocks_per_cu() {
                                                    Cfg::LDS_BYTES) != hipSuccess || n < 1)
     n = 1;
   return n;
+}
+
+// workgroup slots of one whole round of exclusive compute units (one compute unit of every shader engine of every
+// XCD the probe saw); 0: no probe, a launch cannot take the exclusive form
+template <class T>
+long update_exclusive_round() {
+  return (long) update_blocks_per_cu<T>() * g_probe_xcds * g_probe_engines;
 }
 
 template <class T>
@@ -811,11 +753,15 @@ void update_kernels_init() {
 
 template void launch_update<float>(const UpdateArgs<float>&, hipStream_t, int, long, unsigned*, bool, long);
 template int update_blocks_per_cu<float>();
+template long update_exclusive_round<float>();
 template void launch_update<double>(const UpdateArgs<double>&, hipStream_t, int, long, unsigned*, bool, long);
 template int update_blocks_per_cu<double>();
+template long update_exclusive_round<double>();
 template void launch_update<cfloat>(const UpdateArgs<cfloat>&, hipStream_t, int, long, unsigned*, bool, long);
 template int update_blocks_per_cu<cfloat>();
+template long update_exclusive_round<cfloat>();
 template void launch_update<cdouble>(const UpdateArgs<cdouble>&, hipStream_t, int, long, unsigned*, bool, long);
 template int update_blocks_per_cu<cdouble>();
+template long update_exclusive_round<cdouble>();
 
 }  // namespace dlaf_mi355x

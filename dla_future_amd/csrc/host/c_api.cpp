@@ -1167,6 +1167,28 @@ int dlaf_mi355x_tile_gemm(char type, char uplo, int m, int n, int k, const void*
   });
 }
 
+#define DLAF_UPDATE_DIRECT(letter, DT)                                                                            \
+  int dlaf_mi355x_update_direct_##letter(dlaf_mi355x_update_desc* d, void* c, const void* a, const void* b,         \
+                                         const void* a2, const void* b2, void* c_again) noexcept {                \
+    if (!d || !c || !a || !b)                                                                                      \
+      return -3;                                                                                                   \
+    return update_direct<DT>(*d, c, a, b, a2, b2, c_again);                                                        \
+  }
+DLAF_UPDATE_DIRECT(s, float)
+DLAF_UPDATE_DIRECT(d, double)
+DLAF_UPDATE_DIRECT(c, cfloat)
+DLAF_UPDATE_DIRECT(z, cdouble)
+#undef DLAF_UPDATE_DIRECT
+long dlaf_mi355x_update_bulk_slots(char type) noexcept {
+  long slots = 0;
+  const int r = dispatch_api_type(type, [&](auto* tag) {
+    using DT = std::remove_pointer_t<decltype(tag)>;
+    slots = update_bulk_slots<DT>();
+    return 0;
+  });
+  return r == 0 ? slots : -1;
+}
+
 int dlaf_mi355x_dist_owner(long gt, int gs, int src) noexcept {
   return Axis{0, 1, gs, 0, src}.owner(gt);
 }

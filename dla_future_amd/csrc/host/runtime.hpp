@@ -16,6 +16,8 @@
 #include "../device/device_api.hpp"
 #include "distribution.hpp"
 
+struct dlaf_mi355x_update_desc;
+
 namespace dlaf_mi355x {
 
 [[noreturn]] void fatal(const char* fmt, ...);
@@ -272,6 +274,13 @@ template <class T>
 void tile_herk(char uplo, int n, int k, const T* a, int lda, T* c, int ldc);
 template <class T>
 void tile_gemm(char uplo, int m, int n, int k, const T* a, int lda, const T* b, int ldb, T* c, int ldc);
+// one launch of the grouped update kernel, every field given by the caller (update_direct.cpp; the descriptor is
+// declared in dlaf_mi355x/dlaf_mi355x.h)
+template <class T>
+int update_direct(::dlaf_mi355x_update_desc& d, void* c, const void* a, const void* b, const void* a2, const void* b2,
+                  void* c_again);
+template <class T>
+long update_bulk_slots();
 
 // Communication self-test of a grid: every member of every row / column communicator broadcasts a
 // coordinate-dependent pattern in turn (in place, out of place and grouped, the three forms the

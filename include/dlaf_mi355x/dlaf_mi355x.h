@@ -447,6 +447,56 @@ DLAF_EXTERN_C int dlaf_mi355x_tile_herk(char type, char uplo, int n, int k, cons
 DLAF_EXTERN_C int dlaf_mi355x_tile_gemm(char type, char uplo, int m, int n, int k, const void* a, int lda,
                                         const void* b, int ldb, void* c, int ldc) DLAF_NOEXCEPT;
 
+/* ---- the grouped update kernel, one launch (host operands) -------------------------------------- */
+/* Every field of one launch of the update kernel that a driver sets (the kernel's contract: UpdateArgs in
+ * csrc/device/device_api.hpp).  The entry uploads the operands, launches ONCE and downloads C; the tests compare the
+ * kernel itself, at any geometry, with a reference.  Strides, leading dimensions and *_elems are in elements of the
+ * type; an operand's host array of *_elems elements is placed *_off elements into a fresh device allocation (off = 1:
+ * a base that is not 16-byte aligned). */
+struct dlaf_mi355x_update_desc {
+  long c_elems, a_elems, b_elems, a2_elems, b2_elems;
+  long c_off, a_off, b_off, a2_off, b2_off;
+  /* tile_layout != 0: C is ltr x ltc local tiles of nb x nb in tile layout and the panels hold nb x K tiles (ld nb);
+   * c_tsr / c_tsc / ldc / a_ts / lda / ldb / pr / ri / pc / ci / nt / last_rows / rect / nt_c / last_cols below are
+   * then derived from (ltr, nb, pr, ri, pc, ci, nt, last_rows, rect, nt_c, last_cols) the way the drivers derive them */
+  int tile_layout, ltr, ltc;
+  long c_tsr, c_tsc;
+  int ldc;
+  long a_ts;
+  int lda;
+  long b_ts;
+  int ldb;
+  int b_period;
+  long b_ts2;
+  int b_jl0;
+  int il0, il1, jl0, jl1, nb, K;
+  int pr, ri, pc, ci;
+  int nt, last_rows;
+  int rect, nt_c, last_cols;
+  int K1, her2k; /* K1 > 0: a2 / b2 are read */
+  int info;      /* value of the device info word the kernel looks at */
+  int role;      /* 0 .. 4 */
+  long max_blocks; /* 0: one workgroup per work item; > 0: persistent form with at most that many; < 0: this GPU's
+                    * workgroup slots for the type (what the drivers pass for the bulk launches) */
+  int excl_rounds; /* whole rounds of exclusive compute units (0: none) */
+  /* out */
+  long persistent, exclusive; /* launches that took the persistent / exclusive form (0 or 1 per launch) */
+  long bulk_slots;            /* this GPU's workgroup slots for the type */
+};
+/* c (c_elems elements) is updated in place.  c_again != NULL: the launch is repeated on a fresh copy of the original
+ * c with the SAME 16 counter words, not zeroed by the caller (counters_are_zero = false), into c_again.
+ * Returns 0, -1 for an unknown type / role, -3 when a field would make the kernel touch memory outside an operand. */
+DLAF_EXTERN_C int dlaf_mi355x_update_direct_s(struct dlaf_mi355x_update_desc* d, void* c, const void* a, const void* b,
+                                              const void* a2, const void* b2, void* c_again) DLAF_NOEXCEPT;
+DLAF_EXTERN_C int dlaf_mi355x_update_direct_d(struct dlaf_mi355x_update_desc* d, void* c, const void* a, const void* b,
+                                              const void* a2, const void* b2, void* c_again) DLAF_NOEXCEPT;
+DLAF_EXTERN_C int dlaf_mi355x_update_direct_c(struct dlaf_mi355x_update_desc* d, void* c, const void* a, const void* b,
+                                              const void* a2, const void* b2, void* c_again) DLAF_NOEXCEPT;
+DLAF_EXTERN_C int dlaf_mi355x_update_direct_z(struct dlaf_mi355x_update_desc* d, void* c, const void* a, const void* b,
+                                              const void* a2, const void* b2, void* c_again) DLAF_NOEXCEPT;
+/* this GPU's workgroup slots of the bulk update kernel for the type (initialises the runtime) */
+DLAF_EXTERN_C long dlaf_mi355x_update_bulk_slots(char type) DLAF_NOEXCEPT;
+
 /* ---- index helpers (no GPU needed) -------------------------------------------------------------- */
 DLAF_EXTERN_C int dlaf_mi355x_dist_owner(long global_tile, int grid_size, int src_rank) DLAF_NOEXCEPT;
 DLAF_EXTERN_C long dlaf_mi355x_dist_local_tile(long global_tile, int grid_size, int rank, int src_rank) DLAF_NOEXCEPT;

@@ -12,6 +12,8 @@ Python doorway onto that ABI, mirroring the reference's operator surface for the
     dlaf::triangular_solver(side, uplo, op, diag, ...)  include/dlaf/solver/triangular.h:41-177 (next row, SURVEY 8(f)2)
     dlaf::triangular_multiplication(side, uplo, ...)   include/dlaf/multiplication/triangular.h
     dlaf::hermitian_multiplication(side, uplo, ...)    include/dlaf/multiplication/hermitian.h
+    dlaf::triangular_inverse(uplo, diag, A)            LAPACK xTRTRI / p?trtri (upstream: after the reference snapshot)
+    dlaf::inverse_from_cholesky_factor(uplo, A)        LAPACK xPOTRI / p?potri
     generalized_to_standard(grid, uplo, A, B)          include/dlaf/eigensolver/gen_to_std.h:50,:101
     reduction_to_band / bt_reduction_to_band           include/dlaf/eigensolver/reduction_to_band.h:40-122, bt_reduction_to_band.h
 
@@ -22,6 +24,7 @@ from .capi import (DLAFDescriptor, LibraryNotBuilt, lib, lib_path, type_char, ve
 from .cholesky import (DeviceMatrix, GeneralDeviceMatrix, Grid, cholesky_factorization, finalize, generalized_to_standard,  # noqa: F401
                        initialize, make_descriptor, potrf_trace, pxhegst, pxpotrf, pxpotrs, pxtrsm, set_random_hermitian_positive_definite, tile_gemm, tile_herk, tile_potrf,
                        tile_trsm, triangular_solver, triangular_solver_device, potrs_device, release_workspace_pool, solver_profile,
+                       triangular_inverse, inverse_from_cholesky_factor, pxtrtri, pxpotri, inverse_profile,
                        update_launch_stats, multiplication_profile, pxtrmm, triangular_multiplication,
                        triangular_multiplication_device, hermitian_multiplication, hermitian_multiplication_device,
                        pxhemm, update_direct, update_bulk_slots)
@@ -36,6 +39,7 @@ __all__ = ["band_to_tridiagonal", "bt_band_to_tridiagonal", "eigensolver_profile
            "reduction_to_band", "reduction_to_band_device", "DLAFDescriptor", "DeviceMatrix", "GeneralDeviceMatrix", "Grid", "LibraryNotBuilt", "cholesky_factorization", "distribution",
            "finalize", "generalized_to_standard", "initialize", "lib", "lib_path", "make_descriptor", "pxhegst", "pxpotrf", "pxpotrs", "pxtrsm",
            "set_random_hermitian_positive_definite", "solver_profile", "tile_gemm", "tile_herk", "tile_potrf", "tile_trsm",
-           "triangular_solver", "triangular_solver_device", "potrs_device", "type_char", "version",
+           "triangular_solver", "triangular_solver_device", "potrs_device", "triangular_inverse",
+           "inverse_from_cholesky_factor", "pxtrtri", "pxpotri", "inverse_profile", "type_char", "version",
            "triangular_multiplication", "triangular_multiplication_device", "pxtrmm", "multiplication_profile",
            "hermitian_multiplication", "hermitian_multiplication_device", "pxhemm", "update_direct", "update_bulk_slots"]

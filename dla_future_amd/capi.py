@@ -149,6 +149,27 @@ SIGNATURES = {
     "dlaf_mi355x_pchegst": (None, [_i, _ch, _i, _vp, _i, _i, _IP, _vp, _i, _i, _IP, _vp, _IP]),
     "dlaf_mi355x_pzhegst": (None, [_i, _ch, _i, _vp, _i, _i, _IP, _vp, _i, _i, _IP, _vp, _IP]),
     "dlaf_mi355x_generalized_to_standard_device": (_i, [_vp, _vp]),
+    "dlaf_mi355x_triangular_inverse_s": (_i, [_i, _ch, _ch, _vp, DLAFDescriptor]),
+    "dlaf_mi355x_inverse_from_cholesky_factor_s": (_i, [_i, _ch, _vp, DLAFDescriptor]),
+    "dlaf_mi355x_pstrtri": (None, [_ch, _ch, _i, _vp, _i, _i, _IP, _IP]),
+    "dlaf_mi355x_pspotri": (None, [_ch, _i, _vp, _i, _i, _IP, _IP]),
+    "dlaf_mi355x_triangular_inverse_d": (_i, [_i, _ch, _ch, _vp, DLAFDescriptor]),
+    "dlaf_mi355x_inverse_from_cholesky_factor_d": (_i, [_i, _ch, _vp, DLAFDescriptor]),
+    "dlaf_mi355x_pdtrtri": (None, [_ch, _ch, _i, _vp, _i, _i, _IP, _IP]),
+    "dlaf_mi355x_pdpotri": (None, [_ch, _i, _vp, _i, _i, _IP, _IP]),
+    "dlaf_mi355x_triangular_inverse_c": (_i, [_i, _ch, _ch, _vp, DLAFDescriptor]),
+    "dlaf_mi355x_inverse_from_cholesky_factor_c": (_i, [_i, _ch, _vp, DLAFDescriptor]),
+    "dlaf_mi355x_pctrtri": (None, [_ch, _ch, _i, _vp, _i, _i, _IP, _IP]),
+    "dlaf_mi355x_pcpotri": (None, [_ch, _i, _vp, _i, _i, _IP, _IP]),
+    "dlaf_mi355x_triangular_inverse_z": (_i, [_i, _ch, _ch, _vp, DLAFDescriptor]),
+    "dlaf_mi355x_inverse_from_cholesky_factor_z": (_i, [_i, _ch, _vp, DLAFDescriptor]),
+    "dlaf_mi355x_pztrtri": (None, [_ch, _ch, _i, _vp, _i, _i, _IP, _IP]),
+    "dlaf_mi355x_pzpotri": (None, [_ch, _i, _vp, _i, _i, _IP, _IP]),
+    "dlaf_mi355x_triangular_inverse_device": (_i, [_ch, _ch, _vp]),
+    "dlaf_mi355x_inverse_from_cholesky_factor_device": (_i, [_ch, _vp]),
+    "dlaf_mi355x_inverse_profile": (_i, [C.POINTER(C.c_double), C.POINTER(C.c_double)]),
+    "dlaf_mi355x_inverse_plan": (_i, [C.c_long, _i, _i, _i, _i, _i, _i, _i, C.POINTER(C.c_long)]),
+    "dlaf_mi355x_inverse_step": (_i, [C.c_long, _i, _i, _i, _i, _i, _i, _i, C.c_long, C.POINTER(C.c_long)]),
     "dlaf_mi355x_reduction_to_band_s": (_i, [_i, _vp, DLAFDescriptor, _i, _vp]),
     "dlaf_mi355x_reduction_to_band_d": (_i, [_i, _vp, DLAFDescriptor, _i, _vp]),
     "dlaf_mi355x_reduction_to_band_c": (_i, [_i, _vp, DLAFDescriptor, _i, _vp]),

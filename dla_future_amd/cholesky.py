@@ -325,6 +325,60 @@ def pxhegst(ibtype: int, uplo: str, n: int, a: np.ndarray, ia: int, ja: int, des
     return scale.value, info.value
 
 
+def triangular_inverse(grid: Grid, uplo: str, diag: str, a: np.ndarray, nb: int, isrc: int = 0, jsrc: int = 0,
+                       n: int | None = None) -> int:
+    """dlaf::triangular_inverse == dlaf_mi355x_triangular_inverse_{s,d,c,z} (LAPACK xTRTRI): the triangular matrix in the
+    uplo triangle of `a` (this process's local part; diag 'N' / 'U') is overwritten by its inverse.  Returns LAPACK's
+    info: i > 0 when the i-th diagonal element is exactly zero, and `a` is then untouched."""
+    t = type_char(a.dtype)
+    if n is None:
+        if grid.nranks != 1:
+            raise ValueError("the global size n is required on a distributed grid")
+        n = a.shape[0]
+    da = make_descriptor(n, nb, _ld_of(a), isrc, jsrc)
+    return getattr(lib(), f"dlaf_mi355x_triangular_inverse_{t}")(grid.context, uplo.encode(), diag.encode(), _ptr(a), da)
+
+
+def inverse_from_cholesky_factor(grid: Grid, uplo: str, a: np.ndarray, nb: int, isrc: int = 0, jsrc: int = 0,
+                                 n: int | None = None) -> int:
+    """dlaf::inverse_from_cholesky_factor == dlaf_mi355x_inverse_from_cholesky_factor_{s,d,c,z} (LAPACK xPOTRI): the
+    uplo triangle of `a` holds the Cholesky factor and is overwritten by the same triangle of inv(L L^H) / inv(U^H U).
+    Returns LAPACK's info."""
+    t = type_char(a.dtype)
+    if n is None:
+        if grid.nranks != 1:
+            raise ValueError("the global size n is required on a distributed grid")
+        n = a.shape[0]
+    da = make_descriptor(n, nb, _ld_of(a), isrc, jsrc)
+    return getattr(lib(), f"dlaf_mi355x_inverse_from_cholesky_factor_{t}")(grid.context, uplo.encode(), _ptr(a), da)
+
+
+def pxtrtri(uplo: str, diag: str, n: int, a: np.ndarray, ia: int, ja: int, desca) -> int:
+    """dlaf_mi355x_p{s,d,c,z}trtri: ScaLAPACK's p?trtri argument list; returns info."""
+    t = type_char(a.dtype)
+    da = (C.c_int * 9)(*[int(x) for x in desca])
+    info = C.c_int(-999)
+    getattr(lib(), f"dlaf_mi355x_p{t}trtri")(uplo.encode(), diag.encode(), n, _ptr(a), ia, ja, da, C.byref(info))
+    return info.value
+
+
+def pxpotri(uplo: str, n: int, a: np.ndarray, ia: int, ja: int, desca) -> int:
+    """dlaf_mi355x_p{s,d,c,z}potri: ScaLAPACK's p?potri argument list; returns info."""
+    t = type_char(a.dtype)
+    da = (C.c_int * 9)(*[int(x) for x in desca])
+    info = C.c_int(-999)
+    getattr(lib(), f"dlaf_mi355x_p{t}potri")(uplo.encode(), n, _ptr(a), ia, ja, da, C.byref(info))
+    return info.value
+
+
+def inverse_profile():
+    """(ms, flops) of the last triangular_inverse / inverse_from_cholesky_factor on this process (device time, no
+    staging; n^3 / 3 flops per half, x 4 for complex types)."""
+    ms, fl = C.c_double(0), C.c_double(0)
+    lib().dlaf_mi355x_inverse_profile(C.byref(ms), C.byref(fl))
+    return ms.value, fl.value
+
+
 def solver_profile():
     """(ms, flops) of the sweep of the last triangular solve on this process (device time, no staging)."""
     ms, fl = C.c_double(0), C.c_double(0)
@@ -419,6 +473,14 @@ class DeviceMatrix:
     def generalized_to_standard(self, factor_of_b: "DeviceMatrix") -> int:
         """`self` (Hermitian A, resident) <- inv(L) A inv(L^H) with the resident Cholesky factor of B."""
         return lib().dlaf_mi355x_generalized_to_standard_device(self._h, factor_of_b._h)
+
+    def invert_triangular(self, diag: str = "N") -> int:
+        """The resident triangular matrix (this matrix's uplo triangle) <- its inverse; returns LAPACK's info."""
+        return lib().dlaf_mi355x_triangular_inverse_device(self.uplo.encode(), diag.encode(), self._h)
+
+    def invert_from_factor(self) -> int:
+        """The resident Cholesky factor <- the uplo triangle of inv(L L^H) / inv(U^H U); returns LAPACK's info."""
+        return lib().dlaf_mi355x_inverse_from_cholesky_factor_device(self.uplo.encode(), self._h)
 
     def start(self) -> None:
         lib().dlaf_mi355x_cholesky_start(self._h)

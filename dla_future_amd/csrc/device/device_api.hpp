@@ -172,6 +172,36 @@ template <class T>
 void launch_hemm(const HemmArgs<T>& args, hipStream_t stream);
 
 // ------------------------------------------------------------------------------------------
+// Diagonal-tile work of triangular_inverse / inverse_from_cholesky_factor (kernels_inverse.hip).  A batch of
+// `count` lower triangular tiles, tile t at base + t * stride (leading dimension ld), each nb x nb except the last,
+// which is last x last.
+template <class T>
+struct TileBatch {
+  T* base;
+  long stride;
+  int ld;
+  int nb, count, last;
+};
+// N_t = -inv(T_t)^H (upper triangular, whole tile written, zero below the diagonal) at nout + t * nstride (ld as the
+// tiles); winv + t * winv_stride: the inverted 64 x 64 diagonal blocks of tile t (launch_invert_diag_blocks, lower).
+// Only the strictly lower blocks of T_t are read.
+template <class T>
+void launch_tile_trtri(const TileBatch<const T>& tiles, const T* winv, long winv_stride, T* nout, long nstride,
+                       hipStream_t stream);
+// lower(tile t) = lower(Z_t Z_t^H), Z_t = W_t^H upper triangular at z + t * zstride: the self-product W^H W of a lower
+// triangular tile (xLAUUM); the diagonal comes out real.
+template <class T>
+void launch_tile_lauum(const TileBatch<T>& tiles, const T* z, long zstride, hipStream_t stream);
+// mode 0: the lower triangle of src tile t into dst tile t (unit: without the diagonal), nothing else of dst touched;
+// mode 1: dst tile t = lower(src tile t)^H, the whole tile (zero below the diagonal)
+template <class T>
+void launch_tri_tile(const TileBatch<T>& dst, const T* src, long sstride, int mode, bool unit, hipStream_t stream);
+// *first = min(*first, i + 1) over the exactly-zero diagonal elements i (global index); tile t holds the global tile
+// k0 + t * kstep.  The caller presets *first to 0xffffffff.
+template <class T>
+void launch_diag_zero_scan(const TileBatch<const T>& tiles, long k0, long kstep, unsigned* first, hipStream_t stream);
+
+// ------------------------------------------------------------------------------------------
 // Diagonal block factorization + inversion (one workgroup):  a (jb x jb, lda, jb <= 64) is
 // overwritten by its lower Cholesky factor (strict upper part untouched); winv_block (64 x 64,
 // ld 64) receives inv(L) (lower, zero elsewhere).  On a non-positive pivot at column c the

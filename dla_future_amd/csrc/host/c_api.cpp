@@ -337,6 +337,35 @@ void pxhegst(int ibtype, char uplo, int n, HT* a, int ia, int ja, const int desc
     *info = r;
 }
 
+// dlaf::triangular_inverse / dlaf::inverse_from_cholesky_factor through descriptors (inverse.cpp)
+template <class HT>
+int inverse_c(int ctx, char uplo, char diag, bool product, HT* a, const DLAF_descriptor& da) {
+  using DT = typename DevType<HT>::type;
+  check_cholesky_desc(da);
+  if (!(uplo == 'L' || uplo == 'l' || uplo == 'U' || uplo == 'u'))
+    fatal("[dlaf_mi355x] uplo must be 'L' or 'U', got '%c'\n", uplo);
+  Grid& g = grid_from_context(ctx);
+  if (da.isrc < 0 || da.isrc >= g.nprow || da.jsrc < 0 || da.jsrc >= g.npcol)
+    fatal("[dlaf_mi355x] source rank (%d,%d) outside the %d x %d grid\n", da.isrc, da.jsrc, g.nprow, g.npcol);
+  if (product)
+    return inverse_from_cholesky_factor_host<DT>(&g, uplo, reinterpret_cast<DT*>(a), da.ld, da.m, da.nb, da.isrc,
+                                                 da.jsrc);
+  return triangular_inverse_host<DT>(&g, uplo, diag, reinterpret_cast<DT*>(a), da.ld, da.m, da.nb, da.isrc, da.jsrc);
+}
+
+// ScaLAPACK p?trtri / p?potri argument lists
+template <class HT>
+void pxinverse(char uplo, char diag, bool product, int n, HT* a, int ia, int ja, const int desca[9], int* info) {
+  if (desca[0] != 1)
+    fatal("[dlaf_mi355x] desc[0] (dtype) must be 1\n");
+  if (ia != 1 || ja != 1)
+    fatal("[dlaf_mi355x] ia, ja must be 1\n");
+  const DLAF_descriptor da = make_dlaf_descriptor(n, n, ia, ja, desca);
+  const int r = inverse_c<HT>(desca[1], uplo, diag, product, a, da);
+  if (info)
+    *info = r;
+}
+
 // dlaf::eigensolver::internal::reduction_to_band (include/dlaf/eigensolver/reduction_to_band.h:101-122) through the
 // reference's descriptor conventions
 template <class HT>
@@ -798,6 +827,26 @@ DLAF_MI355X_HEGST_ENTRY(c, std::complex<float>, dlaf_complex_c, float)
 DLAF_MI355X_HEGST_ENTRY(z, std::complex<double>, dlaf_complex_z, double)
 #undef DLAF_MI355X_HEGST_ENTRY
 
+#define DLAF_MI355X_INVERSE_ENTRY(S, HT, CT)                                                                      \
+  int dlaf_mi355x_triangular_inverse_##S(int ctx, char uplo, char diag, CT* a, DLAF_descriptor desca) noexcept {     \
+    return inverse_c<HT>(ctx, uplo, diag, false, reinterpret_cast<HT*>(a), desca);                                  \
+  }                                                                                                                \
+  int dlaf_mi355x_inverse_from_cholesky_factor_##S(int ctx, char uplo, CT* a, DLAF_descriptor desca) noexcept {     \
+    return inverse_c<HT>(ctx, uplo, 'N', true, reinterpret_cast<HT*>(a), desca);                                    \
+  }                                                                                                                \
+  void dlaf_mi355x_p##S##trtri(char uplo, char diag, int n, CT* a, int ia, int ja, const int desca[9],              \
+                               int* info) noexcept {                                                               \
+    pxinverse<HT>(uplo, diag, false, n, reinterpret_cast<HT*>(a), ia, ja, desca, info);                             \
+  }                                                                                                                \
+  void dlaf_mi355x_p##S##potri(char uplo, int n, CT* a, int ia, int ja, const int desca[9], int* info) noexcept {   \
+    pxinverse<HT>(uplo, 'N', true, n, reinterpret_cast<HT*>(a), ia, ja, desca, info);                               \
+  }
+DLAF_MI355X_INVERSE_ENTRY(s, float, float)
+DLAF_MI355X_INVERSE_ENTRY(d, double, double)
+DLAF_MI355X_INVERSE_ENTRY(c, std::complex<float>, dlaf_complex_c)
+DLAF_MI355X_INVERSE_ENTRY(z, std::complex<double>, dlaf_complex_z)
+#undef DLAF_MI355X_INVERSE_ENTRY
+
 #define DLAF_MI355X_R2B_ENTRY(S, HT, CT)                                                                          \
   int dlaf_mi355x_reduction_to_band_##S(int ctx, CT* a, DLAF_descriptor desca, int band, CT* taus) noexcept {     \
     return red2band_c<HT>(ctx, reinterpret_cast<HT*>(a), desca, band, reinterpret_cast<HT*>(taus));               \
@@ -1097,6 +1146,41 @@ int dlaf_mi355x_generalized_to_standard_device(dlaf_mi355x_matrix_t a, dlaf_mi35
   if (!a || !l || a->type != l->type)
     return -1;
   WITH_MATRIX(a, return gen_to_std_device(M, static_cast<DeviceMatrix<DT>&>(*l->m));)
+}
+
+static bool same_uplo(char a, char b) {
+  return (a == 'U' || a == 'u') == (b == 'U' || b == 'u');
+}
+int dlaf_mi355x_triangular_inverse_device(char uplo, char diag, dlaf_mi355x_matrix_t m) noexcept {
+  WITH_MATRIX(m, if (!same_uplo(uplo, M.uplo)) fatal("[dlaf_mi355x] triangular inverse: the resident matrix holds the "
+                                                     "'%c' triangle, not '%c'\n", M.uplo, uplo);
+              return triangular_inverse_device(diag, M);)
+}
+int dlaf_mi355x_inverse_from_cholesky_factor_device(char uplo, dlaf_mi355x_matrix_t m) noexcept {
+  WITH_MATRIX(m, if (!same_uplo(uplo, M.uplo)) fatal("[dlaf_mi355x] inverse from the Cholesky factor: the resident "
+                                                     "matrix holds the '%c' triangle, not '%c'\n", M.uplo, uplo);
+              return inverse_from_cholesky_factor_device(M);)
+}
+int dlaf_mi355x_inverse_profile(double* ms, double* flops) noexcept {
+  inverse_last_profile(ms, flops);
+  return 0;
+}
+int dlaf_mi355x_inverse_plan(long n, int nb, int nprow, int npcol, int myrow, int mycol, int isrc, int jsrc,
+                             long out[9]) noexcept {
+  const Axis rows{n, nb, nprow, myrow, isrc}, cols{n, nb, npcol, mycol, jsrc};
+  const DiagTiles d = local_diag_tiles(rows, cols);
+  const long v[9] = {d.count, d.k0, d.kstep, d.il0, d.jl0, d.il_step, d.jl_step, d.last,
+                     inverse_workspace_tiles(rows, cols)};
+  std::copy(v, v + 9, out);
+  return 0;
+}
+int dlaf_mi355x_inverse_step(long n, int nb, int nprow, int npcol, int myrow, int mycol, int isrc, int jsrc, long k,
+                             long out[7]) noexcept {
+  const Axis rows{n, nb, nprow, myrow, isrc}, cols{n, nb, npcol, mycol, jsrc};
+  const InverseStep st = inverse_step_ranges(rows, cols, k);
+  const long v[7] = {st.own_r, st.own_c, st.il_below, st.nrl, st.ncl, st.lr, st.lc};
+  std::copy(v, v + 7, out);
+  return 0;
 }
 
 int dlaf_mi355x_reduction_to_band_device(dlaf_mi355x_matrix_t a, int band, void* taus) noexcept {

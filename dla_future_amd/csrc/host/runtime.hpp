@@ -332,6 +332,37 @@ int gen_to_std_device(DeviceMatrix<T>& a, DeviceMatrix<T>& l);
 template <class T>
 int gen_to_std_host(Grid* g, char uplo, T* a, long lda, const T* l, long ldl, long n, int nb, int isrc, int jsrc);
 
+// A <- A^-1 for the triangular matrix in A's uplo triangle (diag N / U), and the uplo triangle of (L L^H)^-1 /
+// (U^H U)^-1 from the Cholesky factor held there (inverse.cpp; LAPACK xTRTRI / xPOTRI), in place; device-resident and
+// host forms.  Return LAPACK's info: the 1-based index of the first exactly-zero diagonal element (nothing is written
+// then), the same on every rank.
+template <class T>
+int triangular_inverse_device(char diag, DeviceMatrix<T>& a);
+template <class T>
+int inverse_from_cholesky_factor_device(DeviceMatrix<T>& a);
+template <class T>
+int triangular_inverse_host(Grid* g, char uplo, char diag, T* a, long lda, long n, int nb, int isrc, int jsrc);
+template <class T>
+int inverse_from_cholesky_factor_host(Grid* g, char uplo, T* a, long lda, long n, int nb, int isrc, int jsrc);
+// device time and whole-grid flops (n^3 / 3 per half, x 4 for complex types) of the last of them on this process
+void inverse_last_profile(double* ms, double* flops);
+// index arithmetic of the two sweeps (exported for the host-logic tests)
+struct DiagTiles {
+  long count;             // local diagonal tiles: global k0 + m kstep at local (il0 + m il_step, jl0 + m jl_step)
+  long k0, kstep;
+  long il0, jl0, il_step, jl_step;
+  int last;               // extent of the last of them
+};
+DiagTiles local_diag_tiles(const Axis& rows, const Axis& cols);
+struct InverseStep {
+  int own_r, own_c;       // owner of the diagonal tile k
+  long il_below;          // first local tile row below k
+  long nrl, ncl;          // local tile rows / columns before k
+  long lr, lc;            // local index of tile row / column k (-1: elsewhere)
+};
+InverseStep inverse_step_ranges(const Axis& rows, const Axis& cols, long k);
+long inverse_workspace_tiles(const Axis& rows, const Axis& cols);
+
 void runtime_init();
 void runtime_finalize();
 bool runtime_initialized();

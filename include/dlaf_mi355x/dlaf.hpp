@@ -523,6 +523,65 @@ void generalized_to_standard(blas::Uplo uplo, Matrix<T, Device::CPU>& mat_a, Mat
 }
 }  // namespace eigensolver::internal
 
+// dlaf::triangular_inverse (LAPACK xTRTRI) and dlaf::inverse_from_cholesky_factor (LAPACK xPOTRI), in place on the uplo
+// triangle; local and grid forms, host- and device-resident operands.  They return LAPACK's info (the 1-based index of
+// an exactly-zero diagonal element of a non-unit triangular operand, which is then untouched).
+namespace internal {
+template <class T>
+int inverse_host(int ctx, blas::Uplo uplo, blas::Diag diag, bool product, Matrix<T, Device::CPU>& m) {
+  const auto& d = m.distribution();
+  const DLAF_descriptor desc{(int) d.size().rows(), (int) d.size().cols(), (int) d.block_size().rows(),
+                             (int) d.block_size().cols(), (int) d.source_rank_index().row(),
+                             (int) d.source_rank_index().col(), 0, 0, (int) m.ld()};
+  if constexpr (std::is_same_v<T, float>)
+    return product ? dlaf_mi355x_inverse_from_cholesky_factor_s(ctx, (char) uplo, m.ptr(), desc)
+                   : dlaf_mi355x_triangular_inverse_s(ctx, (char) uplo, (char) diag, m.ptr(), desc);
+  else if constexpr (std::is_same_v<T, double>)
+    return product ? dlaf_mi355x_inverse_from_cholesky_factor_d(ctx, (char) uplo, m.ptr(), desc)
+                   : dlaf_mi355x_triangular_inverse_d(ctx, (char) uplo, (char) diag, m.ptr(), desc);
+  else if constexpr (std::is_same_v<T, std::complex<float>>)
+    return product ? dlaf_mi355x_inverse_from_cholesky_factor_c(ctx, (char) uplo, m.ptr(), desc)
+                   : dlaf_mi355x_triangular_inverse_c(ctx, (char) uplo, (char) diag, m.ptr(), desc);
+  else
+    return product ? dlaf_mi355x_inverse_from_cholesky_factor_z(ctx, (char) uplo, m.ptr(), desc)
+                   : dlaf_mi355x_triangular_inverse_z(ctx, (char) uplo, (char) diag, m.ptr(), desc);
+}
+}  // namespace internal
+template <Backend B, class T>
+int triangular_inverse(comm::CommunicatorGrid& grid, blas::Uplo uplo, blas::Diag diag, Matrix<T, Device::CPU>& mat_a) {
+  static_assert(B == Backend::GPU, "this library has no CPU backend");
+  return internal::inverse_host<T>(grid.context(), uplo, diag, false, mat_a);
+}
+template <Backend B, class T>
+int triangular_inverse(comm::CommunicatorGrid& grid, blas::Uplo uplo, blas::Diag diag, Matrix<T, Device::GPU>& mat_a) {
+  static_assert(B == Backend::GPU, "this library has no CPU backend");
+  if (grid.context() != mat_a.context())
+    internal::fail("matrix::equal_process_grid(mat_a, grid)");
+  return dlaf_mi355x_triangular_inverse_device((char) uplo, (char) diag, mat_a.handle());
+}
+template <Backend B, class T>
+int triangular_inverse(blas::Uplo uplo, blas::Diag diag, Matrix<T, Device::CPU>& mat_a) {
+  comm::CommunicatorGrid grid = comm::CommunicatorGrid::single();
+  return triangular_inverse<B, T>(grid, uplo, diag, mat_a);
+}
+template <Backend B, class T>
+int inverse_from_cholesky_factor(comm::CommunicatorGrid& grid, blas::Uplo uplo, Matrix<T, Device::CPU>& mat_a) {
+  static_assert(B == Backend::GPU, "this library has no CPU backend");
+  return internal::inverse_host<T>(grid.context(), uplo, blas::Diag::NonUnit, true, mat_a);
+}
+template <Backend B, class T>
+int inverse_from_cholesky_factor(comm::CommunicatorGrid& grid, blas::Uplo uplo, Matrix<T, Device::GPU>& mat_a) {
+  static_assert(B == Backend::GPU, "this library has no CPU backend");
+  if (grid.context() != mat_a.context())
+    internal::fail("matrix::equal_process_grid(mat_a, grid)");
+  return dlaf_mi355x_inverse_from_cholesky_factor_device((char) uplo, mat_a.handle());
+}
+template <Backend B, class T>
+int inverse_from_cholesky_factor(blas::Uplo uplo, Matrix<T, Device::CPU>& mat_a) {
+  comm::CommunicatorGrid grid = comm::CommunicatorGrid::single();
+  return inverse_from_cholesky_factor<B, T>(grid, uplo, mat_a);
+}
+
 // include/dlaf/eigensolver/reduction_to_band.h:40-122 and bt_reduction_to_band.h (first stage).
 // The reference returns the taus as a Matrix<T, Device::CPU> distributed over the process columns; here every
 // process gets all n - band_size - 1 of them as a std::vector (entry j belongs to the reflector in global column j).

@@ -497,6 +497,62 @@ DLAF_EXTERN_C int dlaf_mi355x_update_direct_z(struct dlaf_mi355x_update_desc* d,
 /* this GPU's workgroup slots of the bulk update kernel for the type (initialises the runtime) */
 DLAF_EXTERN_C long dlaf_mi355x_update_bulk_slots(char type) DLAF_NOEXCEPT;
 
+/* ---- triangular inverse and inverse from the Cholesky factor (LAPACK xTRTRI / xPOTRI) --------------------- */
+/* triangular_inverse: a <- inv(a) for the triangular matrix in a's uplo triangle (diag 'N' / 'U'), in place.  Nothing
+ * outside the uplo triangle is read or written, with diag 'U' the stored diagonal neither.
+ * inverse_from_cholesky_factor: a's uplo triangle holds the Cholesky factor (dlaf_p?potrf output) and is overwritten
+ * by the same triangle of inv(L L^H) (uplo 'L') / inv(U^H U) (uplo 'U'); the diagonal of the result is real.
+ * Square matrix, square blocks, offsets 0, any source process.  Return LAPACK's info: 0, or i > 0 when the i-th
+ * diagonal element (1-based, global) of a non-unit triangular operand is exactly zero -- the check runs before anything
+ * is written, a comes back untouched; the same value on every rank.  The p?trtri / p?potri names take ScaLAPACK's
+ * argument lists (ia = ja = 1). */
+DLAF_EXTERN_C int dlaf_mi355x_triangular_inverse_s(int context, char uplo, char diag, float* a,
+                                                   struct DLAF_descriptor desca) DLAF_NOEXCEPT;
+DLAF_EXTERN_C int dlaf_mi355x_inverse_from_cholesky_factor_s(int context, char uplo, float* a,
+                                                             struct DLAF_descriptor desca) DLAF_NOEXCEPT;
+DLAF_EXTERN_C void dlaf_mi355x_pstrtri(char uplo, char diag, int n, float* a, int ia, int ja, const int desca[9],
+                                       int* info) DLAF_NOEXCEPT;
+DLAF_EXTERN_C void dlaf_mi355x_pspotri(char uplo, int n, float* a, int ia, int ja, const int desca[9],
+                                       int* info) DLAF_NOEXCEPT;
+DLAF_EXTERN_C int dlaf_mi355x_triangular_inverse_d(int context, char uplo, char diag, double* a,
+                                                   struct DLAF_descriptor desca) DLAF_NOEXCEPT;
+DLAF_EXTERN_C int dlaf_mi355x_inverse_from_cholesky_factor_d(int context, char uplo, double* a,
+                                                             struct DLAF_descriptor desca) DLAF_NOEXCEPT;
+DLAF_EXTERN_C void dlaf_mi355x_pdtrtri(char uplo, char diag, int n, double* a, int ia, int ja, const int desca[9],
+                                       int* info) DLAF_NOEXCEPT;
+DLAF_EXTERN_C void dlaf_mi355x_pdpotri(char uplo, int n, double* a, int ia, int ja, const int desca[9],
+                                       int* info) DLAF_NOEXCEPT;
+DLAF_EXTERN_C int dlaf_mi355x_triangular_inverse_c(int context, char uplo, char diag, dlaf_complex_c* a,
+                                                   struct DLAF_descriptor desca) DLAF_NOEXCEPT;
+DLAF_EXTERN_C int dlaf_mi355x_inverse_from_cholesky_factor_c(int context, char uplo, dlaf_complex_c* a,
+                                                             struct DLAF_descriptor desca) DLAF_NOEXCEPT;
+DLAF_EXTERN_C void dlaf_mi355x_pctrtri(char uplo, char diag, int n, dlaf_complex_c* a, int ia, int ja, const int desca[9],
+                                       int* info) DLAF_NOEXCEPT;
+DLAF_EXTERN_C void dlaf_mi355x_pcpotri(char uplo, int n, dlaf_complex_c* a, int ia, int ja, const int desca[9],
+                                       int* info) DLAF_NOEXCEPT;
+DLAF_EXTERN_C int dlaf_mi355x_triangular_inverse_z(int context, char uplo, char diag, dlaf_complex_z* a,
+                                                   struct DLAF_descriptor desca) DLAF_NOEXCEPT;
+DLAF_EXTERN_C int dlaf_mi355x_inverse_from_cholesky_factor_z(int context, char uplo, dlaf_complex_z* a,
+                                                             struct DLAF_descriptor desca) DLAF_NOEXCEPT;
+DLAF_EXTERN_C void dlaf_mi355x_pztrtri(char uplo, char diag, int n, dlaf_complex_z* a, int ia, int ja, const int desca[9],
+                                       int* info) DLAF_NOEXCEPT;
+DLAF_EXTERN_C void dlaf_mi355x_pzpotri(char uplo, int n, dlaf_complex_z* a, int ia, int ja, const int desca[9],
+                                       int* info) DLAF_NOEXCEPT;
+/* the same on a device-resident matrix (uplo must be the one it was created with) */
+DLAF_EXTERN_C int dlaf_mi355x_triangular_inverse_device(char uplo, char diag, dlaf_mi355x_matrix_t m) DLAF_NOEXCEPT;
+DLAF_EXTERN_C int dlaf_mi355x_inverse_from_cholesky_factor_device(char uplo, dlaf_mi355x_matrix_t m) DLAF_NOEXCEPT;
+/* Device time (ms, HIP events on the compute stream; relayout and PCIe staging excluded) of the last of these calls on
+ * this process and the whole-grid flops it stands for: n^3 / 3 for the triangular inverse, as much again for the
+ * product (x 4 for complex types). */
+DLAF_EXTERN_C int dlaf_mi355x_inverse_profile(double* ms, double* flops) DLAF_NOEXCEPT;
+/* index arithmetic of the two sweeps (no GPU needed).  plan: out = {local diagonal tiles, first global one, global
+ * step, il0, jl0, il step, jl step, extent of the last, workspace tiles}; step k: out = {owner row, owner column, first
+ * local row below k, local rows before k, local columns before k, local row of k or -1, local column of k or -1}. */
+DLAF_EXTERN_C int dlaf_mi355x_inverse_plan(long n, int nb, int nprow, int npcol, int myrow, int mycol, int isrc,
+                                           int jsrc, long out[9]) DLAF_NOEXCEPT;
+DLAF_EXTERN_C int dlaf_mi355x_inverse_step(long n, int nb, int nprow, int npcol, int myrow, int mycol, int isrc,
+                                           int jsrc, long k, long out[7]) DLAF_NOEXCEPT;
+
 /* ---- index helpers (no GPU needed) -------------------------------------------------------------- */
 DLAF_EXTERN_C int dlaf_mi355x_dist_owner(long global_tile, int grid_size, int src_rank) DLAF_NOEXCEPT;
 DLAF_EXTERN_C long dlaf_mi355x_dist_local_tile(long global_tile, int grid_size, int rank, int src_rank) DLAF_NOEXCEPT;

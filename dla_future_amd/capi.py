@@ -38,6 +38,13 @@ class UpdateDesc(C.Structure):
                  ("persistent", C.c_long), ("exclusive", C.c_long), ("bulk_slots", C.c_long)])
 
 
+class TrsmDesc(C.Structure):
+    """struct dlaf_mi355x_trsm_desc (include/dlaf_mi355x/dlaf_mi355x.h): one launch of the panel TRSM."""
+    _fields_ = ([(n, C.c_long) for n in ("b_elems", "l_elems", "w_elems", "b_off", "l_off", "w_off", "b_ts")] +
+                [(n, C.c_int) for n in ("ldb", "il0", "il1", "pr", "ri", "nb", "nt", "last_rows", "ldl", "n", "upper",
+                                        "prio", "info", "winv_source", "unit", "path", "vec", "info_out")])
+
+
 BCAST_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_size_t)
 BARRIER_FN = C.CFUNCTYPE(C.c_int, C.c_void_p)
 
@@ -231,6 +238,10 @@ SIGNATURES = {
     "dlaf_mi355x_update_direct_c": (_i, [C.POINTER(UpdateDesc), _vp, _vp, _vp, _vp, _vp, _vp]),
     "dlaf_mi355x_update_direct_z": (_i, [C.POINTER(UpdateDesc), _vp, _vp, _vp, _vp, _vp, _vp]),
     "dlaf_mi355x_update_bulk_slots": (_l, [_ch]),
+    "dlaf_mi355x_trsm_direct_s": (_i, [C.POINTER(TrsmDesc), _vp, _vp, _vp]),
+    "dlaf_mi355x_trsm_direct_d": (_i, [C.POINTER(TrsmDesc), _vp, _vp, _vp]),
+    "dlaf_mi355x_trsm_direct_c": (_i, [C.POINTER(TrsmDesc), _vp, _vp, _vp]),
+    "dlaf_mi355x_trsm_direct_z": (_i, [C.POINTER(TrsmDesc), _vp, _vp, _vp]),
     "dlaf_mi355x_dist_owner": (_i, [_l, _i, _i]),
     "dlaf_mi355x_dist_local_tile": (_l, [_l, _i, _i, _i]),
     "dlaf_mi355x_dist_next_local_tile": (_l, [_l, _i, _i, _i]),

@@ -667,3 +667,37 @@ def update_direct(c: np.ndarray, a: np.ndarray, b: np.ndarray, *, a2: np.ndarray
     if r != 0:
         raise ValueError(f"dlaf_mi355x_update_direct_{type_char(c.dtype)} refused the launch ({r})")
     return int(d.persistent), int(d.exclusive), again
+
+
+TRSM_PATHS = ("strips", "rows-256", "rows-128", "rows-z")
+WINV_SOURCES = {"invert_diag_blocks": 0, "potrf_diag": 1, "caller": 2}
+
+
+def trsm_direct(b: np.ndarray, l: np.ndarray, winv: np.ndarray, *, winv_source: str = "invert_diag_blocks",
+                offsets=(0, 0, 0), **fields):
+    """ONE launch of the panel TRSM (TrsmArgs of csrc/device/device_api.hpp) on flat host arrays.
+
+    `b`, `l`, `winv` are one-dimensional arrays of the same dtype holding the operands as the kernel addresses them;
+    `fields` are the fields of struct dlaf_mi355x_trsm_desc (strides and leading dimensions in elements); `offsets` are
+    the element offsets of (b, l, winv) into their device allocations.  `winv_source` says who fills winv on the
+    device: launch_invert_diag_blocks, a per-block loop of launch_potrf_diag(factor = false), or the caller's array.
+    `b` and `winv` come back as the device left them.  Returns (path, vec, info): the kernel trsm_path chose (one of
+    TRSM_PATHS), whether the strips kernel may use its 16-byte loaders, and the device info word after the launches."""
+    from .capi import TrsmDesc
+    for x in (b, l, winv):
+        if x is None or x.ndim != 1 or x.dtype != b.dtype or not x.flags.c_contiguous:
+            raise ValueError("trsm_direct takes flat contiguous arrays of one dtype")
+    d = TrsmDesc()
+    names = {n for n, _ in TrsmDesc._fields_}
+    for k, v in fields.items():
+        if k not in names:
+            raise TypeError(f"trsm_direct: unknown field {k}")
+        setattr(d, k, v)
+    d.winv_source = WINV_SOURCES[winv_source]
+    d.b_elems, d.l_elems, d.w_elems = b.size, l.size, winv.size
+    d.b_off, d.l_off, d.w_off = offsets
+    fn = getattr(lib(), "dlaf_mi355x_trsm_direct_" + type_char(b.dtype))
+    r = fn(C.byref(d), _ptr(b), _ptr(l), _ptr(winv))
+    if r != 0:
+        raise ValueError(f"dlaf_mi355x_trsm_direct_{type_char(b.dtype)} refused the launch ({r})")
+    return TRSM_PATHS[d.path], bool(d.vec), int(d.info_out)

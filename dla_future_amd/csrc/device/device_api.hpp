@@ -95,7 +95,8 @@ long update_exclusive_round();
 // Panel TRSM (tile::trsm Right/Lower/ConjTrans/NonUnit of a whole panel in ONE launch,
 // impl.h:56-67):   X(il) = B(il) * L^-H for local tiles il in [il0, il1), in place.
 // L: n x n lower triangular (ldl); winv: ceil(n/64) inverted diagonal blocks of L, block j is a
-// dense 64 x 64 column-major array at winv + j*64*64 (lower triangle valid, rest zero).
+// dense 64 x 64 column-major array at winv + j*64*64 (lower triangle valid, rest zero); winv is 16-byte aligned (every
+// kernel reads it with 16-byte loads).  Which kernel runs: trsm_path.hpp.
 template <class T>
 struct TrsmArgs {
   T* b;

@@ -10,12 +10,11 @@
 // "inverted diagonal block" scheme vendor trsm uses).  One read of B, one write of X per strip:
 // algorithmic HBM bytes = (n^2/2 + 2 rows n) sizeof(T) per tile -- this is the kernel whose
 // achieved GB/s is reported next to its n^2 rows flops.
-#include <cstdlib>
-#include <cstring>
 #include <type_traits>
 
 #include "device_api.hpp"
 #include "mma_core.hpp"
+#include "trsm_path.hpp"
 
 namespace dlaf_mi355x {
 
@@ -474,62 +473,31 @@ __global__ __launch_bounds__(kThreads, (TrsmRowsCfg<NW, ST>::WAVES_PER_SIMD)) vo
 #include "trsm_rows_z.hpp"
 namespace dlaf_mi355x {
 
-template <class T>
-static bool aligned16(const void* ptr, long stride_elems) {
-  return (reinterpret_cast<uintptr_t>(ptr) % 16 == 0) && ((stride_elems * (long) sizeof(T)) % 16 == 0);
-}
-
-// tuning knob DLAF_MI355X_TRSM=strips selects the strips kernel everywhere (A/B runs, fallback)
-static bool trsm_rows_enabled() {
-  static const bool on = [] {
-    const char* e = std::getenv("DLAF_MI355X_TRSM");
-    return !(e && std::strcmp(e, "strips") == 0);
-  }();
-  return on;
-}
-
+// which kernel runs: trsm_path.hpp (plain host code, swept on the CPU by tests/trsm_path/sweep.cpp)
 template <class T>
 void launch_trsm(const TrsmArgs<T>& a, hipStream_t stream) {
   using Cfg = typename TrsmCfg<T>::type;
   if (a.il1 <= a.il0 || a.n <= 0 || a.nb <= 0)
     return;
-  const bool vec = aligned16<T>(a.b, a.ldb) && aligned16<T>(a.b, a.b_ts) && aligned16<T>(a.l, a.ldl);
-  if constexpr (std::is_same<T, double>::value) {
-    // row-owner kernel: whole 64-row strips, n a multiple of the macro width, 16-byte aligned operands
-    // (a 512-column macro block -- 256 accumulator registers per lane -- does not survive the register
-    // allocator: spills inside the loops; 256 columns run at two waves per SIMD without any)
-    constexpr int NW = 256;
-    if (vec && !a.upper && trsm_rows_enabled() && a.nb % 64 == 0 && a.last_rows % 64 == 0 && a.n % NW == 0 &&
-        aligned16<T>(a.winv, 0)) {
-      const int spt = a.nb / 64;
-      const long grid = (long) (a.il1 - a.il0) * spt;
-      hipLaunchKernelGGL((trsm_rows_kernel<NW, 2>), dim3((unsigned) grid), dim3(kThreads), (TrsmRowsCfg<NW, 2>::LDS_BYTES),
-                         stream, a, spt);
-      return;
+  const TrsmChoice ch = trsm_path<(int) sizeof(T), TypeInfo<T>::is_complex>(a);
+  if (ch.path != TrsmPath::strips) {
+    // row-owner kernels: one workgroup per 64-row strip
+    const int spt = a.nb / 64;
+    const long grid = (long) (a.il1 - a.il0) * spt;
+    if constexpr (std::is_same<T, double>::value) {
+      if (ch.path == TrsmPath::rows256)
+        hipLaunchKernelGGL((trsm_rows_kernel<256, 2>), dim3((unsigned) grid), dim3(kThreads),
+                           (TrsmRowsCfg<256, 2>::LDS_BYTES), stream, a, spt);
+      else
+        hipLaunchKernelGGL((trsm_rows_kernel<128, 2>), dim3((unsigned) grid), dim3(kThreads),
+                           (TrsmRowsCfg<128, 2>::LDS_BYTES), stream, a, spt);
     }
-    // the same kernel with 128-column macro blocks for the widths that are whole 128s but not whole 256s (the
-    // tall-skinny solves of the blocked panel factorization of reduction_to_band: n = band = 128)
-    constexpr int NW2 = 128;
-    if (vec && !a.upper && trsm_rows_enabled() && a.nb % 64 == 0 && a.last_rows % 64 == 0 && a.n % NW2 == 0 &&
-        aligned16<T>(a.winv, 0)) {
-      const int spt = a.nb / 64;
-      const long grid = (long) (a.il1 - a.il0) * spt;
-      hipLaunchKernelGGL((trsm_rows_kernel<NW2, 2>), dim3((unsigned) grid), dim3(kThreads), (TrsmRowsCfg<NW2, 2>::LDS_BYTES),
-                         stream, a, spt);
-      return;
-    }
+    if constexpr (std::is_same<T, cdouble>::value)
+      hipLaunchKernelGGL((trsm_rows_z_kernel<128, 3>), dim3((unsigned) grid), dim3(kThreads),
+                         (TrsmRowsZCfg<128, 3>::LDS_BYTES), stream, a, spt);
+    return;
   }
-  if constexpr (std::is_same<T, cdouble>::value) {
-    constexpr int NW = 128;
-    if (vec && !a.upper && trsm_rows_enabled() && a.nb % 64 == 0 && a.last_rows % 64 == 0 && a.n % NW == 0 &&
-        aligned16<T>(a.winv, 0)) {
-      const int spt = a.nb / 64;
-      const long grid = (long) (a.il1 - a.il0) * spt;
-      hipLaunchKernelGGL((trsm_rows_z_kernel<NW, 3>), dim3((unsigned) grid), dim3(kThreads),
-                         (TrsmRowsZCfg<NW, 3>::LDS_BYTES), stream, a, spt);
-      return;
-    }
-  }
+  const bool vec = ch.vec;
   const int spt = (a.nb + Cfg::BM - 1) / Cfg::BM;
   const long grid = (long) (a.il1 - a.il0) * spt;
   auto go = [&](auto vtag, auto utag) {

@@ -1263,6 +1263,17 @@ DLAF_UPDATE_DIRECT(d, double)
 DLAF_UPDATE_DIRECT(c, cfloat)
 DLAF_UPDATE_DIRECT(z, cdouble)
 #undef DLAF_UPDATE_DIRECT
+#define DLAF_TRSM_DIRECT(letter, DT)                                                                              \
+  int dlaf_mi355x_trsm_direct_##letter(dlaf_mi355x_trsm_desc* d, void* b, const void* l, void* winv) noexcept {   \
+    if (!d || !b || !l || !winv)                                                                                   \
+      return -3;                                                                                                   \
+    return trsm_direct<DT>(*d, b, l, winv);                                                                        \
+  }
+DLAF_TRSM_DIRECT(s, float)
+DLAF_TRSM_DIRECT(d, double)
+DLAF_TRSM_DIRECT(c, cfloat)
+DLAF_TRSM_DIRECT(z, cdouble)
+#undef DLAF_TRSM_DIRECT
 long dlaf_mi355x_update_bulk_slots(char type) noexcept {
   long slots = 0;
   const int r = dispatch_api_type(type, [&](auto* tag) {

@@ -17,6 +17,7 @@
 #include "distribution.hpp"
 
 struct dlaf_mi355x_update_desc;
+struct dlaf_mi355x_trsm_desc;
 
 namespace dlaf_mi355x {
 
@@ -281,6 +282,10 @@ int update_direct(::dlaf_mi355x_update_desc& d, void* c, const void* a, const vo
                   void* c_again);
 template <class T>
 long update_bulk_slots();
+// one launch of the panel TRSM and the preparation of its inverted diagonal blocks, every field given by the caller
+// (trsm_direct.cpp)
+template <class T>
+int trsm_direct(::dlaf_mi355x_trsm_desc& d, void* b, const void* l, void* winv);
 
 // Communication self-test of a grid: every member of every row / column communicator broadcasts a
 // coordinate-dependent pattern in turn (in place, out of place and grouped, the three forms the

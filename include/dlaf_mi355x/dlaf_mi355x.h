@@ -553,6 +553,38 @@ DLAF_EXTERN_C int dlaf_mi355x_inverse_plan(long n, int nb, int nprow, int npcol,
 DLAF_EXTERN_C int dlaf_mi355x_inverse_step(long n, int nb, int nprow, int npcol, int myrow, int mycol, int isrc,
                                            int jsrc, long k, long out[7]) DLAF_NOEXCEPT;
 
+/* ---- the panel TRSM, one launch (host operands) -------------------------------------------------- */
+/* Every field of one launch of the panel TRSM (the kernel's contract: TrsmArgs in csrc/device/device_api.hpp) and the
+ * preparation of the inverted diagonal blocks that feeds it.  The entry uploads the operands, prepares winv, launches
+ * launch_trsm ONCE and downloads the whole B and winv buffers.  Strides, leading dimensions, *_elems and *_off are in
+ * elements of the type; an operand's host array of *_elems elements is placed *_off elements into a fresh device
+ * allocation (off = 1: a base that is not 16-byte aligned; winv must stay 16-byte aligned). */
+struct dlaf_mi355x_trsm_desc {
+  long b_elems, l_elems, w_elems;
+  long b_off, l_off, w_off;
+  long b_ts;
+  int ldb;
+  int il0, il1, pr, ri;
+  int nb, nt, last_rows;
+  int ldl, n;
+  int upper, prio;
+  int info; /* value of the device info word before the launches */
+  /* where winv comes from: 0 launch_invert_diag_blocks(l, ldl, n, upper, unit); 1 one launch_potrf_diag(factor = false,
+   * upper, unit) per 64 x 64 diagonal block; 2 the caller's winv array as it is */
+  int winv_source;
+  int unit; /* sources 0 and 1: the diagonal of l is taken as 1 and not read */
+  /* out */
+  int path;     /* the kernel trsm_path chose: 0 strips, 1 rows-256, 2 rows-128, 3 rows-z */
+  int vec;      /* strips: the 16-byte loaders */
+  int info_out; /* the device info word after the launches */
+};
+/* b (b_elems) and winv (w_elems) are overwritten by the device buffers as the launches left them.
+ * Returns 0, or -3 when a field would make a kernel touch memory outside an operand (nothing is launched). */
+DLAF_EXTERN_C int dlaf_mi355x_trsm_direct_s(struct dlaf_mi355x_trsm_desc* d, void* b, const void* l, void* winv) DLAF_NOEXCEPT;
+DLAF_EXTERN_C int dlaf_mi355x_trsm_direct_d(struct dlaf_mi355x_trsm_desc* d, void* b, const void* l, void* winv) DLAF_NOEXCEPT;
+DLAF_EXTERN_C int dlaf_mi355x_trsm_direct_c(struct dlaf_mi355x_trsm_desc* d, void* b, const void* l, void* winv) DLAF_NOEXCEPT;
+DLAF_EXTERN_C int dlaf_mi355x_trsm_direct_z(struct dlaf_mi355x_trsm_desc* d, void* b, const void* l, void* winv) DLAF_NOEXCEPT;
+
 /* ---- index helpers (no GPU needed) -------------------------------------------------------------- */
 DLAF_EXTERN_C int dlaf_mi355x_dist_owner(long global_tile, int grid_size, int src_rank) DLAF_NOEXCEPT;
 DLAF_EXTERN_C long dlaf_mi355x_dist_local_tile(long global_tile, int grid_size, int rank, int src_rank) DLAF_NOEXCEPT;

@@ -27,7 +27,7 @@ from .cholesky import (DeviceMatrix, GeneralDeviceMatrix, Grid, cholesky_factori
                        triangular_inverse, inverse_from_cholesky_factor, pxtrtri, pxpotri, inverse_profile,
                        update_launch_stats, multiplication_profile, pxtrmm, triangular_multiplication,
                        triangular_multiplication_device, hermitian_multiplication, hermitian_multiplication_device,
-                       pxhemm, update_direct, update_bulk_slots, trsm_direct)
+                       pxhemm, update_direct, update_bulk_slots, trsm_direct, potrf_direct)
 from . import distribution  # noqa: F401
 from .eigensolver import (band_to_tridiagonal, bt_band_to_tridiagonal, bt_reduction_to_band,  # noqa: F401
                           bt_reduction_to_band_device, eigensolver_min_band, eigensolver_profile, get_band_size, hermitian_eigensolver,
@@ -43,4 +43,4 @@ __all__ = ["band_to_tridiagonal", "bt_band_to_tridiagonal", "eigensolver_profile
            "inverse_from_cholesky_factor", "pxtrtri", "pxpotri", "inverse_profile", "type_char", "version",
            "triangular_multiplication", "triangular_multiplication_device", "pxtrmm", "multiplication_profile",
            "hermitian_multiplication", "hermitian_multiplication_device", "pxhemm", "update_direct", "update_bulk_slots",
-           "trsm_direct"]
+           "trsm_direct", "potrf_direct"]

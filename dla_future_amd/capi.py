@@ -45,6 +45,13 @@ class TrsmDesc(C.Structure):
                                         "prio", "info", "winv_source", "unit", "path", "vec", "info_out")])
 
 
+class PotrfDesc(C.Structure):
+    """struct dlaf_mi355x_potrf_desc (include/dlaf_mi355x/dlaf_mi355x.h): one factorization of one diagonal tile."""
+    _fields_ = ([(n, C.c_long) for n in ("t_elems", "w_elems", "t_off", "w_off")] +
+                [(n, C.c_int) for n in ("kb", "ld", "info", "info_base", "path", "sync_zeroed_by", "count_strips",
+                                        "info_out", "t_before_changed", "w_before_changed")])
+
+
 BCAST_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_size_t)
 BARRIER_FN = C.CFUNCTYPE(C.c_int, C.c_void_p)
 
@@ -242,6 +249,10 @@ SIGNATURES = {
     "dlaf_mi355x_trsm_direct_d": (_i, [C.POINTER(TrsmDesc), _vp, _vp, _vp]),
     "dlaf_mi355x_trsm_direct_c": (_i, [C.POINTER(TrsmDesc), _vp, _vp, _vp]),
     "dlaf_mi355x_trsm_direct_z": (_i, [C.POINTER(TrsmDesc), _vp, _vp, _vp]),
+    "dlaf_mi355x_potrf_direct_s": (_i, [C.POINTER(PotrfDesc), _vp, _vp]),
+    "dlaf_mi355x_potrf_direct_d": (_i, [C.POINTER(PotrfDesc), _vp, _vp]),
+    "dlaf_mi355x_potrf_direct_c": (_i, [C.POINTER(PotrfDesc), _vp, _vp]),
+    "dlaf_mi355x_potrf_direct_z": (_i, [C.POINTER(PotrfDesc), _vp, _vp]),
     "dlaf_mi355x_dist_owner": (_i, [_l, _i, _i]),
     "dlaf_mi355x_dist_local_tile": (_l, [_l, _i, _i, _i]),
     "dlaf_mi355x_dist_next_local_tile": (_l, [_l, _i, _i, _i]),

@@ -701,3 +701,36 @@ def trsm_direct(b: np.ndarray, l: np.ndarray, winv: np.ndarray, *, winv_source: 
     if r != 0:
         raise ValueError(f"dlaf_mi355x_trsm_direct_{type_char(b.dtype)} refused the launch ({r})")
     return TRSM_PATHS[d.path], bool(d.vec), int(d.info_out)
+
+
+POTRF_PATHS = {"coop": 0, "chain": 1}
+
+
+def potrf_direct(tile: np.ndarray, winv: np.ndarray, *, path: str = "coop", offsets=(0, 0), **fields):
+    """ONE factorization of one kb x kb diagonal tile (launch_potrf_coop, or the chain of launch_potrf_diag, launch_trsm
+    and launch_update per 64 columns: csrc/device/device_api.hpp) on flat host arrays.
+
+    `tile` and `winv` are one-dimensional arrays of the same dtype holding the buffers as the kernels address them;
+    `fields` are the fields of struct dlaf_mi355x_potrf_desc (kb, ld, info, info_base, sync_zeroed_by, count_strips);
+    `offsets` are the element offsets of (tile, winv) into their device allocations; the elements in front of each
+    array hold a byte pattern on the device.  Both arrays come back as the device left them.  Returns (info, changed):
+    the device info word after the launches, and the number of bytes in front of the two arrays that the launches
+    changed (0 unless a kernel stored in front of a buffer)."""
+    from .capi import PotrfDesc
+    for x in (tile, winv):
+        if x is None or x.ndim != 1 or x.dtype != tile.dtype or not x.flags.c_contiguous:
+            raise ValueError("potrf_direct takes flat contiguous arrays of one dtype")
+    d = PotrfDesc()
+    names = {n for n, _ in PotrfDesc._fields_}
+    for k, v in fields.items():
+        if k not in names:
+            raise TypeError(f"potrf_direct: unknown field {k}")
+        setattr(d, k, v)
+    d.path = POTRF_PATHS[path]
+    d.t_elems, d.w_elems = tile.size, winv.size
+    d.t_off, d.w_off = offsets
+    fn = getattr(lib(), "dlaf_mi355x_potrf_direct_" + type_char(tile.dtype))
+    r = fn(C.byref(d), _ptr(tile), _ptr(winv))
+    if r != 0:
+        raise ValueError(f"dlaf_mi355x_potrf_direct_{type_char(tile.dtype)} refused the launch ({r})")
+    return int(d.info_out), int(d.t_before_changed) + int(d.w_before_changed)

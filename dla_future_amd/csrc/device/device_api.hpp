@@ -206,7 +206,10 @@ void launch_diag_zero_scan(const TileBatch<const T>& tiles, long k0, long kstep,
 // Diagonal block factorization + inversion (one workgroup):  a (jb x jb, lda, jb <= 64) is
 // overwritten by its lower Cholesky factor (strict upper part untouched); winv_block (64 x 64,
 // ld 64) receives inv(L) (lower, zero elsewhere).  On a non-positive pivot at column c the
-// kernel stores info_base + c + 1 into *info (first failure wins) and leaves garbage.
+// kernel stores info_base + c + 1 into *info (first failure wins) and leaves a and winv_block as they were.
+// *info != 0 on entry: nothing is read or written (a, winv_block and *info stay as they are).  The diagonal of a is
+// taken as real when factoring: its imaginary part is ignored, and the diagonal of the factor is stored with imaginary
+// part 0.
 // factor == false: a already holds a triangular matrix; only winv_block is produced.  In that mode
 // upper: a is upper triangular and winv_block receives inv(a) (upper); unit: the diagonal of a is taken as 1.
 template <class T>
@@ -223,6 +226,17 @@ void launch_invert_diag_blocks(const T* tile, int ld, int kb, T* winv, int* info
 // lower Cholesky factor in place + the ceil(kb/64) inverted diagonal blocks in winv.  sync: device
 // scratch of at least G + G*G unsigned, G = ceil(kb/64) (zeroed by the launcher on the stream):
 // potrf_coop_sync_words(kb).
+// Only the lower triangle of tile[0:kb, 0:kb] is read or written (the diagonal is taken as real and comes back with
+// imaginary part 0); winv block j has the strict upper triangle and every row and column past the block's extent zero.
+// A non-positive or NaN pivot at column c stores info_base + c + 1 into *info (first failure wins): the 64-column
+// blocks left of the failing one, and their winv blocks, are final; the rest of the triangle is garbage.
+// What an early exit leaves in winv differs between the two forms of the tile POTRF, and callers that broadcast winv
+// whatever happened rely on it:
+//   * this launch: every strip that leaves without factoring its diagonal block -- *info != 0 on entry (all
+//     ceil(kb/64) strips: the tile and *info stay as they are), the failing strip and every strip below it, an expired
+//     wait -- fills ITS 64 x 64 block of winv with NaN, real and imaginary parts;
+//   * the chain (launch_potrf_diag + launch_trsm + launch_update per 64 columns): those blocks of winv are left as
+//     they were; with *info != 0 on entry the tile, winv and *info are all untouched.
 template <class T>
 void launch_potrf_coop(T* tile, int ld, int kb, T* winv, int* info, int info_base, unsigned* sync,
                        hipStream_t stream, bool sync_is_zero = false, bool count_strips = true);

@@ -1274,6 +1274,17 @@ DLAF_TRSM_DIRECT(d, double)
 DLAF_TRSM_DIRECT(c, cfloat)
 DLAF_TRSM_DIRECT(z, cdouble)
 #undef DLAF_TRSM_DIRECT
+#define DLAF_POTRF_DIRECT(letter, DT)                                                                             \
+  int dlaf_mi355x_potrf_direct_##letter(dlaf_mi355x_potrf_desc* d, void* tile, void* winv) noexcept {             \
+    if (!d || !tile || !winv)                                                                                      \
+      return -3;                                                                                                   \
+    return potrf_direct<DT>(*d, tile, winv);                                                                       \
+  }
+DLAF_POTRF_DIRECT(s, float)
+DLAF_POTRF_DIRECT(d, double)
+DLAF_POTRF_DIRECT(c, cfloat)
+DLAF_POTRF_DIRECT(z, cdouble)
+#undef DLAF_POTRF_DIRECT
 long dlaf_mi355x_update_bulk_slots(char type) noexcept {
   long slots = 0;
   const int r = dispatch_api_type(type, [&](auto* tag) {

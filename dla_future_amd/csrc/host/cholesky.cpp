@@ -24,16 +24,18 @@ static bool potrf_use_chain() {
   return chain;
 }
 
+// One resident cooperative launch (kernels_potrf_coop.hip).  The factorization passes sync_is_zero (it zeroed sync
+// itself) and count_strips: the strips register for the POTRF yield, on one process and on grids.
 template <class T>
-void potrf_tile(T* t, int ld, int kb, T* winv, int* info, int info_base, unsigned* sync, hipStream_t s) {
+void potrf_tile_coop(T* t, int ld, int kb, T* winv, int* info, int info_base, unsigned* sync, hipStream_t s,
+                     bool sync_is_zero, bool count_strips) {
+  launch_potrf_coop(t, ld, kb, winv, info, info_base, sync, s, sync_is_zero, count_strips);
+}
+
+// The multi-launch form: diagonal block kernel + TRSM kernel + update kernel per 64 columns.
+template <class T>
+void potrf_tile_chain(T* t, int ld, int kb, T* winv, int* info, int info_base, hipStream_t s) {
   constexpr int JB = kDiagBlock;
-  if (!potrf_use_chain()) {
-    // one resident cooperative launch (kernels_potrf_coop.hip); DLAF_MI355X_POTRF=chain selects the
-    // multi-launch form below (diagonal block kernel + TRSM kernel + update kernel per 64 columns).
-    // The strips register for the POTRF yield, on one process and on grids.
-    launch_potrf_coop(t, ld, kb, winv, info, info_base, sync, s, /* sync_is_zero */ true, /* count_strips */ true);
-    return;
-  }
   for (int j0 = 0; j0 < kb; j0 += JB) {
     const int jb = std::min(JB, kb - j0);
     T* djj = t + j0 + (size_t) j0 * ld;
@@ -81,6 +83,15 @@ void potrf_tile(T* t, int ld, int kb, T* winv, int* info, int info_base, unsigne
     ua.info = info;
     launch_update(ua, s, 2);
   }
+}
+
+// DLAF_MI355X_POTRF=chain selects the multi-launch form, anything else the cooperative launch.
+template <class T>
+void potrf_tile(T* t, int ld, int kb, T* winv, int* info, int info_base, unsigned* sync, hipStream_t s) {
+  if (!potrf_use_chain())
+    potrf_tile_coop(t, ld, kb, winv, info, info_base, sync, s, /* sync_is_zero */ true, /* count_strips */ true);
+  else
+    potrf_tile_chain(t, ld, kb, winv, info, info_base, s);
 }
 
 // ------------------------------------------------------------------------------- transposed panel
@@ -816,7 +827,9 @@ void DeviceMatrix<T>::factorize_async() {
   template void DeviceMatrix<T>::factorize_async();                                                 \
   template int DeviceMatrix<T>::bcast_transposed_panel(Transport*, CommAxis, const T*, long, long, T*, \
                                                        hipStream_t, int&, long&);                   \
-  template void potrf_tile<T>(T*, int, int, T*, int*, int, unsigned*, hipStream_t);
+  template void potrf_tile<T>(T*, int, int, T*, int*, int, unsigned*, hipStream_t);                  \
+  template void potrf_tile_coop<T>(T*, int, int, T*, int*, int, unsigned*, hipStream_t, bool, bool); \
+  template void potrf_tile_chain<T>(T*, int, int, T*, int*, int, hipStream_t);
 INST(float)
 INST(double)
 INST(cfloat)

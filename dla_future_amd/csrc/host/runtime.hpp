@@ -18,6 +18,7 @@
 
 struct dlaf_mi355x_update_desc;
 struct dlaf_mi355x_trsm_desc;
+struct dlaf_mi355x_potrf_desc;
 
 namespace dlaf_mi355x {
 
@@ -265,6 +266,13 @@ struct DeviceMatrix : MatrixBase {
 // winv (cholesky.cpp).  sync: potrf_coop_sync_words(kb) words the caller has zeroed on the stream.
 template <class T>
 void potrf_tile(T* t, int ld, int kb, T* winv, int* info, int info_base, unsigned* sync, hipStream_t s);
+// The two forms potrf_tile chooses between by DLAF_MI355X_POTRF: one cooperative launch (sync_is_zero / count_strips as
+// in launch_potrf_coop; potrf_tile passes true, true), or diagonal block + TRSM + update launches per 64 columns.
+template <class T>
+void potrf_tile_coop(T* t, int ld, int kb, T* winv, int* info, int info_base, unsigned* sync, hipStream_t s,
+                     bool sync_is_zero, bool count_strips);
+template <class T>
+void potrf_tile_chain(T* t, int ld, int kb, T* winv, int* info, int info_base, hipStream_t s);
 
 // single-tile operations with host operands (tests of the tile kernels through the C ABI)
 template <class T>
@@ -286,6 +294,9 @@ long update_bulk_slots();
 // (trsm_direct.cpp)
 template <class T>
 int trsm_direct(::dlaf_mi355x_trsm_desc& d, void* b, const void* l, void* winv);
+// one factorization of one diagonal tile on either path, every field given by the caller (potrf_direct.cpp)
+template <class T>
+int potrf_direct(::dlaf_mi355x_potrf_desc& d, void* tile, void* winv);
 
 // Communication self-test of a grid: every member of every row / column communicator broadcasts a
 // coordinate-dependent pattern in turn (in place, out of place and grouped, the three forms the

@@ -585,6 +585,35 @@ DLAF_EXTERN_C int dlaf_mi355x_trsm_direct_d(struct dlaf_mi355x_trsm_desc* d, voi
 DLAF_EXTERN_C int dlaf_mi355x_trsm_direct_c(struct dlaf_mi355x_trsm_desc* d, void* b, const void* l, void* winv) DLAF_NOEXCEPT;
 DLAF_EXTERN_C int dlaf_mi355x_trsm_direct_z(struct dlaf_mi355x_trsm_desc* d, void* b, const void* l, void* winv) DLAF_NOEXCEPT;
 
+/* ---- the tile POTRF, one factorization (host operands) --------------------------------------------- */
+/* Every field of one factorization of ONE kb x kb diagonal tile (the contract: launch_potrf_coop and launch_potrf_diag in
+ * csrc/device/device_api.hpp).  The entry uploads the tile and winv buffers and *info, factors the tile once on the
+ * chosen path and downloads both buffers whole.  ld, *_elems and *_off are in elements of the type; a host array of
+ * *_elems elements is placed *_off elements into a fresh device allocation (t_off = 1: a tile that is not 16-byte
+ * aligned; winv must stay 16-byte aligned).  The *_off elements in front of it are filled with a byte pattern before the
+ * launches and looked at again afterwards. */
+struct dlaf_mi355x_potrf_desc {
+  long t_elems, w_elems;
+  long t_off, w_off;
+  int kb, ld;
+  int info;      /* value of the device info word before the launches */
+  int info_base; /* a failing column c reports info_base + c + 1 */
+  int path;      /* 0: the cooperative launch; 1: the chain (diagonal block + TRSM + update per 64 columns) */
+  /* path 0, who zeroes the hand-off words: 0 the launcher (sync_is_zero = false; the entry fills them with 0xFFFFFFFF
+   * first), 1 the entry (sync_is_zero = true) */
+  int sync_zeroed_by;
+  int count_strips; /* path 0: the strips register in the per-compute-unit table of the bulk update */
+  /* out */
+  int info_out; /* the device info word after the launches */
+  int t_before_changed, w_before_changed; /* bytes in front of the tile / winv buffer that the launches changed */
+};
+/* tile (t_elems) and winv (w_elems) are overwritten by the device buffers as the launches left them.
+ * Returns 0, or -3 when a field would make a kernel touch memory outside a buffer (nothing is launched). */
+DLAF_EXTERN_C int dlaf_mi355x_potrf_direct_s(struct dlaf_mi355x_potrf_desc* d, void* tile, void* winv) DLAF_NOEXCEPT;
+DLAF_EXTERN_C int dlaf_mi355x_potrf_direct_d(struct dlaf_mi355x_potrf_desc* d, void* tile, void* winv) DLAF_NOEXCEPT;
+DLAF_EXTERN_C int dlaf_mi355x_potrf_direct_c(struct dlaf_mi355x_potrf_desc* d, void* tile, void* winv) DLAF_NOEXCEPT;
+DLAF_EXTERN_C int dlaf_mi355x_potrf_direct_z(struct dlaf_mi355x_potrf_desc* d, void* tile, void* winv) DLAF_NOEXCEPT;
+
 /* ---- index helpers (no GPU needed) -------------------------------------------------------------- */
 DLAF_EXTERN_C int dlaf_mi355x_dist_owner(long global_tile, int grid_size, int src_rank) DLAF_NOEXCEPT;
 DLAF_EXTERN_C long dlaf_mi355x_dist_local_tile(long global_tile, int grid_size, int rank, int src_rank) DLAF_NOEXCEPT;

@@ -75,6 +75,133 @@ struct NoHook {
   __device__ __forceinline__ void operator()(int) const {}
 };
 
+// ---- the rotated slab (fp64, paired rows, 4 x 4 MFMA tiles per wave) -----------------------------------------------
+// A k-step of such a wave is 16 MFMAs out of four 16-byte fragment pairs: A0 = rows (0, 1), A1 = rows (2, 3),
+// B0 = columns (0, 1), B1 = columns (2, 3).  Read "all four pairs, wait for all, 16 MFMAs" (the generic loop of
+// mma_slab as hipcc compiles it) leaves the LDS latency of every step uncovered but for the 64 cycles of the previous
+// step's last MFMA.  Here the four quadrants (B pair x A pair, 4 MFMAs each) of a step run in serpentine order, and
+// the order of the A pairs alternates from step to step (F = the pair used first and last, S = the one between):
+//     Q1 (B0, F)   Q2 (B0, S) -> read B0'   Q3 (B1, S) -> read S'   Q4 (B1, F) -> read F', B1'
+//     next step: F := S', S := F'
+// so every pair is re-read into the registers it has just vacated, at least 4 MFMAs (256 cycles) before its first
+// use: 16 fragment registers, as before.  Every accumulator still receives its products in ascending k from the same
+// instruction with the same inputs: the results are bit for bit those of the generic loop.
+//
+// The reads are inline assembly because hipcc waits for ALL of its own LDS reads before the first MFMA of a step
+// (s_waitcnt lgkmcnt(0)), including the two issued a moment ago; the waits here are counted.  LDS reads return in
+// order, so with the issue order  B0, F, S, B1  of the pairs a step consumes, "lgkmcnt(2)" before Q1 leaves S and B1
+// in flight, "lgkmcnt(1)" before Q2 leaves B1, and before Q3 "lgkmcnt(1)" leaves the B0' issued after Q2 (0 in the
+// last step, which reads nothing).  Other LDS or scalar-memory operations of the wave in between only raise the
+// counter, i.e. make a wait stricter.  hipcc does not know when such a read lands: each wait names the pairs it
+// retires as "+v" operands, so no consumer can be scheduled above it, and the sched_barrier after each quadrant pins
+// the reads between the MFMAs.
+//
+// Invariants of the ring this slab is read from (a violation is a timing-dependent wrong result, not a crash):
+//  (i)   a wave's reads of a ring slot have all retired before it enters the barrier after which any wave may issue
+//        DMA (or stores) into that slot: the last step of the slab waits with lgkmcnt(0) before its third quadrant and
+//        reads nothing afterwards, so the slab returns with no read in flight, whatever the caller waits for;
+//  (ii)  no read of the next slab is issued before the barrier that follows every wave's vmcnt wait for that slab: the
+//        first read of a slab is the first statement of this function, which the caller reaches only past that barrier
+//        (asm volatile statements and the barrier keep their program order);
+//  (iii) when hipcc hoists that barrier in front of the MFMAs of the last quadrant (it may: no sched_barrier follows
+//        them), those MFMAs read registers only -- all four pairs were retired by (i).
+typedef double lds_pair_d __attribute__((ext_vector_type(2)));
+
+template <int OFF>
+__device__ __forceinline__ void lds_read_pair_async(lds_pair_d& v, unsigned addr) {
+  static_assert(OFF >= 0 && OFF < 65536 && OFF % 16 == 0, "ds_read_b128: 16-bit unsigned offset, 16-byte aligned");
+  asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(v) : "v"(addr), "i"(OFF) : "memory");
+}
+// at most N of this wave's LDS reads remain in flight afterwards; x (and y) are the pairs this retires
+template <int N>
+__device__ __forceinline__ void lds_wait_pairs(lds_pair_d& x, lds_pair_d& y) {
+  asm volatile("s_waitcnt lgkmcnt(%2)" : "+v"(x), "+v"(y) : "i"(N) : "memory");
+}
+template <int N>
+__device__ __forceinline__ void lds_wait_pairs(lds_pair_d& x) {
+  asm volatile("s_waitcnt lgkmcnt(%1)" : "+v"(x) : "i"(N) : "memory");
+}
+
+template <class Cfg>
+inline constexpr bool kRotatedSlab = Cfg::PAIRED && Cfg::TM == 4 && Cfg::TN == 4 && sizeof(typename Cfg::R) == 8 &&
+                                     (Cfg::BK / 4) % 2 == 0;
+
+// the 4 MFMAs of quadrant (B pair jp, A pair ip)
+template <class Cfg, bool NEG>
+__device__ __forceinline__ void mma_quadrant(Acc<Cfg>& acc, int jp, int ip, const lds_pair_d& b, const lds_pair_d& a) {
+#pragma unroll
+  for (int jj = 0; jj < 2; ++jj)
+#pragma unroll
+    for (int ii = 0; ii < 2; ++ii) {
+      auto& d = acc.re[2 * ip + ii][2 * jp + jj];
+      if constexpr (!NEG)
+        d = Mma<double>::mma(b[jj], a[ii], d);
+      else
+        d = Mma<double>::mma_neg(b[jj], a[ii], d);
+    }
+}
+
+// step K4 of the slab and, recursively, the ones after it.  On entry the reads of b0, a[F], a[S], b1 for this step
+// are in flight in that order (F = K4 odd ? 1 : 0, S = 1 - F).  hook(4 K4 + quadrant) keeps the 16 hook points of the
+// generic loop.
+template <class Cfg, bool NEG, int K4, class Hook>
+__device__ __forceinline__ void mma_slab_rotated_step(unsigned a_addr, unsigned b_addr, Acc<Cfg>& acc, lds_pair_d (&a)[2],
+                                                      lds_pair_d& b0, lds_pair_d& b1, Hook& hook) {
+  constexpr int NS = Cfg::BK / 4;
+  constexpr bool NEXT = K4 + 1 < NS;
+  constexpr int F = K4 & 1, S = 1 - F;
+  // byte offsets of step K4 + 1 from the lane's address of step 0 (image [k][ROWS], 4 k per step, 32 rows per pair)
+  constexpr int KN = NEXT ? K4 + 1 : 0;
+  constexpr int AOFF = 8 * (KN * 4 * Cfg::LDA), BOFF = 8 * (KN * 4 * Cfg::LDB);
+
+  hook(4 * K4 + 0);
+  lds_wait_pairs<2>(b0, a[F]);
+  mma_quadrant<Cfg, NEG>(acc, 0, F, b0, a[F]);
+  __builtin_amdgcn_sched_barrier(0);
+
+  hook(4 * K4 + 1);
+  lds_wait_pairs<1>(a[S]);
+  mma_quadrant<Cfg, NEG>(acc, 0, S, b0, a[S]);
+  if constexpr (NEXT)
+    lds_read_pair_async<BOFF>(b0, b_addr);
+  __builtin_amdgcn_sched_barrier(0);
+
+  hook(4 * K4 + 2);
+  lds_wait_pairs<NEXT ? 1 : 0>(b1);
+  mma_quadrant<Cfg, NEG>(acc, 1, S, b1, a[S]);
+  if constexpr (NEXT)
+    lds_read_pair_async<AOFF + 8 * 32 * S>(a[S], a_addr);
+  __builtin_amdgcn_sched_barrier(0);
+
+  hook(4 * K4 + 3);
+  mma_quadrant<Cfg, NEG>(acc, 1, F, b1, a[F]);
+  if constexpr (NEXT) {
+    lds_read_pair_async<AOFF + 8 * 32 * F>(a[F], a_addr);
+    lds_read_pair_async<BOFF + 8 * 32>(b1, b_addr);
+    __builtin_amdgcn_sched_barrier(0);
+    mma_slab_rotated_step<Cfg, NEG, K4 + 1>(a_addr, b_addr, acc, a, b0, b1, hook);
+  }
+}
+
+template <class Cfg, bool NEG, class Hook>
+__device__ __forceinline__ void mma_slab_rotated(const double* __restrict__ As, const double* __restrict__ Bs,
+                                                 Acc<Cfg>& acc, int wm, int wn, int lane, Hook& hook) {
+  static_assert(kRotatedSlab<Cfg> && Cfg::PAD == 0, "fp64, paired rows, 4 x 4 tiles, an even number of k-steps");
+  const int g = lane >> 4, c = lane & 15;
+  // LDS byte addresses of this lane's pair 0 at k-step 0: element [g][wave tile + 2 c]
+  const unsigned a_addr = (unsigned) (uintptr_t) (const __attribute__((address_space(3))) double*) As +
+                          8u * (unsigned) (g * Cfg::LDA + wm * Cfg::WM + 2 * c);
+  const unsigned b_addr = (unsigned) (uintptr_t) (const __attribute__((address_space(3))) double*) Bs +
+                          8u * (unsigned) (g * Cfg::LDB + wn * Cfg::WN + 2 * c);
+  lds_pair_d a[2], b0, b1;
+  lds_read_pair_async<0>(b0, b_addr);
+  lds_read_pair_async<0>(a[0], a_addr);
+  lds_read_pair_async<8 * 32>(a[1], a_addr);
+  lds_read_pair_async<8 * 32>(b1, b_addr);
+  __builtin_amdgcn_sched_barrier(0);
+  mma_slab_rotated_step<Cfg, NEG, 0>(a_addr, b_addr, acc, a, b0, b1, hook);
+}
+
 // hook(p) is called before each group of TM MFMAs (p = k4 * TN + j counts the groups of a slab): the
 // direct-to-LDS pipeline issues its loads of a later slab there, one at a time in the shadow of the MFMAs,
 // instead of as one block at the head of the iteration (8 x global_load_lds back to back keep the wave from
@@ -85,6 +212,10 @@ __device__ __forceinline__ void mma_slab(const typename Cfg::R* __restrict__ As,
                                          const typename Cfg::R* __restrict__ Bs, Acc<Cfg>& acc, int wm,
                                          int wn, int lane, Hook&& hook = Hook{}) {
   using R = typename Cfg::R;
+  if constexpr (kRotatedSlab<Cfg>) {
+    mma_slab_rotated<Cfg, NEG>(As, Bs, acc, wm, wn, lane, hook);
+    return;
+  }
   const int g = lane >> 4, c = lane & 15;
 #pragma unroll
   for (int k4 = 0; k4 < Cfg::BK / 4; ++k4) {

@@ -32,7 +32,8 @@ from . import distribution  # noqa: F401
 from .eigensolver import (band_to_tridiagonal, bt_band_to_tridiagonal, bt_reduction_to_band,  # noqa: F401
                           bt_reduction_to_band_device, eigensolver_min_band, eigensolver_profile, get_band_size, hermitian_eigensolver,
                           hermitian_generalized_eigensolver, red2band_panel_stats, red2band_profile, reduction_to_band,
-                          reduction_to_band_device, tridiagonal_eigensolver)
+                          reduction_to_band_device, tridiagonal_eigensolver, pxheevd_partial_spectrum,
+                          partial_spectrum_plan)
 
 __all__ = ["band_to_tridiagonal", "bt_band_to_tridiagonal", "eigensolver_profile", "hermitian_eigensolver",
            "hermitian_generalized_eigensolver", "tridiagonal_eigensolver", "bt_reduction_to_band", "bt_reduction_to_band_device", "get_band_size", "eigensolver_min_band", "red2band_profile",
@@ -43,4 +44,4 @@ __all__ = ["band_to_tridiagonal", "bt_band_to_tridiagonal", "eigensolver_profile
            "inverse_from_cholesky_factor", "pxtrtri", "pxpotri", "inverse_profile", "type_char", "version",
            "triangular_multiplication", "triangular_multiplication_device", "pxtrmm", "multiplication_profile",
            "hermitian_multiplication", "hermitian_multiplication_device", "pxhemm", "update_direct", "update_bulk_slots",
-           "trsm_direct", "potrf_direct"]
+           "trsm_direct", "potrf_direct", "pxheevd_partial_spectrum", "partial_spectrum_plan"]

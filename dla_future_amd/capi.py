@@ -69,6 +69,7 @@ def type_char(dtype) -> str:
 # every symbol the headers declare: name -> (restype, argtypes)
 _vp, _i, _l, _ch = C.c_void_p, C.c_int, C.c_long, C.c_char
 _IP = C.POINTER(C.c_int)
+_i64 = C.c_int64
 SIGNATURES = {
     # include/dlaf_c/init.h
     "dlaf_initialize": (None, [_i, C.POINTER(C.c_char_p), _i, C.POINTER(C.c_char_p)]),
@@ -228,6 +229,33 @@ SIGNATURES = {
     "dlaf_pzhegvd_factorized": (None, [_ch, _i, _vp, _i, _i, _IP, _vp, _i, _i, _IP, _vp, _vp, _i, _i, _IP, _IP]),
     "dlaf_mi355x_tridiagonal_eigensolver_s": (_i, [_i, _i, _vp, _vp, _vp, _vp, _i]),
     "dlaf_mi355x_tridiagonal_eigensolver_d": (_i, [_i, _i, _vp, _vp, _vp, _vp, _i]),
+    "dlaf_symmetric_eigensolver_partial_spectrum_s": (_i, [_i, _ch, _vp, DLAFDescriptor, _vp, _vp, DLAFDescriptor, _i64, _i64]),
+    "dlaf_symmetric_generalized_eigensolver_partial_spectrum_s": (_i, [_i, _ch, _vp, DLAFDescriptor, _vp, DLAFDescriptor, _vp, _vp, DLAFDescriptor, _i64, _i64]),
+    "dlaf_symmetric_generalized_eigensolver_factorized_partial_spectrum_s": (_i, [_i, _ch, _vp, DLAFDescriptor, _vp, DLAFDescriptor, _vp, _vp, DLAFDescriptor, _i64, _i64]),
+    "dlaf_symmetric_eigensolver_partial_spectrum_d": (_i, [_i, _ch, _vp, DLAFDescriptor, _vp, _vp, DLAFDescriptor, _i64, _i64]),
+    "dlaf_symmetric_generalized_eigensolver_partial_spectrum_d": (_i, [_i, _ch, _vp, DLAFDescriptor, _vp, DLAFDescriptor, _vp, _vp, DLAFDescriptor, _i64, _i64]),
+    "dlaf_symmetric_generalized_eigensolver_factorized_partial_spectrum_d": (_i, [_i, _ch, _vp, DLAFDescriptor, _vp, DLAFDescriptor, _vp, _vp, DLAFDescriptor, _i64, _i64]),
+    "dlaf_hermitian_eigensolver_partial_spectrum_c": (_i, [_i, _ch, _vp, DLAFDescriptor, _vp, _vp, DLAFDescriptor, _i64, _i64]),
+    "dlaf_hermitian_generalized_eigensolver_partial_spectrum_c": (_i, [_i, _ch, _vp, DLAFDescriptor, _vp, DLAFDescriptor, _vp, _vp, DLAFDescriptor, _i64, _i64]),
+    "dlaf_hermitian_generalized_eigensolver_factorized_partial_spectrum_c": (_i, [_i, _ch, _vp, DLAFDescriptor, _vp, DLAFDescriptor, _vp, _vp, DLAFDescriptor, _i64, _i64]),
+    "dlaf_hermitian_eigensolver_partial_spectrum_z": (_i, [_i, _ch, _vp, DLAFDescriptor, _vp, _vp, DLAFDescriptor, _i64, _i64]),
+    "dlaf_hermitian_generalized_eigensolver_partial_spectrum_z": (_i, [_i, _ch, _vp, DLAFDescriptor, _vp, DLAFDescriptor, _vp, _vp, DLAFDescriptor, _i64, _i64]),
+    "dlaf_hermitian_generalized_eigensolver_factorized_partial_spectrum_z": (_i, [_i, _ch, _vp, DLAFDescriptor, _vp, DLAFDescriptor, _vp, _vp, DLAFDescriptor, _i64, _i64]),
+    "dlaf_pssyevd_partial_spectrum": (None, [_ch, _i, _vp, _i, _i, _IP, _vp, _vp, _i, _i, _IP, _i64, _i64, _IP]),
+    "dlaf_pdsyevd_partial_spectrum": (None, [_ch, _i, _vp, _i, _i, _IP, _vp, _vp, _i, _i, _IP, _i64, _i64, _IP]),
+    "dlaf_pcheevd_partial_spectrum": (None, [_ch, _i, _vp, _i, _i, _IP, _vp, _vp, _i, _i, _IP, _i64, _i64, _IP]),
+    "dlaf_pzheevd_partial_spectrum": (None, [_ch, _i, _vp, _i, _i, _IP, _vp, _vp, _i, _i, _IP, _i64, _i64, _IP]),
+    "dlaf_pssygvd_partial_spectrum": (None, [_ch, _i, _vp, _i, _i, _IP, _vp, _i, _i, _IP, _vp, _vp, _i, _i, _IP, _i64, _i64, _IP]),
+    "dlaf_pssygvd_factorized_partial_spectrum": (None, [_ch, _i, _vp, _i, _i, _IP, _vp, _i, _i, _IP, _vp, _vp, _i, _i, _IP, _i64, _i64, _IP]),
+    "dlaf_pdsygvd_partial_spectrum": (None, [_ch, _i, _vp, _i, _i, _IP, _vp, _i, _i, _IP, _vp, _vp, _i, _i, _IP, _i64, _i64, _IP]),
+    "dlaf_pdsygvd_factorized_partial_spectrum": (None, [_ch, _i, _vp, _i, _i, _IP, _vp, _i, _i, _IP, _vp, _vp, _i, _i, _IP, _i64, _i64, _IP]),
+    "dlaf_pchegvd_partial_spectrum": (None, [_ch, _i, _vp, _i, _i, _IP, _vp, _i, _i, _IP, _vp, _vp, _i, _i, _IP, _i64, _i64, _IP]),
+    "dlaf_pchegvd_factorized_partial_spectrum": (None, [_ch, _i, _vp, _i, _i, _IP, _vp, _i, _i, _IP, _vp, _vp, _i, _i, _IP, _i64, _i64, _IP]),
+    "dlaf_pzhegvd_partial_spectrum": (None, [_ch, _i, _vp, _i, _i, _IP, _vp, _i, _i, _IP, _vp, _vp, _i, _i, _IP, _i64, _i64, _IP]),
+    "dlaf_pzhegvd_factorized_partial_spectrum": (None, [_ch, _i, _vp, _i, _i, _IP, _vp, _i, _i, _IP, _vp, _vp, _i, _i, _IP, _i64, _i64, _IP]),
+    "dlaf_mi355x_tridiagonal_eigensolver_partial_spectrum_s": (_i, [_i, _i, _vp, _vp, _vp, _vp, _i, _l, _l]),
+    "dlaf_mi355x_tridiagonal_eigensolver_partial_spectrum_d": (_i, [_i, _i, _vp, _vp, _vp, _vp, _i, _l, _l]),
+    "dlaf_mi355x_partial_spectrum_plan": (_i, [_l, _i, _i, _i, _i, _l, _l, C.POINTER(C.c_long)]),
     "dlaf_mi355x_eigensolver_profile": (_i, [C.POINTER(C.c_double)]),
     "dlaf_mi355x_get_band_size": (_i, [_i]),
     "dlaf_mi355x_red2band_panel_stats": (_i, [C.POINTER(C.c_long), C.POINTER(C.c_long)]),

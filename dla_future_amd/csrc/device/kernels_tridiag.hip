@@ -1144,15 +1144,15 @@ __global__ __launch_bounds__(kThreads) void b2t_expand_kernel(const T* vout, lon
   }
 }
 
-// e[r + cl * lde] = z[r + gc * ldz] for the local columns cl of a block-cyclic column axis (gc its global column),
-// real -> T on the way (castToComplex, tridiag_solver/impl.h:264-277)
+// e[r + cl * lde] = z[r + (gc - pad) * ldz] for the local columns cl of a block-cyclic column axis (gc its global
+// column; zero for gc < pad), real -> T on the way (castToComplex, tridiag_solver/impl.h:264-277)
 template <class R, class T>
 __global__ __launch_bounds__(kThreads) void cols_gather_cast_kernel(const R* z, long ldz, long n, int nb, int pc, int ci,
-                                                                    long ncols_loc, T* e, long lde) {
+                                                                    long ncols_loc, long pad, T* e, long lde) {
   for (long cl = blockIdx.y; cl < ncols_loc; cl += gridDim.y) {
     const long gc = ((cl / nb) * pc + ci) * nb + cl % nb;
     for (long r = (long) blockIdx.x * kThreads + threadIdx.x; r < n; r += (long) gridDim.x * kThreads)
-      e[r + cl * lde] = make_el<T>((real_t<T>) z[r + gc * ldz], real_t<T>(0));
+      e[r + cl * lde] = make_el<T>(gc < pad ? real_t<T>(0) : (real_t<T>) z[r + (gc - pad) * ldz], real_t<T>(0));
   }
 }
 
@@ -1175,13 +1175,13 @@ __global__ __launch_bounds__(kThreads) void rows_to_tiles_kernel(const T* e, lon
 }  // namespace
 
 template <class R, class T>
-void launch_cols_gather_cast(const R* z, long ldz, long n, int nb, int pc, int ci, long ncols_loc, T* e, long lde,
+void launch_cols_gather_cast(const R* z, long ldz, long n, int nb, int pc, int ci, long ncols_loc, long pad, T* e, long lde,
                              hipStream_t stream) {
   if (n <= 0 || ncols_loc <= 0)
     return;
   hipLaunchKernelGGL((cols_gather_cast_kernel<R, T>), dim3((unsigned) std::min<long>(8, (n + kThreads - 1) / kThreads),
                                                            (unsigned) std::min<long>(ncols_loc, 8192)),
-                     dim3(kThreads), 0, stream, z, ldz, n, nb, pc, ci, ncols_loc, e, lde);
+                     dim3(kThreads), 0, stream, z, ldz, n, nb, pc, ci, ncols_loc, pad, e, lde);
 }
 template <class T>
 void launch_rows_to_tiles(const T* e, long lde, long n, long ncols_loc, int nb, int pr, int ri, long ltr, long ltc, T* tiles,
@@ -1191,10 +1191,10 @@ void launch_rows_to_tiles(const T* e, long lde, long n, long ncols_loc, int nb, 
   hipLaunchKernelGGL((rows_to_tiles_kernel<T>), dim3(8, (unsigned) ltr, (unsigned) ltc), dim3(kThreads), 0, stream, e, lde, n,
                      ncols_loc, nb, pr, ri, ltr, tiles);
 }
-template void launch_cols_gather_cast<float, float>(const float*, long, long, int, int, int, long, float*, long, hipStream_t);
-template void launch_cols_gather_cast<double, double>(const double*, long, long, int, int, int, long, double*, long, hipStream_t);
-template void launch_cols_gather_cast<float, cfloat>(const float*, long, long, int, int, int, long, cfloat*, long, hipStream_t);
-template void launch_cols_gather_cast<double, cdouble>(const double*, long, long, int, int, int, long, cdouble*, long, hipStream_t);
+template void launch_cols_gather_cast<float, float>(const float*, long, long, int, int, int, long, long, float*, long, hipStream_t);
+template void launch_cols_gather_cast<double, double>(const double*, long, long, int, int, int, long, long, double*, long, hipStream_t);
+template void launch_cols_gather_cast<float, cfloat>(const float*, long, long, int, int, int, long, long, cfloat*, long, hipStream_t);
+template void launch_cols_gather_cast<double, cdouble>(const double*, long, long, int, int, int, long, long, cdouble*, long, hipStream_t);
 
 int b2t_max_band() {
   return kB2tMaxBand;

@@ -630,16 +630,57 @@ __global__ __launch_bounds__(256) void dc_finish_kernel(DcMergeArgs<R> p) {
   }
 }
 
-// final: w[i] = 2^wexp d[ord[i]] (undoes the normalisation exactly), z[:, i] = q[:, ord[i]]
+// root merge of a partial spectrum, after the secular equation and before the products.  dn = [k roots ascending |
+// n - k deflated values ascending]; an entry's merged position is what dc_finish_kernel gives it (a root goes before
+// the deflated values that are not smaller, a deflated value behind the roots that are not larger).  Positions ascend
+// within each part, so the entries whose position falls in [begin, end) are one run of each:
+// out = {j0, j1, f0, f1}, roots [j0, j1) and deflated values [f0, f1) (counted from k).  Four threads, one bound each.
+template <class R>
+__global__ __launch_bounds__(64) void dc_range_kernel(const R* dn, int n, int k, int begin, int end, int* out) {
+  const int t = threadIdx.x;
+  if (t >= 4)
+    return;
+  const bool first = t < 2;
+  const int bound = (t & 1) ? end : begin;
+  const int len = first ? k : n - k;
+  const int base_other = first ? k : 0;
+  const int len_other = first ? n - k : k;
+  // number of entries of this part whose merged position is below `bound`
+  int a = 0, b = len;
+  while (a < b) {
+    const int i = (a + b) >> 1;
+    const R val = dn[(first ? 0 : k) + i];
+    int lo = 0, hi = len_other;
+    while (lo < hi) {
+      const int mid = (lo + hi) >> 1;
+      const R o = dn[base_other + mid];
+      const bool before = first ? (o < val) : (o <= val);
+      if (before)
+        lo = mid + 1;
+      else
+        hi = mid;
+    }
+    if (i + lo < bound)
+      a = i + 1;
+    else
+      b = i;
+  }
+  out[t] = a;
+}
+
+// final: w[i] = 2^wexp d[ord[i]] (undoes the normalisation exactly) for all i, z[:, i - begin] = q[:, ord[i]] for i in
+// [begin, end)
 template <class R>
 __global__ __launch_bounds__(256) void dc_output_kernel(const R* q, long ldq, const R* d, const int* ord, long n, int wexp,
-                                                        R* w, R* z, long ldz) {
+                                                        R* w, R* z, long ldz, long begin, long end) {
   for (long c = blockIdx.y; c < n; c += gridDim.y) {
     const long src = ord[c];
     if (blockIdx.x == 0 && threadIdx.x == 0)
       w[c] = ldexp(d[src], wexp);
+    if (c < begin || c >= end)
+      continue;
     for (long r = (long) blockIdx.x * 256 + threadIdx.x; r < n; r += (long) gridDim.x * 256)
-      z[r + c * ldz] = q[r + src * ldq];
+      z[r + (c - begin) * ldz] = q[r + src * ldq];
   }
 }
 
@@ -750,11 +791,16 @@ void launch_dc_finish(const DcMergeArgs<R>& a, int nmerges, int nmax, hipStream_
                      0, s, a);
 }
 template <class R>
-void launch_dc_output(const R* q, long ldq, const R* d, const int* ord, long n, int wexp, R* w, R* z, long ldz, hipStream_t s) {
+void launch_dc_range(const R* dnew, int n, int k, int begin, int end, int* out, hipStream_t s) {
+  hipLaunchKernelGGL((dc_range_kernel<R>), dim3(1), dim3(64), 0, s, dnew, n, k, begin, end, out);
+}
+template <class R>
+void launch_dc_output(const R* q, long ldq, const R* d, const int* ord, long n, int wexp, R* w, R* z, long ldz, long begin,
+                      long end, hipStream_t s) {
   if (n <= 0)
     return;
   hipLaunchKernelGGL((dc_output_kernel<R>), dim3((unsigned) std::min<long>(8, (n + 255) / 256), (unsigned) std::min<long>(n, 8192)),
-                     dim3(256), 0, s, q, ldq, d, ord, n, wexp, w, z, ldz);
+                     dim3(256), 0, s, q, ldq, d, ord, n, wexp, w, z, ldz, begin, end);
 }
 
 #define INST(R)                                                                                        \
@@ -766,7 +812,8 @@ void launch_dc_output(const R* q, long ldq, const R* d, const int* ord, long n, 
   template void launch_dc_rotate_gather<R>(const DcMergeArgs<R>&, int, int, hipStream_t);              \
   template void launch_dc_secular<R>(const DcMergeArgs<R>&, int, int, hipStream_t);                    \
   template void launch_dc_finish<R>(const DcMergeArgs<R>&, int, int, hipStream_t);                     \
-  template void launch_dc_output<R>(const R*, long, const R*, const int*, long, int, R*, R*, long, hipStream_t);
+  template void launch_dc_range<R>(const R*, int, int, int, int, int*, hipStream_t);                   \
+  template void launch_dc_output<R>(const R*, long, const R*, const int*, long, int, R*, R*, long, long, long, hipStream_t);
 INST(float)
 INST(double)
 #undef INST

@@ -58,10 +58,11 @@ template <class T>
 void launch_b2t_expand(const T* vout, long ldv, long n, int b, T* vx, T* taus, hipStream_t stream, bool transposed = false);
 
 // ------------------------------------------------------------------------------------------ eigenvector plumbing
-// e[r + cl * lde] = (T) z[r + gc * ldz]: the local columns cl of a block-cyclic column axis (pc processes, this one at
-// position ci from the source, block nb) out of the replicated real eigenvector matrix z
+// e[r + cl * lde] = (T) z[r + (gc - pad) * ldz]: the local columns cl of a block-cyclic column axis (pc processes, this
+// one at position ci from the source, block nb) out of the replicated real eigenvector matrix z, whose column 0 is the
+// axis' column `pad`; the axis' columns gc < pad (the padding in front of a partial spectrum) become zero
 template <class R, class T>
-void launch_cols_gather_cast(const R* z, long ldz, long n, int nb, int pc, int ci, long ncols_loc, T* e, long lde,
+void launch_cols_gather_cast(const R* z, long ldz, long n, int nb, int pc, int ci, long ncols_loc, long pad, T* e, long lde,
                              hipStream_t stream);
 // the local tile rows (pr processes, position ri) of those columns into a tile-layout matrix of ltr x ltc tiles
 template <class T>

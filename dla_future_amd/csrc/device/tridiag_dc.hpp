@@ -83,8 +83,13 @@ template <class R>
 void launch_dc_secular(const DcMergeArgs<R>& a, int nmerges, int kmax, hipStream_t s);
 template <class R>
 void launch_dc_finish(const DcMergeArgs<R>& a, int nmerges, int nmax, hipStream_t s);
-// w[i] = 2^wexp d[ord[i]], z[:, i] = q[:, ord[i]]
+// partial spectrum, root merge: from dnew = [k roots ascending | n - k deflated ascending] the runs of each part whose
+// merged position falls in [begin, end): out[4] (device) = {j0, j1, f0, f1}
 template <class R>
-void launch_dc_output(const R* q, long ldq, const R* d, const int* ord, long n, int wexp, R* w, R* z, long ldz, hipStream_t s);
+void launch_dc_range(const R* dnew, int n, int k, int begin, int end, int* out, hipStream_t s);
+// w[i] = 2^wexp d[ord[i]] for all i, z[:, i - begin] = q[:, ord[i]] for i in [begin, end)
+template <class R>
+void launch_dc_output(const R* q, long ldq, const R* d, const int* ord, long n, int wexp, R* w, R* z, long ldz, long begin,
+                      long end, hipStream_t s);
 
 }  // namespace dlaf_mi355x

@@ -428,11 +428,13 @@ int band_to_tridiag_c(int ctx, const HT* a, const DLAF_descriptor& da, int band,
                                   reinterpret_cast<DT*>(v), ldv);
 }
 
-// Eigensolver entry (src/c_api/eigensolver/eigensolver.h:33-75): descriptors of A and of the eigenvector matrix
+// Eigensolver entry (src/c_api/eigensolver/eigensolver.h:33-75): descriptors of A and of the eigenvector matrix;
+// [begin, end): the 0-based range of eigenvalue indices whose eigenvectors are wanted ([0, n): the full entries)
 template <class HT>
 int eigensolver_c(int ctx, char uplo, HT* a, const DLAF_descriptor& da, typename RealOf<HT>::type* w, HT* z,
-                  const DLAF_descriptor& dz) {
+                  const DLAF_descriptor& dz, long begin, long end) {
   using DT = typename DevType<HT>::type;
+  check_eigenvalues_index("eigensolver", da.m, begin, end);
   check_cholesky_desc(da);
   Grid& g = grid_from_context(ctx);
   if (dz.i != 0 || dz.j != 0)
@@ -444,13 +446,15 @@ int eigensolver_c(int ctx, char uplo, HT* a, const DLAF_descriptor& da, typename
     if (d->isrc < 0 || d->isrc >= g.nprow || d->jsrc < 0 || d->jsrc >= g.npcol)
       fatal("[dlaf_mi355x] source rank (%d,%d) outside the %d x %d grid\n", d->isrc, d->jsrc, g.nprow, g.npcol);
   return hermitian_eigensolver_host<DT>(&g, uplo, reinterpret_cast<DT*>(a), da.ld, da.m, da.nb, da.isrc, da.jsrc, w,
-                                        reinterpret_cast<DT*>(z), dz.ld, dz.isrc, dz.jsrc);
+                                        reinterpret_cast<DT*>(z), dz.ld, dz.isrc, dz.jsrc, begin, end);
 }
 
 template <class HT>
 int gen_eigensolver_c(int ctx, char uplo, HT* a, const DLAF_descriptor& da, HT* b, const DLAF_descriptor& db,
-                      typename RealOf<HT>::type* w, HT* z, const DLAF_descriptor& dz, bool factorized) {
+                      typename RealOf<HT>::type* w, HT* z, const DLAF_descriptor& dz, bool factorized, long begin,
+                      long end) {
   using DT = typename DevType<HT>::type;
+  check_eigenvalues_index("gen_eigensolver", da.m, begin, end);
   check_cholesky_desc(da);
   check_cholesky_desc(db);
   Grid& g = grid_from_context(ctx);
@@ -465,13 +469,14 @@ int gen_eigensolver_c(int ctx, char uplo, HT* a, const DLAF_descriptor& da, HT* 
       fatal("[dlaf_mi355x] source rank (%d,%d) outside the %d x %d grid\n", d->isrc, d->jsrc, g.nprow, g.npcol);
   return hermitian_gen_eigensolver_host<DT>(&g, uplo, reinterpret_cast<DT*>(a), da.ld, reinterpret_cast<DT*>(b), db.ld,
                                             da.m, da.nb, da.isrc, da.jsrc, db.isrc, db.jsrc, w, reinterpret_cast<DT*>(z),
-                                            dz.ld, dz.isrc, dz.jsrc, factorized);
+                                            dz.ld, dz.isrc, dz.jsrc, factorized, begin, end);
 }
 
-// p?syevd / p?heevd and p?sygvd / p?hegvd argument lists (src/c_api/eigensolver/eigensolver.h:79-124)
+// p?syevd / p?heevd and p?sygvd / p?hegvd argument lists (src/c_api/eigensolver/eigensolver.h:79-124); il, iu: the
+// 1-based inclusive eigenvalue index range of p?syevx (1, n: the full entries; 1, 0: the empty range)
 template <class HT>
 void pxheevd(char uplo, int n, HT* a, int ia, int ja, const int desca[9], typename RealOf<HT>::type* w, HT* z, int iz,
-             int jz, const int descz[9], int* info) {
+             int jz, const int descz[9], long il, long iu, int* info) {
   if (desca[0] != 1 || descz[0] != 1)
     fatal("[dlaf_mi355x] desc[0] (dtype) must be 1\n");
   if (ia != 1 || ja != 1 || iz != 1 || jz != 1)
@@ -480,13 +485,14 @@ void pxheevd(char uplo, int n, HT* a, int ia, int ja, const int desca[9], typena
     fatal("[dlaf_mi355x] A and Z live on different contexts (%d, %d)\n", desca[1], descz[1]);
   const DLAF_descriptor da = make_dlaf_descriptor(n, n, ia, ja, desca);
   const DLAF_descriptor dz = make_dlaf_descriptor(n, n, iz, jz, descz);
-  const int r = eigensolver_c<HT>(desca[1], uplo, a, da, w, z, dz);
+  const int r = eigensolver_c<HT>(desca[1], uplo, a, da, w, z, dz, il - 1, iu);
   if (info)
     *info = r;
 }
 template <class HT>
 void pxhegvd(char uplo, int n, HT* a, int ia, int ja, const int desca[9], HT* b, int ib, int jb, const int descb[9],
-             typename RealOf<HT>::type* w, HT* z, int iz, int jz, const int descz[9], int* info, bool factorized) {
+             typename RealOf<HT>::type* w, HT* z, int iz, int jz, const int descz[9], long il, long iu, int* info,
+             bool factorized) {
   if (desca[0] != 1 || descb[0] != 1 || descz[0] != 1)
     fatal("[dlaf_mi355x] desc[0] (dtype) must be 1\n");
   if (ia != 1 || ja != 1 || ib != 1 || jb != 1 || iz != 1 || jz != 1)
@@ -496,7 +502,7 @@ void pxhegvd(char uplo, int n, HT* a, int ia, int ja, const int desca[9], HT* b,
   const DLAF_descriptor da = make_dlaf_descriptor(n, n, ia, ja, desca);
   const DLAF_descriptor db = make_dlaf_descriptor(n, n, ib, jb, descb);
   const DLAF_descriptor dz = make_dlaf_descriptor(n, n, iz, jz, descz);
-  const int r = gen_eigensolver_c<HT>(desca[1], uplo, a, da, b, db, w, z, dz, factorized);
+  const int r = gen_eigensolver_c<HT>(desca[1], uplo, a, da, b, db, w, z, dz, factorized, il - 1, iu);
   if (info)
     *info = r;
 }
@@ -878,36 +884,78 @@ DLAF_MI355X_R2B_ENTRY(z, std::complex<double>, dlaf_complex_z)
   }                                                                                                                  \
   int dlaf_##KIND##_eigensolver_##S(const int ctx, const char uplo, CT* a, const DLAF_descriptor desca, RT* w, CT* z, \
                                     const DLAF_descriptor descz) noexcept {                                          \
-    return eigensolver_c<HT>(ctx, uplo, reinterpret_cast<HT*>(a), desca, w, reinterpret_cast<HT*>(z), descz);        \
+    return eigensolver_c<HT>(ctx, uplo, reinterpret_cast<HT*>(a), desca, w, reinterpret_cast<HT*>(z), descz, 0,      \
+                             desca.m);                                                                               \
+  }                                                                                                                  \
+  int dlaf_##KIND##_eigensolver_partial_spectrum_##S(const int ctx, const char uplo, CT* a,                           \
+                                                     const DLAF_descriptor desca, RT* w, CT* z,                      \
+                                                     const DLAF_descriptor descz, const int64_t begin,               \
+                                                     const int64_t end) noexcept {                                   \
+    return eigensolver_c<HT>(ctx, uplo, reinterpret_cast<HT*>(a), desca, w, reinterpret_cast<HT*>(z), descz, begin,  \
+                             end);                                                                                   \
   }                                                                                                                  \
   int dlaf_##KIND##_generalized_eigensolver_##S(const int ctx, const char uplo, CT* a, const DLAF_descriptor desca,   \
                                                 CT* b, const DLAF_descriptor descb, RT* w, CT* z,                    \
                                                 const DLAF_descriptor descz) noexcept {                              \
     return gen_eigensolver_c<HT>(ctx, uplo, reinterpret_cast<HT*>(a), desca, reinterpret_cast<HT*>(b), descb, w,      \
-                                 reinterpret_cast<HT*>(z), descz, false);                                            \
+                                 reinterpret_cast<HT*>(z), descz, false, 0, desca.m);                                \
   }                                                                                                                  \
   int dlaf_##KIND##_generalized_eigensolver_factorized_##S(const int ctx, const char uplo, CT* a,                     \
                                                            const DLAF_descriptor desca, CT* b,                       \
                                                            const DLAF_descriptor descb, RT* w, CT* z,                \
                                                            const DLAF_descriptor descz) noexcept {                   \
     return gen_eigensolver_c<HT>(ctx, uplo, reinterpret_cast<HT*>(a), desca, reinterpret_cast<HT*>(b), descb, w,      \
-                                 reinterpret_cast<HT*>(z), descz, true);                                             \
+                                 reinterpret_cast<HT*>(z), descz, true, 0, desca.m);                                 \
+  }                                                                                                                  \
+  int dlaf_##KIND##_generalized_eigensolver_partial_spectrum_##S(                                                     \
+      const int ctx, const char uplo, CT* a, const DLAF_descriptor desca, CT* b, const DLAF_descriptor descb, RT* w,  \
+      CT* z, const DLAF_descriptor descz, const int64_t begin, const int64_t end) noexcept {                         \
+    return gen_eigensolver_c<HT>(ctx, uplo, reinterpret_cast<HT*>(a), desca, reinterpret_cast<HT*>(b), descb, w,      \
+                                 reinterpret_cast<HT*>(z), descz, false, begin, end);                                \
+  }                                                                                                                  \
+  int dlaf_##KIND##_generalized_eigensolver_factorized_partial_spectrum_##S(                                          \
+      const int ctx, const char uplo, CT* a, const DLAF_descriptor desca, CT* b, const DLAF_descriptor descb, RT* w,  \
+      CT* z, const DLAF_descriptor descz, const int64_t begin, const int64_t end) noexcept {                         \
+    return gen_eigensolver_c<HT>(ctx, uplo, reinterpret_cast<HT*>(a), desca, reinterpret_cast<HT*>(b), descb, w,      \
+                                 reinterpret_cast<HT*>(z), descz, true, begin, end);                                 \
   }                                                                                                                  \
   void dlaf_##PEV(const char uplo, const int n, CT* a, const int ia, const int ja, const int desca[9], RT* w, CT* z,  \
                   const int iz, const int jz, const int descz[9], int* info) noexcept {                              \
-    pxheevd<HT>(uplo, n, reinterpret_cast<HT*>(a), ia, ja, desca, w, reinterpret_cast<HT*>(z), iz, jz, descz, info);  \
+    pxheevd<HT>(uplo, n, reinterpret_cast<HT*>(a), ia, ja, desca, w, reinterpret_cast<HT*>(z), iz, jz, descz, 1, n,   \
+                info);                                                                                               \
+  }                                                                                                                  \
+  void dlaf_##PEV##_partial_spectrum(const char uplo, const int n, CT* a, const int ia, const int ja,                 \
+                                     const int desca[9], RT* w, CT* z, const int iz, const int jz,                   \
+                                     const int descz[9], const int64_t il, const int64_t iu, int* info) noexcept {   \
+    pxheevd<HT>(uplo, n, reinterpret_cast<HT*>(a), ia, ja, desca, w, reinterpret_cast<HT*>(z), iz, jz, descz, il, iu, \
+                info);                                                                                               \
   }                                                                                                                  \
   void dlaf_##PGV(const char uplo, const int n, CT* a, const int ia, const int ja, const int desca[9], CT* b,         \
                   const int ib, const int jb, const int descb[9], RT* w, CT* z, const int iz, const int jz,          \
                   const int descz[9], int* info) noexcept {                                                          \
     pxhegvd<HT>(uplo, n, reinterpret_cast<HT*>(a), ia, ja, desca, reinterpret_cast<HT*>(b), ib, jb, descb, w,         \
-                reinterpret_cast<HT*>(z), iz, jz, descz, info, false);                                               \
+                reinterpret_cast<HT*>(z), iz, jz, descz, 1, n, info, false);                                         \
   }                                                                                                                  \
   void dlaf_##PGV##_factorized(const char uplo, const int n, CT* a, const int ia, const int ja, const int desca[9],   \
                                CT* b, const int ib, const int jb, const int descb[9], RT* w, CT* z, const int iz,    \
                                const int jz, const int descz[9], int* info) noexcept {                               \
     pxhegvd<HT>(uplo, n, reinterpret_cast<HT*>(a), ia, ja, desca, reinterpret_cast<HT*>(b), ib, jb, descb, w,         \
-                reinterpret_cast<HT*>(z), iz, jz, descz, info, true);                                                \
+                reinterpret_cast<HT*>(z), iz, jz, descz, 1, n, info, true);                                          \
+  }                                                                                                                  \
+  void dlaf_##PGV##_partial_spectrum(const char uplo, const int n, CT* a, const int ia, const int ja,                 \
+                                     const int desca[9], CT* b, const int ib, const int jb, const int descb[9],      \
+                                     RT* w, CT* z, const int iz, const int jz, const int descz[9], const int64_t il, \
+                                     const int64_t iu, int* info) noexcept {                                         \
+    pxhegvd<HT>(uplo, n, reinterpret_cast<HT*>(a), ia, ja, desca, reinterpret_cast<HT*>(b), ib, jb, descb, w,         \
+                reinterpret_cast<HT*>(z), iz, jz, descz, il, iu, info, false);                                       \
+  }                                                                                                                  \
+  void dlaf_##PGV##_factorized_partial_spectrum(const char uplo, const int n, CT* a, const int ia, const int ja,      \
+                                                const int desca[9], CT* b, const int ib, const int jb,               \
+                                                const int descb[9], RT* w, CT* z, const int iz, const int jz,        \
+                                                const int descz[9], const int64_t il, const int64_t iu,              \
+                                                int* info) noexcept {                                                \
+    pxhegvd<HT>(uplo, n, reinterpret_cast<HT*>(a), ia, ja, desca, reinterpret_cast<HT*>(b), ib, jb, descb, w,         \
+                reinterpret_cast<HT*>(z), iz, jz, descz, il, iu, info, true);                                        \
   }
 DLAF_MI355X_EIG_ENTRY(s, symmetric, float, float, float, pssyevd, pssygvd)
 DLAF_MI355X_EIG_ENTRY(d, symmetric, double, double, double, pdsyevd, pdsygvd)
@@ -918,12 +966,32 @@ DLAF_MI355X_EIG_ENTRY(z, hermitian, std::complex<double>, dlaf_complex_z, double
 int dlaf_mi355x_tridiagonal_eigensolver_s(int n, int nb, const float* d, const float* e, float* w, float* z,
                                           int ldz) noexcept {
   runtime_init();
-  return tridiag_solver_host<float>(n, nb, d, e, w, z, ldz);
+  return tridiag_solver_host<float>(n, nb, d, e, w, z, ldz, 0, n);
 }
 int dlaf_mi355x_tridiagonal_eigensolver_d(int n, int nb, const double* d, const double* e, double* w, double* z,
                                           int ldz) noexcept {
   runtime_init();
-  return tridiag_solver_host<double>(n, nb, d, e, w, z, ldz);
+  return tridiag_solver_host<double>(n, nb, d, e, w, z, ldz, 0, n);
+}
+int dlaf_mi355x_tridiagonal_eigensolver_partial_spectrum_s(int n, int nb, const float* d, const float* e, float* w,
+                                                           float* z, int ldz, long begin, long end) noexcept {
+  check_eigenvalues_index("tridiagonal_eigensolver", n, begin, end);
+  runtime_init();
+  return tridiag_solver_host<float>(n, nb, d, e, w, z, ldz, begin, end);
+}
+int dlaf_mi355x_tridiagonal_eigensolver_partial_spectrum_d(int n, int nb, const double* d, const double* e, double* w,
+                                                           double* z, int ldz, long begin, long end) noexcept {
+  check_eigenvalues_index("tridiagonal_eigensolver", n, begin, end);
+  runtime_init();
+  return tridiag_solver_host<double>(n, nb, d, e, w, z, ldz, begin, end);
+}
+int dlaf_mi355x_partial_spectrum_plan(long n, int nb, int npcol, int mycol, int z_jsrc, long begin, long end,
+                                      long out[5]) noexcept {
+  check_eigenvalues_index("partial_spectrum_plan", n, begin, end);
+  const PartialSpectrumPlan p = partial_spectrum_plan(n, nb, npcol, mycol, z_jsrc, begin, end);
+  const long v[5] = {p.b0, p.jsrc, p.ncl, p.first, p.pad};
+  std::copy(v, v + 5, out);
+  return 0;
 }
 int dlaf_mi355x_eigensolver_profile(double ms[5]) noexcept {
   eigensolver_last_profile(ms);

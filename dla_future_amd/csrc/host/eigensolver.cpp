@@ -433,10 +433,31 @@ int bt_band_to_tridiag_host(long n, int band, const T* v, long ldv, T* e, long l
 }
 
 // ------------------------------------------------------------------------------------------------ drivers
+// the eigenvalue index range of a partial spectrum and the internal eigenvector matrix that holds it (eigensolver.hpp)
+void check_eigenvalues_index(const char* who, long n, long begin, long end) {
+  if (begin < 0 || begin > end || end > n)
+    fatal("[dlaf_mi355x] %s: eigenvalue index range [%ld, %ld) must satisfy 0 <= begin <= end <= n = %ld\n", who, begin,
+          end, n);
+}
+
+PartialSpectrumPlan partial_spectrum_plan(long n, int nb, int npcol, int mycol, int z_jsrc, long begin, long end) {
+  PartialSpectrumPlan p;
+  const long t0 = begin / nb;
+  p.b0 = t0 * nb;
+  p.jsrc = (int) ((z_jsrc + t0) % npcol);
+  p.ncl = Axis{end - p.b0, nb, npcol, mycol, p.jsrc}.local_size();
+  p.first = Axis{n, nb, npcol, mycol, z_jsrc}.next_local(t0) * nb;
+  p.pad = mycol == p.jsrc ? begin - p.b0 : 0;
+  return p;
+}
+
 // Eigensolver::call on resident operands: A (uplo L; destroyed: band + reflectors), eigenvalues to the host array w
-// (all n on every rank), eigenvectors into the resident general matrix Z (n x n, A's block size and row source).
+// (all n on every rank), eigenvectors of the eigenvalues [begin, end) into the resident general matrix Z (A's block
+// size and row source), which covers the global columns [b0, end), b0 = (begin / nb) nb: n x (end - b0), the full
+// matrix for [0, n).  Its columns [b0, begin) are padding and stay zero through both back-transformations (and the
+// triangular solve of the generalized problem): all three act on the columns independently.
 template <class T>
-int hermitian_eigensolver_device(DeviceMatrix<T>& A, real_t<T>* w_host, GeneralMatrix<T>& Z) {
+int hermitian_eigensolver_device(DeviceMatrix<T>& A, real_t<T>* w_host, GeneralMatrix<T>& Z, long begin, long end) {
   using R = real_t<T>;
   const long n = A.n;
   const int nb = A.nb;
@@ -444,8 +465,11 @@ int hermitian_eigensolver_device(DeviceMatrix<T>& A, real_t<T>* w_host, GeneralM
     return 0;
   Grid* g = A.grid;
   TileMatrix<T>& C = Z.m;
-  if (C.grid != g || C.nb != nb || C.rows.n != n || C.cols.n != n || C.rows.src != A.rows.src || C.transposed)
-    fatal("[dlaf_mi355x] eigensolver: the eigenvector matrix must be n x n with A's block size and row source rank\n");
+  const long b0 = (begin / nb) * nb, pad = begin - b0, k = end - begin;
+  check_eigenvalues_index("eigensolver", n, begin, end);
+  if (C.grid != g || C.nb != nb || C.rows.n != n || C.cols.n != end - b0 || C.rows.src != A.rows.src || C.transposed)
+    fatal("[dlaf_mi355x] eigensolver: the eigenvector matrix must be n x %ld with A's block size and row source rank\n",
+          end - b0);
   const int band = get_band_size(nb);  // eigensolver/impl.h:41
   hipStream_t s = A.s_high;
   // a stage's status is made the same on every rank before anybody acts on it: a rank that left alone would leave
@@ -458,12 +482,13 @@ int hermitian_eigensolver_device(DeviceMatrix<T>& A, real_t<T>* w_host, GeneralM
     }
     return info;
   };
-  // stages 2 and 3 run replicated: every rank holds the n x n reflector matrix (T), the n x n real eigenvector matrix
+  // stages 2 and 3 run replicated: every rank holds the n x n reflector matrix (T), the n x k real eigenvector matrix
   // and the divide & conquer workspaces (4 n^2 real) -- say so instead of failing inside an allocation
   {
     size_t free_b = 0, total_b = 0;
     DLAF_HIP_CHECK(hipMemGetInfo(&free_b, &total_b));
-    const double need = (double) n * n * (sizeof(T) + 5.0 * sizeof(R)) + (double) n * bt_aligned_ld(n) / g->npcol * sizeof(T);
+    const double need = (double) n * n * (sizeof(T) + 4.0 * sizeof(R)) + (double) n * k * sizeof(R) +
+                        (double) (end - b0) * bt_aligned_ld(n) / g->npcol * sizeof(T);
     if (need > 0.95 * (double) free_b)
       fatal("[dlaf_mi355x] eigensolver: n = %ld needs %.1f GiB per rank for the replicated stages (band_to_tridiagonal, "
             "tridiagonal_eigensolver), %.1f GiB are free\n", n, need / 1073741824.0, (double) free_b / 1073741824.0);
@@ -508,21 +533,30 @@ int hermitian_eigensolver_device(DeviceMatrix<T>& A, real_t<T>* w_host, GeneralM
   checksum("e", e, (size_t) (n - 1) * sizeof(R));
   checksum("v", v, (size_t) n * n * sizeof(T));
   R* wd = ealloc<R>((size_t) n);
-  R* zr = ealloc<R>((size_t) n * n);
+  R* zr = ealloc<R>((size_t) n * k);
   {
     StageTimer t(s);
-    tridiag_solver_device<R>(n, nb, d, e, wd, zr, n, s, g->nranks > 1 ? grid_transport(*g) : nullptr);
+    tridiag_solver_device<R>(n, nb, d, e, wd, zr, n, begin, end, s, g->nranks > 1 ? grid_transport(*g) : nullptr);
     g_stage_ms[2] = t.stop();
   }
   checksum("w", wd, (size_t) n * sizeof(R));
-  checksum("z (tridiagonal)", zr, (size_t) n * n * sizeof(R));
+  checksum("z (tridiagonal)", zr, (size_t) n * k * sizeof(R));
   DLAF_HIP_CHECK(hipMemcpyAsync(w_host, wd, (size_t) n * sizeof(R), hipMemcpyDeviceToHost, s));
+  if (k == 0) {
+    // no eigenvector is wanted: the eigenvalues are all there is
+    DLAF_HIP_CHECK(hipStreamSynchronize(s));
+    for (R* q : {d, e, wd, zr})
+      DLAF_HIP_CHECK(pool_free(q));
+    DLAF_HIP_CHECK(pool_free(v));
+    g_stage_ms[3] = g_stage_ms[4] = 0;
+    return 0;
+  }
   // the columns of this process column, all rows (the back-transformation mixes rows, never columns)
   const long ncl = C.cols.local_size();
   const long lde = bt_aligned_ld(n);
   T* el_alloc = ealloc<T>((size_t) lde * std::max<long>(ncl, 1) + 4);
   T* el = bt_aligned_base(el_alloc);
-  launch_cols_gather_cast<R, T>(zr, n, n, nb, C.cols.P, C.cols.shift(), ncl, el, lde, s);
+  launch_cols_gather_cast<R, T>(zr, n, n, nb, C.cols.P, C.cols.shift(), ncl, pad, el, lde, s);
   {
     StageTimer t(s);
     bt_band_to_tridiag_device(n, band, v, n, el, lde, ncl, s);
@@ -546,28 +580,51 @@ int hermitian_eigensolver_device(DeviceMatrix<T>& A, real_t<T>* w_host, GeneralM
   return info;
 }
 
+// the local columns of the internal eigenvector matrix behind its padding -> their place in the caller's local array
+// (for the full spectrum: all of them, from column 0).  Nothing else of z is written.
+template <class T>
+static void download_eigenvectors(GeneralMatrix<T>& Z, const PartialSpectrumPlan& pl, T* z, long ldz) {
+  TileMatrix<T>& C = Z.m;
+  const long srows = C.rows.local_size(), scols = C.cols.local_size();
+  if (srows == 0 || scols <= pl.pad)
+    return;
+  hipStream_t s = nullptr;
+  DLAF_HIP_CHECK(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
+  if (!C.staging)
+    C.staging = dev_alloc<T>((size_t) srows * scols);
+  launch_from_tiles(C.layout(C.staging, srows), s);
+  DLAF_HIP_CHECK(hipMemcpy2DAsync(z + (size_t) (pl.first + pl.pad) * ldz, (size_t) ldz * sizeof(T),
+                                  C.staging + (size_t) pl.pad * srows, (size_t) srows * sizeof(T),
+                                  (size_t) srows * sizeof(T), (size_t) (scols - pl.pad), hipMemcpyDeviceToHost, s));
+  DLAF_HIP_CHECK(hipStreamSynchronize(s));
+  DLAF_HIP_CHECK(hipStreamDestroy(s));
+}
+
 template <class T>
 int hermitian_eigensolver_host(Grid* g, char uplo, T* a, long lda, long n, int nb, int isrc, int jsrc, real_t<T>* w, T* z,
-                               long ldz, int z_isrc, int z_jsrc) {
+                               long ldz, int z_isrc, int z_jsrc, long begin, long end) {
+  check_eigenvalues_index("eigensolver", n, begin, end);
   if (uplo != 'L' && uplo != 'l')
     fatal("[dlaf_mi355x] eigensolver: uplo = %c is not implemented (neither upstream: eigensolver/impl.h:43-45)\n", uplo);
   if (z_isrc != isrc)
     fatal("[dlaf_mi355x] eigensolver: the eigenvector matrix must share A's row source rank (%d != %d)\n", z_isrc, isrc);
+  const PartialSpectrumPlan pl = partial_spectrum_plan(n, nb, g->npcol, g->mycol, z_jsrc, begin, end);
   DeviceMatrix<T> A;
   A.create(g, 'L', n, nb, isrc, jsrc);
   A.upload(a, lda);
-  std::unique_ptr<MatrixBase> zh(general_matrix_create(g, TypeInfo<T>::tag, n, n, nb, z_isrc, z_jsrc));
+  std::unique_ptr<MatrixBase> zh(general_matrix_create(g, TypeInfo<T>::tag, n, end - pl.b0, nb, z_isrc, pl.jsrc));
   GeneralMatrix<T>& Z = static_cast<GeneralMatrix<T>&>(*zh);
-  const int r = hermitian_eigensolver_device(A, w, Z);
+  const int r = hermitian_eigensolver_device(A, w, Z, begin, end);
   A.download(a, lda, true);  // (upstream leaves the band + reflectors in A as well)
-  general_matrix_transfer(zh.get(), z, ldz, false);
+  download_eigenvectors(Z, pl, z, ldz);
   return r;
 }
 
 template <class T>
 int hermitian_gen_eigensolver_host(Grid* g, char uplo, T* a, long lda, T* b, long ldb, long n, int nb, int a_isrc,
                                    int a_jsrc, int b_isrc, int b_jsrc, real_t<T>* w, T* z, long ldz, int z_isrc,
-                                   int z_jsrc, bool b_factorized) {
+                                   int z_jsrc, bool b_factorized, long begin, long end) {
+  check_eigenvalues_index("gen_eigensolver", n, begin, end);
   if (uplo != 'L' && uplo != 'l')
     fatal("[dlaf_mi355x] gen_eigensolver: uplo = %c is not implemented (neither upstream: eigensolver/impl.h:43-45)\n", uplo);
   if (a_isrc != b_isrc || a_jsrc != b_jsrc || z_isrc != a_isrc)
@@ -588,25 +645,28 @@ int hermitian_gen_eigensolver_host(Grid* g, char uplo, T* a, long lda, T* b, lon
   info = gen_to_std_device(A, B);
   if (info != 0)
     return info;
-  std::unique_ptr<MatrixBase> zh(general_matrix_create(g, TypeInfo<T>::tag, n, n, nb, z_isrc, z_jsrc));
+  const PartialSpectrumPlan pl = partial_spectrum_plan(n, nb, g->npcol, g->mycol, z_jsrc, begin, end);
+  std::unique_ptr<MatrixBase> zh(general_matrix_create(g, TypeInfo<T>::tag, n, end - pl.b0, nb, z_isrc, pl.jsrc));
   GeneralMatrix<T>& Z = static_cast<GeneralMatrix<T>&>(*zh);
-  info = hermitian_eigensolver_device(A, w, Z);
+  info = hermitian_eigensolver_device(A, w, Z, begin, end);
   if (info != 0)
     return info;
   const T one = make_host_el<T>(1.0);
   B.type = TypeInfo<T>::tag;
-  info = triangular_solver_device('L', 'L', 'C', 'N', &one, &B, zh.get());
+  if (end > begin)
+    info = triangular_solver_device('L', 'L', 'C', 'N', &one, &B, zh.get());
   A.download(a, lda, true);
   if (!b_factorized)
     B.download(b, ldb, true);
-  general_matrix_transfer(zh.get(), z, ldz, false);
+  download_eigenvectors(Z, pl, z, ldz);
   return info;
 }
 
 #define INST(T)                                                                                                          \
-  template int hermitian_eigensolver_host<T>(Grid*, char, T*, long, long, int, int, int, real_t<T>*, T*, long, int, int); \
+  template int hermitian_eigensolver_host<T>(Grid*, char, T*, long, long, int, int, int, real_t<T>*, T*, long, int, int, \
+                                             long, long);                                                                \
   template int hermitian_gen_eigensolver_host<T>(Grid*, char, T*, long, T*, long, long, int, int, int, int, int,         \
-                                                 real_t<T>*, T*, long, int, int, bool);                                  \
+                                                 real_t<T>*, T*, long, int, int, bool, long, long);                      \
   template int band_to_tridiag_device<T>(DeviceMatrix<T>&, int, real_t<T>*, real_t<T>*, T*, long);                       \
   template int band_to_tridiag_host<T>(Grid*, const T*, long, long, int, int, int, int, real_t<T>*, real_t<T>*, T*, long); \
   template int bt_band_to_tridiag_device<T>(long, int, const T*, long, T*, long, long, hipStream_t);                     \

@@ -28,22 +28,42 @@ int bt_band_to_tridiag_host(long n, int band, const T* v, long ldv, T* e, long l
 // tridiagonal_eigensolver (include/dlaf/eigensolver/tridiag_solver.h:30-60): d, e (device, n; e[n-1] unused) ->
 // eigenvalues w (device, n, ascending) and eigenvectors z (device, column-major n x n, ldz).  nb = the leaf size of the
 // divide & conquer tree (the block size of the reference's distribution, tridiag_solver/impl.h:198-262).
+// [begin, end): the 0-based range of eigenvalue indices whose eigenvectors are wanted; w always receives all n
+// eigenvalues, z is n x (end - begin) and column j holds the eigenvector of eigenvalue begin + j.
 template <class R>
-int tridiag_solver_device(long n, int nb, R* d, R* e, R* w, R* z, long ldz, hipStream_t s, Transport* tr = nullptr);
+int tridiag_solver_device(long n, int nb, R* d, R* e, R* w, R* z, long ldz, long begin, long end, hipStream_t s,
+                          Transport* tr = nullptr);
 template <class R>
-int tridiag_solver_host(long n, int nb, const R* d, const R* e, R* w, R* z, long ldz);
+int tridiag_solver_host(long n, int nb, const R* d, const R* e, R* w, R* z, long ldz, long begin, long end);
 
 // Hermitian eigensolver, Eigensolver::call (eigensolver/impl.h:38-55, :57-95): the local parts of A (lower triangle
 // referenced, destroyed), eigenvalues w (all n on every rank), eigenvectors z (distributed like a general n x n matrix
-// with A's block size and z's own source rank)
+// with A's block size and z's own source rank).  [begin, end): the 0-based range of eigenvalue indices whose
+// eigenvectors are computed; global column j of z, j in [begin, end), receives the eigenvector of eigenvalue j and
+// nothing else of z is written.
 template <class T>
 int hermitian_eigensolver_host(Grid* g, char uplo, T* a, long lda, long n, int nb, int isrc, int jsrc, real_t<T>* w, T* z,
-                               long ldz, int z_isrc, int z_jsrc);
+                               long ldz, int z_isrc, int z_jsrc, long begin, long end);
 // Hermitian generalized eigensolver A x = lambda B x, GenEigensolver::call (gen_eigensolver/impl.h:33-92)
 template <class T>
 int hermitian_gen_eigensolver_host(Grid* g, char uplo, T* a, long lda, T* b, long ldb, long n, int nb, int a_isrc,
                                    int a_jsrc, int b_isrc, int b_jsrc, real_t<T>* w, T* z, long ldz, int z_isrc,
-                                   int z_jsrc, bool b_factorized);
+                                   int z_jsrc, bool b_factorized, long begin, long end);
+
+// Index arithmetic of a partial spectrum.  The drivers hold the eigenvectors of [begin, end) in an internal matrix that
+// covers the global columns [b0, end), b0 = (begin / nb) nb: whole tile columns are dropped in front of it, so its local
+// columns are a contiguous run of the caller's local columns, and the columns [b0, begin) are zero padding that is
+// never written back.
+struct PartialSpectrumPlan {
+  long b0;          // first global column of the internal matrix
+  int jsrc;         // its column source rank
+  long ncl;         // this process column's local columns of the internal matrix
+  long first;       // the caller's local column its local column 0 corresponds to
+  long pad;         // how many of its leading local columns are padding
+};
+// 0 <= begin <= end <= n, or fatal (before anything touches the GPU)
+void check_eigenvalues_index(const char* who, long n, long begin, long end);
+PartialSpectrumPlan partial_spectrum_plan(long n, int nb, int npcol, int mycol, int z_jsrc, long begin, long end);
 
 // per-stage device times (ms) of the last eigensolver call on this process:
 // 0 reduction_to_band, 1 band_to_tridiagonal, 2 tridiagonal solver, 3 bt_band_to_tridiagonal, 4 bt_reduction_to_band

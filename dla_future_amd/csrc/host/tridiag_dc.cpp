@@ -80,10 +80,20 @@ int dc_leaf_size() {
 // one grouped broadcast round along the process rows and one along the process columns (an all-gather).  The reference
 // distributes the whole solver (tridiag_solver/impl.h:362-476, multiplyEigenvectors merge.h:1694-1790); here the
 // deflation and the secular equation are a few per cent of the stage and stay replicated.
+//
+// [begin, end) != [0, n) (a partial spectrum): everything below the root merge is unchanged.  At the root the columns of
+// Q_new are stored as [secular roots ascending | deflated ascending], so the eigenvectors at the sorted positions
+// [begin, end) are one run of each part (launch_dc_range, from the new eigenvalues alone): only the run of root columns
+// -- widened to the 16-column granularity of the slices -- is multiplied (and cut over the ranks), only the run of
+// deflated columns is copied.  The secular equation and the Loewner weights still take all the roots.  The workspaces
+// stay n x n; z is n x (end - begin).
 template <class R>
-int tridiag_solver_device(long n, int /*nb*/, R* d, R* e, R* w, R* z, long ldz, hipStream_t s, Transport* tr) {
+int tridiag_solver_device(long n, int /*nb*/, R* d, R* e, R* w, R* z, long ldz, long begin, long end, hipStream_t s,
+                          Transport* tr) {
   if (n <= 0)
     return 0;
+  check_eigenvalues_index("tridiagonal_eigensolver", n, begin, end);
+  const bool partial = !(begin == 0 && end == n);
   const int P = tr ? tr->nprow * tr->npcol : 1;
   static const long dist_min = [] {
     const char* e_ = std::getenv("DLAF_MI355X_DC_DIST_MIN");
@@ -218,12 +228,29 @@ int tridiag_solver_device(long n, int /*nb*/, R* d, R* e, R* w, R* z, long ldz, 
       R* qb = q + nd.off + nd.off * ldq;
       const R* qtb = qt + nd.off + nd.off * ldq;
       const R* ub = u + nd.off + nd.off * ldq;
-      if (hd.k > 0) {
+      // the run [r0, r1) of root columns and [f0, f1) of deflated columns (counted from k) that are needed: all of them,
+      // except at the root merge of a partial spectrum
+      int r0 = 0, r1 = hd.k, f0 = 0, f1 = nn - hd.k;
+      if (partial && h == height) {
+        int run[4];
+        int* d_run = dcalloc<int>(4);
+        launch_dc_range(a.dnew + nd.off, nn, hd.k, (int) begin, (int) end, d_run, s);
+        DLAF_HIP_CHECK(hipMemcpyAsync(run, d_run, sizeof(run), hipMemcpyDeviceToHost, s));
+        DLAF_HIP_CHECK(hipStreamSynchronize(s));
+        DLAF_HIP_CHECK(pool_free(d_run));
+        // (the operand ub + c0 keeps the alignment the product's loaders rely on)
+        r0 = run[0] / 16 * 16;
+        r1 = run[1] > run[0] ? std::min(hd.k, (run[1] + 15) / 16 * 16) : r0;
+        f0 = run[2];
+        f1 = run[3];
+      }
+      if (r1 > r0) {
         // the columns [c0, c1) of the non-deflated block this rank computes: all of them, or its slice
-        const bool split = P > 1 && nn >= dist_min && hd.k >= 16 * P;
-        auto cut = [&](int sidx) -> int { return sidx >= P ? hd.k : (int) (((long) hd.k * sidx / P) / 16 * 16); };
+        const int kk = r1 - r0;
+        const bool split = P > 1 && nn >= dist_min && kk >= 16 * P;
+        auto cut = [&](int sidx) -> int { return sidx >= P ? r1 : r0 + (int) (((long) kk * sidx / P) / 16 * 16); };
         const int me = split ? tr->myrow * tr->npcol + tr->mycol : 0;
-        const int c0 = split ? cut(me) : 0, c1 = split ? cut(me + 1) : hd.k;
+        const int c0 = split ? cut(me) : r0, c1 = split ? cut(me + 1) : r1;
         if (c1 > c0) {
           GemmArgs<R> g;
           g.M = nd.n1;
@@ -276,15 +303,15 @@ int tridiag_solver_device(long n, int /*nb*/, R* d, R* e, R* w, R* z, long ldz, 
           tr->group_end();
         }
       }
-      if (hd.k < nn)
-        DLAF_HIP_CHECK(hipMemcpy2DAsync(qb + (long) hd.k * ldq, (size_t) ldq * sizeof(R), qtb + (long) hd.k * ldq,
-                                        (size_t) ldq * sizeof(R), (size_t) nn * sizeof(R), (size_t) (nn - hd.k),
-                                        hipMemcpyDeviceToDevice, s));
+      if (f1 > f0)
+        DLAF_HIP_CHECK(hipMemcpy2DAsync(qb + (long) (hd.k + f0) * ldq, (size_t) ldq * sizeof(R),
+                                        qtb + (long) (hd.k + f0) * ldq, (size_t) ldq * sizeof(R), (size_t) nn * sizeof(R),
+                                        (size_t) (f1 - f0), hipMemcpyDeviceToDevice, s));
     }
     launch_dc_finish(a, cnt, nmax, s);
     first = last;
   }
-  launch_dc_output(q, ldq, d, iv, n, wexp, w, z, ldz, s);
+  launch_dc_output(q, ldq, d, iv, n, wexp, w, z, ldz, begin, end, s);
   int h_info = 0;
   DLAF_HIP_CHECK(hipMemcpyAsync(&h_info, info, sizeof(int), hipMemcpyDeviceToHost, s));
   DLAF_HIP_CHECK(hipStreamSynchronize(s));
@@ -304,23 +331,25 @@ int tridiag_solver_device(long n, int /*nb*/, R* d, R* e, R* w, R* z, long ldz, 
 }
 
 template <class R>
-int tridiag_solver_host(long n, int nb, const R* d, const R* e, R* w, R* z, long ldz) {
+int tridiag_solver_host(long n, int nb, const R* d, const R* e, R* w, R* z, long ldz, long begin, long end) {
   if (n <= 0)
     return 0;
+  const long k = end - begin;
   hipStream_t s;
   DLAF_HIP_CHECK(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
   R* dd = dcalloc<R>((size_t) n);
   R* de = dcalloc<R>((size_t) n);
   R* dw = dcalloc<R>((size_t) n);
-  R* dz = dcalloc<R>((size_t) n * n);
+  R* dz = dcalloc<R>((size_t) n * k);
   DLAF_HIP_CHECK(hipMemsetAsync(de, 0, (size_t) n * sizeof(R), s));
   DLAF_HIP_CHECK(hipMemcpyAsync(dd, d, (size_t) n * sizeof(R), hipMemcpyHostToDevice, s));
   if (n > 1)
     DLAF_HIP_CHECK(hipMemcpyAsync(de, e, (size_t) (n - 1) * sizeof(R), hipMemcpyHostToDevice, s));
-  const int r = tridiag_solver_device<R>(n, nb, dd, de, dw, dz, n, s, nullptr);
+  const int r = tridiag_solver_device<R>(n, nb, dd, de, dw, dz, n, begin, end, s, nullptr);
   DLAF_HIP_CHECK(hipMemcpyAsync(w, dw, (size_t) n * sizeof(R), hipMemcpyDeviceToHost, s));
-  DLAF_HIP_CHECK(hipMemcpy2DAsync(z, (size_t) ldz * sizeof(R), dz, (size_t) n * sizeof(R), (size_t) n * sizeof(R), (size_t) n,
-                                  hipMemcpyDeviceToHost, s));
+  if (k > 0)
+    DLAF_HIP_CHECK(hipMemcpy2DAsync(z, (size_t) ldz * sizeof(R), dz, (size_t) n * sizeof(R), (size_t) n * sizeof(R), (size_t) k,
+                                    hipMemcpyDeviceToHost, s));
   DLAF_HIP_CHECK(hipStreamSynchronize(s));
   for (R* p : {dd, de, dw, dz})
     DLAF_HIP_CHECK(pool_free(p));
@@ -328,9 +357,11 @@ int tridiag_solver_host(long n, int nb, const R* d, const R* e, R* w, R* z, long
   return r;
 }
 
-template int tridiag_solver_device<float>(long, int, float*, float*, float*, float*, long, hipStream_t, Transport*);
-template int tridiag_solver_device<double>(long, int, double*, double*, double*, double*, long, hipStream_t, Transport*);
-template int tridiag_solver_host<float>(long, int, const float*, const float*, float*, float*, long);
-template int tridiag_solver_host<double>(long, int, const double*, const double*, double*, double*, long);
+template int tridiag_solver_device<float>(long, int, float*, float*, float*, float*, long, long, long, hipStream_t,
+                                          Transport*);
+template int tridiag_solver_device<double>(long, int, double*, double*, double*, double*, long, long, long, hipStream_t,
+                                           Transport*);
+template int tridiag_solver_host<float>(long, int, const float*, const float*, float*, float*, long, long, long);
+template int tridiag_solver_host<double>(long, int, const double*, const double*, double*, double*, long, long, long);
 
 }  // namespace dlaf_mi355x

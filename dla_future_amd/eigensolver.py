@@ -127,14 +127,30 @@ def bt_band_to_tridiagonal(band_size: int, e: np.ndarray, v: np.ndarray) -> None
         raise RuntimeError(f"dlaf_mi355x_bt_band_to_tridiagonal_{t} returned {r}")
 
 
-def tridiagonal_eigensolver(d: np.ndarray, e: np.ndarray, nb: int = 512):
+def _index_range(eigenvalues_index, n):
+    begin, end = eigenvalues_index
+    return int(begin), int(end)
+
+
+def tridiagonal_eigensolver(d: np.ndarray, e: np.ndarray, nb: int = 512, eigenvalues_index=None, z: np.ndarray | None = None):
     """tridiagonal_eigensolver(tridiag, evals, evecs) (include/dlaf/eigensolver/tridiag_solver.h:30-60), local:
-    returns (w ascending, z column-major n x n)."""
+    returns (w ascending, z column-major n x n).  eigenvalues_index = (begin, end): only the eigenvectors of the
+    eigenvalues [begin, end) (0-based, half-open) are computed and z is n x (end - begin); w still holds all n
+    eigenvalues.  z: a preallocated column-major array to write into (only its leading n x (end - begin) block is)."""
     t = type_char(d.dtype)
     n = d.shape[0]
     d = np.ascontiguousarray(d)
     e = np.ascontiguousarray(e, dtype=d.dtype)
     w = np.zeros(n, dtype=d.dtype)
+    if eigenvalues_index is not None:
+        begin, end = _index_range(eigenvalues_index, n)
+        if z is None:
+            z = np.zeros((n, max(end - begin, 0)), dtype=d.dtype, order="F")
+        name = f"dlaf_mi355x_tridiagonal_eigensolver_partial_spectrum_{t}"
+        r = getattr(lib(), name)(n, nb, _ptr(d), _ptr(e), _ptr(w), _ptr(z), _ld_of(z), begin, end)
+        if r != 0:
+            raise RuntimeError(f"{name} returned {r}")
+        return w, z
     z = np.zeros((n, n), dtype=d.dtype, order="F")
     r = getattr(lib(), f"dlaf_mi355x_tridiagonal_eigensolver_{t}")(n, nb, _ptr(d), _ptr(e), _ptr(w), _ptr(z), max(1, n))
     if r != 0:
@@ -147,11 +163,16 @@ def _eig_name(t: str) -> str:
 
 
 def hermitian_eigensolver(grid: Grid, uplo: str, a: np.ndarray, nb: int, isrc: int = 0, jsrc: int = 0,
-                          n: int | None = None, z_jsrc: int | None = None, z_shape=None):
+                          n: int | None = None, z_jsrc: int | None = None, z_shape=None, eigenvalues_index=None,
+                          z: np.ndarray | None = None):
     """dlaf::hermitian_eigensolver(grid, uplo, mat_a, evals, evecs) through the reference's C entry
     dlaf_{symmetric,hermitian}_eigensolver_* (include/dlaf_c/eigensolver/eigensolver.h:39-58).  `a` (local part, the uplo
     triangle referenced) is destroyed.  Returns (w, z): all eigenvalues (ascending) and the local part of the
-    eigenvector matrix."""
+    eigenvector matrix.
+
+    eigenvalues_index = (begin, end): the *_partial_spectrum entry -- only the global columns [begin, end) of z (0-based,
+    half-open) are written, with the eigenvectors of those eigenvalues; w still holds all n.  z: a preallocated
+    column-major local part to write into (nothing outside the wanted columns is touched)."""
     t = type_char(a.dtype)
     if n is None:
         if grid.nranks != 1:
@@ -160,32 +181,48 @@ def hermitian_eigensolver(grid: Grid, uplo: str, a: np.ndarray, nb: int, isrc: i
     if z_jsrc is None:
         z_jsrc = jsrc
     w = np.zeros(n, dtype=_real_dtype(a.dtype))
-    z = np.zeros(z_shape if z_shape is not None else a.shape, dtype=a.dtype, order="F")
+    if z is None:
+        z = np.zeros(z_shape if z_shape is not None else a.shape, dtype=a.dtype, order="F")
     da = make_descriptor(n, nb, _ld_of(a), isrc, jsrc)
     dz = make_descriptor(n, nb, _ld_of(z), isrc, z_jsrc)
-    r = getattr(lib(), f"dlaf_{_eig_name(t)}_eigensolver_{t}")(grid.context, uplo.encode()[0:1], _ptr(a), da, _ptr(w),
-                                                              _ptr(z), dz)
+    name = f"dlaf_{_eig_name(t)}_eigensolver_{t}"
+    if eigenvalues_index is None:
+        r = getattr(lib(), name)(grid.context, uplo.encode()[0:1], _ptr(a), da, _ptr(w), _ptr(z), dz)
+    else:
+        name = f"dlaf_{_eig_name(t)}_eigensolver_partial_spectrum_{t}"
+        begin, end = _index_range(eigenvalues_index, n)
+        r = getattr(lib(), name)(grid.context, uplo.encode()[0:1], _ptr(a), da, _ptr(w), _ptr(z), dz, begin, end)
     if r != 0:
-        raise RuntimeError(f"dlaf_{_eig_name(t)}_eigensolver_{t} returned {r}")
+        raise RuntimeError(f"{name} returned {r}")
     return w, z
 
 
 def hermitian_generalized_eigensolver(grid: Grid, uplo: str, a: np.ndarray, b: np.ndarray, nb: int, isrc: int = 0,
-                                      jsrc: int = 0, n: int | None = None, factorized: bool = False):
+                                      jsrc: int = 0, n: int | None = None, factorized: bool = False,
+                                      eigenvalues_index=None, z: np.ndarray | None = None):
     """dlaf::hermitian_generalized_eigensolver(grid, uplo, mat_a, mat_b, evals, evecs) through the reference's C entry
-    (include/dlaf_c/eigensolver/gen_eigensolver.h:44-135).  a is destroyed, b ends up holding its Cholesky factor."""
+    (include/dlaf_c/eigensolver/gen_eigensolver.h:44-135).  a is destroyed, b ends up holding its Cholesky factor.
+    eigenvalues_index, z: as in hermitian_eigensolver."""
     t = type_char(a.dtype)
     if n is None:
         if grid.nranks != 1:
             raise ValueError("the global size n is required on a distributed grid")
         n = a.shape[0]
     w = np.zeros(n, dtype=_real_dtype(a.dtype))
-    z = np.zeros(a.shape, dtype=a.dtype, order="F")
+    if z is None:
+        z = np.zeros(a.shape, dtype=a.dtype, order="F")
     da = make_descriptor(n, nb, _ld_of(a), isrc, jsrc)
     db = make_descriptor(n, nb, _ld_of(b), isrc, jsrc)
     dz = make_descriptor(n, nb, _ld_of(z), isrc, jsrc)
-    name = f"dlaf_{_eig_name(t)}_generalized_eigensolver{'_factorized' if factorized else ''}_{t}"
-    r = getattr(lib(), name)(grid.context, uplo.encode()[0:1], _ptr(a), da, _ptr(b), db, _ptr(w), _ptr(z), dz)
+    name = f"dlaf_{_eig_name(t)}_generalized_eigensolver{'_factorized' if factorized else ''}"
+    if eigenvalues_index is None:
+        name += f"_{t}"
+        r = getattr(lib(), name)(grid.context, uplo.encode()[0:1], _ptr(a), da, _ptr(b), db, _ptr(w), _ptr(z), dz)
+    else:
+        name += f"_partial_spectrum_{t}"
+        begin, end = _index_range(eigenvalues_index, n)
+        r = getattr(lib(), name)(grid.context, uplo.encode()[0:1], _ptr(a), da, _ptr(b), db, _ptr(w), _ptr(z), dz, begin,
+                                 end)
     if r != 0:
         raise RuntimeError(f"{name} returned {r}")
     return w, z
@@ -197,3 +234,25 @@ def eigensolver_profile():
     ms = (C.c_double * 5)()
     lib().dlaf_mi355x_eigensolver_profile(ms)
     return list(ms)
+
+
+def pxheevd_partial_spectrum(uplo: str, a: np.ndarray, desca, z: np.ndarray, descz, il: int, iu: int, n: int):
+    """dlaf_p{s,d}syevd_partial_spectrum / dlaf_p{c,z}heevd_partial_spectrum: the ScaLAPACK-like argument list with the
+    1-based inclusive index range (il, iu) of p?syevx in front of info ((1, 0): the empty range).  desca, descz: the nine
+    integers of the ScaLAPACK descriptors.  Returns (w, info); z is written in place."""
+    t = type_char(a.dtype)
+    name = f"dlaf_p{t}{'syevd' if t in 'sd' else 'heevd'}_partial_spectrum"
+    w = np.zeros(n, dtype=_real_dtype(a.dtype))
+    da = (C.c_int * 9)(*desca)
+    dz = (C.c_int * 9)(*descz)
+    info = C.c_int(-1)
+    getattr(lib(), name)(uplo.encode()[0:1], n, _ptr(a), 1, 1, da, _ptr(w), _ptr(z), 1, 1, dz, il, iu, C.byref(info))
+    return w, info.value
+
+
+def partial_spectrum_plan(n: int, nb: int, npcol: int, mycol: int, z_jsrc: int, begin: int, end: int):
+    """dlaf_mi355x_partial_spectrum_plan (host only): (b0, column source rank of the internal eigenvector matrix, its
+    local columns on process column mycol, the caller's local column its first one corresponds to, leading pad columns)."""
+    out = (C.c_long * 5)()
+    lib().dlaf_mi355x_partial_spectrum_plan(n, nb, npcol, mycol, z_jsrc, begin, end, out)
+    return tuple(out)

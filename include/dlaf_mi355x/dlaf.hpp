@@ -742,6 +742,66 @@ void hermitian_generalized_eigensolver(comm::CommunicatorGrid& grid, blas::Uplo 
     dlaf::internal::fail("hermitian_generalized_eigensolver");
 }
 
+// the eigenvectors of the eigenvalues [eigenvalues_index_begin, eigenvalues_index_end) only (0-based, half-open; the
+// partial-spectrum overloads of later upstream releases): `eigenvalues` still receives all n, and only the global
+// columns of that range are written in `eigenvectors`
+template <Backend B, class T>
+void hermitian_eigensolver(comm::CommunicatorGrid& grid, blas::Uplo uplo, Matrix<T, Device::CPU>& mat,
+                           std::vector<BaseType<T>>& eigenvalues, Matrix<T, Device::CPU>& eigenvectors,
+                           SizeType eigenvalues_index_begin, SizeType eigenvalues_index_end) {
+  static_assert(B == Backend::GPU, "this library has no CPU backend");
+  const char u = uplo == blas::Uplo::Lower ? 'L' : 'U';
+  eigenvalues.assign((size_t) mat.size().rows(), BaseType<T>(0));
+  BaseType<T> dummy{};
+  BaseType<T>* w = eigenvalues.empty() ? &dummy : eigenvalues.data();
+  const DLAF_descriptor da = internal::descriptor_of(mat), dz = internal::descriptor_of(eigenvectors);
+  const int64_t ib = eigenvalues_index_begin, ie = eigenvalues_index_end;
+  int r;
+  if constexpr (std::is_same_v<T, float>)
+    r = dlaf_symmetric_eigensolver_partial_spectrum_s(grid.context(), u, mat.ptr(), da, w, eigenvectors.ptr(), dz, ib, ie);
+  else if constexpr (std::is_same_v<T, double>)
+    r = dlaf_symmetric_eigensolver_partial_spectrum_d(grid.context(), u, mat.ptr(), da, w, eigenvectors.ptr(), dz, ib, ie);
+  else if constexpr (std::is_same_v<T, std::complex<float>>)
+    r = dlaf_hermitian_eigensolver_partial_spectrum_c(grid.context(), u, reinterpret_cast<dlaf_complex_c*>(mat.ptr()), da,
+                                                      w, reinterpret_cast<dlaf_complex_c*>(eigenvectors.ptr()), dz, ib, ie);
+  else
+    r = dlaf_hermitian_eigensolver_partial_spectrum_z(grid.context(), u, reinterpret_cast<dlaf_complex_z*>(mat.ptr()), da,
+                                                      w, reinterpret_cast<dlaf_complex_z*>(eigenvectors.ptr()), dz, ib, ie);
+  if (r != 0)
+    dlaf::internal::fail("hermitian_eigensolver");
+}
+template <Backend B, class T>
+void hermitian_generalized_eigensolver(comm::CommunicatorGrid& grid, blas::Uplo uplo, Matrix<T, Device::CPU>& mat_a,
+                                       Matrix<T, Device::CPU>& mat_b, std::vector<BaseType<T>>& eigenvalues,
+                                       Matrix<T, Device::CPU>& eigenvectors, SizeType eigenvalues_index_begin,
+                                       SizeType eigenvalues_index_end) {
+  static_assert(B == Backend::GPU, "this library has no CPU backend");
+  const char u = uplo == blas::Uplo::Lower ? 'L' : 'U';
+  eigenvalues.assign((size_t) mat_a.size().rows(), BaseType<T>(0));
+  BaseType<T> dummy{};
+  BaseType<T>* w = eigenvalues.empty() ? &dummy : eigenvalues.data();
+  const DLAF_descriptor da = internal::descriptor_of(mat_a), db = internal::descriptor_of(mat_b),
+                        dz = internal::descriptor_of(eigenvectors);
+  const int64_t ib = eigenvalues_index_begin, ie = eigenvalues_index_end;
+  int r;
+  if constexpr (std::is_same_v<T, float>)
+    r = dlaf_symmetric_generalized_eigensolver_partial_spectrum_s(grid.context(), u, mat_a.ptr(), da, mat_b.ptr(), db, w,
+                                                                  eigenvectors.ptr(), dz, ib, ie);
+  else if constexpr (std::is_same_v<T, double>)
+    r = dlaf_symmetric_generalized_eigensolver_partial_spectrum_d(grid.context(), u, mat_a.ptr(), da, mat_b.ptr(), db, w,
+                                                                  eigenvectors.ptr(), dz, ib, ie);
+  else if constexpr (std::is_same_v<T, std::complex<float>>)
+    r = dlaf_hermitian_generalized_eigensolver_partial_spectrum_c(
+        grid.context(), u, reinterpret_cast<dlaf_complex_c*>(mat_a.ptr()), da, reinterpret_cast<dlaf_complex_c*>(mat_b.ptr()),
+        db, w, reinterpret_cast<dlaf_complex_c*>(eigenvectors.ptr()), dz, ib, ie);
+  else
+    r = dlaf_hermitian_generalized_eigensolver_partial_spectrum_z(
+        grid.context(), u, reinterpret_cast<dlaf_complex_z*>(mat_a.ptr()), da, reinterpret_cast<dlaf_complex_z*>(mat_b.ptr()),
+        db, w, reinterpret_cast<dlaf_complex_z*>(eigenvectors.ptr()), dz, ib, ie);
+  if (r != 0)
+    dlaf::internal::fail("hermitian_generalized_eigensolver");
+}
+
 // include/dlaf/init.h: the library needs no runtime arguments; initialize / finalize are idempotent
 inline void initialize(int argc = 0, const char** argv = nullptr) { dlaf_initialize(argc, argv, 0, nullptr); }
 inline void finalize() { dlaf_finalize(); }

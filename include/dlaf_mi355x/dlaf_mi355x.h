@@ -14,6 +14,7 @@
  * a negative value for an invalid argument, or a positive LAPACK info. */
 #pragma once
 #include <stddef.h>
+#include <stdint.h>
 
 #include <dlaf_c/desc.h>
 #include <dlaf_c/utils.h>
@@ -384,6 +385,102 @@ DLAF_EXTERN_C int dlaf_mi355x_tridiagonal_eigensolver_d(int n, int nb, const dou
 /* device time (ms) per stage of the last eigensolver call on this process: reduction_to_band, band_to_tridiagonal,
  * tridiagonal_eigensolver, bt_band_to_tridiagonal, bt_reduction_to_band */
 DLAF_EXTERN_C int dlaf_mi355x_eigensolver_profile(double ms[5]) DLAF_NOEXCEPT;
+
+/* ---- partial spectrum: the eigenvectors of a range of eigenvalue indices ------------------------------------ */
+/* The *_partial_spectrum entries of later DLA-Future releases (they are not in the dlaf_c headers of the snapshot this
+ * library models, so they are declared here under upstream's names).  [eigenvalues_index_begin, eigenvalues_index_end)
+ * is a 0-based half-open range into the ascending eigenvalues, 0 <= begin <= end <= n.  w receives all n eigenvalues on
+ * every rank, the same bits the full entry returns.  z keeps the full entries' description (n x n); its global column
+ * j, j in [begin, end), receives the eigenvector of eigenvalue j and every other element of the local array is left
+ * as the caller passed it.  begin == end is valid (z may then be a null pointer where the local column range is
+ * empty).  A, B and the return value behave as in the full entries.  The p?syevd / p?heevd / p?sygvd / p?hegvd forms
+ * take the full entries' argument lists with il, iu in front of info: 1-based and inclusive as in p?syevx (il = 1,
+ * iu = 0: the empty range). */
+DLAF_EXTERN_C int dlaf_symmetric_eigensolver_partial_spectrum_s(int dlaf_context, char uplo, float* a,
+    struct DLAF_descriptor dlaf_desca, float* w, float* z, struct DLAF_descriptor dlaf_descz,
+    int64_t eigenvalues_index_begin, int64_t eigenvalues_index_end) DLAF_NOEXCEPT;
+DLAF_EXTERN_C int dlaf_symmetric_generalized_eigensolver_partial_spectrum_s(int dlaf_context, char uplo, float* a,
+    struct DLAF_descriptor dlaf_desca, float* b, struct DLAF_descriptor dlaf_descb, float* w, float* z,
+    struct DLAF_descriptor dlaf_descz, int64_t eigenvalues_index_begin, int64_t eigenvalues_index_end) DLAF_NOEXCEPT;
+DLAF_EXTERN_C int dlaf_symmetric_generalized_eigensolver_factorized_partial_spectrum_s(int dlaf_context, char uplo,
+    float* a, struct DLAF_descriptor dlaf_desca, float* b, struct DLAF_descriptor dlaf_descb, float* w, float* z,
+    struct DLAF_descriptor dlaf_descz, int64_t eigenvalues_index_begin, int64_t eigenvalues_index_end) DLAF_NOEXCEPT;
+DLAF_EXTERN_C void dlaf_pssyevd_partial_spectrum(char uplo, int n, float* a, int ia, int ja, const int desca[9],
+    float* w, float* z, int iz, int jz, const int descz[9], int64_t il, int64_t iu, int* info) DLAF_NOEXCEPT;
+DLAF_EXTERN_C void dlaf_pssygvd_partial_spectrum(char uplo, int n, float* a, int ia, int ja, const int desca[9],
+    float* b, int ib, int jb, const int descb[9], float* w, float* z, int iz, int jz, const int descz[9], int64_t il,
+    int64_t iu, int* info) DLAF_NOEXCEPT;
+DLAF_EXTERN_C void dlaf_pssygvd_factorized_partial_spectrum(char uplo, int n, float* a, int ia, int ja,
+    const int desca[9], float* b, int ib, int jb, const int descb[9], float* w, float* z, int iz, int jz,
+    const int descz[9], int64_t il, int64_t iu, int* info) DLAF_NOEXCEPT;
+DLAF_EXTERN_C int dlaf_symmetric_eigensolver_partial_spectrum_d(int dlaf_context, char uplo, double* a,
+    struct DLAF_descriptor dlaf_desca, double* w, double* z, struct DLAF_descriptor dlaf_descz,
+    int64_t eigenvalues_index_begin, int64_t eigenvalues_index_end) DLAF_NOEXCEPT;
+DLAF_EXTERN_C int dlaf_symmetric_generalized_eigensolver_partial_spectrum_d(int dlaf_context, char uplo, double* a,
+    struct DLAF_descriptor dlaf_desca, double* b, struct DLAF_descriptor dlaf_descb, double* w, double* z,
+    struct DLAF_descriptor dlaf_descz, int64_t eigenvalues_index_begin, int64_t eigenvalues_index_end) DLAF_NOEXCEPT;
+DLAF_EXTERN_C int dlaf_symmetric_generalized_eigensolver_factorized_partial_spectrum_d(int dlaf_context, char uplo,
+    double* a, struct DLAF_descriptor dlaf_desca, double* b, struct DLAF_descriptor dlaf_descb, double* w, double* z,
+    struct DLAF_descriptor dlaf_descz, int64_t eigenvalues_index_begin, int64_t eigenvalues_index_end) DLAF_NOEXCEPT;
+DLAF_EXTERN_C void dlaf_pdsyevd_partial_spectrum(char uplo, int n, double* a, int ia, int ja, const int desca[9],
+    double* w, double* z, int iz, int jz, const int descz[9], int64_t il, int64_t iu, int* info) DLAF_NOEXCEPT;
+DLAF_EXTERN_C void dlaf_pdsygvd_partial_spectrum(char uplo, int n, double* a, int ia, int ja, const int desca[9],
+    double* b, int ib, int jb, const int descb[9], double* w, double* z, int iz, int jz, const int descz[9],
+    int64_t il, int64_t iu, int* info) DLAF_NOEXCEPT;
+DLAF_EXTERN_C void dlaf_pdsygvd_factorized_partial_spectrum(char uplo, int n, double* a, int ia, int ja,
+    const int desca[9], double* b, int ib, int jb, const int descb[9], double* w, double* z, int iz, int jz,
+    const int descz[9], int64_t il, int64_t iu, int* info) DLAF_NOEXCEPT;
+DLAF_EXTERN_C int dlaf_hermitian_eigensolver_partial_spectrum_c(int dlaf_context, char uplo, dlaf_complex_c* a,
+    struct DLAF_descriptor dlaf_desca, float* w, dlaf_complex_c* z, struct DLAF_descriptor dlaf_descz,
+    int64_t eigenvalues_index_begin, int64_t eigenvalues_index_end) DLAF_NOEXCEPT;
+DLAF_EXTERN_C int dlaf_hermitian_generalized_eigensolver_partial_spectrum_c(int dlaf_context, char uplo,
+    dlaf_complex_c* a, struct DLAF_descriptor dlaf_desca, dlaf_complex_c* b, struct DLAF_descriptor dlaf_descb,
+    float* w, dlaf_complex_c* z, struct DLAF_descriptor dlaf_descz, int64_t eigenvalues_index_begin,
+    int64_t eigenvalues_index_end) DLAF_NOEXCEPT;
+DLAF_EXTERN_C int dlaf_hermitian_generalized_eigensolver_factorized_partial_spectrum_c(int dlaf_context, char uplo,
+    dlaf_complex_c* a, struct DLAF_descriptor dlaf_desca, dlaf_complex_c* b, struct DLAF_descriptor dlaf_descb,
+    float* w, dlaf_complex_c* z, struct DLAF_descriptor dlaf_descz, int64_t eigenvalues_index_begin,
+    int64_t eigenvalues_index_end) DLAF_NOEXCEPT;
+DLAF_EXTERN_C void dlaf_pcheevd_partial_spectrum(char uplo, int n, dlaf_complex_c* a, int ia, int ja,
+    const int desca[9], float* w, dlaf_complex_c* z, int iz, int jz, const int descz[9], int64_t il, int64_t iu,
+    int* info) DLAF_NOEXCEPT;
+DLAF_EXTERN_C void dlaf_pchegvd_partial_spectrum(char uplo, int n, dlaf_complex_c* a, int ia, int ja,
+    const int desca[9], dlaf_complex_c* b, int ib, int jb, const int descb[9], float* w, dlaf_complex_c* z, int iz,
+    int jz, const int descz[9], int64_t il, int64_t iu, int* info) DLAF_NOEXCEPT;
+DLAF_EXTERN_C void dlaf_pchegvd_factorized_partial_spectrum(char uplo, int n, dlaf_complex_c* a, int ia, int ja,
+    const int desca[9], dlaf_complex_c* b, int ib, int jb, const int descb[9], float* w, dlaf_complex_c* z, int iz,
+    int jz, const int descz[9], int64_t il, int64_t iu, int* info) DLAF_NOEXCEPT;
+DLAF_EXTERN_C int dlaf_hermitian_eigensolver_partial_spectrum_z(int dlaf_context, char uplo, dlaf_complex_z* a,
+    struct DLAF_descriptor dlaf_desca, double* w, dlaf_complex_z* z, struct DLAF_descriptor dlaf_descz,
+    int64_t eigenvalues_index_begin, int64_t eigenvalues_index_end) DLAF_NOEXCEPT;
+DLAF_EXTERN_C int dlaf_hermitian_generalized_eigensolver_partial_spectrum_z(int dlaf_context, char uplo,
+    dlaf_complex_z* a, struct DLAF_descriptor dlaf_desca, dlaf_complex_z* b, struct DLAF_descriptor dlaf_descb,
+    double* w, dlaf_complex_z* z, struct DLAF_descriptor dlaf_descz, int64_t eigenvalues_index_begin,
+    int64_t eigenvalues_index_end) DLAF_NOEXCEPT;
+DLAF_EXTERN_C int dlaf_hermitian_generalized_eigensolver_factorized_partial_spectrum_z(int dlaf_context, char uplo,
+    dlaf_complex_z* a, struct DLAF_descriptor dlaf_desca, dlaf_complex_z* b, struct DLAF_descriptor dlaf_descb,
+    double* w, dlaf_complex_z* z, struct DLAF_descriptor dlaf_descz, int64_t eigenvalues_index_begin,
+    int64_t eigenvalues_index_end) DLAF_NOEXCEPT;
+DLAF_EXTERN_C void dlaf_pzheevd_partial_spectrum(char uplo, int n, dlaf_complex_z* a, int ia, int ja,
+    const int desca[9], double* w, dlaf_complex_z* z, int iz, int jz, const int descz[9], int64_t il, int64_t iu,
+    int* info) DLAF_NOEXCEPT;
+DLAF_EXTERN_C void dlaf_pzhegvd_partial_spectrum(char uplo, int n, dlaf_complex_z* a, int ia, int ja,
+    const int desca[9], dlaf_complex_z* b, int ib, int jb, const int descb[9], double* w, dlaf_complex_z* z, int iz,
+    int jz, const int descz[9], int64_t il, int64_t iu, int* info) DLAF_NOEXCEPT;
+DLAF_EXTERN_C void dlaf_pzhegvd_factorized_partial_spectrum(char uplo, int n, dlaf_complex_z* a, int ia, int ja,
+    const int desca[9], dlaf_complex_z* b, int ib, int jb, const int descb[9], double* w, dlaf_complex_z* z, int iz,
+    int jz, const int descz[9], int64_t il, int64_t iu, int* info) DLAF_NOEXCEPT;
+/* the tridiagonal stage alone: z is n x (end - begin), column j the eigenvector of eigenvalue begin + j; w all n */
+DLAF_EXTERN_C int dlaf_mi355x_tridiagonal_eigensolver_partial_spectrum_s(int n, int nb, const float* d, const float* e,
+    float* w, float* z, int ldz, long begin, long end) DLAF_NOEXCEPT;
+DLAF_EXTERN_C int dlaf_mi355x_tridiagonal_eigensolver_partial_spectrum_d(int n, int nb, const double* d, const double* e,
+    double* w, double* z, int ldz, long begin, long end) DLAF_NOEXCEPT;
+/* index arithmetic of a partial spectrum (no GPU needed).  The drivers keep the wanted eigenvectors in an internal
+ * matrix over the global columns [b0, end), b0 = (begin / nb) nb, whose columns [b0, begin) are zero padding.
+ * out = {b0, column source rank of the internal matrix, local columns of it on process column mycol, the caller's local
+ * column its first local column corresponds to, how many of its leading local columns are padding}. */
+DLAF_EXTERN_C int dlaf_mi355x_partial_spectrum_plan(long n, int nb, int npcol, int mycol, int z_jsrc, long begin,
+                                                    long end, long out[5]) DLAF_NOEXCEPT;
 
 /* Device-resident operands: a general m x n matrix in HBM (tile layout; square blocks) as the right-hand side,
  * a dlaf_mi355x_matrix_t (the uplo triangle of a resident matrix, e.g. the factor dlaf_mi355x_cholesky_* left there)

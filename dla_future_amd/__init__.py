@@ -14,6 +14,7 @@ Python doorway onto that ABI, mirroring the reference's operator surface for the
     dlaf::hermitian_multiplication(side, uplo, ...)    include/dlaf/multiplication/hermitian.h
     dlaf::triangular_inverse(uplo, diag, A)            LAPACK xTRTRI / p?trtri (upstream: after the reference snapshot)
     dlaf::inverse_from_cholesky_factor(uplo, A)        LAPACK xPOTRI / p?potri
+    dlaf::auxiliary::max_norm(grid, rank, uplo, A)     include/dlaf/auxiliary/norm.h (+ one / inf / Frobenius: p?lange, p?lanhe, p?lantr)
     generalized_to_standard(grid, uplo, A, B)          include/dlaf/eigensolver/gen_to_std.h:50,:101
     reduction_to_band / bt_reduction_to_band           include/dlaf/eigensolver/reduction_to_band.h:40-122, bt_reduction_to_band.h
 
@@ -27,7 +28,8 @@ from .cholesky import (DeviceMatrix, GeneralDeviceMatrix, Grid, cholesky_factori
                        triangular_inverse, inverse_from_cholesky_factor, pxtrtri, pxpotri, inverse_profile,
                        update_launch_stats, multiplication_profile, pxtrmm, triangular_multiplication,
                        triangular_multiplication_device, hermitian_multiplication, hermitian_multiplication_device,
-                       pxhemm, update_direct, update_bulk_slots, trsm_direct, potrf_direct)
+                       pxhemm, update_direct, update_bulk_slots, trsm_direct, potrf_direct, matrix_norm,
+                       matrix_norm_device, pxlange, pxlanhe, pxlantr, norm_profile)
 from . import distribution  # noqa: F401
 from .eigensolver import (band_to_tridiagonal, bt_band_to_tridiagonal, bt_reduction_to_band,  # noqa: F401
                           bt_reduction_to_band_device, eigensolver_min_band, eigensolver_profile, get_band_size, hermitian_eigensolver,
@@ -44,4 +46,5 @@ __all__ = ["band_to_tridiagonal", "bt_band_to_tridiagonal", "eigensolver_profile
            "inverse_from_cholesky_factor", "pxtrtri", "pxpotri", "inverse_profile", "type_char", "version",
            "triangular_multiplication", "triangular_multiplication_device", "pxtrmm", "multiplication_profile",
            "hermitian_multiplication", "hermitian_multiplication_device", "pxhemm", "update_direct", "update_bulk_slots",
-           "trsm_direct", "potrf_direct", "pxheevd_partial_spectrum", "partial_spectrum_plan"]
+           "trsm_direct", "potrf_direct", "pxheevd_partial_spectrum", "partial_spectrum_plan", "matrix_norm",
+           "matrix_norm_device", "pxlange", "pxlanhe", "pxlantr", "norm_profile"]

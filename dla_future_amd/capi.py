@@ -185,6 +185,34 @@ SIGNATURES = {
     "dlaf_mi355x_inverse_profile": (_i, [C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     "dlaf_mi355x_inverse_plan": (_i, [C.c_long, _i, _i, _i, _i, _i, _i, _i, C.POINTER(C.c_long)]),
     "dlaf_mi355x_inverse_step": (_i, [C.c_long, _i, _i, _i, _i, _i, _i, _i, C.c_long, C.POINTER(C.c_long)]),
+    "dlaf_mi355x_general_norm_s": (_i, [_i, _ch, _vp, DLAFDescriptor, C.POINTER(C.c_double)]),
+    "dlaf_mi355x_hermitian_norm_s": (_i, [_i, _ch, _ch, _vp, DLAFDescriptor, C.POINTER(C.c_double)]),
+    "dlaf_mi355x_triangular_norm_s": (_i, [_i, _ch, _ch, _ch, _vp, DLAFDescriptor, C.POINTER(C.c_double)]),
+    "dlaf_mi355x_pslange": (C.c_float, [_ch, _i, _i, _vp, _i, _i, _IP]),
+    "dlaf_mi355x_pslansy": (C.c_float, [_ch, _ch, _i, _vp, _i, _i, _IP]),
+    "dlaf_mi355x_pslantr": (C.c_float, [_ch, _ch, _ch, _i, _vp, _i, _i, _IP]),
+    "dlaf_mi355x_general_norm_d": (_i, [_i, _ch, _vp, DLAFDescriptor, C.POINTER(C.c_double)]),
+    "dlaf_mi355x_hermitian_norm_d": (_i, [_i, _ch, _ch, _vp, DLAFDescriptor, C.POINTER(C.c_double)]),
+    "dlaf_mi355x_triangular_norm_d": (_i, [_i, _ch, _ch, _ch, _vp, DLAFDescriptor, C.POINTER(C.c_double)]),
+    "dlaf_mi355x_pdlange": (C.c_double, [_ch, _i, _i, _vp, _i, _i, _IP]),
+    "dlaf_mi355x_pdlansy": (C.c_double, [_ch, _ch, _i, _vp, _i, _i, _IP]),
+    "dlaf_mi355x_pdlantr": (C.c_double, [_ch, _ch, _ch, _i, _vp, _i, _i, _IP]),
+    "dlaf_mi355x_general_norm_c": (_i, [_i, _ch, _vp, DLAFDescriptor, C.POINTER(C.c_double)]),
+    "dlaf_mi355x_hermitian_norm_c": (_i, [_i, _ch, _ch, _vp, DLAFDescriptor, C.POINTER(C.c_double)]),
+    "dlaf_mi355x_triangular_norm_c": (_i, [_i, _ch, _ch, _ch, _vp, DLAFDescriptor, C.POINTER(C.c_double)]),
+    "dlaf_mi355x_pclange": (C.c_float, [_ch, _i, _i, _vp, _i, _i, _IP]),
+    "dlaf_mi355x_pclanhe": (C.c_float, [_ch, _ch, _i, _vp, _i, _i, _IP]),
+    "dlaf_mi355x_pclantr": (C.c_float, [_ch, _ch, _ch, _i, _vp, _i, _i, _IP]),
+    "dlaf_mi355x_general_norm_z": (_i, [_i, _ch, _vp, DLAFDescriptor, C.POINTER(C.c_double)]),
+    "dlaf_mi355x_hermitian_norm_z": (_i, [_i, _ch, _ch, _vp, DLAFDescriptor, C.POINTER(C.c_double)]),
+    "dlaf_mi355x_triangular_norm_z": (_i, [_i, _ch, _ch, _ch, _vp, DLAFDescriptor, C.POINTER(C.c_double)]),
+    "dlaf_mi355x_pzlange": (C.c_double, [_ch, _i, _i, _vp, _i, _i, _IP]),
+    "dlaf_mi355x_pzlanhe": (C.c_double, [_ch, _ch, _i, _vp, _i, _i, _IP]),
+    "dlaf_mi355x_pzlantr": (C.c_double, [_ch, _ch, _ch, _i, _vp, _i, _i, _IP]),
+    "dlaf_mi355x_matrix_norm": (_i, [_vp, _ch, _ch, _ch, C.POINTER(C.c_double)]),
+    "dlaf_mi355x_general_matrix_norm": (_i, [_vp, _ch, C.POINTER(C.c_double)]),
+    "dlaf_mi355x_gmatrix_device_tiles": (_i, [_vp, C.POINTER(_vp), C.POINTER(C.c_size_t)]),
+    "dlaf_mi355x_norm_profile": (_i, [C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     "dlaf_mi355x_reduction_to_band_s": (_i, [_i, _vp, DLAFDescriptor, _i, _vp]),
     "dlaf_mi355x_reduction_to_band_d": (_i, [_i, _vp, DLAFDescriptor, _i, _vp]),
     "dlaf_mi355x_reduction_to_band_c": (_i, [_i, _vp, DLAFDescriptor, _i, _vp]),

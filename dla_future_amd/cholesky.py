@@ -601,6 +601,83 @@ def potrs_device(uplo: str, factor: DeviceMatrix, b: GeneralDeviceMatrix) -> Non
         raise ValueError(f"dlaf_mi355x_potrs_device failed with {r}")
 
 
+NORM_ERRORS = {-1: "bad norm letter", -2: "bad uplo", -3: "bad diag", -4: "bad descriptor", -5: "source process outside the grid",
+               -6: "missing value or context"}
+
+
+def matrix_norm(grid: Grid, norm: str, a: np.ndarray, nb: int, structure: str = "G", uplo: str = "L", diag: str = "N",
+                m: int | None = None, n: int | None = None, isrc: int = 0, jsrc: int = 0) -> float:
+    """dlaf::auxiliary::max_norm and its one / infinity / Frobenius siblings == dlaf_mi355x_{general,hermitian,
+    triangular}_norm_{s,d,c,z} (LAPACK xLANGE, xLANHE / xLANSY, xLANTR).  norm: 'M', '1' / 'O', 'I', 'F' / 'E';
+    structure 'G' (the m x n matrix), 'H' (Hermitian from the uplo triangle) or 'T' (triangular, diag 'N' / 'U').
+    `a`: this process's local column-major part, only read.  The value is the same on every rank."""
+    t = type_char(a.dtype)
+    if m is None or n is None:
+        if grid.nranks != 1:
+            raise ValueError("the global size m x n is required on a distributed grid")
+        m, n = a.shape
+    da = DLAFDescriptor(m, n, nb, nb, isrc, jsrc, 0, 0, _ld_of(a))
+    v = C.c_double(-1.0)
+    s = structure.upper()
+    if s == "G":
+        r = getattr(lib(), f"dlaf_mi355x_general_norm_{t}")(grid.context, norm.encode(), _ptr(a), da, C.byref(v))
+    elif s in ("H", "S"):
+        r = getattr(lib(), f"dlaf_mi355x_hermitian_norm_{t}")(grid.context, norm.encode(), uplo.encode(), _ptr(a), da,
+                                                              C.byref(v))
+    elif s == "T":
+        r = getattr(lib(), f"dlaf_mi355x_triangular_norm_{t}")(grid.context, norm.encode(), uplo.encode(), diag.encode(),
+                                                               _ptr(a), da, C.byref(v))
+    else:
+        raise ValueError(f"structure must be 'G', 'H' or 'T', got {structure!r}")
+    if r != 0:
+        raise ValueError(f"matrix_norm failed with {r}: {NORM_ERRORS.get(r, '?')}")
+    return v.value
+
+
+def matrix_norm_device(norm: str, A, structure: str | None = None, diag: str = "N") -> float:
+    """The norm of a resident operand, no PCIe traffic but the value: a GeneralDeviceMatrix (structure None / 'G') or the
+    triangle a DeviceMatrix holds, read as Hermitian ('H', the default) or triangular ('T', diag 'N' / 'U')."""
+    v = C.c_double(-1.0)
+    if isinstance(A, GeneralDeviceMatrix):
+        if structure not in (None, "G", "g"):
+            raise ValueError("a GeneralDeviceMatrix is a general matrix")
+        r = lib().dlaf_mi355x_general_matrix_norm(A._h, norm.encode(), C.byref(v))
+    else:
+        r = lib().dlaf_mi355x_matrix_norm(A._h, norm.encode(), (structure or "H").encode(), diag.encode(), C.byref(v))
+    if r != 0:
+        raise ValueError(f"matrix_norm_device failed with {r}: {NORM_ERRORS.get(r, '?')}")
+    return v.value
+
+
+def pxlange(norm: str, m: int, n: int, a: np.ndarray, ia: int, ja: int, desca) -> float:
+    """dlaf_mi355x_p{s,d,c,z}lange: ScaLAPACK's p?lange argument list without work; returns the value."""
+    da = (C.c_int * 9)(*[int(x) for x in desca])
+    return float(getattr(lib(), f"dlaf_mi355x_p{type_char(a.dtype)}lange")(norm.encode(), m, n, _ptr(a), ia, ja, da))
+
+
+def pxlanhe(norm: str, uplo: str, n: int, a: np.ndarray, ia: int, ja: int, desca) -> float:
+    """dlaf_mi355x_p{c,z}lanhe / p{s,d}lansy: ScaLAPACK's argument list without work; returns the value."""
+    t = type_char(a.dtype)
+    da = (C.c_int * 9)(*[int(x) for x in desca])
+    name = f"dlaf_mi355x_p{t}lan{'he' if t in 'cz' else 'sy'}"
+    return float(getattr(lib(), name)(norm.encode(), uplo.encode(), n, _ptr(a), ia, ja, da))
+
+
+def pxlantr(norm: str, uplo: str, diag: str, n: int, a: np.ndarray, ia: int, ja: int, desca) -> float:
+    """dlaf_mi355x_p{s,d,c,z}lantr: ScaLAPACK's p?lantr argument list without work; returns the value."""
+    da = (C.c_int * 9)(*[int(x) for x in desca])
+    return float(getattr(lib(), f"dlaf_mi355x_p{type_char(a.dtype)}lantr")(norm.encode(), uplo.encode(), diag.encode(), n,
+                                                                         _ptr(a), ia, ja, da))
+
+
+def norm_profile():
+    """(ms, bytes) of the last norm on this process: device time (no upload) and the bytes of the tiles it referenced
+    (diagonal tiles counted whole)."""
+    ms, by = C.c_double(0), C.c_double(0)
+    lib().dlaf_mi355x_norm_profile(C.byref(ms), C.byref(by))
+    return ms.value, by.value
+
+
 # ---- tile operations with the argument sets the factorization issues ----------------------------
 def tile_potrf(uplo: str, a: np.ndarray) -> int:
     """tile::potrf (include/dlaf/lapack/tile.h:362-378); returns info."""

@@ -5,6 +5,7 @@
 #include <hip/hip_runtime.h>
 
 #include "common.hpp"
+#include "norm_split.hpp"
 
 namespace dlaf_mi355x {
 
@@ -309,6 +310,35 @@ void launch_max_norm(const T* tiles, int ltr, int ltc, int nb, long rows, long c
                      double* out, hipStream_t stream);
 template <class T>
 void launch_zero_upper_diag(T* tiles, int ltr, int ltc, int nb, int pr, int ri, int pc, int ci, hipStream_t stream);
+
+// ---- matrix norms (kernels_norm.hip; work split and partial-buffer layout: norm_split.hpp) -------------------------
+// Pass 1 streams the referenced tiles once and writes, with plain stores and one writer per slot, per-unit scalars
+// (max, NaN flag, the big / medium / small accumulators of xLASSQ's sum of squares) and partial column / row sums;
+// everything accumulates in fp64.  Only what `mode` needs is computed.  Structure 1 (Hermitian): strictly-lower stored
+// elements count for (i, j) and (j, i) -- column AND row sums, weight 2 in the sum of squares --, the diagonal once and
+// with its real part only.  Structure 2 (triangular): unit != 0 takes the diagonal as 1 without reading it.
+enum NormMode : int { kNormMax = 0, kNormCol = 1, kNormRow = 2, kNormColRow = 3, kNormFro = 4 };
+template <class T>
+struct NormArgs {
+  const T* tiles;
+  NormGeom g;
+  NormSplit s;
+  int unit;
+  int mode;
+  double* scal;  // norm_unit_count * kNormScalars
+  double* colp;  // norm_colp_elems (modes with column sums)
+  double* rowp;  // norm_rowp_elems (modes with row sums)
+};
+template <class T>
+void launch_norm_pass1(const NormArgs<T>& a, hipStream_t stream);
+// Pass 2, fixed order: out[0 .. kNormScalars) from the scalars of all units (max, flag: max; accumulators: sum)
+void launch_norm_scalars(const double* scal, long units, double* out, hipStream_t stream);
+// v[x] for the global index x in [0, len): the column sums of global column x (mode & kNormCol) plus the row sums of
+// global row x (mode & kNormRow) over this process's live units, 0 where it holds neither
+void launch_norm_vector(const NormGeom& g, const NormSplit& s, int mode, const double* colp, const double* rowp,
+                        double* v, long len, hipStream_t stream);
+// *out = max of v[0 .. len) (0 for len == 0)
+void launch_norm_vecmax(const double* v, long len, double* out, hipStream_t stream);
 
 // one-off: opt the kernels into > 64 KiB of dynamic LDS
 void device_kernels_init();

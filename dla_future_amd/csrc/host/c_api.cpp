@@ -366,6 +366,57 @@ void pxinverse(char uplo, char diag, bool product, int n, HT* a, int ia, int ja,
     *info = r;
 }
 
+// dlaf::auxiliary norms through descriptors (norm.cpp): structure 'G' general, 'H' Hermitian / symmetric, 'T' triangular.
+// Every argument is judged before anything touches the GPU; the codes are the header's.
+template <class HT>
+int norm_c(int ctx, char norm, char structure, char uplo, char diag, const HT* a, const DLAF_descriptor& da,
+           double* value) {
+  using DT = typename DevType<HT>::type;
+  auto is = [](char c, const char* set) { return c != 0 && std::strchr(set, c) != nullptr; };
+  if (!value)
+    return -6;
+  if (norm_kind(norm) == 0)
+    return -1;
+  if (structure != 'G' && !is(uplo, "LlUu"))
+    return -2;
+  if (structure == 'T' && !is(diag, "NnUu"))
+    return -3;
+  if (da.i != 0 || da.j != 0 || da.mb != da.nb || da.nb < 1 || da.m < 0 || da.n < 0 ||
+      (structure != 'G' && da.m != da.n))
+    return -4;
+  auto it = g_grids.find(ctx);
+  if (it == g_grids.end())
+    return -6;
+  Grid& g = *it->second;
+  if (da.isrc < 0 || da.isrc >= g.nprow || da.jsrc < 0 || da.jsrc >= g.npcol)
+    return -5;
+  if (da.m == 0 || da.n == 0) {
+    *value = 0.0;
+    return 0;
+  }
+  const DT* ad = reinterpret_cast<const DT*>(a);
+  *value = structure == 'G' ? general_norm_host<DT>(&g, norm, ad, da.ld, da.m, da.n, da.nb, da.isrc, da.jsrc)
+                            : structured_norm_host<DT>(&g, norm, structure, uplo, diag, ad, da.ld, da.m, da.nb, da.isrc,
+                                                       da.jsrc);
+  return 0;
+}
+
+// ScaLAPACK p?lange / p?lansy / p?lanhe / p?lantr argument lists (without work); the value is returned
+template <class HT>
+double pxnorm(char norm, char structure, char uplo, char diag, int m, int n, const HT* a, int ia, int ja,
+              const int desca[9]) {
+  if (desca[0] != 1)
+    fatal("[dlaf_mi355x] desc[0] (dtype) must be 1\n");
+  if (ia != 1 || ja != 1)
+    fatal("[dlaf_mi355x] ia, ja must be 1\n");
+  const DLAF_descriptor da = make_dlaf_descriptor(m, n, ia, ja, desca);
+  double v = 0.0;
+  const int r = norm_c<HT>(desca[1], norm, structure, uplo, diag, a, da, &v);
+  if (r != 0)
+    fatal("[dlaf_mi355x] p?lan*: bad argument (code %d; norm '%c', uplo '%c', diag '%c')\n", r, norm, uplo, diag);
+  return v;
+}
+
 // dlaf::eigensolver::internal::reduction_to_band (include/dlaf/eigensolver/reduction_to_band.h:101-122) through the
 // reference's descriptor conventions
 template <class HT>
@@ -853,6 +904,35 @@ DLAF_MI355X_INVERSE_ENTRY(c, std::complex<float>, dlaf_complex_c)
 DLAF_MI355X_INVERSE_ENTRY(z, std::complex<double>, dlaf_complex_z)
 #undef DLAF_MI355X_INVERSE_ENTRY
 
+#define DLAF_MI355X_NORM_ENTRY(S, HT, CT, RT, HE)                                                                  \
+  int dlaf_mi355x_general_norm_##S(int ctx, char norm, const CT* a, DLAF_descriptor desca, double* value) noexcept { \
+    return norm_c<HT>(ctx, norm, 'G', 'L', 'N', reinterpret_cast<const HT*>(a), desca, value);                      \
+  }                                                                                                                \
+  int dlaf_mi355x_hermitian_norm_##S(int ctx, char norm, char uplo, const CT* a, DLAF_descriptor desca,             \
+                                     double* value) noexcept {                                                     \
+    return norm_c<HT>(ctx, norm, 'H', uplo, 'N', reinterpret_cast<const HT*>(a), desca, value);                     \
+  }                                                                                                                \
+  int dlaf_mi355x_triangular_norm_##S(int ctx, char norm, char uplo, char diag, const CT* a, DLAF_descriptor desca, \
+                                      double* value) noexcept {                                                    \
+    return norm_c<HT>(ctx, norm, 'T', uplo, diag, reinterpret_cast<const HT*>(a), desca, value);                    \
+  }                                                                                                                \
+  RT dlaf_mi355x_p##S##lange(char norm, int m, int n, const CT* a, int ia, int ja, const int desca[9]) noexcept {    \
+    return (RT) pxnorm<HT>(norm, 'G', 'L', 'N', m, n, reinterpret_cast<const HT*>(a), ia, ja, desca);               \
+  }                                                                                                                \
+  RT dlaf_mi355x_p##S##lan##HE(char norm, char uplo, int n, const CT* a, int ia, int ja,                            \
+                               const int desca[9]) noexcept {                                                      \
+    return (RT) pxnorm<HT>(norm, 'H', uplo, 'N', n, n, reinterpret_cast<const HT*>(a), ia, ja, desca);              \
+  }                                                                                                                \
+  RT dlaf_mi355x_p##S##lantr(char norm, char uplo, char diag, int n, const CT* a, int ia, int ja,                   \
+                             const int desca[9]) noexcept {                                                        \
+    return (RT) pxnorm<HT>(norm, 'T', uplo, diag, n, n, reinterpret_cast<const HT*>(a), ia, ja, desca);             \
+  }
+DLAF_MI355X_NORM_ENTRY(s, float, float, float, sy)
+DLAF_MI355X_NORM_ENTRY(d, double, double, double, sy)
+DLAF_MI355X_NORM_ENTRY(c, std::complex<float>, dlaf_complex_c, float, he)
+DLAF_MI355X_NORM_ENTRY(z, std::complex<double>, dlaf_complex_z, double, he)
+#undef DLAF_MI355X_NORM_ENTRY
+
 #define DLAF_MI355X_R2B_ENTRY(S, HT, CT)                                                                          \
   int dlaf_mi355x_reduction_to_band_##S(int ctx, CT* a, DLAF_descriptor desca, int band, CT* taus) noexcept {     \
     return red2band_c<HT>(ctx, reinterpret_cast<HT*>(a), desca, band, reinterpret_cast<HT*>(taus));               \
@@ -1248,6 +1328,42 @@ int dlaf_mi355x_inverse_step(long n, int nb, int nprow, int npcol, int myrow, in
   const InverseStep st = inverse_step_ranges(rows, cols, k);
   const long v[7] = {st.own_r, st.own_c, st.il_below, st.nrl, st.ncl, st.lr, st.lc};
   std::copy(v, v + 7, out);
+  return 0;
+}
+
+int dlaf_mi355x_matrix_norm(dlaf_mi355x_matrix_t m, char norm, char structure, char diag, double* value) noexcept {
+  if (!value)
+    return -6;
+  if (norm_kind(norm) == 0)
+    return -1;
+  if (std::strchr("HhSsTt", structure) == nullptr || structure == 0)
+    return -4;
+  const bool tri = structure == 'T' || structure == 't';
+  if (tri && (diag == 0 || std::strchr("NnUu", diag) == nullptr))
+    return -3;
+  WITH_MATRIX(m, *value = structured_norm_device(norm, structure, diag, M); return 0;)
+}
+int dlaf_mi355x_general_matrix_norm(dlaf_mi355x_gmatrix_t m, char norm, double* value) noexcept {
+  if (!m || !m->m || !value)
+    return -6;
+  if (norm_kind(norm) == 0)
+    return -1;
+  *value = general_norm_device(norm, m->m.get());
+  return 0;
+}
+int dlaf_mi355x_gmatrix_device_tiles(dlaf_mi355x_gmatrix_t m, const void** tiles, size_t* bytes) noexcept {
+  if (!m || !m->m || !tiles || !bytes)
+    return -6;
+  return dispatch_api_type(m->m->type, [&](auto* tag) -> int {
+    using DT = std::remove_pointer_t<decltype(tag)>;
+    const auto& t = static_cast<GeneralMatrix<DT>&>(*m->m).m;
+    *tiles = t.tiles;
+    *bytes = (size_t) t.ltr * t.ltc * t.tile_elems * sizeof(DT);
+    return 0;
+  });
+}
+int dlaf_mi355x_norm_profile(double* ms, double* bytes) noexcept {
+  norm_last_profile(ms, bytes);
   return 0;
 }
 

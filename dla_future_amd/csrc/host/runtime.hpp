@@ -379,6 +379,23 @@ struct InverseStep {
 InverseStep inverse_step_ranges(const Axis& rows, const Axis& cols, long k);
 long inverse_workspace_tiles(const Axis& rows, const Axis& cols);
 
+// Max / one / infinity / Frobenius norm (norm.cpp; LAPACK xLANGE, xLANHE / xLANSY, xLANTR): norm letters M, 1 / O, I,
+// F / E in either case; structure 'G' general, 'H' Hermitian / symmetric from the uplo triangle, 'T' triangular from the
+// uplo triangle with diag N / U.  The operand is only read.  Host forms upload this process's local column-major part
+// and write nothing back; the value -- for s / c the float result widened -- is the same bits on every rank.
+// norm_kind: the canonical letter (M, 1, I, F) of a norm letter, 0 for any other character.
+char norm_kind(char norm);
+template <class T>
+double general_norm_host(Grid* g, char norm, const T* a, long lda, long m, long n, int nb, int isrc, int jsrc);
+template <class T>
+double structured_norm_host(Grid* g, char norm, char structure, char uplo, char diag, const T* a, long lda, long n, int nb,
+                            int isrc, int jsrc);
+template <class T>
+double structured_norm_device(char norm, char structure, char diag, const DeviceMatrix<T>& a);
+double general_norm_device(char norm, MatrixBase* general_matrix);
+// device time and the bytes of the referenced tiles (diagonal tiles whole) of the last norm on this process
+void norm_last_profile(double* ms, double* bytes);
+
 void runtime_init();
 void runtime_finalize();
 bool runtime_initialized();

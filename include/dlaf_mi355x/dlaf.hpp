@@ -582,6 +582,104 @@ int inverse_from_cholesky_factor(blas::Uplo uplo, Matrix<T, Device::CPU>& mat_a)
   return inverse_from_cholesky_factor<B, T>(grid, uplo, mat_a);
 }
 
+// dlaf::auxiliary::max_norm (include/dlaf/auxiliary/norm.h) and its one / infinity / Frobenius siblings (LAPACK xLANGE,
+// xLANHE / xLANSY, xLANTR).  The operand is only read.  The value comes back on EVERY rank (the reference defines it on
+// `rank` alone), and Upper, which the reference leaves unimplemented, is built.
+namespace lapack {
+enum class Norm : char { One = '1', Inf = 'I', Fro = 'F', Max = 'M' };
+}
+namespace auxiliary {
+namespace internal {
+// structure 'G' / 'H' / 'T'
+template <class T>
+BaseType<T> norm_host(int ctx, lapack::Norm norm, char structure, blas::Uplo uplo, blas::Diag diag,
+                      Matrix<T, Device::CPU>& m) {
+  const auto& d = m.distribution();
+  const DLAF_descriptor desc{(int) d.size().rows(), (int) d.size().cols(), (int) d.block_size().rows(),
+                             (int) d.block_size().cols(), (int) d.source_rank_index().row(),
+                             (int) d.source_rank_index().col(), 0, 0, (int) m.ld()};
+  double v = 0;
+  int r;
+  const char nc = (char) norm, uc = (char) uplo, dc = (char) diag;
+  if constexpr (std::is_same_v<T, float>)
+    r = structure == 'G'   ? dlaf_mi355x_general_norm_s(ctx, nc, m.ptr(), desc, &v)
+        : structure == 'H' ? dlaf_mi355x_hermitian_norm_s(ctx, nc, uc, m.ptr(), desc, &v)
+                           : dlaf_mi355x_triangular_norm_s(ctx, nc, uc, dc, m.ptr(), desc, &v);
+  else if constexpr (std::is_same_v<T, double>)
+    r = structure == 'G'   ? dlaf_mi355x_general_norm_d(ctx, nc, m.ptr(), desc, &v)
+        : structure == 'H' ? dlaf_mi355x_hermitian_norm_d(ctx, nc, uc, m.ptr(), desc, &v)
+                           : dlaf_mi355x_triangular_norm_d(ctx, nc, uc, dc, m.ptr(), desc, &v);
+  else if constexpr (std::is_same_v<T, std::complex<float>>)
+    r = structure == 'G'   ? dlaf_mi355x_general_norm_c(ctx, nc, m.ptr(), desc, &v)
+        : structure == 'H' ? dlaf_mi355x_hermitian_norm_c(ctx, nc, uc, m.ptr(), desc, &v)
+                           : dlaf_mi355x_triangular_norm_c(ctx, nc, uc, dc, m.ptr(), desc, &v);
+  else
+    r = structure == 'G'   ? dlaf_mi355x_general_norm_z(ctx, nc, m.ptr(), desc, &v)
+        : structure == 'H' ? dlaf_mi355x_hermitian_norm_z(ctx, nc, uc, m.ptr(), desc, &v)
+                           : dlaf_mi355x_triangular_norm_z(ctx, nc, uc, dc, m.ptr(), desc, &v);
+  if (r != 0)
+    dlaf::internal::fail("norm: bad argument");
+  return (BaseType<T>) v;
+}
+template <class T>
+BaseType<T> norm_device(comm::CommunicatorGrid& grid, lapack::Norm norm, char structure, blas::Uplo uplo,
+                        blas::Diag diag, Matrix<T, Device::GPU>& m) {
+  if (grid.context() != m.context())
+    dlaf::internal::fail("matrix::equal_process_grid(A, grid)");
+  if (uplo != m.uplo())
+    dlaf::internal::fail("a device matrix holds the triangle it was created with");
+  double v = 0;
+  if (dlaf_mi355x_matrix_norm(m.handle(), (char) norm, structure, (char) diag, &v) != 0)
+    dlaf::internal::fail("norm: bad argument");
+  return (BaseType<T>) v;
+}
+}  // namespace internal
+
+// general matrix
+template <Backend B, class T>
+BaseType<T> norm(comm::CommunicatorGrid& grid, lapack::Norm norm_type, Matrix<T, Device::CPU>& A) {
+  static_assert(B == Backend::GPU, "this library has no CPU backend");
+  return internal::norm_host<T>(grid.context(), norm_type, 'G', blas::Uplo::General, blas::Diag::NonUnit, A);
+}
+// Hermitian (symmetric) matrix held in its uplo triangle
+template <Backend B, class T>
+BaseType<T> norm(comm::CommunicatorGrid& grid, lapack::Norm norm_type, blas::Uplo uplo, Matrix<T, Device::CPU>& A) {
+  static_assert(B == Backend::GPU, "this library has no CPU backend");
+  if (uplo == blas::Uplo::General)
+    return norm<B, T>(grid, norm_type, A);
+  return internal::norm_host<T>(grid.context(), norm_type, 'H', uplo, blas::Diag::NonUnit, A);
+}
+template <Backend B, class T>
+BaseType<T> norm(comm::CommunicatorGrid& grid, lapack::Norm norm_type, blas::Uplo uplo, Matrix<T, Device::GPU>& A) {
+  static_assert(B == Backend::GPU, "this library has no CPU backend");
+  return internal::norm_device<T>(grid, norm_type, 'H', uplo, blas::Diag::NonUnit, A);
+}
+// triangular matrix held in its uplo triangle
+template <Backend B, class T>
+BaseType<T> norm(comm::CommunicatorGrid& grid, lapack::Norm norm_type, blas::Uplo uplo, blas::Diag diag,
+                 Matrix<T, Device::CPU>& A) {
+  static_assert(B == Backend::GPU, "this library has no CPU backend");
+  return internal::norm_host<T>(grid.context(), norm_type, 'T', uplo, diag, A);
+}
+template <Backend B, class T>
+BaseType<T> norm(comm::CommunicatorGrid& grid, lapack::Norm norm_type, blas::Uplo uplo, blas::Diag diag,
+                 Matrix<T, Device::GPU>& A) {
+  static_assert(B == Backend::GPU, "this library has no CPU backend");
+  return internal::norm_device<T>(grid, norm_type, 'T', uplo, diag, A);
+}
+
+// max |a_ij| over the whole matrix (General) or over its uplo triangle (Lower, Upper)
+template <Backend B, Device D, class T>
+BaseType<T> max_norm(comm::CommunicatorGrid& grid, comm::Index2D /*rank*/, blas::Uplo uplo, Matrix<T, D>& A) {
+  static_assert(B == Backend::GPU, "this library has no CPU backend");
+  if constexpr (D == Device::CPU) {
+    if (uplo == blas::Uplo::General)
+      return norm<B, T>(grid, lapack::Norm::Max, A);
+  }
+  return norm<B, T>(grid, lapack::Norm::Max, uplo, blas::Diag::NonUnit, A);
+}
+}  // namespace auxiliary
+
 // include/dlaf/eigensolver/reduction_to_band.h:40-122 and bt_reduction_to_band.h (first stage).
 // The reference returns the taus as a Matrix<T, Device::CPU> distributed over the process columns; here every
 // process gets all n - band_size - 1 of them as a std::vector (entry j belongs to the reflector in global column j).

@@ -650,6 +650,78 @@ DLAF_EXTERN_C int dlaf_mi355x_inverse_plan(long n, int nb, int nprow, int npcol,
 DLAF_EXTERN_C int dlaf_mi355x_inverse_step(long n, int nb, int nprow, int npcol, int myrow, int mycol, int isrc,
                                            int jsrc, long k, long out[7]) DLAF_NOEXCEPT;
 
+/* ---- matrix norms (LAPACK xLANGE, xLANHE / xLANSY, xLANTR) --------------------------------------------------- */
+/* norm: 'M' max |a_ij|, '1' / 'O' max column sum, 'I' max row sum, 'F' / 'E' Frobenius, either case.
+ * general_norm: the m x n matrix.  hermitian_norm: the Hermitian (s, d: symmetric) n x n matrix whose uplo triangle a
+ * holds; only the real part of its diagonal is used.  triangular_norm: the triangular matrix in a's uplo triangle;
+ * with diag 'U' the stored diagonal is not read and counts as 1.  Nothing outside the referenced part influences the
+ * value, and a is only read.  Square blocks, offsets 0, any source process.  *value (for s / c the float result
+ * widened) is the same on every rank; any NaN in the referenced part gives NaN, otherwise any Inf gives +Inf; m = 0 or
+ * n = 0 gives 0.  Return 0, or -1 bad norm, -2 bad uplo, -3 bad diag, -4 descriptor (offsets, blocks, sizes, square
+ * for the Hermitian and the triangular form), -5 source process outside the grid, -6 value or context missing --
+ * all decided before the GPU is touched.  The p?lan* names take ScaLAPACK's argument lists without `work`
+ * (ia = ja = 1) and return the value. */
+DLAF_EXTERN_C int dlaf_mi355x_general_norm_s(int context, char norm, const float* a, struct DLAF_descriptor desca,
+                                             double* value) DLAF_NOEXCEPT;
+DLAF_EXTERN_C int dlaf_mi355x_general_norm_d(int context, char norm, const double* a, struct DLAF_descriptor desca,
+                                             double* value) DLAF_NOEXCEPT;
+DLAF_EXTERN_C int dlaf_mi355x_general_norm_c(int context, char norm, const dlaf_complex_c* a,
+                                             struct DLAF_descriptor desca, double* value) DLAF_NOEXCEPT;
+DLAF_EXTERN_C int dlaf_mi355x_general_norm_z(int context, char norm, const dlaf_complex_z* a,
+                                             struct DLAF_descriptor desca, double* value) DLAF_NOEXCEPT;
+DLAF_EXTERN_C int dlaf_mi355x_hermitian_norm_s(int context, char norm, char uplo, const float* a,
+                                               struct DLAF_descriptor desca, double* value) DLAF_NOEXCEPT;
+DLAF_EXTERN_C int dlaf_mi355x_hermitian_norm_d(int context, char norm, char uplo, const double* a,
+                                               struct DLAF_descriptor desca, double* value) DLAF_NOEXCEPT;
+DLAF_EXTERN_C int dlaf_mi355x_hermitian_norm_c(int context, char norm, char uplo, const dlaf_complex_c* a,
+                                               struct DLAF_descriptor desca, double* value) DLAF_NOEXCEPT;
+DLAF_EXTERN_C int dlaf_mi355x_hermitian_norm_z(int context, char norm, char uplo, const dlaf_complex_z* a,
+                                               struct DLAF_descriptor desca, double* value) DLAF_NOEXCEPT;
+DLAF_EXTERN_C int dlaf_mi355x_triangular_norm_s(int context, char norm, char uplo, char diag, const float* a,
+                                                struct DLAF_descriptor desca, double* value) DLAF_NOEXCEPT;
+DLAF_EXTERN_C int dlaf_mi355x_triangular_norm_d(int context, char norm, char uplo, char diag, const double* a,
+                                                struct DLAF_descriptor desca, double* value) DLAF_NOEXCEPT;
+DLAF_EXTERN_C int dlaf_mi355x_triangular_norm_c(int context, char norm, char uplo, char diag, const dlaf_complex_c* a,
+                                                struct DLAF_descriptor desca, double* value) DLAF_NOEXCEPT;
+DLAF_EXTERN_C int dlaf_mi355x_triangular_norm_z(int context, char norm, char uplo, char diag, const dlaf_complex_z* a,
+                                                struct DLAF_descriptor desca, double* value) DLAF_NOEXCEPT;
+DLAF_EXTERN_C float dlaf_mi355x_pslange(char norm, int m, int n, const float* a, int ia, int ja,
+                                        const int desca[9]) DLAF_NOEXCEPT;
+DLAF_EXTERN_C double dlaf_mi355x_pdlange(char norm, int m, int n, const double* a, int ia, int ja,
+                                         const int desca[9]) DLAF_NOEXCEPT;
+DLAF_EXTERN_C float dlaf_mi355x_pclange(char norm, int m, int n, const dlaf_complex_c* a, int ia, int ja,
+                                        const int desca[9]) DLAF_NOEXCEPT;
+DLAF_EXTERN_C double dlaf_mi355x_pzlange(char norm, int m, int n, const dlaf_complex_z* a, int ia, int ja,
+                                         const int desca[9]) DLAF_NOEXCEPT;
+DLAF_EXTERN_C float dlaf_mi355x_pslansy(char norm, char uplo, int n, const float* a, int ia, int ja,
+                                        const int desca[9]) DLAF_NOEXCEPT;
+DLAF_EXTERN_C double dlaf_mi355x_pdlansy(char norm, char uplo, int n, const double* a, int ia, int ja,
+                                         const int desca[9]) DLAF_NOEXCEPT;
+DLAF_EXTERN_C float dlaf_mi355x_pclanhe(char norm, char uplo, int n, const dlaf_complex_c* a, int ia, int ja,
+                                        const int desca[9]) DLAF_NOEXCEPT;
+DLAF_EXTERN_C double dlaf_mi355x_pzlanhe(char norm, char uplo, int n, const dlaf_complex_z* a, int ia, int ja,
+                                         const int desca[9]) DLAF_NOEXCEPT;
+DLAF_EXTERN_C float dlaf_mi355x_pslantr(char norm, char uplo, char diag, int n, const float* a, int ia, int ja,
+                                        const int desca[9]) DLAF_NOEXCEPT;
+DLAF_EXTERN_C double dlaf_mi355x_pdlantr(char norm, char uplo, char diag, int n, const double* a, int ia, int ja,
+                                         const int desca[9]) DLAF_NOEXCEPT;
+DLAF_EXTERN_C float dlaf_mi355x_pclantr(char norm, char uplo, char diag, int n, const dlaf_complex_c* a, int ia, int ja,
+                                        const int desca[9]) DLAF_NOEXCEPT;
+DLAF_EXTERN_C double dlaf_mi355x_pzlantr(char norm, char uplo, char diag, int n, const dlaf_complex_z* a, int ia, int ja,
+                                         const int desca[9]) DLAF_NOEXCEPT;
+/* the same on resident operands: structure 'H' (Hermitian) or 'T' (triangular, diag 'N' / 'U') for the triangle a
+ * dlaf_mi355x_matrix_t holds, and the general resident matrix */
+DLAF_EXTERN_C int dlaf_mi355x_matrix_norm(dlaf_mi355x_matrix_t m, char norm, char structure, char diag,
+                                          double* value) DLAF_NOEXCEPT;
+DLAF_EXTERN_C int dlaf_mi355x_general_matrix_norm(dlaf_mi355x_gmatrix_t m, char norm, double* value) DLAF_NOEXCEPT;
+/* measurement hook (tools/norm_bench.py): the device allocation that holds the local tiles of a resident general
+ * matrix and its size, so that a read-rate yardstick can stream the very allocation the norm reads */
+DLAF_EXTERN_C int dlaf_mi355x_gmatrix_device_tiles(dlaf_mi355x_gmatrix_t m, const void** tiles,
+                                                   size_t* bytes) DLAF_NOEXCEPT;
+/* device time (ms, HIP events on the operand's stream; upload excluded) of the last norm on this process and the bytes
+ * of the tiles it referenced (diagonal tiles counted whole) */
+DLAF_EXTERN_C int dlaf_mi355x_norm_profile(double* ms, double* bytes) DLAF_NOEXCEPT;
+
 /* ---- the panel TRSM, one launch (host operands) -------------------------------------------------- */
 /* Every field of one launch of the panel TRSM (the kernel's contract: TrsmArgs in csrc/device/device_api.hpp) and the
  * preparation of the inverted diagonal blocks that feeds it.  The entry uploads the operands, prepares winv, launches

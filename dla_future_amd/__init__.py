@@ -35,7 +35,10 @@ from .eigensolver import (band_to_tridiagonal, bt_band_to_tridiagonal, bt_reduct
                           bt_reduction_to_band_device, eigensolver_min_band, eigensolver_profile, get_band_size, hermitian_eigensolver,
                           hermitian_generalized_eigensolver, red2band_panel_stats, red2band_profile, reduction_to_band,
                           reduction_to_band_device, tridiagonal_eigensolver, pxheevd_partial_spectrum,
-                          partial_spectrum_plan)
+                          partial_spectrum_plan, hermitian_eigenvalues, hermitian_generalized_eigenvalues,
+                          pxheevd_eigenvalues, pxheevd_partial_spectrum_by_value, pxhegvd_eigenvalues,
+                          pxhegvd_partial_spectrum_by_value, sturm_layout, tridiagonal_eigenvalues,
+                          tridiagonal_sturm_count)
 
 __all__ = ["band_to_tridiagonal", "bt_band_to_tridiagonal", "eigensolver_profile", "hermitian_eigensolver",
            "hermitian_generalized_eigensolver", "tridiagonal_eigensolver", "bt_reduction_to_band", "bt_reduction_to_band_device", "get_band_size", "eigensolver_min_band", "red2band_profile",
@@ -46,5 +49,8 @@ __all__ = ["band_to_tridiagonal", "bt_band_to_tridiagonal", "eigensolver_profile
            "inverse_from_cholesky_factor", "pxtrtri", "pxpotri", "inverse_profile", "type_char", "version",
            "triangular_multiplication", "triangular_multiplication_device", "pxtrmm", "multiplication_profile",
            "hermitian_multiplication", "hermitian_multiplication_device", "pxhemm", "update_direct", "update_bulk_slots",
-           "trsm_direct", "potrf_direct", "pxheevd_partial_spectrum", "partial_spectrum_plan", "matrix_norm",
+           "trsm_direct", "potrf_direct", "pxheevd_partial_spectrum", "partial_spectrum_plan", "hermitian_eigenvalues",
+           "hermitian_generalized_eigenvalues", "pxheevd_eigenvalues", "pxheevd_partial_spectrum_by_value", "pxhegvd_eigenvalues",
+           "pxhegvd_partial_spectrum_by_value", "sturm_layout",
+           "tridiagonal_eigenvalues", "tridiagonal_sturm_count", "matrix_norm",
            "matrix_norm_device", "pxlange", "pxlanhe", "pxlantr", "norm_profile"]

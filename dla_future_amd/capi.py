@@ -70,6 +70,7 @@ def type_char(dtype) -> str:
 _vp, _i, _l, _ch = C.c_void_p, C.c_int, C.c_long, C.c_char
 _IP = C.POINTER(C.c_int)
 _i64 = C.c_int64
+_LP = C.POINTER(C.c_long)
 SIGNATURES = {
     # include/dlaf_c/init.h
     "dlaf_initialize": (None, [_i, C.POINTER(C.c_char_p), _i, C.POINTER(C.c_char_p)]),
@@ -283,6 +284,59 @@ SIGNATURES = {
     "dlaf_pzhegvd_factorized_partial_spectrum": (None, [_ch, _i, _vp, _i, _i, _IP, _vp, _i, _i, _IP, _vp, _vp, _i, _i, _IP, _i64, _i64, _IP]),
     "dlaf_mi355x_tridiagonal_eigensolver_partial_spectrum_s": (_i, [_i, _i, _vp, _vp, _vp, _vp, _i, _l, _l]),
     "dlaf_mi355x_tridiagonal_eigensolver_partial_spectrum_d": (_i, [_i, _i, _vp, _vp, _vp, _vp, _i, _l, _l]),
+    "dlaf_symmetric_eigenvalues_s": (_i, [_i, _ch, _vp, DLAFDescriptor, _vp, _i64, _i64]),
+    "dlaf_symmetric_generalized_eigenvalues_s": (_i, [_i, _ch, _vp, DLAFDescriptor, _vp, DLAFDescriptor, _vp, _i64, _i64]),
+    "dlaf_symmetric_generalized_eigenvalues_factorized_s": (_i, [_i, _ch, _vp, DLAFDescriptor, _vp, DLAFDescriptor, _vp, _i64, _i64]),
+    "dlaf_symmetric_eigensolver_partial_spectrum_by_value_s": (_i, [_i, _ch, _vp, DLAFDescriptor, _vp, _vp, DLAFDescriptor, C.c_float, C.c_float, _LP, _LP]),
+    "dlaf_symmetric_generalized_eigensolver_partial_spectrum_by_value_s": (_i, [_i, _ch, _vp, DLAFDescriptor, _vp, DLAFDescriptor, _vp, _vp, DLAFDescriptor, C.c_float, C.c_float, _LP, _LP]),
+    "dlaf_symmetric_generalized_eigensolver_factorized_partial_spectrum_by_value_s": (_i, [_i, _ch, _vp, DLAFDescriptor, _vp, DLAFDescriptor, _vp, _vp, DLAFDescriptor, C.c_float, C.c_float, _LP, _LP]),
+    "dlaf_pssyevd_eigenvalues": (None, [_ch, _i, _vp, _i, _i, _IP, _vp, _i64, _i64, _IP]),
+    "dlaf_pssygvd_eigenvalues": (None, [_ch, _i, _vp, _i, _i, _IP, _vp, _i, _i, _IP, _vp, _i64, _i64, _IP]),
+    "dlaf_pssygvd_eigenvalues_factorized": (None, [_ch, _i, _vp, _i, _i, _IP, _vp, _i, _i, _IP, _vp, _i64, _i64, _IP]),
+    "dlaf_pssyevd_partial_spectrum_by_value": (None, [_ch, _i, _vp, _i, _i, _IP, _vp, _vp, _i, _i, _IP, C.c_float, C.c_float, _IP, _IP]),
+    "dlaf_pssygvd_partial_spectrum_by_value": (None, [_ch, _i, _vp, _i, _i, _IP, _vp, _i, _i, _IP, _vp, _vp, _i, _i, _IP, C.c_float, C.c_float, _IP, _IP]),
+    "dlaf_pssygvd_factorized_partial_spectrum_by_value": (None, [_ch, _i, _vp, _i, _i, _IP, _vp, _i, _i, _IP, _vp, _vp, _i, _i, _IP, C.c_float, C.c_float, _IP, _IP]),
+    "dlaf_symmetric_eigenvalues_d": (_i, [_i, _ch, _vp, DLAFDescriptor, _vp, _i64, _i64]),
+    "dlaf_symmetric_generalized_eigenvalues_d": (_i, [_i, _ch, _vp, DLAFDescriptor, _vp, DLAFDescriptor, _vp, _i64, _i64]),
+    "dlaf_symmetric_generalized_eigenvalues_factorized_d": (_i, [_i, _ch, _vp, DLAFDescriptor, _vp, DLAFDescriptor, _vp, _i64, _i64]),
+    "dlaf_symmetric_eigensolver_partial_spectrum_by_value_d": (_i, [_i, _ch, _vp, DLAFDescriptor, _vp, _vp, DLAFDescriptor, C.c_double, C.c_double, _LP, _LP]),
+    "dlaf_symmetric_generalized_eigensolver_partial_spectrum_by_value_d": (_i, [_i, _ch, _vp, DLAFDescriptor, _vp, DLAFDescriptor, _vp, _vp, DLAFDescriptor, C.c_double, C.c_double, _LP, _LP]),
+    "dlaf_symmetric_generalized_eigensolver_factorized_partial_spectrum_by_value_d": (_i, [_i, _ch, _vp, DLAFDescriptor, _vp, DLAFDescriptor, _vp, _vp, DLAFDescriptor, C.c_double, C.c_double, _LP, _LP]),
+    "dlaf_pdsyevd_eigenvalues": (None, [_ch, _i, _vp, _i, _i, _IP, _vp, _i64, _i64, _IP]),
+    "dlaf_pdsygvd_eigenvalues": (None, [_ch, _i, _vp, _i, _i, _IP, _vp, _i, _i, _IP, _vp, _i64, _i64, _IP]),
+    "dlaf_pdsygvd_eigenvalues_factorized": (None, [_ch, _i, _vp, _i, _i, _IP, _vp, _i, _i, _IP, _vp, _i64, _i64, _IP]),
+    "dlaf_pdsyevd_partial_spectrum_by_value": (None, [_ch, _i, _vp, _i, _i, _IP, _vp, _vp, _i, _i, _IP, C.c_double, C.c_double, _IP, _IP]),
+    "dlaf_pdsygvd_partial_spectrum_by_value": (None, [_ch, _i, _vp, _i, _i, _IP, _vp, _i, _i, _IP, _vp, _vp, _i, _i, _IP, C.c_double, C.c_double, _IP, _IP]),
+    "dlaf_pdsygvd_factorized_partial_spectrum_by_value": (None, [_ch, _i, _vp, _i, _i, _IP, _vp, _i, _i, _IP, _vp, _vp, _i, _i, _IP, C.c_double, C.c_double, _IP, _IP]),
+    "dlaf_hermitian_eigenvalues_c": (_i, [_i, _ch, _vp, DLAFDescriptor, _vp, _i64, _i64]),
+    "dlaf_hermitian_generalized_eigenvalues_c": (_i, [_i, _ch, _vp, DLAFDescriptor, _vp, DLAFDescriptor, _vp, _i64, _i64]),
+    "dlaf_hermitian_generalized_eigenvalues_factorized_c": (_i, [_i, _ch, _vp, DLAFDescriptor, _vp, DLAFDescriptor, _vp, _i64, _i64]),
+    "dlaf_hermitian_eigensolver_partial_spectrum_by_value_c": (_i, [_i, _ch, _vp, DLAFDescriptor, _vp, _vp, DLAFDescriptor, C.c_float, C.c_float, _LP, _LP]),
+    "dlaf_hermitian_generalized_eigensolver_partial_spectrum_by_value_c": (_i, [_i, _ch, _vp, DLAFDescriptor, _vp, DLAFDescriptor, _vp, _vp, DLAFDescriptor, C.c_float, C.c_float, _LP, _LP]),
+    "dlaf_hermitian_generalized_eigensolver_factorized_partial_spectrum_by_value_c": (_i, [_i, _ch, _vp, DLAFDescriptor, _vp, DLAFDescriptor, _vp, _vp, DLAFDescriptor, C.c_float, C.c_float, _LP, _LP]),
+    "dlaf_pcheevd_eigenvalues": (None, [_ch, _i, _vp, _i, _i, _IP, _vp, _i64, _i64, _IP]),
+    "dlaf_pchegvd_eigenvalues": (None, [_ch, _i, _vp, _i, _i, _IP, _vp, _i, _i, _IP, _vp, _i64, _i64, _IP]),
+    "dlaf_pchegvd_eigenvalues_factorized": (None, [_ch, _i, _vp, _i, _i, _IP, _vp, _i, _i, _IP, _vp, _i64, _i64, _IP]),
+    "dlaf_pcheevd_partial_spectrum_by_value": (None, [_ch, _i, _vp, _i, _i, _IP, _vp, _vp, _i, _i, _IP, C.c_float, C.c_float, _IP, _IP]),
+    "dlaf_pchegvd_partial_spectrum_by_value": (None, [_ch, _i, _vp, _i, _i, _IP, _vp, _i, _i, _IP, _vp, _vp, _i, _i, _IP, C.c_float, C.c_float, _IP, _IP]),
+    "dlaf_pchegvd_factorized_partial_spectrum_by_value": (None, [_ch, _i, _vp, _i, _i, _IP, _vp, _i, _i, _IP, _vp, _vp, _i, _i, _IP, C.c_float, C.c_float, _IP, _IP]),
+    "dlaf_hermitian_eigenvalues_z": (_i, [_i, _ch, _vp, DLAFDescriptor, _vp, _i64, _i64]),
+    "dlaf_hermitian_generalized_eigenvalues_z": (_i, [_i, _ch, _vp, DLAFDescriptor, _vp, DLAFDescriptor, _vp, _i64, _i64]),
+    "dlaf_hermitian_generalized_eigenvalues_factorized_z": (_i, [_i, _ch, _vp, DLAFDescriptor, _vp, DLAFDescriptor, _vp, _i64, _i64]),
+    "dlaf_hermitian_eigensolver_partial_spectrum_by_value_z": (_i, [_i, _ch, _vp, DLAFDescriptor, _vp, _vp, DLAFDescriptor, C.c_double, C.c_double, _LP, _LP]),
+    "dlaf_hermitian_generalized_eigensolver_partial_spectrum_by_value_z": (_i, [_i, _ch, _vp, DLAFDescriptor, _vp, DLAFDescriptor, _vp, _vp, DLAFDescriptor, C.c_double, C.c_double, _LP, _LP]),
+    "dlaf_hermitian_generalized_eigensolver_factorized_partial_spectrum_by_value_z": (_i, [_i, _ch, _vp, DLAFDescriptor, _vp, DLAFDescriptor, _vp, _vp, DLAFDescriptor, C.c_double, C.c_double, _LP, _LP]),
+    "dlaf_pzheevd_eigenvalues": (None, [_ch, _i, _vp, _i, _i, _IP, _vp, _i64, _i64, _IP]),
+    "dlaf_pzhegvd_eigenvalues": (None, [_ch, _i, _vp, _i, _i, _IP, _vp, _i, _i, _IP, _vp, _i64, _i64, _IP]),
+    "dlaf_pzhegvd_eigenvalues_factorized": (None, [_ch, _i, _vp, _i, _i, _IP, _vp, _i, _i, _IP, _vp, _i64, _i64, _IP]),
+    "dlaf_pzheevd_partial_spectrum_by_value": (None, [_ch, _i, _vp, _i, _i, _IP, _vp, _vp, _i, _i, _IP, C.c_double, C.c_double, _IP, _IP]),
+    "dlaf_pzhegvd_partial_spectrum_by_value": (None, [_ch, _i, _vp, _i, _i, _IP, _vp, _i, _i, _IP, _vp, _vp, _i, _i, _IP, C.c_double, C.c_double, _IP, _IP]),
+    "dlaf_pzhegvd_factorized_partial_spectrum_by_value": (None, [_ch, _i, _vp, _i, _i, _IP, _vp, _i, _i, _IP, _vp, _vp, _i, _i, _IP, C.c_double, C.c_double, _IP, _IP]),
+    "dlaf_mi355x_tridiagonal_eigenvalues_s": (_i, [_i, _vp, _vp, _vp, _l, _l]),
+    "dlaf_mi355x_tridiagonal_sturm_count_s": (_i, [_i, _vp, _vp, _l, _vp, _vp]),
+    "dlaf_mi355x_tridiagonal_eigenvalues_d": (_i, [_i, _vp, _vp, _vp, _l, _l]),
+    "dlaf_mi355x_tridiagonal_sturm_count_d": (_i, [_i, _vp, _vp, _l, _vp, _vp]),
+    "dlaf_mi355x_sturm_layout": (_i, [_IP]),
     "dlaf_mi355x_partial_spectrum_plan": (_i, [_l, _i, _i, _i, _i, _l, _l, C.POINTER(C.c_long)]),
     "dlaf_mi355x_eigensolver_profile": (_i, [C.POINTER(C.c_double)]),
     "dlaf_mi355x_get_band_size": (_i, [_i]),

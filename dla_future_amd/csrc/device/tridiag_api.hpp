@@ -1,6 +1,7 @@
 // tridiag_api.hpp -- host-callable launchers of the gfx950 kernels of the eigensolver stages behind the reduction to
 // band form: band -> tridiagonal (bulge chasing), the tridiagonal divide & conquer
-// eigensolver, and the back-transformation band <- tridiagonal.  Everything enqueues on the given stream.
+// eigensolver, Sturm counts and bisection on the tridiagonal matrix, and the back-transformation band <- tridiagonal.
+// Everything enqueues on the given stream.
 //
 // Reference: include/dlaf/eigensolver/band_to_tridiag/mc.h (the reference runs this stage on the CPU, one task per
 // sweep step, also for GPU matrices), include/dlaf/eigensolver/tridiag_solver/{impl,merge}.h (leaf solver stedc and
@@ -68,6 +69,31 @@ void launch_cols_gather_cast(const R* z, long ldz, long n, int nb, int pc, int c
 template <class T>
 void launch_rows_to_tiles(const T* e, long lde, long n, long ncols_loc, int nb, int pr, int ri, long ltr, long ltc, T* tiles,
                           hipStream_t stream);
+
+// ------------------------------------------------------------------------------------------ Sturm counts, bisection
+// (kernels_sturm.hip)  work: sturm_work_doubles(n) device doubles, 16-byte aligned: a header of
+// kSturmHeader doubles, then the n pairs (2^-k d_i, (2^-k e_{i-1})^2), e_{-1} = 0.
+constexpr int kSturmThreads = 64;           // one wave per workgroup, one thread per shift / per eigenvalue index
+constexpr int kSturmChunk = 512;            // pairs staged through LDS at a time (two buffers of 8 KiB)
+constexpr int kSturmMaxIterations = 1200;   // above any cap a finite matrix can ask for (2^3 / 2^-1074 and change)
+constexpr int kSturmHeader = 8;
+enum : int { kSturmGl = 0, kSturmGu, kSturmPivmin, kSturmK, kSturmBad, kSturmCap };
+inline size_t sturm_work_doubles(long n) {
+  return (size_t) kSturmHeader + 2 * (size_t) (n > 0 ? n : 0);
+}
+// d (n), e (n - 1), device, R = float | double.  Header: the Gershgorin interval [gl, gu] of the scaled matrix, widened
+// as dstebz widens it; pivmin = DBL_MIN max(1, max e^2); k (2^k <= max(|d|, |e|) < 2^(k + 1); 0 for a zero or
+// non-finite matrix); 1 when d or e holds a NaN or an Inf; the iteration cap of the bisection.
+template <class R>
+void launch_sturm_prepare(const R* d, const R* e, long n, double* work, hipStream_t stream);
+// counts[s] = the number of eigenvalues <= shifts[s] (shifts in the caller's scale; dstebz's convention: pivots
+// q <= pivmin); -1 for every shift when the matrix is not finite.  One thread per shift.
+template <class R>
+void launch_sturm_count(const double* work, long n, const R* shifts, long nshifts, long long* counts, hipStream_t stream);
+// w[j], j in [begin, end) = eigenvalue j (0-based, ascending) by bisection on the counts, rounded to R once; nothing
+// else of w is written.  NaN for every wanted entry when the matrix is not finite.  One thread per index.
+template <class R>
+void launch_sturm_bisect(const double* work, long n, long begin, long end, R* w, hipStream_t stream);
 
 // ------------------------------------------------------------------------------------------ tridiagonal D&C
 // (kernels of the divide & conquer solver: declared in tridiag_dc.hpp)

@@ -12,6 +12,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <initializer_list>
 #include <memory>
 #include <string>
 #include <unordered_map>
@@ -23,6 +24,7 @@
 #include <dlaf_c/init.h>
 #include <dlaf_mi355x/dlaf_mi355x.h>
 
+#include "../device/tridiag_api.hpp"
 #include "eigensolver.hpp"
 #include "red2band.hpp"
 #include "runtime.hpp"
@@ -479,6 +481,21 @@ int band_to_tridiag_c(int ctx, const HT* a, const DLAF_descriptor& da, int band,
                                   reinterpret_cast<DT*>(v), ldv);
 }
 
+// checks the eigensolver entries share: source ranks inside the grid; B and Z described like A, without offsets
+void check_eig_source(const Grid& g, std::initializer_list<const DLAF_descriptor*> descs) {
+  for (const DLAF_descriptor* d : descs)
+    if (d->isrc < 0 || d->isrc >= g.nprow || d->jsrc < 0 || d->jsrc >= g.npcol)
+      fatal("[dlaf_mi355x] source rank (%d,%d) outside the %d x %d grid\n", d->isrc, d->jsrc, g.nprow, g.npcol);
+}
+void check_eig_like(const char* who, const DLAF_descriptor& da, std::initializer_list<const DLAF_descriptor*> others) {
+  for (const DLAF_descriptor* d : others) {
+    if (d->i != 0 || d->j != 0)
+      fatal("[dlaf_mi355x] %s: sub-matrix offsets must be 0\n", who);
+    if (d->m != da.m || d->n != da.n || d->mb != da.mb || d->nb != da.nb)
+      fatal("[dlaf_mi355x] %s: B and Z must have A's size %d x %d and block %d x %d\n", who, da.m, da.n, da.mb, da.nb);
+  }
+}
+
 // Eigensolver entry (src/c_api/eigensolver/eigensolver.h:33-75): descriptors of A and of the eigenvector matrix;
 // [begin, end): the 0-based range of eigenvalue indices whose eigenvectors are wanted ([0, n): the full entries)
 template <class HT>
@@ -493,9 +510,7 @@ int eigensolver_c(int ctx, char uplo, HT* a, const DLAF_descriptor& da, typename
   if (dz.m != da.m || dz.n != da.n || dz.mb != da.mb || dz.nb != da.nb)
     fatal("[dlaf_mi355x] eigensolver: Z (%d x %d, block %d x %d) must have A's size %d x %d and block %d x %d\n", dz.m, dz.n,
           dz.mb, dz.nb, da.m, da.n, da.mb, da.nb);
-  for (const DLAF_descriptor* d : {&da, &dz})
-    if (d->isrc < 0 || d->isrc >= g.nprow || d->jsrc < 0 || d->jsrc >= g.npcol)
-      fatal("[dlaf_mi355x] source rank (%d,%d) outside the %d x %d grid\n", d->isrc, d->jsrc, g.nprow, g.npcol);
+  check_eig_source(g, {&da, &dz});
   return hermitian_eigensolver_host<DT>(&g, uplo, reinterpret_cast<DT*>(a), da.ld, da.m, da.nb, da.isrc, da.jsrc, w,
                                         reinterpret_cast<DT*>(z), dz.ld, dz.isrc, dz.jsrc, begin, end);
 }
@@ -509,15 +524,8 @@ int gen_eigensolver_c(int ctx, char uplo, HT* a, const DLAF_descriptor& da, HT* 
   check_cholesky_desc(da);
   check_cholesky_desc(db);
   Grid& g = grid_from_context(ctx);
-  if (dz.i != 0 || dz.j != 0)
-    fatal("[dlaf_mi355x] gen_eigensolver: sub-matrix offsets of Z must be 0\n");
-  for (const DLAF_descriptor* d : {&db, &dz})
-    if (d->m != da.m || d->n != da.n || d->mb != da.mb || d->nb != da.nb)
-      fatal("[dlaf_mi355x] gen_eigensolver: B and Z must have A's size %d x %d and block %d x %d\n", da.m, da.n, da.mb,
-            da.nb);
-  for (const DLAF_descriptor* d : {&da, &db, &dz})
-    if (d->isrc < 0 || d->isrc >= g.nprow || d->jsrc < 0 || d->jsrc >= g.npcol)
-      fatal("[dlaf_mi355x] source rank (%d,%d) outside the %d x %d grid\n", d->isrc, d->jsrc, g.nprow, g.npcol);
+  check_eig_like("gen_eigensolver", da, {&db, &dz});
+  check_eig_source(g, {&da, &db, &dz});
   return hermitian_gen_eigensolver_host<DT>(&g, uplo, reinterpret_cast<DT*>(a), da.ld, reinterpret_cast<DT*>(b), db.ld,
                                             da.m, da.nb, da.isrc, da.jsrc, db.isrc, db.jsrc, w, reinterpret_cast<DT*>(z),
                                             dz.ld, dz.isrc, dz.jsrc, factorized, begin, end);
@@ -554,6 +562,118 @@ void pxhegvd(char uplo, int n, HT* a, int ia, int ja, const int desca[9], HT* b,
   const DLAF_descriptor db = make_dlaf_descriptor(n, n, ib, jb, descb);
   const DLAF_descriptor dz = make_dlaf_descriptor(n, n, iz, jz, descz);
   const int r = gen_eigensolver_c<HT>(desca[1], uplo, a, da, b, db, w, z, dz, factorized, il - 1, iu);
+  if (info)
+    *info = r;
+}
+
+// ---- eigenvalues only, and the eigenvalue range given by value ----------------------------
+template <class HT>
+int eigenvalues_c(int ctx, char uplo, const HT* a, const DLAF_descriptor& da, typename RealOf<HT>::type* w, long begin,
+                  long end) {
+  using DT = typename DevType<HT>::type;
+  check_eigenvalues_index("eigenvalues", da.m, begin, end);
+  check_cholesky_desc(da);
+  Grid& g = grid_from_context(ctx);
+  check_eig_source(g, {&da});
+  return hermitian_eigenvalues_host<DT>(&g, uplo, reinterpret_cast<const DT*>(a), da.ld, da.m, da.nb, da.isrc, da.jsrc, w,
+                                        begin, end);
+}
+
+template <class HT>
+int gen_eigenvalues_c(int ctx, char uplo, const HT* a, const DLAF_descriptor& da, HT* b, const DLAF_descriptor& db,
+                      typename RealOf<HT>::type* w, bool factorized, long begin, long end) {
+  using DT = typename DevType<HT>::type;
+  check_eigenvalues_index("gen_eigenvalues", da.m, begin, end);
+  check_cholesky_desc(da);
+  check_cholesky_desc(db);
+  Grid& g = grid_from_context(ctx);
+  check_eig_like("gen_eigenvalues", da, {&db});
+  check_eig_source(g, {&da, &db});
+  return hermitian_gen_eigenvalues_host<DT>(&g, uplo, reinterpret_cast<const DT*>(a), da.ld, reinterpret_cast<DT*>(b),
+                                            db.ld, da.m, da.nb, da.isrc, da.jsrc, db.isrc, db.jsrc, w, factorized, begin,
+                                            end);
+}
+
+template <class HT>
+int eigensolver_by_value_c(int ctx, char uplo, HT* a, const DLAF_descriptor& da, typename RealOf<HT>::type* w, HT* z,
+                           const DLAF_descriptor& dz, typename RealOf<HT>::type vl, typename RealOf<HT>::type vu,
+                           long* begin, long* end) {
+  using DT = typename DevType<HT>::type;
+  if (!begin || !end)
+    fatal("[dlaf_mi355x] eigensolver: the by-value entries return their index range: begin, end must not be null\n");
+  check_cholesky_desc(da);
+  Grid& g = grid_from_context(ctx);
+  check_eig_like("eigensolver", da, {&dz});
+  check_eig_source(g, {&da, &dz});
+  return hermitian_eigensolver_by_value_host<DT>(&g, uplo, reinterpret_cast<DT*>(a), da.ld, da.m, da.nb, da.isrc, da.jsrc,
+                                                 w, reinterpret_cast<DT*>(z), dz.ld, dz.isrc, dz.jsrc, vl, vu, begin, end);
+}
+
+template <class HT>
+int gen_eigensolver_by_value_c(int ctx, char uplo, HT* a, const DLAF_descriptor& da, HT* b, const DLAF_descriptor& db,
+                               typename RealOf<HT>::type* w, HT* z, const DLAF_descriptor& dz, bool factorized,
+                               typename RealOf<HT>::type vl, typename RealOf<HT>::type vu, long* begin, long* end) {
+  using DT = typename DevType<HT>::type;
+  if (!begin || !end)
+    fatal("[dlaf_mi355x] gen_eigensolver: the by-value entries return their index range: begin, end must not be null\n");
+  check_cholesky_desc(da);
+  check_cholesky_desc(db);
+  Grid& g = grid_from_context(ctx);
+  check_eig_like("gen_eigensolver", da, {&db, &dz});
+  check_eig_source(g, {&da, &db, &dz});
+  return hermitian_gen_eigensolver_by_value_host<DT>(&g, uplo, reinterpret_cast<DT*>(a), da.ld, reinterpret_cast<DT*>(b),
+                                                     db.ld, da.m, da.nb, da.isrc, da.jsrc, db.isrc, db.jsrc, w,
+                                                     reinterpret_cast<DT*>(z), dz.ld, dz.isrc, dz.jsrc, factorized, vl, vu,
+                                                     begin, end);
+}
+
+// the ScaLAPACK-like argument lists: b == nullptr for the standard problem
+void check_scalapack_args(std::initializer_list<const int*> descs, std::initializer_list<int> offsets) {
+  for (const int* d : descs) {
+    if (d[0] != 1)
+      fatal("[dlaf_mi355x] desc[0] (dtype) must be 1\n");
+    if (d[1] != (*descs.begin())[1])
+      fatal("[dlaf_mi355x] the matrices live on different contexts\n");
+  }
+  for (int o : offsets)
+    if (o != 1)
+      fatal("[dlaf_mi355x] ia, ja, ib, jb, iz, jz must be 1\n");
+}
+template <class HT>
+void pxhegvd_eigenvalues(char uplo, int n, const HT* a, int ia, int ja, const int desca[9], HT* b, int ib, int jb,
+                         const int descb[9], typename RealOf<HT>::type* w, long il, long iu, int* info, bool factorized) {
+  int r;
+  if (descb) {
+    check_scalapack_args({desca, descb}, {ia, ja, ib, jb});
+    r = gen_eigenvalues_c<HT>(desca[1], uplo, a, make_dlaf_descriptor(n, n, ia, ja, desca), b,
+                              make_dlaf_descriptor(n, n, ib, jb, descb), w, factorized, il - 1, iu);
+  }
+  else {
+    check_scalapack_args({desca}, {ia, ja});
+    r = eigenvalues_c<HT>(desca[1], uplo, a, make_dlaf_descriptor(n, n, ia, ja, desca), w, il - 1, iu);
+  }
+  if (info)
+    *info = r;
+}
+template <class HT>
+void pxhegvd_by_value(char uplo, int n, HT* a, int ia, int ja, const int desca[9], HT* b, int ib, int jb,
+                      const int descb[9], typename RealOf<HT>::type* w, HT* z, int iz, int jz, const int descz[9],
+                      typename RealOf<HT>::type vl, typename RealOf<HT>::type vu, int* m, int* info, bool factorized) {
+  long begin = 0, end = 0;
+  int r;
+  if (descb) {
+    check_scalapack_args({desca, descb, descz}, {ia, ja, ib, jb, iz, jz});
+    r = gen_eigensolver_by_value_c<HT>(desca[1], uplo, a, make_dlaf_descriptor(n, n, ia, ja, desca), b,
+                                       make_dlaf_descriptor(n, n, ib, jb, descb), w, z,
+                                       make_dlaf_descriptor(n, n, iz, jz, descz), factorized, vl, vu, &begin, &end);
+  }
+  else {
+    check_scalapack_args({desca, descz}, {ia, ja, iz, jz});
+    r = eigensolver_by_value_c<HT>(desca[1], uplo, a, make_dlaf_descriptor(n, n, ia, ja, desca), w, z,
+                                   make_dlaf_descriptor(n, n, iz, jz, descz), vl, vu, &begin, &end);
+  }
+  if (m)
+    *m = (int) (end - begin);
   if (info)
     *info = r;
 }
@@ -1042,6 +1162,116 @@ DLAF_MI355X_EIG_ENTRY(d, symmetric, double, double, double, pdsyevd, pdsygvd)
 DLAF_MI355X_EIG_ENTRY(c, hermitian, std::complex<float>, dlaf_complex_c, float, pcheevd, pchegvd)
 DLAF_MI355X_EIG_ENTRY(z, hermitian, std::complex<double>, dlaf_complex_z, double, pzheevd, pzhegvd)
 #undef DLAF_MI355X_EIG_ENTRY
+
+#define DLAF_MI355X_EIGVAL_ENTRY(S, KIND, HT, CT, RT, PEV, PGV)                                                       \
+  int dlaf_##KIND##_eigenvalues_##S(const int ctx, const char uplo, const CT* a, const DLAF_descriptor desca, RT* w,  \
+                                    const int64_t begin, const int64_t end) noexcept {                               \
+    return eigenvalues_c<HT>(ctx, uplo, reinterpret_cast<const HT*>(a), desca, w, begin, end);                       \
+  }                                                                                                                  \
+  int dlaf_##KIND##_generalized_eigenvalues_##S(const int ctx, const char uplo, const CT* a,                          \
+                                                const DLAF_descriptor desca, CT* b, const DLAF_descriptor descb,     \
+                                                RT* w, const int64_t begin, const int64_t end) noexcept {            \
+    return gen_eigenvalues_c<HT>(ctx, uplo, reinterpret_cast<const HT*>(a), desca, reinterpret_cast<HT*>(b), descb,   \
+                                 w, false, begin, end);                                                              \
+  }                                                                                                                  \
+  int dlaf_##KIND##_generalized_eigenvalues_factorized_##S(const int ctx, const char uplo, const CT* a,               \
+                                                           const DLAF_descriptor desca, CT* b,                       \
+                                                           const DLAF_descriptor descb, RT* w, const int64_t begin,  \
+                                                           const int64_t end) noexcept {                             \
+    return gen_eigenvalues_c<HT>(ctx, uplo, reinterpret_cast<const HT*>(a), desca, reinterpret_cast<HT*>(b), descb,   \
+                                 w, true, begin, end);                                                               \
+  }                                                                                                                  \
+  int dlaf_##KIND##_eigensolver_partial_spectrum_by_value_##S(const int ctx, const char uplo, CT* a,                  \
+                                                              const DLAF_descriptor desca, RT* w, CT* z,             \
+                                                              const DLAF_descriptor descz, const RT vl, const RT vu, \
+                                                              long* begin, long* end) noexcept {                     \
+    return eigensolver_by_value_c<HT>(ctx, uplo, reinterpret_cast<HT*>(a), desca, w, reinterpret_cast<HT*>(z), descz, \
+                                      vl, vu, begin, end);                                                           \
+  }                                                                                                                  \
+  int dlaf_##KIND##_generalized_eigensolver_partial_spectrum_by_value_##S(                                            \
+      const int ctx, const char uplo, CT* a, const DLAF_descriptor desca, CT* b, const DLAF_descriptor descb, RT* w,  \
+      CT* z, const DLAF_descriptor descz, const RT vl, const RT vu, long* begin, long* end) noexcept {               \
+    return gen_eigensolver_by_value_c<HT>(ctx, uplo, reinterpret_cast<HT*>(a), desca, reinterpret_cast<HT*>(b),       \
+                                          descb, w, reinterpret_cast<HT*>(z), descz, false, vl, vu, begin, end);     \
+  }                                                                                                                  \
+  int dlaf_##KIND##_generalized_eigensolver_factorized_partial_spectrum_by_value_##S(                                 \
+      const int ctx, const char uplo, CT* a, const DLAF_descriptor desca, CT* b, const DLAF_descriptor descb, RT* w,  \
+      CT* z, const DLAF_descriptor descz, const RT vl, const RT vu, long* begin, long* end) noexcept {               \
+    return gen_eigensolver_by_value_c<HT>(ctx, uplo, reinterpret_cast<HT*>(a), desca, reinterpret_cast<HT*>(b),       \
+                                          descb, w, reinterpret_cast<HT*>(z), descz, true, vl, vu, begin, end);      \
+  }                                                                                                                  \
+  void dlaf_##PEV##_eigenvalues(const char uplo, const int n, const CT* a, const int ia, const int ja,                \
+                                const int desca[9], RT* w, const int64_t il, const int64_t iu, int* info) noexcept { \
+    pxhegvd_eigenvalues<HT>(uplo, n, reinterpret_cast<const HT*>(a), ia, ja, desca, nullptr, 1, 1, nullptr, w, il,    \
+                            iu, info, false);                                                                        \
+  }                                                                                                                  \
+  void dlaf_##PGV##_eigenvalues(const char uplo, const int n, const CT* a, const int ia, const int ja,                \
+                                const int desca[9], CT* b, const int ib, const int jb, const int descb[9], RT* w,    \
+                                const int64_t il, const int64_t iu, int* info) noexcept {                            \
+    pxhegvd_eigenvalues<HT>(uplo, n, reinterpret_cast<const HT*>(a), ia, ja, desca, reinterpret_cast<HT*>(b), ib, jb, \
+                            descb, w, il, iu, info, false);                                                          \
+  }                                                                                                                  \
+  void dlaf_##PGV##_eigenvalues_factorized(const char uplo, const int n, const CT* a, const int ia, const int ja,     \
+                                           const int desca[9], CT* b, const int ib, const int jb,                    \
+                                           const int descb[9], RT* w, const int64_t il, const int64_t iu,            \
+                                           int* info) noexcept {                                                     \
+    pxhegvd_eigenvalues<HT>(uplo, n, reinterpret_cast<const HT*>(a), ia, ja, desca, reinterpret_cast<HT*>(b), ib, jb, \
+                            descb, w, il, iu, info, true);                                                           \
+  }                                                                                                                  \
+  void dlaf_##PEV##_partial_spectrum_by_value(const char uplo, const int n, CT* a, const int ia, const int ja,        \
+                                              const int desca[9], RT* w, CT* z, const int iz, const int jz,          \
+                                              const int descz[9], const RT vl, const RT vu, int* m,                  \
+                                              int* info) noexcept {                                                  \
+    pxhegvd_by_value<HT>(uplo, n, reinterpret_cast<HT*>(a), ia, ja, desca, nullptr, 1, 1, nullptr, w,                 \
+                         reinterpret_cast<HT*>(z), iz, jz, descz, vl, vu, m, info, false);                           \
+  }                                                                                                                  \
+  void dlaf_##PGV##_partial_spectrum_by_value(const char uplo, const int n, CT* a, const int ia, const int ja,        \
+                                              const int desca[9], CT* b, const int ib, const int jb,                 \
+                                              const int descb[9], RT* w, CT* z, const int iz, const int jz,          \
+                                              const int descz[9], const RT vl, const RT vu, int* m,                  \
+                                              int* info) noexcept {                                                  \
+    pxhegvd_by_value<HT>(uplo, n, reinterpret_cast<HT*>(a), ia, ja, desca, reinterpret_cast<HT*>(b), ib, jb, descb,   \
+                         w, reinterpret_cast<HT*>(z), iz, jz, descz, vl, vu, m, info, false);                        \
+  }                                                                                                                  \
+  void dlaf_##PGV##_factorized_partial_spectrum_by_value(const char uplo, const int n, CT* a, const int ia,           \
+                                                         const int ja, const int desca[9], CT* b, const int ib,      \
+                                                         const int jb, const int descb[9], RT* w, CT* z,             \
+                                                         const int iz, const int jz, const int descz[9],             \
+                                                         const RT vl, const RT vu, int* m, int* info) noexcept {     \
+    pxhegvd_by_value<HT>(uplo, n, reinterpret_cast<HT*>(a), ia, ja, desca, reinterpret_cast<HT*>(b), ib, jb, descb,   \
+                         w, reinterpret_cast<HT*>(z), iz, jz, descz, vl, vu, m, info, true);                         \
+  }
+DLAF_MI355X_EIGVAL_ENTRY(s, symmetric, float, float, float, pssyevd, pssygvd)
+DLAF_MI355X_EIGVAL_ENTRY(d, symmetric, double, double, double, pdsyevd, pdsygvd)
+DLAF_MI355X_EIGVAL_ENTRY(c, hermitian, std::complex<float>, dlaf_complex_c, float, pcheevd, pchegvd)
+DLAF_MI355X_EIGVAL_ENTRY(z, hermitian, std::complex<double>, dlaf_complex_z, double, pzheevd, pzhegvd)
+#undef DLAF_MI355X_EIGVAL_ENTRY
+
+int dlaf_mi355x_tridiagonal_eigenvalues_s(int n, const float* d, const float* e, float* w, long begin,
+                                          long end) noexcept {
+  runtime_init();
+  return tridiag_eigenvalues_host<float>(n, d, e, w, begin, end);
+}
+int dlaf_mi355x_tridiagonal_eigenvalues_d(int n, const double* d, const double* e, double* w, long begin,
+                                          long end) noexcept {
+  runtime_init();
+  return tridiag_eigenvalues_host<double>(n, d, e, w, begin, end);
+}
+int dlaf_mi355x_tridiagonal_sturm_count_s(int n, const float* d, const float* e, long nshifts, const float* shifts,
+                                          long* counts) noexcept {
+  runtime_init();
+  return sturm_count_host<float>(n, d, e, nshifts, shifts, counts);
+}
+int dlaf_mi355x_tridiagonal_sturm_count_d(int n, const double* d, const double* e, long nshifts, const double* shifts,
+                                          long* counts) noexcept {
+  runtime_init();
+  return sturm_count_host<double>(n, d, e, nshifts, shifts, counts);
+}
+int dlaf_mi355x_sturm_layout(int out[2]) noexcept {
+  out[0] = kSturmChunk;
+  out[1] = kSturmThreads;
+  return 0;
+}
 
 int dlaf_mi355x_tridiagonal_eigensolver_s(int n, int nb, const float* d, const float* e, float* w, float* z,
                                           int ldz) noexcept {

@@ -451,67 +451,100 @@ PartialSpectrumPlan partial_spectrum_plan(long n, int nb, int npcol, int mycol, 
   return p;
 }
 
-// Eigensolver::call on resident operands: A (uplo L; destroyed: band + reflectors), eigenvalues to the host array w
-// (all n on every rank), eigenvectors of the eigenvalues [begin, end) into the resident general matrix Z (A's block
-// size and row source), which covers the global columns [b0, end), b0 = (begin / nb) nb: n x (end - b0), the full
-// matrix for [0, n).  Its columns [b0, begin) are padding and stay zero through both back-transformations (and the
-// triangular solve of the generalized problem): all three act on the columns independently.
-template <class T>
-int hermitian_eigensolver_device(DeviceMatrix<T>& A, real_t<T>* w_host, GeneralMatrix<T>& Z, long begin, long end) {
-  using R = real_t<T>;
-  const long n = A.n;
-  const int nb = A.nb;
-  if (n == 0)
-    return 0;
-  Grid* g = A.grid;
-  TileMatrix<T>& C = Z.m;
-  const long b0 = (begin / nb) * nb, pad = begin - b0, k = end - begin;
-  check_eigenvalues_index("eigensolver", n, begin, end);
-  if (C.grid != g || C.nb != nb || C.rows.n != n || C.cols.n != end - b0 || C.rows.src != A.rows.src || C.transposed)
-    fatal("[dlaf_mi355x] eigensolver: the eigenvector matrix must be n x %ld with A's block size and row source rank\n",
-          end - b0);
-  const int band = get_band_size(nb);  // eigensolver/impl.h:41
-  hipStream_t s = A.s_high;
-  // a stage's status is made the same on every rank before anybody acts on it: a rank that left alone would leave
-  // the others inside the next collective
-  auto agreed = [&](int info) {
-    if (g->nranks > 1 && g->transport) {
-      double v[2] = {info > 0 ? (double) info : 0.0, info < 0 ? 1.0 : 0.0};
-      g->transport->allreduce_max(v, 2, g->nprow, g->npcol, g->myrow, g->mycol);
-      info = v[1] > 0 ? kInfoSchedulingFailure : (int) v[0];
-    }
-    return info;
-  };
-  // stages 2 and 3 run replicated: every rank holds the n x n reflector matrix (T), the n x k real eigenvector matrix
-  // and the divide & conquer workspaces (4 n^2 real) -- say so instead of failing inside an allocation
-  {
-    size_t free_b = 0, total_b = 0;
-    DLAF_HIP_CHECK(hipMemGetInfo(&free_b, &total_b));
-    const double need = (double) n * n * (sizeof(T) + 4.0 * sizeof(R)) + (double) n * k * sizeof(R) +
-                        (double) (end - b0) * bt_aligned_ld(n) / g->npcol * sizeof(T);
-    if (need > 0.95 * (double) free_b)
-      fatal("[dlaf_mi355x] eigensolver: n = %ld needs %.1f GiB per rank for the replicated stages (band_to_tridiagonal, "
-            "tridiagonal_eigensolver), %.1f GiB are free\n", n, need / 1073741824.0, (double) free_b / 1073741824.0);
+// Eigensolver::call on resident operands, in two halves.  The reductions (stages 1-2) turn A (uplo L; destroyed: band
+// + reflectors) into the tridiagonal matrix d, e and the reflector matrix v, all resident; the rest (stages 3-5) takes
+// them to the eigenvalues (host array w, all n on every rank) and the eigenvectors of the eigenvalues [begin, end) in
+// the resident general matrix Z (A's block size and row source), which covers the global columns [b0, end),
+// b0 = (begin / nb) nb: n x (end - b0), the full matrix for [0, n).  Its columns [b0, begin) are padding and stay zero
+// through both back-transformations (and the triangular solve of the generalized problem): all three act on the
+// columns independently.  Between the halves the eigenvalues-only entries stop (bisection on d, e) and the by-value
+// entries turn (vl, vu] into an index range (two Sturm counts), which is why Z is made only then.
+namespace {
+// a stage's status is made the same on every rank before anybody acts on it: a rank that left alone would leave
+// the others inside the next collective
+int agreed(Grid* g, int info) {
+  if (g->nranks > 1 && g->transport) {
+    double v[2] = {info > 0 ? (double) info : 0.0, info < 0 ? 1.0 : 0.0};
+    g->transport->allreduce_max(v, 2, g->nprow, g->npcol, g->myrow, g->mycol);
+    info = v[1] > 0 ? kInfoSchedulingFailure : (int) v[0];
   }
-  // DLAF_MI355X_EIG_DEBUG=1: a checksum of every stage's output per rank (diagnosis: each stage is deterministic)
+  return info;
+}
+
+// DLAF_MI355X_EIG_DEBUG=1: a checksum of every stage's output per rank (diagnosis: each stage is deterministic)
+void debug_checksum(Grid* g, hipStream_t s, const char* what, const void* dev, size_t bytes) {
   static const bool dbg = [] {
     const char* e_ = std::getenv("DLAF_MI355X_EIG_DEBUG");
     return e_ && std::atoi(e_) != 0;
   }();
-  auto checksum = [&](const char* what, const void* dev, size_t bytes) {
-    if (!dbg)
-      return;
-    DLAF_HIP_CHECK(hipStreamSynchronize(s));
-    std::vector<unsigned long long> h((bytes + 7) / 8, 0ull);
-    DLAF_HIP_CHECK(hipMemcpy(h.data(), dev, bytes, hipMemcpyDeviceToHost));
-    unsigned long long acc = 1469598103934665603ull;
-    for (unsigned long long x : h)
-      acc = (acc ^ x) * 1099511628211ull;
-    std::fprintf(stderr, "[dlaf_mi355x] eig debug rank (%d,%d) %-24s %016llx\n", g->myrow, g->mycol, what, acc);
-  };
-  std::vector<T> taus((size_t) std::max<long>(0, n - band - 1) + 1);
-  int info = agreed(reduction_to_band_device(A, band, taus.data()));
-  checksum("A after red2band", A.tiles, (size_t) A.ltr * A.ltc * A.tile_elems * sizeof(T));
+  if (!dbg)
+    return;
+  DLAF_HIP_CHECK(hipStreamSynchronize(s));
+  std::vector<unsigned long long> h((bytes + 7) / 8, 0ull);
+  DLAF_HIP_CHECK(hipMemcpy(h.data(), dev, bytes, hipMemcpyDeviceToHost));
+  unsigned long long acc = 1469598103934665603ull;
+  for (unsigned long long x : h)
+    acc = (acc ^ x) * 1099511628211ull;
+  std::fprintf(stderr, "[dlaf_mi355x] eig debug rank (%d,%d) %-24s %016llx\n", g->myrow, g->mycol, what, acc);
+}
+
+// stages 2 and 3 run replicated: say what they need instead of failing inside an allocation
+void check_replicated_memory(long n, double need) {
+  size_t free_b = 0, total_b = 0;
+  DLAF_HIP_CHECK(hipMemGetInfo(&free_b, &total_b));
+  if (need > 0.95 * (double) free_b)
+    fatal("[dlaf_mi355x] eigensolver: n = %ld needs %.1f GiB per rank for the replicated stages (band_to_tridiagonal, "
+          "tridiagonal_eigensolver), %.1f GiB are free\n", n, need / 1073741824.0, (double) free_b / 1073741824.0);
+}
+// every rank holds the n x n reflector matrix (T) ...
+template <class T>
+double reflector_bytes(long n) {
+  return (double) n * n * sizeof(T);
+}
+// ... and, behind the reductions, the n x k real eigenvector matrix, the divide & conquer workspaces (4 n^2 real) and
+// its columns of the internal eigenvector matrix
+template <class T>
+double solver_bytes(long n, int nb, int npcol, long begin, long end) {
+  using R = real_t<T>;
+  const long b0 = (begin / nb) * nb;
+  return (double) n * n * 4.0 * sizeof(R) + (double) n * (end - begin) * sizeof(R) +
+         (double) (end - b0) * bt_aligned_ld(n) / npcol * sizeof(T);
+}
+
+// what the reductions leave resident
+template <class T>
+struct Reduced {
+  std::vector<T> taus;
+  int band = 0;
+  real_t<T>* d = nullptr;
+  real_t<T>* e = nullptr;
+  T* v = nullptr;
+  Reduced() = default;
+  Reduced(const Reduced&) = delete;
+  Reduced& operator=(const Reduced&) = delete;
+  void release() {
+    for (real_t<T>* q : {d, e})
+      if (q)
+        DLAF_HIP_CHECK(pool_free(q));
+    if (v)
+      DLAF_HIP_CHECK(pool_free(v));
+    d = e = nullptr;
+    v = nullptr;
+  }
+  ~Reduced() { release(); }
+};
+
+// stages 1-2: reduction_to_band, band_to_tridiagonal (n > 0)
+template <class T>
+int eigensolver_reductions(DeviceMatrix<T>& A, Reduced<T>& r) {
+  using R = real_t<T>;
+  const long n = A.n;
+  Grid* g = A.grid;
+  hipStream_t s = A.s_high;
+  r.band = get_band_size(A.nb);  // eigensolver/impl.h:41
+  r.taus.assign((size_t) std::max<long>(0, n - r.band - 1) + 1, T{});
+  int info = agreed(g, reduction_to_band_device(A, r.band, r.taus.data()));
+  debug_checksum(g, s, "A after red2band", A.tiles, (size_t) A.ltr * A.ltc * A.tile_elems * sizeof(T));
   {
     double ms = 0, fl = 0;
     red2band_last_profile(&ms, &fl);
@@ -519,35 +552,50 @@ int hermitian_eigensolver_device(DeviceMatrix<T>& A, real_t<T>* w_host, GeneralM
   }
   if (info != 0)
     return info;
-  R* d = ealloc<R>((size_t) n);
-  R* e = ealloc<R>((size_t) n);
-  T* v = ealloc<T>((size_t) n * n);
-  info = agreed(band_to_tridiag_device(A, band, d, e, v, n));
+  r.d = ealloc<R>((size_t) n);
+  r.e = ealloc<R>((size_t) n);
+  r.v = ealloc<T>((size_t) n * n);
+  info = agreed(g, band_to_tridiag_device(A, r.band, r.d, r.e, r.v, n));
   if (info != 0) {
-    for (R* q : {d, e})
-      DLAF_HIP_CHECK(pool_free(q));
-    DLAF_HIP_CHECK(pool_free(v));
+    r.release();
     return info;
   }
-  checksum("d", d, (size_t) n * sizeof(R));
-  checksum("e", e, (size_t) (n - 1) * sizeof(R));
-  checksum("v", v, (size_t) n * n * sizeof(T));
+  debug_checksum(g, s, "d", r.d, (size_t) n * sizeof(R));
+  debug_checksum(g, s, "e", r.e, (size_t) (n - 1) * sizeof(R));
+  debug_checksum(g, s, "v", r.v, (size_t) n * n * sizeof(T));
+  return 0;
+}
+
+// stages 3-5: tridiagonal_eigensolver, bt_band_to_tridiagonal, bt_reduction_to_band; releases what the reductions left
+template <class T>
+int eigensolver_back(DeviceMatrix<T>& A, Reduced<T>& r, real_t<T>* w_host, GeneralMatrix<T>& Z, long begin, long end) {
+  using R = real_t<T>;
+  const long n = A.n;
+  const int nb = A.nb;
+  Grid* g = A.grid;
+  TileMatrix<T>& C = Z.m;
+  const long b0 = (begin / nb) * nb, pad = begin - b0, k = end - begin;
+  if (C.grid != g || C.nb != nb || C.rows.n != n || C.cols.n != end - b0 || C.rows.src != A.rows.src || C.transposed)
+    fatal("[dlaf_mi355x] eigensolver: the eigenvector matrix must be n x %ld with A's block size and row source rank\n",
+          end - b0);
+  hipStream_t s = A.s_high;
+  const int band = r.band;
   R* wd = ealloc<R>((size_t) n);
   R* zr = ealloc<R>((size_t) n * k);
   {
     StageTimer t(s);
-    tridiag_solver_device<R>(n, nb, d, e, wd, zr, n, begin, end, s, g->nranks > 1 ? grid_transport(*g) : nullptr);
+    tridiag_solver_device<R>(n, nb, r.d, r.e, wd, zr, n, begin, end, s, g->nranks > 1 ? grid_transport(*g) : nullptr);
     g_stage_ms[2] = t.stop();
   }
-  checksum("w", wd, (size_t) n * sizeof(R));
-  checksum("z (tridiagonal)", zr, (size_t) n * k * sizeof(R));
+  debug_checksum(g, s, "w", wd, (size_t) n * sizeof(R));
+  debug_checksum(g, s, "z (tridiagonal)", zr, (size_t) n * k * sizeof(R));
   DLAF_HIP_CHECK(hipMemcpyAsync(w_host, wd, (size_t) n * sizeof(R), hipMemcpyDeviceToHost, s));
   if (k == 0) {
     // no eigenvector is wanted: the eigenvalues are all there is
     DLAF_HIP_CHECK(hipStreamSynchronize(s));
-    for (R* q : {d, e, wd, zr})
+    for (R* q : {wd, zr})
       DLAF_HIP_CHECK(pool_free(q));
-    DLAF_HIP_CHECK(pool_free(v));
+    r.release();
     g_stage_ms[3] = g_stage_ms[4] = 0;
     return 0;
   }
@@ -559,19 +607,19 @@ int hermitian_eigensolver_device(DeviceMatrix<T>& A, real_t<T>* w_host, GeneralM
   launch_cols_gather_cast<R, T>(zr, n, n, nb, C.cols.P, C.cols.shift(), ncl, pad, el, lde, s);
   {
     StageTimer t(s);
-    bt_band_to_tridiag_device(n, band, v, n, el, lde, ncl, s);
+    bt_band_to_tridiag_device(n, band, r.v, n, el, lde, ncl, s);
     g_stage_ms[3] = t.stop();
   }
-  checksum("E after bt_b2t", el, (size_t) lde * std::max<long>(ncl, 1) * sizeof(T));
+  debug_checksum(g, s, "E after bt_b2t", el, (size_t) lde * std::max<long>(ncl, 1) * sizeof(T));
   launch_rows_to_tiles(el, lde, n, ncl, nb, C.rows.P, C.rows.shift(), C.ltr, C.ltc, C.tiles, s);
   DLAF_HIP_CHECK(hipStreamSynchronize(s));
-  for (R* q : {d, e, wd, zr})
+  for (R* q : {wd, zr})
     DLAF_HIP_CHECK(pool_free(q));
-  DLAF_HIP_CHECK(pool_free(v));
+  r.release();
   DLAF_HIP_CHECK(pool_free(el_alloc));
-  checksum("C before bt_red2band", C.tiles, (size_t) C.ltr * C.ltc * C.tile_elems * sizeof(T));
-  info = agreed(bt_reduction_to_band_device(band, C, A, taus.data()));
-  checksum("C after bt_red2band", C.tiles, (size_t) C.ltr * C.ltc * C.tile_elems * sizeof(T));
+  debug_checksum(g, s, "C before bt_red2band", C.tiles, (size_t) C.ltr * C.ltc * C.tile_elems * sizeof(T));
+  const int info = agreed(g, bt_reduction_to_band_device(band, C, A, r.taus.data()));
+  debug_checksum(g, s, "C after bt_red2band", C.tiles, (size_t) C.ltr * C.ltc * C.tile_elems * sizeof(T));
   {
     double ms = 0, fl = 0;
     red2band_last_profile(&ms, &fl);
@@ -579,6 +627,99 @@ int hermitian_eigensolver_device(DeviceMatrix<T>& A, real_t<T>* w_host, GeneralM
   }
   return info;
 }
+
+// (vl, vu] -> [begin, end) = [count(vl), count(vu)): two Sturm counts of the computed tridiagonal matrix in one launch,
+// made the same on every rank before anybody acts on them (the replicated stages are deterministic, but a rank that
+// disagreed would hang the next collective).  vl >= vu: the empty range at count(vl).
+template <class T>
+void index_range_of_values(Grid* g, long n, const Reduced<T>& r, real_t<T> vl, real_t<T> vu, hipStream_t s, long& begin,
+                           long& end) {
+  using R = real_t<T>;
+  const R shifts[2] = {vl, vu};
+  long counts[2] = {0, 0};
+  sturm_count_device<R>(n, r.d, r.e, shifts, 2, counts, s);
+  if (g->nranks > 1 && g->transport) {
+    double v[2] = {(double) counts[0], (double) counts[1]};
+    g->transport->allreduce_max(v, 2, g->nprow, g->npcol, g->myrow, g->mycol);
+    counts[0] = (long) v[0];
+    counts[1] = (long) v[1];
+  }
+  if (counts[0] < 0)
+    fatal("[dlaf_mi355x] eigensolver: the tridiagonal matrix holds a NaN or an Inf: no eigenvalue can be selected by "
+          "value\n");
+  begin = counts[0];
+  end = vl < vu ? std::max(counts[0], counts[1]) : counts[0];
+}
+
+// The eigensolver on the resident A: the index range [begin, end) as given, or, with by_value = {vl, vu}, found
+// between the two halves and returned.  zh: the internal eigenvector matrix it creates (see partial_spectrum_plan).
+template <class T>
+int hermitian_eigensolver_device(DeviceMatrix<T>& A, real_t<T>* w_host, int z_isrc, int z_jsrc, const real_t<T>* by_value,
+                                 long& begin, long& end, std::unique_ptr<MatrixBase>& zh, PartialSpectrumPlan& pl) {
+  const long n = A.n;
+  const int nb = A.nb;
+  Grid* g = A.grid;
+  if (by_value)
+    begin = end = 0;
+  else
+    check_eigenvalues_index("eigensolver", n, begin, end);
+  auto make_z = [&] {
+    pl = partial_spectrum_plan(n, nb, g->npcol, g->mycol, z_jsrc, begin, end);
+    zh.reset(general_matrix_create(g, TypeInfo<T>::tag, n, end - pl.b0, nb, z_isrc, pl.jsrc));
+  };
+  if (n == 0) {
+    make_z();
+    return 0;
+  }
+  check_replicated_memory(n, reflector_bytes<T>(n) + (by_value ? 0.0 : solver_bytes<T>(n, nb, g->npcol, begin, end)));
+  Reduced<T> r;
+  int info = eigensolver_reductions(A, r);
+  if (info != 0) {
+    make_z();
+    return info;
+  }
+  if (by_value) {
+    index_range_of_values(g, n, r, by_value[0], by_value[1], A.s_high, begin, end);
+    check_replicated_memory(n, solver_bytes<T>(n, nb, g->npcol, begin, end));
+  }
+  make_z();
+  return eigensolver_back(A, r, w_host, static_cast<GeneralMatrix<T>&>(*zh), begin, end);
+}
+
+// Eigenvalues only, on the resident A: the reductions, then bisection for [begin, end) on the tridiagonal matrix.  No
+// divide & conquer, no back-transformation, no eigenvector matrix; w_host[begin, end) is written and nothing else.
+template <class T>
+int hermitian_eigenvalues_device(DeviceMatrix<T>& A, real_t<T>* w_host, long begin, long end) {
+  using R = real_t<T>;
+  const long n = A.n;
+  check_eigenvalues_index("eigenvalues", n, begin, end);
+  if (n == 0)
+    return 0;
+  hipStream_t s = A.s_high;
+  // what is still allocated: the reflector matrix band_to_tridiagonal writes
+  check_replicated_memory(n, reflector_bytes<T>(n));
+  Reduced<T> r;
+  const int info = eigensolver_reductions(A, r);
+  if (info != 0)
+    return info;
+  DLAF_HIP_CHECK(pool_free(r.v));
+  r.v = nullptr;
+  g_stage_ms[2] = g_stage_ms[3] = g_stage_ms[4] = 0;
+  if (end > begin) {
+    R* wd = ealloc<R>((size_t) n);
+    double* work = ealloc<double>(sturm_work_doubles(n));
+    StageTimer t(s);
+    tridiag_eigenvalues_device<R>(n, r.d, r.e, wd, begin, end, work, s);
+    g_stage_ms[2] = t.stop();
+    debug_checksum(A.grid, s, "w (bisection)", wd + begin, (size_t) (end - begin) * sizeof(R));
+    DLAF_HIP_CHECK(hipMemcpyAsync(w_host + begin, wd + begin, (size_t) (end - begin) * sizeof(R), hipMemcpyDeviceToHost, s));
+    DLAF_HIP_CHECK(hipStreamSynchronize(s));
+    DLAF_HIP_CHECK(pool_free(wd));
+    DLAF_HIP_CHECK(pool_free(work));
+  }
+  return 0;
+}
+}  // namespace
 
 // the local columns of the internal eigenvector matrix behind its padding -> their place in the caller's local array
 // (for the full spectrum: all of them, from column 0).  Nothing else of z is written.
@@ -600,57 +741,69 @@ static void download_eigenvectors(GeneralMatrix<T>& Z, const PartialSpectrumPlan
   DLAF_HIP_CHECK(hipStreamDestroy(s));
 }
 
-template <class T>
-int hermitian_eigensolver_host(Grid* g, char uplo, T* a, long lda, long n, int nb, int isrc, int jsrc, real_t<T>* w, T* z,
-                               long ldz, int z_isrc, int z_jsrc, long begin, long end) {
-  check_eigenvalues_index("eigensolver", n, begin, end);
+namespace {
+void check_uplo(const char* who, char uplo) {
   if (uplo != 'L' && uplo != 'l')
-    fatal("[dlaf_mi355x] eigensolver: uplo = %c is not implemented (neither upstream: eigensolver/impl.h:43-45)\n", uplo);
-  if (z_isrc != isrc)
-    fatal("[dlaf_mi355x] eigensolver: the eigenvector matrix must share A's row source rank (%d != %d)\n", z_isrc, isrc);
-  const PartialSpectrumPlan pl = partial_spectrum_plan(n, nb, g->npcol, g->mycol, z_jsrc, begin, end);
-  DeviceMatrix<T> A;
-  A.create(g, 'L', n, nb, isrc, jsrc);
-  A.upload(a, lda);
-  std::unique_ptr<MatrixBase> zh(general_matrix_create(g, TypeInfo<T>::tag, n, end - pl.b0, nb, z_isrc, pl.jsrc));
-  GeneralMatrix<T>& Z = static_cast<GeneralMatrix<T>&>(*zh);
-  const int r = hermitian_eigensolver_device(A, w, Z, begin, end);
-  A.download(a, lda, true);  // (upstream leaves the band + reflectors in A as well)
-  download_eigenvectors(Z, pl, z, ldz);
-  return r;
+    fatal("[dlaf_mi355x] %s: uplo = %c is not implemented (neither upstream: eigensolver/impl.h:43-45)\n", who, uplo);
 }
 
 template <class T>
-int hermitian_gen_eigensolver_host(Grid* g, char uplo, T* a, long lda, T* b, long ldb, long n, int nb, int a_isrc,
-                                   int a_jsrc, int b_isrc, int b_jsrc, real_t<T>* w, T* z, long ldz, int z_isrc,
-                                   int z_jsrc, bool b_factorized, long begin, long end) {
-  check_eigenvalues_index("gen_eigensolver", n, begin, end);
-  if (uplo != 'L' && uplo != 'l')
-    fatal("[dlaf_mi355x] gen_eigensolver: uplo = %c is not implemented (neither upstream: eigensolver/impl.h:43-45)\n", uplo);
+int eigensolver_host_impl(Grid* g, char uplo, T* a, long lda, long n, int nb, int isrc, int jsrc, real_t<T>* w, T* z,
+                          long ldz, int z_isrc, int z_jsrc, const real_t<T>* by_value, long& begin, long& end) {
+  if (!by_value)
+    check_eigenvalues_index("eigensolver", n, begin, end);
+  check_uplo("eigensolver", uplo);
+  if (z_isrc != isrc)
+    fatal("[dlaf_mi355x] eigensolver: the eigenvector matrix must share A's row source rank (%d != %d)\n", z_isrc, isrc);
+  DeviceMatrix<T> A;
+  A.create(g, 'L', n, nb, isrc, jsrc);
+  A.upload(a, lda);
+  std::unique_ptr<MatrixBase> zh;
+  PartialSpectrumPlan pl;
+  const int r = hermitian_eigensolver_device(A, w, z_isrc, z_jsrc, by_value, begin, end, zh, pl);
+  A.download(a, lda, true);  // (upstream leaves the band + reflectors in A as well)
+  download_eigenvectors(static_cast<GeneralMatrix<T>&>(*zh), pl, z, ldz);
+  return r;
+}
+
+// gen_eigensolver/impl.h:33-60: cholesky_factorization(uplo, B) unless the caller passes the factor,
+// generalized_to_standard(uplo, A, B); A, B resident on return (info == 0)
+template <class T>
+int gen_to_std_resident(const char* who, Grid* g, char uplo, const T* a, long lda, T* b, long ldb, long n, int nb, int a_isrc,
+                        int a_jsrc, int b_isrc, int b_jsrc, int z_isrc, bool b_factorized, DeviceMatrix<T>& A,
+                        DeviceMatrix<T>& B) {
+  check_uplo(who, uplo);
   if (a_isrc != b_isrc || a_jsrc != b_jsrc || z_isrc != a_isrc)
-    fatal("[dlaf_mi355x] gen_eigensolver: A, B and the eigenvector matrix must share their source rank\n");
-  DeviceMatrix<T> A, B;
+    fatal("[dlaf_mi355x] %s: A, B and the eigenvector matrix must share their source rank\n", who);
   A.create(g, 'L', n, nb, a_isrc, a_jsrc);
   B.create(g, 'L', n, nb, b_isrc, b_jsrc);
   A.upload(a, lda);
   B.upload(b, ldb);
-  // gen_eigensolver/impl.h:33-60: cholesky_factorization(uplo, B) unless the caller passes the factor,
-  // generalized_to_standard(uplo, A, B), the eigensolver, triangular_solver(Left, uplo, ConjTrans, NonUnit, 1, B, Z)
-  int info = 0;
   if (!b_factorized) {
-    info = B.factorize();
+    const int info = B.factorize();
     if (info != 0)
       return info;
   }
-  info = gen_to_std_device(A, B);
+  return gen_to_std_device(A, B);
+}
+
+template <class T>
+int gen_eigensolver_host_impl(Grid* g, char uplo, T* a, long lda, T* b, long ldb, long n, int nb, int a_isrc, int a_jsrc,
+                              int b_isrc, int b_jsrc, real_t<T>* w, T* z, long ldz, int z_isrc, int z_jsrc,
+                              bool b_factorized, const real_t<T>* by_value, long& begin, long& end) {
+  if (!by_value)
+    check_eigenvalues_index("gen_eigensolver", n, begin, end);
+  DeviceMatrix<T> A, B;
+  int info = gen_to_std_resident("gen_eigensolver", g, uplo, a, lda, b, ldb, n, nb, a_isrc, a_jsrc, b_isrc, b_jsrc, z_isrc,
+                                 b_factorized, A, B);
   if (info != 0)
     return info;
-  const PartialSpectrumPlan pl = partial_spectrum_plan(n, nb, g->npcol, g->mycol, z_jsrc, begin, end);
-  std::unique_ptr<MatrixBase> zh(general_matrix_create(g, TypeInfo<T>::tag, n, end - pl.b0, nb, z_isrc, pl.jsrc));
-  GeneralMatrix<T>& Z = static_cast<GeneralMatrix<T>&>(*zh);
-  info = hermitian_eigensolver_device(A, w, Z, begin, end);
+  std::unique_ptr<MatrixBase> zh;
+  PartialSpectrumPlan pl;
+  info = hermitian_eigensolver_device(A, w, z_isrc, z_jsrc, by_value, begin, end, zh, pl);
   if (info != 0)
     return info;
+  // triangular_solver(Left, uplo, ConjTrans, NonUnit, 1, B, Z)
   const T one = make_host_el<T>(1.0);
   B.type = TypeInfo<T>::tag;
   if (end > begin)
@@ -658,7 +811,67 @@ int hermitian_gen_eigensolver_host(Grid* g, char uplo, T* a, long lda, T* b, lon
   A.download(a, lda, true);
   if (!b_factorized)
     B.download(b, ldb, true);
-  download_eigenvectors(Z, pl, z, ldz);
+  download_eigenvectors(static_cast<GeneralMatrix<T>&>(*zh), pl, z, ldz);
+  return info;
+}
+}  // namespace
+
+template <class T>
+int hermitian_eigensolver_host(Grid* g, char uplo, T* a, long lda, long n, int nb, int isrc, int jsrc, real_t<T>* w, T* z,
+                               long ldz, int z_isrc, int z_jsrc, long begin, long end) {
+  return eigensolver_host_impl<T>(g, uplo, a, lda, n, nb, isrc, jsrc, w, z, ldz, z_isrc, z_jsrc, nullptr, begin, end);
+}
+
+template <class T>
+int hermitian_eigensolver_by_value_host(Grid* g, char uplo, T* a, long lda, long n, int nb, int isrc, int jsrc,
+                                        real_t<T>* w, T* z, long ldz, int z_isrc, int z_jsrc, real_t<T> vl, real_t<T> vu,
+                                        long* begin, long* end) {
+  const real_t<T> by_value[2] = {vl, vu};
+  return eigensolver_host_impl<T>(g, uplo, a, lda, n, nb, isrc, jsrc, w, z, ldz, z_isrc, z_jsrc, by_value, *begin, *end);
+}
+
+template <class T>
+int hermitian_gen_eigensolver_host(Grid* g, char uplo, T* a, long lda, T* b, long ldb, long n, int nb, int a_isrc,
+                                   int a_jsrc, int b_isrc, int b_jsrc, real_t<T>* w, T* z, long ldz, int z_isrc,
+                                   int z_jsrc, bool b_factorized, long begin, long end) {
+  return gen_eigensolver_host_impl<T>(g, uplo, a, lda, b, ldb, n, nb, a_isrc, a_jsrc, b_isrc, b_jsrc, w, z, ldz, z_isrc,
+                                      z_jsrc, b_factorized, nullptr, begin, end);
+}
+
+template <class T>
+int hermitian_gen_eigensolver_by_value_host(Grid* g, char uplo, T* a, long lda, T* b, long ldb, long n, int nb, int a_isrc,
+                                            int a_jsrc, int b_isrc, int b_jsrc, real_t<T>* w, T* z, long ldz, int z_isrc,
+                                            int z_jsrc, bool b_factorized, real_t<T> vl, real_t<T> vu, long* begin,
+                                            long* end) {
+  const real_t<T> by_value[2] = {vl, vu};
+  return gen_eigensolver_host_impl<T>(g, uplo, a, lda, b, ldb, n, nb, a_isrc, a_jsrc, b_isrc, b_jsrc, w, z, ldz, z_isrc,
+                                      z_jsrc, b_factorized, by_value, *begin, *end);
+}
+
+template <class T>
+int hermitian_eigenvalues_host(Grid* g, char uplo, const T* a, long lda, long n, int nb, int isrc, int jsrc, real_t<T>* w,
+                               long begin, long end) {
+  check_eigenvalues_index("eigenvalues", n, begin, end);
+  check_uplo("eigenvalues", uplo);
+  DeviceMatrix<T> A;
+  A.create(g, 'L', n, nb, isrc, jsrc);
+  A.upload(a, lda);
+  return hermitian_eigenvalues_device(A, w, begin, end);
+}
+
+template <class T>
+int hermitian_gen_eigenvalues_host(Grid* g, char uplo, const T* a, long lda, T* b, long ldb, long n, int nb, int a_isrc,
+                                   int a_jsrc, int b_isrc, int b_jsrc, real_t<T>* w, bool b_factorized, long begin,
+                                   long end) {
+  check_eigenvalues_index("gen_eigenvalues", n, begin, end);
+  DeviceMatrix<T> A, B;
+  int info = gen_to_std_resident("gen_eigenvalues", g, uplo, a, lda, b, ldb, n, nb, a_isrc, a_jsrc, b_isrc, b_jsrc, a_isrc,
+                                 b_factorized, A, B);
+  if (info != 0)
+    return info;
+  info = hermitian_eigenvalues_device(A, w, begin, end);
+  if (info == 0 && !b_factorized)
+    B.download(b, ldb, true);
   return info;
 }
 
@@ -667,6 +880,14 @@ int hermitian_gen_eigensolver_host(Grid* g, char uplo, T* a, long lda, T* b, lon
                                              long, long);                                                                \
   template int hermitian_gen_eigensolver_host<T>(Grid*, char, T*, long, T*, long, long, int, int, int, int, int,         \
                                                  real_t<T>*, T*, long, int, int, bool, long, long);                      \
+  template int hermitian_eigensolver_by_value_host<T>(Grid*, char, T*, long, long, int, int, int, real_t<T>*, T*, long, \
+                                                      int, int, real_t<T>, real_t<T>, long*, long*);                     \
+  template int hermitian_gen_eigensolver_by_value_host<T>(Grid*, char, T*, long, T*, long, long, int, int, int, int,     \
+                                                          int, real_t<T>*, T*, long, int, int, bool, real_t<T>,          \
+                                                          real_t<T>, long*, long*);                                      \
+  template int hermitian_eigenvalues_host<T>(Grid*, char, const T*, long, long, int, int, int, real_t<T>*, long, long);  \
+  template int hermitian_gen_eigenvalues_host<T>(Grid*, char, const T*, long, T*, long, long, int, int, int, int, int,   \
+                                                 real_t<T>*, bool, long, long);                                          \
   template int band_to_tridiag_device<T>(DeviceMatrix<T>&, int, real_t<T>*, real_t<T>*, T*, long);                       \
   template int band_to_tridiag_host<T>(Grid*, const T*, long, long, int, int, int, int, real_t<T>*, real_t<T>*, T*, long); \
   template int bt_band_to_tridiag_device<T>(long, int, const T*, long, T*, long, long, hipStream_t);                     \

@@ -50,6 +50,46 @@ int hermitian_gen_eigensolver_host(Grid* g, char uplo, T* a, long lda, T* b, lon
                                    int a_jsrc, int b_isrc, int b_jsrc, real_t<T>* w, T* z, long ldz, int z_isrc,
                                    int z_jsrc, bool b_factorized, long begin, long end);
 
+// The same with the eigenvalue range given by value, LAPACK's range = 'V': the eigenpairs in (vl, vu].  After
+// band_to_tridiagonal the drivers take [begin, end) = [count(vl), count(vu)) from two Sturm counts of the computed
+// tridiagonal matrix (vl >= vu: the empty range at count(vl)), return it, and go on exactly as the entries above do
+// for that index range.  An eigenvalue within rounding of vl or vu may fall on either side.
+template <class T>
+int hermitian_eigensolver_by_value_host(Grid* g, char uplo, T* a, long lda, long n, int nb, int isrc, int jsrc,
+                                        real_t<T>* w, T* z, long ldz, int z_isrc, int z_jsrc, real_t<T> vl, real_t<T> vu,
+                                        long* begin, long* end);
+template <class T>
+int hermitian_gen_eigensolver_by_value_host(Grid* g, char uplo, T* a, long lda, T* b, long ldb, long n, int nb, int a_isrc,
+                                            int a_jsrc, int b_isrc, int b_jsrc, real_t<T>* w, T* z, long ldz, int z_isrc,
+                                            int z_jsrc, bool b_factorized, real_t<T> vl, real_t<T> vu, long* begin,
+                                            long* end);
+
+// Eigenvalues only: reduction_to_band, band_to_tridiagonal, bisection for the eigenvalues [begin, end) (0-based,
+// half-open).  w[begin, end) is written (the same on every rank) and nothing else; a is read only (its resident copy is
+// destroyed); the generalized form leaves the Cholesky factor in b as the eigensolver does.  No divide & conquer, no
+// back-transformation, no eigenvector matrix: the replicated memory is the n x n reflector matrix alone.
+template <class T>
+int hermitian_eigenvalues_host(Grid* g, char uplo, const T* a, long lda, long n, int nb, int isrc, int jsrc, real_t<T>* w,
+                               long begin, long end);
+template <class T>
+int hermitian_gen_eigenvalues_host(Grid* g, char uplo, const T* a, long lda, T* b, long ldb, long n, int nb, int a_isrc,
+                                   int a_jsrc, int b_isrc, int b_jsrc, real_t<T>* w, bool b_factorized, long begin,
+                                   long end);
+
+// Eigenvalues of the symmetric tridiagonal matrix d (n), e (n - 1) by bisection on Sturm counts (kernels_sturm.hip).
+// _device: d, e, w on the device, work = sturm_work_doubles(n) doubles; enqueues on s and returns.  Only w[begin, end)
+// is written.  sturm_count: counts[i] = the number of eigenvalues <= shifts[i] (-1 when d or e is not finite); the
+// _device form takes d, e on the device and host shifts / counts, and waits for the stream.
+template <class R>
+void tridiag_eigenvalues_device(long n, const R* d, const R* e, R* w, long begin, long end, double* work, hipStream_t s);
+template <class R>
+int tridiag_eigenvalues_host(long n, const R* d, const R* e, R* w, long begin, long end);
+template <class R>
+void sturm_count_device(long n, const R* d, const R* e, const R* shifts_host, long nshifts, long* counts_host,
+                        hipStream_t s);
+template <class R>
+int sturm_count_host(long n, const R* d, const R* e, long nshifts, const R* shifts, long* counts);
+
 // Index arithmetic of a partial spectrum.  The drivers hold the eigenvectors of [begin, end) in an internal matrix that
 // covers the global columns [b0, end), b0 = (begin / nb) nb: whole tile columns are dropped in front of it, so its local
 // columns are a contiguous run of the caller's local columns, and the columns [b0, begin) are zero padding that is
@@ -66,7 +106,8 @@ void check_eigenvalues_index(const char* who, long n, long begin, long end);
 PartialSpectrumPlan partial_spectrum_plan(long n, int nb, int npcol, int mycol, int z_jsrc, long begin, long end);
 
 // per-stage device times (ms) of the last eigensolver call on this process:
-// 0 reduction_to_band, 1 band_to_tridiagonal, 2 tridiagonal solver, 3 bt_band_to_tridiagonal, 4 bt_reduction_to_band
+// 0 reduction_to_band, 1 band_to_tridiagonal, 2 tridiagonal solver (the bisection of an eigenvalues-only call),
+// 3 bt_band_to_tridiagonal, 4 bt_reduction_to_band (both 0 after an eigenvalues-only call)
 void eigensolver_last_profile(double ms[5]);
 
 }  // namespace dlaf_mi355x

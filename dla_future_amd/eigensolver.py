@@ -162,9 +162,101 @@ def _eig_name(t: str) -> str:
     return "symmetric" if t in "sd" else "hermitian"
 
 
+def _one_selection(eigenvalues_index, eigenvalues_value):
+    if eigenvalues_index is not None and eigenvalues_value is not None:
+        raise ValueError("eigenvalues_index and eigenvalues_value are mutually exclusive")
+
+
+# ---- eigenvalues only: bisection on Sturm counts of the tridiagonal matrix ------------------
+def sturm_layout():
+    """(pairs of the tridiagonal matrix staged through LDS at a time, threads per workgroup) of the Sturm kernels."""
+    out = (C.c_int * 2)()
+    lib().dlaf_mi355x_sturm_layout(out)
+    return out[0], out[1]
+
+
+def tridiagonal_eigenvalues(d: np.ndarray, e: np.ndarray, eigenvalues_index=None, w: np.ndarray | None = None):
+    """Eigenvalues of the symmetric tridiagonal matrix d (n), e (n - 1) by bisection on Sturm counts, local, on the GPU:
+    no eigenvectors, O(n) memory.  eigenvalues_index = (begin, end): only w[begin:end] is computed and written (0-based,
+    half-open; default all n).  w: a preallocated array to write into.  Returns w (ascending)."""
+    t = type_char(d.dtype)
+    n = d.shape[0]
+    d = np.ascontiguousarray(d)
+    e = np.ascontiguousarray(e, dtype=d.dtype)
+    if w is None:
+        w = np.zeros(n, dtype=d.dtype)
+    begin, end = (0, n) if eigenvalues_index is None else _index_range(eigenvalues_index, n)
+    name = f"dlaf_mi355x_tridiagonal_eigenvalues_{t}"
+    r = getattr(lib(), name)(n, _ptr(d), _ptr(e), _ptr(w), begin, end)
+    if r != 0:
+        raise RuntimeError(f"{name} returned {r}")
+    return w
+
+
+def tridiagonal_sturm_count(d: np.ndarray, e: np.ndarray, shifts) -> np.ndarray:
+    """counts[i] = the number of eigenvalues of the symmetric tridiagonal matrix d, e that are <= shifts[i] (LAPACK
+    dstebz's convention), one GPU thread per shift.  -1 for every shift when d or e holds a NaN or an Inf."""
+    t = type_char(d.dtype)
+    n = d.shape[0]
+    d = np.ascontiguousarray(d)
+    e = np.ascontiguousarray(e, dtype=d.dtype)
+    shifts = np.ascontiguousarray(shifts, dtype=d.dtype).reshape(-1)
+    counts = np.zeros(shifts.shape[0], dtype=np.int64)
+    name = f"dlaf_mi355x_tridiagonal_sturm_count_{t}"
+    r = getattr(lib(), name)(n, _ptr(d), _ptr(e), shifts.shape[0], _ptr(shifts), _ptr(counts))
+    if r != 0:
+        raise RuntimeError(f"{name} returned {r}")
+    return counts
+
+
+def hermitian_eigenvalues(grid: Grid, uplo: str, a: np.ndarray, nb: int, isrc: int = 0, jsrc: int = 0,
+                          n: int | None = None, eigenvalues_index=None, w: np.ndarray | None = None) -> np.ndarray:
+    """Eigenvalues only (dlaf_{symmetric,hermitian}_eigenvalues_*): reduction_to_band, band_to_tridiagonal and bisection
+    for the eigenvalues eigenvalues_index = [begin, end) (default all n).  No divide & conquer, no back-transformation,
+    no eigenvector matrix.  `a` (local part, the uplo triangle referenced) is not modified.  Only w[begin:end] is
+    written (w: a preallocated array of n reals); returns w."""
+    t = type_char(a.dtype)
+    if n is None:
+        if grid.nranks != 1:
+            raise ValueError("the global size n is required on a distributed grid")
+        n = a.shape[0]
+    if w is None:
+        w = np.zeros(n, dtype=_real_dtype(a.dtype))
+    begin, end = (0, n) if eigenvalues_index is None else _index_range(eigenvalues_index, n)
+    da = make_descriptor(n, nb, _ld_of(a), isrc, jsrc)
+    name = f"dlaf_{_eig_name(t)}_eigenvalues_{t}"
+    r = getattr(lib(), name)(grid.context, uplo.encode()[0:1], _ptr(a), da, _ptr(w), begin, end)
+    if r != 0:
+        raise RuntimeError(f"{name} returned {r}")
+    return w
+
+
+def hermitian_generalized_eigenvalues(grid: Grid, uplo: str, a: np.ndarray, b: np.ndarray, nb: int, isrc: int = 0,
+                                      jsrc: int = 0, n: int | None = None, factorized: bool = False,
+                                      eigenvalues_index=None, w: np.ndarray | None = None) -> np.ndarray:
+    """Eigenvalues only of A x = lambda B x (dlaf_{symmetric,hermitian}_generalized_eigenvalues[_factorized]_*):
+    Cholesky of b (unless factorized), generalized_to_standard, then as hermitian_eigenvalues.  b ends up holding its
+    Cholesky factor."""
+    t = type_char(a.dtype)
+    if n is None:
+        if grid.nranks != 1:
+            raise ValueError("the global size n is required on a distributed grid")
+        n = a.shape[0]
+    if w is None:
+        w = np.zeros(n, dtype=_real_dtype(a.dtype))
+    begin, end = (0, n) if eigenvalues_index is None else _index_range(eigenvalues_index, n)
+    da = make_descriptor(n, nb, _ld_of(a), isrc, jsrc)
+    db = make_descriptor(n, nb, _ld_of(b), isrc, jsrc)
+    name = f"dlaf_{_eig_name(t)}_generalized_eigenvalues{'_factorized' if factorized else ''}_{t}"
+    r = getattr(lib(), name)(grid.context, uplo.encode()[0:1], _ptr(a), da, _ptr(b), db, _ptr(w), begin, end)
+    if r != 0:
+        raise RuntimeError(f"{name} returned {r}")
+    return w
+
+
 def hermitian_eigensolver(grid: Grid, uplo: str, a: np.ndarray, nb: int, isrc: int = 0, jsrc: int = 0,
                           n: int | None = None, z_jsrc: int | None = None, z_shape=None, eigenvalues_index=None,
-                          z: np.ndarray | None = None):
+                          z: np.ndarray | None = None, eigenvalues_value=None):
     """dlaf::hermitian_eigensolver(grid, uplo, mat_a, evals, evecs) through the reference's C entry
     dlaf_{symmetric,hermitian}_eigensolver_* (include/dlaf_c/eigensolver/eigensolver.h:39-58).  `a` (local part, the uplo
     triangle referenced) is destroyed.  Returns (w, z): all eigenvalues (ascending) and the local part of the
@@ -172,8 +264,13 @@ def hermitian_eigensolver(grid: Grid, uplo: str, a: np.ndarray, nb: int, isrc: i
 
     eigenvalues_index = (begin, end): the *_partial_spectrum entry -- only the global columns [begin, end) of z (0-based,
     half-open) are written, with the eigenvectors of those eigenvalues; w still holds all n.  z: a preallocated
-    column-major local part to write into (nothing outside the wanted columns is touched)."""
+    column-major local part to write into (nothing outside the wanted columns is touched).
+
+    eigenvalues_value = (vl, vu): the *_partial_spectrum_by_value entry -- the eigenpairs with eigenvalues in (vl, vu].
+    Returns (w, z, (begin, end)): the index range the two Sturm counts of the tridiagonal matrix gave, and otherwise what
+    eigenvalues_index=(begin, end) returns.  An eigenvalue within rounding of vl or vu may fall on either side."""
     t = type_char(a.dtype)
+    _one_selection(eigenvalues_index, eigenvalues_value)
     if n is None:
         if grid.nranks != 1:
             raise ValueError("the global size n is required on a distributed grid")
@@ -186,6 +283,14 @@ def hermitian_eigensolver(grid: Grid, uplo: str, a: np.ndarray, nb: int, isrc: i
     da = make_descriptor(n, nb, _ld_of(a), isrc, jsrc)
     dz = make_descriptor(n, nb, _ld_of(z), isrc, z_jsrc)
     name = f"dlaf_{_eig_name(t)}_eigensolver_{t}"
+    if eigenvalues_value is not None:
+        name = f"dlaf_{_eig_name(t)}_eigensolver_partial_spectrum_by_value_{t}"
+        begin, end = C.c_long(-1), C.c_long(-1)
+        r = getattr(lib(), name)(grid.context, uplo.encode()[0:1], _ptr(a), da, _ptr(w), _ptr(z), dz,
+                                 float(eigenvalues_value[0]), float(eigenvalues_value[1]), C.byref(begin), C.byref(end))
+        if r != 0:
+            raise RuntimeError(f"{name} returned {r}")
+        return w, z, (begin.value, end.value)
     if eigenvalues_index is None:
         r = getattr(lib(), name)(grid.context, uplo.encode()[0:1], _ptr(a), da, _ptr(w), _ptr(z), dz)
     else:
@@ -199,11 +304,12 @@ def hermitian_eigensolver(grid: Grid, uplo: str, a: np.ndarray, nb: int, isrc: i
 
 def hermitian_generalized_eigensolver(grid: Grid, uplo: str, a: np.ndarray, b: np.ndarray, nb: int, isrc: int = 0,
                                       jsrc: int = 0, n: int | None = None, factorized: bool = False,
-                                      eigenvalues_index=None, z: np.ndarray | None = None):
+                                      eigenvalues_index=None, z: np.ndarray | None = None, eigenvalues_value=None):
     """dlaf::hermitian_generalized_eigensolver(grid, uplo, mat_a, mat_b, evals, evecs) through the reference's C entry
     (include/dlaf_c/eigensolver/gen_eigensolver.h:44-135).  a is destroyed, b ends up holding its Cholesky factor.
-    eigenvalues_index, z: as in hermitian_eigensolver."""
+    eigenvalues_index, z, eigenvalues_value: as in hermitian_eigensolver."""
     t = type_char(a.dtype)
+    _one_selection(eigenvalues_index, eigenvalues_value)
     if n is None:
         if grid.nranks != 1:
             raise ValueError("the global size n is required on a distributed grid")
@@ -215,6 +321,14 @@ def hermitian_generalized_eigensolver(grid: Grid, uplo: str, a: np.ndarray, b: n
     db = make_descriptor(n, nb, _ld_of(b), isrc, jsrc)
     dz = make_descriptor(n, nb, _ld_of(z), isrc, jsrc)
     name = f"dlaf_{_eig_name(t)}_generalized_eigensolver{'_factorized' if factorized else ''}"
+    if eigenvalues_value is not None:
+        name += f"_partial_spectrum_by_value_{t}"
+        begin, end = C.c_long(-1), C.c_long(-1)
+        r = getattr(lib(), name)(grid.context, uplo.encode()[0:1], _ptr(a), da, _ptr(b), db, _ptr(w), _ptr(z), dz,
+                                 float(eigenvalues_value[0]), float(eigenvalues_value[1]), C.byref(begin), C.byref(end))
+        if r != 0:
+            raise RuntimeError(f"{name} returned {r}")
+        return w, z, (begin.value, end.value)
     if eigenvalues_index is None:
         name += f"_{t}"
         r = getattr(lib(), name)(grid.context, uplo.encode()[0:1], _ptr(a), da, _ptr(b), db, _ptr(w), _ptr(z), dz)
@@ -248,6 +362,65 @@ def pxheevd_partial_spectrum(uplo: str, a: np.ndarray, desca, z: np.ndarray, des
     info = C.c_int(-1)
     getattr(lib(), name)(uplo.encode()[0:1], n, _ptr(a), 1, 1, da, _ptr(w), _ptr(z), 1, 1, dz, il, iu, C.byref(info))
     return w, info.value
+
+
+def pxheevd_eigenvalues(uplo: str, a: np.ndarray, desca, il: int, iu: int, n: int, w: np.ndarray | None = None):
+    """dlaf_p{s,d}syevd_eigenvalues / dlaf_p{c,z}heevd_eigenvalues: eigenvalues only through the ScaLAPACK-like argument
+    list, 1-based inclusive (il, iu) in front of info.  Returns (w, info); only w[il - 1:iu] is written."""
+    t = type_char(a.dtype)
+    name = f"dlaf_p{t}{'syevd' if t in 'sd' else 'heevd'}_eigenvalues"
+    if w is None:
+        w = np.zeros(n, dtype=_real_dtype(a.dtype))
+    da = (C.c_int * 9)(*desca)
+    info = C.c_int(-1)
+    getattr(lib(), name)(uplo.encode()[0:1], n, _ptr(a), 1, 1, da, _ptr(w), il, iu, C.byref(info))
+    return w, info.value
+
+
+def pxheevd_partial_spectrum_by_value(uplo: str, a: np.ndarray, desca, z: np.ndarray, descz, vl: float, vu: float, n: int):
+    """dlaf_p{s,d}syevd_partial_spectrum_by_value / dlaf_p{c,z}heevd_partial_spectrum_by_value: the eigenpairs in
+    (vl, vu] through the ScaLAPACK-like argument list, with vl, vu, m in front of info.  Returns (w, m, info); z is
+    written in place (m columns, from the column of the first eigenvalue above vl)."""
+    t = type_char(a.dtype)
+    name = f"dlaf_p{t}{'syevd' if t in 'sd' else 'heevd'}_partial_spectrum_by_value"
+    w = np.zeros(n, dtype=_real_dtype(a.dtype))
+    da = (C.c_int * 9)(*desca)
+    dz = (C.c_int * 9)(*descz)
+    m, info = C.c_int(-1), C.c_int(-1)
+    getattr(lib(), name)(uplo.encode()[0:1], n, _ptr(a), 1, 1, da, _ptr(w), _ptr(z), 1, 1, dz, float(vl), float(vu),
+                         C.byref(m), C.byref(info))
+    return w, m.value, info.value
+
+
+def _gv_name(t: str) -> str:
+    return f"dlaf_p{t}{'sygvd' if t in 'sd' else 'hegvd'}"
+
+
+def pxhegvd_eigenvalues(uplo: str, a: np.ndarray, desca, b: np.ndarray, descb, il: int, iu: int, n: int,
+                        factorized: bool = False, w: np.ndarray | None = None):
+    """dlaf_p{s,d}sygvd_eigenvalues[_factorized] / dlaf_p{c,z}hegvd_eigenvalues[_factorized]: eigenvalues only of
+    A x = lambda B x through the ScaLAPACK-like argument list.  Returns (w, info); only w[il - 1:iu] is written."""
+    t = type_char(a.dtype)
+    name = _gv_name(t) + "_eigenvalues" + ("_factorized" if factorized else "")
+    if w is None:
+        w = np.zeros(n, dtype=_real_dtype(a.dtype))
+    info = C.c_int(-1)
+    getattr(lib(), name)(uplo.encode()[0:1], n, _ptr(a), 1, 1, (C.c_int * 9)(*desca), _ptr(b), 1, 1, (C.c_int * 9)(*descb),
+                         _ptr(w), il, iu, C.byref(info))
+    return w, info.value
+
+
+def pxhegvd_partial_spectrum_by_value(uplo: str, a: np.ndarray, desca, b: np.ndarray, descb, z: np.ndarray, descz,
+                                      vl: float, vu: float, n: int, factorized: bool = False):
+    """dlaf_p{s,d}sygvd[_factorized]_partial_spectrum_by_value / dlaf_p{c,z}hegvd[_factorized]_partial_spectrum_by_value.
+    Returns (w, m, info); z is written in place."""
+    t = type_char(a.dtype)
+    name = _gv_name(t) + ("_factorized" if factorized else "") + "_partial_spectrum_by_value"
+    w = np.zeros(n, dtype=_real_dtype(a.dtype))
+    m, info = C.c_int(-1), C.c_int(-1)
+    getattr(lib(), name)(uplo.encode()[0:1], n, _ptr(a), 1, 1, (C.c_int * 9)(*desca), _ptr(b), 1, 1, (C.c_int * 9)(*descb),
+                         _ptr(w), _ptr(z), 1, 1, (C.c_int * 9)(*descz), float(vl), float(vu), C.byref(m), C.byref(info))
+    return w, m.value, info.value
 
 
 def partial_spectrum_plan(n: int, nb: int, npcol: int, mycol: int, z_jsrc: int, begin: int, end: int):

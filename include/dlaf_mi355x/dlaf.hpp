@@ -900,6 +900,137 @@ void hermitian_generalized_eigensolver(comm::CommunicatorGrid& grid, blas::Uplo 
     dlaf::internal::fail("hermitian_generalized_eigensolver");
 }
 
+// the eigenpairs with eigenvalues in (vl, vu] (LAPACK's range = 'V'): the index range is found from two Sturm counts of
+// the tridiagonal matrix and returned as {begin, end}; everything else as in the overloads above for that range.  An
+// eigenvalue within rounding of vl or vu may fall on either side.
+template <class R>
+struct EigenvaluesValue {
+  R vl, vu;
+};
+template <Backend B, class T>
+std::pair<SizeType, SizeType> hermitian_eigensolver(comm::CommunicatorGrid& grid, blas::Uplo uplo, Matrix<T, Device::CPU>& mat,
+                                                    std::vector<BaseType<T>>& eigenvalues,
+                                                    Matrix<T, Device::CPU>& eigenvectors,
+                                                    EigenvaluesValue<BaseType<T>> eigenvalues_value) {
+  static_assert(B == Backend::GPU, "this library has no CPU backend");
+  const char u = uplo == blas::Uplo::Lower ? 'L' : 'U';
+  eigenvalues.assign((size_t) mat.size().rows(), BaseType<T>(0));
+  BaseType<T> dummy{};
+  BaseType<T>* w = eigenvalues.empty() ? &dummy : eigenvalues.data();
+  const DLAF_descriptor da = internal::descriptor_of(mat), dz = internal::descriptor_of(eigenvectors);
+  const BaseType<T> vl = eigenvalues_value.vl, vu = eigenvalues_value.vu;
+  long ib = 0, ie = 0;
+  int r;
+  if constexpr (std::is_same_v<T, float>)
+    r = dlaf_symmetric_eigensolver_partial_spectrum_by_value_s(grid.context(), u, mat.ptr(), da, w, eigenvectors.ptr(), dz,
+                                                               vl, vu, &ib, &ie);
+  else if constexpr (std::is_same_v<T, double>)
+    r = dlaf_symmetric_eigensolver_partial_spectrum_by_value_d(grid.context(), u, mat.ptr(), da, w, eigenvectors.ptr(), dz,
+                                                               vl, vu, &ib, &ie);
+  else if constexpr (std::is_same_v<T, std::complex<float>>)
+    r = dlaf_hermitian_eigensolver_partial_spectrum_by_value_c(
+        grid.context(), u, reinterpret_cast<dlaf_complex_c*>(mat.ptr()), da, w,
+        reinterpret_cast<dlaf_complex_c*>(eigenvectors.ptr()), dz, vl, vu, &ib, &ie);
+  else
+    r = dlaf_hermitian_eigensolver_partial_spectrum_by_value_z(
+        grid.context(), u, reinterpret_cast<dlaf_complex_z*>(mat.ptr()), da, w,
+        reinterpret_cast<dlaf_complex_z*>(eigenvectors.ptr()), dz, vl, vu, &ib, &ie);
+  if (r != 0)
+    dlaf::internal::fail("hermitian_eigensolver");
+  return {(SizeType) ib, (SizeType) ie};
+}
+template <Backend B, class T>
+std::pair<SizeType, SizeType> hermitian_generalized_eigensolver(comm::CommunicatorGrid& grid, blas::Uplo uplo,
+                                                                Matrix<T, Device::CPU>& mat_a, Matrix<T, Device::CPU>& mat_b,
+                                                                std::vector<BaseType<T>>& eigenvalues,
+                                                                Matrix<T, Device::CPU>& eigenvectors,
+                                                                EigenvaluesValue<BaseType<T>> eigenvalues_value) {
+  static_assert(B == Backend::GPU, "this library has no CPU backend");
+  const char u = uplo == blas::Uplo::Lower ? 'L' : 'U';
+  eigenvalues.assign((size_t) mat_a.size().rows(), BaseType<T>(0));
+  BaseType<T> dummy{};
+  BaseType<T>* w = eigenvalues.empty() ? &dummy : eigenvalues.data();
+  const DLAF_descriptor da = internal::descriptor_of(mat_a), db = internal::descriptor_of(mat_b),
+                        dz = internal::descriptor_of(eigenvectors);
+  const BaseType<T> vl = eigenvalues_value.vl, vu = eigenvalues_value.vu;
+  long ib = 0, ie = 0;
+  int r;
+  if constexpr (std::is_same_v<T, float>)
+    r = dlaf_symmetric_generalized_eigensolver_partial_spectrum_by_value_s(grid.context(), u, mat_a.ptr(), da, mat_b.ptr(),
+                                                                           db, w, eigenvectors.ptr(), dz, vl, vu, &ib, &ie);
+  else if constexpr (std::is_same_v<T, double>)
+    r = dlaf_symmetric_generalized_eigensolver_partial_spectrum_by_value_d(grid.context(), u, mat_a.ptr(), da, mat_b.ptr(),
+                                                                           db, w, eigenvectors.ptr(), dz, vl, vu, &ib, &ie);
+  else if constexpr (std::is_same_v<T, std::complex<float>>)
+    r = dlaf_hermitian_generalized_eigensolver_partial_spectrum_by_value_c(
+        grid.context(), u, reinterpret_cast<dlaf_complex_c*>(mat_a.ptr()), da, reinterpret_cast<dlaf_complex_c*>(mat_b.ptr()),
+        db, w, reinterpret_cast<dlaf_complex_c*>(eigenvectors.ptr()), dz, vl, vu, &ib, &ie);
+  else
+    r = dlaf_hermitian_generalized_eigensolver_partial_spectrum_by_value_z(
+        grid.context(), u, reinterpret_cast<dlaf_complex_z*>(mat_a.ptr()), da, reinterpret_cast<dlaf_complex_z*>(mat_b.ptr()),
+        db, w, reinterpret_cast<dlaf_complex_z*>(eigenvectors.ptr()), dz, vl, vu, &ib, &ie);
+  if (r != 0)
+    dlaf::internal::fail("hermitian_generalized_eigensolver");
+  return {(SizeType) ib, (SizeType) ie};
+}
+
+// Eigenvalues only: reduction_to_band, band_to_tridiagonal and bisection on Sturm counts for the eigenvalues
+// [eigenvalues_index_begin, eigenvalues_index_end) (0-based, half-open; a negative end: all n).  No eigenvector matrix
+// exists anywhere.  `eigenvalues` is resized to n when its size differs (new entries zero) and only the entries of the
+// range are written; mat (mat_a) is read only; mat_b ends up holding its Cholesky factor.
+template <Backend B, class T>
+void hermitian_eigenvalues(comm::CommunicatorGrid& grid, blas::Uplo uplo, const Matrix<T, Device::CPU>& mat,
+                           std::vector<BaseType<T>>& eigenvalues, SizeType eigenvalues_index_begin = 0,
+                           SizeType eigenvalues_index_end = -1) {
+  static_assert(B == Backend::GPU, "this library has no CPU backend");
+  const char u = uplo == blas::Uplo::Lower ? 'L' : 'U';
+  const SizeType n = mat.size().rows();
+  if ((SizeType) eigenvalues.size() != n)
+    eigenvalues.assign((size_t) n, BaseType<T>(0));
+  BaseType<T> dummy{};
+  BaseType<T>* w = eigenvalues.empty() ? &dummy : eigenvalues.data();
+  const DLAF_descriptor da = internal::descriptor_of(mat);
+  const int64_t ib = eigenvalues_index_begin, ie = eigenvalues_index_end < 0 ? n : eigenvalues_index_end;
+  int r;
+  if constexpr (std::is_same_v<T, float>)
+    r = dlaf_symmetric_eigenvalues_s(grid.context(), u, mat.ptr(), da, w, ib, ie);
+  else if constexpr (std::is_same_v<T, double>)
+    r = dlaf_symmetric_eigenvalues_d(grid.context(), u, mat.ptr(), da, w, ib, ie);
+  else if constexpr (std::is_same_v<T, std::complex<float>>)
+    r = dlaf_hermitian_eigenvalues_c(grid.context(), u, reinterpret_cast<const dlaf_complex_c*>(mat.ptr()), da, w, ib, ie);
+  else
+    r = dlaf_hermitian_eigenvalues_z(grid.context(), u, reinterpret_cast<const dlaf_complex_z*>(mat.ptr()), da, w, ib, ie);
+  if (r != 0)
+    dlaf::internal::fail("hermitian_eigenvalues");
+}
+template <Backend B, class T>
+void hermitian_generalized_eigenvalues(comm::CommunicatorGrid& grid, blas::Uplo uplo, const Matrix<T, Device::CPU>& mat_a,
+                                       Matrix<T, Device::CPU>& mat_b, std::vector<BaseType<T>>& eigenvalues,
+                                       SizeType eigenvalues_index_begin = 0, SizeType eigenvalues_index_end = -1) {
+  static_assert(B == Backend::GPU, "this library has no CPU backend");
+  const char u = uplo == blas::Uplo::Lower ? 'L' : 'U';
+  const SizeType n = mat_a.size().rows();
+  if ((SizeType) eigenvalues.size() != n)
+    eigenvalues.assign((size_t) n, BaseType<T>(0));
+  BaseType<T> dummy{};
+  BaseType<T>* w = eigenvalues.empty() ? &dummy : eigenvalues.data();
+  const DLAF_descriptor da = internal::descriptor_of(mat_a), db = internal::descriptor_of(mat_b);
+  const int64_t ib = eigenvalues_index_begin, ie = eigenvalues_index_end < 0 ? n : eigenvalues_index_end;
+  int r;
+  if constexpr (std::is_same_v<T, float>)
+    r = dlaf_symmetric_generalized_eigenvalues_s(grid.context(), u, mat_a.ptr(), da, mat_b.ptr(), db, w, ib, ie);
+  else if constexpr (std::is_same_v<T, double>)
+    r = dlaf_symmetric_generalized_eigenvalues_d(grid.context(), u, mat_a.ptr(), da, mat_b.ptr(), db, w, ib, ie);
+  else if constexpr (std::is_same_v<T, std::complex<float>>)
+    r = dlaf_hermitian_generalized_eigenvalues_c(grid.context(), u, reinterpret_cast<const dlaf_complex_c*>(mat_a.ptr()), da,
+                                                 reinterpret_cast<dlaf_complex_c*>(mat_b.ptr()), db, w, ib, ie);
+  else
+    r = dlaf_hermitian_generalized_eigenvalues_z(grid.context(), u, reinterpret_cast<const dlaf_complex_z*>(mat_a.ptr()), da,
+                                                 reinterpret_cast<dlaf_complex_z*>(mat_b.ptr()), db, w, ib, ie);
+  if (r != 0)
+    dlaf::internal::fail("hermitian_generalized_eigenvalues");
+}
+
 // include/dlaf/init.h: the library needs no runtime arguments; initialize / finalize are idempotent
 inline void initialize(int argc = 0, const char** argv = nullptr) { dlaf_initialize(argc, argv, 0, nullptr); }
 inline void finalize() { dlaf_finalize(); }

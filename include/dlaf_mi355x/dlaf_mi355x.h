@@ -482,6 +482,177 @@ DLAF_EXTERN_C int dlaf_mi355x_tridiagonal_eigensolver_partial_spectrum_d(int n, 
 DLAF_EXTERN_C int dlaf_mi355x_partial_spectrum_plan(long n, int nb, int npcol, int mycol, int z_jsrc, long begin,
                                                     long end, long out[5]) DLAF_NOEXCEPT;
 
+/* ---- eigenvalues only, and a partial spectrum selected by value ------------------------- */
+/* Eigenvalues only.  reduction_to_band, band_to_tridiagonal, then bisection on Sturm counts of the tridiagonal matrix
+ * for the eigenvalues [eigenvalues_index_begin, eigenvalues_index_end) (0-based, half-open, ascending): no divide &
+ * conquer, no back-transformation, no eigenvector matrix, and per rank the n x n reflector matrix is the only n^2
+ * allocation.  w[begin, end) is written -- the same bits on every rank -- and nothing else of w.  a is read only (the
+ * uplo = 'L' triangle); the generalized entries leave the Cholesky factor in b as the eigensolver does (the
+ * _factorized ones take it there).  The p?syevd / p?heevd / p?sygvd / p?hegvd forms carry the 1-based inclusive il, iu
+ * of p?syevx in front of info (il = 1, iu = 0: the empty range).  Stages 3 and 4 of dlaf_mi355x_eigensolver_profile
+ * read 0 afterwards and stage 2 holds the bisection.
+ *
+ * By value, LAPACK's range = 'V'.  The eigenpairs with eigenvalues in (vl, vu]: after band_to_tridiagonal the driver
+ * counts the eigenvalues <= vl and <= vu (two Sturm counts of the computed tridiagonal matrix, agreed over the grid),
+ * returns [*begin, *end) = [count(vl), count(vu)) and goes on exactly as the *_partial_spectrum entry does for that
+ * index range: w receives all n eigenvalues, the global columns [*begin, *end) of z their eigenvectors, and nothing
+ * else of z is written.  vl >= vu gives the empty range at count(vl).  The boundary is that of the Sturm counts: an
+ * eigenvalue within rounding of vl or vu may fall on either side.  The ScaLAPACK-like forms return m = *end - *begin;
+ * the columns written start at the number of eigenvalues not above vl. */
+DLAF_EXTERN_C int dlaf_symmetric_eigenvalues_s(int dlaf_context, char uplo, const float* a, struct DLAF_descriptor
+    dlaf_desca, float* w, int64_t eigenvalues_index_begin, int64_t eigenvalues_index_end) DLAF_NOEXCEPT;
+DLAF_EXTERN_C int dlaf_symmetric_generalized_eigenvalues_s(int dlaf_context, char uplo, const float* a, struct
+    DLAF_descriptor dlaf_desca, float* b, struct DLAF_descriptor dlaf_descb, float* w, int64_t
+    eigenvalues_index_begin, int64_t eigenvalues_index_end) DLAF_NOEXCEPT;
+DLAF_EXTERN_C int dlaf_symmetric_generalized_eigenvalues_factorized_s(int dlaf_context, char uplo, const float* a,
+    struct DLAF_descriptor dlaf_desca, float* b, struct DLAF_descriptor dlaf_descb, float* w, int64_t
+    eigenvalues_index_begin, int64_t eigenvalues_index_end) DLAF_NOEXCEPT;
+DLAF_EXTERN_C int dlaf_symmetric_eigensolver_partial_spectrum_by_value_s(int dlaf_context, char uplo, float* a, struct
+    DLAF_descriptor dlaf_desca, float* w, float* z, struct DLAF_descriptor dlaf_descz, float vl, float vu, long*
+    begin, long* end) DLAF_NOEXCEPT;
+DLAF_EXTERN_C int dlaf_symmetric_generalized_eigensolver_partial_spectrum_by_value_s(int dlaf_context, char uplo,
+    float* a, struct DLAF_descriptor dlaf_desca, float* b, struct DLAF_descriptor dlaf_descb, float* w, float* z,
+    struct DLAF_descriptor dlaf_descz, float vl, float vu, long* begin, long* end) DLAF_NOEXCEPT;
+DLAF_EXTERN_C int dlaf_symmetric_generalized_eigensolver_factorized_partial_spectrum_by_value_s(int dlaf_context, char
+    uplo, float* a, struct DLAF_descriptor dlaf_desca, float* b, struct DLAF_descriptor dlaf_descb, float* w, float*
+    z, struct DLAF_descriptor dlaf_descz, float vl, float vu, long* begin, long* end) DLAF_NOEXCEPT;
+DLAF_EXTERN_C void dlaf_pssyevd_eigenvalues(char uplo, int n, const float* a, int ia, int ja, const int desca[9],
+    float* w, int64_t il, int64_t iu, int* info) DLAF_NOEXCEPT;
+DLAF_EXTERN_C void dlaf_pssygvd_eigenvalues(char uplo, int n, const float* a, int ia, int ja, const int desca[9],
+    float* b, int ib, int jb, const int descb[9], float* w, int64_t il, int64_t iu, int* info) DLAF_NOEXCEPT;
+DLAF_EXTERN_C void dlaf_pssygvd_eigenvalues_factorized(char uplo, int n, const float* a, int ia, int ja, const int
+    desca[9], float* b, int ib, int jb, const int descb[9], float* w, int64_t il, int64_t iu, int* info)
+    DLAF_NOEXCEPT;
+DLAF_EXTERN_C void dlaf_pssyevd_partial_spectrum_by_value(char uplo, int n, float* a, int ia, int ja, const int
+    desca[9], float* w, float* z, int iz, int jz, const int descz[9], float vl, float vu, int* m, int* info)
+    DLAF_NOEXCEPT;
+DLAF_EXTERN_C void dlaf_pssygvd_partial_spectrum_by_value(char uplo, int n, float* a, int ia, int ja, const int
+    desca[9], float* b, int ib, int jb, const int descb[9], float* w, float* z, int iz, int jz, const int descz[9],
+    float vl, float vu, int* m, int* info) DLAF_NOEXCEPT;
+DLAF_EXTERN_C void dlaf_pssygvd_factorized_partial_spectrum_by_value(char uplo, int n, float* a, int ia, int ja, const
+    int desca[9], float* b, int ib, int jb, const int descb[9], float* w, float* z, int iz, int jz, const int
+    descz[9], float vl, float vu, int* m, int* info) DLAF_NOEXCEPT;
+DLAF_EXTERN_C int dlaf_symmetric_eigenvalues_d(int dlaf_context, char uplo, const double* a, struct DLAF_descriptor
+    dlaf_desca, double* w, int64_t eigenvalues_index_begin, int64_t eigenvalues_index_end) DLAF_NOEXCEPT;
+DLAF_EXTERN_C int dlaf_symmetric_generalized_eigenvalues_d(int dlaf_context, char uplo, const double* a, struct
+    DLAF_descriptor dlaf_desca, double* b, struct DLAF_descriptor dlaf_descb, double* w, int64_t
+    eigenvalues_index_begin, int64_t eigenvalues_index_end) DLAF_NOEXCEPT;
+DLAF_EXTERN_C int dlaf_symmetric_generalized_eigenvalues_factorized_d(int dlaf_context, char uplo, const double* a,
+    struct DLAF_descriptor dlaf_desca, double* b, struct DLAF_descriptor dlaf_descb, double* w, int64_t
+    eigenvalues_index_begin, int64_t eigenvalues_index_end) DLAF_NOEXCEPT;
+DLAF_EXTERN_C int dlaf_symmetric_eigensolver_partial_spectrum_by_value_d(int dlaf_context, char uplo, double* a,
+    struct DLAF_descriptor dlaf_desca, double* w, double* z, struct DLAF_descriptor dlaf_descz, double vl, double vu,
+    long* begin, long* end) DLAF_NOEXCEPT;
+DLAF_EXTERN_C int dlaf_symmetric_generalized_eigensolver_partial_spectrum_by_value_d(int dlaf_context, char uplo,
+    double* a, struct DLAF_descriptor dlaf_desca, double* b, struct DLAF_descriptor dlaf_descb, double* w, double* z,
+    struct DLAF_descriptor dlaf_descz, double vl, double vu, long* begin, long* end) DLAF_NOEXCEPT;
+DLAF_EXTERN_C int dlaf_symmetric_generalized_eigensolver_factorized_partial_spectrum_by_value_d(int dlaf_context, char
+    uplo, double* a, struct DLAF_descriptor dlaf_desca, double* b, struct DLAF_descriptor dlaf_descb, double* w,
+    double* z, struct DLAF_descriptor dlaf_descz, double vl, double vu, long* begin, long* end) DLAF_NOEXCEPT;
+DLAF_EXTERN_C void dlaf_pdsyevd_eigenvalues(char uplo, int n, const double* a, int ia, int ja, const int desca[9],
+    double* w, int64_t il, int64_t iu, int* info) DLAF_NOEXCEPT;
+DLAF_EXTERN_C void dlaf_pdsygvd_eigenvalues(char uplo, int n, const double* a, int ia, int ja, const int desca[9],
+    double* b, int ib, int jb, const int descb[9], double* w, int64_t il, int64_t iu, int* info) DLAF_NOEXCEPT;
+DLAF_EXTERN_C void dlaf_pdsygvd_eigenvalues_factorized(char uplo, int n, const double* a, int ia, int ja, const int
+    desca[9], double* b, int ib, int jb, const int descb[9], double* w, int64_t il, int64_t iu, int* info)
+    DLAF_NOEXCEPT;
+DLAF_EXTERN_C void dlaf_pdsyevd_partial_spectrum_by_value(char uplo, int n, double* a, int ia, int ja, const int
+    desca[9], double* w, double* z, int iz, int jz, const int descz[9], double vl, double vu, int* m, int* info)
+    DLAF_NOEXCEPT;
+DLAF_EXTERN_C void dlaf_pdsygvd_partial_spectrum_by_value(char uplo, int n, double* a, int ia, int ja, const int
+    desca[9], double* b, int ib, int jb, const int descb[9], double* w, double* z, int iz, int jz, const int descz[9],
+    double vl, double vu, int* m, int* info) DLAF_NOEXCEPT;
+DLAF_EXTERN_C void dlaf_pdsygvd_factorized_partial_spectrum_by_value(char uplo, int n, double* a, int ia, int ja,
+    const int desca[9], double* b, int ib, int jb, const int descb[9], double* w, double* z, int iz, int jz, const int
+    descz[9], double vl, double vu, int* m, int* info) DLAF_NOEXCEPT;
+DLAF_EXTERN_C int dlaf_hermitian_eigenvalues_c(int dlaf_context, char uplo, const dlaf_complex_c* a, struct
+    DLAF_descriptor dlaf_desca, float* w, int64_t eigenvalues_index_begin, int64_t eigenvalues_index_end)
+    DLAF_NOEXCEPT;
+DLAF_EXTERN_C int dlaf_hermitian_generalized_eigenvalues_c(int dlaf_context, char uplo, const dlaf_complex_c* a,
+    struct DLAF_descriptor dlaf_desca, dlaf_complex_c* b, struct DLAF_descriptor dlaf_descb, float* w, int64_t
+    eigenvalues_index_begin, int64_t eigenvalues_index_end) DLAF_NOEXCEPT;
+DLAF_EXTERN_C int dlaf_hermitian_generalized_eigenvalues_factorized_c(int dlaf_context, char uplo, const
+    dlaf_complex_c* a, struct DLAF_descriptor dlaf_desca, dlaf_complex_c* b, struct DLAF_descriptor dlaf_descb, float*
+    w, int64_t eigenvalues_index_begin, int64_t eigenvalues_index_end) DLAF_NOEXCEPT;
+DLAF_EXTERN_C int dlaf_hermitian_eigensolver_partial_spectrum_by_value_c(int dlaf_context, char uplo, dlaf_complex_c*
+    a, struct DLAF_descriptor dlaf_desca, float* w, dlaf_complex_c* z, struct DLAF_descriptor dlaf_descz, float vl,
+    float vu, long* begin, long* end) DLAF_NOEXCEPT;
+DLAF_EXTERN_C int dlaf_hermitian_generalized_eigensolver_partial_spectrum_by_value_c(int dlaf_context, char uplo,
+    dlaf_complex_c* a, struct DLAF_descriptor dlaf_desca, dlaf_complex_c* b, struct DLAF_descriptor dlaf_descb, float*
+    w, dlaf_complex_c* z, struct DLAF_descriptor dlaf_descz, float vl, float vu, long* begin, long* end)
+    DLAF_NOEXCEPT;
+DLAF_EXTERN_C int dlaf_hermitian_generalized_eigensolver_factorized_partial_spectrum_by_value_c(int dlaf_context, char
+    uplo, dlaf_complex_c* a, struct DLAF_descriptor dlaf_desca, dlaf_complex_c* b, struct DLAF_descriptor dlaf_descb,
+    float* w, dlaf_complex_c* z, struct DLAF_descriptor dlaf_descz, float vl, float vu, long* begin, long* end)
+    DLAF_NOEXCEPT;
+DLAF_EXTERN_C void dlaf_pcheevd_eigenvalues(char uplo, int n, const dlaf_complex_c* a, int ia, int ja, const int
+    desca[9], float* w, int64_t il, int64_t iu, int* info) DLAF_NOEXCEPT;
+DLAF_EXTERN_C void dlaf_pchegvd_eigenvalues(char uplo, int n, const dlaf_complex_c* a, int ia, int ja, const int
+    desca[9], dlaf_complex_c* b, int ib, int jb, const int descb[9], float* w, int64_t il, int64_t iu, int* info)
+    DLAF_NOEXCEPT;
+DLAF_EXTERN_C void dlaf_pchegvd_eigenvalues_factorized(char uplo, int n, const dlaf_complex_c* a, int ia, int ja,
+    const int desca[9], dlaf_complex_c* b, int ib, int jb, const int descb[9], float* w, int64_t il, int64_t iu, int*
+    info) DLAF_NOEXCEPT;
+DLAF_EXTERN_C void dlaf_pcheevd_partial_spectrum_by_value(char uplo, int n, dlaf_complex_c* a, int ia, int ja, const
+    int desca[9], float* w, dlaf_complex_c* z, int iz, int jz, const int descz[9], float vl, float vu, int* m, int*
+    info) DLAF_NOEXCEPT;
+DLAF_EXTERN_C void dlaf_pchegvd_partial_spectrum_by_value(char uplo, int n, dlaf_complex_c* a, int ia, int ja, const
+    int desca[9], dlaf_complex_c* b, int ib, int jb, const int descb[9], float* w, dlaf_complex_c* z, int iz, int jz,
+    const int descz[9], float vl, float vu, int* m, int* info) DLAF_NOEXCEPT;
+DLAF_EXTERN_C void dlaf_pchegvd_factorized_partial_spectrum_by_value(char uplo, int n, dlaf_complex_c* a, int ia, int
+    ja, const int desca[9], dlaf_complex_c* b, int ib, int jb, const int descb[9], float* w, dlaf_complex_c* z, int
+    iz, int jz, const int descz[9], float vl, float vu, int* m, int* info) DLAF_NOEXCEPT;
+DLAF_EXTERN_C int dlaf_hermitian_eigenvalues_z(int dlaf_context, char uplo, const dlaf_complex_z* a, struct
+    DLAF_descriptor dlaf_desca, double* w, int64_t eigenvalues_index_begin, int64_t eigenvalues_index_end)
+    DLAF_NOEXCEPT;
+DLAF_EXTERN_C int dlaf_hermitian_generalized_eigenvalues_z(int dlaf_context, char uplo, const dlaf_complex_z* a,
+    struct DLAF_descriptor dlaf_desca, dlaf_complex_z* b, struct DLAF_descriptor dlaf_descb, double* w, int64_t
+    eigenvalues_index_begin, int64_t eigenvalues_index_end) DLAF_NOEXCEPT;
+DLAF_EXTERN_C int dlaf_hermitian_generalized_eigenvalues_factorized_z(int dlaf_context, char uplo, const
+    dlaf_complex_z* a, struct DLAF_descriptor dlaf_desca, dlaf_complex_z* b, struct DLAF_descriptor dlaf_descb,
+    double* w, int64_t eigenvalues_index_begin, int64_t eigenvalues_index_end) DLAF_NOEXCEPT;
+DLAF_EXTERN_C int dlaf_hermitian_eigensolver_partial_spectrum_by_value_z(int dlaf_context, char uplo, dlaf_complex_z*
+    a, struct DLAF_descriptor dlaf_desca, double* w, dlaf_complex_z* z, struct DLAF_descriptor dlaf_descz, double vl,
+    double vu, long* begin, long* end) DLAF_NOEXCEPT;
+DLAF_EXTERN_C int dlaf_hermitian_generalized_eigensolver_partial_spectrum_by_value_z(int dlaf_context, char uplo,
+    dlaf_complex_z* a, struct DLAF_descriptor dlaf_desca, dlaf_complex_z* b, struct DLAF_descriptor dlaf_descb,
+    double* w, dlaf_complex_z* z, struct DLAF_descriptor dlaf_descz, double vl, double vu, long* begin, long* end)
+    DLAF_NOEXCEPT;
+DLAF_EXTERN_C int dlaf_hermitian_generalized_eigensolver_factorized_partial_spectrum_by_value_z(int dlaf_context, char
+    uplo, dlaf_complex_z* a, struct DLAF_descriptor dlaf_desca, dlaf_complex_z* b, struct DLAF_descriptor dlaf_descb,
+    double* w, dlaf_complex_z* z, struct DLAF_descriptor dlaf_descz, double vl, double vu, long* begin, long* end)
+    DLAF_NOEXCEPT;
+DLAF_EXTERN_C void dlaf_pzheevd_eigenvalues(char uplo, int n, const dlaf_complex_z* a, int ia, int ja, const int
+    desca[9], double* w, int64_t il, int64_t iu, int* info) DLAF_NOEXCEPT;
+DLAF_EXTERN_C void dlaf_pzhegvd_eigenvalues(char uplo, int n, const dlaf_complex_z* a, int ia, int ja, const int
+    desca[9], dlaf_complex_z* b, int ib, int jb, const int descb[9], double* w, int64_t il, int64_t iu, int* info)
+    DLAF_NOEXCEPT;
+DLAF_EXTERN_C void dlaf_pzhegvd_eigenvalues_factorized(char uplo, int n, const dlaf_complex_z* a, int ia, int ja,
+    const int desca[9], dlaf_complex_z* b, int ib, int jb, const int descb[9], double* w, int64_t il, int64_t iu, int*
+    info) DLAF_NOEXCEPT;
+DLAF_EXTERN_C void dlaf_pzheevd_partial_spectrum_by_value(char uplo, int n, dlaf_complex_z* a, int ia, int ja, const
+    int desca[9], double* w, dlaf_complex_z* z, int iz, int jz, const int descz[9], double vl, double vu, int* m, int*
+    info) DLAF_NOEXCEPT;
+DLAF_EXTERN_C void dlaf_pzhegvd_partial_spectrum_by_value(char uplo, int n, dlaf_complex_z* a, int ia, int ja, const
+    int desca[9], dlaf_complex_z* b, int ib, int jb, const int descb[9], double* w, dlaf_complex_z* z, int iz, int jz,
+    const int descz[9], double vl, double vu, int* m, int* info) DLAF_NOEXCEPT;
+DLAF_EXTERN_C void dlaf_pzhegvd_factorized_partial_spectrum_by_value(char uplo, int n, dlaf_complex_z* a, int ia, int
+    ja, const int desca[9], dlaf_complex_z* b, int ib, int jb, const int descb[9], double* w, dlaf_complex_z* z, int
+    iz, int jz, const int descz[9], double vl, double vu, int* m, int* info) DLAF_NOEXCEPT;
+/* the tridiagonal level, local: d (n), e (n - 1).  tridiagonal_eigenvalues: w[begin, end) = the eigenvalues [begin,
+ * end) by bisection (nothing else of w is written; NaN for every wanted entry when d or e holds a NaN or an Inf).
+ * tridiagonal_sturm_count: counts[i] = the number of eigenvalues <= shifts[i], dstebz's convention (-1 for every shift
+ * when d or e is not finite).  sturm_layout: out = {pairs staged through LDS at a time, threads per workgroup}. */
+DLAF_EXTERN_C int dlaf_mi355x_tridiagonal_eigenvalues_s(int n, const float* d, const float* e, float* w, long begin,
+    long end) DLAF_NOEXCEPT;
+DLAF_EXTERN_C int dlaf_mi355x_tridiagonal_sturm_count_s(int n, const float* d, const float* e, long nshifts, const
+    float* shifts, long* counts) DLAF_NOEXCEPT;
+DLAF_EXTERN_C int dlaf_mi355x_tridiagonal_eigenvalues_d(int n, const double* d, const double* e, double* w, long
+    begin, long end) DLAF_NOEXCEPT;
+DLAF_EXTERN_C int dlaf_mi355x_tridiagonal_sturm_count_d(int n, const double* d, const double* e, long nshifts, const
+    double* shifts, long* counts) DLAF_NOEXCEPT;
+DLAF_EXTERN_C int dlaf_mi355x_sturm_layout(int out[2]) DLAF_NOEXCEPT;
+
 /* Device-resident operands: a general m x n matrix in HBM (tile layout; square blocks) as the right-hand side,
  * a dlaf_mi355x_matrix_t (the uplo triangle of a resident matrix, e.g. the factor dlaf_mi355x_cholesky_* left there)
  * as the triangular matrix.  b is overwritten by the solution; nothing crosses PCIe.  potrs_device = the two solves of

@@ -35,7 +35,8 @@ class UpdateDesc(C.Structure):
                 [(n, C.c_int) for n in ("il0", "il1", "jl0", "jl1", "nb", "K", "pr", "ri", "pc", "ci", "nt", "last_rows",
                                         "rect", "nt_c", "last_cols", "K1", "her2k", "info", "role")] +
                 [("max_blocks", C.c_long), ("excl_rounds", C.c_int),
-                 ("persistent", C.c_long), ("exclusive", C.c_long), ("bulk_slots", C.c_long)])
+                 ("persistent", C.c_long), ("exclusive", C.c_long), ("bulk_slots", C.c_long),
+                 ("second_below", C.c_int)])
 
 
 class TrsmDesc(C.Structure):

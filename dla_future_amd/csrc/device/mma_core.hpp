@@ -3,7 +3,10 @@
 // A, B column-major in global memory; slabs of BK columns are staged global -> registers -> LDS
 // (double-buffered, one barrier per slab) and consumed as 16x16x4 MFMA fragments.
 #pragma once
+#include <type_traits>
+
 #include "common.hpp"
+#include "glds_addr.hpp"
 
 namespace dlaf_mi355x {
 
@@ -361,39 +364,28 @@ __device__ __forceinline__ void stage_glds(const T* __restrict__ A, long lda, co
   }
 }
 
-// The IDX-th of the LPS instructions stage_glds issues for this wave (real types), alone: lets the pipelined
-// loop spread them over the MFMA stream.
-template <class Cfg, class T, int IDX>
-__device__ __forceinline__ void stage_glds_one(const T* __restrict__ A, long lda, const T* __restrict__ B, long ldb,
-                                               int k0, typename Cfg::R* __restrict__ buf, int wave, int lane) {
-  static_assert(!Cfg::CXI, "real types");
-  constexpr int NA = Cfg::PIECES_A / Cfg::NWAVES, NB = Cfg::PIECES_B / Cfg::NWAVES;
-  constexpr int PER = 16 / (int) sizeof(T), EPP = Cfg::EPP;
-  // address = (wave-uniform base: scalar registers) + (a per-lane byte offset that does not depend on the slab):
-  // a piece is EPP consecutive elements of the image [k][ROWS] starting at element e0 (uniform); lane l moves the
-  // PER elements at e0 + l PER, i.e. row (e0 + l PER) % ROWS of column (e0 + l PER) / ROWS.  With ROWS | EPP or
-  // EPP | ROWS the lane part is (l PER) % ROWS + ((l PER) / ROWS) ld and the uniform part (e0 % ROWS) + (k0 + e0 /
-  // ROWS) ld.  Written per lane -- "(e % ROWS) + (k0 + e / ROWS) * ld" -- every load costs a 64-bit multiply-add
-  // per lane in the middle of the MFMA stream (A/B: profiles/r02_update_kernel_scalar_addressing_ab_timing.txt).
-  auto at = [](const T* base, unsigned byte_off) {
-    return reinterpret_cast<const T*>(reinterpret_cast<const char*>(base) + byte_off);
-  };
-  if constexpr (IDX < NA) {
-    static_assert(EPP % Cfg::BM == 0 || Cfg::BM % EPP == 0, "pieces and columns nest");
-    const int e0 = (wave * NA + IDX) * EPP;
-    const unsigned loff = (unsigned) sizeof(T) * (unsigned) ((lane * PER) % Cfg::BM + ((lane * PER) / Cfg::BM) * (int) lda);
-    const T* ga = A + (e0 % Cfg::BM) + (long) (k0 + e0 / Cfg::BM) * lda;
-    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*) at(ga, loff),
-                                     (__attribute__((address_space(3))) void*) (buf + e0), 16, 0, 0);
-  }
-  else if constexpr (IDX < NA + NB) {
-    static_assert(EPP % Cfg::BN == 0 || Cfg::BN % EPP == 0, "pieces and columns nest");
-    const int e0 = (wave * NB + (IDX - NA)) * EPP;
-    const unsigned loff = (unsigned) sizeof(T) * (unsigned) ((lane * PER) % Cfg::BN + ((lane * PER) / Cfg::BN) * (int) ldb);
-    const T* gb = B + (e0 % Cfg::BN) + (long) (k0 + e0 / Cfg::BN) * ldb;
-    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*) at(gb, loff),
-                                     (__attribute__((address_space(3))) void*) (buf + Cfg::A_ELEMS + e0), 16, 0, 0);
-  }
+// One direct-to-LDS load of the pipelined loop (real types): 64 lanes x 16 bytes, from `piece` (wave-uniform: a scalar
+// register pair) plus the lane's 32-bit byte offset, into the 1 KiB at `dst`.  The address arithmetic is GldsPieces
+// (glds_addr.hpp).  The empty statement makes the offset opaque where the load stands, so that its zero-extension is
+// formed beside the load instead of once, as a 64-bit value, in front of the K loop: hipcc selects the instruction's
+// (scalar base + 32-bit VGPR offset) form only when it finds the extension in the load's own block, and otherwise
+// spends a 64-bit vector add and two more registers on every load (profiles/kloop_slab_bases_isa.txt).  The offset
+// is passed by reference so that the statement rewrites the caller's register in place: no copy per load.
+template <class R>
+__device__ __forceinline__ void glds_load_piece(const char* piece, unsigned& lane_off, R* dst) {
+  asm volatile("" : "+v"(lane_off));
+  __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*) (piece + lane_off),
+                                   (__attribute__((address_space(3))) void*) dst, 16, 0, 0);
+}
+
+// The group of MFMAs (hook point p of mma_slab) in front of which the pipelined loop issues the I-th load of a slab.
+// Rotated slab: hook point 0 stands in the slab's exposed head -- between the slab barrier and the first MFMA, behind
+// the four first-step fragment reads -- so the loads go out in front of groups 1 .. LPS instead of 0 .. LPS - 1.
+// Measured (profiles/kloop_slab_bases_ab.txt): one-block-per-workgroup launches +0.65 %, persistent ones unchanged; a
+// spread that also avoids the groups followed by two fragment re-reads (1 2 4 5 6 8 9 10) measured the same.
+template <class Cfg>
+__device__ __host__ constexpr int glds_hook_of(int i) {
+  return kRotatedSlab<Cfg> ? i + 1 : i;
 }
 
 // acc += A(mrows x K) * B(ncols x K)^H for one BM x BN block.  lds: 2 * BUF_ELEMS of R.
@@ -450,45 +442,94 @@ __device__ __forceinline__ void gemm_nt_block(const T* __restrict__ A, long lda,
     // iteration.  Measured (profiles/r02_update_kernel_kloop_ab_timing.txt, fp64): persistent launches 65.7 -> 67.0
     // TFlop/s at K = 1024, 66.2 -> 67.4 at K = 2048, 60.4 -> 61.5 at nb = 512.  The last ST-1 iterations load nothing.
     constexpr bool SPLIT = !Cfg::CXI && LPS <= (Cfg::BK / 4) * Cfg::TN && LPS <= 16;
-    for (int kt = 0; kt < nk; ++kt) {
-      R* cur = lds + cur_i * Cfg::BUF_ELEMS;
-      const bool load = UTAIL || (kt + ST - 1 < nk);
-      // (one copy of the MFMA stream: `load` only guards the single instructions, a scalar branch each)
-      int sn = s0 + min(kt + ST - 1, nk - 1);
-      sn = sn >= nk ? sn - nk : sn;
-      const int kn = sn * Cfg::BK;
-      const T* An = kn < K1 ? A : A2;
-      const T* Bn = kn < K1 ? B : B2;
-      R* nbuf = lds + nxt_i * Cfg::BUF_ELEMS;
-      if constexpr (SPLIT) {
-        mma_slab<Cfg, NEG>(cur, cur + Cfg::A_ELEMS, acc, wm, wn, lane, [&](int p) {
-          // (p is a compile-time constant after unrolling: the chain folds to the one instruction of group p)
-#define DLAF_GLDS_AT(I)                                                                     \
-  if (p == I) {                                                                           \
-    if constexpr (I < LPS)                                                                \
-      if (load)                                                                           \
-        stage_glds_one<Cfg, T, (I < LPS ? I : 0)>(An, lda, Bn, ldb, kn, nbuf, wave, lane); \
-  }
-          DLAF_GLDS_AT(0) DLAF_GLDS_AT(1) DLAF_GLDS_AT(2) DLAF_GLDS_AT(3) DLAF_GLDS_AT(4) DLAF_GLDS_AT(5)
-          DLAF_GLDS_AT(6) DLAF_GLDS_AT(7) DLAF_GLDS_AT(8) DLAF_GLDS_AT(9) DLAF_GLDS_AT(10) DLAF_GLDS_AT(11)
-          DLAF_GLDS_AT(12) DLAF_GLDS_AT(13) DLAF_GLDS_AT(14) DLAF_GLDS_AT(15)
-#undef DLAF_GLDS_AT
-        });
-      }
-      else {
+    if constexpr (!SPLIT) {
+      // (complex types, or more loads than MFMA groups: the loads of a slab as one block at the head of the iteration)
+      for (int kt = 0; kt < nk; ++kt) {
+        R* cur = lds + cur_i * Cfg::BUF_ELEMS;
+        const bool load = UTAIL || (kt + ST - 1 < nk);
+        int sn = s0 + min(kt + ST - 1, nk - 1);
+        sn = sn >= nk ? sn - nk : sn;
+        const int kn = sn * Cfg::BK;
+        const T* An = kn < K1 ? A : A2;
+        const T* Bn = kn < K1 ? B : B2;
+        R* nbuf = lds + nxt_i * Cfg::BUF_ELEMS;
         if (load)
           stage_glds<Cfg, T>(An, lda, Bn, ldb, kn, nbuf, wave, lane);
         mma_slab<Cfg, NEG>(cur, cur + Cfg::A_ELEMS, acc, wm, wn, lane);
+        // slab kt+1 landed?  still in flight afterwards: the loads of slabs kt+2 .. kt+ST-1 (none in the tail)
+        if (load)
+          __builtin_amdgcn_s_waitcnt(0x0070 | ((LPS * (ST - 2)) & 0xF) | ((((LPS * (ST - 2)) >> 4) & 0x3) << 14));
+        else
+          asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        __builtin_amdgcn_s_barrier();
+        cur_i = (cur_i + 1 == ST) ? 0 : cur_i + 1;
+        nxt_i = (nxt_i + 1 == ST) ? 0 : nxt_i + 1;
       }
-      // slab kt+1 landed?  still in flight afterwards: the loads of slabs kt+2 .. kt+ST-1 (none in the tail)
-      if (load)
-        __builtin_amdgcn_s_waitcnt(0x0070 | ((LPS * (ST - 2)) & 0xF) | ((((LPS * (ST - 2)) >> 4) & 0x3) << 14));
-      else
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-      __builtin_amdgcn_s_barrier();
-      cur_i = (cur_i + 1 == ST) ? 0 : cur_i + 1;
-      nxt_i = (nxt_i + 1 == ST) ? 0 : nxt_i + 1;
+    }
+    else {
+      constexpr int NA = Cfg::PIECES_A / Cfg::NWAVES, NB = Cfg::PIECES_B / Cfg::NWAVES;
+      using PA = GldsPieces<Cfg::BM, Cfg::EPP, NA, (int) sizeof(T)>;
+      using PB = GldsPieces<Cfg::BN, Cfg::EPP, NB, (int) sizeof(T)>;
+      // the one 32-bit part of a load's address: it depends on neither the slab nor the piece
+      unsigned lane_a = PA::lane_bytes(lane, lda), lane_b = PB::lane_bytes(lane, ldb);
+      // one iteration: slab kt is consumed, slab kt+ST-1 loaded.  `load` is a constant true (no branch around any load)
+      // or a flag (one copy of the MFMA stream: it only guards the single instructions, a scalar branch each)
+      auto iteration = [&](int kt, auto load) {
+        R* cur = lds + cur_i * Cfg::BUF_ELEMS;
+        R* nbuf = lds + nxt_i * Cfg::BUF_ELEMS;
+        {
+          // Addresses once per slab and operand: the wave's first piece, then a 64-bit scalar add from piece to piece
+          // (GldsPieces).  Recomputed from kt in every slab, so the wrap past nk, the segment switch at K1 and UTAIL's
+          // clamp cannot go stale.  The arithmetic stands at the first load's hook point, not at the loop top: there
+          // it sat between the slab barrier and the first-step fragment reads.
+          const char* pa = nullptr;
+          const char* pb = nullptr;
+          mma_slab<Cfg, NEG>(cur, cur + Cfg::A_ELEMS, acc, wm, wn, lane, [&](int p) {
+            if (p == glds_hook_of<Cfg>(0)) {
+              const int kn = glds_slab_ahead(kt, ST - 1, nk, s0) * Cfg::BK;
+              pa = reinterpret_cast<const char*>((kn < K1 ? A : A2) + PA::base_elems(wave, kn, lda));
+              pb = reinterpret_cast<const char*>((kn < K1 ? B : B2) + PB::base_elems(wave, kn, ldb));
+            }
+            // (p is a compile-time constant after unrolling: the chain folds to the one instruction of group p)
+#define DLAF_GLDS_AT(I)                                                                              \
+  if constexpr (I < LPS)                                                                             \
+    if (p == glds_hook_of<Cfg>(I)) {                                                                 \
+      if constexpr (I < NA) {                                                                        \
+        if (load)                                                                                    \
+          glds_load_piece(pa, lane_a, nbuf + (wave * NA + I) * Cfg::EPP);                            \
+        if constexpr (I + 1 < NA)                                                                    \
+          pa += PA::step_bytes(I + 1, lda);                                                          \
+      }                                                                                              \
+      else {                                                                                         \
+        if (load)                                                                                    \
+          glds_load_piece(pb, lane_b, nbuf + Cfg::A_ELEMS + (wave * NB + (I - NA)) * Cfg::EPP);      \
+        if constexpr (I + 1 < LPS)                                                                   \
+          pb += PB::step_bytes(I + 1 - NA, ldb);                                                     \
+      }                                                                                              \
+    }
+            DLAF_GLDS_AT(0) DLAF_GLDS_AT(1) DLAF_GLDS_AT(2) DLAF_GLDS_AT(3) DLAF_GLDS_AT(4) DLAF_GLDS_AT(5)
+            DLAF_GLDS_AT(6) DLAF_GLDS_AT(7) DLAF_GLDS_AT(8) DLAF_GLDS_AT(9) DLAF_GLDS_AT(10) DLAF_GLDS_AT(11)
+            DLAF_GLDS_AT(12) DLAF_GLDS_AT(13) DLAF_GLDS_AT(14) DLAF_GLDS_AT(15)
+#undef DLAF_GLDS_AT
+          });
+        }
+        // slab kt+1 landed?  still in flight afterwards: the loads of slabs kt+2 .. kt+ST-1 (none in the tail)
+        if (load)
+          __builtin_amdgcn_s_waitcnt(0x0070 | ((LPS * (ST - 2)) & 0xF) | ((((LPS * (ST - 2)) >> 4) & 0x3) << 14));
+        else
+          asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        __builtin_amdgcn_s_barrier();
+        cur_i = (cur_i + 1 == ST) ? 0 : cur_i + 1;
+        nxt_i = (nxt_i + 1 == ST) ? 0 : nxt_i + 1;
+      };
+      for (int kt = 0; kt < nk; ++kt) {
+        if constexpr (UTAIL)
+          iteration(kt, std::true_type{});
+        else
+          iteration(kt, kt + ST - 1 < nk);
+      }
     }
     if constexpr (UTAIL) {
       // the re-fetched slabs of the last ST-1 iterations: nobody reads them, but they must have landed (in every

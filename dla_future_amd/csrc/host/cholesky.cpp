@@ -213,10 +213,14 @@ constexpr long kSidecarSlots = 32;
 
 // Rate table of the pairs order's two placement decisions (in-situ measurements on MI355X):
 // the bulk update, the panel TRSM per free slot beside it, the tile POTRF per (64-column block)^2 beside it.
+// r_bulk of real fp64 was 66e12 while its bulk launch ran at 67.4 TFlop/s in situ; it runs at 71.2 since the K loop's
+// fragment rotation and scalar slab bases, and the rate moved with it (N=65536 nb=1024: U1 goes to s_main one pair
+// earlier, k = 30, and the reservation of pair k = 50 grows from 128 to 192 slots; profiles/kloop_slab_bases_ab.txt).
+// The complex kernel has not changed and keeps its rate.
 template <class T>
 struct PairRates {
   static constexpr bool dbl = sizeof(real_t<T>) == 8;
-  static constexpr double r_bulk = dbl ? 66e12 : 118e12;
+  static constexpr double r_bulk = dbl ? (TypeInfo<T>::is_complex ? 66e12 : 70e12) : 118e12;
   static constexpr double r_trsm_slot = (dbl ? 5e12 : 8e12) / 32.0;
   static constexpr double t_potrf_blk2 = 11.3e-6 * (TypeInfo<T>::is_complex ? 2.0 : 1.0);  // 2.9 ms per real 1024-tile
 };

@@ -35,6 +35,16 @@ struct Operand {
     if (elems > 0)
       DLAF_HIP_CHECK(hipMemcpyAsync(p, host, (size_t) elems * sizeof(T), hipMemcpyHostToDevice, s));
   }
+  // this operand and, behind it in the SAME allocation (16 elements apart at least in alignment), `hi`: p < hi.p
+  void put_below(const void* host, long elems, long off, Operand& hi, const void* hi_host, long hi_elems, long hi_off,
+                 hipStream_t s) {
+    const long span = (off + elems + 15) / 16 * 16;
+    buf.alloc((size_t) (span + hi_off + hi_elems));
+    p = buf.p + off;
+    hi.p = buf.p + span + hi_off;
+    DLAF_HIP_CHECK(hipMemcpyAsync(p, host, (size_t) elems * sizeof(T), hipMemcpyHostToDevice, s));
+    DLAF_HIP_CHECK(hipMemcpyAsync(hi.p, hi_host, (size_t) hi_elems * sizeof(T), hipMemcpyHostToDevice, s));
+  }
 };
 
 // Every element the launch may touch lies inside its operand?  Walks the tiles the kernel's contract names
@@ -120,11 +130,17 @@ int update_direct(dlaf_mi355x_update_desc& d, void* c, const void* a, const void
   hipStream_t s = nullptr;
   Operand<T> dc, da, db, da2, db2;
   dc.put(c, d.c_elems, d.c_off, s);
-  da.put(a, d.a_elems, d.a_off, s);
-  db.put(b, d.b_elems, d.b_off, s);
-  if (d.K1 > 0) {
-    da2.put(a2, d.a2_elems, d.a2_off, s);
-    db2.put(b2, d.b2_elems, d.b2_off, s);
+  if (d.K1 > 0 && d.second_below) {
+    da2.put_below(a2, d.a2_elems, d.a2_off, da, a, d.a_elems, d.a_off, s);
+    db2.put_below(b2, d.b2_elems, d.b2_off, db, b, d.b_elems, d.b_off, s);
+  }
+  else {
+    da.put(a, d.a_elems, d.a_off, s);
+    db.put(b, d.b_elems, d.b_off, s);
+    if (d.K1 > 0) {
+      da2.put(a2, d.a2_elems, d.a2_off, s);
+      db2.put(b2, d.b2_elems, d.b2_off, s);
+    }
   }
   DevBuf<int> info(1);
   DevBuf<unsigned> counters(16);

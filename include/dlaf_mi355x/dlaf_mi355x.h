@@ -750,6 +750,9 @@ struct dlaf_mi355x_update_desc {
   /* out */
   long persistent, exclusive; /* launches that took the persistent / exclusive form (0 or 1 per launch) */
   long bulk_slots;            /* this GPU's workgroup slots for the type */
+  /* in */
+  int second_below; /* K1 > 0: a2 / b2 share one device allocation with a / b and lie in front of them, so the second
+                     * panel's address is below the first's whatever the allocator does (0: allocations of their own) */
 };
 /* c (c_elems elements) is updated in place.  c_again != NULL: the launch is repeated on a fresh copy of the original
  * c with the SAME 16 counter words, not zeroed by the caller (counters_are_zero = false), into c_again.

@@ -27,17 +27,12 @@
 
 #include "../device/band_api.hpp"
 #include "../device/tridiag_api.hpp"
+#include "bt_wavefronts.hpp"
 #include "eigensolver.hpp"
 
 namespace dlaf_mi355x {
 
 namespace {
-template <class T>
-T* ealloc(size_t elems) {
-  T* p = nullptr;
-  DLAF_HIP_CHECK(pool_malloc(reinterpret_cast<void**>(&p), std::max<size_t>(elems, 1) * sizeof(T)));
-  return p;
-}
 double g_stage_ms[5] = {0, 0, 0, 0, 0};
 
 struct StageTimer {
@@ -58,6 +53,48 @@ struct StageTimer {
     return ms;
   }
 };
+
+// an on/off switch of the environment; every caller keeps what it read (static const): a switch is read once
+bool env_flag(const char* name, bool dflt) {
+  const char* e = std::getenv(name);
+  return e ? std::atoi(e) != 0 : dflt;
+}
+
+// DLAF_MI355X_EIG_DEBUG=1: a checksum of every stage's output (diagnosis: each stage is deterministic).  Who prints:
+// the words in front of the name and the width of the name's column.
+struct DebugWho {
+  char words[48];
+  int width;
+};
+const DebugWho kBtDebug = {"bt debug", 22};
+DebugWho eig_debug(const Grid* g) {
+  DebugWho w;
+  std::snprintf(w.words, sizeof(w.words), "eig debug rank (%d,%d)", g->myrow, g->mycol);
+  w.width = 24;
+  return w;
+}
+bool debug_on() {
+  static const bool on = env_flag("DLAF_MI355X_EIG_DEBUG", false);
+  return on;
+}
+// FNV-1a over the 64-bit words of a device range (the last one padded with zeros), continued from acc
+constexpr unsigned long long kFnvSeed = 1469598103934665603ull;
+unsigned long long fnv1a_device(unsigned long long acc, const void* dev, size_t bytes) {
+  std::vector<unsigned long long> h((bytes + 7) / 8, 0ull);
+  DLAF_HIP_CHECK(hipMemcpy(h.data(), dev, bytes, hipMemcpyDeviceToHost));
+  for (unsigned long long x : h)
+    acc = (acc ^ x) * 1099511628211ull;
+  return acc;
+}
+void debug_print(const DebugWho& who, const char* what, unsigned long long acc) {
+  std::fprintf(stderr, "[dlaf_mi355x] %s %-*s %016llx\n", who.words, who.width, what, acc);
+}
+void debug_checksum(const DebugWho& who, hipStream_t s, const char* what, const void* dev, size_t bytes) {
+  if (!debug_on())
+    return;
+  DLAF_HIP_CHECK(hipStreamSynchronize(s));
+  debug_print(who, what, fnv1a_device(kFnvSeed, dev, bytes));
+}
 }  // namespace
 
 // E of the back-transformation band <- tridiagonal: leading dimension a multiple of 16 bytes, element 1 (not 0) on a
@@ -104,26 +141,25 @@ int band_to_tridiag_device(DeviceMatrix<T>& A, int band, real_t<T>* d, real_t<T>
   if (n == 0)
     return 0;
   StageTimer timer(s);
-  T* bandm = ealloc<T>((size_t) (n + 2) * 2 * band);
+  PoolScope ws;
+  T* bandm = ws.get<T>((size_t) (n + 2) * 2 * band);
   // (the two columns of slack behind the matrix are read, never used: they must hold numbers)
   DLAF_HIP_CHECK(hipMemsetAsync(bandm + (size_t) n * 2 * band, 0, (size_t) 2 * 2 * band * sizeof(T), s));
-  unsigned* sync = ealloc<unsigned>(b2t_sync_words(n));
+  unsigned* sync = ws.get<unsigned>(b2t_sync_words(n));
   launch_band_extract(A.tiles, A.ltr, A.nb, A.rows.P, A.rows.shift(), A.cols.P, A.cols.shift(), n, band, bandm, s);
   if (dist)
     tr->allreduce_sum(bandm, (size_t) n * 2 * band, TypeInfo<T>::tag, 'A', s);
   DLAF_HIP_CHECK(hipMemset2DAsync(v, (size_t) ldv * sizeof(T), 0, (size_t) n * sizeof(T), (size_t) n, s));
   // the bulge chase works on 2^-k A, max(|Re|, |Im|) in [1, 2): its unscaled sums of squares neither overflow nor
   // underflow whatever the scale of A (every rank holds the same band after the all-reduce and takes the same k)
-  unsigned long long* mx = ealloc<unsigned long long>(1);
+  unsigned long long* mx = ws.get<unsigned long long>(1);
   launch_band_normalise(bandm, n, band, mx, s);
   launch_band_to_tridiag(bandm, n, band, v, ldv, sync, A.info, s);
   launch_tridiag_extract(bandm, n, band, mx, d, e, s);
   int h_info = 0;
   DLAF_HIP_CHECK(hipMemcpyAsync(&h_info, A.info, sizeof(int), hipMemcpyDeviceToHost, s));
   g_stage_ms[1] = timer.stop();
-  DLAF_HIP_CHECK(pool_free(bandm));
-  DLAF_HIP_CHECK(pool_free(sync));
-  DLAF_HIP_CHECK(pool_free(mx));
+  ws.release();
   if (h_info == kInfoSchedulingFailure)
     fatal("[dlaf_mi355x] band_to_tridiagonal: a sweep gave up waiting for its predecessor (the workgroup that owns it "
           "made no progress)\n");
@@ -137,9 +173,10 @@ int band_to_tridiag_host(Grid* g, const T* a, long lda, long n, int nb, int isrc
   DeviceMatrix<T> A;
   A.create(g, 'L', n, nb, isrc, jsrc);
   A.upload(a, lda);
-  R* dd = ealloc<R>((size_t) n);
-  R* de = ealloc<R>((size_t) n);
-  T* dv = ealloc<T>((size_t) n * n);
+  PoolScope ws;
+  R* dd = ws.get<R>((size_t) n);
+  R* de = ws.get<R>((size_t) n);
+  T* dv = ws.get<T>((size_t) n * n);
   const int r = band_to_tridiag_device(A, band, dd, de, dv, n);
   if (n > 0) {
     DLAF_HIP_CHECK(hipMemcpy(d, dd, (size_t) n * sizeof(R), hipMemcpyDeviceToHost));
@@ -147,31 +184,37 @@ int band_to_tridiag_host(Grid* g, const T* a, long lda, long n, int nb, int isrc
     DLAF_HIP_CHECK(hipMemcpy2D(v, (size_t) ldv * sizeof(T), dv, (size_t) n * sizeof(T), (size_t) n * sizeof(T), (size_t) n,
                                hipMemcpyDeviceToHost));
   }
-  DLAF_HIP_CHECK(pool_free(dd));
-  DLAF_HIP_CHECK(pool_free(de));
-  DLAF_HIP_CHECK(pool_free(dv));
   return r;
 }
 
 // ------------------------------------------------------------------------------------------------ band <- tridiagonal
+namespace {
+// what the steps of bt_band_to_tridiagonal share.  Block (jb, ib) -- sweep group jb, rows 1 + ib b -- lives in slot
+// jb nblk + ib of vx (V, 2b x b; fused: V^T), wx (W = V T), sm (S = V^H V), tm (T) and taus; it exists for jb <= ib only.
 template <class T>
-int bt_band_to_tridiag_device(long n, int band, const T* v, long ldv, T* e, long lde, long ncols, hipStream_t s) {
-  const int b = band;
-  const long nsweeps = TypeInfo<T>::is_complex ? n - 1 : n - 2;
-  if (nsweeps <= 0 || ncols <= 0)
-    return 0;
-  if (ncols > 0x7fffffffL || n > 0x7fffffffL)
-    fatal("[dlaf_mi355x] bt_band_to_tridiagonal: sizes beyond 32-bit tile counts\n");
-  const long nblk = (n + b - 1) / b;
-  const size_t vblk = (size_t) 2 * b * b;
-  const size_t nb2 = (size_t) nblk * nblk;
-  // DLAF_MI355X_BT_VERBOSE=1: wall time of the phases of this stage (synchronising: diagnosis only)
-  static const bool verbose = [] {
-    const char* e = std::getenv("DLAF_MI355X_BT_VERBOSE");
-    return e && std::atoi(e) != 0;
-  }();
-  auto t_last = std::chrono::steady_clock::now();
-  auto phase = [&](const char* what) {
+struct BtBlocks {
+  long n;
+  int b;
+  long nblk;    // block rows and columns of the block grid
+  size_t vblk;  // elements of a block of vx / wx
+  bool fused;   // fp64, band 128: the fused kernel (kernels_bt.hip) on E transposed
+  const T* v;
+  long ldv;
+  T* e;
+  long lde, ncols;
+  T *vx, *wx, *sm, *tm, *taus;
+  double* et;  // fused: E^T (ncols x n, ldet)
+  long ldet;
+  T* w2;  // strided batch: W2 = V^H E of a batch
+  hipStream_t s;
+};
+
+// DLAF_MI355X_BT_VERBOSE=1: wall time of the phases of this stage (synchronising: diagnosis only)
+struct BtPhases {
+  hipStream_t s;
+  std::chrono::steady_clock::time_point t_last = std::chrono::steady_clock::now();
+  void operator()(const char* what) {
+    static const bool verbose = env_flag("DLAF_MI355X_BT_VERBOSE", false);
     if (!verbose)
       return;
     DLAF_HIP_CHECK(hipStreamSynchronize(s));
@@ -179,227 +222,216 @@ int bt_band_to_tridiag_device(long n, int band, const T* v, long ldv, T* e, long
     std::fprintf(stderr, "[dlaf_mi355x] bt_band_to_tridiagonal: %-28s %8.2f ms\n", what,
                  std::chrono::duration<double, std::milli>(now - t_last).count());
     t_last = now;
-  };
-  static const bool dbg = [] {
-    const char* e_ = std::getenv("DLAF_MI355X_EIG_DEBUG");
-    return e_ && std::atoi(e_) != 0;
-  }();
-  auto checksum = [&](const char* what, const void* dev, size_t bytes) {
-    if (!dbg)
-      return;
-    DLAF_HIP_CHECK(hipStreamSynchronize(s));
-    std::vector<unsigned long long> h((bytes + 7) / 8, 0ull);
-    DLAF_HIP_CHECK(hipMemcpy(h.data(), dev, bytes, hipMemcpyDeviceToHost));
-    unsigned long long acc = 1469598103934665603ull;
-    for (unsigned long long x : h)
-      acc = (acc ^ x) * 1099511628211ull;
-    std::fprintf(stderr, "[dlaf_mi355x] bt debug %-22s %016llx\n", what, acc);
-  };
-  T* vx = ealloc<T>(nb2 * vblk);
-  T* wx = ealloc<T>(nb2 * vblk);
-  T* sm = ealloc<T>(nb2 * (size_t) b * b);
-  T* tm = ealloc<T>(nb2 * (size_t) b * b);
-  T* taus = ealloc<T>(nb2 * (size_t) b);
-  // (no memsets: the expansion writes every block (jb <= ib) in full, zeros included, and nothing reads the others)
-  phase("allocations");
-  // fp64, band 128: the fused kernel (kernels_bt.hip) applies a block to a column strip in one go, on E transposed, and
-  // streams V^T: the expansion writes that image directly (S = V^H V and W = V T take it as their operand);
-  // DLAF_MI355X_BT_FUSED=0: the two strided-batch products per wavefront (every type, every band)
-  static const bool fused_on = [] {
-    const char* e = std::getenv("DLAF_MI355X_BT_FUSED");
-    return e ? std::atoi(e) != 0 : true;
-  }();
-  const bool fused = fused_on && bt_fused_supported(b, sizeof(T), TypeInfo<T>::is_complex);
-  launch_b2t_expand(v, ldv, n, b, vx, taus, s, fused);
-  const T one = make_host_el<T>(1.0), zero = make_host_el<T>(0.0), mone = make_host_el<T>(-1.0);
-  // Block (jb, ib) -- sweep group jb, rows 1 + ib b -- exists for jb <= ib only (ib = jb + step): the strided-batch
-  // launches below take one row of the block grid at a time, the blocks ib = jb .. nblk - 1 of sweep group jb, instead
-  // of all nblk^2 slots (half of which hold zeros: 28 ms of T factors alone at n = 20480)
-  const long jb_end = std::min<long>(nblk, (nsweeps - 1) / b + 1);
+  }
+};
+
+// The reflector blocks: the compact reflectors expanded to well-formed V (and their taus), then per row of the block
+// grid -- the blocks ib = jb .. nblk - 1 of sweep group jb, instead of all nblk^2 slots (half of which hold zeros: 28 ms
+// of T factors alone at n = 20480) -- S = V^H V, the T factors and W = V T as three strided-batch launches.
+// (no memsets: the expansion writes every block (jb <= ib) in full, zeros included, and nothing reads the others)
+template <class T>
+void bt_prepare_blocks(const BtBlocks<T>& k, long jb_end) {
+  const int b = k.b;
+  const bool fused = k.fused;
+  const size_t vblk = k.vblk, tblk = (size_t) b * b;
+  hipStream_t s = k.s;
+  // (fused: the expansion writes V^T directly; S = V^H V and W = V T take it as their operand)
+  launch_b2t_expand(k.v, k.ldv, k.n, b, k.vx, k.taus, s, fused);
+  const T one = make_host_el<T>(1.0), zero = make_host_el<T>(0.0);
   for (long jb = 0; jb < jb_end; ++jb) {
-    const size_t q0 = (size_t) jb * nblk + (size_t) jb;
-    const int cnt = (int) (nblk - jb);
+    const size_t q0 = (size_t) jb * k.nblk + (size_t) jb;
+    const int cnt = (int) (k.nblk - jb);
     {
       GemmArgs<T> g;  // S = V^H V  (fused: vx holds V^T, S = V^T (V^T)^H for the real types of that path)
       g.M = b;
       g.N = b;
       g.K = 2 * b;
-      g.a = vx + q0 * vblk;
+      g.a = k.vx + q0 * vblk;
       g.lda = fused ? b : 2 * b;
       g.opa = fused ? 'N' : 'C';
-      g.b = vx + q0 * vblk;
+      g.b = k.vx + q0 * vblk;
       g.ldb = fused ? b : 2 * b;
       g.opb = fused ? 'C' : 'N';
-      g.c = sm + q0 * (size_t) b * b;
+      g.c = k.sm + q0 * tblk;
       g.ldc = b;
       g.alpha = one;
       g.beta = zero;
       g.batch = cnt;
       g.sa = (long) vblk;
       g.sb = (long) vblk;
-      g.sc = (long) b * b;
+      g.sc = (long) tblk;
       launch_gemm(g, s);
     }
-    launch_tfactor(sm + q0 * (size_t) b * b, (long) b, taus + q0 * (size_t) b, b, tm + q0 * (size_t) b * b, (long) b, s, cnt,
-                   (long) b * b, (long) b, (long) b * b);
+    launch_tfactor(k.sm + q0 * tblk, (long) b, k.taus + q0 * (size_t) b, b, k.tm + q0 * tblk, (long) b, s, cnt, (long) tblk,
+                   (long) b, (long) tblk);
     {
       GemmArgs<T> g;  // W = V T
       g.M = 2 * b;
       g.N = b;
       g.K = b;
-      g.a = vx + q0 * vblk;
+      g.a = k.vx + q0 * vblk;
       g.lda = fused ? b : 2 * b;
       g.opa = fused ? 'C' : 'N';
-      g.b = tm + q0 * (size_t) b * b;
+      g.b = k.tm + q0 * tblk;
       g.ldb = b;
       g.opb = 'N';
-      g.c = wx + q0 * vblk;
+      g.c = k.wx + q0 * vblk;
       g.ldc = 2 * b;
       g.alpha = one;
       g.beta = zero;
       g.batch = cnt;
       g.sa = (long) vblk;
-      g.sb = (long) b * b;
+      g.sb = (long) tblk;
       g.sc = (long) vblk;
       launch_gemm(g, s);
     }
   }
-  if (dbg) {
-    // existing blocks only (the others are never written): block row jb, blocks jb .. nblk - 1
-    DLAF_HIP_CHECK(hipStreamSynchronize(s));
-    for (const char* nm : {"vx", "wx", "tm"}) {
-      unsigned long long acc = 1469598103934665603ull;
-      for (long jb = 0; jb < jb_end; ++jb) {
-        const size_t q0 = (size_t) jb * nblk + (size_t) jb, cnt = (size_t) (nblk - jb);
-        const bool is_t = nm[0] == 't';
-        const size_t per = is_t ? (size_t) b * b : vblk;
-        const T* base = (nm[0] == 'v' ? vx : (nm[0] == 'w' ? wx : tm)) + q0 * per;
-        std::vector<unsigned long long> h(cnt * per * sizeof(T) / 8);
-        DLAF_HIP_CHECK(hipMemcpy(h.data(), base, cnt * per * sizeof(T), hipMemcpyDeviceToHost));
-        for (unsigned long long x : h)
-          acc = (acc ^ x) * 1099511628211ull;
-      }
-      std::fprintf(stderr, "[dlaf_mi355x] bt debug %-22s %016llx\n", nm, acc);
-    }
+  if (!debug_on())
+    return;
+  // existing blocks only (the others are never written): block row jb, blocks jb .. nblk - 1
+  DLAF_HIP_CHECK(hipStreamSynchronize(s));
+  const struct {
+    const char* name;
+    const T* base;
+    size_t per;
+  } sets[3] = {{"vx", k.vx, vblk}, {"wx", k.wx, vblk}, {"tm", k.tm, tblk}};
+  for (const auto& set : sets) {
+    unsigned long long acc = kFnvSeed;
+    for (long jb = 0; jb < jb_end; ++jb)
+      acc = fnv1a_device(acc, set.base + ((size_t) jb * k.nblk + (size_t) jb) * set.per,
+                         (size_t) (k.nblk - jb) * set.per * sizeof(T));
+    debug_print(kBtDebug, set.name, acc);
   }
-  phase("expand, S, T factors, W");
-  double* et = nullptr;
-  const long ldet = (ncols + 63) / 64 * 64;
+}
+
+// fused: E -> E^T in a workspace of ws (the kernel streams V^T and works on columns of E^T)
+template <class T>
+void bt_transpose_in(BtBlocks<T>& k, PoolScope& ws) {
+  k.et = nullptr;
+  k.ldet = (k.ncols + 63) / 64 * 64;
   if constexpr (std::is_same_v<T, double>) {
-    if (fused) {
-      et = ealloc<double>((size_t) ldet * n);
-      launch_bt_transpose(e, lde, n, ncols, et, ldet, s);
+    if (k.fused) {
+      k.et = ws.get<double>((size_t) k.ldet * k.n);
+      launch_bt_transpose(k.e, k.lde, k.n, k.ncols, k.et, k.ldet, k.s);
     }
   }
-  if (et)
-    checksum("et after transpose", et, (size_t) ldet * n * sizeof(double));
-  phase("transposition");
-  // steps of sweep group jb (its first sweep has the most)
-  auto steps_of = [&](long jb) -> long {
-    const long sw = jb * b;
-    if (sw >= nsweeps)
-      return 0;
-    if (TypeInfo<T>::is_complex && sw == n - 2)
-      return 1;
-    return (n - sw - 2 + b - 1) / b;
-  };
-  const long jb_last = (nsweeps - 1) / b;
-  const long max_batch = nblk / 2 + 2;
-  T* w2 = ealloc<T>((size_t) max_batch * b * (size_t) ncols);
-  // wavefront t = step - jb, from the last sweep group's first step to the first group's last step
-  const long t_lo = -jb_last, t_hi = steps_of(0) - 1;
-  for (long t = t_lo; t <= t_hi; ++t) {
-    const long jb0 = std::max<long>(0, -t);
-    // blocks (jb, st = t + jb), jb = jb0 ...: valid while st < steps_of(jb)
-    long cnt = 0, full = 0;
-    for (long jb = jb0; jb <= jb_last; ++jb) {
-      const long st = t + jb;
-      if (st >= steps_of(jb))
-        break;
-      const long r0 = 1 + (jb + st) * b;
-      if (r0 >= n)
-        break;
-      ++cnt;
-      if (r0 + 2 * b <= n)
-        ++full;
-    }
-    if (cnt == 0)
+  if (k.et)
+    debug_checksum(kBtDebug, k.s, "et after transpose", k.et, (size_t) k.ldet * k.n * sizeof(double));
+}
+
+// The batches of the wavefront schedule (bt_wavefronts.hpp), each one fused launch or W2 = V^H E and E -= W W2 as two
+// strided-batch products: from block to block of a batch nblk + 2 slots of the block grid and 2 b rows of E.
+template <class T>
+void bt_apply_wavefronts(const BtBlocks<T>& k, const BtSchedule& sc) {
+  const int b = k.b;
+  const long ncols = k.ncols, max_batch = sc.max_batch();
+  const long blk_stride = (long) ((k.nblk + 2) * (long) k.vblk);
+  const T one = make_host_el<T>(1.0), zero = make_host_el<T>(0.0), mone = make_host_el<T>(-1.0);
+  hipStream_t s = k.s;
+  for (const BtBatch& w : bt_wavefront_batches(k.n, b, TypeInfo<T>::is_complex)) {
+    if (w.count > max_batch)
+      fatal("[dlaf_mi355x] bt_band_to_tridiagonal: wavefront of %ld blocks exceeds the workspace (%ld)\n", w.count,
+            max_batch);
+    const size_t blk = (size_t) (w.jb * k.nblk + w.ib) * k.vblk;
+    if (k.fused) {
+      if constexpr (std::is_same_v<T, double>)
+        launch_bt_apply(k.vx + blk, k.wx + blk, blk_stride, (int) w.count, k.et, k.ldet, ncols, w.r0, (int) w.rows, s);
       continue;
-    if (cnt > max_batch)
-      fatal("[dlaf_mi355x] bt_band_to_tridiagonal: wavefront of %ld blocks exceeds the workspace (%ld)\n", cnt, max_batch);
-    // the blocks of a wavefront: block index (jb, ib = 2 jb + t) -> stride nblk + 2 blocks; rows 1 + (2 jb + t) b ->
-    // stride 2 b rows of E
-    auto run = [&](long first, long count, long rows) {
-      if (count <= 0)
-        return;
-      const long jb = jb0 + first;
-      const long ib = 2 * jb + t;
-      const long blk = jb * nblk + ib;
-      const long r0 = 1 + ib * b;
-      if (fused) {
-        if constexpr (std::is_same_v<T, double>)
-          launch_bt_apply(vx + (size_t) blk * vblk, wx + (size_t) blk * vblk, (long) ((nblk + 2) * (long) vblk), (int) count, et,
-                          ldet, ncols, r0, (int) rows, s);
-        return;
-      }
-      GemmArgs<T> g;  // W2 = V^H E
-      g.M = b;
-      g.N = (int) ncols;
-      g.K = (int) rows;
-      g.a = vx + (size_t) blk * vblk;
-      g.lda = 2 * b;
-      g.opa = 'C';
-      g.b = e + r0;
-      g.ldb = lde;
-      g.opb = 'N';
-      g.c = w2;
-      g.ldc = b;
-      g.alpha = one;
-      g.beta = zero;
-      g.batch = (int) count;
-      g.sa = (long) ((nblk + 2) * (long) vblk);
-      g.sb = 2L * b;
-      g.sc = (long) b * ncols;
-      launch_gemm(g, s);
-      GemmArgs<T> u;  // E -= W W2
-      u.M = (int) rows;
-      u.N = (int) ncols;
-      u.K = b;
-      u.a = wx + (size_t) blk * vblk;
-      u.lda = 2 * b;
-      u.opa = 'N';
-      u.b = w2;
-      u.ldb = b;
-      u.opb = 'N';
-      u.c = e + r0;
-      u.ldc = lde;
-      u.alpha = mone;
-      u.beta = one;
-      u.batch = (int) count;
-      u.sa = (long) ((nblk + 2) * (long) vblk);
-      u.sb = (long) b * ncols;
-      u.sc = 2L * b;
-      launch_gemm(u, s);
-    };
-    run(0, full, 2L * b);
-    for (long q = full; q < cnt; ++q) {
-      const long ib = 2 * (jb0 + q) + t;
-      run(q, 1, n - (1 + ib * b));
     }
+    GemmArgs<T> g;  // W2 = V^H E
+    g.M = b;
+    g.N = (int) ncols;
+    g.K = (int) w.rows;
+    g.a = k.vx + blk;
+    g.lda = 2 * b;
+    g.opa = 'C';
+    g.b = k.e + w.r0;
+    g.ldb = k.lde;
+    g.opb = 'N';
+    g.c = k.w2;
+    g.ldc = b;
+    g.alpha = one;
+    g.beta = zero;
+    g.batch = (int) w.count;
+    g.sa = blk_stride;
+    g.sb = 2L * b;
+    g.sc = (long) b * ncols;
+    launch_gemm(g, s);
+    GemmArgs<T> u;  // E -= W W2
+    u.M = (int) w.rows;
+    u.N = (int) ncols;
+    u.K = b;
+    u.a = k.wx + blk;
+    u.lda = 2 * b;
+    u.opa = 'N';
+    u.b = k.w2;
+    u.ldb = b;
+    u.opb = 'N';
+    u.c = k.e + w.r0;
+    u.ldc = k.lde;
+    u.alpha = mone;
+    u.beta = one;
+    u.batch = (int) w.count;
+    u.sa = blk_stride;
+    u.sb = (long) b * ncols;
+    u.sc = 2L * b;
+    launch_gemm(u, s);
   }
-  if (et)
-    checksum("et after wavefronts", et, (size_t) ldet * n * sizeof(double));
-  phase("wavefronts");
+  if (k.et)
+    debug_checksum(kBtDebug, s, "et after wavefronts", k.et, (size_t) k.ldet * k.n * sizeof(double));
+}
+
+template <class T>
+void bt_transpose_back(const BtBlocks<T>& k) {
   if constexpr (std::is_same_v<T, double>) {
-    if (fused)
-      launch_bt_transpose(et, ldet, ncols, n, e, lde, s);
+    if (k.fused)
+      launch_bt_transpose(k.et, k.ldet, k.ncols, k.n, k.e, k.lde, k.s);
   }
+}
+}  // namespace
+
+template <class T>
+int bt_band_to_tridiag_device(long n, int band, const T* v, long ldv, T* e, long lde, long ncols, hipStream_t s) {
+  const BtSchedule sc(n, band, TypeInfo<T>::is_complex);
+  if (sc.nsweeps <= 0 || ncols <= 0)
+    return 0;
+  if (ncols > 0x7fffffffL || n > 0x7fffffffL)
+    fatal("[dlaf_mi355x] bt_band_to_tridiagonal: sizes beyond 32-bit tile counts\n");
+  BtPhases phase{s};
+  BtBlocks<T> k{};
+  k.n = n;
+  k.b = band;
+  k.nblk = sc.nblk;
+  k.vblk = (size_t) 2 * band * band;
+  k.v = v;
+  k.ldv = ldv;
+  k.e = e;
+  k.lde = lde;
+  k.ncols = ncols;
+  k.s = s;
+  const size_t nb2 = (size_t) k.nblk * k.nblk;
+  PoolScope ws, ws_et;  // (E^T has a scope of its own: it goes back behind W2, which is taken after it)
+  k.vx = ws.get<T>(nb2 * k.vblk);
+  k.wx = ws.get<T>(nb2 * k.vblk);
+  k.sm = ws.get<T>(nb2 * (size_t) band * band);
+  k.tm = ws.get<T>(nb2 * (size_t) band * band);
+  k.taus = ws.get<T>(nb2 * (size_t) band);
+  phase("allocations");
+  // DLAF_MI355X_BT_FUSED=0: the two strided-batch products per batch (every type, every band)
+  static const bool fused_on = env_flag("DLAF_MI355X_BT_FUSED", true);
+  k.fused = fused_on && bt_fused_supported(band, sizeof(T), TypeInfo<T>::is_complex);
+  bt_prepare_blocks(k, std::min<long>(k.nblk, sc.jb_last() + 1));
+  phase("expand, S, T factors, W");
+  bt_transpose_in(k, ws_et);
+  phase("transposition");
+  k.w2 = ws.get<T>((size_t) sc.max_batch() * band * (size_t) ncols);
+  bt_apply_wavefronts(k, sc);
+  phase("wavefronts");
+  bt_transpose_back(k);
   DLAF_HIP_CHECK(hipStreamSynchronize(s));
   phase("transposition back");
-  for (T* q : {vx, wx, sm, tm, taus, w2})
-    DLAF_HIP_CHECK(pool_free(q));
-  if (et)
-    DLAF_HIP_CHECK(pool_free(et));
+  ws.release();
+  ws_et.release();
   phase("frees");
   return 0;
 }
@@ -410,12 +442,12 @@ int bt_band_to_tridiag_host(long n, int band, const T* v, long ldv, T* e, long l
     return 0;
   hipStream_t s;
   DLAF_HIP_CHECK(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
-  T* dv = ealloc<T>((size_t) n * n);
+  PoolScope ws;
+  T* dv = ws.get<T>((size_t) n * n);
   // row 1 of E on a 16-byte boundary, even leading dimension: the row blocks the reflector blocks act on start at the
   // rows 1 + i b, and the k-contiguous operand loader of the general product wants them aligned
   const long ldd = bt_aligned_ld(n);
-  T* de_alloc = ealloc<T>((size_t) ldd * ncols + 4);
-  T* de = bt_aligned_base(de_alloc);
+  T* de = bt_aligned_base(ws.get<T>((size_t) ldd * ncols + 4));
   DLAF_HIP_CHECK(hipMemcpy2DAsync(dv, (size_t) n * sizeof(T), v, (size_t) ldv * sizeof(T), (size_t) n * sizeof(T), (size_t) n,
                                   hipMemcpyHostToDevice, s));
   DLAF_HIP_CHECK(hipMemcpy2DAsync(de, (size_t) ldd * sizeof(T), e, (size_t) lde * sizeof(T), (size_t) n * sizeof(T),
@@ -426,8 +458,7 @@ int bt_band_to_tridiag_host(long n, int band, const T* v, long ldv, T* e, long l
   DLAF_HIP_CHECK(hipMemcpy2DAsync(e, (size_t) lde * sizeof(T), de, (size_t) ldd * sizeof(T), (size_t) n * sizeof(T),
                                   (size_t) ncols, hipMemcpyDeviceToHost, s));
   DLAF_HIP_CHECK(hipStreamSynchronize(s));
-  DLAF_HIP_CHECK(pool_free(dv));
-  DLAF_HIP_CHECK(pool_free(de_alloc));
+  ws.release();
   DLAF_HIP_CHECK(hipStreamDestroy(s));
   return r;
 }
@@ -471,23 +502,6 @@ int agreed(Grid* g, int info) {
   return info;
 }
 
-// DLAF_MI355X_EIG_DEBUG=1: a checksum of every stage's output per rank (diagnosis: each stage is deterministic)
-void debug_checksum(Grid* g, hipStream_t s, const char* what, const void* dev, size_t bytes) {
-  static const bool dbg = [] {
-    const char* e_ = std::getenv("DLAF_MI355X_EIG_DEBUG");
-    return e_ && std::atoi(e_) != 0;
-  }();
-  if (!dbg)
-    return;
-  DLAF_HIP_CHECK(hipStreamSynchronize(s));
-  std::vector<unsigned long long> h((bytes + 7) / 8, 0ull);
-  DLAF_HIP_CHECK(hipMemcpy(h.data(), dev, bytes, hipMemcpyDeviceToHost));
-  unsigned long long acc = 1469598103934665603ull;
-  for (unsigned long long x : h)
-    acc = (acc ^ x) * 1099511628211ull;
-  std::fprintf(stderr, "[dlaf_mi355x] eig debug rank (%d,%d) %-24s %016llx\n", g->myrow, g->mycol, what, acc);
-}
-
 // stages 2 and 3 run replicated: say what they need instead of failing inside an allocation
 void check_replicated_memory(long n, double need) {
   size_t free_b = 0, total_b = 0;
@@ -519,32 +533,26 @@ struct Reduced {
   real_t<T>* d = nullptr;
   real_t<T>* e = nullptr;
   T* v = nullptr;
-  Reduced() = default;
-  Reduced(const Reduced&) = delete;
-  Reduced& operator=(const Reduced&) = delete;
+  PoolScope tridiag, reflectors;  // d, e | v: an eigenvalues-only call gives the reflectors back early
   void release() {
-    for (real_t<T>* q : {d, e})
-      if (q)
-        DLAF_HIP_CHECK(pool_free(q));
-    if (v)
-      DLAF_HIP_CHECK(pool_free(v));
-    d = e = nullptr;
-    v = nullptr;
+    tridiag.release();
+    reflectors.release();
   }
   ~Reduced() { release(); }
 };
 
-// stages 1-2: reduction_to_band, band_to_tridiagonal (n > 0)
+// stages 1-2: reduction_to_band, band_to_tridiagonal (n > 0); holds nothing when it fails
 template <class T>
 int eigensolver_reductions(DeviceMatrix<T>& A, Reduced<T>& r) {
   using R = real_t<T>;
   const long n = A.n;
   Grid* g = A.grid;
   hipStream_t s = A.s_high;
+  const DebugWho who = eig_debug(g);
   r.band = get_band_size(A.nb);  // eigensolver/impl.h:41
   r.taus.assign((size_t) std::max<long>(0, n - r.band - 1) + 1, T{});
   int info = agreed(g, reduction_to_band_device(A, r.band, r.taus.data()));
-  debug_checksum(g, s, "A after red2band", A.tiles, (size_t) A.ltr * A.ltc * A.tile_elems * sizeof(T));
+  debug_checksum(who, s, "A after red2band", A.tiles, (size_t) A.ltr * A.ltc * A.tile_elems * sizeof(T));
   {
     double ms = 0, fl = 0;
     red2band_last_profile(&ms, &fl);
@@ -552,17 +560,17 @@ int eigensolver_reductions(DeviceMatrix<T>& A, Reduced<T>& r) {
   }
   if (info != 0)
     return info;
-  r.d = ealloc<R>((size_t) n);
-  r.e = ealloc<R>((size_t) n);
-  r.v = ealloc<T>((size_t) n * n);
+  r.d = r.tridiag.template get<R>((size_t) n);
+  r.e = r.tridiag.template get<R>((size_t) n);
+  r.v = r.reflectors.template get<T>((size_t) n * n);
   info = agreed(g, band_to_tridiag_device(A, r.band, r.d, r.e, r.v, n));
   if (info != 0) {
     r.release();
     return info;
   }
-  debug_checksum(g, s, "d", r.d, (size_t) n * sizeof(R));
-  debug_checksum(g, s, "e", r.e, (size_t) (n - 1) * sizeof(R));
-  debug_checksum(g, s, "v", r.v, (size_t) n * n * sizeof(T));
+  debug_checksum(who, s, "d", r.d, (size_t) n * sizeof(R));
+  debug_checksum(who, s, "e", r.e, (size_t) (n - 1) * sizeof(R));
+  debug_checksum(who, s, "v", r.v, (size_t) n * n * sizeof(T));
   return 0;
 }
 
@@ -579,47 +587,45 @@ int eigensolver_back(DeviceMatrix<T>& A, Reduced<T>& r, real_t<T>* w_host, Gener
     fatal("[dlaf_mi355x] eigensolver: the eigenvector matrix must be n x %ld with A's block size and row source rank\n",
           end - b0);
   hipStream_t s = A.s_high;
+  const DebugWho who = eig_debug(g);
   const int band = r.band;
-  R* wd = ealloc<R>((size_t) n);
-  R* zr = ealloc<R>((size_t) n * k);
+  PoolScope ws, ws_el;
+  R* wd = ws.get<R>((size_t) n);
+  R* zr = ws.get<R>((size_t) n * k);
   {
     StageTimer t(s);
     tridiag_solver_device<R>(n, nb, r.d, r.e, wd, zr, n, begin, end, s, g->nranks > 1 ? grid_transport(*g) : nullptr);
     g_stage_ms[2] = t.stop();
   }
-  debug_checksum(g, s, "w", wd, (size_t) n * sizeof(R));
-  debug_checksum(g, s, "z (tridiagonal)", zr, (size_t) n * k * sizeof(R));
+  debug_checksum(who, s, "w", wd, (size_t) n * sizeof(R));
+  debug_checksum(who, s, "z (tridiagonal)", zr, (size_t) n * k * sizeof(R));
   DLAF_HIP_CHECK(hipMemcpyAsync(w_host, wd, (size_t) n * sizeof(R), hipMemcpyDeviceToHost, s));
   if (k == 0) {
     // no eigenvector is wanted: the eigenvalues are all there is
     DLAF_HIP_CHECK(hipStreamSynchronize(s));
-    for (R* q : {wd, zr})
-      DLAF_HIP_CHECK(pool_free(q));
-    r.release();
     g_stage_ms[3] = g_stage_ms[4] = 0;
     return 0;
   }
   // the columns of this process column, all rows (the back-transformation mixes rows, never columns)
   const long ncl = C.cols.local_size();
   const long lde = bt_aligned_ld(n);
-  T* el_alloc = ealloc<T>((size_t) lde * std::max<long>(ncl, 1) + 4);
-  T* el = bt_aligned_base(el_alloc);
+  T* el = bt_aligned_base(ws_el.get<T>((size_t) lde * std::max<long>(ncl, 1) + 4));
   launch_cols_gather_cast<R, T>(zr, n, n, nb, C.cols.P, C.cols.shift(), ncl, pad, el, lde, s);
   {
     StageTimer t(s);
     bt_band_to_tridiag_device(n, band, r.v, n, el, lde, ncl, s);
     g_stage_ms[3] = t.stop();
   }
-  debug_checksum(g, s, "E after bt_b2t", el, (size_t) lde * std::max<long>(ncl, 1) * sizeof(T));
+  debug_checksum(who, s, "E after bt_b2t", el, (size_t) lde * std::max<long>(ncl, 1) * sizeof(T));
   launch_rows_to_tiles(el, lde, n, ncl, nb, C.rows.P, C.rows.shift(), C.ltr, C.ltc, C.tiles, s);
   DLAF_HIP_CHECK(hipStreamSynchronize(s));
-  for (R* q : {wd, zr})
-    DLAF_HIP_CHECK(pool_free(q));
+  // the last stage takes its own workspaces: everything of the earlier ones goes back first
+  ws.release();
   r.release();
-  DLAF_HIP_CHECK(pool_free(el_alloc));
-  debug_checksum(g, s, "C before bt_red2band", C.tiles, (size_t) C.ltr * C.ltc * C.tile_elems * sizeof(T));
+  ws_el.release();
+  debug_checksum(who, s, "C before bt_red2band", C.tiles, (size_t) C.ltr * C.ltc * C.tile_elems * sizeof(T));
   const int info = agreed(g, bt_reduction_to_band_device(band, C, A, r.taus.data()));
-  debug_checksum(g, s, "C after bt_red2band", C.tiles, (size_t) C.ltr * C.ltc * C.tile_elems * sizeof(T));
+  debug_checksum(who, s, "C after bt_red2band", C.tiles, (size_t) C.ltr * C.ltc * C.tile_elems * sizeof(T));
   {
     double ms = 0, fl = 0;
     red2band_last_profile(&ms, &fl);
@@ -702,20 +708,19 @@ int hermitian_eigenvalues_device(DeviceMatrix<T>& A, real_t<T>* w_host, long beg
   const int info = eigensolver_reductions(A, r);
   if (info != 0)
     return info;
-  DLAF_HIP_CHECK(pool_free(r.v));
+  r.reflectors.release();  // (the bisection needs d and e alone)
   r.v = nullptr;
   g_stage_ms[2] = g_stage_ms[3] = g_stage_ms[4] = 0;
   if (end > begin) {
-    R* wd = ealloc<R>((size_t) n);
-    double* work = ealloc<double>(sturm_work_doubles(n));
+    PoolScope ws;
+    R* wd = ws.get<R>((size_t) n);
+    double* work = ws.get<double>(sturm_work_doubles(n));
     StageTimer t(s);
     tridiag_eigenvalues_device<R>(n, r.d, r.e, wd, begin, end, work, s);
     g_stage_ms[2] = t.stop();
-    debug_checksum(A.grid, s, "w (bisection)", wd + begin, (size_t) (end - begin) * sizeof(R));
+    debug_checksum(eig_debug(A.grid), s, "w (bisection)", wd + begin, (size_t) (end - begin) * sizeof(R));
     DLAF_HIP_CHECK(hipMemcpyAsync(w_host + begin, wd + begin, (size_t) (end - begin) * sizeof(R), hipMemcpyDeviceToHost, s));
     DLAF_HIP_CHECK(hipStreamSynchronize(s));
-    DLAF_HIP_CHECK(pool_free(wd));
-    DLAF_HIP_CHECK(pool_free(work));
   }
   return 0;
 }

@@ -89,6 +89,9 @@ void sturm_count_device(long n, const R* d, const R* e, const R* shifts_host, lo
                         hipStream_t s);
 template <class R>
 int sturm_count_host(long n, const R* d, const R* e, long nshifts, const R* shifts, long* counts);
+// d, e of a host tridiagonal matrix on the device, in workspaces of ws (e padded to n entries); enqueues on s
+template <class R>
+void upload_tridiag(PoolScope& ws, long n, const R* d, const R* e, R*& dd, R*& de, hipStream_t s);
 
 // Index arithmetic of a partial spectrum.  The drivers hold the eigenvectors of [begin, end) in an internal matrix that
 // covers the global columns [b0, end), b0 = (begin / nb) nb: whole tile columns are dropped in front of it, so its local

@@ -12,12 +12,6 @@
 namespace dlaf_mi355x {
 
 namespace {
-template <class T>
-T* valloc(size_t elems) {
-  T* p = nullptr;
-  DLAF_HIP_CHECK(pool_malloc(reinterpret_cast<void**>(&p), std::max<size_t>(elems, 1) * sizeof(T)));
-  return p;
-}
 static_assert(sizeof(long) == sizeof(long long), "the counts are 64-bit on both sides of the C ABI");
 }  // namespace
 
@@ -38,31 +32,26 @@ void sturm_count_device(long n, const R* d, const R* e, const R* shifts_host, lo
     std::fill(counts_host, counts_host + nshifts, 0L);
     return;
   }
-  double* work = valloc<double>(sturm_work_doubles(n));
-  R* dsh = valloc<R>((size_t) nshifts);
-  long long* dcn = valloc<long long>((size_t) nshifts);
+  PoolScope ws;
+  double* work = ws.get<double>(sturm_work_doubles(n));
+  R* dsh = ws.get<R>((size_t) nshifts);
+  long long* dcn = ws.get<long long>((size_t) nshifts);
   DLAF_HIP_CHECK(hipMemcpyAsync(dsh, shifts_host, (size_t) nshifts * sizeof(R), hipMemcpyHostToDevice, s));
   launch_sturm_prepare<R>(d, e, n, work, s);
   launch_sturm_count<R>(work, n, dsh, nshifts, dcn, s);
   DLAF_HIP_CHECK(hipMemcpyAsync(counts_host, dcn, (size_t) nshifts * sizeof(long long), hipMemcpyDeviceToHost, s));
   DLAF_HIP_CHECK(hipStreamSynchronize(s));
-  DLAF_HIP_CHECK(pool_free(work));
-  DLAF_HIP_CHECK(pool_free(dsh));
-  DLAF_HIP_CHECK(pool_free(dcn));
 }
 
-namespace {
-// d, e of a host tridiagonal matrix on the device (e padded to n entries)
 template <class R>
-void upload_tridiag(long n, const R* d, const R* e, R*& dd, R*& de, hipStream_t s) {
-  dd = valloc<R>((size_t) n);
-  de = valloc<R>((size_t) n);
+void upload_tridiag(PoolScope& ws, long n, const R* d, const R* e, R*& dd, R*& de, hipStream_t s) {
+  dd = ws.get<R>((size_t) n);
+  de = ws.get<R>((size_t) n);
   DLAF_HIP_CHECK(hipMemsetAsync(de, 0, (size_t) n * sizeof(R), s));
   DLAF_HIP_CHECK(hipMemcpyAsync(dd, d, (size_t) n * sizeof(R), hipMemcpyHostToDevice, s));
   if (n > 1)
     DLAF_HIP_CHECK(hipMemcpyAsync(de, e, (size_t) (n - 1) * sizeof(R), hipMemcpyHostToDevice, s));
 }
-}  // namespace
 
 template <class R>
 int tridiag_eigenvalues_host(long n, const R* d, const R* e, R* w, long begin, long end) {
@@ -71,16 +60,15 @@ int tridiag_eigenvalues_host(long n, const R* d, const R* e, R* w, long begin, l
     return 0;
   hipStream_t s;
   DLAF_HIP_CHECK(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
+  PoolScope ws;
   R *dd, *de;
-  upload_tridiag(n, d, e, dd, de, s);
-  R* dw = valloc<R>((size_t) n);
-  double* work = valloc<double>(sturm_work_doubles(n));
+  upload_tridiag(ws, n, d, e, dd, de, s);
+  R* dw = ws.get<R>((size_t) n);
+  double* work = ws.get<double>(sturm_work_doubles(n));
   tridiag_eigenvalues_device<R>(n, dd, de, dw, begin, end, work, s);
   DLAF_HIP_CHECK(hipMemcpyAsync(w + begin, dw + begin, (size_t) (end - begin) * sizeof(R), hipMemcpyDeviceToHost, s));
   DLAF_HIP_CHECK(hipStreamSynchronize(s));
-  for (R* p : {dd, de, dw})
-    DLAF_HIP_CHECK(pool_free(p));
-  DLAF_HIP_CHECK(pool_free(work));
+  ws.release();
   DLAF_HIP_CHECK(hipStreamDestroy(s));
   return 0;
 }
@@ -97,11 +85,11 @@ int sturm_count_host(long n, const R* d, const R* e, long nshifts, const R* shif
   }
   hipStream_t s;
   DLAF_HIP_CHECK(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
+  PoolScope ws;
   R *dd, *de;
-  upload_tridiag(n, d, e, dd, de, s);
+  upload_tridiag(ws, n, d, e, dd, de, s);
   sturm_count_device<R>(n, dd, de, shifts, nshifts, counts, s);
-  DLAF_HIP_CHECK(pool_free(dd));
-  DLAF_HIP_CHECK(pool_free(de));
+  ws.release();
   DLAF_HIP_CHECK(hipStreamDestroy(s));
   return 0;
 }
@@ -109,6 +97,7 @@ int sturm_count_host(long n, const R* d, const R* e, long nshifts, const R* shif
 #define INST(R)                                                                                                    \
   template void tridiag_eigenvalues_device<R>(long, const R*, const R*, R*, long, long, double*, hipStream_t);     \
   template void sturm_count_device<R>(long, const R*, const R*, const R*, long, long*, hipStream_t);               \
+  template void upload_tridiag<R>(PoolScope&, long, const R*, const R*, R*&, R*&, hipStream_t);                    \
   template int tridiag_eigenvalues_host<R>(long, const R*, const R*, R*, long, long);                              \
   template int sturm_count_host<R>(long, const R*, const R*, long, const R*, long*);
 INST(float)

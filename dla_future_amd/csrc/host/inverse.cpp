@@ -40,18 +40,6 @@ namespace dlaf_mi355x {
 
 namespace {
 
-// a workspace from the pool (runtime.hpp) that goes back to it with its scope
-template <class T>
-struct PoolBuf {
-  T* p = nullptr;
-  explicit PoolBuf(size_t elems) {
-    DLAF_HIP_CHECK(pool_malloc(reinterpret_cast<void**>(&p), std::max<size_t>(elems, 1) * sizeof(T)));
-  }
-  PoolBuf(const PoolBuf&) = delete;
-  PoolBuf& operator=(const PoolBuf&) = delete;
-  ~PoolBuf() { (void) pool_free(p); }
-};
-
 double g_profile_ms = 0, g_profile_flops = 0;
 
 }  // namespace
@@ -114,22 +102,23 @@ struct Inverse {
   int* const info;
   const hipStream_t s;
   const DiagTiles dt;
-  PoolBuf<T> wn;     // per local diagonal tile [W | N] (product: [Z | unused]); one more pair for a received one
-  PoolBuf<T> tw;     // adjoint tiles of row k, one per local column left of the diagonal
-  PoolBuf<T> panel;  // received column panel (inverse) / the adjoint tiles by local ROW (product)
+  PoolScope ws;
+  T* const wn;     // per local diagonal tile [W | N] (product: [Z | unused]); one more pair for a received one
+  T* const tw;     // adjoint tiles of row k, one per local column left of the diagonal
+  T* const panel;  // received column panel (inverse) / the adjoint tiles by local ROW (product)
 
   Inverse(DeviceMatrix<T>& A_, Transport* tr_)
       : A(A_), tr(tr_), dist(A_.grid->nranks > 1), rows(A_.rows), cols(A_.cols), nt(A_.nt), ltr(A_.ltr), ltc(A_.ltc),
         nb(A_.nb), te(A_.tile_elems), ax_row(A_.transposed ? CommAxis::Col : CommAxis::Row),
         ax_col(A_.transposed ? CommAxis::Row : CommAxis::Col), info(A_.info), s(A_.s_high),
-        dt(local_diag_tiles(A_.rows, A_.cols)), wn((size_t) 2 * (dt.count + 1) * te), tw((size_t) ltc * te),
-        panel((size_t) ltr * te) {}
+        dt(local_diag_tiles(A_.rows, A_.cols)), wn(ws.get<T>((size_t) 2 * (dt.count + 1) * te)),
+        tw(ws.get<T>((size_t) ltc * te)), panel(ws.get<T>((size_t) ltr * te)) {}
 
   long diag_slot(long k) const { return (k - dt.k0) / dt.kstep; }
   // [first | second] tile of the diagonal tile k: the owner's own slot, elsewhere the slot a broadcast fills
   T* pair_of(long k) const {
     const bool own = rows.mine(k) && cols.mine(k);
-    return wn.p + (size_t) 2 * (own ? diag_slot(k) : dt.count) * te;
+    return wn + (size_t) 2 * (own ? diag_slot(k) : dt.count) * te;
   }
   template <class U>
   TileBatch<U> diag_batch() const {
@@ -144,18 +133,19 @@ struct Inverse {
   }
   TileBatch<T> pair_batch(int which) const {
     TileBatch<T> b = diag_batch<T>();
-    b.base = wn.p + (size_t) which * te;
+    b.base = wn + (size_t) which * te;
     b.stride = 2 * (long) te;
     return b;
   }
 
   // LAPACK's info of xTRTRI: the first exactly-zero diagonal element, before anything is written (this process's)
   int scan_zero_diagonal() {
-    PoolBuf<unsigned> first(1);
-    DLAF_HIP_CHECK(hipMemsetAsync(first.p, 0xff, sizeof(unsigned), s));
-    launch_diag_zero_scan(diag_batch<const T>(), dt.k0, dt.kstep, first.p, s);
+    PoolScope scan;
+    unsigned* first = scan.get<unsigned>(1);
+    DLAF_HIP_CHECK(hipMemsetAsync(first, 0xff, sizeof(unsigned), s));
+    launch_diag_zero_scan(diag_batch<const T>(), dt.k0, dt.kstep, first, s);
     unsigned h = 0;
-    DLAF_HIP_CHECK(hipMemcpyAsync(&h, first.p, sizeof(unsigned), hipMemcpyDeviceToHost, s));
+    DLAF_HIP_CHECK(hipMemcpyAsync(&h, first, sizeof(unsigned), hipMemcpyDeviceToHost, s));
     DLAF_HIP_CHECK(hipStreamSynchronize(s));
     return h == 0xffffffffu ? 0 : (int) h;
   }
@@ -169,11 +159,11 @@ struct Inverse {
   }
   // row k's tiles left of the diagonal <-> their adjoints in tw
   void stage_row(const InverseStep& st, int kb) {
-    launch_tile_xform(tw.p, (long) nb, (long) te, A.tile(st.lr, 0), (long) nb, (long) (te * ltr), kb, nb, (int) st.ncl, 0,
+    launch_tile_xform(tw, (long) nb, (long) te, A.tile(st.lr, 0), (long) nb, (long) (te * ltr), kb, nb, (int) st.ncl, 0,
                       1.0, s);
   }
   void unstage_row(const InverseStep& st, int kb) {
-    launch_tile_xform(A.tile(st.lr, 0), (long) nb, (long) (te * ltr), tw.p, (long) nb, (long) te, nb, kb, (int) st.ncl, 0,
+    launch_tile_xform(A.tile(st.lr, 0), (long) nb, (long) (te * ltr), tw, (long) nb, (long) te, nb, kb, (int) st.ncl, 0,
                       1.0, s);
   }
   void end_of_step() {
@@ -187,16 +177,17 @@ struct Inverse {
     if (dt.count == 0)
       return;
     const size_t wel = A.winv_elems();
-    PoolBuf<T> winv((size_t) dt.count * wel);
+    PoolScope blocks;
+    T* winv = blocks.get<T>((size_t) dt.count * wel);
     const TileBatch<const T> tiles = diag_batch<const T>();
     for (long m = 0; m < dt.count; ++m)
-      launch_invert_diag_blocks(tiles.base + m * tiles.stride, nb, m == dt.count - 1 ? dt.last : nb, winv.p + m * wel,
+      launch_invert_diag_blocks(tiles.base + m * tiles.stride, nb, m == dt.count - 1 ? dt.last : nb, winv + m * wel,
                                 info, s, false, unit);
-    launch_tile_trtri(tiles, winv.p, (long) wel, wn.p + te, 2 * (long) te, s);
+    launch_tile_trtri(tiles, winv, (long) wel, wn + te, 2 * (long) te, s);
     // W = -N^H
-    launch_tile_xform_alpha(wn.p, (long) nb, 2 * (long) te, wn.p + te, (long) nb, 2 * (long) te, nb, nb, (int) dt.count,
+    launch_tile_xform_alpha(wn, (long) nb, 2 * (long) te, wn + te, (long) nb, 2 * (long) te, nb, nb, (int) dt.count,
                             0, neg_one(), true, s);
-    launch_tri_tile(diag_batch<T>(), wn.p, 2 * (long) te, 0, unit, s);
+    launch_tri_tile(diag_batch<T>(), wn, 2 * (long) te, 0, unit, s);
   }
   static T neg_one() {
     if constexpr (TypeInfo<T>::is_complex)
@@ -223,19 +214,19 @@ struct Inverse {
     }
     if (k == 0)
       return end_of_step();
-    T* colL = in_col ? A.tile(st.il_below < ltr ? st.il_below : 0, st.lc) : panel.p;
+    T* colL = in_col ? A.tile(st.il_below < ltr ? st.il_below : 0, st.lc) : panel;
     if (cols.P > 1 && st.il_below < ltr)
       tr->bcast(ax_row, st.own_c, cols.rank, colL, colL, (size_t) (ltr - st.il_below) * te * sizeof(T), s);
     // (2) update with the adjoint tiles of row k as it is before (3)
     if (in_row && st.ncl > 0)
       stage_row(st, kb);
     if (rows.P > 1 && st.ncl > 0 && k + 1 < nt)
-      tr->bcast(ax_col, st.own_r, rows.rank, tw.p, tw.p, (size_t) st.ncl * te * sizeof(T), s);
+      tr->bcast(ax_col, st.own_r, rows.rank, tw, tw, (size_t) st.ncl * te * sizeof(T), s);
     if (st.il_below < ltr && st.ncl > 0)
-      launch_update(rect_update_args(A, st.il_below, ltr, 0, st.ncl, colL, tw.p, (long) te, kb, info), s, 4);
+      launch_update(rect_update_args(A, st.il_below, ltr, 0, st.ncl, colL, tw, (long) te, kb, info), s, 4);
     // (3) row: (W L(k,j))^H = L(k,j)^H W^H
     if (in_row && st.ncl > 0) {
-      trmm_tiles(tw.p, st.ncl, nb, W, kb, false);
+      trmm_tiles(tw, st.ncl, nb, W, kb, false);
       unstage_row(st, kb);
     }
     end_of_step();
@@ -247,7 +238,7 @@ struct Inverse {
     if (dt.count == 0)
       return;
     launch_tri_tile(pair_batch(0), A.tile(dt.il0, dt.jl0), diag_batch<T>().stride, 1, false, s);
-    launch_tile_lauum(diag_batch<T>(), wn.p, 2 * (long) te, s);
+    launch_tile_lauum(diag_batch<T>(), wn, 2 * (long) te, s);
   }
 
   void product_step(long k) {
@@ -260,31 +251,31 @@ struct Inverse {
     if (in_row && st.ncl > 0)
       stage_row(st, kb);
     if (rows.P > 1 && st.ncl > 0)
-      tr->bcast(ax_col, st.own_r, rows.rank, tw.p, tw.p, (size_t) st.ncl * te * sizeof(T), s);
+      tr->bcast(ax_col, st.own_r, rows.rank, tw, tw, (size_t) st.ncl * te * sizeof(T), s);
     // the first operand: the adjoint tile of global column i for every local tile ROW i < k
-    const T* a = tw.p;
+    const T* a = tw;
     if (dist && st.nrl > 0) {
-      a = panel.p;
+      a = panel;
       if (cols.P > 1)
         tr->group_begin();
       for (long il = 0; il < st.nrl; ++il) {
         const long gi = rows.global_of(il);
         const int root = cols.owner(gi);
-        const T* src = cols.rank == root ? tw.p + (size_t) cols.local_of(gi) * te : nullptr;
+        const T* src = cols.rank == root ? tw + (size_t) cols.local_of(gi) * te : nullptr;
         if (cols.P > 1)
-          tr->bcast(ax_row, root, cols.rank, src, panel.p + (size_t) il * te, te * sizeof(T), s);
+          tr->bcast(ax_row, root, cols.rank, src, panel + (size_t) il * te, te * sizeof(T), s);
         else
-          DLAF_HIP_CHECK(hipMemcpyAsync(panel.p + (size_t) il * te, src, te * sizeof(T), hipMemcpyDeviceToDevice, s));
+          DLAF_HIP_CHECK(hipMemcpyAsync(panel + (size_t) il * te, src, te * sizeof(T), hipMemcpyDeviceToDevice, s));
       }
       if (cols.P > 1)
         tr->group_end();
     }
     // (1) update, triangle form
     if (st.nrl > 0 && st.ncl > 0)
-      launch_update(update_args(A, 0, st.nrl, 0, st.ncl, a, (const T*) tw.p, (long) te, kb, info), s, 4);
+      launch_update(update_args(A, 0, st.nrl, 0, st.ncl, a, (const T*) tw, (long) te, kb, info), s, 4);
     // (2) row: (L_kk^H L(k,j))^H = L(k,j)^H L_kk = L(k,j)^H Z^H
     if (in_row && st.ncl > 0) {
-      trmm_tiles(tw.p, st.ncl, nb, Z, kb, true);
+      trmm_tiles(tw, st.ncl, nb, Z, kb, true);
       unstage_row(st, kb);
     }
     end_of_step();

@@ -24,17 +24,6 @@ namespace dlaf_mi355x {
 
 namespace {
 
-template <class T>
-struct PoolBuf {
-  T* p = nullptr;
-  explicit PoolBuf(size_t elems) {
-    DLAF_HIP_CHECK(pool_malloc(reinterpret_cast<void**>(&p), std::max<size_t>(elems, 1) * sizeof(T)));
-  }
-  PoolBuf(const PoolBuf&) = delete;
-  PoolBuf& operator=(const PoolBuf&) = delete;
-  ~PoolBuf() { (void) pool_free(p); }
-};
-
 double g_profile_ms = 0, g_profile_bytes = 0;
 
 // the end of xLASSQ + xNRM2 (LAPACK 3.10): sqrt of the sum of squares from its three scaled accumulators
@@ -94,14 +83,15 @@ double norm_of_view(Grid& grid, char kind, int structure, bool unit, const T* ti
   const bool sums = a.mode == kNormCol || a.mode == kNormRow || a.mode == kNormColRow;
   const long len = !sums ? 0 : (a.mode == kNormRow ? rows.n : cols.n);
   const long units = norm_unit_count(a.g, a.s);
-  PoolBuf<double> scal((size_t) units * kNormScalars);
-  PoolBuf<double> colp((a.mode & kNormCol) && sums ? (size_t) norm_colp_elems(a.g, a.s) : 0);
-  PoolBuf<double> rowp((a.mode & kNormRow) && sums ? (size_t) norm_rowp_elems(a.g, a.s) : 0);
-  PoolBuf<double> vec((size_t) len);
-  PoolBuf<double> out(8);
-  a.scal = scal.p;
-  a.colp = colp.p;
-  a.rowp = rowp.p;
+  PoolScope ws;
+  double* scal = ws.get<double>((size_t) units * kNormScalars);
+  double* colp = ws.get<double>((a.mode & kNormCol) && sums ? (size_t) norm_colp_elems(a.g, a.s) : 0);
+  double* rowp = ws.get<double>((a.mode & kNormRow) && sums ? (size_t) norm_rowp_elems(a.g, a.s) : 0);
+  double* vec = ws.get<double>((size_t) len);
+  double* out = ws.get<double>(8);
+  a.scal = scal;
+  a.colp = colp;
+  a.rowp = rowp;
 
   double bytes = 0;
   for (int jl = 0; jl < a.g.ltc; ++jl)
@@ -114,18 +104,18 @@ double norm_of_view(Grid& grid, char kind, int structure, bool unit, const T* ti
   DLAF_HIP_CHECK(hipEventCreate(&e1));
   DLAF_HIP_CHECK(hipEventRecord(e0, s));
   launch_norm_pass1(a, s);
-  launch_norm_scalars(scal.p, units, out.p, s);
+  launch_norm_scalars(scal, units, out, s);
   if (a.mode == kNormFro && dist)
-    tr->allreduce_sum(out.p + 2, 3, 'd', 'A', s);
+    tr->allreduce_sum(out + 2, 3, 'd', 'A', s);
   if (sums) {
-    launch_norm_vector(a.g, a.s, a.mode, colp.p, rowp.p, vec.p, len, s);
+    launch_norm_vector(a.g, a.s, a.mode, colp, rowp, vec, len, s);
     if (dist)
-      tr->allreduce_sum(vec.p, (size_t) len, 'd', 'A', s);
-    launch_norm_vecmax(vec.p, len, out.p + kNormScalars, s);
+      tr->allreduce_sum(vec, (size_t) len, 'd', 'A', s);
+    launch_norm_vecmax(vec, len, out + kNormScalars, s);
   }
   DLAF_HIP_CHECK(hipEventRecord(e1, s));
   double h[kNormScalars + 1] = {0, 0, 0, 0, 0, 0};
-  DLAF_HIP_CHECK(hipMemcpyAsync(h, out.p, sizeof(h), hipMemcpyDeviceToHost, s));
+  DLAF_HIP_CHECK(hipMemcpyAsync(h, out, sizeof(h), hipMemcpyDeviceToHost, s));
   DLAF_HIP_CHECK(hipStreamSynchronize(s));
   float ms = 0;
   DLAF_HIP_CHECK(hipEventElapsedTime(&ms, e0, e1));

@@ -40,12 +40,6 @@ namespace dlaf_mi355x {
 
 namespace {
 template <class T>
-T* dalloc(size_t elems) {
-  T* p = nullptr;
-  DLAF_HIP_CHECK(pool_malloc(reinterpret_cast<void**>(&p), std::max<size_t>(elems, 1) * sizeof(T)));
-  return p;
-}
-template <class T>
 T scalar(double re) {
   return make_host_el<T>(re);
 }
@@ -278,6 +272,7 @@ struct Red2BandIssue : PanelSteps<T> {
   int* hr_flag_host = nullptr;
   long panels_blocked = 0, panels_fallback = 0;
   hipEvent_t ev0, ev1, ev_x[2], ev_rest[2];
+  PoolScope ws;
 
   Red2BandIssue(DeviceMatrix<T>& a, Transport* t, int band, long nr)
       : Base(a, t), b(band), nrefls(nr),
@@ -287,16 +282,16 @@ struct Red2BandIssue : PanelSteps<T> {
     // (the pool hands out blocks of equal size in the order they were released: this order is kept on purpose)
     const long n = A.n, ltr = A.ltr, ltc = A.ltc;
     const int nb = A.nb;
-    qt = dalloc<T>((size_t) b * (size_t) n);
-    Vb[0] = dalloc<T>((size_t) ldp * b);
-    Vb[1] = dalloc<T>((size_t) ldp * b);
-    W = dalloc<T>((size_t) ldp * b);
-    Xb[0] = dalloc<T>((size_t) ldp * b);
-    Xb[1] = dalloc<T>((size_t) ldp * b);
-    S = dalloc<T>((size_t) b * b);
-    Tm = dalloc<T>((size_t) b * b);
-    W2 = dalloc<T>((size_t) b * b);
-    taus = dalloc<T>((size_t) nrefls + 1);
+    qt = ws.get<T>((size_t) b * (size_t) n);
+    Vb[0] = ws.get<T>((size_t) ldp * b);
+    Vb[1] = ws.get<T>((size_t) ldp * b);
+    W = ws.get<T>((size_t) ldp * b);
+    Xb[0] = ws.get<T>((size_t) ldp * b);
+    Xb[1] = ws.get<T>((size_t) ldp * b);
+    S = ws.get<T>((size_t) b * b);
+    Tm = ws.get<T>((size_t) b * b);
+    W2 = ws.get<T>((size_t) b * b);
+    taus = ws.get<T>((size_t) nrefls + 1);
     for (int q = 0; q < 2; ++q) {
       DLAF_HIP_CHECK(hipMemsetAsync(Vb[q], 0, (size_t) ldp * b * sizeof(T), s));
       DLAF_HIP_CHECK(hipMemsetAsync(Xb[q], 0, (size_t) ldp * b * sizeof(T), s));
@@ -304,7 +299,7 @@ struct Red2BandIssue : PanelSteps<T> {
     DLAF_HIP_CHECK(hipMemsetAsync(W, 0, (size_t) ldp * b * sizeof(T), s));
     DLAF_HIP_CHECK(hipMemsetAsync(taus, 0, ((size_t) nrefls + 1) * sizeof(T), s));
     ksplit_max = std::max(1, gemm_pick_ksplit<T>(b, b, n));
-    gpart = dalloc<T>(gemm_partial_elems<T>(b, b, ksplit_max));
+    gpart = ws.get<T>(gemm_partial_elems<T>(b, b, ksplit_max));
     // partial layers of the xHEMM: (layers + 1) * out tiles at its maximum over the panels (trailing matrices of
     // ot x ot local tiles: the local tile counts shrink together)
     for (long k = 0; k <= std::max(ltr, ltc); ++k) {
@@ -319,17 +314,17 @@ struct Red2BandIssue : PanelSteps<T> {
       cap_s = std::max<long>(cap_s, (long) (tile_panel_layers(otc + 1, cs) + 1) * (otr + 1));
       cap_t = std::max<long>(cap_t, (long) (tile_panel_layers(otr + 1, ct) + 1) * (otc + 1));
     }
-    part_s = dalloc<T>((size_t) cap_s * nb * (size_t) b);
-    part_t = dalloc<T>((size_t) cap_t * nb * (size_t) b);
+    part_s = ws.get<T>((size_t) cap_s * nb * (size_t) b);
+    part_t = ws.get<T>((size_t) cap_t * nb * (size_t) b);
     DLAF_HIP_CHECK(hipMalloc(&qr_scratch, panel_qr_scratch_bytes(b, sizeof(T))));
     if (blocked) {
-      Pcm = dalloc<T>((size_t) ldp * b);
-      hr_g = dalloc<T>((size_t) b * b);
-      hr_l2 = dalloc<T>((size_t) b * b);
-      hr_r = dalloc<T>((size_t) b * b);
-      hr_lu = dalloc<T>((size_t) b * b);
-      hr_y1 = dalloc<T>((size_t) b * b);
-      hr_winv = dalloc<T>(4 * hr_wblk);
+      Pcm = ws.get<T>((size_t) ldp * b);
+      hr_g = ws.get<T>((size_t) b * b);
+      hr_l2 = ws.get<T>((size_t) b * b);
+      hr_r = ws.get<T>((size_t) b * b);
+      hr_lu = ws.get<T>((size_t) b * b);
+      hr_y1 = ws.get<T>((size_t) b * b);
+      hr_winv = ws.get<T>(4 * hr_wblk);
       // [0] failure, [1] second pass skipped, [2] status of the second Cholesky factorization
       DLAF_HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&hr_flag), 3 * sizeof(int)));
       DLAF_HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&hr_sync), sizeof(unsigned) * potrf_coop_sync_words(b)));
@@ -356,12 +351,9 @@ struct Red2BandIssue : PanelSteps<T> {
       DLAF_HIP_CHECK(hipEventDestroy(ev_x[q]));
       DLAF_HIP_CHECK(hipEventDestroy(ev_rest[q]));
     }
-    for (T* q : {qt, Vb[0], Vb[1], W, Xb[0], Xb[1], S, Tm, W2, taus, gpart, part_s, part_t})
-      DLAF_HIP_CHECK(pool_free(q));
+    ws.release();
     DLAF_HIP_CHECK(hipFree(qr_scratch));
     if (blocked) {
-      for (T* q : {Pcm, hr_g, hr_l2, hr_r, hr_lu, hr_y1, hr_winv})
-        DLAF_HIP_CHECK(pool_free(q));
       DLAF_HIP_CHECK(hipFree(hr_flag));
       DLAF_HIP_CHECK(hipFree(hr_sync));
     }
@@ -624,24 +616,25 @@ int bt_reduction_to_band_device(int band, TileMatrix<T>& C, DeviceMatrix<T>& A, 
   const long ldp = ps.ldp;
   const long ldw2 = std::max<long>(cltc * nb, 1);
 
-  ps.qt = dalloc<T>((size_t) nb * (size_t) n);
-  T* V = dalloc<T>((size_t) ldp * nb);
-  ps.W = dalloc<T>((size_t) ldp * nb);
-  ps.S = dalloc<T>((size_t) nb * nb);
-  ps.Tm = dalloc<T>((size_t) nb * nb);
-  T* W2H = dalloc<T>((size_t) ldw2 * nb);
-  ps.taus = dalloc<T>((size_t) total + 1);
+  PoolScope ws;
+  ps.qt = ws.get<T>((size_t) nb * (size_t) n);
+  T* V = ws.get<T>((size_t) ldp * nb);
+  ps.W = ws.get<T>((size_t) ldp * nb);
+  ps.S = ws.get<T>((size_t) nb * nb);
+  ps.Tm = ws.get<T>((size_t) nb * nb);
+  T* W2H = ws.get<T>((size_t) ldw2 * nb);
+  ps.taus = ws.get<T>((size_t) total + 1);
   DLAF_HIP_CHECK(hipMemcpyAsync(ps.taus, taus_host, (size_t) total * sizeof(T), hipMemcpyHostToDevice, s));
   DLAF_HIP_CHECK(hipMemsetAsync(V, 0, (size_t) ldp * nb * sizeof(T), s));
   DLAF_HIP_CHECK(hipMemsetAsync(ps.W, 0, (size_t) ldp * nb * sizeof(T), s));
   ps.ksplit_max = std::max(1, gemm_pick_ksplit<T>(nb, nb, n));
-  ps.gpart = dalloc<T>(gemm_partial_elems<T>(nb, nb, ps.ksplit_max));
+  ps.gpart = ws.get<T>(gemm_partial_elems<T>(nb, nb, ps.ksplit_max));
   long lay_cap = 2;
   for (long src = 1; src <= std::max<long>(cltr, 1); ++src) {
     const int ch = tile_panel_pick_chunk(std::max<long>(cltc, 1), nb, nb, src, false, sizeof(T));
     lay_cap = std::max<long>(lay_cap, (long) (tile_panel_layers(src, ch) + 1) * std::max<long>(cltc, 1));
   }
-  T* part_t = dalloc<T>((size_t) lay_cap * nb * (size_t) nb);
+  T* part_t = ws.get<T>((size_t) lay_cap * nb * (size_t) nb);
 
   hipEvent_t ev0, ev1;
   DLAF_HIP_CHECK(hipEventCreate(&ev0));
@@ -718,8 +711,6 @@ int bt_reduction_to_band_device(int band, TileMatrix<T>& C, DeviceMatrix<T>& A, 
   g_last_flops = (TypeInfo<T>::is_complex ? 4.0 : 1.0) * 2.0 * (double) (n - b) * (double) (n - b) * (double) ccols.n;
   DLAF_HIP_CHECK(hipEventDestroy(ev0));
   DLAF_HIP_CHECK(hipEventDestroy(ev1));
-  for (T* q : {ps.qt, V, ps.W, ps.S, ps.Tm, W2H, ps.taus, ps.gpart, part_t})
-    DLAF_HIP_CHECK(pool_free(q));
   return 0;
 }
 

@@ -44,6 +44,36 @@ hipError_t pool_free(void* p);
 void pool_release();
 size_t pool_idle_bytes();
 
+// The owner of a function's (or a step's) pool workspaces: get() takes them, release() -- at the latest the destructor --
+// gives them back IN THE ORDER THEY WERE TAKEN.  The pool hands out blocks of equal size first-in-first-out, so a
+// buffer taken and released at the same position gets the same block on the next call; releasing in reverse order (one
+// owner per buffer, destroyed as C++ destroys locals) would swap equal-sized neighbours between calls.  Memory that
+// must go early -- to bound the peak, or to place the device synchronisation of pool_free -- gets a scope of its own or
+// an explicit release() at that point.
+class PoolScope {
+public:
+  PoolScope() = default;
+  PoolScope(const PoolScope&) = delete;
+  PoolScope& operator=(const PoolScope&) = delete;
+  ~PoolScope() { release(); }
+  // `elems` elements (at least one)
+  template <class T>
+  T* get(size_t elems) {
+    void* p = nullptr;
+    DLAF_HIP_CHECK(pool_malloc(&p, (elems > 0 ? elems : 1) * sizeof(T)));
+    held_.push_back(p);
+    return static_cast<T*>(p);
+  }
+  void release() {
+    for (void* p : held_)
+      DLAF_HIP_CHECK(pool_free(p));
+    held_.clear();
+  }
+
+private:
+  std::vector<void*> held_;
+};
+
 // hipMalloc of `elems` elements (at least one); an allocation that fails releases the workspace pool -- it may be
 // holding what this allocation needs -- and is tried once more before it is fatal
 template <class T>

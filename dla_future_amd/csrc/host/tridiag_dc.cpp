@@ -17,12 +17,6 @@
 namespace dlaf_mi355x {
 
 namespace {
-template <class T>
-T* dcalloc(size_t elems) {
-  T* p = nullptr;
-  DLAF_HIP_CHECK(pool_malloc(reinterpret_cast<void**>(&p), std::max<size_t>(elems, 1) * sizeof(T)));
-  return p;
-}
 struct Node {
   long off;
   int n1, n2;
@@ -112,20 +106,21 @@ int tridiag_solver_device(long n, int /*nb*/, R* d, R* e, R* w, R* z, long ldz, 
   const int height = build_tree(0, nleaves, leaf_off, nodes, bounds);
 
   const long ldq = ((n + 15) / 16) * 16;
-  R* q = dcalloc<R>((size_t) ldq * n);
-  R* qt = dcalloc<R>((size_t) ldq * n);
-  R* dlt = dcalloc<R>((size_t) ldq * n);
-  R* u = dcalloc<R>((size_t) ldq * n);
-  R* rv = dcalloc<R>((size_t) n * 8);  // dnew, z, z2, zhat, dsrt, zsrt, dsec, zsec
-  int* iv = dcalloc<int>((size_t) n * 6);  // ord, srt, ctype, tpos, sec2t, dfl
-  DcRot<R>* rots = dcalloc<DcRot<R>>((size_t) n);
-  long* d_leaf_off = dcalloc<long>((size_t) nleaves + 1);
-  int* d_leaf_n = dcalloc<int>((size_t) nleaves);
-  long* d_bounds = dcalloc<long>(bounds.size());
-  R* d_rho = dcalloc<R>(bounds.size());
-  DcMerge* d_merges = dcalloc<DcMerge>(nodes.size());
-  DcHeader<R>* d_headers = dcalloc<DcHeader<R>>(nodes.size());
-  int* info = dcalloc<int>(1);
+  PoolScope ws;
+  R* q = ws.get<R>((size_t) ldq * n);
+  R* qt = ws.get<R>((size_t) ldq * n);
+  R* dlt = ws.get<R>((size_t) ldq * n);
+  R* u = ws.get<R>((size_t) ldq * n);
+  R* rv = ws.get<R>((size_t) n * 8);  // dnew, z, z2, zhat, dsrt, zsrt, dsec, zsec
+  int* iv = ws.get<int>((size_t) n * 6);  // ord, srt, ctype, tpos, sec2t, dfl
+  DcRot<R>* rots = ws.get<DcRot<R>>((size_t) n);
+  long* d_leaf_off = ws.get<long>((size_t) nleaves + 1);
+  int* d_leaf_n = ws.get<int>((size_t) nleaves);
+  long* d_bounds = ws.get<long>(bounds.size());
+  R* d_rho = ws.get<R>(bounds.size());
+  DcMerge* d_merges = ws.get<DcMerge>(nodes.size());
+  DcHeader<R>* d_headers = ws.get<DcHeader<R>>(nodes.size());
+  int* info = ws.get<int>(1);
   DLAF_HIP_CHECK(hipMemsetAsync(info, 0, sizeof(int), s));
   DLAF_HIP_CHECK(hipMemsetAsync(q, 0, (size_t) ldq * n * sizeof(R), s));
   DLAF_HIP_CHECK(hipMemcpyAsync(d_leaf_off, leaf_off.data(), (nleaves + 1) * sizeof(long), hipMemcpyHostToDevice, s));
@@ -148,12 +143,13 @@ int tridiag_solver_device(long n, int /*nb*/, R* d, R* e, R* w, R* z, long ldz, 
   // same k.  d and e are work arrays: no caller reads them afterwards.
   int wexp = 0;
   {
-    R* d_mx = dcalloc<R>(1);
+    PoolScope ws_mx;
+    R* d_mx = ws_mx.get<R>(1);
     R mx = R(0);
     launch_dc_maxabs(d, e, n, d_mx, s);
     DLAF_HIP_CHECK(hipMemcpyAsync(&mx, d_mx, sizeof(R), hipMemcpyDeviceToHost, s));
     DLAF_HIP_CHECK(hipStreamSynchronize(s));
-    DLAF_HIP_CHECK(pool_free(d_mx));
+    ws_mx.release();
     if (mx > R(0) && std::isfinite(mx)) {
       wexp = std::ilogb(mx);
       if (wexp != 0)
@@ -233,11 +229,12 @@ int tridiag_solver_device(long n, int /*nb*/, R* d, R* e, R* w, R* z, long ldz, 
       int r0 = 0, r1 = hd.k, f0 = 0, f1 = nn - hd.k;
       if (partial && h == height) {
         int run[4];
-        int* d_run = dcalloc<int>(4);
+        PoolScope ws_run;
+        int* d_run = ws_run.get<int>(4);
         launch_dc_range(a.dnew + nd.off, nn, hd.k, (int) begin, (int) end, d_run, s);
         DLAF_HIP_CHECK(hipMemcpyAsync(run, d_run, sizeof(run), hipMemcpyDeviceToHost, s));
         DLAF_HIP_CHECK(hipStreamSynchronize(s));
-        DLAF_HIP_CHECK(pool_free(d_run));
+        ws_run.release();
         // (the operand ub + c0 keeps the alignment the product's loaders rely on)
         r0 = run[0] / 16 * 16;
         r1 = run[1] > run[0] ? std::min(hd.k, (run[1] + 15) / 16 * 16) : r0;
@@ -315,16 +312,7 @@ int tridiag_solver_device(long n, int /*nb*/, R* d, R* e, R* w, R* z, long ldz, 
   int h_info = 0;
   DLAF_HIP_CHECK(hipMemcpyAsync(&h_info, info, sizeof(int), hipMemcpyDeviceToHost, s));
   DLAF_HIP_CHECK(hipStreamSynchronize(s));
-  for (R* p : {q, qt, dlt, u, rv, d_rho})
-    DLAF_HIP_CHECK(pool_free(p));
-  DLAF_HIP_CHECK(pool_free(iv));
-  DLAF_HIP_CHECK(pool_free(rots));
-  DLAF_HIP_CHECK(pool_free(d_leaf_off));
-  DLAF_HIP_CHECK(pool_free(d_leaf_n));
-  DLAF_HIP_CHECK(pool_free(d_bounds));
-  DLAF_HIP_CHECK(pool_free(d_merges));
-  DLAF_HIP_CHECK(pool_free(d_headers));
-  DLAF_HIP_CHECK(pool_free(info));
+  ws.release();
   if (h_info != 0)
     fatal("[dlaf_mi355x] tridiagonal_eigensolver: the QL iteration of the leaf at row %d did not converge\n", h_info - 1);
   return 0;
@@ -337,22 +325,18 @@ int tridiag_solver_host(long n, int nb, const R* d, const R* e, R* w, R* z, long
   const long k = end - begin;
   hipStream_t s;
   DLAF_HIP_CHECK(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
-  R* dd = dcalloc<R>((size_t) n);
-  R* de = dcalloc<R>((size_t) n);
-  R* dw = dcalloc<R>((size_t) n);
-  R* dz = dcalloc<R>((size_t) n * k);
-  DLAF_HIP_CHECK(hipMemsetAsync(de, 0, (size_t) n * sizeof(R), s));
-  DLAF_HIP_CHECK(hipMemcpyAsync(dd, d, (size_t) n * sizeof(R), hipMemcpyHostToDevice, s));
-  if (n > 1)
-    DLAF_HIP_CHECK(hipMemcpyAsync(de, e, (size_t) (n - 1) * sizeof(R), hipMemcpyHostToDevice, s));
+  PoolScope ws;
+  R *dd, *de;
+  upload_tridiag(ws, n, d, e, dd, de, s);
+  R* dw = ws.get<R>((size_t) n);
+  R* dz = ws.get<R>((size_t) n * k);
   const int r = tridiag_solver_device<R>(n, nb, dd, de, dw, dz, n, begin, end, s, nullptr);
   DLAF_HIP_CHECK(hipMemcpyAsync(w, dw, (size_t) n * sizeof(R), hipMemcpyDeviceToHost, s));
   if (k > 0)
     DLAF_HIP_CHECK(hipMemcpy2DAsync(z, (size_t) ldz * sizeof(R), dz, (size_t) n * sizeof(R), (size_t) n * sizeof(R), (size_t) k,
                                     hipMemcpyDeviceToHost, s));
   DLAF_HIP_CHECK(hipStreamSynchronize(s));
-  for (R* p : {dd, de, dw, dz})
-    DLAF_HIP_CHECK(pool_free(p));
+  ws.release();
   DLAF_HIP_CHECK(hipStreamDestroy(s));
   return r;
 }

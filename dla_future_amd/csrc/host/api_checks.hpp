@@ -1,0 +1,123 @@
+// api_checks.hpp -- the argument checks of the C API (c_api.cpp, c_api_host.cpp, c_api_device.cpp) in one vocabulary.
+// Host only: no HIP header, usable from a plain g++ program (tests/api_checks/sweep.cpp sweeps the predicates against a
+// brute-force model).  The predicates answer; the require_* helpers terminate through fatal() (runtime.cpp) before
+// anything touches the GPU, the way upstream's asserts do.  who names the routine in a message; nullptr: no prefix.
+#pragma once
+#include <cstring>
+#include <initializer_list>
+#include <string>
+
+#include <dlaf_c/desc.h>
+
+namespace dlaf_mi355x {
+
+[[noreturn]] void fatal(const char* fmt, ...);
+
+#pragma GCC visibility push(hidden)  // helpers of the C API's own files: the library exports none of them
+
+// ---- letters (NUL is in no set)
+inline bool in_set(char c, const char* set) {
+  return c != 0 && std::strchr(set, c) != nullptr;
+}
+inline bool is_uplo(char c) { return in_set(c, "LlUu"); }
+inline bool is_lower(char c) { return in_set(c, "Ll"); }
+inline bool is_upper(char c) { return in_set(c, "Uu"); }
+inline bool is_side(char c) { return in_set(c, "LlRr"); }
+inline bool is_left(char c) { return in_set(c, "Ll"); }
+inline bool is_op(char c) { return in_set(c, "NnTtCc"); }
+inline bool is_diag(char c) { return in_set(c, "NnUu"); }
+
+// ---- source process inside the grid (GridT: anything with nprow, npcol; the library passes its Grid)
+inline bool source_in_grid(int nprow, int npcol, int isrc, int jsrc) {
+  return isrc >= 0 && isrc < nprow && jsrc >= 0 && jsrc < npcol;
+}
+template <class GridT>
+bool source_in_grid(const GridT& g, const DLAF_descriptor& d) {
+  return source_in_grid(g.nprow, g.npcol, d.isrc, d.jsrc);
+}
+template <class GridT>
+void require_sources(const char* who, const GridT& g, std::initializer_list<const DLAF_descriptor*> descs) {
+  for (const DLAF_descriptor* d : descs)
+    if (!source_in_grid(g, *d))
+      fatal("[dlaf_mi355x] %s%ssource rank (%d,%d) outside the %d x %d grid\n", who ? who : "", who ? ": " : "", d->isrc,
+            d->jsrc, g.nprow, g.npcol);
+}
+
+// ---- descriptors
+inline void require_uplo(char uplo) {
+  if (!is_uplo(uplo))
+    fatal("[dlaf_mi355x] uplo must be 'L' or 'U', got '%c'\n", uplo);
+}
+// square matrix, square blocks, no offsets: the preconditions of dlaf::cholesky_factorization
+// (include/dlaf/factorization/cholesky.h:39-79) and of its C wrapper (src/c_api/factorization/cholesky.h:37-38), which
+// gen_to_std, the inverses, reduction_to_band (reduction_to_band.h:103-106), band_to_tridiagonal
+// (band_to_tridiag.h:76-80) and the eigensolvers share
+inline void require_square_desc(const DLAF_descriptor& d) {
+  if (d.i != 0 || d.j != 0)
+    fatal("[dlaf_mi355x] sub-matrices are not supported: i = %d, j = %d must be 0\n", d.i, d.j);
+  if (d.m != d.n)
+    fatal("[dlaf_mi355x] Cholesky needs a square matrix: %d x %d\n", d.m, d.n);
+  if (d.mb != d.nb || d.nb < 1)
+    fatal("[dlaf_mi355x] Cholesky needs square blocks: %d x %d\n", d.mb, d.nb);
+  if (d.m < 0)
+    fatal("[dlaf_mi355x] negative matrix size %d\n", d.m);
+}
+// the eigensolvers' B and Z: described like A, without offsets (eigensolver.h:44-45 upstream)
+inline void require_like(const char* who, const DLAF_descriptor& da, std::initializer_list<const DLAF_descriptor*> others) {
+  for (const DLAF_descriptor* d : others) {
+    if (d->i != 0 || d->j != 0)
+      fatal("[dlaf_mi355x] %s: sub-matrix offsets must be 0\n", who);
+    if (d->m != da.m || d->n != da.n || d->mb != da.mb || d->nb != da.nb)
+      fatal("[dlaf_mi355x] %s: B and Z must have A's size %d x %d and block %d x %d\n", who, da.m, da.n, da.mb, da.nb);
+  }
+}
+// reduction_to_band.h:108-109, band_to_tridiag.h:78-80
+inline void require_band(const char* who, int band, int nb) {
+  if (band < 2 || nb % band != 0)
+    fatal("[dlaf_mi355x] %s: band_size %d must be >= 2 and divide the block size %d\n", who, band, nb);
+}
+
+// ---- the prologue of a ScaLAPACK argument list: every operand as (name letter, desc, row offset, column offset)
+struct ScalapackOperand {
+  char name;
+  const int* desc;
+  int i, j;
+};
+// "ia, ja, ib, jb": the offsets the call takes
+inline std::string offset_names(std::initializer_list<ScalapackOperand> ops) {
+  std::string s;
+  for (const ScalapackOperand& o : ops) {
+    const char l = (char) (o.name | 0x20);
+    s += std::string(s.empty() ? "" : ", ") + 'i' + l + ", j" + l;
+  }
+  return s;
+}
+// "A", "A and B", "A, B and Z"
+inline std::string operand_names(std::initializer_list<ScalapackOperand> ops) {
+  std::string s;
+  size_t k = 0;
+  for (const ScalapackOperand& o : ops)
+    s += std::string(k++ == 0 ? "" : k == ops.size() ? " and " : ", ") + o.name;
+  return s;
+}
+// dtype 1 (src/c_api/factorization/cholesky.h:65-75), all offsets 1, one context; returns the context
+inline int require_scalapack_args(std::initializer_list<ScalapackOperand> ops, const char* who = nullptr) {
+  const std::string pre = who ? std::string(who) + ": " : "";
+  for (const ScalapackOperand& o : ops)
+    if (o.desc[0] != 1)
+      fatal("[dlaf_mi355x] %sdesc[0] (dtype) must be 1\n", pre.c_str());
+  for (const ScalapackOperand& o : ops)
+    if (o.i != 1 || o.j != 1)
+      fatal("[dlaf_mi355x] %s%s must be 1\n", pre.c_str(), offset_names(ops).c_str());
+  const int ctx = ops.begin()->desc[1];
+  std::string all;
+  for (const ScalapackOperand& o : ops)
+    all += (all.empty() ? "" : ", ") + std::to_string(o.desc[1]);
+  for (const ScalapackOperand& o : ops)
+    if (o.desc[1] != ctx)
+      fatal("[dlaf_mi355x] %s%s live on different contexts (%s)\n", pre.c_str(), operand_names(ops).c_str(), all.c_str());
+  return ctx;
+}
+
+#pragma GCC visibility pop
+}  // namespace dlaf_mi355x

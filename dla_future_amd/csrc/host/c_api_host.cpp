@@ -1,0 +1,817 @@
+// c_api_host.cpp -- the extern "C" surface, part 2 of 3 (c_api_internal.hpp has the map): the entries that take
+// descriptors or ScaLAPACK argument lists over host memory -- triangular solver and multiplication, Hermitian
+// multiplication, p?potrs, generalized to standard, the inverses, the norms, reduction to band and the eigensolver
+// stages and drivers (include/dlaf_c/eigensolver/*.h as upstream, include/dlaf_mi355x/dlaf_mi355x.h).  Every argument
+// is judged (api_checks.hpp) before anything touches the GPU.
+#define DLAF_MI355X_NO_MPI 1  // as in c_api.cpp: no <mpi.h> in the core
+#include <algorithm>
+#include <complex>
+#include <cstring>
+
+#include <dlaf_c/eigensolver/eigensolver.h>
+#include <dlaf_c/eigensolver/gen_eigensolver.h>
+#include <dlaf_mi355x/dlaf_mi355x.h>
+
+#include "../device/tridiag_api.hpp"
+#include "c_api_internal.hpp"
+#include "eigensolver.hpp"
+#include "red2band.hpp"
+#include "tile_matrix.hpp"
+
+using namespace dlaf_mi355x;
+
+namespace {
+// Preconditions of the triangular solver and multiplication through descriptors (who names the routine in the
+// messages); they terminate before the GPU is touched.  Returns the grid.
+Grid& triangular_checks(const char* who, int ctx, char side, char uplo, char op, char diag, const DLAF_descriptor& da,
+                        const DLAF_descriptor& db) {
+  if (!is_side(side) || !is_uplo(uplo) || !is_op(op) || !is_diag(diag))
+    fatal("[dlaf_mi355x] %s: bad side/uplo/op/diag '%c' '%c' '%c' '%c'\n", who, side, uplo, op, diag);
+  if (da.i != 0 || da.j != 0 || db.i != 0 || db.j != 0)
+    fatal("[dlaf_mi355x] sub-matrices are not supported: offsets must be 0\n");
+  // preconditions of triangular.h:43-48, :57 / :93-98: A square with square blocks, op(A) and B multipliable
+  if (da.m != da.n || da.mb != da.nb || da.nb < 1)
+    fatal("[dlaf_mi355x] %s: A must be square with square blocks (%d x %d, %d x %d)\n", who, da.m, da.n, da.mb, da.nb);
+  const bool left = is_left(side);
+  if (db.m < 0 || db.n < 0 || da.m != (left ? db.m : db.n))
+    fatal("[dlaf_mi355x] %s: A is %d x %d, B is %d x %d (side %c)\n", who, da.m, da.n, db.m, db.n, side);
+  // multipliable (util_matrix.h:123-143): B's block along the triangular dimension is A's; the other one is free
+  // (the device tiles stay square: the free dimension is re-cut locally, tile_matrix.hpp create_rhs)
+  if ((left ? db.mb : db.nb) != da.nb || db.mb < 1 || db.nb < 1)
+    fatal("[dlaf_mi355x] %s: B's blocks (%d x %d) do not match A's (%d x %d) for side %c\n", who, db.mb, db.nb, da.mb,
+          da.nb, side);
+  Grid& g = grid_from_context(ctx);
+  require_sources(nullptr, g, {&da, &db});
+  if (db.m > 0 && db.n > 0 && (left ? (da.isrc != db.isrc) : (da.jsrc != db.jsrc)))
+    fatal("[dlaf_mi355x] %s: A and B must share the source process along the triangular dimension\n", who);
+  return g;
+}
+
+// The two routines over a triangular A, B = the m x n matrix they overwrite: dlaf::triangular_solver
+// (include/dlaf/solver/triangular.h:41-177) and dlaf::triangular_multiplication
+// (include/dlaf/multiplication/triangular.h), B = alpha op(A) B (side L) / alpha B op(A) (side R).  Same arguments,
+// same preconditions; who names the routine in the messages.
+template <class HT>
+struct TriangularOp {
+  using DT = typename DevType<HT>::type;
+  const char* who;
+  int (*host)(Grid*, char, char, char, char, DT, const DT*, long, int, int, DT*, long, long, long, int, int, int, int);
+};
+template <class HT>
+constexpr TriangularOp<HT> kTrsm{"triangular solver", &triangular_solver_host<typename DevType<HT>::type>};
+template <class HT>
+constexpr TriangularOp<HT> kTrmm{"triangular multiplication",
+                                 &triangular_multiplication_host<typename DevType<HT>::type>};
+
+// through descriptors
+template <class HT>
+int triangular_c(const TriangularOp<HT>& op_, int ctx, char side, char uplo, char op, char diag, const HT* alpha,
+                 const HT* a, const DLAF_descriptor& da, HT* b, const DLAF_descriptor& db) {
+  using DT = typename DevType<HT>::type;
+  Grid& g = triangular_checks(op_.who, ctx, side, uplo, op, diag, da, db);
+  const bool left = is_left(side);
+  DT al;
+  std::memcpy(&al, alpha, sizeof(DT));
+  return op_.host(&g, side, uplo, op, diag, al, reinterpret_cast<const DT*>(a), da.ld, da.isrc, da.jsrc,
+                  reinterpret_cast<DT*>(b), db.ld, db.m, db.n, da.nb, db.isrc, db.jsrc, left ? db.nb : db.mb);
+}
+
+// ScaLAPACK p?trsm / p?trmm argument list
+template <class HT>
+void pxtriangular(const TriangularOp<HT>& op_, char side, char uplo, char op, char diag, int m, int n, const HT* alpha,
+                  const HT* a, int ia, int ja, const int desca[9], HT* b, int ib, int jb, const int descb[9]) {
+  const int ctx = require_scalapack_args({{'A', desca, ia, ja}, {'B', descb, ib, jb}});
+  const int na = is_left(side) ? m : n;
+  const DLAF_descriptor da = make_dlaf_descriptor(na, na, ia, ja, desca);
+  const DLAF_descriptor db = make_dlaf_descriptor(m, n, ib, jb, descb);
+  (void) triangular_c<HT>(op_, ctx, side, uplo, op, diag, alpha, a, da, b, db);
+}
+
+// Preconditions of dlaf::hermitian_multiplication (include/dlaf/multiplication/hermitian.h) through descriptors, and
+// this build's own (the solver's); they terminate before the GPU is touched.  Returns the grid.
+Grid& hermitian_checks(int ctx, char side, char uplo, const DLAF_descriptor& da, const DLAF_descriptor& db,
+                       const DLAF_descriptor& dc) {
+  const char* who = "hermitian multiplication";
+  if (!is_side(side) || !is_uplo(uplo))
+    fatal("[dlaf_mi355x] %s: bad side/uplo '%c' '%c'\n", who, side, uplo);
+  if (da.i != 0 || da.j != 0 || db.i != 0 || db.j != 0 || dc.i != 0 || dc.j != 0)
+    fatal("[dlaf_mi355x] %s: sub-matrices are not supported: offsets must be 0\n", who);
+  if (da.m != da.n || da.mb != da.nb || da.nb < 1)
+    fatal("[dlaf_mi355x] %s: A must be square with square blocks (%d x %d, %d x %d)\n", who, da.m, da.n, da.mb, da.nb);
+  const bool left = is_left(side);
+  if (dc.m < 0 || dc.n < 0 || db.m != dc.m || db.n != dc.n || db.mb != dc.mb || db.nb != dc.nb)
+    fatal("[dlaf_mi355x] %s: B (%d x %d, blocks %d x %d) and C (%d x %d, blocks %d x %d) differ\n", who, db.m, db.n, db.mb,
+          db.nb, dc.m, dc.n, dc.mb, dc.nb);
+  if (da.m != (left ? dc.m : dc.n))
+    fatal("[dlaf_mi355x] %s: A is %d x %d, B and C are %d x %d (side %c)\n", who, da.m, da.n, dc.m, dc.n, side);
+  if ((left ? dc.mb : dc.nb) != da.nb || dc.mb < 1 || dc.nb < 1)
+    fatal("[dlaf_mi355x] %s: the blocks of B and C (%d x %d) do not match A's (%d x %d) for side %c\n", who, dc.mb, dc.nb,
+          da.mb, da.nb, side);
+  Grid& g = grid_from_context(ctx);
+  require_sources(who, g, {&da, &db, &dc});
+  if (db.isrc != dc.isrc || db.jsrc != dc.jsrc)
+    fatal("[dlaf_mi355x] %s: B and C must share the source process ((%d,%d) vs (%d,%d))\n", who, db.isrc, db.jsrc,
+          dc.isrc, dc.jsrc);
+  if (dc.m > 0 && dc.n > 0 && (left ? (da.isrc != dc.isrc) : (da.jsrc != dc.jsrc)))
+    fatal("[dlaf_mi355x] %s: A must share the source process of B and C along A's dimension\n", who);
+  return g;
+}
+
+// dlaf::hermitian_multiplication through descriptors: C = beta C + alpha A B (side L) / beta C + alpha B A (side R)
+template <class HT>
+int hermitian_multiplication_c(int ctx, char side, char uplo, const HT* alpha, const HT* a, const DLAF_descriptor& da,
+                               const HT* b, const DLAF_descriptor& db, const HT* beta, HT* c, const DLAF_descriptor& dc) {
+  using DT = typename DevType<HT>::type;
+  Grid& g = hermitian_checks(ctx, side, uplo, da, db, dc);
+  const bool left = is_left(side);
+  DT al, be;
+  std::memcpy(&al, alpha, sizeof(DT));
+  std::memcpy(&be, beta, sizeof(DT));
+  return hermitian_multiplication_host<DT>(&g, side, uplo, al, reinterpret_cast<const DT*>(a), da.ld, da.isrc, da.jsrc,
+                                           reinterpret_cast<const DT*>(b), db.ld, be, reinterpret_cast<DT*>(c), dc.ld, dc.m,
+                                           dc.n, da.nb, dc.isrc, dc.jsrc, left ? dc.nb : dc.mb);
+}
+
+// ScaLAPACK p?symm / p?hemm argument list
+template <class HT>
+void pxhemm(char side, char uplo, int m, int n, const HT* alpha, const HT* a, int ia, int ja, const int desca[9],
+            const HT* b, int ib, int jb, const int descb[9], const HT* beta, HT* c, int ic, int jc, const int descc[9]) {
+  const int ctx = require_scalapack_args({{'A', desca, ia, ja}, {'B', descb, ib, jb}, {'C', descc, ic, jc}},
+                                         "hermitian multiplication");
+  const int na = is_left(side) ? m : n;
+  const DLAF_descriptor da = make_dlaf_descriptor(na, na, ia, ja, desca);
+  const DLAF_descriptor db = make_dlaf_descriptor(m, n, ib, jb, descb);
+  const DLAF_descriptor dc = make_dlaf_descriptor(m, n, ic, jc, descc);
+  (void) hermitian_multiplication_c<HT>(ctx, side, uplo, alpha, a, da, b, db, beta, c, dc);
+}
+
+// ScaLAPACK p?potrs: solve A X = B with the factor p?potrf left in a (uplo L: L L^H, uplo U: U^H U)
+template <class HT>
+void pxpotrs(char uplo, int n, int nrhs, const HT* a, int ia, int ja, const int desca[9], HT* b, int ib, int jb,
+             const int descb[9], int* info) {
+  const HT one(1);
+  const bool lower = is_lower(uplo);
+  pxtriangular<HT>(kTrsm<HT>, 'L', uplo, lower ? 'N' : 'C', 'N', n, nrhs, &one, a, ia, ja, desca, b, ib, jb, descb);
+  pxtriangular<HT>(kTrsm<HT>, 'L', uplo, lower ? 'C' : 'N', 'N', n, nrhs, &one, a, ia, ja, desca, b, ib, jb, descb);
+  if (info)
+    *info = 0;
+}
+
+// dlaf::eigensolver::internal::generalized_to_standard (include/dlaf/eigensolver/gen_to_std.h:50,:101) through
+// descriptors: preconditions of gen_to_std.h:52-60 / :103-113 (square, square blocks, same size and blocks)
+template <class HT>
+int gen_to_std_c(int ctx, char uplo, HT* a, const DLAF_descriptor& da, const HT* b, const DLAF_descriptor& db) {
+  using DT = typename DevType<HT>::type;
+  require_square_desc(da);
+  require_square_desc(db);
+  require_uplo(uplo);
+  if (da.m != db.m || da.nb != db.nb || da.isrc != db.isrc || da.jsrc != db.jsrc)
+    fatal("[dlaf_mi355x] gen_to_std: A (%d, block %d, source %d,%d) and B (%d, block %d, source %d,%d) must be "
+          "distributed alike\n", da.m, da.nb, da.isrc, da.jsrc, db.m, db.nb, db.isrc, db.jsrc);
+  Grid& g = grid_from_context(ctx);
+  require_sources(nullptr, g, {&da});
+  return gen_to_std_host<DT>(&g, uplo, reinterpret_cast<DT*>(a), da.ld, reinterpret_cast<const DT*>(b), db.ld, da.m,
+                             da.nb, da.isrc, da.jsrc);
+}
+
+// ScaLAPACK p?sygst / p?hegst argument list (ibtype 1 only: inv(L) A inv(L^H) / inv(U^H) A inv(U))
+template <class HT, class RT>
+void pxhegst(int ibtype, char uplo, int n, HT* a, int ia, int ja, const int desca[9], const HT* b, int ib, int jb,
+             const int descb[9], RT* scale, int* info) {
+  if (ibtype != 1)
+    fatal("[dlaf_mi355x] p?hegst: only ibtype = 1 is built (got %d)\n", ibtype);
+  const int ctx = require_scalapack_args({{'A', desca, ia, ja}, {'B', descb, ib, jb}});
+  const int r = gen_to_std_c<HT>(ctx, uplo, a, make_dlaf_descriptor(n, n, ia, ja, desca), b,
+                                 make_dlaf_descriptor(n, n, ib, jb, descb));
+  if (scale)
+    *scale = RT(1);
+  if (info)
+    *info = r;
+}
+
+// dlaf::triangular_inverse / dlaf::inverse_from_cholesky_factor through descriptors (inverse.cpp)
+template <class HT>
+int inverse_c(int ctx, char uplo, char diag, bool product, HT* a, const DLAF_descriptor& da) {
+  using DT = typename DevType<HT>::type;
+  require_square_desc(da);
+  require_uplo(uplo);
+  Grid& g = grid_from_context(ctx);
+  require_sources(nullptr, g, {&da});
+  if (product)
+    return inverse_from_cholesky_factor_host<DT>(&g, uplo, reinterpret_cast<DT*>(a), da.ld, da.m, da.nb, da.isrc,
+                                                 da.jsrc);
+  return triangular_inverse_host<DT>(&g, uplo, diag, reinterpret_cast<DT*>(a), da.ld, da.m, da.nb, da.isrc, da.jsrc);
+}
+
+// ScaLAPACK p?trtri / p?potri argument lists
+template <class HT>
+void pxinverse(char uplo, char diag, bool product, int n, HT* a, int ia, int ja, const int desca[9], int* info) {
+  const int ctx = require_scalapack_args({{'A', desca, ia, ja}});
+  const int r = inverse_c<HT>(ctx, uplo, diag, product, a, make_dlaf_descriptor(n, n, ia, ja, desca));
+  if (info)
+    *info = r;
+}
+
+// dlaf::auxiliary norms through descriptors (norm.cpp): structure 'G' general, 'H' Hermitian / symmetric, 'T' triangular.
+// Every argument is judged before anything touches the GPU; the codes are the header's.
+template <class HT>
+int norm_c(int ctx, char norm, char structure, char uplo, char diag, const HT* a, const DLAF_descriptor& da,
+           double* value) {
+  using DT = typename DevType<HT>::type;
+  if (!value)
+    return -6;
+  if (norm_kind(norm) == 0)
+    return -1;
+  if (structure != 'G' && !is_uplo(uplo))
+    return -2;
+  if (structure == 'T' && !is_diag(diag))
+    return -3;
+  if (da.i != 0 || da.j != 0 || da.mb != da.nb || da.nb < 1 || da.m < 0 || da.n < 0 ||
+      (structure != 'G' && da.m != da.n))
+    return -4;
+  Grid* g = find_grid(ctx);
+  if (!g)
+    return -6;
+  if (!source_in_grid(*g, da))
+    return -5;
+  if (da.m == 0 || da.n == 0) {
+    *value = 0.0;
+    return 0;
+  }
+  const DT* ad = reinterpret_cast<const DT*>(a);
+  *value = structure == 'G' ? general_norm_host<DT>(g, norm, ad, da.ld, da.m, da.n, da.nb, da.isrc, da.jsrc)
+                            : structured_norm_host<DT>(g, norm, structure, uplo, diag, ad, da.ld, da.m, da.nb, da.isrc,
+                                                       da.jsrc);
+  return 0;
+}
+
+// ScaLAPACK p?lange / p?lansy / p?lanhe / p?lantr argument lists (without work); the value is returned
+template <class HT>
+double pxnorm(char norm, char structure, char uplo, char diag, int m, int n, const HT* a, int ia, int ja,
+              const int desca[9]) {
+  const int ctx = require_scalapack_args({{'A', desca, ia, ja}});
+  double v = 0.0;
+  const int r = norm_c<HT>(ctx, norm, structure, uplo, diag, a, make_dlaf_descriptor(m, n, ia, ja, desca), &v);
+  if (r != 0)
+    fatal("[dlaf_mi355x] p?lan*: bad argument (code %d; norm '%c', uplo '%c', diag '%c')\n", r, norm, uplo, diag);
+  return v;
+}
+
+// dlaf::eigensolver::internal::reduction_to_band (include/dlaf/eigensolver/reduction_to_band.h:101-122) through the
+// reference's descriptor conventions
+template <class HT>
+int red2band_c(int ctx, HT* a, const DLAF_descriptor& da, int band, HT* taus) {
+  using DT = typename DevType<HT>::type;
+  require_square_desc(da);
+  Grid& g = grid_from_context(ctx);
+  require_sources(nullptr, g, {&da});
+  require_band("reduction_to_band", band, da.nb);
+  return reduction_to_band_host<DT>(&g, reinterpret_cast<DT*>(a), da.ld, da.m, da.nb, da.isrc, da.jsrc, band,
+                                    reinterpret_cast<DT*>(taus));
+}
+
+template <class HT>
+int bt_red2band_c(int ctx, int band, HT* c, const DLAF_descriptor& dc, const HT* v, const DLAF_descriptor& dv,
+                  const HT* taus) {
+  using DT = typename DevType<HT>::type;
+  require_square_desc(dv);
+  Grid& g = grid_from_context(ctx);
+  if (dc.i != 0 || dc.j != 0 || dc.mb != dc.nb || dc.nb != dv.nb || dc.m != dv.m || dc.isrc != dv.isrc)
+    fatal("[dlaf_mi355x] bt_reduction_to_band: C (%d x %d, block %d x %d, row source %d) must have V's block size %d, "
+          "row count %d and row source %d, and no offsets\n", dc.m, dc.n, dc.mb, dc.nb, dc.isrc, dv.nb, dv.m, dv.isrc);
+  require_sources(nullptr, g, {&dc, &dv});  // (C's row source is V's by now)
+  require_band("bt_reduction_to_band", band, dv.nb);
+  return bt_reduction_to_band_host<DT>(&g, band, reinterpret_cast<DT*>(c), dc.ld, dc.n, dc.jsrc,
+                                       reinterpret_cast<const DT*>(v), dv.ld, dv.m, dv.nb, dv.isrc, dv.jsrc,
+                                       reinterpret_cast<const DT*>(taus));
+}
+
+// ---- the eigensolver stages and drivers ------------------------------------------------------
+template <class HT>
+int band_to_tridiag_c(int ctx, const HT* a, const DLAF_descriptor& da, int band, typename RealOf<HT>::type* d,
+                      typename RealOf<HT>::type* e, HT* v, int ldv) {
+  using DT = typename DevType<HT>::type;
+  require_square_desc(da);
+  Grid& g = grid_from_context(ctx);
+  require_sources(nullptr, g, {&da});
+  require_band("band_to_tridiagonal", band, da.nb);
+  if (ldv < std::max(1, da.m))
+    fatal("[dlaf_mi355x] band_to_tridiagonal: ldv = %d < n = %d\n", ldv, da.m);
+  return band_to_tridiag_host<DT>(&g, reinterpret_cast<const DT*>(a), da.ld, da.m, da.nb, da.isrc, da.jsrc, band, d, e,
+                                  reinterpret_cast<DT*>(v), ldv);
+}
+
+// Eigensolver entry (src/c_api/eigensolver/eigensolver.h:33-75): descriptors of A and of the eigenvector matrix;
+// [begin, end): the 0-based range of eigenvalue indices whose eigenvectors are wanted ([0, n): the full entries)
+template <class HT>
+int eigensolver_c(int ctx, char uplo, HT* a, const DLAF_descriptor& da, typename RealOf<HT>::type* w, HT* z,
+                  const DLAF_descriptor& dz, long begin, long end) {
+  using DT = typename DevType<HT>::type;
+  check_eigenvalues_index("eigensolver", da.m, begin, end);
+  require_square_desc(da);
+  Grid& g = grid_from_context(ctx);
+  require_like("eigensolver", da, {&dz});
+  require_sources(nullptr, g, {&da, &dz});
+  return hermitian_eigensolver_host<DT>(&g, uplo, reinterpret_cast<DT*>(a), da.ld, da.m, da.nb, da.isrc, da.jsrc, w,
+                                        reinterpret_cast<DT*>(z), dz.ld, dz.isrc, dz.jsrc, begin, end);
+}
+
+template <class HT>
+int gen_eigensolver_c(int ctx, char uplo, HT* a, const DLAF_descriptor& da, HT* b, const DLAF_descriptor& db,
+                      typename RealOf<HT>::type* w, HT* z, const DLAF_descriptor& dz, bool factorized, long begin,
+                      long end) {
+  using DT = typename DevType<HT>::type;
+  check_eigenvalues_index("gen_eigensolver", da.m, begin, end);
+  require_square_desc(da);
+  require_square_desc(db);
+  Grid& g = grid_from_context(ctx);
+  require_like("gen_eigensolver", da, {&db, &dz});
+  require_sources(nullptr, g, {&da, &db, &dz});
+  return hermitian_gen_eigensolver_host<DT>(&g, uplo, reinterpret_cast<DT*>(a), da.ld, reinterpret_cast<DT*>(b), db.ld,
+                                            da.m, da.nb, da.isrc, da.jsrc, db.isrc, db.jsrc, w, reinterpret_cast<DT*>(z),
+                                            dz.ld, dz.isrc, dz.jsrc, factorized, begin, end);
+}
+
+// p?syevd / p?heevd and p?sygvd / p?hegvd argument lists (src/c_api/eigensolver/eigensolver.h:79-124), descb == nullptr
+// for the standard problem; il, iu: the 1-based inclusive eigenvalue index range of p?syevx (1, n: the full entries;
+// 1, 0: the empty range)
+template <class HT>
+void pxhegvd(char uplo, int n, HT* a, int ia, int ja, const int desca[9], HT* b, int ib, int jb, const int descb[9],
+             typename RealOf<HT>::type* w, HT* z, int iz, int jz, const int descz[9], long il, long iu, int* info,
+             bool factorized) {
+  const int ctx = descb ? require_scalapack_args({{'A', desca, ia, ja}, {'B', descb, ib, jb}, {'Z', descz, iz, jz}})
+                        : require_scalapack_args({{'A', desca, ia, ja}, {'Z', descz, iz, jz}});
+  const DLAF_descriptor da = make_dlaf_descriptor(n, n, ia, ja, desca), dz = make_dlaf_descriptor(n, n, iz, jz, descz);
+  const int r = descb ? gen_eigensolver_c<HT>(ctx, uplo, a, da, b, make_dlaf_descriptor(n, n, ib, jb, descb), w, z, dz,
+                                              factorized, il - 1, iu)
+                      : eigensolver_c<HT>(ctx, uplo, a, da, w, z, dz, il - 1, iu);
+  if (info)
+    *info = r;
+}
+
+// ---- eigenvalues only, and the eigenvalue range given by value ----------------------------
+template <class HT>
+int eigenvalues_c(int ctx, char uplo, const HT* a, const DLAF_descriptor& da, typename RealOf<HT>::type* w, long begin,
+                  long end) {
+  using DT = typename DevType<HT>::type;
+  check_eigenvalues_index("eigenvalues", da.m, begin, end);
+  require_square_desc(da);
+  Grid& g = grid_from_context(ctx);
+  require_sources(nullptr, g, {&da});
+  return hermitian_eigenvalues_host<DT>(&g, uplo, reinterpret_cast<const DT*>(a), da.ld, da.m, da.nb, da.isrc, da.jsrc, w,
+                                        begin, end);
+}
+
+template <class HT>
+int gen_eigenvalues_c(int ctx, char uplo, const HT* a, const DLAF_descriptor& da, HT* b, const DLAF_descriptor& db,
+                      typename RealOf<HT>::type* w, bool factorized, long begin, long end) {
+  using DT = typename DevType<HT>::type;
+  check_eigenvalues_index("gen_eigenvalues", da.m, begin, end);
+  require_square_desc(da);
+  require_square_desc(db);
+  Grid& g = grid_from_context(ctx);
+  require_like("gen_eigenvalues", da, {&db});
+  require_sources(nullptr, g, {&da, &db});
+  return hermitian_gen_eigenvalues_host<DT>(&g, uplo, reinterpret_cast<const DT*>(a), da.ld, reinterpret_cast<DT*>(b),
+                                            db.ld, da.m, da.nb, da.isrc, da.jsrc, db.isrc, db.jsrc, w, factorized, begin,
+                                            end);
+}
+
+template <class HT>
+int eigensolver_by_value_c(int ctx, char uplo, HT* a, const DLAF_descriptor& da, typename RealOf<HT>::type* w, HT* z,
+                           const DLAF_descriptor& dz, typename RealOf<HT>::type vl, typename RealOf<HT>::type vu,
+                           long* begin, long* end) {
+  using DT = typename DevType<HT>::type;
+  if (!begin || !end)
+    fatal("[dlaf_mi355x] eigensolver: the by-value entries return their index range: begin, end must not be null\n");
+  require_square_desc(da);
+  Grid& g = grid_from_context(ctx);
+  require_like("eigensolver", da, {&dz});
+  require_sources(nullptr, g, {&da, &dz});
+  return hermitian_eigensolver_by_value_host<DT>(&g, uplo, reinterpret_cast<DT*>(a), da.ld, da.m, da.nb, da.isrc, da.jsrc,
+                                                 w, reinterpret_cast<DT*>(z), dz.ld, dz.isrc, dz.jsrc, vl, vu, begin, end);
+}
+
+template <class HT>
+int gen_eigensolver_by_value_c(int ctx, char uplo, HT* a, const DLAF_descriptor& da, HT* b, const DLAF_descriptor& db,
+                               typename RealOf<HT>::type* w, HT* z, const DLAF_descriptor& dz, bool factorized,
+                               typename RealOf<HT>::type vl, typename RealOf<HT>::type vu, long* begin, long* end) {
+  using DT = typename DevType<HT>::type;
+  if (!begin || !end)
+    fatal("[dlaf_mi355x] gen_eigensolver: the by-value entries return their index range: begin, end must not be null\n");
+  require_square_desc(da);
+  require_square_desc(db);
+  Grid& g = grid_from_context(ctx);
+  require_like("gen_eigensolver", da, {&db, &dz});
+  require_sources(nullptr, g, {&da, &db, &dz});
+  return hermitian_gen_eigensolver_by_value_host<DT>(&g, uplo, reinterpret_cast<DT*>(a), da.ld, reinterpret_cast<DT*>(b),
+                                                     db.ld, da.m, da.nb, da.isrc, da.jsrc, db.isrc, db.jsrc, w,
+                                                     reinterpret_cast<DT*>(z), dz.ld, dz.isrc, dz.jsrc, factorized, vl, vu,
+                                                     begin, end);
+}
+
+// the ScaLAPACK-like argument lists: descb == nullptr for the standard problem
+template <class HT>
+void pxhegvd_eigenvalues(char uplo, int n, const HT* a, int ia, int ja, const int desca[9], HT* b, int ib, int jb,
+                         const int descb[9], typename RealOf<HT>::type* w, long il, long iu, int* info, bool factorized) {
+  const int ctx = descb ? require_scalapack_args({{'A', desca, ia, ja}, {'B', descb, ib, jb}})
+                        : require_scalapack_args({{'A', desca, ia, ja}});
+  const DLAF_descriptor da = make_dlaf_descriptor(n, n, ia, ja, desca);
+  const int r = descb ? gen_eigenvalues_c<HT>(ctx, uplo, a, da, b, make_dlaf_descriptor(n, n, ib, jb, descb), w,
+                                              factorized, il - 1, iu)
+                      : eigenvalues_c<HT>(ctx, uplo, a, da, w, il - 1, iu);
+  if (info)
+    *info = r;
+}
+template <class HT>
+void pxhegvd_by_value(char uplo, int n, HT* a, int ia, int ja, const int desca[9], HT* b, int ib, int jb,
+                      const int descb[9], typename RealOf<HT>::type* w, HT* z, int iz, int jz, const int descz[9],
+                      typename RealOf<HT>::type vl, typename RealOf<HT>::type vu, int* m, int* info, bool factorized) {
+  long begin = 0, end = 0;
+  const int ctx = descb ? require_scalapack_args({{'A', desca, ia, ja}, {'B', descb, ib, jb}, {'Z', descz, iz, jz}})
+                        : require_scalapack_args({{'A', desca, ia, ja}, {'Z', descz, iz, jz}});
+  const DLAF_descriptor da = make_dlaf_descriptor(n, n, ia, ja, desca), dz = make_dlaf_descriptor(n, n, iz, jz, descz);
+  const int r = descb ? gen_eigensolver_by_value_c<HT>(ctx, uplo, a, da, b, make_dlaf_descriptor(n, n, ib, jb, descb), w,
+                                                       z, dz, factorized, vl, vu, &begin, &end)
+                      : eigensolver_by_value_c<HT>(ctx, uplo, a, da, w, z, dz, vl, vu, &begin, &end);
+  if (m)
+    *m = (int) (end - begin);
+  if (info)
+    *info = r;
+}
+}  // namespace
+
+// ===================================================================================================== entries
+extern "C" {
+
+// NAME / PNAME / OP: triangular_solver / trsm / kTrsm, triangular_multiplication / trmm / kTrmm
+#define DLAF_MI355X_TRIANGULAR_ENTRY(S, HT, CT, NAME, PNAME, OP)                                                 \
+  int dlaf_mi355x_##NAME##_##S(int ctx, char side, char uplo, char op, char diag, const CT* alpha, const CT* a,   \
+                               DLAF_descriptor desca, CT* b, DLAF_descriptor descb) noexcept {                   \
+    return triangular_c<HT>(OP<HT>, ctx, side, uplo, op, diag, reinterpret_cast<const HT*>(alpha),               \
+                            reinterpret_cast<const HT*>(a), desca, reinterpret_cast<HT*>(b), descb);             \
+  }                                                                                                             \
+  void dlaf_mi355x_p##S##PNAME(char side, char uplo, char op, char diag, int m, int n, const CT* alpha, const CT* a, \
+                               int ia, int ja, const int desca[9], CT* b, int ib, int jb,                        \
+                               const int descb[9]) noexcept {                                                   \
+    pxtriangular<HT>(OP<HT>, side, uplo, op, diag, m, n, reinterpret_cast<const HT*>(alpha),                     \
+                     reinterpret_cast<const HT*>(a), ia, ja, desca, reinterpret_cast<HT*>(b), ib, jb, descb);    \
+  }
+#define DLAF_MI355X_TRIANGULAR_ENTRIES(NAME, PNAME, OP)                                  \
+  DLAF_MI355X_TRIANGULAR_ENTRY(s, float, float, NAME, PNAME, OP)                         \
+  DLAF_MI355X_TRIANGULAR_ENTRY(d, double, double, NAME, PNAME, OP)                       \
+  DLAF_MI355X_TRIANGULAR_ENTRY(c, std::complex<float>, dlaf_complex_c, NAME, PNAME, OP)  \
+  DLAF_MI355X_TRIANGULAR_ENTRY(z, std::complex<double>, dlaf_complex_z, NAME, PNAME, OP)
+DLAF_MI355X_TRIANGULAR_ENTRIES(triangular_multiplication, trmm, kTrmm)
+DLAF_MI355X_TRIANGULAR_ENTRIES(triangular_solver, trsm, kTrsm)
+#undef DLAF_MI355X_TRIANGULAR_ENTRIES
+#undef DLAF_MI355X_TRIANGULAR_ENTRY
+#define DLAF_MI355X_HEMM_ENTRY(S, HT, CT, NAME)                                                                  \
+  int dlaf_mi355x_hermitian_multiplication_##S(int ctx, char side, char uplo, const CT* alpha, const CT* a,         \
+                                               DLAF_descriptor desca, const CT* b, DLAF_descriptor descb,          \
+                                               const CT* beta, CT* c, DLAF_descriptor descc) noexcept {            \
+    return hermitian_multiplication_c<HT>(ctx, side, uplo, reinterpret_cast<const HT*>(alpha),                     \
+                                          reinterpret_cast<const HT*>(a), desca, reinterpret_cast<const HT*>(b),   \
+                                          descb, reinterpret_cast<const HT*>(beta), reinterpret_cast<HT*>(c), descc); \
+  }                                                                                                             \
+  void dlaf_mi355x_p##S##NAME(char side, char uplo, int m, int n, const CT* alpha, const CT* a, int ia, int ja,     \
+                              const int desca[9], const CT* b, int ib, int jb, const int descb[9], const CT* beta,  \
+                              CT* c, int ic, int jc, const int descc[9]) noexcept {                               \
+    pxhemm<HT>(side, uplo, m, n, reinterpret_cast<const HT*>(alpha), reinterpret_cast<const HT*>(a), ia, ja, desca, \
+               reinterpret_cast<const HT*>(b), ib, jb, descb, reinterpret_cast<const HT*>(beta),                   \
+               reinterpret_cast<HT*>(c), ic, jc, descc);                                                          \
+  }
+DLAF_MI355X_HEMM_ENTRY(s, float, float, symm)
+DLAF_MI355X_HEMM_ENTRY(d, double, double, symm)
+DLAF_MI355X_HEMM_ENTRY(c, std::complex<float>, dlaf_complex_c, hemm)
+DLAF_MI355X_HEMM_ENTRY(z, std::complex<double>, dlaf_complex_z, hemm)
+#undef DLAF_MI355X_HEMM_ENTRY
+#define DLAF_MI355X_POTRS_ENTRY(S, HT, CT)                                                                       \
+  void dlaf_mi355x_p##S##potrs(char uplo, int n, int nrhs, const CT* a, int ia, int ja, const int desca[9], CT* b,  \
+                               int ib, int jb, const int descb[9], int* info) noexcept {                        \
+    pxpotrs<HT>(uplo, n, nrhs, reinterpret_cast<const HT*>(a), ia, ja, desca, reinterpret_cast<HT*>(b), ib, jb,  \
+                descb, info);                                                                                   \
+  }
+DLAF_MI355X_POTRS_ENTRY(s, float, float)
+DLAF_MI355X_POTRS_ENTRY(d, double, double)
+DLAF_MI355X_POTRS_ENTRY(c, std::complex<float>, dlaf_complex_c)
+DLAF_MI355X_POTRS_ENTRY(z, std::complex<double>, dlaf_complex_z)
+#undef DLAF_MI355X_POTRS_ENTRY
+
+#define DLAF_MI355X_HEGST_ENTRY(S, HT, CT, RT)                                                                    \
+  int dlaf_mi355x_generalized_to_standard_##S(int ctx, char uplo, CT* a, DLAF_descriptor desca, const CT* b,       \
+                                              DLAF_descriptor descb) noexcept {                                  \
+    return gen_to_std_c<HT>(ctx, uplo, reinterpret_cast<HT*>(a), desca, reinterpret_cast<const HT*>(b), descb);    \
+  }                                                                                                              \
+  void dlaf_mi355x_p##S##hegst(int ibtype, char uplo, int n, CT* a, int ia, int ja, const int desca[9], const CT* b, \
+                               int ib, int jb, const int descb[9], RT* scale, int* info) noexcept {               \
+    pxhegst<HT, RT>(ibtype, uplo, n, reinterpret_cast<HT*>(a), ia, ja, desca, reinterpret_cast<const HT*>(b), ib, \
+                    jb, descb, scale, info);                                                                     \
+  }
+DLAF_MI355X_HEGST_ENTRY(s, float, float, float)
+DLAF_MI355X_HEGST_ENTRY(d, double, double, double)
+DLAF_MI355X_HEGST_ENTRY(c, std::complex<float>, dlaf_complex_c, float)
+DLAF_MI355X_HEGST_ENTRY(z, std::complex<double>, dlaf_complex_z, double)
+#undef DLAF_MI355X_HEGST_ENTRY
+
+#define DLAF_MI355X_INVERSE_ENTRY(S, HT, CT)                                                                      \
+  int dlaf_mi355x_triangular_inverse_##S(int ctx, char uplo, char diag, CT* a, DLAF_descriptor desca) noexcept {     \
+    return inverse_c<HT>(ctx, uplo, diag, false, reinterpret_cast<HT*>(a), desca);                                  \
+  }                                                                                                                \
+  int dlaf_mi355x_inverse_from_cholesky_factor_##S(int ctx, char uplo, CT* a, DLAF_descriptor desca) noexcept {     \
+    return inverse_c<HT>(ctx, uplo, 'N', true, reinterpret_cast<HT*>(a), desca);                                    \
+  }                                                                                                                \
+  void dlaf_mi355x_p##S##trtri(char uplo, char diag, int n, CT* a, int ia, int ja, const int desca[9],              \
+                               int* info) noexcept {                                                               \
+    pxinverse<HT>(uplo, diag, false, n, reinterpret_cast<HT*>(a), ia, ja, desca, info);                             \
+  }                                                                                                                \
+  void dlaf_mi355x_p##S##potri(char uplo, int n, CT* a, int ia, int ja, const int desca[9], int* info) noexcept {   \
+    pxinverse<HT>(uplo, 'N', true, n, reinterpret_cast<HT*>(a), ia, ja, desca, info);                               \
+  }
+DLAF_MI355X_INVERSE_ENTRY(s, float, float)
+DLAF_MI355X_INVERSE_ENTRY(d, double, double)
+DLAF_MI355X_INVERSE_ENTRY(c, std::complex<float>, dlaf_complex_c)
+DLAF_MI355X_INVERSE_ENTRY(z, std::complex<double>, dlaf_complex_z)
+#undef DLAF_MI355X_INVERSE_ENTRY
+
+#define DLAF_MI355X_NORM_ENTRY(S, HT, CT, RT, HE)                                                                  \
+  int dlaf_mi355x_general_norm_##S(int ctx, char norm, const CT* a, DLAF_descriptor desca, double* value) noexcept { \
+    return norm_c<HT>(ctx, norm, 'G', 'L', 'N', reinterpret_cast<const HT*>(a), desca, value);                      \
+  }                                                                                                                \
+  int dlaf_mi355x_hermitian_norm_##S(int ctx, char norm, char uplo, const CT* a, DLAF_descriptor desca,             \
+                                     double* value) noexcept {                                                     \
+    return norm_c<HT>(ctx, norm, 'H', uplo, 'N', reinterpret_cast<const HT*>(a), desca, value);                     \
+  }                                                                                                                \
+  int dlaf_mi355x_triangular_norm_##S(int ctx, char norm, char uplo, char diag, const CT* a, DLAF_descriptor desca, \
+                                      double* value) noexcept {                                                    \
+    return norm_c<HT>(ctx, norm, 'T', uplo, diag, reinterpret_cast<const HT*>(a), desca, value);                    \
+  }                                                                                                                \
+  RT dlaf_mi355x_p##S##lange(char norm, int m, int n, const CT* a, int ia, int ja, const int desca[9]) noexcept {    \
+    return (RT) pxnorm<HT>(norm, 'G', 'L', 'N', m, n, reinterpret_cast<const HT*>(a), ia, ja, desca);               \
+  }                                                                                                                \
+  RT dlaf_mi355x_p##S##lan##HE(char norm, char uplo, int n, const CT* a, int ia, int ja,                            \
+                               const int desca[9]) noexcept {                                                      \
+    return (RT) pxnorm<HT>(norm, 'H', uplo, 'N', n, n, reinterpret_cast<const HT*>(a), ia, ja, desca);              \
+  }                                                                                                                \
+  RT dlaf_mi355x_p##S##lantr(char norm, char uplo, char diag, int n, const CT* a, int ia, int ja,                   \
+                             const int desca[9]) noexcept {                                                        \
+    return (RT) pxnorm<HT>(norm, 'T', uplo, diag, n, n, reinterpret_cast<const HT*>(a), ia, ja, desca);             \
+  }
+DLAF_MI355X_NORM_ENTRY(s, float, float, float, sy)
+DLAF_MI355X_NORM_ENTRY(d, double, double, double, sy)
+DLAF_MI355X_NORM_ENTRY(c, std::complex<float>, dlaf_complex_c, float, he)
+DLAF_MI355X_NORM_ENTRY(z, std::complex<double>, dlaf_complex_z, double, he)
+#undef DLAF_MI355X_NORM_ENTRY
+
+#define DLAF_MI355X_R2B_ENTRY(S, HT, CT)                                                                          \
+  int dlaf_mi355x_reduction_to_band_##S(int ctx, CT* a, DLAF_descriptor desca, int band, CT* taus) noexcept {     \
+    return red2band_c<HT>(ctx, reinterpret_cast<HT*>(a), desca, band, reinterpret_cast<HT*>(taus));               \
+  }                                                                                                              \
+  int dlaf_mi355x_bt_reduction_to_band_##S(int ctx, int band, CT* c, DLAF_descriptor descc, const CT* v,          \
+                                           DLAF_descriptor descv, const CT* taus) noexcept {                     \
+    return bt_red2band_c<HT>(ctx, band, reinterpret_cast<HT*>(c), descc, reinterpret_cast<const HT*>(v), descv,   \
+                             reinterpret_cast<const HT*>(taus));                                                 \
+  }
+DLAF_MI355X_R2B_ENTRY(s, float, float)
+DLAF_MI355X_R2B_ENTRY(d, double, double)
+DLAF_MI355X_R2B_ENTRY(c, std::complex<float>, dlaf_complex_c)
+DLAF_MI355X_R2B_ENTRY(z, std::complex<double>, dlaf_complex_z)
+#undef DLAF_MI355X_R2B_ENTRY
+
+
+#define DLAF_MI355X_EIG_ENTRY(S, KIND, HT, CT, RT, PEV, PGV)                                                          \
+  int dlaf_mi355x_band_to_tridiagonal_##S(int ctx, const CT* a, DLAF_descriptor desca, int band, RT* d, RT* e, CT* v, \
+                                          int ldv) noexcept {                                                       \
+    return band_to_tridiag_c<HT>(ctx, reinterpret_cast<const HT*>(a), desca, band, d, e, reinterpret_cast<HT*>(v), ldv); \
+  }                                                                                                                  \
+  int dlaf_mi355x_bt_band_to_tridiagonal_##S(int band, int n, int ncols, const CT* v, int ldv, CT* e, int lde) noexcept { \
+    using DT = typename DevType<HT>::type;                                                                           \
+    runtime_init();                                                                                                  \
+    if (band < 2 || ldv < std::max(1, n) || lde < std::max(1, n))                                                    \
+      fatal("[dlaf_mi355x] bt_band_to_tridiagonal: bad band_size / leading dimensions\n");                           \
+    return bt_band_to_tridiag_host<DT>(n, band, reinterpret_cast<const DT*>(v), ldv, reinterpret_cast<DT*>(e), lde,   \
+                                       ncols);                                                                       \
+  }                                                                                                                  \
+  int dlaf_##KIND##_eigensolver_##S(const int ctx, const char uplo, CT* a, const DLAF_descriptor desca, RT* w, CT* z, \
+                                    const DLAF_descriptor descz) noexcept {                                          \
+    return eigensolver_c<HT>(ctx, uplo, reinterpret_cast<HT*>(a), desca, w, reinterpret_cast<HT*>(z), descz, 0,      \
+                             desca.m);                                                                               \
+  }                                                                                                                  \
+  int dlaf_##KIND##_eigensolver_partial_spectrum_##S(const int ctx, const char uplo, CT* a,                           \
+                                                     const DLAF_descriptor desca, RT* w, CT* z,                      \
+                                                     const DLAF_descriptor descz, const int64_t begin,               \
+                                                     const int64_t end) noexcept {                                   \
+    return eigensolver_c<HT>(ctx, uplo, reinterpret_cast<HT*>(a), desca, w, reinterpret_cast<HT*>(z), descz, begin,  \
+                             end);                                                                                   \
+  }                                                                                                                  \
+  int dlaf_##KIND##_generalized_eigensolver_##S(const int ctx, const char uplo, CT* a, const DLAF_descriptor desca,   \
+                                                CT* b, const DLAF_descriptor descb, RT* w, CT* z,                    \
+                                                const DLAF_descriptor descz) noexcept {                              \
+    return gen_eigensolver_c<HT>(ctx, uplo, reinterpret_cast<HT*>(a), desca, reinterpret_cast<HT*>(b), descb, w,      \
+                                 reinterpret_cast<HT*>(z), descz, false, 0, desca.m);                                \
+  }                                                                                                                  \
+  int dlaf_##KIND##_generalized_eigensolver_factorized_##S(const int ctx, const char uplo, CT* a,                     \
+                                                           const DLAF_descriptor desca, CT* b,                       \
+                                                           const DLAF_descriptor descb, RT* w, CT* z,                \
+                                                           const DLAF_descriptor descz) noexcept {                   \
+    return gen_eigensolver_c<HT>(ctx, uplo, reinterpret_cast<HT*>(a), desca, reinterpret_cast<HT*>(b), descb, w,      \
+                                 reinterpret_cast<HT*>(z), descz, true, 0, desca.m);                                 \
+  }                                                                                                                  \
+  int dlaf_##KIND##_generalized_eigensolver_partial_spectrum_##S(                                                     \
+      const int ctx, const char uplo, CT* a, const DLAF_descriptor desca, CT* b, const DLAF_descriptor descb, RT* w,  \
+      CT* z, const DLAF_descriptor descz, const int64_t begin, const int64_t end) noexcept {                         \
+    return gen_eigensolver_c<HT>(ctx, uplo, reinterpret_cast<HT*>(a), desca, reinterpret_cast<HT*>(b), descb, w,      \
+                                 reinterpret_cast<HT*>(z), descz, false, begin, end);                                \
+  }                                                                                                                  \
+  int dlaf_##KIND##_generalized_eigensolver_factorized_partial_spectrum_##S(                                          \
+      const int ctx, const char uplo, CT* a, const DLAF_descriptor desca, CT* b, const DLAF_descriptor descb, RT* w,  \
+      CT* z, const DLAF_descriptor descz, const int64_t begin, const int64_t end) noexcept {                         \
+    return gen_eigensolver_c<HT>(ctx, uplo, reinterpret_cast<HT*>(a), desca, reinterpret_cast<HT*>(b), descb, w,      \
+                                 reinterpret_cast<HT*>(z), descz, true, begin, end);                                 \
+  }                                                                                                                  \
+  void dlaf_##PEV(const char uplo, const int n, CT* a, const int ia, const int ja, const int desca[9], RT* w, CT* z,  \
+                  const int iz, const int jz, const int descz[9], int* info) noexcept {                              \
+    pxhegvd<HT>(uplo, n, reinterpret_cast<HT*>(a), ia, ja, desca, nullptr, 1, 1, nullptr, w, reinterpret_cast<HT*>(z), \
+                iz, jz, descz, 1, n, info, false);                                                                   \
+  }                                                                                                                  \
+  void dlaf_##PEV##_partial_spectrum(const char uplo, const int n, CT* a, const int ia, const int ja,                 \
+                                     const int desca[9], RT* w, CT* z, const int iz, const int jz,                   \
+                                     const int descz[9], const int64_t il, const int64_t iu, int* info) noexcept {   \
+    pxhegvd<HT>(uplo, n, reinterpret_cast<HT*>(a), ia, ja, desca, nullptr, 1, 1, nullptr, w, reinterpret_cast<HT*>(z), \
+                iz, jz, descz, il, iu, info, false);                                                                 \
+  }                                                                                                                  \
+  void dlaf_##PGV(const char uplo, const int n, CT* a, const int ia, const int ja, const int desca[9], CT* b,         \
+                  const int ib, const int jb, const int descb[9], RT* w, CT* z, const int iz, const int jz,          \
+                  const int descz[9], int* info) noexcept {                                                          \
+    pxhegvd<HT>(uplo, n, reinterpret_cast<HT*>(a), ia, ja, desca, reinterpret_cast<HT*>(b), ib, jb, descb, w,         \
+                reinterpret_cast<HT*>(z), iz, jz, descz, 1, n, info, false);                                         \
+  }                                                                                                                  \
+  void dlaf_##PGV##_factorized(const char uplo, const int n, CT* a, const int ia, const int ja, const int desca[9],   \
+                               CT* b, const int ib, const int jb, const int descb[9], RT* w, CT* z, const int iz,    \
+                               const int jz, const int descz[9], int* info) noexcept {                               \
+    pxhegvd<HT>(uplo, n, reinterpret_cast<HT*>(a), ia, ja, desca, reinterpret_cast<HT*>(b), ib, jb, descb, w,         \
+                reinterpret_cast<HT*>(z), iz, jz, descz, 1, n, info, true);                                          \
+  }                                                                                                                  \
+  void dlaf_##PGV##_partial_spectrum(const char uplo, const int n, CT* a, const int ia, const int ja,                 \
+                                     const int desca[9], CT* b, const int ib, const int jb, const int descb[9],      \
+                                     RT* w, CT* z, const int iz, const int jz, const int descz[9], const int64_t il, \
+                                     const int64_t iu, int* info) noexcept {                                         \
+    pxhegvd<HT>(uplo, n, reinterpret_cast<HT*>(a), ia, ja, desca, reinterpret_cast<HT*>(b), ib, jb, descb, w,         \
+                reinterpret_cast<HT*>(z), iz, jz, descz, il, iu, info, false);                                       \
+  }                                                                                                                  \
+  void dlaf_##PGV##_factorized_partial_spectrum(const char uplo, const int n, CT* a, const int ia, const int ja,      \
+                                                const int desca[9], CT* b, const int ib, const int jb,               \
+                                                const int descb[9], RT* w, CT* z, const int iz, const int jz,        \
+                                                const int descz[9], const int64_t il, const int64_t iu,              \
+                                                int* info) noexcept {                                                \
+    pxhegvd<HT>(uplo, n, reinterpret_cast<HT*>(a), ia, ja, desca, reinterpret_cast<HT*>(b), ib, jb, descb, w,         \
+                reinterpret_cast<HT*>(z), iz, jz, descz, il, iu, info, true);                                        \
+  }
+DLAF_MI355X_EIG_ENTRY(s, symmetric, float, float, float, pssyevd, pssygvd)
+DLAF_MI355X_EIG_ENTRY(d, symmetric, double, double, double, pdsyevd, pdsygvd)
+DLAF_MI355X_EIG_ENTRY(c, hermitian, std::complex<float>, dlaf_complex_c, float, pcheevd, pchegvd)
+DLAF_MI355X_EIG_ENTRY(z, hermitian, std::complex<double>, dlaf_complex_z, double, pzheevd, pzhegvd)
+#undef DLAF_MI355X_EIG_ENTRY
+
+#define DLAF_MI355X_EIGVAL_ENTRY(S, KIND, HT, CT, RT, PEV, PGV)                                                       \
+  int dlaf_##KIND##_eigenvalues_##S(const int ctx, const char uplo, const CT* a, const DLAF_descriptor desca, RT* w,  \
+                                    const int64_t begin, const int64_t end) noexcept {                               \
+    return eigenvalues_c<HT>(ctx, uplo, reinterpret_cast<const HT*>(a), desca, w, begin, end);                       \
+  }                                                                                                                  \
+  int dlaf_##KIND##_generalized_eigenvalues_##S(const int ctx, const char uplo, const CT* a,                          \
+                                                const DLAF_descriptor desca, CT* b, const DLAF_descriptor descb,     \
+                                                RT* w, const int64_t begin, const int64_t end) noexcept {            \
+    return gen_eigenvalues_c<HT>(ctx, uplo, reinterpret_cast<const HT*>(a), desca, reinterpret_cast<HT*>(b), descb,   \
+                                 w, false, begin, end);                                                              \
+  }                                                                                                                  \
+  int dlaf_##KIND##_generalized_eigenvalues_factorized_##S(const int ctx, const char uplo, const CT* a,               \
+                                                           const DLAF_descriptor desca, CT* b,                       \
+                                                           const DLAF_descriptor descb, RT* w, const int64_t begin,  \
+                                                           const int64_t end) noexcept {                             \
+    return gen_eigenvalues_c<HT>(ctx, uplo, reinterpret_cast<const HT*>(a), desca, reinterpret_cast<HT*>(b), descb,   \
+                                 w, true, begin, end);                                                               \
+  }                                                                                                                  \
+  int dlaf_##KIND##_eigensolver_partial_spectrum_by_value_##S(const int ctx, const char uplo, CT* a,                  \
+                                                              const DLAF_descriptor desca, RT* w, CT* z,             \
+                                                              const DLAF_descriptor descz, const RT vl, const RT vu, \
+                                                              long* begin, long* end) noexcept {                     \
+    return eigensolver_by_value_c<HT>(ctx, uplo, reinterpret_cast<HT*>(a), desca, w, reinterpret_cast<HT*>(z), descz, \
+                                      vl, vu, begin, end);                                                           \
+  }                                                                                                                  \
+  int dlaf_##KIND##_generalized_eigensolver_partial_spectrum_by_value_##S(                                            \
+      const int ctx, const char uplo, CT* a, const DLAF_descriptor desca, CT* b, const DLAF_descriptor descb, RT* w,  \
+      CT* z, const DLAF_descriptor descz, const RT vl, const RT vu, long* begin, long* end) noexcept {               \
+    return gen_eigensolver_by_value_c<HT>(ctx, uplo, reinterpret_cast<HT*>(a), desca, reinterpret_cast<HT*>(b),       \
+                                          descb, w, reinterpret_cast<HT*>(z), descz, false, vl, vu, begin, end);     \
+  }                                                                                                                  \
+  int dlaf_##KIND##_generalized_eigensolver_factorized_partial_spectrum_by_value_##S(                                 \
+      const int ctx, const char uplo, CT* a, const DLAF_descriptor desca, CT* b, const DLAF_descriptor descb, RT* w,  \
+      CT* z, const DLAF_descriptor descz, const RT vl, const RT vu, long* begin, long* end) noexcept {               \
+    return gen_eigensolver_by_value_c<HT>(ctx, uplo, reinterpret_cast<HT*>(a), desca, reinterpret_cast<HT*>(b),       \
+                                          descb, w, reinterpret_cast<HT*>(z), descz, true, vl, vu, begin, end);      \
+  }                                                                                                                  \
+  void dlaf_##PEV##_eigenvalues(const char uplo, const int n, const CT* a, const int ia, const int ja,                \
+                                const int desca[9], RT* w, const int64_t il, const int64_t iu, int* info) noexcept { \
+    pxhegvd_eigenvalues<HT>(uplo, n, reinterpret_cast<const HT*>(a), ia, ja, desca, nullptr, 1, 1, nullptr, w, il,    \
+                            iu, info, false);                                                                        \
+  }                                                                                                                  \
+  void dlaf_##PGV##_eigenvalues(const char uplo, const int n, const CT* a, const int ia, const int ja,                \
+                                const int desca[9], CT* b, const int ib, const int jb, const int descb[9], RT* w,    \
+                                const int64_t il, const int64_t iu, int* info) noexcept {                            \
+    pxhegvd_eigenvalues<HT>(uplo, n, reinterpret_cast<const HT*>(a), ia, ja, desca, reinterpret_cast<HT*>(b), ib, jb, \
+                            descb, w, il, iu, info, false);                                                          \
+  }                                                                                                                  \
+  void dlaf_##PGV##_eigenvalues_factorized(const char uplo, const int n, const CT* a, const int ia, const int ja,     \
+                                           const int desca[9], CT* b, const int ib, const int jb,                    \
+                                           const int descb[9], RT* w, const int64_t il, const int64_t iu,            \
+                                           int* info) noexcept {                                                     \
+    pxhegvd_eigenvalues<HT>(uplo, n, reinterpret_cast<const HT*>(a), ia, ja, desca, reinterpret_cast<HT*>(b), ib, jb, \
+                            descb, w, il, iu, info, true);                                                           \
+  }                                                                                                                  \
+  void dlaf_##PEV##_partial_spectrum_by_value(const char uplo, const int n, CT* a, const int ia, const int ja,        \
+                                              const int desca[9], RT* w, CT* z, const int iz, const int jz,          \
+                                              const int descz[9], const RT vl, const RT vu, int* m,                  \
+                                              int* info) noexcept {                                                  \
+    pxhegvd_by_value<HT>(uplo, n, reinterpret_cast<HT*>(a), ia, ja, desca, nullptr, 1, 1, nullptr, w,                 \
+                         reinterpret_cast<HT*>(z), iz, jz, descz, vl, vu, m, info, false);                           \
+  }                                                                                                                  \
+  void dlaf_##PGV##_partial_spectrum_by_value(const char uplo, const int n, CT* a, const int ia, const int ja,        \
+                                              const int desca[9], CT* b, const int ib, const int jb,                 \
+                                              const int descb[9], RT* w, CT* z, const int iz, const int jz,          \
+                                              const int descz[9], const RT vl, const RT vu, int* m,                  \
+                                              int* info) noexcept {                                                  \
+    pxhegvd_by_value<HT>(uplo, n, reinterpret_cast<HT*>(a), ia, ja, desca, reinterpret_cast<HT*>(b), ib, jb, descb,   \
+                         w, reinterpret_cast<HT*>(z), iz, jz, descz, vl, vu, m, info, false);                        \
+  }                                                                                                                  \
+  void dlaf_##PGV##_factorized_partial_spectrum_by_value(const char uplo, const int n, CT* a, const int ia,           \
+                                                         const int ja, const int desca[9], CT* b, const int ib,      \
+                                                         const int jb, const int descb[9], RT* w, CT* z,             \
+                                                         const int iz, const int jz, const int descz[9],             \
+                                                         const RT vl, const RT vu, int* m, int* info) noexcept {     \
+    pxhegvd_by_value<HT>(uplo, n, reinterpret_cast<HT*>(a), ia, ja, desca, reinterpret_cast<HT*>(b), ib, jb, descb,   \
+                         w, reinterpret_cast<HT*>(z), iz, jz, descz, vl, vu, m, info, true);                         \
+  }
+DLAF_MI355X_EIGVAL_ENTRY(s, symmetric, float, float, float, pssyevd, pssygvd)
+DLAF_MI355X_EIGVAL_ENTRY(d, symmetric, double, double, double, pdsyevd, pdsygvd)
+DLAF_MI355X_EIGVAL_ENTRY(c, hermitian, std::complex<float>, dlaf_complex_c, float, pcheevd, pchegvd)
+DLAF_MI355X_EIGVAL_ENTRY(z, hermitian, std::complex<double>, dlaf_complex_z, double, pzheevd, pzhegvd)
+#undef DLAF_MI355X_EIGVAL_ENTRY
+
+int dlaf_mi355x_tridiagonal_eigenvalues_s(int n, const float* d, const float* e, float* w, long begin,
+                                          long end) noexcept {
+  runtime_init();
+  return tridiag_eigenvalues_host<float>(n, d, e, w, begin, end);
+}
+int dlaf_mi355x_tridiagonal_eigenvalues_d(int n, const double* d, const double* e, double* w, long begin,
+                                          long end) noexcept {
+  runtime_init();
+  return tridiag_eigenvalues_host<double>(n, d, e, w, begin, end);
+}
+int dlaf_mi355x_tridiagonal_sturm_count_s(int n, const float* d, const float* e, long nshifts, const float* shifts,
+                                          long* counts) noexcept {
+  runtime_init();
+  return sturm_count_host<float>(n, d, e, nshifts, shifts, counts);
+}
+int dlaf_mi355x_tridiagonal_sturm_count_d(int n, const double* d, const double* e, long nshifts, const double* shifts,
+                                          long* counts) noexcept {
+  runtime_init();
+  return sturm_count_host<double>(n, d, e, nshifts, shifts, counts);
+}
+int dlaf_mi355x_sturm_layout(int out[2]) noexcept {
+  out[0] = kSturmChunk;
+  out[1] = kSturmThreads;
+  return 0;
+}
+
+int dlaf_mi355x_tridiagonal_eigensolver_s(int n, int nb, const float* d, const float* e, float* w, float* z,
+                                          int ldz) noexcept {
+  runtime_init();
+  return tridiag_solver_host<float>(n, nb, d, e, w, z, ldz, 0, n);
+}
+int dlaf_mi355x_tridiagonal_eigensolver_d(int n, int nb, const double* d, const double* e, double* w, double* z,
+                                          int ldz) noexcept {
+  runtime_init();
+  return tridiag_solver_host<double>(n, nb, d, e, w, z, ldz, 0, n);
+}
+int dlaf_mi355x_tridiagonal_eigensolver_partial_spectrum_s(int n, int nb, const float* d, const float* e, float* w,
+                                                           float* z, int ldz, long begin, long end) noexcept {
+  check_eigenvalues_index("tridiagonal_eigensolver", n, begin, end);
+  runtime_init();
+  return tridiag_solver_host<float>(n, nb, d, e, w, z, ldz, begin, end);
+}
+int dlaf_mi355x_tridiagonal_eigensolver_partial_spectrum_d(int n, int nb, const double* d, const double* e, double* w,
+                                                           double* z, int ldz, long begin, long end) noexcept {
+  check_eigenvalues_index("tridiagonal_eigensolver", n, begin, end);
+  runtime_init();
+  return tridiag_solver_host<double>(n, nb, d, e, w, z, ldz, begin, end);
+}
+int dlaf_mi355x_get_eigensolver_min_band(void) noexcept {
+  return eigensolver_min_band();
+}
+void dlaf_mi355x_set_eigensolver_min_band(int b_min) noexcept {
+  set_eigensolver_min_band(b_min);
+}
+int dlaf_mi355x_get_band_size(int nb) noexcept {
+  return get_band_size(nb);
+}
+}  // extern "C"

@@ -21,7 +21,9 @@
 #include <dlaf_mi355x/dlaf_mi355x.h>
 
 #include "c_api_internal.hpp"
+#include "device_matrix.hpp"
 #include "eigensolver.hpp"
+#include "pool.hpp"
 #include "tile_matrix.hpp"
 
 using namespace dlaf_mi355x;

@@ -10,7 +10,11 @@
 #include <dlaf_mi355x/dlaf_mi355x.h>
 
 #include "c_api_internal.hpp"
+#include "device_matrix.hpp"
+#include "direct.hpp"
+#include "drivers.hpp"
 #include "eigensolver.hpp"
+#include "pool.hpp"
 #include "red2band.hpp"
 #include "tile_matrix.hpp"
 

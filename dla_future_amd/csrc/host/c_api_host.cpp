@@ -14,6 +14,8 @@
 
 #include "../device/tridiag_api.hpp"
 #include "c_api_internal.hpp"
+#include "device_matrix.hpp"
+#include "drivers.hpp"
 #include "eigensolver.hpp"
 #include "red2band.hpp"
 #include "tile_matrix.hpp"

@@ -8,6 +8,7 @@
 
 #include "api_checks.hpp"
 #include "runtime.hpp"
+#include "transport.hpp"
 
 namespace dlaf_mi355x {
 

@@ -1,8 +1,8 @@
 // cholesky.cpp -- the issue side of the tile Cholesky: which kernels, broadcasts and events one factorization
-// enqueues on the three streams of a DeviceMatrix, in one of four orders.  See runtime.hpp for the matrix and the
-// transports, runtime.cpp for wait() and the blocking entry points.
+// enqueues on the three streams of a DeviceMatrix, in one of four orders.  See device_matrix.hpp for the matrix,
+// transport.hpp for the transports, device_matrix.cpp for wait() and the blocking entry points.
+#include "device_matrix.hpp"
 #include "launch_args.hpp"
-#include "runtime.hpp"
 
 #include <algorithm>
 #include <cstdlib>

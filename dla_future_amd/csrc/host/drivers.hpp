@@ -1,0 +1,103 @@
+// drivers.hpp -- what the algorithms on top of the tile kernels export: the triangular solver (solver.cpp), the
+// triangular and Hermitian multiplications (multiplication.cpp), generalized-to-standard (gen_to_std.cpp), the inverses
+// (inverse.cpp) and the norms (norm.cpp), host and device-resident forms.  reduction_to_band and the eigensolver stages
+// have headers of their own (red2band.hpp, eigensolver.hpp).
+#pragma once
+#include "device_matrix.hpp"
+
+namespace dlaf_mi355x {
+
+// op(A) X = alpha B (side L) / X op(A) = alpha B (side R) on the grid, host operands (solver.cpp);
+// m x n: size of B, nb: the square block of A = B's block along the triangular dimension, nb_free: B's block along
+// the other dimension (<= 0: nb)
+template <class T>
+int triangular_solver_host(Grid* g, char side, char uplo, char op, char diag, T alpha, const T* a, long lda, int a_isrc,
+                           int a_jsrc, T* b, long ldb, long m, long n, int nb, int b_isrc, int b_jsrc, int nb_free = 0);
+
+void solver_last_profile(double* ms, double* flops);
+
+// Device-resident operands for the solver (solver.cpp): a general m x n matrix in tile layout behind a MatrixBase
+// handle, and dlaf::triangular_solver on a resident triangular matrix (a DeviceMatrix, e.g. the factor p?potrf left
+// there) and a resident right-hand side -- no PCIe traffic.
+MatrixBase* general_matrix_create(Grid* g, char type, long m, long n, int nb, int isrc, int jsrc);
+void general_matrix_transfer(MatrixBase* h, void* host, long ld, bool upload);
+int triangular_solver_device(char side, char uplo, char op, char diag, const void* alpha, MatrixBase* a, MatrixBase* b);
+
+// B = alpha op(A) B (side L) / B = alpha B op(A) (side R) on the grid (multiplication.cpp): the arguments and the
+// operand mapping of triangular_solver_host, host and resident forms; device time of the last sweep
+template <class T>
+int triangular_multiplication_host(Grid* g, char side, char uplo, char op, char diag, T alpha, const T* a, long lda,
+                                   int a_isrc, int a_jsrc, T* b, long ldb, long m, long n, int nb, int b_isrc, int b_jsrc,
+                                   int nb_free = 0);
+int triangular_multiplication_device(char side, char uplo, char op, char diag, const void* alpha, MatrixBase* a,
+                                     MatrixBase* b);
+// device time and whole-grid flops of the last sweep of EITHER multiplication (triangular or Hermitian) on this process
+void multiplication_last_profile(double* ms, double* flops);
+
+// C = beta C + alpha A B (side L) / beta C + alpha B A (side R), A Hermitian with only its uplo triangle read
+// (multiplication.cpp; dlaf::hermitian_multiplication, every side x uplo).  m x n: size of B and C, nb: A's square block =
+// their block along A's dimension, nb_free: their block along the other one (<= 0: nb); (isrc, jsrc): source process of
+// B and C.  Host and resident forms.
+template <class T>
+int hermitian_multiplication_host(Grid* g, char side, char uplo, T alpha, const T* a, long lda, int a_isrc, int a_jsrc,
+                                  const T* b, long ldb, T beta, T* c, long ldc, long m, long n, int nb, int isrc, int jsrc,
+                                  int nb_free = 0);
+int hermitian_multiplication_device(char side, char uplo, const void* alpha, MatrixBase* a, MatrixBase* b,
+                                    const void* beta, MatrixBase* c);
+
+// A <- L^-1 A L^-H (uplo L) / U^-H A U^-1 (uplo U) with the Cholesky factor held in the same uplo triangle of
+// `l` (gen_to_std.cpp; dlaf::eigensolver::internal::generalized_to_standard); device-resident and host forms
+template <class T>
+int gen_to_std_device(DeviceMatrix<T>& a, DeviceMatrix<T>& l);
+template <class T>
+int gen_to_std_host(Grid* g, char uplo, T* a, long lda, const T* l, long ldl, long n, int nb, int isrc, int jsrc);
+
+// A <- A^-1 for the triangular matrix in A's uplo triangle (diag N / U), and the uplo triangle of (L L^H)^-1 /
+// (U^H U)^-1 from the Cholesky factor held there (inverse.cpp; LAPACK xTRTRI / xPOTRI), in place; device-resident and
+// host forms.  Return LAPACK's info: the 1-based index of the first exactly-zero diagonal element (nothing is written
+// then), the same on every rank.
+template <class T>
+int triangular_inverse_device(char diag, DeviceMatrix<T>& a);
+template <class T>
+int inverse_from_cholesky_factor_device(DeviceMatrix<T>& a);
+template <class T>
+int triangular_inverse_host(Grid* g, char uplo, char diag, T* a, long lda, long n, int nb, int isrc, int jsrc);
+template <class T>
+int inverse_from_cholesky_factor_host(Grid* g, char uplo, T* a, long lda, long n, int nb, int isrc, int jsrc);
+// device time and whole-grid flops (n^3 / 3 per half, x 4 for complex types) of the last of them on this process
+void inverse_last_profile(double* ms, double* flops);
+// index arithmetic of the two sweeps (exported for the host-logic tests)
+struct DiagTiles {
+  long count;             // local diagonal tiles: global k0 + m kstep at local (il0 + m il_step, jl0 + m jl_step)
+  long k0, kstep;
+  long il0, jl0, il_step, jl_step;
+  int last;               // extent of the last of them
+};
+DiagTiles local_diag_tiles(const Axis& rows, const Axis& cols);
+struct InverseStep {
+  int own_r, own_c;       // owner of the diagonal tile k
+  long il_below;          // first local tile row below k
+  long nrl, ncl;          // local tile rows / columns before k
+  long lr, lc;            // local index of tile row / column k (-1: elsewhere)
+};
+InverseStep inverse_step_ranges(const Axis& rows, const Axis& cols, long k);
+long inverse_workspace_tiles(const Axis& rows, const Axis& cols);
+
+// Max / one / infinity / Frobenius norm (norm.cpp; LAPACK xLANGE, xLANHE / xLANSY, xLANTR): norm letters M, 1 / O, I,
+// F / E in either case; structure 'G' general, 'H' Hermitian / symmetric from the uplo triangle, 'T' triangular from the
+// uplo triangle with diag N / U.  The operand is only read.  Host forms upload this process's local column-major part
+// and write nothing back; the value -- for s / c the float result widened -- is the same bits on every rank.
+// norm_kind: the canonical letter (M, 1, I, F) of a norm letter, 0 for any other character.
+char norm_kind(char norm);
+template <class T>
+double general_norm_host(Grid* g, char norm, const T* a, long lda, long m, long n, int nb, int isrc, int jsrc);
+template <class T>
+double structured_norm_host(Grid* g, char norm, char structure, char uplo, char diag, const T* a, long lda, long n, int nb,
+                            int isrc, int jsrc);
+template <class T>
+double structured_norm_device(char norm, char structure, char diag, const DeviceMatrix<T>& a);
+double general_norm_device(char norm, MatrixBase* general_matrix);
+// device time and the bytes of the referenced tiles (diagonal tiles whole) of the last norm on this process
+void norm_last_profile(double* ms, double* bytes);
+
+}  // namespace dlaf_mi355x

@@ -28,7 +28,9 @@
 #include "../device/band_api.hpp"
 #include "../device/tridiag_api.hpp"
 #include "bt_wavefronts.hpp"
+#include "drivers.hpp"
 #include "eigensolver.hpp"
+#include "pool.hpp"
 
 namespace dlaf_mi355x {
 
@@ -506,9 +508,13 @@ int agreed(Grid* g, int info) {
 void check_replicated_memory(long n, double need) {
   size_t free_b = 0, total_b = 0;
   DLAF_HIP_CHECK(hipMemGetInfo(&free_b, &total_b));
-  if (need > 0.95 * (double) free_b)
+  // the idle blocks of the workspace pool count as free: the stages take them again, and pool_malloc gives them back to
+  // the driver when an allocation fails
+  const size_t idle_b = pool_idle_bytes();
+  if (need > 0.95 * (double) (free_b + idle_b))
     fatal("[dlaf_mi355x] eigensolver: n = %ld needs %.1f GiB per rank for the replicated stages (band_to_tridiagonal, "
-          "tridiagonal_eigensolver), %.1f GiB are free\n", n, need / 1073741824.0, (double) free_b / 1073741824.0);
+          "tridiagonal_eigensolver), %.1f GiB are free and %.1f GiB idle in the workspace pool\n", n, need / 1073741824.0,
+          (double) free_b / 1073741824.0, (double) idle_b / 1073741824.0);
 }
 // every rank holds the n x n reflector matrix (T) ...
 template <class T>

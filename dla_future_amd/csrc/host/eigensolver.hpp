@@ -2,8 +2,8 @@
 // band -> tridiagonal, tridiagonal eigensolver, back-transformation band <- tridiagonal, and the drivers
 // (include/dlaf/eigensolver/eigensolver/impl.h:38-55).
 #pragma once
+#include "device_matrix.hpp"
 #include "red2band.hpp"
-#include "runtime.hpp"
 #include "tile_matrix.hpp"
 
 namespace dlaf_mi355x {

@@ -8,6 +8,7 @@
 
 #include "../device/tridiag_api.hpp"
 #include "eigensolver.hpp"
+#include "pool.hpp"
 
 namespace dlaf_mi355x {
 

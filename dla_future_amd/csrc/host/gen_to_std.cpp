@@ -33,8 +33,9 @@
 #include <algorithm>
 #include <cstdlib>
 
+#include "drivers.hpp"
 #include "launch_args.hpp"
-#include "runtime.hpp"
+#include "pool.hpp"
 #include "sweep.hpp"
 #include "tile_matrix.hpp"
 

@@ -31,8 +31,9 @@
 #include <algorithm>
 #include <numeric>
 
+#include "drivers.hpp"
 #include "launch_args.hpp"
-#include "runtime.hpp"
+#include "pool.hpp"
 #include "sweep.hpp"
 #include "tile_matrix.hpp"
 

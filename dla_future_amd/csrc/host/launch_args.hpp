@@ -97,4 +97,58 @@ Args tile_batch_args(T* b, long b_ts, int ld, long ntiles, int rows_each, const 
   return ta;
 }
 
+// the tile sq x sq (ld sq) at c, alone: C -= a b^H with a, b of K columns (ld sq).  below_diagonal: the tile takes the
+// place of global tile (1, 0) of a 3 x 3 grid -- a plain gemm --, otherwise it is the only diagonal tile (herk, lower)
+template <class T>
+UpdateArgs<T> single_tile_update_args(T* c, const T* a, const T* b, int sq, int K, bool below_diagonal, const int* info) {
+  UpdateArgs<T> ua{};
+  ua.c = c;
+  ua.ldc = sq;
+  ua.a = a;
+  ua.lda = sq;
+  ua.b = b;
+  ua.ldb = sq;
+  // every tile stride stays 0: the tile index does not move a base
+  ua.il0 = below_diagonal ? 1 : 0;
+  ua.il1 = ua.il0 + 1;
+  ua.jl0 = 0;
+  ua.jl1 = 1;
+  ua.nb = sq;
+  ua.K = K;
+  ua.pr = ua.pc = 1;
+  ua.ri = ua.ci = 0;
+  ua.nt = below_diagonal ? 3 : 1;
+  ua.last_rows = sq;
+  ua.info = info;
+  return ua;
+}
+
+// the relayout between m's tiles and a column-major array cm (ld_cm) of the caller's local part; what is particular
+// to a relayout is set on the result (full, rev_rows / rev_cols, conj, scale / alpha, jl_first / jl_count)
+template <class M, class T>
+LayoutArgs<T> layout_args(const M& m, T* cm, long ld_cm) {
+  LayoutArgs<T> a;
+  a.tiles = m.tiles;
+  a.cm = cm;
+  a.ld_cm = ld_cm;
+  a.ltr = (int) m.ltr;
+  a.ltc = (int) m.ltc;
+  a.nb = m.nb;
+  a.rows = m.rows.local_size();
+  a.cols = m.cols.local_size();
+  a.pr = m.rows.P;
+  a.ri = m.rows.shift();
+  a.pc = m.cols.P;
+  a.ci = m.cols.shift();
+  a.transpose = m.transposed ? 1 : 0;
+  return a;
+}
+
+// Source (caller-side) local extents: rows/cols of the UNtransposed distribution.
+template <class M>
+void source_extents(const M& m, long& srows, long& scols) {
+  srows = m.transposed ? m.cols.local_size() : m.rows.local_size();
+  scols = m.transposed ? m.rows.local_size() : m.cols.local_size();
+}
+
 }  // namespace dlaf_mi355x

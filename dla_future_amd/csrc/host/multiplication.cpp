@@ -22,7 +22,7 @@
 #include <type_traits>
 #include <vector>
 
-#include "runtime.hpp"
+#include "drivers.hpp"
 #include "sweep.hpp"
 #include "tile_matrix.hpp"
 

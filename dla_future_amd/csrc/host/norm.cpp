@@ -17,7 +17,8 @@
 #include <cmath>
 #include <limits>
 
-#include "runtime.hpp"
+#include "drivers.hpp"
+#include "pool.hpp"
 #include "tile_matrix.hpp"
 
 namespace dlaf_mi355x {

@@ -2,46 +2,15 @@
 // (dlaf_mi355x_potrf_direct_*): the entry the tests compare the tile POTRF kernels with a reference through, on either
 // path, at leading dimensions, placements, info words and hand-off states no driver happens to produce.  Upload,
 // factor once, download.
-#include <vector>
-
 #include <dlaf_mi355x/dlaf_mi355x.h>
 
-#include "runtime.hpp"
-#include "tile_matrix.hpp"
+#include "device_matrix.hpp"
+#include "direct.hpp"
+#include "direct_operand.hpp"
 
 namespace dlaf_mi355x {
 
 namespace {
-
-constexpr int kBeforeByte = 0xA5;
-
-// a buffer's host array `off` elements into a device allocation of its own; the `off` elements before it hold a
-// byte pattern that before_changed() looks for again: a store in front of the buffer shows
-template <class T>
-struct Operand {
-  DevBuf<T> buf;
-  T* p = nullptr;
-  size_t before = 0;  // bytes in front of the host array
-  void put(const void* host, long elems, long off, hipStream_t s) {
-    buf.alloc((size_t) (elems + off));
-    p = buf.p + off;
-    before = (size_t) off * sizeof(T);
-    if (before > 0)
-      DLAF_HIP_CHECK(hipMemsetAsync(buf.p, kBeforeByte, before, s));
-    DLAF_HIP_CHECK(hipMemcpyAsync(p, host, (size_t) elems * sizeof(T), hipMemcpyHostToDevice, s));
-  }
-  // bytes in front of the host array that no longer hold the pattern (synchronises the stream)
-  int before_changed(hipStream_t s) const {
-    std::vector<unsigned char> h(before);
-    if (before > 0)
-      DLAF_HIP_CHECK(hipMemcpyAsync(h.data(), buf.p, before, hipMemcpyDeviceToHost, s));
-    DLAF_HIP_CHECK(hipStreamSynchronize(s));
-    int n = 0;
-    for (unsigned char b : h)
-      n += b != kBeforeByte;
-    return n;
-  }
-};
 
 // Every element the launches may touch lies inside its buffer?  The extents the contract names (launch_potrf_coop and
 // launch_potrf_diag in device_api.hpp): the kb x kb tile with leading dimension ld, ceil(kb / 64) dense 64 x 64 blocks.
@@ -64,8 +33,8 @@ int potrf_direct(dlaf_mi355x_potrf_desc& d, void* tile, void* winv) {
     return -3;
   hipStream_t s = nullptr;
   Operand<T> dt, dw;
-  dt.put(tile, d.t_elems, d.t_off, s);
-  dw.put(winv, d.w_elems, d.w_off, s);
+  dt.put(tile, d.t_elems, d.t_off, s, true);
+  dw.put(winv, d.w_elems, d.w_off, s, true);
   DevBuf<int> info(1);
   DLAF_HIP_CHECK(hipMemcpyAsync(info.p, &d.info, sizeof(int), hipMemcpyHostToDevice, s));
 

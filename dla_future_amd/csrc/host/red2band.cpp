@@ -31,9 +31,10 @@
 #include <vector>
 
 #include "../device/band_api.hpp"
+#include "device_matrix.hpp"
 #include "launch_args.hpp"
+#include "pool.hpp"
 #include "red2band.hpp"
-#include "runtime.hpp"
 #include "tile_matrix.hpp"
 
 namespace dlaf_mi355x {

@@ -1,6 +1,6 @@
 // red2band.hpp -- reduction to band + back-transformation (red2band.cpp), SURVEY.md section 8(f) item 4
 #pragma once
-#include "runtime.hpp"
+#include "device_matrix.hpp"
 #include "tile_matrix.hpp"
 
 namespace dlaf_mi355x {

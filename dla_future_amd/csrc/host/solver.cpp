@@ -34,7 +34,8 @@
 #include <type_traits>
 #include <vector>
 
-#include "runtime.hpp"
+#include "drivers.hpp"
+#include "pool.hpp"
 #include "sweep.hpp"
 #include "tile_matrix.hpp"
 

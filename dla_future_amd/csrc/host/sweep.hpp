@@ -11,8 +11,9 @@
 #include <algorithm>
 #include <vector>
 
+#include "device_matrix.hpp"
 #include "launch_args.hpp"
-#include "runtime.hpp"
+#include "pool.hpp"
 #include "tile_matrix.hpp"
 
 namespace dlaf_mi355x {

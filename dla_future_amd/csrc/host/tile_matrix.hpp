@@ -2,21 +2,13 @@
 // the triangular solver (solver.cpp) and the matrix the back-transformations act on (red2band.cpp).
 // Reference: matrix/matrix.h with a tileLayout (matrix/layout_info.h:140-159).
 #pragma once
+#include "distribution.hpp"
+#include "launch_args.hpp"
+#include "pool.hpp"
 #include "runtime.hpp"
+#include "transport.hpp"
 
 namespace dlaf_mi355x {
-
-// a device allocation that lives as long as its scope (empty until alloc())
-template <class T>
-struct DevBuf {
-  T* p = nullptr;
-  DevBuf() = default;
-  explicit DevBuf(size_t elems) { alloc(elems); }
-  DevBuf(const DevBuf&) = delete;
-  DevBuf& operator=(const DevBuf&) = delete;
-  ~DevBuf() { (void) hipFree(p); }
-  void alloc(size_t elems) { p = dev_alloc<T>(elems); }
-};
 
 // General block-cyclic matrix in device tile layout (nb x nb tiles, tile (il,jl) at (il + jl*ltr) nb^2).
 template <class T>
@@ -92,32 +84,15 @@ struct TileMatrix {
   int col_dim() const { return transposed ? 0 : 1; }
 
   LayoutArgs<T> layout(T* cm, long ld) const {
-    LayoutArgs<T> a;
-    a.tiles = tiles;
-    a.cm = cm;
-    a.ld_cm = ld;
-    a.ltr = (int) ltr;
-    a.ltc = (int) ltc;
-    a.nb = nb;
-    a.rows = rows.local_size();
-    a.cols = cols.local_size();
-    a.pr = rows.P;
-    a.ri = rows.shift();
-    a.pc = cols.P;
-    a.ci = cols.shift();
-    a.transpose = transposed ? 1 : 0;
+    LayoutArgs<T> a = layout_args(*this, cm, ld);
     a.full = 1;
     a.rev_rows = rev_rows ? 1 : 0;
     a.rev_cols = rev_cols ? 1 : 0;
     return a;
   }
-  void source_extents(long& srows, long& scols) const {
-    srows = transposed ? cols.local_size() : rows.local_size();
-    scols = transposed ? rows.local_size() : cols.local_size();
-  }
   void upload(const T* host, long ld, bool conj, bool scale, T alpha, hipStream_t s) {
     long srows, scols;
-    source_extents(srows, scols);
+    source_extents(*this, srows, scols);
     if (srows == 0 || scols == 0)
       return;
     if (!staging)
@@ -132,7 +107,7 @@ struct TileMatrix {
   }
   void download(T* host, long ld, bool conj, hipStream_t s) {
     long srows, scols;
-    source_extents(srows, scols);
+    source_extents(*this, srows, scols);
     if (srows == 0 || scols == 0)
       return;
     if (!staging)

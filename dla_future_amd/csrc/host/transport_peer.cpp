@@ -30,6 +30,7 @@
 #include <vector>
 
 #include "runtime.hpp"
+#include "transport.hpp"
 
 namespace dlaf_mi355x {
 

@@ -11,6 +11,7 @@
 #include <cstring>
 
 #include "runtime.hpp"
+#include "transport.hpp"
 
 namespace dlaf_mi355x {
 

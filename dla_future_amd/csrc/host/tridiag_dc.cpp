@@ -13,6 +13,7 @@
 #include "../device/band_api.hpp"
 #include "../device/tridiag_dc.hpp"
 #include "eigensolver.hpp"
+#include "pool.hpp"
 
 namespace dlaf_mi355x {
 

@@ -7,24 +7,12 @@
 #include <dlaf_mi355x/dlaf_mi355x.h>
 
 #include "../device/trsm_path.hpp"
-#include "runtime.hpp"
-#include "tile_matrix.hpp"
+#include "direct.hpp"
+#include "direct_operand.hpp"
 
 namespace dlaf_mi355x {
 
 namespace {
-
-// an operand's host array `off` elements into a device allocation of its own
-template <class T>
-struct Operand {
-  DevBuf<T> buf;
-  T* p = nullptr;
-  void put(const void* host, long elems, long off, hipStream_t s) {
-    buf.alloc((size_t) (elems + off));
-    p = buf.p + off;
-    DLAF_HIP_CHECK(hipMemcpyAsync(p, host, (size_t) elems * sizeof(T), hipMemcpyHostToDevice, s));
-  }
-};
 
 // Every element the launches may touch lies inside its operand?  Walks the tiles and extents the contract names
 // (TrsmArgs, launch_potrf_diag and launch_invert_diag_blocks in device_api.hpp), not the kernels' blocks.

@@ -6,9 +6,10 @@
 
 #include <dlaf_mi355x/dlaf_mi355x.h>
 
+#include "device_matrix.hpp"
+#include "direct.hpp"
+#include "direct_operand.hpp"
 #include "launch_args.hpp"
-#include "runtime.hpp"
-#include "tile_matrix.hpp"
 
 namespace dlaf_mi355x {
 
@@ -22,29 +23,6 @@ struct TileGrid {
   long ltr, ltc;
   int nb;
   Axis rows, cols;
-};
-
-// an operand's host array `off` elements into a device allocation of its own
-template <class T>
-struct Operand {
-  DevBuf<T> buf;
-  T* p = nullptr;
-  void put(const void* host, long elems, long off, hipStream_t s) {
-    buf.alloc((size_t) (elems + off));
-    p = buf.p + off;
-    if (elems > 0)
-      DLAF_HIP_CHECK(hipMemcpyAsync(p, host, (size_t) elems * sizeof(T), hipMemcpyHostToDevice, s));
-  }
-  // this operand and, behind it in the SAME allocation (16 elements apart at least in alignment), `hi`: p < hi.p
-  void put_below(const void* host, long elems, long off, Operand& hi, const void* hi_host, long hi_elems, long hi_off,
-                 hipStream_t s) {
-    const long span = (off + elems + 15) / 16 * 16;
-    buf.alloc((size_t) (span + hi_off + hi_elems));
-    p = buf.p + off;
-    hi.p = buf.p + span + hi_off;
-    DLAF_HIP_CHECK(hipMemcpyAsync(p, host, (size_t) elems * sizeof(T), hipMemcpyHostToDevice, s));
-    DLAF_HIP_CHECK(hipMemcpyAsync(hi.p, hi_host, (size_t) hi_elems * sizeof(T), hipMemcpyHostToDevice, s));
-  }
 };
 
 // Every element the launch may touch lies inside its operand?  Walks the tiles the kernel's contract names
@@ -107,16 +85,6 @@ bool in_bounds(const UpdateArgs<T>& ua, const dlaf_mi355x_update_desc& d) {
 }
 
 }  // namespace
-
-template <class T>
-long update_bulk_slots() {
-  runtime_init();
-  hipDeviceProp_t prop;
-  int dev = 0;
-  DLAF_HIP_CHECK(hipGetDevice(&dev));
-  DLAF_HIP_CHECK(hipGetDeviceProperties(&prop, dev));
-  return (long) prop.multiProcessorCount * update_blocks_per_cu<T>();
-}
 
 template <class T>
 int update_direct(dlaf_mi355x_update_desc& d, void* c, const void* a, const void* b, const void* a2, const void* b2,
@@ -230,8 +198,7 @@ int update_direct(dlaf_mi355x_update_desc& d, void* c, const void* a, const void
   return 0;
 }
 
-#define INST(T)                                  \
-  template long update_bulk_slots<T>();          \
+#define INST(T) \
   template int update_direct<T>(dlaf_mi355x_update_desc&, void*, const void*, const void*, const void*, const void*, void*);
 INST(float)
 INST(double)

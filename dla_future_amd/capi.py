@@ -143,6 +143,14 @@ SIGNATURES = {
     "dlaf_mi355x_pdsymm": (None, [_ch, _ch, _i, _i, _vp, _vp, _i, _i, _IP, _vp, _i, _i, _IP, _vp, _vp, _i, _i, _IP]),
     "dlaf_mi355x_pchemm": (None, [_ch, _ch, _i, _i, _vp, _vp, _i, _i, _IP, _vp, _i, _i, _IP, _vp, _vp, _i, _i, _IP]),
     "dlaf_mi355x_pzhemm": (None, [_ch, _ch, _i, _i, _vp, _vp, _i, _i, _IP, _vp, _i, _i, _IP, _vp, _vp, _i, _i, _IP]),
+    "dlaf_mi355x_general_multiplication_s": (_i, [_i, _ch, _ch, _vp, _vp, DLAFDescriptor, _vp, DLAFDescriptor, _vp, _vp, DLAFDescriptor]),
+    "dlaf_mi355x_general_multiplication_d": (_i, [_i, _ch, _ch, _vp, _vp, DLAFDescriptor, _vp, DLAFDescriptor, _vp, _vp, DLAFDescriptor]),
+    "dlaf_mi355x_general_multiplication_c": (_i, [_i, _ch, _ch, _vp, _vp, DLAFDescriptor, _vp, DLAFDescriptor, _vp, _vp, DLAFDescriptor]),
+    "dlaf_mi355x_general_multiplication_z": (_i, [_i, _ch, _ch, _vp, _vp, DLAFDescriptor, _vp, DLAFDescriptor, _vp, _vp, DLAFDescriptor]),
+    "dlaf_mi355x_psgemm": (None, [_ch, _ch, _i, _i, _i, _vp, _vp, _i, _i, _IP, _vp, _i, _i, _IP, _vp, _vp, _i, _i, _IP]),
+    "dlaf_mi355x_pdgemm": (None, [_ch, _ch, _i, _i, _i, _vp, _vp, _i, _i, _IP, _vp, _i, _i, _IP, _vp, _vp, _i, _i, _IP]),
+    "dlaf_mi355x_pcgemm": (None, [_ch, _ch, _i, _i, _i, _vp, _vp, _i, _i, _IP, _vp, _i, _i, _IP, _vp, _vp, _i, _i, _IP]),
+    "dlaf_mi355x_pzgemm": (None, [_ch, _ch, _i, _i, _i, _vp, _vp, _i, _i, _IP, _vp, _i, _i, _IP, _vp, _vp, _i, _i, _IP]),
     "dlaf_mi355x_pspotrs": (None, [_ch, _i, _i, _vp, _i, _i, _IP, _vp, _i, _i, _IP, _IP]),
     "dlaf_mi355x_pdpotrs": (None, [_ch, _i, _i, _vp, _i, _i, _IP, _vp, _i, _i, _IP, _IP]),
     "dlaf_mi355x_pcpotrs": (None, [_ch, _i, _i, _vp, _i, _i, _IP, _vp, _i, _i, _IP, _IP]),
@@ -156,6 +164,7 @@ SIGNATURES = {
     "dlaf_mi355x_triangular_solver_device": (_i, [_ch, _ch, _ch, _ch, _vp, _vp, _vp]),
     "dlaf_mi355x_triangular_multiplication_device": (_i, [_ch, _ch, _ch, _ch, _vp, _vp, _vp]),
     "dlaf_mi355x_hermitian_multiplication_device": (_i, [_ch, _ch, _vp, _vp, _vp, _vp, _vp]),
+    "dlaf_mi355x_general_multiplication_device": (_i, [_ch, _ch, _vp, _vp, _vp, _vp, _vp]),
     "dlaf_mi355x_potrs_device": (_i, [_ch, _vp, _vp]),
     "dlaf_mi355x_generalized_to_standard_s": (_i, [_i, _ch, _vp, DLAFDescriptor, _vp, DLAFDescriptor]),
     "dlaf_mi355x_generalized_to_standard_d": (_i, [_i, _ch, _vp, DLAFDescriptor, _vp, DLAFDescriptor]),

@@ -274,8 +274,49 @@ def pxhemm(side: str, uplo: str, m: int, n: int, alpha, a: np.ndarray, ia: int, 
                          _ptr(be), _ptr(c), ic, jc, dc)
 
 
+def general_multiplication(grid: Grid, opa: str, opb: str, alpha, a: np.ndarray, b: np.ndarray, beta, c: np.ndarray,
+                           nb: int, m: int | None = None, n: int | None = None, k: int | None = None, a_src=(0, 0),
+                           b_src=(0, 0), c_src=(0, 0)) -> None:
+    """dlaf::multiplication::internal::generalMatrix(opA, opB, alpha, A, B, beta, C) (include/dlaf/multiplication/general.h)
+    == dlaf_mi355x_general_multiplication_{s,d,c,z}: C = beta C + alpha op(A) op(B), op 'N', 'T' or 'C'.  `a`, `b`, `c`:
+    this process's local column-major parts of the matrices as stored (A is m x k for 'N', k x m otherwise; B is k x n
+    for 'N', n x k otherwise); `c` is overwritten.  nb: the square block of all three.  On a grid of more than one
+    process only 'N' 'N' is built, m, n, k are required, A must start on C's process row and B on C's process column."""
+    t = type_char(c.dtype)
+    if a.dtype != c.dtype or b.dtype != c.dtype:
+        raise ValueError("A, B and C must have the same element type")
+    an, bn = opa.upper() == "N", opb.upper() == "N"
+    if m is None or n is None or k is None:
+        if grid.nranks != 1:
+            raise ValueError("the global sizes m, n, k are required on a distributed grid")
+        m, n = c.shape
+        k = a.shape[1] if an else a.shape[0]
+    da = DLAFDescriptor(m if an else k, k if an else m, nb, nb, a_src[0], a_src[1], 0, 0, _ld_of(a))
+    db = DLAFDescriptor(k if bn else n, n if bn else k, nb, nb, b_src[0], b_src[1], 0, 0, _ld_of(b))
+    dc = DLAFDescriptor(m, n, nb, nb, c_src[0], c_src[1], 0, 0, _ld_of(c))
+    al = np.array([alpha], dtype=c.dtype)
+    be = np.array([beta], dtype=c.dtype)
+    fn = getattr(lib(), f"dlaf_mi355x_general_multiplication_{t}")
+    r = fn(grid.context, opa.encode(), opb.encode(), _ptr(al), _ptr(a), da, _ptr(b), db, _ptr(be), _ptr(c), dc)
+    if r != 0:
+        raise ValueError(f"dlaf_mi355x_general_multiplication_{t} failed with {r}")
+
+
+def pxgemm(transa: str, transb: str, m: int, n: int, k: int, alpha, a: np.ndarray, ia: int, ja: int, desca,
+           b: np.ndarray, ib: int, jb: int, descb, beta, c: np.ndarray, ic: int, jc: int, descc) -> None:
+    """dlaf_mi355x_p{s,d,c,z}gemm: ScaLAPACK's argument list (9-int descriptors)."""
+    t = type_char(c.dtype)
+    da = (C.c_int * 9)(*[int(x) for x in desca])
+    db = (C.c_int * 9)(*[int(x) for x in descb])
+    dc = (C.c_int * 9)(*[int(x) for x in descc])
+    al = np.array([alpha], dtype=c.dtype)
+    be = np.array([beta], dtype=c.dtype)
+    getattr(lib(), f"dlaf_mi355x_p{t}gemm")(transa.encode(), transb.encode(), m, n, k, _ptr(al), _ptr(a), ia, ja, da,
+                                            _ptr(b), ib, jb, db, _ptr(be), _ptr(c), ic, jc, dc)
+
+
 def multiplication_profile():
-    """(ms, flops) of the sweep of the last multiplication (triangular or Hermitian) on this process (device time, no
+    """(ms, flops) of the sweep of the last multiplication (triangular, Hermitian or general) on this process (device time, no
     staging)."""
     ms, fl = C.c_double(0), C.c_double(0)
     lib().dlaf_mi355x_multiplication_profile(C.byref(ms), C.byref(fl))
@@ -592,6 +633,17 @@ def hermitian_multiplication_device(side: str, uplo: str, alpha, a: DeviceMatrix
                                                           c._h)
     if r != 0:
         raise ValueError(f"dlaf_mi355x_hermitian_multiplication_device failed with {r}")
+
+
+def general_multiplication_device(opa: str, opb: str, alpha, a: GeneralDeviceMatrix, b: GeneralDeviceMatrix, beta,
+                                  c: GeneralDeviceMatrix) -> None:
+    """general_multiplication on resident operands: C = beta C + alpha op(A) op(B) on three general resident matrices
+    (`a`, `b` as stored); only `c` is written; no PCIe traffic."""
+    al = np.array([alpha], dtype=c.dtype)
+    be = np.array([beta], dtype=c.dtype)
+    r = lib().dlaf_mi355x_general_multiplication_device(opa.encode(), opb.encode(), _ptr(al), a._h, b._h, _ptr(be), c._h)
+    if r != 0:
+        raise ValueError(f"dlaf_mi355x_general_multiplication_device failed with {r}")
 
 
 def potrs_device(uplo: str, factor: DeviceMatrix, b: GeneralDeviceMatrix) -> None:

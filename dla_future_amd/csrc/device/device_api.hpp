@@ -174,6 +174,35 @@ template <class T>
 void launch_hemm(const HemmArgs<T>& args, hipStream_t stream);
 
 // ------------------------------------------------------------------------------------------
+// General multiplication (kernels_gemm.hip):  C(il, jl) = [first ? beta : 1] C(il, jl) + alpha sum_t opA(A)(il, t)
+// opB(B)(t, jl) over the nk tiles t of the k dimension, for every local tile of C in ONE launch; a block of C stays in
+// the accumulators over all of them.  The operands are tiles AS STORED (leading dimension nb), whatever the op:
+//   opa N: the m x k tile of (il, t) at a + il a_ts + t a_ks;   T / C: the k x m tile of (t, il) at the same address
+//   opb N: the k x n tile of (t, jl) at b + jl b_ts + t b_ks;   T / C: the n x k tile of (jl, t) at the same address
+// Every k tile has nb values of k but the last, which has k_last.  nk == 0: C = beta C (first) and a, b are not read.
+// first != 0 with beta == 0: C is not read.  (GemmArgs / launch_gemm, band_api.hpp, is the single product of two
+// column-major matrices of the eigensolver stages.)
+template <class T>
+struct GeneralArgs {
+  T* c;
+  long c_tsr, c_tsc;
+  const T* a;
+  long a_ts, a_ks;
+  const T* b;
+  long b_ts, b_ks;
+  char opa = 'N', opb = 'N';
+  int nk, k_last;
+  int ltr, ltc;   // local tiles of C
+  int nb;         // tile size = leading dimension of every tile
+  int pr, ri, nt_r, last_rows;
+  int pc, ci, nt_c, last_cols;
+  T alpha, beta;
+  int first = 1;
+};
+template <class T>
+void launch_general(const GeneralArgs<T>& args, hipStream_t stream);
+
+// ------------------------------------------------------------------------------------------
 // Diagonal-tile work of triangular_inverse / inverse_from_cholesky_factor (kernels_inverse.hip).  A batch of
 // `count` lower triangular tiles, tile t at base + t * stride (leading dimension ld), each nb x nb except the last,
 // which is last x last.

@@ -346,6 +346,7 @@ void update_kernels_init();
 void trsm_kernels_init();
 void trmm_kernels_init();
 void hemm_kernels_init();
+void gemm_kernels_init();
 void inverse_kernels_init();
 void potrf_kernels_init();
 void potrf_coop_kernels_init();
@@ -358,6 +359,7 @@ void device_kernels_init() {
   trsm_kernels_init();
   trmm_kernels_init();
   hemm_kernels_init();
+  gemm_kernels_init();
   inverse_kernels_init();
   potrf_kernels_init();
   potrf_coop_kernels_init();

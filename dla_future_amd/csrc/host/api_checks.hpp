@@ -77,6 +77,45 @@ inline void require_band(const char* who, int band, int nb) {
     fatal("[dlaf_mi355x] %s: band_size %d must be >= 2 and divide the block size %d\n", who, band, nb);
 }
 
+// ---- general multiplication  C = beta C + alpha op(A) op(B): one judgement for the descriptor entries and the resident
+// one.  Every operand as (rows, columns, row block, column block, source process) of the matrix AS STORED.
+struct GemmOperand {
+  long m, n;
+  int mb, nb;
+  int isrc, jsrc;
+};
+inline GemmOperand gemm_operand(const DLAF_descriptor& d) {
+  return {d.m, d.n, d.mb, d.nb, d.isrc, d.jsrc};
+}
+inline bool is_notrans(char c) { return in_set(c, "Nn"); }
+// Terminates unless: both ops are letters; one square block for the three matrices; op(A) is m x k, op(B) k x n for C's
+// m x n; every source inside the grid; on a grid of more than one process both ops are 'N' (the transposed forms need
+// the two-hop transposed-panel broadcast, which is not built), A starts on C's process row and B on C's process column.
+template <class GridT>
+void require_general_multiplication(const char* who, const GridT& g, char opa, char opb, const GemmOperand& a,
+                                    const GemmOperand& b, const GemmOperand& c) {
+  if (!is_op(opa) || !is_op(opb))
+    fatal("[dlaf_mi355x] %s: bad opa/opb '%c' '%c'\n", who, opa, opb);
+  if (a.mb != a.nb || b.mb != b.nb || c.mb != c.nb || a.nb != c.nb || b.nb != c.nb || c.nb < 1)
+    fatal("[dlaf_mi355x] %s: A, B and C need one square block (A %d x %d, B %d x %d, C %d x %d)\n", who, a.mb, a.nb,
+          b.mb, b.nb, c.mb, c.nb);
+  const long am = is_notrans(opa) ? a.m : a.n, ak = is_notrans(opa) ? a.n : a.m;
+  const long bk = is_notrans(opb) ? b.m : b.n, bn = is_notrans(opb) ? b.n : b.m;
+  if (c.m < 0 || c.n < 0 || ak < 0 || am != c.m || bn != c.n || ak != bk)
+    fatal("[dlaf_mi355x] %s: op(A) is %ld x %ld (op '%c'), op(B) is %ld x %ld (op '%c'), C is %ld x %ld\n", who, am, ak,
+          opa, bk, bn, opb, c.m, c.n);
+  for (const GemmOperand* o : {&a, &b, &c})
+    if (!source_in_grid(g.nprow, g.npcol, o->isrc, o->jsrc))
+      fatal("[dlaf_mi355x] %s: source rank (%d,%d) outside the %d x %d grid\n", who, o->isrc, o->jsrc, g.nprow, g.npcol);
+  if (g.nprow * g.npcol > 1 && (!is_notrans(opa) || !is_notrans(opb)))
+    fatal("[dlaf_mi355x] %s: opa '%c', opb '%c' on a %d x %d grid: only 'N' 'N' is built on more than one process\n", who,
+          opa, opb, g.nprow, g.npcol);
+  if (a.isrc != c.isrc)
+    fatal("[dlaf_mi355x] %s: A must start on C's process row (source row %d vs %d)\n", who, a.isrc, c.isrc);
+  if (b.jsrc != c.jsrc)
+    fatal("[dlaf_mi355x] %s: B must start on C's process column (source column %d vs %d)\n", who, b.jsrc, c.jsrc);
+}
+
 // ---- the prologue of a ScaLAPACK argument list: every operand as (name letter, desc, row offset, column offset)
 struct ScalapackOperand {
   char name;

@@ -152,6 +152,31 @@ int dlaf_mi355x_hermitian_multiplication_device(char side, char uplo, const void
   return hermitian_multiplication_device(side, uplo, alpha, a->m.get(), b->m.get(), beta, c->m.get());
 }
 
+int dlaf_mi355x_general_multiplication_device(char opa, char opb, const void* alpha, dlaf_mi355x_gmatrix_t a,
+                                              dlaf_mi355x_gmatrix_t b, const void* beta,
+                                              dlaf_mi355x_gmatrix_t c) noexcept {
+  const char* who = "general multiplication";
+  if (!a || !a->m || !b || !b->m || !c || !c->m || !alpha || !beta)
+    return -1;
+  if (a->ctx != b->ctx || a->ctx != c->ctx)
+    fatal("[dlaf_mi355x] %s: A, B and C live on different contexts (%d, %d, %d)\n", who, a->ctx, b->ctx, c->ctx);
+  if (a->m->type != c->m->type || b->m->type != c->m->type)
+    fatal("[dlaf_mi355x] %s: operands of different element types ('%c', '%c', '%c')\n", who, a->m->type, b->m->type,
+          c->m->type);
+  auto operand = [](dlaf_mi355x_gmatrix_t h) {
+    GemmOperand o{};
+    (void) dispatch_api_type(h->m->type, [&](auto* tag) {
+      using DT = std::remove_pointer_t<decltype(tag)>;
+      const auto& gm = static_cast<GeneralMatrix<DT>&>(*h->m);
+      o = GemmOperand{gm.rows_g, gm.cols_g, gm.m.nb, gm.m.nb, gm.isrc, gm.jsrc};
+      return 0;
+    });
+    return o;
+  };
+  require_general_multiplication(who, grid_from_context(c->ctx), opa, opb, operand(a), operand(b), operand(c));
+  return general_multiplication_device(opa, opb, alpha, a->m.get(), b->m.get(), beta, c->m.get());
+}
+
 int dlaf_mi355x_multiplication_profile(double* ms, double* flops) noexcept {
   multiplication_last_profile(ms, flops);
   return 0;

@@ -1,6 +1,6 @@
 // c_api_host.cpp -- the extern "C" surface, part 2 of 3 (c_api_internal.hpp has the map): the entries that take
-// descriptors or ScaLAPACK argument lists over host memory -- triangular solver and multiplication, Hermitian
-// multiplication, p?potrs, generalized to standard, the inverses, the norms, reduction to band and the eigensolver
+// descriptors or ScaLAPACK argument lists over host memory -- triangular solver and multiplication, Hermitian and
+// general multiplication, p?potrs, generalized to standard, the inverses, the norms, reduction to band and the eigensolver
 // stages and drivers (include/dlaf_c/eigensolver/*.h as upstream, include/dlaf_mi355x/dlaf_mi355x.h).  Every argument
 // is judged (api_checks.hpp) before anything touches the GPU.
 #define DLAF_MI355X_NO_MPI 1  // as in c_api.cpp: no <mpi.h> in the core
@@ -145,6 +145,40 @@ void pxhemm(char side, char uplo, int m, int n, const HT* alpha, const HT* a, in
   const DLAF_descriptor db = make_dlaf_descriptor(m, n, ib, jb, descb);
   const DLAF_descriptor dc = make_dlaf_descriptor(m, n, ic, jc, descc);
   (void) hermitian_multiplication_c<HT>(ctx, side, uplo, alpha, a, da, b, db, beta, c, dc);
+}
+
+// dlaf::multiplication::internal::generalMatrix (include/dlaf/multiplication/general.h) through descriptors:
+// C = beta C + alpha op(A) op(B), a / b / c described as stored; every argument judged before the GPU is touched
+template <class HT>
+int general_multiplication_c(int ctx, char opa, char opb, const HT* alpha, const HT* a, const DLAF_descriptor& da,
+                             const HT* b, const DLAF_descriptor& db, const HT* beta, HT* c, const DLAF_descriptor& dc) {
+  using DT = typename DevType<HT>::type;
+  const char* who = "general multiplication";
+  if (da.i != 0 || da.j != 0 || db.i != 0 || db.j != 0 || dc.i != 0 || dc.j != 0)
+    fatal("[dlaf_mi355x] %s: sub-matrices are not supported: offsets must be 0\n", who);
+  Grid& g = grid_from_context(ctx);
+  require_general_multiplication(who, g, opa, opb, gemm_operand(da), gemm_operand(db), gemm_operand(dc));
+  DT al, be;
+  std::memcpy(&al, alpha, sizeof(DT));
+  std::memcpy(&be, beta, sizeof(DT));
+  const long k = is_notrans(opa) ? da.n : da.m;
+  return general_multiplication_host<DT>(&g, opa, opb, al, reinterpret_cast<const DT*>(a), da.ld, da.isrc, da.jsrc,
+                                         reinterpret_cast<const DT*>(b), db.ld, db.isrc, db.jsrc, be,
+                                         reinterpret_cast<DT*>(c), dc.ld, dc.m, dc.n, k, dc.nb, dc.isrc, dc.jsrc);
+}
+
+// ScaLAPACK p?gemm argument list
+template <class HT>
+void pxgemm(char transa, char transb, int m, int n, int k, const HT* alpha, const HT* a, int ia, int ja,
+            const int desca[9], const HT* b, int ib, int jb, const int descb[9], const HT* beta, HT* c, int ic, int jc,
+            const int descc[9]) {
+  const int ctx = require_scalapack_args({{'A', desca, ia, ja}, {'B', descb, ib, jb}, {'C', descc, ic, jc}},
+                                         "general multiplication");
+  const bool an = is_notrans(transa), bn = is_notrans(transb);
+  const DLAF_descriptor da = make_dlaf_descriptor(an ? m : k, an ? k : m, ia, ja, desca);
+  const DLAF_descriptor db = make_dlaf_descriptor(bn ? k : n, bn ? n : k, ib, jb, descb);
+  const DLAF_descriptor dc = make_dlaf_descriptor(m, n, ic, jc, descc);
+  (void) general_multiplication_c<HT>(ctx, transa, transb, alpha, a, da, b, db, beta, c, dc);
 }
 
 // ScaLAPACK p?potrs: solve A X = B with the factor p?potrf left in a (uplo L: L L^H, uplo U: U^H U)
@@ -488,6 +522,26 @@ DLAF_MI355X_HEMM_ENTRY(d, double, double, symm)
 DLAF_MI355X_HEMM_ENTRY(c, std::complex<float>, dlaf_complex_c, hemm)
 DLAF_MI355X_HEMM_ENTRY(z, std::complex<double>, dlaf_complex_z, hemm)
 #undef DLAF_MI355X_HEMM_ENTRY
+#define DLAF_MI355X_GEMM_ENTRY(S, HT, CT)                                                                         \
+  int dlaf_mi355x_general_multiplication_##S(int ctx, char opa, char opb, const CT* alpha, const CT* a,             \
+                                             DLAF_descriptor desca, const CT* b, DLAF_descriptor descb,            \
+                                             const CT* beta, CT* c, DLAF_descriptor descc) noexcept {              \
+    return general_multiplication_c<HT>(ctx, opa, opb, reinterpret_cast<const HT*>(alpha),                          \
+                                        reinterpret_cast<const HT*>(a), desca, reinterpret_cast<const HT*>(b),     \
+                                        descb, reinterpret_cast<const HT*>(beta), reinterpret_cast<HT*>(c), descc); \
+  }                                                                                                             \
+  void dlaf_mi355x_p##S##gemm(char transa, char transb, int m, int n, int k, const CT* alpha, const CT* a, int ia,  \
+                              int ja, const int desca[9], const CT* b, int ib, int jb, const int descb[9],          \
+                              const CT* beta, CT* c, int ic, int jc, const int descc[9]) noexcept {               \
+    pxgemm<HT>(transa, transb, m, n, k, reinterpret_cast<const HT*>(alpha), reinterpret_cast<const HT*>(a), ia, ja, \
+               desca, reinterpret_cast<const HT*>(b), ib, jb, descb, reinterpret_cast<const HT*>(beta),            \
+               reinterpret_cast<HT*>(c), ic, jc, descc);                                                          \
+  }
+DLAF_MI355X_GEMM_ENTRY(s, float, float)
+DLAF_MI355X_GEMM_ENTRY(d, double, double)
+DLAF_MI355X_GEMM_ENTRY(c, std::complex<float>, dlaf_complex_c)
+DLAF_MI355X_GEMM_ENTRY(z, std::complex<double>, dlaf_complex_z)
+#undef DLAF_MI355X_GEMM_ENTRY
 #define DLAF_MI355X_POTRS_ENTRY(S, HT, CT)                                                                       \
   void dlaf_mi355x_p##S##potrs(char uplo, int n, int nrhs, const CT* a, int ia, int ja, const int desca[9], CT* b,  \
                                int ib, int jb, const int descb[9], int* info) noexcept {                        \

@@ -1,5 +1,5 @@
 // drivers.hpp -- what the algorithms on top of the tile kernels export: the triangular solver (solver.cpp), the
-// triangular and Hermitian multiplications (multiplication.cpp), generalized-to-standard (gen_to_std.cpp), the inverses
+// triangular, Hermitian and general multiplications (multiplication.cpp), generalized-to-standard (gen_to_std.cpp), the inverses
 // (inverse.cpp) and the norms (norm.cpp), host and device-resident forms.  reduction_to_band and the eigensolver stages
 // have headers of their own (red2band.hpp, eigensolver.hpp).
 #pragma once
@@ -31,7 +31,7 @@ int triangular_multiplication_host(Grid* g, char side, char uplo, char op, char 
                                    int nb_free = 0);
 int triangular_multiplication_device(char side, char uplo, char op, char diag, const void* alpha, MatrixBase* a,
                                      MatrixBase* b);
-// device time and whole-grid flops of the last sweep of EITHER multiplication (triangular or Hermitian) on this process
+// device time and whole-grid flops of the last sweep of ANY multiplication (triangular, Hermitian, general) on this process
 void multiplication_last_profile(double* ms, double* flops);
 
 // C = beta C + alpha A B (side L) / beta C + alpha B A (side R), A Hermitian with only its uplo triangle read
@@ -44,6 +44,16 @@ int hermitian_multiplication_host(Grid* g, char side, char uplo, T alpha, const 
                                   int nb_free = 0);
 int hermitian_multiplication_device(char side, char uplo, const void* alpha, MatrixBase* a, MatrixBase* b,
                                     const void* beta, MatrixBase* c);
+
+// C = beta C + alpha op(A) op(B) (multiplication.cpp; dlaf::multiplication::internal::generalMatrix, every op pair on
+// one process, N x N on a grid).  a, b, c: the matrices as stored (A m x k or k x m, B k x n or n x k), one square block
+// nb.  The arguments must have passed require_general_multiplication (api_checks.hpp).  Host and resident forms.
+template <class T>
+int general_multiplication_host(Grid* g, char opa, char opb, T alpha, const T* a, long lda, int a_isrc, int a_jsrc,
+                                const T* b, long ldb, int b_isrc, int b_jsrc, T beta, T* c, long ldc, long m, long n,
+                                long k, int nb, int c_isrc, int c_jsrc);
+int general_multiplication_device(char opa, char opb, const void* alpha, MatrixBase* a, MatrixBase* b, const void* beta,
+                                  MatrixBase* c);
 
 // A <- L^-1 A L^-H (uplo L) / U^-H A U^-1 (uplo U) with the Cholesky factor held in the same uplo triangle of
 // `l` (gen_to_std.cpp; dlaf::eigensolver::internal::generalized_to_standard); device-resident and host forms

@@ -1,10 +1,12 @@
 // multiplication.cpp -- distributed triangular multiplication  B = alpha op(A) B  /  B = alpha B op(A)  on the tile
-// kernels of the triangular solver, and (second half) the Hermitian multiplication  C = beta C + alpha A B  /
-// beta C + alpha B A  on its own step kernel.
+// kernels of the triangular solver, (second part) the Hermitian multiplication  C = beta C + alpha A B  /
+// beta C + alpha B A  on its own step kernel, and (third part) the general multiplication  C = beta C + alpha op(A) op(B)
+// on a kernel that keeps a block of C in its accumulators over the k dimension.
 //
 // Reference: dlaf::triangular_multiplication (include/dlaf/multiplication/triangular.h) and its hand-written
 // variants (multiplication/triangular/impl.h); dlaf::hermitian_multiplication (include/dlaf/multiplication/hermitian.h),
-// which implements side L / uplo L only and reduces a panel of C along process columns at every step.
+// which implements side L / uplo L only and reduces a panel of C along process columns at every step;
+// dlaf::multiplication::internal::generalMatrix (include/dlaf/multiplication/general.h), NoTrans x NoTrans.
 //
 // MI355X design: the solver's operand mapping (solver.cpp header: side / op decide T and B_dev, the relayout
 // transposes, conjugates and scales) turns every combination into ONE device algorithm,
@@ -22,6 +24,7 @@
 #include <type_traits>
 #include <vector>
 
+#include "../device/gemm_forms.hpp"
 #include "drivers.hpp"
 #include "sweep.hpp"
 #include "tile_matrix.hpp"
@@ -278,6 +281,127 @@ void hermitian_canonical(TileMatrix<T>& Hd, TileMatrix<T>& Xd, TileMatrix<T>& Yd
   g_last_mult_flops = (TypeInfo<T>::is_complex ? 8.0 : 2.0) * (double) Yd.rows_global * (double) Yd.cols.n * (double) Yd.cols.n;
 }
 
+// ================================================================================ general multiplication
+// C = beta C + alpha op(A) op(B).  Ad, Bd, Cd: the three matrices AS STORED (no view is transposed, nothing is
+// re-laid out); nkt: the tiles of the k dimension to multiply (0: k == 0 or alpha == 0 -- C = beta C, Ad and Bd are not
+// touched).  One process: ONE launch over all the k tiles, every op pair.  A grid (N x N only: the entries refuse the
+// rest) runs SUMMA, one step per k tile l, nothing reduced:
+//   column l of A      along the process rows from the owner column (bcast_view_column)       Cd.ltr tiles
+//   row l of B         packed, then down the process columns from the owner row               Cd.ltc tiles
+//   C += A(:, l) B(l, :)   one launch with nk = 1 (first: l == 0)
+// both broadcasts on s_comm one step ahead, into a ring of kBuf buffers per operand.  A starts on C's process row and B
+// on C's process column (the entries check); A's columns and B's rows need no common source.
+template <class T>
+void general_canonical(TileMatrix<T>& Ad, TileMatrix<T>& Bd, TileMatrix<T>& Cd, char opa, char opb, long k, long nkt,
+                       T alpha, T beta) {
+  Grid* g = Cd.grid;
+  Transport* tr = grid_transport(*g);
+  const bool dist = g->nranks > 1;
+  const bool an = gemm_op_is_n(opa), bn = gemm_op_is_n(opb);
+  const size_t tile_elems = Cd.tile_elems, tile_bytes = tile_elems * sizeof(T);
+  const Axis& ka = an ? Ad.cols : Ad.rows;  // the k axis as A has it (tile extents), and as B has it (owners)
+  const Axis& kb = bn ? Bd.rows : Bd.cols;
+
+  GeneralArgs<T> ga;
+  ga.c = Cd.tiles;
+  ga.c_tsr = (long) tile_elems;
+  ga.c_tsc = (long) (tile_elems * Cd.ltr);
+  ga.opa = opa;
+  ga.opb = opb;
+  ga.ltr = (int) Cd.ltr;
+  ga.ltc = (int) Cd.ltc;
+  ga.nb = Cd.nb;
+  ga.pr = Cd.rows.P;
+  ga.ri = Cd.rows.shift();
+  ga.nt_r = (int) Cd.rows.nt();
+  ga.last_rows = Cd.rows.last_extent();
+  ga.pc = Cd.cols.P;
+  ga.ci = Cd.cols.shift();
+  ga.nt_c = (int) Cd.cols.nt();
+  ga.last_cols = Cd.cols.last_extent();
+  ga.alpha = alpha;
+  ga.beta = beta;
+  ga.a = ga.b = nullptr;
+  ga.a_ts = ga.a_ks = ga.b_ts = ga.b_ks = 0;
+  ga.nk = 0;
+  ga.k_last = 0;
+  const bool work = Cd.ltr > 0 && Cd.ltc > 0;
+
+  Sweep sw(false, false);
+  const hipStream_t s_main = sw.s_main, s_comm = sw.s_comm;
+  if (nkt == 0 || !dist) {
+    sw.begin(false);
+    if (nkt > 0) {
+      // tile (i, t) of a stored m x k matrix: rows next to each other; tile (t, i) of a stored k x m one: columns
+      ga.a = Ad.tiles;
+      ga.a_ts = (long) (an ? tile_elems : tile_elems * Ad.ltr);
+      ga.a_ks = (long) (an ? tile_elems * Ad.ltr : tile_elems);
+      ga.b = Bd.tiles;
+      ga.b_ts = (long) (bn ? tile_elems * Bd.ltr : tile_elems);
+      ga.b_ks = (long) (bn ? tile_elems : tile_elems * Bd.ltr);
+      ga.nk = (int) nkt;
+      ga.k_last = ka.last_extent();
+    }
+    if (work)
+      launch_general(ga, s_main);
+  }
+  else {
+    // ev_in: the operands of step l are in place; ev_done: its launch is done, its buffers are free
+    Events ev_in((size_t) nkt), ev_done((size_t) nkt);
+    Ring<T> apanel((size_t) Cd.ltr * tile_elems, Ad.cols.P > 1), bpanel((size_t) Cd.ltc * tile_elems, Bd.rows.P > 1);
+    struct StepOperands {
+      const T* a = nullptr;
+      const T* b = nullptr;
+      long b_ts = 0;
+    };
+    std::vector<StepOperands> sop((size_t) nkt);
+    auto fetch = [&](long l) {
+      const int buf = (int) (l % kBuf);
+      if (l >= kBuf)
+        DLAF_HIP_CHECK(hipStreamWaitEvent(s_comm, ev_done[(size_t) (l - kBuf)], 0));
+      StepOperands& o = sop[(size_t) l];
+      o.a = bcast_view_column(tr, Ad, l, apanel[buf], s_comm);
+      if (Bd.rows.P > 1) {
+        // local tiles (lrow, 0 .. ltc) of Bd, one tile row, packed next to each other
+        if (kb.mine(l) && Bd.ltc > 0)
+          DLAF_HIP_CHECK(hipMemcpy2DAsync(bpanel[buf], tile_bytes, Bd.tile(kb.local_of(l), 0), (size_t) Bd.ltr * tile_bytes,
+                                          tile_bytes, (size_t) Bd.ltc, hipMemcpyDeviceToDevice, s_comm));
+        if (Bd.ltc > 0)
+          tr->bcast(CommAxis::Col, kb.owner(l), kb.rank, bpanel[buf], bpanel[buf], (size_t) Bd.ltc * tile_bytes, s_comm);
+        o.b = bpanel[buf];
+        o.b_ts = (long) tile_elems;
+      }
+      else {
+        o.b = Bd.tile(l, 0);
+        o.b_ts = (long) (tile_elems * Bd.ltr);
+      }
+      DLAF_HIP_CHECK(hipEventRecord(ev_in[(size_t) l], s_comm));
+    };
+
+    sw.begin(true);
+    fetch(0);
+    for (long l = 0; l < nkt; ++l) {
+      if (l + 1 < nkt)
+        fetch(l + 1);
+      DLAF_HIP_CHECK(hipStreamWaitEvent(s_main, ev_in[(size_t) l], 0));
+      if (work) {
+        ga.a = sop[(size_t) l].a;
+        ga.a_ts = (long) tile_elems;
+        ga.b = sop[(size_t) l].b;
+        ga.b_ts = sop[(size_t) l].b_ts;
+        ga.nk = 1;
+        ga.k_last = ka.tile_extent(l);
+        ga.first = l == 0 ? 1 : 0;
+        launch_general(ga, s_main);
+      }
+      DLAF_HIP_CHECK(hipEventRecord(ev_done[(size_t) l], s_main));
+    }
+  }
+  g_last_mult_ms = sw.finish();
+  // whole-grid algorithmic flops: 2 m n k (x4 complex)
+  g_last_mult_flops = (TypeInfo<T>::is_complex ? 8.0 : 2.0) * (double) Cd.rows.n * (double) Cd.cols.n * (double) k;
+}
+
 }  // namespace
 
 void multiplication_last_profile(double* ms, double* flops) {
@@ -413,9 +537,71 @@ int hermitian_multiplication_device(char side, char uplo, const void* alpha, Mat
   });
 }
 
+// C = beta C + alpha op(A) op(B) on host operands: this process's local column-major parts, the three matrices as
+// stored (A is m x k or k x m, B k x n or n x k), one square block nb.  The arguments have passed
+// require_general_multiplication (api_checks.hpp).  k == 0 or alpha == 0: A and B are not referenced (BLAS).
+template <class T>
+int general_multiplication_host(Grid* g, char opa, char opb, T alpha, const T* a, long lda, int a_isrc, int a_jsrc,
+                                const T* b, long ldb, int b_isrc, int b_jsrc, T beta, T* c, long ldc, long m, long n,
+                                long k, int nb, int c_isrc, int c_jsrc) {
+  if (m == 0 || n == 0)
+    return 0;
+  runtime_init();
+  (void) grid_transport(*g);
+  if (g->nranks > 1 && !g->transport)
+    fatal("[dlaf_mi355x] grid with %d ranks has no transport\n", g->nranks);
+  const bool an = gemm_op_is_n(opa), bn = gemm_op_is_n(opb);
+  const bool product = k > 0 && !is_zero(alpha);
+  hipStream_t s = nullptr;
+  DLAF_HIP_CHECK(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
+  {
+    TileMatrix<T> Ad, Bd, Cd;
+    Cd.create(g, false, m, n, nb, c_isrc, c_jsrc);
+    if (product) {
+      Ad.create(g, false, an ? m : k, an ? k : m, nb, a_isrc, a_jsrc);
+      Bd.create(g, false, bn ? k : n, bn ? n : k, nb, b_isrc, b_jsrc);
+      Ad.upload(a, lda, false, false, T{}, s);
+      Bd.upload(b, ldb, false, false, T{}, s);
+    }
+    if (!is_zero(beta))  // beta = 0: C is not read
+      Cd.upload(c, ldc, false, false, T{}, s);
+    DLAF_HIP_CHECK(hipStreamSynchronize(s));
+    general_canonical(Ad, Bd, Cd, opa, opb, k, product ? (k + nb - 1) / nb : 0, alpha, beta);
+    Cd.download(c, ldc, false, s);
+    DLAF_HIP_CHECK(hipStreamSynchronize(s));
+  }
+  DLAF_HIP_CHECK(hipStreamDestroy(s));
+  return 0;
+}
+
+// The same on three RESIDENT general matrices (arguments judged by the entry, c_api_device.cpp): the tiles are the
+// operands, only C's are written.
+int general_multiplication_device(char opa, char opb, const void* alpha, MatrixBase* a, MatrixBase* b, const void* beta,
+                                  MatrixBase* c) {
+  if (!a || !b || !c || a->type != b->type || a->type != c->type)
+    fatal("[dlaf_mi355x] general multiplication: operands of different element types\n");
+  return dispatch_type(a->type, [&](auto* tag) {
+    using T = std::remove_pointer_t<decltype(tag)>;
+    auto& A = static_cast<GeneralMatrix<T>&>(*a);
+    auto& B = static_cast<GeneralMatrix<T>&>(*b);
+    auto& C = static_cast<GeneralMatrix<T>&>(*c);
+    if (A.m.grid != C.m.grid || B.m.grid != C.m.grid)
+      fatal("[dlaf_mi355x] general multiplication: A, B and C live on different grids\n");
+    if (C.rows_g == 0 || C.cols_g == 0)
+      return 0;
+    const T al = *static_cast<const T*>(alpha), be = *static_cast<const T*>(beta);
+    const long k = gemm_op_is_n(opa) ? A.cols_g : A.rows_g;
+    const bool product = k > 0 && !is_zero(al);
+    general_canonical(A.m, B.m, C.m, opa, opb, k, product ? (k + C.m.nb - 1) / C.m.nb : 0, al, be);
+    return 0;
+  });
+}
+
 #define DLAF_MULT_INST(T)                                                                                          \
   template int hermitian_multiplication_host<T>(Grid*, char, char, T, const T*, long, int, int, const T*, long, T, T*, \
                                                 long, long, long, int, int, int, int);                                \
+  template int general_multiplication_host<T>(Grid*, char, char, T, const T*, long, int, int, const T*, long, int, int, \
+                                              T, T*, long, long, long, long, int, int, int);                          \
   template int triangular_multiplication_host<T>(Grid*, char, char, char, char, T, const T*, long, int, int, T*, long, \
                                                  long, long, int, int, int, int);
 DLAF_MULT_INST(float)

@@ -12,6 +12,8 @@
  *                                                                     // include/dlaf/multiplication/triangular.h
  *     dlaf::hermitian_multiplication<Backend::GPU, Device::GPU, T>(grid, side, uplo, alpha, a, b, beta, c);
  *                                                                     // include/dlaf/multiplication/hermitian.h
+ *     dlaf::multiplication::internal::generalMatrix<Backend::GPU, Device::GPU, T>(opA, opB, alpha, a, b, beta, c);
+ *                                                                     // include/dlaf/multiplication/general.h
  *
  * What differs from the reference, by design: there is no pika runtime (the calls are blocking, no pika::wait),
  * Backend::MC does not exist (the library has no CPU path: static_assert), Matrix<T, Device::CPU> stores its
@@ -473,6 +475,51 @@ void hermitian_multiplication(blas::Side side, blas::Uplo uplo, const T alpha, c
   comm::CommunicatorGrid grid = comm::CommunicatorGrid::single();
   hermitian_multiplication<B, D, T>(grid, side, uplo, alpha, mat_a, mat_b, beta, mat_c);
 }
+
+// include/dlaf/multiplication/general.h: C = beta C + alpha op(A) op(B) on host-resident operands, under the reference's
+// names.  Local matrices: every op pair (the reference: NoTrans x NoTrans).  The grid overload is NoTrans x NoTrans,
+// as in the reference.  mat_a and mat_b are the matrices as stored; one square block for the three.
+namespace multiplication::internal {
+template <Backend B, Device D, class T>
+void generalMatrix(comm::CommunicatorGrid& grid, blas::Op opA, blas::Op opB, const T alpha,
+                   const Matrix<T, Device::CPU>& mat_a, const Matrix<T, Device::CPU>& mat_b, const T beta,
+                   Matrix<T, Device::CPU>& mat_c) {
+  static_assert(B == Backend::GPU, "this library has no CPU backend");
+  auto desc_of = [](const auto& m) {
+    const auto& d = m.distribution();
+    return DLAF_descriptor{(int) d.size().rows(), (int) d.size().cols(), (int) d.block_size().rows(),
+                           (int) d.block_size().cols(), (int) d.source_rank_index().row(),
+                           (int) d.source_rank_index().col(), 0, 0, (int) m.ld()};
+  };
+  int r;
+  if constexpr (std::is_same_v<T, float>)
+    r = dlaf_mi355x_general_multiplication_s(grid.context(), (char) opA, (char) opB, &alpha, mat_a.ptr(), desc_of(mat_a),
+                                             mat_b.ptr(), desc_of(mat_b), &beta, mat_c.ptr(), desc_of(mat_c));
+  else if constexpr (std::is_same_v<T, double>)
+    r = dlaf_mi355x_general_multiplication_d(grid.context(), (char) opA, (char) opB, &alpha, mat_a.ptr(), desc_of(mat_a),
+                                             mat_b.ptr(), desc_of(mat_b), &beta, mat_c.ptr(), desc_of(mat_c));
+  else if constexpr (std::is_same_v<T, std::complex<float>>)
+    r = dlaf_mi355x_general_multiplication_c(grid.context(), (char) opA, (char) opB, &alpha, mat_a.ptr(), desc_of(mat_a),
+                                             mat_b.ptr(), desc_of(mat_b), &beta, mat_c.ptr(), desc_of(mat_c));
+  else
+    r = dlaf_mi355x_general_multiplication_z(grid.context(), (char) opA, (char) opB, &alpha, mat_a.ptr(), desc_of(mat_a),
+                                             mat_b.ptr(), desc_of(mat_b), &beta, mat_c.ptr(), desc_of(mat_c));
+  if (r != 0)
+    dlaf::internal::fail("generalMatrix");
+}
+// the reference's two signatures: local matrices with ops, a grid without (NoTrans x NoTrans)
+template <Backend B, Device D, class T>
+void generalMatrix(blas::Op opA, blas::Op opB, const T alpha, const Matrix<T, Device::CPU>& mat_a,
+                   const Matrix<T, Device::CPU>& mat_b, const T beta, Matrix<T, Device::CPU>& mat_c) {
+  comm::CommunicatorGrid grid = comm::CommunicatorGrid::single();
+  generalMatrix<B, D, T>(grid, opA, opB, alpha, mat_a, mat_b, beta, mat_c);
+}
+template <Backend B, Device D, class T>
+void generalMatrix(comm::CommunicatorGrid& grid, const T alpha, const Matrix<T, Device::CPU>& mat_a,
+                   const Matrix<T, Device::CPU>& mat_b, const T beta, Matrix<T, Device::CPU>& mat_c) {
+  generalMatrix<B, D, T>(grid, blas::Op::NoTrans, blas::Op::NoTrans, alpha, mat_a, mat_b, beta, mat_c);
+}
+}  // namespace multiplication::internal
 
 // include/dlaf/eigensolver/gen_to_std.h:50, :101: A <- inv(L) A inv(L^H) (Lower) / inv(U^H) A inv(U) (Upper) with
 // the Cholesky factor of B in mat_b (host-resident operands; only the uplo triangles are referenced)

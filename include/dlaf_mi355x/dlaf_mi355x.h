@@ -250,6 +250,50 @@ DLAF_EXTERN_C void dlaf_mi355x_pzhemm(char side, char uplo, int m, int n, const 
                                       const dlaf_complex_z* beta, dlaf_complex_z* c, int ic, int jc,
                                       const int descc[9]) DLAF_NOEXCEPT;
 
+/* ---- General multiplication ---------------------------------------------------------------- */
+/* dlaf::multiplication::internal::generalMatrix(opA, opB, alpha, A, B, beta, C), include/dlaf/multiplication/general.h
+ * (the reference has no C entry for it; the p?gemm names take ScaLAPACK's argument list):
+ *   C = beta C + alpha op(A) op(B),  op(X) = X ('N'), X^T ('T') or X^H ('C');  C (m x n) is overwritten, A and B are not.
+ * a, b, c and their descriptors describe the matrices AS STORED: A is m x k ('N') or k x m, B is k x n ('N') or n x k.
+ * One process: every op pair.  A grid of more than one process: 'N' 'N' only (the reference's distributed coverage).
+ * beta = 0: C is not read.  k = 0 or alpha = 0: C = beta C and A, B are not referenced.  m = 0 or n = 0: returns at
+ * once.  alpha, beta passed by address; a, b, c: local column-major parts on the grid of `context`; only the m x n
+ * elements of c are written.  Requirements of this build: one square block for A, B and C; no sub-matrix offsets; A
+ * starts on C's process row (desca.isrc = descc.isrc) and B on C's process column (descb.jsrc = descc.jsrc).  Returns
+ * 0; a violated requirement terminates with a message "general multiplication: ..." before the GPU is touched. */
+DLAF_EXTERN_C int dlaf_mi355x_general_multiplication_s(int context, char opa, char opb, const float* alpha,
+                                                       const float* a, struct DLAF_descriptor desca, const float* b,
+                                                       struct DLAF_descriptor descb, const float* beta, float* c,
+                                                       struct DLAF_descriptor descc) DLAF_NOEXCEPT;
+DLAF_EXTERN_C int dlaf_mi355x_general_multiplication_d(int context, char opa, char opb, const double* alpha,
+                                                       const double* a, struct DLAF_descriptor desca, const double* b,
+                                                       struct DLAF_descriptor descb, const double* beta, double* c,
+                                                       struct DLAF_descriptor descc) DLAF_NOEXCEPT;
+DLAF_EXTERN_C int dlaf_mi355x_general_multiplication_c(int context, char opa, char opb, const dlaf_complex_c* alpha,
+                                                       const dlaf_complex_c* a, struct DLAF_descriptor desca, const dlaf_complex_c* b,
+                                                       struct DLAF_descriptor descb, const dlaf_complex_c* beta, dlaf_complex_c* c,
+                                                       struct DLAF_descriptor descc) DLAF_NOEXCEPT;
+DLAF_EXTERN_C int dlaf_mi355x_general_multiplication_z(int context, char opa, char opb, const dlaf_complex_z* alpha,
+                                                       const dlaf_complex_z* a, struct DLAF_descriptor desca, const dlaf_complex_z* b,
+                                                       struct DLAF_descriptor descb, const dlaf_complex_z* beta, dlaf_complex_z* c,
+                                                       struct DLAF_descriptor descc) DLAF_NOEXCEPT;
+DLAF_EXTERN_C void dlaf_mi355x_psgemm(char transa, char transb, int m, int n, int k, const float* alpha,
+                                      const float* a, int ia, int ja, const int desca[9], const float* b, int ib, int jb,
+                                      const int descb[9], const float* beta, float* c, int ic, int jc,
+                                      const int descc[9]) DLAF_NOEXCEPT;
+DLAF_EXTERN_C void dlaf_mi355x_pdgemm(char transa, char transb, int m, int n, int k, const double* alpha,
+                                      const double* a, int ia, int ja, const int desca[9], const double* b, int ib, int jb,
+                                      const int descb[9], const double* beta, double* c, int ic, int jc,
+                                      const int descc[9]) DLAF_NOEXCEPT;
+DLAF_EXTERN_C void dlaf_mi355x_pcgemm(char transa, char transb, int m, int n, int k, const dlaf_complex_c* alpha,
+                                      const dlaf_complex_c* a, int ia, int ja, const int desca[9], const dlaf_complex_c* b, int ib, int jb,
+                                      const int descb[9], const dlaf_complex_c* beta, dlaf_complex_c* c, int ic, int jc,
+                                      const int descc[9]) DLAF_NOEXCEPT;
+DLAF_EXTERN_C void dlaf_mi355x_pzgemm(char transa, char transb, int m, int n, int k, const dlaf_complex_z* alpha,
+                                      const dlaf_complex_z* a, int ia, int ja, const int desca[9], const dlaf_complex_z* b, int ib, int jb,
+                                      const int descb[9], const dlaf_complex_z* beta, dlaf_complex_z* c, int ic, int jc,
+                                      const int descc[9]) DLAF_NOEXCEPT;
+
 /* ScaLAPACK p?potrs: A X = B with the factor dlaf_p?potrf left in a (two triangular solves; b is overwritten) */
 DLAF_EXTERN_C void dlaf_mi355x_pspotrs(char uplo, int n, int nrhs, const float* a, int ia, int ja, const int desca[9],
                                        float* b, int ib, int jb, const int descb[9], int* info) DLAF_NOEXCEPT;
@@ -686,10 +730,17 @@ DLAF_EXTERN_C int dlaf_mi355x_triangular_multiplication_device(char side, char u
 DLAF_EXTERN_C int dlaf_mi355x_hermitian_multiplication_device(char side, char uplo, const void* alpha,
                                                               dlaf_mi355x_matrix_t a, dlaf_mi355x_gmatrix_t b,
                                                               const void* beta, dlaf_mi355x_gmatrix_t c) DLAF_NOEXCEPT;
+/* general_multiplication on three resident general matrices of one context and element type (a, b as stored, see the
+ * host entry; only c is written); nothing crosses PCIe.  Same requirements as the host entry; a handle or scalar that
+ * is null returns -1. */
+DLAF_EXTERN_C int dlaf_mi355x_general_multiplication_device(char opa, char opb, const void* alpha,
+                                                            dlaf_mi355x_gmatrix_t a, dlaf_mi355x_gmatrix_t b,
+                                                            const void* beta, dlaf_mi355x_gmatrix_t c) DLAF_NOEXCEPT;
 /* Device time (ms, HIP events on the compute stream) of the sweep of the last triangular multiplication on this
  * process -- relayout and PCIe staging excluded -- and the whole-grid algorithmic flops it stands for (m n^2 for
  * side R, m^2 n for side L; x4 complex), as dlaf_mi355x_solver_profile.  The last multiplication of EITHER kind is
- * reported: after a Hermitian multiplication, its sweep and twice those flops (2 m n^2 / 2 m^2 n; x4 complex). */
+ * reported: after a Hermitian multiplication, its sweep and twice those flops (2 m n^2 / 2 m^2 n; x4 complex); after a
+ * general multiplication, its sweep and 2 m n k (x4 complex). */
 DLAF_EXTERN_C int dlaf_mi355x_multiplication_profile(double* ms, double* flops) DLAF_NOEXCEPT;
 
 /* ---- synthetic input ------------------------------------------------------------------------ */

@@ -147,6 +147,22 @@ SIGNATURES = {
     "dlaf_mi355x_general_multiplication_d": (_i, [_i, _ch, _ch, _vp, _vp, DLAFDescriptor, _vp, DLAFDescriptor, _vp, _vp, DLAFDescriptor]),
     "dlaf_mi355x_general_multiplication_c": (_i, [_i, _ch, _ch, _vp, _vp, DLAFDescriptor, _vp, DLAFDescriptor, _vp, _vp, DLAFDescriptor]),
     "dlaf_mi355x_general_multiplication_z": (_i, [_i, _ch, _ch, _vp, _vp, DLAFDescriptor, _vp, DLAFDescriptor, _vp, _vp, DLAFDescriptor]),
+    "dlaf_mi355x_hermitian_rank_k_update_s": (_i, [_i, _ch, _ch, _vp, _vp, DLAFDescriptor, _vp, _vp, DLAFDescriptor]),
+    "dlaf_mi355x_hermitian_rank_k_update_d": (_i, [_i, _ch, _ch, _vp, _vp, DLAFDescriptor, _vp, _vp, DLAFDescriptor]),
+    "dlaf_mi355x_hermitian_rank_k_update_c": (_i, [_i, _ch, _ch, _vp, _vp, DLAFDescriptor, _vp, _vp, DLAFDescriptor]),
+    "dlaf_mi355x_hermitian_rank_k_update_z": (_i, [_i, _ch, _ch, _vp, _vp, DLAFDescriptor, _vp, _vp, DLAFDescriptor]),
+    "dlaf_mi355x_hermitian_rank_2k_update_s": (_i, [_i, _ch, _ch, _vp, _vp, DLAFDescriptor, _vp, DLAFDescriptor, _vp, _vp, DLAFDescriptor]),
+    "dlaf_mi355x_hermitian_rank_2k_update_d": (_i, [_i, _ch, _ch, _vp, _vp, DLAFDescriptor, _vp, DLAFDescriptor, _vp, _vp, DLAFDescriptor]),
+    "dlaf_mi355x_hermitian_rank_2k_update_c": (_i, [_i, _ch, _ch, _vp, _vp, DLAFDescriptor, _vp, DLAFDescriptor, _vp, _vp, DLAFDescriptor]),
+    "dlaf_mi355x_hermitian_rank_2k_update_z": (_i, [_i, _ch, _ch, _vp, _vp, DLAFDescriptor, _vp, DLAFDescriptor, _vp, _vp, DLAFDescriptor]),
+    "dlaf_mi355x_pssyrk": (None, [_ch, _ch, _i, _i, _vp, _vp, _i, _i, _IP, _vp, _vp, _i, _i, _IP]),
+    "dlaf_mi355x_pdsyrk": (None, [_ch, _ch, _i, _i, _vp, _vp, _i, _i, _IP, _vp, _vp, _i, _i, _IP]),
+    "dlaf_mi355x_pcherk": (None, [_ch, _ch, _i, _i, _vp, _vp, _i, _i, _IP, _vp, _vp, _i, _i, _IP]),
+    "dlaf_mi355x_pzherk": (None, [_ch, _ch, _i, _i, _vp, _vp, _i, _i, _IP, _vp, _vp, _i, _i, _IP]),
+    "dlaf_mi355x_pssyr2k": (None, [_ch, _ch, _i, _i, _vp, _vp, _i, _i, _IP, _vp, _i, _i, _IP, _vp, _vp, _i, _i, _IP]),
+    "dlaf_mi355x_pdsyr2k": (None, [_ch, _ch, _i, _i, _vp, _vp, _i, _i, _IP, _vp, _i, _i, _IP, _vp, _vp, _i, _i, _IP]),
+    "dlaf_mi355x_pcher2k": (None, [_ch, _ch, _i, _i, _vp, _vp, _i, _i, _IP, _vp, _i, _i, _IP, _vp, _vp, _i, _i, _IP]),
+    "dlaf_mi355x_pzher2k": (None, [_ch, _ch, _i, _i, _vp, _vp, _i, _i, _IP, _vp, _i, _i, _IP, _vp, _vp, _i, _i, _IP]),
     "dlaf_mi355x_psgemm": (None, [_ch, _ch, _i, _i, _i, _vp, _vp, _i, _i, _IP, _vp, _i, _i, _IP, _vp, _vp, _i, _i, _IP]),
     "dlaf_mi355x_pdgemm": (None, [_ch, _ch, _i, _i, _i, _vp, _vp, _i, _i, _IP, _vp, _i, _i, _IP, _vp, _vp, _i, _i, _IP]),
     "dlaf_mi355x_pcgemm": (None, [_ch, _ch, _i, _i, _i, _vp, _vp, _i, _i, _IP, _vp, _i, _i, _IP, _vp, _vp, _i, _i, _IP]),
@@ -165,6 +181,8 @@ SIGNATURES = {
     "dlaf_mi355x_triangular_multiplication_device": (_i, [_ch, _ch, _ch, _ch, _vp, _vp, _vp]),
     "dlaf_mi355x_hermitian_multiplication_device": (_i, [_ch, _ch, _vp, _vp, _vp, _vp, _vp]),
     "dlaf_mi355x_general_multiplication_device": (_i, [_ch, _ch, _vp, _vp, _vp, _vp, _vp]),
+    "dlaf_mi355x_hermitian_rank_k_update_device": (_i, [_ch, _ch, _vp, _vp, _vp, _vp]),
+    "dlaf_mi355x_hermitian_rank_2k_update_device": (_i, [_ch, _ch, _vp, _vp, _vp, _vp, _vp]),
     "dlaf_mi355x_potrs_device": (_i, [_ch, _vp, _vp]),
     "dlaf_mi355x_generalized_to_standard_s": (_i, [_i, _ch, _vp, DLAFDescriptor, _vp, DLAFDescriptor]),
     "dlaf_mi355x_generalized_to_standard_d": (_i, [_i, _ch, _vp, DLAFDescriptor, _vp, DLAFDescriptor]),

@@ -315,9 +315,87 @@ def pxgemm(transa: str, transb: str, m: int, n: int, k: int, alpha, a: np.ndarra
                                             _ptr(b), ib, jb, db, _ptr(be), _ptr(c), ic, jc, dc)
 
 
+def _real_dtype(dtype):
+    return np.dtype(dtype).type(0).real.dtype
+
+
+def _rank_update(two: bool, grid: Grid, uplo: str, trans: str, alpha, a: np.ndarray, b, beta, c: np.ndarray, nb: int,
+                 n, k, a_src, c_src) -> None:
+    t = type_char(c.dtype)
+    if a.dtype != c.dtype or (two and b.dtype != c.dtype):
+        raise ValueError("the operands must have the same element type")
+    tn = trans.upper() == "N"
+    if n is None or k is None:
+        if grid.nranks != 1:
+            raise ValueError("the global sizes n, k are required on a distributed grid")
+        n = c.shape[0]
+        k = a.shape[1] if tn else a.shape[0]
+    rdt = _real_dtype(c.dtype)
+    da = DLAFDescriptor(n if tn else k, k if tn else n, nb, nb, a_src[0], a_src[1], 0, 0, _ld_of(a))
+    dc = DLAFDescriptor(n, n, nb, nb, c_src[0], c_src[1], 0, 0, _ld_of(c))
+    be = np.array([beta], dtype=rdt)
+    if two:
+        db = DLAFDescriptor(n if tn else k, k if tn else n, nb, nb, a_src[0], a_src[1], 0, 0, _ld_of(b))
+        al = np.array([alpha], dtype=c.dtype)
+        name = f"dlaf_mi355x_hermitian_rank_2k_update_{t}"
+        r = getattr(lib(), name)(grid.context, uplo.encode(), trans.encode(), _ptr(al), _ptr(a), da, _ptr(b), db, _ptr(be),
+                                 _ptr(c), dc)
+    else:
+        al = np.array([alpha], dtype=rdt)
+        name = f"dlaf_mi355x_hermitian_rank_k_update_{t}"
+        r = getattr(lib(), name)(grid.context, uplo.encode(), trans.encode(), _ptr(al), _ptr(a), da, _ptr(be), _ptr(c), dc)
+    if r != 0:
+        raise ValueError(f"{name} failed with {r}")
+
+
+def hermitian_rank_k_update(grid: Grid, uplo: str, trans: str, alpha, a: np.ndarray, beta, c: np.ndarray, nb: int,
+                            n: int | None = None, k: int | None = None, a_src=(0, 0), c_src=(0, 0)) -> None:
+    """xSYRK / xHERK on the grid == dlaf_mi355x_hermitian_rank_k_update_{s,d,c,z}: the uplo triangle of the n x n matrix C
+    becomes alpha A A^H + beta C (trans 'N', A stored n x k) or alpha A^H A + beta C (trans 'C', A stored k x n); alpha
+    and beta are real.  `a`, `c`: this process's local column-major parts; only the uplo triangle of `c` is read or
+    written, and its diagonal comes back with imaginary part 0.  nb: the square block of both.  On a grid of more than
+    one process only trans 'N' is built, n and k are required and A must start on C's process row."""
+    _rank_update(False, grid, uplo, trans, alpha, a, None, beta, c, nb, n, k, a_src, c_src)
+
+
+def hermitian_rank_2k_update(grid: Grid, uplo: str, trans: str, alpha, a: np.ndarray, b: np.ndarray, beta, c: np.ndarray,
+                             nb: int, n: int | None = None, k: int | None = None, a_src=(0, 0), c_src=(0, 0)) -> None:
+    """xSYR2K / xHER2K on the grid == dlaf_mi355x_hermitian_rank_2k_update_{s,d,c,z}: the uplo triangle of C becomes
+    alpha A B^H + conj(alpha) B A^H + beta C (trans 'N') or alpha A^H B + conj(alpha) B^H A + beta C (trans 'C'); alpha
+    is of the element type, beta is real; B is stored, blocked and distributed like A.  Otherwise as
+    hermitian_rank_k_update."""
+    _rank_update(True, grid, uplo, trans, alpha, a, b, beta, c, nb, n, k, a_src, c_src)
+
+
+def pxherk(uplo: str, trans: str, n: int, k: int, alpha, a: np.ndarray, ia: int, ja: int, desca, beta, c: np.ndarray,
+           ic: int, jc: int, descc) -> None:
+    """dlaf_mi355x_p{s,d}syrk / p{c,z}herk: ScaLAPACK's argument list (9-int descriptors; alpha and beta real)."""
+    t = type_char(c.dtype)
+    da = (C.c_int * 9)(*[int(x) for x in desca])
+    dc = (C.c_int * 9)(*[int(x) for x in descc])
+    al = np.array([alpha], dtype=_real_dtype(c.dtype))
+    be = np.array([beta], dtype=_real_dtype(c.dtype))
+    name = f"dlaf_mi355x_p{t}{'herk' if t in 'cz' else 'syrk'}"
+    getattr(lib(), name)(uplo.encode(), trans.encode(), n, k, _ptr(al), _ptr(a), ia, ja, da, _ptr(be), _ptr(c), ic, jc, dc)
+
+
+def pxher2k(uplo: str, trans: str, n: int, k: int, alpha, a: np.ndarray, ia: int, ja: int, desca, b: np.ndarray, ib: int,
+            jb: int, descb, beta, c: np.ndarray, ic: int, jc: int, descc) -> None:
+    """dlaf_mi355x_p{s,d}syr2k / p{c,z}her2k: ScaLAPACK's argument list (9-int descriptors; beta real)."""
+    t = type_char(c.dtype)
+    da = (C.c_int * 9)(*[int(x) for x in desca])
+    db = (C.c_int * 9)(*[int(x) for x in descb])
+    dc = (C.c_int * 9)(*[int(x) for x in descc])
+    al = np.array([alpha], dtype=c.dtype)
+    be = np.array([beta], dtype=_real_dtype(c.dtype))
+    name = f"dlaf_mi355x_p{t}{'her2k' if t in 'cz' else 'syr2k'}"
+    getattr(lib(), name)(uplo.encode(), trans.encode(), n, k, _ptr(al), _ptr(a), ia, ja, da, _ptr(b), ib, jb, db, _ptr(be),
+                         _ptr(c), ic, jc, dc)
+
+
 def multiplication_profile():
-    """(ms, flops) of the sweep of the last multiplication (triangular, Hermitian or general) on this process (device time, no
-    staging)."""
+    """(ms, flops) of the sweep of the last multiplication (triangular, Hermitian, general or Hermitian rank update) on this
+    process (device time, no staging)."""
     ms, fl = C.c_double(0), C.c_double(0)
     lib().dlaf_mi355x_multiplication_profile(C.byref(ms), C.byref(fl))
     return ms.value, fl.value
@@ -644,6 +722,28 @@ def general_multiplication_device(opa: str, opb: str, alpha, a: GeneralDeviceMat
     r = lib().dlaf_mi355x_general_multiplication_device(opa.encode(), opb.encode(), _ptr(al), a._h, b._h, _ptr(be), c._h)
     if r != 0:
         raise ValueError(f"dlaf_mi355x_general_multiplication_device failed with {r}")
+
+
+def hermitian_rank_k_update_device(uplo: str, trans: str, alpha, a: GeneralDeviceMatrix, beta, c: DeviceMatrix) -> None:
+    """hermitian_rank_k_update on resident operands: `c` a DeviceMatrix created with this uplo (what factorize() takes),
+    `a` a general resident matrix as stored; only the uplo triangle of `c` is written; no PCIe traffic."""
+    rdt = _real_dtype(a.dtype)
+    al, be = np.array([alpha], dtype=rdt), np.array([beta], dtype=rdt)
+    r = lib().dlaf_mi355x_hermitian_rank_k_update_device(uplo.encode(), trans.encode(), _ptr(al), a._h, _ptr(be), c._h)
+    if r != 0:
+        raise ValueError(f"dlaf_mi355x_hermitian_rank_k_update_device failed with {r}")
+
+
+def hermitian_rank_2k_update_device(uplo: str, trans: str, alpha, a: GeneralDeviceMatrix, b: GeneralDeviceMatrix, beta,
+                                    c: DeviceMatrix) -> None:
+    """hermitian_rank_2k_update on resident operands (`a`, `b` general resident matrices as stored, `c` a DeviceMatrix
+    created with this uplo); only the uplo triangle of `c` is written; no PCIe traffic."""
+    al = np.array([alpha], dtype=a.dtype)
+    be = np.array([beta], dtype=_real_dtype(a.dtype))
+    r = lib().dlaf_mi355x_hermitian_rank_2k_update_device(uplo.encode(), trans.encode(), _ptr(al), a._h, b._h, _ptr(be),
+                                                          c._h)
+    if r != 0:
+        raise ValueError(f"dlaf_mi355x_hermitian_rank_2k_update_device failed with {r}")
 
 
 def potrs_device(uplo: str, factor: DeviceMatrix, b: GeneralDeviceMatrix) -> None:

@@ -203,6 +203,40 @@ template <class T>
 void launch_general(const GeneralArgs<T>& args, hipStream_t stream);
 
 // ------------------------------------------------------------------------------------------
+// Hermitian rank-k / rank-2k update (kernels_herk.hip; index arithmetic and operand forms: herk_map.hpp) of the local
+// tiles of the LOWER triangle of a square view V, in ONE launch, a block of V in the accumulators over all nk k tiles:
+//   herk  : V(il, jl) = [first ? beta : 1] V(il, jl) + alpha sum_t x(il, t) y(jl, t)^H
+//   her2k : ... + alpha sum_t x(il, t) y2(jl, t)^H + conj(alpha) sum_t x2(il, t) y(jl, t)^H          (x2 != nullptr)
+// x / y: the tiles of A (x2 / y2: of B) AS STORED for the local tile rows / columns of V -- trans N the nb x K tile of
+// (row, t), trans C the K x nb tile of (t, row) -- tile idx of k tile t at base + herk_panel_offset(idx, period, ts, ts2)
+// + t ks; B's panels share A's strides.  conj_view: V holds the plain transpose of an upper-stored C (conj(A), conj(B)
+// and conj(alpha) take the place of A, B and alpha).  Tiles above the diagonal, and the elements of a diagonal tile
+// above it, are neither read nor written.  On the diagonal the imaginary part of V is ignored and stored as 0.
+// first != 0 with beta == 0: V is not read.  nk == 0: V = beta V (first), the operands are not read.
+template <class T>
+struct RankKArgs {
+  T* c;
+  long c_tsr, c_tsc;
+  const T* x;
+  const T* y;
+  const T* x2 = nullptr;
+  const T* y2 = nullptr;
+  long x_ts, x_ts2 = 0, y_ts, y_ts2 = 0, ks;
+  int x_period = 1, y_period = 1;
+  char trans = 'N';
+  int conj_view = 0;
+  int nk, k_last;
+  int ltr, ltc;   // local tiles of V
+  int nb;         // tile size = leading dimension of every tile
+  int pr, ri, pc, ci, nt, last;  // block-cyclic geometry; nt tiles per dimension, the last one `last` wide
+  T alpha;
+  real_t<T> beta;
+  int first = 1;
+};
+template <class T>
+void launch_rank_k(const RankKArgs<T>& args, hipStream_t stream);
+
+// ------------------------------------------------------------------------------------------
 // Diagonal-tile work of triangular_inverse / inverse_from_cholesky_factor (kernels_inverse.hip).  A batch of
 // `count` lower triangular tiles, tile t at base + t * stride (leading dimension ld), each nb x nb except the last,
 // which is last x last.

@@ -347,6 +347,7 @@ void trsm_kernels_init();
 void trmm_kernels_init();
 void hemm_kernels_init();
 void gemm_kernels_init();
+void herk_kernels_init();
 void inverse_kernels_init();
 void potrf_kernels_init();
 void potrf_coop_kernels_init();
@@ -360,6 +361,7 @@ void device_kernels_init() {
   trmm_kernels_init();
   hemm_kernels_init();
   gemm_kernels_init();
+  herk_kernels_init();
   inverse_kernels_init();
   potrf_kernels_init();
   potrf_coop_kernels_init();

@@ -116,6 +116,44 @@ void require_general_multiplication(const char* who, const GridT& g, char opa, c
     fatal("[dlaf_mi355x] %s: B must start on C's process column (source column %d vs %d)\n", who, b.jsrc, c.jsrc);
 }
 
+// ---- Hermitian rank-k / rank-2k update of the uplo triangle of C: one judgement for the descriptor entries, the p?
+// entries and the resident ones.  a (and b, rank-2k; nullptr: rank-k) as stored; c_stored: the triangle a resident C
+// holds (0: C is a host array).  Terminates unless: uplo and trans are letters, and trans is not 'T' on a complex type
+// (that is the complex-symmetric p{c,z}syrk, which is not built); C is square; A is n x k (trans N) or k x n; B has A's
+// shape, blocks and source; one square block for all; every source inside the grid; a resident C holds the uplo
+// triangle; on a grid of more than one process trans is 'N' (the transposed forms need the two-hop transposed-panel
+// broadcast of A's ROWS, which is not built) and A starts on C's process row.
+template <class GridT>
+void require_rank_update(const char* who, const GridT& g, bool complex_type, char uplo, char trans, const GemmOperand& a,
+                         const GemmOperand* b, const GemmOperand& c, char c_stored = 0) {
+  if (!is_uplo(uplo) || !is_op(trans))
+    fatal("[dlaf_mi355x] %s: bad uplo/trans '%c' '%c'\n", who, uplo, trans);
+  if (complex_type && in_set(trans, "Tt"))
+    fatal("[dlaf_mi355x] %s: trans '%c' on a complex type (the complex-symmetric update) is not built; use 'N' or 'C'\n",
+          who, trans);
+  if (c.m != c.n || c.n < 0)
+    fatal("[dlaf_mi355x] %s: C must be square (%ld x %ld)\n", who, c.m, c.n);
+  const bool tn = is_notrans(trans);
+  const long an = tn ? a.m : a.n, ak = tn ? a.n : a.m;
+  if (an != c.n || ak < 0)
+    fatal("[dlaf_mi355x] %s: A is %ld x %ld (trans '%c'), C is %ld x %ld\n", who, a.m, a.n, trans, c.m, c.n);
+  if (b && (b->m != a.m || b->n != a.n || b->mb != a.mb || b->nb != a.nb || b->isrc != a.isrc || b->jsrc != a.jsrc))
+    fatal("[dlaf_mi355x] %s: A (%ld x %ld, block %d x %d, source %d,%d) and B (%ld x %ld, block %d x %d, source %d,%d) "
+          "differ\n", who, a.m, a.n, a.mb, a.nb, a.isrc, a.jsrc, b->m, b->n, b->mb, b->nb, b->isrc, b->jsrc);
+  if (a.mb != a.nb || c.mb != c.nb || a.nb != c.nb || c.nb < 1)
+    fatal("[dlaf_mi355x] %s: the operands need one square block (A %d x %d, C %d x %d)\n", who, a.mb, a.nb, c.mb, c.nb);
+  for (const GemmOperand* o : {&a, &c})
+    if (!source_in_grid(g.nprow, g.npcol, o->isrc, o->jsrc))
+      fatal("[dlaf_mi355x] %s: source rank (%d,%d) outside the %d x %d grid\n", who, o->isrc, o->jsrc, g.nprow, g.npcol);
+  if (c_stored != 0 && is_upper(c_stored) != is_upper(uplo))
+    fatal("[dlaf_mi355x] %s: uplo '%c' but the resident matrix holds its '%c' triangle\n", who, uplo, c_stored);
+  if (g.nprow * g.npcol > 1 && !tn)
+    fatal("[dlaf_mi355x] %s: trans '%c' on a %d x %d grid: only 'N' is built on more than one process\n", who, trans,
+          g.nprow, g.npcol);
+  if (tn && a.isrc != c.isrc)
+    fatal("[dlaf_mi355x] %s: A must start on C's process row (source row %d vs %d)\n", who, a.isrc, c.isrc);
+}
+
 // ---- the prologue of a ScaLAPACK argument list: every operand as (name letter, desc, row offset, column offset)
 struct ScalapackOperand {
   char name;

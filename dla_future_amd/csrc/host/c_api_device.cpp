@@ -177,6 +177,48 @@ int dlaf_mi355x_general_multiplication_device(char opa, char opb, const void* al
   return general_multiplication_device(opa, opb, alpha, a->m.get(), b->m.get(), beta, c->m.get());
 }
 
+// b null: rank-k (alpha points to a real), else rank-2k (alpha points to an element); beta points to a real
+static int rank_update_device(const char* who, char uplo, char trans, const void* alpha, dlaf_mi355x_gmatrix_t a,
+                              dlaf_mi355x_gmatrix_t b, bool her2k, const void* beta, dlaf_mi355x_matrix_t c) {
+  if (!a || !a->m || !c || !c->m || !alpha || !beta || (her2k && (!b || !b->m)))
+    return -1;
+  if (a->ctx != c->ctx || (her2k && b->ctx != c->ctx))
+    fatal("[dlaf_mi355x] %s: the operands live on different contexts (A %d, C %d)\n", who, a->ctx, c->ctx);
+  if (a->m->type != c->m->type || (her2k && b->m->type != c->m->type))
+    fatal("[dlaf_mi355x] %s: operands of different element types (A '%c', C '%c')\n", who, a->m->type, c->m->type);
+  GemmOperand oa{}, ob{}, oc{};
+  char stored = 'L';
+  bool cx = false;
+  (void) dispatch_api_type(c->m->type, [&](auto* tag) {
+    using DT = std::remove_pointer_t<decltype(tag)>;
+    auto operand = [](dlaf_mi355x_gmatrix_t h) {
+      const auto& gm = static_cast<GeneralMatrix<DT>&>(*h->m);
+      return GemmOperand{gm.rows_g, gm.cols_g, gm.m.nb, gm.m.nb, gm.isrc, gm.jsrc};
+    };
+    oa = operand(a);
+    if (her2k)
+      ob = operand(b);
+    const auto& cm = static_cast<DeviceMatrix<DT>&>(*c->m);
+    const Axis& srow = cm.transposed ? cm.cols : cm.rows;
+    const Axis& scol = cm.transposed ? cm.rows : cm.cols;
+    oc = GemmOperand{cm.n, cm.n, cm.nb, cm.nb, srow.src, scol.src};
+    stored = cm.uplo;
+    cx = TypeInfo<DT>::is_complex;
+    return 0;
+  });
+  require_rank_update(who, grid_from_context(c->ctx), cx, uplo, trans, oa, her2k ? &ob : nullptr, oc, stored);
+  return hermitian_rank_update_device(trans, alpha, a->m.get(), her2k ? b->m.get() : nullptr, beta, c->m.get());
+}
+int dlaf_mi355x_hermitian_rank_k_update_device(char uplo, char trans, const void* alpha, dlaf_mi355x_gmatrix_t a,
+                                               const void* beta, dlaf_mi355x_matrix_t c) noexcept {
+  return rank_update_device("hermitian rank-k update", uplo, trans, alpha, a, nullptr, false, beta, c);
+}
+int dlaf_mi355x_hermitian_rank_2k_update_device(char uplo, char trans, const void* alpha, dlaf_mi355x_gmatrix_t a,
+                                                dlaf_mi355x_gmatrix_t b, const void* beta,
+                                                dlaf_mi355x_matrix_t c) noexcept {
+  return rank_update_device("hermitian rank-2k update", uplo, trans, alpha, a, b, true, beta, c);
+}
+
 int dlaf_mi355x_multiplication_profile(double* ms, double* flops) noexcept {
   multiplication_last_profile(ms, flops);
   return 0;

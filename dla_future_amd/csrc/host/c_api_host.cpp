@@ -1,6 +1,6 @@
 // c_api_host.cpp -- the extern "C" surface, part 2 of 3 (c_api_internal.hpp has the map): the entries that take
 // descriptors or ScaLAPACK argument lists over host memory -- triangular solver and multiplication, Hermitian and
-// general multiplication, p?potrs, generalized to standard, the inverses, the norms, reduction to band and the eigensolver
+// general multiplication, the Hermitian rank updates, p?potrs, generalized to standard, the inverses, the norms, reduction to band and the eigensolver
 // stages and drivers (include/dlaf_c/eigensolver/*.h as upstream, include/dlaf_mi355x/dlaf_mi355x.h).  Every argument
 // is judged (api_checks.hpp) before anything touches the GPU.
 #define DLAF_MI355X_NO_MPI 1  // as in c_api.cpp: no <mpi.h> in the core
@@ -179,6 +179,55 @@ void pxgemm(char transa, char transb, int m, int n, int k, const HT* alpha, cons
   const DLAF_descriptor db = make_dlaf_descriptor(bn ? k : n, bn ? n : k, ib, jb, descb);
   const DLAF_descriptor dc = make_dlaf_descriptor(m, n, ic, jc, descc);
   (void) general_multiplication_c<HT>(ctx, transa, transb, alpha, a, da, b, db, beta, c, dc);
+}
+
+// Hermitian rank-k (b null) / rank-2k update of the uplo triangle of C through descriptors (rank_update.cpp): a, b as
+// stored; alpha an element (rank-k: its real alpha with imaginary part 0), beta real; every argument judged before the
+// GPU is touched
+template <class HT>
+using real_of_t = typename TypeInfo<typename DevType<HT>::type>::real;
+template <class HT>
+typename DevType<HT>::type element_of_real(real_of_t<HT> v) {
+  using DT = typename DevType<HT>::type;
+  if constexpr (TypeInfo<DT>::is_complex)
+    return DT{v, real_of_t<HT>(0)};
+  else
+    return v;
+}
+template <class HT>
+int rank_update_c(int ctx, char uplo, char trans, typename DevType<HT>::type alpha, const HT* a, const DLAF_descriptor& da,
+                  const HT* b, const DLAF_descriptor* db, real_of_t<HT> beta, HT* c, const DLAF_descriptor& dc) {
+  using DT = typename DevType<HT>::type;
+  const char* who = db ? "hermitian rank-2k update" : "hermitian rank-k update";
+  if (da.i != 0 || da.j != 0 || dc.i != 0 || dc.j != 0 || (db && (db->i != 0 || db->j != 0)))
+    fatal("[dlaf_mi355x] %s: sub-matrices are not supported: offsets must be 0\n", who);
+  Grid& g = grid_from_context(ctx);
+  GemmOperand ob{};
+  if (db)
+    ob = gemm_operand(*db);
+  require_rank_update(who, g, TypeInfo<DT>::is_complex, uplo, trans, gemm_operand(da), db ? &ob : nullptr,
+                      gemm_operand(dc));
+  const long k = is_notrans(trans) ? da.n : da.m;
+  return hermitian_rank_update_host<DT>(&g, db != nullptr, uplo, trans, alpha, reinterpret_cast<const DT*>(a), da.ld,
+                                        da.isrc, da.jsrc, reinterpret_cast<const DT*>(b), db ? db->ld : 0, beta,
+                                        reinterpret_cast<DT*>(c), dc.ld, dc.n, k, dc.nb, dc.isrc, dc.jsrc);
+}
+
+// ScaLAPACK p?syrk / p?herk (b null) and p?syr2k / p?her2k argument lists
+template <class HT>
+void pxrank_update(char uplo, char trans, int n, int k, typename DevType<HT>::type alpha, const HT* a, int ia, int ja,
+                   const int desca[9], const HT* b, int ib, int jb, const int* descb, real_of_t<HT> beta, HT* c, int ic,
+                   int jc, const int descc[9]) {
+  const bool tn = is_notrans(trans);
+  const int ctx = descb ? require_scalapack_args({{'A', desca, ia, ja}, {'B', descb, ib, jb}, {'C', descc, ic, jc}},
+                                                 "hermitian rank-2k update")
+                        : require_scalapack_args({{'A', desca, ia, ja}, {'C', descc, ic, jc}}, "hermitian rank-k update");
+  const DLAF_descriptor da = make_dlaf_descriptor(tn ? n : k, tn ? k : n, ia, ja, desca);
+  const DLAF_descriptor dc = make_dlaf_descriptor(n, n, ic, jc, descc);
+  DLAF_descriptor db{};
+  if (descb)
+    db = make_dlaf_descriptor(tn ? n : k, tn ? k : n, ib, jb, descb);
+  (void) rank_update_c<HT>(ctx, uplo, trans, alpha, a, da, b, descb ? &db : nullptr, beta, c, dc);
 }
 
 // ScaLAPACK p?potrs: solve A X = B with the factor p?potrf left in a (uplo L: L L^H, uplo U: U^H U)
@@ -542,6 +591,41 @@ DLAF_MI355X_GEMM_ENTRY(d, double, double)
 DLAF_MI355X_GEMM_ENTRY(c, std::complex<float>, dlaf_complex_c)
 DLAF_MI355X_GEMM_ENTRY(z, std::complex<double>, dlaf_complex_z)
 #undef DLAF_MI355X_GEMM_ENTRY
+// RT: the real type of alpha (rank-k) and beta; NAME / NAME2: syrk / syr2k or herk / her2k
+#define DLAF_MI355X_RANK_UPDATE_ENTRY(S, HT, CT, RT, NAME, NAME2)                                                   \
+  int dlaf_mi355x_hermitian_rank_k_update_##S(int ctx, char uplo, char trans, const RT* alpha, const CT* a,           \
+                                              DLAF_descriptor desca, const RT* beta, CT* c,                          \
+                                              DLAF_descriptor descc) noexcept {                                      \
+    return rank_update_c<HT>(ctx, uplo, trans, element_of_real<HT>(*alpha), reinterpret_cast<const HT*>(a), desca,   \
+                             nullptr, nullptr, *beta, reinterpret_cast<HT*>(c), descc);                              \
+  }                                                                                                                 \
+  int dlaf_mi355x_hermitian_rank_2k_update_##S(int ctx, char uplo, char trans, const CT* alpha, const CT* a,          \
+                                               DLAF_descriptor desca, const CT* b, DLAF_descriptor descb,            \
+                                               const RT* beta, CT* c, DLAF_descriptor descc) noexcept {              \
+    DevType<HT>::type al;                                                                                           \
+    std::memcpy(&al, alpha, sizeof(al));                                                                            \
+    return rank_update_c<HT>(ctx, uplo, trans, al, reinterpret_cast<const HT*>(a), desca,                            \
+                             reinterpret_cast<const HT*>(b), &descb, *beta, reinterpret_cast<HT*>(c), descc);        \
+  }                                                                                                                 \
+  void dlaf_mi355x_p##S##NAME(char uplo, char trans, int n, int k, const RT* alpha, const CT* a, int ia, int ja,      \
+                              const int desca[9], const RT* beta, CT* c, int ic, int jc,                             \
+                              const int descc[9]) noexcept {                                                         \
+    pxrank_update<HT>(uplo, trans, n, k, element_of_real<HT>(*alpha), reinterpret_cast<const HT*>(a), ia, ja, desca, \
+                      nullptr, 1, 1, nullptr, *beta, reinterpret_cast<HT*>(c), ic, jc, descc);                       \
+  }                                                                                                                 \
+  void dlaf_mi355x_p##S##NAME2(char uplo, char trans, int n, int k, const CT* alpha, const CT* a, int ia, int ja,     \
+                               const int desca[9], const CT* b, int ib, int jb, const int descb[9], const RT* beta,  \
+                               CT* c, int ic, int jc, const int descc[9]) noexcept {                                 \
+    DevType<HT>::type al;                                                                                           \
+    std::memcpy(&al, alpha, sizeof(al));                                                                            \
+    pxrank_update<HT>(uplo, trans, n, k, al, reinterpret_cast<const HT*>(a), ia, ja, desca,                          \
+                      reinterpret_cast<const HT*>(b), ib, jb, descb, *beta, reinterpret_cast<HT*>(c), ic, jc, descc); \
+  }
+DLAF_MI355X_RANK_UPDATE_ENTRY(s, float, float, float, syrk, syr2k)
+DLAF_MI355X_RANK_UPDATE_ENTRY(d, double, double, double, syrk, syr2k)
+DLAF_MI355X_RANK_UPDATE_ENTRY(c, std::complex<float>, dlaf_complex_c, float, herk, her2k)
+DLAF_MI355X_RANK_UPDATE_ENTRY(z, std::complex<double>, dlaf_complex_z, double, herk, her2k)
+#undef DLAF_MI355X_RANK_UPDATE_ENTRY
 #define DLAF_MI355X_POTRS_ENTRY(S, HT, CT)                                                                       \
   void dlaf_mi355x_p##S##potrs(char uplo, int n, int nrhs, const CT* a, int ia, int ja, const int desca[9], CT* b,  \
                                int ib, int jb, const int descb[9], int* info) noexcept {                        \

@@ -1,7 +1,8 @@
 // drivers.hpp -- what the algorithms on top of the tile kernels export: the triangular solver (solver.cpp), the
-// triangular, Hermitian and general multiplications (multiplication.cpp), generalized-to-standard (gen_to_std.cpp), the inverses
-// (inverse.cpp) and the norms (norm.cpp), host and device-resident forms.  reduction_to_band and the eigensolver stages
-// have headers of their own (red2band.hpp, eigensolver.hpp).
+// triangular, Hermitian and general multiplications (multiplication.cpp), the rank updates (rank_update.cpp),
+// generalized-to-standard (gen_to_std.cpp), the inverses (inverse.cpp) and the norms (norm.cpp), host and
+// device-resident forms.  reduction_to_band and the eigensolver stages have headers of their own (red2band.hpp,
+// eigensolver.hpp).
 #pragma once
 #include "device_matrix.hpp"
 
@@ -31,8 +32,10 @@ int triangular_multiplication_host(Grid* g, char side, char uplo, char op, char 
                                    int nb_free = 0);
 int triangular_multiplication_device(char side, char uplo, char op, char diag, const void* alpha, MatrixBase* a,
                                      MatrixBase* b);
-// device time and whole-grid flops of the last sweep of ANY multiplication (triangular, Hermitian, general) on this process
+// device time and whole-grid flops of the last sweep of ANY multiplication (triangular, Hermitian, general, rank update) on
+// this process; set_profile: how a sweep outside multiplication.cpp (rank_update.cpp) reports its own
 void multiplication_last_profile(double* ms, double* flops);
+void multiplication_set_profile(double ms, double flops);
 
 // C = beta C + alpha A B (side L) / beta C + alpha B A (side R), A Hermitian with only its uplo triangle read
 // (multiplication.cpp; dlaf::hermitian_multiplication, every side x uplo).  m x n: size of B and C, nb: A's square block =
@@ -54,6 +57,21 @@ int general_multiplication_host(Grid* g, char opa, char opb, T alpha, const T* a
                                 long k, int nb, int c_isrc, int c_jsrc);
 int general_multiplication_device(char opa, char opb, const void* alpha, MatrixBase* a, MatrixBase* b, const void* beta,
                                   MatrixBase* c);
+
+// Hermitian rank-k (her2k false) / rank-2k update of the uplo triangle of C (rank_update.cpp; xSYRK / xHERK, xSYR2K /
+// xHER2K): C = alpha A A^H + beta C (trans N, A n x k) / alpha A^H A + beta C (trans C, A k x n); her2k: alpha A B^H +
+// conj(alpha) B A^H + beta C / alpha A^H B + conj(alpha) B^H A + beta C, B stored, blocked and distributed like A.  alpha
+// of herk is real (im 0), beta is real.  The other triangle is never referenced; the imaginary part of C's diagonal is
+// ignored on entry and 0 on exit; beta == 0: C is not read; alpha == 0 or k == 0: A and B are not referenced, and with
+// beta == 1 nothing is touched.  Trans N on any grid, trans C on one process.  The arguments must have passed
+// require_rank_update (api_checks.hpp).  Host and resident forms (resident: C a DeviceMatrix whose stored triangle is
+// uplo, a / b general matrices, b null for herk; alpha points to a real for herk, to an element for her2k).
+template <class T>
+int hermitian_rank_update_host(Grid* g, bool her2k, char uplo, char trans, T alpha, const T* a, long lda, int a_isrc,
+                               int a_jsrc, const T* b, long ldb, real_t<T> beta, T* c, long ldc, long n, long k, int nb,
+                               int c_isrc, int c_jsrc);
+int hermitian_rank_update_device(char trans, const void* alpha, MatrixBase* a, MatrixBase* b, const void* beta,
+                                 MatrixBase* c);
 
 // A <- L^-1 A L^-H (uplo L) / U^-H A U^-1 (uplo U) with the Cholesky factor held in the same uplo triangle of
 // `l` (gen_to_std.cpp; dlaf::eigensolver::internal::generalized_to_standard); device-resident and host forms

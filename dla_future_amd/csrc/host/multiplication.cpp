@@ -404,6 +404,11 @@ void general_canonical(TileMatrix<T>& Ad, TileMatrix<T>& Bd, TileMatrix<T>& Cd, 
 
 }  // namespace
 
+void multiplication_set_profile(double ms, double flops) {
+  g_last_mult_ms = ms;
+  g_last_mult_flops = flops;
+}
+
 void multiplication_last_profile(double* ms, double* flops) {
   if (ms)
     *ms = g_last_mult_ms;

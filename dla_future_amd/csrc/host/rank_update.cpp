@@ -1,0 +1,257 @@
+// rank_update.cpp -- the Hermitian rank-k and rank-2k updates (xSYRK / xHERK, xSYR2K / xHER2K) of the uplo triangle
+// of C on a kernel that keeps a block of C in its accumulators over the k dimension (kernels_herk.hip):
+//        herk  : C = alpha A A^H + beta C (trans N)            alpha A^H A + beta C (trans C)
+//        her2k : C = alpha A B^H + conj(alpha) B A^H + beta C  alpha A^H B + conj(alpha) B^H A + beta C
+// alpha of herk and every beta are real.  BLAS semantics: the other triangle of C is never referenced; the imaginary
+// part of C's diagonal is ignored on entry and exactly 0 on exit; beta == 0: C is not read; alpha == 0 or k == 0: A and
+// B are not referenced; then with beta == 1 nothing at all is touched.
+//
+// Reference: the herk / her2k tile calls of dlaf::cholesky_factorization and generalized_to_standard
+// (factorization/cholesky/impl.h, eigensolver/gen_to_std/impl.h), which the reference never exposes as an algorithm.
+//
+// C is a DeviceMatrix (the operand of factorize(), gen_to_std and the eigensolvers): uplo U holds the plain transposed
+// view, whose lower triangle is conj(C)'s -- the kernel updates it with conj(A), conj(B) and conj(alpha) (conj_view).
+// One process: ONE launch over all the k tiles, both trans.  A grid (trans N only: the entries refuse the rest) runs
+// SUMMA, one step per k tile l, nothing reduced:
+//   column l of A        along the process rows from the owner column (bcast_view_column): the tiles A(i, l) of my
+//                        local tile rows i of C
+//   its transposed panel down the process columns, one broadcast per root process row
+//                        (bcast_transposed_panel_whole): the tiles A(j, l) of my local tile columns j of C
+//   (her2k: the same for B)
+//   one launch with nk = 1 (first: l == 0)
+// all of it on s_comm one step ahead, into rings of kBuf buffers.  A (and B) start on C's process row (the entries check).
+#include <algorithm>
+#include <type_traits>
+#include <vector>
+
+#include "../device/herk_map.hpp"
+#include "drivers.hpp"
+#include "sweep.hpp"
+#include "tile_matrix.hpp"
+
+namespace dlaf_mi355x {
+
+namespace {
+
+// Ad (and Bd, her2k; null: herk): the operands AS STORED, n x k (trans N) or k x n; nkt: the k tiles to multiply
+// (0: k == 0 or alpha == 0 -- the triangle becomes beta C, Ad and Bd are not touched)
+template <class T>
+void rank_update_canonical(DeviceMatrix<T>& C, TileMatrix<T>* Ad, TileMatrix<T>* Bd, bool trans_n, long k, long nkt,
+                           T alpha, real_t<T> beta) {
+  Grid* g = C.grid;
+  Transport* tr = grid_transport(*g);
+  const bool dist = g->nranks > 1;
+  const bool two = Bd != nullptr;
+  const size_t te = C.tile_elems;
+
+  RankKArgs<T> ra;
+  ra.c = C.tiles;
+  ra.c_tsr = (long) te;
+  ra.c_tsc = (long) (te * C.ltr);
+  ra.x = ra.y = nullptr;
+  ra.x_ts = ra.y_ts = ra.ks = 0;
+  ra.trans = trans_n ? 'N' : 'C';
+  ra.conj_view = C.transposed ? 1 : 0;
+  ra.nk = 0;
+  ra.k_last = 0;
+  ra.ltr = (int) C.ltr;
+  ra.ltc = (int) C.ltc;
+  ra.nb = C.nb;
+  ra.pr = C.rows.P;
+  ra.ri = C.rows.shift();
+  ra.pc = C.cols.P;
+  ra.ci = C.cols.shift();
+  ra.nt = (int) C.nt;
+  ra.last = C.rows.last_extent();
+  ra.alpha = alpha;
+  ra.beta = beta;
+  const bool work = C.ltr > 0 && C.ltc > 0;
+
+  Sweep sw(false, false);
+  const hipStream_t s_main = sw.s_main, s_comm = sw.s_comm;
+  if (nkt == 0 || !dist) {
+    sw.begin(false);
+    if (nkt > 0) {
+      // tile (i, t) of a stored n x k matrix: rows next to each other; tile (t, i) of a stored k x n one: columns
+      ra.x = ra.y = Ad->tiles;
+      ra.x_ts = ra.y_ts = (long) (trans_n ? te : te * Ad->ltr);
+      ra.ks = (long) (trans_n ? te * Ad->ltr : te);
+      if (two)
+        ra.x2 = ra.y2 = Bd->tiles;
+      ra.nk = (int) nkt;
+      ra.k_last = (trans_n ? Ad->cols : Ad->rows).last_extent();
+    }
+    if (work)
+      launch_rank_k(ra, s_main);
+  }
+  else {
+    // in terms of the caller's C: its tile rows are spread like A's (the same axis), its tile columns over the
+    // process columns
+    const Axis& srow = Ad->rows;
+    const Axis& scol = C.transposed ? C.rows : C.cols;
+    const Axis& ka = Ad->cols;
+    const bool hop = srow.P > 1;  // the transposed panel travels; else every tile of the column panel is here
+    Events ev_in((size_t) nkt), ev_done((size_t) nkt);
+    const size_t rp = (size_t) Ad->ltr * te, cp = (size_t) (scol.local_tiles() + srow.P) * te;
+    Ring<T> arow(rp, ka.P > 1), acol(cp, hop), brow(rp, two && ka.P > 1), bcol(cp, two && hop);
+    struct Panel {
+      const T* base = nullptr;
+      long ts = 0, ts2 = 0;
+      int period = 1;
+    };
+    struct StepOperands {
+      Panel arow, acol, brow, bcol;
+    };
+    std::vector<StepOperands> sop((size_t) nkt);
+    auto fetch_one = [&](TileMatrix<T>& M, long l, T* rbuf, T* cbuf, Panel& prow, Panel& pcol) {
+      prow.base = bcast_view_column(tr, M, l, rbuf, s_comm);
+      prow.ts = (long) te;
+      if (hop) {
+        (void) bcast_transposed_panel_whole(tr, CommAxis::Col, srow, scol, prow.base, cbuf, te, s_comm, pcol.period,
+                                            pcol.ts2);
+        pcol.base = cbuf;
+        pcol.ts = (long) te;
+      }
+      else {
+        // I hold every tile row of the panel: the tile of global row gj sits at local row gj
+        pcol.base = prow.base + (size_t) scol.shift() * te;
+        pcol.ts = (long) te * scol.P;
+      }
+    };
+    auto fetch = [&](long l) {
+      const int buf = (int) (l % kBuf);
+      if (l >= kBuf)
+        DLAF_HIP_CHECK(hipStreamWaitEvent(s_comm, ev_done[(size_t) (l - kBuf)], 0));
+      StepOperands& o = sop[(size_t) l];
+      fetch_one(*Ad, l, arow[buf], acol[buf], o.arow, o.acol);
+      if (two)
+        fetch_one(*Bd, l, brow[buf], bcol[buf], o.brow, o.bcol);
+      DLAF_HIP_CHECK(hipEventRecord(ev_in[(size_t) l], s_comm));
+    };
+
+    sw.begin(true);
+    fetch(0);
+    for (long l = 0; l < nkt; ++l) {
+      if (l + 1 < nkt)
+        fetch(l + 1);
+      DLAF_HIP_CHECK(hipStreamWaitEvent(s_main, ev_in[(size_t) l], 0));
+      if (work) {
+        const StepOperands& o = sop[(size_t) l];
+        // the view's rows are C's rows (uplo L) or C's columns (uplo U: the transposed view)
+        const Panel& px = C.transposed ? o.acol : o.arow;
+        const Panel& py = C.transposed ? o.arow : o.acol;
+        ra.x = px.base;
+        ra.x_ts = px.ts;
+        ra.x_ts2 = px.ts2;
+        ra.x_period = px.period;
+        ra.y = py.base;
+        ra.y_ts = py.ts;
+        ra.y_ts2 = py.ts2;
+        ra.y_period = py.period;
+        if (two) {
+          ra.x2 = (C.transposed ? o.bcol : o.brow).base;
+          ra.y2 = (C.transposed ? o.brow : o.bcol).base;
+        }
+        ra.ks = 0;
+        ra.nk = 1;
+        ra.k_last = ka.tile_extent(l);
+        ra.first = l == 0 ? 1 : 0;
+        launch_rank_k(ra, s_main);
+      }
+      DLAF_HIP_CHECK(hipEventRecord(ev_done[(size_t) l], s_main));
+    }
+  }
+  const double ms = sw.finish();
+  // whole-grid algorithmic flops: k n (n + 1) per product (x4 complex)
+  multiplication_set_profile(ms, (TypeInfo<T>::is_complex ? 4.0 : 1.0) * (two ? 2.0 : 1.0) * (double) k * (double) C.n *
+                                     (double) (C.n + 1));
+}
+
+}  // namespace
+
+template <class T>
+int hermitian_rank_update_host(Grid* g, bool her2k, char uplo, char trans, T alpha, const T* a, long lda, int a_isrc,
+                               int a_jsrc, const T* b, long ldb, real_t<T> beta, T* c, long ldc, long n, long k, int nb,
+                               int c_isrc, int c_jsrc) {
+  if (n == 0)
+    return 0;
+  const bool product = k > 0 && !is_zero(alpha);
+  if (!product && beta == real_t<T>(1))
+    return 0;  // quick return: C is untouched, the imaginary parts of its diagonal included
+  runtime_init();
+  (void) grid_transport(*g);
+  if (g->nranks > 1 && !g->transport)
+    fatal("[dlaf_mi355x] grid with %d ranks has no transport\n", g->nranks);
+  const bool tn = herk_trans_is_n(trans);
+  hipStream_t s = nullptr;
+  DLAF_HIP_CHECK(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
+  {
+    DeviceMatrix<T> Cd;
+    Cd.create(g, uplo, n, nb, c_isrc, c_jsrc);
+    TileMatrix<T> Ad, Bd;
+    if (product) {
+      Ad.create(g, false, tn ? n : k, tn ? k : n, nb, a_isrc, a_jsrc);
+      Ad.upload(a, lda, false, false, T{}, s);
+      if (her2k) {
+        Bd.create(g, false, tn ? n : k, tn ? k : n, nb, a_isrc, a_jsrc);
+        Bd.upload(b, ldb, false, false, T{}, s);
+      }
+      DLAF_HIP_CHECK(hipStreamSynchronize(s));
+    }
+    const bool read_c = beta != real_t<T>(0);  // beta = 0: C is not read
+    if (read_c)
+      Cd.upload(c, ldc);
+    rank_update_canonical<T>(Cd, product ? &Ad : nullptr, (product && her2k) ? &Bd : nullptr, tn, k,
+                             product ? (k + nb - 1) / nb : 0, alpha, beta);
+    Cd.download(c, ldc, read_c);
+  }
+  DLAF_HIP_CHECK(hipStreamDestroy(s));
+  return 0;
+}
+
+// The same on RESIDENT operands (arguments judged by the entry, c_api_device.cpp): C a DeviceMatrix whose stored triangle
+// is uplo, A (and B; null: herk) general resident matrices.  alpha: real_t<T> for herk, T for her2k; beta: real_t<T>.
+int hermitian_rank_update_device(char trans, const void* alpha, MatrixBase* a, MatrixBase* b, const void* beta,
+                                 MatrixBase* c) {
+  const char* who = b ? "hermitian rank-2k update" : "hermitian rank-k update";
+  if (!a || !c || a->type != c->type || (b && b->type != c->type))
+    fatal("[dlaf_mi355x] %s: operands of different element types\n", who);
+  return dispatch_type(c->type, [&](auto* tag) {
+    using T = std::remove_pointer_t<decltype(tag)>;
+    using R = real_t<T>;
+    auto& A = static_cast<GeneralMatrix<T>&>(*a);
+    auto* B = b ? &static_cast<GeneralMatrix<T>&>(*b) : nullptr;
+    auto& C = static_cast<DeviceMatrix<T>&>(*c);
+    if (A.m.grid != C.grid || (B && B->m.grid != C.grid))
+      fatal("[dlaf_mi355x] %s: the operands live on different grids\n", who);
+    if (C.n == 0)
+      return 0;
+    T al{};
+    if (b)
+      al = *static_cast<const T*>(alpha);
+    else if constexpr (TypeInfo<T>::is_complex)
+      al = T{*static_cast<const R*>(alpha), R(0)};
+    else
+      al = *static_cast<const R*>(alpha);
+    const R be = *static_cast<const R*>(beta);
+    const bool tn = herk_trans_is_n(trans);
+    const long k = tn ? A.cols_g : A.rows_g;
+    const bool product = k > 0 && !is_zero(al);
+    if (!product && be == R(1))
+      return 0;
+    rank_update_canonical<T>(C, product ? &A.m : nullptr, (product && B) ? &B->m : nullptr, tn, k,
+                             product ? (k + C.nb - 1) / C.nb : 0, al, be);
+    return 0;
+  });
+}
+
+#define DLAF_RANK_UPDATE_INST(T)                                                                                     \
+  template int hermitian_rank_update_host<T>(Grid*, bool, char, char, T, const T*, long, int, int, const T*, long,  \
+                                             real_t<T>, T*, long, long, long, int, int, int);
+DLAF_RANK_UPDATE_INST(float)
+DLAF_RANK_UPDATE_INST(double)
+DLAF_RANK_UPDATE_INST(cfloat)
+DLAF_RANK_UPDATE_INST(cdouble)
+#undef DLAF_RANK_UPDATE_INST
+
+}  // namespace dlaf_mi355x

@@ -289,6 +289,47 @@ const T* bcast_view_column(Transport* tr, const TileMatrix<T>& V, long k, T* els
   return p;
 }
 
+// The WHOLE transposed panel of a step (DeviceMatrix::bcast_transposed_panel leaves out the last global tile row, which
+// the factorization never needs): `have` is the axis the column panel at a_base is spread over -- the tile of global row
+// g sits at a_base + have.local_of(g) * tile_elems on the process have.owner(g) of my communicator `ax` --, `want` the
+// axis whose EVERY local tile jl needs the panel's tile of global row want.global_of(jl).  One broadcast per root
+// process: the local tiles fall into `period` classes by root, class c = tiles c, c + period, ... lands contiguously
+// at dst + c * ts2 (the root packs its -- strided -- tiles there first), so tile jl is read at
+// dst + (jl % period) * ts2 + (jl / period) * tile_elems.  dst holds (want.local_tiles() + have.P) tiles.  Returns the
+// number of broadcasts issued.
+template <class T>
+int bcast_transposed_panel_whole(Transport* tr, CommAxis ax, const Axis& have, const Axis& want, const T* a_base, T* dst,
+                                 size_t tile_elems, hipStream_t s, int& period, long& ts2) {
+  const size_t tile_bytes = tile_elems * sizeof(T);
+  const long ncols = want.local_tiles();
+  long g = have.P, r = want.P;
+  while (r) {
+    const long t = g % r;
+    g = r;
+    r = t;
+  }
+  // owner(global_of(jl)) repeats in jl with period lcm(have.P, want.P) / want.P
+  period = (int) (have.P / g);
+  const long lstep = want.P / g;  // local-row distance on the root between consecutive tiles of a class
+  const long cap = ncols > 0 ? (ncols + period - 1) / period : 0;
+  ts2 = cap * (long) tile_elems;
+  int issued = 0;
+  tr->group_begin();
+  for (long c = 0; c < period && c < ncols; ++c) {
+    const long gj_first = want.global_of(c);
+    const int root = have.owner(gj_first);
+    const long cnt = (ncols - c + period - 1) / period;
+    T* d = dst + c * ts2;
+    if (have.rank == root)
+      DLAF_HIP_CHECK(hipMemcpy2DAsync(d, tile_bytes, a_base + (size_t) have.local_of(gj_first) * tile_elems,
+                                      (size_t) lstep * tile_bytes, tile_bytes, (size_t) cnt, hipMemcpyDeviceToDevice, s));
+    tr->bcast(ax, root, have.rank, d, d, (size_t) cnt * tile_bytes, s);
+    ++issued;
+  }
+  tr->group_end();
+  return issued;
+}
+
 // ---- drivers ----------------------------------------------------------------------------------------------
 inline bool side_is_left(char side) {
   return side == 'L' || side == 'l';

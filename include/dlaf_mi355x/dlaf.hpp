@@ -521,6 +521,80 @@ void generalMatrix(comm::CommunicatorGrid& grid, const T alpha, const Matrix<T, 
 }
 }  // namespace multiplication::internal
 
+// BLAS xSYRK / xHERK and xSYR2K / xHER2K on host-resident operands (the reference runs them tile by tile inside its
+// algorithms and exposes no such call; the names follow hermitian_multiplication): only the uplo triangle of mat_c is read
+// or written, its diagonal comes back real.
+//   rank-k : C = alpha A A^H + beta C (NoTrans, A n x k) / alpha A^H A + beta C (ConjTrans, A k x n); alpha, beta real
+//   rank-2k: C = alpha A B^H + conj(alpha) B A^H + beta C / alpha A^H B + conj(alpha) B^H A + beta C; beta real
+// Real types also take Trans (= ConjTrans); complex types refuse it.  Local matrices: both ops.  A grid of more than one
+// process: NoTrans only.  One square block for all operands; mat_b is stored, blocked and distributed like mat_a.
+namespace internal {
+template <class M>
+DLAF_descriptor rank_update_descriptor(const M& m) {
+  const auto& d = m.distribution();
+  return DLAF_descriptor{(int) d.size().rows(), (int) d.size().cols(), (int) d.block_size().rows(),
+                         (int) d.block_size().cols(), (int) d.source_rank_index().row(),
+                         (int) d.source_rank_index().col(), 0, 0, (int) m.ld()};
+}
+}  // namespace internal
+template <Backend B, Device D, class T>
+void hermitian_rank_k_update(comm::CommunicatorGrid& grid, blas::Uplo uplo, blas::Op op, const BaseType<T> alpha,
+                             const Matrix<T, Device::CPU>& mat_a, const BaseType<T> beta, Matrix<T, Device::CPU>& mat_c) {
+  static_assert(B == Backend::GPU, "this library has no CPU backend");
+  const DLAF_descriptor da = internal::rank_update_descriptor(mat_a), dc = internal::rank_update_descriptor(mat_c);
+  int r;
+  if constexpr (std::is_same_v<T, float>)
+    r = dlaf_mi355x_hermitian_rank_k_update_s(grid.context(), (char) uplo, (char) op, &alpha, mat_a.ptr(), da, &beta,
+                                              mat_c.ptr(), dc);
+  else if constexpr (std::is_same_v<T, double>)
+    r = dlaf_mi355x_hermitian_rank_k_update_d(grid.context(), (char) uplo, (char) op, &alpha, mat_a.ptr(), da, &beta,
+                                              mat_c.ptr(), dc);
+  else if constexpr (std::is_same_v<T, std::complex<float>>)
+    r = dlaf_mi355x_hermitian_rank_k_update_c(grid.context(), (char) uplo, (char) op, &alpha, mat_a.ptr(), da, &beta,
+                                              mat_c.ptr(), dc);
+  else
+    r = dlaf_mi355x_hermitian_rank_k_update_z(grid.context(), (char) uplo, (char) op, &alpha, mat_a.ptr(), da, &beta,
+                                              mat_c.ptr(), dc);
+  if (r != 0)
+    internal::fail("hermitian_rank_k_update");
+}
+template <Backend B, Device D, class T>
+void hermitian_rank_2k_update(comm::CommunicatorGrid& grid, blas::Uplo uplo, blas::Op op, const T alpha,
+                              const Matrix<T, Device::CPU>& mat_a, const Matrix<T, Device::CPU>& mat_b,
+                              const BaseType<T> beta, Matrix<T, Device::CPU>& mat_c) {
+  static_assert(B == Backend::GPU, "this library has no CPU backend");
+  const DLAF_descriptor da = internal::rank_update_descriptor(mat_a), db = internal::rank_update_descriptor(mat_b),
+                        dc = internal::rank_update_descriptor(mat_c);
+  int r;
+  if constexpr (std::is_same_v<T, float>)
+    r = dlaf_mi355x_hermitian_rank_2k_update_s(grid.context(), (char) uplo, (char) op, &alpha, mat_a.ptr(), da, mat_b.ptr(),
+                                               db, &beta, mat_c.ptr(), dc);
+  else if constexpr (std::is_same_v<T, double>)
+    r = dlaf_mi355x_hermitian_rank_2k_update_d(grid.context(), (char) uplo, (char) op, &alpha, mat_a.ptr(), da, mat_b.ptr(),
+                                               db, &beta, mat_c.ptr(), dc);
+  else if constexpr (std::is_same_v<T, std::complex<float>>)
+    r = dlaf_mi355x_hermitian_rank_2k_update_c(grid.context(), (char) uplo, (char) op, &alpha, mat_a.ptr(), da, mat_b.ptr(),
+                                               db, &beta, mat_c.ptr(), dc);
+  else
+    r = dlaf_mi355x_hermitian_rank_2k_update_z(grid.context(), (char) uplo, (char) op, &alpha, mat_a.ptr(), da, mat_b.ptr(),
+                                               db, &beta, mat_c.ptr(), dc);
+  if (r != 0)
+    internal::fail("hermitian_rank_2k_update");
+}
+// the local overloads
+template <Backend B, Device D, class T>
+void hermitian_rank_k_update(blas::Uplo uplo, blas::Op op, const BaseType<T> alpha, const Matrix<T, Device::CPU>& mat_a,
+                             const BaseType<T> beta, Matrix<T, Device::CPU>& mat_c) {
+  comm::CommunicatorGrid grid = comm::CommunicatorGrid::single();
+  hermitian_rank_k_update<B, D, T>(grid, uplo, op, alpha, mat_a, beta, mat_c);
+}
+template <Backend B, Device D, class T>
+void hermitian_rank_2k_update(blas::Uplo uplo, blas::Op op, const T alpha, const Matrix<T, Device::CPU>& mat_a,
+                              const Matrix<T, Device::CPU>& mat_b, const BaseType<T> beta, Matrix<T, Device::CPU>& mat_c) {
+  comm::CommunicatorGrid grid = comm::CommunicatorGrid::single();
+  hermitian_rank_2k_update<B, D, T>(grid, uplo, op, alpha, mat_a, mat_b, beta, mat_c);
+}
+
 // include/dlaf/eigensolver/gen_to_std.h:50, :101: A <- inv(L) A inv(L^H) (Lower) / inv(U^H) A inv(U) (Upper) with
 // the Cholesky factor of B in mat_b (host-resident operands; only the uplo triangles are referenced)
 namespace eigensolver::internal {

@@ -294,6 +294,85 @@ DLAF_EXTERN_C void dlaf_mi355x_pzgemm(char transa, char transb, int m, int n, in
                                       const int descb[9], const dlaf_complex_z* beta, dlaf_complex_z* c, int ic, int jc,
                                       const int descc[9]) DLAF_NOEXCEPT;
 
+/* ---- Hermitian rank-k and rank-2k updates ---------------------------------------------------- */
+/* BLAS xSYRK / xHERK and xSYR2K / xHER2K on the grid (the reference runs them tile by tile inside its Cholesky and
+ * generalized-to-standard algorithms and has no entry for them; the p? names take ScaLAPACK's argument lists).  uplo
+ * 'L' or 'U': only that triangle of the n x n matrix C is read or written.
+ *   rank-k  (s, d: syrk;  c, z: herk)    alpha and beta are REAL
+ *     trans 'N':  C = alpha A A^H + beta C,  A stored n x k        trans 'C':  C = alpha A^H A + beta C,  A stored k x n
+ *   rank-2k (s, d: syr2k; c, z: her2k)   alpha is of the element type, beta is REAL; B is stored like A
+ *     trans 'N':  C = alpha A B^H + conj(alpha) B A^H + beta C     trans 'C':  C = alpha A^H B + conj(alpha) B^H A + beta C
+ * Real types also accept trans 'T', which equals 'C'.  Complex types refuse 'T': that is the complex-symmetric
+ * p{c,z}syrk / p{c,z}syr2k, which is not built.
+ * Semantics (BLAS):
+ *   - the other triangle of C is never referenced: it stays bit for bit, and NaNs in it reach nothing;
+ *   - complex types: the imaginary part of C's diagonal is ignored on entry and is exactly 0 on exit, also when only
+ *     beta is applied;
+ *   - beta = 0: C is not read (NaNs in its triangle do not survive);
+ *   - alpha = 0 or k = 0: A (and B) are not referenced and the triangle becomes beta C;
+ *   - if, in addition, beta = 1: quick return, C is untouched bit for bit, diagonal imaginary parts included;
+ *   - n = 0 returns before the GPU is touched.
+ * One process: both trans.  A grid of more than one process: trans 'N' only.  Requirements of this build: one square
+ * block for A, B and C; no sub-matrix offsets; B has A's shape, blocks and source process; with trans 'N', A starts on
+ * C's process row (desca.isrc = descc.isrc).  Returns 0; a violated requirement terminates with a message "hermitian
+ * rank-k update: ..." / "hermitian rank-2k update: ..." before the GPU is touched. */
+DLAF_EXTERN_C int dlaf_mi355x_hermitian_rank_k_update_s(int context, char uplo, char trans, const float* alpha,
+                                                        const float* a, struct DLAF_descriptor desca, const float* beta,
+                                                        float* c, struct DLAF_descriptor descc) DLAF_NOEXCEPT;
+DLAF_EXTERN_C int dlaf_mi355x_hermitian_rank_k_update_d(int context, char uplo, char trans, const double* alpha,
+                                                        const double* a, struct DLAF_descriptor desca, const double* beta,
+                                                        double* c, struct DLAF_descriptor descc) DLAF_NOEXCEPT;
+DLAF_EXTERN_C int dlaf_mi355x_hermitian_rank_k_update_c(int context, char uplo, char trans, const float* alpha,
+                                                        const dlaf_complex_c* a, struct DLAF_descriptor desca, const float* beta,
+                                                        dlaf_complex_c* c, struct DLAF_descriptor descc) DLAF_NOEXCEPT;
+DLAF_EXTERN_C int dlaf_mi355x_hermitian_rank_k_update_z(int context, char uplo, char trans, const double* alpha,
+                                                        const dlaf_complex_z* a, struct DLAF_descriptor desca, const double* beta,
+                                                        dlaf_complex_z* c, struct DLAF_descriptor descc) DLAF_NOEXCEPT;
+DLAF_EXTERN_C int dlaf_mi355x_hermitian_rank_2k_update_s(int context, char uplo, char trans, const float* alpha,
+                                                         const float* a, struct DLAF_descriptor desca, const float* b,
+                                                         struct DLAF_descriptor descb, const float* beta, float* c,
+                                                         struct DLAF_descriptor descc) DLAF_NOEXCEPT;
+DLAF_EXTERN_C int dlaf_mi355x_hermitian_rank_2k_update_d(int context, char uplo, char trans, const double* alpha,
+                                                         const double* a, struct DLAF_descriptor desca, const double* b,
+                                                         struct DLAF_descriptor descb, const double* beta, double* c,
+                                                         struct DLAF_descriptor descc) DLAF_NOEXCEPT;
+DLAF_EXTERN_C int dlaf_mi355x_hermitian_rank_2k_update_c(int context, char uplo, char trans, const dlaf_complex_c* alpha,
+                                                         const dlaf_complex_c* a, struct DLAF_descriptor desca, const dlaf_complex_c* b,
+                                                         struct DLAF_descriptor descb, const float* beta, dlaf_complex_c* c,
+                                                         struct DLAF_descriptor descc) DLAF_NOEXCEPT;
+DLAF_EXTERN_C int dlaf_mi355x_hermitian_rank_2k_update_z(int context, char uplo, char trans, const dlaf_complex_z* alpha,
+                                                         const dlaf_complex_z* a, struct DLAF_descriptor desca, const dlaf_complex_z* b,
+                                                         struct DLAF_descriptor descb, const double* beta, dlaf_complex_z* c,
+                                                         struct DLAF_descriptor descc) DLAF_NOEXCEPT;
+DLAF_EXTERN_C void dlaf_mi355x_pssyrk(char uplo, char trans, int n, int k, const float* alpha, const float* a, int ia,
+                                      int ja, const int desca[9], const float* beta, float* c, int ic, int jc,
+                                      const int descc[9]) DLAF_NOEXCEPT;
+DLAF_EXTERN_C void dlaf_mi355x_pdsyrk(char uplo, char trans, int n, int k, const double* alpha, const double* a, int ia,
+                                      int ja, const int desca[9], const double* beta, double* c, int ic, int jc,
+                                      const int descc[9]) DLAF_NOEXCEPT;
+DLAF_EXTERN_C void dlaf_mi355x_pcherk(char uplo, char trans, int n, int k, const float* alpha, const dlaf_complex_c* a, int ia,
+                                      int ja, const int desca[9], const float* beta, dlaf_complex_c* c, int ic, int jc,
+                                      const int descc[9]) DLAF_NOEXCEPT;
+DLAF_EXTERN_C void dlaf_mi355x_pzherk(char uplo, char trans, int n, int k, const double* alpha, const dlaf_complex_z* a, int ia,
+                                      int ja, const int desca[9], const double* beta, dlaf_complex_z* c, int ic, int jc,
+                                      const int descc[9]) DLAF_NOEXCEPT;
+DLAF_EXTERN_C void dlaf_mi355x_pssyr2k(char uplo, char trans, int n, int k, const float* alpha, const float* a,
+                                       int ia, int ja, const int desca[9], const float* b, int ib, int jb,
+                                       const int descb[9], const float* beta, float* c, int ic, int jc,
+                                       const int descc[9]) DLAF_NOEXCEPT;
+DLAF_EXTERN_C void dlaf_mi355x_pdsyr2k(char uplo, char trans, int n, int k, const double* alpha, const double* a,
+                                       int ia, int ja, const int desca[9], const double* b, int ib, int jb,
+                                       const int descb[9], const double* beta, double* c, int ic, int jc,
+                                       const int descc[9]) DLAF_NOEXCEPT;
+DLAF_EXTERN_C void dlaf_mi355x_pcher2k(char uplo, char trans, int n, int k, const dlaf_complex_c* alpha, const dlaf_complex_c* a,
+                                       int ia, int ja, const int desca[9], const dlaf_complex_c* b, int ib, int jb,
+                                       const int descb[9], const float* beta, dlaf_complex_c* c, int ic, int jc,
+                                       const int descc[9]) DLAF_NOEXCEPT;
+DLAF_EXTERN_C void dlaf_mi355x_pzher2k(char uplo, char trans, int n, int k, const dlaf_complex_z* alpha, const dlaf_complex_z* a,
+                                       int ia, int ja, const int desca[9], const dlaf_complex_z* b, int ib, int jb,
+                                       const int descb[9], const double* beta, dlaf_complex_z* c, int ic, int jc,
+                                       const int descc[9]) DLAF_NOEXCEPT;
+
 /* ScaLAPACK p?potrs: A X = B with the factor dlaf_p?potrf left in a (two triangular solves; b is overwritten) */
 DLAF_EXTERN_C void dlaf_mi355x_pspotrs(char uplo, int n, int nrhs, const float* a, int ia, int ja, const int desca[9],
                                        float* b, int ib, int jb, const int descb[9], int* info) DLAF_NOEXCEPT;
@@ -736,11 +815,23 @@ DLAF_EXTERN_C int dlaf_mi355x_hermitian_multiplication_device(char side, char up
 DLAF_EXTERN_C int dlaf_mi355x_general_multiplication_device(char opa, char opb, const void* alpha,
                                                             dlaf_mi355x_gmatrix_t a, dlaf_mi355x_gmatrix_t b,
                                                             const void* beta, dlaf_mi355x_gmatrix_t c) DLAF_NOEXCEPT;
+/* The Hermitian rank-k / rank-2k updates on resident operands: c a dlaf_mi355x_matrix_t created with this uplo (the
+ * operand of dlaf_mi355x_matrix_factorize, gen_to_std and the eigensolvers), a and b general resident matrices as stored
+ * (n x k for trans 'N', k x n for 'C'); only c's uplo triangle is written, nothing crosses PCIe.  alpha points to a real
+ * (rank-k) or to an element (rank-2k), beta to a real, of c's precision.  Semantics and requirements of the host
+ * entries; a handle or scalar that is null returns -1. */
+DLAF_EXTERN_C int dlaf_mi355x_hermitian_rank_k_update_device(char uplo, char trans, const void* alpha,
+                                                             dlaf_mi355x_gmatrix_t a, const void* beta,
+                                                             dlaf_mi355x_matrix_t c) DLAF_NOEXCEPT;
+DLAF_EXTERN_C int dlaf_mi355x_hermitian_rank_2k_update_device(char uplo, char trans, const void* alpha,
+                                                              dlaf_mi355x_gmatrix_t a, dlaf_mi355x_gmatrix_t b,
+                                                              const void* beta, dlaf_mi355x_matrix_t c) DLAF_NOEXCEPT;
 /* Device time (ms, HIP events on the compute stream) of the sweep of the last triangular multiplication on this
  * process -- relayout and PCIe staging excluded -- and the whole-grid algorithmic flops it stands for (m n^2 for
  * side R, m^2 n for side L; x4 complex), as dlaf_mi355x_solver_profile.  The last multiplication of EITHER kind is
  * reported: after a Hermitian multiplication, its sweep and twice those flops (2 m n^2 / 2 m^2 n; x4 complex); after a
- * general multiplication, its sweep and 2 m n k (x4 complex). */
+ * general multiplication, its sweep and 2 m n k (x4 complex); after a Hermitian rank-k update, its sweep and k n (n + 1)
+ * (rank-2k: twice that; x4 complex). */
 DLAF_EXTERN_C int dlaf_mi355x_multiplication_profile(double* ms, double* flops) DLAF_NOEXCEPT;
 
 /* ---- synthetic input ------------------------------------------------------------------------ */

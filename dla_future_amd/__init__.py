@@ -14,6 +14,7 @@ Python doorway onto that ABI, mirroring the reference's operator surface for the
     dlaf::hermitian_multiplication(side, uplo, ...)    include/dlaf/multiplication/hermitian.h
     dlaf::multiplication::internal::generalMatrix(...) include/dlaf/multiplication/general.h (p?gemm)
     hermitian_rank_k_update / hermitian_rank_2k_update BLAS xSYRK / xHERK, xSYR2K / xHER2K (p?syrk, p?herk, p?syr2k, p?her2k)
+    general_addition / hermitian_complete              PBLAS p?geadd, p?tradd, p?tran / p?tranu / p?tranc, ScaLAPACK p?lacpy
     dlaf::triangular_inverse(uplo, diag, A)            LAPACK xTRTRI / p?trtri (upstream: after the reference snapshot)
     dlaf::inverse_from_cholesky_factor(uplo, A)        LAPACK xPOTRI / p?potri
     dlaf::auxiliary::max_norm(grid, rank, uplo, A)     include/dlaf/auxiliary/norm.h (+ one / inf / Frobenius: p?lange, p?lanhe, p?lantr)
@@ -32,6 +33,8 @@ from .cholesky import (DeviceMatrix, GeneralDeviceMatrix, Grid, cholesky_factori
                        triangular_multiplication_device, hermitian_multiplication, hermitian_multiplication_device,
                        pxhemm, general_multiplication, general_multiplication_device, pxgemm, hermitian_rank_k_update,
                        hermitian_rank_2k_update, hermitian_rank_k_update_device, hermitian_rank_2k_update_device, pxherk, pxher2k,
+                       general_addition, hermitian_complete, pxgeadd, pxtradd, pxtran, pxlacpy, general_addition_device,
+                       hermitian_complete_device, addition_profile,
                        update_direct, update_bulk_slots, trsm_direct, potrf_direct, matrix_norm,
                        matrix_norm_device, pxlange, pxlanhe, pxlantr, norm_profile)
 from . import distribution  # noqa: F401
@@ -54,7 +57,9 @@ __all__ = ["band_to_tridiagonal", "bt_band_to_tridiagonal", "eigensolver_profile
            "triangular_multiplication", "triangular_multiplication_device", "pxtrmm", "multiplication_profile",
            "hermitian_multiplication", "hermitian_multiplication_device", "pxhemm", "general_multiplication",
            "general_multiplication_device", "pxgemm", "hermitian_rank_k_update", "hermitian_rank_2k_update",
-           "hermitian_rank_k_update_device", "hermitian_rank_2k_update_device", "pxherk", "pxher2k", "update_direct",
+           "hermitian_rank_k_update_device", "hermitian_rank_2k_update_device", "pxherk", "pxher2k", "general_addition",
+           "hermitian_complete", "pxgeadd", "pxtradd", "pxtran", "pxlacpy", "general_addition_device",
+           "hermitian_complete_device", "addition_profile", "update_direct",
            "update_bulk_slots",
            "trsm_direct", "potrf_direct", "pxheevd_partial_spectrum", "partial_spectrum_plan", "hermitian_eigenvalues",
            "hermitian_generalized_eigenvalues", "pxheevd_eigenvalues", "pxheevd_partial_spectrum_by_value", "pxhegvd_eigenvalues",

@@ -163,6 +163,32 @@ SIGNATURES = {
     "dlaf_mi355x_pdsyr2k": (None, [_ch, _ch, _i, _i, _vp, _vp, _i, _i, _IP, _vp, _i, _i, _IP, _vp, _vp, _i, _i, _IP]),
     "dlaf_mi355x_pcher2k": (None, [_ch, _ch, _i, _i, _vp, _vp, _i, _i, _IP, _vp, _i, _i, _IP, _vp, _vp, _i, _i, _IP]),
     "dlaf_mi355x_pzher2k": (None, [_ch, _ch, _i, _i, _vp, _vp, _i, _i, _IP, _vp, _i, _i, _IP, _vp, _vp, _i, _i, _IP]),
+    "dlaf_mi355x_general_addition_s": (_i, [_i, _ch, _ch, _vp, _vp, DLAFDescriptor, _vp, _vp, DLAFDescriptor]),
+    "dlaf_mi355x_general_addition_d": (_i, [_i, _ch, _ch, _vp, _vp, DLAFDescriptor, _vp, _vp, DLAFDescriptor]),
+    "dlaf_mi355x_general_addition_c": (_i, [_i, _ch, _ch, _vp, _vp, DLAFDescriptor, _vp, _vp, DLAFDescriptor]),
+    "dlaf_mi355x_general_addition_z": (_i, [_i, _ch, _ch, _vp, _vp, DLAFDescriptor, _vp, _vp, DLAFDescriptor]),
+    "dlaf_mi355x_hermitian_complete_s": (_i, [_i, _ch, _ch, _vp, DLAFDescriptor]),
+    "dlaf_mi355x_hermitian_complete_d": (_i, [_i, _ch, _ch, _vp, DLAFDescriptor]),
+    "dlaf_mi355x_hermitian_complete_c": (_i, [_i, _ch, _ch, _vp, DLAFDescriptor]),
+    "dlaf_mi355x_hermitian_complete_z": (_i, [_i, _ch, _ch, _vp, DLAFDescriptor]),
+    "dlaf_mi355x_psgeadd": (None, [_ch, _i, _i, _vp, _vp, _i, _i, _IP, _vp, _vp, _i, _i, _IP]),
+    "dlaf_mi355x_pstradd": (None, [_ch, _ch, _i, _i, _vp, _vp, _i, _i, _IP, _vp, _vp, _i, _i, _IP]),
+    "dlaf_mi355x_pslacpy": (None, [_ch, _i, _i, _vp, _i, _i, _IP, _vp, _i, _i, _IP]),
+    "dlaf_mi355x_pdgeadd": (None, [_ch, _i, _i, _vp, _vp, _i, _i, _IP, _vp, _vp, _i, _i, _IP]),
+    "dlaf_mi355x_pdtradd": (None, [_ch, _ch, _i, _i, _vp, _vp, _i, _i, _IP, _vp, _vp, _i, _i, _IP]),
+    "dlaf_mi355x_pdlacpy": (None, [_ch, _i, _i, _vp, _i, _i, _IP, _vp, _i, _i, _IP]),
+    "dlaf_mi355x_pcgeadd": (None, [_ch, _i, _i, _vp, _vp, _i, _i, _IP, _vp, _vp, _i, _i, _IP]),
+    "dlaf_mi355x_pctradd": (None, [_ch, _ch, _i, _i, _vp, _vp, _i, _i, _IP, _vp, _vp, _i, _i, _IP]),
+    "dlaf_mi355x_pclacpy": (None, [_ch, _i, _i, _vp, _i, _i, _IP, _vp, _i, _i, _IP]),
+    "dlaf_mi355x_pzgeadd": (None, [_ch, _i, _i, _vp, _vp, _i, _i, _IP, _vp, _vp, _i, _i, _IP]),
+    "dlaf_mi355x_pztradd": (None, [_ch, _ch, _i, _i, _vp, _vp, _i, _i, _IP, _vp, _vp, _i, _i, _IP]),
+    "dlaf_mi355x_pzlacpy": (None, [_ch, _i, _i, _vp, _i, _i, _IP, _vp, _i, _i, _IP]),
+    "dlaf_mi355x_pstran": (None, [_i, _i, _vp, _vp, _i, _i, _IP, _vp, _vp, _i, _i, _IP]),
+    "dlaf_mi355x_pdtran": (None, [_i, _i, _vp, _vp, _i, _i, _IP, _vp, _vp, _i, _i, _IP]),
+    "dlaf_mi355x_pctranu": (None, [_i, _i, _vp, _vp, _i, _i, _IP, _vp, _vp, _i, _i, _IP]),
+    "dlaf_mi355x_pctranc": (None, [_i, _i, _vp, _vp, _i, _i, _IP, _vp, _vp, _i, _i, _IP]),
+    "dlaf_mi355x_pztranu": (None, [_i, _i, _vp, _vp, _i, _i, _IP, _vp, _vp, _i, _i, _IP]),
+    "dlaf_mi355x_pztranc": (None, [_i, _i, _vp, _vp, _i, _i, _IP, _vp, _vp, _i, _i, _IP]),
     "dlaf_mi355x_psgemm": (None, [_ch, _ch, _i, _i, _i, _vp, _vp, _i, _i, _IP, _vp, _i, _i, _IP, _vp, _vp, _i, _i, _IP]),
     "dlaf_mi355x_pdgemm": (None, [_ch, _ch, _i, _i, _i, _vp, _vp, _i, _i, _IP, _vp, _i, _i, _IP, _vp, _vp, _i, _i, _IP]),
     "dlaf_mi355x_pcgemm": (None, [_ch, _ch, _i, _i, _i, _vp, _vp, _i, _i, _IP, _vp, _i, _i, _IP, _vp, _vp, _i, _i, _IP]),
@@ -173,6 +199,7 @@ SIGNATURES = {
     "dlaf_mi355x_pzpotrs": (None, [_ch, _i, _i, _vp, _i, _i, _IP, _vp, _i, _i, _IP, _IP]),
     "dlaf_mi355x_solver_profile": (_i, [C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     "dlaf_mi355x_multiplication_profile": (_i, [C.POINTER(C.c_double), C.POINTER(C.c_double)]),
+    "dlaf_mi355x_addition_profile": (_i, [C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     "dlaf_mi355x_gmatrix_create": (_i, [_i, _ch, DLAFDescriptor, C.POINTER(_vp)]),
     "dlaf_mi355x_gmatrix_destroy": (None, [_vp]),
     "dlaf_mi355x_gmatrix_upload": (_i, [_vp, _vp, _i]),
@@ -183,6 +210,10 @@ SIGNATURES = {
     "dlaf_mi355x_general_multiplication_device": (_i, [_ch, _ch, _vp, _vp, _vp, _vp, _vp]),
     "dlaf_mi355x_hermitian_rank_k_update_device": (_i, [_ch, _ch, _vp, _vp, _vp, _vp]),
     "dlaf_mi355x_hermitian_rank_2k_update_device": (_i, [_ch, _ch, _vp, _vp, _vp, _vp, _vp]),
+    "dlaf_mi355x_general_addition_device": (_i, [_ch, _ch, _vp, _vp, _vp, _vp]),
+    "dlaf_mi355x_hermitian_complete_device": (_i, [_ch, _ch, _vp]),
+    "dlaf_mi355x_matrix_to_general": (_i, [_ch, _vp, _vp]),
+    "dlaf_mi355x_matrix_from_general": (_i, [_vp, _vp]),
     "dlaf_mi355x_potrs_device": (_i, [_ch, _vp, _vp]),
     "dlaf_mi355x_generalized_to_standard_s": (_i, [_i, _ch, _vp, DLAFDescriptor, _vp, DLAFDescriptor]),
     "dlaf_mi355x_generalized_to_standard_d": (_i, [_i, _ch, _vp, DLAFDescriptor, _vp, DLAFDescriptor]),

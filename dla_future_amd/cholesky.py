@@ -393,6 +393,99 @@ def pxher2k(uplo: str, trans: str, n: int, k: int, alpha, a: np.ndarray, ia: int
                          _ptr(c), ic, jc, dc)
 
 
+def general_addition(grid: Grid, uplo: str, op: str, alpha, a: np.ndarray, beta, c: np.ndarray, nb: int,
+                     m: int | None = None, n: int | None = None, a_src=(0, 0), c_src=(0, 0)) -> None:
+    """C = beta C + alpha op(A) on the uplo part of the m x n matrix C == dlaf_mi355x_general_addition_{s,d,c,z} (PBLAS
+    p?geadd / p?tradd, p?tran / p?tranu / p?tranc; ScaLAPACK p?lacpy is alpha 1, beta 0, op 'N').  uplo 'A' all, 'L' i >= j,
+    'U' i <= j; op 'N' (A stored m x n), 'T' or 'C' (A stored n x m).  `a`, `c`: this process's local column-major parts;
+    outside the uplo part `c` stays bit for bit; alpha 1, beta 0 with op 'N' / 'T' is a bit copy.  nb: the square block of
+    both.  Any grid (m and n are required on more than one process); op 'N' needs A on C's source process, and only op
+    'N' accepts `a is c`."""
+    t = type_char(c.dtype)
+    if a.dtype != c.dtype:
+        raise ValueError("A and C must have the same element type")
+    if m is None or n is None:
+        if grid.nranks != 1:
+            raise ValueError("the global sizes m, n are required on a distributed grid")
+        m, n = c.shape
+    tn = op.upper() == "N"
+    da = DLAFDescriptor(m if tn else n, n if tn else m, nb, nb, a_src[0], a_src[1], 0, 0, _ld_of(a))
+    dc = DLAFDescriptor(m, n, nb, nb, c_src[0], c_src[1], 0, 0, _ld_of(c))
+    al = np.array([alpha], dtype=c.dtype)
+    be = np.array([beta], dtype=c.dtype)
+    name = f"dlaf_mi355x_general_addition_{t}"
+    r = getattr(lib(), name)(grid.context, uplo.encode(), op.encode(), _ptr(al), _ptr(a), da, _ptr(be), _ptr(c), dc)
+    if r != 0:
+        raise ValueError(f"{name} failed with {r}")
+
+
+def hermitian_complete(grid: Grid, uplo: str, kind: str, a: np.ndarray, nb: int, n: int | None = None, src=(0, 0)) -> None:
+    """Fills the OTHER triangle of the n x n matrix from its uplo one, in place == dlaf_mi355x_hermitian_complete_{s,d,c,z}:
+    kind 'H' conjugates the mirror and makes the diagonal's imaginary parts exactly 0, kind 'S' transposes plainly and
+    leaves the diagonal untouched.  `a`: this process's local column-major part; nb: its square block."""
+    t = type_char(a.dtype)
+    if n is None:
+        if grid.nranks != 1:
+            raise ValueError("the global size n is required on a distributed grid")
+        n = a.shape[0]
+    da = DLAFDescriptor(n, n, nb, nb, src[0], src[1], 0, 0, _ld_of(a))
+    name = f"dlaf_mi355x_hermitian_complete_{t}"
+    r = getattr(lib(), name)(grid.context, uplo.encode(), kind.encode(), _ptr(a), da)
+    if r != 0:
+        raise ValueError(f"{name} failed with {r}")
+
+
+def pxgeadd(trans: str, m: int, n: int, alpha, a: np.ndarray, ia: int, ja: int, desca, beta, c: np.ndarray, ic: int,
+            jc: int, descc) -> None:
+    """dlaf_mi355x_p{s,d,c,z}geadd: PBLAS's argument list (9-int descriptors): C = beta C + alpha op(A)."""
+    t = type_char(c.dtype)
+    da = (C.c_int * 9)(*[int(x) for x in desca])
+    dc = (C.c_int * 9)(*[int(x) for x in descc])
+    al, be = np.array([alpha], dtype=c.dtype), np.array([beta], dtype=c.dtype)
+    getattr(lib(), f"dlaf_mi355x_p{t}geadd")(trans.encode(), m, n, _ptr(al), _ptr(a), ia, ja, da, _ptr(be), _ptr(c), ic, jc,
+                                             dc)
+
+
+def pxtradd(uplo: str, trans: str, m: int, n: int, alpha, a: np.ndarray, ia: int, ja: int, desca, beta, c: np.ndarray,
+            ic: int, jc: int, descc) -> None:
+    """dlaf_mi355x_p{s,d,c,z}tradd: the same on the uplo ('L' / 'U') trapezoid of C."""
+    t = type_char(c.dtype)
+    da = (C.c_int * 9)(*[int(x) for x in desca])
+    dc = (C.c_int * 9)(*[int(x) for x in descc])
+    al, be = np.array([alpha], dtype=c.dtype), np.array([beta], dtype=c.dtype)
+    getattr(lib(), f"dlaf_mi355x_p{t}tradd")(uplo.encode(), trans.encode(), m, n, _ptr(al), _ptr(a), ia, ja, da, _ptr(be),
+                                             _ptr(c), ic, jc, dc)
+
+
+def pxtran(m: int, n: int, alpha, a: np.ndarray, ia: int, ja: int, desca, beta, c: np.ndarray, ic: int, jc: int, descc,
+           conj: bool = False) -> None:
+    """dlaf_mi355x_p{s,d}tran / p{c,z}tranu (conj False) / p{c,z}tranc (conj True): C (m x n) = beta C + alpha A^T / A^H,
+    A stored n x m."""
+    t = type_char(c.dtype)
+    da = (C.c_int * 9)(*[int(x) for x in desca])
+    dc = (C.c_int * 9)(*[int(x) for x in descc])
+    al, be = np.array([alpha], dtype=c.dtype), np.array([beta], dtype=c.dtype)
+    name = f"dlaf_mi355x_p{t}tran" + (("c" if conj else "u") if t in "cz" else "")
+    getattr(lib(), name)(m, n, _ptr(al), _ptr(a), ia, ja, da, _ptr(be), _ptr(c), ic, jc, dc)
+
+
+def pxlacpy(uplo: str, m: int, n: int, a: np.ndarray, ia: int, ja: int, desca, b: np.ndarray, ib: int, jb: int,
+            descb) -> None:
+    """dlaf_mi355x_p{s,d,c,z}lacpy: B = A on the uplo part; as in LAPACK any letter other than 'U' / 'L' means all."""
+    t = type_char(b.dtype)
+    da = (C.c_int * 9)(*[int(x) for x in desca])
+    db = (C.c_int * 9)(*[int(x) for x in descb])
+    getattr(lib(), f"dlaf_mi355x_p{t}lacpy")(uplo.encode(), m, n, _ptr(a), ia, ja, da, _ptr(b), ib, jb, db)
+
+
+def addition_profile():
+    """(ms, bytes) of the last general_addition / hermitian_complete / conversion on this process: device time, and the
+    whole-grid algorithmic bytes (read A + write C, + read C when beta != 0; a completion reads and writes half)."""
+    ms, by = C.c_double(0), C.c_double(0)
+    lib().dlaf_mi355x_addition_profile(C.byref(ms), C.byref(by))
+    return ms.value, by.value
+
+
 def multiplication_profile():
     """(ms, flops) of the sweep of the last multiplication (triangular, Hermitian, general or Hermitian rank update) on this
     process (device time, no staging)."""
@@ -601,6 +694,20 @@ class DeviceMatrix:
         """The resident Cholesky factor <- the uplo triangle of inv(L L^H) / inv(U^H U); returns LAPACK's info."""
         return lib().dlaf_mi355x_inverse_from_cholesky_factor_device(self.uplo.encode(), self._h)
 
+    def to_general(self, g: "GeneralDeviceMatrix", kind: str = "H") -> None:
+        """Writes into the resident general matrix `g` (same grid, type, n x n, block and source process) the Hermitian
+        (kind 'H') / symmetric ('S') matrix whose uplo triangle this matrix holds, or the triangular one ('T': exact
+        zeros in the other triangle), as download() of `g` shows it; nothing crosses PCIe."""
+        r = lib().dlaf_mi355x_matrix_to_general(kind.encode(), self._h, g._h)
+        if r != 0:
+            raise ValueError(f"dlaf_mi355x_matrix_to_general failed with {r}")
+
+    def from_general(self, g: "GeneralDeviceMatrix") -> None:
+        """Takes this matrix's uplo triangle from the resident general matrix `g`; nothing crosses PCIe."""
+        r = lib().dlaf_mi355x_matrix_from_general(self._h, g._h)
+        if r != 0:
+            raise ValueError(f"dlaf_mi355x_matrix_from_general failed with {r}")
+
     def start(self) -> None:
         lib().dlaf_mi355x_cholesky_start(self._h)
 
@@ -744,6 +851,22 @@ def hermitian_rank_2k_update_device(uplo: str, trans: str, alpha, a: GeneralDevi
                                                           c._h)
     if r != 0:
         raise ValueError(f"dlaf_mi355x_hermitian_rank_2k_update_device failed with {r}")
+
+
+def general_addition_device(uplo: str, op: str, alpha, a: GeneralDeviceMatrix, beta, c: GeneralDeviceMatrix) -> None:
+    """general_addition on resident general matrices (`a` as stored; only the uplo part of `c` is written; `a is c` is op
+    'N' in place); no PCIe traffic."""
+    al, be = np.array([alpha], dtype=c.dtype), np.array([beta], dtype=c.dtype)
+    r = lib().dlaf_mi355x_general_addition_device(uplo.encode(), op.encode(), _ptr(al), a._h, _ptr(be), c._h)
+    if r != 0:
+        raise ValueError(f"dlaf_mi355x_general_addition_device failed with {r}")
+
+
+def hermitian_complete_device(uplo: str, kind: str, a: GeneralDeviceMatrix) -> None:
+    """hermitian_complete on a resident general matrix, in place; no PCIe traffic."""
+    r = lib().dlaf_mi355x_hermitian_complete_device(uplo.encode(), kind.encode(), a._h)
+    if r != 0:
+        raise ValueError(f"dlaf_mi355x_hermitian_complete_device failed with {r}")
 
 
 def potrs_device(uplo: str, factor: DeviceMatrix, b: GeneralDeviceMatrix) -> None:

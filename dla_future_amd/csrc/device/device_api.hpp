@@ -5,6 +5,7 @@
 #include <hip/hip_runtime.h>
 
 #include "common.hpp"
+#include "geadd_map.hpp"
 #include "norm_split.hpp"
 
 namespace dlaf_mi355x {
@@ -235,6 +236,32 @@ struct RankKArgs {
 };
 template <class T>
 void launch_rank_k(const RankKArgs<T>& args, hipStream_t stream);
+
+// ------------------------------------------------------------------------------------------
+// Addition / transposition (kernels_geadd.hip; index arithmetic: geadd_map.hpp) of the `mask` part of the local tile
+// rows [g.il0, g.il0 + g.nil) of D, every local tile column, in ONE launch:
+//   D(il, jl) = beta D(il, jl) + alpha op(S(il, jl)),  op = identity (trans 0) or transpose (trans 1), conj on top
+// S(il, jl): the source tile at a + geadd_src_tile_offset(...), ld nb like every tile.  arith (geadd_arith) says which of
+// the two operands are read at all and whether anything is multiplied: kGeaddCopy moves bits.  diag_real: an element on
+// the GLOBAL diagonal is stored with imaginary part 0.  ve: geadd_vector_elems of the two bases.  Elements outside the
+// part, outside the local extents and the padding of ragged tiles are never written; nothing outside a tile's nb x nb
+// storage is read.  a == c is allowed for trans 0, and for trans 1 when the part of D and the part of S that is USED
+// are disjoint up to the diagonal (hermitian_complete): a workgroup reads its source sub-block whole before it writes.
+template <class T>
+struct GeaddArgs {
+  T* c;
+  long c_tsr, c_tsc;
+  const T* a = nullptr;
+  long a_tsi = 0, a_ts = 0, a_ts2 = 0;
+  int a_period = 1;
+  int trans = 0, conj = 0, mask = kGeaddAll, diag_real = 0;
+  int arith = kGeaddCopy;
+  int ve = 1;
+  GeaddGeom g;
+  T alpha, beta;
+};
+template <class T>
+void launch_geadd(const GeaddArgs<T>& args, hipStream_t stream);
 
 // ------------------------------------------------------------------------------------------
 // Diagonal-tile work of triangular_inverse / inverse_from_cholesky_factor (kernels_inverse.hip).  A batch of

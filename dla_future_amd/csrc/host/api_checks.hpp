@@ -154,6 +154,52 @@ void require_rank_update(const char* who, const GridT& g, bool complex_type, cha
     fatal("[dlaf_mi355x] %s: A must start on C's process row (source row %d vs %d)\n", who, a.isrc, c.isrc);
 }
 
+// ---- general addition  C = beta C + alpha op(A) on the uplo part, hermitian_complete and the resident conversions: one
+// judgement for the descriptor entries, the p? entries and the resident ones.  a, c as stored; same_storage: A and C are
+// the same array / handle.  Terminates unless: uplo is A, L or U and op a letter; one square block for both; C is m x n
+// and A m x n (op N) or n x m; every source inside the grid; for op N A starts on C's source process (the launch is
+// local: both must hold the same elements); the same storage twice only with op N.
+inline bool is_part(char c) { return in_set(c, "AaLlUu"); }
+template <class GridT>
+void require_general_addition(const char* who, const GridT& g, char uplo, char op, const GemmOperand& a,
+                              const GemmOperand& c, bool same_storage) {
+  if (!is_part(uplo) || !is_op(op))
+    fatal("[dlaf_mi355x] %s: bad uplo/op '%c' '%c' (uplo is 'A', 'L' or 'U')\n", who, uplo, op);
+  if (a.mb != a.nb || c.mb != c.nb || a.nb != c.nb || c.nb < 1)
+    fatal("[dlaf_mi355x] %s: A and C need one square block (A %d x %d, C %d x %d)\n", who, a.mb, a.nb, c.mb, c.nb);
+  const bool tn = is_notrans(op);
+  if (c.m < 0 || c.n < 0 || (tn ? a.m : a.n) != c.m || (tn ? a.n : a.m) != c.n)
+    fatal("[dlaf_mi355x] %s: A is %ld x %ld (op '%c'), C is %ld x %ld\n", who, a.m, a.n, op, c.m, c.n);
+  for (const GemmOperand* o : {&a, &c})
+    if (!source_in_grid(g.nprow, g.npcol, o->isrc, o->jsrc))
+      fatal("[dlaf_mi355x] %s: source rank (%d,%d) outside the %d x %d grid\n", who, o->isrc, o->jsrc, g.nprow, g.npcol);
+  if (tn && (a.isrc != c.isrc || a.jsrc != c.jsrc))
+    fatal("[dlaf_mi355x] %s: op 'N' needs A on C's source process (source %d,%d vs %d,%d)\n", who, a.isrc, a.jsrc, c.isrc,
+          c.jsrc);
+  if (same_storage && !tn)
+    fatal("[dlaf_mi355x] %s: A and C are the same matrix, which only op 'N' accepts (op '%c')\n", who, op);
+}
+template <class GridT>
+void require_hermitian_complete(const char* who, const GridT& g, char uplo, char kind, const GemmOperand& a) {
+  if (!is_uplo(uplo) || !in_set(kind, "HhSs"))
+    fatal("[dlaf_mi355x] %s: bad uplo/kind '%c' '%c' (kind is 'H' or 'S')\n", who, uplo, kind);
+  if (a.m != a.n || a.n < 0)
+    fatal("[dlaf_mi355x] %s: the matrix must be square (%ld x %ld)\n", who, a.m, a.n);
+  if (a.mb != a.nb || a.nb < 1)
+    fatal("[dlaf_mi355x] %s: the matrix needs a square block (%d x %d)\n", who, a.mb, a.nb);
+  if (!source_in_grid(g.nprow, g.npcol, a.isrc, a.jsrc))
+    fatal("[dlaf_mi355x] %s: source rank (%d,%d) outside the %d x %d grid\n", who, a.isrc, a.jsrc, g.nprow, g.npcol);
+}
+// d: the DeviceMatrix as an n x n operand of the caller's matrix; kinds: the letters the direction takes ("" : none)
+inline void require_matrix_conversion(const char* who, char kind, const char* kinds, const GemmOperand& d,
+                                      const GemmOperand& g) {
+  if (kinds[0] != 0 && !in_set(kind, kinds))
+    fatal("[dlaf_mi355x] %s: bad kind '%c' (one of %s)\n", who, kind, kinds);
+  if (g.m != d.m || g.n != d.n || g.mb != d.mb || g.nb != d.nb || g.isrc != d.isrc || g.jsrc != d.jsrc)
+    fatal("[dlaf_mi355x] %s: the matrix (%ld x %ld, block %d, source %d,%d) and the general matrix (%ld x %ld, block %d x "
+          "%d, source %d,%d) differ\n", who, d.m, d.n, d.nb, d.isrc, d.jsrc, g.m, g.n, g.mb, g.nb, g.isrc, g.jsrc);
+}
+
 // ---- the prologue of a ScaLAPACK argument list: every operand as (name letter, desc, row offset, column offset)
 struct ScalapackOperand {
   char name;

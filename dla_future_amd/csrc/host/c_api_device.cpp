@@ -219,6 +219,72 @@ int dlaf_mi355x_hermitian_rank_2k_update_device(char uplo, char trans, const voi
   return rank_update_device("hermitian rank-2k update", uplo, trans, alpha, a, b, true, beta, c);
 }
 
+// general_addition / hermitian_complete on resident general matrices, and the conversions between a DeviceMatrix and a
+// general matrix (addition.cpp)
+static GemmOperand general_operand(dlaf_mi355x_gmatrix_t h) {
+  GemmOperand o{};
+  (void) dispatch_api_type(h->m->type, [&](auto* tag) {
+    using DT = std::remove_pointer_t<decltype(tag)>;
+    const auto& gm = static_cast<GeneralMatrix<DT>&>(*h->m);
+    o = GemmOperand{gm.rows_g, gm.cols_g, gm.m.nb, gm.m.nb, gm.isrc, gm.jsrc};
+    return 0;
+  });
+  return o;
+}
+// the n x n matrix of the caller whose triangle the handle holds
+static GemmOperand triangle_operand(dlaf_mi355x_matrix_t h) {
+  GemmOperand o{};
+  (void) dispatch_api_type(h->m->type, [&](auto* tag) {
+    using DT = std::remove_pointer_t<decltype(tag)>;
+    const auto& dm = static_cast<DeviceMatrix<DT>&>(*h->m);
+    const Axis& srow = dm.transposed ? dm.cols : dm.rows;
+    const Axis& scol = dm.transposed ? dm.rows : dm.cols;
+    o = GemmOperand{dm.n, dm.n, dm.nb, dm.nb, srow.src, scol.src};
+    return 0;
+  });
+  return o;
+}
+int dlaf_mi355x_general_addition_device(char uplo, char op, const void* alpha, dlaf_mi355x_gmatrix_t a, const void* beta,
+                                        dlaf_mi355x_gmatrix_t c) noexcept {
+  const char* who = "general addition";
+  if (!a || !a->m || !c || !c->m || !alpha || !beta)
+    return -1;
+  if (a->ctx != c->ctx)
+    fatal("[dlaf_mi355x] %s: the operands live on different contexts (A %d, C %d)\n", who, a->ctx, c->ctx);
+  if (a->m->type != c->m->type)
+    fatal("[dlaf_mi355x] %s: operands of different element types (A '%c', C '%c')\n", who, a->m->type, c->m->type);
+  require_general_addition(who, grid_from_context(c->ctx), uplo, op, general_operand(a), general_operand(c),
+                           a->m.get() == c->m.get());
+  return general_addition_device(uplo, op, alpha, a->m.get(), beta, c->m.get());
+}
+int dlaf_mi355x_hermitian_complete_device(char uplo, char kind, dlaf_mi355x_gmatrix_t a) noexcept {
+  if (!a || !a->m)
+    return -1;
+  require_hermitian_complete("hermitian complete", grid_from_context(a->ctx), uplo, kind, general_operand(a));
+  return hermitian_complete_device(uplo, kind, a->m.get());
+}
+static int matrix_conversion(const char* who, char kind, const char* kinds, dlaf_mi355x_matrix_t m, dlaf_mi355x_gmatrix_t g,
+                             bool to_general) {
+  if (!m || !m->m || !g || !g->m)
+    return -1;
+  if (m->ctx != g->ctx)
+    fatal("[dlaf_mi355x] %s: the operands live on different contexts (%d, %d)\n", who, m->ctx, g->ctx);
+  if (m->m->type != g->m->type)
+    fatal("[dlaf_mi355x] %s: operands of different element types ('%c', '%c')\n", who, m->m->type, g->m->type);
+  require_matrix_conversion(who, kind, kinds, triangle_operand(m), general_operand(g));
+  return to_general ? matrix_to_general(kind, m->m.get(), g->m.get()) : matrix_from_general(m->m.get(), g->m.get());
+}
+int dlaf_mi355x_matrix_to_general(char kind, dlaf_mi355x_matrix_t m, dlaf_mi355x_gmatrix_t g) noexcept {
+  return matrix_conversion("general addition: matrix_to_general", kind, "HhSsTt", m, g, true);
+}
+int dlaf_mi355x_matrix_from_general(dlaf_mi355x_matrix_t m, dlaf_mi355x_gmatrix_t g) noexcept {
+  return matrix_conversion("general addition: matrix_from_general", 0, "", m, g, false);
+}
+int dlaf_mi355x_addition_profile(double* ms, double* bytes) noexcept {
+  addition_last_profile(ms, bytes);
+  return 0;
+}
+
 int dlaf_mi355x_multiplication_profile(double* ms, double* flops) noexcept {
   multiplication_last_profile(ms, flops);
   return 0;

@@ -1,6 +1,6 @@
 // c_api_host.cpp -- the extern "C" surface, part 2 of 3 (c_api_internal.hpp has the map): the entries that take
 // descriptors or ScaLAPACK argument lists over host memory -- triangular solver and multiplication, Hermitian and
-// general multiplication, the Hermitian rank updates, p?potrs, generalized to standard, the inverses, the norms, reduction to band and the eigensolver
+// general multiplication, the Hermitian rank updates, the addition / transposition, p?potrs, generalized to standard, the inverses, the norms, reduction to band and the eigensolver
 // stages and drivers (include/dlaf_c/eigensolver/*.h as upstream, include/dlaf_mi355x/dlaf_mi355x.h).  Every argument
 // is judged (api_checks.hpp) before anything touches the GPU.
 #define DLAF_MI355X_NO_MPI 1  // as in c_api.cpp: no <mpi.h> in the core
@@ -228,6 +228,51 @@ void pxrank_update(char uplo, char trans, int n, int k, typename DevType<HT>::ty
   if (descb)
     db = make_dlaf_descriptor(tn ? n : k, tn ? k : n, ib, jb, descb);
   (void) rank_update_c<HT>(ctx, uplo, trans, alpha, a, da, b, descb ? &db : nullptr, beta, c, dc);
+}
+
+// general_addition / hermitian_complete through descriptors (addition.cpp): a, c as stored; every argument judged before
+// the GPU is touched
+template <class HT>
+int general_addition_c(int ctx, char uplo, char op, const HT* alpha, const HT* a, const DLAF_descriptor& da, const HT* beta,
+                       HT* c, const DLAF_descriptor& dc) {
+  using DT = typename DevType<HT>::type;
+  const char* who = "general addition";
+  if (da.i != 0 || da.j != 0 || dc.i != 0 || dc.j != 0)
+    fatal("[dlaf_mi355x] %s: sub-matrices are not supported: offsets must be 0\n", who);
+  Grid& g = grid_from_context(ctx);
+  require_general_addition(who, g, uplo, op, gemm_operand(da), gemm_operand(dc), a == c);
+  DT al, be;
+  std::memcpy(&al, alpha, sizeof(DT));
+  std::memcpy(&be, beta, sizeof(DT));
+  return general_addition_host<DT>(&g, uplo, op, al, reinterpret_cast<const DT*>(a), da.ld, da.isrc, da.jsrc, be,
+                                   reinterpret_cast<DT*>(c), dc.ld, dc.m, dc.n, dc.nb, dc.isrc, dc.jsrc);
+}
+template <class HT>
+int hermitian_complete_c(int ctx, char uplo, char kind, HT* a, const DLAF_descriptor& da) {
+  using DT = typename DevType<HT>::type;
+  const char* who = "hermitian complete";
+  if (da.i != 0 || da.j != 0)
+    fatal("[dlaf_mi355x] %s: sub-matrices are not supported: offsets must be 0\n", who);
+  Grid& g = grid_from_context(ctx);
+  require_hermitian_complete(who, g, uplo, kind, gemm_operand(da));
+  return hermitian_complete_host<DT>(&g, uplo, kind, reinterpret_cast<DT*>(a), da.ld, da.n, da.nb, da.isrc, da.jsrc);
+}
+
+// PBLAS p?geadd / p?tradd / p?tran* and ScaLAPACK p?lacpy argument lists: C (m x n) = beta C + alpha op(A)
+template <class HT>
+void pxgeadd(char uplo, char trans, int m, int n, const HT* alpha, const HT* a, int ia, int ja, const int desca[9],
+             const HT* beta, HT* c, int ic, int jc, const int descc[9]) {
+  const int ctx = require_scalapack_args({{'A', desca, ia, ja}, {'C', descc, ic, jc}}, "general addition");
+  const bool tn = is_notrans(trans);
+  const DLAF_descriptor da = make_dlaf_descriptor(tn ? m : n, tn ? n : m, ia, ja, desca);
+  const DLAF_descriptor dc = make_dlaf_descriptor(m, n, ic, jc, descc);
+  (void) general_addition_c<HT>(ctx, uplo, trans, alpha, a, da, beta, c, dc);
+}
+template <class HT>
+void pxlacpy(char uplo, int m, int n, const HT* a, int ia, int ja, const int desca[9], HT* b, int ib, int jb,
+             const int descb[9]) {
+  const HT one(1), zero(0);
+  pxgeadd<HT>(is_uplo(uplo) ? uplo : 'A', 'N', m, n, &one, a, ia, ja, desca, &zero, b, ib, jb, descb);
 }
 
 // ScaLAPACK p?potrs: solve A X = B with the factor p?potrf left in a (uplo L: L L^H, uplo U: U^H U)
@@ -626,6 +671,51 @@ DLAF_MI355X_RANK_UPDATE_ENTRY(d, double, double, double, syrk, syr2k)
 DLAF_MI355X_RANK_UPDATE_ENTRY(c, std::complex<float>, dlaf_complex_c, float, herk, her2k)
 DLAF_MI355X_RANK_UPDATE_ENTRY(z, std::complex<double>, dlaf_complex_z, double, herk, her2k)
 #undef DLAF_MI355X_RANK_UPDATE_ENTRY
+#define DLAF_MI355X_GEADD_ENTRY(S, HT, CT)                                                                            \
+  int dlaf_mi355x_general_addition_##S(int ctx, char uplo, char op, const CT* alpha, const CT* a, DLAF_descriptor desca, \
+                                       const CT* beta, CT* c, DLAF_descriptor descc) noexcept {                      \
+    return general_addition_c<HT>(ctx, uplo, op, reinterpret_cast<const HT*>(alpha), reinterpret_cast<const HT*>(a),  \
+                                  desca, reinterpret_cast<const HT*>(beta), reinterpret_cast<HT*>(c), descc);         \
+  }                                                                                                                 \
+  int dlaf_mi355x_hermitian_complete_##S(int ctx, char uplo, char kind, CT* a, DLAF_descriptor desca) noexcept {       \
+    return hermitian_complete_c<HT>(ctx, uplo, kind, reinterpret_cast<HT*>(a), desca);                               \
+  }                                                                                                                 \
+  void dlaf_mi355x_p##S##geadd(char trans, int m, int n, const CT* alpha, const CT* a, int ia, int ja,                 \
+                               const int desca[9], const CT* beta, CT* c, int ic, int jc,                            \
+                               const int descc[9]) noexcept {                                                        \
+    pxgeadd<HT>('A', trans, m, n, reinterpret_cast<const HT*>(alpha), reinterpret_cast<const HT*>(a), ia, ja, desca,  \
+                reinterpret_cast<const HT*>(beta), reinterpret_cast<HT*>(c), ic, jc, descc);                          \
+  }                                                                                                                 \
+  void dlaf_mi355x_p##S##tradd(char uplo, char trans, int m, int n, const CT* alpha, const CT* a, int ia, int ja,      \
+                               const int desca[9], const CT* beta, CT* c, int ic, int jc,                            \
+                               const int descc[9]) noexcept {                                                        \
+    if (!is_uplo(uplo))                                                                                             \
+      fatal("[dlaf_mi355x] general addition: p?tradd: uplo must be 'L' or 'U', got '%c'\n", uplo);                   \
+    pxgeadd<HT>(uplo, trans, m, n, reinterpret_cast<const HT*>(alpha), reinterpret_cast<const HT*>(a), ia, ja, desca, \
+                reinterpret_cast<const HT*>(beta), reinterpret_cast<HT*>(c), ic, jc, descc);                          \
+  }                                                                                                                 \
+  void dlaf_mi355x_p##S##lacpy(char uplo, int m, int n, const CT* a, int ia, int ja, const int desca[9], CT* b,        \
+                               int ib, int jb, const int descb[9]) noexcept {                                        \
+    pxlacpy<HT>(uplo, m, n, reinterpret_cast<const HT*>(a), ia, ja, desca, reinterpret_cast<HT*>(b), ib, jb, descb);  \
+  }
+DLAF_MI355X_GEADD_ENTRY(s, float, float)
+DLAF_MI355X_GEADD_ENTRY(d, double, double)
+DLAF_MI355X_GEADD_ENTRY(c, std::complex<float>, dlaf_complex_c)
+DLAF_MI355X_GEADD_ENTRY(z, std::complex<double>, dlaf_complex_z)
+#undef DLAF_MI355X_GEADD_ENTRY
+#define DLAF_MI355X_TRAN_ENTRY(S, NAME, OP, HT, CT)                                                                   \
+  void dlaf_mi355x_p##S##NAME(int m, int n, const CT* alpha, const CT* a, int ia, int ja, const int desca[9],          \
+                              const CT* beta, CT* c, int ic, int jc, const int descc[9]) noexcept {                  \
+    pxgeadd<HT>('A', OP, m, n, reinterpret_cast<const HT*>(alpha), reinterpret_cast<const HT*>(a), ia, ja, desca,     \
+                reinterpret_cast<const HT*>(beta), reinterpret_cast<HT*>(c), ic, jc, descc);                          \
+  }
+DLAF_MI355X_TRAN_ENTRY(s, tran, 'T', float, float)
+DLAF_MI355X_TRAN_ENTRY(d, tran, 'T', double, double)
+DLAF_MI355X_TRAN_ENTRY(c, tranu, 'T', std::complex<float>, dlaf_complex_c)
+DLAF_MI355X_TRAN_ENTRY(c, tranc, 'C', std::complex<float>, dlaf_complex_c)
+DLAF_MI355X_TRAN_ENTRY(z, tranu, 'T', std::complex<double>, dlaf_complex_z)
+DLAF_MI355X_TRAN_ENTRY(z, tranc, 'C', std::complex<double>, dlaf_complex_z)
+#undef DLAF_MI355X_TRAN_ENTRY
 #define DLAF_MI355X_POTRS_ENTRY(S, HT, CT)                                                                       \
   void dlaf_mi355x_p##S##potrs(char uplo, int n, int nrhs, const CT* a, int ia, int ja, const int desca[9], CT* b,  \
                                int ib, int jb, const int descb[9], int* info) noexcept {                        \

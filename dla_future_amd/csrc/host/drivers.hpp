@@ -1,5 +1,5 @@
 // drivers.hpp -- what the algorithms on top of the tile kernels export: the triangular solver (solver.cpp), the
-// triangular, Hermitian and general multiplications (multiplication.cpp), the rank updates (rank_update.cpp),
+// triangular, Hermitian and general multiplications (multiplication.cpp), the rank updates (rank_update.cpp), the addition / transposition (addition.cpp),
 // generalized-to-standard (gen_to_std.cpp), the inverses (inverse.cpp) and the norms (norm.cpp), host and
 // device-resident forms.  reduction_to_band and the eigensolver stages have headers of their own (red2band.hpp,
 // eigensolver.hpp).
@@ -72,6 +72,32 @@ int hermitian_rank_update_host(Grid* g, bool her2k, char uplo, char trans, T alp
                                int c_isrc, int c_jsrc);
 int hermitian_rank_update_device(char trans, const void* alpha, MatrixBase* a, MatrixBase* b, const void* beta,
                                  MatrixBase* c);
+
+// C = beta C + alpha op(A) on the uplo part (A all, L i >= j, U i <= j) of the m x n matrix C (addition.cpp; PBLAS p?geadd /
+// p?tradd, p?tran / p?tranu / p?tranc, ScaLAPACK p?lacpy): op N, T, C; A as stored, m x n for N and n x m for T / C, one
+// square block nb.  Outside the part C stays bit for bit, the padding rows of ldc too; A is only read; beta == 0: C is
+// not read; alpha == 0: A is not referenced, and with beta == 1 nothing is touched; alpha == 1, beta == 0, op N / T: a bit
+// copy.  The arguments must have passed require_general_addition (api_checks.hpp).  Host and resident forms (resident:
+// two general matrices; the same handle twice is op N in place).
+template <class T>
+int general_addition_host(Grid* g, char uplo, char op, T alpha, const T* a, long lda, int a_isrc, int a_jsrc, T beta, T* c,
+                          long ldc, long m, long n, int nb, int c_isrc, int c_jsrc);
+int general_addition_device(char uplo, char op, const void* alpha, MatrixBase* a, const void* beta, MatrixBase* c);
+// The other triangle of the n x n general matrix A from its uplo one, in place: kind H the conjugated mirror and the
+// diagonal's imaginary parts exactly 0, kind S the plain transpose and the diagonal untouched.  The arguments must have
+// passed require_hermitian_complete.  Host and resident (a general matrix) forms.
+template <class T>
+int hermitian_complete_host(Grid* g, char uplo, char kind, T* a, long lda, long n, int nb, int isrc, int jsrc);
+int hermitian_complete_device(char uplo, char kind, MatrixBase* general_matrix);
+// Resident conversions, defined by what download() of either object shows: to_general writes into the general matrix g
+// the Hermitian (kind H) / symmetric (S) matrix whose stored triangle m holds, or the triangular one (T: exact zeros in
+// the other triangle); from_general takes m's stored triangle from g.  Same grid, order, block and source process (the
+// entry checks).
+int matrix_to_general(char kind, MatrixBase* m, MatrixBase* g);
+int matrix_from_general(MatrixBase* m, MatrixBase* g);
+// device time and whole-grid algorithmic bytes (read A + write C, + read C when beta != 0; a completion reads and writes
+// half the matrix) of the last of them on this process
+void addition_last_profile(double* ms, double* bytes);
 
 // A <- L^-1 A L^-H (uplo L) / U^-H A U^-1 (uplo U) with the Cholesky factor held in the same uplo triangle of
 // `l` (gen_to_std.cpp; dlaf::eigensolver::internal::generalized_to_standard); device-resident and host forms

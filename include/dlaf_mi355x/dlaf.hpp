@@ -595,6 +595,62 @@ void hermitian_rank_2k_update(blas::Uplo uplo, blas::Op op, const T alpha, const
   hermitian_rank_2k_update<B, D, T>(grid, uplo, op, alpha, mat_a, mat_b, beta, mat_c);
 }
 
+// C = beta C + alpha op(A) on the uplo part of mat_c (PBLAS p?geadd / p?tradd, p?tran / p?tranu / p?tranc; ScaLAPACK
+// p?lacpy is alpha 1, beta 0, NoTrans) and the completion of a Hermitian / symmetric matrix from one triangle, on
+// host-resident operands.  The reference has no such algorithm (its matrix::copy is the alpha 1, beta 0, NoTrans case);
+// the names follow hermitian_rank_k_update.  uplo: blas::Uplo::General (all), Lower (i >= j), Upper (i <= j).  Outside
+// the part mat_c keeps its bits; alpha 1, beta 0 with NoTrans / Trans is a bit copy.  Any grid, every op; one square
+// block for both; NoTrans needs mat_a on mat_c's source process.  hermitian_complete fills the OTHER triangle of the
+// square mat_a from its uplo one: conjugate = true the Hermitian completion (diagonal imaginary parts exactly 0),
+// false the symmetric one (diagonal untouched).
+template <Backend B, Device D, class T>
+void general_addition(comm::CommunicatorGrid& grid, blas::Uplo uplo, blas::Op op, const T alpha,
+                      const Matrix<T, Device::CPU>& mat_a, const T beta, Matrix<T, Device::CPU>& mat_c) {
+  static_assert(B == Backend::GPU, "this library has no CPU backend");
+  const DLAF_descriptor da = internal::rank_update_descriptor(mat_a), dc = internal::rank_update_descriptor(mat_c);
+  const char u = uplo == blas::Uplo::Lower ? 'L' : uplo == blas::Uplo::Upper ? 'U' : 'A';
+  int r;
+  if constexpr (std::is_same_v<T, float>)
+    r = dlaf_mi355x_general_addition_s(grid.context(), u, (char) op, &alpha, mat_a.ptr(), da, &beta, mat_c.ptr(), dc);
+  else if constexpr (std::is_same_v<T, double>)
+    r = dlaf_mi355x_general_addition_d(grid.context(), u, (char) op, &alpha, mat_a.ptr(), da, &beta, mat_c.ptr(), dc);
+  else if constexpr (std::is_same_v<T, std::complex<float>>)
+    r = dlaf_mi355x_general_addition_c(grid.context(), u, (char) op, &alpha, mat_a.ptr(), da, &beta, mat_c.ptr(), dc);
+  else
+    r = dlaf_mi355x_general_addition_z(grid.context(), u, (char) op, &alpha, mat_a.ptr(), da, &beta, mat_c.ptr(), dc);
+  if (r != 0)
+    internal::fail("general_addition");
+}
+template <Backend B, Device D, class T>
+void hermitian_complete(comm::CommunicatorGrid& grid, blas::Uplo uplo, bool conjugate, Matrix<T, Device::CPU>& mat_a) {
+  static_assert(B == Backend::GPU, "this library has no CPU backend");
+  const DLAF_descriptor da = internal::rank_update_descriptor(mat_a);
+  const char kind = conjugate ? 'H' : 'S';
+  int r;
+  if constexpr (std::is_same_v<T, float>)
+    r = dlaf_mi355x_hermitian_complete_s(grid.context(), (char) uplo, kind, mat_a.ptr(), da);
+  else if constexpr (std::is_same_v<T, double>)
+    r = dlaf_mi355x_hermitian_complete_d(grid.context(), (char) uplo, kind, mat_a.ptr(), da);
+  else if constexpr (std::is_same_v<T, std::complex<float>>)
+    r = dlaf_mi355x_hermitian_complete_c(grid.context(), (char) uplo, kind, mat_a.ptr(), da);
+  else
+    r = dlaf_mi355x_hermitian_complete_z(grid.context(), (char) uplo, kind, mat_a.ptr(), da);
+  if (r != 0)
+    internal::fail("hermitian_complete");
+}
+// the local overloads
+template <Backend B, Device D, class T>
+void general_addition(blas::Uplo uplo, blas::Op op, const T alpha, const Matrix<T, Device::CPU>& mat_a, const T beta,
+                      Matrix<T, Device::CPU>& mat_c) {
+  comm::CommunicatorGrid grid = comm::CommunicatorGrid::single();
+  general_addition<B, D, T>(grid, uplo, op, alpha, mat_a, beta, mat_c);
+}
+template <Backend B, Device D, class T>
+void hermitian_complete(blas::Uplo uplo, bool conjugate, Matrix<T, Device::CPU>& mat_a) {
+  comm::CommunicatorGrid grid = comm::CommunicatorGrid::single();
+  hermitian_complete<B, D, T>(grid, uplo, conjugate, mat_a);
+}
+
 // include/dlaf/eigensolver/gen_to_std.h:50, :101: A <- inv(L) A inv(L^H) (Lower) / inv(U^H) A inv(U) (Upper) with
 // the Cholesky factor of B in mat_b (host-resident operands; only the uplo triangles are referenced)
 namespace eigensolver::internal {

@@ -373,6 +373,98 @@ DLAF_EXTERN_C void dlaf_mi355x_pzher2k(char uplo, char trans, int n, int k, cons
                                        const int descb[9], const double* beta, dlaf_complex_z* c, int ic, int jc,
                                        const int descc[9]) DLAF_NOEXCEPT;
 
+/* general_addition: C = beta C + alpha op(A) on the uplo part of the m x n matrix C -- PBLAS p?geadd (uplo 'A') and
+ * p?tradd, the transpositions p?tran / p?tranu / p?tranc (op 'T' / 'C'), ScaLAPACK p?lacpy (alpha 1, beta 0, op 'N').
+ *   uplo 'A': every element, 'L': i >= j, 'U': i <= j (for m != n the trapezoids of xLACPY)
+ *   op 'N': A stored m x n;  'T' / 'C': A stored n x m (real types: 'C' equals 'T')
+ * hermitian_complete: the OTHER triangle of the n x n matrix A from its uplo one, in place; kind 'H': the mirror is
+ * conjugated and the imaginary part of the diagonal becomes exactly 0 (the convention of hermitian_rank_k_update), kind
+ * 'S': plain transpose, the diagonal untouched bit for bit.
+ * Semantics:
+ *   - outside the uplo part C stays bit for bit, and so do the padding rows of its leading dimension; A is only read;
+ *   - beta = 0: C is not read (NaNs in its part do not survive);
+ *   - alpha = 0: A is not referenced (NaNs in it reach nothing), and the part becomes beta C;
+ *   - if, in addition, beta = 1: quick return, nothing is touched;
+ *   - alpha = 1, beta = 0, op 'N' or 'T': the result is a BIT COPY of the source elements (signed zeros, denormals and
+ *     NaN payloads are moved, never multiplied): p?lacpy and a plain transpose are exact;
+ *   - m = 0 or n = 0 returns before the GPU is touched.
+ * Any grid, every op.  Requirements of this build: one square block for A and C; no sub-matrix offsets; op 'N' needs A
+ * on C's source process; A and C being the same array is accepted for op 'N' only; hermitian_complete needs a square
+ * matrix.  Returns 0; a violated requirement terminates with a message "general addition: ..." / "hermitian complete:
+ * ..." before the GPU is touched. */
+DLAF_EXTERN_C int dlaf_mi355x_general_addition_s(int context, char uplo, char op, const float* alpha, const float* a,
+                                                  struct DLAF_descriptor desca, const float* beta, float* c,
+                                                  struct DLAF_descriptor descc) DLAF_NOEXCEPT;
+DLAF_EXTERN_C int dlaf_mi355x_general_addition_d(int context, char uplo, char op, const double* alpha, const double* a,
+                                                  struct DLAF_descriptor desca, const double* beta, double* c,
+                                                  struct DLAF_descriptor descc) DLAF_NOEXCEPT;
+DLAF_EXTERN_C int dlaf_mi355x_general_addition_c(int context, char uplo, char op, const dlaf_complex_c* alpha, const dlaf_complex_c* a,
+                                                  struct DLAF_descriptor desca, const dlaf_complex_c* beta, dlaf_complex_c* c,
+                                                  struct DLAF_descriptor descc) DLAF_NOEXCEPT;
+DLAF_EXTERN_C int dlaf_mi355x_general_addition_z(int context, char uplo, char op, const dlaf_complex_z* alpha, const dlaf_complex_z* a,
+                                                  struct DLAF_descriptor desca, const dlaf_complex_z* beta, dlaf_complex_z* c,
+                                                  struct DLAF_descriptor descc) DLAF_NOEXCEPT;
+DLAF_EXTERN_C int dlaf_mi355x_hermitian_complete_s(int context, char uplo, char kind, float* a,
+                                                    struct DLAF_descriptor desca) DLAF_NOEXCEPT;
+DLAF_EXTERN_C int dlaf_mi355x_hermitian_complete_d(int context, char uplo, char kind, double* a,
+                                                    struct DLAF_descriptor desca) DLAF_NOEXCEPT;
+DLAF_EXTERN_C int dlaf_mi355x_hermitian_complete_c(int context, char uplo, char kind, dlaf_complex_c* a,
+                                                    struct DLAF_descriptor desca) DLAF_NOEXCEPT;
+DLAF_EXTERN_C int dlaf_mi355x_hermitian_complete_z(int context, char uplo, char kind, dlaf_complex_z* a,
+                                                    struct DLAF_descriptor desca) DLAF_NOEXCEPT;
+/* the ScaLAPACK / PBLAS argument lists (ia = ja = ic = jc = 1); p?lacpy: as in LAPACK, any uplo letter other than 'U' /
+ * 'L' means all; p?tran* : C (m x n) = beta C + alpha A^T (tran, tranu) / alpha A^H (tranc), A n x m */
+DLAF_EXTERN_C void dlaf_mi355x_psgeadd(char trans, int m, int n, const float* alpha, const float* a, int ia, int ja,
+                                       const int desca[9], const float* beta, float* c, int ic, int jc,
+                                       const int descc[9]) DLAF_NOEXCEPT;
+DLAF_EXTERN_C void dlaf_mi355x_pstradd(char uplo, char trans, int m, int n, const float* alpha, const float* a, int ia,
+                                       int ja, const int desca[9], const float* beta, float* c, int ic, int jc,
+                                       const int descc[9]) DLAF_NOEXCEPT;
+DLAF_EXTERN_C void dlaf_mi355x_pslacpy(char uplo, int m, int n, const float* a, int ia, int ja, const int desca[9],
+                                       float* b, int ib, int jb, const int descb[9]) DLAF_NOEXCEPT;
+DLAF_EXTERN_C void dlaf_mi355x_pdgeadd(char trans, int m, int n, const double* alpha, const double* a, int ia, int ja,
+                                       const int desca[9], const double* beta, double* c, int ic, int jc,
+                                       const int descc[9]) DLAF_NOEXCEPT;
+DLAF_EXTERN_C void dlaf_mi355x_pdtradd(char uplo, char trans, int m, int n, const double* alpha, const double* a, int ia,
+                                       int ja, const int desca[9], const double* beta, double* c, int ic, int jc,
+                                       const int descc[9]) DLAF_NOEXCEPT;
+DLAF_EXTERN_C void dlaf_mi355x_pdlacpy(char uplo, int m, int n, const double* a, int ia, int ja, const int desca[9],
+                                       double* b, int ib, int jb, const int descb[9]) DLAF_NOEXCEPT;
+DLAF_EXTERN_C void dlaf_mi355x_pcgeadd(char trans, int m, int n, const dlaf_complex_c* alpha, const dlaf_complex_c* a, int ia, int ja,
+                                       const int desca[9], const dlaf_complex_c* beta, dlaf_complex_c* c, int ic, int jc,
+                                       const int descc[9]) DLAF_NOEXCEPT;
+DLAF_EXTERN_C void dlaf_mi355x_pctradd(char uplo, char trans, int m, int n, const dlaf_complex_c* alpha, const dlaf_complex_c* a, int ia,
+                                       int ja, const int desca[9], const dlaf_complex_c* beta, dlaf_complex_c* c, int ic, int jc,
+                                       const int descc[9]) DLAF_NOEXCEPT;
+DLAF_EXTERN_C void dlaf_mi355x_pclacpy(char uplo, int m, int n, const dlaf_complex_c* a, int ia, int ja, const int desca[9],
+                                       dlaf_complex_c* b, int ib, int jb, const int descb[9]) DLAF_NOEXCEPT;
+DLAF_EXTERN_C void dlaf_mi355x_pzgeadd(char trans, int m, int n, const dlaf_complex_z* alpha, const dlaf_complex_z* a, int ia, int ja,
+                                       const int desca[9], const dlaf_complex_z* beta, dlaf_complex_z* c, int ic, int jc,
+                                       const int descc[9]) DLAF_NOEXCEPT;
+DLAF_EXTERN_C void dlaf_mi355x_pztradd(char uplo, char trans, int m, int n, const dlaf_complex_z* alpha, const dlaf_complex_z* a, int ia,
+                                       int ja, const int desca[9], const dlaf_complex_z* beta, dlaf_complex_z* c, int ic, int jc,
+                                       const int descc[9]) DLAF_NOEXCEPT;
+DLAF_EXTERN_C void dlaf_mi355x_pzlacpy(char uplo, int m, int n, const dlaf_complex_z* a, int ia, int ja, const int desca[9],
+                                       dlaf_complex_z* b, int ib, int jb, const int descb[9]) DLAF_NOEXCEPT;
+DLAF_EXTERN_C void dlaf_mi355x_pstran(int m, int n, const float* alpha, const float* a, int ia, int ja,
+                                      const int desca[9], const float* beta, float* c, int ic, int jc,
+                                      const int descc[9]) DLAF_NOEXCEPT;
+DLAF_EXTERN_C void dlaf_mi355x_pdtran(int m, int n, const double* alpha, const double* a, int ia, int ja,
+                                      const int desca[9], const double* beta, double* c, int ic, int jc,
+                                      const int descc[9]) DLAF_NOEXCEPT;
+DLAF_EXTERN_C void dlaf_mi355x_pctranu(int m, int n, const dlaf_complex_c* alpha, const dlaf_complex_c* a, int ia, int ja,
+                                      const int desca[9], const dlaf_complex_c* beta, dlaf_complex_c* c, int ic, int jc,
+                                      const int descc[9]) DLAF_NOEXCEPT;
+DLAF_EXTERN_C void dlaf_mi355x_pctranc(int m, int n, const dlaf_complex_c* alpha, const dlaf_complex_c* a, int ia, int ja,
+                                      const int desca[9], const dlaf_complex_c* beta, dlaf_complex_c* c, int ic, int jc,
+                                      const int descc[9]) DLAF_NOEXCEPT;
+DLAF_EXTERN_C void dlaf_mi355x_pztranu(int m, int n, const dlaf_complex_z* alpha, const dlaf_complex_z* a, int ia, int ja,
+                                      const int desca[9], const dlaf_complex_z* beta, dlaf_complex_z* c, int ic, int jc,
+                                      const int descc[9]) DLAF_NOEXCEPT;
+DLAF_EXTERN_C void dlaf_mi355x_pztranc(int m, int n, const dlaf_complex_z* alpha, const dlaf_complex_z* a, int ia, int ja,
+                                      const int desca[9], const dlaf_complex_z* beta, dlaf_complex_z* c, int ic, int jc,
+                                      const int descc[9]) DLAF_NOEXCEPT;
+
 /* ScaLAPACK p?potrs: A X = B with the factor dlaf_p?potrf left in a (two triangular solves; b is overwritten) */
 DLAF_EXTERN_C void dlaf_mi355x_pspotrs(char uplo, int n, int nrhs, const float* a, int ia, int ja, const int desca[9],
                                        float* b, int ib, int jb, const int descb[9], int* info) DLAF_NOEXCEPT;
@@ -826,6 +918,21 @@ DLAF_EXTERN_C int dlaf_mi355x_hermitian_rank_k_update_device(char uplo, char tra
 DLAF_EXTERN_C int dlaf_mi355x_hermitian_rank_2k_update_device(char uplo, char trans, const void* alpha,
                                                               dlaf_mi355x_gmatrix_t a, dlaf_mi355x_gmatrix_t b,
                                                               const void* beta, dlaf_mi355x_matrix_t c) DLAF_NOEXCEPT;
+/* general_addition / hermitian_complete on resident general matrices of one context and element type (a as stored; only
+ * c's uplo part is written; the same handle twice is op 'N' in place), and the resident conversions between a
+ * dlaf_mi355x_matrix_t (one triangle) and a general matrix of the same context, type, order, block and source process,
+ * defined by what the download of either object shows: matrix_to_general writes into g the Hermitian (kind 'H') /
+ * symmetric ('S') matrix whose stored triangle m holds, or the triangular one ('T': exact zeros in the other triangle);
+ * matrix_from_general takes m's stored triangle from g.  Nothing crosses PCIe.  Semantics and requirements of the host
+ * entries; a handle or scalar that is null returns -1. */
+DLAF_EXTERN_C int dlaf_mi355x_general_addition_device(char uplo, char op, const void* alpha, dlaf_mi355x_gmatrix_t a,
+                                                      const void* beta, dlaf_mi355x_gmatrix_t c) DLAF_NOEXCEPT;
+DLAF_EXTERN_C int dlaf_mi355x_hermitian_complete_device(char uplo, char kind, dlaf_mi355x_gmatrix_t a) DLAF_NOEXCEPT;
+DLAF_EXTERN_C int dlaf_mi355x_matrix_to_general(char kind, dlaf_mi355x_matrix_t m, dlaf_mi355x_gmatrix_t g) DLAF_NOEXCEPT;
+DLAF_EXTERN_C int dlaf_mi355x_matrix_from_general(dlaf_mi355x_matrix_t m, dlaf_mi355x_gmatrix_t g) DLAF_NOEXCEPT;
+/* Device time (ms, HIP events) of the last of them on this process and the whole-grid algorithmic bytes it stands for:
+ * read A + write C, + read C when beta != 0, over the uplo part; a completion reads and writes half the matrix. */
+DLAF_EXTERN_C int dlaf_mi355x_addition_profile(double* ms, double* bytes) DLAF_NOEXCEPT;
 /* Device time (ms, HIP events on the compute stream) of the sweep of the last triangular multiplication on this
  * process -- relayout and PCIe staging excluded -- and the whole-grid algorithmic flops it stands for (m n^2 for
  * side R, m^2 n for side L; x4 complex), as dlaf_mi355x_solver_profile.  The last multiplication of EITHER kind is

@@ -115,62 +115,36 @@ void launch(GeaddArgs<T>& a, hipStream_t s) {
 template <class T>
 void transposed_walk(Sweep& sw, TileMatrix<T>& C, TileMatrix<T>& A, GeaddArgs<T> proto, bool descending) {
   Transport* tr = grid_transport(*C.grid);
-  const hipStream_t s_main = sw.s_main, s_comm = sw.s_comm;
   const size_t te = C.tile_elems;
   const long nkt = A.cols.nt();
   const Axis& have = A.rows;
   const Axis& want = C.cols;
-  const bool hop = have.P > 1;  // the transposed panel travels; else every tile of the column panel is here
-  Events ev_in((size_t) nkt), ev_done((size_t) nkt);
-  Ring<T> arow((size_t) A.ltr * te, A.cols.P > 1), acol((size_t) (want.local_tiles() + have.P) * te, hop);
-  struct Panel {
-    const T* base = nullptr;
-    long ts = 0, ts2 = 0;
-    int period = 1;
-  };
-  std::vector<Panel> panel((size_t) nkt);
+  StepPipeline pipe(nkt);
+  // the transposed panel travels when A's rows are spread; else every tile of the column panel is here
+  Ring<T> arow((size_t) A.ltr * te, A.cols.P > 1), acol((size_t) (want.local_tiles() + have.P) * te, have.P > 1);
+  std::vector<Panel<T>> panel((size_t) nkt);
   auto column_of = [&](long s) { return descending ? nkt - 1 - s : s; };
-  auto fetch = [&](long s) {
-    const int buf = (int) (s % kBuf);
-    if (s >= kBuf)
-      DLAF_HIP_CHECK(hipStreamWaitEvent(s_comm, ev_done[(size_t) (s - kBuf)], 0));
-    Panel& p = panel[(size_t) s];
-    const T* col = bcast_view_column(tr, A, column_of(s), arow[buf], s_comm);
-    if (hop) {
-      (void) bcast_transposed_panel_whole(tr, CommAxis::Col, have, want, col, acol[buf], te, s_comm, p.period, p.ts2);
-      p.base = acol[buf];
-      p.ts = (long) te;
-    }
-    else {
-      // I hold every tile row of the panel: the tile of global row gj sits at local row gj
-      p.base = col + (size_t) want.shift() * te;
-      p.ts = (long) te * want.P;
-    }
-    DLAF_HIP_CHECK(hipEventRecord(ev_in[(size_t) s], s_comm));
+  auto fetch = [&](long s, int buf) {
+    panel[(size_t) s] =
+        bcast_column_and_transposed_panel(tr, A, column_of(s), have, want, arow[buf], acol[buf], sw.s_comm).col;
   };
   proto.trans = 1;
   proto.a_tsi = 0;
   proto.g.nil = 1;
-  sw.begin(true);
-  if (nkt > 0)
-    fetch(0);
-  for (long s = 0; s < nkt; ++s) {
-    if (s + 1 < nkt)
-      fetch(s + 1);
-    DLAF_HIP_CHECK(hipStreamWaitEvent(s_main, ev_in[(size_t) s], 0));
+  auto apply = [&](long s) {
     const long k = column_of(s);
     if (C.rows.mine(k) && C.ltc > 0) {
-      const Panel& p = panel[(size_t) s];
+      const Panel<T>& p = panel[(size_t) s];
       GeaddArgs<T> a = proto;
       a.g.il0 = (int) C.rows.local_of(k);
       a.a = p.base;
       a.a_ts = p.ts;
       a.a_ts2 = p.ts2;
       a.a_period = p.period;
-      launch(a, s_main);
+      launch(a, sw.s_main);
     }
-    DLAF_HIP_CHECK(hipEventRecord(ev_done[(size_t) s], s_main));
-  }
+  };
+  pipe.run(sw, fetch, apply);
 }
 
 void set_profile(double ms, int mask, long m, long n, size_t elem, int arith, bool in_place_half) {
@@ -240,30 +214,23 @@ int general_addition_host(Grid* g, char uplo, char op, T alpha, const T* a, long
   const bool use_a = !is_zero(alpha);
   if (!use_a && is_one(beta))
     return 0;  // quick return: nothing is touched
-  runtime_init();
-  (void) grid_transport(*g);
-  if (g->nranks > 1 && !g->transport)
-    fatal("[dlaf_mi355x] grid with %d ranks has no transport\n", g->nranks);
+  (void) checked_transport(*g);
   const int mask = mask_of_uplo(uplo);
   const bool tn = op_is_n(op);
-  hipStream_t s = nullptr;
-  DLAF_HIP_CHECK(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
-  {
-    TileMatrix<T> Ad, Cd;
-    Cd.create(g, false, m, n, nb, c_isrc, c_jsrc);
-    if (use_a) {
-      Ad.create(g, false, tn ? m : n, tn ? n : m, nb, a_isrc, a_jsrc);
-      Ad.upload(a, lda, false, false, T{}, s);
-    }
-    // beta = 0: the part of C is not read; what lies outside the part travels there and back unchanged
-    if (!is_zero(beta) || mask != kGeaddAll)
-      Cd.upload(c, ldc, false, false, T{}, s);
-    DLAF_HIP_CHECK(hipStreamSynchronize(s));
-    addition_canonical<T>(Cd, use_a ? &Ad : nullptr, op, mask, alpha, beta);
-    Cd.download(c, ldc, false, s);
-    DLAF_HIP_CHECK(hipStreamSynchronize(s));
+  ScratchStream s;  // before the matrices: destroyed after them
+  TileMatrix<T> Ad, Cd;
+  Cd.create(g, false, m, n, nb, c_isrc, c_jsrc);
+  if (use_a) {
+    Ad.create(g, false, tn ? m : n, tn ? n : m, nb, a_isrc, a_jsrc);
+    Ad.upload(a, lda, false, false, T{}, s);
   }
-  DLAF_HIP_CHECK(hipStreamDestroy(s));
+  // beta = 0: the part of C is not read; what lies outside the part travels there and back unchanged
+  if (!is_zero(beta) || mask != kGeaddAll)
+    Cd.upload(c, ldc, false, false, T{}, s);
+  s.sync();
+  addition_canonical<T>(Cd, use_a ? &Ad : nullptr, op, mask, alpha, beta);
+  Cd.download(c, ldc, false, s);
+  s.sync();
   return 0;
 }
 
@@ -292,22 +259,15 @@ template <class T>
 int hermitian_complete_host(Grid* g, char uplo, char kind, T* a, long lda, long n, int nb, int isrc, int jsrc) {
   if (n == 0)
     return 0;
-  runtime_init();
-  (void) grid_transport(*g);
-  if (g->nranks > 1 && !g->transport)
-    fatal("[dlaf_mi355x] grid with %d ranks has no transport\n", g->nranks);
-  hipStream_t s = nullptr;
-  DLAF_HIP_CHECK(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
-  {
-    TileMatrix<T> Ad;
-    Ad.create(g, false, n, n, nb, isrc, jsrc);
-    Ad.upload(a, lda, false, false, T{}, s);
-    DLAF_HIP_CHECK(hipStreamSynchronize(s));
-    complete_canonical<T>(Ad, uplo_is_upper(uplo), kind == 'H' || kind == 'h');
-    Ad.download(a, lda, false, s);
-    DLAF_HIP_CHECK(hipStreamSynchronize(s));
-  }
-  DLAF_HIP_CHECK(hipStreamDestroy(s));
+  (void) checked_transport(*g);
+  ScratchStream s;  // before the matrices: destroyed after them
+  TileMatrix<T> Ad;
+  Ad.create(g, false, n, n, nb, isrc, jsrc);
+  Ad.upload(a, lda, false, false, T{}, s);
+  s.sync();
+  complete_canonical<T>(Ad, uplo_is_upper(uplo), kind == 'H' || kind == 'h');
+  Ad.download(a, lda, false, s);
+  s.sync();
   return 0;
 }
 

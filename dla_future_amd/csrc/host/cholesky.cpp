@@ -284,12 +284,10 @@ struct CholeskyIssue {
   size_t next_update_slice = 0;  // next pre-zeroed counter slice of coop_sync for a persistent update launch
 
   explicit CholeskyIssue(DeviceMatrix<T>& mat)
-      : m(mat), tr(grid_transport(*mat.grid)), dist(mat.grid->nranks > 1), tile_bytes(mat.tile_elems * sizeof(T)),
+      : m(mat), tr(checked_transport(*mat.grid)), dist(mat.grid->nranks > 1), tile_bytes(mat.tile_elems * sizeof(T)),
         ax_row(mat.transposed ? CommAxis::Col : CommAxis::Row),
         ax_col(mat.transposed ? CommAxis::Row : CommAxis::Col), s_main(mat.s_low), s_panel(mat.s_high),
         s_comm(mat.s_comm) {
-    if (dist && !tr)
-      fatal("[dlaf_mi355x] grid with %d ranks has no transport\n", m.grid->nranks);
     if (const char* e = std::getenv("DLAF_MI355X_POTRF_SLOTS"))
       potrf_slots = std::atol(e);
     else

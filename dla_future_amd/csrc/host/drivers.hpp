@@ -2,7 +2,10 @@
 // triangular, Hermitian and general multiplications (multiplication.cpp), the rank updates (rank_update.cpp), the addition / transposition (addition.cpp),
 // generalized-to-standard (gen_to_std.cpp), the inverses (inverse.cpp) and the norms (norm.cpp), host and
 // device-resident forms.  reduction_to_band and the eigensolver stages have headers of their own (red2band.hpp,
-// eigensolver.hpp).
+// eigensolver.hpp).  A further family is written on three shared pieces: its sweep on sweep.hpp (Sweep, Ring, the
+// one-step-ahead StepPipeline, bcast_view_column / bcast_column_and_transposed_panel), its host form on the host scope --
+// checked_transport (transport.hpp) after the quick returns, then a ScratchStream (pool.hpp) declared before the
+// matrices it serves.
 #pragma once
 #include "device_matrix.hpp"
 

@@ -133,10 +133,8 @@ int band_to_tridiag_device(DeviceMatrix<T>& A, int band, real_t<T>* d, real_t<T>
   if (band > b2t_max_band())
     fatal("[dlaf_mi355x] band_to_tridiagonal: band_size %d above the supported %d\n", band, b2t_max_band());
   Grid* grid = A.grid;
-  Transport* tr = grid_transport(*grid);
+  Transport* tr = checked_transport(*grid);
   const bool dist = grid->nranks > 1;
-  if (dist && !tr)
-    fatal("[dlaf_mi355x] grid with %d ranks has no transport\n", grid->nranks);
   const long n = A.n;
   hipStream_t s = A.s_high;
   DLAF_HIP_CHECK(hipMemsetAsync(A.info, 0, sizeof(int), s));
@@ -442,8 +440,7 @@ template <class T>
 int bt_band_to_tridiag_host(long n, int band, const T* v, long ldv, T* e, long lde, long ncols) {
   if (n <= 0 || ncols <= 0)
     return 0;
-  hipStream_t s;
-  DLAF_HIP_CHECK(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
+  ScratchStream s;
   PoolScope ws;
   T* dv = ws.get<T>((size_t) n * n);
   // row 1 of E on a 16-byte boundary, even leading dimension: the row blocks the reflector blocks act on start at the
@@ -460,8 +457,6 @@ int bt_band_to_tridiag_host(long n, int band, const T* v, long ldv, T* e, long l
   DLAF_HIP_CHECK(hipMemcpy2DAsync(e, (size_t) lde * sizeof(T), de, (size_t) ldd * sizeof(T), (size_t) n * sizeof(T),
                                   (size_t) ncols, hipMemcpyDeviceToHost, s));
   DLAF_HIP_CHECK(hipStreamSynchronize(s));
-  ws.release();
-  DLAF_HIP_CHECK(hipStreamDestroy(s));
   return r;
 }
 
@@ -740,16 +735,14 @@ static void download_eigenvectors(GeneralMatrix<T>& Z, const PartialSpectrumPlan
   const long srows = C.rows.local_size(), scols = C.cols.local_size();
   if (srows == 0 || scols <= pl.pad)
     return;
-  hipStream_t s = nullptr;
-  DLAF_HIP_CHECK(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
+  ScratchStream s;
   if (!C.staging)
     C.staging = dev_alloc<T>((size_t) srows * scols);
   launch_from_tiles(C.layout(C.staging, srows), s);
   DLAF_HIP_CHECK(hipMemcpy2DAsync(z + (size_t) (pl.first + pl.pad) * ldz, (size_t) ldz * sizeof(T),
                                   C.staging + (size_t) pl.pad * srows, (size_t) srows * sizeof(T),
                                   (size_t) srows * sizeof(T), (size_t) (scols - pl.pad), hipMemcpyDeviceToHost, s));
-  DLAF_HIP_CHECK(hipStreamSynchronize(s));
-  DLAF_HIP_CHECK(hipStreamDestroy(s));
+  s.sync();
 }
 
 namespace {

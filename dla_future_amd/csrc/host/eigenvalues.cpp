@@ -59,8 +59,7 @@ int tridiag_eigenvalues_host(long n, const R* d, const R* e, R* w, long begin, l
   check_eigenvalues_index("tridiagonal_eigenvalues", n, begin, end);
   if (n <= 0 || end <= begin)
     return 0;
-  hipStream_t s;
-  DLAF_HIP_CHECK(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
+  ScratchStream s;
   PoolScope ws;
   R *dd, *de;
   upload_tridiag(ws, n, d, e, dd, de, s);
@@ -69,8 +68,6 @@ int tridiag_eigenvalues_host(long n, const R* d, const R* e, R* w, long begin, l
   tridiag_eigenvalues_device<R>(n, dd, de, dw, begin, end, work, s);
   DLAF_HIP_CHECK(hipMemcpyAsync(w + begin, dw + begin, (size_t) (end - begin) * sizeof(R), hipMemcpyDeviceToHost, s));
   DLAF_HIP_CHECK(hipStreamSynchronize(s));
-  ws.release();
-  DLAF_HIP_CHECK(hipStreamDestroy(s));
   return 0;
 }
 
@@ -84,14 +81,11 @@ int sturm_count_host(long n, const R* d, const R* e, long nshifts, const R* shif
     std::fill(counts, counts + nshifts, 0L);
     return 0;
   }
-  hipStream_t s;
-  DLAF_HIP_CHECK(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
+  ScratchStream s;
   PoolScope ws;
   R *dd, *de;
   upload_tridiag(ws, n, d, e, dd, de, s);
   sturm_count_device<R>(n, dd, de, shifts, nshifts, counts, s);
-  ws.release();
-  DLAF_HIP_CHECK(hipStreamDestroy(s));
   return 0;
 }
 

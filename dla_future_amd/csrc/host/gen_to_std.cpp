@@ -343,9 +343,7 @@ template <class T>
 int gen_to_std_device(DeviceMatrix<T>& A, DeviceMatrix<T>& L) {
   if (A.grid != L.grid || A.n != L.n || A.nb != L.nb || A.ltr != L.ltr || A.ltc != L.ltc || A.transposed != L.transposed)
     fatal("[dlaf_mi355x] gen_to_std: A and the Cholesky factor differ in shape, uplo or distribution\n");
-  Transport* tr = grid_transport(*A.grid);
-  if (A.grid->nranks > 1 && !tr)
-    fatal("[dlaf_mi355x] grid with %d ranks has no transport\n", A.grid->nranks);
+  Transport* tr = checked_transport(*A.grid);
   // work enqueued on the factor's streams (a cholesky_start without a wait) must be done before it is read here
   for (hipStream_t ls : {L.s_high, L.s_low, L.s_comm})
     if (ls != nullptr && ls != A.s_high)

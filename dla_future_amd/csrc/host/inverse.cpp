@@ -285,9 +285,7 @@ struct Inverse {
 
 template <class T>
 Transport* transport_of(DeviceMatrix<T>& A) {
-  Transport* tr = grid_transport(*A.grid);
-  if (A.grid->nranks > 1 && !tr)
-    fatal("[dlaf_mi355x] grid with %d ranks has no transport\n", A.grid->nranks);
+  Transport* tr = checked_transport(*A.grid);
   // work enqueued on the matrix's other streams (a cholesky_start without a wait) must be done before it is read here
   for (hipStream_t ls : {A.s_low, A.s_comm})
     if (ls != nullptr && ls != A.s_high)

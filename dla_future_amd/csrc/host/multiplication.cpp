@@ -58,12 +58,14 @@ void multiply_canonical(TileMatrix<T>& Td, TileMatrix<T>& Bd, bool upper, bool u
   // ev_u: the update of step s has read P_k; ev_m: the TRMM of step s is done (and every buffer of the step free)
   Events ev_xb((size_t) nt), ev_u((size_t) nt), ev_m((size_t) nt);
 
-  TOperandFetch<T> tf(Td, Bd, tr, upper, !upper, s_comm, ev_m);
+  TOperandFetch<T> tf(Td, Bd, tr, upper, !upper, s_comm);
   Ring<T> xpanel((size_t) Bd.ltr * tile_elems, dist);
   std::vector<const T*> xp((size_t) nt, nullptr);  // P_k of step s as the update's first operand
 
-  // s_comm: the T operands of step s and the original column k to the other members of my Bd row
+  // s_comm: once the TRMM of step s - kBuf has freed the buffers, the T operands of step s and the original column k
+  // to the other members of my Bd row
   auto fetch = [&](long s) {
+    wait_ring_free(s_comm, ev_m, s);
     tf.fetch(s);
     xp[(size_t) s] = bcast_view_column(tr, Bd, tf.step_k(s), xpanel[(int) (s % kBuf)], s_comm);
     if (Bd.cols.P > 1)
@@ -154,11 +156,11 @@ void hermitian_canonical(TileMatrix<T>& Hd, TileMatrix<T>& Xd, TileMatrix<T>& Yd
 
   Sweep sw(false, false);
   const hipStream_t s_main = sw.s_main, s_comm = sw.s_comm;
-  // tf.ev_t: column l and the diagonal tile are in place (TOperandFetch); ev_in: so are row l and X(:, l);
-  // ev_done: the launch of step s is done, its buffers are free
-  Events ev_in((size_t) nt), ev_done((size_t) nt);
+  // one step ahead through the pipeline (its ring-reuse wait covers the buffers of TOperandFetch too).  tf.ev_t:
+  // column l and the diagonal tile are in place; the pipeline's ev_in: so are row l and X(:, l)
+  StepPipeline pipe(nt);
 
-  TOperandFetch<T> tf(Hd, Yd, tr, false, false, s_comm, ev_done);
+  TOperandFetch<T> tf(Hd, Yd, tr, false, false, s_comm);
   Ring<T> rpanel((size_t) Yd.ltc * tile_elems, dist), rstage((size_t) Hd.ltc * tile_elems, dist && aligned);
   Ring<T> xpanel((size_t) Yd.ltr * tile_elems, dist);
   struct RowOperand {
@@ -175,9 +177,8 @@ void hermitian_canonical(TileMatrix<T>& Hd, TileMatrix<T>& Xd, TileMatrix<T>& Yd
                                       (size_t) count, hipMemcpyDeviceToDevice, s_comm));
   };
 
-  auto fetch = [&](long l) {
-    tf.fetch(l);  // waits for the buffers of step l - kBuf first
-    const int buf = (int) (l % kBuf);
+  auto fetch = [&](long l, int buf) {
+    tf.fetch(l);
     RowOperand& o = rop[(size_t) l];
     const long jr1 = Yd.cols.next_local(l);  // local columns of Yd left of l
     if (!dist) {
@@ -229,16 +230,9 @@ void hermitian_canonical(TileMatrix<T>& Hd, TileMatrix<T>& Xd, TileMatrix<T>& Yd
     }
     // X(:, l) to the other members of my row of the view (X is not written: the owner sends its own tiles)
     o.x = bcast_view_column(tr, Xd, l, xpanel[buf], s_comm);
-    DLAF_HIP_CHECK(hipEventRecord(ev_in[(size_t) l], s_comm));
   };
 
-  sw.begin(true);
-
-  fetch(0);
-  for (long l = 0; l < nt; ++l) {
-    if (l + 1 < nt)
-      fetch(l + 1);
-    DLAF_HIP_CHECK(hipStreamWaitEvent(s_main, ev_in[(size_t) l], 0));
+  auto apply = [&](long l) {
     if (Yd.ltr > 0 && Yd.ltc > 0) {
       const TOperand<T>& o = tf.top[(size_t) l];
       const RowOperand& r = rop[(size_t) l];
@@ -273,8 +267,8 @@ void hermitian_canonical(TileMatrix<T>& Hd, TileMatrix<T>& Xd, TileMatrix<T>& Yd
       ha.conj_h = conj_h ? 1 : 0;
       launch_hemm(ha, s_main);
     }
-    DLAF_HIP_CHECK(hipEventRecord(ev_done[(size_t) l], s_main));
-  }
+  };
+  pipe.run(sw, fetch, apply);
 
   g_last_mult_ms = sw.finish();
   // whole-grid algorithmic flops: 2 x rows x na^2 (x4 complex)
@@ -346,8 +340,7 @@ void general_canonical(TileMatrix<T>& Ad, TileMatrix<T>& Bd, TileMatrix<T>& Cd, 
       launch_general(ga, s_main);
   }
   else {
-    // ev_in: the operands of step l are in place; ev_done: its launch is done, its buffers are free
-    Events ev_in((size_t) nkt), ev_done((size_t) nkt);
+    StepPipeline pipe(nkt);
     Ring<T> apanel((size_t) Cd.ltr * tile_elems, Ad.cols.P > 1), bpanel((size_t) Cd.ltc * tile_elems, Bd.rows.P > 1);
     struct StepOperands {
       const T* a = nullptr;
@@ -355,10 +348,7 @@ void general_canonical(TileMatrix<T>& Ad, TileMatrix<T>& Bd, TileMatrix<T>& Cd, 
       long b_ts = 0;
     };
     std::vector<StepOperands> sop((size_t) nkt);
-    auto fetch = [&](long l) {
-      const int buf = (int) (l % kBuf);
-      if (l >= kBuf)
-        DLAF_HIP_CHECK(hipStreamWaitEvent(s_comm, ev_done[(size_t) (l - kBuf)], 0));
+    auto fetch = [&](long l, int buf) {
       StepOperands& o = sop[(size_t) l];
       o.a = bcast_view_column(tr, Ad, l, apanel[buf], s_comm);
       if (Bd.rows.P > 1) {
@@ -375,15 +365,8 @@ void general_canonical(TileMatrix<T>& Ad, TileMatrix<T>& Bd, TileMatrix<T>& Cd, 
         o.b = Bd.tile(l, 0);
         o.b_ts = (long) (tile_elems * Bd.ltr);
       }
-      DLAF_HIP_CHECK(hipEventRecord(ev_in[(size_t) l], s_comm));
     };
-
-    sw.begin(true);
-    fetch(0);
-    for (long l = 0; l < nkt; ++l) {
-      if (l + 1 < nkt)
-        fetch(l + 1);
-      DLAF_HIP_CHECK(hipStreamWaitEvent(s_main, ev_in[(size_t) l], 0));
+    auto apply = [&](long l) {
       if (work) {
         ga.a = sop[(size_t) l].a;
         ga.a_ts = (long) tile_elems;
@@ -394,8 +377,8 @@ void general_canonical(TileMatrix<T>& Ad, TileMatrix<T>& Bd, TileMatrix<T>& Cd, 
         ga.first = l == 0 ? 1 : 0;
         launch_general(ga, s_main);
       }
-      DLAF_HIP_CHECK(hipEventRecord(ev_done[(size_t) l], s_main));
-    }
+    };
+    pipe.run(sw, fetch, apply);
   }
   g_last_mult_ms = sw.finish();
   // whole-grid algorithmic flops: 2 m n k (x4 complex)
@@ -448,30 +431,23 @@ int hermitian_multiplication_host(Grid* g, char side, char uplo, T alpha, const 
     fatal("[dlaf_mi355x] hermitian multiplication: A must share the source process of B and C along A's dimension\n");
   if (m == 0 || n == 0)
     return 0;
-  runtime_init();
-  (void) grid_transport(*g);
-  if (g->nranks > 1 && !g->transport)
-    fatal("[dlaf_mi355x] grid with %d ranks has no transport\n", g->nranks);
+  (void) checked_transport(*g);
   const long na = left ? m : n;
-  hipStream_t s = nullptr;
-  DLAF_HIP_CHECK(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
-  {
-    TileMatrix<T> Hd, Xd, Yd;
-    Hd.create(g, a_upper, na, na, nb, a_isrc, a_jsrc);
-    if (nb_free <= 0)
-      nb_free = nb;
-    Xd.create_rhs(g, left, m, n, left ? nb : nb_free, left ? nb_free : nb, isrc, jsrc);
-    Yd.create_rhs(g, left, m, n, left ? nb : nb_free, left ? nb_free : nb, isrc, jsrc);
-    Hd.upload(a, lda, a_upper, false, T{}, s);
-    Xd.upload(b, ldb, left, false, T{}, s);
-    if (!is_zero(beta))  // beta = 0: C is not read
-      Yd.upload(c, ldc, left, false, T{}, s);
-    DLAF_HIP_CHECK(hipStreamSynchronize(s));
-    hermitian_canonical(Hd, Xd, Yd, left ? conj_of(alpha) : alpha, left ? conj_of(beta) : beta, false);
-    Yd.download(c, ldc, left, s);
-    DLAF_HIP_CHECK(hipStreamSynchronize(s));
-  }
-  DLAF_HIP_CHECK(hipStreamDestroy(s));
+  ScratchStream s;  // before the matrices: destroyed after them
+  TileMatrix<T> Hd, Xd, Yd;
+  Hd.create(g, a_upper, na, na, nb, a_isrc, a_jsrc);
+  if (nb_free <= 0)
+    nb_free = nb;
+  Xd.create_rhs(g, left, m, n, left ? nb : nb_free, left ? nb_free : nb, isrc, jsrc);
+  Yd.create_rhs(g, left, m, n, left ? nb : nb_free, left ? nb_free : nb, isrc, jsrc);
+  Hd.upload(a, lda, a_upper, false, T{}, s);
+  Xd.upload(b, ldb, left, false, T{}, s);
+  if (!is_zero(beta))  // beta = 0: C is not read
+    Yd.upload(c, ldc, left, false, T{}, s);
+  s.sync();
+  hermitian_canonical(Hd, Xd, Yd, left ? conj_of(alpha) : alpha, left ? conj_of(beta) : beta, false);
+  Yd.download(c, ldc, left, s);
+  s.sync();
   return 0;
 }
 
@@ -502,31 +478,27 @@ int hermitian_device_t(char side, char uplo, T alpha, DeviceMatrix<T>& A, Genera
     fatal("[dlaf_mi355x] %s: A must share the source process of B and C along A's dimension\n", who);
   if (m == 0 || n == 0)
     return 0;
-  hipStream_t s = nullptr;
-  DLAF_HIP_CHECK(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
-  {
-    TileMatrix<T> Hd, Xd, Yd;
-    const size_t te = A.tile_elems;
-    Hd.create(g, A.transposed, na, na, nb, a_rows.src, a_cols.src, A.tiles);
-    if (left) {
-      Xd.create(g, true, m, n, nb, C.isrc, C.jsrc);
-      Yd.create(g, true, m, n, nb, C.isrc, C.jsrc);
-      xform_tiles(Xd.tiles, Xd.ltr, Xd.ltc, B.m.tiles, B.m.ltr, te, nb, 0, T{}, false, s);
-      if (!is_zero(beta))
-        xform_tiles(Yd.tiles, Yd.ltr, Yd.ltc, C.m.tiles, C.m.ltr, te, nb, 0, T{}, false, s);
-      DLAF_HIP_CHECK(hipStreamSynchronize(s));
-    }
-    else {
-      Xd.create(g, false, m, n, nb, C.isrc, C.jsrc, B.m.tiles);
-      Yd.create(g, false, m, n, nb, C.isrc, C.jsrc, C.m.tiles);
-    }
-    hermitian_canonical(Hd, Xd, Yd, left ? conj_of(alpha) : alpha, left ? conj_of(beta) : beta, A.transposed);
-    if (left) {
-      xform_tiles(C.m.tiles, C.m.ltr, C.m.ltc, Yd.tiles, Yd.ltr, te, nb, 0, T{}, false, s);
-      DLAF_HIP_CHECK(hipStreamSynchronize(s));
-    }
+  ScratchStream s;  // before the matrices: destroyed after them
+  TileMatrix<T> Hd, Xd, Yd;
+  const size_t te = A.tile_elems;
+  Hd.create(g, A.transposed, na, na, nb, a_rows.src, a_cols.src, A.tiles);
+  if (left) {
+    Xd.create(g, true, m, n, nb, C.isrc, C.jsrc);
+    Yd.create(g, true, m, n, nb, C.isrc, C.jsrc);
+    xform_tiles(Xd.tiles, Xd.ltr, Xd.ltc, B.m.tiles, B.m.ltr, te, nb, 0, T{}, false, s);
+    if (!is_zero(beta))
+      xform_tiles(Yd.tiles, Yd.ltr, Yd.ltc, C.m.tiles, C.m.ltr, te, nb, 0, T{}, false, s);
+    s.sync();
   }
-  DLAF_HIP_CHECK(hipStreamDestroy(s));
+  else {
+    Xd.create(g, false, m, n, nb, C.isrc, C.jsrc, B.m.tiles);
+    Yd.create(g, false, m, n, nb, C.isrc, C.jsrc, C.m.tiles);
+  }
+  hermitian_canonical(Hd, Xd, Yd, left ? conj_of(alpha) : alpha, left ? conj_of(beta) : beta, A.transposed);
+  if (left) {
+    xform_tiles(C.m.tiles, C.m.ltr, C.m.ltc, Yd.tiles, Yd.ltr, te, nb, 0, T{}, false, s);
+    s.sync();
+  }
   return 0;
 }
 
@@ -551,31 +523,24 @@ int general_multiplication_host(Grid* g, char opa, char opb, T alpha, const T* a
                                 long k, int nb, int c_isrc, int c_jsrc) {
   if (m == 0 || n == 0)
     return 0;
-  runtime_init();
-  (void) grid_transport(*g);
-  if (g->nranks > 1 && !g->transport)
-    fatal("[dlaf_mi355x] grid with %d ranks has no transport\n", g->nranks);
+  (void) checked_transport(*g);
   const bool an = gemm_op_is_n(opa), bn = gemm_op_is_n(opb);
   const bool product = k > 0 && !is_zero(alpha);
-  hipStream_t s = nullptr;
-  DLAF_HIP_CHECK(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
-  {
-    TileMatrix<T> Ad, Bd, Cd;
-    Cd.create(g, false, m, n, nb, c_isrc, c_jsrc);
-    if (product) {
-      Ad.create(g, false, an ? m : k, an ? k : m, nb, a_isrc, a_jsrc);
-      Bd.create(g, false, bn ? k : n, bn ? n : k, nb, b_isrc, b_jsrc);
-      Ad.upload(a, lda, false, false, T{}, s);
-      Bd.upload(b, ldb, false, false, T{}, s);
-    }
-    if (!is_zero(beta))  // beta = 0: C is not read
-      Cd.upload(c, ldc, false, false, T{}, s);
-    DLAF_HIP_CHECK(hipStreamSynchronize(s));
-    general_canonical(Ad, Bd, Cd, opa, opb, k, product ? (k + nb - 1) / nb : 0, alpha, beta);
-    Cd.download(c, ldc, false, s);
-    DLAF_HIP_CHECK(hipStreamSynchronize(s));
+  ScratchStream s;  // before the matrices: destroyed after them
+  TileMatrix<T> Ad, Bd, Cd;
+  Cd.create(g, false, m, n, nb, c_isrc, c_jsrc);
+  if (product) {
+    Ad.create(g, false, an ? m : k, an ? k : m, nb, a_isrc, a_jsrc);
+    Bd.create(g, false, bn ? k : n, bn ? n : k, nb, b_isrc, b_jsrc);
+    Ad.upload(a, lda, false, false, T{}, s);
+    Bd.upload(b, ldb, false, false, T{}, s);
   }
-  DLAF_HIP_CHECK(hipStreamDestroy(s));
+  if (!is_zero(beta))  // beta = 0: C is not read
+    Cd.upload(c, ldc, false, false, T{}, s);
+  s.sync();
+  general_canonical(Ad, Bd, Cd, opa, opb, k, product ? (k + nb - 1) / nb : 0, alpha, beta);
+  Cd.download(c, ldc, false, s);
+  s.sync();
   return 0;
 }
 

@@ -60,10 +60,8 @@ double combine_squares(double big, double med, double sml) {
 template <class T>
 double norm_of_view(Grid& grid, char kind, int structure, bool unit, const T* tiles, const Axis& rows, const Axis& cols,
                     int nb, hipStream_t s) {
-  Transport* tr = grid_transport(grid);
+  Transport* tr = checked_transport(grid);
   const bool dist = grid.nranks > 1;
-  if (dist && !tr)
-    fatal("[dlaf_mi355x] grid with %d ranks has no transport\n", grid.nranks);
   g_profile_ms = 0;
   g_profile_bytes = 0;
   const long ltr = rows.local_tiles(), ltc = cols.local_tiles();
@@ -199,17 +197,11 @@ double general_norm_host(Grid* g, char norm, const T* a, long lda, long m, long 
   if (m <= 0 || n <= 0)
     return 0.0;
   runtime_init();
-  hipStream_t s;
-  DLAF_HIP_CHECK(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
-  double v;
-  {
-    TileMatrix<T> A;
-    A.create(g, false, m, n, nb, isrc, jsrc);
-    A.upload(a, lda, false, false, T{}, s);
-    v = norm_of_tile_matrix(kind, A, s);
-  }
-  DLAF_HIP_CHECK(hipStreamDestroy(s));
-  return v;
+  ScratchStream s;
+  TileMatrix<T> A;
+  A.create(g, false, m, n, nb, isrc, jsrc);
+  A.upload(a, lda, false, false, T{}, s);
+  return norm_of_tile_matrix(kind, A, s);
 }
 
 template <class T>
@@ -247,11 +239,8 @@ double general_norm_device(char norm, MatrixBase* h) {
     auto& gm = static_cast<GeneralMatrix<T>&>(*h);
     if (gm.rows_g <= 0 || gm.cols_g <= 0)
       return 0.0;
-    hipStream_t s;
-    DLAF_HIP_CHECK(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
-    const double v = norm_of_tile_matrix(kind, gm.m, s);
-    DLAF_HIP_CHECK(hipStreamDestroy(s));
-    return v;
+    ScratchStream s;
+    return norm_of_tile_matrix(kind, gm.m, s);
   });
 }
 

@@ -78,4 +78,17 @@ struct DevBuf {
   void alloc(size_t elems) { p = dev_alloc<T>(elems); }
 };
 
+// The scratch stream of a host form or a transfer (uploads, downloads, tile transforms): non-blocking, lives as long as
+// its scope.  Declare it BEFORE the matrices it serves: they are destroyed first, the stream after them.  The destructor
+// does not wait: the owner calls sync() where the results are needed.
+struct ScratchStream {
+  hipStream_t s = nullptr;
+  ScratchStream() { DLAF_HIP_CHECK(hipStreamCreateWithFlags(&s, hipStreamNonBlocking)); }
+  ScratchStream(const ScratchStream&) = delete;
+  ScratchStream& operator=(const ScratchStream&) = delete;
+  ~ScratchStream() { (void) hipStreamDestroy(s); }
+  operator hipStream_t() const { return s; }
+  void sync() const { DLAF_HIP_CHECK(hipStreamSynchronize(s)); }
+};
+
 }  // namespace dlaf_mi355x

@@ -91,55 +91,25 @@ void rank_update_canonical(DeviceMatrix<T>& C, TileMatrix<T>* Ad, TileMatrix<T>*
     const Axis& scol = C.transposed ? C.rows : C.cols;
     const Axis& ka = Ad->cols;
     const bool hop = srow.P > 1;  // the transposed panel travels; else every tile of the column panel is here
-    Events ev_in((size_t) nkt), ev_done((size_t) nkt);
+    StepPipeline pipe(nkt);
     const size_t rp = (size_t) Ad->ltr * te, cp = (size_t) (scol.local_tiles() + srow.P) * te;
     Ring<T> arow(rp, ka.P > 1), acol(cp, hop), brow(rp, two && ka.P > 1), bcol(cp, two && hop);
-    struct Panel {
-      const T* base = nullptr;
-      long ts = 0, ts2 = 0;
-      int period = 1;
-    };
     struct StepOperands {
-      Panel arow, acol, brow, bcol;
+      PanelPair<T> a, b;
     };
     std::vector<StepOperands> sop((size_t) nkt);
-    auto fetch_one = [&](TileMatrix<T>& M, long l, T* rbuf, T* cbuf, Panel& prow, Panel& pcol) {
-      prow.base = bcast_view_column(tr, M, l, rbuf, s_comm);
-      prow.ts = (long) te;
-      if (hop) {
-        (void) bcast_transposed_panel_whole(tr, CommAxis::Col, srow, scol, prow.base, cbuf, te, s_comm, pcol.period,
-                                            pcol.ts2);
-        pcol.base = cbuf;
-        pcol.ts = (long) te;
-      }
-      else {
-        // I hold every tile row of the panel: the tile of global row gj sits at local row gj
-        pcol.base = prow.base + (size_t) scol.shift() * te;
-        pcol.ts = (long) te * scol.P;
-      }
-    };
-    auto fetch = [&](long l) {
-      const int buf = (int) (l % kBuf);
-      if (l >= kBuf)
-        DLAF_HIP_CHECK(hipStreamWaitEvent(s_comm, ev_done[(size_t) (l - kBuf)], 0));
+    auto fetch = [&](long l, int buf) {
       StepOperands& o = sop[(size_t) l];
-      fetch_one(*Ad, l, arow[buf], acol[buf], o.arow, o.acol);
+      o.a = bcast_column_and_transposed_panel(tr, *Ad, l, srow, scol, arow[buf], acol[buf], s_comm);
       if (two)
-        fetch_one(*Bd, l, brow[buf], bcol[buf], o.brow, o.bcol);
-      DLAF_HIP_CHECK(hipEventRecord(ev_in[(size_t) l], s_comm));
+        o.b = bcast_column_and_transposed_panel(tr, *Bd, l, srow, scol, brow[buf], bcol[buf], s_comm);
     };
-
-    sw.begin(true);
-    fetch(0);
-    for (long l = 0; l < nkt; ++l) {
-      if (l + 1 < nkt)
-        fetch(l + 1);
-      DLAF_HIP_CHECK(hipStreamWaitEvent(s_main, ev_in[(size_t) l], 0));
+    auto apply = [&](long l) {
       if (work) {
         const StepOperands& o = sop[(size_t) l];
         // the view's rows are C's rows (uplo L) or C's columns (uplo U: the transposed view)
-        const Panel& px = C.transposed ? o.acol : o.arow;
-        const Panel& py = C.transposed ? o.arow : o.acol;
+        const Panel<T>& px = C.transposed ? o.a.col : o.a.row;
+        const Panel<T>& py = C.transposed ? o.a.row : o.a.col;
         ra.x = px.base;
         ra.x_ts = px.ts;
         ra.x_ts2 = px.ts2;
@@ -149,8 +119,8 @@ void rank_update_canonical(DeviceMatrix<T>& C, TileMatrix<T>* Ad, TileMatrix<T>*
         ra.y_ts2 = py.ts2;
         ra.y_period = py.period;
         if (two) {
-          ra.x2 = (C.transposed ? o.bcol : o.brow).base;
-          ra.y2 = (C.transposed ? o.brow : o.bcol).base;
+          ra.x2 = (C.transposed ? o.b.col : o.b.row).base;
+          ra.y2 = (C.transposed ? o.b.row : o.b.col).base;
         }
         ra.ks = 0;
         ra.nk = 1;
@@ -158,8 +128,8 @@ void rank_update_canonical(DeviceMatrix<T>& C, TileMatrix<T>* Ad, TileMatrix<T>*
         ra.first = l == 0 ? 1 : 0;
         launch_rank_k(ra, s_main);
       }
-      DLAF_HIP_CHECK(hipEventRecord(ev_done[(size_t) l], s_main));
-    }
+    };
+    pipe.run(sw, fetch, apply);
   }
   const double ms = sw.finish();
   // whole-grid algorithmic flops: k n (n + 1) per product (x4 complex)
@@ -178,34 +148,27 @@ int hermitian_rank_update_host(Grid* g, bool her2k, char uplo, char trans, T alp
   const bool product = k > 0 && !is_zero(alpha);
   if (!product && beta == real_t<T>(1))
     return 0;  // quick return: C is untouched, the imaginary parts of its diagonal included
-  runtime_init();
-  (void) grid_transport(*g);
-  if (g->nranks > 1 && !g->transport)
-    fatal("[dlaf_mi355x] grid with %d ranks has no transport\n", g->nranks);
+  (void) checked_transport(*g);
   const bool tn = herk_trans_is_n(trans);
-  hipStream_t s = nullptr;
-  DLAF_HIP_CHECK(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
-  {
-    DeviceMatrix<T> Cd;
-    Cd.create(g, uplo, n, nb, c_isrc, c_jsrc);
-    TileMatrix<T> Ad, Bd;
-    if (product) {
-      Ad.create(g, false, tn ? n : k, tn ? k : n, nb, a_isrc, a_jsrc);
-      Ad.upload(a, lda, false, false, T{}, s);
-      if (her2k) {
-        Bd.create(g, false, tn ? n : k, tn ? k : n, nb, a_isrc, a_jsrc);
-        Bd.upload(b, ldb, false, false, T{}, s);
-      }
-      DLAF_HIP_CHECK(hipStreamSynchronize(s));
+  ScratchStream s;  // before the matrices: destroyed after them
+  DeviceMatrix<T> Cd;
+  Cd.create(g, uplo, n, nb, c_isrc, c_jsrc);
+  TileMatrix<T> Ad, Bd;
+  if (product) {
+    Ad.create(g, false, tn ? n : k, tn ? k : n, nb, a_isrc, a_jsrc);
+    Ad.upload(a, lda, false, false, T{}, s);
+    if (her2k) {
+      Bd.create(g, false, tn ? n : k, tn ? k : n, nb, a_isrc, a_jsrc);
+      Bd.upload(b, ldb, false, false, T{}, s);
     }
-    const bool read_c = beta != real_t<T>(0);  // beta = 0: C is not read
-    if (read_c)
-      Cd.upload(c, ldc);
-    rank_update_canonical<T>(Cd, product ? &Ad : nullptr, (product && her2k) ? &Bd : nullptr, tn, k,
-                             product ? (k + nb - 1) / nb : 0, alpha, beta);
-    Cd.download(c, ldc, read_c);
+    s.sync();
   }
-  DLAF_HIP_CHECK(hipStreamDestroy(s));
+  const bool read_c = beta != real_t<T>(0);  // beta = 0: C is not read
+  if (read_c)
+    Cd.upload(c, ldc);
+  rank_update_canonical<T>(Cd, product ? &Ad : nullptr, (product && her2k) ? &Bd : nullptr, tn, k,
+                           product ? (k + nb - 1) / nb : 0, alpha, beta);
+  Cd.download(c, ldc, read_c);
   return 0;
 }
 

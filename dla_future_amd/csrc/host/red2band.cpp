@@ -102,13 +102,6 @@ int get_band_size(int nb) {
 }
 
 namespace {
-Transport* checked_transport(Grid& grid) {
-  Transport* tr = grid_transport(grid);
-  if (grid.nranks > 1 && !tr)
-    fatal("[dlaf_mi355x] grid with %d ranks has no transport\n", grid.nranks);
-  return tr;
-}
-
 template <class T>
 void gemm(int M, int N, int K, const T* a, long lda, char opa, const T* b, long ldb, char opb, T* c, long ldc,
           double alpha, double beta, hipStream_t s, int ksplit = 1, T* partial = nullptr) {

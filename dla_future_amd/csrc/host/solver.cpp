@@ -86,7 +86,7 @@ void solve_canonical(TileMatrix<T>& Td, TileMatrix<T>& Bd, bool upper, bool unit
   DLAF_HIP_CHECK(hipStreamWaitEvent(s_comm, ev_prep[0], 0));
 
   // the T operands of every step (and the global step order), the X panel on the processes that do not own it
-  TOperandFetch<T> tf(Td, Bd, tr, upper, upper, s_comm, ev_free, winv_of.data(), winv_elems);
+  TOperandFetch<T> tf(Td, Bd, tr, upper, upper, s_comm, winv_of.data(), winv_elems);
   Ring<T> xpanel((size_t) Bd.ltr * tile_elems, dist);
 
   auto update = [&](long s, const T* xp, long j0, long j1) {
@@ -109,8 +109,10 @@ void solve_canonical(TileMatrix<T>& Td, TileMatrix<T>& Bd, bool upper, bool unit
   const T* xp_prev = nullptr;
   for (long s = 0; s < nt; ++s) {
     const long k = tf.step_k(s);
-    if (s + 1 < nt)
+    if (s + 1 < nt) {
+      wait_ring_free(s_comm, ev_free, s + 1);  // the buffers of step s + 1 - kBuf, T operands and X panel alike
       tf.fetch(s + 1);
+    }
     DLAF_HIP_CHECK(hipStreamWaitEvent(s_main, tf.ev_t[(size_t) s], 0));
 
     // column k of Bd: X(:,k) = B(:,k) T_kk^-H
@@ -180,10 +182,7 @@ template <class T>
 int triangular_canonical_host(const char* who, CanonicalSweep<T> sweep, bool may_reverse, Grid* g, char side, char uplo,
                               char op, char diag, T alpha, const T* a, long lda, int a_isrc, int a_jsrc, T* b, long ldb,
                               long m, long n, int nb, int b_isrc, int b_jsrc, int nb_free) {
-  runtime_init();
-  (void) grid_transport(*g);
-  if (g->nranks > 1 && !g->transport)
-    fatal("[dlaf_mi355x] grid with %d ranks has no transport\n", g->nranks);
+  (void) checked_transport(*g);
   if (m == 0 || n == 0)
     return 0;
   const auto [left, a_upper, unit, t_transposed, t_conj, t_upper] = operand_map(side, uplo, op, diag);
@@ -191,37 +190,33 @@ int triangular_canonical_host(const char* who, CanonicalSweep<T> sweep, bool may
   if (left ? (a_isrc != b_isrc) : (a_jsrc != b_jsrc))
     fatal("[dlaf_mi355x] %s: A and B must share the source process along the triangular dimension\n", who);
 
-  hipStream_t s = nullptr;
-  DLAF_HIP_CHECK(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
-  {
-    TileMatrix<T> Td, Bd;
-    Td.create(g, t_transposed, na, na, nb, a_isrc, a_jsrc);
-    // B's blocks: nb along the triangular dimension (its rows for side = Left), nb_free along the other
-    if (nb_free <= 0)
-      nb_free = nb;
-    Bd.create_rhs(g, left, m, n, left ? nb : nb_free, left ? nb_free : nb, b_isrc, b_jsrc);
-    // One process, whole tiles: an upper triangular T (swept backward by the round-1 strips kernel) is laid out
-    // REVERSED -- T'(i, j) = T(na-1-i, na-1-j) is lower triangular, X'(:, j) = X(:, na-1-j) solves X' T'^H = B' -- and
-    // the forward sweep of the row-owner kernel does the work; the download reverses back.
-    // DLAF_MI355X_SOLVER_REVERSE=0: the backward sweep (A/B).
-    static const bool reverse_on = [] {
-      const char* e = std::getenv("DLAF_MI355X_SOLVER_REVERSE");
-      return e ? std::atoi(e) != 0 : true;
-    }();
-    const bool reversed = may_reverse && reverse_on && t_upper && g->nranks == 1 && na % nb == 0;
-    if (reversed) {
-      Td.rev_rows = Td.rev_cols = true;
-      Bd.rev_cols = true;  // the view's columns are the triangular dimension
-    }
-    Td.upload(a, lda, t_conj, false, T{}, s);
-    // Left: B_dev = (alpha B)^H = conj(alpha) B^H (the relayout conjugates first, then scales)
-    Bd.upload(b, ldb, left, true, left ? conj_of(alpha) : alpha, s);
-    DLAF_HIP_CHECK(hipStreamSynchronize(s));
-    sweep(Td, Bd, reversed ? false : t_upper, unit);
-    Bd.download(b, ldb, left, s);
-    DLAF_HIP_CHECK(hipStreamSynchronize(s));
+  ScratchStream s;  // before the matrices: destroyed after them
+  TileMatrix<T> Td, Bd;
+  Td.create(g, t_transposed, na, na, nb, a_isrc, a_jsrc);
+  // B's blocks: nb along the triangular dimension (its rows for side = Left), nb_free along the other
+  if (nb_free <= 0)
+    nb_free = nb;
+  Bd.create_rhs(g, left, m, n, left ? nb : nb_free, left ? nb_free : nb, b_isrc, b_jsrc);
+  // One process, whole tiles: an upper triangular T (swept backward by the round-1 strips kernel) is laid out
+  // REVERSED -- T'(i, j) = T(na-1-i, na-1-j) is lower triangular, X'(:, j) = X(:, na-1-j) solves X' T'^H = B' -- and
+  // the forward sweep of the row-owner kernel does the work; the download reverses back.
+  // DLAF_MI355X_SOLVER_REVERSE=0: the backward sweep (A/B).
+  static const bool reverse_on = [] {
+    const char* e = std::getenv("DLAF_MI355X_SOLVER_REVERSE");
+    return e ? std::atoi(e) != 0 : true;
+  }();
+  const bool reversed = may_reverse && reverse_on && t_upper && g->nranks == 1 && na % nb == 0;
+  if (reversed) {
+    Td.rev_rows = Td.rev_cols = true;
+    Bd.rev_cols = true;  // the view's columns are the triangular dimension
   }
-  DLAF_HIP_CHECK(hipStreamDestroy(s));
+  Td.upload(a, lda, t_conj, false, T{}, s);
+  // Left: B_dev = (alpha B)^H = conj(alpha) B^H (the relayout conjugates first, then scales)
+  Bd.upload(b, ldb, left, true, left ? conj_of(alpha) : alpha, s);
+  s.sync();
+  sweep(Td, Bd, reversed ? false : t_upper, unit);
+  Bd.download(b, ldb, left, s);
+  s.sync();
   return 0;
 }
 
@@ -254,14 +249,12 @@ MatrixBase* general_matrix_create(Grid* g, char type, long m, long n, int nb, in
 
 template <class T>
 static void gm_transfer(GeneralMatrix<T>& gm, void* host, long ld, bool up) {
-  hipStream_t s = nullptr;
-  DLAF_HIP_CHECK(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
+  ScratchStream s;
   if (up)
     gm.m.upload(static_cast<const T*>(host), ld, false, false, T{}, s);
   else
     gm.m.download(static_cast<T*>(host), ld, false, s);
-  DLAF_HIP_CHECK(hipStreamSynchronize(s));
-  DLAF_HIP_CHECK(hipStreamDestroy(s));
+  s.sync();
 }
 
 void general_matrix_transfer(MatrixBase* h, void* host, long ld, bool upload) {
@@ -314,37 +307,33 @@ int triangular_canonical_device(const char* who, CanonicalSweep<T> sweep, char s
   const bool s_transpose = t_transposed != A.transposed;
   const int t_mode = s_transpose ? (t_conj ? 0 : 3) : (t_conj ? 4 : 5);
 
-  hipStream_t s = nullptr;
-  DLAF_HIP_CHECK(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
-  {
-    TileMatrix<T> Td, Bd;
-    const size_t te = A.tile_elems;
-    if (t_mode == 5) {
-      Td.create(g, t_transposed, na, na, nb, a_rows.src, a_cols.src, A.tiles);  // T is the stored matrix itself
-    }
-    else {
-      Td.create(g, t_transposed, na, na, nb, a_rows.src, a_cols.src);
-      xform_tiles(Td.tiles, Td.ltr, Td.ltc, A.tiles, A.ltr, te, nb, t_mode, T{}, false, s);
-    }
-    const bool scale = !is_one(alpha);
-    if (left) {
-      // B_dev = (alpha B)^H = conj(alpha) B^H
-      Bd.create(g, true, m, n, nb, B.isrc, B.jsrc);
-      xform_tiles(Bd.tiles, Bd.ltr, Bd.ltc, B.m.tiles, B.m.ltr, te, nb, 0, conj_of(alpha), scale, s);
-    }
-    else {
-      Bd.create(g, false, m, n, nb, B.isrc, B.jsrc, B.m.tiles);  // in place
-      if (scale)
-        xform_tiles(Bd.tiles, Bd.ltr, Bd.ltc, B.m.tiles, B.m.ltr, te, nb, 5, alpha, true, s);
-    }
-    DLAF_HIP_CHECK(hipStreamSynchronize(s));
-    sweep(Td, Bd, t_upper, unit);
-    if (left) {
-      xform_tiles(B.m.tiles, B.m.ltr, B.m.ltc, Bd.tiles, Bd.ltr, te, nb, 0, T{}, false, s);
-      DLAF_HIP_CHECK(hipStreamSynchronize(s));
-    }
+  ScratchStream s;  // before the matrices: destroyed after them
+  TileMatrix<T> Td, Bd;
+  const size_t te = A.tile_elems;
+  if (t_mode == 5) {
+    Td.create(g, t_transposed, na, na, nb, a_rows.src, a_cols.src, A.tiles);  // T is the stored matrix itself
   }
-  DLAF_HIP_CHECK(hipStreamDestroy(s));
+  else {
+    Td.create(g, t_transposed, na, na, nb, a_rows.src, a_cols.src);
+    xform_tiles(Td.tiles, Td.ltr, Td.ltc, A.tiles, A.ltr, te, nb, t_mode, T{}, false, s);
+  }
+  const bool scale = !is_one(alpha);
+  if (left) {
+    // B_dev = (alpha B)^H = conj(alpha) B^H
+    Bd.create(g, true, m, n, nb, B.isrc, B.jsrc);
+    xform_tiles(Bd.tiles, Bd.ltr, Bd.ltc, B.m.tiles, B.m.ltr, te, nb, 0, conj_of(alpha), scale, s);
+  }
+  else {
+    Bd.create(g, false, m, n, nb, B.isrc, B.jsrc, B.m.tiles);  // in place
+    if (scale)
+      xform_tiles(Bd.tiles, Bd.ltr, Bd.ltc, B.m.tiles, B.m.ltr, te, nb, 5, alpha, true, s);
+  }
+  s.sync();
+  sweep(Td, Bd, t_upper, unit);
+  if (left) {
+    xform_tiles(B.m.tiles, B.m.ltr, B.m.ltc, Bd.tiles, Bd.ltr, te, nb, 0, T{}, false, s);
+    s.sync();
+  }
   return 0;
 }
 

@@ -1,12 +1,23 @@
 // sweep.hpp -- the scaffold shared by the sweeps over a canonical form (solver.cpp: solve_canonical  X T^H = B;
 // multiplication.cpp: multiply_canonical  X = B T^H  and hermitian_canonical  Y = beta Y + alpha X H) and by the
-// drivers that map side / uplo / op / diag onto them.  A sweep writes its step logic; from here it takes
+// drivers that map side / uplo / op / diag onto them, and by the SUMMA-like walks of general_canonical
+// (multiplication.cpp), rank_update.cpp and addition.cpp.  A sweep writes its step logic; from here it takes
 //   Sweep              its streams, the timing window and the kernels' status word
 //   Events, Ring       one event per step; kBuf device buffers, step s uses s % kBuf
+//   wait_ring_free     the ONE statement of the ring-reuse wait: before step s is fetched into buffer s % kBuf, s_comm
+//                      waits for the kernels of step s - kBuf
+//   StepPipeline       the whole one-step-ahead protocol of a sweep whose step is "fetch on s_comm, then launch on
+//                      s_main": the caller gives fetch(s, buf) and apply(s) and touches no event
 //   TOperandFetch      the operands taken from the triangular / Hermitian matrix, one step ahead (below)
 //   bcast_view_column  tile column k of a view to the other members of the view's row communicator
+//   bcast_column_and_transposed_panel   that column, then its whole transposed panel: the row-side and column-side
+//                      Panel of a step of the rank-k update and of the transposing addition
+//   ScratchStream      (pool.hpp) the scoped stream of a host form: uploads, downloads, tile transforms
+//   checked_transport  (transport.hpp) the opening of every entry: runtime, the grid's transport, fatal without one
 //   launch_args.hpp    rect_update_args / panel_args over every local row of Bd: the launch arguments of a step
 //   operand_map        side / uplo / op / diag -> T and B_dev (the table in solver.cpp's header)
+// solve_canonical and multiply_canonical keep loops of their own (a side stream, the update split around the previous
+// step's column) and state the ring-reuse wait with wait_ring_free.
 #pragma once
 #include <algorithm>
 #include <vector>
@@ -99,6 +110,43 @@ struct Sweep {
   }
 };
 
+// The ring-reuse wait: buffer s % kBuf was last read by the kernels of step s - kBuf, whose end ev_done[s - kBuf] marks
+// (recorded before this call is made).  Nothing may be fetched into the buffers of step s before s_comm has waited here.
+inline void wait_ring_free(hipStream_t s_comm, const Events& ev_done, long s) {
+  if (s >= kBuf)
+    DLAF_HIP_CHECK(hipStreamWaitEvent(s_comm, ev_done[(size_t) (s - kBuf)], 0));
+}
+
+// The one-step-ahead pipeline of a sweep whose step is "operands on s_comm, then kernels on s_main".  fetch(s, buf)
+// enqueues the broadcasts of step s on s_comm into ring buffer buf and stores the operand pointers; apply(s) fills the
+// arguments and launches on s_main.  ev_in[s]: the operands of step s are in place; ev_done[s]: its kernels are done,
+// its buffers are free.  run() opens the sweep's window; the caller closes it (Sweep::finish).  Declare the pipeline
+// before the Rings it guards, so that its events outlive them.
+struct StepPipeline {
+  Events ev_in, ev_done;
+  explicit StepPipeline(long nsteps) : ev_in((size_t) nsteps), ev_done((size_t) nsteps) {}
+
+  template <class Fetch, class Apply>
+  void run(Sweep& sw, Fetch&& fetch, Apply&& apply) {
+    const long nsteps = (long) ev_in.v.size();
+    auto fetch_step = [&](long s) {
+      wait_ring_free(sw.s_comm, ev_done, s);
+      fetch(s, (int) (s % kBuf));
+      DLAF_HIP_CHECK(hipEventRecord(ev_in[(size_t) s], sw.s_comm));
+    };
+    sw.begin(true);
+    if (nsteps > 0)
+      fetch_step(0);
+    for (long s = 0; s < nsteps; ++s) {
+      if (s + 1 < nsteps)
+        fetch_step(s + 1);
+      DLAF_HIP_CHECK(hipStreamWaitEvent(sw.s_main, ev_in[(size_t) s], 0));
+      apply(s);
+      DLAF_HIP_CHECK(hipEventRecord(ev_done[(size_t) s], sw.s_main));
+    }
+  }
+};
+
 // ---- scalars of the device element types (host side) ------------------------------------------------------
 template <class T>
 T conj_of(T v) {
@@ -149,7 +197,8 @@ void check_t_aligned(const TileMatrix<T>& Td, const TileMatrix<T>& Bd, const cha
 
 // Owns its workspaces (a ring each of [T_kk | W_k], of the T column panel as the update's second operand -- one tile
 // per local column of Bd --, and of its staging for the crossed shape), the events ev_t[s] it records on s_comm once
-// the operands of step s are in place, and the operands top[s] themselves.
+// the operands of step s are in place, and the operands top[s] themselves.  fetch(s) fills the buffers s % kBuf: its
+// caller states the ring-reuse wait first (wait_ring_free, or the StepPipeline that calls it).
 template <class T>
 struct TOperandFetch {
   TileMatrix<T>& Td;
@@ -158,7 +207,6 @@ struct TOperandFetch {
   bool upper;      // T upper triangular: the columns beyond k are j < k
   bool backward;   // step s works on column nt - 1 - s (else s)
   hipStream_t s_comm;
-  const Events& ev_free;    // ev_free[s]: the kernels of step s are done with its buffers
   const T* const* winv_of;  // winv_of[k]: the inverted blocks of the diagonal tile k, where this process owns it
   size_t winv_elems;        // their size (0, winv_of == nullptr: the sweep uses none)
   const bool dist, aligned;
@@ -167,9 +215,9 @@ struct TOperandFetch {
   std::vector<TOperand<T>> top;
 
   TOperandFetch(TileMatrix<T>& Td_, TileMatrix<T>& Bd_, Transport* tr_, bool upper_, bool backward_, hipStream_t s_comm_,
-                const Events& ev_free_, const T* const* winv_of_ = nullptr, size_t winv_elems_ = 0)
-      : Td(Td_), Bd(Bd_), tr(tr_), upper(upper_), backward(backward_), s_comm(s_comm_), ev_free(ev_free_),
-        winv_of(winv_of_), winv_elems(winv_elems_), dist(Bd_.grid->nranks > 1), aligned(Td_.row_dim() == Bd_.col_dim()),
+                const T* const* winv_of_ = nullptr, size_t winv_elems_ = 0)
+      : Td(Td_), Bd(Bd_), tr(tr_), upper(upper_), backward(backward_), s_comm(s_comm_), winv_of(winv_of_),
+        winv_elems(winv_elems_), dist(Bd_.grid->nranks > 1), aligned(Td_.row_dim() == Bd_.col_dim()),
         diag_ws(Bd_.tile_elems + winv_elems_, true), tpanel((size_t) Bd_.ltc * Bd_.tile_elems, dist),
         tstage((size_t) Td_.ltr * Bd_.tile_elems, dist && !aligned), ev_t((size_t) Bd_.cols.nt()),
         top((size_t) Bd_.cols.nt()) {}
@@ -189,9 +237,6 @@ struct TOperandFetch {
     // local columns of Bd beyond k
     o.jl0 = upper ? 0 : Bd.cols.next_local(k + 1);
     o.jl1 = upper ? Bd.cols.next_local(k) : Bd.ltc;
-    // these buffers were last read by the kernels of step s - kBuf (event recorded before this call is made)
-    if (s >= kBuf)
-      DLAF_HIP_CHECK(hipStreamWaitEvent(s_comm, ev_free[(size_t) (s - kBuf)], 0));
 
     // (1) T_kk (and its inverted diagonal blocks) to every process holding column k of Bd
     const bool own_diag = Td.rows.mine(k) && Td.cols.mine(k);
@@ -328,6 +373,42 @@ int bcast_transposed_panel_whole(Transport* tr, CommAxis ax, const Axis& have, c
   }
   tr->group_end();
   return issued;
+}
+
+// A panel of tiles as a kernel reads it: tile j at base + (j % period) * ts2 + (j / period) * ts (period 1: base + j * ts)
+template <class T>
+struct Panel {
+  const T* base = nullptr;
+  long ts = 0, ts2 = 0;
+  int period = 1;
+};
+template <class T>
+struct PanelPair {
+  Panel<T> row, col;
+};
+
+// Tile column l of M for both sides of a step, on s_comm: `row`, the column as it is spread over `have` (M's rows) -- the
+// tiles of my local tile rows, through bcast_view_column into rbuf --, and `col`, its whole transposed panel -- the tiles
+// of every local tile of `want`, down the process columns into cbuf (bcast_transposed_panel_whole).
+template <class T>
+PanelPair<T> bcast_column_and_transposed_panel(Transport* tr, const TileMatrix<T>& M, long l, const Axis& have,
+                                               const Axis& want, T* rbuf, T* cbuf, hipStream_t s_comm) {
+  const size_t te = M.tile_elems;
+  PanelPair<T> p;
+  p.row.base = bcast_view_column(tr, M, l, rbuf, s_comm);
+  p.row.ts = (long) te;
+  if (have.P > 1) {
+    (void) bcast_transposed_panel_whole(tr, CommAxis::Col, have, want, p.row.base, cbuf, te, s_comm, p.col.period,
+                                        p.col.ts2);
+    p.col.base = cbuf;
+    p.col.ts = (long) te;
+  }
+  else {
+    // no hop: I hold every tile row of the panel, the tile of global row gj sits at local row gj
+    p.col.base = p.row.base + (size_t) want.shift() * te;
+    p.col.ts = (long) te * want.P;
+  }
+  return p;
 }
 
 // ---- drivers ----------------------------------------------------------------------------------------------

@@ -86,6 +86,9 @@ void rccl_get_unique_id(void* out128);
 // creates the lazily-built host transport of a grid and, when the grid's communication log is on, wraps the
 // transport with the recorder; idempotent.  Returns the transport (null for a 1x1 grid without communicators).
 Transport* grid_transport(Grid& g);
+// The opening of an entry that may communicate: initialises the runtime (idempotent), then grid_transport; a grid of
+// more than one process without a transport is fatal.  Returns the transport (null on one process).
+Transport* checked_transport(Grid& g);
 // One status word for the whole grid from every rank's own (collective; a one-process grid returns `info`): the
 // SMALLEST positive LAPACK index wins -- ranks that did not see the failing tile keep computing on the garbage it
 // broadcast and may flag a later pivot of their own --, and the scheduling-failure code wins over everything.

@@ -200,6 +200,14 @@ Transport* grid_transport(Grid& g) {
   return g.transport.get();
 }
 
+Transport* checked_transport(Grid& g) {
+  runtime_init();
+  Transport* tr = grid_transport(g);
+  if (g.nranks > 1 && !tr)
+    fatal("[dlaf_mi355x] grid with %d ranks has no transport\n", g.nranks);
+  return tr;
+}
+
 int agree_on_info(Grid& g, int info) {
   if (g.nranks > 1 && g.transport) {
     // v[0] carries the LAPACK index (MAX of 2^31 - info = MIN of info), v[1] the scheduling failure

@@ -324,8 +324,7 @@ int tridiag_solver_host(long n, int nb, const R* d, const R* e, R* w, R* z, long
   if (n <= 0)
     return 0;
   const long k = end - begin;
-  hipStream_t s;
-  DLAF_HIP_CHECK(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
+  ScratchStream s;
   PoolScope ws;
   R *dd, *de;
   upload_tridiag(ws, n, d, e, dd, de, s);
@@ -337,8 +336,6 @@ int tridiag_solver_host(long n, int nb, const R* d, const R* e, R* w, R* z, long
     DLAF_HIP_CHECK(hipMemcpy2DAsync(z, (size_t) ldz * sizeof(R), dz, (size_t) n * sizeof(R), (size_t) n * sizeof(R), (size_t) k,
                                     hipMemcpyDeviceToHost, s));
   DLAF_HIP_CHECK(hipStreamSynchronize(s));
-  ws.release();
-  DLAF_HIP_CHECK(hipStreamDestroy(s));
   return r;
 }
 

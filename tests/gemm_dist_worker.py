@@ -1,8 +1,11 @@
 """Worker of the distributed general multiplication test (tests/test_gpu_general_multiplication_grid.py): one process
 per rank, every rank drives the same GPU through the host-staged transport over gloo (the pattern of dist_worker.py).
-C = beta C + alpha A B (NoTrans x NoTrans, the SUMMA sweep) on exact operands -- integer entries in [-3, 3], k = 170 --
+C = beta C + alpha A B (NoTrans x NoTrans, the SUMMA sweep) on exact operands -- integer entries in [-3, 3]; k = 170
+(three k tiles at nb = 64) and k = 390 (2 kBuf + 1 = 7 k tiles with a ragged last one: the sweep's ring of kBuf = 3 operand
+buffers is reused twice, so the wait that guards the reuse runs; the sums stay below 4 * 9 * 390, exact in fp64) --
 through the host entry and the resident one; every rank compares its local part of C with equality and checks that its
 parts of A and B did not change."""
+import itertools
 import os
 import sys
 
@@ -33,7 +36,7 @@ def main():
         return bool(cond)
 
     ok = True
-    m, n, k, nb = 200, 150, 170, 64
+    m, n, nb = 200, 150, 64
     r1, c1 = nprow - 1, npcol - 1
     # (source of C, column source of A, row source of B): A starts on C's process row, B on C's process column; the
     # last set has A's columns and B's rows start on different processes wherever the grid has room for it
@@ -41,7 +44,7 @@ def main():
     for t in ("d", "z"):
         dt = DT[t]
         alpha, beta = scalars(t)
-        for (ci, cj), aj, bi in sources:
+        for k, ((ci, cj), aj, bi) in itertools.product((170, 390), sources):
             rng = np.random.default_rng(41)  # the same global operands on every rank
             a, b, c0 = integers(rng, t, (m, k)), integers(rng, t, (k, n)), integers(rng, t, (m, n))
             want = reference(t, "N", "N", alpha, a, b, beta, c0).astype(dt)
@@ -49,7 +52,7 @@ def main():
             lb = np.asfortranarray(oracle.scatter(b, nb, nprow, npcol, bi, cj, extra_ld=2)[me])
             lc = np.asfortranarray(oracle.scatter(c0, nb, nprow, npcol, ci, cj, extra_ld=3)[me])
             lw = np.asfortranarray(oracle.scatter(want, nb, nprow, npcol, ci, cj)[me])
-            tag = f"{t} C@({ci},{cj}) A@({ci},{aj}) B@({bi},{cj}) grid {nprow}x{npcol}"
+            tag = f"{t} k {k} C@({ci},{cj}) A@({ci},{aj}) B@({bi},{cj}) grid {nprow}x{npcol}"
             la_in, lb_in, lc_in = la.copy(order="F"), lb.copy(order="F"), lc.copy(order="F")
             dlaf.general_multiplication(grid, "N", "N", alpha, la, lb, beta, lc, nb, m=m, n=n, k=k, a_src=(ci, aj),
                                         b_src=(bi, cj), c_src=(ci, cj))

@@ -2,9 +2,12 @@
 process per rank, every rank drives the same GPU through the host-staged transport over gloo (the pattern of
 dist_worker.py).  Trans N (the SUMMA sweep with the transposed-panel broadcast) on exact operands -- integer entries in
 [-3, 3], n = 5 nb + 3 at nb = 32 (on 2 x 3 the transposed panel has more than one class per root row and a ragged last
-tile row), k = 72 (three k tiles) -- for d and z, both updates, both uplo, zero and non-zero source processes, through the
-host entry and the resident one; every rank compares its local part of the triangle with equality and its part of the
-other triangle, filled with NaN, bit for bit, and checks that its parts of A and B did not change."""
+tile row), k = 72 (three k tiles) -- for d and z, both updates, both uplo, zero and non-zero source processes, and once
+more per type and update (uplo U, the non-zero sources) with k = 200: 2 kBuf + 1 = 7 k tiles with a ragged last one, so
+that the sweep's ring of kBuf = 3 operand buffers is reused twice and the wait that guards the reuse runs (the sums stay
+below 2 * 4 * 9 * 200, exact in fp64) -- through the host entry and the resident one; every rank compares its local part
+of the triangle with equality and its part of the other triangle, filled with NaN, bit for bit, and checks that its parts
+of A and B did not change."""
 import os
 import sys
 
@@ -36,7 +39,7 @@ def main():
 
     ok = True
     nb = 32
-    n, k = 5 * nb + 3, 72
+    n = 5 * nb + 3
     r1, c1 = nprow - 1, npcol - 1
     # (source of C, column source of A and B): A starts on C's process row; its columns elsewhere where there is room
     sources = [((0, 0), 0), ((r1, c1), c1 - 1 if npcol > 2 else c1)]
@@ -44,8 +47,8 @@ def main():
         dt = DT[t]
         for two in (False, True):
             alpha, beta = scalars(t, two)
-            for uplo in ("L", "U"):
-                for (ci, cj), aj in sources:
+            for uplo, k, srcs in (("L", 72, sources), ("U", 72, sources), ("U", 6 * nb + 8, sources[1:])):
+                for (ci, cj), aj in srcs:
                     rng = np.random.default_rng(71)  # the same global operands on every rank
                     a, b, c0 = operands(integers, rng, t, "N", n, k)
                     tri = in_triangle(uplo, n)
@@ -56,7 +59,7 @@ def main():
                     lc = np.asfortranarray(oracle.scatter(c_in, nb, nprow, npcol, ci, cj, extra_ld=3)[me])
                     lw = np.asfortranarray(oracle.scatter(want, nb, nprow, npcol, ci, cj)[me])
                     lt = np.asfortranarray(oracle.scatter(tri.astype(np.float64), nb, nprow, npcol, ci, cj)[me]) != 0
-                    tag = f"{t} {'her2k' if two else 'herk'} uplo {uplo} C@({ci},{cj}) A@({ci},{aj}) grid {nprow}x{npcol}"
+                    tag = f"{t} {'her2k' if two else 'herk'} uplo {uplo} k {k} C@({ci},{cj}) A@({ci},{aj}) grid {nprow}x{npcol}"
                     la_in, lb_in, lc_in = la.copy(order="F"), lb.copy(order="F"), lc.copy(order="F")
 
                     def check(got, what):

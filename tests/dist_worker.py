@@ -443,6 +443,24 @@ def main():
                     if not good:
                         print(f"[dist_worker] gen_to_std random FAILED {t}{uplo} n={n} nb={nb}: max diff {md} tol {tol}", flush=True)
                     ok &= bool(good)
+                # the same sizes on operands with real off-diagonal coupling, every element of the triangle against the
+                # wide-precision reference at roundoff level (tests/hegst_cases.py); a non-zero source rank on the first
+                import hegst_cases as hc
+                sr, sc = (max(0, nprow - 1), min(1, npcol - 1)) if t == "d" else (0, 0)
+                case = hc.coupled_case(t, n, hc.seed_of(n))
+                fac_in = hc.factor_operand(case, uplo)
+                la = np.asfortranarray(oracle.scatter(hc.a_operand(case, uplo), nb, nprow, npcol, sr, sc, extra_ld=1)[(grid.myrow, grid.mycol)])
+                lf = np.asfortranarray(oracle.scatter(fac_in, nb, nprow, npcol, sr, sc)[(grid.myrow, grid.mycol)])
+                lf0 = lf.copy(order="F")
+                ok &= said(dlaf.generalized_to_standard(grid, uplo, la, lf, nb, sr, sc, n=n) == 0,
+                           f"generalized_to_standard == 0, coupled {t}{uplo} n={n} nb={nb}")
+                ok &= said(hc.same_bits(lf, lf0), f"the factor is unchanged, coupled {t}{uplo} n={n} nb={nb}")
+                got = gather_global(la, grid, n, nb, sr, sc, oracle)
+                if rank == 0:
+                    good, msg = hc.verdict(got, case, uplo, nb, hc.rho_ref(oracle, case, uplo, nb), f"grid {nprow}x{npcol} src=({sr},{sc})")
+                    if not good:
+                        print(f"[dist_worker] gen_to_std coupled FAILED {msg}", flush=True)
+                    ok &= bool(good)
             lap("gen_to_std")
             # reduction_to_band + bt_reduction_to_band on the grid: the reference's distributed test
             # (test_reduction_to_band.cpp:405-489 -- its size lists on the 6-rank grids, checkResult: Q B Q^H == A within

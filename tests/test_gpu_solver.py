@@ -6,6 +6,8 @@ import itertools
 import numpy as np
 import pytest
 
+import solver_cases as sc
+
 pytestmark = pytest.mark.gpu
 
 TYPES = ["s", "d", "c", "z"]
@@ -108,6 +110,26 @@ def test_triangular_solver_random_vs_oracle(dlaf, grid, oracle, t):
         tol = 40 * (m + 1) * err_of(oracle, t)
         ok, md = oracle.check_near(ref, got, tol, tol)
         assert ok, (md, tol, m, n, nb, side, uplo, op, diag)
+
+
+@pytest.mark.parametrize("t", TYPES)
+def test_triangular_solver_uniform_componentwise_bound(dlaf, grid, t):
+    """Operands whose off-diagonal tiles carry weight (tests/solver_cases.py: diagonal magnitude in [1, 2], the rest of the
+    triangle uniform(-1, 1) / 8, -9.9 in the other triangle), every side / uplo / op / diag at (260, 200, 64) and
+    (190, 321, 128), against the component-wise residual bound |R_j| <= c (K_j + 67) u G_j (|W_j|^H |L_jj|^H) of the
+    whole solve.  With a / na + 2 I and the absolute tolerance 40 (m + 1) err of the random cases above a solve that drops
+    a whole off-diagonal tile passes in complex float; here it is orders above 1 (tests/test_solver_cases.py)."""
+    alpha = sc.alpha_of(t)
+    worst = 0.0
+    for (m, n, nb), side, uplo, op, diag in sc.VARIANTS:
+        a, b = sc.triangle(t, m if side == "L" else n, uplo), sc.rhs(t, m, n)
+        a_io, got = a.copy(order="F"), b.copy(order="F")
+        dlaf.triangular_solver(grid, side, uplo, op, diag, alpha, a_io, got, nb)
+        assert a_io.tobytes() == a.tobytes(), "the triangular operand changed"
+        r, where = sc.residual_ratio(t, side, uplo, op, diag, alpha, a, b, got)
+        assert r <= 1, (t, m, n, nb, side, uplo, op, diag, r, where)
+        worst = max(worst, r)
+    print(f"{t}: max |residual| / bound over {len(sc.VARIANTS)} solves = {worst:.3f}")
 
 
 def test_pdtrsm_after_pdpotrf_solves_the_system(dlaf, grid, oracle):

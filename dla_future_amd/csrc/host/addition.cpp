@@ -207,29 +207,27 @@ void addition_last_profile(double* ms, double* bytes) {
 }
 
 template <class T>
-int general_addition_host(Grid* g, char uplo, char op, T alpha, const T* a, long lda, int a_isrc, int a_jsrc, T beta, T* c,
-                          long ldc, long m, long n, int nb, int c_isrc, int c_jsrc) {
-  if (m == 0 || n == 0)
+int general_addition_host(Grid* g, char uplo, char op, T alpha, HostOperand<const T> a, T beta, HostOperand<T> c) {
+  if (c.m == 0 || c.n == 0)
     return 0;
   const bool use_a = !is_zero(alpha);
   if (!use_a && is_one(beta))
     return 0;  // quick return: nothing is touched
   (void) checked_transport(*g);
   const int mask = mask_of_uplo(uplo);
-  const bool tn = op_is_n(op);
   ScratchStream s;  // before the matrices: destroyed after them
   TileMatrix<T> Ad, Cd;
-  Cd.create(g, false, m, n, nb, c_isrc, c_jsrc);
+  Cd.create(g, false, c.m, c.n, c.nb, c.isrc, c.jsrc);
   if (use_a) {
-    Ad.create(g, false, tn ? m : n, tn ? n : m, nb, a_isrc, a_jsrc);
-    Ad.upload(a, lda, false, false, T{}, s);
+    Ad.create(g, false, a.m, a.n, c.nb, a.isrc, a.jsrc);
+    Ad.upload(a.p, a.ld, false, false, T{}, s);
   }
   // beta = 0: the part of C is not read; what lies outside the part travels there and back unchanged
   if (!is_zero(beta) || mask != kGeaddAll)
-    Cd.upload(c, ldc, false, false, T{}, s);
+    Cd.upload(c.p, c.ld, false, false, T{}, s);
   s.sync();
   addition_canonical<T>(Cd, use_a ? &Ad : nullptr, op, mask, alpha, beta);
-  Cd.download(c, ldc, false, s);
+  Cd.download(c.p, c.ld, false, s);
   s.sync();
   return 0;
 }
@@ -256,17 +254,17 @@ int general_addition_device(char uplo, char op, const void* alpha, MatrixBase* a
 }
 
 template <class T>
-int hermitian_complete_host(Grid* g, char uplo, char kind, T* a, long lda, long n, int nb, int isrc, int jsrc) {
-  if (n == 0)
+int hermitian_complete_host(Grid* g, char uplo, char kind, HostOperand<T> a) {
+  if (a.n == 0)
     return 0;
   (void) checked_transport(*g);
   ScratchStream s;  // before the matrices: destroyed after them
   TileMatrix<T> Ad;
-  Ad.create(g, false, n, n, nb, isrc, jsrc);
-  Ad.upload(a, lda, false, false, T{}, s);
+  Ad.create(g, false, a.n, a.n, a.nb, a.isrc, a.jsrc);
+  Ad.upload(a.p, a.ld, false, false, T{}, s);
   s.sync();
   complete_canonical<T>(Ad, uplo_is_upper(uplo), kind == 'H' || kind == 'h');
-  Ad.download(a, lda, false, s);
+  Ad.download(a.p, a.ld, false, s);
   s.sync();
   return 0;
 }
@@ -361,10 +359,9 @@ int matrix_from_general(MatrixBase* m, MatrixBase* gm) {
   });
 }
 
-#define DLAF_ADDITION_INST(T)                                                                                          \
-  template int general_addition_host<T>(Grid*, char, char, T, const T*, long, int, int, T, T*, long, long, long, int, int, \
-                                        int);                                                                          \
-  template int hermitian_complete_host<T>(Grid*, char, char, T*, long, long, int, int, int);
+#define DLAF_ADDITION_INST(T)                                                                               \
+  template int general_addition_host<T>(Grid*, char, char, T, HostOperand<const T>, T, HostOperand<T>);     \
+  template int hermitian_complete_host<T>(Grid*, char, char, HostOperand<T>);
 DLAF_ADDITION_INST(float)
 DLAF_ADDITION_INST(double)
 DLAF_ADDITION_INST(cfloat)

@@ -9,6 +9,8 @@
 
 #include <dlaf_c/desc.h>
 
+#include "host_operand.hpp"
+
 namespace dlaf_mi355x {
 
 [[noreturn]] void fatal(const char* fmt, ...);
@@ -77,23 +79,83 @@ inline void require_band(const char* who, int band, int nb) {
     fatal("[dlaf_mi355x] %s: band_size %d must be >= 2 and divide the block size %d\n", who, band, nb);
 }
 
-// ---- general multiplication  C = beta C + alpha op(A) op(B): one judgement for the descriptor entries and the resident
-// one.  Every operand as (rows, columns, row block, column block, source process) of the matrix AS STORED.
-struct GemmOperand {
-  long m, n;
-  int mb, nb;
-  int isrc, jsrc;
-};
-inline GemmOperand gemm_operand(const DLAF_descriptor& d) {
+// ---- the Level-3 families: one judgement each for the descriptor entries, the p? entries and the resident ones.  Every
+// operand as an OperandDesc (host_operand.hpp) of the matrix AS STORED; a HostOperand is one.
+inline OperandDesc operand_desc(const DLAF_descriptor& d) {
   return {d.m, d.n, d.mb, d.nb, d.isrc, d.jsrc};
 }
 inline bool is_notrans(char c) { return in_set(c, "Nn"); }
+
+// ---- triangular solver / multiplication  B = alpha op(A)^-1 B, alpha op(A) B (side L) / the same from the right: a the
+// triangular matrix, b the m x n matrix that is overwritten; a_stored: the triangle a resident A holds (0: A is a host
+// array).  Terminates unless: the four letters are letters; A is square with one square block; A's order is B's rows
+// (side L) / columns (side R); B's block along the triangular dimension is A's (util_matrix.h:123-143; the other one is
+// free: the device tiles stay square, the free dimension is re-cut locally, tile_matrix.hpp create_rhs); every source
+// inside the grid; a resident A holds the uplo triangle; A and a non-empty B start on the same process along the
+// triangular dimension.
+template <class GridT>
+void require_triangular(const char* who, const GridT& g, char side, char uplo, char op, char diag, const OperandDesc& a,
+                        const OperandDesc& b, char a_stored = 0) {
+  if (!is_side(side) || !is_uplo(uplo) || !is_op(op) || !is_diag(diag))
+    fatal("[dlaf_mi355x] %s: bad side/uplo/op/diag '%c' '%c' '%c' '%c'\n", who, side, uplo, op, diag);
+  if (a.m != a.n || a.mb != a.nb || a.nb < 1)
+    fatal("[dlaf_mi355x] %s: A must be square with square blocks (%ld x %ld, %d x %d)\n", who, a.m, a.n, a.mb, a.nb);
+  const bool left = is_left(side);
+  if (b.m < 0 || b.n < 0 || a.m != (left ? b.m : b.n))
+    fatal("[dlaf_mi355x] %s: A is %ld x %ld, B is %ld x %ld (side %c)\n", who, a.m, a.n, b.m, b.n, side);
+  if ((left ? b.mb : b.nb) != a.nb || b.mb < 1 || b.nb < 1)
+    fatal("[dlaf_mi355x] %s: B's blocks (%d x %d) do not match A's (%d x %d) for side %c\n", who, b.mb, b.nb, a.mb, a.nb,
+          side);
+  for (const OperandDesc* o : {&a, &b})
+    if (!source_in_grid(g.nprow, g.npcol, o->isrc, o->jsrc))
+      fatal("[dlaf_mi355x] source rank (%d,%d) outside the %d x %d grid\n", o->isrc, o->jsrc, g.nprow, g.npcol);
+  if (a_stored != 0 && is_upper(a_stored) != is_upper(uplo))
+    fatal("[dlaf_mi355x] %s: uplo '%c' but the resident matrix holds its '%c' triangle\n", who, uplo, a_stored);
+  if (b.m > 0 && b.n > 0 && (left ? (a.isrc != b.isrc) : (a.jsrc != b.jsrc)))
+    fatal("[dlaf_mi355x] %s: A and B must share the source process along the triangular dimension\n", who);
+}
+
+// ---- Hermitian multiplication  C = beta C + alpha A B (side L) / beta C + alpha B A (side R), A Hermitian in its uplo
+// triangle (dlaf::hermitian_multiplication, include/dlaf/multiplication/hermitian.h, and this build's own conditions, the
+// solver's); a_stored as above.  Terminates unless: side and uplo are letters; A is square with one square block; B has
+// C's shape and blocks; A's order is C's rows (side L) / columns (side R) and C's block along that dimension is A's;
+// every source inside the grid; a resident A holds the uplo triangle; B starts on C's process, and A on a non-empty C's
+// along A's dimension.
+template <class GridT>
+void require_hermitian_multiplication(const char* who, const GridT& g, char side, char uplo, const OperandDesc& a,
+                                      const OperandDesc& b, const OperandDesc& c, char a_stored = 0) {
+  if (!is_side(side) || !is_uplo(uplo))
+    fatal("[dlaf_mi355x] %s: bad side/uplo '%c' '%c'\n", who, side, uplo);
+  if (a.m != a.n || a.mb != a.nb || a.nb < 1)
+    fatal("[dlaf_mi355x] %s: A must be square with square blocks (%ld x %ld, %d x %d)\n", who, a.m, a.n, a.mb, a.nb);
+  const bool left = is_left(side);
+  if (c.m < 0 || c.n < 0 || b.m != c.m || b.n != c.n || b.mb != c.mb || b.nb != c.nb)
+    fatal("[dlaf_mi355x] %s: B (%ld x %ld, blocks %d x %d) and C (%ld x %ld, blocks %d x %d) differ\n", who, b.m, b.n, b.mb,
+          b.nb, c.m, c.n, c.mb, c.nb);
+  if (a.m != (left ? c.m : c.n))
+    fatal("[dlaf_mi355x] %s: A is %ld x %ld, B and C are %ld x %ld (side %c)\n", who, a.m, a.n, c.m, c.n, side);
+  if ((left ? c.mb : c.nb) != a.nb || c.mb < 1 || c.nb < 1)
+    fatal("[dlaf_mi355x] %s: the blocks of B and C (%d x %d) do not match A's (%d x %d) for side %c\n", who, c.mb, c.nb,
+          a.mb, a.nb, side);
+  for (const OperandDesc* o : {&a, &b, &c})
+    if (!source_in_grid(g.nprow, g.npcol, o->isrc, o->jsrc))
+      fatal("[dlaf_mi355x] %s: source rank (%d,%d) outside the %d x %d grid\n", who, o->isrc, o->jsrc, g.nprow, g.npcol);
+  if (a_stored != 0 && is_upper(a_stored) != is_upper(uplo))
+    fatal("[dlaf_mi355x] %s: uplo '%c' but the resident matrix holds its '%c' triangle\n", who, uplo, a_stored);
+  if (b.isrc != c.isrc || b.jsrc != c.jsrc)
+    fatal("[dlaf_mi355x] %s: B and C must share the source process ((%d,%d) vs (%d,%d))\n", who, b.isrc, b.jsrc, c.isrc,
+          c.jsrc);
+  if (c.m > 0 && c.n > 0 && (left ? (a.isrc != c.isrc) : (a.jsrc != c.jsrc)))
+    fatal("[dlaf_mi355x] %s: A must share the source process of B and C along A's dimension\n", who);
+}
+
+// ---- general multiplication  C = beta C + alpha op(A) op(B)
 // Terminates unless: both ops are letters; one square block for the three matrices; op(A) is m x k, op(B) k x n for C's
 // m x n; every source inside the grid; on a grid of more than one process both ops are 'N' (the transposed forms need
 // the two-hop transposed-panel broadcast, which is not built), A starts on C's process row and B on C's process column.
 template <class GridT>
-void require_general_multiplication(const char* who, const GridT& g, char opa, char opb, const GemmOperand& a,
-                                    const GemmOperand& b, const GemmOperand& c) {
+void require_general_multiplication(const char* who, const GridT& g, char opa, char opb, const OperandDesc& a,
+                                    const OperandDesc& b, const OperandDesc& c) {
   if (!is_op(opa) || !is_op(opb))
     fatal("[dlaf_mi355x] %s: bad opa/opb '%c' '%c'\n", who, opa, opb);
   if (a.mb != a.nb || b.mb != b.nb || c.mb != c.nb || a.nb != c.nb || b.nb != c.nb || c.nb < 1)
@@ -104,7 +166,7 @@ void require_general_multiplication(const char* who, const GridT& g, char opa, c
   if (c.m < 0 || c.n < 0 || ak < 0 || am != c.m || bn != c.n || ak != bk)
     fatal("[dlaf_mi355x] %s: op(A) is %ld x %ld (op '%c'), op(B) is %ld x %ld (op '%c'), C is %ld x %ld\n", who, am, ak,
           opa, bk, bn, opb, c.m, c.n);
-  for (const GemmOperand* o : {&a, &b, &c})
+  for (const OperandDesc* o : {&a, &b, &c})
     if (!source_in_grid(g.nprow, g.npcol, o->isrc, o->jsrc))
       fatal("[dlaf_mi355x] %s: source rank (%d,%d) outside the %d x %d grid\n", who, o->isrc, o->jsrc, g.nprow, g.npcol);
   if (g.nprow * g.npcol > 1 && (!is_notrans(opa) || !is_notrans(opb)))
@@ -124,8 +186,8 @@ void require_general_multiplication(const char* who, const GridT& g, char opa, c
 // triangle; on a grid of more than one process trans is 'N' (the transposed forms need the two-hop transposed-panel
 // broadcast of A's ROWS, which is not built) and A starts on C's process row.
 template <class GridT>
-void require_rank_update(const char* who, const GridT& g, bool complex_type, char uplo, char trans, const GemmOperand& a,
-                         const GemmOperand* b, const GemmOperand& c, char c_stored = 0) {
+void require_rank_update(const char* who, const GridT& g, bool complex_type, char uplo, char trans, const OperandDesc& a,
+                         const OperandDesc* b, const OperandDesc& c, char c_stored = 0) {
   if (!is_uplo(uplo) || !is_op(trans))
     fatal("[dlaf_mi355x] %s: bad uplo/trans '%c' '%c'\n", who, uplo, trans);
   if (complex_type && in_set(trans, "Tt"))
@@ -142,7 +204,7 @@ void require_rank_update(const char* who, const GridT& g, bool complex_type, cha
           "differ\n", who, a.m, a.n, a.mb, a.nb, a.isrc, a.jsrc, b->m, b->n, b->mb, b->nb, b->isrc, b->jsrc);
   if (a.mb != a.nb || c.mb != c.nb || a.nb != c.nb || c.nb < 1)
     fatal("[dlaf_mi355x] %s: the operands need one square block (A %d x %d, C %d x %d)\n", who, a.mb, a.nb, c.mb, c.nb);
-  for (const GemmOperand* o : {&a, &c})
+  for (const OperandDesc* o : {&a, &c})
     if (!source_in_grid(g.nprow, g.npcol, o->isrc, o->jsrc))
       fatal("[dlaf_mi355x] %s: source rank (%d,%d) outside the %d x %d grid\n", who, o->isrc, o->jsrc, g.nprow, g.npcol);
   if (c_stored != 0 && is_upper(c_stored) != is_upper(uplo))
@@ -161,8 +223,8 @@ void require_rank_update(const char* who, const GridT& g, bool complex_type, cha
 // local: both must hold the same elements); the same storage twice only with op N.
 inline bool is_part(char c) { return in_set(c, "AaLlUu"); }
 template <class GridT>
-void require_general_addition(const char* who, const GridT& g, char uplo, char op, const GemmOperand& a,
-                              const GemmOperand& c, bool same_storage) {
+void require_general_addition(const char* who, const GridT& g, char uplo, char op, const OperandDesc& a,
+                              const OperandDesc& c, bool same_storage) {
   if (!is_part(uplo) || !is_op(op))
     fatal("[dlaf_mi355x] %s: bad uplo/op '%c' '%c' (uplo is 'A', 'L' or 'U')\n", who, uplo, op);
   if (a.mb != a.nb || c.mb != c.nb || a.nb != c.nb || c.nb < 1)
@@ -170,7 +232,7 @@ void require_general_addition(const char* who, const GridT& g, char uplo, char o
   const bool tn = is_notrans(op);
   if (c.m < 0 || c.n < 0 || (tn ? a.m : a.n) != c.m || (tn ? a.n : a.m) != c.n)
     fatal("[dlaf_mi355x] %s: A is %ld x %ld (op '%c'), C is %ld x %ld\n", who, a.m, a.n, op, c.m, c.n);
-  for (const GemmOperand* o : {&a, &c})
+  for (const OperandDesc* o : {&a, &c})
     if (!source_in_grid(g.nprow, g.npcol, o->isrc, o->jsrc))
       fatal("[dlaf_mi355x] %s: source rank (%d,%d) outside the %d x %d grid\n", who, o->isrc, o->jsrc, g.nprow, g.npcol);
   if (tn && (a.isrc != c.isrc || a.jsrc != c.jsrc))
@@ -180,7 +242,7 @@ void require_general_addition(const char* who, const GridT& g, char uplo, char o
     fatal("[dlaf_mi355x] %s: A and C are the same matrix, which only op 'N' accepts (op '%c')\n", who, op);
 }
 template <class GridT>
-void require_hermitian_complete(const char* who, const GridT& g, char uplo, char kind, const GemmOperand& a) {
+void require_hermitian_complete(const char* who, const GridT& g, char uplo, char kind, const OperandDesc& a) {
   if (!is_uplo(uplo) || !in_set(kind, "HhSs"))
     fatal("[dlaf_mi355x] %s: bad uplo/kind '%c' '%c' (kind is 'H' or 'S')\n", who, uplo, kind);
   if (a.m != a.n || a.n < 0)
@@ -191,8 +253,8 @@ void require_hermitian_complete(const char* who, const GridT& g, char uplo, char
     fatal("[dlaf_mi355x] %s: source rank (%d,%d) outside the %d x %d grid\n", who, a.isrc, a.jsrc, g.nprow, g.npcol);
 }
 // d: the DeviceMatrix as an n x n operand of the caller's matrix; kinds: the letters the direction takes ("" : none)
-inline void require_matrix_conversion(const char* who, char kind, const char* kinds, const GemmOperand& d,
-                                      const GemmOperand& g) {
+inline void require_matrix_conversion(const char* who, char kind, const char* kinds, const OperandDesc& d,
+                                      const OperandDesc& g) {
   if (kinds[0] != 0 && !in_set(kind, kinds))
     fatal("[dlaf_mi355x] %s: bad kind '%c' (one of %s)\n", who, kind, kinds);
   if (g.m != d.m || g.n != d.n || g.mb != d.mb || g.nb != d.nb || g.isrc != d.isrc || g.jsrc != d.jsrc)

@@ -106,12 +106,40 @@ int dlaf_mi355x_gmatrix_download(dlaf_mi355x_gmatrix_t h, void* host, int ld) no
   general_matrix_transfer(h->m.get(), host, ld, false);
   return 0;
 }
+// how the judgements of api_checks.hpp see a resident operand: a general matrix as stored, and the n x n matrix of the
+// caller whose triangle a matrix handle holds (stored: that triangle's letter)
+static OperandDesc general_operand(dlaf_mi355x_gmatrix_t h) {
+  OperandDesc o{};
+  (void) dispatch_api_type(h->m->type, [&](auto* tag) {
+    using DT = std::remove_pointer_t<decltype(tag)>;
+    const auto& gm = static_cast<GeneralMatrix<DT>&>(*h->m);
+    o = OperandDesc{gm.rows_g, gm.cols_g, gm.m.nb, gm.m.nb, gm.isrc, gm.jsrc};
+    return 0;
+  });
+  return o;
+}
+static OperandDesc triangle_operand(dlaf_mi355x_matrix_t h, char* stored = nullptr) {
+  OperandDesc o{};
+  (void) dispatch_api_type(h->m->type, [&](auto* tag) {
+    using DT = std::remove_pointer_t<decltype(tag)>;
+    const auto& dm = static_cast<DeviceMatrix<DT>&>(*h->m);
+    const Axis& srow = dm.transposed ? dm.cols : dm.rows;
+    const Axis& scol = dm.transposed ? dm.rows : dm.cols;
+    o = OperandDesc{dm.n, dm.n, dm.nb, dm.nb, srow.src, scol.src};
+    if (stored)
+      *stored = dm.uplo;
+    return 0;
+  });
+  return o;
+}
+
 int dlaf_mi355x_triangular_solver_device(char side, char uplo, char op, char diag, const void* alpha,
                                          dlaf_mi355x_matrix_t a, dlaf_mi355x_gmatrix_t b) noexcept {
   if (!a || !a->m || !b || !b->m || a->ctx != b->ctx)
     return -1;
-  if (!is_side(side) || !is_uplo(uplo) || !is_op(op) || !is_diag(diag))
-    fatal("[dlaf_mi355x] triangular solver: bad side/uplo/op/diag '%c' '%c' '%c' '%c'\n", side, uplo, op, diag);
+  char stored = 0;
+  const OperandDesc oa = triangle_operand(a, &stored);
+  require_triangular("triangular solver", grid_from_context(a->ctx), side, uplo, op, diag, oa, general_operand(b), stored);
   return triangular_solver_device(side, uplo, op, diag, alpha, a->m.get(), b->m.get());
 }
 // A X = B from the resident factor (p?potrs without leaving HBM): two solves, nothing crosses PCIe in between
@@ -137,8 +165,10 @@ int dlaf_mi355x_triangular_multiplication_device(char side, char uplo, char op, 
                                                  dlaf_mi355x_matrix_t a, dlaf_mi355x_gmatrix_t b) noexcept {
   if (!a || !a->m || !b || !b->m || a->ctx != b->ctx)
     return -1;
-  if (!is_side(side) || !is_uplo(uplo) || !is_op(op) || !is_diag(diag))
-    fatal("[dlaf_mi355x] triangular multiplication: bad side/uplo/op/diag '%c' '%c' '%c' '%c'\n", side, uplo, op, diag);
+  char stored = 0;
+  const OperandDesc oa = triangle_operand(a, &stored);
+  require_triangular("triangular multiplication", grid_from_context(a->ctx), side, uplo, op, diag, oa, general_operand(b),
+                     stored);
   return triangular_multiplication_device(side, uplo, op, diag, alpha, a->m.get(), b->m.get());
 }
 
@@ -147,8 +177,10 @@ int dlaf_mi355x_hermitian_multiplication_device(char side, char uplo, const void
                                                dlaf_mi355x_gmatrix_t c) noexcept {
   if (!a || !a->m || !b || !b->m || !c || !c->m || a->ctx != b->ctx || a->ctx != c->ctx)
     return -1;
-  if (!is_side(side) || !is_uplo(uplo))
-    fatal("[dlaf_mi355x] hermitian multiplication: bad side/uplo '%c' '%c'\n", side, uplo);
+  char stored = 0;
+  const OperandDesc oa = triangle_operand(a, &stored);
+  require_hermitian_multiplication("hermitian multiplication", grid_from_context(a->ctx), side, uplo, oa,
+                                   general_operand(b), general_operand(c), stored);
   return hermitian_multiplication_device(side, uplo, alpha, a->m.get(), b->m.get(), beta, c->m.get());
 }
 
@@ -163,17 +195,8 @@ int dlaf_mi355x_general_multiplication_device(char opa, char opb, const void* al
   if (a->m->type != c->m->type || b->m->type != c->m->type)
     fatal("[dlaf_mi355x] %s: operands of different element types ('%c', '%c', '%c')\n", who, a->m->type, b->m->type,
           c->m->type);
-  auto operand = [](dlaf_mi355x_gmatrix_t h) {
-    GemmOperand o{};
-    (void) dispatch_api_type(h->m->type, [&](auto* tag) {
-      using DT = std::remove_pointer_t<decltype(tag)>;
-      const auto& gm = static_cast<GeneralMatrix<DT>&>(*h->m);
-      o = GemmOperand{gm.rows_g, gm.cols_g, gm.m.nb, gm.m.nb, gm.isrc, gm.jsrc};
-      return 0;
-    });
-    return o;
-  };
-  require_general_multiplication(who, grid_from_context(c->ctx), opa, opb, operand(a), operand(b), operand(c));
+  require_general_multiplication(who, grid_from_context(c->ctx), opa, opb, general_operand(a), general_operand(b),
+                                 general_operand(c));
   return general_multiplication_device(opa, opb, alpha, a->m.get(), b->m.get(), beta, c->m.get());
 }
 
@@ -186,26 +209,9 @@ static int rank_update_device(const char* who, char uplo, char trans, const void
     fatal("[dlaf_mi355x] %s: the operands live on different contexts (A %d, C %d)\n", who, a->ctx, c->ctx);
   if (a->m->type != c->m->type || (her2k && b->m->type != c->m->type))
     fatal("[dlaf_mi355x] %s: operands of different element types (A '%c', C '%c')\n", who, a->m->type, c->m->type);
-  GemmOperand oa{}, ob{}, oc{};
-  char stored = 'L';
-  bool cx = false;
-  (void) dispatch_api_type(c->m->type, [&](auto* tag) {
-    using DT = std::remove_pointer_t<decltype(tag)>;
-    auto operand = [](dlaf_mi355x_gmatrix_t h) {
-      const auto& gm = static_cast<GeneralMatrix<DT>&>(*h->m);
-      return GemmOperand{gm.rows_g, gm.cols_g, gm.m.nb, gm.m.nb, gm.isrc, gm.jsrc};
-    };
-    oa = operand(a);
-    if (her2k)
-      ob = operand(b);
-    const auto& cm = static_cast<DeviceMatrix<DT>&>(*c->m);
-    const Axis& srow = cm.transposed ? cm.cols : cm.rows;
-    const Axis& scol = cm.transposed ? cm.rows : cm.cols;
-    oc = GemmOperand{cm.n, cm.n, cm.nb, cm.nb, srow.src, scol.src};
-    stored = cm.uplo;
-    cx = TypeInfo<DT>::is_complex;
-    return 0;
-  });
+  char stored = 0;
+  const OperandDesc oa = general_operand(a), ob = general_operand(her2k ? b : a), oc = triangle_operand(c, &stored);
+  const bool cx = c->m->type == 'c' || c->m->type == 'z';
   require_rank_update(who, grid_from_context(c->ctx), cx, uplo, trans, oa, her2k ? &ob : nullptr, oc, stored);
   return hermitian_rank_update_device(trans, alpha, a->m.get(), her2k ? b->m.get() : nullptr, beta, c->m.get());
 }
@@ -221,29 +227,6 @@ int dlaf_mi355x_hermitian_rank_2k_update_device(char uplo, char trans, const voi
 
 // general_addition / hermitian_complete on resident general matrices, and the conversions between a DeviceMatrix and a
 // general matrix (addition.cpp)
-static GemmOperand general_operand(dlaf_mi355x_gmatrix_t h) {
-  GemmOperand o{};
-  (void) dispatch_api_type(h->m->type, [&](auto* tag) {
-    using DT = std::remove_pointer_t<decltype(tag)>;
-    const auto& gm = static_cast<GeneralMatrix<DT>&>(*h->m);
-    o = GemmOperand{gm.rows_g, gm.cols_g, gm.m.nb, gm.m.nb, gm.isrc, gm.jsrc};
-    return 0;
-  });
-  return o;
-}
-// the n x n matrix of the caller whose triangle the handle holds
-static GemmOperand triangle_operand(dlaf_mi355x_matrix_t h) {
-  GemmOperand o{};
-  (void) dispatch_api_type(h->m->type, [&](auto* tag) {
-    using DT = std::remove_pointer_t<decltype(tag)>;
-    const auto& dm = static_cast<DeviceMatrix<DT>&>(*h->m);
-    const Axis& srow = dm.transposed ? dm.cols : dm.rows;
-    const Axis& scol = dm.transposed ? dm.rows : dm.cols;
-    o = GemmOperand{dm.n, dm.n, dm.nb, dm.nb, srow.src, scol.src};
-    return 0;
-  });
-  return o;
-}
 int dlaf_mi355x_general_addition_device(char uplo, char op, const void* alpha, dlaf_mi355x_gmatrix_t a, const void* beta,
                                         dlaf_mi355x_gmatrix_t c) noexcept {
   const char* who = "general addition";

@@ -23,41 +23,15 @@
 using namespace dlaf_mi355x;
 
 namespace {
-// Preconditions of the triangular solver and multiplication through descriptors (who names the routine in the
-// messages); they terminate before the GPU is touched.  Returns the grid.
-Grid& triangular_checks(const char* who, int ctx, char side, char uplo, char op, char diag, const DLAF_descriptor& da,
-                        const DLAF_descriptor& db) {
-  if (!is_side(side) || !is_uplo(uplo) || !is_op(op) || !is_diag(diag))
-    fatal("[dlaf_mi355x] %s: bad side/uplo/op/diag '%c' '%c' '%c' '%c'\n", who, side, uplo, op, diag);
-  if (da.i != 0 || da.j != 0 || db.i != 0 || db.j != 0)
-    fatal("[dlaf_mi355x] sub-matrices are not supported: offsets must be 0\n");
-  // preconditions of triangular.h:43-48, :57 / :93-98: A square with square blocks, op(A) and B multipliable
-  if (da.m != da.n || da.mb != da.nb || da.nb < 1)
-    fatal("[dlaf_mi355x] %s: A must be square with square blocks (%d x %d, %d x %d)\n", who, da.m, da.n, da.mb, da.nb);
-  const bool left = is_left(side);
-  if (db.m < 0 || db.n < 0 || da.m != (left ? db.m : db.n))
-    fatal("[dlaf_mi355x] %s: A is %d x %d, B is %d x %d (side %c)\n", who, da.m, da.n, db.m, db.n, side);
-  // multipliable (util_matrix.h:123-143): B's block along the triangular dimension is A's; the other one is free
-  // (the device tiles stay square: the free dimension is re-cut locally, tile_matrix.hpp create_rhs)
-  if ((left ? db.mb : db.nb) != da.nb || db.mb < 1 || db.nb < 1)
-    fatal("[dlaf_mi355x] %s: B's blocks (%d x %d) do not match A's (%d x %d) for side %c\n", who, db.mb, db.nb, da.mb,
-          da.nb, side);
-  Grid& g = grid_from_context(ctx);
-  require_sources(nullptr, g, {&da, &db});
-  if (db.m > 0 && db.n > 0 && (left ? (da.isrc != db.isrc) : (da.jsrc != db.jsrc)))
-    fatal("[dlaf_mi355x] %s: A and B must share the source process along the triangular dimension\n", who);
-  return g;
-}
-
 // The two routines over a triangular A, B = the m x n matrix they overwrite: dlaf::triangular_solver
 // (include/dlaf/solver/triangular.h:41-177) and dlaf::triangular_multiplication
 // (include/dlaf/multiplication/triangular.h), B = alpha op(A) B (side L) / alpha B op(A) (side R).  Same arguments,
-// same preconditions; who names the routine in the messages.
+// same preconditions (triangular.h:43-48, :57 / :93-98: require_triangular); who names the routine in the messages.
 template <class HT>
 struct TriangularOp {
   using DT = typename DevType<HT>::type;
   const char* who;
-  int (*host)(Grid*, char, char, char, char, DT, const DT*, long, int, int, DT*, long, long, long, int, int, int, int);
+  int (*host)(Grid*, char, char, char, char, DT, HostOperand<const DT>, HostOperand<DT>);
 };
 template <class HT>
 constexpr TriangularOp<HT> kTrsm{"triangular solver", &triangular_solver_host<typename DevType<HT>::type>};
@@ -70,12 +44,15 @@ template <class HT>
 int triangular_c(const TriangularOp<HT>& op_, int ctx, char side, char uplo, char op, char diag, const HT* alpha,
                  const HT* a, const DLAF_descriptor& da, HT* b, const DLAF_descriptor& db) {
   using DT = typename DevType<HT>::type;
-  Grid& g = triangular_checks(op_.who, ctx, side, uplo, op, diag, da, db);
-  const bool left = is_left(side);
+  if (da.i != 0 || da.j != 0 || db.i != 0 || db.j != 0)
+    fatal("[dlaf_mi355x] sub-matrices are not supported: offsets must be 0\n");
+  Grid& g = grid_from_context(ctx);
+  const auto oa = host_operand(a, da);
+  const auto ob = host_operand(b, db);
+  require_triangular(op_.who, g, side, uplo, op, diag, oa, ob);
   DT al;
   std::memcpy(&al, alpha, sizeof(DT));
-  return op_.host(&g, side, uplo, op, diag, al, reinterpret_cast<const DT*>(a), da.ld, da.isrc, da.jsrc,
-                  reinterpret_cast<DT*>(b), db.ld, db.m, db.n, da.nb, db.isrc, db.jsrc, left ? db.nb : db.mb);
+  return op_.host(&g, side, uplo, op, diag, al, oa, ob);
 }
 
 // ScaLAPACK p?trsm / p?trmm argument list
@@ -89,49 +66,22 @@ void pxtriangular(const TriangularOp<HT>& op_, char side, char uplo, char op, ch
   (void) triangular_c<HT>(op_, ctx, side, uplo, op, diag, alpha, a, da, b, db);
 }
 
-// Preconditions of dlaf::hermitian_multiplication (include/dlaf/multiplication/hermitian.h) through descriptors, and
-// this build's own (the solver's); they terminate before the GPU is touched.  Returns the grid.
-Grid& hermitian_checks(int ctx, char side, char uplo, const DLAF_descriptor& da, const DLAF_descriptor& db,
-                       const DLAF_descriptor& dc) {
-  const char* who = "hermitian multiplication";
-  if (!is_side(side) || !is_uplo(uplo))
-    fatal("[dlaf_mi355x] %s: bad side/uplo '%c' '%c'\n", who, side, uplo);
-  if (da.i != 0 || da.j != 0 || db.i != 0 || db.j != 0 || dc.i != 0 || dc.j != 0)
-    fatal("[dlaf_mi355x] %s: sub-matrices are not supported: offsets must be 0\n", who);
-  if (da.m != da.n || da.mb != da.nb || da.nb < 1)
-    fatal("[dlaf_mi355x] %s: A must be square with square blocks (%d x %d, %d x %d)\n", who, da.m, da.n, da.mb, da.nb);
-  const bool left = is_left(side);
-  if (dc.m < 0 || dc.n < 0 || db.m != dc.m || db.n != dc.n || db.mb != dc.mb || db.nb != dc.nb)
-    fatal("[dlaf_mi355x] %s: B (%d x %d, blocks %d x %d) and C (%d x %d, blocks %d x %d) differ\n", who, db.m, db.n, db.mb,
-          db.nb, dc.m, dc.n, dc.mb, dc.nb);
-  if (da.m != (left ? dc.m : dc.n))
-    fatal("[dlaf_mi355x] %s: A is %d x %d, B and C are %d x %d (side %c)\n", who, da.m, da.n, dc.m, dc.n, side);
-  if ((left ? dc.mb : dc.nb) != da.nb || dc.mb < 1 || dc.nb < 1)
-    fatal("[dlaf_mi355x] %s: the blocks of B and C (%d x %d) do not match A's (%d x %d) for side %c\n", who, dc.mb, dc.nb,
-          da.mb, da.nb, side);
-  Grid& g = grid_from_context(ctx);
-  require_sources(who, g, {&da, &db, &dc});
-  if (db.isrc != dc.isrc || db.jsrc != dc.jsrc)
-    fatal("[dlaf_mi355x] %s: B and C must share the source process ((%d,%d) vs (%d,%d))\n", who, db.isrc, db.jsrc,
-          dc.isrc, dc.jsrc);
-  if (dc.m > 0 && dc.n > 0 && (left ? (da.isrc != dc.isrc) : (da.jsrc != dc.jsrc)))
-    fatal("[dlaf_mi355x] %s: A must share the source process of B and C along A's dimension\n", who);
-  return g;
-}
-
 // dlaf::hermitian_multiplication through descriptors: C = beta C + alpha A B (side L) / beta C + alpha B A (side R)
 template <class HT>
 int hermitian_multiplication_c(int ctx, char side, char uplo, const HT* alpha, const HT* a, const DLAF_descriptor& da,
                                const HT* b, const DLAF_descriptor& db, const HT* beta, HT* c, const DLAF_descriptor& dc) {
   using DT = typename DevType<HT>::type;
-  Grid& g = hermitian_checks(ctx, side, uplo, da, db, dc);
-  const bool left = is_left(side);
+  const char* who = "hermitian multiplication";
+  if (da.i != 0 || da.j != 0 || db.i != 0 || db.j != 0 || dc.i != 0 || dc.j != 0)
+    fatal("[dlaf_mi355x] %s: sub-matrices are not supported: offsets must be 0\n", who);
+  Grid& g = grid_from_context(ctx);
+  const auto oa = host_operand(a, da), ob = host_operand(b, db);
+  const auto oc = host_operand(c, dc);
+  require_hermitian_multiplication(who, g, side, uplo, oa, ob, oc);
   DT al, be;
   std::memcpy(&al, alpha, sizeof(DT));
   std::memcpy(&be, beta, sizeof(DT));
-  return hermitian_multiplication_host<DT>(&g, side, uplo, al, reinterpret_cast<const DT*>(a), da.ld, da.isrc, da.jsrc,
-                                           reinterpret_cast<const DT*>(b), db.ld, be, reinterpret_cast<DT*>(c), dc.ld, dc.m,
-                                           dc.n, da.nb, dc.isrc, dc.jsrc, left ? dc.nb : dc.mb);
+  return hermitian_multiplication_host<DT>(&g, side, uplo, al, oa, ob, be, oc);
 }
 
 // ScaLAPACK p?symm / p?hemm argument list
@@ -157,14 +107,13 @@ int general_multiplication_c(int ctx, char opa, char opb, const HT* alpha, const
   if (da.i != 0 || da.j != 0 || db.i != 0 || db.j != 0 || dc.i != 0 || dc.j != 0)
     fatal("[dlaf_mi355x] %s: sub-matrices are not supported: offsets must be 0\n", who);
   Grid& g = grid_from_context(ctx);
-  require_general_multiplication(who, g, opa, opb, gemm_operand(da), gemm_operand(db), gemm_operand(dc));
+  const auto oa = host_operand(a, da), ob = host_operand(b, db);
+  const auto oc = host_operand(c, dc);
+  require_general_multiplication(who, g, opa, opb, oa, ob, oc);
   DT al, be;
   std::memcpy(&al, alpha, sizeof(DT));
   std::memcpy(&be, beta, sizeof(DT));
-  const long k = is_notrans(opa) ? da.n : da.m;
-  return general_multiplication_host<DT>(&g, opa, opb, al, reinterpret_cast<const DT*>(a), da.ld, da.isrc, da.jsrc,
-                                         reinterpret_cast<const DT*>(b), db.ld, db.isrc, db.jsrc, be,
-                                         reinterpret_cast<DT*>(c), dc.ld, dc.m, dc.n, k, dc.nb, dc.isrc, dc.jsrc);
+  return general_multiplication_host<DT>(&g, opa, opb, al, oa, ob, be, oc);
 }
 
 // ScaLAPACK p?gemm argument list
@@ -202,15 +151,10 @@ int rank_update_c(int ctx, char uplo, char trans, typename DevType<HT>::type alp
   if (da.i != 0 || da.j != 0 || dc.i != 0 || dc.j != 0 || (db && (db->i != 0 || db->j != 0)))
     fatal("[dlaf_mi355x] %s: sub-matrices are not supported: offsets must be 0\n", who);
   Grid& g = grid_from_context(ctx);
-  GemmOperand ob{};
-  if (db)
-    ob = gemm_operand(*db);
-  require_rank_update(who, g, TypeInfo<DT>::is_complex, uplo, trans, gemm_operand(da), db ? &ob : nullptr,
-                      gemm_operand(dc));
-  const long k = is_notrans(trans) ? da.n : da.m;
-  return hermitian_rank_update_host<DT>(&g, db != nullptr, uplo, trans, alpha, reinterpret_cast<const DT*>(a), da.ld,
-                                        da.isrc, da.jsrc, reinterpret_cast<const DT*>(b), db ? db->ld : 0, beta,
-                                        reinterpret_cast<DT*>(c), dc.ld, dc.n, k, dc.nb, dc.isrc, dc.jsrc);
+  const auto oa = host_operand(a, da), ob = host_operand(b, db ? *db : da);  // (rank-k: ob is never passed on)
+  const auto oc = host_operand(c, dc);
+  require_rank_update(who, g, TypeInfo<DT>::is_complex, uplo, trans, oa, db ? &ob : nullptr, oc);
+  return hermitian_rank_update_host<DT>(&g, uplo, trans, alpha, oa, db ? &ob : nullptr, beta, oc);
 }
 
 // ScaLAPACK p?syrk / p?herk (b null) and p?syr2k / p?her2k argument lists
@@ -240,12 +184,13 @@ int general_addition_c(int ctx, char uplo, char op, const HT* alpha, const HT* a
   if (da.i != 0 || da.j != 0 || dc.i != 0 || dc.j != 0)
     fatal("[dlaf_mi355x] %s: sub-matrices are not supported: offsets must be 0\n", who);
   Grid& g = grid_from_context(ctx);
-  require_general_addition(who, g, uplo, op, gemm_operand(da), gemm_operand(dc), a == c);
+  const auto oa = host_operand(a, da);
+  const auto oc = host_operand(c, dc);
+  require_general_addition(who, g, uplo, op, oa, oc, a == c);
   DT al, be;
   std::memcpy(&al, alpha, sizeof(DT));
   std::memcpy(&be, beta, sizeof(DT));
-  return general_addition_host<DT>(&g, uplo, op, al, reinterpret_cast<const DT*>(a), da.ld, da.isrc, da.jsrc, be,
-                                   reinterpret_cast<DT*>(c), dc.ld, dc.m, dc.n, dc.nb, dc.isrc, dc.jsrc);
+  return general_addition_host<DT>(&g, uplo, op, al, oa, be, oc);
 }
 template <class HT>
 int hermitian_complete_c(int ctx, char uplo, char kind, HT* a, const DLAF_descriptor& da) {
@@ -254,8 +199,9 @@ int hermitian_complete_c(int ctx, char uplo, char kind, HT* a, const DLAF_descri
   if (da.i != 0 || da.j != 0)
     fatal("[dlaf_mi355x] %s: sub-matrices are not supported: offsets must be 0\n", who);
   Grid& g = grid_from_context(ctx);
-  require_hermitian_complete(who, g, uplo, kind, gemm_operand(da));
-  return hermitian_complete_host<DT>(&g, uplo, kind, reinterpret_cast<DT*>(a), da.ld, da.n, da.nb, da.isrc, da.jsrc);
+  const auto oa = host_operand(a, da);
+  require_hermitian_complete(who, g, uplo, kind, oa);
+  return hermitian_complete_host<DT>(&g, uplo, kind, oa);
 }
 
 // PBLAS p?geadd / p?tradd / p?tran* and ScaLAPACK p?lacpy argument lists: C (m x n) = beta C + alpha op(A)
@@ -300,8 +246,7 @@ int gen_to_std_c(int ctx, char uplo, HT* a, const DLAF_descriptor& da, const HT*
           "distributed alike\n", da.m, da.nb, da.isrc, da.jsrc, db.m, db.nb, db.isrc, db.jsrc);
   Grid& g = grid_from_context(ctx);
   require_sources(nullptr, g, {&da});
-  return gen_to_std_host<DT>(&g, uplo, reinterpret_cast<DT*>(a), da.ld, reinterpret_cast<const DT*>(b), db.ld, da.m,
-                             da.nb, da.isrc, da.jsrc);
+  return gen_to_std_host<DT>(&g, uplo, host_operand(a, da), host_operand(b, db));
 }
 
 // ScaLAPACK p?sygst / p?hegst argument list (ibtype 1 only: inv(L) A inv(L^H) / inv(U^H) A inv(U))
@@ -328,9 +273,8 @@ int inverse_c(int ctx, char uplo, char diag, bool product, HT* a, const DLAF_des
   Grid& g = grid_from_context(ctx);
   require_sources(nullptr, g, {&da});
   if (product)
-    return inverse_from_cholesky_factor_host<DT>(&g, uplo, reinterpret_cast<DT*>(a), da.ld, da.m, da.nb, da.isrc,
-                                                 da.jsrc);
-  return triangular_inverse_host<DT>(&g, uplo, diag, reinterpret_cast<DT*>(a), da.ld, da.m, da.nb, da.isrc, da.jsrc);
+    return inverse_from_cholesky_factor_host<DT>(&g, uplo, host_operand(a, da));
+  return triangular_inverse_host<DT>(&g, uplo, diag, host_operand(a, da));
 }
 
 // ScaLAPACK p?trtri / p?potri argument lists
@@ -368,10 +312,8 @@ int norm_c(int ctx, char norm, char structure, char uplo, char diag, const HT* a
     *value = 0.0;
     return 0;
   }
-  const DT* ad = reinterpret_cast<const DT*>(a);
-  *value = structure == 'G' ? general_norm_host<DT>(g, norm, ad, da.ld, da.m, da.n, da.nb, da.isrc, da.jsrc)
-                            : structured_norm_host<DT>(g, norm, structure, uplo, diag, ad, da.ld, da.m, da.nb, da.isrc,
-                                                       da.jsrc);
+  *value = structure == 'G' ? general_norm_host<DT>(g, norm, host_operand(a, da))
+                            : structured_norm_host<DT>(g, norm, structure, uplo, diag, host_operand(a, da));
   return 0;
 }
 
@@ -396,8 +338,7 @@ int red2band_c(int ctx, HT* a, const DLAF_descriptor& da, int band, HT* taus) {
   Grid& g = grid_from_context(ctx);
   require_sources(nullptr, g, {&da});
   require_band("reduction_to_band", band, da.nb);
-  return reduction_to_band_host<DT>(&g, reinterpret_cast<DT*>(a), da.ld, da.m, da.nb, da.isrc, da.jsrc, band,
-                                    reinterpret_cast<DT*>(taus));
+  return reduction_to_band_host<DT>(&g, host_operand(a, da), band, reinterpret_cast<DT*>(taus));
 }
 
 template <class HT>
@@ -411,8 +352,7 @@ int bt_red2band_c(int ctx, int band, HT* c, const DLAF_descriptor& dc, const HT*
           "row count %d and row source %d, and no offsets\n", dc.m, dc.n, dc.mb, dc.nb, dc.isrc, dv.nb, dv.m, dv.isrc);
   require_sources(nullptr, g, {&dc, &dv});  // (C's row source is V's by now)
   require_band("bt_reduction_to_band", band, dv.nb);
-  return bt_reduction_to_band_host<DT>(&g, band, reinterpret_cast<DT*>(c), dc.ld, dc.n, dc.jsrc,
-                                       reinterpret_cast<const DT*>(v), dv.ld, dv.m, dv.nb, dv.isrc, dv.jsrc,
+  return bt_reduction_to_band_host<DT>(&g, band, host_operand(c, dc), host_operand(v, dv),
                                        reinterpret_cast<const DT*>(taus));
 }
 
@@ -427,8 +367,7 @@ int band_to_tridiag_c(int ctx, const HT* a, const DLAF_descriptor& da, int band,
   require_band("band_to_tridiagonal", band, da.nb);
   if (ldv < std::max(1, da.m))
     fatal("[dlaf_mi355x] band_to_tridiagonal: ldv = %d < n = %d\n", ldv, da.m);
-  return band_to_tridiag_host<DT>(&g, reinterpret_cast<const DT*>(a), da.ld, da.m, da.nb, da.isrc, da.jsrc, band, d, e,
-                                  reinterpret_cast<DT*>(v), ldv);
+  return band_to_tridiag_host<DT>(&g, host_operand(a, da), band, d, e, reinterpret_cast<DT*>(v), ldv);
 }
 
 // Eigensolver entry (src/c_api/eigensolver/eigensolver.h:33-75): descriptors of A and of the eigenvector matrix;
@@ -442,8 +381,7 @@ int eigensolver_c(int ctx, char uplo, HT* a, const DLAF_descriptor& da, typename
   Grid& g = grid_from_context(ctx);
   require_like("eigensolver", da, {&dz});
   require_sources(nullptr, g, {&da, &dz});
-  return hermitian_eigensolver_host<DT>(&g, uplo, reinterpret_cast<DT*>(a), da.ld, da.m, da.nb, da.isrc, da.jsrc, w,
-                                        reinterpret_cast<DT*>(z), dz.ld, dz.isrc, dz.jsrc, begin, end);
+  return hermitian_eigensolver_host<DT>(&g, uplo, host_operand(a, da), w, host_operand(z, dz), begin, end);
 }
 
 template <class HT>
@@ -457,9 +395,8 @@ int gen_eigensolver_c(int ctx, char uplo, HT* a, const DLAF_descriptor& da, HT* 
   Grid& g = grid_from_context(ctx);
   require_like("gen_eigensolver", da, {&db, &dz});
   require_sources(nullptr, g, {&da, &db, &dz});
-  return hermitian_gen_eigensolver_host<DT>(&g, uplo, reinterpret_cast<DT*>(a), da.ld, reinterpret_cast<DT*>(b), db.ld,
-                                            da.m, da.nb, da.isrc, da.jsrc, db.isrc, db.jsrc, w, reinterpret_cast<DT*>(z),
-                                            dz.ld, dz.isrc, dz.jsrc, factorized, begin, end);
+  return hermitian_gen_eigensolver_host<DT>(&g, uplo, host_operand(a, da), host_operand(b, db), w, host_operand(z, dz),
+                                            factorized, begin, end);
 }
 
 // p?syevd / p?heevd and p?sygvd / p?hegvd argument lists (src/c_api/eigensolver/eigensolver.h:79-124), descb == nullptr
@@ -488,8 +425,7 @@ int eigenvalues_c(int ctx, char uplo, const HT* a, const DLAF_descriptor& da, ty
   require_square_desc(da);
   Grid& g = grid_from_context(ctx);
   require_sources(nullptr, g, {&da});
-  return hermitian_eigenvalues_host<DT>(&g, uplo, reinterpret_cast<const DT*>(a), da.ld, da.m, da.nb, da.isrc, da.jsrc, w,
-                                        begin, end);
+  return hermitian_eigenvalues_host<DT>(&g, uplo, host_operand(a, da), w, begin, end);
 }
 
 template <class HT>
@@ -502,8 +438,7 @@ int gen_eigenvalues_c(int ctx, char uplo, const HT* a, const DLAF_descriptor& da
   Grid& g = grid_from_context(ctx);
   require_like("gen_eigenvalues", da, {&db});
   require_sources(nullptr, g, {&da, &db});
-  return hermitian_gen_eigenvalues_host<DT>(&g, uplo, reinterpret_cast<const DT*>(a), da.ld, reinterpret_cast<DT*>(b),
-                                            db.ld, da.m, da.nb, da.isrc, da.jsrc, db.isrc, db.jsrc, w, factorized, begin,
+  return hermitian_gen_eigenvalues_host<DT>(&g, uplo, host_operand(a, da), host_operand(b, db), w, factorized, begin,
                                             end);
 }
 
@@ -518,8 +453,8 @@ int eigensolver_by_value_c(int ctx, char uplo, HT* a, const DLAF_descriptor& da,
   Grid& g = grid_from_context(ctx);
   require_like("eigensolver", da, {&dz});
   require_sources(nullptr, g, {&da, &dz});
-  return hermitian_eigensolver_by_value_host<DT>(&g, uplo, reinterpret_cast<DT*>(a), da.ld, da.m, da.nb, da.isrc, da.jsrc,
-                                                 w, reinterpret_cast<DT*>(z), dz.ld, dz.isrc, dz.jsrc, vl, vu, begin, end);
+  return hermitian_eigensolver_by_value_host<DT>(&g, uplo, host_operand(a, da), w, host_operand(z, dz), vl, vu, begin,
+                                                 end);
 }
 
 template <class HT>
@@ -534,10 +469,8 @@ int gen_eigensolver_by_value_c(int ctx, char uplo, HT* a, const DLAF_descriptor&
   Grid& g = grid_from_context(ctx);
   require_like("gen_eigensolver", da, {&db, &dz});
   require_sources(nullptr, g, {&da, &db, &dz});
-  return hermitian_gen_eigensolver_by_value_host<DT>(&g, uplo, reinterpret_cast<DT*>(a), da.ld, reinterpret_cast<DT*>(b),
-                                                     db.ld, da.m, da.nb, da.isrc, da.jsrc, db.isrc, db.jsrc, w,
-                                                     reinterpret_cast<DT*>(z), dz.ld, dz.isrc, dz.jsrc, factorized, vl, vu,
-                                                     begin, end);
+  return hermitian_gen_eigensolver_by_value_host<DT>(&g, uplo, host_operand(a, da), host_operand(b, db), w,
+                                                     host_operand(z, dz), factorized, vl, vu, begin, end);
 }
 
 // the ScaLAPACK-like argument lists: descb == nullptr for the standard problem

@@ -6,17 +6,23 @@
 // one-step-ahead StepPipeline, bcast_view_column / bcast_column_and_transposed_panel), its host form on the host scope --
 // checked_transport (transport.hpp) after the quick returns, then a ScratchStream (pool.hpp) declared before the
 // matrices it serves.
+//
+// Every matrix of a _host driver is a HostOperand (host_operand.hpp): this process's local column-major part with the
+// matrix's global description as stored -- size, blocks, source process.  A driver reads every size from its operands
+// (the k of a product is op(A)'s inner extent, the free block of a right-hand side is B's own) and trusts them: the
+// entries judge them first, each family with its one require_* function (api_checks.hpp).
 #pragma once
 #include "device_matrix.hpp"
+#include "host_operand.hpp"
 
 namespace dlaf_mi355x {
 
-// op(A) X = alpha B (side L) / X op(A) = alpha B (side R) on the grid, host operands (solver.cpp);
-// m x n: size of B, nb: the square block of A = B's block along the triangular dimension, nb_free: B's block along
-// the other dimension (<= 0: nb)
+// op(A) X = alpha B (side L) / X op(A) = alpha B (side R) on the grid, host operands (solver.cpp): a the triangular
+// matrix with one square block, b the m x n matrix, overwritten; b's block along the triangular dimension is a's, the
+// other one is its own.  The arguments must have passed require_triangular (api_checks.hpp).
 template <class T>
-int triangular_solver_host(Grid* g, char side, char uplo, char op, char diag, T alpha, const T* a, long lda, int a_isrc,
-                           int a_jsrc, T* b, long ldb, long m, long n, int nb, int b_isrc, int b_jsrc, int nb_free = 0);
+int triangular_solver_host(Grid* g, char side, char uplo, char op, char diag, T alpha, HostOperand<const T> a,
+                           HostOperand<T> b);
 
 void solver_last_profile(double* ms, double* flops);
 
@@ -28,11 +34,11 @@ void general_matrix_transfer(MatrixBase* h, void* host, long ld, bool upload);
 int triangular_solver_device(char side, char uplo, char op, char diag, const void* alpha, MatrixBase* a, MatrixBase* b);
 
 // B = alpha op(A) B (side L) / B = alpha B op(A) (side R) on the grid (multiplication.cpp): the arguments and the
-// operand mapping of triangular_solver_host, host and resident forms; device time of the last sweep
+// operand mapping of triangular_solver_host (require_triangular too), host and resident forms; device time of the
+// last sweep
 template <class T>
-int triangular_multiplication_host(Grid* g, char side, char uplo, char op, char diag, T alpha, const T* a, long lda,
-                                   int a_isrc, int a_jsrc, T* b, long ldb, long m, long n, int nb, int b_isrc, int b_jsrc,
-                                   int nb_free = 0);
+int triangular_multiplication_host(Grid* g, char side, char uplo, char op, char diag, T alpha, HostOperand<const T> a,
+                                   HostOperand<T> b);
 int triangular_multiplication_device(char side, char uplo, char op, char diag, const void* alpha, MatrixBase* a,
                                      MatrixBase* b);
 // device time and whole-grid flops of the last sweep of ANY multiplication (triangular, Hermitian, general, rank update) on
@@ -41,13 +47,12 @@ void multiplication_last_profile(double* ms, double* flops);
 void multiplication_set_profile(double ms, double flops);
 
 // C = beta C + alpha A B (side L) / beta C + alpha B A (side R), A Hermitian with only its uplo triangle read
-// (multiplication.cpp; dlaf::hermitian_multiplication, every side x uplo).  m x n: size of B and C, nb: A's square block =
-// their block along A's dimension, nb_free: their block along the other one (<= 0: nb); (isrc, jsrc): source process of
-// B and C.  Host and resident forms.
+// (multiplication.cpp; dlaf::hermitian_multiplication, every side x uplo).  b and c are described alike; their block
+// along A's dimension is a's square block, the other one is their own.  The arguments must have passed
+// require_hermitian_multiplication (api_checks.hpp).  Host and resident forms.
 template <class T>
-int hermitian_multiplication_host(Grid* g, char side, char uplo, T alpha, const T* a, long lda, int a_isrc, int a_jsrc,
-                                  const T* b, long ldb, T beta, T* c, long ldc, long m, long n, int nb, int isrc, int jsrc,
-                                  int nb_free = 0);
+int hermitian_multiplication_host(Grid* g, char side, char uplo, T alpha, HostOperand<const T> a, HostOperand<const T> b,
+                                  T beta, HostOperand<T> c);
 int hermitian_multiplication_device(char side, char uplo, const void* alpha, MatrixBase* a, MatrixBase* b,
                                     const void* beta, MatrixBase* c);
 
@@ -55,13 +60,12 @@ int hermitian_multiplication_device(char side, char uplo, const void* alpha, Mat
 // one process, N x N on a grid).  a, b, c: the matrices as stored (A m x k or k x m, B k x n or n x k), one square block
 // nb.  The arguments must have passed require_general_multiplication (api_checks.hpp).  Host and resident forms.
 template <class T>
-int general_multiplication_host(Grid* g, char opa, char opb, T alpha, const T* a, long lda, int a_isrc, int a_jsrc,
-                                const T* b, long ldb, int b_isrc, int b_jsrc, T beta, T* c, long ldc, long m, long n,
-                                long k, int nb, int c_isrc, int c_jsrc);
+int general_multiplication_host(Grid* g, char opa, char opb, T alpha, HostOperand<const T> a, HostOperand<const T> b,
+                                T beta, HostOperand<T> c);
 int general_multiplication_device(char opa, char opb, const void* alpha, MatrixBase* a, MatrixBase* b, const void* beta,
                                   MatrixBase* c);
 
-// Hermitian rank-k (her2k false) / rank-2k update of the uplo triangle of C (rank_update.cpp; xSYRK / xHERK, xSYR2K /
+// Hermitian rank-k (b null) / rank-2k update of the uplo triangle of C (rank_update.cpp; xSYRK / xHERK, xSYR2K /
 // xHER2K): C = alpha A A^H + beta C (trans N, A n x k) / alpha A^H A + beta C (trans C, A k x n); her2k: alpha A B^H +
 // conj(alpha) B A^H + beta C / alpha A^H B + conj(alpha) B^H A + beta C, B stored, blocked and distributed like A.  alpha
 // of herk is real (im 0), beta is real.  The other triangle is never referenced; the imaginary part of C's diagonal is
@@ -70,9 +74,8 @@ int general_multiplication_device(char opa, char opb, const void* alpha, MatrixB
 // require_rank_update (api_checks.hpp).  Host and resident forms (resident: C a DeviceMatrix whose stored triangle is
 // uplo, a / b general matrices, b null for herk; alpha points to a real for herk, to an element for her2k).
 template <class T>
-int hermitian_rank_update_host(Grid* g, bool her2k, char uplo, char trans, T alpha, const T* a, long lda, int a_isrc,
-                               int a_jsrc, const T* b, long ldb, real_t<T> beta, T* c, long ldc, long n, long k, int nb,
-                               int c_isrc, int c_jsrc);
+int hermitian_rank_update_host(Grid* g, char uplo, char trans, T alpha, HostOperand<const T> a,
+                               const HostOperand<const T>* b, real_t<T> beta, HostOperand<T> c);
 int hermitian_rank_update_device(char trans, const void* alpha, MatrixBase* a, MatrixBase* b, const void* beta,
                                  MatrixBase* c);
 
@@ -83,14 +86,13 @@ int hermitian_rank_update_device(char trans, const void* alpha, MatrixBase* a, M
 // copy.  The arguments must have passed require_general_addition (api_checks.hpp).  Host and resident forms (resident:
 // two general matrices; the same handle twice is op N in place).
 template <class T>
-int general_addition_host(Grid* g, char uplo, char op, T alpha, const T* a, long lda, int a_isrc, int a_jsrc, T beta, T* c,
-                          long ldc, long m, long n, int nb, int c_isrc, int c_jsrc);
+int general_addition_host(Grid* g, char uplo, char op, T alpha, HostOperand<const T> a, T beta, HostOperand<T> c);
 int general_addition_device(char uplo, char op, const void* alpha, MatrixBase* a, const void* beta, MatrixBase* c);
 // The other triangle of the n x n general matrix A from its uplo one, in place: kind H the conjugated mirror and the
 // diagonal's imaginary parts exactly 0, kind S the plain transpose and the diagonal untouched.  The arguments must have
 // passed require_hermitian_complete.  Host and resident (a general matrix) forms.
 template <class T>
-int hermitian_complete_host(Grid* g, char uplo, char kind, T* a, long lda, long n, int nb, int isrc, int jsrc);
+int hermitian_complete_host(Grid* g, char uplo, char kind, HostOperand<T> a);
 int hermitian_complete_device(char uplo, char kind, MatrixBase* general_matrix);
 // Resident conversions, defined by what download() of either object shows: to_general writes into the general matrix g
 // the Hermitian (kind H) / symmetric (S) matrix whose stored triangle m holds, or the triangular one (T: exact zeros in
@@ -103,11 +105,12 @@ int matrix_from_general(MatrixBase* m, MatrixBase* g);
 void addition_last_profile(double* ms, double* bytes);
 
 // A <- L^-1 A L^-H (uplo L) / U^-H A U^-1 (uplo U) with the Cholesky factor held in the same uplo triangle of
-// `l` (gen_to_std.cpp; dlaf::eigensolver::internal::generalized_to_standard); device-resident and host forms
+// `l` (gen_to_std.cpp; dlaf::eigensolver::internal::generalized_to_standard); device-resident and host forms (a and l
+// square, described alike)
 template <class T>
 int gen_to_std_device(DeviceMatrix<T>& a, DeviceMatrix<T>& l);
 template <class T>
-int gen_to_std_host(Grid* g, char uplo, T* a, long lda, const T* l, long ldl, long n, int nb, int isrc, int jsrc);
+int gen_to_std_host(Grid* g, char uplo, HostOperand<T> a, HostOperand<const T> l);
 
 // A <- A^-1 for the triangular matrix in A's uplo triangle (diag N / U), and the uplo triangle of (L L^H)^-1 /
 // (U^H U)^-1 from the Cholesky factor held there (inverse.cpp; LAPACK xTRTRI / xPOTRI), in place; device-resident and
@@ -118,9 +121,9 @@ int triangular_inverse_device(char diag, DeviceMatrix<T>& a);
 template <class T>
 int inverse_from_cholesky_factor_device(DeviceMatrix<T>& a);
 template <class T>
-int triangular_inverse_host(Grid* g, char uplo, char diag, T* a, long lda, long n, int nb, int isrc, int jsrc);
+int triangular_inverse_host(Grid* g, char uplo, char diag, HostOperand<T> a);
 template <class T>
-int inverse_from_cholesky_factor_host(Grid* g, char uplo, T* a, long lda, long n, int nb, int isrc, int jsrc);
+int inverse_from_cholesky_factor_host(Grid* g, char uplo, HostOperand<T> a);
 // device time and whole-grid flops (n^3 / 3 per half, x 4 for complex types) of the last of them on this process
 void inverse_last_profile(double* ms, double* flops);
 // index arithmetic of the two sweeps (exported for the host-logic tests)
@@ -147,10 +150,9 @@ long inverse_workspace_tiles(const Axis& rows, const Axis& cols);
 // norm_kind: the canonical letter (M, 1, I, F) of a norm letter, 0 for any other character.
 char norm_kind(char norm);
 template <class T>
-double general_norm_host(Grid* g, char norm, const T* a, long lda, long m, long n, int nb, int isrc, int jsrc);
+double general_norm_host(Grid* g, char norm, HostOperand<const T> a);
 template <class T>
-double structured_norm_host(Grid* g, char norm, char structure, char uplo, char diag, const T* a, long lda, long n, int nb,
-                            int isrc, int jsrc);
+double structured_norm_host(Grid* g, char norm, char structure, char uplo, char diag, HostOperand<const T> a);
 template <class T>
 double structured_norm_device(char norm, char structure, char diag, const DeviceMatrix<T>& a);
 double general_norm_device(char norm, MatrixBase* general_matrix);

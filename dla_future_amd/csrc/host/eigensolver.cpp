@@ -167,12 +167,12 @@ int band_to_tridiag_device(DeviceMatrix<T>& A, int band, real_t<T>* d, real_t<T>
 }
 
 template <class T>
-int band_to_tridiag_host(Grid* g, const T* a, long lda, long n, int nb, int isrc, int jsrc, int band, real_t<T>* d,
-                         real_t<T>* e, T* v, long ldv) {
+int band_to_tridiag_host(Grid* g, HostOperand<const T> a, int band, real_t<T>* d, real_t<T>* e, T* v, long ldv) {
   using R = real_t<T>;
+  const long n = a.n;
   DeviceMatrix<T> A;
-  A.create(g, 'L', n, nb, isrc, jsrc);
-  A.upload(a, lda);
+  A.create(g, 'L', n, a.nb, a.isrc, a.jsrc);
+  A.upload(a.p, a.ld);
   PoolScope ws;
   R* dd = ws.get<R>((size_t) n);
   R* de = ws.get<R>((size_t) n);
@@ -752,37 +752,36 @@ void check_uplo(const char* who, char uplo) {
 }
 
 template <class T>
-int eigensolver_host_impl(Grid* g, char uplo, T* a, long lda, long n, int nb, int isrc, int jsrc, real_t<T>* w, T* z,
-                          long ldz, int z_isrc, int z_jsrc, const real_t<T>* by_value, long& begin, long& end) {
+int eigensolver_host_impl(Grid* g, char uplo, HostOperand<T> a, real_t<T>* w, HostOperand<T> z, const real_t<T>* by_value,
+                          long& begin, long& end) {
   if (!by_value)
-    check_eigenvalues_index("eigensolver", n, begin, end);
+    check_eigenvalues_index("eigensolver", a.n, begin, end);
   check_uplo("eigensolver", uplo);
-  if (z_isrc != isrc)
-    fatal("[dlaf_mi355x] eigensolver: the eigenvector matrix must share A's row source rank (%d != %d)\n", z_isrc, isrc);
+  if (z.isrc != a.isrc)
+    fatal("[dlaf_mi355x] eigensolver: the eigenvector matrix must share A's row source rank (%d != %d)\n", z.isrc, a.isrc);
   DeviceMatrix<T> A;
-  A.create(g, 'L', n, nb, isrc, jsrc);
-  A.upload(a, lda);
+  A.create(g, 'L', a.n, a.nb, a.isrc, a.jsrc);
+  A.upload(a.p, a.ld);
   std::unique_ptr<MatrixBase> zh;
   PartialSpectrumPlan pl;
-  const int r = hermitian_eigensolver_device(A, w, z_isrc, z_jsrc, by_value, begin, end, zh, pl);
-  A.download(a, lda, true);  // (upstream leaves the band + reflectors in A as well)
-  download_eigenvectors(static_cast<GeneralMatrix<T>&>(*zh), pl, z, ldz);
+  const int r = hermitian_eigensolver_device(A, w, z.isrc, z.jsrc, by_value, begin, end, zh, pl);
+  A.download(a.p, a.ld, true);  // (upstream leaves the band + reflectors in A as well)
+  download_eigenvectors(static_cast<GeneralMatrix<T>&>(*zh), pl, z.p, z.ld);
   return r;
 }
 
 // gen_eigensolver/impl.h:33-60: cholesky_factorization(uplo, B) unless the caller passes the factor,
 // generalized_to_standard(uplo, A, B); A, B resident on return (info == 0)
 template <class T>
-int gen_to_std_resident(const char* who, Grid* g, char uplo, const T* a, long lda, T* b, long ldb, long n, int nb, int a_isrc,
-                        int a_jsrc, int b_isrc, int b_jsrc, int z_isrc, bool b_factorized, DeviceMatrix<T>& A,
-                        DeviceMatrix<T>& B) {
+int gen_to_std_resident(const char* who, Grid* g, char uplo, HostOperand<const T> a, HostOperand<const T> b, int z_isrc,
+                        bool b_factorized, DeviceMatrix<T>& A, DeviceMatrix<T>& B) {
   check_uplo(who, uplo);
-  if (a_isrc != b_isrc || a_jsrc != b_jsrc || z_isrc != a_isrc)
+  if (a.isrc != b.isrc || a.jsrc != b.jsrc || z_isrc != a.isrc)
     fatal("[dlaf_mi355x] %s: A, B and the eigenvector matrix must share their source rank\n", who);
-  A.create(g, 'L', n, nb, a_isrc, a_jsrc);
-  B.create(g, 'L', n, nb, b_isrc, b_jsrc);
-  A.upload(a, lda);
-  B.upload(b, ldb);
+  A.create(g, 'L', a.n, a.nb, a.isrc, a.jsrc);
+  B.create(g, 'L', b.n, b.nb, b.isrc, b.jsrc);
+  A.upload(a.p, a.ld);
+  B.upload(b.p, b.ld);
   if (!b_factorized) {
     const int info = B.factorize();
     if (info != 0)
@@ -792,19 +791,17 @@ int gen_to_std_resident(const char* who, Grid* g, char uplo, const T* a, long ld
 }
 
 template <class T>
-int gen_eigensolver_host_impl(Grid* g, char uplo, T* a, long lda, T* b, long ldb, long n, int nb, int a_isrc, int a_jsrc,
-                              int b_isrc, int b_jsrc, real_t<T>* w, T* z, long ldz, int z_isrc, int z_jsrc,
+int gen_eigensolver_host_impl(Grid* g, char uplo, HostOperand<T> a, HostOperand<T> b, real_t<T>* w, HostOperand<T> z,
                               bool b_factorized, const real_t<T>* by_value, long& begin, long& end) {
   if (!by_value)
-    check_eigenvalues_index("gen_eigensolver", n, begin, end);
+    check_eigenvalues_index("gen_eigensolver", a.n, begin, end);
   DeviceMatrix<T> A, B;
-  int info = gen_to_std_resident("gen_eigensolver", g, uplo, a, lda, b, ldb, n, nb, a_isrc, a_jsrc, b_isrc, b_jsrc, z_isrc,
-                                 b_factorized, A, B);
+  int info = gen_to_std_resident<T>("gen_eigensolver", g, uplo, a, b, z.isrc, b_factorized, A, B);
   if (info != 0)
     return info;
   std::unique_ptr<MatrixBase> zh;
   PartialSpectrumPlan pl;
-  info = hermitian_eigensolver_device(A, w, z_isrc, z_jsrc, by_value, begin, end, zh, pl);
+  info = hermitian_eigensolver_device(A, w, z.isrc, z.jsrc, by_value, begin, end, zh, pl);
   if (info != 0)
     return info;
   // triangular_solver(Left, uplo, ConjTrans, NonUnit, 1, B, Z)
@@ -812,88 +809,77 @@ int gen_eigensolver_host_impl(Grid* g, char uplo, T* a, long lda, T* b, long ldb
   B.type = TypeInfo<T>::tag;
   if (end > begin)
     info = triangular_solver_device('L', 'L', 'C', 'N', &one, &B, zh.get());
-  A.download(a, lda, true);
+  A.download(a.p, a.ld, true);
   if (!b_factorized)
-    B.download(b, ldb, true);
-  download_eigenvectors(static_cast<GeneralMatrix<T>&>(*zh), pl, z, ldz);
+    B.download(b.p, b.ld, true);
+  download_eigenvectors(static_cast<GeneralMatrix<T>&>(*zh), pl, z.p, z.ld);
   return info;
 }
 }  // namespace
 
 template <class T>
-int hermitian_eigensolver_host(Grid* g, char uplo, T* a, long lda, long n, int nb, int isrc, int jsrc, real_t<T>* w, T* z,
-                               long ldz, int z_isrc, int z_jsrc, long begin, long end) {
-  return eigensolver_host_impl<T>(g, uplo, a, lda, n, nb, isrc, jsrc, w, z, ldz, z_isrc, z_jsrc, nullptr, begin, end);
+int hermitian_eigensolver_host(Grid* g, char uplo, HostOperand<T> a, real_t<T>* w, HostOperand<T> z, long begin, long end) {
+  return eigensolver_host_impl<T>(g, uplo, a, w, z, nullptr, begin, end);
 }
 
 template <class T>
-int hermitian_eigensolver_by_value_host(Grid* g, char uplo, T* a, long lda, long n, int nb, int isrc, int jsrc,
-                                        real_t<T>* w, T* z, long ldz, int z_isrc, int z_jsrc, real_t<T> vl, real_t<T> vu,
-                                        long* begin, long* end) {
+int hermitian_eigensolver_by_value_host(Grid* g, char uplo, HostOperand<T> a, real_t<T>* w, HostOperand<T> z, real_t<T> vl,
+                                        real_t<T> vu, long* begin, long* end) {
   const real_t<T> by_value[2] = {vl, vu};
-  return eigensolver_host_impl<T>(g, uplo, a, lda, n, nb, isrc, jsrc, w, z, ldz, z_isrc, z_jsrc, by_value, *begin, *end);
+  return eigensolver_host_impl<T>(g, uplo, a, w, z, by_value, *begin, *end);
 }
 
 template <class T>
-int hermitian_gen_eigensolver_host(Grid* g, char uplo, T* a, long lda, T* b, long ldb, long n, int nb, int a_isrc,
-                                   int a_jsrc, int b_isrc, int b_jsrc, real_t<T>* w, T* z, long ldz, int z_isrc,
-                                   int z_jsrc, bool b_factorized, long begin, long end) {
-  return gen_eigensolver_host_impl<T>(g, uplo, a, lda, b, ldb, n, nb, a_isrc, a_jsrc, b_isrc, b_jsrc, w, z, ldz, z_isrc,
-                                      z_jsrc, b_factorized, nullptr, begin, end);
+int hermitian_gen_eigensolver_host(Grid* g, char uplo, HostOperand<T> a, HostOperand<T> b, real_t<T>* w, HostOperand<T> z,
+                                   bool b_factorized, long begin, long end) {
+  return gen_eigensolver_host_impl<T>(g, uplo, a, b, w, z, b_factorized, nullptr, begin, end);
 }
 
 template <class T>
-int hermitian_gen_eigensolver_by_value_host(Grid* g, char uplo, T* a, long lda, T* b, long ldb, long n, int nb, int a_isrc,
-                                            int a_jsrc, int b_isrc, int b_jsrc, real_t<T>* w, T* z, long ldz, int z_isrc,
-                                            int z_jsrc, bool b_factorized, real_t<T> vl, real_t<T> vu, long* begin,
+int hermitian_gen_eigensolver_by_value_host(Grid* g, char uplo, HostOperand<T> a, HostOperand<T> b, real_t<T>* w,
+                                            HostOperand<T> z, bool b_factorized, real_t<T> vl, real_t<T> vu, long* begin,
                                             long* end) {
   const real_t<T> by_value[2] = {vl, vu};
-  return gen_eigensolver_host_impl<T>(g, uplo, a, lda, b, ldb, n, nb, a_isrc, a_jsrc, b_isrc, b_jsrc, w, z, ldz, z_isrc,
-                                      z_jsrc, b_factorized, by_value, *begin, *end);
+  return gen_eigensolver_host_impl<T>(g, uplo, a, b, w, z, b_factorized, by_value, *begin, *end);
 }
 
 template <class T>
-int hermitian_eigenvalues_host(Grid* g, char uplo, const T* a, long lda, long n, int nb, int isrc, int jsrc, real_t<T>* w,
-                               long begin, long end) {
-  check_eigenvalues_index("eigenvalues", n, begin, end);
+int hermitian_eigenvalues_host(Grid* g, char uplo, HostOperand<const T> a, real_t<T>* w, long begin, long end) {
+  check_eigenvalues_index("eigenvalues", a.n, begin, end);
   check_uplo("eigenvalues", uplo);
   DeviceMatrix<T> A;
-  A.create(g, 'L', n, nb, isrc, jsrc);
-  A.upload(a, lda);
+  A.create(g, 'L', a.n, a.nb, a.isrc, a.jsrc);
+  A.upload(a.p, a.ld);
   return hermitian_eigenvalues_device(A, w, begin, end);
 }
 
 template <class T>
-int hermitian_gen_eigenvalues_host(Grid* g, char uplo, const T* a, long lda, T* b, long ldb, long n, int nb, int a_isrc,
-                                   int a_jsrc, int b_isrc, int b_jsrc, real_t<T>* w, bool b_factorized, long begin,
-                                   long end) {
-  check_eigenvalues_index("gen_eigenvalues", n, begin, end);
+int hermitian_gen_eigenvalues_host(Grid* g, char uplo, HostOperand<const T> a, HostOperand<T> b, real_t<T>* w,
+                                   bool b_factorized, long begin, long end) {
+  check_eigenvalues_index("gen_eigenvalues", a.n, begin, end);
   DeviceMatrix<T> A, B;
-  int info = gen_to_std_resident("gen_eigenvalues", g, uplo, a, lda, b, ldb, n, nb, a_isrc, a_jsrc, b_isrc, b_jsrc, a_isrc,
-                                 b_factorized, A, B);
+  int info = gen_to_std_resident<T>("gen_eigenvalues", g, uplo, a, b, a.isrc, b_factorized, A, B);
   if (info != 0)
     return info;
   info = hermitian_eigenvalues_device(A, w, begin, end);
   if (info == 0 && !b_factorized)
-    B.download(b, ldb, true);
+    B.download(b.p, b.ld, true);
   return info;
 }
 
 #define INST(T)                                                                                                          \
-  template int hermitian_eigensolver_host<T>(Grid*, char, T*, long, long, int, int, int, real_t<T>*, T*, long, int, int, \
-                                             long, long);                                                                \
-  template int hermitian_gen_eigensolver_host<T>(Grid*, char, T*, long, T*, long, long, int, int, int, int, int,         \
-                                                 real_t<T>*, T*, long, int, int, bool, long, long);                      \
-  template int hermitian_eigensolver_by_value_host<T>(Grid*, char, T*, long, long, int, int, int, real_t<T>*, T*, long, \
-                                                      int, int, real_t<T>, real_t<T>, long*, long*);                     \
-  template int hermitian_gen_eigensolver_by_value_host<T>(Grid*, char, T*, long, T*, long, long, int, int, int, int,     \
-                                                          int, real_t<T>*, T*, long, int, int, bool, real_t<T>,          \
-                                                          real_t<T>, long*, long*);                                      \
-  template int hermitian_eigenvalues_host<T>(Grid*, char, const T*, long, long, int, int, int, real_t<T>*, long, long);  \
-  template int hermitian_gen_eigenvalues_host<T>(Grid*, char, const T*, long, T*, long, long, int, int, int, int, int,   \
-                                                 real_t<T>*, bool, long, long);                                          \
+  template int hermitian_eigensolver_host<T>(Grid*, char, HostOperand<T>, real_t<T>*, HostOperand<T>, long, long);       \
+  template int hermitian_gen_eigensolver_host<T>(Grid*, char, HostOperand<T>, HostOperand<T>, real_t<T>*, HostOperand<T>, \
+                                                 bool, long, long);                                                      \
+  template int hermitian_eigensolver_by_value_host<T>(Grid*, char, HostOperand<T>, real_t<T>*, HostOperand<T>, real_t<T>, \
+                                                      real_t<T>, long*, long*);                                          \
+  template int hermitian_gen_eigensolver_by_value_host<T>(Grid*, char, HostOperand<T>, HostOperand<T>, real_t<T>*,       \
+                                                          HostOperand<T>, bool, real_t<T>, real_t<T>, long*, long*);     \
+  template int hermitian_eigenvalues_host<T>(Grid*, char, HostOperand<const T>, real_t<T>*, long, long);                 \
+  template int hermitian_gen_eigenvalues_host<T>(Grid*, char, HostOperand<const T>, HostOperand<T>, real_t<T>*, bool,    \
+                                                 long, long);                                                            \
   template int band_to_tridiag_device<T>(DeviceMatrix<T>&, int, real_t<T>*, real_t<T>*, T*, long);                       \
-  template int band_to_tridiag_host<T>(Grid*, const T*, long, long, int, int, int, int, real_t<T>*, real_t<T>*, T*, long); \
+  template int band_to_tridiag_host<T>(Grid*, HostOperand<const T>, int, real_t<T>*, real_t<T>*, T*, long);              \
   template int bt_band_to_tridiag_device<T>(long, int, const T*, long, T*, long, long, hipStream_t);                     \
   template int bt_band_to_tridiag_host<T>(long, int, const T*, long, T*, long, long);
 INST(float)

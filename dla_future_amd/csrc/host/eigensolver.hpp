@@ -12,11 +12,13 @@ namespace dlaf_mi355x {
 // Hermitian band matrix in its lower band (what reduction_to_band leaves).  Device outputs: d, e (n reals each, e[n-1]
 // = 0), v (n x n, ldv): the compact Householder reflectors with tau in the place of the leading 1.  On a process grid
 // every rank ends up with the whole result (the band is summed over the grid, the chase runs replicated).
+// In the _host drivers of this header a distributed matrix is a HostOperand (host_operand.hpp): this process's local
+// column-major part with the matrix's global size, square block and source process, as the entries have judged it
+// (c_api_host.cpp); d, e, w and the reflector matrix v are plain arrays.
 template <class T>
 int band_to_tridiag_device(DeviceMatrix<T>& a, int band, real_t<T>* d, real_t<T>* e, T* v, long ldv);
 template <class T>
-int band_to_tridiag_host(Grid* g, const T* a, long lda, long n, int nb, int isrc, int jsrc, int band, real_t<T>* d,
-                         real_t<T>* e, T* v, long ldv);
+int band_to_tridiag_host(Grid* g, HostOperand<const T> a, int band, real_t<T>* d, real_t<T>* e, T* v, long ldv);
 
 // bt_band_to_tridiagonal (include/dlaf/eigensolver/bt_band_to_tridiag.h:28-61): E <- Q E on the rows of a
 // column-major device array e (n x ncols, lde); v as band_to_tridiag_device left it.
@@ -36,32 +38,29 @@ int tridiag_solver_device(long n, int nb, R* d, R* e, R* w, R* z, long ldz, long
 template <class R>
 int tridiag_solver_host(long n, int nb, const R* d, const R* e, R* w, R* z, long ldz, long begin, long end);
 
-// Hermitian eigensolver, Eigensolver::call (eigensolver/impl.h:38-55, :57-95): the local parts of A (lower triangle
-// referenced, destroyed), eigenvalues w (all n on every rank), eigenvectors z (distributed like a general n x n matrix
-// with A's block size and z's own source rank).  [begin, end): the 0-based range of eigenvalue indices whose
-// eigenvectors are computed; global column j of z, j in [begin, end), receives the eigenvector of eigenvalue j and
-// nothing else of z is written.
+// Hermitian eigensolver, Eigensolver::call (eigensolver/impl.h:38-55, :57-95): a (lower triangle referenced,
+// destroyed), eigenvalues w (all n on every rank), eigenvectors z (a general n x n matrix with a's block and its own
+// source process, whose row must be a's).  [begin, end): the 0-based range of eigenvalue indices whose eigenvectors
+// are computed; global column j of z, j in [begin, end), receives the eigenvector of eigenvalue j and nothing else of
+// z is written.
 template <class T>
-int hermitian_eigensolver_host(Grid* g, char uplo, T* a, long lda, long n, int nb, int isrc, int jsrc, real_t<T>* w, T* z,
-                               long ldz, int z_isrc, int z_jsrc, long begin, long end);
-// Hermitian generalized eigensolver A x = lambda B x, GenEigensolver::call (gen_eigensolver/impl.h:33-92)
+int hermitian_eigensolver_host(Grid* g, char uplo, HostOperand<T> a, real_t<T>* w, HostOperand<T> z, long begin, long end);
+// Hermitian generalized eigensolver A x = lambda B x, GenEigensolver::call (gen_eigensolver/impl.h:33-92); a, b and z
+// share their source process
 template <class T>
-int hermitian_gen_eigensolver_host(Grid* g, char uplo, T* a, long lda, T* b, long ldb, long n, int nb, int a_isrc,
-                                   int a_jsrc, int b_isrc, int b_jsrc, real_t<T>* w, T* z, long ldz, int z_isrc,
-                                   int z_jsrc, bool b_factorized, long begin, long end);
+int hermitian_gen_eigensolver_host(Grid* g, char uplo, HostOperand<T> a, HostOperand<T> b, real_t<T>* w, HostOperand<T> z,
+                                   bool b_factorized, long begin, long end);
 
 // The same with the eigenvalue range given by value, LAPACK's range = 'V': the eigenpairs in (vl, vu].  After
 // band_to_tridiagonal the drivers take [begin, end) = [count(vl), count(vu)) from two Sturm counts of the computed
 // tridiagonal matrix (vl >= vu: the empty range at count(vl)), return it, and go on exactly as the entries above do
 // for that index range.  An eigenvalue within rounding of vl or vu may fall on either side.
 template <class T>
-int hermitian_eigensolver_by_value_host(Grid* g, char uplo, T* a, long lda, long n, int nb, int isrc, int jsrc,
-                                        real_t<T>* w, T* z, long ldz, int z_isrc, int z_jsrc, real_t<T> vl, real_t<T> vu,
-                                        long* begin, long* end);
+int hermitian_eigensolver_by_value_host(Grid* g, char uplo, HostOperand<T> a, real_t<T>* w, HostOperand<T> z, real_t<T> vl,
+                                        real_t<T> vu, long* begin, long* end);
 template <class T>
-int hermitian_gen_eigensolver_by_value_host(Grid* g, char uplo, T* a, long lda, T* b, long ldb, long n, int nb, int a_isrc,
-                                            int a_jsrc, int b_isrc, int b_jsrc, real_t<T>* w, T* z, long ldz, int z_isrc,
-                                            int z_jsrc, bool b_factorized, real_t<T> vl, real_t<T> vu, long* begin,
+int hermitian_gen_eigensolver_by_value_host(Grid* g, char uplo, HostOperand<T> a, HostOperand<T> b, real_t<T>* w,
+                                            HostOperand<T> z, bool b_factorized, real_t<T> vl, real_t<T> vu, long* begin,
                                             long* end);
 
 // Eigenvalues only: reduction_to_band, band_to_tridiagonal, bisection for the eigenvalues [begin, end) (0-based,
@@ -69,12 +68,10 @@ int hermitian_gen_eigensolver_by_value_host(Grid* g, char uplo, T* a, long lda, 
 // destroyed); the generalized form leaves the Cholesky factor in b as the eigensolver does.  No divide & conquer, no
 // back-transformation, no eigenvector matrix: the replicated memory is the n x n reflector matrix alone.
 template <class T>
-int hermitian_eigenvalues_host(Grid* g, char uplo, const T* a, long lda, long n, int nb, int isrc, int jsrc, real_t<T>* w,
-                               long begin, long end);
+int hermitian_eigenvalues_host(Grid* g, char uplo, HostOperand<const T> a, real_t<T>* w, long begin, long end);
 template <class T>
-int hermitian_gen_eigenvalues_host(Grid* g, char uplo, const T* a, long lda, T* b, long ldb, long n, int nb, int a_isrc,
-                                   int a_jsrc, int b_isrc, int b_jsrc, real_t<T>* w, bool b_factorized, long begin,
-                                   long end);
+int hermitian_gen_eigenvalues_host(Grid* g, char uplo, HostOperand<const T> a, HostOperand<T> b, real_t<T>* w,
+                                   bool b_factorized, long begin, long end);
 
 // Eigenvalues of the symmetric tridiagonal matrix d (n), e (n - 1) by bisection on Sturm counts (kernels_sturm.hip).
 // _device: d, e, w on the device, work = sturm_work_doubles(n) doubles; enqueues on s and returns.  Only w[begin, end)

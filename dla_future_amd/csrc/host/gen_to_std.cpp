@@ -364,20 +364,20 @@ int gen_to_std_device(DeviceMatrix<T>& A, DeviceMatrix<T>& L) {
 
 // Host entry: a, l = this process's local column-major parts of A and of the Cholesky factor of B
 template <class T>
-int gen_to_std_host(Grid* g, char uplo, T* a, long lda, const T* l, long ldl, long n, int nb, int isrc, int jsrc) {
+int gen_to_std_host(Grid* g, char uplo, HostOperand<T> a, HostOperand<const T> l) {
   DeviceMatrix<T> A, Lm;
-  A.create(g, uplo, n, nb, isrc, jsrc);
-  Lm.create(g, uplo, n, nb, isrc, jsrc);
-  A.upload(a, lda);
-  Lm.upload(l, ldl);
+  A.create(g, uplo, a.n, a.nb, a.isrc, a.jsrc);
+  Lm.create(g, uplo, l.n, l.nb, l.isrc, l.jsrc);
+  A.upload(a.p, a.ld);
+  Lm.upload(l.p, l.ld);
   const int r = gen_to_std_device(A, Lm);
-  A.download(a, lda, true);
+  A.download(a.p, a.ld, true);
   return r;
 }
 
 #define INST(T)                                                     \
   template int gen_to_std_device<T>(DeviceMatrix<T>&, DeviceMatrix<T>&); \
-  template int gen_to_std_host<T>(Grid*, char, T*, long, const T*, long, long, int, int, int);
+  template int gen_to_std_host<T>(Grid*, char, HostOperand<T>, HostOperand<const T>);
 INST(float)
 INST(double)
 INST(cfloat)

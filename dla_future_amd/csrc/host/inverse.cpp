@@ -369,24 +369,24 @@ int inverse_from_cholesky_factor_device(DeviceMatrix<T>& A) {
 
 // Host entries: a = this process's local column-major part; only the uplo triangle is moved back
 template <class T>
-int triangular_inverse_host(Grid* g, char uplo, char diag, T* a, long lda, long n, int nb, int isrc, int jsrc) {
+int triangular_inverse_host(Grid* g, char uplo, char diag, HostOperand<T> a) {
   const bool unit = is_unit(diag);
   DeviceMatrix<T> A;
-  A.create(g, uplo, n, nb, isrc, jsrc);
-  A.upload(a, lda);
+  A.create(g, uplo, a.n, a.nb, a.isrc, a.jsrc);
+  A.upload(a.p, a.ld);
   const int r = inverse_device(A, unit, false);
   if (r == 0)
-    A.download(a, lda, true);
+    A.download(a.p, a.ld, true);
   return r;
 }
 template <class T>
-int inverse_from_cholesky_factor_host(Grid* g, char uplo, T* a, long lda, long n, int nb, int isrc, int jsrc) {
+int inverse_from_cholesky_factor_host(Grid* g, char uplo, HostOperand<T> a) {
   DeviceMatrix<T> A;
-  A.create(g, uplo, n, nb, isrc, jsrc);
-  A.upload(a, lda);
+  A.create(g, uplo, a.n, a.nb, a.isrc, a.jsrc);
+  A.upload(a.p, a.ld);
   const int r = inverse_device(A, false, true);
   if (r == 0)
-    A.download(a, lda, true);
+    A.download(a.p, a.ld, true);
   return r;
 }
 
@@ -400,8 +400,8 @@ void inverse_last_profile(double* ms, double* flops) {
 #define INST(T)                                                                                   \
   template int triangular_inverse_device<T>(char, DeviceMatrix<T>&);                              \
   template int inverse_from_cholesky_factor_device<T>(DeviceMatrix<T>&);                          \
-  template int triangular_inverse_host<T>(Grid*, char, char, T*, long, long, int, int, int);      \
-  template int inverse_from_cholesky_factor_host<T>(Grid*, char, T*, long, long, int, int, int);
+  template int triangular_inverse_host<T>(Grid*, char, char, HostOperand<T>);                     \
+  template int inverse_from_cholesky_factor_host<T>(Grid*, char, HostOperand<T>);
 INST(float)
 INST(double)
 INST(cfloat)

@@ -400,11 +400,9 @@ void multiplication_last_profile(double* ms, double* flops) {
 }
 
 template <class T>
-int triangular_multiplication_host(Grid* g, char side, char uplo, char op, char diag, T alpha, const T* a, long lda,
-                                   int a_isrc, int a_jsrc, T* b, long ldb, long m, long n, int nb, int b_isrc, int b_jsrc,
-                                   int nb_free) {
-  return triangular_canonical_host<T>("triangular multiplication", multiply_canonical<T>, false, g, side, uplo, op, diag,
-                                      alpha, a, lda, a_isrc, a_jsrc, b, ldb, m, n, nb, b_isrc, b_jsrc, nb_free);
+int triangular_multiplication_host(Grid* g, char side, char uplo, char op, char diag, T alpha, HostOperand<const T> a,
+                                   HostOperand<T> b) {
+  return triangular_canonical_host<T>(multiply_canonical<T>, false, g, side, uplo, op, diag, alpha, a, b);
 }
 
 int triangular_multiplication_device(char side, char uplo, char op, char diag, const void* alpha, MatrixBase* a,
@@ -423,37 +421,32 @@ int triangular_multiplication_device(char side, char uplo, char op, char diag, c
 // canonical form; side L runs it on the adjoints, C^H = conj(beta) C^H + conj(alpha) B^H A (the relayout transposes and
 // conjugates).  uplo U: the transposed, conjugated view of A holds A itself with its LOWER triangle valid.
 template <class T>
-int hermitian_multiplication_host(Grid* g, char side, char uplo, T alpha, const T* a, long lda, int a_isrc, int a_jsrc,
-                                  const T* b, long ldb, T beta, T* c, long ldc, long m, long n, int nb, int isrc, int jsrc,
-                                  int nb_free) {
+int hermitian_multiplication_host(Grid* g, char side, char uplo, T alpha, HostOperand<const T> a, HostOperand<const T> b,
+                                  T beta, HostOperand<T> c) {
   const bool left = side_is_left(side), a_upper = uplo_is_upper(uplo);
-  if (left ? (a_isrc != isrc) : (a_jsrc != jsrc))
-    fatal("[dlaf_mi355x] hermitian multiplication: A must share the source process of B and C along A's dimension\n");
-  if (m == 0 || n == 0)
+  if (c.m == 0 || c.n == 0)
     return 0;
   (void) checked_transport(*g);
-  const long na = left ? m : n;
   ScratchStream s;  // before the matrices: destroyed after them
   TileMatrix<T> Hd, Xd, Yd;
-  Hd.create(g, a_upper, na, na, nb, a_isrc, a_jsrc);
-  if (nb_free <= 0)
-    nb_free = nb;
-  Xd.create_rhs(g, left, m, n, left ? nb : nb_free, left ? nb_free : nb, isrc, jsrc);
-  Yd.create_rhs(g, left, m, n, left ? nb : nb_free, left ? nb_free : nb, isrc, jsrc);
-  Hd.upload(a, lda, a_upper, false, T{}, s);
-  Xd.upload(b, ldb, left, false, T{}, s);
+  Hd.create(g, a_upper, a.n, a.n, a.nb, a.isrc, a.jsrc);
+  Xd.create_rhs(g, left, c.m, c.n, c.mb, c.nb, c.isrc, c.jsrc);
+  Yd.create_rhs(g, left, c.m, c.n, c.mb, c.nb, c.isrc, c.jsrc);
+  Hd.upload(a.p, a.ld, a_upper, false, T{}, s);
+  Xd.upload(b.p, b.ld, left, false, T{}, s);
   if (!is_zero(beta))  // beta = 0: C is not read
-    Yd.upload(c, ldc, left, false, T{}, s);
+    Yd.upload(c.p, c.ld, left, false, T{}, s);
   s.sync();
   hermitian_canonical(Hd, Xd, Yd, left ? conj_of(alpha) : alpha, left ? conj_of(beta) : beta, false);
-  Yd.download(c, ldc, left, s);
+  Yd.download(c.p, c.ld, left, s);
   s.sync();
   return 0;
 }
 
 // The same on RESIDENT operands: A a DeviceMatrix (its uplo triangle; for uplo U it holds the transposed view, whose
-// lower triangle is conj(A)'s: conj_h), B and C general resident matrices of the same shape.  Side R works on B's and
-// C's tiles in place; side L on adjoint copies made by tile transforms on the device.  Only C is written.
+// lower triangle is conj(A)'s: conj_h), B and C general resident matrices of the same shape, judged by the entry with
+// require_hermitian_multiplication (c_api_device.cpp).  Side R works on B's and C's tiles in place; side L on adjoint
+// copies made by tile transforms on the device.  Only C is written.
 template <class T>
 int hermitian_device_t(char side, char uplo, T alpha, DeviceMatrix<T>& A, GeneralMatrix<T>& B, T beta,
                        GeneralMatrix<T>& C) {
@@ -461,21 +454,11 @@ int hermitian_device_t(char side, char uplo, T alpha, DeviceMatrix<T>& A, Genera
   Grid* g = A.grid;
   if (B.m.grid != g || C.m.grid != g)
     fatal("[dlaf_mi355x] %s: A, B and C live on different grids\n", who);
-  const bool left = side_is_left(side), a_upper = uplo_is_upper(uplo);
-  if (a_upper != A.transposed)
-    fatal("[dlaf_mi355x] %s: uplo '%c' but the resident matrix holds its '%c' triangle\n", who, uplo, A.uplo);
-  const long m = C.rows_g, n = C.cols_g, na = left ? m : n;
+  const bool left = side_is_left(side);
+  const long m = C.rows_g, n = C.cols_g, na = A.n;
   const int nb = A.nb;
-  if (B.rows_g != m || B.cols_g != n || B.m.nb != C.m.nb || B.isrc != C.isrc || B.jsrc != C.jsrc)
-    fatal("[dlaf_mi355x] %s: B (%ld x %ld, block %d, source %d,%d) and C (%ld x %ld, block %d, source %d,%d) differ\n", who,
-          B.rows_g, B.cols_g, B.m.nb, B.isrc, B.jsrc, m, n, C.m.nb, C.isrc, C.jsrc);
-  if (A.n != na || C.m.nb != nb)
-    fatal("[dlaf_mi355x] %s: A is %ld x %ld (block %d), C is %ld x %ld (block %d), side %c\n", who, A.n, A.n, nb, m, n,
-          C.m.nb, side);
   const Axis& a_rows = A.transposed ? A.cols : A.rows;
   const Axis& a_cols = A.transposed ? A.rows : A.cols;
-  if (left ? (a_rows.src != C.isrc) : (a_cols.src != C.jsrc))
-    fatal("[dlaf_mi355x] %s: A must share the source process of B and C along A's dimension\n", who);
   if (m == 0 || n == 0)
     return 0;
   ScratchStream s;  // before the matrices: destroyed after them
@@ -518,28 +501,28 @@ int hermitian_multiplication_device(char side, char uplo, const void* alpha, Mat
 // stored (A is m x k or k x m, B k x n or n x k), one square block nb.  The arguments have passed
 // require_general_multiplication (api_checks.hpp).  k == 0 or alpha == 0: A and B are not referenced (BLAS).
 template <class T>
-int general_multiplication_host(Grid* g, char opa, char opb, T alpha, const T* a, long lda, int a_isrc, int a_jsrc,
-                                const T* b, long ldb, int b_isrc, int b_jsrc, T beta, T* c, long ldc, long m, long n,
-                                long k, int nb, int c_isrc, int c_jsrc) {
-  if (m == 0 || n == 0)
+int general_multiplication_host(Grid* g, char opa, char opb, T alpha, HostOperand<const T> a, HostOperand<const T> b,
+                                T beta, HostOperand<T> c) {
+  if (c.m == 0 || c.n == 0)
     return 0;
   (void) checked_transport(*g);
-  const bool an = gemm_op_is_n(opa), bn = gemm_op_is_n(opb);
+  const long k = gemm_op_is_n(opa) ? a.n : a.m;
+  const int nb = c.nb;
   const bool product = k > 0 && !is_zero(alpha);
   ScratchStream s;  // before the matrices: destroyed after them
   TileMatrix<T> Ad, Bd, Cd;
-  Cd.create(g, false, m, n, nb, c_isrc, c_jsrc);
+  Cd.create(g, false, c.m, c.n, nb, c.isrc, c.jsrc);
   if (product) {
-    Ad.create(g, false, an ? m : k, an ? k : m, nb, a_isrc, a_jsrc);
-    Bd.create(g, false, bn ? k : n, bn ? n : k, nb, b_isrc, b_jsrc);
-    Ad.upload(a, lda, false, false, T{}, s);
-    Bd.upload(b, ldb, false, false, T{}, s);
+    Ad.create(g, false, a.m, a.n, nb, a.isrc, a.jsrc);
+    Bd.create(g, false, b.m, b.n, nb, b.isrc, b.jsrc);
+    Ad.upload(a.p, a.ld, false, false, T{}, s);
+    Bd.upload(b.p, b.ld, false, false, T{}, s);
   }
   if (!is_zero(beta))  // beta = 0: C is not read
-    Cd.upload(c, ldc, false, false, T{}, s);
+    Cd.upload(c.p, c.ld, false, false, T{}, s);
   s.sync();
   general_canonical(Ad, Bd, Cd, opa, opb, k, product ? (k + nb - 1) / nb : 0, alpha, beta);
-  Cd.download(c, ldc, false, s);
+  Cd.download(c.p, c.ld, false, s);
   s.sync();
   return 0;
 }
@@ -568,12 +551,11 @@ int general_multiplication_device(char opa, char opb, const void* alpha, MatrixB
 }
 
 #define DLAF_MULT_INST(T)                                                                                          \
-  template int hermitian_multiplication_host<T>(Grid*, char, char, T, const T*, long, int, int, const T*, long, T, T*, \
-                                                long, long, long, int, int, int, int);                                \
-  template int general_multiplication_host<T>(Grid*, char, char, T, const T*, long, int, int, const T*, long, int, int, \
-                                              T, T*, long, long, long, long, int, int, int);                          \
-  template int triangular_multiplication_host<T>(Grid*, char, char, char, char, T, const T*, long, int, int, T*, long, \
-                                                 long, long, int, int, int, int);
+  template int hermitian_multiplication_host<T>(Grid*, char, char, T, HostOperand<const T>, HostOperand<const T>, T, \
+                                                HostOperand<T>);                                                   \
+  template int general_multiplication_host<T>(Grid*, char, char, T, HostOperand<const T>, HostOperand<const T>, T,   \
+                                              HostOperand<T>);                                                     \
+  template int triangular_multiplication_host<T>(Grid*, char, char, char, char, T, HostOperand<const T>, HostOperand<T>);
 DLAF_MULT_INST(float)
 DLAF_MULT_INST(double)
 DLAF_MULT_INST(cfloat)

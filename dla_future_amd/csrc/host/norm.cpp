@@ -192,31 +192,30 @@ static bool checked_unit(char diag) {
 }
 
 template <class T>
-double general_norm_host(Grid* g, char norm, const T* a, long lda, long m, long n, int nb, int isrc, int jsrc) {
+double general_norm_host(Grid* g, char norm, HostOperand<const T> a) {
   const char kind = checked_kind(norm);
-  if (m <= 0 || n <= 0)
+  if (a.m <= 0 || a.n <= 0)
     return 0.0;
   runtime_init();
   ScratchStream s;
   TileMatrix<T> A;
-  A.create(g, false, m, n, nb, isrc, jsrc);
-  A.upload(a, lda, false, false, T{}, s);
+  A.create(g, false, a.m, a.n, a.nb, a.isrc, a.jsrc);
+  A.upload(a.p, a.ld, false, false, T{}, s);
   return norm_of_tile_matrix(kind, A, s);
 }
 
 template <class T>
-double structured_norm_host(Grid* g, char norm, char structure, char uplo, char diag, const T* a, long lda, long n, int nb,
-                            int isrc, int jsrc) {
+double structured_norm_host(Grid* g, char norm, char structure, char uplo, char diag, HostOperand<const T> a) {
   const char kind = checked_kind(norm);
   const int st = structure_index(structure);
   const bool unit = st == 2 && checked_unit(diag);
   if (st == 0)
-    return general_norm_host<T>(g, norm, a, lda, n, n, nb, isrc, jsrc);
-  if (n <= 0)
+    return general_norm_host<T>(g, norm, a);
+  if (a.n <= 0)
     return 0.0;
   DeviceMatrix<T> A;
-  A.create(g, uplo, n, nb, isrc, jsrc);
-  A.upload(a, lda);
+  A.create(g, uplo, a.n, a.nb, a.isrc, a.jsrc);
+  A.upload(a.p, a.ld);
   return norm_of_device_matrix(kind, st, unit, A);
 }
 
@@ -252,8 +251,8 @@ void norm_last_profile(double* ms, double* bytes) {
 }
 
 #define INST(T)                                                                                                    \
-  template double general_norm_host<T>(Grid*, char, const T*, long, long, long, int, int, int);                    \
-  template double structured_norm_host<T>(Grid*, char, char, char, char, const T*, long, long, int, int, int);     \
+  template double general_norm_host<T>(Grid*, char, HostOperand<const T>);                                         \
+  template double structured_norm_host<T>(Grid*, char, char, char, char, HostOperand<const T>);                    \
   template double structured_norm_device<T>(char, char, char, const DeviceMatrix<T>&);
 INST(float)
 INST(double)

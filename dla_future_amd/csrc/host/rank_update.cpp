@@ -140,35 +140,36 @@ void rank_update_canonical(DeviceMatrix<T>& C, TileMatrix<T>* Ad, TileMatrix<T>*
 }  // namespace
 
 template <class T>
-int hermitian_rank_update_host(Grid* g, bool her2k, char uplo, char trans, T alpha, const T* a, long lda, int a_isrc,
-                               int a_jsrc, const T* b, long ldb, real_t<T> beta, T* c, long ldc, long n, long k, int nb,
-                               int c_isrc, int c_jsrc) {
-  if (n == 0)
+int hermitian_rank_update_host(Grid* g, char uplo, char trans, T alpha, HostOperand<const T> a,
+                               const HostOperand<const T>* b, real_t<T> beta, HostOperand<T> c) {
+  if (c.n == 0)
     return 0;
+  const bool tn = herk_trans_is_n(trans);
+  const long k = tn ? a.n : a.m;
+  const int nb = c.nb;
   const bool product = k > 0 && !is_zero(alpha);
   if (!product && beta == real_t<T>(1))
     return 0;  // quick return: C is untouched, the imaginary parts of its diagonal included
   (void) checked_transport(*g);
-  const bool tn = herk_trans_is_n(trans);
   ScratchStream s;  // before the matrices: destroyed after them
   DeviceMatrix<T> Cd;
-  Cd.create(g, uplo, n, nb, c_isrc, c_jsrc);
+  Cd.create(g, uplo, c.n, nb, c.isrc, c.jsrc);
   TileMatrix<T> Ad, Bd;
   if (product) {
-    Ad.create(g, false, tn ? n : k, tn ? k : n, nb, a_isrc, a_jsrc);
-    Ad.upload(a, lda, false, false, T{}, s);
-    if (her2k) {
-      Bd.create(g, false, tn ? n : k, tn ? k : n, nb, a_isrc, a_jsrc);
-      Bd.upload(b, ldb, false, false, T{}, s);
+    Ad.create(g, false, a.m, a.n, nb, a.isrc, a.jsrc);
+    Ad.upload(a.p, a.ld, false, false, T{}, s);
+    if (b) {
+      Bd.create(g, false, b->m, b->n, nb, b->isrc, b->jsrc);
+      Bd.upload(b->p, b->ld, false, false, T{}, s);
     }
     s.sync();
   }
   const bool read_c = beta != real_t<T>(0);  // beta = 0: C is not read
   if (read_c)
-    Cd.upload(c, ldc);
-  rank_update_canonical<T>(Cd, product ? &Ad : nullptr, (product && her2k) ? &Bd : nullptr, tn, k,
+    Cd.upload(c.p, c.ld);
+  rank_update_canonical<T>(Cd, product ? &Ad : nullptr, (product && b) ? &Bd : nullptr, tn, k,
                            product ? (k + nb - 1) / nb : 0, alpha, beta);
-  Cd.download(c, ldc, read_c);
+  Cd.download(c.p, c.ld, read_c);
   return 0;
 }
 
@@ -209,8 +210,8 @@ int hermitian_rank_update_device(char trans, const void* alpha, MatrixBase* a, M
 }
 
 #define DLAF_RANK_UPDATE_INST(T)                                                                                     \
-  template int hermitian_rank_update_host<T>(Grid*, bool, char, char, T, const T*, long, int, int, const T*, long,  \
-                                             real_t<T>, T*, long, long, long, int, int, int);
+  template int hermitian_rank_update_host<T>(Grid*, char, char, T, HostOperand<const T>, const HostOperand<const T>*, \
+                                             real_t<T>, HostOperand<T>);
 DLAF_RANK_UPDATE_INST(float)
 DLAF_RANK_UPDATE_INST(double)
 DLAF_RANK_UPDATE_INST(cfloat)

@@ -565,15 +565,15 @@ int reduction_to_band_device(DeviceMatrix<T>& A, int band, T* taus_host) {
   return h_info;
 }
 
-// Host entry: a = this process's local column-major part of the Hermitian matrix (lower triangle referenced),
-// overwritten with the band + reflectors; taus: n - band - 1 values, all of them on every rank
+// Host entry: a = the Hermitian matrix (lower triangle referenced), overwritten with the band + reflectors; taus:
+// n - band - 1 values, all of them on every rank
 template <class T>
-int reduction_to_band_host(Grid* g, T* a, long lda, long n, int nb, int isrc, int jsrc, int band, T* taus) {
+int reduction_to_band_host(Grid* g, HostOperand<T> a, int band, T* taus) {
   DeviceMatrix<T> A;
-  A.create(g, 'L', n, nb, isrc, jsrc);
-  A.upload(a, lda);
+  A.create(g, 'L', a.n, a.nb, a.isrc, a.jsrc);
+  A.upload(a.p, a.ld);
   const int r = reduction_to_band_device(A, band, taus);
-  A.download(a, lda, true);
+  A.download(a.p, a.ld, true);
   return r;
 }
 
@@ -709,25 +709,24 @@ int bt_reduction_to_band_device(int band, TileMatrix<T>& C, DeviceMatrix<T>& A, 
 }
 
 template <class T>
-int bt_reduction_to_band_host(Grid* g, int band, T* c, long ldc, long ncols_c, int c_jsrc, const T* a, long lda, long n,
-                              int nb, int isrc, int jsrc, const T* taus) {
+int bt_reduction_to_band_host(Grid* g, int band, HostOperand<T> c, HostOperand<const T> a, const T* taus) {
   DeviceMatrix<T> A;
-  A.create(g, 'L', n, nb, isrc, jsrc);
-  A.upload(a, lda);
+  A.create(g, 'L', a.n, a.nb, a.isrc, a.jsrc);
+  A.upload(a.p, a.ld);
   TileMatrix<T> C;
-  C.create(g, false, n, ncols_c, nb, isrc, c_jsrc);
-  C.upload(c, ldc, false, false, T{}, A.s_high);
+  C.create(g, false, c.m, c.n, c.nb, c.isrc, c.jsrc);
+  C.upload(c.p, c.ld, false, false, T{}, A.s_high);
   const int r = bt_reduction_to_band_device(band, C, A, taus);
-  C.download(c, ldc, false, A.s_high);
+  C.download(c.p, c.ld, false, A.s_high);
   DLAF_HIP_CHECK(hipStreamSynchronize(A.s_high));
   return r;
 }
 
 #define INST(T)                                                           \
   template int reduction_to_band_device<T>(DeviceMatrix<T>&, int, T*);    \
-  template int reduction_to_band_host<T>(Grid*, T*, long, long, int, int, int, int, T*); \
+  template int reduction_to_band_host<T>(Grid*, HostOperand<T>, int, T*); \
   template int bt_reduction_to_band_device<T>(int, TileMatrix<T>&, DeviceMatrix<T>&, const T*); \
-  template int bt_reduction_to_band_host<T>(Grid*, int, T*, long, long, int, const T*, long, long, int, int, int, const T*);
+  template int bt_reduction_to_band_host<T>(Grid*, int, HostOperand<T>, HostOperand<const T>, const T*);
 INST(float)
 INST(double)
 INST(cfloat)

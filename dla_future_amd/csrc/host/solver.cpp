@@ -175,28 +175,24 @@ void solver_last_profile(double* ms, double* flops) {
     *flops = g_last_sweep_flops;
 }
 
-// Host entry of a canonical sweep (the solve, or the multiplication of multiplication.cpp): a (local part of the
-// triangular matrix, column-major lda), b (local part of the m x n matrix B, ldb) on the grid; b is overwritten by
-// the result.  may_reverse: the one-process reversal of an upper T below is allowed (the solve).
+// Host entry of a canonical sweep (the solve, or the multiplication of multiplication.cpp): a the triangular matrix, b
+// the matrix B on the grid, overwritten by the result; both have passed require_triangular (api_checks.hpp).
+// may_reverse: the one-process reversal of an upper T below is allowed (the solve).
 template <class T>
-int triangular_canonical_host(const char* who, CanonicalSweep<T> sweep, bool may_reverse, Grid* g, char side, char uplo,
-                              char op, char diag, T alpha, const T* a, long lda, int a_isrc, int a_jsrc, T* b, long ldb,
-                              long m, long n, int nb, int b_isrc, int b_jsrc, int nb_free) {
+int triangular_canonical_host(CanonicalSweep<T> sweep, bool may_reverse, Grid* g, char side, char uplo, char op, char diag,
+                              T alpha, HostOperand<const T> a, HostOperand<T> b) {
   (void) checked_transport(*g);
-  if (m == 0 || n == 0)
+  if (b.m == 0 || b.n == 0)
     return 0;
   const auto [left, a_upper, unit, t_transposed, t_conj, t_upper] = operand_map(side, uplo, op, diag);
-  const long na = left ? m : n;
-  if (left ? (a_isrc != b_isrc) : (a_jsrc != b_jsrc))
-    fatal("[dlaf_mi355x] %s: A and B must share the source process along the triangular dimension\n", who);
+  const long na = a.n;
+  const int nb = a.nb;
 
   ScratchStream s;  // before the matrices: destroyed after them
   TileMatrix<T> Td, Bd;
-  Td.create(g, t_transposed, na, na, nb, a_isrc, a_jsrc);
-  // B's blocks: nb along the triangular dimension (its rows for side = Left), nb_free along the other
-  if (nb_free <= 0)
-    nb_free = nb;
-  Bd.create_rhs(g, left, m, n, left ? nb : nb_free, left ? nb_free : nb, b_isrc, b_jsrc);
+  Td.create(g, t_transposed, na, na, nb, a.isrc, a.jsrc);
+  // B's blocks: A's along the triangular dimension (its rows for side = Left), its own along the other
+  Bd.create_rhs(g, left, b.m, b.n, b.mb, b.nb, b.isrc, b.jsrc);
   // One process, whole tiles: an upper triangular T (swept backward by the round-1 strips kernel) is laid out
   // REVERSED -- T'(i, j) = T(na-1-i, na-1-j) is lower triangular, X'(:, j) = X(:, na-1-j) solves X' T'^H = B' -- and
   // the forward sweep of the row-owner kernel does the work; the download reverses back.
@@ -210,21 +206,20 @@ int triangular_canonical_host(const char* who, CanonicalSweep<T> sweep, bool may
     Td.rev_rows = Td.rev_cols = true;
     Bd.rev_cols = true;  // the view's columns are the triangular dimension
   }
-  Td.upload(a, lda, t_conj, false, T{}, s);
+  Td.upload(a.p, a.ld, t_conj, false, T{}, s);
   // Left: B_dev = (alpha B)^H = conj(alpha) B^H (the relayout conjugates first, then scales)
-  Bd.upload(b, ldb, left, true, left ? conj_of(alpha) : alpha, s);
+  Bd.upload(b.p, b.ld, left, true, left ? conj_of(alpha) : alpha, s);
   s.sync();
   sweep(Td, Bd, reversed ? false : t_upper, unit);
-  Bd.download(b, ldb, left, s);
+  Bd.download(b.p, b.ld, left, s);
   s.sync();
   return 0;
 }
 
 template <class T>
-int triangular_solver_host(Grid* g, char side, char uplo, char op, char diag, T alpha, const T* a, long lda, int a_isrc,
-                           int a_jsrc, T* b, long ldb, long m, long n, int nb, int b_isrc, int b_jsrc, int nb_free) {
-  return triangular_canonical_host<T>("triangular solver", solve_canonical<T>, true, g, side, uplo, op, diag, alpha, a,
-                                      lda, a_isrc, a_jsrc, b, ldb, m, n, nb, b_isrc, b_jsrc, nb_free);
+int triangular_solver_host(Grid* g, char side, char uplo, char op, char diag, T alpha, HostOperand<const T> a,
+                           HostOperand<T> b) {
+  return triangular_canonical_host<T>(solve_canonical<T>, true, g, side, uplo, op, diag, alpha, a, b);
 }
 
 // ================================================================================ device-resident operands
@@ -280,7 +275,8 @@ void xform_tiles(T* dst, long dltr, long dltc, const T* src, long sltr, size_t t
 
 // A canonical sweep on RESIDENT operands (dlaf::triangular_solver, or the multiplication): A = a DeviceMatrix (its
 // uplo triangle: a Cholesky factor, or any triangular matrix uploaded as such), B = a general resident matrix,
-// overwritten by the result.  Nothing crosses PCIe: the operand views of the one device algorithm (X T^H = B, or
+// overwritten by the result; the entry has judged them with require_triangular (c_api_device.cpp), and a caller inside
+// the library builds them to fit.  Nothing crosses PCIe: the operand views of the one device algorithm (X T^H = B, or
 // X = B T^H) are made by tile transforms on the device.
 template <class T>
 int triangular_canonical_device(const char* who, CanonicalSweep<T> sweep, char side, char uplo, char op, char diag,
@@ -289,20 +285,13 @@ int triangular_canonical_device(const char* who, CanonicalSweep<T> sweep, char s
   if (B.m.grid != g)
     fatal("[dlaf_mi355x] %s: A and B live on different grids\n", who);
   const auto [left, a_upper, unit, t_transposed, t_conj, t_upper] = operand_map(side, uplo, op, diag);
-  if (a_upper != A.transposed)
-    fatal("[dlaf_mi355x] %s: uplo '%c' but the resident matrix holds its '%c' triangle\n", who, uplo, A.uplo);
-  const long m = B.rows_g, n = B.cols_g, na = left ? m : n;
+  const long m = B.rows_g, n = B.cols_g, na = A.n;
   const int nb = A.nb;
-  if (A.n != na || B.m.nb != nb)
-    fatal("[dlaf_mi355x] %s: A is %ld x %ld (block %d), B is %ld x %ld (block %d), side %c\n", who, A.n, A.n, nb, m, n,
-          B.m.nb, side);
   if (m == 0 || n == 0)
     return 0;
   // the caller's A and its source process (the DeviceMatrix holds the transposed view for uplo U)
   const Axis& a_rows = A.transposed ? A.cols : A.rows;
   const Axis& a_cols = A.transposed ? A.rows : A.cols;
-  if (left ? (a_rows.src != B.isrc) : (a_cols.src != B.jsrc))
-    fatal("[dlaf_mi355x] %s: A and B must share the source process along the triangular dimension\n", who);
   // in terms of the STORED tiles S (S = A for uplo L, S = A^T for uplo U): T = op(S)
   const bool s_transpose = t_transposed != A.transposed;
   const int t_mode = s_transpose ? (t_conj ? 0 : 3) : (t_conj ? 4 : 5);
@@ -349,13 +338,12 @@ int triangular_solver_device(char side, char uplo, char op, char diag, const voi
 }
 
 #define DLAF_CANONICAL_INST(T)                                                                                   \
-  template int triangular_canonical_host<T>(const char*, CanonicalSweep<T>, bool, Grid*, char, char, char, char, T,  \
-                                            const T*, long, int, int, T*, long, long, long, int, int, int, int);    \
+  template int triangular_canonical_host<T>(CanonicalSweep<T>, bool, Grid*, char, char, char, char, T,             \
+                                            HostOperand<const T>, HostOperand<T>);                               \
   template int triangular_canonical_device<T>(const char*, CanonicalSweep<T>, char, char, char, char, T,             \
                                               DeviceMatrix<T>&, GeneralMatrix<T>&);                                \
   template void xform_tiles<T>(T*, long, long, const T*, long, size_t, int, int, T, bool, hipStream_t);            \
-  template int triangular_solver_host<T>(Grid*, char, char, char, char, T, const T*, long, int, int, T*, long, long, \
-                                         long, int, int, int, int);
+  template int triangular_solver_host<T>(Grid*, char, char, char, char, T, HostOperand<const T>, HostOperand<T>);
 DLAF_CANONICAL_INST(float)
 DLAF_CANONICAL_INST(double)
 DLAF_CANONICAL_INST(cfloat)

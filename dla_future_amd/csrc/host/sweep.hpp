@@ -442,9 +442,8 @@ inline OperandMap operand_map(char side, char uplo, char op, char diag) {
 template <class T>
 using CanonicalSweep = void (*)(TileMatrix<T>& Td, TileMatrix<T>& Bd, bool upper, bool unit);
 template <class T>
-int triangular_canonical_host(const char* who, CanonicalSweep<T> sweep, bool may_reverse, Grid* g, char side, char uplo,
-                              char op, char diag, T alpha, const T* a, long lda, int a_isrc, int a_jsrc, T* b, long ldb,
-                              long m, long n, int nb, int b_isrc, int b_jsrc, int nb_free);
+int triangular_canonical_host(CanonicalSweep<T> sweep, bool may_reverse, Grid* g, char side, char uplo, char op, char diag,
+                              T alpha, HostOperand<const T> a, HostOperand<T> b);
 template <class T>
 int triangular_canonical_device(const char* who, CanonicalSweep<T> sweep, char side, char uplo, char op, char diag,
                                 T alpha, DeviceMatrix<T>& A, GeneralMatrix<T>& B);

@@ -34,7 +34,10 @@ PRELUDE = ("import numpy as np, ctypes as C, dla_future_amd as d\n"
            "dr = DLAFDescriptor(6, 4, 2, 2, 0, 0, 0, 0, 6)\n"
            "uplo = b'L'; band = 2; ldv = 6; ibtype = 1; ia = ja = ib = jb = iz = jz = 1\n"
            "info = C.c_int(0); m = C.c_int(0); begin = C.c_long(0); end = C.c_long(0)\n"
-           "pinfo, pm, pbegin, pend = C.byref(info), C.byref(m), C.byref(begin), C.byref(end)\n")
+           "pinfo, pm, pbegin, pend = C.byref(info), C.byref(m), C.byref(begin), C.byref(end)\n"
+           # trsm / trmm: B = rhs (6 x 4, dr); hemm: B = rhs (dr), C = c (drc)
+           "side = b'L'; op = b'N'; diag = b'N'; be = np.array([0.5]); c = np.zeros((6, 4), order='F')\n"
+           "drc = DLAFDescriptor(6, 4, 2, 2, 0, 0, 0, 0, 6)\n")
 DESCS = ("ctx = g.context\n"
          "sa, sb, sz = ((C.c_int * 9)(1, ctx, 6, 6, 2, 2, 0, 0, 6) for _ in range(3))\n")
 
@@ -43,6 +46,11 @@ CALLS = {
     "pdpotrf": "L.dlaf_pdpotrf(uplo, 6, pa, ia, ja, sa, pinfo)",
     "make_descriptor": "L.make_dlaf_descriptor(6, 6, ia, ja, sa)",
     "trsm": "L.dlaf_mi355x_triangular_solver_d(ctx, b'L', uplo, b'N', b'N', al.ctypes.data, pa, da, rhs.ctypes.data, dr)",
+    "trsm_any": "L.dlaf_mi355x_triangular_solver_d(ctx, side, uplo, op, diag, al.ctypes.data, pa, da, rhs.ctypes.data, dr)",
+    "trmm": "L.dlaf_mi355x_triangular_multiplication_d(ctx, side, uplo, op, diag, al.ctypes.data, pa, da, rhs.ctypes.data, "
+            "dr)",
+    "hemm": "L.dlaf_mi355x_hermitian_multiplication_d(ctx, side, uplo, al.ctypes.data, pa, da, rhs.ctypes.data, dr, "
+            "be.ctypes.data, c.ctypes.data, drc)",
     "pdpotrs": "L.dlaf_mi355x_pdpotrs(uplo, 6, 6, pa, ia, ja, sa, pb, ib, jb, sb, pinfo)",
     "gen_to_std": "L.dlaf_mi355x_generalized_to_standard_d(ctx, uplo, pa, da, pb, db)",
     "pdhegst": "L.dlaf_mi355x_pdhegst(ibtype, uplo, 6, pa, ia, ja, sa, pb, ib, jb, sb, None, pinfo)",
@@ -171,6 +179,75 @@ def test_source_process_terminates(entry, mutate, needle):
     """On a 2 x 2 host grid (no broadcast is ever made) a source coordinate of 1 is inside the grid: the checks that
     compare the sources of two operands fire, and the grid's own bounds are the ones in the message."""
     _terminates(HOST_2X2, entry, mutate, needle)
+
+
+# ---- triangular solver / multiplication and Hermitian multiplication: one case per terminating check of the descriptor
+# entries, the full sentence each prints.  A is 6 x 6, B (and C) 6 x 4, block 2; side R cases shrink A to 4 x 4.
+TRI = {"trsm_any": "triangular solver", "trmm": "triangular multiplication"}
+TRI_CASES = [
+    ("side = b'Q'", "{who}: bad side/uplo/op/diag 'Q' 'L' 'N' 'N'\n"),
+    ("op = b'X'", "{who}: bad side/uplo/op/diag 'L' 'L' 'X' 'N'\n"),
+    ("da.i = 1", "[dlaf_mi355x] sub-matrices are not supported: offsets must be 0\n"),
+    ("dr.j = 1", "[dlaf_mi355x] sub-matrices are not supported: offsets must be 0\n"),
+    ("da.n = 5", "{who}: A must be square with square blocks (6 x 5, 2 x 2)\n"),
+    ("da.mb = 3", "{who}: A must be square with square blocks (6 x 6, 3 x 2)\n"),
+    ("dr.m = 5", "{who}: A is 6 x 6, B is 5 x 4 (side L)\n"),
+    ("side = b'R'", "{who}: A is 6 x 6, B is 6 x 4 (side R)\n"),
+    ("dr.mb = 3", "{who}: B's blocks (3 x 2) do not match A's (2 x 2) for side L\n"),
+    ("side = b'R'; da.m = da.n = 4; dr.nb = 3", "{who}: B's blocks (2 x 3) do not match A's (2 x 2) for side R\n"),
+    ("da.isrc = 2", "[dlaf_mi355x] source rank (2,0) outside the 1 x 1 grid\n"),
+    ("dr.jsrc = -1", "[dlaf_mi355x] source rank (0,-1) outside the 1 x 1 grid\n"),
+]
+TRI_SOURCE_CASES = [
+    ("dr.isrc = 1", "{who}: A and B must share the source process along the triangular dimension\n"),
+    ("side = b'R'; da.m = da.n = 4; da.jsrc = 1",
+     "{who}: A and B must share the source process along the triangular dimension\n"),
+]
+HEMM = "[dlaf_mi355x] hermitian multiplication: "
+HEMM_CASES = [
+    ("side = b'Q'", HEMM + "bad side/uplo 'Q' 'L'\n"),
+    ("uplo = b'Q'", HEMM + "bad side/uplo 'L' 'Q'\n"),
+    ("da.j = 1", HEMM + "sub-matrices are not supported: offsets must be 0\n"),
+    ("drc.i = 1", HEMM + "sub-matrices are not supported: offsets must be 0\n"),
+    ("da.n = 5", HEMM + "A must be square with square blocks (6 x 5, 2 x 2)\n"),
+    ("dr.n = 5", HEMM + "B (6 x 5, blocks 2 x 2) and C (6 x 4, blocks 2 x 2) differ\n"),
+    ("drc.mb = 3", HEMM + "B (6 x 4, blocks 2 x 2) and C (6 x 4, blocks 3 x 2) differ\n"),
+    ("dr.m = drc.m = 5", HEMM + "A is 6 x 6, B and C are 5 x 4 (side L)\n"),
+    ("side = b'R'", HEMM + "A is 6 x 6, B and C are 6 x 4 (side R)\n"),
+    ("dr.mb = drc.mb = 3", HEMM + "the blocks of B and C (3 x 2) do not match A's (2 x 2) for side L\n"),
+    ("side = b'R'; da.m = da.n = 4; dr.nb = drc.nb = 3",
+     HEMM + "the blocks of B and C (2 x 3) do not match A's (2 x 2) for side R\n"),
+    ("da.isrc = 2", HEMM + "source rank (2,0) outside the 1 x 1 grid\n"),
+]
+HEMM_SOURCE_CASES = [
+    ("dr.jsrc = 1", HEMM + "B and C must share the source process ((0,1) vs (0,0))\n"),
+    ("drc.isrc = 1", HEMM + "B and C must share the source process ((0,0) vs (1,0))\n"),
+    ("da.isrc = 1", HEMM + "A must share the source process of B and C along A's dimension\n"),
+    ("side = b'R'; da.m = da.n = 4; da.jsrc = 1",
+     HEMM + "A must share the source process of B and C along A's dimension\n"),
+]
+
+
+@pytest.mark.parametrize("mutate,needle", TRI_CASES)
+@pytest.mark.parametrize("entry", sorted(TRI))
+def test_triangular_preconditions_terminate(entry, mutate, needle):
+    _terminates(SINGLE, entry, mutate, needle.format(who="[dlaf_mi355x] " + TRI[entry]))
+
+
+@pytest.mark.parametrize("mutate,needle", TRI_SOURCE_CASES)
+@pytest.mark.parametrize("entry", sorted(TRI))
+def test_triangular_source_process_terminates(entry, mutate, needle):
+    _terminates(HOST_2X2, entry, mutate, needle.format(who="[dlaf_mi355x] " + TRI[entry]))
+
+
+@pytest.mark.parametrize("mutate,needle", HEMM_CASES)
+def test_hermitian_multiplication_preconditions_terminate(mutate, needle):
+    _terminates(SINGLE, "hemm", mutate, needle)
+
+
+@pytest.mark.parametrize("mutate,needle", HEMM_SOURCE_CASES)
+def test_hermitian_multiplication_source_process_terminates(mutate, needle):
+    _terminates(HOST_2X2, "hemm", mutate, needle)
 
 
 def _codes(body, expected):

@@ -14,6 +14,8 @@ Python doorway onto that ABI, mirroring the reference's operator surface for the
     dlaf::hermitian_multiplication(side, uplo, ...)    include/dlaf/multiplication/hermitian.h
     dlaf::multiplication::internal::generalMatrix(...) include/dlaf/multiplication/general.h (p?gemm)
     hermitian_rank_k_update / hermitian_rank_2k_update BLAS xSYRK / xHERK, xSYR2K / xHER2K (p?syrk, p?herk, p?syr2k, p?her2k)
+    hermitian_weighted_rank_k_update                   "xHERK with weights": C = alpha A D A^H + beta C, D a real diagonal
+    hermitian_function / hermitian_power               f(A) = Z f(W) Z^H of a Hermitian matrix (S^(-1/2), projectors, ...)
     general_addition / hermitian_complete              PBLAS p?geadd, p?tradd, p?tran / p?tranu / p?tranc, ScaLAPACK p?lacpy
     dlaf::triangular_inverse(uplo, diag, A)            LAPACK xTRTRI / p?trtri (upstream: after the reference snapshot)
     dlaf::inverse_from_cholesky_factor(uplo, A)        LAPACK xPOTRI / p?potri
@@ -46,8 +48,13 @@ from .eigensolver import (band_to_tridiagonal, bt_band_to_tridiagonal, bt_reduct
                           pxheevd_eigenvalues, pxheevd_partial_spectrum_by_value, pxhegvd_eigenvalues,
                           pxhegvd_partial_spectrum_by_value, sturm_layout, tridiagonal_eigenvalues,
                           tridiagonal_sturm_count)
+from .matrix_function import (hermitian_function, hermitian_function_device, hermitian_power,  # noqa: F401
+                              hermitian_power_device, hermitian_weighted_rank_k_update,
+                              hermitian_weighted_rank_k_update_device)
 
-__all__ = ["band_to_tridiagonal", "bt_band_to_tridiagonal", "eigensolver_profile", "hermitian_eigensolver",
+__all__ = ["hermitian_function", "hermitian_function_device", "hermitian_power", "hermitian_power_device",
+           "hermitian_weighted_rank_k_update", "hermitian_weighted_rank_k_update_device",
+           "band_to_tridiagonal", "bt_band_to_tridiagonal", "eigensolver_profile", "hermitian_eigensolver",
            "hermitian_generalized_eigensolver", "tridiagonal_eigensolver", "bt_reduction_to_band", "bt_reduction_to_band_device", "get_band_size", "eigensolver_min_band", "red2band_profile",
            "reduction_to_band", "reduction_to_band_device", "DLAFDescriptor", "DeviceMatrix", "GeneralDeviceMatrix", "Grid", "LibraryNotBuilt", "cholesky_factorization", "distribution",
            "finalize", "generalized_to_standard", "initialize", "lib", "lib_path", "make_descriptor", "pxhegst", "pxpotrf", "pxpotrs", "pxtrsm",

@@ -55,6 +55,9 @@ class PotrfDesc(C.Structure):
 
 BCAST_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_size_t)
 BARRIER_FN = C.CFUNCTYPE(C.c_int, C.c_void_p)
+# dlaf_mi355x_spectral_weights_{s,d}: (n, w, begin, end, g, user)
+WEIGHTS_FN_S = C.CFUNCTYPE(None, C.c_long, C.POINTER(C.c_float), C.c_long, C.c_long, C.POINTER(C.c_float), C.c_void_p)
+WEIGHTS_FN_D = C.CFUNCTYPE(None, C.c_long, C.POINTER(C.c_double), C.c_long, C.c_long, C.POINTER(C.c_double), C.c_void_p)
 
 _TYPE_CHARS = {np.dtype(np.float32): "s", np.dtype(np.float64): "d", np.dtype(np.complex64): "c",
                np.dtype(np.complex128): "z"}
@@ -155,6 +158,21 @@ SIGNATURES = {
     "dlaf_mi355x_hermitian_rank_2k_update_d": (_i, [_i, _ch, _ch, _vp, _vp, DLAFDescriptor, _vp, DLAFDescriptor, _vp, _vp, DLAFDescriptor]),
     "dlaf_mi355x_hermitian_rank_2k_update_c": (_i, [_i, _ch, _ch, _vp, _vp, DLAFDescriptor, _vp, DLAFDescriptor, _vp, _vp, DLAFDescriptor]),
     "dlaf_mi355x_hermitian_rank_2k_update_z": (_i, [_i, _ch, _ch, _vp, _vp, DLAFDescriptor, _vp, DLAFDescriptor, _vp, _vp, DLAFDescriptor]),
+    "dlaf_mi355x_hermitian_weighted_rank_k_update_s": (_i, [_i, _ch, _ch, _vp, _vp, DLAFDescriptor, _vp, _vp, _vp, DLAFDescriptor]),
+    "dlaf_mi355x_hermitian_weighted_rank_k_update_d": (_i, [_i, _ch, _ch, _vp, _vp, DLAFDescriptor, _vp, _vp, _vp, DLAFDescriptor]),
+    "dlaf_mi355x_hermitian_weighted_rank_k_update_c": (_i, [_i, _ch, _ch, _vp, _vp, DLAFDescriptor, _vp, _vp, _vp, DLAFDescriptor]),
+    "dlaf_mi355x_hermitian_weighted_rank_k_update_z": (_i, [_i, _ch, _ch, _vp, _vp, DLAFDescriptor, _vp, _vp, _vp, DLAFDescriptor]),
+    "dlaf_mi355x_hermitian_weighted_rank_k_update_device": (_i, [_ch, _ch, _vp, _vp, _vp, _vp, _vp]),
+    "dlaf_mi355x_hermitian_function_s": (_i, [_i, _ch, _vp, DLAFDescriptor, _vp, WEIGHTS_FN_S, _vp, _vp, _vp, _vp]),
+    "dlaf_mi355x_hermitian_function_d": (_i, [_i, _ch, _vp, DLAFDescriptor, _vp, WEIGHTS_FN_D, _vp, _vp, _vp, _vp]),
+    "dlaf_mi355x_hermitian_function_c": (_i, [_i, _ch, _vp, DLAFDescriptor, _vp, WEIGHTS_FN_S, _vp, _vp, _vp, _vp]),
+    "dlaf_mi355x_hermitian_function_z": (_i, [_i, _ch, _vp, DLAFDescriptor, _vp, WEIGHTS_FN_D, _vp, _vp, _vp, _vp]),
+    "dlaf_mi355x_hermitian_function_device": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "dlaf_mi355x_hermitian_power_s": (_i, [_i, _ch, _vp, DLAFDescriptor, _vp, C.c_double, C.c_double, _LP]),
+    "dlaf_mi355x_hermitian_power_d": (_i, [_i, _ch, _vp, DLAFDescriptor, _vp, C.c_double, C.c_double, _LP]),
+    "dlaf_mi355x_hermitian_power_c": (_i, [_i, _ch, _vp, DLAFDescriptor, _vp, C.c_double, C.c_double, _LP]),
+    "dlaf_mi355x_hermitian_power_z": (_i, [_i, _ch, _vp, DLAFDescriptor, _vp, C.c_double, C.c_double, _LP]),
+    "dlaf_mi355x_hermitian_power_device": (_i, [_vp, _vp, C.c_double, C.c_double, _LP]),
     "dlaf_mi355x_pssyrk": (None, [_ch, _ch, _i, _i, _vp, _vp, _i, _i, _IP, _vp, _vp, _i, _i, _IP]),
     "dlaf_mi355x_pdsyrk": (None, [_ch, _ch, _i, _i, _vp, _vp, _i, _i, _IP, _vp, _vp, _i, _i, _IP]),
     "dlaf_mi355x_pcherk": (None, [_ch, _ch, _i, _i, _vp, _vp, _i, _i, _IP, _vp, _vp, _i, _i, _IP]),

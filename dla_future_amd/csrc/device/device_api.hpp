@@ -233,9 +233,15 @@ struct RankKArgs {
   T alpha;
   real_t<T> beta;
   int first = 1;
+  // the weighted update (launch_rank_k_weighted; x2 == nullptr): x(il, t)[:, k] is multiplied by the real weight
+  // kw[t nb + k] on its way into LDS -- kw a device pointer to the weight of k = 0 of k tile 0 of this launch.
+  // conj_view leaves the weights alone (they are real).  launch_rank_k never reads it.
+  const real_t<T>* kw = nullptr;
 };
 template <class T>
 void launch_rank_k(const RankKArgs<T>& args, hipStream_t stream);
+template <class T>
+void launch_rank_k_weighted(const RankKArgs<T>& args, hipStream_t stream);
 
 // ------------------------------------------------------------------------------------------
 // Addition / transposition (kernels_geadd.hip; index arithmetic: geadd_map.hpp) of the `mask` part of the local tile

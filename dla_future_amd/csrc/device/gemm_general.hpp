@@ -10,6 +10,8 @@
 // Reference: the tile::gemm / tile::hemm / tile::trmm3 calls of eigensolver/reduction_to_band/impl.h:231-281,
 // :425-462, :520-542 and eigensolver/bt_reduction_to_band/impl.h:91-129 (blaspp / rocBLAS one tile at a time).
 #pragma once
+#include <type_traits>
+
 #include "mma_core.hpp"
 
 namespace dlaf_mi355x {
@@ -254,9 +256,14 @@ __device__ __forceinline__ void mma_slab_g(const typename Cfg::R* __restrict__ A
 // workgroup call it; lds: 2 * Cfg::BUF_ELEMS of R (Cfg must be an un-paired, plane-separated configuration).
 // MA / MB >= 0: the slab mode of the operand is a compile-time promise of the caller (the loaders of the other modes are
 // not even compiled into the kernel: a kernel that may meet every mode keeps the registers of all three loaders busy)
-template <class Cfg, class T, int MA = -1, int MB = -1>
+// XW: a scaling of operand a along k between its global load and its LDS image (the weighted rank-k update,
+// kernels_herk.hip: SlabWeights).  xw.fetch(ma, k0, K) runs next to the slab's global loads, xw.scale(ma, regs) just
+// before the registers are stored.  NoSlabWeight (every other caller): neither exists in the kernel.
+struct NoSlabWeight {};
+template <class Cfg, class T, int MA = -1, int MB = -1, class XW = NoSlabWeight>
 __device__ __forceinline__ void gemm_acc(const OpDesc<T>& da, int mrows, const OpDesc<T>& db, int ncols, int K,
-                                         typename Cfg::R* __restrict__ lds, Acc<Cfg>& acc) {
+                                         typename Cfg::R* __restrict__ lds, Acc<Cfg>& acc, XW xw = XW{}) {
+  constexpr bool WEIGHTED = !std::is_same<XW, NoSlabWeight>::value;
   using R = typename Cfg::R;
   static_assert(!Cfg::PAIRED && !Cfg::CXI, "plane-separated, padded LDS images");
   const int nk = (K + Cfg::BK - 1) / Cfg::BK;
@@ -274,6 +281,10 @@ __device__ __forceinline__ void gemm_acc(const OpDesc<T>& da, int mrows, const O
   const int ma = MA >= 0 ? MA : sa.pick_mode(da, mrows, K), mb = MB >= 0 ? MB : sb.pick_mode(db, ncols, K);
   sa.load(da, ma, 0, mrows, K);
   sb.load(db, mb, 0, ncols, K);
+  if constexpr (WEIGHTED) {
+    xw.fetch(ma, 0, K);
+    xw.scale(ma, sa.regs);
+  }
   sa.template store<TA>(lds, ma, da.conj != 0);
   sb.template store<TB>(lds + Cfg::A_ELEMS, mb, db.conj != 0);
   __syncthreads();
@@ -284,12 +295,16 @@ __device__ __forceinline__ void gemm_acc(const OpDesc<T>& da, int mrows, const O
     if (more) {
       sa.load(da, ma, (kt + 1) * Cfg::BK, mrows, K);
       sb.load(db, mb, (kt + 1) * Cfg::BK, ncols, K);
+      if constexpr (WEIGHTED)
+        xw.fetch(ma, (kt + 1) * Cfg::BK, K);
     }
     if constexpr (TA || TB)
       mma_slab_g<Cfg, TA, TB>(cur, cur + Cfg::A_ELEMS, acc, wm, wn, lane);
     else
       mma_slab<Cfg>(cur, cur + Cfg::A_ELEMS, acc, wm, wn, lane);
     if (more) {
+      if constexpr (WEIGHTED)
+        xw.scale(ma, sa.regs);
       sa.template store<TA>(nxt, ma, da.conj != 0);
       sb.template store<TB>(nxt + Cfg::A_ELEMS, mb, db.conj != 0);
     }

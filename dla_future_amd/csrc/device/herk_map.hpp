@@ -66,4 +66,29 @@ DLAF_GEMM_FORMS_FN long herk_panel_offset(int idx, int period, long ts, long ts2
   return period <= 1 ? (long) idx * ts : (long) (idx % period) * ts2 + (long) (idx / period) * ts;
 }
 
+// The weighted update (hermitian_weighted_rank_k_update: x scaled by a real weight per k between its global load and its
+// LDS image): which weights of a slab a thread of the slab loader needs, and which of them each of its registers takes.
+// OpSlab::load (gemm_general.hpp) gives thread t of `threads` the pieces idx = t + threads q: a 16-byte load of ve
+// elements into registers [q ve, (q + 1) ve) in modes 0 and 1, the single element of register q in mode 2.
+//   mode 0: the ve elements of a piece are ve rows of ONE k = idx / (rows / ve)         slot q,  one weight per piece
+//   mode 1: ve consecutive k of one row from (idx % (bk / ve)) ve; `threads` is a multiple of bk / ve, so every piece
+//           of a thread covers the SAME ve k                                            slot e,  ve weights per thread
+//   mode 2: k = idx / rows                                                              slot q,  one weight per element
+// herk_weight_slots: how many weights a thread holds; herk_weight_k: the k (inside the slab) of its slot s;
+// herk_weight_slot: the slot register r takes.  tests/herk_weight_map/sweep.cpp sweeps the three against the loader's
+// own enumeration.
+DLAF_GEMM_FORMS_FN int herk_weight_slots(int mode, int rows, int bk, int ve, int threads) {
+  return mode == 1 ? ve : (mode == 0 ? rows * bk / (threads * ve) : rows * bk / threads);
+}
+DLAF_GEMM_FORMS_FN int herk_weight_k(int mode, int t, int s, int rows, int bk, int ve, int threads) {
+  if (mode == 0)
+    return (t + threads * s) / (rows / ve);
+  if (mode == 1)
+    return (t % (bk / ve)) * ve + s;
+  return (t + threads * s) / rows;
+}
+DLAF_GEMM_FORMS_FN int herk_weight_slot(int mode, int r, int ve) {
+  return mode == 0 ? r / ve : (mode == 1 ? r % ve : r);
+}
+
 }  // namespace dlaf_mi355x

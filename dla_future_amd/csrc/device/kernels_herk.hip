@@ -16,6 +16,8 @@
 // no room for a second set of accumulators, so the workgroup makes two passes over k:  V = beta V + alpha acc, clear,
 // V += conj(alpha) acc -- the block's extra read and write of V is a 1 / k share of the operand traffic.  Real types
 // and Im alpha == 0 take one pass with both products per k tile.
+// The weighted update (herk only: V += alpha sum_t x(il, t) D_t y(jl, t)^H, D real diagonal) is the same kernel with WT:
+// SlabWeights multiplies the weights into the x slab between its global load and its LDS image (gemm_acc's XW hook).
 #include <type_traits>
 
 #include "device_api.hpp"
@@ -61,14 +63,63 @@ __device__ __forceinline__ void herk_acc_foreach(const Acc<Cfg>& acc, F&& f) {
     }
 }
 
+// The weights of the weighted update for the x slab of one k tile (gemm_acc's XW, gemm_general.hpp): kw points to the
+// weight of k = 0 of the tile.  fetch reads the weights of the slab at k0 this thread's registers need next to the slab's
+// own global loads, scale multiplies them in just before the registers go to LDS -- both parts of a complex element;
+// which weight a register takes is herk_map.hpp's.  Mode 2 reads no weight at or beyond K (the element is zero there).
+template <class T, class Cfg>
+struct SlabWeights {
+  using R = real_t<T>;
+  using S = OpSlab<T, Cfg::BM, Cfg::BK, Cfg::LDA, Cfg::THREADS>;
+  static constexpr int NMAX = S::PER;  // (mode 2; the slots beyond a mode's own count are never touched)
+  // LATE: the complex ELEMENT kernels have no registers to carry the weights over a slab of MFMAs (holding them cost
+  // complex float 80 and complex double 12 bytes of scratch per lane): their mode 2 notes the slab in fetch and reads the
+  // weights in scale, where they live for one multiply each
+  static constexpr bool LATE = TypeInfo<T>::is_complex;
+  const R* kw;
+  R w[NMAX];
+  int k0_late = 0, K_late = 0;
+
+  __device__ __forceinline__ void read(int mode, int k0, int K) {
+    const int t = threadIdx.x;
+#pragma unroll
+    for (int s = 0; s < NMAX; ++s)
+      if (s < herk_weight_slots(mode, Cfg::BM, Cfg::BK, S::VE, Cfg::THREADS)) {
+        const int k = k0 + herk_weight_k(mode, t, s, Cfg::BM, Cfg::BK, S::VE, Cfg::THREADS);
+        w[s] = (mode != 2 || k < K) ? kw[k] : R(0);
+      }
+  }
+  __device__ __forceinline__ void fetch(int mode, int k0, int K) {
+    if (LATE && mode == 2) {
+      k0_late = k0;
+      K_late = K;
+    }
+    else
+      read(mode, k0, K);
+  }
+  __device__ __forceinline__ void scale(int mode, T (&regs)[S::PER]) {
+    if (LATE && mode == 2)
+      read(mode, k0_late, K_late);
+#pragma unroll
+    for (int r = 0; r < S::PER; ++r) {
+      const R v = w[herk_weight_slot(mode, r, S::VE)];
+      if constexpr (TypeInfo<T>::is_complex)
+        regs[r] = T{regs[r].re * v, regs[r].im * v};
+      else
+        regs[r] = regs[r] * v;
+    }
+  }
+};
+
 }  // namespace
 
 // Workgroups per compute unit, as for the general kernels: two, except the fp64 element kernel (kernels_gemm.hip).
 template <class T, bool VEC>
 constexpr int kHerkMinBlocks = (!VEC && std::is_same<T, double>::value) ? 1 : 2;
 
-// MODE: the OpSlab mode of both operands (0 trans N, 1 trans C); the element kernel (VEC false) serves both
-template <class T, int MODE, bool VEC>
+// MODE: the OpSlab mode of both operands (0 trans N, 1 trans C); the element kernel (VEC false) serves both.
+// WT: the weighted update -- x(il, t)[:, k] is multiplied by the real p.kw[t nb + k] on its way into LDS (herk only)
+template <class T, int MODE, bool VEC, bool WT = false>
 __global__ __launch_bounds__(GenCfg<T>::type::THREADS, (kHerkMinBlocks<T, VEC>) ) void rank_k_kernel(RankKArgs<T> p, int bpr,
                                                                                                    int bpc) {
   using Cfg = typename GenCfg<T>::type;
@@ -128,7 +179,15 @@ __global__ __launch_bounds__(GenCfg<T>::type::THREADS, (kHerkMinBlocks<T, VEC>) 
       OpDesc<T> dx = herk_desc(fx, xb + xo + (long) t * p.ks), dy = herk_desc(fy, yb + yo + (long) t * p.ks);
       // (opaque per k tile: hipcc would keep every lane's slab offsets in registers over the loop, kernels_gemm.hip)
       asm volatile("" : "+s"(dx.rs), "+s"(dx.ks), "+s"(dy.rs), "+s"(dy.ks));
-      if constexpr (VEC)
+      if constexpr (WT) {
+        SlabWeights<T, Cfg> xw;
+        xw.kw = p.kw + (long) t * p.nb;
+        if constexpr (VEC)
+          gemm_acc<Cfg, T, MODE, MODE>(dx, mr, dy, nc, K, lds, acc, xw);
+        else
+          gemm_acc<Cfg, T, 2, 2>(dx, mr, dy, nc, K, lds, acc, xw);
+      }
+      else if constexpr (VEC)
         gemm_acc<Cfg, T, MODE, MODE>(dx, mr, dy, nc, K, lds, acc);
       else
         gemm_acc<Cfg, T, 2, 2>(dx, mr, dy, nc, K, lds, acc);
@@ -177,12 +236,12 @@ __global__ __launch_bounds__(GenCfg<T>::type::THREADS, (kHerkMinBlocks<T, VEC>) 
   }
 }
 
-template <class T, int MODE, bool VEC>
+template <class T, int MODE, bool VEC, bool WT = false>
 static void launch_rank_k_kernel(const RankKArgs<T>& a, hipStream_t stream) {
   using Cfg = typename GenCfg<T>::type;
   const int bpr = (a.nb + Cfg::BM - 1) / Cfg::BM, bpc = (a.nb + Cfg::BN - 1) / Cfg::BN;
   const long grid = (long) a.ltr * a.ltc * bpr * bpc;
-  hipLaunchKernelGGL((rank_k_kernel<T, MODE, VEC>), dim3((unsigned) grid), dim3(Cfg::THREADS), Cfg::LDS_BYTES, stream, a, bpr,
+  hipLaunchKernelGGL((rank_k_kernel<T, MODE, VEC, WT>), dim3((unsigned) grid), dim3(Cfg::THREADS), Cfg::LDS_BYTES, stream, a, bpr,
                      bpc);
 }
 
@@ -201,6 +260,22 @@ void launch_rank_k(const RankKArgs<T>& a, hipStream_t stream) {
   launch_rank_k_kernel<T, 0, false>(a, stream);  // (one element kernel per type: the forms do not enter it)
 }
 
+// The weighted update: the same grids with the WT kernels.  args.kw: the weight of k = 0 of k tile 0 of this launch
+// (device memory, nk - 1 whole tiles and k_last more reals); x2 / y2 must be null.  nk == 0: no weight is read.
+template <class T>
+void launch_rank_k_weighted(const RankKArgs<T>& a, hipStream_t stream) {
+  using Cfg = typename GenCfg<T>::type;
+  if (a.ltr <= 0 || a.ltc <= 0 || a.nb <= 0 || a.nk < 0)
+    return;
+  if (a.nk > 0 && a.k_last % Cfg::BK == 0) {
+    if (herk_vector_mode(a.trans) == 0)
+      launch_rank_k_kernel<T, 0, true, true>(a, stream);
+    else
+      launch_rank_k_kernel<T, 1, true, true>(a, stream);
+  }
+  launch_rank_k_kernel<T, 0, false, true>(a, stream);
+}
+
 template <class T>
 static void herk_init_one() {
   using Cfg = typename GenCfg<T>::type;
@@ -209,6 +284,12 @@ static void herk_init_one() {
   (void) hipFuncSetAttribute(reinterpret_cast<const void*>(&rank_k_kernel<T, 1, true>),
                              hipFuncAttributeMaxDynamicSharedMemorySize, Cfg::LDS_BYTES);
   (void) hipFuncSetAttribute(reinterpret_cast<const void*>(&rank_k_kernel<T, 0, false>),
+                             hipFuncAttributeMaxDynamicSharedMemorySize, Cfg::LDS_BYTES);
+  (void) hipFuncSetAttribute(reinterpret_cast<const void*>(&rank_k_kernel<T, 0, true, true>),
+                             hipFuncAttributeMaxDynamicSharedMemorySize, Cfg::LDS_BYTES);
+  (void) hipFuncSetAttribute(reinterpret_cast<const void*>(&rank_k_kernel<T, 1, true, true>),
+                             hipFuncAttributeMaxDynamicSharedMemorySize, Cfg::LDS_BYTES);
+  (void) hipFuncSetAttribute(reinterpret_cast<const void*>(&rank_k_kernel<T, 0, false, true>),
                              hipFuncAttributeMaxDynamicSharedMemorySize, Cfg::LDS_BYTES);
 }
 
@@ -223,5 +304,9 @@ template void launch_rank_k<float>(const RankKArgs<float>&, hipStream_t);
 template void launch_rank_k<double>(const RankKArgs<double>&, hipStream_t);
 template void launch_rank_k<cfloat>(const RankKArgs<cfloat>&, hipStream_t);
 template void launch_rank_k<cdouble>(const RankKArgs<cdouble>&, hipStream_t);
+template void launch_rank_k_weighted<float>(const RankKArgs<float>&, hipStream_t);
+template void launch_rank_k_weighted<double>(const RankKArgs<double>&, hipStream_t);
+template void launch_rank_k_weighted<cfloat>(const RankKArgs<cfloat>&, hipStream_t);
+template void launch_rank_k_weighted<cdouble>(const RankKArgs<cdouble>&, hipStream_t);
 
 }  // namespace dlaf_mi355x

@@ -216,6 +216,39 @@ void require_rank_update(const char* who, const GridT& g, bool complex_type, cha
     fatal("[dlaf_mi355x] %s: A must start on C's process row (source row %d vs %d)\n", who, a.isrc, c.isrc);
 }
 
+// ---- the weighted rank-k update  C = alpha A D A^H + beta C: require_rank_update's tests (b: none) under its own
+// name, and the weights: d null while they would be read (k > 0 and alpha != 0).  Their values are not judged.
+template <class GridT>
+void require_weighted_rank_update(const GridT& g, bool complex_type, char uplo, char trans, bool alpha_is_zero,
+                                  const OperandDesc& a, const void* d, const OperandDesc& c, char c_stored = 0) {
+  const char* who = "hermitian weighted rank-k update";
+  require_rank_update(who, g, complex_type, uplo, trans, a, nullptr, c, c_stored);
+  const long k = is_notrans(trans) ? a.n : a.m;
+  if (!d && k > 0 && !alpha_is_zero)
+    fatal("[dlaf_mi355x] %s: the weights d are null (k = %ld, alpha != 0)\n", who, k);
+}
+// ---- functions of a Hermitian matrix: uplo 'L' (the eigensolver's); a square matrix in square blocks with its source
+// inside the grid; at most one selection; hermitian_power: threshold >= 0
+template <class GridT>
+void require_hermitian_function(const char* who, const GridT& g, char uplo, const OperandDesc& a, bool by_index,
+                                bool by_value) {
+  if (uplo != 'L' && uplo != 'l')
+    fatal("[dlaf_mi355x] %s: uplo = %c is not implemented (neither by the eigensolver)\n", who, uplo);
+  if (a.m != a.n || a.n < 0)
+    fatal("[dlaf_mi355x] %s: the matrix must be square (%ld x %ld)\n", who, a.m, a.n);
+  if (a.mb != a.nb || a.nb < 1)
+    fatal("[dlaf_mi355x] %s: the matrix needs a square block (%d x %d)\n", who, a.mb, a.nb);
+  if (!source_in_grid(g.nprow, g.npcol, a.isrc, a.jsrc))
+    fatal("[dlaf_mi355x] %s: source rank (%d,%d) outside the %d x %d grid\n", who, a.isrc, a.jsrc, g.nprow, g.npcol);
+  if (by_index && by_value)
+    fatal("[dlaf_mi355x] %s: two selections at once: give an index range or a value interval, not both\n", who);
+}
+inline void require_power_threshold(const char* who, double threshold) {
+  if (!(threshold >= 0))
+    fatal("[dlaf_mi355x] %s: threshold %g < 0: eigenvalues at or below the threshold are dropped, and a negative one "
+          "has no real power\n", who, threshold);
+}
+
 // ---- general addition  C = beta C + alpha op(A) on the uplo part, hermitian_complete and the resident conversions: one
 // judgement for the descriptor entries, the p? entries and the resident ones.  a, c as stored; same_storage: A and C are
 // the same array / handle.  Terminates unless: uplo is A, L or U and op a letter; one square block for both; C is m x n

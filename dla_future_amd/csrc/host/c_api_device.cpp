@@ -224,6 +224,80 @@ int dlaf_mi355x_hermitian_rank_2k_update_device(char uplo, char trans, const voi
                                                 dlaf_mi355x_matrix_t c) noexcept {
   return rank_update_device("hermitian rank-2k update", uplo, trans, alpha, a, b, true, beta, c);
 }
+int dlaf_mi355x_hermitian_weighted_rank_k_update_device(char uplo, char trans, const void* alpha, dlaf_mi355x_gmatrix_t a,
+                                                        const void* d, const void* beta,
+                                                        dlaf_mi355x_matrix_t c) noexcept {
+  const char* who = "hermitian weighted rank-k update";
+  if (!a || !a->m || !c || !c->m || !alpha || !beta)
+    return -1;
+  if (a->ctx != c->ctx)
+    fatal("[dlaf_mi355x] %s: the operands live on different contexts (A %d, C %d)\n", who, a->ctx, c->ctx);
+  if (a->m->type != c->m->type)
+    fatal("[dlaf_mi355x] %s: operands of different element types (A '%c', C '%c')\n", who, a->m->type, c->m->type);
+  char stored = 0;
+  const OperandDesc oa = general_operand(a), oc = triangle_operand(c, &stored);
+  const char t = c->m->type;
+  const bool cx = t == 'c' || t == 'z';
+  const bool alpha_zero = (t == 's' || t == 'c') ? *static_cast<const float*>(alpha) == 0.0f
+                                                 : *static_cast<const double*>(alpha) == 0.0;
+  require_weighted_rank_update(grid_from_context(c->ctx), cx, uplo, trans, alpha_zero, oa, d, oc, stored);
+  // (a null d is the plain update to the driver; it is null only where no weight would be read)
+  return hermitian_rank_update_device(trans, alpha, a->m.get(), nullptr, beta, c->m.get(), d);
+}
+
+// Functions of a resident Hermitian matrix (matrix_function.cpp): A := f(A) in place
+extern "C++" {
+template <class DT>
+static int function_device(const char* who, dlaf_mi355x_matrix_t a, real_t<DT>* w, SpectralWeights fn, void* self,
+                           const long* index_range, const real_t<DT>* value_interval, long* selected) {
+  using R = real_t<DT>;
+  char stored = 0;
+  const OperandDesc oa = triangle_operand(a, &stored);
+  require_hermitian_function(who, grid_from_context(a->ctx), stored, oa, index_range != nullptr,
+                             value_interval != nullptr);
+  SpectralSelection<R> sel(oa.n, index_range, value_interval);
+  if (!sel.by_value)
+    check_eigenvalues_index(who, oa.n, sel.begin, sel.end);
+  const int r = hermitian_function_resident<DT>(static_cast<DeviceMatrix<DT>&>(*a->m), w, sel.by_value ? sel.values : nullptr,
+                                                sel.begin, sel.end, fn, self);
+  if (selected) {
+    selected[0] = sel.begin;
+    selected[1] = sel.end;
+  }
+  return r;
+}
+}  // extern "C++"
+int dlaf_mi355x_hermitian_function_device(dlaf_mi355x_matrix_t a, void* w, void* weights, void* user,
+                                          const long* index_range, const void* value_interval,
+                                          long* selected) noexcept {
+  if (!a || !a->m || !w || !weights)
+    return -1;
+  return dispatch_api_type(a->type, [&](auto* tag) -> int {
+    using DT = std::remove_pointer_t<decltype(tag)>;
+    using R = real_t<DT>;
+    SpectralWeightsCall<R> call{reinterpret_cast<void (*)(long, const R*, long, long, R*, void*)>(weights), user};
+    return function_device<DT>("hermitian function", a, static_cast<R*>(w), &SpectralWeightsCall<R>::call, &call,
+                               index_range, static_cast<const R*>(value_interval), selected);
+  });
+}
+int dlaf_mi355x_hermitian_power_device(dlaf_mi355x_matrix_t a, void* w, double exponent, double threshold,
+                                       long* n_dropped) noexcept {
+  if (!a || !a->m || !w)
+    return -1;
+  require_power_threshold("hermitian power", threshold);
+  return dispatch_api_type(a->type, [&](auto* tag) -> int {
+    using DT = std::remove_pointer_t<decltype(tag)>;
+    using R = real_t<DT>;
+    const R interval[2] = {(R) threshold, std::numeric_limits<R>::infinity()};
+    SpectralPower<R> p{exponent};
+    long sel[2] = {0, 0};
+    const int r = function_device<DT>("hermitian power", a, static_cast<R*>(w), &SpectralPower<R>::call, &p, nullptr,
+                                      interval, sel);
+    if (n_dropped)
+      *n_dropped = sel[0];
+    return r;
+  });
+}
 
 // general_addition / hermitian_complete on resident general matrices, and the conversions between a DeviceMatrix and a
 // general matrix (addition.cpp)

@@ -157,6 +157,60 @@ int rank_update_c(int ctx, char uplo, char trans, typename DevType<HT>::type alp
   return hermitian_rank_update_host<DT>(&g, uplo, trans, alpha, oa, db ? &ob : nullptr, beta, oc);
 }
 
+// The weighted rank-k update  C = alpha A D A^H + beta C  through descriptors: d the k real weights on the host
+template <class HT>
+int weighted_rank_update_c(int ctx, char uplo, char trans, real_of_t<HT> alpha, const HT* a, const DLAF_descriptor& da,
+                           const real_of_t<HT>* d, real_of_t<HT> beta, HT* c, const DLAF_descriptor& dc) {
+  using DT = typename DevType<HT>::type;
+  if (da.i != 0 || da.j != 0 || dc.i != 0 || dc.j != 0)
+    fatal("[dlaf_mi355x] hermitian weighted rank-k update: sub-matrices are not supported: offsets must be 0\n");
+  Grid& g = grid_from_context(ctx);
+  const auto oa = host_operand(a, da);
+  const auto oc = host_operand(c, dc);
+  require_weighted_rank_update(g, TypeInfo<DT>::is_complex, uplo, trans, alpha == real_of_t<HT>(0), oa, d, oc);
+  return hermitian_rank_update_host<DT>(&g, uplo, trans, element_of_real<HT>(alpha), oa, nullptr, beta, oc, d);
+}
+
+// Functions of a Hermitian matrix through a descriptor (matrix_function.cpp): `fn(…, self)` the untyped weights
+// callback; selected (null allowed) receives [begin, end)
+template <class HT>
+int hermitian_function_c(const char* who, int ctx, char uplo, HT* a, const DLAF_descriptor& da, real_of_t<HT>* w,
+                         SpectralWeights fn, void* self, const long* index_range, const real_of_t<HT>* value_interval,
+                         long* selected) {
+  using DT = typename DevType<HT>::type;
+  if (da.i != 0 || da.j != 0)
+    fatal("[dlaf_mi355x] %s: sub-matrices are not supported: offsets must be 0\n", who);
+  Grid& g = grid_from_context(ctx);
+  const auto oa = host_operand(a, da);
+  require_hermitian_function(who, g, uplo, oa, index_range != nullptr, value_interval != nullptr);
+  if (!w)
+    fatal("[dlaf_mi355x] %s: the eigenvalue array w is null\n", who);
+  SpectralSelection<real_of_t<HT>> sel(da.m, index_range, value_interval);
+  if (!sel.by_value)
+    check_eigenvalues_index(who, da.m, sel.begin, sel.end);
+  const int r = hermitian_function_host<DT>(&g, uplo, oa, w, sel.by_value ? sel.values : nullptr, sel.begin, sel.end, fn,
+                                            self);
+  if (selected) {
+    selected[0] = sel.begin;
+    selected[1] = sel.end;
+  }
+  return r;
+}
+template <class HT>
+int hermitian_power_c(int ctx, char uplo, HT* a, const DLAF_descriptor& da, real_of_t<HT>* w, double exponent,
+                      double threshold, long* n_dropped) {
+  using R = real_of_t<HT>;
+  require_power_threshold("hermitian power", threshold);
+  const R interval[2] = {(R) threshold, std::numeric_limits<R>::infinity()};
+  SpectralPower<R> p{exponent};
+  long sel[2] = {0, 0};
+  const int r = hermitian_function_c<HT>("hermitian power", ctx, uplo, a, da, w, &SpectralPower<R>::call, &p, nullptr,
+                                         interval, sel);
+  if (n_dropped)
+    *n_dropped = sel[0];
+  return r;
+}
+
 // ScaLAPACK p?syrk / p?herk (b null) and p?syr2k / p?her2k argument lists
 template <class HT>
 void pxrank_update(char uplo, char trans, int n, int k, typename DevType<HT>::type alpha, const HT* a, int ia, int ja,
@@ -604,6 +658,33 @@ DLAF_MI355X_RANK_UPDATE_ENTRY(d, double, double, double, syrk, syr2k)
 DLAF_MI355X_RANK_UPDATE_ENTRY(c, std::complex<float>, dlaf_complex_c, float, herk, her2k)
 DLAF_MI355X_RANK_UPDATE_ENTRY(z, std::complex<double>, dlaf_complex_z, double, herk, her2k)
 #undef DLAF_MI355X_RANK_UPDATE_ENTRY
+// RS: the letter of the real type (its weights callback)
+#define DLAF_MI355X_WEIGHTED_ENTRY(S, HT, CT, RT, RS)                                                                \
+  int dlaf_mi355x_hermitian_weighted_rank_k_update_##S(int ctx, char uplo, char trans, const RT* alpha, const CT* a,   \
+                                                       DLAF_descriptor desca, const RT* d, const RT* beta, CT* c,     \
+                                                       DLAF_descriptor descc) noexcept {                              \
+    return weighted_rank_update_c<HT>(ctx, uplo, trans, *alpha, reinterpret_cast<const HT*>(a), desca, d, *beta,      \
+                                      reinterpret_cast<HT*>(c), descc);                                              \
+  }                                                                                                                 \
+  int dlaf_mi355x_hermitian_function_##S(int ctx, char uplo, CT* a, DLAF_descriptor desca, RT* w,                      \
+                                         dlaf_mi355x_spectral_weights_##RS weights, void* user,                       \
+                                         const long* index_range, const RT* value_interval,                          \
+                                         long* selected) noexcept {                                                   \
+    if (!weights)                                                                                                   \
+      fatal("[dlaf_mi355x] hermitian function: the weights callback is null\n");                                     \
+    SpectralWeightsCall<RT> call{weights, user};                                                                    \
+    return hermitian_function_c<HT>("hermitian function", ctx, uplo, reinterpret_cast<HT*>(a), desca, w,              \
+                                    &SpectralWeightsCall<RT>::call, &call, index_range, value_interval, selected);   \
+  }                                                                                                                 \
+  int dlaf_mi355x_hermitian_power_##S(int ctx, char uplo, CT* a, DLAF_descriptor desca, RT* w, double exponent,        \
+                                      double threshold, long* n_dropped) noexcept {                                   \
+    return hermitian_power_c<HT>(ctx, uplo, reinterpret_cast<HT*>(a), desca, w, exponent, threshold, n_dropped);      \
+  }
+DLAF_MI355X_WEIGHTED_ENTRY(s, float, float, float, s)
+DLAF_MI355X_WEIGHTED_ENTRY(d, double, double, double, d)
+DLAF_MI355X_WEIGHTED_ENTRY(c, std::complex<float>, dlaf_complex_c, float, s)
+DLAF_MI355X_WEIGHTED_ENTRY(z, std::complex<double>, dlaf_complex_z, double, d)
+#undef DLAF_MI355X_WEIGHTED_ENTRY
 #define DLAF_MI355X_GEADD_ENTRY(S, HT, CT)                                                                            \
   int dlaf_mi355x_general_addition_##S(int ctx, char uplo, char op, const CT* alpha, const CT* a, DLAF_descriptor desca, \
                                        const CT* beta, CT* c, DLAF_descriptor descc) noexcept {                      \

@@ -17,6 +17,9 @@
 
 namespace dlaf_mi355x {
 
+template <class T>
+struct TileMatrix;  // (tile_matrix.hpp)
+
 // op(A) X = alpha B (side L) / X op(A) = alpha B (side R) on the grid, host operands (solver.cpp): a the triangular
 // matrix with one square block, b the m x n matrix, overwritten; b's block along the triangular dimension is a's, the
 // other one is its own.  The arguments must have passed require_triangular (api_checks.hpp).
@@ -73,11 +76,39 @@ int general_multiplication_device(char opa, char opb, const void* alpha, MatrixB
 // beta == 1 nothing is touched.  Trans N on any grid, trans C on one process.  The arguments must have passed
 // require_rank_update (api_checks.hpp).  Host and resident forms (resident: C a DeviceMatrix whose stored triangle is
 // uplo, a / b general matrices, b null for herk; alpha points to a real for herk, to an element for her2k).
+// d (herk only; null: the plain update): the weighted update  C = alpha A D A^H + beta C (trans N) / alpha A^H D A + beta C
+// (trans C), D = diag(d) REAL of any sign -- a HOST array of k reals, the same on every rank (the caller's duty, as for
+// alpha), uploaded once; the kernel multiplies d into one operand between its global load and its LDS image, no scaled
+// copy of A exists.  herk's semantics hold; alpha == 0 or k == 0: d is not referenced either.  A zero weight does NOT
+// unreference its column (0 * NaN is NaN); non-finite weights are not judged.  The arguments must have passed
+// require_weighted_rank_update.
 template <class T>
 int hermitian_rank_update_host(Grid* g, char uplo, char trans, T alpha, HostOperand<const T> a,
-                               const HostOperand<const T>* b, real_t<T> beta, HostOperand<T> c);
+                               const HostOperand<const T>* b, real_t<T> beta, HostOperand<T> c,
+                               const real_t<T>* d = nullptr);
 int hermitian_rank_update_device(char trans, const void* alpha, MatrixBase* a, MatrixBase* b, const void* beta,
-                                 MatrixBase* c);
+                                 MatrixBase* c, const void* d = nullptr);
+// C = alpha A D A^H + beta C on a resident C (stored triangle: its own) and ALL k columns of the resident tile matrix A
+// (on C's grid and row source): the synthesis step of matrix_function.cpp
+template <class T>
+void hermitian_weighted_update_resident(DeviceMatrix<T>& C, TileMatrix<T>& A, const real_t<T>* d_host, long k, T alpha,
+                                        real_t<T> beta);
+
+// Functions of a Hermitian matrix (matrix_function.cpp): the uplo ('L': what the eigensolver takes) triangle of the
+// resident A becomes that of  sum_{j selected} g_j z_j z_j^H  with (w, Z) A's eigenpairs and g = weights(w): the
+// eigensolver on A (hermitian_eigensolver_device: all pairs, the index range [begin, end), or, by_value, the value
+// interval (vl, vu]), ONE call of `weights` on the host with all n eigenvalues and the selected range -- it fills
+// g[begin, end) --, then the weighted update with trans N, beta = 0 into A itself; Z never leaves HBM.  Unselected
+// eigenvalues weigh 0 by definition and their eigenvectors are never computed; an empty selection gives a zero triangle.
+// w_host: all n eigenvalues.  Returns the eigensolver's status (agreed over the grid); non-zero: A holds what the
+// eigensolver left and the host form leaves the caller's array unchanged.  The host form downloads the triangle alone.
+using SpectralWeights = void (*)(long n, const void* w, long begin, long end, void* g, void* user);
+template <class T>
+int hermitian_function_resident(DeviceMatrix<T>& A, real_t<T>* w_host, const real_t<T>* by_value, long& begin, long& end,
+                                SpectralWeights weights, void* user);
+template <class T>
+int hermitian_function_host(Grid* g, char uplo, HostOperand<T> a, real_t<T>* w_host, const real_t<T>* by_value, long& begin,
+                            long& end, SpectralWeights weights, void* user);
 
 // C = beta C + alpha op(A) on the uplo part (A all, L i >= j, U i <= j) of the m x n matrix C (addition.cpp; PBLAS p?geadd /
 // p?tradd, p?tran / p?tranu / p?tranc, ScaLAPACK p?lacpy): op N, T, C; A as stored, m x n for N and n x m for T / C, one

@@ -867,7 +867,15 @@ int hermitian_gen_eigenvalues_host(Grid* g, char uplo, HostOperand<const T> a, H
   return info;
 }
 
+template <class T>
+int hermitian_eigensolver_resident(DeviceMatrix<T>& A, real_t<T>* w_host, const real_t<T>* by_value, long& begin, long& end,
+                                   std::unique_ptr<MatrixBase>& zh, PartialSpectrumPlan& pl) {
+  return hermitian_eigensolver_device(A, w_host, A.rows.src, A.cols.src, by_value, begin, end, zh, pl);
+}
+
 #define INST(T)                                                                                                          \
+  template int hermitian_eigensolver_resident<T>(DeviceMatrix<T>&, real_t<T>*, const real_t<T>*, long&, long&,           \
+                                                 std::unique_ptr<MatrixBase>&, PartialSpectrumPlan&);                    \
   template int hermitian_eigensolver_host<T>(Grid*, char, HostOperand<T>, real_t<T>*, HostOperand<T>, long, long);       \
   template int hermitian_gen_eigensolver_host<T>(Grid*, char, HostOperand<T>, HostOperand<T>, real_t<T>*, HostOperand<T>, \
                                                  bool, long, long);                                                      \

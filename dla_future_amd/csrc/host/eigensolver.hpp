@@ -2,6 +2,8 @@
 // band -> tridiagonal, tridiagonal eigensolver, back-transformation band <- tridiagonal, and the drivers
 // (include/dlaf/eigensolver/eigensolver/impl.h:38-55).
 #pragma once
+#include <memory>
+
 #include "device_matrix.hpp"
 #include "red2band.hpp"
 #include "tile_matrix.hpp"
@@ -104,6 +106,14 @@ struct PartialSpectrumPlan {
 // 0 <= begin <= end <= n, or fatal (before anything touches the GPU)
 void check_eigenvalues_index(const char* who, long n, long begin, long end);
 PartialSpectrumPlan partial_spectrum_plan(long n, int nb, int npcol, int mycol, int z_jsrc, long begin, long end);
+
+// The eigensolver on a RESIDENT A (an uplo 'L' DeviceMatrix, destroyed): w_host receives all n eigenvalues; zh the
+// internal general matrix (n x (end - pl.b0), A's grid, block and row source, resident) whose columns behind the zero
+// padding [pl.b0, begin) are the eigenvectors of [begin, end).  by_value = {vl, vu}: the range is found and returned as
+// the _by_value_host entries do.  Returns the status agreed over the grid.  (matrix_function.cpp builds on it.)
+template <class T>
+int hermitian_eigensolver_resident(DeviceMatrix<T>& A, real_t<T>* w_host, const real_t<T>* by_value, long& begin, long& end,
+                                   std::unique_ptr<MatrixBase>& zh, PartialSpectrumPlan& pl);
 
 // per-stage device times (ms) of the last eigensolver call on this process:
 // 0 reduction_to_band, 1 band_to_tridiagonal, 2 tridiagonal solver (the bisection of an eigenvalues-only call),

@@ -2,6 +2,7 @@
 // of C on a kernel that keeps a block of C in its accumulators over the k dimension (kernels_herk.hip):
 //        herk  : C = alpha A A^H + beta C (trans N)            alpha A^H A + beta C (trans C)
 //        her2k : C = alpha A B^H + conj(alpha) B A^H + beta C  alpha A^H B + conj(alpha) B^H A + beta C
+//        weighted herk : C = alpha A D A^H + beta C (trans N)    alpha A^H D A + beta C (trans C),  D a real diagonal
 // alpha of herk and every beta are real.  BLAS semantics: the other triangle of C is never referenced; the imaginary
 // part of C's diagonal is ignored on entry and exactly 0 on exit; beta == 0: C is not read; alpha == 0 or k == 0: A and
 // B are not referenced; then with beta == 1 nothing at all is touched.
@@ -34,10 +35,14 @@ namespace dlaf_mi355x {
 namespace {
 
 // Ad (and Bd, her2k; null: herk): the operands AS STORED, n x k (trans N) or k x n; nkt: the k tiles to multiply
-// (0: k == 0 or alpha == 0 -- the triangle becomes beta C, Ad and Bd are not touched)
+// (0: k == 0 or alpha == 0 -- the triangle becomes beta C, Ad, Bd and d_host are not touched).
+// d_host (herk only; null: the plain update): the k real weights of the weighted update C = alpha A D A^H + beta C, a
+// HOST array, the same on every rank; uploaded once (k reals) into a pool workspace, the kernel multiplies them into the
+// row operand on its way to LDS (launch_rank_k_weighted).  One process: one launch, the pointer at weight 0; a grid: the
+// pointer advanced by l nb at step l.
 template <class T>
-void rank_update_canonical(DeviceMatrix<T>& C, TileMatrix<T>* Ad, TileMatrix<T>* Bd, bool trans_n, long k, long nkt,
-                           T alpha, real_t<T> beta) {
+void rank_update_canonical(DeviceMatrix<T>& C, TileMatrix<T>* Ad, TileMatrix<T>* Bd, const real_t<T>* d_host, bool trans_n,
+                           long k, long nkt, T alpha, real_t<T> beta) {
   Grid* g = C.grid;
   Transport* tr = grid_transport(*g);
   const bool dist = g->nranks > 1;
@@ -69,6 +74,20 @@ void rank_update_canonical(DeviceMatrix<T>& C, TileMatrix<T>* Ad, TileMatrix<T>*
 
   Sweep sw(false, false);
   const hipStream_t s_main = sw.s_main, s_comm = sw.s_comm;
+  const bool weighted = d_host != nullptr && nkt > 0;
+  PoolScope ws;
+  const real_t<T>* dw = nullptr;
+  if (weighted) {
+    real_t<T>* w = ws.get<real_t<T>>((size_t) k);
+    DLAF_HIP_CHECK(hipMemcpyAsync(w, d_host, (size_t) k * sizeof(real_t<T>), hipMemcpyHostToDevice, s_main));
+    dw = w;
+  }
+  auto launch = [&] {
+    if (weighted)
+      launch_rank_k_weighted(ra, s_main);
+    else
+      launch_rank_k(ra, s_main);
+  };
   if (nkt == 0 || !dist) {
     sw.begin(false);
     if (nkt > 0) {
@@ -80,9 +99,10 @@ void rank_update_canonical(DeviceMatrix<T>& C, TileMatrix<T>* Ad, TileMatrix<T>*
         ra.x2 = ra.y2 = Bd->tiles;
       ra.nk = (int) nkt;
       ra.k_last = (trans_n ? Ad->cols : Ad->rows).last_extent();
+      ra.kw = dw;
     }
     if (work)
-      launch_rank_k(ra, s_main);
+      launch();
   }
   else {
     // in terms of the caller's C: its tile rows are spread like A's (the same axis), its tile columns over the
@@ -126,12 +146,14 @@ void rank_update_canonical(DeviceMatrix<T>& C, TileMatrix<T>* Ad, TileMatrix<T>*
         ra.nk = 1;
         ra.k_last = ka.tile_extent(l);
         ra.first = l == 0 ? 1 : 0;
-        launch_rank_k(ra, s_main);
+        ra.kw = weighted ? dw + l * C.nb : nullptr;
+        launch();
       }
     };
     pipe.run(sw, fetch, apply);
   }
   const double ms = sw.finish();
+  ws.release();
   // whole-grid algorithmic flops: k n (n + 1) per product (x4 complex)
   multiplication_set_profile(ms, (TypeInfo<T>::is_complex ? 4.0 : 1.0) * (two ? 2.0 : 1.0) * (double) k * (double) C.n *
                                      (double) (C.n + 1));
@@ -141,7 +163,7 @@ void rank_update_canonical(DeviceMatrix<T>& C, TileMatrix<T>* Ad, TileMatrix<T>*
 
 template <class T>
 int hermitian_rank_update_host(Grid* g, char uplo, char trans, T alpha, HostOperand<const T> a,
-                               const HostOperand<const T>* b, real_t<T> beta, HostOperand<T> c) {
+                               const HostOperand<const T>* b, real_t<T> beta, HostOperand<T> c, const real_t<T>* d) {
   if (c.n == 0)
     return 0;
   const bool tn = herk_trans_is_n(trans);
@@ -167,7 +189,7 @@ int hermitian_rank_update_host(Grid* g, char uplo, char trans, T alpha, HostOper
   const bool read_c = beta != real_t<T>(0);  // beta = 0: C is not read
   if (read_c)
     Cd.upload(c.p, c.ld);
-  rank_update_canonical<T>(Cd, product ? &Ad : nullptr, (product && b) ? &Bd : nullptr, tn, k,
+  rank_update_canonical<T>(Cd, product ? &Ad : nullptr, (product && b) ? &Bd : nullptr, product ? d : nullptr, tn, k,
                            product ? (k + nb - 1) / nb : 0, alpha, beta);
   Cd.download(c.p, c.ld, read_c);
   return 0;
@@ -176,8 +198,8 @@ int hermitian_rank_update_host(Grid* g, char uplo, char trans, T alpha, HostOper
 // The same on RESIDENT operands (arguments judged by the entry, c_api_device.cpp): C a DeviceMatrix whose stored triangle
 // is uplo, A (and B; null: herk) general resident matrices.  alpha: real_t<T> for herk, T for her2k; beta: real_t<T>.
 int hermitian_rank_update_device(char trans, const void* alpha, MatrixBase* a, MatrixBase* b, const void* beta,
-                                 MatrixBase* c) {
-  const char* who = b ? "hermitian rank-2k update" : "hermitian rank-k update";
+                                 MatrixBase* c, const void* d) {
+  const char* who = b ? "hermitian rank-2k update" : (d ? "hermitian weighted rank-k update" : "hermitian rank-k update");
   if (!a || !c || a->type != c->type || (b && b->type != c->type))
     fatal("[dlaf_mi355x] %s: operands of different element types\n", who);
   return dispatch_type(c->type, [&](auto* tag) {
@@ -203,15 +225,28 @@ int hermitian_rank_update_device(char trans, const void* alpha, MatrixBase* a, M
     const bool product = k > 0 && !is_zero(al);
     if (!product && be == R(1))
       return 0;
-    rank_update_canonical<T>(C, product ? &A.m : nullptr, (product && B) ? &B->m : nullptr, tn, k,
-                             product ? (k + C.nb - 1) / C.nb : 0, al, be);
+    rank_update_canonical<T>(C, product ? &A.m : nullptr, (product && B) ? &B->m : nullptr,
+                             product ? static_cast<const R*>(d) : nullptr, tn, k, product ? (k + C.nb - 1) / C.nb : 0, al,
+                             be);
     return 0;
   });
 }
 
+// The weighted update on a resident C and the resident A `a` of which only the leading k columns (trans N) are
+// multiplied -- the eigenvector matrix of a partial spectrum behind matrix_function.cpp, whose own k is all of them.
+template <class T>
+void hermitian_weighted_update_resident(DeviceMatrix<T>& C, TileMatrix<T>& A, const real_t<T>* d_host, long k, T alpha,
+                                        real_t<T> beta) {
+  const bool product = k > 0 && !is_zero(alpha);
+  rank_update_canonical<T>(C, product ? &A : nullptr, nullptr, product ? d_host : nullptr, true, k,
+                           product ? (k + C.nb - 1) / C.nb : 0, alpha, beta);
+}
+
 #define DLAF_RANK_UPDATE_INST(T)                                                                                     \
   template int hermitian_rank_update_host<T>(Grid*, char, char, T, HostOperand<const T>, const HostOperand<const T>*, \
-                                             real_t<T>, HostOperand<T>);
+                                             real_t<T>, HostOperand<T>, const real_t<T>*);                            \
+  template void hermitian_weighted_update_resident<T>(DeviceMatrix<T>&, TileMatrix<T>&, const real_t<T>*, long, T,    \
+                                                      real_t<T>);
 DLAF_RANK_UPDATE_INST(float)
 DLAF_RANK_UPDATE_INST(double)
 DLAF_RANK_UPDATE_INST(cfloat)

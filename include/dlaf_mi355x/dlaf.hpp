@@ -595,6 +595,113 @@ void hermitian_rank_2k_update(blas::Uplo uplo, blas::Op op, const T alpha, const
   hermitian_rank_2k_update<B, D, T>(grid, uplo, op, alpha, mat_a, mat_b, beta, mat_c);
 }
 
+// The weighted rank-k update ("xSYRK / xHERK with weights"): the uplo triangle of mat_c becomes
+//   alpha A D A^H + beta C (NoTrans, A n x k) / alpha A^H D A + beta C (ConjTrans, A k x n),  D = diag(d) REAL, any sign;
+// d: k reals on the host, the same on every rank.  The weights are multiplied in inside the rank-k kernel: no scaled copy
+// of A, the flops of a rank-k update.  Semantics and requirements of hermitian_rank_k_update; a zero weight does NOT
+// unreference its column (0 * NaN is NaN).
+template <Backend B, Device D, class T>
+void hermitian_weighted_rank_k_update(comm::CommunicatorGrid& grid, blas::Uplo uplo, blas::Op op, const BaseType<T> alpha,
+                                      const Matrix<T, Device::CPU>& mat_a, const BaseType<T>* d, const BaseType<T> beta,
+                                      Matrix<T, Device::CPU>& mat_c) {
+  static_assert(B == Backend::GPU, "this library has no CPU backend");
+  const DLAF_descriptor da = internal::rank_update_descriptor(mat_a), dc = internal::rank_update_descriptor(mat_c);
+  int r;
+  if constexpr (std::is_same_v<T, float>)
+    r = dlaf_mi355x_hermitian_weighted_rank_k_update_s(grid.context(), (char) uplo, (char) op, &alpha, mat_a.ptr(), da, d,
+                                                       &beta, mat_c.ptr(), dc);
+  else if constexpr (std::is_same_v<T, double>)
+    r = dlaf_mi355x_hermitian_weighted_rank_k_update_d(grid.context(), (char) uplo, (char) op, &alpha, mat_a.ptr(), da, d,
+                                                       &beta, mat_c.ptr(), dc);
+  else if constexpr (std::is_same_v<T, std::complex<float>>)
+    r = dlaf_mi355x_hermitian_weighted_rank_k_update_c(grid.context(), (char) uplo, (char) op, &alpha, mat_a.ptr(), da, d,
+                                                       &beta, mat_c.ptr(), dc);
+  else
+    r = dlaf_mi355x_hermitian_weighted_rank_k_update_z(grid.context(), (char) uplo, (char) op, &alpha, mat_a.ptr(), da, d,
+                                                       &beta, mat_c.ptr(), dc);
+  if (r != 0)
+    internal::fail("hermitian_weighted_rank_k_update");
+}
+template <Backend B, Device D, class T>
+void hermitian_weighted_rank_k_update(blas::Uplo uplo, blas::Op op, const BaseType<T> alpha,
+                                      const Matrix<T, Device::CPU>& mat_a, const BaseType<T>* d, const BaseType<T> beta,
+                                      Matrix<T, Device::CPU>& mat_c) {
+  comm::CommunicatorGrid grid = comm::CommunicatorGrid::single();
+  hermitian_weighted_rank_k_update<B, D, T>(grid, uplo, op, alpha, mat_a, d, beta, mat_c);
+}
+
+// Functions of a Hermitian matrix: the Lower triangle of mat_a becomes that of f(A) = sum_j g_j z_j z_j^H over the selected
+// eigenpairs, g = weights(w): the eigensolver, ONE call of `weights`, and the weighted rank-k update with the eigenvectors
+// still in HBM.  weights(n, w, begin, end, g) writes g[begin, end).  selection: all eigenpairs (default), an index range
+// [begin, end), or a value interval (vl, vu]; unselected eigenvalues weigh 0 and their eigenvectors are never computed.
+// Returns the eigensolver's status; `eigenvalues` (n reals) receives all eigenvalues, `selected` (null allowed) the
+// selected [begin, end).  hermitian_power: x^exponent above `threshold` (>= 0), the rest dropped and counted.
+template <class R>
+using SpectralWeights = std::function<void(SizeType n, const R* w, SizeType begin, SizeType end, R* g)>;
+template <class R>
+struct SpectralSelection {
+  const SizeType* index_range = nullptr;  // {begin, end}
+  const R* value_interval = nullptr;      // {vl, vu}
+};
+namespace internal {
+template <class R>
+void spectral_weights_trampoline(long n, const R* w, long begin, long end, R* g, void* user) {
+  (*static_cast<const SpectralWeights<R>*>(user))(n, w, begin, end, g);
+}
+}  // namespace internal
+template <Backend B, Device D, class T>
+int hermitian_function(comm::CommunicatorGrid& grid, blas::Uplo uplo, Matrix<T, Device::CPU>& mat_a,
+                       BaseType<T>* eigenvalues, const SpectralWeights<BaseType<T>>& weights,
+                       SpectralSelection<BaseType<T>> selection = {}, SizeType* selected = nullptr) {
+  static_assert(B == Backend::GPU, "this library has no CPU backend");
+  using R = BaseType<T>;
+  const DLAF_descriptor da = internal::rank_update_descriptor(mat_a);
+  void* user = const_cast<SpectralWeights<R>*>(&weights);
+  long range[2] = {0, 0}, sel[2] = {0, 0};
+  if (selection.index_range) {
+    range[0] = (long) selection.index_range[0];
+    range[1] = (long) selection.index_range[1];
+  }
+  const long* ir = selection.index_range ? range : nullptr;
+  int r;
+  if constexpr (std::is_same_v<T, float>)
+    r = dlaf_mi355x_hermitian_function_s(grid.context(), (char) uplo, mat_a.ptr(), da, eigenvalues,
+                                         &internal::spectral_weights_trampoline<R>, user, ir, selection.value_interval, sel);
+  else if constexpr (std::is_same_v<T, double>)
+    r = dlaf_mi355x_hermitian_function_d(grid.context(), (char) uplo, mat_a.ptr(), da, eigenvalues,
+                                         &internal::spectral_weights_trampoline<R>, user, ir, selection.value_interval, sel);
+  else if constexpr (std::is_same_v<T, std::complex<float>>)
+    r = dlaf_mi355x_hermitian_function_c(grid.context(), (char) uplo, mat_a.ptr(), da, eigenvalues,
+                                         &internal::spectral_weights_trampoline<R>, user, ir, selection.value_interval, sel);
+  else
+    r = dlaf_mi355x_hermitian_function_z(grid.context(), (char) uplo, mat_a.ptr(), da, eigenvalues,
+                                         &internal::spectral_weights_trampoline<R>, user, ir, selection.value_interval, sel);
+  if (selected) {
+    selected[0] = (SizeType) sel[0];
+    selected[1] = (SizeType) sel[1];
+  }
+  return r;
+}
+template <Backend B, Device D, class T>
+int hermitian_power(comm::CommunicatorGrid& grid, blas::Uplo uplo, Matrix<T, Device::CPU>& mat_a, BaseType<T>* eigenvalues,
+                    double exponent, double threshold = 0.0, SizeType* n_dropped = nullptr) {
+  static_assert(B == Backend::GPU, "this library has no CPU backend");
+  const DLAF_descriptor da = internal::rank_update_descriptor(mat_a);
+  long dropped = 0;
+  int r;
+  if constexpr (std::is_same_v<T, float>)
+    r = dlaf_mi355x_hermitian_power_s(grid.context(), (char) uplo, mat_a.ptr(), da, eigenvalues, exponent, threshold, &dropped);
+  else if constexpr (std::is_same_v<T, double>)
+    r = dlaf_mi355x_hermitian_power_d(grid.context(), (char) uplo, mat_a.ptr(), da, eigenvalues, exponent, threshold, &dropped);
+  else if constexpr (std::is_same_v<T, std::complex<float>>)
+    r = dlaf_mi355x_hermitian_power_c(grid.context(), (char) uplo, mat_a.ptr(), da, eigenvalues, exponent, threshold, &dropped);
+  else
+    r = dlaf_mi355x_hermitian_power_z(grid.context(), (char) uplo, mat_a.ptr(), da, eigenvalues, exponent, threshold, &dropped);
+  if (n_dropped)
+    *n_dropped = (SizeType) dropped;
+  return r;
+}
+
 // C = beta C + alpha op(A) on the uplo part of mat_c (PBLAS p?geadd / p?tradd, p?tran / p?tranu / p?tranc; ScaLAPACK
 // p?lacpy is alpha 1, beta 0, NoTrans) and the completion of a Hermitian / symmetric matrix from one triangle, on
 // host-resident operands.  The reference has no such algorithm (its matrix::copy is the alpha 1, beta 0, NoTrans case);

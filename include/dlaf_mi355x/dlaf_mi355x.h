@@ -373,6 +373,87 @@ DLAF_EXTERN_C void dlaf_mi355x_pzher2k(char uplo, char trans, int n, int k, cons
                                        const int descb[9], const double* beta, dlaf_complex_z* c, int ic, int jc,
                                        const int descc[9]) DLAF_NOEXCEPT;
 
+/* ---- weighted Hermitian rank-k update and functions of a Hermitian matrix -------------------- */
+/* "xSYRK / xHERK with weights": the uplo triangle of
+ *     trans 'N':  C = alpha A D A^H + beta C,  A stored n x k        trans 'C':  C = alpha A^H D A + beta C,  A stored k x n
+ * with D = diag(d) a REAL diagonal of any sign (also the normal-equations product A D A^T); alpha and beta are REAL.  d:
+ * k reals in HOST memory, the SAME on every rank of the grid (the caller's duty, as for alpha); they are uploaded once
+ * (k reals) and multiplied into one operand inside the rank-k kernel, between its global load and its LDS image: no
+ * scaled copy of A is made and the flops are those of a rank-k update, k n (n + 1).  PBLAS has no such routine, hence no
+ * p? names.  Real types also accept trans 'T'; complex types refuse it.
+ * Semantics are those of the rank-k update above: the other triangle of C is never referenced; the imaginary part of C's
+ * diagonal is ignored on entry and exactly 0 on exit; beta = 0: C is not read; alpha = 0 or k = 0: A AND d are not
+ * referenced (d may be null then) and the triangle becomes beta C; with beta = 1 on top of that nothing is touched;
+ * n = 0 returns before the GPU is touched.  A ZERO weight does NOT unreference its column: 0 * NaN is NaN, as in
+ * A diag(d) A^H computed by hand.  Non-finite weights are not judged.
+ * One process: both trans.  More than one process: trans 'N' only, A on C's process row.  Requirements of the rank-k
+ * update, plus: d non-null while k > 0 and alpha != 0.  A violated one terminates with "hermitian weighted rank-k
+ * update: ..." before the GPU is touched. */
+DLAF_EXTERN_C int dlaf_mi355x_hermitian_weighted_rank_k_update_s(int context, char uplo, char trans, const float* alpha,
+                                                                 const float* a, struct DLAF_descriptor desca,
+                                                                 const float* d, const float* beta, float* c,
+                                                                 struct DLAF_descriptor descc) DLAF_NOEXCEPT;
+DLAF_EXTERN_C int dlaf_mi355x_hermitian_weighted_rank_k_update_d(int context, char uplo, char trans, const double* alpha,
+                                                                 const double* a, struct DLAF_descriptor desca,
+                                                                 const double* d, const double* beta, double* c,
+                                                                 struct DLAF_descriptor descc) DLAF_NOEXCEPT;
+DLAF_EXTERN_C int dlaf_mi355x_hermitian_weighted_rank_k_update_c(int context, char uplo, char trans, const float* alpha,
+                                                                 const dlaf_complex_c* a, struct DLAF_descriptor desca,
+                                                                 const float* d, const float* beta, dlaf_complex_c* c,
+                                                                 struct DLAF_descriptor descc) DLAF_NOEXCEPT;
+DLAF_EXTERN_C int dlaf_mi355x_hermitian_weighted_rank_k_update_z(int context, char uplo, char trans, const double* alpha,
+                                                                 const dlaf_complex_z* a, struct DLAF_descriptor desca,
+                                                                 const double* d, const double* beta, dlaf_complex_z* c,
+                                                                 struct DLAF_descriptor descc) DLAF_NOEXCEPT;
+/* Functions of a Hermitian matrix: the uplo triangle of the n x n matrix A becomes that of
+ *     f(A) = sum over the selected j of  g_j z_j z_j^H,    (w, Z) the eigenpairs of A,  g = weights(w)
+ * (a density matrix, a spectral projector, S^(-1/2), a square root, an inverse or pseudo-inverse, an exponential): the
+ * eigensolver on A, ONE call of `weights` on the host, and the weighted rank-k update above (trans 'N', beta 0) with the
+ * eigenvectors still in HBM: Z is never downloaded, only the triangle is.
+ *   uplo            'L' (what the eigensolver takes).
+ *   w               n reals: all eigenvalues, ascending, as the eigensolver gives them, on every rank.
+ *   weights         called once per rank with (n, w, begin, end, g, user): it writes g[j] for begin <= j < end and nothing
+ *                   else (g has n entries).  Every rank must compute the same weights.
+ *   index_range     null, or {begin, end}: the 0-based half-open range of eigenvalue indices that take part.
+ *   value_interval  null, or {vl, vu}: the eigenvalues in (vl, vu] take part (infinite ends allowed).
+ *                   Both null: all n.  Both given: refused.  Eigenvalues that are not selected have weight 0 by
+ *                   definition, and their eigenvectors are never computed.  An empty selection gives a zero triangle.
+ *   selected        null, or two longs that receive the selected [begin, end).
+ * Returns the eigensolver's status, agreed over the grid; when it is not 0 the caller's a is unchanged.  The other
+ * triangle of a is never touched; the diagonal of a complex result is exactly real.  A violated requirement terminates
+ * with "hermitian function: ..." before the GPU is touched.
+ * hermitian_power: f = x^exponent on the eigenvalues above `threshold` (>= 0, else refused), the others DROPPED (weight
+ * 0: the pseudo-inverse for exponent -1, Loewdin's S^(-1/2) for -1/2).  It is the value interval (threshold, +inf): the
+ * dropped eigenvectors are not computed and *n_dropped (null allowed) is the Sturm count of `threshold`. */
+typedef void (*dlaf_mi355x_spectral_weights_s)(long n, const float* w, long begin, long end, float* g, void* user);
+typedef void (*dlaf_mi355x_spectral_weights_d)(long n, const double* w, long begin, long end, double* g, void* user);
+DLAF_EXTERN_C int dlaf_mi355x_hermitian_function_s(int context, char uplo, float* a, struct DLAF_descriptor desca, float* w,
+                                                   dlaf_mi355x_spectral_weights_s weights, void* user,
+                                                   const long* index_range, const float* value_interval,
+                                                   long* selected) DLAF_NOEXCEPT;
+DLAF_EXTERN_C int dlaf_mi355x_hermitian_function_d(int context, char uplo, double* a, struct DLAF_descriptor desca, double* w,
+                                                   dlaf_mi355x_spectral_weights_d weights, void* user,
+                                                   const long* index_range, const double* value_interval,
+                                                   long* selected) DLAF_NOEXCEPT;
+DLAF_EXTERN_C int dlaf_mi355x_hermitian_function_c(int context, char uplo, dlaf_complex_c* a, struct DLAF_descriptor desca,
+                                                   float* w, dlaf_mi355x_spectral_weights_s weights, void* user,
+                                                   const long* index_range, const float* value_interval,
+                                                   long* selected) DLAF_NOEXCEPT;
+DLAF_EXTERN_C int dlaf_mi355x_hermitian_function_z(int context, char uplo, dlaf_complex_z* a, struct DLAF_descriptor desca,
+                                                   double* w, dlaf_mi355x_spectral_weights_d weights, void* user,
+                                                   const long* index_range, const double* value_interval,
+                                                   long* selected) DLAF_NOEXCEPT;
+DLAF_EXTERN_C int dlaf_mi355x_hermitian_power_s(int context, char uplo, float* a, struct DLAF_descriptor desca, float* w,
+                                                double exponent, double threshold, long* n_dropped) DLAF_NOEXCEPT;
+DLAF_EXTERN_C int dlaf_mi355x_hermitian_power_d(int context, char uplo, double* a, struct DLAF_descriptor desca, double* w,
+                                                double exponent, double threshold, long* n_dropped) DLAF_NOEXCEPT;
+DLAF_EXTERN_C int dlaf_mi355x_hermitian_power_c(int context, char uplo, dlaf_complex_c* a, struct DLAF_descriptor desca,
+                                                float* w, double exponent, double threshold,
+                                                long* n_dropped) DLAF_NOEXCEPT;
+DLAF_EXTERN_C int dlaf_mi355x_hermitian_power_z(int context, char uplo, dlaf_complex_z* a, struct DLAF_descriptor desca,
+                                                double* w, double exponent, double threshold,
+                                                long* n_dropped) DLAF_NOEXCEPT;
+
 /* general_addition: C = beta C + alpha op(A) on the uplo part of the m x n matrix C -- PBLAS p?geadd (uplo 'A') and
  * p?tradd, the transpositions p?tran / p?tranu / p?tranc (op 'T' / 'C'), ScaLAPACK p?lacpy (alpha 1, beta 0, op 'N').
  *   uplo 'A': every element, 'L': i >= j, 'U': i <= j (for m != n the trapezoids of xLACPY)
@@ -918,6 +999,22 @@ DLAF_EXTERN_C int dlaf_mi355x_hermitian_rank_k_update_device(char uplo, char tra
 DLAF_EXTERN_C int dlaf_mi355x_hermitian_rank_2k_update_device(char uplo, char trans, const void* alpha,
                                                               dlaf_mi355x_gmatrix_t a, dlaf_mi355x_gmatrix_t b,
                                                               const void* beta, dlaf_mi355x_matrix_t c) DLAF_NOEXCEPT;
+/* The weighted rank-k update on resident operands: as dlaf_mi355x_hermitian_rank_k_update_device, with d the k real
+ * weights of c's precision in HOST memory (null only while k = 0 or alpha = 0). */
+DLAF_EXTERN_C int dlaf_mi355x_hermitian_weighted_rank_k_update_device(char uplo, char trans, const void* alpha,
+                                                                      dlaf_mi355x_gmatrix_t a, const void* d,
+                                                                      const void* beta,
+                                                                      dlaf_mi355x_matrix_t c) DLAF_NOEXCEPT;
+/* Functions of a resident Hermitian matrix, A := f(A) in place (a created with uplo 'L'): w receives the n eigenvalues
+ * (reals of a's precision); weights is a dlaf_mi355x_spectral_weights_s (types s, c) or _d (d, z); value_interval points
+ * to two reals of a's precision; exponent and threshold are doubles.  Nothing but w crosses PCIe.  Semantics and
+ * requirements of the host entries; a null handle or w returns -1; on a non-zero status a holds what the eigensolver
+ * left there. */
+DLAF_EXTERN_C int dlaf_mi355x_hermitian_function_device(dlaf_mi355x_matrix_t a, void* w, void* weights, void* user,
+                                                        const long* index_range, const void* value_interval,
+                                                        long* selected) DLAF_NOEXCEPT;
+DLAF_EXTERN_C int dlaf_mi355x_hermitian_power_device(dlaf_mi355x_matrix_t a, void* w, double exponent, double threshold,
+                                                     long* n_dropped) DLAF_NOEXCEPT;
 /* general_addition / hermitian_complete on resident general matrices of one context and element type (a as stored; only
  * c's uplo part is written; the same handle twice is op 'N' in place), and the resident conversions between a
  * dlaf_mi355x_matrix_t (one triangle) and a general matrix of the same context, type, order, block and source process,

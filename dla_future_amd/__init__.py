@@ -23,22 +23,33 @@ Python doorway onto that ABI, mirroring the reference's operator surface for the
     generalized_to_standard(grid, uplo, A, B)          include/dlaf/eigensolver/gen_to_std.h:50,:101
     reduction_to_band / bt_reduction_to_band           include/dlaf/eigensolver/reduction_to_band.h:40-122, bt_reduction_to_band.h
 
+One module per owner, named after the host sources (csrc/host/*.cpp): grid, device_matrix, cholesky, solver,
+multiplication, rank_update, addition, inverse, norm, gen_to_std, eigensolver, matrix_function, distribution, and direct
+(the tile operations and the one-launch doors of the kernels).  capi holds the ctypes signature table, _abi the few lines
+every wrapper shares.  Everything public is re-exported here.
+
 There is no CPU fallback: importing works anywhere, every compute call needs the HIP library
 and a GPU and fails loudly otherwise.
 """
 from .capi import (DLAFDescriptor, LibraryNotBuilt, lib, lib_path, type_char, version)  # noqa: F401
-from .cholesky import (DeviceMatrix, GeneralDeviceMatrix, Grid, cholesky_factorization, finalize, generalized_to_standard,  # noqa: F401
-                       initialize, make_descriptor, potrf_trace, pxhegst, pxpotrf, pxpotrs, pxtrsm, set_random_hermitian_positive_definite, tile_gemm, tile_herk, tile_potrf,
-                       tile_trsm, triangular_solver, triangular_solver_device, potrs_device, release_workspace_pool, solver_profile,
-                       triangular_inverse, inverse_from_cholesky_factor, pxtrtri, pxpotri, inverse_profile,
-                       update_launch_stats, multiplication_profile, pxtrmm, triangular_multiplication,
-                       triangular_multiplication_device, hermitian_multiplication, hermitian_multiplication_device,
-                       pxhemm, general_multiplication, general_multiplication_device, pxgemm, hermitian_rank_k_update,
-                       hermitian_rank_2k_update, hermitian_rank_k_update_device, hermitian_rank_2k_update_device, pxherk, pxher2k,
-                       general_addition, hermitian_complete, pxgeadd, pxtradd, pxtran, pxlacpy, general_addition_device,
-                       hermitian_complete_device, addition_profile,
-                       update_direct, update_bulk_slots, trsm_direct, potrf_direct, matrix_norm,
-                       matrix_norm_device, pxlange, pxlanhe, pxlantr, norm_profile)
+from ._abi import make_descriptor  # noqa: F401
+from .grid import Grid, finalize, initialize  # noqa: F401
+from .device_matrix import DeviceMatrix, GeneralDeviceMatrix  # noqa: F401
+from .cholesky import (cholesky_factorization, potrf_trace, potrs_device, pxpotrf, pxpotrs, release_workspace_pool,  # noqa: F401
+                       set_random_hermitian_positive_definite, update_launch_stats)
+from .solver import pxtrsm, solver_profile, triangular_solver, triangular_solver_device  # noqa: F401
+from .multiplication import (general_multiplication, general_multiplication_device, hermitian_multiplication,  # noqa: F401
+                             hermitian_multiplication_device, multiplication_profile, pxgemm, pxhemm, pxtrmm,
+                             triangular_multiplication, triangular_multiplication_device)
+from .rank_update import (hermitian_rank_2k_update, hermitian_rank_2k_update_device, hermitian_rank_k_update,  # noqa: F401
+                          hermitian_rank_k_update_device, pxher2k, pxherk)
+from .addition import (addition_profile, general_addition, general_addition_device, hermitian_complete,  # noqa: F401
+                       hermitian_complete_device, pxgeadd, pxlacpy, pxtradd, pxtran)
+from .inverse import inverse_from_cholesky_factor, inverse_profile, pxpotri, pxtrtri, triangular_inverse  # noqa: F401
+from .norm import matrix_norm, matrix_norm_device, norm_profile, pxlange, pxlanhe, pxlantr  # noqa: F401
+from .gen_to_std import generalized_to_standard, pxhegst  # noqa: F401
+from .direct import (potrf_direct, tile_gemm, tile_herk, tile_potrf, tile_trsm, trsm_direct, update_bulk_slots,  # noqa: F401
+                     update_direct)
 from . import distribution  # noqa: F401
 from .eigensolver import (band_to_tridiagonal, bt_band_to_tridiagonal, bt_reduction_to_band,  # noqa: F401
                           bt_reduction_to_band_device, eigensolver_min_band, eigensolver_profile, get_band_size, hermitian_eigensolver,

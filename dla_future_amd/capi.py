@@ -75,6 +75,32 @@ _vp, _i, _l, _ch = C.c_void_p, C.c_int, C.c_long, C.c_char
 _IP = C.POINTER(C.c_int)
 _i64 = C.c_int64
 _LP = C.POINTER(C.c_long)
+_DP = C.POINTER(C.c_double)
+_D = DLAFDescriptor
+_A = [_vp, _i, _i, _IP]  # a matrix in a ScaLAPACK argument list: a, ia, ja, desca
+
+
+class _PerType(tuple):
+    """One ctypes type per element type, in the order s, d, c, z, where a signature depends on it."""
+
+
+_real = _PerType((C.c_float, C.c_double, C.c_float, C.c_double))
+_weights = _PerType((WEIGHTS_FN_S, WEIGHTS_FN_D, WEIGHTS_FN_S, WEIGHTS_FN_D))
+
+
+def _family(names, res, args, types="sdcz"):
+    """The entries of one routine for every element type: `names` is a pattern with {t}, and with {sy} / {symmetric} for
+    the sy / he and symmetric / hermitian spellings, or the names themselves where they follow no pattern."""
+    if isinstance(names, str):
+        names = [names.format(t=t, sy="sy" if t in "sd" else "he", symmetric="symmetric" if t in "sd" else "hermitian")
+                 for t in types]
+
+    def pick(x, k):
+        return x[k] if isinstance(x, _PerType) else x
+
+    return {name: (pick(res, k), [pick(x, k) for x in args]) for k, name in enumerate(names)}
+
+
 SIGNATURES = {
     # include/dlaf_c/init.h
     "dlaf_initialize": (None, [_i, C.POINTER(C.c_char_p), _i, C.POINTER(C.c_char_p)]),
@@ -82,17 +108,8 @@ SIGNATURES = {
     # include/dlaf_c/grid.h
     "dlaf_free_grid": (None, [_i]),
     # include/dlaf_c/utils.h
-    "make_dlaf_descriptor": (DLAFDescriptor, [_i, _i, _i, _i, _IP]),
-    # include/dlaf_c/factorization/cholesky.h
-    "dlaf_cholesky_factorization_s": (_i, [_i, _ch, _vp, DLAFDescriptor]),
-    "dlaf_cholesky_factorization_d": (_i, [_i, _ch, _vp, DLAFDescriptor]),
-    "dlaf_cholesky_factorization_c": (_i, [_i, _ch, _vp, DLAFDescriptor]),
-    "dlaf_cholesky_factorization_z": (_i, [_i, _ch, _vp, DLAFDescriptor]),
-    "dlaf_pspotrf": (None, [_ch, _i, _vp, _i, _i, _IP, _IP]),
-    "dlaf_pdpotrf": (None, [_ch, _i, _vp, _i, _i, _IP, _IP]),
-    "dlaf_pcpotrf": (None, [_ch, _i, _vp, _i, _i, _IP, _IP]),
-    "dlaf_pzpotrf": (None, [_ch, _i, _vp, _i, _i, _IP, _IP]),
-    # include/dlaf_mi355x/dlaf_mi355x.h
+    "make_dlaf_descriptor": (_D, [_i, _i, _i, _i, _IP]),
+    # include/dlaf_mi355x/dlaf_mi355x.h: the entries that exist once
     "dlaf_mi355x_version": (C.c_char_p, []),
     "dlaf_mi355x_create_grid_single": (_i, []),
     "dlaf_mi355x_rccl_unique_id": (None, [_vp]),
@@ -102,344 +119,73 @@ SIGNATURES = {
     "dlaf_mi355x_grid_info": (_i, [_i, _IP, _IP, _IP, _IP]),
     "dlaf_mi355x_grid_barrier": (_i, [_i]),
     "dlaf_mi355x_grid_selftest": (_i, [_i, C.c_size_t]),
-    "dlaf_mi355x_matrix_create": (_i, [_i, _ch, _ch, DLAFDescriptor, C.POINTER(_vp)]),
+    "dlaf_mi355x_grid_on_free": (_i, [_i, _vp, _vp]),
+    "dlaf_mi355x_grid_rekey": (_i, [_i, _i]),
+    "dlaf_mi355x_grid_comm_log": (_i, [_i, _i]),
+    "dlaf_mi355x_grid_comm_log_read": (_l, [_i, _LP, _l]),
+    "dlaf_mi355x_matrix_create": (_i, [_i, _ch, _ch, _D, C.POINTER(_vp)]),
     "dlaf_mi355x_matrix_destroy": (None, [_vp]),
     "dlaf_mi355x_matrix_upload": (_i, [_vp, _vp, _i]),
     "dlaf_mi355x_matrix_download": (_i, [_vp, _vp, _i]),
     "dlaf_mi355x_matrix_copy": (_i, [_vp, _vp]),
     "dlaf_mi355x_matrix_fetch_tile": (_i, [_vp, _l, _l, _vp, _i]),
-    "dlaf_mi355x_grid_on_free": (_i, [_i, _vp, _vp]),
-    "dlaf_mi355x_grid_rekey": (_i, [_i, _i]),
-    "dlaf_mi355x_grid_comm_log": (_i, [_i, _i]),
-    "dlaf_mi355x_grid_comm_log_read": (_l, [_i, C.POINTER(C.c_long), _l]),
     "dlaf_mi355x_matrix_local_info": (_i, [_vp]),
-    "dlaf_mi355x_potrf_trace": (_i, [C.POINTER(C.c_ulonglong)]),
-    "dlaf_mi355x_update_launch_stats": (_i, [C.POINTER(C.c_long), C.POINTER(C.c_long)]),
-    "dlaf_mi355x_cholesky_start": (_i, [_vp]),
-    "dlaf_mi355x_cholesky_wait": (_i, [_vp]),
-    "dlaf_mi355x_cholesky_factorization_device": (_i, [_vp]),
-    "dlaf_mi355x_cholesky_residual": (_i, [_vp, _vp, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
-    "dlaf_mi355x_matrix_trsm_profile": (_i, [_vp, _i, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double)]),
-    "dlaf_mi355x_matrix_profile": (_i, [_vp, _i, C.POINTER(C.c_double), C.POINTER(C.c_long),
-                                        C.POINTER(C.c_double), C.POINTER(C.c_double)]),
-    "dlaf_mi355x_triangular_solver_s": (_i, [_i, _ch, _ch, _ch, _ch, _vp, _vp, DLAFDescriptor, _vp, DLAFDescriptor]),
-    "dlaf_mi355x_triangular_solver_d": (_i, [_i, _ch, _ch, _ch, _ch, _vp, _vp, DLAFDescriptor, _vp, DLAFDescriptor]),
-    "dlaf_mi355x_triangular_solver_c": (_i, [_i, _ch, _ch, _ch, _ch, _vp, _vp, DLAFDescriptor, _vp, DLAFDescriptor]),
-    "dlaf_mi355x_triangular_solver_z": (_i, [_i, _ch, _ch, _ch, _ch, _vp, _vp, DLAFDescriptor, _vp, DLAFDescriptor]),
-    "dlaf_mi355x_triangular_multiplication_s": (_i, [_i, _ch, _ch, _ch, _ch, _vp, _vp, DLAFDescriptor, _vp, DLAFDescriptor]),
-    "dlaf_mi355x_triangular_multiplication_d": (_i, [_i, _ch, _ch, _ch, _ch, _vp, _vp, DLAFDescriptor, _vp, DLAFDescriptor]),
-    "dlaf_mi355x_triangular_multiplication_c": (_i, [_i, _ch, _ch, _ch, _ch, _vp, _vp, DLAFDescriptor, _vp, DLAFDescriptor]),
-    "dlaf_mi355x_triangular_multiplication_z": (_i, [_i, _ch, _ch, _ch, _ch, _vp, _vp, DLAFDescriptor, _vp, DLAFDescriptor]),
-    "dlaf_mi355x_pstrsm": (None, [_ch, _ch, _ch, _ch, _i, _i, _vp, _vp, _i, _i, _IP, _vp, _i, _i, _IP]),
-    "dlaf_mi355x_pdtrsm": (None, [_ch, _ch, _ch, _ch, _i, _i, _vp, _vp, _i, _i, _IP, _vp, _i, _i, _IP]),
-    "dlaf_mi355x_pctrsm": (None, [_ch, _ch, _ch, _ch, _i, _i, _vp, _vp, _i, _i, _IP, _vp, _i, _i, _IP]),
-    "dlaf_mi355x_pztrsm": (None, [_ch, _ch, _ch, _ch, _i, _i, _vp, _vp, _i, _i, _IP, _vp, _i, _i, _IP]),
-    "dlaf_mi355x_pstrmm": (None, [_ch, _ch, _ch, _ch, _i, _i, _vp, _vp, _i, _i, _IP, _vp, _i, _i, _IP]),
-    "dlaf_mi355x_pdtrmm": (None, [_ch, _ch, _ch, _ch, _i, _i, _vp, _vp, _i, _i, _IP, _vp, _i, _i, _IP]),
-    "dlaf_mi355x_pctrmm": (None, [_ch, _ch, _ch, _ch, _i, _i, _vp, _vp, _i, _i, _IP, _vp, _i, _i, _IP]),
-    "dlaf_mi355x_pztrmm": (None, [_ch, _ch, _ch, _ch, _i, _i, _vp, _vp, _i, _i, _IP, _vp, _i, _i, _IP]),
-    "dlaf_mi355x_hermitian_multiplication_s": (_i, [_i, _ch, _ch, _vp, _vp, DLAFDescriptor, _vp, DLAFDescriptor, _vp, _vp, DLAFDescriptor]),
-    "dlaf_mi355x_hermitian_multiplication_d": (_i, [_i, _ch, _ch, _vp, _vp, DLAFDescriptor, _vp, DLAFDescriptor, _vp, _vp, DLAFDescriptor]),
-    "dlaf_mi355x_hermitian_multiplication_c": (_i, [_i, _ch, _ch, _vp, _vp, DLAFDescriptor, _vp, DLAFDescriptor, _vp, _vp, DLAFDescriptor]),
-    "dlaf_mi355x_hermitian_multiplication_z": (_i, [_i, _ch, _ch, _vp, _vp, DLAFDescriptor, _vp, DLAFDescriptor, _vp, _vp, DLAFDescriptor]),
-    "dlaf_mi355x_pssymm": (None, [_ch, _ch, _i, _i, _vp, _vp, _i, _i, _IP, _vp, _i, _i, _IP, _vp, _vp, _i, _i, _IP]),
-    "dlaf_mi355x_pdsymm": (None, [_ch, _ch, _i, _i, _vp, _vp, _i, _i, _IP, _vp, _i, _i, _IP, _vp, _vp, _i, _i, _IP]),
-    "dlaf_mi355x_pchemm": (None, [_ch, _ch, _i, _i, _vp, _vp, _i, _i, _IP, _vp, _i, _i, _IP, _vp, _vp, _i, _i, _IP]),
-    "dlaf_mi355x_pzhemm": (None, [_ch, _ch, _i, _i, _vp, _vp, _i, _i, _IP, _vp, _i, _i, _IP, _vp, _vp, _i, _i, _IP]),
-    "dlaf_mi355x_general_multiplication_s": (_i, [_i, _ch, _ch, _vp, _vp, DLAFDescriptor, _vp, DLAFDescriptor, _vp, _vp, DLAFDescriptor]),
-    "dlaf_mi355x_general_multiplication_d": (_i, [_i, _ch, _ch, _vp, _vp, DLAFDescriptor, _vp, DLAFDescriptor, _vp, _vp, DLAFDescriptor]),
-    "dlaf_mi355x_general_multiplication_c": (_i, [_i, _ch, _ch, _vp, _vp, DLAFDescriptor, _vp, DLAFDescriptor, _vp, _vp, DLAFDescriptor]),
-    "dlaf_mi355x_general_multiplication_z": (_i, [_i, _ch, _ch, _vp, _vp, DLAFDescriptor, _vp, DLAFDescriptor, _vp, _vp, DLAFDescriptor]),
-    "dlaf_mi355x_hermitian_rank_k_update_s": (_i, [_i, _ch, _ch, _vp, _vp, DLAFDescriptor, _vp, _vp, DLAFDescriptor]),
-    "dlaf_mi355x_hermitian_rank_k_update_d": (_i, [_i, _ch, _ch, _vp, _vp, DLAFDescriptor, _vp, _vp, DLAFDescriptor]),
-    "dlaf_mi355x_hermitian_rank_k_update_c": (_i, [_i, _ch, _ch, _vp, _vp, DLAFDescriptor, _vp, _vp, DLAFDescriptor]),
-    "dlaf_mi355x_hermitian_rank_k_update_z": (_i, [_i, _ch, _ch, _vp, _vp, DLAFDescriptor, _vp, _vp, DLAFDescriptor]),
-    "dlaf_mi355x_hermitian_rank_2k_update_s": (_i, [_i, _ch, _ch, _vp, _vp, DLAFDescriptor, _vp, DLAFDescriptor, _vp, _vp, DLAFDescriptor]),
-    "dlaf_mi355x_hermitian_rank_2k_update_d": (_i, [_i, _ch, _ch, _vp, _vp, DLAFDescriptor, _vp, DLAFDescriptor, _vp, _vp, DLAFDescriptor]),
-    "dlaf_mi355x_hermitian_rank_2k_update_c": (_i, [_i, _ch, _ch, _vp, _vp, DLAFDescriptor, _vp, DLAFDescriptor, _vp, _vp, DLAFDescriptor]),
-    "dlaf_mi355x_hermitian_rank_2k_update_z": (_i, [_i, _ch, _ch, _vp, _vp, DLAFDescriptor, _vp, DLAFDescriptor, _vp, _vp, DLAFDescriptor]),
-    "dlaf_mi355x_hermitian_weighted_rank_k_update_s": (_i, [_i, _ch, _ch, _vp, _vp, DLAFDescriptor, _vp, _vp, _vp, DLAFDescriptor]),
-    "dlaf_mi355x_hermitian_weighted_rank_k_update_d": (_i, [_i, _ch, _ch, _vp, _vp, DLAFDescriptor, _vp, _vp, _vp, DLAFDescriptor]),
-    "dlaf_mi355x_hermitian_weighted_rank_k_update_c": (_i, [_i, _ch, _ch, _vp, _vp, DLAFDescriptor, _vp, _vp, _vp, DLAFDescriptor]),
-    "dlaf_mi355x_hermitian_weighted_rank_k_update_z": (_i, [_i, _ch, _ch, _vp, _vp, DLAFDescriptor, _vp, _vp, _vp, DLAFDescriptor]),
-    "dlaf_mi355x_hermitian_weighted_rank_k_update_device": (_i, [_ch, _ch, _vp, _vp, _vp, _vp, _vp]),
-    "dlaf_mi355x_hermitian_function_s": (_i, [_i, _ch, _vp, DLAFDescriptor, _vp, WEIGHTS_FN_S, _vp, _vp, _vp, _vp]),
-    "dlaf_mi355x_hermitian_function_d": (_i, [_i, _ch, _vp, DLAFDescriptor, _vp, WEIGHTS_FN_D, _vp, _vp, _vp, _vp]),
-    "dlaf_mi355x_hermitian_function_c": (_i, [_i, _ch, _vp, DLAFDescriptor, _vp, WEIGHTS_FN_S, _vp, _vp, _vp, _vp]),
-    "dlaf_mi355x_hermitian_function_z": (_i, [_i, _ch, _vp, DLAFDescriptor, _vp, WEIGHTS_FN_D, _vp, _vp, _vp, _vp]),
-    "dlaf_mi355x_hermitian_function_device": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp]),
-    "dlaf_mi355x_hermitian_power_s": (_i, [_i, _ch, _vp, DLAFDescriptor, _vp, C.c_double, C.c_double, _LP]),
-    "dlaf_mi355x_hermitian_power_d": (_i, [_i, _ch, _vp, DLAFDescriptor, _vp, C.c_double, C.c_double, _LP]),
-    "dlaf_mi355x_hermitian_power_c": (_i, [_i, _ch, _vp, DLAFDescriptor, _vp, C.c_double, C.c_double, _LP]),
-    "dlaf_mi355x_hermitian_power_z": (_i, [_i, _ch, _vp, DLAFDescriptor, _vp, C.c_double, C.c_double, _LP]),
-    "dlaf_mi355x_hermitian_power_device": (_i, [_vp, _vp, C.c_double, C.c_double, _LP]),
-    "dlaf_mi355x_pssyrk": (None, [_ch, _ch, _i, _i, _vp, _vp, _i, _i, _IP, _vp, _vp, _i, _i, _IP]),
-    "dlaf_mi355x_pdsyrk": (None, [_ch, _ch, _i, _i, _vp, _vp, _i, _i, _IP, _vp, _vp, _i, _i, _IP]),
-    "dlaf_mi355x_pcherk": (None, [_ch, _ch, _i, _i, _vp, _vp, _i, _i, _IP, _vp, _vp, _i, _i, _IP]),
-    "dlaf_mi355x_pzherk": (None, [_ch, _ch, _i, _i, _vp, _vp, _i, _i, _IP, _vp, _vp, _i, _i, _IP]),
-    "dlaf_mi355x_pssyr2k": (None, [_ch, _ch, _i, _i, _vp, _vp, _i, _i, _IP, _vp, _i, _i, _IP, _vp, _vp, _i, _i, _IP]),
-    "dlaf_mi355x_pdsyr2k": (None, [_ch, _ch, _i, _i, _vp, _vp, _i, _i, _IP, _vp, _i, _i, _IP, _vp, _vp, _i, _i, _IP]),
-    "dlaf_mi355x_pcher2k": (None, [_ch, _ch, _i, _i, _vp, _vp, _i, _i, _IP, _vp, _i, _i, _IP, _vp, _vp, _i, _i, _IP]),
-    "dlaf_mi355x_pzher2k": (None, [_ch, _ch, _i, _i, _vp, _vp, _i, _i, _IP, _vp, _i, _i, _IP, _vp, _vp, _i, _i, _IP]),
-    "dlaf_mi355x_general_addition_s": (_i, [_i, _ch, _ch, _vp, _vp, DLAFDescriptor, _vp, _vp, DLAFDescriptor]),
-    "dlaf_mi355x_general_addition_d": (_i, [_i, _ch, _ch, _vp, _vp, DLAFDescriptor, _vp, _vp, DLAFDescriptor]),
-    "dlaf_mi355x_general_addition_c": (_i, [_i, _ch, _ch, _vp, _vp, DLAFDescriptor, _vp, _vp, DLAFDescriptor]),
-    "dlaf_mi355x_general_addition_z": (_i, [_i, _ch, _ch, _vp, _vp, DLAFDescriptor, _vp, _vp, DLAFDescriptor]),
-    "dlaf_mi355x_hermitian_complete_s": (_i, [_i, _ch, _ch, _vp, DLAFDescriptor]),
-    "dlaf_mi355x_hermitian_complete_d": (_i, [_i, _ch, _ch, _vp, DLAFDescriptor]),
-    "dlaf_mi355x_hermitian_complete_c": (_i, [_i, _ch, _ch, _vp, DLAFDescriptor]),
-    "dlaf_mi355x_hermitian_complete_z": (_i, [_i, _ch, _ch, _vp, DLAFDescriptor]),
-    "dlaf_mi355x_psgeadd": (None, [_ch, _i, _i, _vp, _vp, _i, _i, _IP, _vp, _vp, _i, _i, _IP]),
-    "dlaf_mi355x_pstradd": (None, [_ch, _ch, _i, _i, _vp, _vp, _i, _i, _IP, _vp, _vp, _i, _i, _IP]),
-    "dlaf_mi355x_pslacpy": (None, [_ch, _i, _i, _vp, _i, _i, _IP, _vp, _i, _i, _IP]),
-    "dlaf_mi355x_pdgeadd": (None, [_ch, _i, _i, _vp, _vp, _i, _i, _IP, _vp, _vp, _i, _i, _IP]),
-    "dlaf_mi355x_pdtradd": (None, [_ch, _ch, _i, _i, _vp, _vp, _i, _i, _IP, _vp, _vp, _i, _i, _IP]),
-    "dlaf_mi355x_pdlacpy": (None, [_ch, _i, _i, _vp, _i, _i, _IP, _vp, _i, _i, _IP]),
-    "dlaf_mi355x_pcgeadd": (None, [_ch, _i, _i, _vp, _vp, _i, _i, _IP, _vp, _vp, _i, _i, _IP]),
-    "dlaf_mi355x_pctradd": (None, [_ch, _ch, _i, _i, _vp, _vp, _i, _i, _IP, _vp, _vp, _i, _i, _IP]),
-    "dlaf_mi355x_pclacpy": (None, [_ch, _i, _i, _vp, _i, _i, _IP, _vp, _i, _i, _IP]),
-    "dlaf_mi355x_pzgeadd": (None, [_ch, _i, _i, _vp, _vp, _i, _i, _IP, _vp, _vp, _i, _i, _IP]),
-    "dlaf_mi355x_pztradd": (None, [_ch, _ch, _i, _i, _vp, _vp, _i, _i, _IP, _vp, _vp, _i, _i, _IP]),
-    "dlaf_mi355x_pzlacpy": (None, [_ch, _i, _i, _vp, _i, _i, _IP, _vp, _i, _i, _IP]),
-    "dlaf_mi355x_pstran": (None, [_i, _i, _vp, _vp, _i, _i, _IP, _vp, _vp, _i, _i, _IP]),
-    "dlaf_mi355x_pdtran": (None, [_i, _i, _vp, _vp, _i, _i, _IP, _vp, _vp, _i, _i, _IP]),
-    "dlaf_mi355x_pctranu": (None, [_i, _i, _vp, _vp, _i, _i, _IP, _vp, _vp, _i, _i, _IP]),
-    "dlaf_mi355x_pctranc": (None, [_i, _i, _vp, _vp, _i, _i, _IP, _vp, _vp, _i, _i, _IP]),
-    "dlaf_mi355x_pztranu": (None, [_i, _i, _vp, _vp, _i, _i, _IP, _vp, _vp, _i, _i, _IP]),
-    "dlaf_mi355x_pztranc": (None, [_i, _i, _vp, _vp, _i, _i, _IP, _vp, _vp, _i, _i, _IP]),
-    "dlaf_mi355x_psgemm": (None, [_ch, _ch, _i, _i, _i, _vp, _vp, _i, _i, _IP, _vp, _i, _i, _IP, _vp, _vp, _i, _i, _IP]),
-    "dlaf_mi355x_pdgemm": (None, [_ch, _ch, _i, _i, _i, _vp, _vp, _i, _i, _IP, _vp, _i, _i, _IP, _vp, _vp, _i, _i, _IP]),
-    "dlaf_mi355x_pcgemm": (None, [_ch, _ch, _i, _i, _i, _vp, _vp, _i, _i, _IP, _vp, _i, _i, _IP, _vp, _vp, _i, _i, _IP]),
-    "dlaf_mi355x_pzgemm": (None, [_ch, _ch, _i, _i, _i, _vp, _vp, _i, _i, _IP, _vp, _i, _i, _IP, _vp, _vp, _i, _i, _IP]),
-    "dlaf_mi355x_pspotrs": (None, [_ch, _i, _i, _vp, _i, _i, _IP, _vp, _i, _i, _IP, _IP]),
-    "dlaf_mi355x_pdpotrs": (None, [_ch, _i, _i, _vp, _i, _i, _IP, _vp, _i, _i, _IP, _IP]),
-    "dlaf_mi355x_pcpotrs": (None, [_ch, _i, _i, _vp, _i, _i, _IP, _vp, _i, _i, _IP, _IP]),
-    "dlaf_mi355x_pzpotrs": (None, [_ch, _i, _i, _vp, _i, _i, _IP, _vp, _i, _i, _IP, _IP]),
-    "dlaf_mi355x_solver_profile": (_i, [C.POINTER(C.c_double), C.POINTER(C.c_double)]),
-    "dlaf_mi355x_multiplication_profile": (_i, [C.POINTER(C.c_double), C.POINTER(C.c_double)]),
-    "dlaf_mi355x_addition_profile": (_i, [C.POINTER(C.c_double), C.POINTER(C.c_double)]),
-    "dlaf_mi355x_gmatrix_create": (_i, [_i, _ch, DLAFDescriptor, C.POINTER(_vp)]),
+    "dlaf_mi355x_matrix_to_general": (_i, [_ch, _vp, _vp]),
+    "dlaf_mi355x_matrix_from_general": (_i, [_vp, _vp]),
+    "dlaf_mi355x_matrix_trsm_profile": (_i, [_vp, _i, _DP, _DP, _DP]),
+    "dlaf_mi355x_matrix_profile": (_i, [_vp, _i, _DP, _LP, _DP, _DP]),
+    "dlaf_mi355x_matrix_norm": (_i, [_vp, _ch, _ch, _ch, _DP]),
+    "dlaf_mi355x_gmatrix_create": (_i, [_i, _ch, _D, C.POINTER(_vp)]),
     "dlaf_mi355x_gmatrix_destroy": (None, [_vp]),
     "dlaf_mi355x_gmatrix_upload": (_i, [_vp, _vp, _i]),
     "dlaf_mi355x_gmatrix_download": (_i, [_vp, _vp, _i]),
+    "dlaf_mi355x_gmatrix_device_tiles": (_i, [_vp, C.POINTER(_vp), C.POINTER(C.c_size_t)]),
+    "dlaf_mi355x_general_matrix_norm": (_i, [_vp, _ch, _DP]),
+    "dlaf_mi355x_potrf_trace": (_i, [C.POINTER(C.c_ulonglong)]),
+    "dlaf_mi355x_update_launch_stats": (_i, [_LP, _LP]),
+    "dlaf_mi355x_workspace_pool_release": (_l, []),
+    "dlaf_mi355x_set_random_hpd": (_i, [_i, _ch, _vp, _D, _i]),
+    "dlaf_mi355x_cholesky_start": (_i, [_vp]),
+    "dlaf_mi355x_cholesky_wait": (_i, [_vp]),
+    "dlaf_mi355x_cholesky_factorization_device": (_i, [_vp]),
+    "dlaf_mi355x_cholesky_residual": (_i, [_vp, _vp, _DP, _DP]),
+    "dlaf_mi355x_potrs_device": (_i, [_ch, _vp, _vp]),
     "dlaf_mi355x_triangular_solver_device": (_i, [_ch, _ch, _ch, _ch, _vp, _vp, _vp]),
     "dlaf_mi355x_triangular_multiplication_device": (_i, [_ch, _ch, _ch, _ch, _vp, _vp, _vp]),
     "dlaf_mi355x_hermitian_multiplication_device": (_i, [_ch, _ch, _vp, _vp, _vp, _vp, _vp]),
     "dlaf_mi355x_general_multiplication_device": (_i, [_ch, _ch, _vp, _vp, _vp, _vp, _vp]),
     "dlaf_mi355x_hermitian_rank_k_update_device": (_i, [_ch, _ch, _vp, _vp, _vp, _vp]),
     "dlaf_mi355x_hermitian_rank_2k_update_device": (_i, [_ch, _ch, _vp, _vp, _vp, _vp, _vp]),
+    "dlaf_mi355x_hermitian_weighted_rank_k_update_device": (_i, [_ch, _ch, _vp, _vp, _vp, _vp, _vp]),
+    "dlaf_mi355x_hermitian_function_device": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "dlaf_mi355x_hermitian_power_device": (_i, [_vp, _vp, C.c_double, C.c_double, _LP]),
     "dlaf_mi355x_general_addition_device": (_i, [_ch, _ch, _vp, _vp, _vp, _vp]),
     "dlaf_mi355x_hermitian_complete_device": (_i, [_ch, _ch, _vp]),
-    "dlaf_mi355x_matrix_to_general": (_i, [_ch, _vp, _vp]),
-    "dlaf_mi355x_matrix_from_general": (_i, [_vp, _vp]),
-    "dlaf_mi355x_potrs_device": (_i, [_ch, _vp, _vp]),
-    "dlaf_mi355x_generalized_to_standard_s": (_i, [_i, _ch, _vp, DLAFDescriptor, _vp, DLAFDescriptor]),
-    "dlaf_mi355x_generalized_to_standard_d": (_i, [_i, _ch, _vp, DLAFDescriptor, _vp, DLAFDescriptor]),
-    "dlaf_mi355x_generalized_to_standard_c": (_i, [_i, _ch, _vp, DLAFDescriptor, _vp, DLAFDescriptor]),
-    "dlaf_mi355x_generalized_to_standard_z": (_i, [_i, _ch, _vp, DLAFDescriptor, _vp, DLAFDescriptor]),
-    "dlaf_mi355x_pshegst": (None, [_i, _ch, _i, _vp, _i, _i, _IP, _vp, _i, _i, _IP, _vp, _IP]),
-    "dlaf_mi355x_pdhegst": (None, [_i, _ch, _i, _vp, _i, _i, _IP, _vp, _i, _i, _IP, _vp, _IP]),
-    "dlaf_mi355x_pchegst": (None, [_i, _ch, _i, _vp, _i, _i, _IP, _vp, _i, _i, _IP, _vp, _IP]),
-    "dlaf_mi355x_pzhegst": (None, [_i, _ch, _i, _vp, _i, _i, _IP, _vp, _i, _i, _IP, _vp, _IP]),
     "dlaf_mi355x_generalized_to_standard_device": (_i, [_vp, _vp]),
-    "dlaf_mi355x_triangular_inverse_s": (_i, [_i, _ch, _ch, _vp, DLAFDescriptor]),
-    "dlaf_mi355x_inverse_from_cholesky_factor_s": (_i, [_i, _ch, _vp, DLAFDescriptor]),
-    "dlaf_mi355x_pstrtri": (None, [_ch, _ch, _i, _vp, _i, _i, _IP, _IP]),
-    "dlaf_mi355x_pspotri": (None, [_ch, _i, _vp, _i, _i, _IP, _IP]),
-    "dlaf_mi355x_triangular_inverse_d": (_i, [_i, _ch, _ch, _vp, DLAFDescriptor]),
-    "dlaf_mi355x_inverse_from_cholesky_factor_d": (_i, [_i, _ch, _vp, DLAFDescriptor]),
-    "dlaf_mi355x_pdtrtri": (None, [_ch, _ch, _i, _vp, _i, _i, _IP, _IP]),
-    "dlaf_mi355x_pdpotri": (None, [_ch, _i, _vp, _i, _i, _IP, _IP]),
-    "dlaf_mi355x_triangular_inverse_c": (_i, [_i, _ch, _ch, _vp, DLAFDescriptor]),
-    "dlaf_mi355x_inverse_from_cholesky_factor_c": (_i, [_i, _ch, _vp, DLAFDescriptor]),
-    "dlaf_mi355x_pctrtri": (None, [_ch, _ch, _i, _vp, _i, _i, _IP, _IP]),
-    "dlaf_mi355x_pcpotri": (None, [_ch, _i, _vp, _i, _i, _IP, _IP]),
-    "dlaf_mi355x_triangular_inverse_z": (_i, [_i, _ch, _ch, _vp, DLAFDescriptor]),
-    "dlaf_mi355x_inverse_from_cholesky_factor_z": (_i, [_i, _ch, _vp, DLAFDescriptor]),
-    "dlaf_mi355x_pztrtri": (None, [_ch, _ch, _i, _vp, _i, _i, _IP, _IP]),
-    "dlaf_mi355x_pzpotri": (None, [_ch, _i, _vp, _i, _i, _IP, _IP]),
     "dlaf_mi355x_triangular_inverse_device": (_i, [_ch, _ch, _vp]),
     "dlaf_mi355x_inverse_from_cholesky_factor_device": (_i, [_ch, _vp]),
-    "dlaf_mi355x_inverse_profile": (_i, [C.POINTER(C.c_double), C.POINTER(C.c_double)]),
-    "dlaf_mi355x_inverse_plan": (_i, [C.c_long, _i, _i, _i, _i, _i, _i, _i, C.POINTER(C.c_long)]),
-    "dlaf_mi355x_inverse_step": (_i, [C.c_long, _i, _i, _i, _i, _i, _i, _i, C.c_long, C.POINTER(C.c_long)]),
-    "dlaf_mi355x_general_norm_s": (_i, [_i, _ch, _vp, DLAFDescriptor, C.POINTER(C.c_double)]),
-    "dlaf_mi355x_hermitian_norm_s": (_i, [_i, _ch, _ch, _vp, DLAFDescriptor, C.POINTER(C.c_double)]),
-    "dlaf_mi355x_triangular_norm_s": (_i, [_i, _ch, _ch, _ch, _vp, DLAFDescriptor, C.POINTER(C.c_double)]),
-    "dlaf_mi355x_pslange": (C.c_float, [_ch, _i, _i, _vp, _i, _i, _IP]),
-    "dlaf_mi355x_pslansy": (C.c_float, [_ch, _ch, _i, _vp, _i, _i, _IP]),
-    "dlaf_mi355x_pslantr": (C.c_float, [_ch, _ch, _ch, _i, _vp, _i, _i, _IP]),
-    "dlaf_mi355x_general_norm_d": (_i, [_i, _ch, _vp, DLAFDescriptor, C.POINTER(C.c_double)]),
-    "dlaf_mi355x_hermitian_norm_d": (_i, [_i, _ch, _ch, _vp, DLAFDescriptor, C.POINTER(C.c_double)]),
-    "dlaf_mi355x_triangular_norm_d": (_i, [_i, _ch, _ch, _ch, _vp, DLAFDescriptor, C.POINTER(C.c_double)]),
-    "dlaf_mi355x_pdlange": (C.c_double, [_ch, _i, _i, _vp, _i, _i, _IP]),
-    "dlaf_mi355x_pdlansy": (C.c_double, [_ch, _ch, _i, _vp, _i, _i, _IP]),
-    "dlaf_mi355x_pdlantr": (C.c_double, [_ch, _ch, _ch, _i, _vp, _i, _i, _IP]),
-    "dlaf_mi355x_general_norm_c": (_i, [_i, _ch, _vp, DLAFDescriptor, C.POINTER(C.c_double)]),
-    "dlaf_mi355x_hermitian_norm_c": (_i, [_i, _ch, _ch, _vp, DLAFDescriptor, C.POINTER(C.c_double)]),
-    "dlaf_mi355x_triangular_norm_c": (_i, [_i, _ch, _ch, _ch, _vp, DLAFDescriptor, C.POINTER(C.c_double)]),
-    "dlaf_mi355x_pclange": (C.c_float, [_ch, _i, _i, _vp, _i, _i, _IP]),
-    "dlaf_mi355x_pclanhe": (C.c_float, [_ch, _ch, _i, _vp, _i, _i, _IP]),
-    "dlaf_mi355x_pclantr": (C.c_float, [_ch, _ch, _ch, _i, _vp, _i, _i, _IP]),
-    "dlaf_mi355x_general_norm_z": (_i, [_i, _ch, _vp, DLAFDescriptor, C.POINTER(C.c_double)]),
-    "dlaf_mi355x_hermitian_norm_z": (_i, [_i, _ch, _ch, _vp, DLAFDescriptor, C.POINTER(C.c_double)]),
-    "dlaf_mi355x_triangular_norm_z": (_i, [_i, _ch, _ch, _ch, _vp, DLAFDescriptor, C.POINTER(C.c_double)]),
-    "dlaf_mi355x_pzlange": (C.c_double, [_ch, _i, _i, _vp, _i, _i, _IP]),
-    "dlaf_mi355x_pzlanhe": (C.c_double, [_ch, _ch, _i, _vp, _i, _i, _IP]),
-    "dlaf_mi355x_pzlantr": (C.c_double, [_ch, _ch, _ch, _i, _vp, _i, _i, _IP]),
-    "dlaf_mi355x_matrix_norm": (_i, [_vp, _ch, _ch, _ch, C.POINTER(C.c_double)]),
-    "dlaf_mi355x_general_matrix_norm": (_i, [_vp, _ch, C.POINTER(C.c_double)]),
-    "dlaf_mi355x_gmatrix_device_tiles": (_i, [_vp, C.POINTER(_vp), C.POINTER(C.c_size_t)]),
-    "dlaf_mi355x_norm_profile": (_i, [C.POINTER(C.c_double), C.POINTER(C.c_double)]),
-    "dlaf_mi355x_reduction_to_band_s": (_i, [_i, _vp, DLAFDescriptor, _i, _vp]),
-    "dlaf_mi355x_reduction_to_band_d": (_i, [_i, _vp, DLAFDescriptor, _i, _vp]),
-    "dlaf_mi355x_reduction_to_band_c": (_i, [_i, _vp, DLAFDescriptor, _i, _vp]),
-    "dlaf_mi355x_reduction_to_band_z": (_i, [_i, _vp, DLAFDescriptor, _i, _vp]),
+    "dlaf_mi355x_inverse_plan": (_i, [_l, _i, _i, _i, _i, _i, _i, _i, _LP]),
+    "dlaf_mi355x_inverse_step": (_i, [_l, _i, _i, _i, _i, _i, _i, _i, _l, _LP]),
     "dlaf_mi355x_reduction_to_band_device": (_i, [_vp, _i, _vp]),
-    "dlaf_mi355x_bt_reduction_to_band_s": (_i, [_i, _i, _vp, DLAFDescriptor, _vp, DLAFDescriptor, _vp]),
-    "dlaf_mi355x_bt_reduction_to_band_d": (_i, [_i, _i, _vp, DLAFDescriptor, _vp, DLAFDescriptor, _vp]),
-    "dlaf_mi355x_bt_reduction_to_band_c": (_i, [_i, _i, _vp, DLAFDescriptor, _vp, DLAFDescriptor, _vp]),
-    "dlaf_mi355x_bt_reduction_to_band_z": (_i, [_i, _i, _vp, DLAFDescriptor, _vp, DLAFDescriptor, _vp]),
     "dlaf_mi355x_bt_reduction_to_band_device": (_i, [_i, _vp, _vp, _vp]),
-    "dlaf_mi355x_band_to_tridiagonal_s": (_i, [_i, _vp, DLAFDescriptor, _i, _vp, _vp, _vp, _i]),
-    "dlaf_mi355x_bt_band_to_tridiagonal_s": (_i, [_i, _i, _i, _vp, _i, _vp, _i]),
-    "dlaf_mi355x_band_to_tridiagonal_d": (_i, [_i, _vp, DLAFDescriptor, _i, _vp, _vp, _vp, _i]),
-    "dlaf_mi355x_bt_band_to_tridiagonal_d": (_i, [_i, _i, _i, _vp, _i, _vp, _i]),
-    "dlaf_mi355x_band_to_tridiagonal_c": (_i, [_i, _vp, DLAFDescriptor, _i, _vp, _vp, _vp, _i]),
-    "dlaf_mi355x_bt_band_to_tridiagonal_c": (_i, [_i, _i, _i, _vp, _i, _vp, _i]),
-    "dlaf_mi355x_band_to_tridiagonal_z": (_i, [_i, _vp, DLAFDescriptor, _i, _vp, _vp, _vp, _i]),
-    "dlaf_mi355x_bt_band_to_tridiagonal_z": (_i, [_i, _i, _i, _vp, _i, _vp, _i]),
-    "dlaf_symmetric_eigensolver_s": (_i, [_i, _ch, _vp, DLAFDescriptor, _vp, _vp, DLAFDescriptor]),
-    "dlaf_symmetric_generalized_eigensolver_s": (_i, [_i, _ch, _vp, DLAFDescriptor, _vp, DLAFDescriptor, _vp, _vp, DLAFDescriptor]),
-    "dlaf_symmetric_generalized_eigensolver_factorized_s": (_i, [_i, _ch, _vp, DLAFDescriptor, _vp, DLAFDescriptor, _vp, _vp, DLAFDescriptor]),
-    "dlaf_symmetric_eigensolver_d": (_i, [_i, _ch, _vp, DLAFDescriptor, _vp, _vp, DLAFDescriptor]),
-    "dlaf_symmetric_generalized_eigensolver_d": (_i, [_i, _ch, _vp, DLAFDescriptor, _vp, DLAFDescriptor, _vp, _vp, DLAFDescriptor]),
-    "dlaf_symmetric_generalized_eigensolver_factorized_d": (_i, [_i, _ch, _vp, DLAFDescriptor, _vp, DLAFDescriptor, _vp, _vp, DLAFDescriptor]),
-    "dlaf_hermitian_eigensolver_c": (_i, [_i, _ch, _vp, DLAFDescriptor, _vp, _vp, DLAFDescriptor]),
-    "dlaf_hermitian_generalized_eigensolver_c": (_i, [_i, _ch, _vp, DLAFDescriptor, _vp, DLAFDescriptor, _vp, _vp, DLAFDescriptor]),
-    "dlaf_hermitian_generalized_eigensolver_factorized_c": (_i, [_i, _ch, _vp, DLAFDescriptor, _vp, DLAFDescriptor, _vp, _vp, DLAFDescriptor]),
-    "dlaf_hermitian_eigensolver_z": (_i, [_i, _ch, _vp, DLAFDescriptor, _vp, _vp, DLAFDescriptor]),
-    "dlaf_hermitian_generalized_eigensolver_z": (_i, [_i, _ch, _vp, DLAFDescriptor, _vp, DLAFDescriptor, _vp, _vp, DLAFDescriptor]),
-    "dlaf_hermitian_generalized_eigensolver_factorized_z": (_i, [_i, _ch, _vp, DLAFDescriptor, _vp, DLAFDescriptor, _vp, _vp, DLAFDescriptor]),
-    "dlaf_pssyevd": (None, [_ch, _i, _vp, _i, _i, _IP, _vp, _vp, _i, _i, _IP, _IP]),
-    "dlaf_pdsyevd": (None, [_ch, _i, _vp, _i, _i, _IP, _vp, _vp, _i, _i, _IP, _IP]),
-    "dlaf_pcheevd": (None, [_ch, _i, _vp, _i, _i, _IP, _vp, _vp, _i, _i, _IP, _IP]),
-    "dlaf_pzheevd": (None, [_ch, _i, _vp, _i, _i, _IP, _vp, _vp, _i, _i, _IP, _IP]),
-    "dlaf_pssygvd": (None, [_ch, _i, _vp, _i, _i, _IP, _vp, _i, _i, _IP, _vp, _vp, _i, _i, _IP, _IP]),
-    "dlaf_pssygvd_factorized": (None, [_ch, _i, _vp, _i, _i, _IP, _vp, _i, _i, _IP, _vp, _vp, _i, _i, _IP, _IP]),
-    "dlaf_pdsygvd": (None, [_ch, _i, _vp, _i, _i, _IP, _vp, _i, _i, _IP, _vp, _vp, _i, _i, _IP, _IP]),
-    "dlaf_pdsygvd_factorized": (None, [_ch, _i, _vp, _i, _i, _IP, _vp, _i, _i, _IP, _vp, _vp, _i, _i, _IP, _IP]),
-    "dlaf_pchegvd": (None, [_ch, _i, _vp, _i, _i, _IP, _vp, _i, _i, _IP, _vp, _vp, _i, _i, _IP, _IP]),
-    "dlaf_pchegvd_factorized": (None, [_ch, _i, _vp, _i, _i, _IP, _vp, _i, _i, _IP, _vp, _vp, _i, _i, _IP, _IP]),
-    "dlaf_pzhegvd": (None, [_ch, _i, _vp, _i, _i, _IP, _vp, _i, _i, _IP, _vp, _vp, _i, _i, _IP, _IP]),
-    "dlaf_pzhegvd_factorized": (None, [_ch, _i, _vp, _i, _i, _IP, _vp, _i, _i, _IP, _vp, _vp, _i, _i, _IP, _IP]),
-    "dlaf_mi355x_tridiagonal_eigensolver_s": (_i, [_i, _i, _vp, _vp, _vp, _vp, _i]),
-    "dlaf_mi355x_tridiagonal_eigensolver_d": (_i, [_i, _i, _vp, _vp, _vp, _vp, _i]),
-    "dlaf_symmetric_eigensolver_partial_spectrum_s": (_i, [_i, _ch, _vp, DLAFDescriptor, _vp, _vp, DLAFDescriptor, _i64, _i64]),
-    "dlaf_symmetric_generalized_eigensolver_partial_spectrum_s": (_i, [_i, _ch, _vp, DLAFDescriptor, _vp, DLAFDescriptor, _vp, _vp, DLAFDescriptor, _i64, _i64]),
-    "dlaf_symmetric_generalized_eigensolver_factorized_partial_spectrum_s": (_i, [_i, _ch, _vp, DLAFDescriptor, _vp, DLAFDescriptor, _vp, _vp, DLAFDescriptor, _i64, _i64]),
-    "dlaf_symmetric_eigensolver_partial_spectrum_d": (_i, [_i, _ch, _vp, DLAFDescriptor, _vp, _vp, DLAFDescriptor, _i64, _i64]),
-    "dlaf_symmetric_generalized_eigensolver_partial_spectrum_d": (_i, [_i, _ch, _vp, DLAFDescriptor, _vp, DLAFDescriptor, _vp, _vp, DLAFDescriptor, _i64, _i64]),
-    "dlaf_symmetric_generalized_eigensolver_factorized_partial_spectrum_d": (_i, [_i, _ch, _vp, DLAFDescriptor, _vp, DLAFDescriptor, _vp, _vp, DLAFDescriptor, _i64, _i64]),
-    "dlaf_hermitian_eigensolver_partial_spectrum_c": (_i, [_i, _ch, _vp, DLAFDescriptor, _vp, _vp, DLAFDescriptor, _i64, _i64]),
-    "dlaf_hermitian_generalized_eigensolver_partial_spectrum_c": (_i, [_i, _ch, _vp, DLAFDescriptor, _vp, DLAFDescriptor, _vp, _vp, DLAFDescriptor, _i64, _i64]),
-    "dlaf_hermitian_generalized_eigensolver_factorized_partial_spectrum_c": (_i, [_i, _ch, _vp, DLAFDescriptor, _vp, DLAFDescriptor, _vp, _vp, DLAFDescriptor, _i64, _i64]),
-    "dlaf_hermitian_eigensolver_partial_spectrum_z": (_i, [_i, _ch, _vp, DLAFDescriptor, _vp, _vp, DLAFDescriptor, _i64, _i64]),
-    "dlaf_hermitian_generalized_eigensolver_partial_spectrum_z": (_i, [_i, _ch, _vp, DLAFDescriptor, _vp, DLAFDescriptor, _vp, _vp, DLAFDescriptor, _i64, _i64]),
-    "dlaf_hermitian_generalized_eigensolver_factorized_partial_spectrum_z": (_i, [_i, _ch, _vp, DLAFDescriptor, _vp, DLAFDescriptor, _vp, _vp, DLAFDescriptor, _i64, _i64]),
-    "dlaf_pssyevd_partial_spectrum": (None, [_ch, _i, _vp, _i, _i, _IP, _vp, _vp, _i, _i, _IP, _i64, _i64, _IP]),
-    "dlaf_pdsyevd_partial_spectrum": (None, [_ch, _i, _vp, _i, _i, _IP, _vp, _vp, _i, _i, _IP, _i64, _i64, _IP]),
-    "dlaf_pcheevd_partial_spectrum": (None, [_ch, _i, _vp, _i, _i, _IP, _vp, _vp, _i, _i, _IP, _i64, _i64, _IP]),
-    "dlaf_pzheevd_partial_spectrum": (None, [_ch, _i, _vp, _i, _i, _IP, _vp, _vp, _i, _i, _IP, _i64, _i64, _IP]),
-    "dlaf_pssygvd_partial_spectrum": (None, [_ch, _i, _vp, _i, _i, _IP, _vp, _i, _i, _IP, _vp, _vp, _i, _i, _IP, _i64, _i64, _IP]),
-    "dlaf_pssygvd_factorized_partial_spectrum": (None, [_ch, _i, _vp, _i, _i, _IP, _vp, _i, _i, _IP, _vp, _vp, _i, _i, _IP, _i64, _i64, _IP]),
-    "dlaf_pdsygvd_partial_spectrum": (None, [_ch, _i, _vp, _i, _i, _IP, _vp, _i, _i, _IP, _vp, _vp, _i, _i, _IP, _i64, _i64, _IP]),
-    "dlaf_pdsygvd_factorized_partial_spectrum": (None, [_ch, _i, _vp, _i, _i, _IP, _vp, _i, _i, _IP, _vp, _vp, _i, _i, _IP, _i64, _i64, _IP]),
-    "dlaf_pchegvd_partial_spectrum": (None, [_ch, _i, _vp, _i, _i, _IP, _vp, _i, _i, _IP, _vp, _vp, _i, _i, _IP, _i64, _i64, _IP]),
-    "dlaf_pchegvd_factorized_partial_spectrum": (None, [_ch, _i, _vp, _i, _i, _IP, _vp, _i, _i, _IP, _vp, _vp, _i, _i, _IP, _i64, _i64, _IP]),
-    "dlaf_pzhegvd_partial_spectrum": (None, [_ch, _i, _vp, _i, _i, _IP, _vp, _i, _i, _IP, _vp, _vp, _i, _i, _IP, _i64, _i64, _IP]),
-    "dlaf_pzhegvd_factorized_partial_spectrum": (None, [_ch, _i, _vp, _i, _i, _IP, _vp, _i, _i, _IP, _vp, _vp, _i, _i, _IP, _i64, _i64, _IP]),
-    "dlaf_mi355x_tridiagonal_eigensolver_partial_spectrum_s": (_i, [_i, _i, _vp, _vp, _vp, _vp, _i, _l, _l]),
-    "dlaf_mi355x_tridiagonal_eigensolver_partial_spectrum_d": (_i, [_i, _i, _vp, _vp, _vp, _vp, _i, _l, _l]),
-    "dlaf_symmetric_eigenvalues_s": (_i, [_i, _ch, _vp, DLAFDescriptor, _vp, _i64, _i64]),
-    "dlaf_symmetric_generalized_eigenvalues_s": (_i, [_i, _ch, _vp, DLAFDescriptor, _vp, DLAFDescriptor, _vp, _i64, _i64]),
-    "dlaf_symmetric_generalized_eigenvalues_factorized_s": (_i, [_i, _ch, _vp, DLAFDescriptor, _vp, DLAFDescriptor, _vp, _i64, _i64]),
-    "dlaf_symmetric_eigensolver_partial_spectrum_by_value_s": (_i, [_i, _ch, _vp, DLAFDescriptor, _vp, _vp, DLAFDescriptor, C.c_float, C.c_float, _LP, _LP]),
-    "dlaf_symmetric_generalized_eigensolver_partial_spectrum_by_value_s": (_i, [_i, _ch, _vp, DLAFDescriptor, _vp, DLAFDescriptor, _vp, _vp, DLAFDescriptor, C.c_float, C.c_float, _LP, _LP]),
-    "dlaf_symmetric_generalized_eigensolver_factorized_partial_spectrum_by_value_s": (_i, [_i, _ch, _vp, DLAFDescriptor, _vp, DLAFDescriptor, _vp, _vp, DLAFDescriptor, C.c_float, C.c_float, _LP, _LP]),
-    "dlaf_pssyevd_eigenvalues": (None, [_ch, _i, _vp, _i, _i, _IP, _vp, _i64, _i64, _IP]),
-    "dlaf_pssygvd_eigenvalues": (None, [_ch, _i, _vp, _i, _i, _IP, _vp, _i, _i, _IP, _vp, _i64, _i64, _IP]),
-    "dlaf_pssygvd_eigenvalues_factorized": (None, [_ch, _i, _vp, _i, _i, _IP, _vp, _i, _i, _IP, _vp, _i64, _i64, _IP]),
-    "dlaf_pssyevd_partial_spectrum_by_value": (None, [_ch, _i, _vp, _i, _i, _IP, _vp, _vp, _i, _i, _IP, C.c_float, C.c_float, _IP, _IP]),
-    "dlaf_pssygvd_partial_spectrum_by_value": (None, [_ch, _i, _vp, _i, _i, _IP, _vp, _i, _i, _IP, _vp, _vp, _i, _i, _IP, C.c_float, C.c_float, _IP, _IP]),
-    "dlaf_pssygvd_factorized_partial_spectrum_by_value": (None, [_ch, _i, _vp, _i, _i, _IP, _vp, _i, _i, _IP, _vp, _vp, _i, _i, _IP, C.c_float, C.c_float, _IP, _IP]),
-    "dlaf_symmetric_eigenvalues_d": (_i, [_i, _ch, _vp, DLAFDescriptor, _vp, _i64, _i64]),
-    "dlaf_symmetric_generalized_eigenvalues_d": (_i, [_i, _ch, _vp, DLAFDescriptor, _vp, DLAFDescriptor, _vp, _i64, _i64]),
-    "dlaf_symmetric_generalized_eigenvalues_factorized_d": (_i, [_i, _ch, _vp, DLAFDescriptor, _vp, DLAFDescriptor, _vp, _i64, _i64]),
-    "dlaf_symmetric_eigensolver_partial_spectrum_by_value_d": (_i, [_i, _ch, _vp, DLAFDescriptor, _vp, _vp, DLAFDescriptor, C.c_double, C.c_double, _LP, _LP]),
-    "dlaf_symmetric_generalized_eigensolver_partial_spectrum_by_value_d": (_i, [_i, _ch, _vp, DLAFDescriptor, _vp, DLAFDescriptor, _vp, _vp, DLAFDescriptor, C.c_double, C.c_double, _LP, _LP]),
-    "dlaf_symmetric_generalized_eigensolver_factorized_partial_spectrum_by_value_d": (_i, [_i, _ch, _vp, DLAFDescriptor, _vp, DLAFDescriptor, _vp, _vp, DLAFDescriptor, C.c_double, C.c_double, _LP, _LP]),
-    "dlaf_pdsyevd_eigenvalues": (None, [_ch, _i, _vp, _i, _i, _IP, _vp, _i64, _i64, _IP]),
-    "dlaf_pdsygvd_eigenvalues": (None, [_ch, _i, _vp, _i, _i, _IP, _vp, _i, _i, _IP, _vp, _i64, _i64, _IP]),
-    "dlaf_pdsygvd_eigenvalues_factorized": (None, [_ch, _i, _vp, _i, _i, _IP, _vp, _i, _i, _IP, _vp, _i64, _i64, _IP]),
-    "dlaf_pdsyevd_partial_spectrum_by_value": (None, [_ch, _i, _vp, _i, _i, _IP, _vp, _vp, _i, _i, _IP, C.c_double, C.c_double, _IP, _IP]),
-    "dlaf_pdsygvd_partial_spectrum_by_value": (None, [_ch, _i, _vp, _i, _i, _IP, _vp, _i, _i, _IP, _vp, _vp, _i, _i, _IP, C.c_double, C.c_double, _IP, _IP]),
-    "dlaf_pdsygvd_factorized_partial_spectrum_by_value": (None, [_ch, _i, _vp, _i, _i, _IP, _vp, _i, _i, _IP, _vp, _vp, _i, _i, _IP, C.c_double, C.c_double, _IP, _IP]),
-    "dlaf_hermitian_eigenvalues_c": (_i, [_i, _ch, _vp, DLAFDescriptor, _vp, _i64, _i64]),
-    "dlaf_hermitian_generalized_eigenvalues_c": (_i, [_i, _ch, _vp, DLAFDescriptor, _vp, DLAFDescriptor, _vp, _i64, _i64]),
-    "dlaf_hermitian_generalized_eigenvalues_factorized_c": (_i, [_i, _ch, _vp, DLAFDescriptor, _vp, DLAFDescriptor, _vp, _i64, _i64]),
-    "dlaf_hermitian_eigensolver_partial_spectrum_by_value_c": (_i, [_i, _ch, _vp, DLAFDescriptor, _vp, _vp, DLAFDescriptor, C.c_float, C.c_float, _LP, _LP]),
-    "dlaf_hermitian_generalized_eigensolver_partial_spectrum_by_value_c": (_i, [_i, _ch, _vp, DLAFDescriptor, _vp, DLAFDescriptor, _vp, _vp, DLAFDescriptor, C.c_float, C.c_float, _LP, _LP]),
-    "dlaf_hermitian_generalized_eigensolver_factorized_partial_spectrum_by_value_c": (_i, [_i, _ch, _vp, DLAFDescriptor, _vp, DLAFDescriptor, _vp, _vp, DLAFDescriptor, C.c_float, C.c_float, _LP, _LP]),
-    "dlaf_pcheevd_eigenvalues": (None, [_ch, _i, _vp, _i, _i, _IP, _vp, _i64, _i64, _IP]),
-    "dlaf_pchegvd_eigenvalues": (None, [_ch, _i, _vp, _i, _i, _IP, _vp, _i, _i, _IP, _vp, _i64, _i64, _IP]),
-    "dlaf_pchegvd_eigenvalues_factorized": (None, [_ch, _i, _vp, _i, _i, _IP, _vp, _i, _i, _IP, _vp, _i64, _i64, _IP]),
-    "dlaf_pcheevd_partial_spectrum_by_value": (None, [_ch, _i, _vp, _i, _i, _IP, _vp, _vp, _i, _i, _IP, C.c_float, C.c_float, _IP, _IP]),
-    "dlaf_pchegvd_partial_spectrum_by_value": (None, [_ch, _i, _vp, _i, _i, _IP, _vp, _i, _i, _IP, _vp, _vp, _i, _i, _IP, C.c_float, C.c_float, _IP, _IP]),
-    "dlaf_pchegvd_factorized_partial_spectrum_by_value": (None, [_ch, _i, _vp, _i, _i, _IP, _vp, _i, _i, _IP, _vp, _vp, _i, _i, _IP, C.c_float, C.c_float, _IP, _IP]),
-    "dlaf_hermitian_eigenvalues_z": (_i, [_i, _ch, _vp, DLAFDescriptor, _vp, _i64, _i64]),
-    "dlaf_hermitian_generalized_eigenvalues_z": (_i, [_i, _ch, _vp, DLAFDescriptor, _vp, DLAFDescriptor, _vp, _i64, _i64]),
-    "dlaf_hermitian_generalized_eigenvalues_factorized_z": (_i, [_i, _ch, _vp, DLAFDescriptor, _vp, DLAFDescriptor, _vp, _i64, _i64]),
-    "dlaf_hermitian_eigensolver_partial_spectrum_by_value_z": (_i, [_i, _ch, _vp, DLAFDescriptor, _vp, _vp, DLAFDescriptor, C.c_double, C.c_double, _LP, _LP]),
-    "dlaf_hermitian_generalized_eigensolver_partial_spectrum_by_value_z": (_i, [_i, _ch, _vp, DLAFDescriptor, _vp, DLAFDescriptor, _vp, _vp, DLAFDescriptor, C.c_double, C.c_double, _LP, _LP]),
-    "dlaf_hermitian_generalized_eigensolver_factorized_partial_spectrum_by_value_z": (_i, [_i, _ch, _vp, DLAFDescriptor, _vp, DLAFDescriptor, _vp, _vp, DLAFDescriptor, C.c_double, C.c_double, _LP, _LP]),
-    "dlaf_pzheevd_eigenvalues": (None, [_ch, _i, _vp, _i, _i, _IP, _vp, _i64, _i64, _IP]),
-    "dlaf_pzhegvd_eigenvalues": (None, [_ch, _i, _vp, _i, _i, _IP, _vp, _i, _i, _IP, _vp, _i64, _i64, _IP]),
-    "dlaf_pzhegvd_eigenvalues_factorized": (None, [_ch, _i, _vp, _i, _i, _IP, _vp, _i, _i, _IP, _vp, _i64, _i64, _IP]),
-    "dlaf_pzheevd_partial_spectrum_by_value": (None, [_ch, _i, _vp, _i, _i, _IP, _vp, _vp, _i, _i, _IP, C.c_double, C.c_double, _IP, _IP]),
-    "dlaf_pzhegvd_partial_spectrum_by_value": (None, [_ch, _i, _vp, _i, _i, _IP, _vp, _i, _i, _IP, _vp, _vp, _i, _i, _IP, C.c_double, C.c_double, _IP, _IP]),
-    "dlaf_pzhegvd_factorized_partial_spectrum_by_value": (None, [_ch, _i, _vp, _i, _i, _IP, _vp, _i, _i, _IP, _vp, _vp, _i, _i, _IP, C.c_double, C.c_double, _IP, _IP]),
-    "dlaf_mi355x_tridiagonal_eigenvalues_s": (_i, [_i, _vp, _vp, _vp, _l, _l]),
-    "dlaf_mi355x_tridiagonal_sturm_count_s": (_i, [_i, _vp, _vp, _l, _vp, _vp]),
-    "dlaf_mi355x_tridiagonal_eigenvalues_d": (_i, [_i, _vp, _vp, _vp, _l, _l]),
-    "dlaf_mi355x_tridiagonal_sturm_count_d": (_i, [_i, _vp, _vp, _l, _vp, _vp]),
+    "dlaf_mi355x_solver_profile": (_i, [_DP, _DP]),
+    "dlaf_mi355x_multiplication_profile": (_i, [_DP, _DP]),
+    "dlaf_mi355x_addition_profile": (_i, [_DP, _DP]),
+    "dlaf_mi355x_inverse_profile": (_i, [_DP, _DP]),
+    "dlaf_mi355x_norm_profile": (_i, [_DP, _DP]),
+    "dlaf_mi355x_red2band_profile": (_i, [_DP, _DP]),
+    "dlaf_mi355x_eigensolver_profile": (_i, [_DP]),
     "dlaf_mi355x_sturm_layout": (_i, [_IP]),
-    "dlaf_mi355x_partial_spectrum_plan": (_i, [_l, _i, _i, _i, _i, _l, _l, C.POINTER(C.c_long)]),
-    "dlaf_mi355x_eigensolver_profile": (_i, [C.POINTER(C.c_double)]),
+    "dlaf_mi355x_partial_spectrum_plan": (_i, [_l, _i, _i, _i, _i, _l, _l, _LP]),
     "dlaf_mi355x_get_band_size": (_i, [_i]),
-    "dlaf_mi355x_red2band_panel_stats": (_i, [C.POINTER(C.c_long), C.POINTER(C.c_long)]),
-    "dlaf_mi355x_workspace_pool_release": (C.c_long, []),
+    "dlaf_mi355x_red2band_panel_stats": (_i, [_LP, _LP]),
     "dlaf_mi355x_get_eigensolver_min_band": (_i, []),
     "dlaf_mi355x_set_eigensolver_min_band": (None, [_i]),
-    "dlaf_mi355x_red2band_profile": (_i, [C.POINTER(C.c_double), C.POINTER(C.c_double)]),
-    "dlaf_mi355x_set_random_hpd": (_i, [_i, _ch, _vp, DLAFDescriptor, _i]),
     "dlaf_mi355x_tile_potrf": (_i, [_ch, _ch, _i, _vp, _i]),
     "dlaf_mi355x_tile_trsm": (_i, [_ch, _ch, _i, _i, _vp, _i, _vp, _i]),
     "dlaf_mi355x_tile_herk": (_i, [_ch, _ch, _i, _i, _vp, _i, _vp, _i]),
     "dlaf_mi355x_tile_gemm": (_i, [_ch, _ch, _i, _i, _i, _vp, _i, _vp, _i, _vp, _i]),
-    "dlaf_mi355x_update_direct_s": (_i, [C.POINTER(UpdateDesc), _vp, _vp, _vp, _vp, _vp, _vp]),
-    "dlaf_mi355x_update_direct_d": (_i, [C.POINTER(UpdateDesc), _vp, _vp, _vp, _vp, _vp, _vp]),
-    "dlaf_mi355x_update_direct_c": (_i, [C.POINTER(UpdateDesc), _vp, _vp, _vp, _vp, _vp, _vp]),
-    "dlaf_mi355x_update_direct_z": (_i, [C.POINTER(UpdateDesc), _vp, _vp, _vp, _vp, _vp, _vp]),
     "dlaf_mi355x_update_bulk_slots": (_l, [_ch]),
-    "dlaf_mi355x_trsm_direct_s": (_i, [C.POINTER(TrsmDesc), _vp, _vp, _vp]),
-    "dlaf_mi355x_trsm_direct_d": (_i, [C.POINTER(TrsmDesc), _vp, _vp, _vp]),
-    "dlaf_mi355x_trsm_direct_c": (_i, [C.POINTER(TrsmDesc), _vp, _vp, _vp]),
-    "dlaf_mi355x_trsm_direct_z": (_i, [C.POINTER(TrsmDesc), _vp, _vp, _vp]),
-    "dlaf_mi355x_potrf_direct_s": (_i, [C.POINTER(PotrfDesc), _vp, _vp]),
-    "dlaf_mi355x_potrf_direct_d": (_i, [C.POINTER(PotrfDesc), _vp, _vp]),
-    "dlaf_mi355x_potrf_direct_c": (_i, [C.POINTER(PotrfDesc), _vp, _vp]),
-    "dlaf_mi355x_potrf_direct_z": (_i, [C.POINTER(PotrfDesc), _vp, _vp]),
     "dlaf_mi355x_dist_owner": (_i, [_l, _i, _i]),
     "dlaf_mi355x_dist_local_tile": (_l, [_l, _i, _i, _i]),
     "dlaf_mi355x_dist_next_local_tile": (_l, [_l, _i, _i, _i]),
@@ -447,6 +193,94 @@ SIGNATURES = {
     "dlaf_mi355x_dist_local_size": (_l, [_l, _i, _i, _i, _i]),
     "dlaf_mi355x_dist_local_tiles": (_l, [_l, _i, _i, _i, _i]),
 }
+
+# the entries that exist per element type, each family stated once: (names, restype, argtypes[, types])
+_FAMILIES = [
+    # factorization, solver, multiplication (include/dlaf_c/factorization/cholesky.h, dlaf_mi355x.h)
+    ("dlaf_cholesky_factorization_{t}", _i, [_i, _ch, _vp, _D]),
+    ("dlaf_p{t}potrf", None, [_ch, _i, *_A, _IP]),
+    ("dlaf_mi355x_p{t}potrs", None, [_ch, _i, _i, *_A, *_A, _IP]),
+    ("dlaf_mi355x_triangular_solver_{t}", _i, [_i, _ch, _ch, _ch, _ch, _vp, _vp, _D, _vp, _D]),
+    ("dlaf_mi355x_triangular_multiplication_{t}", _i, [_i, _ch, _ch, _ch, _ch, _vp, _vp, _D, _vp, _D]),
+    ("dlaf_mi355x_p{t}trsm", None, [_ch, _ch, _ch, _ch, _i, _i, _vp, *_A, *_A]),
+    ("dlaf_mi355x_p{t}trmm", None, [_ch, _ch, _ch, _ch, _i, _i, _vp, *_A, *_A]),
+    ("dlaf_mi355x_hermitian_multiplication_{t}", _i, [_i, _ch, _ch, _vp, _vp, _D, _vp, _D, _vp, _vp, _D]),
+    (["dlaf_mi355x_pssymm", "dlaf_mi355x_pdsymm", "dlaf_mi355x_pchemm", "dlaf_mi355x_pzhemm"], None,
+     [_ch, _ch, _i, _i, _vp, *_A, *_A, _vp, *_A]),
+    ("dlaf_mi355x_general_multiplication_{t}", _i, [_i, _ch, _ch, _vp, _vp, _D, _vp, _D, _vp, _vp, _D]),
+    ("dlaf_mi355x_p{t}gemm", None, [_ch, _ch, _i, _i, _i, _vp, *_A, *_A, _vp, *_A]),
+    # rank updates and matrix functions
+    ("dlaf_mi355x_hermitian_rank_k_update_{t}", _i, [_i, _ch, _ch, _vp, _vp, _D, _vp, _vp, _D]),
+    ("dlaf_mi355x_hermitian_rank_2k_update_{t}", _i, [_i, _ch, _ch, _vp, _vp, _D, _vp, _D, _vp, _vp, _D]),
+    (["dlaf_mi355x_pssyrk", "dlaf_mi355x_pdsyrk", "dlaf_mi355x_pcherk", "dlaf_mi355x_pzherk"], None,
+     [_ch, _ch, _i, _i, _vp, *_A, _vp, *_A]),
+    (["dlaf_mi355x_pssyr2k", "dlaf_mi355x_pdsyr2k", "dlaf_mi355x_pcher2k", "dlaf_mi355x_pzher2k"], None,
+     [_ch, _ch, _i, _i, _vp, *_A, *_A, _vp, *_A]),
+    ("dlaf_mi355x_hermitian_weighted_rank_k_update_{t}", _i, [_i, _ch, _ch, _vp, _vp, _D, _vp, _vp, _vp, _D]),
+    ("dlaf_mi355x_hermitian_function_{t}", _i, [_i, _ch, _vp, _D, _vp, _weights, _vp, _vp, _vp, _vp]),
+    ("dlaf_mi355x_hermitian_power_{t}", _i, [_i, _ch, _vp, _D, _vp, C.c_double, C.c_double, _LP]),
+    # addition, transposition, copy, completion
+    ("dlaf_mi355x_general_addition_{t}", _i, [_i, _ch, _ch, _vp, _vp, _D, _vp, _vp, _D]),
+    ("dlaf_mi355x_hermitian_complete_{t}", _i, [_i, _ch, _ch, _vp, _D]),
+    ("dlaf_mi355x_p{t}geadd", None, [_ch, _i, _i, _vp, *_A, _vp, *_A]),
+    ("dlaf_mi355x_p{t}tradd", None, [_ch, _ch, _i, _i, _vp, *_A, _vp, *_A]),
+    ("dlaf_mi355x_p{t}lacpy", None, [_ch, _i, _i, *_A, *_A]),
+    (["dlaf_mi355x_pstran", "dlaf_mi355x_pdtran", "dlaf_mi355x_pctranu", "dlaf_mi355x_pctranc", "dlaf_mi355x_pztranu",
+      "dlaf_mi355x_pztranc"], None, [_i, _i, _vp, *_A, _vp, *_A]),
+    # gen_to_std, inverses, norms
+    ("dlaf_mi355x_generalized_to_standard_{t}", _i, [_i, _ch, _vp, _D, _vp, _D]),
+    ("dlaf_mi355x_p{t}hegst", None, [_i, _ch, _i, *_A, *_A, _vp, _IP]),
+    ("dlaf_mi355x_triangular_inverse_{t}", _i, [_i, _ch, _ch, _vp, _D]),
+    ("dlaf_mi355x_inverse_from_cholesky_factor_{t}", _i, [_i, _ch, _vp, _D]),
+    ("dlaf_mi355x_p{t}trtri", None, [_ch, _ch, _i, *_A, _IP]),
+    ("dlaf_mi355x_p{t}potri", None, [_ch, _i, *_A, _IP]),
+    ("dlaf_mi355x_general_norm_{t}", _i, [_i, _ch, _vp, _D, _DP]),
+    ("dlaf_mi355x_hermitian_norm_{t}", _i, [_i, _ch, _ch, _vp, _D, _DP]),
+    ("dlaf_mi355x_triangular_norm_{t}", _i, [_i, _ch, _ch, _ch, _vp, _D, _DP]),
+    ("dlaf_mi355x_p{t}lange", _real, [_ch, _i, _i, *_A]),
+    ("dlaf_mi355x_p{t}lan{sy}", _real, [_ch, _ch, _i, *_A]),
+    ("dlaf_mi355x_p{t}lantr", _real, [_ch, _ch, _ch, _i, *_A]),
+    # the eigensolver stages
+    ("dlaf_mi355x_reduction_to_band_{t}", _i, [_i, _vp, _D, _i, _vp]),
+    ("dlaf_mi355x_bt_reduction_to_band_{t}", _i, [_i, _i, _vp, _D, _vp, _D, _vp]),
+    ("dlaf_mi355x_band_to_tridiagonal_{t}", _i, [_i, _vp, _D, _i, _vp, _vp, _vp, _i]),
+    ("dlaf_mi355x_bt_band_to_tridiagonal_{t}", _i, [_i, _i, _i, _vp, _i, _vp, _i]),
+    ("dlaf_mi355x_tridiagonal_eigensolver_{t}", _i, [_i, _i, _vp, _vp, _vp, _vp, _i], "sd"),
+    ("dlaf_mi355x_tridiagonal_eigensolver_partial_spectrum_{t}", _i, [_i, _i, _vp, _vp, _vp, _vp, _i, _l, _l], "sd"),
+    ("dlaf_mi355x_tridiagonal_eigenvalues_{t}", _i, [_i, _vp, _vp, _vp, _l, _l], "sd"),
+    ("dlaf_mi355x_tridiagonal_sturm_count_{t}", _i, [_i, _vp, _vp, _l, _vp, _vp], "sd"),
+    # the direct doors of the kernels
+    ("dlaf_mi355x_update_direct_{t}", _i, [C.POINTER(UpdateDesc), _vp, _vp, _vp, _vp, _vp, _vp]),
+    ("dlaf_mi355x_trsm_direct_{t}", _i, [C.POINTER(TrsmDesc), _vp, _vp, _vp]),
+    ("dlaf_mi355x_potrf_direct_{t}", _i, [C.POINTER(PotrfDesc), _vp, _vp]),
+]
+
+# the eigensolver drivers (include/dlaf_c/eigensolver/*.h and their partial-spectrum / eigenvalues-only forms): the
+# standard problem takes A, the generalized one A and B ("", "_factorized"); every driver exists in three selections
+_EVD = [_vp, _D, _vp, _vp, _D]                    # a, desca, w, z, descz
+_GVD = [_vp, _D, _vp, _D, _vp, _vp, _D]           # a, desca, b, descb, w, z, descz
+_PEVD = [*_A, _vp, *_A]                           # a, ia, ja, desca, w, z, iz, jz, descz
+_PGVD = [*_A, *_A, _vp, *_A]                      # a, ..., b, ..., w, z, ...
+for _sel, _c, _p in (("", [], [_IP]), ("_partial_spectrum", [_i64, _i64], [_i64, _i64, _IP]),
+                     ("_partial_spectrum_by_value", [_real, _real, _LP, _LP], [_real, _real, _IP, _IP])):
+    _FAMILIES.append(("dlaf_{symmetric}_eigensolver" + _sel + "_{t}", _i, [_i, _ch, *_EVD, *_c]))
+    _FAMILIES.append(("dlaf_p{t}{sy}evd" + _sel, None, [_ch, _i, *_PEVD, *_p]))
+    for _fac in ("", "_factorized"):
+        _FAMILIES.append(("dlaf_{symmetric}_generalized_eigensolver" + _fac + _sel + "_{t}", _i, [_i, _ch, *_GVD, *_c]))
+        _FAMILIES.append(("dlaf_p{t}{sy}gvd" + _fac + _sel, None, [_ch, _i, *_PGVD, *_p]))
+_FAMILIES += [
+    ("dlaf_{symmetric}_eigenvalues_{t}", _i, [_i, _ch, _vp, _D, _vp, _i64, _i64]),
+    ("dlaf_p{t}{sy}evd_eigenvalues", None, [_ch, _i, *_A, _vp, _i64, _i64, _IP]),
+]
+for _fac in ("", "_factorized"):
+    _FAMILIES.append(("dlaf_{symmetric}_generalized_eigenvalues" + _fac + "_{t}", _i,
+                      [_i, _ch, _vp, _D, _vp, _D, _vp, _i64, _i64]))
+    _FAMILIES.append(("dlaf_p{t}{sy}gvd_eigenvalues" + _fac, None, [_ch, _i, *_A, *_A, _vp, _i64, _i64, _IP]))
+
+for _f in _FAMILIES:
+    _entries = _family(*_f)
+    assert not set(_entries) & set(SIGNATURES), set(_entries) & set(SIGNATURES)  # a family stated twice
+    SIGNATURES.update(_entries)
 
 _lib = None
 

@@ -9,8 +9,11 @@ import ctypes as C
 
 import numpy as np
 
-from .capi import DLAFDescriptor, lib, type_char
-from .cholesky import DeviceMatrix, GeneralDeviceMatrix, Grid, _ld_of, _ptr, make_descriptor
+from ._abi import (check_stage, desc9, descriptor, entry, global_size, global_sizes, ld_of, make_descriptor, ptr, real_dtype,
+                   two_doubles)
+from .capi import lib, type_char
+from .device_matrix import DeviceMatrix, GeneralDeviceMatrix
+from .grid import Grid
 
 
 def get_band_size(nb: int) -> int:
@@ -40,15 +43,10 @@ def reduction_to_band(grid: Grid, a: np.ndarray, nb: int, band_size: int, isrc: 
     overwritten with the band and the Householder reflectors below it; returns taus (n - band_size - 1 values, all
     of them on every process)."""
     t = type_char(a.dtype)
-    if n is None:
-        if grid.nranks != 1:
-            raise ValueError("the global size n is required on a distributed grid")
-        n = a.shape[0]
+    n = global_size(grid, n, a)
     taus = np.zeros(max(0, n - band_size - 1), dtype=a.dtype)
-    da = make_descriptor(n, nb, _ld_of(a), isrc, jsrc)
-    r = getattr(lib(), f"dlaf_mi355x_reduction_to_band_{t}")(grid.context, _ptr(a), da, band_size, _ptr(taus))
-    if r != 0:
-        raise RuntimeError(f"dlaf_mi355x_reduction_to_band_{t} returned {r}")
+    da = make_descriptor(n, nb, ld_of(a), isrc, jsrc)
+    check_stage(f"dlaf_mi355x_reduction_to_band_{t}", grid.context, ptr(a), da, band_size, ptr(taus))
     return taus
 
 
@@ -56,44 +54,29 @@ def bt_reduction_to_band(grid: Grid, band_size: int, c: np.ndarray, v: np.ndarra
                          jsrc: int = 0, c_jsrc: int = 0, n: int | None = None, k: int | None = None) -> None:
     """bt_reduction_to_band(grid, band_size, mat_c, mat_v, taus): c (local part of the n x k matrix) <- Q c."""
     t = type_char(c.dtype)
-    if n is None or k is None:
-        if grid.nranks != 1:
-            raise ValueError("global sizes n, k are required on a distributed grid")
-        n, k = v.shape[0], c.shape[1]
-    dc = DLAFDescriptor(n, k, nb, nb, isrc, c_jsrc, 0, 0, _ld_of(c))
-    dv = make_descriptor(n, nb, _ld_of(v), isrc, jsrc)
-    r = getattr(lib(), f"dlaf_mi355x_bt_reduction_to_band_{t}")(grid.context, band_size, _ptr(c), dc, _ptr(v), dv, _ptr(taus))
-    if r != 0:
-        raise RuntimeError(f"dlaf_mi355x_bt_reduction_to_band_{t} returned {r}")
+    n, k = global_sizes(grid, (n, k), lambda: (v.shape[0], c.shape[1]), "global sizes n, k are")
+    dc = descriptor(n, k, nb, (isrc, c_jsrc), ld_of(c))
+    dv = make_descriptor(n, nb, ld_of(v), isrc, jsrc)
+    check_stage(f"dlaf_mi355x_bt_reduction_to_band_{t}", grid.context, band_size, ptr(c), dc, ptr(v), dv, ptr(taus))
 
 
 def reduction_to_band_device(a: DeviceMatrix, band_size: int) -> np.ndarray:
     """The same on a resident matrix (uplo 'L'); returns taus."""
     taus = np.zeros(max(0, a.n - band_size - 1), dtype=a.dtype)
-    r = lib().dlaf_mi355x_reduction_to_band_device(a._h, band_size, _ptr(taus))
-    if r != 0:
-        raise RuntimeError(f"dlaf_mi355x_reduction_to_band_device returned {r}")
+    check_stage("dlaf_mi355x_reduction_to_band_device", a._h, band_size, ptr(taus))
     return taus
 
 
 def bt_reduction_to_band_device(band_size: int, c: GeneralDeviceMatrix, v: DeviceMatrix, taus: np.ndarray) -> None:
-    r = lib().dlaf_mi355x_bt_reduction_to_band_device(band_size, c._h, v._h, _ptr(taus))
-    if r != 0:
-        raise RuntimeError(f"dlaf_mi355x_bt_reduction_to_band_device returned {r}")
+    check_stage("dlaf_mi355x_bt_reduction_to_band_device", band_size, c._h, v._h, ptr(taus))
 
 
 def red2band_profile():
     """(device ms, whole-grid algorithmic flops) of the last reduction_to_band / bt_reduction_to_band here."""
-    ms, fl = C.c_double(0), C.c_double(0)
-    lib().dlaf_mi355x_red2band_profile(C.byref(ms), C.byref(fl))
-    return ms.value, fl.value
+    return two_doubles("dlaf_mi355x_red2band_profile")
 
 
 # ---- the stages behind reduction_to_band and the eigensolver drivers --------------------------------------------
-def _real_dtype(dtype):
-    return np.zeros(0, dtype=dtype).real.dtype
-
-
 def band_to_tridiagonal(grid: Grid, a: np.ndarray, nb: int, band_size: int, isrc: int = 0, jsrc: int = 0,
                         n: int | None = None):
     """band_to_tridiagonal<Backend::MC>(grid, Lower, band_size, mat_a) (include/dlaf/eigensolver/band_to_tridiag.h:74-176):
@@ -101,19 +84,13 @@ def band_to_tridiagonal(grid: Grid, a: np.ndarray, nb: int, band_size: int, isrc
     off-diagonal (n - 1, real) and the n x n matrix of compact Householder reflectors (tau in the place of the leading
     1, band_to_tridiag.h:40-72) -- complete on every process."""
     t = type_char(a.dtype)
-    if n is None:
-        if grid.nranks != 1:
-            raise ValueError("the global size n is required on a distributed grid")
-        n = a.shape[0]
-    rt = _real_dtype(a.dtype)
+    n = global_size(grid, n, a)
+    rt = real_dtype(a.dtype)
     d = np.zeros(n, dtype=rt)
     e = np.zeros(n, dtype=rt)
     v = np.zeros((n, n), dtype=a.dtype, order="F")
-    da = make_descriptor(n, nb, _ld_of(a), isrc, jsrc)
-    r = getattr(lib(), f"dlaf_mi355x_band_to_tridiagonal_{t}")(grid.context, _ptr(a), da, band_size, _ptr(d), _ptr(e),
-                                                               _ptr(v), max(1, n))
-    if r != 0:
-        raise RuntimeError(f"dlaf_mi355x_band_to_tridiagonal_{t} returned {r}")
+    da = make_descriptor(n, nb, ld_of(a), isrc, jsrc)
+    check_stage(f"dlaf_mi355x_band_to_tridiagonal_{t}", grid.context, ptr(a), da, band_size, ptr(d), ptr(e), ptr(v), max(1, n))
     return d, e[:max(n - 1, 0)].copy(), v
 
 
@@ -122,9 +99,7 @@ def bt_band_to_tridiagonal(band_size: int, e: np.ndarray, v: np.ndarray) -> None
     e (n x k, column-major) <- Q e."""
     t = type_char(e.dtype)
     n, k = e.shape
-    r = getattr(lib(), f"dlaf_mi355x_bt_band_to_tridiagonal_{t}")(band_size, n, k, _ptr(v), _ld_of(v), _ptr(e), _ld_of(e))
-    if r != 0:
-        raise RuntimeError(f"dlaf_mi355x_bt_band_to_tridiagonal_{t} returned {r}")
+    check_stage(f"dlaf_mi355x_bt_band_to_tridiagonal_{t}", band_size, n, k, ptr(v), ld_of(v), ptr(e), ld_of(e))
 
 
 def _index_range(eigenvalues_index, n):
@@ -146,15 +121,11 @@ def tridiagonal_eigensolver(d: np.ndarray, e: np.ndarray, nb: int = 512, eigenva
         begin, end = _index_range(eigenvalues_index, n)
         if z is None:
             z = np.zeros((n, max(end - begin, 0)), dtype=d.dtype, order="F")
-        name = f"dlaf_mi355x_tridiagonal_eigensolver_partial_spectrum_{t}"
-        r = getattr(lib(), name)(n, nb, _ptr(d), _ptr(e), _ptr(w), _ptr(z), _ld_of(z), begin, end)
-        if r != 0:
-            raise RuntimeError(f"{name} returned {r}")
+        check_stage(f"dlaf_mi355x_tridiagonal_eigensolver_partial_spectrum_{t}", n, nb, ptr(d), ptr(e), ptr(w), ptr(z),
+                    ld_of(z), begin, end)
         return w, z
     z = np.zeros((n, n), dtype=d.dtype, order="F")
-    r = getattr(lib(), f"dlaf_mi355x_tridiagonal_eigensolver_{t}")(n, nb, _ptr(d), _ptr(e), _ptr(w), _ptr(z), max(1, n))
-    if r != 0:
-        raise RuntimeError(f"dlaf_mi355x_tridiagonal_eigensolver_{t} returned {r}")
+    check_stage(f"dlaf_mi355x_tridiagonal_eigensolver_{t}", n, nb, ptr(d), ptr(e), ptr(w), ptr(z), max(1, n))
     return w, z
 
 
@@ -186,10 +157,7 @@ def tridiagonal_eigenvalues(d: np.ndarray, e: np.ndarray, eigenvalues_index=None
     if w is None:
         w = np.zeros(n, dtype=d.dtype)
     begin, end = (0, n) if eigenvalues_index is None else _index_range(eigenvalues_index, n)
-    name = f"dlaf_mi355x_tridiagonal_eigenvalues_{t}"
-    r = getattr(lib(), name)(n, _ptr(d), _ptr(e), _ptr(w), begin, end)
-    if r != 0:
-        raise RuntimeError(f"{name} returned {r}")
+    check_stage(f"dlaf_mi355x_tridiagonal_eigenvalues_{t}", n, ptr(d), ptr(e), ptr(w), begin, end)
     return w
 
 
@@ -202,10 +170,7 @@ def tridiagonal_sturm_count(d: np.ndarray, e: np.ndarray, shifts) -> np.ndarray:
     e = np.ascontiguousarray(e, dtype=d.dtype)
     shifts = np.ascontiguousarray(shifts, dtype=d.dtype).reshape(-1)
     counts = np.zeros(shifts.shape[0], dtype=np.int64)
-    name = f"dlaf_mi355x_tridiagonal_sturm_count_{t}"
-    r = getattr(lib(), name)(n, _ptr(d), _ptr(e), shifts.shape[0], _ptr(shifts), _ptr(counts))
-    if r != 0:
-        raise RuntimeError(f"{name} returned {r}")
+    check_stage(f"dlaf_mi355x_tridiagonal_sturm_count_{t}", n, ptr(d), ptr(e), shifts.shape[0], ptr(shifts), ptr(counts))
     return counts
 
 
@@ -216,18 +181,12 @@ def hermitian_eigenvalues(grid: Grid, uplo: str, a: np.ndarray, nb: int, isrc: i
     no eigenvector matrix.  `a` (local part, the uplo triangle referenced) is not modified.  Only w[begin:end] is
     written (w: a preallocated array of n reals); returns w."""
     t = type_char(a.dtype)
-    if n is None:
-        if grid.nranks != 1:
-            raise ValueError("the global size n is required on a distributed grid")
-        n = a.shape[0]
+    n = global_size(grid, n, a)
     if w is None:
-        w = np.zeros(n, dtype=_real_dtype(a.dtype))
+        w = np.zeros(n, dtype=real_dtype(a.dtype))
     begin, end = (0, n) if eigenvalues_index is None else _index_range(eigenvalues_index, n)
-    da = make_descriptor(n, nb, _ld_of(a), isrc, jsrc)
-    name = f"dlaf_{_eig_name(t)}_eigenvalues_{t}"
-    r = getattr(lib(), name)(grid.context, uplo.encode()[0:1], _ptr(a), da, _ptr(w), begin, end)
-    if r != 0:
-        raise RuntimeError(f"{name} returned {r}")
+    da = make_descriptor(n, nb, ld_of(a), isrc, jsrc)
+    check_stage(f"dlaf_{_eig_name(t)}_eigenvalues_{t}", grid.context, uplo.encode()[0:1], ptr(a), da, ptr(w), begin, end)
     return w
 
 
@@ -238,20 +197,30 @@ def hermitian_generalized_eigenvalues(grid: Grid, uplo: str, a: np.ndarray, b: n
     Cholesky of b (unless factorized), generalized_to_standard, then as hermitian_eigenvalues.  b ends up holding its
     Cholesky factor."""
     t = type_char(a.dtype)
-    if n is None:
-        if grid.nranks != 1:
-            raise ValueError("the global size n is required on a distributed grid")
-        n = a.shape[0]
+    n = global_size(grid, n, a)
     if w is None:
-        w = np.zeros(n, dtype=_real_dtype(a.dtype))
+        w = np.zeros(n, dtype=real_dtype(a.dtype))
     begin, end = (0, n) if eigenvalues_index is None else _index_range(eigenvalues_index, n)
-    da = make_descriptor(n, nb, _ld_of(a), isrc, jsrc)
-    db = make_descriptor(n, nb, _ld_of(b), isrc, jsrc)
-    name = f"dlaf_{_eig_name(t)}_generalized_eigenvalues{'_factorized' if factorized else ''}_{t}"
-    r = getattr(lib(), name)(grid.context, uplo.encode()[0:1], _ptr(a), da, _ptr(b), db, _ptr(w), begin, end)
-    if r != 0:
-        raise RuntimeError(f"{name} returned {r}")
+    da = make_descriptor(n, nb, ld_of(a), isrc, jsrc)
+    db = make_descriptor(n, nb, ld_of(b), isrc, jsrc)
+    check_stage(f"dlaf_{_eig_name(t)}_generalized_eigenvalues{'_factorized' if factorized else ''}_{t}", grid.context,
+                uplo.encode()[0:1], ptr(a), da, ptr(b), db, ptr(w), begin, end)
     return w
+
+
+def _solve(stem: str, t: str, grid, uplo, operands, n, w, z, dz, eigenvalues_index, eigenvalues_value):
+    """The three forms of a driver: all eigenpairs, <stem>_partial_spectrum and <stem>_partial_spectrum_by_value."""
+    head = (grid.context, uplo.encode()[0:1], *operands, ptr(w), ptr(z), dz)
+    if eigenvalues_value is not None:
+        begin, end = C.c_long(-1), C.c_long(-1)
+        check_stage(f"{stem}_partial_spectrum_by_value_{t}", *head, float(eigenvalues_value[0]), float(eigenvalues_value[1]),
+                    C.byref(begin), C.byref(end))
+        return w, z, (begin.value, end.value)
+    if eigenvalues_index is None:
+        check_stage(f"{stem}_{t}", *head)
+    else:
+        check_stage(f"{stem}_partial_spectrum_{t}", *head, *_index_range(eigenvalues_index, n))
+    return w, z
 
 
 def hermitian_eigensolver(grid: Grid, uplo: str, a: np.ndarray, nb: int, isrc: int = 0, jsrc: int = 0,
@@ -271,35 +240,16 @@ def hermitian_eigensolver(grid: Grid, uplo: str, a: np.ndarray, nb: int, isrc: i
     eigenvalues_index=(begin, end) returns.  An eigenvalue within rounding of vl or vu may fall on either side."""
     t = type_char(a.dtype)
     _one_selection(eigenvalues_index, eigenvalues_value)
-    if n is None:
-        if grid.nranks != 1:
-            raise ValueError("the global size n is required on a distributed grid")
-        n = a.shape[0]
+    n = global_size(grid, n, a)
     if z_jsrc is None:
         z_jsrc = jsrc
-    w = np.zeros(n, dtype=_real_dtype(a.dtype))
+    w = np.zeros(n, dtype=real_dtype(a.dtype))
     if z is None:
         z = np.zeros(z_shape if z_shape is not None else a.shape, dtype=a.dtype, order="F")
-    da = make_descriptor(n, nb, _ld_of(a), isrc, jsrc)
-    dz = make_descriptor(n, nb, _ld_of(z), isrc, z_jsrc)
-    name = f"dlaf_{_eig_name(t)}_eigensolver_{t}"
-    if eigenvalues_value is not None:
-        name = f"dlaf_{_eig_name(t)}_eigensolver_partial_spectrum_by_value_{t}"
-        begin, end = C.c_long(-1), C.c_long(-1)
-        r = getattr(lib(), name)(grid.context, uplo.encode()[0:1], _ptr(a), da, _ptr(w), _ptr(z), dz,
-                                 float(eigenvalues_value[0]), float(eigenvalues_value[1]), C.byref(begin), C.byref(end))
-        if r != 0:
-            raise RuntimeError(f"{name} returned {r}")
-        return w, z, (begin.value, end.value)
-    if eigenvalues_index is None:
-        r = getattr(lib(), name)(grid.context, uplo.encode()[0:1], _ptr(a), da, _ptr(w), _ptr(z), dz)
-    else:
-        name = f"dlaf_{_eig_name(t)}_eigensolver_partial_spectrum_{t}"
-        begin, end = _index_range(eigenvalues_index, n)
-        r = getattr(lib(), name)(grid.context, uplo.encode()[0:1], _ptr(a), da, _ptr(w), _ptr(z), dz, begin, end)
-    if r != 0:
-        raise RuntimeError(f"{name} returned {r}")
-    return w, z
+    da = make_descriptor(n, nb, ld_of(a), isrc, jsrc)
+    dz = make_descriptor(n, nb, ld_of(z), isrc, z_jsrc)
+    return _solve(f"dlaf_{_eig_name(t)}_eigensolver", t, grid, uplo, (ptr(a), da), n, w, z, dz, eigenvalues_index,
+                  eigenvalues_value)
 
 
 def hermitian_generalized_eigensolver(grid: Grid, uplo: str, a: np.ndarray, b: np.ndarray, nb: int, isrc: int = 0,
@@ -310,36 +260,15 @@ def hermitian_generalized_eigensolver(grid: Grid, uplo: str, a: np.ndarray, b: n
     eigenvalues_index, z, eigenvalues_value: as in hermitian_eigensolver."""
     t = type_char(a.dtype)
     _one_selection(eigenvalues_index, eigenvalues_value)
-    if n is None:
-        if grid.nranks != 1:
-            raise ValueError("the global size n is required on a distributed grid")
-        n = a.shape[0]
-    w = np.zeros(n, dtype=_real_dtype(a.dtype))
+    n = global_size(grid, n, a)
+    w = np.zeros(n, dtype=real_dtype(a.dtype))
     if z is None:
         z = np.zeros(a.shape, dtype=a.dtype, order="F")
-    da = make_descriptor(n, nb, _ld_of(a), isrc, jsrc)
-    db = make_descriptor(n, nb, _ld_of(b), isrc, jsrc)
-    dz = make_descriptor(n, nb, _ld_of(z), isrc, jsrc)
-    name = f"dlaf_{_eig_name(t)}_generalized_eigensolver{'_factorized' if factorized else ''}"
-    if eigenvalues_value is not None:
-        name += f"_partial_spectrum_by_value_{t}"
-        begin, end = C.c_long(-1), C.c_long(-1)
-        r = getattr(lib(), name)(grid.context, uplo.encode()[0:1], _ptr(a), da, _ptr(b), db, _ptr(w), _ptr(z), dz,
-                                 float(eigenvalues_value[0]), float(eigenvalues_value[1]), C.byref(begin), C.byref(end))
-        if r != 0:
-            raise RuntimeError(f"{name} returned {r}")
-        return w, z, (begin.value, end.value)
-    if eigenvalues_index is None:
-        name += f"_{t}"
-        r = getattr(lib(), name)(grid.context, uplo.encode()[0:1], _ptr(a), da, _ptr(b), db, _ptr(w), _ptr(z), dz)
-    else:
-        name += f"_partial_spectrum_{t}"
-        begin, end = _index_range(eigenvalues_index, n)
-        r = getattr(lib(), name)(grid.context, uplo.encode()[0:1], _ptr(a), da, _ptr(b), db, _ptr(w), _ptr(z), dz, begin,
-                                 end)
-    if r != 0:
-        raise RuntimeError(f"{name} returned {r}")
-    return w, z
+    da = make_descriptor(n, nb, ld_of(a), isrc, jsrc)
+    db = make_descriptor(n, nb, ld_of(b), isrc, jsrc)
+    dz = make_descriptor(n, nb, ld_of(z), isrc, jsrc)
+    return _solve(f"dlaf_{_eig_name(t)}_generalized_eigensolver{'_factorized' if factorized else ''}", t, grid, uplo,
+                  (ptr(a), da, ptr(b), db), n, w, z, dz, eigenvalues_index, eigenvalues_value)
 
 
 def eigensolver_profile():
@@ -356,11 +285,11 @@ def pxheevd_partial_spectrum(uplo: str, a: np.ndarray, desca, z: np.ndarray, des
     integers of the ScaLAPACK descriptors.  Returns (w, info); z is written in place."""
     t = type_char(a.dtype)
     name = f"dlaf_p{t}{'syevd' if t in 'sd' else 'heevd'}_partial_spectrum"
-    w = np.zeros(n, dtype=_real_dtype(a.dtype))
-    da = (C.c_int * 9)(*desca)
-    dz = (C.c_int * 9)(*descz)
+    w = np.zeros(n, dtype=real_dtype(a.dtype))
+    da = desc9(desca)
+    dz = desc9(descz)
     info = C.c_int(-1)
-    getattr(lib(), name)(uplo.encode()[0:1], n, _ptr(a), 1, 1, da, _ptr(w), _ptr(z), 1, 1, dz, il, iu, C.byref(info))
+    entry(name)(uplo.encode()[0:1], n, ptr(a), 1, 1, da, ptr(w), ptr(z), 1, 1, dz, il, iu, C.byref(info))
     return w, info.value
 
 
@@ -370,10 +299,10 @@ def pxheevd_eigenvalues(uplo: str, a: np.ndarray, desca, il: int, iu: int, n: in
     t = type_char(a.dtype)
     name = f"dlaf_p{t}{'syevd' if t in 'sd' else 'heevd'}_eigenvalues"
     if w is None:
-        w = np.zeros(n, dtype=_real_dtype(a.dtype))
-    da = (C.c_int * 9)(*desca)
+        w = np.zeros(n, dtype=real_dtype(a.dtype))
+    da = desc9(desca)
     info = C.c_int(-1)
-    getattr(lib(), name)(uplo.encode()[0:1], n, _ptr(a), 1, 1, da, _ptr(w), il, iu, C.byref(info))
+    entry(name)(uplo.encode()[0:1], n, ptr(a), 1, 1, da, ptr(w), il, iu, C.byref(info))
     return w, info.value
 
 
@@ -383,11 +312,11 @@ def pxheevd_partial_spectrum_by_value(uplo: str, a: np.ndarray, desca, z: np.nda
     written in place (m columns, from the column of the first eigenvalue above vl)."""
     t = type_char(a.dtype)
     name = f"dlaf_p{t}{'syevd' if t in 'sd' else 'heevd'}_partial_spectrum_by_value"
-    w = np.zeros(n, dtype=_real_dtype(a.dtype))
-    da = (C.c_int * 9)(*desca)
-    dz = (C.c_int * 9)(*descz)
+    w = np.zeros(n, dtype=real_dtype(a.dtype))
+    da = desc9(desca)
+    dz = desc9(descz)
     m, info = C.c_int(-1), C.c_int(-1)
-    getattr(lib(), name)(uplo.encode()[0:1], n, _ptr(a), 1, 1, da, _ptr(w), _ptr(z), 1, 1, dz, float(vl), float(vu),
+    entry(name)(uplo.encode()[0:1], n, ptr(a), 1, 1, da, ptr(w), ptr(z), 1, 1, dz, float(vl), float(vu),
                          C.byref(m), C.byref(info))
     return w, m.value, info.value
 
@@ -403,10 +332,10 @@ def pxhegvd_eigenvalues(uplo: str, a: np.ndarray, desca, b: np.ndarray, descb, i
     t = type_char(a.dtype)
     name = _gv_name(t) + "_eigenvalues" + ("_factorized" if factorized else "")
     if w is None:
-        w = np.zeros(n, dtype=_real_dtype(a.dtype))
+        w = np.zeros(n, dtype=real_dtype(a.dtype))
     info = C.c_int(-1)
-    getattr(lib(), name)(uplo.encode()[0:1], n, _ptr(a), 1, 1, (C.c_int * 9)(*desca), _ptr(b), 1, 1, (C.c_int * 9)(*descb),
-                         _ptr(w), il, iu, C.byref(info))
+    entry(name)(uplo.encode()[0:1], n, ptr(a), 1, 1, desc9(desca), ptr(b), 1, 1, desc9(descb),
+                         ptr(w), il, iu, C.byref(info))
     return w, info.value
 
 
@@ -416,10 +345,10 @@ def pxhegvd_partial_spectrum_by_value(uplo: str, a: np.ndarray, desca, b: np.nda
     Returns (w, m, info); z is written in place."""
     t = type_char(a.dtype)
     name = _gv_name(t) + ("_factorized" if factorized else "") + "_partial_spectrum_by_value"
-    w = np.zeros(n, dtype=_real_dtype(a.dtype))
+    w = np.zeros(n, dtype=real_dtype(a.dtype))
     m, info = C.c_int(-1), C.c_int(-1)
-    getattr(lib(), name)(uplo.encode()[0:1], n, _ptr(a), 1, 1, (C.c_int * 9)(*desca), _ptr(b), 1, 1, (C.c_int * 9)(*descb),
-                         _ptr(w), _ptr(z), 1, 1, (C.c_int * 9)(*descz), float(vl), float(vu), C.byref(m), C.byref(info))
+    entry(name)(uplo.encode()[0:1], n, ptr(a), 1, 1, desc9(desca), ptr(b), 1, 1, desc9(descb),
+                         ptr(w), ptr(z), 1, 1, desc9(descz), float(vl), float(vu), C.byref(m), C.byref(info))
     return w, m.value, info.value
 
 

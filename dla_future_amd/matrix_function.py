@@ -7,18 +7,22 @@ import ctypes as C
 
 import numpy as np
 
-from .capi import WEIGHTS_FN_D, WEIGHTS_FN_S, DLAFDescriptor, lib, type_char
-from .cholesky import DeviceMatrix, GeneralDeviceMatrix, Grid, _ld_of, _ptr, _real_dtype, make_descriptor
+from ._abi import (check, check_stage, descriptor, entry, global_size, global_sizes, ld_of, make_descriptor, ptr, real_dtype,
+                   scalar)
+from .capi import WEIGHTS_FN_D, WEIGHTS_FN_S, lib, type_char
+from .device_matrix import DeviceMatrix, GeneralDeviceMatrix
+from .grid import Grid
 
 
 def _weights_ptr(d, k, rdt):
-    """the k real weights as a contiguous array of the real type (None stays None: the entry judges it)"""
+    """the k real weights as a contiguous array of the real type (None stays None: the entry judges it); the pointer
+    keeps the array alive"""
     if d is None:
-        return None, None
+        return None
     d = np.ascontiguousarray(d, dtype=rdt).reshape(-1)
     if d.shape[0] != k:
         raise ValueError(f"d holds {d.shape[0]} weights, k is {k}")
-    return d, _ptr(d)
+    return ptr(d)
 
 
 def hermitian_weighted_rank_k_update(grid: Grid, uplo: str, trans: str, alpha, a: np.ndarray, d, beta, c: np.ndarray,
@@ -35,34 +39,22 @@ def hermitian_weighted_rank_k_update(grid: Grid, uplo: str, trans: str, alpha, a
     if a.dtype != c.dtype:
         raise ValueError("the operands must have the same element type")
     tn = trans.upper() == "N"
-    if n is None or k is None:
-        if grid.nranks != 1:
-            raise ValueError("the global sizes n, k are required on a distributed grid")
-        n = c.shape[0]
-        k = a.shape[1] if tn else a.shape[0]
-    rdt = _real_dtype(c.dtype)
-    da = DLAFDescriptor(n if tn else k, k if tn else n, nb, nb, a_src[0], a_src[1], 0, 0, _ld_of(a))
-    dc = DLAFDescriptor(n, n, nb, nb, c_src[0], c_src[1], 0, 0, _ld_of(c))
-    al, be = np.array([alpha], dtype=rdt), np.array([beta], dtype=rdt)
-    keep, dp = _weights_ptr(d, k, rdt)
-    name = f"dlaf_mi355x_hermitian_weighted_rank_k_update_{t}"
-    r = getattr(lib(), name)(grid.context, uplo.encode(), trans.encode(), _ptr(al), _ptr(a), da, dp, _ptr(be), _ptr(c), dc)
-    if r != 0:
-        raise ValueError(f"{name} failed with {r}")
+    n, k = global_sizes(grid, (n, k), lambda: (c.shape[0], a.shape[1] if tn else a.shape[0]), "the global sizes n, k are")
+    rdt = real_dtype(c.dtype)
+    da = descriptor(n if tn else k, k if tn else n, nb, a_src, ld_of(a))
+    dc = descriptor(n, n, nb, c_src, ld_of(c))
+    check(f"dlaf_mi355x_hermitian_weighted_rank_k_update_{t}", grid.context, uplo.encode(), trans.encode(), scalar(alpha, rdt),
+          ptr(a), da, _weights_ptr(d, k, rdt), scalar(beta, rdt), ptr(c), dc)
 
 
 def hermitian_weighted_rank_k_update_device(uplo: str, trans: str, alpha, a: GeneralDeviceMatrix, d, beta,
                                             c: DeviceMatrix) -> None:
     """hermitian_weighted_rank_k_update on resident operands: `c` a DeviceMatrix created with this uplo, `a` a general
     resident matrix as stored, `d` the k real weights on the host; only the uplo triangle of `c` is written."""
-    rdt = _real_dtype(a.dtype)
-    al, be = np.array([alpha], dtype=rdt), np.array([beta], dtype=rdt)
+    rdt = real_dtype(a.dtype)
     k = a.n if trans.upper() == "N" else a.m
-    keep, dp = _weights_ptr(d, k, rdt)
-    r = lib().dlaf_mi355x_hermitian_weighted_rank_k_update_device(uplo.encode(), trans.encode(), _ptr(al), a._h, dp,
-                                                                  _ptr(be), c._h)
-    if r != 0:
-        raise ValueError(f"dlaf_mi355x_hermitian_weighted_rank_k_update_device failed with {r}")
+    check("dlaf_mi355x_hermitian_weighted_rank_k_update_device", uplo.encode(), trans.encode(), scalar(alpha, rdt), a._h,
+          _weights_ptr(d, k, rdt), scalar(beta, rdt), c._h)
 
 
 def _weights_callback(fn, rdt):
@@ -103,19 +95,15 @@ def hermitian_function(grid: Grid, uplo: str, a: np.ndarray, nb: int, fn, isrc: 
     computed.  The eigenvectors never leave the GPU.  Returns (w, (begin, end)): all n eigenvalues and the selected range.
     Raises RuntimeError with the eigensolver's status when that is not 0 (`a` is unchanged then)."""
     t = type_char(a.dtype)
-    if n is None:
-        if grid.nranks != 1:
-            raise ValueError("the global size n is required on a distributed grid")
-        n = a.shape[0]
-    rdt = _real_dtype(a.dtype)
+    n = global_size(grid, n, a)
+    rdt = real_dtype(a.dtype)
     w = np.zeros(max(n, 1), dtype=rdt)
     idx, val = _selection(eigenvalues_index, eigenvalues_value, rdt)
     cb, failure = _weights_callback(fn, rdt)
     sel = np.zeros(2, dtype=np.int64)
-    da = make_descriptor(n, nb, _ld_of(a), isrc, jsrc)
+    da = make_descriptor(n, nb, ld_of(a), isrc, jsrc)
     name = f"dlaf_mi355x_hermitian_function_{t}"
-    r = getattr(lib(), name)(grid.context, uplo.encode()[0:1], _ptr(a), da, _ptr(w), cb, None,
-                             None if idx is None else _ptr(idx), None if val is None else _ptr(val), _ptr(sel))
+    r = entry(name)(grid.context, uplo.encode()[0:1], ptr(a), da, ptr(w), cb, None, ptr(idx), ptr(val), ptr(sel))
     if failure:
         raise failure[0]
     if r != 0:
@@ -126,14 +114,13 @@ def hermitian_function(grid: Grid, uplo: str, a: np.ndarray, nb: int, fn, isrc: 
 def hermitian_function_device(a: DeviceMatrix, fn, eigenvalues_index=None, eigenvalues_value=None):
     """hermitian_function on a resident matrix (created with uplo 'L'): A := f(A) in place, only the eigenvalues cross
     PCIe.  Returns (w, (begin, end))."""
-    rdt = _real_dtype(a.dtype)
+    rdt = real_dtype(a.dtype)
     w = np.zeros(max(a.n, 1), dtype=rdt)
     idx, val = _selection(eigenvalues_index, eigenvalues_value, rdt)
     cb, failure = _weights_callback(fn, rdt)
     sel = np.zeros(2, dtype=np.int64)
-    r = lib().dlaf_mi355x_hermitian_function_device(a._h, _ptr(w), C.cast(cb, C.c_void_p), None,
-                                                    None if idx is None else _ptr(idx),
-                                                    None if val is None else _ptr(val), _ptr(sel))
+    r = lib().dlaf_mi355x_hermitian_function_device(a._h, ptr(w), C.cast(cb, C.c_void_p), None, ptr(idx), ptr(val),
+                                                    ptr(sel))
     if failure:
         raise failure[0]
     if r != 0:
@@ -147,26 +134,18 @@ def hermitian_power(grid: Grid, uplo: str, a: np.ndarray, nb: int, exponent: flo
     pseudo-inverse for -1, Loewdin's S^(-1/2) for -0.5) == dlaf_mi355x_hermitian_power_{s,d,c,z}.  The dropped
     eigenvectors are not computed.  Returns (w, n_dropped)."""
     t = type_char(a.dtype)
-    if n is None:
-        if grid.nranks != 1:
-            raise ValueError("the global size n is required on a distributed grid")
-        n = a.shape[0]
-    w = np.zeros(max(n, 1), dtype=_real_dtype(a.dtype))
+    n = global_size(grid, n, a)
+    w = np.zeros(max(n, 1), dtype=real_dtype(a.dtype))
     dropped = C.c_long(0)
-    da = make_descriptor(n, nb, _ld_of(a), isrc, jsrc)
-    name = f"dlaf_mi355x_hermitian_power_{t}"
-    r = getattr(lib(), name)(grid.context, uplo.encode()[0:1], _ptr(a), da, _ptr(w), float(exponent), float(threshold),
-                             C.byref(dropped))
-    if r != 0:
-        raise RuntimeError(f"{name} returned {r}")
+    da = make_descriptor(n, nb, ld_of(a), isrc, jsrc)
+    check_stage(f"dlaf_mi355x_hermitian_power_{t}", grid.context, uplo.encode()[0:1], ptr(a), da, ptr(w), float(exponent),
+                float(threshold), C.byref(dropped))
     return w[:n], dropped.value
 
 
 def hermitian_power_device(a: DeviceMatrix, exponent: float, threshold: float = 0.0):
     """hermitian_power on a resident matrix (created with uplo 'L'), in place.  Returns (w, n_dropped)."""
-    w = np.zeros(max(a.n, 1), dtype=_real_dtype(a.dtype))
+    w = np.zeros(max(a.n, 1), dtype=real_dtype(a.dtype))
     dropped = C.c_long(0)
-    r = lib().dlaf_mi355x_hermitian_power_device(a._h, _ptr(w), float(exponent), float(threshold), C.byref(dropped))
-    if r != 0:
-        raise RuntimeError(f"dlaf_mi355x_hermitian_power_device returned {r}")
+    check_stage("dlaf_mi355x_hermitian_power_device", a._h, ptr(w), float(exponent), float(threshold), C.byref(dropped))
     return w[:a.n], dropped.value

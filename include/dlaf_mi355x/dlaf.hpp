@@ -276,6 +276,39 @@ private:
   dlaf_mi355x_matrix_t h_ = nullptr;
 };
 
+// ---- what every call into the C ABI below shares ----------------------------------------------------------------
+namespace internal {
+// a host matrix as the C entries take it, next to its pointer
+template <class T>
+DLAF_descriptor descriptor_of(const Matrix<T, Device::CPU>& m) {
+  const auto& d = m.distribution();
+  return DLAF_descriptor{(int) d.size().rows(), (int) d.size().cols(), (int) d.block_size().rows(),
+                         (int) d.block_size().cols(), (int) d.source_rank_index().row(),
+                         (int) d.source_rank_index().col(), 0, 0, (int) m.ld()};
+}
+// the C entry of a family for the element type T: one of its four functions, chosen when the template is instantiated.
+// In C++ dlaf_complex_c / dlaf_complex_z are std::complex<float> / <double>, so the complex entries take T* as it is.
+template <class T, auto S, auto D, auto C, auto Z>
+constexpr auto c_entry() {
+  if constexpr (std::is_same_v<T, float>)
+    return S;
+  else if constexpr (std::is_same_v<T, double>)
+    return D;
+  else if constexpr (std::is_same_v<T, std::complex<float>>)
+    return C;
+  else {
+    static_assert(std::is_same_v<T, std::complex<double>>, "element type must be float, double or their complex");
+    return Z;
+  }
+}
+}  // namespace internal
+// DLAF_MI355X_ENTRY(T, dlaf_mi355x_foo) is dlaf_mi355x_foo_{s,d,c,z}; DLAF_MI355X_EIGEN_ENTRY(T, foo) is
+// dlaf_symmetric_foo_{s,d} / dlaf_hermitian_foo_{c,z} (the dlaf_c names).  Both are #undef'd at the end of this header.
+#define DLAF_MI355X_ENTRY(T, family) (::dlaf::internal::c_entry<T, family##_s, family##_d, family##_c, family##_z>())
+#define DLAF_MI355X_EIGEN_ENTRY(T, family)                                                                 \
+  (::dlaf::internal::c_entry<T, dlaf_symmetric_##family##_s, dlaf_symmetric_##family##_d, dlaf_hermitian_##family##_c, \
+                             dlaf_hermitian_##family##_z>())
+
 namespace matrix {
 
 // matrix/matrix_mirror.h:137-173: copies the source to the target device on construction and back on
@@ -319,11 +352,7 @@ void set(Matrix<T, Device::CPU>& m, ElementGetter&& el) {
 // util_matrix.h:498-501
 template <class T>
 void set_random_hermitian_positive_definite(const comm::CommunicatorGrid& grid, Matrix<T, Device::CPU>& m) {
-  const auto& d = m.distribution();
-  DLAF_descriptor desc{(int) d.size().rows(), (int) d.size().cols(), (int) d.block_size().rows(),
-                       (int) d.block_size().cols(), (int) d.source_rank_index().row(),
-                       (int) d.source_rank_index().col(), 0, 0, (int) m.ld()};
-  if (dlaf_mi355x_set_random_hpd(grid.context(), internal::type_tag<T>(), m.ptr(), desc, 0) != 0)
+  if (dlaf_mi355x_set_random_hpd(grid.context(), internal::type_tag<T>(), m.ptr(), internal::descriptor_of(m), 0) != 0)
     internal::fail("square matrix with square blocks");
 }
 }  // namespace util
@@ -365,26 +394,10 @@ template <Backend B, Device D, class T>
 void triangular_solver(comm::CommunicatorGrid& grid, blas::Side side, blas::Uplo uplo, blas::Op op, blas::Diag diag,
                        T alpha, Matrix<T, Device::CPU>& mat_a, Matrix<T, Device::CPU>& mat_b) {
   static_assert(B == Backend::GPU, "this library has no CPU backend");
-  auto desc_of = [](const Matrix<T, Device::CPU>& m) {
-    const auto& d = m.distribution();
-    return DLAF_descriptor{(int) d.size().rows(), (int) d.size().cols(), (int) d.block_size().rows(),
-                           (int) d.block_size().cols(), (int) d.source_rank_index().row(),
-                           (int) d.source_rank_index().col(), 0, 0, (int) m.ld()};
-  };
-  int r;
-  if constexpr (std::is_same_v<T, float>)
-    r = dlaf_mi355x_triangular_solver_s(grid.context(), (char) side, (char) uplo, (char) op, (char) diag, &alpha,
-                                        mat_a.ptr(), desc_of(mat_a), mat_b.ptr(), desc_of(mat_b));
-  else if constexpr (std::is_same_v<T, double>)
-    r = dlaf_mi355x_triangular_solver_d(grid.context(), (char) side, (char) uplo, (char) op, (char) diag, &alpha,
-                                        mat_a.ptr(), desc_of(mat_a), mat_b.ptr(), desc_of(mat_b));
-  else if constexpr (std::is_same_v<T, std::complex<float>>)
-    r = dlaf_mi355x_triangular_solver_c(grid.context(), (char) side, (char) uplo, (char) op, (char) diag, &alpha,
-                                        mat_a.ptr(), desc_of(mat_a), mat_b.ptr(), desc_of(mat_b));
-  else
-    r = dlaf_mi355x_triangular_solver_z(grid.context(), (char) side, (char) uplo, (char) op, (char) diag, &alpha,
-                                        mat_a.ptr(), desc_of(mat_a), mat_b.ptr(), desc_of(mat_b));
-  if (r != 0)
+  using internal::descriptor_of;
+  if (DLAF_MI355X_ENTRY(T, dlaf_mi355x_triangular_solver)(grid.context(), (char) side, (char) uplo, (char) op, (char) diag,
+                                                          &alpha, mat_a.ptr(), descriptor_of(mat_a), mat_b.ptr(),
+                                                          descriptor_of(mat_b)) != 0)
     internal::fail("triangular_solver");
 }
 
@@ -402,26 +415,10 @@ template <Backend B, Device D, class T>
 void triangular_multiplication(comm::CommunicatorGrid& grid, blas::Side side, blas::Uplo uplo, blas::Op op,
                                blas::Diag diag, T alpha, Matrix<T, Device::CPU>& mat_a, Matrix<T, Device::CPU>& mat_b) {
   static_assert(B == Backend::GPU, "this library has no CPU backend");
-  auto desc_of = [](const Matrix<T, Device::CPU>& m) {
-    const auto& d = m.distribution();
-    return DLAF_descriptor{(int) d.size().rows(), (int) d.size().cols(), (int) d.block_size().rows(),
-                           (int) d.block_size().cols(), (int) d.source_rank_index().row(),
-                           (int) d.source_rank_index().col(), 0, 0, (int) m.ld()};
-  };
-  int r;
-  if constexpr (std::is_same_v<T, float>)
-    r = dlaf_mi355x_triangular_multiplication_s(grid.context(), (char) side, (char) uplo, (char) op, (char) diag, &alpha,
-                                                mat_a.ptr(), desc_of(mat_a), mat_b.ptr(), desc_of(mat_b));
-  else if constexpr (std::is_same_v<T, double>)
-    r = dlaf_mi355x_triangular_multiplication_d(grid.context(), (char) side, (char) uplo, (char) op, (char) diag, &alpha,
-                                                mat_a.ptr(), desc_of(mat_a), mat_b.ptr(), desc_of(mat_b));
-  else if constexpr (std::is_same_v<T, std::complex<float>>)
-    r = dlaf_mi355x_triangular_multiplication_c(grid.context(), (char) side, (char) uplo, (char) op, (char) diag, &alpha,
-                                                mat_a.ptr(), desc_of(mat_a), mat_b.ptr(), desc_of(mat_b));
-  else
-    r = dlaf_mi355x_triangular_multiplication_z(grid.context(), (char) side, (char) uplo, (char) op, (char) diag, &alpha,
-                                                mat_a.ptr(), desc_of(mat_a), mat_b.ptr(), desc_of(mat_b));
-  if (r != 0)
+  using internal::descriptor_of;
+  if (DLAF_MI355X_ENTRY(T, dlaf_mi355x_triangular_multiplication)(grid.context(), (char) side, (char) uplo, (char) op,
+                                                                  (char) diag, &alpha, mat_a.ptr(), descriptor_of(mat_a),
+                                                                  mat_b.ptr(), descriptor_of(mat_b)) != 0)
     internal::fail("triangular_multiplication");
 }
 
@@ -441,30 +438,10 @@ void hermitian_multiplication(comm::CommunicatorGrid& grid, blas::Side side, bla
                               const Matrix<T, Device::CPU>& mat_a, const Matrix<T, Device::CPU>& mat_b, const T beta,
                               Matrix<T, Device::CPU>& mat_c) {
   static_assert(B == Backend::GPU, "this library has no CPU backend");
-  auto desc_of = [](const auto& m) {
-    const auto& d = m.distribution();
-    return DLAF_descriptor{(int) d.size().rows(), (int) d.size().cols(), (int) d.block_size().rows(),
-                           (int) d.block_size().cols(), (int) d.source_rank_index().row(),
-                           (int) d.source_rank_index().col(), 0, 0, (int) m.ld()};
-  };
-  int r;
-  if constexpr (std::is_same_v<T, float>)
-    r = dlaf_mi355x_hermitian_multiplication_s(grid.context(), (char) side, (char) uplo, &alpha, mat_a.ptr(),
-                                               desc_of(mat_a), mat_b.ptr(), desc_of(mat_b), &beta, mat_c.ptr(),
-                                               desc_of(mat_c));
-  else if constexpr (std::is_same_v<T, double>)
-    r = dlaf_mi355x_hermitian_multiplication_d(grid.context(), (char) side, (char) uplo, &alpha, mat_a.ptr(),
-                                               desc_of(mat_a), mat_b.ptr(), desc_of(mat_b), &beta, mat_c.ptr(),
-                                               desc_of(mat_c));
-  else if constexpr (std::is_same_v<T, std::complex<float>>)
-    r = dlaf_mi355x_hermitian_multiplication_c(grid.context(), (char) side, (char) uplo, &alpha, mat_a.ptr(),
-                                               desc_of(mat_a), mat_b.ptr(), desc_of(mat_b), &beta, mat_c.ptr(),
-                                               desc_of(mat_c));
-  else
-    r = dlaf_mi355x_hermitian_multiplication_z(grid.context(), (char) side, (char) uplo, &alpha, mat_a.ptr(),
-                                               desc_of(mat_a), mat_b.ptr(), desc_of(mat_b), &beta, mat_c.ptr(),
-                                               desc_of(mat_c));
-  if (r != 0)
+  using internal::descriptor_of;
+  if (DLAF_MI355X_ENTRY(T, dlaf_mi355x_hermitian_multiplication)(grid.context(), (char) side, (char) uplo, &alpha, mat_a.ptr(),
+                                                                 descriptor_of(mat_a), mat_b.ptr(), descriptor_of(mat_b),
+                                                                 &beta, mat_c.ptr(), descriptor_of(mat_c)) != 0)
     internal::fail("hermitian_multiplication");
 }
 
@@ -485,26 +462,10 @@ void generalMatrix(comm::CommunicatorGrid& grid, blas::Op opA, blas::Op opB, con
                    const Matrix<T, Device::CPU>& mat_a, const Matrix<T, Device::CPU>& mat_b, const T beta,
                    Matrix<T, Device::CPU>& mat_c) {
   static_assert(B == Backend::GPU, "this library has no CPU backend");
-  auto desc_of = [](const auto& m) {
-    const auto& d = m.distribution();
-    return DLAF_descriptor{(int) d.size().rows(), (int) d.size().cols(), (int) d.block_size().rows(),
-                           (int) d.block_size().cols(), (int) d.source_rank_index().row(),
-                           (int) d.source_rank_index().col(), 0, 0, (int) m.ld()};
-  };
-  int r;
-  if constexpr (std::is_same_v<T, float>)
-    r = dlaf_mi355x_general_multiplication_s(grid.context(), (char) opA, (char) opB, &alpha, mat_a.ptr(), desc_of(mat_a),
-                                             mat_b.ptr(), desc_of(mat_b), &beta, mat_c.ptr(), desc_of(mat_c));
-  else if constexpr (std::is_same_v<T, double>)
-    r = dlaf_mi355x_general_multiplication_d(grid.context(), (char) opA, (char) opB, &alpha, mat_a.ptr(), desc_of(mat_a),
-                                             mat_b.ptr(), desc_of(mat_b), &beta, mat_c.ptr(), desc_of(mat_c));
-  else if constexpr (std::is_same_v<T, std::complex<float>>)
-    r = dlaf_mi355x_general_multiplication_c(grid.context(), (char) opA, (char) opB, &alpha, mat_a.ptr(), desc_of(mat_a),
-                                             mat_b.ptr(), desc_of(mat_b), &beta, mat_c.ptr(), desc_of(mat_c));
-  else
-    r = dlaf_mi355x_general_multiplication_z(grid.context(), (char) opA, (char) opB, &alpha, mat_a.ptr(), desc_of(mat_a),
-                                             mat_b.ptr(), desc_of(mat_b), &beta, mat_c.ptr(), desc_of(mat_c));
-  if (r != 0)
+  using dlaf::internal::descriptor_of;
+  if (DLAF_MI355X_ENTRY(T, dlaf_mi355x_general_multiplication)(grid.context(), (char) opA, (char) opB, &alpha, mat_a.ptr(),
+                                                               descriptor_of(mat_a), mat_b.ptr(), descriptor_of(mat_b), &beta,
+                                                               mat_c.ptr(), descriptor_of(mat_c)) != 0)
     dlaf::internal::fail("generalMatrix");
 }
 // the reference's two signatures: local matrices with ops, a grid without (NoTrans x NoTrans)
@@ -528,34 +489,14 @@ void generalMatrix(comm::CommunicatorGrid& grid, const T alpha, const Matrix<T, 
 //   rank-2k: C = alpha A B^H + conj(alpha) B A^H + beta C / alpha A^H B + conj(alpha) B^H A + beta C; beta real
 // Real types also take Trans (= ConjTrans); complex types refuse it.  Local matrices: both ops.  A grid of more than one
 // process: NoTrans only.  One square block for all operands; mat_b is stored, blocked and distributed like mat_a.
-namespace internal {
-template <class M>
-DLAF_descriptor rank_update_descriptor(const M& m) {
-  const auto& d = m.distribution();
-  return DLAF_descriptor{(int) d.size().rows(), (int) d.size().cols(), (int) d.block_size().rows(),
-                         (int) d.block_size().cols(), (int) d.source_rank_index().row(),
-                         (int) d.source_rank_index().col(), 0, 0, (int) m.ld()};
-}
-}  // namespace internal
 template <Backend B, Device D, class T>
 void hermitian_rank_k_update(comm::CommunicatorGrid& grid, blas::Uplo uplo, blas::Op op, const BaseType<T> alpha,
                              const Matrix<T, Device::CPU>& mat_a, const BaseType<T> beta, Matrix<T, Device::CPU>& mat_c) {
   static_assert(B == Backend::GPU, "this library has no CPU backend");
-  const DLAF_descriptor da = internal::rank_update_descriptor(mat_a), dc = internal::rank_update_descriptor(mat_c);
-  int r;
-  if constexpr (std::is_same_v<T, float>)
-    r = dlaf_mi355x_hermitian_rank_k_update_s(grid.context(), (char) uplo, (char) op, &alpha, mat_a.ptr(), da, &beta,
-                                              mat_c.ptr(), dc);
-  else if constexpr (std::is_same_v<T, double>)
-    r = dlaf_mi355x_hermitian_rank_k_update_d(grid.context(), (char) uplo, (char) op, &alpha, mat_a.ptr(), da, &beta,
-                                              mat_c.ptr(), dc);
-  else if constexpr (std::is_same_v<T, std::complex<float>>)
-    r = dlaf_mi355x_hermitian_rank_k_update_c(grid.context(), (char) uplo, (char) op, &alpha, mat_a.ptr(), da, &beta,
-                                              mat_c.ptr(), dc);
-  else
-    r = dlaf_mi355x_hermitian_rank_k_update_z(grid.context(), (char) uplo, (char) op, &alpha, mat_a.ptr(), da, &beta,
-                                              mat_c.ptr(), dc);
-  if (r != 0)
+  using internal::descriptor_of;
+  if (DLAF_MI355X_ENTRY(T, dlaf_mi355x_hermitian_rank_k_update)(grid.context(), (char) uplo, (char) op, &alpha, mat_a.ptr(),
+                                                                descriptor_of(mat_a), &beta, mat_c.ptr(),
+                                                                descriptor_of(mat_c)) != 0)
     internal::fail("hermitian_rank_k_update");
 }
 template <Backend B, Device D, class T>
@@ -563,22 +504,10 @@ void hermitian_rank_2k_update(comm::CommunicatorGrid& grid, blas::Uplo uplo, bla
                               const Matrix<T, Device::CPU>& mat_a, const Matrix<T, Device::CPU>& mat_b,
                               const BaseType<T> beta, Matrix<T, Device::CPU>& mat_c) {
   static_assert(B == Backend::GPU, "this library has no CPU backend");
-  const DLAF_descriptor da = internal::rank_update_descriptor(mat_a), db = internal::rank_update_descriptor(mat_b),
-                        dc = internal::rank_update_descriptor(mat_c);
-  int r;
-  if constexpr (std::is_same_v<T, float>)
-    r = dlaf_mi355x_hermitian_rank_2k_update_s(grid.context(), (char) uplo, (char) op, &alpha, mat_a.ptr(), da, mat_b.ptr(),
-                                               db, &beta, mat_c.ptr(), dc);
-  else if constexpr (std::is_same_v<T, double>)
-    r = dlaf_mi355x_hermitian_rank_2k_update_d(grid.context(), (char) uplo, (char) op, &alpha, mat_a.ptr(), da, mat_b.ptr(),
-                                               db, &beta, mat_c.ptr(), dc);
-  else if constexpr (std::is_same_v<T, std::complex<float>>)
-    r = dlaf_mi355x_hermitian_rank_2k_update_c(grid.context(), (char) uplo, (char) op, &alpha, mat_a.ptr(), da, mat_b.ptr(),
-                                               db, &beta, mat_c.ptr(), dc);
-  else
-    r = dlaf_mi355x_hermitian_rank_2k_update_z(grid.context(), (char) uplo, (char) op, &alpha, mat_a.ptr(), da, mat_b.ptr(),
-                                               db, &beta, mat_c.ptr(), dc);
-  if (r != 0)
+  using internal::descriptor_of;
+  if (DLAF_MI355X_ENTRY(T, dlaf_mi355x_hermitian_rank_2k_update)(grid.context(), (char) uplo, (char) op, &alpha, mat_a.ptr(),
+                                                                 descriptor_of(mat_a), mat_b.ptr(), descriptor_of(mat_b),
+                                                                 &beta, mat_c.ptr(), descriptor_of(mat_c)) != 0)
     internal::fail("hermitian_rank_2k_update");
 }
 // the local overloads
@@ -605,21 +534,10 @@ void hermitian_weighted_rank_k_update(comm::CommunicatorGrid& grid, blas::Uplo u
                                       const Matrix<T, Device::CPU>& mat_a, const BaseType<T>* d, const BaseType<T> beta,
                                       Matrix<T, Device::CPU>& mat_c) {
   static_assert(B == Backend::GPU, "this library has no CPU backend");
-  const DLAF_descriptor da = internal::rank_update_descriptor(mat_a), dc = internal::rank_update_descriptor(mat_c);
-  int r;
-  if constexpr (std::is_same_v<T, float>)
-    r = dlaf_mi355x_hermitian_weighted_rank_k_update_s(grid.context(), (char) uplo, (char) op, &alpha, mat_a.ptr(), da, d,
-                                                       &beta, mat_c.ptr(), dc);
-  else if constexpr (std::is_same_v<T, double>)
-    r = dlaf_mi355x_hermitian_weighted_rank_k_update_d(grid.context(), (char) uplo, (char) op, &alpha, mat_a.ptr(), da, d,
-                                                       &beta, mat_c.ptr(), dc);
-  else if constexpr (std::is_same_v<T, std::complex<float>>)
-    r = dlaf_mi355x_hermitian_weighted_rank_k_update_c(grid.context(), (char) uplo, (char) op, &alpha, mat_a.ptr(), da, d,
-                                                       &beta, mat_c.ptr(), dc);
-  else
-    r = dlaf_mi355x_hermitian_weighted_rank_k_update_z(grid.context(), (char) uplo, (char) op, &alpha, mat_a.ptr(), da, d,
-                                                       &beta, mat_c.ptr(), dc);
-  if (r != 0)
+  using internal::descriptor_of;
+  if (DLAF_MI355X_ENTRY(T, dlaf_mi355x_hermitian_weighted_rank_k_update)(grid.context(), (char) uplo, (char) op, &alpha,
+                                                                         mat_a.ptr(), descriptor_of(mat_a), d, &beta,
+                                                                         mat_c.ptr(), descriptor_of(mat_c)) != 0)
     internal::fail("hermitian_weighted_rank_k_update");
 }
 template <Backend B, Device D, class T>
@@ -655,7 +573,6 @@ int hermitian_function(comm::CommunicatorGrid& grid, blas::Uplo uplo, Matrix<T, 
                        SpectralSelection<BaseType<T>> selection = {}, SizeType* selected = nullptr) {
   static_assert(B == Backend::GPU, "this library has no CPU backend");
   using R = BaseType<T>;
-  const DLAF_descriptor da = internal::rank_update_descriptor(mat_a);
   void* user = const_cast<SpectralWeights<R>*>(&weights);
   long range[2] = {0, 0}, sel[2] = {0, 0};
   if (selection.index_range) {
@@ -663,19 +580,9 @@ int hermitian_function(comm::CommunicatorGrid& grid, blas::Uplo uplo, Matrix<T, 
     range[1] = (long) selection.index_range[1];
   }
   const long* ir = selection.index_range ? range : nullptr;
-  int r;
-  if constexpr (std::is_same_v<T, float>)
-    r = dlaf_mi355x_hermitian_function_s(grid.context(), (char) uplo, mat_a.ptr(), da, eigenvalues,
-                                         &internal::spectral_weights_trampoline<R>, user, ir, selection.value_interval, sel);
-  else if constexpr (std::is_same_v<T, double>)
-    r = dlaf_mi355x_hermitian_function_d(grid.context(), (char) uplo, mat_a.ptr(), da, eigenvalues,
-                                         &internal::spectral_weights_trampoline<R>, user, ir, selection.value_interval, sel);
-  else if constexpr (std::is_same_v<T, std::complex<float>>)
-    r = dlaf_mi355x_hermitian_function_c(grid.context(), (char) uplo, mat_a.ptr(), da, eigenvalues,
-                                         &internal::spectral_weights_trampoline<R>, user, ir, selection.value_interval, sel);
-  else
-    r = dlaf_mi355x_hermitian_function_z(grid.context(), (char) uplo, mat_a.ptr(), da, eigenvalues,
-                                         &internal::spectral_weights_trampoline<R>, user, ir, selection.value_interval, sel);
+  const int r = DLAF_MI355X_ENTRY(T, dlaf_mi355x_hermitian_function)(
+      grid.context(), (char) uplo, mat_a.ptr(), internal::descriptor_of(mat_a), eigenvalues,
+      &internal::spectral_weights_trampoline<R>, user, ir, selection.value_interval, sel);
   if (selected) {
     selected[0] = (SizeType) sel[0];
     selected[1] = (SizeType) sel[1];
@@ -686,17 +593,10 @@ template <Backend B, Device D, class T>
 int hermitian_power(comm::CommunicatorGrid& grid, blas::Uplo uplo, Matrix<T, Device::CPU>& mat_a, BaseType<T>* eigenvalues,
                     double exponent, double threshold = 0.0, SizeType* n_dropped = nullptr) {
   static_assert(B == Backend::GPU, "this library has no CPU backend");
-  const DLAF_descriptor da = internal::rank_update_descriptor(mat_a);
   long dropped = 0;
-  int r;
-  if constexpr (std::is_same_v<T, float>)
-    r = dlaf_mi355x_hermitian_power_s(grid.context(), (char) uplo, mat_a.ptr(), da, eigenvalues, exponent, threshold, &dropped);
-  else if constexpr (std::is_same_v<T, double>)
-    r = dlaf_mi355x_hermitian_power_d(grid.context(), (char) uplo, mat_a.ptr(), da, eigenvalues, exponent, threshold, &dropped);
-  else if constexpr (std::is_same_v<T, std::complex<float>>)
-    r = dlaf_mi355x_hermitian_power_c(grid.context(), (char) uplo, mat_a.ptr(), da, eigenvalues, exponent, threshold, &dropped);
-  else
-    r = dlaf_mi355x_hermitian_power_z(grid.context(), (char) uplo, mat_a.ptr(), da, eigenvalues, exponent, threshold, &dropped);
+  const int r = DLAF_MI355X_ENTRY(T, dlaf_mi355x_hermitian_power)(grid.context(), (char) uplo, mat_a.ptr(),
+                                                                  internal::descriptor_of(mat_a), eigenvalues, exponent,
+                                                                  threshold, &dropped);
   if (n_dropped)
     *n_dropped = (SizeType) dropped;
   return r;
@@ -714,35 +614,17 @@ template <Backend B, Device D, class T>
 void general_addition(comm::CommunicatorGrid& grid, blas::Uplo uplo, blas::Op op, const T alpha,
                       const Matrix<T, Device::CPU>& mat_a, const T beta, Matrix<T, Device::CPU>& mat_c) {
   static_assert(B == Backend::GPU, "this library has no CPU backend");
-  const DLAF_descriptor da = internal::rank_update_descriptor(mat_a), dc = internal::rank_update_descriptor(mat_c);
   const char u = uplo == blas::Uplo::Lower ? 'L' : uplo == blas::Uplo::Upper ? 'U' : 'A';
-  int r;
-  if constexpr (std::is_same_v<T, float>)
-    r = dlaf_mi355x_general_addition_s(grid.context(), u, (char) op, &alpha, mat_a.ptr(), da, &beta, mat_c.ptr(), dc);
-  else if constexpr (std::is_same_v<T, double>)
-    r = dlaf_mi355x_general_addition_d(grid.context(), u, (char) op, &alpha, mat_a.ptr(), da, &beta, mat_c.ptr(), dc);
-  else if constexpr (std::is_same_v<T, std::complex<float>>)
-    r = dlaf_mi355x_general_addition_c(grid.context(), u, (char) op, &alpha, mat_a.ptr(), da, &beta, mat_c.ptr(), dc);
-  else
-    r = dlaf_mi355x_general_addition_z(grid.context(), u, (char) op, &alpha, mat_a.ptr(), da, &beta, mat_c.ptr(), dc);
-  if (r != 0)
+  if (DLAF_MI355X_ENTRY(T, dlaf_mi355x_general_addition)(grid.context(), u, (char) op, &alpha, mat_a.ptr(),
+                                                         internal::descriptor_of(mat_a), &beta, mat_c.ptr(),
+                                                         internal::descriptor_of(mat_c)) != 0)
     internal::fail("general_addition");
 }
 template <Backend B, Device D, class T>
 void hermitian_complete(comm::CommunicatorGrid& grid, blas::Uplo uplo, bool conjugate, Matrix<T, Device::CPU>& mat_a) {
   static_assert(B == Backend::GPU, "this library has no CPU backend");
-  const DLAF_descriptor da = internal::rank_update_descriptor(mat_a);
-  const char kind = conjugate ? 'H' : 'S';
-  int r;
-  if constexpr (std::is_same_v<T, float>)
-    r = dlaf_mi355x_hermitian_complete_s(grid.context(), (char) uplo, kind, mat_a.ptr(), da);
-  else if constexpr (std::is_same_v<T, double>)
-    r = dlaf_mi355x_hermitian_complete_d(grid.context(), (char) uplo, kind, mat_a.ptr(), da);
-  else if constexpr (std::is_same_v<T, std::complex<float>>)
-    r = dlaf_mi355x_hermitian_complete_c(grid.context(), (char) uplo, kind, mat_a.ptr(), da);
-  else
-    r = dlaf_mi355x_hermitian_complete_z(grid.context(), (char) uplo, kind, mat_a.ptr(), da);
-  if (r != 0)
+  if (DLAF_MI355X_ENTRY(T, dlaf_mi355x_hermitian_complete)(grid.context(), (char) uplo, conjugate ? 'H' : 'S', mat_a.ptr(),
+                                                           internal::descriptor_of(mat_a)) != 0)
     internal::fail("hermitian_complete");
 }
 // the local overloads
@@ -765,26 +647,9 @@ template <Backend B, class T>
 void generalized_to_standard(comm::CommunicatorGrid& grid, blas::Uplo uplo, Matrix<T, Device::CPU>& mat_a,
                              Matrix<T, Device::CPU>& mat_b) {
   static_assert(B == Backend::GPU, "this library has no CPU backend");
-  auto desc_of = [](const Matrix<T, Device::CPU>& m) {
-    const auto& d = m.distribution();
-    return DLAF_descriptor{(int) d.size().rows(), (int) d.size().cols(), (int) d.block_size().rows(),
-                           (int) d.block_size().cols(), (int) d.source_rank_index().row(),
-                           (int) d.source_rank_index().col(), 0, 0, (int) m.ld()};
-  };
-  int r;
-  if constexpr (std::is_same_v<T, float>)
-    r = dlaf_mi355x_generalized_to_standard_s(grid.context(), (char) uplo, mat_a.ptr(), desc_of(mat_a), mat_b.ptr(),
-                                              desc_of(mat_b));
-  else if constexpr (std::is_same_v<T, double>)
-    r = dlaf_mi355x_generalized_to_standard_d(grid.context(), (char) uplo, mat_a.ptr(), desc_of(mat_a), mat_b.ptr(),
-                                              desc_of(mat_b));
-  else if constexpr (std::is_same_v<T, std::complex<float>>)
-    r = dlaf_mi355x_generalized_to_standard_c(grid.context(), (char) uplo, mat_a.ptr(), desc_of(mat_a), mat_b.ptr(),
-                                              desc_of(mat_b));
-  else
-    r = dlaf_mi355x_generalized_to_standard_z(grid.context(), (char) uplo, mat_a.ptr(), desc_of(mat_a), mat_b.ptr(),
-                                              desc_of(mat_b));
-  if (r != 0)
+  using dlaf::internal::descriptor_of;
+  if (DLAF_MI355X_ENTRY(T, dlaf_mi355x_generalized_to_standard)(grid.context(), (char) uplo, mat_a.ptr(), descriptor_of(mat_a),
+                                                                mat_b.ptr(), descriptor_of(mat_b)) != 0)
     dlaf::internal::fail("generalized_to_standard");
 }
 // device-resident operands (the reference's miniapp times exactly this: both mirrors on the device,
@@ -813,22 +678,9 @@ void generalized_to_standard(blas::Uplo uplo, Matrix<T, Device::CPU>& mat_a, Mat
 namespace internal {
 template <class T>
 int inverse_host(int ctx, blas::Uplo uplo, blas::Diag diag, bool product, Matrix<T, Device::CPU>& m) {
-  const auto& d = m.distribution();
-  const DLAF_descriptor desc{(int) d.size().rows(), (int) d.size().cols(), (int) d.block_size().rows(),
-                             (int) d.block_size().cols(), (int) d.source_rank_index().row(),
-                             (int) d.source_rank_index().col(), 0, 0, (int) m.ld()};
-  if constexpr (std::is_same_v<T, float>)
-    return product ? dlaf_mi355x_inverse_from_cholesky_factor_s(ctx, (char) uplo, m.ptr(), desc)
-                   : dlaf_mi355x_triangular_inverse_s(ctx, (char) uplo, (char) diag, m.ptr(), desc);
-  else if constexpr (std::is_same_v<T, double>)
-    return product ? dlaf_mi355x_inverse_from_cholesky_factor_d(ctx, (char) uplo, m.ptr(), desc)
-                   : dlaf_mi355x_triangular_inverse_d(ctx, (char) uplo, (char) diag, m.ptr(), desc);
-  else if constexpr (std::is_same_v<T, std::complex<float>>)
-    return product ? dlaf_mi355x_inverse_from_cholesky_factor_c(ctx, (char) uplo, m.ptr(), desc)
-                   : dlaf_mi355x_triangular_inverse_c(ctx, (char) uplo, (char) diag, m.ptr(), desc);
-  else
-    return product ? dlaf_mi355x_inverse_from_cholesky_factor_z(ctx, (char) uplo, m.ptr(), desc)
-                   : dlaf_mi355x_triangular_inverse_z(ctx, (char) uplo, (char) diag, m.ptr(), desc);
+  const DLAF_descriptor desc = descriptor_of(m);
+  return product ? DLAF_MI355X_ENTRY(T, dlaf_mi355x_inverse_from_cholesky_factor)(ctx, (char) uplo, m.ptr(), desc)
+                 : DLAF_MI355X_ENTRY(T, dlaf_mi355x_triangular_inverse)(ctx, (char) uplo, (char) diag, m.ptr(), desc);
 }
 }  // namespace internal
 template <Backend B, class T>
@@ -878,29 +730,12 @@ namespace internal {
 template <class T>
 BaseType<T> norm_host(int ctx, lapack::Norm norm, char structure, blas::Uplo uplo, blas::Diag diag,
                       Matrix<T, Device::CPU>& m) {
-  const auto& d = m.distribution();
-  const DLAF_descriptor desc{(int) d.size().rows(), (int) d.size().cols(), (int) d.block_size().rows(),
-                             (int) d.block_size().cols(), (int) d.source_rank_index().row(),
-                             (int) d.source_rank_index().col(), 0, 0, (int) m.ld()};
+  const DLAF_descriptor desc = dlaf::internal::descriptor_of(m);
   double v = 0;
-  int r;
   const char nc = (char) norm, uc = (char) uplo, dc = (char) diag;
-  if constexpr (std::is_same_v<T, float>)
-    r = structure == 'G'   ? dlaf_mi355x_general_norm_s(ctx, nc, m.ptr(), desc, &v)
-        : structure == 'H' ? dlaf_mi355x_hermitian_norm_s(ctx, nc, uc, m.ptr(), desc, &v)
-                           : dlaf_mi355x_triangular_norm_s(ctx, nc, uc, dc, m.ptr(), desc, &v);
-  else if constexpr (std::is_same_v<T, double>)
-    r = structure == 'G'   ? dlaf_mi355x_general_norm_d(ctx, nc, m.ptr(), desc, &v)
-        : structure == 'H' ? dlaf_mi355x_hermitian_norm_d(ctx, nc, uc, m.ptr(), desc, &v)
-                           : dlaf_mi355x_triangular_norm_d(ctx, nc, uc, dc, m.ptr(), desc, &v);
-  else if constexpr (std::is_same_v<T, std::complex<float>>)
-    r = structure == 'G'   ? dlaf_mi355x_general_norm_c(ctx, nc, m.ptr(), desc, &v)
-        : structure == 'H' ? dlaf_mi355x_hermitian_norm_c(ctx, nc, uc, m.ptr(), desc, &v)
-                           : dlaf_mi355x_triangular_norm_c(ctx, nc, uc, dc, m.ptr(), desc, &v);
-  else
-    r = structure == 'G'   ? dlaf_mi355x_general_norm_z(ctx, nc, m.ptr(), desc, &v)
-        : structure == 'H' ? dlaf_mi355x_hermitian_norm_z(ctx, nc, uc, m.ptr(), desc, &v)
-                           : dlaf_mi355x_triangular_norm_z(ctx, nc, uc, dc, m.ptr(), desc, &v);
+  const int r = structure == 'G'   ? DLAF_MI355X_ENTRY(T, dlaf_mi355x_general_norm)(ctx, nc, m.ptr(), desc, &v)
+                : structure == 'H' ? DLAF_MI355X_ENTRY(T, dlaf_mi355x_hermitian_norm)(ctx, nc, uc, m.ptr(), desc, &v)
+                                   : DLAF_MI355X_ENTRY(T, dlaf_mi355x_triangular_norm)(ctx, nc, uc, dc, m.ptr(), desc, &v);
   if (r != 0)
     dlaf::internal::fail("norm: bad argument");
   return (BaseType<T>) v;
@@ -1002,25 +837,11 @@ std::vector<T> reduction_to_band(comm::CommunicatorGrid& grid, Matrix<T, Device:
 template <Backend B, class T>
 std::vector<T> reduction_to_band(comm::CommunicatorGrid& grid, Matrix<T, Device::CPU>& mat_a, SizeType band_size) {
   static_assert(B == Backend::GPU, "this library has no CPU backend");
-  const auto& d = mat_a.distribution();
-  const DLAF_descriptor desc{(int) d.size().rows(), (int) d.size().cols(), (int) d.block_size().rows(),
-                             (int) d.block_size().cols(), (int) d.source_rank_index().row(),
-                             (int) d.source_rank_index().col(), 0, 0, (int) mat_a.ld()};
-  std::vector<T> taus((size_t) std::max<SizeType>(0, d.size().rows() - band_size - 1));
+  std::vector<T> taus((size_t) std::max<SizeType>(0, mat_a.size().rows() - band_size - 1));
   T dummy{};
   T* tp = taus.empty() ? &dummy : taus.data();
-  int r;
-  if constexpr (std::is_same_v<T, float>)
-    r = dlaf_mi355x_reduction_to_band_s(grid.context(), mat_a.ptr(), desc, (int) band_size, tp);
-  else if constexpr (std::is_same_v<T, double>)
-    r = dlaf_mi355x_reduction_to_band_d(grid.context(), mat_a.ptr(), desc, (int) band_size, tp);
-  else if constexpr (std::is_same_v<T, std::complex<float>>)
-    r = dlaf_mi355x_reduction_to_band_c(grid.context(), reinterpret_cast<dlaf_complex_c*>(mat_a.ptr()), desc,
-                                        (int) band_size, reinterpret_cast<dlaf_complex_c*>(tp));
-  else
-    r = dlaf_mi355x_reduction_to_band_z(grid.context(), reinterpret_cast<dlaf_complex_z*>(mat_a.ptr()), desc,
-                                        (int) band_size, reinterpret_cast<dlaf_complex_z*>(tp));
-  if (r != 0)
+  if (DLAF_MI355X_ENTRY(T, dlaf_mi355x_reduction_to_band)(grid.context(), mat_a.ptr(), dlaf::internal::descriptor_of(mat_a),
+                                                          (int) band_size, tp) != 0)
     dlaf::internal::fail("reduction_to_band");
   return taus;
 }
@@ -1034,30 +855,12 @@ template <Backend B, class T>
 void bt_reduction_to_band(comm::CommunicatorGrid& grid, SizeType band_size, Matrix<T, Device::CPU>& mat_c,
                           Matrix<T, Device::CPU>& mat_v, const std::vector<T>& taus) {
   static_assert(B == Backend::GPU, "this library has no CPU backend");
-  auto desc_of = [](const Matrix<T, Device::CPU>& m) {
-    const auto& d = m.distribution();
-    return DLAF_descriptor{(int) d.size().rows(), (int) d.size().cols(), (int) d.block_size().rows(),
-                           (int) d.block_size().cols(), (int) d.source_rank_index().row(),
-                           (int) d.source_rank_index().col(), 0, 0, (int) m.ld()};
-  };
+  using dlaf::internal::descriptor_of;
   T dummy{};
   const T* tp = taus.empty() ? &dummy : taus.data();
-  int r;
-  if constexpr (std::is_same_v<T, float>)
-    r = dlaf_mi355x_bt_reduction_to_band_s(grid.context(), (int) band_size, mat_c.ptr(), desc_of(mat_c), mat_v.ptr(),
-                                           desc_of(mat_v), tp);
-  else if constexpr (std::is_same_v<T, double>)
-    r = dlaf_mi355x_bt_reduction_to_band_d(grid.context(), (int) band_size, mat_c.ptr(), desc_of(mat_c), mat_v.ptr(),
-                                           desc_of(mat_v), tp);
-  else if constexpr (std::is_same_v<T, std::complex<float>>)
-    r = dlaf_mi355x_bt_reduction_to_band_c(grid.context(), (int) band_size, reinterpret_cast<dlaf_complex_c*>(mat_c.ptr()),
-                                           desc_of(mat_c), reinterpret_cast<const dlaf_complex_c*>(mat_v.ptr()),
-                                           desc_of(mat_v), reinterpret_cast<const dlaf_complex_c*>(tp));
-  else
-    r = dlaf_mi355x_bt_reduction_to_band_z(grid.context(), (int) band_size, reinterpret_cast<dlaf_complex_z*>(mat_c.ptr()),
-                                           desc_of(mat_c), reinterpret_cast<const dlaf_complex_z*>(mat_v.ptr()),
-                                           desc_of(mat_v), reinterpret_cast<const dlaf_complex_z*>(tp));
-  if (r != 0)
+  if (DLAF_MI355X_ENTRY(T, dlaf_mi355x_bt_reduction_to_band)(grid.context(), (int) band_size, mat_c.ptr(),
+                                                             descriptor_of(mat_c), mat_v.ptr(), descriptor_of(mat_v),
+                                                             tp) != 0)
     dlaf::internal::fail("bt_reduction_to_band");
 }
 }  // namespace eigensolver::internal
@@ -1065,63 +868,42 @@ void bt_reduction_to_band(comm::CommunicatorGrid& grid, SizeType band_size, Matr
 // include/dlaf/eigensolver/eigensolver.h:56-190 and gen_eigensolver.h: host-resident matrices, as
 // the reference's C entries take them.  eigenvalues: all n on every process (the reference returns a local N x 1 Matrix).
 namespace internal {
-template <class T>
-DLAF_descriptor descriptor_of(const Matrix<T, Device::CPU>& m) {
-  const auto& d = m.distribution();
-  return DLAF_descriptor{(int) d.size().rows(), (int) d.size().cols(), (int) d.block_size().rows(),
-                         (int) d.block_size().cols(), (int) d.source_rank_index().row(),
-                         (int) d.source_rank_index().col(), 0, 0, (int) m.ld()};
+// What every overload below does around its C call: `eigenvalues` gets its n entries (always_assign: zero-filled on every
+// call, as the eigensolvers do; otherwise only when the size differs, as the eigenvalues-only calls do), then
+// call(uplo, w) runs with the uplo character ('U' for anything but Lower) and the eigenvalue pointer (never null, n = 0
+// included); a non-zero status fails as `what`.
+template <class R, class Call>
+void eigen_call(const char* what, blas::Uplo uplo, SizeType n, std::vector<R>& eigenvalues, bool always_assign,
+                Call&& call) {
+  if (always_assign || (SizeType) eigenvalues.size() != n)
+    eigenvalues.assign((size_t) n, R(0));
+  R dummy{};
+  if (call(uplo == blas::Uplo::Lower ? 'L' : 'U', eigenvalues.empty() ? &dummy : eigenvalues.data()) != 0)
+    fail(what);
 }
 }  // namespace internal
 template <Backend B, class T>
 void hermitian_eigensolver(comm::CommunicatorGrid& grid, blas::Uplo uplo, Matrix<T, Device::CPU>& mat,
                            std::vector<BaseType<T>>& eigenvalues, Matrix<T, Device::CPU>& eigenvectors) {
   static_assert(B == Backend::GPU, "this library has no CPU backend");
-  const char u = uplo == blas::Uplo::Lower ? 'L' : 'U';
-  eigenvalues.assign((size_t) mat.size().rows(), BaseType<T>(0));
-  BaseType<T> dummy{};
-  BaseType<T>* w = eigenvalues.empty() ? &dummy : eigenvalues.data();
-  const DLAF_descriptor da = internal::descriptor_of(mat), dz = internal::descriptor_of(eigenvectors);
-  int r;
-  if constexpr (std::is_same_v<T, float>)
-    r = dlaf_symmetric_eigensolver_s(grid.context(), u, mat.ptr(), da, w, eigenvectors.ptr(), dz);
-  else if constexpr (std::is_same_v<T, double>)
-    r = dlaf_symmetric_eigensolver_d(grid.context(), u, mat.ptr(), da, w, eigenvectors.ptr(), dz);
-  else if constexpr (std::is_same_v<T, std::complex<float>>)
-    r = dlaf_hermitian_eigensolver_c(grid.context(), u, reinterpret_cast<dlaf_complex_c*>(mat.ptr()), da, w,
-                                     reinterpret_cast<dlaf_complex_c*>(eigenvectors.ptr()), dz);
-  else
-    r = dlaf_hermitian_eigensolver_z(grid.context(), u, reinterpret_cast<dlaf_complex_z*>(mat.ptr()), da, w,
-                                     reinterpret_cast<dlaf_complex_z*>(eigenvectors.ptr()), dz);
-  if (r != 0)
-    dlaf::internal::fail("hermitian_eigensolver");
+  using internal::descriptor_of;
+  internal::eigen_call("hermitian_eigensolver", uplo, mat.size().rows(), eigenvalues, true, [&](char u, BaseType<T>* w) {
+    return DLAF_MI355X_EIGEN_ENTRY(T, eigensolver)(grid.context(), u, mat.ptr(), descriptor_of(mat), w, eigenvectors.ptr(),
+                                                   descriptor_of(eigenvectors));
+  });
 }
 template <Backend B, class T>
 void hermitian_generalized_eigensolver(comm::CommunicatorGrid& grid, blas::Uplo uplo, Matrix<T, Device::CPU>& mat_a,
                                        Matrix<T, Device::CPU>& mat_b, std::vector<BaseType<T>>& eigenvalues,
                                        Matrix<T, Device::CPU>& eigenvectors) {
   static_assert(B == Backend::GPU, "this library has no CPU backend");
-  const char u = uplo == blas::Uplo::Lower ? 'L' : 'U';
-  eigenvalues.assign((size_t) mat_a.size().rows(), BaseType<T>(0));
-  BaseType<T> dummy{};
-  BaseType<T>* w = eigenvalues.empty() ? &dummy : eigenvalues.data();
-  const DLAF_descriptor da = internal::descriptor_of(mat_a), db = internal::descriptor_of(mat_b),
-                        dz = internal::descriptor_of(eigenvectors);
-  int r;
-  if constexpr (std::is_same_v<T, float>)
-    r = dlaf_symmetric_generalized_eigensolver_s(grid.context(), u, mat_a.ptr(), da, mat_b.ptr(), db, w, eigenvectors.ptr(), dz);
-  else if constexpr (std::is_same_v<T, double>)
-    r = dlaf_symmetric_generalized_eigensolver_d(grid.context(), u, mat_a.ptr(), da, mat_b.ptr(), db, w, eigenvectors.ptr(), dz);
-  else if constexpr (std::is_same_v<T, std::complex<float>>)
-    r = dlaf_hermitian_generalized_eigensolver_c(grid.context(), u, reinterpret_cast<dlaf_complex_c*>(mat_a.ptr()), da,
-                                                 reinterpret_cast<dlaf_complex_c*>(mat_b.ptr()), db, w,
-                                                 reinterpret_cast<dlaf_complex_c*>(eigenvectors.ptr()), dz);
-  else
-    r = dlaf_hermitian_generalized_eigensolver_z(grid.context(), u, reinterpret_cast<dlaf_complex_z*>(mat_a.ptr()), da,
-                                                 reinterpret_cast<dlaf_complex_z*>(mat_b.ptr()), db, w,
-                                                 reinterpret_cast<dlaf_complex_z*>(eigenvectors.ptr()), dz);
-  if (r != 0)
-    dlaf::internal::fail("hermitian_generalized_eigensolver");
+  using internal::descriptor_of;
+  internal::eigen_call("hermitian_generalized_eigensolver", uplo, mat_a.size().rows(), eigenvalues, true,
+                       [&](char u, BaseType<T>* w) {
+                         return DLAF_MI355X_EIGEN_ENTRY(T, generalized_eigensolver)(
+                             grid.context(), u, mat_a.ptr(), descriptor_of(mat_a), mat_b.ptr(), descriptor_of(mat_b), w,
+                             eigenvectors.ptr(), descriptor_of(eigenvectors));
+                       });
 }
 
 // the eigenvectors of the eigenvalues [eigenvalues_index_begin, eigenvalues_index_end) only (0-based, half-open; the
@@ -1132,25 +914,12 @@ void hermitian_eigensolver(comm::CommunicatorGrid& grid, blas::Uplo uplo, Matrix
                            std::vector<BaseType<T>>& eigenvalues, Matrix<T, Device::CPU>& eigenvectors,
                            SizeType eigenvalues_index_begin, SizeType eigenvalues_index_end) {
   static_assert(B == Backend::GPU, "this library has no CPU backend");
-  const char u = uplo == blas::Uplo::Lower ? 'L' : 'U';
-  eigenvalues.assign((size_t) mat.size().rows(), BaseType<T>(0));
-  BaseType<T> dummy{};
-  BaseType<T>* w = eigenvalues.empty() ? &dummy : eigenvalues.data();
-  const DLAF_descriptor da = internal::descriptor_of(mat), dz = internal::descriptor_of(eigenvectors);
+  using internal::descriptor_of;
   const int64_t ib = eigenvalues_index_begin, ie = eigenvalues_index_end;
-  int r;
-  if constexpr (std::is_same_v<T, float>)
-    r = dlaf_symmetric_eigensolver_partial_spectrum_s(grid.context(), u, mat.ptr(), da, w, eigenvectors.ptr(), dz, ib, ie);
-  else if constexpr (std::is_same_v<T, double>)
-    r = dlaf_symmetric_eigensolver_partial_spectrum_d(grid.context(), u, mat.ptr(), da, w, eigenvectors.ptr(), dz, ib, ie);
-  else if constexpr (std::is_same_v<T, std::complex<float>>)
-    r = dlaf_hermitian_eigensolver_partial_spectrum_c(grid.context(), u, reinterpret_cast<dlaf_complex_c*>(mat.ptr()), da,
-                                                      w, reinterpret_cast<dlaf_complex_c*>(eigenvectors.ptr()), dz, ib, ie);
-  else
-    r = dlaf_hermitian_eigensolver_partial_spectrum_z(grid.context(), u, reinterpret_cast<dlaf_complex_z*>(mat.ptr()), da,
-                                                      w, reinterpret_cast<dlaf_complex_z*>(eigenvectors.ptr()), dz, ib, ie);
-  if (r != 0)
-    dlaf::internal::fail("hermitian_eigensolver");
+  internal::eigen_call("hermitian_eigensolver", uplo, mat.size().rows(), eigenvalues, true, [&](char u, BaseType<T>* w) {
+    return DLAF_MI355X_EIGEN_ENTRY(T, eigensolver_partial_spectrum)(grid.context(), u, mat.ptr(), descriptor_of(mat), w,
+                                                                    eigenvectors.ptr(), descriptor_of(eigenvectors), ib, ie);
+  });
 }
 template <Backend B, class T>
 void hermitian_generalized_eigensolver(comm::CommunicatorGrid& grid, blas::Uplo uplo, Matrix<T, Device::CPU>& mat_a,
@@ -1158,30 +927,14 @@ void hermitian_generalized_eigensolver(comm::CommunicatorGrid& grid, blas::Uplo 
                                        Matrix<T, Device::CPU>& eigenvectors, SizeType eigenvalues_index_begin,
                                        SizeType eigenvalues_index_end) {
   static_assert(B == Backend::GPU, "this library has no CPU backend");
-  const char u = uplo == blas::Uplo::Lower ? 'L' : 'U';
-  eigenvalues.assign((size_t) mat_a.size().rows(), BaseType<T>(0));
-  BaseType<T> dummy{};
-  BaseType<T>* w = eigenvalues.empty() ? &dummy : eigenvalues.data();
-  const DLAF_descriptor da = internal::descriptor_of(mat_a), db = internal::descriptor_of(mat_b),
-                        dz = internal::descriptor_of(eigenvectors);
+  using internal::descriptor_of;
   const int64_t ib = eigenvalues_index_begin, ie = eigenvalues_index_end;
-  int r;
-  if constexpr (std::is_same_v<T, float>)
-    r = dlaf_symmetric_generalized_eigensolver_partial_spectrum_s(grid.context(), u, mat_a.ptr(), da, mat_b.ptr(), db, w,
-                                                                  eigenvectors.ptr(), dz, ib, ie);
-  else if constexpr (std::is_same_v<T, double>)
-    r = dlaf_symmetric_generalized_eigensolver_partial_spectrum_d(grid.context(), u, mat_a.ptr(), da, mat_b.ptr(), db, w,
-                                                                  eigenvectors.ptr(), dz, ib, ie);
-  else if constexpr (std::is_same_v<T, std::complex<float>>)
-    r = dlaf_hermitian_generalized_eigensolver_partial_spectrum_c(
-        grid.context(), u, reinterpret_cast<dlaf_complex_c*>(mat_a.ptr()), da, reinterpret_cast<dlaf_complex_c*>(mat_b.ptr()),
-        db, w, reinterpret_cast<dlaf_complex_c*>(eigenvectors.ptr()), dz, ib, ie);
-  else
-    r = dlaf_hermitian_generalized_eigensolver_partial_spectrum_z(
-        grid.context(), u, reinterpret_cast<dlaf_complex_z*>(mat_a.ptr()), da, reinterpret_cast<dlaf_complex_z*>(mat_b.ptr()),
-        db, w, reinterpret_cast<dlaf_complex_z*>(eigenvectors.ptr()), dz, ib, ie);
-  if (r != 0)
-    dlaf::internal::fail("hermitian_generalized_eigensolver");
+  internal::eigen_call("hermitian_generalized_eigensolver", uplo, mat_a.size().rows(), eigenvalues, true,
+                       [&](char u, BaseType<T>* w) {
+                         return DLAF_MI355X_EIGEN_ENTRY(T, generalized_eigensolver_partial_spectrum)(
+                             grid.context(), u, mat_a.ptr(), descriptor_of(mat_a), mat_b.ptr(), descriptor_of(mat_b), w,
+                             eigenvectors.ptr(), descriptor_of(eigenvectors), ib, ie);
+                       });
 }
 
 // the eigenpairs with eigenvalues in (vl, vu] (LAPACK's range = 'V'): the index range is found from two Sturm counts of
@@ -1197,30 +950,13 @@ std::pair<SizeType, SizeType> hermitian_eigensolver(comm::CommunicatorGrid& grid
                                                     Matrix<T, Device::CPU>& eigenvectors,
                                                     EigenvaluesValue<BaseType<T>> eigenvalues_value) {
   static_assert(B == Backend::GPU, "this library has no CPU backend");
-  const char u = uplo == blas::Uplo::Lower ? 'L' : 'U';
-  eigenvalues.assign((size_t) mat.size().rows(), BaseType<T>(0));
-  BaseType<T> dummy{};
-  BaseType<T>* w = eigenvalues.empty() ? &dummy : eigenvalues.data();
-  const DLAF_descriptor da = internal::descriptor_of(mat), dz = internal::descriptor_of(eigenvectors);
-  const BaseType<T> vl = eigenvalues_value.vl, vu = eigenvalues_value.vu;
+  using internal::descriptor_of;
   long ib = 0, ie = 0;
-  int r;
-  if constexpr (std::is_same_v<T, float>)
-    r = dlaf_symmetric_eigensolver_partial_spectrum_by_value_s(grid.context(), u, mat.ptr(), da, w, eigenvectors.ptr(), dz,
-                                                               vl, vu, &ib, &ie);
-  else if constexpr (std::is_same_v<T, double>)
-    r = dlaf_symmetric_eigensolver_partial_spectrum_by_value_d(grid.context(), u, mat.ptr(), da, w, eigenvectors.ptr(), dz,
-                                                               vl, vu, &ib, &ie);
-  else if constexpr (std::is_same_v<T, std::complex<float>>)
-    r = dlaf_hermitian_eigensolver_partial_spectrum_by_value_c(
-        grid.context(), u, reinterpret_cast<dlaf_complex_c*>(mat.ptr()), da, w,
-        reinterpret_cast<dlaf_complex_c*>(eigenvectors.ptr()), dz, vl, vu, &ib, &ie);
-  else
-    r = dlaf_hermitian_eigensolver_partial_spectrum_by_value_z(
-        grid.context(), u, reinterpret_cast<dlaf_complex_z*>(mat.ptr()), da, w,
-        reinterpret_cast<dlaf_complex_z*>(eigenvectors.ptr()), dz, vl, vu, &ib, &ie);
-  if (r != 0)
-    dlaf::internal::fail("hermitian_eigensolver");
+  internal::eigen_call("hermitian_eigensolver", uplo, mat.size().rows(), eigenvalues, true, [&](char u, BaseType<T>* w) {
+    return DLAF_MI355X_EIGEN_ENTRY(T, eigensolver_partial_spectrum_by_value)(
+        grid.context(), u, mat.ptr(), descriptor_of(mat), w, eigenvectors.ptr(), descriptor_of(eigenvectors),
+        eigenvalues_value.vl, eigenvalues_value.vu, &ib, &ie);
+  });
   return {(SizeType) ib, (SizeType) ie};
 }
 template <Backend B, class T>
@@ -1230,31 +966,15 @@ std::pair<SizeType, SizeType> hermitian_generalized_eigensolver(comm::Communicat
                                                                 Matrix<T, Device::CPU>& eigenvectors,
                                                                 EigenvaluesValue<BaseType<T>> eigenvalues_value) {
   static_assert(B == Backend::GPU, "this library has no CPU backend");
-  const char u = uplo == blas::Uplo::Lower ? 'L' : 'U';
-  eigenvalues.assign((size_t) mat_a.size().rows(), BaseType<T>(0));
-  BaseType<T> dummy{};
-  BaseType<T>* w = eigenvalues.empty() ? &dummy : eigenvalues.data();
-  const DLAF_descriptor da = internal::descriptor_of(mat_a), db = internal::descriptor_of(mat_b),
-                        dz = internal::descriptor_of(eigenvectors);
-  const BaseType<T> vl = eigenvalues_value.vl, vu = eigenvalues_value.vu;
+  using internal::descriptor_of;
   long ib = 0, ie = 0;
-  int r;
-  if constexpr (std::is_same_v<T, float>)
-    r = dlaf_symmetric_generalized_eigensolver_partial_spectrum_by_value_s(grid.context(), u, mat_a.ptr(), da, mat_b.ptr(),
-                                                                           db, w, eigenvectors.ptr(), dz, vl, vu, &ib, &ie);
-  else if constexpr (std::is_same_v<T, double>)
-    r = dlaf_symmetric_generalized_eigensolver_partial_spectrum_by_value_d(grid.context(), u, mat_a.ptr(), da, mat_b.ptr(),
-                                                                           db, w, eigenvectors.ptr(), dz, vl, vu, &ib, &ie);
-  else if constexpr (std::is_same_v<T, std::complex<float>>)
-    r = dlaf_hermitian_generalized_eigensolver_partial_spectrum_by_value_c(
-        grid.context(), u, reinterpret_cast<dlaf_complex_c*>(mat_a.ptr()), da, reinterpret_cast<dlaf_complex_c*>(mat_b.ptr()),
-        db, w, reinterpret_cast<dlaf_complex_c*>(eigenvectors.ptr()), dz, vl, vu, &ib, &ie);
-  else
-    r = dlaf_hermitian_generalized_eigensolver_partial_spectrum_by_value_z(
-        grid.context(), u, reinterpret_cast<dlaf_complex_z*>(mat_a.ptr()), da, reinterpret_cast<dlaf_complex_z*>(mat_b.ptr()),
-        db, w, reinterpret_cast<dlaf_complex_z*>(eigenvectors.ptr()), dz, vl, vu, &ib, &ie);
-  if (r != 0)
-    dlaf::internal::fail("hermitian_generalized_eigensolver");
+  internal::eigen_call("hermitian_generalized_eigensolver", uplo, mat_a.size().rows(), eigenvalues, true,
+                       [&](char u, BaseType<T>* w) {
+                         return DLAF_MI355X_EIGEN_ENTRY(T, generalized_eigensolver_partial_spectrum_by_value)(
+                             grid.context(), u, mat_a.ptr(), descriptor_of(mat_a), mat_b.ptr(), descriptor_of(mat_b), w,
+                             eigenvectors.ptr(), descriptor_of(eigenvectors), eigenvalues_value.vl, eigenvalues_value.vu,
+                             &ib, &ie);
+                       });
   return {(SizeType) ib, (SizeType) ie};
 }
 
@@ -1267,52 +987,24 @@ void hermitian_eigenvalues(comm::CommunicatorGrid& grid, blas::Uplo uplo, const 
                            std::vector<BaseType<T>>& eigenvalues, SizeType eigenvalues_index_begin = 0,
                            SizeType eigenvalues_index_end = -1) {
   static_assert(B == Backend::GPU, "this library has no CPU backend");
-  const char u = uplo == blas::Uplo::Lower ? 'L' : 'U';
   const SizeType n = mat.size().rows();
-  if ((SizeType) eigenvalues.size() != n)
-    eigenvalues.assign((size_t) n, BaseType<T>(0));
-  BaseType<T> dummy{};
-  BaseType<T>* w = eigenvalues.empty() ? &dummy : eigenvalues.data();
-  const DLAF_descriptor da = internal::descriptor_of(mat);
   const int64_t ib = eigenvalues_index_begin, ie = eigenvalues_index_end < 0 ? n : eigenvalues_index_end;
-  int r;
-  if constexpr (std::is_same_v<T, float>)
-    r = dlaf_symmetric_eigenvalues_s(grid.context(), u, mat.ptr(), da, w, ib, ie);
-  else if constexpr (std::is_same_v<T, double>)
-    r = dlaf_symmetric_eigenvalues_d(grid.context(), u, mat.ptr(), da, w, ib, ie);
-  else if constexpr (std::is_same_v<T, std::complex<float>>)
-    r = dlaf_hermitian_eigenvalues_c(grid.context(), u, reinterpret_cast<const dlaf_complex_c*>(mat.ptr()), da, w, ib, ie);
-  else
-    r = dlaf_hermitian_eigenvalues_z(grid.context(), u, reinterpret_cast<const dlaf_complex_z*>(mat.ptr()), da, w, ib, ie);
-  if (r != 0)
-    dlaf::internal::fail("hermitian_eigenvalues");
+  internal::eigen_call("hermitian_eigenvalues", uplo, n, eigenvalues, false, [&](char u, BaseType<T>* w) {
+    return DLAF_MI355X_EIGEN_ENTRY(T, eigenvalues)(grid.context(), u, mat.ptr(), internal::descriptor_of(mat), w, ib, ie);
+  });
 }
 template <Backend B, class T>
 void hermitian_generalized_eigenvalues(comm::CommunicatorGrid& grid, blas::Uplo uplo, const Matrix<T, Device::CPU>& mat_a,
                                        Matrix<T, Device::CPU>& mat_b, std::vector<BaseType<T>>& eigenvalues,
                                        SizeType eigenvalues_index_begin = 0, SizeType eigenvalues_index_end = -1) {
   static_assert(B == Backend::GPU, "this library has no CPU backend");
-  const char u = uplo == blas::Uplo::Lower ? 'L' : 'U';
+  using internal::descriptor_of;
   const SizeType n = mat_a.size().rows();
-  if ((SizeType) eigenvalues.size() != n)
-    eigenvalues.assign((size_t) n, BaseType<T>(0));
-  BaseType<T> dummy{};
-  BaseType<T>* w = eigenvalues.empty() ? &dummy : eigenvalues.data();
-  const DLAF_descriptor da = internal::descriptor_of(mat_a), db = internal::descriptor_of(mat_b);
   const int64_t ib = eigenvalues_index_begin, ie = eigenvalues_index_end < 0 ? n : eigenvalues_index_end;
-  int r;
-  if constexpr (std::is_same_v<T, float>)
-    r = dlaf_symmetric_generalized_eigenvalues_s(grid.context(), u, mat_a.ptr(), da, mat_b.ptr(), db, w, ib, ie);
-  else if constexpr (std::is_same_v<T, double>)
-    r = dlaf_symmetric_generalized_eigenvalues_d(grid.context(), u, mat_a.ptr(), da, mat_b.ptr(), db, w, ib, ie);
-  else if constexpr (std::is_same_v<T, std::complex<float>>)
-    r = dlaf_hermitian_generalized_eigenvalues_c(grid.context(), u, reinterpret_cast<const dlaf_complex_c*>(mat_a.ptr()), da,
-                                                 reinterpret_cast<dlaf_complex_c*>(mat_b.ptr()), db, w, ib, ie);
-  else
-    r = dlaf_hermitian_generalized_eigenvalues_z(grid.context(), u, reinterpret_cast<const dlaf_complex_z*>(mat_a.ptr()), da,
-                                                 reinterpret_cast<dlaf_complex_z*>(mat_b.ptr()), db, w, ib, ie);
-  if (r != 0)
-    dlaf::internal::fail("hermitian_generalized_eigenvalues");
+  internal::eigen_call("hermitian_generalized_eigenvalues", uplo, n, eigenvalues, false, [&](char u, BaseType<T>* w) {
+    return DLAF_MI355X_EIGEN_ENTRY(T, generalized_eigenvalues)(grid.context(), u, mat_a.ptr(), descriptor_of(mat_a),
+                                                               mat_b.ptr(), descriptor_of(mat_b), w, ib, ie);
+  });
 }
 
 // include/dlaf/init.h: the library needs no runtime arguments; initialize / finalize are idempotent
@@ -1320,3 +1012,6 @@ inline void initialize(int argc = 0, const char** argv = nullptr) { dlaf_initial
 inline void finalize() { dlaf_finalize(); }
 
 }  // namespace dlaf
+
+#undef DLAF_MI355X_ENTRY
+#undef DLAF_MI355X_EIGEN_ENTRY

@@ -6,10 +6,6 @@
 // download) -- upstream times the call on device-resident mirrors; the device time of the five stages alone is printed
 // beside it (dlaf_mi355x_eigensolver_profile).  Input as upstream: a random Hermitian matrix (set_random_hermitian, :136-144).
 //   g++ -std=c++17 -O2 -I include miniapp/miniapp_eigensolver.cpp -L dla_future_amd/lib -ldlaf_mi355x -o miniapp_eigensolver
-#ifdef DLAF_MI355X_WITH_MPI
-#include <mpi.h>
-#endif
-
 #include <chrono>
 #include <cstdint>
 #include <cstdlib>
@@ -21,15 +17,12 @@
 #include <limits>
 #include <string>
 
-#include <dlaf_mi355x/dlaf.hpp>
+#include "miniapp_common.hpp"
 
 using namespace dlaf;
 
-struct Options {
+struct Options : miniapp::CommonOptions {
   SizeType m = 4096, mb = 256;
-  int grid_rows = 1, grid_cols = 1;
-  int64_t nruns = 1, nwarmups = 1;
-  char type = 'd';
   SizeType b = -1;  // --band-size (default: the block size, miniapp_reduction_to_band.cpp:62-63)
   std::string check = "none";
   bool csv = false;
@@ -38,36 +31,11 @@ struct Options {
 
 static Options parse(int argc, char** argv) {
   Options o;
-  for (int i = 1; i < argc; ++i) {
-    std::string a = argv[i], v;
-    const auto eq = a.find('=');
-    if (eq != std::string::npos) {
-      v = a.substr(eq + 1);
-      a = a.substr(0, eq);
-    }
-    auto val = [&]() -> std::string {
-      if (!v.empty())
-        return v;
-      if (i + 1 >= argc) {
-        std::cerr << "missing value for " << a << std::endl;
-        std::exit(2);
-      }
-      return argv[++i];
-    };
+  auto own = [&o](const std::string& a, auto& val) {
     if (a == "--matrix-size")
       o.m = std::stoll(val());
     else if (a == "--block-size")
       o.mb = std::stoll(val());
-    else if (a == "--grid-rows")
-      o.grid_rows = std::stoi(val());
-    else if (a == "--grid-cols")
-      o.grid_cols = std::stoi(val());
-    else if (a == "--nruns")
-      o.nruns = std::stoll(val());
-    else if (a == "--nwarmups")
-      o.nwarmups = std::stoll(val());
-    else if (a == "--type")
-      o.type = (char) std::tolower(val()[0]);
     else if (a == "--band-size")
       o.b = std::stoll(val());
     else if (a == "--check-result")
@@ -76,22 +44,17 @@ static Options parse(int argc, char** argv) {
       o.csv = true;
     else if (a == "--pp-info")
       o.info = val();
-    else if (a == "--local" || a == "--backend" || a.rfind("--pika:", 0) == 0 || a.rfind("--dlaf:", 0) == 0) {
-      if (a == "--backend")
-        (void) val();  // there is one backend
-    }
-    else {
-      std::cerr << "unknown option " << a << "\nusage: miniapp_eigensolver --matrix-size N --block-size NB [--band-size B] [--grid-rows R "
-                   "--grid-cols C] [--nruns K] [--nwarmups W] [--type s|d|c|z] [--uplo L|U] "
-                   "[--check-result none|last|all] [--csv]" << std::endl;
-      std::exit(2);
-    }
-  }
-  if (o.m < 0 || o.mb < 1 || o.nruns < 1 || o.nwarmups < 0 || std::strchr("sdcz", o.type) == nullptr ||
-      (o.check != "none" && o.check != "last" && o.check != "all")) {
-    std::cerr << "invalid option value" << std::endl;
-    std::exit(2);
-  }
+    else
+      return false;
+    return true;
+  };
+  miniapp::parse_options(argc, argv, o,
+                         "miniapp_eigensolver --matrix-size N --block-size NB [--band-size B] [--grid-rows R "
+                         "--grid-cols C] [--nruns K] [--nwarmups W] [--type s|d|c|z] [--uplo L|U] "
+                         "[--check-result none|last|all] [--csv]",
+                         own);
+  if (o.m < 0 || o.mb < 1 || o.nwarmups < 0 || !o.valid() || (o.check != "none" && o.check != "last" && o.check != "all"))
+    miniapp::invalid_option_value();
   return o;
 }
 
@@ -182,44 +145,7 @@ static void run(const Options& opts, comm::CommunicatorGrid& comm_grid, int worl
 
 int main(int argc, char** argv) {
   const Options opts = parse(argc, argv);
-  int world_rank = 0, world_size = 1;
-#ifdef DLAF_MI355X_WITH_MPI
-  int provided = 0;
-  MPI_Init_thread(&argc, &argv, MPI_THREAD_MULTIPLE, &provided);
-  MPI_Comm_rank(MPI_COMM_WORLD, &world_rank);
-  MPI_Comm_size(MPI_COMM_WORLD, &world_size);
-  if (std::getenv("LOCAL_RANK") == nullptr) {
-    MPI_Comm node;
-    MPI_Comm_split_type(MPI_COMM_WORLD, MPI_COMM_TYPE_SHARED, world_rank, MPI_INFO_NULL, &node);
-    int local = 0;
-    MPI_Comm_rank(node, &local);
-    setenv("LOCAL_RANK", std::to_string(local).c_str(), 0);  // the library picks its GPU from it
-    MPI_Comm_free(&node);
-  }
-#endif
-  if (opts.grid_rows * opts.grid_cols != world_size) {
-    if (world_rank == 0)
-      std::cerr << "grid " << opts.grid_rows << " x " << opts.grid_cols << " needs " << opts.grid_rows * opts.grid_cols
-                << " processes, got " << world_size << std::endl;
-    return 2;
-  }
-  dlaf::initialize();
-  {
-#ifdef DLAF_MI355X_WITH_MPI
-    comm::CommunicatorGrid comm_grid(MPI_COMM_WORLD, opts.grid_rows, opts.grid_cols, common::Ordering::ColumnMajor);
-#else
-    comm::CommunicatorGrid comm_grid = comm::CommunicatorGrid::single();
-#endif
-    switch (opts.type) {
-      case 's': run<float>(opts, comm_grid, world_rank); break;
-      case 'd': run<double>(opts, comm_grid, world_rank); break;
-      case 'c': run<std::complex<float>>(opts, comm_grid, world_rank); break;
-      default: run<std::complex<double>>(opts, comm_grid, world_rank); break;
-    }
-  }
-  dlaf::finalize();
-#ifdef DLAF_MI355X_WITH_MPI
-  MPI_Finalize();
-#endif
-  return 0;
+  return miniapp::run_main(argc, argv, opts, true, [&opts](auto t, comm::CommunicatorGrid& comm_grid, int world_rank, int) {
+    run<decltype(t)>(opts, comm_grid, world_rank);
+  });
 }

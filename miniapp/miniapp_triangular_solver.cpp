@@ -7,10 +7,6 @@
 // sweep (dlaf_mi355x_solver_profile) -- the operands of this entry start on the host, the wall time with PCIe
 // staging is printed next to it.
 //   g++ -std=c++17 -O2 -I include miniapp/miniapp_triangular_solver.cpp -L dla_future_amd/lib -ldlaf_mi355x -o miniapp_triangular_solver
-#ifdef DLAF_MI355X_WITH_MPI
-#include <mpi.h>
-#endif
-
 #include <chrono>
 #include <cmath>
 #include <cstdint>
@@ -19,15 +15,12 @@
 #include <iostream>
 #include <string>
 
-#include <dlaf_mi355x/dlaf.hpp>
+#include "miniapp_common.hpp"
 
 using namespace dlaf;
 
-struct Options {
+struct Options : miniapp::CommonOptions {
   SizeType m = 4096, n = 512, mb = 256, nb = 256;
-  int grid_rows = 1, grid_cols = 1;
-  int64_t nruns = 1, nwarmups = 1;
-  char type = 'd';
   blas::Side side = blas::Side::Left;
   blas::Uplo uplo = blas::Uplo::Lower;
   blas::Op op = blas::Op::NoTrans;
@@ -35,50 +28,26 @@ struct Options {
 };
 
 static Options parse(int argc, char** argv) {
+  using miniapp::upper_initial;
   Options o;
-  for (int i = 1; i < argc; ++i) {
-    std::string a = argv[i], v;
-    const auto eq = a.find('=');
-    if (eq != std::string::npos) {
-      v = a.substr(eq + 1);
-      a = a.substr(0, eq);
-    }
-    auto val = [&]() -> std::string {
-      if (!v.empty())
-        return v;
-      if (i + 1 >= argc) {
-        std::cerr << "missing value for " << a << std::endl;
-        std::exit(2);
-      }
-      return argv[++i];
-    };
+  miniapp::parse_options(argc, argv, o, nullptr, [&o](const std::string& a, auto& val) {
     if (a == "--m") o.m = std::stoll(val());
     else if (a == "--n") o.n = std::stoll(val());
     else if (a == "--mb") o.mb = std::stoll(val());
     else if (a == "--nb") o.nb = std::stoll(val());
-    else if (a == "--grid-rows") o.grid_rows = std::stoi(val());
-    else if (a == "--grid-cols") o.grid_cols = std::stoi(val());
-    else if (a == "--nruns") o.nruns = std::stoll(val());
-    else if (a == "--nwarmups") o.nwarmups = std::stoll(val());
-    else if (a == "--type") o.type = (char) std::tolower(val()[0]);
-    else if (a == "--side") o.side = std::toupper(val()[0]) == 'R' ? blas::Side::Right : blas::Side::Left;
-    else if (a == "--uplo") o.uplo = std::toupper(val()[0]) == 'U' ? blas::Uplo::Upper : blas::Uplo::Lower;
+    else if (a == "--side") o.side = upper_initial(val()) == 'R' ? blas::Side::Right : blas::Side::Left;
+    else if (a == "--uplo") o.uplo = upper_initial(val()) == 'U' ? blas::Uplo::Upper : blas::Uplo::Lower;
     else if (a == "--op") {
-      const char c = (char) std::toupper(val()[0]);
+      const char c = upper_initial(val());
       o.op = c == 'T' ? blas::Op::Trans : c == 'C' ? blas::Op::ConjTrans : blas::Op::NoTrans;
     }
-    else if (a == "--diag") o.diag = std::toupper(val()[0]) == 'U' ? blas::Diag::Unit : blas::Diag::NonUnit;
-    else if (a == "--check-result" || a == "--backend") (void) val();
-    else if (a == "--csv" || a == "--local" || a.rfind("--pika:", 0) == 0 || a.rfind("--dlaf:", 0) == 0) {}
-    else {
-      std::cerr << "unknown option " << a << std::endl;
-      std::exit(2);
-    }
-  }
-  if (o.m <= 0 || o.n <= 0 || o.mb <= 0 || o.nb <= 0 || o.nruns < 1 || std::strchr("sdcz", o.type) == nullptr) {
-    std::cerr << "invalid option value" << std::endl;
-    std::exit(2);
-  }
+    else if (a == "--diag") o.diag = upper_initial(val()) == 'U' ? blas::Diag::Unit : blas::Diag::NonUnit;
+    else if (a == "--check-result") (void) val();
+    else if (a != "--csv") return false;
+    return true;
+  });
+  if (o.m <= 0 || o.n <= 0 || o.mb <= 0 || o.nb <= 0 || !o.valid())
+    miniapp::invalid_option_value();
   if (o.mb != o.nb) {
     std::cerr << "this build needs square blocks: --mb == --nb" << std::endl;
     std::exit(2);
@@ -86,28 +55,11 @@ static Options parse(int argc, char** argv) {
   return o;
 }
 
-// counter-based generator: uniform in [-1, 1) from a hash of the global element index (every grid sees the
-// same global matrices; cheap enough for benchmark sizes)
-static inline double uniform_pm1(uint64_t x) {
-  x += 0x9E3779B97F4A7C15ull;  // splitmix64
-  x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ull;
-  x = (x ^ (x >> 27)) * 0x94D049BB133111EBull;
-  x ^= x >> 31;
-  return (double) (x >> 11) * (2.0 / 9007199254740992.0) - 1.0;
-}
-template <class T>
-struct Rand {
-  static T make(uint64_t key) { return (T) uniform_pm1(key); }
-};
-template <class R>
-struct Rand<std::complex<R>> {
-  static std::complex<R> make(uint64_t key) { return {(R) uniform_pm1(2 * key), (R) uniform_pm1(2 * key + 1)}; }
-};
+using miniapp::Rand;
 
 template <class T>
 static void run(const Options& opts, comm::CommunicatorGrid& grid, int world_rank) {
   using Base = decltype(std::abs(T{}));
-  constexpr bool complex = !std::is_same<T, Base>::value;
   const SizeType k = opts.side == blas::Side::Left ? opts.m : opts.n;
   matrix::Distribution da(GlobalElementSize(k, k), TileElementSize(opts.mb, opts.mb), grid.size(), grid.rank(), comm::Index2D(0, 0));
   matrix::Distribution db(GlobalElementSize(opts.m, opts.n), TileElementSize(opts.mb, opts.nb), grid.size(), grid.rank(), comm::Index2D(0, 0));
@@ -138,7 +90,7 @@ static void run(const Options& opts, comm::CommunicatorGrid& grid, int world_ran
     dlaf_mi355x_solver_profile(&ms, &fl);
     const double elapsed_time = ms * 1e-3;
     const double add_mul = (double) opts.n * (double) opts.m * (double) k / 2;
-    const double gigaflops = (complex ? 2 * add_mul + 6 * add_mul : 2 * add_mul) / elapsed_time / 1e9;
+    const double gigaflops = miniapp::total_ops<T>(add_mul) / elapsed_time / 1e9;
     if (0 == world_rank && run_index >= 0)
       std::cout << "[" << run_index << "] " << elapsed_time << "s " << gigaflops << "GFlop/s " << opts.type
                 << (char) opts.side << (char) opts.uplo << (char) opts.op << (char) opts.diag << " (" << opts.m << ", "
@@ -165,36 +117,7 @@ static void run(const Options& opts, comm::CommunicatorGrid& grid, int world_ran
 
 int main(int argc, char** argv) {
   const Options opts = parse(argc, argv);
-  int world_rank = 0, world_size = 1;
-#ifdef DLAF_MI355X_WITH_MPI
-  int provided = 0;
-  MPI_Init_thread(&argc, &argv, MPI_THREAD_MULTIPLE, &provided);
-  MPI_Comm_rank(MPI_COMM_WORLD, &world_rank);
-  MPI_Comm_size(MPI_COMM_WORLD, &world_size);
-#endif
-  if (opts.grid_rows * opts.grid_cols != world_size) {
-    if (world_rank == 0)
-      std::cerr << "grid " << opts.grid_rows << " x " << opts.grid_cols << " needs " << opts.grid_rows * opts.grid_cols
-                << " processes, got " << world_size << std::endl;
-    return 2;
-  }
-  dlaf::initialize();
-  {
-#ifdef DLAF_MI355X_WITH_MPI
-    comm::CommunicatorGrid grid(MPI_COMM_WORLD, opts.grid_rows, opts.grid_cols, common::Ordering::ColumnMajor);
-#else
-    comm::CommunicatorGrid grid = comm::CommunicatorGrid::single();
-#endif
-    switch (opts.type) {
-      case 's': run<float>(opts, grid, world_rank); break;
-      case 'd': run<double>(opts, grid, world_rank); break;
-      case 'c': run<std::complex<float>>(opts, grid, world_rank); break;
-      default: run<std::complex<double>>(opts, grid, world_rank); break;
-    }
-  }
-  dlaf::finalize();
-#ifdef DLAF_MI355X_WITH_MPI
-  MPI_Finalize();
-#endif
-  return 0;
+  return miniapp::run_main(argc, argv, opts, false, [&opts](auto t, comm::CommunicatorGrid& grid, int world_rank, int) {
+    run<decltype(t)>(opts, grid, world_rank);
+  });
 }

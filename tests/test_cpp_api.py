@@ -8,45 +8,51 @@ import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 LIB = os.path.join(ROOT, "dla_future_amd", "lib")
-SRC = os.path.join(ROOT, "tests", "cpp_api", "test_cholesky_cpp.cpp")
-EXE = os.path.join(ROOT, "tests", "cpp_api", "test_cholesky_cpp")
+HEADERS = [os.path.join(ROOT, "include", "dlaf_mi355x", h) for h in ("dlaf.hpp", "dlaf_mi355x.h")]
+MINIAPPS = ["miniapp_cholesky", "miniapp_triangular_solver", "miniapp_triangular_multiplication",
+            "miniapp_hermitian_multiplication", "miniapp_gen_to_std", "miniapp_inverse_from_cholesky_factor",
+            "miniapp_reduction_to_band", "miniapp_eigensolver"]
 
 
-def build():
-    newest = max(os.path.getmtime(SRC), os.path.getmtime(os.path.join(ROOT, "include", "dlaf_mi355x", "dlaf.hpp")))
-    if not os.path.exists(EXE) or os.path.getmtime(EXE) < newest:
-        subprocess.run(["g++", "-std=c++17", "-O1", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"), SRC, "-L", LIB,
-                        "-ldlaf_mi355x", f"-Wl,-rpath,{LIB}", "-Wl,-rpath,/opt/rocm/lib", "-o", EXE], check=True)
-    return EXE
+def _stale(exe, sources):
+    return not os.path.exists(exe) or os.path.getmtime(exe) < max(os.path.getmtime(s) for s in sources)
+
+
+def build_cpp_test(name):
+    """tests/cpp_api/<name>.cpp -> tests/cpp_api/<name>, rebuilt when the source or a facade header is newer."""
+    src = os.path.join(ROOT, "tests", "cpp_api", name + ".cpp")
+    exe = os.path.join(ROOT, "tests", "cpp_api", name)
+    if _stale(exe, [src] + HEADERS):
+        subprocess.run(["g++", "-std=c++17", "-O1", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"), src, "-L", LIB,
+                        "-ldlaf_mi355x", f"-Wl,-rpath,{LIB}", "-Wl,-rpath,/opt/rocm/lib", "-o", exe], check=True)
+    return exe
 
 
 def test_cpp_facade_compiles_and_links():
-    assert os.path.exists(build())
+    assert os.path.exists(build_cpp_test("test_cholesky_cpp"))
+
+
+def test_every_facade_template_instantiates_and_links_for_every_type():
+    """instantiate_all.cpp instantiates every public template of the facade for s, d, c and z: a signature that moved
+    fails the compilation, a missing or misspelt C entry of any type fails the link."""
+    assert os.path.exists(build_cpp_test("instantiate_all"))
 
 
 @pytest.mark.gpu
 def test_reference_style_cpp_tests_on_the_facade():
-    r = subprocess.run([build()], cwd=ROOT, capture_output=True, text=True, timeout=600,
+    r = subprocess.run([build_cpp_test("test_cholesky_cpp")], cwd=ROOT, capture_output=True, text=True, timeout=600,
                        env=dict(os.environ, DLAF_MI355X_DEVICE="0"))
     assert r.returncode == 0 and "CPP_API_TEST OK" in r.stdout, (r.stdout[-1500:], r.stderr[-3000:])
 
 
-MINI_SRC = os.path.join(ROOT, "miniapp", "miniapp_cholesky.cpp")
-MINI_EXE = os.path.join(ROOT, "miniapp", "miniapp_cholesky")
-MINI_MPI = os.path.join(ROOT, "miniapp", "miniapp_cholesky_mpi")
-
-
 def build_miniapp(mpi=False, name="miniapp_cholesky"):
+    """miniapp/<name>.cpp -> miniapp/<name>[_mpi], rebuilt when the source, the shared miniapp header or a facade header
+    is newer."""
     src = os.path.join(ROOT, "miniapp", name + ".cpp")
     exe = os.path.join(ROOT, "miniapp", name + ("_mpi" if mpi else ""))
-    return _build_miniapp(src, exe, mpi)
-
-
-def _build_miniapp(MINI_SRC, exe, mpi):
-    newest = max(os.path.getmtime(MINI_SRC), os.path.getmtime(os.path.join(ROOT, "include", "dlaf_mi355x", "dlaf.hpp")))
-    if os.path.exists(exe) and os.path.getmtime(exe) >= newest:
+    if not _stale(exe, [src, os.path.join(ROOT, "miniapp", "miniapp_common.hpp")] + HEADERS):
         return exe
-    cmd = ["g++", "-std=c++17", "-O2", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"), MINI_SRC, "-L", LIB]
+    cmd = ["g++", "-std=c++17", "-O2", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"), src, "-L", LIB]
     if mpi:
         import test_c_api
         test_c_api.build("test_grid_mpi")   # makes sure the MPI shim and its private link directory exist
@@ -59,11 +65,42 @@ def _build_miniapp(MINI_SRC, exe, mpi):
 
 
 def test_miniapp_compiles():
-    assert os.path.exists(build_miniapp())
-    assert os.path.exists(build_miniapp(name="miniapp_triangular_solver"))
-    assert os.path.exists(build_miniapp(name="miniapp_gen_to_std"))
-    assert os.path.exists(build_miniapp(name="miniapp_reduction_to_band"))
-    assert os.path.exists(build_miniapp(name="miniapp_eigensolver"))
+    for name in MINIAPPS:
+        assert os.path.exists(build_miniapp(name=name))
+
+
+# Only the five miniapps that mirror an upstream program print a usage line after an unknown option.
+MINIAPP_USAGE = {
+    "miniapp_cholesky": "usage: miniapp_cholesky --matrix-size N --block-size NB [--grid-rows R --grid-cols C]",
+    "miniapp_gen_to_std": "usage: miniapp_gen_to_std --matrix-size N --block-size NB [--grid-rows R --grid-cols C]",
+    "miniapp_inverse_from_cholesky_factor":
+        "usage: miniapp_inverse_from_cholesky_factor --matrix-size N --block-size NB [--grid-rows R --grid-cols C]",
+    "miniapp_reduction_to_band": "usage: miniapp_reduction_to_band --matrix-size N --block-size NB [--band-size B]",
+    "miniapp_eigensolver": "usage: miniapp_eigensolver --matrix-size N --block-size NB [--band-size B]",
+}
+
+
+@pytest.mark.parametrize("name", MINIAPPS)
+def test_miniapp_argument_errors(name):
+    """The exits of the option parser and of the process-count check: status 2, nothing on stdout, one message on stderr.
+    They all happen before dlaf::initialize(), so no GPU is touched."""
+    exe = build_miniapp(name=name)
+
+    def stderr_of(*args):
+        r = subprocess.run([exe, *args], cwd=ROOT, capture_output=True, text=True, timeout=60)
+        assert r.returncode == 2 and r.stdout == "", (args, r.returncode, r.stdout, r.stderr)
+        return r.stderr
+
+    unknown = stderr_of("--bogus").splitlines()
+    assert unknown[0] == "unknown option --bogus", unknown
+    if name in MINIAPP_USAGE:
+        assert len(unknown) == 2 and unknown[1].startswith(MINIAPP_USAGE[name]) and unknown[1].endswith("[--csv]"), unknown
+    else:
+        assert len(unknown) == 1, unknown
+    assert stderr_of("--nruns") == "missing value for --nruns\n"
+    assert stderr_of("--nruns", "2", "--type") == "missing value for --type\n"
+    assert stderr_of("--type", "q") == "invalid option value\n"
+    assert stderr_of("--grid-rows", "2") == "grid 2 x 1 needs 2 processes, got 1\n"
 
 
 def check_miniapp_output(out, nruns, nchecks):

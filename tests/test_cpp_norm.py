@@ -7,27 +7,17 @@ import subprocess
 
 import pytest
 
+from test_cpp_api import build_cpp_test
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-LIB = os.path.join(ROOT, "dla_future_amd", "lib")
-SRC = os.path.join(ROOT, "tests", "cpp_api", "test_norm_cpp.cpp")
-EXE = os.path.join(ROOT, "tests", "cpp_api", "test_norm_cpp")
-
-
-def build():
-    newest = max(os.path.getmtime(SRC), os.path.getmtime(os.path.join(ROOT, "include", "dlaf_mi355x", "dlaf.hpp")),
-                 os.path.getmtime(os.path.join(ROOT, "include", "dlaf_mi355x", "dlaf_mi355x.h")))
-    if not os.path.exists(EXE) or os.path.getmtime(EXE) < newest:
-        subprocess.run(["g++", "-std=c++17", "-O1", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"), SRC, "-L", LIB,
-                        "-ldlaf_mi355x", f"-Wl,-rpath,{LIB}", "-Wl,-rpath,/opt/rocm/lib", "-o", EXE], check=True)
-    return EXE
 
 
 def test_cpp_norm_compiles_and_links():
-    assert os.path.exists(build())
+    assert os.path.exists(build_cpp_test("test_norm_cpp"))
 
 
 @pytest.mark.gpu
 def test_cpp_norm_overloads_agree_with_the_c_entries():
-    r = subprocess.run([build()], cwd=ROOT, capture_output=True, text=True, timeout=300,
+    r = subprocess.run([build_cpp_test("test_norm_cpp")], cwd=ROOT, capture_output=True, text=True, timeout=300,
                        env=dict(os.environ, DLAF_MI355X_DEVICE="0"))
     assert r.returncode == 0 and "CPP_NORM_TEST OK" in r.stdout, (r.stdout[-1500:], r.stderr[-3000:])
